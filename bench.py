@@ -21,11 +21,21 @@ uint8 masks copied to the host (the reference's timed region
 HBM when the clock starts.  value = frames all ranks produced / max-over-ranks wall time.
 Everything is fp32 (the reference's precision); data and weights are synthetic (seeded).
 
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, `--dump-outputs DIR` when given, the JSON
+line.  `--full` adds everything else, measured after the timed region: the steady-state block of a short run, the host enqueue
+time and the card's clock per rank, parity against the reference masks, the roofline of the dominant kernel, the CPU baseline
+(`--no-cpu-baseline` skips it) and the `variants` (`--no-extras` skips them and the clock-and-power pass).
+
 `variants` (never the headline): the reference-exact 1072x1920 post-processing, the key-frame cache (one new key frame per
 window), two windows in flight, the other BASELINE configs on one GPU (configs[0] per-frame PSPNet, configs[2] DeepLabv3-R101
 + logit warp, configs[3] ViT-S/16 + feature flow) and the reference's default real-video route (8 crops of a 1072x1920 frame).
+
+`--dump-outputs DIR`: what the last timed step returned to its caller, from rank 0, as float32 arrays: DIR/pred.npy (the logits,
+[5,5,713,713]) and DIR/mask.npy (the argmax masks, [5,713,713]), 61 MB in all.  Inputs and weights come from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
+import contextlib
 import glob
 import hashlib
 import json
@@ -274,6 +284,25 @@ def timed(fn, steps, warmup, dev, per_step=None, marks=None):
     return time.perf_counter() - t0
 
 
+def effective_tflops(fps, world):
+    """Direct-convolution-equivalent rate per GPU (727.44 GFLOP per key frame); the heavy 3x3 convs run as Winograd
+    F(6x6,3x3) and the head skips the pyramid channels, which together execute ~2.3x fewer FLOPs, so this "effective" figure may
+    exceed the fp32 MFMA peak -- it is NOT a roofline fraction."""
+    return round(2 * KEYFRAME_GFLOP * 1e-3 * (fps / world) / N_DELTA, 2)
+
+
+def dump_outputs(d, out, rank):
+    """--dump-outputs: rank 0 writes what the last timed step returned to its caller as float32 .npy files (logits 51 MB, masks
+    10 MB)."""
+    import numpy as np
+
+    if rank != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    for name in ("pred", "mask"):
+        np.save(os.path.join(d, name + ".npy"), out[name].float().cpu().numpy())
+
+
 def median(xs):
     xs = sorted(xs)
     n = len(xs)
@@ -330,7 +359,7 @@ IPC_FAILURE = re.compile(r"hipIpc|IpcGetMemHandle|IpcOpenMemHandle|ncclUnhandled
 SIGNAL_EXIT = re.compile(r"Signal \d+ \(SIG|exitcode\s*:\s*-\d+|core dumped|Memory access fault|HSA_STATUS_ERROR|Aborted", re.I)
 
 
-def spawn_ranks(n):
+def spawn_ranks(n, argv=None):
     """`bench.py --gpus N` launched directly (no WORLD_SIZE): start the N ranks as FRESH child processes under
     torch.distributed.run and hand back their return code.  Nothing in this process has touched a GPU, and it does not
     replace itself (no exec): the children are ordinary subprocesses; rank 0's JSON line is relayed on stdout, the ranks' stderr
@@ -361,7 +390,7 @@ def spawn_ranks(n):
             env["FS_BENCH_PREV_ATTEMPT_RC"] = str(prev_rc)
         env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or n) // n)))
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+               "--master-port", str(port), os.path.abspath(__file__)] + (sys.argv[1:] if argv is None else argv)
         proc = subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         err_tail = []
 
@@ -422,8 +451,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary variants")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: steady-state block, host enqueue time, clocks, parity, "
+                         "roofline, CPU baseline, variants (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0) to DIR/pred.npy and DIR/mask.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary variants and the clock-and-power pass")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank rehearsal on a 1-GPU box: every rank uses cuda:0 and the reduction runs over gloo")
     ap.add_argument("--lib", default=None,
@@ -437,8 +471,15 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(spawn_ranks(args.gpus))  # launcher only: no torch, no GPU in this process
+        # launcher only: no torch, no GPU in this process.  The ranks run in ROOT: they get the dump directory as an absolute path
+        # (argparse keeps the last occurrence of an option)
+        extra = ["--dump-outputs", args.dump_outputs] if args.dump_outputs else []
+        sys.exit(spawn_ranks(args.gpus, sys.argv[1:] + extra))
     if args.launch_check:
         return launch_check(args)
     for o in args.hip_opt:
@@ -488,11 +529,15 @@ def main():
     host_post = torch.empty((N_DELTA, 1072, 1920), dtype=torch.uint8).pin_memory()
     net.reserve(2, SIZE, SIZE)  # the library's workspace for this geometry, once, before the clock starts (fs_reserve)
 
+    last = {} if args.dump_outputs else None  # --dump-outputs: what the last timed step returned
+
     def step_native(i):
         prev, nxt = windows[i % nwin]
         out = fm.predict(prev, nxt, dl, dr, N_DELTA, None, with_mask=True)  # logits [5,K,713,713] AND their argmax, from one fused tail
         host_masks.copy_(out["mask"], non_blocking=True)
         torch.cuda.current_stream().synchronize()  # masks are on the host when the step ends
+        if last is not None and i == args.steps - 1:
+            last.update(out)
 
     def enqueue_native(i):
         """step_native without the wait: what the HOST does per window (Python, ctypes, launches, the async copy)."""
@@ -500,9 +545,13 @@ def main():
         host_masks.copy_(fm.predict(prev, nxt, dl, dr, N_DELTA, None, with_mask=True)["mask"], non_blocking=True)
 
     step_s, marks = [], {}
-    cs_timed = ClockSampler(torch, 0.01)  # this rank's card while the timed region runs (one sysfs read per 10 ms)
-    with cs_timed:
+    # --full: this rank's card while the timed region runs (one sysfs read per 10 ms)
+    cs_timed = ClockSampler(torch, 0.01) if args.full else None
+    with cs_timed or contextlib.nullcontext():
         elapsed = timed(step_native, args.steps, args.warmup, dev, step_s, marks)
+    if last is not None:
+        dump_outputs(args.dump_outputs, last, rank)
+        last = None  # the --full passes below loop step_native again: they must not replace the timed step's outputs
     _, frames_total, elapsed_max = shard.reduce_run(torch.zeros(3, CLASSES, dtype=torch.int64), args.steps * N_DELTA, elapsed, rdev)
     fps = frames_total / elapsed_max
     # process start (the launcher's, when bench.py spawned the ranks itself) -> first timed step, per rank: imports, weights, data,
@@ -511,17 +560,19 @@ def main():
     # every rank's own figures (mean and median step, start-up), so that a straggler is visible in the N > 1 line
     # a short timed region says little about the clock the card settles at: the same step for >= 0.8 s right behind it (every rank
     # runs it, so the ranks stay symmetric; rank 0 reports its own)
-    steady = steady_state_block(step_native, torch) if elapsed < STEADY_MIN_TIMED_S else None
-    # host time to ENQUEUE one window (no wait; a short burst, so the launch queue never pushes back): with one process per GPU on a
-    # many-GPU node this is what the ranks' share of the host cores has to sustain -- a rank is host-bound once it reaches ms_per_step
-    torch.cuda.synchronize()
-    t_enq = time.perf_counter()
-    for i in range(4):
-        enqueue_native(i)
-    enqueue_ms = (time.perf_counter() - t_enq) / 4 * 1e3
-    torch.cuda.synchronize()
-    # the clock this rank's card held: sampled inside the timed region when that was long enough for a few samples, else in the block above
-    sclk = (sum(cs_timed.clk) / len(cs_timed.clk)) if len(cs_timed.clk) >= 4 else ((steady or {}).get("sclk_mhz_mean") or -1.0)
+    steady, enqueue_ms, sclk = None, -1.0, -1.0
+    if args.full:
+        steady = steady_state_block(step_native, torch) if elapsed < STEADY_MIN_TIMED_S else None
+        # host time to ENQUEUE one window (no wait; a short burst, so the launch queue never pushes back): with one process per GPU on a
+        # many-GPU node this is what the ranks' share of the host cores has to sustain -- a rank is host-bound once it reaches ms_per_step
+        torch.cuda.synchronize()
+        t_enq = time.perf_counter()
+        for i in range(4):
+            enqueue_native(i)
+        enqueue_ms = (time.perf_counter() - t_enq) / 4 * 1e3
+        torch.cuda.synchronize()
+        # the clock this rank's card held: sampled inside the timed region when that was long enough for a few samples, else in the block above
+        sclk = (sum(cs_timed.clk) / len(cs_timed.clk)) if len(cs_timed.clk) >= 4 else ((steady or {}).get("sclk_mhz_mean") or -1.0)
     per_rank = shard.gather_floats([elapsed / args.steps * 1e3, median(step_s) * 1e3, marks["first_timed_step"] - t_ref, enqueue_ms, float(sclk),
                                     float(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))], rdev)
 
@@ -532,7 +583,6 @@ def main():
         # median window latency (the reference reports the mean of its per-call timer, flow/base.py:321-328): per-step
         # perf_counter stamps inside the same timed region, this rank's steps (N > 1: the slowest rank's median)
         "median_ms_per_step": round(max(r[1] for r in per_rank), 4),
-        "steady_state": steady,
         "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "arithmetic": ARITHMETIC, "data": "synthetic",
         "config": {"workload": ("BASELINE configs[1]: PSPNet-ResNet50 keyframe + linear interp (no_warp=True, feature_based=False), "
@@ -549,14 +599,8 @@ def main():
         "distributed": {"backend": backend, "rccl_world_size": dist_world if backend == "nccl" else 0, "world_size": dist_world,
                         "rank_ms_per_step": {"min": round(min(r[0] for r in per_rank), 4), "max": round(max(r[0] for r in per_rank), 4),
                                              "per_rank": [round(r[0], 4) for r in per_rank]},
-                        # what an N = 8 line is read with: the host side of every rank -- time to enqueue one window
-                        # (host-bound when it approaches ms_per_step), the cores the rank may run on, and the clock its card held
-                        "host_enqueue_ms_per_step": {"max": round(max(r[3] for r in per_rank), 4), "per_rank": [round(r[3], 4) for r in per_rank],
-                                                     "what": "host wall time to enqueue one window without waiting (4 windows, after the timed region)"},
                         "host_cpus": {"cpu_count": os.cpu_count(), "affinity_per_rank": [int(r[5]) for r in per_rank], "ranks": world,
                                       "cpus_per_rank": round(min(r[5] for r in per_rank) / max(world, 1), 2)},
-                        "sclk_mhz_mean": {"per_rank": [round(r[4], 1) if r[4] > 0 else None for r in per_rank],
-                                          "source": "hwmon freq1_input of each rank's card during its timed region (the steady-state block when that was too short)"},
                         "startup_s": {"max": round(max(r[2] for r in per_rank), 2), "per_rank": [round(r[2], 2) for r in per_rank],
                                       "from": "bench.py launcher start" if "FS_BENCH_LAUNCHER_T0" in os.environ else "this process's start",
                                       "to": "first timed step (after imports, weights, resident inputs, fs_reserve, warm-up, barrier)"},
@@ -570,6 +614,22 @@ def main():
         "hip_options": dict(HIP_OPTS) or None,  # null = the shipped defaults (what the driver runs)
         "reference_claim_fps_other_hw": 76.85,
     }
+    if not args.full:  # a plain run: the headline line only
+        if rank == 0:
+            result["effective_tflops_direct_conv_equivalent_per_gpu"] = effective_tflops(fps, world)
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    result["steady_state"] = steady
+    # what an N = 8 line is read with: the host side of every rank -- time to enqueue one window (host-bound when it
+    # approaches ms_per_step), the cores the rank may run on (host_cpus, above), and the clock its card held
+    result["distributed"]["host_enqueue_ms_per_step"] = {
+        "max": round(max(r[3] for r in per_rank), 4), "per_rank": [round(r[3], 4) for r in per_rank],
+        "what": "host wall time to enqueue one window without waiting (4 windows, after the timed region)"}
+    result["distributed"]["sclk_mhz_mean"] = {
+        "per_rank": [round(r[4], 1) if r[4] > 0 else None for r in per_rank],
+        "source": "hwmon freq1_input of each rank's card during its timed region (the steady-state block when that was too short)"}
 
     if rank == 0:
         # ---- parity on the bench inputs: HIP masks vs the reference's own masks (golden fixture, clip seed 1000)
@@ -656,10 +716,7 @@ def main():
         result["variants"] = variants(args, dev, rdev, net, state, fm, windows, dl, dr, host_masks, host_post)
 
     if rank == 0:
-        # direct-convolution-equivalent rate (727.44 GFLOP per key frame); the heavy 3x3 convs run as Winograd
-        # F(6x6,3x3) and the head skips the pyramid channels, which together execute ~2.3x fewer FLOPs, so this "effective"
-        # figure may exceed the fp32 MFMA peak -- it is NOT a roofline fraction
-        result["effective_tflops_direct_conv_equivalent_per_gpu"] = round(2 * KEYFRAME_GFLOP * 1e-3 * (fps / world) / N_DELTA, 2)
+        result["effective_tflops_direct_conv_equivalent_per_gpu"] = effective_tflops(fps, world)
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(state, windows_cpu)
         print(json.dumps(result), flush=True)

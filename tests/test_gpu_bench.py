@@ -19,7 +19,7 @@ def _last_json(stdout):
 
 
 def test_bench_json_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -60,6 +60,35 @@ def test_bench_json_line_has_the_contract_fields():
     assert len(sc) == 1 and (sc[0] is None or 500 < sc[0] < 3000)
 
 
+def test_plain_bench_run_times_k_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) measures the headline only: set-up, warm-up, the K timed steps, --dump-outputs, the line.  The dump is
+    what the last timed step returned to its caller (logits and masks of window (K - 1) mod 4, float32); inputs and weights come
+    from fixed seeds, so another run whose last step is the same window returns the same arrays."""
+    import numpy as np
+
+    def run(steps, warmup, d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return _last_json(r.stdout)
+
+    j = run(3, 1, tmp_path / "a")
+    assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "frames/s" and j["dtype"] == "f32"
+    assert j["higher_is_better"] is True and "segmentation FPS" in j["metric"]
+    assert abs(j["value"] - 5 * 1000.0 / j["ms_per_step"]) < 1e-2 * j["value"]
+    for k in ("roofline", "parity", "steady_state", "cpu_baseline", "variants"):
+        assert k not in j, k
+    assert "host_enqueue_ms_per_step" not in j["distributed"] and "sclk_mhz_mean" not in j["distributed"]
+    pred, mask = np.load(tmp_path / "a" / "pred.npy"), np.load(tmp_path / "a" / "mask.npy")
+    assert pred.dtype == mask.dtype == np.float32 and pred.shape == (5, 5, 713, 713) and mask.shape == (5, 713, 713)
+    assert pred.nbytes + mask.nbytes <= 64e6
+    assert np.isfinite(pred).all() and (mask == pred.argmax(1)).mean() > 0.9999
+    j2 = run(7, 0, tmp_path / "b")  # last step: window 6 mod 4 = 2, as above
+    assert j2["steps"] == 7 and j2["warmup"] == 0
+    np.testing.assert_allclose(np.load(tmp_path / "b" / "pred.npy"), pred, rtol=0, atol=1e-5 * np.abs(pred).max())
+    assert (np.load(tmp_path / "b" / "mask.npy") == mask).mean() > 0.9999
+
+
 def test_bench_two_ranks_rehearsed_on_one_gpu():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -81,7 +110,7 @@ def test_bench_launched_directly_with_gpus_2_spawns_its_own_ranks():
     fresh children (here rehearsed on the one GPU over gloo) and relays rank 0's line; the N > 1 step is the BASELINE configs[4]
     workload: 64 clips sharded by clip, 32 clips = 128 windows on each of two ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--full", "--no-extras",
                         "--no-cpu-baseline", "--rehearse-on-one-gpu"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _last_json(r.stdout)
@@ -102,7 +131,7 @@ def test_bench_four_ranks_spawned_by_the_launcher_on_one_gpu():
     a GPU box admits at most 6 processes on its card, this test runner included, so eight GPU ranks cannot be started here;
     four leave a margin.)  64 clips over 4 ranks = 16 clips = 64 windows each; every rank reports its own ms per step."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "1", "--full", "--no-extras",
                         "--no-cpu-baseline", "--rehearse-on-one-gpu"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _last_json(r.stdout)
@@ -129,7 +158,7 @@ def test_four_ranks_squeezed_onto_four_cores_keep_their_step_time():
     if len(cpus) < 8:
         pytest.skip("needs at least 8 cores to compare a free run with a 4-core one")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "24", "--warmup", "4", "--no-extras", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "24", "--warmup", "4", "--full", "--no-extras", "--no-cpu-baseline",
            "--rehearse-on-one-gpu"]
 
     def run(pin):

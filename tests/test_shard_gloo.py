@@ -150,6 +150,9 @@ def test_bench_launches_its_own_ranks_without_touching_torch():
     # the image exports the variable: the first attempt keeps what it finds
     body1 = "assert calls[0][1]['env']['HSA_ENABLE_IPC_MODE_LEGACY'] == '1' and rc == 0\n"
     _run_launcher([(0, ['{"value": 1}\n'])], ['bench.py', '--gpus', '8'], body1, {"HSA_ENABLE_IPC_MODE_LEGACY": "1"})
+    # the ranks run in the repository root: a relative --dump-outputs directory reaches them as an absolute path
+    body2 = "assert rc == 0 and calls[0][0][-2:] == ['--dump-outputs', os.path.abspath('out')], calls[0][0]\n"
+    _run_launcher([(0, ['{"value": 1}\n'])], ['bench.py', '--gpus', '8', '--dump-outputs', 'out'], body2)
 
 
 def test_bench_launcher_retries_once_with_the_other_ipc_setting_only_for_an_ipc_failure_before_the_result_line():

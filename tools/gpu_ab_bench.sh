@@ -7,6 +7,7 @@ mkdir -p gpurun_out
 for i in 1 2 3; do
   for which in other tree; do
     if [ $which == other ]; then L="--lib $OTHER"; else L=""; fi
+    L="$L --full"  # the roofline figures printed below come with --full
     timeout -k 10 300 python bench.py --steps $STEPS --warmup 20 --no-extras --no-cpu-baseline $L > gpurun_out/ab_${which}_$i.json 2> gpurun_out/ab_err.txt || { tail -5 gpurun_out/ab_err.txt; exit 1; }
     python - <<PY
 import json

@@ -7,7 +7,7 @@ ROUND=${ROUND:-r06}
 O=$R/gpurun_out/prof_$ROUND
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/bench.err; echo "bench rocprof exit=$?"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/bench.err; echo "bench rocprof exit=$?"
 for c in cfg2 cfg3 crops feat; do
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$c -- python3 $R/tools/bench_configs.py --only $c --steps 10 > $O/$c.txt 2> $O/$c.err; echo "$c rocprof exit=$?"; grep configs $O/$c.txt
 done
