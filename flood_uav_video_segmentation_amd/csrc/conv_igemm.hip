@@ -20,8 +20,8 @@
 // per chunk (120 TFLOP/s on the decoder conv); double-buffered LDS + register-pinned fragment prefetch alone: null;
 // global_load_lds with a zero page: 128; buffer_load...lds with range-check padding: 138.  Tried and measured null,
 // removed: start-time stagger of co-resident blocks; s_setprio around the MFMAs; an LDS-transposed epilogue with 16-B
-// stores; persistent tiles with the next tile's first DMA issued before the epilogue; a 256x128 eight-wave tile (kept as
-// tile 5, not selected); raster panels sized to the XCD's co-resident tiles; skipping the chunks of taps that are outside
+// stores; persistent tiles with the next tile's first DMA issued before the epilogue; a 256x128 eight-wave tile (tile
+// id 5, since retired); raster panels sized to the XCD's co-resident tiles; skipping the chunks of taps that are outside
 // the image for a whole tile (ASPP dilation 24 / 36 on a 90x90 map: up to 27 % of the chunks) -- every tile is resident at
 // once, so the launch lasts as long as its full-price centre tiles; with scattered m-tiles and 64x64 tiles to mix cheap and
 // expensive ones per CU: +6 % on the dilation-24 conv, 0 on DeepLabv3 end to end.
@@ -49,7 +49,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // the sentinel voffset 0x80000000.  Per chunk the issue is 8 DMAs + ~12 VALU: the per-lane offsets are loop
 // invariants, the chunk position is the scalar soffset, tap validity is one bit of a per-row mask.
 // Elimination runs on the decoder conv (profiles/): VGPR-staged loads cost ~9 %, the ds_write pass ~5 %.
-// Workgroup timelines (tools/probe_conv_trace.hip, profiles/r01_conv_wg_timeline.txt): with two workgroups per CU the
+// Workgroup timelines (a cycle-stamp trace build, profiles/r01_conv_wg_timeline.txt): with two workgroups per CU the
 // main loop keeps the MFMA pipe busy 93 % of its cycles and only 1.6 % of them are spent in the per-chunk wait+barrier;
 // a lone workgroup reaches 83 %.  What short-K layers lose is outside the loop, because the co-resident workgroup is
 // in the same phase (both were dispatched together): prologue (index math + first DMA) and epilogue.  The first
@@ -59,24 +59,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // De-phasing the two workgroups of a CU (delaying bid+256 by 4-40 k cycles) was measured before and after that change:
 // null to negative every time (the late workgroup's prologue/epilogue slow down under the neighbour's DMA + MFMA stream).
 // ---------------------------------------------------------------------------------------------------------
-#ifdef FS_TRACE
-// tools/probe_conv_trace.hip only (never in libfloodseg.so): per-workgroup timeline, 8 x u64 per workgroup:
-// [0] start, [1] first stage landed, [2] main loop done, [3] epilogue done (shader clock, s_memtime),
-// [4] cycles spent in the per-chunk wait+barrier, [5] HW_ID | XCC_ID << 32, [6] start (100 MHz wall clock), [7] end (wall)
-__device__ unsigned long long fs_trace_buf[8 * 65536];
-// round 5: end-of-chunk stamps of the first 8 K chunks of the split main loop (scalar registers; written out by lane 0 at the end)
-__device__ unsigned long long fs_trace_chunks[8 * 65536];
-#define FS_TRACE_DECL unsigned long long tr_start = __builtin_readcyclecounter(), tr_wall = wall_clock64(), tr_ready = 0, tr_loop = 0, tr_wait = 0; \
-    unsigned long long tr_c0 = 0, tr_c1 = 0, tr_c2 = 0, tr_c3 = 0, tr_c4 = 0, tr_c5 = 0, tr_c6 = 0, tr_c7 = 0;
-#define FS_TRACE_CHUNK(KC_) { const unsigned long long tc_ = __builtin_readcyclecounter(); \
-    if ((KC_) == 0) tr_c0 = tc_; else if ((KC_) == 1) tr_c1 = tc_; else if ((KC_) == 2) tr_c2 = tc_; else if ((KC_) == 3) tr_c3 = tc_; \
-    else if ((KC_) == 4) tr_c4 = tc_; else if ((KC_) == 5) tr_c5 = tc_; else if ((KC_) == 6) tr_c6 = tc_; else if ((KC_) == 7) tr_c7 = tc_; }
-#define FS_TRACE_SYNC() { const unsigned long long tw = __builtin_readcyclecounter(); FS_DMA_PUBLISH() tr_wait += __builtin_readcyclecounter() - tw; }
-#else
-#define FS_TRACE_DECL
-#define FS_TRACE_CHUNK(KC_)
-#define FS_TRACE_SYNC() FS_DMA_PUBLISH()
-#endif
 // A wave's buffer_load...lds writes are complete when ITS vmcnt reaches 0; the other waves may read them only after that.
 // __syncthreads() does not imply it: the compiler tracks LDS-DMA only against the SAME wave's later ds_reads and is free
 // to wait for vmcnt after the barrier (it did, in the 128x64 instantiation, once two unrelated global loads were added
@@ -97,7 +79,7 @@ constexpr int conv_tile_lds_floats() { return 2 * (BM * 32 + (SPLIT ? 3 * conv_s
 // One BM x BN output tile at (m0, n0): prologue, main loop, epilogue.  `lds` = conv_tile_lds_floats() floats, 1 KiB aligned; every
 // wave of the workgroup calls it with the same arguments.
 template <int BM, int BN, int WGM, int WGN, bool DUAL, bool SPLIT>
-__device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int n0, float* __restrict__ lds, const int bid) {
+__device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int n0, float* __restrict__ lds) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the buffer-resource builtins do not exist in the host pass, which only needs the launch stub
     constexpr int BK = 32;
     constexpr int NT = 64 * WGM * WGN;   // threads
@@ -111,7 +93,6 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
     constexpr int RB1 = SPLIT ? (BNL / 16) / (NT / 64) : RB;  // of them per plane
     static_assert(BN % 32 == 0 && WN % 32 == 0 && (SPLIT || BN % RSTEP == 0), "tile columns: whole 32-column MFMA blocks per wave");
     constexpr int STAGE = BM * BK + (SPLIT ? 3 * BPL : BN * BK);
-    FS_TRACE_DECL
 
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int wm = wv / WGN, wn = wv % WGN, l31 = lane & 31, hh = lane >> 5;
@@ -213,15 +194,8 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
     unsigned b_soff = 0;               // its byte offset along k in the packed filters
 
     // One DMA row (A rows first, then B rows): ROW_ in [0, RA+RB).
-#ifdef FS_TRACE  // elimination experiments (results invalid, timing only; profiles/r05_experiments.txt section 17): dbg & 64 no pixel-row DMAs,
-                 // & 128 (below) no pixel-fragment LDS reads, & 256 no filter-row DMAs
-#define FS_DMA_SKIP(ROW_) (((ROW_) < RA && (p.dbg & 64)) || ((ROW_) >= RA && (p.dbg & 256)))
-#else
-#define FS_DMA_SKIP(ROW_) false
-#endif
 #define FS_DMA_ROW(STG, ROW_)                                                                                     \
-    if (FS_DMA_SKIP(ROW_)) {                                                                                      \
-    } else if ((ROW_) < RA) {                                                                                     \
+    if ((ROW_) < RA) {                                                                                            \
         const int j = (ROW_) < RA ? (ROW_) : 0;                                                                   \
         if (DUAL && second) {                                                                                     \
             const unsigned vo = (a_mask[j] & 1u) ? a2_voff[DUAL ? j : 0] : SENT;                                  \
@@ -283,9 +257,6 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
     FS_DMA_ALL(0)
     FS_DMA_ADVANCE()
     FS_DMA_PUBLISH()  // stage 0 has landed for every wave
-#ifdef FS_TRACE
-    tr_ready = __builtin_readcyclecounter();
-#endif
     // Software pipeline across the chunk boundary: the barrier that hands stage cur^1 over (and frees stage cur) sits
     // between sub-steps 2 and 3; the DMA of chunk kc+2 and the first fragment reads of chunk kc+1 are issued right
     // behind it and hide under the 16 MFMAs of sub-step 3, so the MFMA pipe does not drain at a chunk boundary.
@@ -313,30 +284,15 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
         // A chunk of 32 k = two MFMA steps of 16 k; lane (i, hh) owns k = 16 s + 8 hh .. + 7 of row i in both operands.
         bf16x8 A3[TM][3], B3[TN][3], A3n[TM][3], B3n[TN][3];
         f32x4 araw[TM][2];
-#ifdef FS_TRACE
-        const bool FS_NO_A_READ = (p.dbg & 128) != 0;  // elimination experiment: the pixel fragments are not read from LDS
-        f32x4 fake_a = {1.f + lane, 2.f, 3.f, 4.f};
-        asm volatile("" : "+v"(fake_a));
-#define FS_FAKE_A_OPAQUE() asm volatile("" : "+v"(fake_a));
-#else
-        constexpr bool FS_NO_A_READ = false;
-        const f32x4 fake_a = {0.f, 0.f, 0.f, 0.f};
-#define FS_FAKE_A_OPAQUE()
-#endif
         u32x4 ah[TM][3];
 #define FS_READ3(STG, S_, RAW_, B_)                                                                               \
     {                                                                                                             \
         const float* a_src = lds + (STG) * STAGE;                                                                 \
         const float* b_src = a_src + BM * BK;                                                                     \
         const int c0 = (4 * (S_) + 2 * hh) ^ sw;                                                                  \
-        if (FS_NO_A_READ) {                                                                                       \
-            FS_FAKE_A_OPAQUE()  /* per use: the split of the fake fragments is not to be hoisted out of the loop */ \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i) { RAW_[i][0] = fake_a; RAW_[i][1] = fake_a; }          \
-        } else {                                                                                                  \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                          \
             RAW_[i][0] = *reinterpret_cast<const f32x4*>(&a_src[(wm * WM + i * 32 + l31) * BK + 4 * c0]);         \
             RAW_[i][1] = *reinterpret_cast<const f32x4*>(&a_src[(wm * WM + i * 32 + l31) * BK + 4 * (c0 ^ 1)]);   \
-        }                                                                                                         \
         }                                                                                                         \
         const int bslot = (2 * (S_) + hh) ^ ((l31 >> 2) & 3);                                                     \
         _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                            \
@@ -401,7 +357,7 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
             __builtin_amdgcn_sched_barrier(0);
             FS_STEP3(A3, B3, araw, A3n)
             __builtin_amdgcn_sched_barrier(0);
-            FS_TRACE_SYNC()  // every wave's reads of stage `cur` are done, chunk kc + 1 has landed
+            FS_DMA_PUBLISH()  // every wave's reads of stage `cur` are done, chunk kc + 1 has landed
             if (kc + 2 < nchunks) {
                 FS_DMA_ALL(cur)
                 FS_DMA_ADVANCE()
@@ -422,14 +378,12 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
             __builtin_amdgcn_sched_barrier(0);
             FS_STEP3(A3n, B3n, araw, A3)
             __builtin_amdgcn_sched_barrier(0);
-            FS_TRACE_CHUNK(kc)
             cur ^= 1;
         }
         asm volatile("" ::"v"(touch0), "v"(touch1));  // keeps the two dead loads (and their registers) alive to here
         if (!DUAL && p.res) igemm_load_residual(rv, p, M, em_base, en_base);
 #undef FS_READ3
 #undef FS_STEP3
-#undef FS_FAKE_A_OPAQUE
     } else {
     if (!DUAL && p.res && nchunks <= 2) igemm_load_residual(rv, p, M, em_base, en_base);
     FS_FRAGS(0, 0, a0, b0)
@@ -450,7 +404,7 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
         __builtin_amdgcn_sched_barrier(0);
         FS_MMA(a0, b0)
         __builtin_amdgcn_sched_barrier(0);
-        FS_TRACE_SYNC()  // __syncthreads: all fragment reads of stage `cur` are done (lgkmcnt(0)) and chunk kc+1 has landed (vmcnt(0))
+        FS_DMA_PUBLISH()  // __syncthreads: all fragment reads of stage `cur` are done (lgkmcnt(0)) and chunk kc+1 has landed (vmcnt(0))
         if (kc + 2 < nchunks) {
             FS_DMA_ALL(cur)
             FS_DMA_ADVANCE()
@@ -463,20 +417,13 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
         cur ^= 1;
     }
     }
-#ifdef FS_TRACE
-    tr_loop = __builtin_readcyclecounter();
-#endif
 #undef FS_DMA_ROW
 #undef FS_DMA_ADVANCE
 #undef FS_DMA_ALL
-#undef FS_DMA_SKIP
 #undef FS_FRAGS
 #undef FS_MMA
 
     // ---- epilogue
-#ifdef FS_TRACE
-    if ((p.dbg & 16) && p.ld_out >= 0) return;  // timing experiment: skip the epilogue (the test keeps the main loop alive)
-#endif
     if constexpr (SPLIT && !DUAL && BN == 96 && TM == 1) {
         // the Segmenter's qkv Linear: K / V column tiles leave as the attention's operand planes (ConvParams::kv_k, igemm_epilogue.h)
         const int Dm = p.kv_heads * 64;
@@ -495,16 +442,6 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
         else if (p.relu == 2) igemm_epilogue<2, false>(acc, rv, sc_n, sh_n, p, M, em_base, en_base);
         else igemm_epilogue<0, false>(acc, rv, sc_n, sh_n, p, M, em_base, en_base);
     }
-#ifdef FS_TRACE
-    if (t == 0) {
-        unsigned long long* o = fs_trace_buf + 8 * (size_t)(bid & 65535);
-        o[0] = tr_start; o[1] = tr_ready; o[2] = tr_loop; o[3] = __builtin_readcyclecounter(); o[4] = tr_wait;
-        o[5] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
-        o[6] = tr_wall; o[7] = wall_clock64();
-        unsigned long long* c = fs_trace_chunks + 8 * (size_t)(bid & 65535);
-        c[0] = tr_c0; c[1] = tr_c1; c[2] = tr_c2; c[3] = tr_c3; c[4] = tr_c4; c[5] = tr_c5; c[6] = tr_c6; c[7] = tr_c7;
-    }
-#endif
 #endif
 }
 
@@ -514,11 +451,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_dma_f32(ConvParams 
     constexpr int PM = 8;  // m-tiles per raster panel (panels sized to the ~64 tiles co-resident on an XCD: same time, +3 % L2 misses)
     __shared__ __attribute__((aligned(1024))) float lds[conv_tile_lds_floats<BM, BN, SPLIT, WGM * WGN>()];
     const int nblk = gridDim.x, bid = blockIdx.x;
-#ifdef FS_TRACE
-    // experiment: de-phase the workgroups that share a CU (dispatch order puts bid and bid + 256 on the same CU)
-    if ((p.dbg & 32) && ((bid >> 8) & 1))
-        for (int i = 0; i < (p.dbg >> 8); ++i) __builtin_amdgcn_s_sleep(4);  // 256 cycles each
-#endif
     const int q = nblk >> 3, rr = nblk & 7, xcd = bid & 7;
     const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
     const int per_group = tiles_m * tiles_n;
@@ -533,14 +465,16 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_dma_f32(ConvParams 
     if (SPLIT) p.wgt3 = (const char*)p.wgt3 + (long long)grp * p.g_wgt * 2;  // the group's rows inside every plane
     p.out += (long long)grp * p.g_out;
     p.kv_b = grp;
-    conv_tile<BM, BN, WGM, WGN, DUAL, SPLIT>(p, m0, n0, lds, bid);
+    conv_tile<BM, BN, WGM, WGN, DUAL, SPLIT>(p, m0, n0, lds);
 #endif
 }
 
 namespace {
 struct TileCfg { int bm, bn; const char* name; };
+// indexed by tile id; id 5 (a 256 x 128 tile) is retired and refused, the ids after it keep their numbers
 const TileCfg kTiles[7] = {{0, 0, "auto"}, {128, 128, "igemm128x128"}, {128, 64, "igemm128x64"},
-                           {64, 64, "igemm64x64"}, {64, 128, "igemm64x128"}, {0, 0, "(retired)"}, {128, 96, "split128x96"}};
+                           {64, 64, "igemm64x64"}, {64, 128, "igemm64x128"}, {0, 0, nullptr}, {128, 96, "split128x96"}};
+bool tile_id_ok(int tile) { return tile >= 0 && tile <= 6 && tile != 5; }
 
 int pick_tile(const ConvParams& p) {
     // Cost model fitted to the MI355X tile sweeps (profiles/r01_conv_tile_sweep*.txt): per-tile MFMA efficiency by tile
@@ -570,8 +504,8 @@ int pick_tile(const ConvParams& p) {
 }  // namespace
 
 const char* conv_igemm_tile_name(const ConvParams& p, int tile) {
-    tile &= 0xff;
-    if (tile <= 0 || tile > 6 || tile == 5) tile = pick_tile(p);
+    if (!tile_id_ok(tile)) return "(bad tile)";
+    if (tile == 0) tile = pick_tile(p);
     if (p.in2 && p.wgt3) return tile == 2 ? "split128x64cat" : "split128x128cat";
     if (p.in2) return tile == 2 ? "igemm128x64cat" : "igemm128x128cat";  // the concatenated-K instantiations are kernels of their own
     if (p.wgt3) return tile == 1 ? "split128x128" : tile == 2 ? "split128x64" : tile == 4 ? "split64x128" : tile == 6 ? "split128x96" : "split64x64";
@@ -638,8 +572,8 @@ int check_conv_params(const ConvParams& p) {
 
 int launch_conv_igemm(const ConvParams& p, hipStream_t s, int tile) {
     FS_TRY(check_conv_params(p));
-    tile &= 0xff;
-    if (tile <= 0 || tile > 6 || tile == 5) tile = pick_tile(p);
+    FS_REQUIRE(tile_id_ok(tile), "conv_igemm: tile %d is not 0..4 or 6", tile);
+    if (tile == 0) tile = pick_tile(p);
     FS_REQUIRE(tile < 6 || (p.wgt3 && !p.in2), "conv_igemm: tile 6 (128 x 96) exists on the split-operand route only");
     const int M = p.B * p.Ho * p.Wo;
     const int bm = kTiles[tile].bm, bn = kTiles[tile].bn;
@@ -693,12 +627,7 @@ int launch_conv_igemm(const ConvParams& p, hipStream_t s, int tile) {
         FS_HIP(hipGetLastError());
         return 0;
     }
-#ifdef FS_TRACE
-    const size_t dyn = (p.dbg & 2) ? 56 * 1024 : 0;  // timing experiment: push occupancy to one block per CU
-#else
-    const size_t dyn = 0;
-#endif
-#define FS_CONV_LAUNCH(BM_, BN_) hipLaunchKernelGGL((conv_igemm_dma_f32<BM_, BN_>), grid, block, dyn, s, p, tm, tn);
+#define FS_CONV_LAUNCH(BM_, BN_) hipLaunchKernelGGL((conv_igemm_dma_f32<BM_, BN_>), grid, block, 0, s, p, tm, tn);
     switch (tile) {
         case 1: FS_CONV_LAUNCH(128, 128) break;
         case 2: FS_CONV_LAUNCH(128, 64) break;

@@ -54,12 +54,8 @@ struct ConvParams {
     int kv_N, kv_Npad, kv_heads;
     unsigned kv_plane_bytes;   // bytes of one plane of K (= of V^T): B * heads * Npad * 64 * 2
     int kv_b;                  // image of this workgroup's group (set by the kernel)
-#ifdef FS_TRACE  // tools/probe_conv_trace.hip builds only -- the field does not exist in libfloodseg.so
-    int dbg;     // timing experiments (results are wrong when != 0): 2 = one block per CU, 16 = skip the epilogue,
-                 // 32 | n << 8 = start workgroups bid+256.. n*256 cycles late
-#endif
 };
-// tile: 0 = heuristic, 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 64x128
+// tile: 0 = heuristic, 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 64x128, 6 = 128x96 (split route only); any other id is refused
 int launch_conv_igemm(const ConvParams& p, hipStream_t s, int tile = 0);
 const char* conv_igemm_tile_name(const ConvParams& p, int tile = 0);
 // planes[t][i] (t = 0, 1, 2; bf16) with w[i] == planes[0][i] + planes[1][i] + planes[2][i] exactly (ConvParams::wgt3)
@@ -274,8 +270,8 @@ int launch_dec_assemble(const float* Y, const float* cls_emb, float* Z, int B, i
 // (the cls token) is skipped in the output (segm/model/segmenter.py:41-42).
 int launch_layernorm(const float* in, const float* gamma, const float* beta, float* out, int rows, int D, int rows_per_batch,
                      int drop_first, hipStream_t s);
-// softmax(q k^T * scale) v for all heads, fp32 MFMA flash-style; qkv rows are [3][heads][64] (blocks.py:56-77).
-// scratch: attention_scratch_floats(B, N, heads) floats for the key-split partials (nullptr = single pass)
+// softmax(q k^T * scale) v for all heads, fp32 MFMA flash-style; qkv rows are [3][heads][64] (blocks.py:56-77), qkv 16-B aligned and
+// one image's qkv smaller than 2 GiB.  scratch: attention_scratch_floats(B, N, heads) floats for the key-split partials (nullptr = single pass)
 size_t attention_scratch_floats(int B, int N, int heads);
 int launch_attention_f32(const float* qkv, float* out, int B, int N, int heads, float scale, float* scratch, hipStream_t s);
 // the same on the bf16 matrix cores with split operands (three bf16 terms per fp32 value, fp32 accumulate: vit_ops.hip);
@@ -343,8 +339,8 @@ static inline int winograd_pick_m(int /*B*/, int H, int W, int dil) {
 size_t wino_fused_bank_floats(int Cin, int Cout);
 bool wino_fused_supported(int Cin, int Cout, int KH, int KW, int stride, int pad, int dil);
 int launch_wino4_filter_packed(const float* w, float* U, int O, int I, hipStream_t s, int chunk_major = 0);
-// variant: 0 = by workgroup count, 1 = 32 tiles x 64 channels per workgroup (8 waves), 2 = 16 tiles x 64 channels (4 waves, two
-// workgroups per CU), 3 = 16 x 64 warp-specialised (4 MFMA waves + 4 transform waves); bit-identical results
+// variant: 0 = by workgroup count, 2 = 16 tiles x 64 channels per workgroup (4 waves, two
+// workgroups per CU), 3 = 16 x 64 warp-specialised (4 MFMA waves + 4 transform waves); bit-identical results.  1 (retired) is refused.
 int launch_wino4_fused(const float* in, int ld_in, const float* U, const float* scale, const float* shift, float* out, int ld_out, int B, int H,
                        int W, int Cin, int Cout, int relu, hipStream_t s, int variant = 0);
 

@@ -1,7 +1,7 @@
 // Segmenter executor: ViT encoder + mask-transformer decoder as a fixed launch sequence.
 // Restates model/vit.py:13-56 -> segm/model/segmenter.py:32-48, vit.py:108-137, blocks.py:16-95,
 // decoder.py:80-102, utils.py:22-40,65-76.  Every nn.Linear runs on conv_igemm_f32 (1x1 "conv" over
-// the token matrix), attention on attention_f32_kernel.
+// the token matrix), attention on attention_bf16x3_kernel (split operands) or attention_dma_kernel (fp32 MFMA).
 #include "net.h"
 
 namespace fs {

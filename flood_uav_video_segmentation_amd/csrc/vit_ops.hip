@@ -197,36 +197,43 @@ int launch_layernorm(const float* in, const float* gamma, const float* beta, flo
 // (the 32x32 accumulator has its column on the lane and rows (r&3)+8(r>>2)+4h in registers: fed back as
 //  the B operand, step r consumes key (r&3)+8(r>>2) from lane-half 0 and that key + 4 from lane-half 1,
 //  and the A operand reads V at exactly those two keys.)
-// K tile rows are padded to 68 floats: ds_read_b128 of a 16-lane group then hits 16 distinct 4-bank slots.
-#ifndef FS_ATT_EXP
-#define FS_ATT_EXP 0  // tools/probe_attention.hip only: elimination experiments (1 no exp, 2 no PV MFMAs, 3 no K/V re-staging, 4 no S MFMAs)
-#endif
 constexpr int ATT_DH = 64;
-constexpr int ATT_KT = 64;   // keys per LDS tile
-constexpr int ATT_LDK = 68;
-#ifndef ATT_USE_DMA
-#define ATT_USE_DMA 1  // 0: the register-staged kernel (A/B builds)
-#endif
+constexpr int ATT_KT = 64;   // keys per tile of the key split (the unit nsplit divides)
 constexpr int ATT_NW = 4;    // waves per workgroup = 128 queries per staged K/V tile.  Measured on ViT-S/16 (N = 1937): 2 waves
                              // (64 queries, 4 workgroups/CU) 36 TFLOP/s -- the K/V staging per query doubles; 4 waves 52+
 
+// K / V staged global -> LDS DIRECTLY (round 3): a stage is 32 keys, K and V of the NEXT stage are requested with
+// buffer_load_dwordx4 ... lds (four 1-KiB pieces per wave, no VGPRs) right behind the barrier that publishes the current one, and
+// land under its 64 MFMAs; two LDS stage buffers, one barrier per 32 keys.  A piece is lane-linear in LDS (4 rows x 256 B), so rows
+// cannot be padded: the K image is XOR-swizzled instead -- 16-B chunk j of key row r lives at chunk j ^ (r & 15), applied to the
+// per-lane SOURCE offset -- which keeps the fragment reads (ds_read_b128 of one column chunk across 16 different rows)
+// conflict-free; V is read along rows (32 consecutive floats) and stays linear.  Keys beyond N are zero-filled by the descriptor's
+// range check (sentinel offset) and masked to -inf.
+// History: it replaced a register-staged kernel (64-key K / V tiles through VGPRs, ds_write_b128, two barriers per tile: ~7 % of
+// the launch on moving K and V) with the same arithmetic in the same order and bit-identical results.  Measured (ViT-S/16, B = 2,
+// 14 launches): 1.7225 ms against 1.7297 ms -- no gain: with three workgroups per CU the staging was already hidden behind the
+// neighbours' MFMAs; what it frees is 32 VGPRs (122 instead of 154).  A fourth workgroup per CU with a 5-way key split (960
+// workgroups) was measured too: 1.85 ms, worse (more partials to merge, same pipe).  The register-staged kernel was removed in a
+// later cleanup.
+//
 // Key split (flash-decoding style): ViT-S/16 at 713x713 has 16 query tiles x 6 heads x 2 frames = 192 workgroups for 256
 // CUs, one wave per SIMD, so the softmax VALU work of a wave is never hidden behind another wave's MFMAs.  With
 // nsplit > 1 workgroup (query tile, split) walks only its share of the key tiles and stores the UNNORMALISED O^T plus
 // (running max, running sum) per query; attention_combine_kernel merges the splits.  nsplit == 1 writes `out` directly.
-// __launch_bounds__(.., 3): three waves per SIMD (the compiler fits 154 VGPRs instead of 210, no spills), so that the three
-// workgroups the key split aims at per CU are really co-resident: 96.8 -> 101.9 TFLOP/s on ViT-S/16 (profiles/r02_experiments.txt).
+// __launch_bounds__(.., 3): three waves per SIMD (the register-staged kernel fitted 154 VGPRs instead of 210, no spills), so that
+// the three workgroups the key split aims at per CU are really co-resident: 96.8 -> 101.9 TFLOP/s on ViT-S/16
+// (profiles/r02_experiments.txt).
 template <bool SPLIT>
-__global__ __launch_bounds__(64 * ATT_NW, 3) void attention_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+__global__ __launch_bounds__(64 * ATT_NW, 3) void attention_dma_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                      float* __restrict__ part_o, float* __restrict__ part_ml, int N,
                                                                      int heads, float scale, int nsplit) {
-    __shared__ __attribute__((aligned(16))) float Ks[ATT_KT * ATT_LDK];
-    __shared__ __attribute__((aligned(16))) float Vs[ATT_KT * ATT_DH];
-    constexpr int NT = 64 * ATT_NW;
-    constexpr int LPT = ATT_KT * 16 / NT;  // float4 of K (and of V) staged per thread
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int ST = 32;  // keys per stage
+    __shared__ __attribute__((aligned(1024))) float Ks[2][ST * ATT_DH];
+    __shared__ __attribute__((aligned(1024))) float Vs[2][ST * ATT_DH];
     const int D = heads * ATT_DH, ld = 3 * D;
     const int b = blockIdx.z, head = blockIdx.y;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
     const int qtiles = SPLIT ? gridDim.x / nsplit : gridDim.x;
     const int qt = SPLIT ? blockIdx.x % qtiles : blockIdx.x, split = SPLIT ? blockIdx.x / qtiles : 0;
@@ -254,175 +261,7 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_f32_kernel(const flo
         for (int e = 0; e < 16; ++e) acc_o[i][e] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
 
-    const int ntiles_all = (N + ATT_KT - 1) / ATT_KT;
-    const int kt0 = SPLIT ? (ntiles_all * split) / nsplit : 0;             // launcher: nsplit <= ntiles_all, so never empty
-    const int ntiles = SPLIT ? (ntiles_all * (split + 1)) / nsplit : ntiles_all;
-    f32x4 kreg[LPT], vreg[LPT];  // next K/V tile, in flight while the current one is multiplied
-    auto fetch = [&](int kt) {
-#pragma unroll
-        for (int j = 0; j < LPT; ++j) {
-            const int idx = t + NT * j;
-            const int row = idx >> 4, c4 = idx & 15;
-            const int key = min(kt * ATT_KT + row, N - 1);  // clamped; rows beyond N are zeroed when stored
-            const float* rp = base + (size_t)key * ld + c4 * 4;
-            kreg[j] = *reinterpret_cast<const f32x4*>(rp + D);
-            vreg[j] = *reinterpret_cast<const f32x4*>(rp + 2 * D);
-        }
-    };
-    fetch(kt0);
-    for (int kt = kt0; kt < ntiles; ++kt) {
-        __syncthreads();  // previous tile fully consumed
-        if (FS_ATT_EXP != 3 || kt == kt0)
-#pragma unroll
-        for (int j = 0; j < LPT; ++j) {
-            const int idx = t + NT * j;
-            const int row = idx >> 4, c4 = idx & 15;
-            const bool ok = kt * ATT_KT + row < N;
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(&Ks[row * ATT_LDK + c4 * 4]) = ok ? kreg[j] : z;
-            *reinterpret_cast<f32x4*>(&Vs[row * ATT_DH + c4 * 4]) = ok ? vreg[j] : z;
-        }
-        __syncthreads();
-        if (kt + 1 < ntiles && FS_ATT_EXP != 3) fetch(kt + 1);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const int key0 = kt * ATT_KT + kb * 32;
-            if (key0 >= N) break;  // block-uniform
-            f32x16 sT;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sT[e] = 0.f;
-            const float* krow = &Ks[(kb * 32 + l31) * ATT_LDK + 32 * hh];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(krow + 4 * u);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (FS_ATT_EXP != 4 || (u == 0 && e == 0)) sT = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qreg[4 * u + e], sT, 0, 0, 0);
-            }
-            // mask keys beyond N, running max over this lane's 16 keys and the other half's 16
-            if (key0 + 32 > N) {  // block-uniform: only the last block has keys to mask
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (key0 + (r & 3) + 8 * (r >> 2) + 4 * hh >= N) sT[r] = -INFINITY;
-            }
-            float mloc = sT[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, sT[r]);
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-            const float m_new = fmaxf(m_run, mloc);                        // finite: key0 < N guarantees one valid key
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);     // 2^(-inf) = 0 on the first block
-            float lsum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                sT[r] = FS_ATT_EXP == 1 ? sT[r] - m_new : __builtin_amdgcn_exp2f(sT[r] - m_new);
-                lsum += sT[r];
-            }
-            l_run = l_run * alpha + lsum;
-            m_run = m_new;
-            if (__any(alpha != 1.f)) {  // the running max settles after a few blocks: skip the 32 rescaling multiplies then
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc_o[i][e] *= alpha;
-            }
-            // O^T += V^T P^T
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int krow_r = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                const float v0 = Vs[krow_r * ATT_DH + l31];
-                const float v1 = Vs[krow_r * ATT_DH + 32 + l31];
-                if (FS_ATT_EXP == 2 && r > 0) continue;
-                acc_o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, sT[r], acc_o[0], 0, 0, 0);
-                acc_o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, sT[r], acc_o[1], 0, 0, 0);
-            }
-        }
-    }
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (SPLIT) {
-        if (q < N) {
-            const size_t row = ((size_t)(b * heads + head) * nsplit + split) * N + q;
-            float* op = part_o + row * ATT_DH;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc_o[i][4 * g + e];
-                    *reinterpret_cast<f32x4*>(op + i * 32 + 8 * g + 4 * hh) = v;
-                }
-            if (hh == 0) {
-                part_ml[2 * row] = m_run;
-                part_ml[2 * row + 1] = l_tot;
-            }
-        }
-        return;
-    }
-    const float inv = 1.f / l_tot;
-    if (q < N) {
-        float* op = out + ((size_t)b * N + q) * D + head * ATT_DH;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc_o[i][4 * g + e] * inv;
-                *reinterpret_cast<f32x4*>(op + i * 32 + 8 * g + 4 * hh) = v;
-            }
-    }
-}
-
-// ------------------------------------------------------------------ the same kernel with K / V staged global -> LDS DIRECTLY
-// (round 3).  The register-staged form above spends, per 64 keys and thread, 8 global loads into 32 VGPRs, 8 ds_write_b128 and
-// two barriers on moving K and V (measured: ~7 % of the launch, tools/probe_attention.hip).  Here a stage is 32 keys, K and V
-// of the NEXT stage are requested with buffer_load_dwordx4 ... lds (four 1-KiB pieces per wave, no VGPRs) right behind the barrier
-// that publishes the current one, and land under its 64 MFMAs; two LDS stage buffers, one barrier per 32 keys.  A piece is
-// lane-linear in LDS (4 rows x 256 B), so rows cannot be padded: the K image is XOR-swizzled instead -- 16-B chunk j of key row r
-// lives at chunk j ^ (r & 15), applied to the per-lane SOURCE offset -- which keeps the fragment reads (ds_read_b128 of one
-// column chunk across 16 different rows) conflict-free; V is read along rows (32 consecutive floats) and stays linear.  Keys
-// beyond N are zero-filled by the descriptor's range check (sentinel offset) and masked to -inf as before.  Same arithmetic,
-// same order: bit-identical to the register-staged kernel.  Measured (ViT-S/16, B = 2, 14 launches): 1.7225 ms against 1.7297 ms --
-// no gain: with three workgroups per CU the staging was already hidden behind the neighbours' MFMAs; what it frees is 32 VGPRs
-// (122 instead of 154).  A fourth workgroup per CU with a 5-way key split (960 workgroups) was measured too: 1.85 ms, worse (more
-// partials to merge, same pipe).  Kept as the shipped form (ATT_USE_DMA 0 builds the register-staged one for A/B).
-template <bool SPLIT>
-__global__ __launch_bounds__(64 * ATT_NW, 3) void attention_dma_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                                     float* __restrict__ part_o, float* __restrict__ part_ml, int N,
-                                                                     int heads, float scale, int nsplit) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int ST = 32;  // keys per stage
-    __shared__ __attribute__((aligned(1024))) float Ks[2][ST * ATT_DH];
-    __shared__ __attribute__((aligned(1024))) float Vs[2][ST * ATT_DH];
-    const int D = heads * ATT_DH, ld = 3 * D;
-    const int b = blockIdx.z, head = blockIdx.y;
-    const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int l31 = lane & 31, hh = lane >> 5;
-    const int qtiles = SPLIT ? gridDim.x / nsplit : gridDim.x;
-    const int qt = SPLIT ? blockIdx.x % qtiles : blockIdx.x, split = SPLIT ? blockIdx.x / qtiles : 0;
-    const int q = qt * (32 * ATT_NW) + wv * 32 + l31;
-    const int qc = min(q, N - 1);
-    const float* base = qkv + (size_t)b * N * ld + head * ATT_DH;
-
-    const float scale2 = scale * 1.44269504088896340736f;
-    float qreg[32];
-    {
-        const f32x4* qp = reinterpret_cast<const f32x4*>(base + (size_t)qc * ld + 32 * hh);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const f32x4 v = qp[u];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qreg[4 * u + e] = v[e] * scale2;
-        }
-    }
-    f32x16 acc_o[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc_o[i][e] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    // this workgroup's keys: the same 64-key tile ranges as the register-staged kernel, walked 32 keys at a time
+    // this workgroup's keys: its share of the 64-key tiles, walked 32 keys at a time
     const int ntiles_all = (N + ATT_KT - 1) / ATT_KT;
     const int kt0 = SPLIT ? (ntiles_all * split) / nsplit : 0;
     const int kt1 = SPLIT ? (ntiles_all * (split + 1)) / nsplit : ntiles_all;
@@ -636,7 +475,7 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_bf16x3_kernel(const 
         for (int e = 0; e < 16; ++e) acc_o[i][e] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
 
-    const int ntiles_all = (N + ATT_KT - 1) / ATT_KT;  // the same key ranges per split as the fp32 kernels
+    const int ntiles_all = (N + ATT_KT - 1) / ATT_KT;  // the same key ranges per split as attention_dma_kernel
     const int kt0 = SPLIT ? (ntiles_all * split) / nsplit : 0;
     const int kt1 = SPLIT ? (ntiles_all * (split + 1)) / nsplit : ntiles_all;
     const int s0 = 2 * kt0, s1 = min(2 * kt1, (N + ST - 1) / ST);
@@ -903,23 +742,18 @@ int launch_attention_split(const float* qkv, float* out, int B, int N, int heads
 
 int launch_attention_f32(const float* qkv, float* out, int B, int N, int heads, float scale, float* scratch, hipStream_t s) {
     FS_REQUIRE(B >= 1 && N >= 1 && heads >= 1, "attention: bad shape");
+    // the direct-to-LDS loads address one image's [N][3D] rows with 32-bit byte offsets and 16-B pieces
+    FS_REQUIRE((int64_t)N * 3 * heads * ATT_DH * 4 < ((int64_t)1 << 31) && ((uintptr_t)qkv & 15) == 0, "attention: qkv too large or unaligned");
     const int qtiles = cdiv(N, 32 * ATT_NW);
     const int ns = scratch ? attention_splits(B, N, heads) : 1;
-    // the 32-bit byte offsets of the direct-to-LDS form cover one image's [N][3D] rows; beyond 2 GiB (never in practice) the
-    // register-staged kernel takes over
-    const bool dma = ATT_USE_DMA && (int64_t)N * 3 * heads * ATT_DH * 4 < ((int64_t)1 << 31) && ((uintptr_t)qkv & 15) == 0;
     if (ns == 1) {
-        if (dma) hipLaunchKernelGGL(attention_dma_kernel<false>, dim3(qtiles, heads, B), dim3(64 * ATT_NW), 0, s, qkv, out, nullptr, nullptr, N, heads, scale, 1);
-        else hipLaunchKernelGGL(attention_f32_kernel<false>, dim3(qtiles, heads, B), dim3(64 * ATT_NW), 0, s, qkv, out, nullptr, nullptr, N, heads,
-                           scale, 1);
+        hipLaunchKernelGGL(attention_dma_kernel<false>, dim3(qtiles, heads, B), dim3(64 * ATT_NW), 0, s, qkv, out, nullptr, nullptr, N, heads, scale, 1);
         FS_HIP(hipGetLastError());
         return 0;
     }
     float* part_o = scratch;
     float* part_ml = scratch + (size_t)B * heads * ns * N * ATT_DH;
-    if (dma) hipLaunchKernelGGL(attention_dma_kernel<true>, dim3(qtiles * ns, heads, B), dim3(64 * ATT_NW), 0, s, qkv, out, part_o, part_ml, N, heads, scale, ns);
-    else hipLaunchKernelGGL(attention_f32_kernel<true>, dim3(qtiles * ns, heads, B), dim3(64 * ATT_NW), 0, s, qkv, out, part_o, part_ml, N, heads,
-                       scale, ns);
+    hipLaunchKernelGGL(attention_dma_kernel<true>, dim3(qtiles * ns, heads, B), dim3(64 * ATT_NW), 0, s, qkv, out, part_o, part_ml, N, heads, scale, ns);
     FS_HIP(hipGetLastError());
     launch_attention_combine(part_o, part_ml, out, B, N, heads, ns, s);
     FS_HIP(hipGetLastError());

@@ -5,7 +5,8 @@
 // 2.25x the map and would cross HBM twice (layer0.3 at 713^2: 590 MB for a 19-GFLOP conv), and a K = 64 GEMM runs the
 // implicit-GEMM kernel at 57 TFLOP/s.  Here nothing but the input map and the output map touches HBM:
 //
-//   workgroup = NT = 16*WM tiles (4x4 outputs each) x NC = 16*WN output channels, all 36 Winograd positions at once;
+//   workgroup = NT = 16*WM tiles (4x4 outputs each) x NC = 16*WN output channels, all 36 Winograd positions at once
+//   (instantiated with WM = 1, WN = 4: 16 tiles x 64 channels, 4 waves);
 //   wave (wm, wn) owns 16 tiles x 16 channels: 36 accumulators of v_mfma_f32_16x16x4_f32 = 144 registers per lane;
 //   K loop in stages of 16 input channels:
 //     * every thread loads the 6x6 patch of ONE (tile, channel) straight from the NHWC map (16 lanes = 16 consecutive
@@ -15,9 +16,7 @@
 //       wave, conflict-free), B = one 16-B global load of the packed filter bank U[xi][Cin/16][Cout][16] (lane (n, q):
 //       U[..][cout n][4q..4q+3], 1 KiB contiguous per wave, L2-resident: 0.6-2.4 MB per conv), 4 MFMAs (element e of both
 //       = k 4q+e: the MFMA sums over k, any k permutation is legal as long as A and B agree);
-//     * LDS is double-buffered by stage (2 x 72 KiB at 32 tiles): one barrier per 16 channels.  The waves of the second tile block (wm = 1) run
-//       "MFMA then transform", those of the first "transform then MFMA", so that the two waves sharing a SIMD keep the
-//       matrix pipe and the VALU busy at the same time instead of in lock-step (MI355X_MICROARCH.md, two waves per SIMD, 9);
+//     * LDS is double-buffered by stage (2 x 36 KiB at 16 tiles): one barrier per 16 channels;
 //   epilogue: a lane holds all 36 positions of 4 (tile, channel) pairs: A^T m A in registers, BatchNorm + ReLU, stores
 //   (16 lanes = 16 consecutive channels of one pixel).
 // FLOPs executed: 36/16 = 2.25 multiplies per output instead of 9.  fp32 error ~1e-5 relative (as F(4,3) elsewhere).
@@ -240,7 +239,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused_kernel(WinoFusedP
     constexpr int NT = 16 * WM, NC = 16 * WN, NTHR = 64 * WM * WN;
     constexpr int ITEMS = NT * 16 / NTHR;  // (tile, channel) patches a thread transforms per sub-chunk (1 when WN == 4)
     static_assert(NT * 16 % NTHR == 0, "threads must divide the patches of a sub-chunk");
-    constexpr int SUB = 36 * NT * 16;      // floats of one stage image V[xi][tile][16]: 72 KiB at 32 tiles
+    constexpr int SUB = 36 * NT * 16;      // floats of one stage image V[xi][tile][16]: 36 KiB at 16 tiles
     __shared__ __attribute__((aligned(1024))) float lds[2 * SUB];
     constexpr unsigned BAD = 0x40000000u;  // row / column outside the image: pushes the byte offset beyond num_records (< 1 GiB)
 
@@ -368,15 +367,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused_kernel(WinoFusedP
 // different waves the M waves never wait for anything but their own filter stream, the T waves have a whole stage of slack
 // per transform, and the SIMD issues T's VALU work in the shadow of M's MFMAs (one M wave and one T wave per SIMD).
 // One barrier per stage (16 input channels).
-#ifdef FS_TRACE
-// tools/probe_wino_trace.hip only: per-workgroup stamps (shader clock).  [0..15]: M wave 0 -- start, first barrier passed, end of
-// stage 0..7 (as many as there are), [14] epilogue done; [16..31]: T wave 4 -- start, after transform 0, 1, then after each loop transform
-__device__ unsigned long long fs_wino_trace[32 * 16384];
-#define FS_WT(slot) { if (lane == 0 && blockIdx.x < 16384) fs_wino_trace[32 * blockIdx.x + (slot)] = __builtin_readcyclecounter(); }
-#else
-#define FS_WT(slot) {}
-#endif
-
 // The kernel is PERSISTENT: one workgroup per CU walks the (tile block, channel block) pairs blk, blk + gridDim.x, ... (the grid is
 // a multiple of the channel blocks, so a workgroup keeps its channel block and its filter stream), and the T waves' run-ahead
 // crosses the block boundary: while the M waves transform and store the outputs of block i (no MFMA work: ~6 k cycles), the T
@@ -387,7 +377,7 @@ __device__ unsigned long long fs_wino_trace[32 * 16384];
 // -- the T waves' transform (7-9 k cycles per stage; s_setprio on them changes nothing) and the M waves' MFMAs do not overlap.
 // (Built and measured before settling on four M waves x 16 channels: two waves sharing each filter stream through the L1 -- half
 // the L2 traffic -- make the T waves transform two patches per thread and become the critical path, 100 us against 83 on
-// layer0.3; with the loads pipelined it spills.  Workgroup timelines, tools/probe_wino_trace.hip: an M stage takes 5.1 k cycles
+// layer0.3; with the loads pipelined it spills.  Workgroup timelines (a cycle-stamp trace build): an M stage takes 5.1 k cycles
 // for 4.6 k of MFMA issue when the T waves are idle and 6.3-7.4 k while they transform -- the fp32 MFMA runs at the vector rate
 // and the T waves' VALU work does not hide under it.)
 // PD: filter prefetch distance in position pairs; must divide 18 (a pair's slot is pair % PD in every stage).
@@ -479,14 +469,11 @@ __global__ __launch_bounds__(512, 2) void wino4_ws_kernel(WinoFusedParams p) {
             ++done;
             if (++ring == NB) ring = 0;
         };
-        if (wv == 4) FS_WT(16)
         patch_load(0);
         produce();
-        if (wv == 4) FS_WT(17)
         for (int S = 0; S < total; ++S) {
             __syncthreads();  // barrier S: global stage S is complete, the M waves are done with stage S - 1 -> its image may be overwritten
             while (done < total && done < S + NB) produce();
-            if (wv == 4 && S < 12) FS_WT(18 + S)
         }
         return;
     }
@@ -511,12 +498,10 @@ __global__ __launch_bounds__(512, 2) void wino4_ws_kernel(WinoFusedParams p) {
     };
 #pragma unroll
     for (int k = 0; k < PD; ++k) load_b(0, k, k);
-    if (wv == 0) FS_WT(0)
 
     int blk = blockIdx.x, ms = 0, ring = 0;  // block being multiplied, stage inside it, ring image of the global stage
     for (int S = 0; S < total; ++S) {
         __syncthreads();
-        if (wv == 0 && S == 0) FS_WT(1)
         const float* vsrc = lds + ring * SUB + a_off;
         const bool more = S + 1 < total;
         const int ns = ms + 1 == nstages ? 0 : ms + 1;  // the stage after this one: the next block starts at its stage 0 (same filters)
@@ -541,11 +526,9 @@ __global__ __launch_bounds__(512, 2) void wino4_ws_kernel(WinoFusedParams p) {
             else if (more) load_b(ns, k + PD - 18, k % PD);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (wv == 0 && S < 12) FS_WT(2 + S)
         if (++ring == NB) ring = 0;
         if (++ms == nstages) {  // block complete: outputs, then the next block's accumulators start from zero
             wino4_epilogue(acc, p, (blk / ncb) * NT + 4 * q4, n0 + wn * 16 + m16);
-            if (wv == 0 && blk == (int)blockIdx.x) FS_WT(14)
 #pragma unroll
             for (int g = 0; g < 36; ++g) acc[g] = f32x4(0.f);
             ms = 0;
@@ -562,10 +545,12 @@ bool wino_fused_supported(int Cin, int Cout, int KH, int KW, int stride, int pad
     return KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && Cin % 32 == 0 && Cin >= 32 && Cin <= 256 && Cout % 64 == 0;
 }
 
-// variant: 0 = by tile count, 1 = 32 tiles x 64 channels (8 waves), 2 = 16 tiles x 64 channels (4 waves, two workgroups per CU)
+// variant: 0 = by tile count, 2 = 16 tiles x 64 channels (4 waves, two workgroups per CU), 3 = warp-specialised (see above).
+// Variant 1 (32 tiles x 64 channels, 8 waves) was retired; its number is refused, not reused.
 int launch_wino4_fused(const float* in, int ld_in, const float* U, const float* scale, const float* shift, float* out, int ld_out, int B, int H,
                        int W, int Cin, int Cout, int relu, hipStream_t s, int variant) {
     FS_REQUIRE(wino_fused_supported(Cin, Cout, 3, 3, 1, 1, 1), "wino_fused: unsupported shape (Cin=%d Cout=%d)", Cin, Cout);
+    FS_REQUIRE(variant == 0 || variant == 2 || variant == 3, "wino_fused: variant %d is not 0, 2 or 3", variant);
     FS_REQUIRE(ld_in >= Cin && ld_out >= Cout && ((uintptr_t)U & 15) == 0 && ((uintptr_t)in & 3) == 0, "wino_fused: bad strides / alignment");
     FS_REQUIRE((int64_t)B * H * W * ld_in * 4 < (int64_t)1 << 30 && (int64_t)B * H * W * ld_out * 4 < (int64_t)1 << 31,
                "wino_fused: input map must be smaller than 1 GiB, output smaller than 2 GiB");
@@ -584,7 +569,6 @@ int launch_wino4_fused(const float* in, int ld_in, const float* U, const float* 
         const int nblk = cdiv(p.T, 16) * ncb;
         hipLaunchKernelGGL((wino4_ws_kernel<6>), dim3(std::min(nblk, 256 - 256 % ncb)), dim3(512), 0, s, p);
     }
-    else if (variant == 1) hipLaunchKernelGGL((wino4_fused_kernel<2, 4>), dim3(cdiv(p.T, 32) * ncb), dim3(512), 0, s, p);
     else hipLaunchKernelGGL((wino4_fused_kernel<1, 4>), dim3(cdiv(p.T, 16) * ncb), dim3(256), 0, s, p);
     FS_HIP(hipGetLastError());
     return 0;

@@ -67,8 +67,9 @@ typedef struct fs_test_api {
      * F(4x4,3x3) kernel: input transform, the 36 position GEMMs on the fp32 matrix cores and the output transform (+ scale/shift,
      * ReLU) without the Winograd-domain tensors ever reaching HBM (the deep stem's 64-channel convs, conv2 of layer1:
      * model/resnet.py:110-116, 67-69).  workspace: winograd_fused_workspace_floats(Cin, Cout) floats (the packed filter bank, rebuilt by
-     * every call of this test entry; the network builds it once at fs_finalize).  variant: 0 = by workgroup count, 1 = 32 tiles x 64
-     * channels per workgroup, 2 = 16 x 64 (two workgroups per CU), 3 = 16 x 64 warp-specialised; all give bit-identical results. */
+     * every call of this test entry; the network builds it once at fs_finalize).  variant: 0 = by workgroup count, 2 = 16 tiles x 64
+     * channels per workgroup (two workgroups per CU), 3 = 16 x 64 warp-specialised; all give bit-identical results.  1 (a retired
+     * 32 x 64 form) and anything else are refused. */
     size_t (*winograd_fused_workspace_floats)(int Cin, int Cout);
     int (*conv3x3_winograd_fused_nhwc)(const float* in, int ld_in, const float* wgt_oihw, const float* scale, const float* shift, float* out,
                                        int ld_out, int B, int H, int W, int Cin, int Cout, int relu, int variant, float* workspace,

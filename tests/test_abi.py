@@ -110,6 +110,27 @@ def test_conv2d_refuses_every_bit_that_is_not_a_tile_id_or_the_chunk_major_flag(
     assert "fs_trace_buf" not in sym  # the FS_TRACE instrumentation never ships
 
 
+def test_fused_winograd_refuses_the_retired_variant():
+    """Variant 1 of the fused Winograd (32 tiles x 64 channels) is retired: the hook refuses it, and every other number that is not
+    0, 2 or 3, in its argument check -- before the filter-pack launch (dummy non-null pointers: nothing may be launched)."""
+    lib = _lib.load()
+    fake = ctypes.c_void_p(0x1000)
+    for bad in (1, 4, -1):
+        assert lib.fs_conv3x3_winograd_fused_nhwc(fake, 64, fake, None, None, fake, 64, 1, 8, 8, 64, 64, 1, bad, fake, None) != 0, bad
+        assert b"variant" in lib.fs_last_error()
+
+
+def test_fp32_attention_refuses_a_misaligned_or_oversized_qkv():
+    """The fp32 attention route stages K / V with 16-B direct-to-LDS loads at 32-bit offsets: a qkv that is not 16-B aligned, or one
+    image's qkv of 2 GiB or more, is refused in argument validation (dummy pointers: nothing may be launched)."""
+    lib = _lib.load()
+    fake = ctypes.c_void_p(0x1000)
+    assert lib.fs_attention(ctypes.c_void_p(0x1004), fake, 1, 64, 1, 0.125, 0, fake, None) != 0
+    assert b"unaligned" in lib.fs_last_error()
+    assert lib.fs_attention(fake, fake, 1, 1 << 20, 4, 0.125, 0, fake, None) != 0  # 2^20 tokens x 3 x 256 floats = 3 GiB
+    assert b"too large" in lib.fs_last_error()
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "libfloodseg.so"))

@@ -582,7 +582,7 @@ WINO_FUSED_TOL = 3e-5  # F(4x4,3x3) in fp32 at Cin <= 256: measured <= 1e-5 (gpu
     (1, 20, 20, 96, 64, False),      # six K stages (not a power of two)
     (2, 70, 66, 32, 192, True),      # three channel blocks: the persistent form's grid must stay a multiple of 3 (630 blocks on 255 workgroups)
 ])
-@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+@pytest.mark.parametrize("variant", [0, 2, 3])
 def test_winograd_fused_conv3x3(case, variant):
     """The one-kernel Winograd F(4x4,3x3) (wino_fused.hip: transforms and the 36 position GEMMs fused, nothing but the input and
     output maps in HBM) vs torch conv2d + scale/shift (+ReLU): both workgroup shapes, ragged maps, a channel slice of a wider

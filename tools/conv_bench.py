@@ -24,6 +24,20 @@ SHAPES = {  # b, h, w, cin, cout, k, stride, pad, dil
     "aspp12": (2, 90, 90, 2048, 256, 3, 1, 12, 12),
     "aspp24": (2, 90, 90, 2048, 256, 3, 1, 24, 24),
     "aspp36": (2, 90, 90, 2048, 256, 3, 1, 36, 36),
+    # the grouped Winograd GEMMs at B = 2 (36 position groups of T tile rows: l3 / l4 F(4,3), decoder F(6,3)) as ONE 1x1 GEMM of
+    # 36 x T rows -- same K, Cout and FLOPs; the grouped launch has no forced-tile hook
+    "l3wino": (36, 1152, 1, 256, 256, 1, 1, 0, 1),
+    "l4wino": (36, 1152, 1, 512, 512, 1, 1, 0, 1),
+    "decwino": (36, 1058, 1, 2048, 512, 1, 1, 0, 1),
+    # the Segmenter's nn.Linear GEMMs at B = 2 as 1x1 convs over the token rows (ViT-S/16 @704: 3874 rows; ViT-B/32 @704: 970)
+    "s16qkv": (1, 3874, 1, 384, 1152, 1, 1, 0, 1),
+    "s16proj": (1, 3874, 1, 384, 384, 1, 1, 0, 1),
+    "s16fc1": (1, 3874, 1, 384, 1536, 1, 1, 0, 1),
+    "s16fc2": (1, 3874, 1, 1536, 384, 1, 1, 0, 1),
+    "b32qkv": (1, 970, 1, 768, 2304, 1, 1, 0, 1),
+    "b32proj": (1, 970, 1, 768, 768, 1, 1, 0, 1),
+    "b32fc1": (1, 970, 1, 768, 3072, 1, 1, 0, 1),
+    "b32fc2": (1, 970, 1, 3072, 768, 1, 1, 0, 1),
 }
 
 
