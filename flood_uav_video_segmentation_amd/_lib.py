@@ -105,6 +105,15 @@ _HOOKS = [
     ("adaptive_avgpool_nhwc", c_int, [c_void, c_int, c_void, c_int, c_int, c_int, c_int, c_int, c_void]),
     ("nchw_to_nhwc", c_int, [c_void, c_void, c_int, c_int, c_int, c_void]),
     ("nhwc_to_nchw", c_int, [c_void, c_void, c_int, c_int, c_int, c_void]),
+    ("layernorm", c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
+    ("linear_splits", c_int, [c_int] * 5),
+    ("linear", c_int, [c_void] * 6 + [c_int] * 6 + [c_void] * 4 + [c_void]),
+    ("qkv_attention_workspace_floats", ctypes.c_size_t, [c_int] * 3),
+    ("qkv_attention", c_int, [c_void] * 4 + [c_int] * 3 + [c_void, c_void, c_int, c_void, c_void]),
+    ("mask_head", c_int, [c_void] * 5 + [c_int] * 4 + [c_void]),
+    ("patchify", c_int, [c_void, c_void, c_int, c_void, c_int, c_int, c_int, c_int, c_void]),
+    ("vit_assemble", c_int, [c_void] * 4 + [c_int] * 3 + [c_void]),
+    ("dec_assemble", c_int, [c_void] * 3 + [c_int] * 4 + [c_void]),
 ]
 
 

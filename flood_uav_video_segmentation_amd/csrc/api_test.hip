@@ -190,6 +190,91 @@ static int fs_nhwc_to_nchw(const float* in, float* out, int B, int C, int HW, fs
     return fs::launch_nhwc_to_nchw(in, C, out, B, C, HW, S(stream));
 }
 
+// ---- Segmenter pieces: the launchers and the Linear geometry builders the network runs (vit_net.hip), nothing restated here
+static int fs_layernorm(const float* in, const float* gamma, const float* beta, float* out, int rows, int D, int rows_per_batch, int drop_first,
+                        fs_stream stream) {
+    if (!in || !gamma || !beta || !out || rows < 1 || (drop_first && (rows_per_batch < 1 || rows % rows_per_batch != 0)))
+        return fs::fail("fs_layernorm: bad arguments");
+    return fs::launch_layernorm(in, gamma, beta, out, rows, D, rows_per_batch, drop_first, S(stream));
+}
+static int fs_linear_splits(int K, int N, int rows_per_image, int act, int split_route) {
+    if (K < 1 || N < 1 || rows_per_image < 1) return 0;
+    return fs::linear_splits(K, N, rows_per_image, act, split_route != 0);
+}
+static int fs_linear(const float* in, const float* w, const void* w_planes, const float* bias, const float* res, float* out, int rows, int K,
+                     int N, int act, int nsplit, int rows_per_image, float* part, const float* gamma, const float* beta, float* ln_out,
+                     fs_stream stream) {
+    if (!in || !w || !out || rows < 1 || K < 1 || N < 1 || act < 0 || act > 2 || nsplit < 0 || nsplit > 16 || rows_per_image < 0)
+        return fs::fail("fs_linear: bad arguments");
+    const bool ln = gamma || beta || ln_out;
+    if (ln && !(gamma && beta && ln_out)) return fs::fail("fs_linear: the LayerNorm merge needs gamma, beta and ln_out");
+    int split = 0;
+    if (nsplit == 0) split = part ? fs::linear_splits(K, N, rows_per_image ? rows_per_image : rows, act, w_planes != nullptr) : 0;
+    else if (nsplit >= 2) {
+        if (!part || act != 0 || K % (32 * nsplit) != 0)
+            return fs::fail("fs_linear: a forced split-K needs `part`, act 0 and K %% (32 * nsplit) == 0 (K %d, nsplit %d, act %d)", K, nsplit, act);
+        split = nsplit;
+    }
+    if (ln && !split) return fs::fail("fs_linear: the LayerNorm merge runs on split-K launches only");
+    const unsigned plane_bytes = (unsigned)((size_t)N * K * 2);
+    if (split) {
+        fs::ConvParams p = fs::linear_splitk_params(in, w, part, rows, K, N, split);
+        p.wgt3 = w_planes;
+        p.plane_bytes = plane_bytes;
+        if (int rc = fs::launch_conv_igemm(p, S(stream))) return rc;
+        if (ln) return fs::launch_splitk_combine_ln(part, split, bias, res, out, gamma, beta, ln_out, rows, N, S(stream));
+        return fs::launch_splitk_combine(part, split, bias, res, out, rows, N, S(stream));
+    }
+    fs::ConvParams p = fs::linear_params(in, w, bias, res, out, rows, K, N, act, res != nullptr);
+    p.wgt3 = w_planes;
+    p.plane_bytes = plane_bytes;
+    return fs::launch_conv_igemm(p, S(stream));
+}
+static size_t fs_qkv_attention_workspace_floats(int B, int tokens, int D) {
+    if (B < 1 || tokens < 1 || D < 64 || D % 64 != 0) return 0;
+    return fs::attention_split_floats(B, tokens, D / 64) + fs::attention_scratch_floats(B, tokens, D / 64);
+}
+static int fs_qkv_attention(const float* in, const float* w, const void* w_planes, const float* bias, int B, int tokens, int D, float* qkv_out,
+                            float* att_out, int fused, float* workspace, fs_stream stream) {
+    if (!in || !w || !w_planes || !qkv_out || !att_out || !workspace || B < 1 || tokens < 1 || D < 64 || D % 64 != 0 || fused < 0 || fused > 1 ||
+        ((uintptr_t)workspace & 15) != 0)
+        return fs::fail("fs_qkv_attention: bad arguments");
+    if (fused && D % 96 != 0) return fs::fail("fs_qkv_attention: the fused K / V^T epilogue needs D %% 96 == 0 (D %d)", D);
+    const int heads = D / 64;
+    float* planes = workspace;
+    float* scratch = fs::attention_scratch_floats(B, tokens, heads) ? workspace + fs::attention_split_floats(B, tokens, heads) : nullptr;
+    const unsigned plane_bytes = (unsigned)((size_t)3 * D * D * 2);
+    if (fused) {
+        fs::ConvParams p = fs::linear_qkv_params(in, w, bias, qkv_out, B, tokens, D, planes);
+        p.wgt3 = w_planes;
+        p.plane_bytes = plane_bytes;
+        if (int rc = fs::launch_conv_igemm(p, S(stream), 6)) return rc;
+    } else {
+        fs::ConvParams p = fs::linear_params(in, w, bias, nullptr, qkv_out, B * tokens, D, 3 * D, 0, false);
+        p.wgt3 = w_planes;
+        p.plane_bytes = plane_bytes;
+        if (int rc = fs::launch_conv_igemm(p, S(stream))) return rc;
+    }
+    return fs::launch_attention_split(qkv_out, att_out, B, tokens, heads, 0.125f, scratch, planes, S(stream), fused != 0);
+}
+static int fs_mask_head(const float* pp, const float* cc, const float* gamma, const float* beta, float* out, int B, int N, int K, int D,
+                        fs_stream stream) {
+    if (!pp || !cc || !gamma || !beta || !out || B < 1 || N < 1 || D < 4) return fs::fail("fs_mask_head: bad arguments");
+    return fs::launch_mask_head(pp, cc, gamma, beta, out, B, N, K, D, S(stream));
+}
+static int fs_patchify(const float* in, const float* in2, int B1, float* out, int B, int H, int W, int P, fs_stream stream) {
+    if (!out || B < 1 || H < 1 || W < 1 || P < 1) return fs::fail("fs_patchify: bad arguments");
+    return fs::launch_patchify(in, in2, B1, out, B, H, W, P, (H + P - 1) / P, (W + P - 1) / P, S(stream));
+}
+static int fs_vit_assemble(const float* emb, const float* cls, const float* pos, float* X, int B, int N, int D, fs_stream stream) {
+    if (!emb || !cls || !pos || !X || B < 1 || N < 1 || D < 4) return fs::fail("fs_vit_assemble: bad arguments");
+    return fs::launch_vit_assemble(emb, cls, pos, X, B, N, D, S(stream));
+}
+static int fs_dec_assemble(const float* Y, const float* cls_emb, float* Z, int B, int N, int K, int D, fs_stream stream) {
+    if (!Y || !cls_emb || !Z || B < 1 || N < 1 || K < 1 || D < 4) return fs::fail("fs_dec_assemble: bad arguments");
+    return fs::launch_dec_assemble(Y, cls_emb, Z, B, N, K, D, S(stream));
+}
+
 FS_API const fs_test_api* fs_test_hooks(void) {
     static const fs_test_api api = {
         sizeof(fs_test_api),
@@ -210,6 +295,15 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_adaptive_avgpool_nhwc,
         fs_nchw_to_nhwc,
         fs_nhwc_to_nchw,
+        fs_layernorm,
+        fs_linear_splits,
+        fs_linear,
+        fs_qkv_attention_workspace_floats,
+        fs_qkv_attention,
+        fs_mask_head,
+        fs_patchify,
+        fs_vit_assemble,
+        fs_dec_assemble,
     };
     return &api;
 }

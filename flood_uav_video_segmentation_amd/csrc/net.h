@@ -183,6 +183,19 @@ int ws_grow(fs_net* h, float** p, size_t* have, size_t need, bool zero);
 // of a GEMM filter bank; split_use points a launch at them when its `wgt` lies inside a registered bank (no-op otherwise)
 int split_attach(fs_net* h, const float* bank, size_t elems, hipStream_t s);
 void split_use(const fs_net* h, ConvParams& p);
+
+// The launch geometry of the Segmenter's nn.Linear layers (vit_net.hip), shared by the network and the op-level test hooks so that both
+// run the same GEMMs; the caller attaches the split filter bank (split_use, or wgt3 / plane_bytes directly).
+// linear_splits: split-K slice count of a [rows][K] x [K][N] Linear (0 = no split), decided on ONE image's rows.
+int linear_splits(int K, int N, int rows_per_image, int act, bool split_route);
+// out[rows][N] = act(in[rows][K] @ w^T + bias (+ res)), w = [N][K]
+ConvParams linear_params(const float* in, const float* w, const float* bias, const float* res, float* out, int rows, int K, int N, int act,
+                         bool res_touch);
+// split-K: group g multiplies columns g*K/split .. of w's rows into part + g * rows * N (no bias, no residual: the merge adds them)
+ConvParams linear_splitk_params(const float* in, const float* w, float* part, int rows, int K, int N, int split);
+// the qkv Linear with the K / V^T plane epilogue (launch on tile 6): grouped by image, Q columns to out[B * tokens][3D], K planes at
+// `planes`, V^T planes 3 * B * (D / 64) * Npad * 64 bf16 after them (layout of launch_attention_split)
+ConvParams linear_qkv_params(const float* in, const float* w, const float* bias, float* out, int B, int tokens, int D, float* planes);
 int vit_reserve(fs_handle h, int B, int H, int W, hipStream_t s);
 int fetch(fs_net* h, const std::string& name, const RawTensor** out);
 int prof_begin(fs_net* h, const std::string& name, const char* kernel, double flops, double bytes, hipStream_t s);

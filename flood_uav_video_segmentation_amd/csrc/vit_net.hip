@@ -5,6 +5,84 @@
 #include "net.h"
 
 namespace fs {
+
+// A Linear whose 64x64 tiles do not even give every CU two workgroups (ViT-S/16 fc2: 61 x 6 = 366 tiles for 256 CUs, 110 of
+// them with two and the rest with one) while its K is long: cut K into `split` slices -- grouped launch, group g multiplies
+// columns g*K/split .. of the [out][in] weight rows (ConvParams::ld_wgt) into its own partial buffer -- and merge the partials
+// with bias + residual in one small pass.  S/16 fc2 59 -> 4x us (profiles/r02_experiments.txt).  0 = no split.
+int linear_splits(int K, int N, int rows_per_image, int act, bool split_route) {
+    // decided on ONE image's rows (for the usual batch of two key frames: ~768 workgroups), never on the batch: a frame's
+    // result must not depend on the batch it is computed in (the key-frame cache relies on it)
+    if (act != 0 || K < 768) return 0;
+    // the tile the launch will get (conv_igemm.hip::pick_tile): 128 x 96 where 96 divides the columns -- a tile of the split-operand
+    // route only (ADVICE r5: the fp32-MFMA route keeps the 64 x 64 estimate it was fitted with) -- else 64 x 64; aim at two workgroups
+    // per CU for a pair of images
+    const bool t96 = split_route && N % 96 == 0;
+    const long tiles = t96 ? (long)cdiv(rows_per_image, 128) * (N / 96) : (long)cdiv(rows_per_image, 64) * cdiv(N, 64);
+    const long want = t96 ? 256 : 384;
+    int split = (int)std::min<long>(4, (want + tiles / 2) / std::max<long>(tiles, 1));
+    while (split >= 2 && (K % (32 * split) != 0 || K / split < 384)) --split;
+    return split >= 2 ? split : 0;
+}
+
+ConvParams linear_params(const float* in, const float* w, const float* bias, const float* res, float* out, int rows, int K, int N, int act,
+                         bool res_touch) {
+    ConvParams p{};
+    p.in = in;
+    p.ld_in = K;
+    p.wgt = w;
+    p.scale = nullptr;
+    p.shift = bias;
+    p.res = res;
+    p.ld_res = N;
+    p.out = out;
+    p.ld_out = N;
+    p.B = 1;
+    p.H = rows;
+    p.W = 1;
+    p.Cin = K;
+    p.Ho = rows;
+    p.Wo = 1;
+    p.Cout = N;
+    p.KH = p.KW = 1;
+    p.stride = 1;
+    p.pad = 0;
+    p.dil = 1;
+    p.relu = act;
+    p.res_touch = res_touch;
+    return p;
+}
+
+ConvParams linear_splitk_params(const float* in, const float* w, float* part, int rows, int K, int N, int split) {
+    ConvParams p{};
+    p.in = in; p.ld_in = K; p.wgt = w; p.ld_wgt = K; p.out = part; p.ld_out = N;
+    p.B = 1; p.H = rows; p.W = 1; p.Cin = K / split; p.Ho = rows; p.Wo = 1; p.Cout = N;
+    p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
+    p.groups = split;
+    p.g_in = K / split;
+    p.g_wgt = K / split;
+    p.g_out = (long long)rows * N;
+    return p;
+}
+
+ConvParams linear_qkv_params(const float* in, const float* w, const float* bias, float* out, int B, int tokens, int D, float* planes) {
+    const int heads = D / 64, Npad = (tokens + 31) / 32 * 32;
+    const size_t plane_elems = (size_t)B * heads * Npad * 64;
+    ConvParams p{};
+    p.in = in; p.ld_in = D; p.wgt = w; p.shift = bias; p.out = out; p.ld_out = 3 * D;
+    p.B = 1; p.H = tokens; p.W = 1; p.Cin = D; p.Ho = tokens; p.Wo = 1; p.Cout = 3 * D;
+    p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
+    p.groups = B;
+    p.g_in = (long long)tokens * D;
+    p.g_wgt = 0;
+    p.g_out = (long long)tokens * 3 * D;
+    p.kv_k = reinterpret_cast<unsigned short*>(planes);
+    p.kv_vt = p.kv_k + 3 * plane_elems;
+    p.kv_N = tokens; p.kv_Npad = Npad; p.kv_heads = heads;
+    p.kv_plane_bytes = (unsigned)(plane_elems * 2);
+    return p;
+}
+
 namespace {
 
 int copy_param(fs_net* h, const std::string& name, int64_t expect, float** dst) {
@@ -44,41 +122,15 @@ int make_block(fs_net* h, VitBlock& b, const std::string& p, int D, hipStream_t 
     return 0;
 }
 
-// A Linear whose 64x64 tiles do not even give every CU two workgroups (ViT-S/16 fc2: 61 x 6 = 366 tiles for 256 CUs, 110 of
-// them with two and the rest with one) while its K is long: cut K into `split` slices -- grouped launch, group g multiplies
-// columns g*K/split .. of the [out][in] weight rows (ConvParams::ld_wgt) into its own partial buffer -- and merge the partials
-// with bias + residual in one small pass.  S/16 fc2 59 -> 4x us (profiles/r02_experiments.txt).  0 = no split.
-int linear_splits(const Linear& l, int rows_per_image, int act, bool split_route) {
-    // decided on ONE image's rows (for the usual batch of two key frames: ~768 workgroups), never on the batch: a frame's
-    // result must not depend on the batch it is computed in (the key-frame cache relies on it)
-    if (act != 0 || l.in < 768) return 0;
-    // the tile the launch will get (conv_igemm.hip::pick_tile): 128 x 96 where 96 divides the columns -- a tile of the split-operand
-    // route only (ADVICE r5: the fp32-MFMA route keeps the 64 x 64 estimate it was fitted with) -- else 64 x 64; aim at two workgroups
-    // per CU for a pair of images
-    const bool t96 = split_route && l.out % 96 == 0;
-    const long tiles = t96 ? (long)cdiv(rows_per_image, 128) * (l.out / 96) : (long)cdiv(rows_per_image, 64) * cdiv(l.out, 64);
-    const long want = t96 ? 256 : 384;
-    int split = (int)std::min<long>(4, (want + tiles / 2) / std::max<long>(tiles, 1));
-    while (split >= 2 && (l.in % (32 * split) != 0 || l.in / split < 384)) --split;
-    return split >= 2 ? split : 0;
-}
-
 // out[rows][l.out] = act(in[rows][l.in] @ W^T + b (+ res))
 // ln / ln_out: when the Linear is split-K, the merge pass also writes LayerNorm(ln)(out) into ln_out (the next block's norm1) and
 // *ln_done is set; otherwise the caller runs that LayerNorm itself.
 int run_linear(fs_net* h, const Linear& l, const float* in, int rows, float* out, const float* res, int act, hipStream_t s, float* part = nullptr,
                int rows_per_image = 0, const LNorm* ln = nullptr, float* ln_out = nullptr, bool* ln_done = nullptr) {
-    const int split = part ? linear_splits(l, rows_per_image ? rows_per_image : rows, act, h->use_split) : 0;
+    const int split = part ? linear_splits(l.in, l.out, rows_per_image ? rows_per_image : rows, act, h->use_split) : 0;
     if (ln_done) *ln_done = false;
     if (split) {
-        ConvParams p{};
-        p.in = in; p.ld_in = l.in; p.wgt = l.w; p.ld_wgt = l.in; p.out = part; p.ld_out = l.out;
-        p.B = 1; p.H = rows; p.W = 1; p.Cin = l.in / split; p.Ho = rows; p.Wo = 1; p.Cout = l.out;
-        p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
-        p.groups = split;
-        p.g_in = l.in / split;
-        p.g_wgt = l.in / split;
-        p.g_out = (long long)rows * l.out;
+        ConvParams p = linear_splitk_params(in, l.w, part, rows, l.in, l.out, split);
         split_use(h, p);
         const double flops = 2.0 * rows * (double)l.in * l.out;
         FS_TRY(prof_begin(h, l.name, conv_igemm_tile_name(p), flops, 4.0 * ((double)rows * (l.in + (split + 1.0) * l.out) + (double)l.in * l.out), s));
@@ -91,29 +143,7 @@ int run_linear(fs_net* h, const Linear& l, const float* in, int rows, float* out
         }
         return prof_end(h, s);
     }
-    ConvParams p{};
-    p.in = in;
-    p.ld_in = l.in;
-    p.wgt = l.w;
-    p.scale = nullptr;
-    p.shift = l.b;
-    p.res = res;
-    p.ld_res = l.out;
-    p.out = out;
-    p.ld_out = l.out;
-    p.B = 1;
-    p.H = rows;
-    p.W = 1;
-    p.Cin = l.in;
-    p.Ho = rows;
-    p.Wo = 1;
-    p.Cout = l.out;
-    p.KH = p.KW = 1;
-    p.stride = 1;
-    p.pad = 0;
-    p.dil = 1;
-    p.relu = act;
-    p.res_touch = res != nullptr && h->res_touch;
+    ConvParams p = linear_params(in, l.w, l.b, res, out, rows, l.in, l.out, act, res != nullptr && h->res_touch);
     split_use(h, p);
     const double flops = 2.0 * rows * (double)l.in * l.out;
     FS_TRY(prof_begin(h, l.name, conv_igemm_tile_name(p), flops, 4.0 * ((double)rows * (l.in + l.out) + (double)l.in * l.out), s));
@@ -124,20 +154,7 @@ int run_linear(fs_net* h, const Linear& l, const float* in, int rows, float* out
 // qkv = in @ W^T + b for B images of `tokens` rows, grouped by image; the Q columns go to out[rows][3D] as fp32, the K and V columns to the
 // attention's operand planes (layout of launch_attention_split: K planes, then V^T planes, keys padded to a multiple of 32)
 int run_linear_qkv(fs_net* h, const Linear& l, const float* in, int B, int tokens, float* out, float* planes, hipStream_t s) {
-    const int D = l.in, heads = D / 64, Npad = (tokens + 31) / 32 * 32;
-    const size_t plane_elems = (size_t)B * heads * Npad * 64;
-    ConvParams p{};
-    p.in = in; p.ld_in = l.in; p.wgt = l.w; p.shift = l.b; p.out = out; p.ld_out = l.out;
-    p.B = 1; p.H = tokens; p.W = 1; p.Cin = l.in; p.Ho = tokens; p.Wo = 1; p.Cout = l.out;
-    p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
-    p.groups = B;
-    p.g_in = (long long)tokens * l.in;
-    p.g_wgt = 0;
-    p.g_out = (long long)tokens * l.out;
-    p.kv_k = reinterpret_cast<unsigned short*>(planes);
-    p.kv_vt = p.kv_k + 3 * plane_elems;
-    p.kv_N = tokens; p.kv_Npad = Npad; p.kv_heads = heads;
-    p.kv_plane_bytes = (unsigned)(plane_elems * 2);
+    ConvParams p = linear_qkv_params(in, l.w, l.b, out, B, tokens, l.in, planes);
     split_use(h, p);
     FS_REQUIRE(p.wgt3, "segmenter: the fused qkv epilogue needs the split filter bank");
     const double rows = (double)B * tokens;

@@ -109,6 +109,24 @@ int launch_dec_assemble(const float* Y, const float* cls_emb, float* Z, int B, i
 }
 
 // ------------------------------------------------------------------ LayerNorm: one wave per row, D <= 1024
+// Sum of (x - mean)^2 over the valid chunks of a row, with every rounding written out: fma(d0, d0, d1 * d1), then one fma per further
+// element, chunk after chunk.  layernorm_kernel and splitk_combine_ln_kernel must produce the same float from it whatever NI they are
+// instantiated with (the merge + LayerNorm pass is bit-identical to the two launches it replaces).  Left to the compiler's mul / add
+// contraction, NI = 2..4 compiled to exactly this chain while NI = 1 got packed multiplies and separate adds: 1 ulp off for D <= 256.
+template <int NI>
+__device__ __forceinline__ float ln_sq_sum(const f32x4 (&v)[NI], float mean, int lane, int D4) {
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {  // element by element into ONE running sum, valid chunks only (as the round-1 kernel did)
+        const bool ok = lane + 64 * i < D4;
+        const float d0 = v[i][0] - mean, d1 = v[i][1] - mean, d2 = v[i][2] - mean, d3 = v[i][3] - mean;
+        float c = i == 0 ? __builtin_fmaf(d0, d0, d1 * d1) : __builtin_fmaf(d1, d1, __builtin_fmaf(d0, d0, sq));
+        c = __builtin_fmaf(d3, d3, __builtin_fmaf(d2, d2, c));
+        sq = ok ? c : sq;
+    }
+    return sq;
+}
+
 // NI = chunks of 64 float4 a row has.  Everything a row needs -- its values, gamma, beta -- is requested before anything is used
 // (round 6: the gamma / beta loads sat behind the two reductions, a second memory round trip in a kernel that is one round trip
 // long); lanes past the row's end load from clamped addresses and contribute exact zeros, as before.
@@ -151,16 +169,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
     const float mean = sum / (float)(D4 * 4);
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {  // element by element into ONE running sum, valid chunks only (as the round-1 kernel did)
-        const bool ok = lane + 64 * i < D4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = v[i][e] - mean;
-            sq = ok ? sq + d * d : sq;
-        }
-    }
+    float sq = ln_sq_sum<NI>(v, mean, lane, D4);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
     const float rstd = 1.f / sqrtf(sq / (float)(D4 * 4) + 1e-5f);
@@ -170,7 +179,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         const int c = lane + 64 * i;
         f32x4 r;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = (v[i][e] - mean) * rstd * g[i][e] + bt[i][e];
+        for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf((v[i][e] - mean) * rstd, g[i][e], bt[i][e]);
         if (c < D4) y[c] = r;
     }
 }
@@ -852,16 +861,7 @@ __global__ __launch_bounds__(256) void splitk_combine_ln_kernel(const float* __r
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
     const float mean = sum / (float)(D4 * 4);
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const bool ok = lane + 64 * i < D4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = v[i][e] - mean;
-            sq = ok ? sq + d * d : sq;
-        }
-    }
+    float sq = ln_sq_sum<NI>(v, mean, lane, D4);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
     const float rstd = 1.f / sqrtf(sq / (float)(D4 * 4) + 1e-5f);
@@ -872,7 +872,7 @@ __global__ __launch_bounds__(256) void splitk_combine_ln_kernel(const float* __r
         if (c < D4) {
             f32x4 r;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = (v[i][e] - mean) * rstd * g[i][e] + bt[i][e];
+            for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf((v[i][e] - mean) * rstd, g[i][e], bt[i][e]);
             y[c] = r;
         }
     }

@@ -1,6 +1,7 @@
 /*
  * floodseg_test.h -- op-level hooks of libfloodseg.so: the building blocks behind the networks (implicit-GEMM conv, Winograd forms,
- * stem, pooling, attention, layout copies), for the parity tests (tests/test_gpu_ops.py) and the measurement tools (tools/).
+ * stem, pooling, attention, layout copies, and the Segmenter's LayerNorm, Linear / split-K merges, qkv + attention, mask head, patchify
+ * and token assembly), for the parity tests (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py) and the measurement tools (tools/).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table is append-only; `size` is sizeof(fs_test_api) of the library that was built, so a
@@ -90,6 +91,42 @@ typedef struct fs_test_api {
     int (*adaptive_avgpool_nhwc)(const float* in, int ld_in, float* out, int B, int H, int W, int C, int bin, fs_stream stream);
     int (*nchw_to_nhwc)(const float* in, float* out, int B, int C, int HW, fs_stream stream);
     int (*nhwc_to_nchw)(const float* in, float* out, int B, int C, int HW, fs_stream stream);
+
+    /* ---- Segmenter pieces (csrc/vit_ops.hip, vit_net.hip): the launchers and the Linear geometry the network itself runs.  Token
+     * matrices are row-major [rows][D] fp32; weights of a Linear are [N][K] as torch stores them. */
+    /* nn.LayerNorm(D) per row, eps 1e-5; 4 <= D <= 1024, D % 4 == 0.  drop_first != 0: rows = B * rows_per_batch and row 0 of every batch
+     * (the cls token) is left out of `out`, which then holds B * (rows_per_batch - 1) rows in order (the encoder's final norm). */
+    int (*layernorm)(const float* in, const float* gamma, const float* beta, float* out, int rows, int D, int rows_per_batch, int drop_first,
+                     fs_stream stream);
+    /* the split-K slice count the network chooses for a Linear (0 = none) from ONE image's rows; split_route: the split-operand filters */
+    int (*linear_splits)(int K, int N, int rows_per_image, int act, int split_route);
+    /* out[rows][N] = act(in[rows][K] @ w^T + bias (+ res)), act 0 / 1 (ReLU) / 2 (GELU); K % 32 == 0.  w_planes: split_bf16x3 of w (the
+     * split-operand route), or NULL (fp32 matrix cores).  nsplit: 0 = the network's choice (linear_splits(K, N, rows_per_image or rows,
+     * act, w_planes != NULL), only when `part` is given), 1 = no split, >= 2 (<= 16) = split-K forced (act 0, K % (32 nsplit) == 0).
+     * part: nsplit * rows * N floats of partial products.  gamma / beta / ln_out (all or none, split-K only): the merge also writes
+     * LayerNorm(gamma, beta) of `out` into ln_out (splitk_combine_ln, N <= 1024). */
+    int (*linear)(const float* in, const float* w, const void* w_planes, const float* bias, const float* res, float* out, int rows, int K,
+                  int N, int act, int nsplit, int rows_per_image, float* part, const float* gamma, const float* beta, float* ln_out,
+                  fs_stream stream);
+    /* The first half of a transformer block on the split-operand route: qkv_out[B * tokens][3D] = in @ w^T + bias, then multi-head
+     * attention (head_dim 64, scale 1/8) into att_out[B * tokens][D].  fused = 1: the qkv Linear's epilogue writes the attention's K / V^T
+     * operand planes (D % 96 == 0); 0: the plain Linear and the attention's own pre-pass.  workspace (16-B aligned):
+     * qkv_attention_workspace_floats(B, tokens, D) floats; at byte 0 the K planes, bf16 [3][B * heads][Npad][64], then the V^T planes,
+     * bf16 [3][B * heads][64][Npad] (Npad = tokens rounded up to 32; keys tokens .. Npad-1 are zeros), then the key-split scratch. */
+    size_t (*qkv_attention_workspace_floats)(int B, int tokens, int D);
+    int (*qkv_attention)(const float* in, const float* w, const void* w_planes, const float* bias, int B, int tokens, int D, float* qkv_out,
+                         float* att_out, int fused, float* workspace, fs_stream stream);
+    /* decoder mask head: pp, cc = [B][N + K][D]; out[b][k][i] = LayerNorm_K(<pp[b][i] / |pp[b][i]|, cc[b][N + k] / |cc[b][N + k]|>) (eps 1e-5),
+     * NCHW; 1 <= K <= 64, D % 4 == 0, D <= 1024 */
+    int (*mask_head)(const float* pp, const float* cc, const float* gamma, const float* beta, float* out, int B, int N, int K, int D,
+                     fs_stream stream);
+    /* zero-padded (right / bottom) P x P patches of NCHW frames -> [B * ceil(H/P) * ceil(W/P)][3 P P], columns (c, py, px); images
+     * 0 .. B1-1 from in, B1 .. B-1 from in2 */
+    int (*patchify)(const float* in, const float* in2, int B1, float* out, int B, int H, int W, int P, fs_stream stream);
+    /* X[b][0] = cls + pos[0], X[b][1 + i] = emb[b * N + i] + pos[1 + i]; D % 4 == 0 */
+    int (*vit_assemble)(const float* emb, const float* cls, const float* pos, float* X, int B, int N, int D, fs_stream stream);
+    /* Z[b][i < N] = Y[b * N + i], Z[b][N + k] = cls_emb[k]; D % 4 == 0 */
+    int (*dec_assemble)(const float* Y, const float* cls_emb, float* Z, int B, int N, int K, int D, fs_stream stream);
 } fs_test_api;
 
 const fs_test_api* fs_test_hooks(void);

@@ -80,6 +80,31 @@ def test_small_segmenters_against_oracle(cfg):
         VITSegmentModel(5, cfg["image_size"], hip_att_pipelined=True)  # a retired / mistyped option is refused, not ignored
 
 
+@pytest.mark.parametrize("cfg", [dict(d_model=64, classes=1, n_layers=2, dec_layers=1, size=64, b=2),
+                                 dict(d_model=192, classes=19, n_layers=1, dec_layers=2, size=70, b=1),
+                                 dict(d_model=576, classes=64, n_layers=2, dec_layers=1, size=64, b=3),
+                                 dict(d_model=1024, classes=19, n_layers=1, dec_layers=1, size=80, b=2)])
+def test_segmenter_widths_and_class_counts_against_oracle(cfg):
+    """Dispatch branches the shipped widths (384 / 768, K = 5) never take: one head (d_model 64), odd head counts on the fused qkv
+    epilogue (192: 3 heads, 576: 9), 16 heads and LayerNorm with four full chunks (1024, whose fc2 with K = 4096 runs split-K and the
+    merge + LayerNorm at that width); K = 1 (the mask LayerNorm's variance is 0: every logit is the bias), 19 and 64 classes (every lane of
+    the mask head).  Encoder tokens at TOKEN_TOL, logits at VIT_TOL."""
+    D, K, P = cfg["d_model"], cfg["classes"], 16
+    state = synth.make_vit_state(K, 64, P, D, cfg["n_layers"], cfg["dec_layers"], seed=D + K)
+    net = VITSegmentModel(K, 64, patch_size=P, d_model=D, n_layers=cfg["n_layers"], dec_layers=cfg["dec_layers"]).eval()
+    net.load_state_dict(state)
+    x = synth.make_clip(cfg["b"], cfg["size"], seed=D)
+    g = -(-cfg["size"] // P)
+    xp = torch.nn.functional.pad(x, (0, g * P - cfg["size"], 0, g * P - cfg["size"]))
+    tok = net.encoder(x.cuda()).permute(0, 2, 3, 1).reshape(cfg["b"], g * g, D)
+    ref_tok = vit_oracle.encoder_tokens(xp, state, P, cfg["n_layers"], 64)[:, 1:]
+    assert note(f"vit_d{D}_k{K}_tokens_vs_oracle", rel_err(tok.cpu(), ref_tok)) < TOKEN_TOL
+    got = net(x.cuda())["pred"]
+    ref = vit_oracle.forward(x, state, P, cfg["n_layers"], cfg["dec_layers"], 64, K)["pred"]
+    assert got.shape == ref.shape == (cfg["b"], K, cfg["size"], cfg["size"])
+    assert note(f"vit_d{D}_k{K}_logits_vs_oracle", rel_err(got.cpu(), ref)) < VIT_TOL
+
+
 def test_vit_feature_flow_extension_against_oracle_parity_unpinned():
     """BASELINE configs[3] semantics: key-frame ViT + feature-based propagation.  The reference has no such path
     (flow/base.py:94-103 returns None for arch == 'vit'), so this is OUR definition -- token map [B,D,gh,gw] through
