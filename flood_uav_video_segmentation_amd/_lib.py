@@ -114,6 +114,17 @@ _HOOKS = [
     ("patchify", c_int, [c_void, c_void, c_int, c_void, c_int, c_int, c_int, c_int, c_void]),
     ("vit_assemble", c_int, [c_void] * 4 + [c_int] * 3 + [c_void]),
     ("dec_assemble", c_int, [c_void] * 3 + [c_int] * 4 + [c_void]),
+    ("concat_scaled_filters", c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_void, c_int, c_void, c_void, c_int, c_void]),
+    ("pack_slice_tap_major", c_int, [c_void, c_void] + [c_int] * 5 + [c_void]),
+    ("dual_conv", c_int, [c_void, c_int, c_void, c_int, c_void, c_void, c_void, c_void] + [c_int] * 12 + [c_void]),
+    ("pyramid_pool", c_int, [c_void, c_int, c_void] + [c_int] * 4 + [c_void]),
+    ("rowdot_batch", c_int, [c_int] + [c_void] * 6 + [c_int] * 5 + [c_void]),
+    ("upsample_into", c_int, [c_void, c_int, c_int, c_void] + [c_int] * 6 + [c_void]),
+    ("classifier_nchw", c_int, [c_void, c_int, c_void, c_void, c_void] + [c_int] * 4 + [c_void]),
+    ("ppm_term_scratch_floats", ctypes.c_size_t, [c_int] * 3),
+    ("ppm_term_classify", c_int, [c_void, c_int] + [c_void] * 7 + [c_int] * 5 + [c_void] * 3 + [c_int, c_void, c_void]),
+    ("ppm_head_workspace_floats", ctypes.c_size_t, [c_int] * 3),
+    ("ppm_head", c_int, [c_void, c_int, c_void, c_int] + [c_void] * 5 + [c_int] * 5 + [c_void] * 3 + [c_int, c_void, c_void]),
 ]
 
 

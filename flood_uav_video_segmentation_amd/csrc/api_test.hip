@@ -275,6 +275,88 @@ static int fs_dec_assemble(const float* Y, const float* cls_emb, float* Z, int B
     return fs::launch_dec_assemble(Y, cls_emb, Z, B, N, K, D, S(stream));
 }
 
+// ---- CNN heads and projection shortcut: the launchers and the geometry builders of net.h that net.hip itself calls
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int fs_concat_scaled_filters(const float* wa, const float* sa, const float* ha, int Ka, const float* wb, const float* sb, const float* hb, int Kb,
+                                    float* out, float* shift_out, int O, fs_stream stream) {
+    return fs::launch_concat_scaled_filters(wa, sa, ha, Ka, wb, sb, hb, Kb, out, shift_out, O, S(stream));  // validates its arguments itself
+}
+static int fs_pack_slice_tap_major(const float* oihw, float* out, int O, int I, int c0, int nc, int taps, fs_stream stream) {
+    if (!oihw || !out || O < 1 || I < 1 || taps < 1) return fs::fail("fs_pack_slice_tap_major: bad arguments");
+    return fs::launch_pack_slice_tap_major(oihw, out, O, I, c0, nc, taps, S(stream));
+}
+static int fs_dual_conv(const float* a, int ld_a, const float* b, int ld_b, const float* wgt, const void* wgt_planes, const float* shift, float* out,
+                        int ld_out, int B, int Ho, int Wo, int Cin, int Cin2, int H2, int W2, int stride2, int Cout, int relu, int tile,
+                        fs_stream stream) {
+    if (!a || !b || (!wgt && !wgt_planes) || !out || B < 1 || Ho < 1 || Wo < 1 || H2 < 1 || W2 < 1 || Cin < 32 || Cin2 < 32 || Cout < 1 || stride2 < 1 ||
+        relu < 0 || relu > 2)
+        return fs::fail("fs_dual_conv: bad arguments");
+    if (tile < 0 || tile > 2) return fs::fail("fs_dual_conv: tile must be 0, 1 or 2 (got %d): the concatenated-K kernels have the two 128-row tiles", tile);
+    fs::ConvParams p = fs::dual_conv_params(a, ld_a, b, ld_b, wgt, shift, out, ld_out, B, Ho, Wo, Cin, Cin2, H2, W2, stride2, Cout, relu);
+    p.wgt3 = wgt_planes;
+    p.plane_bytes = (unsigned)((size_t)Cout * ((size_t)Cin + Cin2) * 2);
+    return fs::launch_conv_igemm(p, S(stream), tile);
+}
+static int fs_pyramid_pool(const float* in, int ld_in, float* out, int B, int H, int W, int C, fs_stream stream) {
+    if (!in || !out || B < 1 || B > 65535 || H < 1 || W < 1 || C < 32 || C % 32 != 0 || ld_in < C || ld_in % 4 != 0 || !al16(in) || !al16(out))
+        return fs::fail("fs_pyramid_pool: bad arguments (C %% 32 == 0, ld_in >= C, ld_in %% 4 == 0, 16-B aligned maps)");
+    const int bins[4] = {1, 2, 3, 6};
+    return fs::pyramid_pool(nullptr, in, ld_in, out, B, H, W, C, bins, S(stream));
+}
+static int fs_rowdot_batch(int nprob, const float* const* in, const float* const* wgt, const float* const* scale, const float* const* shift,
+                           float* const* out, const int* M, int ld_in, int ld_out, int K, int N, int relu, fs_stream stream) {
+    if (nprob < 1 || nprob > 4 || !in || !wgt || !out || !M || K < 1 || N < 1 || ld_in < K || ld_in % 4 != 0 || ld_out < N)
+        return fs::fail("fs_rowdot_batch: bad arguments (1..4 problems, ld_in >= K, ld_in %% 4 == 0, ld_out >= N)");
+    fs::RowdotBatch pb{};
+    for (int i = 0; i < nprob; ++i) {
+        if (!in[i] || !wgt[i] || !out[i] || M[i] < 1 || !al16(in[i]) || !al16(wgt[i])) return fs::fail("fs_rowdot_batch: bad problem %d", i);
+        pb.p[i] = fs::RowdotProblem{in[i], wgt[i], scale ? scale[i] : nullptr, shift ? shift[i] : nullptr, out[i], M[i]};
+    }
+    return fs::launch_rowdot_1x1_batch(pb, nprob, ld_in, ld_out, K, N, relu, S(stream));
+}
+static int fs_upsample_into(const float* in, int hi, int wi, float* out, int ld_out, int B, int Ho, int Wo, int C, int align_corners, fs_stream stream) {
+    if (!in || !out || hi < 1 || wi < 1 || B < 1 || Ho < 1 || Wo < 1 || C < 4 || ld_out < C || align_corners < 0 || align_corners > 1 || !al16(in))
+        return fs::fail("fs_upsample_into: bad arguments");
+    return fs::launch_upsample_into(in, hi, wi, out, ld_out, B, Ho, Wo, C, align_corners, S(stream));
+}
+static int fs_classifier_nchw(const float* in, int ld_in, const float* wgt, const float* bias, float* out, int B, int HW, int C, int K, fs_stream stream) {
+    if (!in || !wgt || !out || B < 1 || HW < 1 || C < 4 || K < 1 || ld_in < C || !al16(in)) return fs::fail("fs_classifier_nchw: bad arguments");
+    return fs::launch_classifier_nchw(in, ld_in, wgt, bias, out, B, HW, C, K, S(stream));
+}
+static int ppm_head_args(const char* what, const float* T, int ld, const int* bins, const float* scale, const float* shift, int B, int H, int W, int C,
+                         const float* cls_w, float* logits, int K, const float* scratch) {
+    if (!T || !bins || !cls_w || !logits || !scratch || B < 1 || H < 1 || W < 1 || C < 4 || K < 1 || ld < C || !al16(scale) || !al16(shift) || !al16(scratch))
+        return fs::fail("%s: bad arguments", what);
+    return 0;
+}
+static size_t fs_ppm_term_scratch_floats(int B, int H, int C) { return B < 1 || H < 1 || C < 1 ? 0 : fs::ppm_term_scratch_floats(B, H, C); }
+static int fs_ppm_term_classify(const float* T, int ld, const float* z1, const float* z2, const float* z3, const float* z6, const int* bins,
+                                const float* scale, const float* shift, int B, int H, int W, int C, int relu, const float* cls_w, const float* cls_b,
+                                float* logits, int K, float* scratch, fs_stream stream) {
+    if (int rc = ppm_head_args("fs_ppm_term_classify", T, ld, bins, scale, shift, B, H, W, C, cls_w, logits, K, scratch)) return rc;
+    const float* Z[4] = {z1, z2, z3, z6};
+    return fs::launch_ppm_term_classify(T, ld, Z, bins, scratch, scale, shift, B, H, W, C, relu, cls_w, cls_b, logits, K, S(stream));
+}
+static size_t fs_ppm_head_workspace_floats(int B, int H, int C) {
+    return B < 1 || H < 1 || C < 1 ? 0 : (size_t)4 * B * 36 * 9 * C + fs::ppm_term_scratch_floats(B, H, C);
+}
+static int fs_ppm_head(const float* T, int ld, const float* reduced, int Cr, const float* zw, const void* zw_planes, const int* bins, const float* scale,
+                       const float* shift, int B, int H, int W, int C, int relu, const float* cls_w, const float* cls_b, float* logits, int K,
+                       float* workspace, fs_stream stream) {
+    if (int rc = ppm_head_args("fs_ppm_head", T, ld, bins, scale, shift, B, H, W, C, cls_w, logits, K, workspace)) return rc;
+    if (!reduced || !zw || Cr < 32 || Cr % 32 != 0) return fs::fail("fs_ppm_head: bad reduced maps / filter bank (Cr %% 32 == 0 required, got %d)", Cr);
+    for (int i = 0; i < 4; ++i)
+        if (bins[i] < 1 || bins[i] > 6) return fs::fail("fs_ppm_head: a level's slot holds 36 cells (bin %d)", bins[i]);
+    float* zbuf = workspace;
+    fs::ConvParams p = fs::ppm_z_params(reduced, zw, zbuf, B, Cr, 9 * C);
+    p.wgt3 = zw_planes;
+    p.plane_bytes = (unsigned)((size_t)4 * 9 * C * Cr * 2);
+    if (int rc = fs::launch_conv_igemm(p, S(stream))) return rc;
+    const float* Z[4];
+    for (int i = 0; i < 4; ++i) Z[i] = zbuf + (size_t)i * p.g_out;
+    return fs::launch_ppm_term_classify(T, ld, Z, bins, zbuf + (size_t)4 * p.g_out, scale, shift, B, H, W, C, relu, cls_w, cls_b, logits, K, S(stream));
+}
+
 FS_API const fs_test_api* fs_test_hooks(void) {
     static const fs_test_api api = {
         sizeof(fs_test_api),
@@ -304,6 +386,17 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_patchify,
         fs_vit_assemble,
         fs_dec_assemble,
+        fs_concat_scaled_filters,
+        fs_pack_slice_tap_major,
+        fs_dual_conv,
+        fs_pyramid_pool,
+        fs_rowdot_batch,
+        fs_upsample_into,
+        fs_classifier_nchw,
+        fs_ppm_term_scratch_floats,
+        fs_ppm_term_classify,
+        fs_ppm_head_workspace_floats,
+        fs_ppm_head,
     };
     return &api;
 }

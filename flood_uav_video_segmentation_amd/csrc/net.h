@@ -196,6 +196,18 @@ ConvParams linear_splitk_params(const float* in, const float* w, float* part, in
 // the qkv Linear with the K / V^T plane epilogue (launch on tile 6): grouped by image, Q columns to out[B * tokens][3D], K planes at
 // `planes`, V^T planes 3 * B * (D / 64) * Npad * 64 bf16 after them (layout of launch_attention_split)
 ConvParams linear_qkv_params(const float* in, const float* w, const float* bias, float* out, int B, int tokens, int D, float* planes);
+// The launch geometry of the CNN pieces that net.hip used to fill inline, shared with the op-level test hooks in the same way.
+// conv3 + projection shortcut of a bottleneck as one launch over the concatenated K (encoder_core): out = act(a (x) W[:, :Cin] +
+// b[::stride2, ::stride2] (x) W[:, Cin:] + shift) for a = [B][Ho][Wo][Cin], b = [B][H2][W2][Cin2], W from launch_concat_scaled_filters
+ConvParams dual_conv_params(const float* a, int ld_a, const float* b, int ld_b, const float* wgt, const float* shift, float* out, int ld_out, int B,
+                            int Ho, int Wo, int Cin, int Cin2, int H2, int W2, int stride2, int Cout, int relu);
+// the fused PSPNet head's Z GEMM (net_segment): four groups (pyramid levels) of [B * 36 rows] x [Cout9 = 9 * O] x Cr; level i reads
+// reduced + i * B * 36 * Cr (its B * bin^2 real rows first), multiplies zw + i * Cout9 * Cr and writes zbuf + i * B * 36 * Cout9
+ConvParams ppm_z_params(const float* reduced, const float* zw, float* zbuf, int B, int Cr, int Cout9);
+// Pooling half of the pyramid (pyramid_reduce): AdaptiveAvgPool2d(bins) of a C-channel NHWC map into `pooled`, the levels back to back
+// ([B][bin^2][C] each); one pass + ppm_pool_combine when H and W are multiples of 6 and the bins are 1, 2, 3, 6, four pooling launches
+// otherwise.  h: the handle whose profile the launches are recorded in, or nullptr.
+int pyramid_pool(fs_net* h, const float* feat, int ld_feat, float* pooled, int B, int H, int W, int C, const int bins[4], hipStream_t s);
 int vit_reserve(fs_handle h, int B, int H, int W, hipStream_t s);
 int fetch(fs_net* h, const std::string& name, const RawTensor** out);
 int prof_begin(fs_net* h, const std::string& name, const char* kernel, double flops, double bytes, hipStream_t s);

@@ -386,7 +386,11 @@ int net_create(const fs_config* cfg, fs_handle* out) {
                "fs_create: unknown arch %d", cfg->arch);
     FS_REQUIRE(cfg->arch == FS_ARCH_SEGMENTER || cfg->layers == 50 || cfg->layers == 101 || cfg->layers == 152,
                "fs_create: layers must be 50, 101 or 152");
-    FS_REQUIRE(cfg->classes >= 1 && cfg->classes <= 255, "fs_create: classes out of range");
+    // what the handle's own last kernel can take: the classifier keeps its [K][C] filters in 64 KiB of LDS (C = 512 behind PSPNet's head,
+    // 256 behind DeepLabv3's), the Segmenter's mask head keeps one class per lane.  Refused here, where the caller configures the
+    // network, rather than by whichever forward meets the limit first (PSPNet's fused route alone would take any K).
+    const int max_classes = cfg->arch == FS_ARCH_PSPNET ? 32 : 64;
+    FS_REQUIRE(cfg->classes >= 1 && cfg->classes <= max_classes, "fs_create: classes out of range (%d; this arch takes 1..%d)", cfg->classes, max_classes);
     FS_REQUIRE((cfg->flags & ~(FS_OPT_NO_WINOGRAD | FS_OPT_NO_FUSED_HEAD | FS_OPT_NO_FUSED_SHORTCUT | FS_OPT_NO_FUSED_WINOGRAD | FS_OPT_NO_SPLIT_BF16 |
                                FS_OPT_NO_RES_TOUCH | FS_OPT_NO_FUSED_POOL | FS_OPT_NO_FUSED_QKV)) == 0,
                "fs_create: unknown option bits 0x%x", cfg->flags);
@@ -681,6 +685,55 @@ size_t net_reserved_bytes(fs_handle h) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The builders of net.h: launch geometry shared with the op-level test hooks (api_test.hip)
+ConvParams dual_conv_params(const float* a, int ld_a, const float* b, int ld_b, const float* wgt, const float* shift, float* out, int ld_out, int B,
+                            int Ho, int Wo, int Cin, int Cin2, int H2, int W2, int stride2, int Cout, int relu) {
+    ConvParams p{};
+    p.in = a; p.ld_in = ld_a; p.wgt = wgt; p.shift = shift; p.out = out; p.ld_out = ld_out;
+    p.B = B; p.H = Ho; p.W = Wo; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
+    p.KH = p.KW = 1; p.stride = 1; p.dil = 1; p.relu = relu;
+    p.in2 = b; p.ld_in2 = ld_b; p.Cin2 = Cin2; p.stride2 = stride2; p.H2 = H2; p.W2 = W2;
+    return p;
+}
+
+ConvParams ppm_z_params(const float* reduced, const float* zw, float* zbuf, int B, int Cr, int Cout9) {
+    const int rows = B * 36;
+    ConvParams p{};
+    p.in = reduced; p.ld_in = Cr; p.wgt = zw; p.out = zbuf; p.ld_out = Cout9;
+    p.B = 1; p.H = rows; p.W = 1; p.Cin = Cr; p.Ho = rows; p.Wo = 1; p.Cout = Cout9;
+    p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
+    p.groups = 4;
+    p.g_in = (long long)rows * Cr;
+    p.g_wgt = (long long)Cout9 * Cr;
+    p.g_out = (long long)rows * Cout9;
+    return p;
+}
+
+int pyramid_pool(fs_net* h, const float* feat, int ld_feat, float* pooled, int B, int H, int W, int C, const int bins[4], hipStream_t s) {
+    size_t pool_off[4];
+    {
+        size_t po = 0;
+        for (int i = 0; i < 4; ++i) {
+            pool_off[i] = po;
+            po += (size_t)B * bins[i] * bins[i] * C;
+        }
+    }
+    const double bytes = 4.0 * B * H * W * C;
+    if (H % 6 == 0 && W % 6 == 0 && bins[0] == 1 && bins[1] == 2 && bins[2] == 3 && bins[3] == 6) {  // one pass over the map instead of four
+        if (h) FS_TRY(prof_begin(h, "ppm.pool6+combine", "adaptive_avgpool", 0, bytes, s));
+        FS_TRY(launch_adaptive_avgpool(feat, ld_feat, pooled + pool_off[3], B, H, W, C, 6, s));
+        FS_TRY(launch_ppm_pool_combine(pooled + pool_off[3], pooled + pool_off[0], pooled + pool_off[1], pooled + pool_off[2], B, C, s));
+        if (h) FS_TRY(prof_end(h, s));
+        return 0;
+    }
+    for (int i = 0; i < 4; ++i) {
+        if (h) FS_TRY(prof_begin(h, "ppm.pool" + std::to_string(bins[i]), "adaptive_avgpool", 0, bytes, s));
+        FS_TRY(launch_adaptive_avgpool(feat, ld_feat, pooled + pool_off[i], B, H, W, C, bins[i], s));
+        if (h) FS_TRY(prof_end(h, s));
+    }
+    return 0;
+}
+
 namespace {
 // Pyramid pooling up to the reduced maps (model/pspnet.py:22-26): adaptive average pools (bins 1, 2, 3, 6) of the 2048
 // backbone channels -> 1x1 conv + BN + ReLU.  Layout in h->small: pooled maps back to back (1 + 4 + 9 + 36 cells per
@@ -688,33 +741,15 @@ namespace {
 int pyramid_reduce(fs_net* h, const float* feat, int ld_feat, int B, int H, int W, hipStream_t s) {
     float* pooled = h->small;
     float* reduced = h->small + (size_t)B * 50 * 2048;
-    size_t pool_off[4];
-    {
-        size_t po = 0;
-        for (int i = 0; i < 4; ++i) {
-            pool_off[i] = po;
-            po += (size_t)B * h->bins[i] * h->bins[i] * 2048;
-        }
-    }
-    const bool even = H % 6 == 0 && W % 6 == 0 && h->bins[0] == 1 && h->bins[1] == 2 && h->bins[2] == 3 && h->bins[3] == 6;
-    if (even) {  // one pass over the 2048-channel map instead of four
-        FS_TRY(prof_begin(h, "ppm.pool6+combine", "adaptive_avgpool", 0, 4.0 * B * H * W * 2048.0, s));
-        FS_TRY(launch_adaptive_avgpool(feat, ld_feat, pooled + pool_off[3], B, H, W, 2048, 6, s));
-        FS_TRY(launch_ppm_pool_combine(pooled + pool_off[3], pooled + pool_off[0], pooled + pool_off[1], pooled + pool_off[2], B, 2048, s));
-        FS_TRY(prof_end(h, s));
-    }
+    FS_TRY(pyramid_pool(h, feat, ld_feat, pooled, B, H, W, 2048, h->bins, s));
     RowdotBatch pb{};
     double flops = 0;
+    size_t pool_off = 0;
     for (int i = 0; i < 4; ++i) {
-        const int bin = h->bins[i];
-        const int cells = bin * bin;
-        if (!even) {
-            FS_TRY(prof_begin(h, "ppm.pool" + std::to_string(bin), "adaptive_avgpool", 0, 4.0 * B * H * W * 2048.0, s));
-            FS_TRY(launch_adaptive_avgpool(feat, ld_feat, pooled + pool_off[i], B, H, W, 2048, bin, s));
-            FS_TRY(prof_end(h, s));
-        }
+        const int cells = h->bins[i] * h->bins[i];
         const ConvBN& c = h->ppm[i];
-        pb.p[i] = RowdotProblem{pooled + pool_off[i], c.w, c.scale, c.shift, reduced + (size_t)i * B * 36 * 512, B * cells};
+        pb.p[i] = RowdotProblem{pooled + pool_off, c.w, c.scale, c.shift, reduced + (size_t)i * B * 36 * 512, B * cells};
+        pool_off += (size_t)B * cells * 2048;
         flops += 2.0 * B * cells * 2048.0 * 512.0;
     }
     // the four levels' 1x1 conv + BN + ReLU (model/pspnet.py:23-25) as ONE launch: M = B, 4B, 9B, 36B rows of the same (K, N)
@@ -804,11 +839,8 @@ int encoder_core(fs_handle h, const FrameSrc& src, int B, int H, int W, float* o
         if (blk.has_ds && blk.c3ds.w && h->use_fused_shortcut) {
             // conv3 and the projection shortcut as one launch over the concatenated K: the shortcut map is never written
             if (!dst) dst = F3;
-            ConvParams p{};
-            p.in = F2; p.ld_in = blk.c2.Cout; p.wgt = blk.c3ds.w; p.shift = blk.c3ds.shift; p.out = dst; p.ld_out = ld_dst;
-            p.B = B; p.H = oH; p.W = oW; p.Cin = blk.c3ds.Cin; p.Ho = oH; p.Wo = oW; p.Cout = Cn;
-            p.KH = p.KW = 1; p.stride = 1; p.dil = 1; p.relu = 1;
-            p.in2 = X; p.ld_in2 = C; p.Cin2 = blk.ds_cin; p.stride2 = blk.ds_stride; p.H2 = curH; p.W2 = curW;
+            ConvParams p = dual_conv_params(F2, blk.c2.Cout, X, C, blk.c3ds.w, blk.c3ds.shift, dst, ld_dst, B, oH, oW, blk.c3ds.Cin, blk.ds_cin, curH,
+                                            curW, blk.ds_stride, Cn, 1);
             split_use(h, p);
             const double M = (double)B * oH * oW;
             const double fl = 2.0 * M * Cn * (p.Cin + p.Cin2), by = 4.0 * (M * p.Cin + (double)B * curH * curW * p.Cin2 + (double)Cn * (p.Cin + p.Cin2) + M * Cn);
@@ -910,15 +942,7 @@ int net_segment(fs_handle h, const FrameSrc& src, int B, int H, int W, float* ou
     const float* Z[4];
     {   // one grouped GEMM, 4 groups x [B*36 rows (the level's B*bin^2 real ones first)] x [9*O] x 512
         const ConvBN& z = h->ppm_z[0];
-        const int rows = B * 36;
-        ConvParams p{};
-        p.in = reduced; p.ld_in = 512; p.wgt = z.w; p.out = zbuf; p.ld_out = z.Cout;
-        p.B = 1; p.H = rows; p.W = 1; p.Cin = 512; p.Ho = rows; p.Wo = 1; p.Cout = z.Cout;
-        p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
-        p.groups = 4;
-        p.g_in = (long long)rows * 512;
-        p.g_wgt = (long long)z.Cout * 512;
-        p.g_out = (long long)rows * z.Cout;
+        ConvParams p = ppm_z_params(reduced, z.w, zbuf, B, 512, z.Cout);
         split_use(h, p);
         FS_TRY(prof_begin(h, "decoder.0.weight[:, ppm]", conv_igemm_tile_name(p), 2.0 * B * 50 * 512.0 * z.Cout,
                           4.0 * (4.0 * z.Cout * 512 + B * 50.0 * (512 + z.Cout)), ps));

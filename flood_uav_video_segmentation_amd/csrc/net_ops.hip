@@ -925,6 +925,8 @@ int ppm_term_any(float* T, int ld, const float* const Z[4], const int bins[4], f
     FS_REQUIRE(logits && cls_w && K >= 1 && ((uintptr_t)cls_w & 15) == 0, "ppm_term_classify: bad classifier");
     FS_REQUIRE(H <= 65535 && B <= 65535, "ppm_term_classify: map too large for the launch grid");
     FS_REQUIRE(bins[0] + bins[1] + bins[2] + bins[3] == PPM_J && scratch, "ppm_term_classify: pyramid levels must add up to %d columns", PPM_J);
+    for (int i = 0; i < 4; ++i)  // the finish pass keeps six column weights per (level, tap column)
+        FS_REQUIRE(bins[i] >= 1 && bins[i] <= 6 && Z[i] && ((uintptr_t)Z[i] & 15) == 0, "ppm_term_classify: bad pyramid level %d (bin %d)", i, bins[i]);
     PpmTermParams p{};
     p.T = T; p.ld = ld; p.R = scratch; p.scale = scale; p.shift = shift;
     p.B = B; p.H = H; p.W = W; p.C = C; p.relu = relu;

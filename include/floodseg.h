@@ -45,6 +45,10 @@ typedef struct fs_config {
     int arch;        /* FS_ARCH_*                               flow/base.py:94-103            */
     int layers;      /* ResNet depth 50 | 101 | 152             model/pspnet.py:45-50          */
     int classes;     /* K                                       dataset/flow/config.yaml:2     */
+                     /* 1..32 for FS_ARCH_PSPNET, 1..64 for FS_ARCH_DEEPLABV3 and FS_ARCH_SEGMENTER: fs_create refuses anything else
+                      * ("classes out of range"), so that no forward of a handle can meet a class count its kernels do not take.
+                      * The window tails (fs_seg_tail, fs_seg_tail_accumulate) take K <= 32 whatever produced the logits and
+                      * refuse more with a message of their own.                                */
     /* FS_ARCH_SEGMENTER only (ignored otherwise)               model/vit.py:13-56             */
     int patch;       /* patch size P (32 as shipped, 16 for ViT-S/16)                          */
     int d_model;     /* 768 | 384 ...; head_dim is fixed to 64 => heads = d_model / 64         */

@@ -1,7 +1,8 @@
 /*
  * floodseg_test.h -- op-level hooks of libfloodseg.so: the building blocks behind the networks (implicit-GEMM conv, Winograd forms,
- * stem, pooling, attention, layout copies, and the Segmenter's LayerNorm, Linear / split-K merges, qkv + attention, mask head, patchify
- * and token assembly), for the parity tests (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py) and the measurement tools (tools/).
+ * stem, pooling, attention, layout copies, the Segmenter's LayerNorm, Linear / split-K merges, qkv + attention, mask head, patchify
+ * and token assembly, and the CNN heads' pyramid, classifier and concatenated-K shortcut kernels), for the parity tests
+ * (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py, tests/test_gpu_head_ops.py) and the measurement tools (tools/).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table is append-only; `size` is sizeof(fs_test_api) of the library that was built, so a
@@ -127,6 +128,56 @@ typedef struct fs_test_api {
     int (*vit_assemble)(const float* emb, const float* cls, const float* pos, float* X, int B, int N, int D, fs_stream stream);
     /* Z[b][i < N] = Y[b * N + i], Z[b][N + k] = cls_emb[k]; D % 4 == 0 */
     int (*dec_assemble)(const float* Y, const float* cls_emb, float* Z, int B, int N, int K, int D, fs_stream stream);
+    /* ---- CNN heads and projection shortcut (csrc/net_ops.hip, net.hip): the launchers and the launch geometry the networks run. */
+    /* out[o][0..Ka) = sa[o] * wa[o][:], out[o][Ka..Ka+Kb) = sb[o] * wb[o][:], shift_out[o] = ha[o] + hb[o] (one fp32 rounding each): the
+     * filter bank and bias of BN_a(conv_a(x)) + BN_b(conv_b(y)) as one GEMM over the concatenated K (both convs 1x1, filters [O][K*]) */
+    int (*concat_scaled_filters)(const float* wa, const float* sa, const float* ha, int Ka, const float* wb, const float* sb, const float* hb,
+                                 int Kb, float* out, float* shift_out, int O, fs_stream stream);
+    /* out[(tap * O + o) * nc + c] = oihw[o][c0 + c][tap]: the input-channel slice c0 .. c0 + nc - 1 of an [O][I][taps] bank as a
+     * [taps * O][nc] 1x1 filter matrix (the pyramid levels' share of the PSPNet head conv); 0 <= c0, c0 + nc <= I */
+    int (*pack_slice_tap_major)(const float* oihw, float* out, int O, int I, int c0, int nc, int taps, fs_stream stream);
+    /* conv3 + projection shortcut of a bottleneck as ONE launch: out[b][y][x][:] = act(a[b][y][x][:] @ W[:, :Cin]^T +
+     * b[b][y * stride2][x * stride2][:] @ W[:, Cin:]^T + shift), a = [B][Ho][Wo] x ld_a, b = [B][H2][W2] x ld_b with
+     * (H2 - 1) / stride2 + 1 == Ho (same for W), W = [Cout][Cin + Cin2] from concat_scaled_filters; Cin, Cin2 multiples of 32.
+     * wgt_planes: split_bf16x3 of W (the split-operand route) or NULL (fp32 matrix cores).  tile: 0 = cost-model choice, 1 = 128x128,
+     * 2 = 128x64 (the only concatenated-K tiles); all give the same bits.  relu as conv2d_nhwc (the network passes 1). */
+    int (*dual_conv)(const float* a, int ld_a, const float* b, int ld_b, const float* wgt, const void* wgt_planes, const float* shift, float* out,
+                     int ld_out, int B, int Ho, int Wo, int Cin, int Cin2, int H2, int W2, int stride2, int Cout, int relu, int tile,
+                     fs_stream stream);
+    /* The pooling half of the PSPNet pyramid: AdaptiveAvgPool2d(1, 2, 3, 6) of an NHWC map into out = [B][1][C] | [B][4][C] | [B][9][C] |
+     * [B][36][C] back to back (50 * B * C floats).  H and W multiples of 6: one pass over the map (6 x 6 cell means) + a combine of the
+     * cells into bins 3, 2, 1; otherwise four adaptive_avgpool launches.  C % 32 == 0. */
+    int (*pyramid_pool)(const float* in, int ld_in, float* out, int B, int H, int W, int C, fs_stream stream);
+    /* 1..4 small-M 1x1 convs of one (K, N) in one launch (the pyramid levels' conv + BN + ReLU; ASPP's pooling branch): problem i computes
+     * out[i][m][n] = act(scale[i][n] * <in[i][m], wgt[i][n]> + shift[i][n]) for m < M[i].  in / wgt / scale / shift / out / M are HOST
+     * arrays of nprob entries (device pointers inside; scale / shift, or single entries of them, may be NULL = 1 / 0).  K % 256 == 0,
+     * K <= 4096; rows are cut into min(12, max M / 6) chunks, the same cut for every problem. */
+    int (*rowdot_batch)(int nprob, const float* const* in, const float* const* wgt, const float* const* scale, const float* const* shift,
+                        float* const* out, const int* M, int ld_in, int ld_out, int K, int N, int relu, fs_stream stream);
+    /* bilinear resize of a small map in = [B][hi * wi][C] into the C-channel slice that starts at `out` of an NHWC buffer
+     * [B][Ho][Wo] x ld_out (out already points at the slice's first channel); C % 4 == 0, ld_out % 4 == 0, out 16-B aligned */
+    int (*upsample_into)(const float* in, int hi, int wi, float* out, int ld_out, int B, int Ho, int Wo, int C, int align_corners,
+                         fs_stream stream);
+    /* classifier 1x1 conv + bias (NULL = none), NHWC in -> NCHW out [B][K][HW]; wgt = [K][C]; C % 4 == 0; the filters live in LDS:
+     * K * C <= 16384, more is refused */
+    int (*classifier_nchw)(const float* in, int ld_in, const float* wgt, const float* bias, float* out, int B, int HW, int C, int K,
+                           fs_stream stream);
+    /* The PSPNet head finish: logits[b][k][y][x] = cls_b[k] + <cls_w[k], act(scale * (T[b][y][x] + term[b][y][x]) + shift)> with
+     * term = sum over the four levels of conv3x3(pad 1) of the align_corners = True upsampling of the level's pooled map, taken from
+     * z_i = [B * bin_i^2][9][C] (cell-major, then tap (r, s), then channel): what the level's cells contribute per tap.  T = [B][H][W] x ld
+     * raw head-conv sums, bins = 4 host ints (1..6 each, adding up to 12), scale / shift / cls_b may be NULL, C % 4 == 0, C <= 1024, any
+     * K >= 1.  scratch: ppm_term_scratch_floats(B, H, C) floats. */
+    size_t (*ppm_term_scratch_floats)(int B, int H, int C);
+    int (*ppm_term_classify)(const float* T, int ld, const float* z1, const float* z2, const float* z3, const float* z6, const int* bins,
+                             const float* scale, const float* shift, int B, int H, int W, int C, int relu, const float* cls_w, const float* cls_b,
+                             float* logits, int K, float* scratch, fs_stream stream);
+    /* The same preceded by the network's grouped Z GEMM: reduced = [4][B * 36][Cr] (level i's B * bin_i^2 rows first in its slot, the
+     * rest of the slot is multiplied but never used), zw = [4][9 * C][Cr] from pack_slice_tap_major (zw_planes: split_bf16x3 of all of
+     * it, or NULL for the fp32 matrix cores); Cr % 32 == 0.  workspace: ppm_head_workspace_floats(B, H, C) floats. */
+    size_t (*ppm_head_workspace_floats)(int B, int H, int C);
+    int (*ppm_head)(const float* T, int ld, const float* reduced, int Cr, const float* zw, const void* zw_planes, const int* bins,
+                    const float* scale, const float* shift, int B, int H, int W, int C, int relu, const float* cls_w, const float* cls_b,
+                    float* logits, int K, float* workspace, fs_stream stream);
 } fs_test_api;
 
 const fs_test_api* fs_test_hooks(void);

@@ -82,6 +82,18 @@ def test_bad_config_is_rejected_with_a_message():
     assert b"layers" in lib.fs_last_error()
 
 
+def test_class_counts_beyond_what_the_heads_take_are_rejected_at_create():
+    """include/floodseg.h, fs_config::classes: 1..32 for PSPNet (the unfused head's classifier keeps [K][512] filters in 64 KiB of LDS),
+    1..64 for DeepLabv3 ([K][256]) and the Segmenter (one class per lane of the mask head) -- refused when the handle is configured, not by
+    whichever forward meets the limit first."""
+    lib = _lib.load()
+    h = ctypes.c_void_p()
+    for arch, classes in ((_lib.ARCH_PSPNET, 33), (_lib.ARCH_PSPNET, 255), (_lib.ARCH_DEEPLABV3, 65), (_lib.ARCH_SEGMENTER, 65), (_lib.ARCH_PSPNET, 0)):
+        cfg = _lib.FsConfig(arch, 50, classes)
+        assert lib.fs_create(ctypes.byref(cfg), ctypes.byref(h)) != 0, (arch, classes)
+        assert b"classes out of range" in lib.fs_last_error()
+
+
 def test_unknown_option_bits_and_tile_sizes_are_rejected():
     """The A/B routes are explicit fs_config options (nothing is read from the environment); anything undefined is refused."""
     lib = _lib.load()

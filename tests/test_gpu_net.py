@@ -343,10 +343,11 @@ def test_split_operand_route_is_as_close_to_a_float64_network_as_the_fp32_mfma_r
         assert e_split < 2.0 * max(e_f32, e_cpu) + 2e-7, (e_split, e_f32, e_cpu)  # measured 0.86x / 1.49x (129 / 257)
 
 
-@pytest.mark.parametrize("classes", [19, 3, 9])
+@pytest.mark.parametrize("classes", [19, 3, 9, 32])
 def test_other_class_counts_through_the_fused_head_and_the_tail(classes):
     """Every test above uses the dataset's K = 5.  The head finish applies the classifier in passes of 8 classes (19 = 8 + 8 + 3,
-    9 = 8 + 1) and the fused tail has an instantiation for K > 8: a PSPNet with K classes at 97x97 against the oracle -- the fused
+    9 = 8 + 1; 32 is the most a PSPNet handle takes: the unfused head's classifier fills its 64 KiB of LDS, the tail its 32 class
+    registers) and the fused tail has an instantiation for K > 8: a PSPNet with K classes at 97x97 against the oracle -- the fused
     segment route, the decoder(encoder) route, and a whole logit-warp window (logits and masks)."""
     from flood_uav_video_segmentation_amd.flow.model import FlowModel
     from oracle import flow_oracle
@@ -370,3 +371,42 @@ def test_other_class_counts_through_the_fused_head_and_the_tail(classes):
     assert note(f"pspnet50_K{classes}_97_window_logits_vs_oracle", rel_err(got["pred"].cpu(), ref)) < LOGIT_TOL
     assert (got["mask"].cpu() == ref.max(1)[1].to(torch.uint8)).float().mean().item() > 0.999
     assert torch.equal(got["mask"], got["pred"].max(1)[1].to(torch.uint8))
+
+
+@pytest.mark.parametrize("size", [(41, 89), (89, 137)])
+def test_pspnet_on_small_maps_that_are_multiples_of_six(psp, size):
+    """A 6 x 12 and a 12 x 18 feature map: the one-pass pyramid pooling (6 x 6 cell means + combine) away from the 90 x 90 map of 713,
+    where a window is a single cell or two -- fused route and decoder(encoder) against the oracle."""
+    net, state = psp
+    x = synth.make_clip(2, size, seed=51)
+    ofeat = pspnet_oracle.encoder(x, state, 50)
+    ref = pspnet_oracle.decoder(ofeat, state)
+    assert ref.shape[2:] == ((size[0] - 1) // 8 + 1, (size[1] - 1) // 8 + 1) and ref.shape[2] % 6 == 0 and ref.shape[3] % 6 == 0
+    feat = net.encoder(x.cuda())
+    name = f"pspnet_{size[0]}x{size[1]}"
+    assert note(name + "_feat_vs_oracle", rel_err(feat.cpu(), ofeat)) < LOGIT_TOL
+    assert note(name + "_logits_vs_oracle", rel_err(net.decoder(feat).cpu(), ref)) < LOGIT_TOL
+    assert note(name + "_segment_vs_oracle", rel_err(net.segment(x.cuda()).cpu(), ref)) < LOGIT_TOL
+
+
+def test_thirty_three_classes_match_the_oracle_or_are_refused_with_a_message():
+    """fs_create takes 1..32 classes for PSPNet (include/floodseg.h): with 33 the unfused head's classifier would not fit its LDS and the
+    fused route alone would work, so the handle is refused where it is configured.  DeepLabv3 takes up to 64: both its routes match the
+    oracle at K = 33, and the window tail, which holds at most 32 classes, refuses such logits with its own message."""
+    from flood_uav_video_segmentation_amd import ops
+
+    with pytest.raises(RuntimeError, match="classes out of range"):
+        net = FlowPSPNet(HP(50, 33)).eval()
+        net.load_state_dict(synth.make_pspnet_state(50, 33, seed=5))
+        net.segment(synth.make_clip(1, 65, seed=41).cuda())
+    state = synth.make_deeplab_state(50, 33, seed=6)
+    net = FlowDeepLabv3(HP(50, 33)).eval()
+    net.load_state_dict(state)
+    x = synth.make_clip(2, 97, seed=43)
+    ref = deeplab_oracle.decoder(deeplab_oracle.encoder(x, state, 50), state)
+    assert ref.shape[1] == 33
+    lo = net.segment(x.cuda())
+    assert note("deeplab50_K33_97_segment_vs_oracle", rel_err(lo.cpu(), ref)) < LOGIT_TOL
+    assert rel_err(net.decoder(net.encoder(x.cuda())).cpu(), ref) < LOGIT_TOL
+    with pytest.raises(RuntimeError, match="seg_tail: K=33 out of range"):
+        ops.seg_tail(lo[0:1], None, [], [], 1, (97, 97), True, want_logits=False, want_mask=True)
