@@ -82,6 +82,9 @@ _SIGNATURES = {
     "fs_mv_to_grids": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void, c_void, c_void]),
     "fs_softmax_accumulate": (c_int, [c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "fs_canvas_finish": (c_int, [c_void, c_void, c_int, c_int, c_i64, c_void, c_void]),
+    "fs_ms_prepare": (c_int, [c_void] + [c_int] * 6 + [c_float_p, c_float_p, c_void, c_int, c_void]),
+    "fs_ms_fuse": (c_int, [c_void, c_void, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)] + [c_int] * 9 + [c_void, c_void] + [c_int] * 4
+                   + [c_void, c_void]),
     "fs_test_hooks": (c_void, []),
 }
 

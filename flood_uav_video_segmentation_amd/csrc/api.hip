@@ -280,3 +280,41 @@ FS_API int fs_crops_fuse(const float* lo_prev, const float* lo_next, const float
     return fs::launch_crops_fuse(p, crop_grids, scratch, S(stream));
 }
 
+// A pointer the kernels may dereference: memory the HIP runtime knows as device (or managed) memory.  A host pointer is refused
+// here, before any launch, instead of faulting on the device.
+static bool on_device(const void* p) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+FS_API int fs_ms_prepare(const float* raw, int H, int W, int new_h, int new_w, int PH, int PW, const float* mean, const float* std, float* out,
+                         int flip, fs_stream stream) {
+    if (!raw || !out || !mean || !std) return fs::fail("fs_ms_prepare: null pointer");
+    if (!on_device(raw) || !on_device(out)) return fs::fail("fs_ms_prepare: raw and out must be device pointers");
+    return fs::launch_ms_prepare(raw, H, W, new_h, new_w, PH, PW, mean, std, out, flip, S(stream));
+}
+
+FS_API int fs_ms_fuse(const float* lo_plain, const float* lo_flip, int ncrops, const int* crop_y, const int* crop_x, int K, int h, int w, int ch,
+                      int cw, int PH, int PW, int new_h, int new_w, double* scaled, double* pred, int H, int W, int scale_index, int nscales,
+                      uint8_t* mask, fs_stream stream) {
+    if (!lo_plain || !crop_y || !crop_x || !scaled) return fs::fail("fs_ms_fuse: null pointer");
+    if (ncrops < 1 || ncrops > 64) return fs::fail("fs_ms_fuse: %d crops; one scale takes 1..64 (a larger scale is refused, not split)", ncrops);
+    if (!on_device(lo_plain) || (lo_flip && !on_device(lo_flip)) || !on_device(scaled) || (pred && !on_device(pred)) || (mask && !on_device(mask)))
+        return fs::fail("fs_ms_fuse: logits, scaled, pred and mask must be device pointers");
+    fs::MsFuseParams p{};
+    p.lo_plain = lo_plain;
+    p.lo_flip = lo_flip;
+    p.nc = ncrops;
+    for (int c = 0; c < ncrops; ++c) {
+        if (crop_y[c] < 0 || crop_x[c] < 0 || crop_y[c] > 32767 || crop_x[c] > 32767) return fs::fail("fs_ms_fuse: crop %d outside the %dx%d frame", c, PH, PW);
+        p.cy[c] = (short)crop_y[c];
+        p.cx[c] = (short)crop_x[c];
+    }
+    p.K = K; p.h = h; p.w = w; p.ch = ch; p.cw = cw; p.PH = PH; p.PW = PW; p.new_h = new_h; p.new_w = new_w;
+    p.scaled = scaled;
+    return fs::launch_ms_fuse(p, pred, H, W, scale_index, nscales, mask, S(stream));
+}

@@ -217,6 +217,25 @@ struct CropsFuseParams {
 // grids: [nc][2(n-1)][Hg][Wg][2] (fs_crop_grids' output) in warp mode; scratch: nc * 2(n-1) * K * Hg * Wg floats
 int launch_crops_fuse(CropsFuseParams p, const float* grids, float* scratch, hipStream_t s);
 
+// Single-frame multi-scale test (base/foundation.py:177-221, 264-330), ms_ops.hip.
+// (a) raw 0-255 frame [3,H,W] -> out[0] = scaled to new_h x new_w, mean-padded to PH x PW, normalised; out[1] (flip) = its mirror
+int launch_ms_prepare(const float* raw, int H, int W, int new_h, int new_w, int PH, int PW, const float* mean, const float* std, float* out,
+                      int flip, hipStream_t s);
+struct MsFuseParams {
+    const float* lo_plain;  // [nc, K, h, w] logits of the crops of the prepared frame
+    const float* lo_flip;   // the same crops of the mirrored frame (net_process' input.flip(3) half), or nullptr: flip=False
+    int nc;
+    short cy[64], cx[64];   // crop offsets in the PADDED scaled frame, in the reference's crop order
+    int K, h, w, ch, cw;
+    int PH, PW, new_h, new_w;  // padded and un-padded size of the scaled frame
+    double* scaled;         // [new_h, new_w, K] crop- and flip-averaged probabilities of the un-padded region
+    int pad_top, pad_left;  // filled by the launcher
+    float sy_lo, sx_lo;
+};
+// (b) scaled = fusion of the crops; (c) when pred != nullptr: pred[H,W,K] (+)= resize(scaled), the last scale divides by nscales
+// and writes mask[H,W] (may be nullptr).  At most 64 crops: a scale that needs more is refused.
+int launch_ms_fuse(MsFuseParams p, double* pred, int H, int W, int scale_index, int nscales, uint8_t* mask, hipStream_t s);
+
 // argmax over channel dim of NCHW logits -> uint8 (first max wins; flow/base.py:276).
 int launch_argmax_u8(const float* in, int B, int K, int64_t HW, uint8_t* out, hipStream_t s);
 // argmax of the align_corners=True bilinear upsample of NCHW logits, without materialising it

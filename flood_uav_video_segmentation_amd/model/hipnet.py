@@ -204,9 +204,10 @@ class HipNet:
                                                     stream_ptr()))
         return out
 
-    def segment_crops(self, frame_a, frame_b, crop_yx, crop_hw):
+    def segment_crops(self, frame_a, frame_b, crop_yx, crop_hw, out=None):
         """decoder(encoder(.)) of the crop windows of one or two FULL frames [1,3,H,W] as one batch, read in place
-        (fs_segment_crops; flow/base.py:199-200 clones each crop).  -> [ncrops * (2 if frame_b is given else 1), K, fh, fw]."""
+        (fs_segment_crops; flow/base.py:199-200 clones each crop).  -> [ncrops * (2 if frame_b is given else 1), K, fh, fw],
+        written into `out` when the caller brings a contiguous fp32 tensor of that shape."""
         self._need_ready()
         frames = self._frames((frame_a,) if frame_b is None else (frame_a, frame_b), "segment_crops")
         if any(f.shape[0] != 1 for f in frames):
@@ -219,7 +220,11 @@ class HipNet:
             ys = (ctypes.c_int * nc)(*[int(y) for y, _ in crop_yx])
             xs = (ctypes.c_int * nc)(*[int(x) for _, x in crop_yx])
             _, fh, fw = self.feature_shape(ch, cw)
-            out = torch.empty((nc * len(xs_), self.classes, fh, fw), dtype=torch.float32, device=xs_[0].device)
+            shape = (nc * len(xs_), self.classes, fh, fw)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=xs_[0].device)
+            elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != xs_[0].device:
+                raise RuntimeError(f"floodseg segment_crops: out must be a contiguous fp32 {shape} tensor on {xs_[0].device}")
             check(self._lib.fs_segment_crops(self._h, ptr(xs_[0]), ptr(xs_[1]) if len(xs_) > 1 else None, fh_, fw_, nc, ys, xs, ch, cw,
                                              ptr(out), stream_ptr()))
         return out

@@ -38,10 +38,12 @@ class FlowPSPNet(HipSegNet):
         (flow/model.py:39-40, 189-191, 202-204) use it when the wrapped network offers it."""
         return self._hip_net.segment(*frames)
 
-    def segment_crops(self, frame_a, frame_b, crop_yx, crop_hw):
+    def segment_crops(self, frame_a, frame_b, crop_yx, crop_hw, out=None):
         """The same composition on crop windows of full frames, read in place: the sliding-crop route (flow/base.py:182-209)
         batches its crops through the network with this."""
-        return self._hip_net.segment_crops(frame_a, frame_b, crop_yx, crop_hw)
+        if out is None:
+            return self._hip_net.segment_crops(frame_a, frame_b, crop_yx, crop_hw)
+        return self._hip_net.segment_crops(frame_a, frame_b, crop_yx, crop_hw, out=out)
 
     @staticmethod
     def canonical_name(key):

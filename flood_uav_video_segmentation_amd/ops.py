@@ -396,6 +396,63 @@ def iou_hist(pred_u8, target_u8, classes, ignore_index=255, hist=None):
     return hist
 
 
+# ------------------------------------------------------------------------------------------ single-frame multi-scale test
+def ms_prepare(raw, new_hw, padded_hw, mean, std, flip=True):
+    """One scale's network input from the raw 0-255 frame [3,H,W] (base/foundation.py:193-200, 267-273, 300-306): resized to
+    `new_hw` (half-pixel bilinear), mean-padded to `padded_hw`, normalised -> fp32 [2 if flip else 1, 3, PH, PW]; [1] is the
+    horizontal mirror of [0] (fs_ms_prepare)."""
+    lib = _lib.load()
+    if raw.dim() != 3 or raw.shape[0] != 3:
+        raise RuntimeError(f"floodseg.ms_prepare: expected a [3,H,W] frame, got {tuple(raw.shape)}")
+    with torch.cuda.device(one_device(raw, what="floodseg.ms_prepare")):
+        x = _f32c(raw)
+        ph, pw = int(padded_hw[0]), int(padded_hw[1])
+        out = torch.empty((2 if flip else 1, 3, ph, pw), dtype=torch.float32, device=x.device)
+        m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        s = (ctypes.c_float * 3)(*[float(v) for v in std])
+        check(lib.fs_ms_prepare(ptr(x), x.shape[1], x.shape[2], int(new_hw[0]), int(new_hw[1]), ph, pw, m, s, ptr(out), int(bool(flip)),
+                                stream_ptr()))
+    return out
+
+
+def ms_fuse(lo_plain, lo_flip, crop_yx, crop_hw, padded_hw, new_hw, pred=None, frame_hw=None, scale_index=0, nscales=1, want_mask=False):
+    """Crop / flip fusion of one scale and its accumulation over the scales (base/foundation.py:279-295, 322-325, 201-203;
+    fs_ms_fuse).  lo_plain / lo_flip: [ncrops,K,h,w] logits of the crops `crop_yx` (offsets in the padded frame) of the prepared
+    frame / of its mirror (None: flip=False).  Returns (scaled [new_h,new_w,K] float64, pred, mask): with `frame_hw` the scale is
+    resized to the frame and added to `pred` [H,W,K] float64 (allocated when None; written, not added, at scale_index 0); the
+    last scale divides by `nscales` and, if want_mask, gives the uint8 argmax."""
+    lib = _lib.load()
+    dev = one_device(lo_plain, lo_flip, pred, what="floodseg.ms_fuse")
+    if lo_plain.dim() != 4 or (lo_flip is not None and lo_flip.shape != lo_plain.shape):
+        raise RuntimeError("floodseg.ms_fuse: logits must be [ncrops,K,h,w], the flipped ones of the same shape")
+    nc, k, h, w = lo_plain.shape
+    if nc != len(crop_yx):
+        raise RuntimeError(f"floodseg.ms_fuse: {nc} logit maps for {len(crop_yx)} crops")
+    with torch.cuda.device(dev):
+        a = _f32c(lo_plain)
+        b = _f32c(lo_flip) if lo_flip is not None else None
+        nh, nw = int(new_hw[0]), int(new_hw[1])
+        scaled = torch.empty((max(nh, 0), max(nw, 0), k), dtype=torch.float64, device=dev)
+        mask = None
+        fh = fw = 0
+        if frame_hw is not None:
+            fh, fw = int(frame_hw[0]), int(frame_hw[1])
+            if pred is None:
+                pred = torch.empty((fh, fw, k), dtype=torch.float64, device=dev)
+            if pred.dtype != torch.float64 or tuple(pred.shape) != (fh, fw, k) or not pred.is_contiguous():
+                raise RuntimeError(f"floodseg.ms_fuse: pred must be a contiguous float64 [{fh},{fw},{k}] tensor")
+            if want_mask and scale_index == nscales - 1:
+                mask = torch.empty((fh, fw), dtype=torch.uint8, device=dev)
+        elif pred is not None or want_mask:
+            raise RuntimeError("floodseg.ms_fuse: pred / mask need frame_hw")
+        ys = (ctypes.c_int * nc)(*[int(y) for y, _ in crop_yx])
+        xs = (ctypes.c_int * nc)(*[int(x) for _, x in crop_yx])
+        check(lib.fs_ms_fuse(ptr(a), ptr(b), nc, ys, xs, k, h, w, int(crop_hw[0]), int(crop_hw[1]), int(padded_hw[0]), int(padded_hw[1]), nh, nw,
+                             ptr(scaled), ptr(pred) if frame_hw is not None else None, fh, fw, int(scale_index), int(nscales), ptr(mask),
+                             stream_ptr()))
+    return scaled, pred, mask
+
+
 # ------------------------------------------------------------------------------------------ building blocks
 # (test / bring-up helpers over the op-level hooks of include/floodseg_test.h; nothing on the product path calls them)
 def conv2d_nhwc(x, weight, scale=None, shift=None, residual=None, stride=1, pad=0, dil=1, relu=False, tile=0, out=None, split=False):

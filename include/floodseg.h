@@ -232,6 +232,33 @@ int fs_crops_fuse(const float* lo_prev, const float* lo_next, const float* crop_
                   int K, int h, int w, int Hg, int Wg, int ch, int cw, int n, int no_warp, double* canvas, uint8_t* mask, int H, int W,
                   float* scratch, fs_stream stream);
 
+/* ---- single-frame multi-scale, flip-averaged sliding-crop test (base/foundation.py:177-221 test_step, :264-295
+ * compute_test_output_for_scales, :299-330 net_process) ------------------------------------------------------------
+ * Per scale: fs_ms_prepare -> fs_segment_crops on out[0] (and on out[1] with the mirrored columns) -> fs_ms_fuse.  Both refuse
+ * host pointers, null pointers and geometry that does not fit with an error return before any launch.
+ * The two interpolating cv2.resize calls (:200, :294) are restated as half-pixel bilinear interpolation -- source coordinate
+ * (i + 0.5) * src / dst - 0.5 in double, taps clamped to the image -- and are the exact identity when dst == src.
+ *
+ * fs_ms_prepare: raw = the frame test_step receives (:179, :188-189), fp32 [3,H,W] in 0..255.  out = fp32 [flip ? 2 : 1][3][PH][PW]:
+ *   out[0] = the frame resized to new_h x new_w (:193-200; the caller computes long_size and the rounding), padded to
+ *   PH x PW = max(new, crop) with `mean` split int(pad / 2) before / the rest after (:267-273) and normalised (v - mean[c]) / std[c]
+ *   (:300-306; a padding pixel is exactly 0); out[1] = out[0].flip(3): the flipped crop [s_w, e_w) of :311 is the window
+ *   [PW - e_w, PW - s_w) of it, so both halves of the flip batch are read in place by fs_segment_crops.
+ *   mean / std: HOST arrays of 3 floats (:27-31). */
+int fs_ms_prepare(const float* raw, int H, int W, int new_h, int new_w, int PH, int PW, const float* mean, const float* std, float* out,
+                  int flip, fs_stream stream);
+/* fs_ms_fuse: lo_plain / lo_flip = the network's logits [ncrops,K,h,w] of the crops (crop_y, crop_x: host arrays, offsets in the
+ *   PADDED frame, in the order of :281-288) of out[0] / of the mirrored windows of out[1]; lo_flip NULL = net_process(flip=False) (:299).
+ *   Per pixel of the un-padded region and per covering crop, in crop order: upsample to ch x cw (align_corners=True, :322), fp32
+ *   softmax over K (:323), the flipped half read at column cw - 1 - x, (a + b) / 2 in fp32 (:325); summed in float64 (:291), divided
+ *   by the float64 crop count (:292), padding cut (:293) -> scaled, float64 [new_h][new_w][K] (pixel-major, as prediction_crop).
+ *   pred != NULL: pred[H][W][K] (float64, :191) = (scale_index == 0 ? 0 : pred) + resize(scaled, (H, W)) in float64 (:294, :201); at
+ *   scale_index == nscales - 1 it is divided by nscales (:202) and mask[H][W] (may be NULL) takes its argmax, first maximum wins
+ *   (:203).  K <= 8; at most 64 crops per scale -- a scale that needs more is refused with a message, not split. */
+int fs_ms_fuse(const float* lo_plain, const float* lo_flip, int ncrops, const int* crop_y, const int* crop_x, int K, int h, int w, int ch,
+               int cw, int PH, int PW, int new_h, int new_w, double* scaled, double* pred, int H, int W, int scale_index, int nscales,
+               uint8_t* mask, fs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,9 +45,29 @@ def timeit(fn, steps=10, warmup=2):
     return (time.perf_counter() - t0) / steps
 
 
+def _bench_lib():
+    from flood_uav_video_segmentation_amd import _lib
+    return _lib.load()
+
+
+def _check(rc):
+    from flood_uav_video_segmentation_amd import _lib
+    _lib.check(rc)
+
+
+def _ptr(t):
+    from flood_uav_video_segmentation_amd import _lib
+    return _lib.ptr(t)
+
+
+def _stream():
+    from flood_uav_video_segmentation_amd import _lib
+    return _lib.stream_ptr()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -77,7 +97,7 @@ def main():
         return step
 
     psp = None
-    if any(want(k) for k in ("cfg0", "cfg1", "cfg4", "feat", "crops", "crops_cached")):
+    if any(want(k) for k in ("cfg0", "cfg1", "cfg4", "feat", "crops", "crops_cached", "ms1", "ms6")):
         psp = FlowPSPNet(HP(50)).eval()
         psp.load_state_dict(synth.make_pspnet_state(50, 5, 0))
 
@@ -122,6 +142,48 @@ def main():
         t = timeit(crops_step, steps=max(3, st))
         rows.append(("(reference default route) 1072x1920, 8 crops x 2 key frames, warp" + (", key-frame cache" if cached else ""), N / t, t * 1e3))
         del pred, hd
+    for key, scales in (("ms1", [1.0]), ("ms6", [0.5, 0.75, 1.0, 1.25, 1.5, 1.75])):
+        if not want(key):
+            continue
+        # the single-frame multi-scale test (base/foundation.py:177-221): 1080 x 1920, 713 x 713 crops, every crop with its flip
+        from flood_uav_video_segmentation_amd.base.foundation import SingleFrameEvaluator, crop_windows, mean, scaled_size, std
+        ev = SingleFrameEvaluator(psp, 5, 713, 713, test_scales=scales, crop_batch=8)
+        raw = (synth.make_clip(1, (1080, 1920), seed=1300)[0] * torch.tensor(std)[:, None, None] + torch.tensor(mean)[:, None, None]).clamp(0, 255).to(dev)
+        host_ms = torch.empty((1080, 1920), dtype=torch.uint8).pin_memory()
+
+        def ms_step(i, ev=ev, raw=raw):
+            host_ms.copy_(ev.predict(raw)[1], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        t = timeit(ms_step, steps=max(3, st // 2))
+        # the same frame without the network: the new kernels on held logits, and the per-crop composition of existing ops they replace
+        geo = []
+        for sc in scales:
+            nh, nw = scaled_size(1080, 1920, sc)
+            ph, pw = max(nh, 713), max(nw, 713)
+            wins = crop_windows(ph, pw, 713, 713)
+            geo.append((nh, nw, ph, pw, wins, torch.randn((2, len(wins), 5, 90, 90), device=dev)))
+        canvas = torch.zeros((1, 5, 2016, 3584), dtype=torch.float64, device=dev)
+        count = torch.zeros((2016, 3584), dtype=torch.float64, device=dev)
+        lib = _bench_lib()
+
+        def new_kernels(i):
+            pred = None
+            for j, (nh, nw, ph, pw, wins, lo) in enumerate(geo):
+                ops.ms_prepare(raw, (nh, nw), (ph, pw), mean, std)
+                pred = ops.ms_fuse(lo[0], lo[1], wins, (713, 713), (ph, pw), (nh, nw), pred=pred, frame_hw=(1080, 1920), scale_index=j,
+                                   nscales=len(geo), want_mask=True)[1]
+
+        def old_composition(i):  # upsample + softmax-accumulate per crop and flip (no un-flip, no averaging, no resize back: a lower bound)
+            for nh, nw, ph, pw, wins, lo in geo:
+                for half in range(2):
+                    for c, (y, x) in enumerate(wins):
+                        up = ops.resize_bilinear(lo[half, c:c + 1], (713, 713), align_corners=True)
+                        _check(lib.fs_softmax_accumulate(_ptr(up), 1, 5, 713, 713, _ptr(canvas), _ptr(count), ph, pw, y, x, _stream()))
+        t_new, t_old = timeit(new_kernels, steps=max(3, st // 2)), timeit(old_composition, steps=max(3, st // 2))
+        rows.append((f"single-frame multi-scale test 1080x1920, 713 crops + flips, {len(scales)} scale(s)", 1 / t, t * 1e3))
+        rows.append((f"  new kernels alone (prepare + fuse + accumulate): {100 * t_new / t:.1f} % of the frame", 1 / t_new, t_new * 1e3))
+        rows.append(("  existing ops per crop and flip (resize + softmax_accumulate only)", 1 / t_old, t_old * 1e3))
+        del ev, geo, canvas, count
     del psp
     if want("cfg2"):
         dl3 = FlowDeepLabv3(HP(101)).eval()
