@@ -128,6 +128,7 @@ _HOOKS = [
     ("ppm_term_classify", c_int, [c_void, c_int] + [c_void] * 7 + [c_int] * 5 + [c_void] * 3 + [c_int, c_void, c_void]),
     ("ppm_head_workspace_floats", ctypes.c_size_t, [c_int] * 3),
     ("ppm_head", c_int, [c_void, c_int, c_void, c_int] + [c_void] * 5 + [c_int] * 5 + [c_void] * 3 + [c_int, c_void, c_void]),
+    ("block_match", c_int, [c_void, c_void] + [c_int] * 5 + [c_void, c_void, c_void]),
 ]
 
 

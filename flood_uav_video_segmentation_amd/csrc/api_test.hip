@@ -356,6 +356,16 @@ static int fs_ppm_head(const float* T, int ld, const float* reduced, int Cr, con
     for (int i = 0; i < 4; ++i) Z[i] = zbuf + (size_t)i * p.g_out;
     return fs::launch_ppm_term_classify(T, ld, Z, bins, zbuf + (size_t)4 * p.g_out, scale, shift, B, H, W, C, relu, cls_w, cls_b, logits, K, S(stream));
 }
+static int fs_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int32_t* mv, int32_t* cost,
+                          fs_stream stream) {
+    if (!cur || !ref || !mv) return fs::fail("fs_block_match: null pointer");
+    if (channels != 1 && channels != 3) return fs::fail("fs_block_match: channels must be 1 (luma) or 3 (RGB), got %d", channels);
+    if (H < 16 || W < 16) return fs::fail("fs_block_match: frame %d x %d is smaller than one 16 x 16 block", H, W);
+    if (search < 1 || search > 32) return fs::fail("fs_block_match: search range must be 1..32, got %d", search);
+    if (penalty < 0 || penalty > 255) return fs::fail("fs_block_match: penalty must be 0..255, got %d", penalty);
+    if ((int64_t)H * W * channels >= ((int64_t)1 << 31)) return fs::fail("fs_block_match: frame too large (%d x %d x %d bytes pass 2^31)", H, W, channels);
+    return fs::launch_block_match(cur, ref, H, W, channels, search, penalty, mv, cost, S(stream));
+}
 
 FS_API const fs_test_api* fs_test_hooks(void) {
     static const fs_test_api api = {
@@ -397,6 +407,7 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_ppm_term_classify,
         fs_ppm_head_workspace_floats,
         fs_ppm_head,
+        fs_block_match,
     };
     return &api;
 }

@@ -268,6 +268,12 @@ int launch_colorize(const uint8_t* mask, const uint8_t* palette, int K, uint8_t*
 // H.264 block motion vectors -> forward / inverse sampling grids (dataset/flow/extract_motion_vectors.py:21-43), float64
 int launch_mv_to_grids(const int* mv, int n, int stride, int hb, int wb, int bs, int H, int W, int* owners, double* grid,
                        double* inv_grid, hipStream_t s);
+// Full-search block matching of two uint8 frames (luma [H][W], channels = 1, or RGB [H][W][3], channels = 3; ref = the past frame):
+// for every 16x16 block of `cur` the displacement |dx|, |dy| <= R whose window lies inside `ref` and minimises
+// (SAD + lambda (|dx| + |dy|), |dx| + |dy|, dy, dx); mv = int32 [H/16 * W/16][7] rows (-1, 16, 16, src_x, src_y, dst_x, dst_y) in
+// block raster order (the table launch_mv_to_grids takes), cost = int32 [H/16 * W/16] winning costs or nullptr (motion_ops.hip)
+int launch_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int R, int lambda, int* mv, int* cost,
+                       hipStream_t s);
 // intersection / union / target histograms (util/util.py:52-63), int64[3][K] accumulated.
 int launch_iou_hist(const uint8_t* pred, const uint8_t* target, int64_t numel, int K, int ignore_index,
                     long long* hist3K, hipStream_t s);

@@ -21,10 +21,26 @@ MEAN = [0.485 * 255, 0.456 * 255, 0.406 * 255]
 STD = [0.229 * 255, 0.224 * 255, 0.225 * 255]
 
 
-class PredictWindows:
-    """Window i of a video = key frames (i*delta, (i+1)*delta) + the delta-1 grids in between (flow/dataset.py:112-146)."""
+def _grid_source(grids, search, penalty):
+    """grids="files": the grids/ and inv_grids/ folders (the reference's layout); "estimate": a flow.motion.GridEstimator."""
+    if grids == "files":
+        return None
+    if grids != "estimate":
+        raise ValueError(f'grids must be "files" or "estimate", got {grids!r}')
+    from .motion import GridEstimator
 
-    def __init__(self, data_root, predict_v_id, frame_delta=5, no_warp=False, size=None, device="cuda"):
+    return GridEstimator(search, penalty)
+
+
+class PredictWindows:
+    """Window i of a video = key frames (i*delta, (i+1)*delta) + the delta-1 grids in between (flow/dataset.py:112-146).
+
+    grids="estimate" (extension): the grids come from block matching of the decoded frames (flow/motion.py, `search`, `penalty`)
+    instead of the grids/ and inv_grids/ folders -- the same grid ids, and a frame is complete when its image exists."""
+
+    def __init__(self, data_root, predict_v_id, frame_delta=5, no_warp=False, size=None, device="cuda", grids="files", search=16,
+                 penalty=0):
+        self.estimator = _grid_source(grids, search, penalty)
         self.data_root, self.video_id = data_root, predict_v_id
         self.frame_delta, self.no_warp = frame_delta, no_warp
         self.size = size  # (h, w) of transform_predict's Resize, None = native
@@ -43,6 +59,8 @@ class PredictWindows:
         return os.path.join(self.data_root, "frames", self.video_id, name, f"{i}.npy")
 
     def _complete(self, f_id):
+        if self.estimator is not None:
+            return os.path.exists(self.frame_path(f_id))
         return all(os.path.exists(p) for p in (self.frame_path(f_id), self.grid_path(f_id, "grids"), self.grid_path(f_id, "inv_grids")))
 
     def indices(self, index, max_search=100000):
@@ -70,6 +88,25 @@ class PredictWindows:
         ids = [f_index + i + 1 for i in range(self.frame_delta - 1)]
         return ids, ids[::-1]
 
+    def raw_frame(self, f_id):
+        """The decoded uint8 frame [H,W,3] on the device, before Resize and normalisation (what the grid estimator sees, as
+        mvextractor sees the decoded picture); None when the image does not exist."""
+        from PIL import Image
+
+        if f_id < 0 or not os.path.exists(self.frame_path(f_id)):
+            return None
+        return torch.from_numpy(np.array(Image.open(self.frame_path(f_id)).convert("RGB"))).to(self.device)
+
+    def _grid(self, g, name):
+        """Grid `g` of grids/ (name "grids") or inv_grids/ as the float32 [1,67,120,2] device tensor of an item."""
+        if self.estimator is None:
+            return load_grid(self.grid_path(g, name))[None].to(self.device)
+        if getattr(self, "_estimator_video", None) != self.video_id:  # EvalWindows walks several videos: frame ids are per video
+            self.estimator.reset()
+            self._estimator_video = self.video_id
+        pair = self.estimator.grids_for(g, self.raw_frame)
+        return pair[0 if name == "grids" else 1].float()[None]
+
     def _frame(self, f_id):
         from PIL import Image
 
@@ -96,8 +133,8 @@ class PredictWindows:
             item["mvs_right"] = [torch.zeros(1, 1, device=self.device) for _ in range(self.frame_delta - 1)]
         else:
             fwd, inv = self.grid_ids(index)
-            item["mvs_left"] = [load_grid(self.grid_path(i, "grids"))[None].to(self.device) for i in fwd]
-            item["mvs_right"] = [load_grid(self.grid_path(i, "inv_grids"))[None].to(self.device) for i in inv]
+            item["mvs_left"] = [self._grid(i, "grids") for i in fwd]
+            item["mvs_right"] = [self._grid(i, "inv_grids") for i in inv]
         return item
 
 
@@ -138,9 +175,10 @@ class EvalWindows(PredictWindows):
     (batch_size_test = 1, flow/base.py:164)."""
 
     def __init__(self, data_root, data_list, split="test", frame_delta=5, no_warp=False, size=None, center_crop=None,
-                 classes_ignore=(), device="cuda"):
+                 classes_ignore=(), device="cuda", grids="files", search=16, penalty=0):
         if split not in ("val", "test"):
             raise ValueError("EvalWindows mirrors the val / test splits; use PredictWindows for predict")
+        self.estimator = _grid_source(grids, search, penalty)
         self.data_root, self.split = data_root, split
         self.frame_delta, self.no_warp = frame_delta, no_warp
         self.size, self.center_crop = size, center_crop      # Resize target (h, w); Crop('center') size of transform_val
@@ -202,8 +240,7 @@ class EvalWindows(PredictWindows):
             right = [torch.zeros(1, 1, device=self.device) for _ in range(n1)]
         else:
             def grid(g, name):
-                t = self.default_grid if g is None else load_grid(self.grid_path(g, name))
-                return t[None].to(self.device)
+                return self.default_grid[None].to(self.device) if g is None else self._grid(g, name)
             left = [grid(g, "grids") for g in p["left_ids"]]
             right = [grid(g, "inv_grids") for g in p["right_ids"]]
         if self.center_crop is not None:                      # Crop(..., 'center') of transform_val (flow/transform.py:183-211)

@@ -13,14 +13,16 @@ BLOCK = 16
 HEIGHT, WIDTH = 1072, 1920  # the geometry get_default_grid() is built for (flow/model.py:11)
 
 
-def motion_vectors_to_grids(motion_vectors, frame_h, frame_w):
+def motion_vectors_to_grids(motion_vectors, frame_h, frame_w, validate=True):
     """motion_vectors: int tensor/array [N, >=7] rows (source, w, h, src_x, src_y, dst_x, dst_y, ...).
-    Returns (grid, inv_grid): float64 CUDA tensors [67, 120, 2], last dim (x, y) in [-1, 1]."""
+    Returns (grid, inv_grid): float64 CUDA tensors [67, 120, 2], last dim (x, y) in [-1, 1].
+    validate=False skips the two assertions of the reference's script on the table's contents -- they read the table on the host, a
+    synchronisation; flow/motion.py turns them off for device tables the block matcher wrote (source -1, 16 x 16 by construction)."""
     lib = _lib.load()
     mv = torch.as_tensor(np.asarray(motion_vectors) if not isinstance(motion_vectors, torch.Tensor) else motion_vectors)
     if mv.numel() and (mv.dim() != 2 or mv.shape[1] < 7):
         raise RuntimeError(f"motion vectors must be [N, >=7], got {tuple(mv.shape)}")
-    if mv.numel():
+    if validate and mv.numel():
         if not bool((mv[:, 0] == -1).all()):
             raise AssertionError("only past-frame references (source == -1) are supported")       # :27
         if not bool(((mv[:, 1] == BLOCK) & (mv[:, 2] == BLOCK)).all()):

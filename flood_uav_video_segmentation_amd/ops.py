@@ -396,6 +396,27 @@ def iou_hist(pred_u8, target_u8, classes, ignore_index=255, hist=None):
     return hist
 
 
+# ------------------------------------------------------------------------------------------ block motion estimation
+def block_match(cur, ref, search=16, penalty=0, return_cost=False):
+    """Full-search block matching of two uint8 frames [H,W] (luma) or [H,W,3] (RGB as decoded), `ref` the past frame: the motion-vector
+    table int32 [H//16 * W//16, 7] that flow.grids.motion_vectors_to_grids takes (definition: include/floodseg_test.h, block_match).
+    return_cost: also the winning costs, int32 [H//16 * W//16]."""
+    lib = _lib.load()
+    dev = one_device(cur, ref, what="floodseg.block_match")
+    if cur.dtype != torch.uint8 or ref.dtype != torch.uint8:
+        raise RuntimeError(f"floodseg.block_match: frames must be uint8, got {cur.dtype} and {ref.dtype}")
+    if cur.shape != ref.shape or cur.dim() not in (2, 3) or (cur.dim() == 3 and cur.shape[2] != 3):
+        raise RuntimeError(f"floodseg.block_match: frames must be two [H,W] or [H,W,3] tensors of one size, got {tuple(cur.shape)} and {tuple(ref.shape)}")
+    h, w = int(cur.shape[0]), int(cur.shape[1])
+    with torch.cuda.device(dev):
+        cur, ref = cur.contiguous(), ref.contiguous()
+        n = (h // 16) * (w // 16)
+        mv = torch.empty((n, 7), dtype=torch.int32, device=dev)
+        cost = torch.empty((n,), dtype=torch.int32, device=dev) if return_cost else None
+        check(lib.fs_block_match(ptr(cur), ptr(ref), h, w, 3 if cur.dim() == 3 else 1, int(search), int(penalty), ptr(mv), ptr(cost), stream_ptr()))
+    return (mv, cost) if return_cost else mv
+
+
 # ------------------------------------------------------------------------------------------ single-frame multi-scale test
 def ms_prepare(raw, new_hw, padded_hw, mean, std, flip=True):
     """One scale's network input from the raw 0-255 frame [3,H,W] (base/foundation.py:193-200, 267-273, 300-306): resized to

@@ -2,7 +2,9 @@
  * floodseg_test.h -- op-level hooks of libfloodseg.so: the building blocks behind the networks (implicit-GEMM conv, Winograd forms,
  * stem, pooling, attention, layout copies, the Segmenter's LayerNorm, Linear / split-K merges, qkv + attention, mask head, patchify
  * and token assembly, and the CNN heads' pyramid, classifier and concatenated-K shortcut kernels), for the parity tests
- * (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py, tests/test_gpu_head_ops.py) and the measurement tools (tools/).
+ * (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py, tests/test_gpu_head_ops.py) and the measurement tools (tools/).  The table
+ * also carries EXTENSION OPS: product features that have no reference call site (block matching, flow/motion.py) and therefore no
+ * place in the capped export list of floodseg.h; the Python package reaches them like any other function.
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table is append-only; `size` is sizeof(fs_test_api) of the library that was built, so a
@@ -178,6 +180,17 @@ typedef struct fs_test_api {
     int (*ppm_head)(const float* T, int ld, const float* reduced, int Cr, const float* zw, const void* zw_planes, const int* bins,
                     const float* scale, const float* shift, int B, int H, int W, int C, int relu, const float* cls_w, const float* cls_b,
                     float* logits, int K, float* workspace, fs_stream stream);
+    /* ---- Extension ops: product features that no reference call site binds to (the exported surface of floodseg.h is capped). */
+    /* Full-search block matching (csrc/motion_ops.hip): cur, ref = two uint8 device frames of one size, luma [H][W] (channels = 1) or
+     * RGB [H][W][3] (channels = 3, reduced to Y = (77 R + 150 G + 29 B + 128) >> 8); ref is the PAST frame.  Blocks are 16 x 16,
+     * hb = H / 16, wb = W / 16 (a remainder strip belongs to no block but is searched).  For every block the winner among the
+     * displacements |dx|, |dy| <= search (1..32) whose 16 x 16 window lies inside ref minimises, lexicographically,
+     * (SAD + penalty (|dx| + |dy|), |dx| + |dy|, dy, dx), penalty 0..255.  mv = int32 [hb * wb][7], block raster order, rows
+     * (-1, 16, 16, src_x, src_y, dst_x, dst_y) with dst = the block centre and src = dst + (dx, dy): the table fs_mv_to_grids takes.
+     * cost = int32 [hb * wb] winning costs, or NULL.  Integer arithmetic throughout: results are exact.  H, W >= 16 and
+     * H * W * channels < 2^31; anything else is refused before a launch. */
+    int (*block_match)(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int32_t* mv, int32_t* cost,
+                       fs_stream stream);
 } fs_test_api;
 
 const fs_test_api* fs_test_hooks(void);

@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -97,7 +97,7 @@ def main():
         return step
 
     psp = None
-    if any(want(k) for k in ("cfg0", "cfg1", "cfg4", "feat", "crops", "crops_cached", "ms1", "ms6")):
+    if any(want(k) for k in ("cfg0", "cfg1", "cfg4", "feat", "crops", "crops_cached", "ms1", "ms6", "motion")):
         psp = FlowPSPNet(HP(50)).eval()
         psp.load_state_dict(synth.make_pspnet_state(50, 5, 0))
 
@@ -184,6 +184,35 @@ def main():
         rows.append((f"  new kernels alone (prepare + fuse + accumulate): {100 * t_new / t:.1f} % of the frame", 1 / t_new, t_new * 1e3))
         rows.append(("  existing ops per crop and flip (resize + softmax_accumulate only)", 1 / t_old, t_old * 1e3))
         del ev, geo, canvas, count
+    if want("motion"):
+        # block motion estimation (csrc/motion_ops.hip, flow/motion.py): one 1080 x 1920 frame pair per call, every loop >= 0.5 s; a
+        # full search does the same work whatever the frames hold.  Beside it the window that consumes four pairs' grids.
+        from flood_uav_video_segmentation_amd.flow import motion
+        gen = torch.Generator().manual_seed(1400)
+        rgb = [torch.randint(0, 256, (1080, 1920, 3), generator=gen, dtype=torch.uint8).to(dev) for _ in range(2)]
+        luma = [f[..., 1].contiguous() for f in rgb]
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+        pairs_ms = {}
+        for search in (8, 16, 32):
+            for name, (a, b) in (("luma", luma), ("RGB", rgb)):
+                t = timed(lambda i, a=a, b=b, search=search: ops.block_match(a, b, search=search))
+                rows.append((f"block_match 1080x1920 R={search:2d} {name} input (pairs/s)", 1 / t, t * 1e3))
+                t = timed(lambda i, a=a, b=b, search=search: motion.estimate_grids(a, b, search=search))
+                rows.append((f"  estimate_grids (matcher + grid producer) R={search:2d} {name}", 1 / t, t * 1e3))
+                pairs_ms[(search, name)] = t * 1e3
+        fm = FlowModel(psp, feature_based=False, no_warp=False).eval()
+        t_win = timeit(window(fm, (wl, wr)), st)
+        lows = psp.segment(keys[0:1], keys[1:2])
+        t_tail = timed(lambda i: ops.seg_tail(lows[0:1], lows[1:2], wl, wr, N, (713, 713), False, want_logits=True, want_mask=True))
+        rows.append(("warp window 713x713 (configs[1] geometry, logit warp), frames/s", N / t_win, t_win * 1e3))
+        rows.append(("  its seg tail alone (warp + blend + upsample + argmax on held logits)", 1 / t_tail, t_tail * 1e3))
+        for search in (8, 16, 32):
+            four = 4 * pairs_ms[(search, "RGB")]
+            rows.append((f"  four RGB pairs' grids at R={search}: {100 * four / (t_win * 1e3):.2f} % of the window, {four / (t_tail * 1e3):.2f} x its seg tail",
+                         1e3 / four, four))
     del psp
     if want("cfg2"):
         dl3 = FlowDeepLabv3(HP(101)).eval()
@@ -211,7 +240,7 @@ def main():
         rows.append(("(extra) Segmenter ViT-B/32 per-frame (as model/vit.py builds it)", 1 / t, t * 1e3))
     print(f"{'config':68s} {'FPS':>9s} {'ms/step':>9s}")
     for name, fps, ms in rows:
-        print(f"{name:68s} {fps:9.1f} {ms:9.3f}")
+        print(f"{name:68s} {fps:9.1f} {ms:9.4f}" if ms < 1 else f"{name:68s} {fps:9.1f} {ms:9.3f}")
     if args.json and rows:
         import json
         print(json.dumps({"config": rows[-1][0], "options": list(HP.OPTIONS), "value": round(rows[-1][1], 2), "unit": "frames/s",

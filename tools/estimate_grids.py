@@ -1,0 +1,52 @@
+#!/usr/bin/env python3
+"""Offline replacement for the reference's dataset/flow/extract_motion_vectors.py on a FRAME FOLDER: writes
+
+    <DATA_ROOT>/frames/<VIDEO_ID>/grids/<i>.npy  and  inv_grids/<i>.npy      (float64 [67,120,2], the reference's format)
+
+for every <DATA_ROOT>/frames/<VIDEO_ID>/images/<i>.jpg, from block matching of frame i against frame i-1 on the GPU
+(flow/motion.py) instead of an H.264 stream's vectors.  Files that exist are skipped, as the reference's script does.  Frame 0
+and a frame whose predecessor is missing get the default grid.  Encoder vectors and these differ (rate-distortion choices,
+sub-pel vectors, I-frames); the table -> grid step is the same code.
+
+    python tools/estimate_grids.py dataset/flow florida-01 --search 16 --penalty 0
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.grids import save_grid  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.motion import GridEstimator  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("data_root")
+    ap.add_argument("video_id")
+    ap.add_argument("--search", type=int, default=16)
+    ap.add_argument("--penalty", type=int, default=0)
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+
+    folder = os.path.join(args.data_root, "frames", args.video_id)
+    ids = sorted(int(n[:-4]) for n in os.listdir(os.path.join(folder, "images")) if n.endswith(".jpg") and n[:-4].isdigit())
+    for name in ("grids", "inv_grids"):
+        os.makedirs(os.path.join(folder, name), exist_ok=True)
+    frames = PredictWindows(args.data_root, args.video_id, no_warp=True, device=args.device)  # paths + decoding only
+    estimator = GridEstimator(args.search, args.penalty)
+    written = 0
+    for i in ids:
+        paths = [frames.grid_path(i, "grids"), frames.grid_path(i, "inv_grids")]
+        if all(os.path.exists(p) for p in paths):
+            continue
+        for path, grid in zip(paths, estimator.grids_for(i, frames.raw_frame)):
+            if not os.path.exists(path):
+                save_grid(path, grid)
+                written += 1
+    print(f"estimate_grids: {len(ids)} frames, {written} files written under {folder}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
