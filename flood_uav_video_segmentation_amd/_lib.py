@@ -131,9 +131,24 @@ _HOOKS = [
     ("block_match", c_int, [c_void, c_void] + [c_int] * 5 + [c_void, c_void, c_void]),
 ]
 
+# members of fs_ext_api (include/floodseg_test.h), the append-only extension table the library places right behind the frozen
+# fs_test_api, in declaration order after `magic` and `size`; reached as load().fs_<name>(...) like the hooks above
+_EXT_HOOKS = [
+    ("frame_prepare", c_int, [c_void, c_void, c_void] + [c_int] * 5 + [c_void, c_void, c_void, c_int, c_int, c_void]),
+]
+EXT_MAGIC = 0x4653455854414231  # FS_EXT_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
+
+
+class FsExtApi(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT_HOOKS]
+
+
+class FsHookTables(ctypes.Structure):
+    _fields_ = [("test", FsTestApi), ("ext", FsExtApi)]
 
 
 class _Library:
@@ -143,8 +158,18 @@ class _Library:
     def __init__(self, cdll):
         self._cdll = cdll
         self._hooks = None
+        self._ext = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT_HOOKS):
+            if self._ext is None:
+                tables = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables)).contents
+                if tables.test.size != ctypes.sizeof(FsTestApi) or tables.ext.magic != EXT_MAGIC or tables.ext.size < ctypes.sizeof(FsExtApi):
+                    raise RuntimeError(f"floodseg: the library has no extension table, or an older one than this binding ({name} is missing)")
+                self._ext = tables.ext
+            fn = getattr(self._ext, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and name != "fs_test_hooks" and any(name == "fs_" + h[0] for h in _HOOKS):
             if self._hooks is None:
                 table = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsTestApi)).contents
@@ -188,6 +213,11 @@ def exported_symbols():
 def hook_names():
     """Members of fs_test_api after `size`, in declaration order."""
     return [h[0] for h in _HOOKS]
+
+
+def ext_hook_names():
+    """Members of fs_ext_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT_HOOKS]
 
 
 def check(rc):

@@ -366,9 +366,23 @@ static int fs_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, 
     if ((int64_t)H * W * channels >= ((int64_t)1 << 31)) return fs::fail("fs_block_match: frame too large (%d x %d x %d bytes pass 2^31)", H, W, channels);
     return fs::launch_block_match(cur, ref, H, W, channels, search, penalty, mv, cost, S(stream));
 }
+static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
+                            const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
+    if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
+    if (format < 0 || format > 2) return fs::fail("fs_frame_prepare: format must be 0 (RGB24), 1 (NV12) or 2 (I420), got %d", format);
+    if (matrix != 0 && matrix != 1) return fs::fail("fs_frame_prepare: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
+    if (full_range != 0 && full_range != 1) return fs::fail("fs_frame_prepare: range must be 0 (limited) or 1 (full), got %d", full_range);
+    if (H < 1 || W < 1 || h < 1 || w < 1) return fs::fail("fs_frame_prepare: empty frame (%d x %d -> %d x %d)", H, W, h, w);
+    if ((int64_t)H * W * 3 >= ((int64_t)1 << 31)) return fs::fail("fs_frame_prepare: frame too large (%d x %d x 3 bytes pass 2^31)", H, W);
+    if ((int64_t)h * w * 3 >= ((int64_t)1 << 31)) return fs::fail("fs_frame_prepare: output too large (3 x %d x %d values pass 2^31)", h, w);
+    if (format != 0 && (!u || (format == 2 && !v))) return fs::fail("fs_frame_prepare: null chroma pointer for a YUV format");
+    if (reinterpret_cast<uintptr_t>(out) % 4 != 0) return fs::fail("fs_frame_prepare: out is not aligned to a float");
+    return fs::launch_frame_prepare(frame, u, v, format, matrix, full_range, H, W, mean, std, out, h, w, S(stream));
+}
 
 FS_API const fs_test_api* fs_test_hooks(void) {
-    static const fs_test_api api = {
+    // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
+    static const fs_hook_tables tables = {{
         sizeof(fs_test_api),
         fs_pack_conv_weight,
         fs_conv2d_nhwc,
@@ -408,6 +422,10 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_ppm_head_workspace_floats,
         fs_ppm_head,
         fs_block_match,
-    };
-    return &api;
+    }, {
+        FS_EXT_MAGIC,
+        sizeof(fs_ext_api),
+        fs_frame_prepare,
+    }};
+    return &tables.test;
 }

@@ -274,6 +274,12 @@ int launch_mv_to_grids(const int* mv, int n, int stride, int hb, int wb, int bs,
 // block raster order (the table launch_mv_to_grids takes), cost = int32 [H/16 * W/16] winning costs or nullptr (motion_ops.hip)
 int launch_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int R, int lambda, int* mv, int* cost,
                        hipStream_t s);
+// Frame ingest (ingest_ops.hip): one decoded uint8 frame -> normalised NCHW fp32 [3][h][w].  format 0: RGB24 [H][W][3] in `frame`;
+// 1: NV12, `frame` = Y [H][W], u = interleaved UV [ceil(H/2)][ceil(W/2)][2] (v unused); 2: I420, u and v = [ceil(H/2)][ceil(W/2)] each.
+// matrix 0 / 1 (BT.601 / BT.709) and full_range 0 / 1 pick the integer conversion of include/floodseg_test.h.  mean, std: 3 device
+// floats each.  Arguments are validated by the caller (api_test.hip).
+int launch_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
+                         const float* mean, const float* std, float* out, int h, int w, hipStream_t s);
 // intersection / union / target histograms (util/util.py:52-63), int64[3][K] accumulated.
 int launch_iou_hist(const uint8_t* pred, const uint8_t* target, int64_t numel, int K, int ignore_index,
                     long long* hist3K, hipStream_t s);

@@ -4,10 +4,12 @@ transforms flow/base.py:426-431 -> Resize, ToTensor, Normalize of flow/transform
 
 `PredictWindows` mirrors `split == "predict"`, `EvalWindows` the labelled `val` / `test` splits that feed
 validation_step / test_step (flow/base.py:143-176); the random training sampling is out of scope.  Decoding is done with
-PIL (the reference uses skimage.io.imread), resize + normalisation run on the GPU.
+PIL (the reference uses skimage.io.imread), resize + normalisation run on the GPU in one launch (ops.prepare_frame).
+`RawVideoWindows` (extension) yields the same windows from one headerless raw video file (NV12, I420 or RGB24).
 """
 import os
 import random
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -88,14 +90,32 @@ class PredictWindows:
         ids = [f_index + i + 1 for i in range(self.frame_delta - 1)]
         return ids, ids[::-1]
 
+    def _decode(self, f_id):
+        """Decode frame `f_id` on the host and upload it: uint8 [H,W,3] on the device."""
+        from PIL import Image
+
+        return torch.from_numpy(np.array(Image.open(self.frame_path(f_id)).convert("RGB"))).to(self.device)
+
+    def _decoded(self, f_id):
+        """The decoded frame on the device, decoded and uploaded ONCE: the last frame_delta + 2 frames (a window touches
+        frame_delta + 1) are kept by (video, frame id), so the key frame the grid estimator asks for (raw_frame) and the one the
+        network gets (_frame), in this window and as the next window's previous key, are one decode and one copy."""
+        cache = self.__dict__.setdefault("_decoded_frames", OrderedDict())
+        key = (self.video_id, f_id)
+        if key in cache:
+            cache.move_to_end(key)
+            return cache[key]
+        frame = cache[key] = self._decode(f_id)
+        while len(cache) > self.frame_delta + 2:
+            cache.popitem(last=False)
+        return frame
+
     def raw_frame(self, f_id):
         """The decoded uint8 frame [H,W,3] on the device, before Resize and normalisation (what the grid estimator sees, as
         mvextractor sees the decoded picture); None when the image does not exist."""
-        from PIL import Image
-
         if f_id < 0 or not os.path.exists(self.frame_path(f_id)):
             return None
-        return torch.from_numpy(np.array(Image.open(self.frame_path(f_id)).convert("RGB"))).to(self.device)
+        return self._decoded(f_id)
 
     def _grid(self, g, name):
         """Grid `g` of grids/ (name "grids") or inv_grids/ as the float32 [1,67,120,2] device tensor of an item."""
@@ -108,16 +128,9 @@ class PredictWindows:
         return pair[0 if name == "grids" else 1].float()[None]
 
     def _frame(self, f_id):
-        from PIL import Image
-
-        img = np.array(Image.open(self.frame_path(f_id)).convert("RGB"))  # writable copy
-        x = torch.from_numpy(img).to(self.device).permute(2, 0, 1)[None].float()       # ToTensor (flow/transform.py:26-51)
-        if self.size is not None and tuple(x.shape[2:]) != tuple(self.size):
-            # Resize: cv2.INTER_LINEAR on the uint8 image (:91-106) = half-pixel bilinear, result stored back as uint8
-            x = ops.resize_bilinear(x, self.size, align_corners=False).round_().clamp_(0, 255)
-        mean = torch.tensor(MEAN, device=self.device).view(1, 3, 1, 1)
-        std = torch.tensor(STD, device=self.device).view(1, 3, 1, 1)
-        return (x - mean) / std                                                          # Normalize (:56-86)
+        """ToTensor, Resize (cv2.INTER_LINEAR on the uint8 image = half-pixel bilinear, stored back as uint8) and Normalize
+        (flow/transform.py:26-106) of the decoded frame: one launch (ops.prepare_frame)."""
+        return ops.prepare_frame(self._decoded(f_id), self.size, MEAN, STD)
 
     def __getitem__(self, index):
         if not 0 <= index < self.length:
@@ -257,3 +270,85 @@ class EvalWindows(PredictWindows):
                 left, right = crop_motion_vector(left, right, h, w, ch, cw, ho, wo)
         return {"frame_prev": frame_prev, "frame_next": frame_next, "mvs_left": left, "mvs_right": right, "label": label,
                 "left_index": torch.tensor([p["l"]]), "right_index": torch.tensor([p["r"]])}
+
+
+RAW_PIX_FMTS = ("nv12", "i420", "rgb24")
+
+
+def raw_frame_bytes(height, width, pix_fmt):
+    """Bytes of one frame of a headerless raw video (ffmpeg -f rawvideo): chroma planes of the 4:2:0 formats round up."""
+    if pix_fmt == "rgb24":
+        return height * width * 3
+    return height * width + 2 * ((height + 1) // 2) * ((width + 1) // 2)
+
+
+class RawVideoWindows(PredictWindows):
+    """The windows of PredictWindows (frame_prev, frame_next, mvs_left, mvs_right, frame_id, key_ids) over ONE headerless raw video
+    file, as `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24` writes it (extension: the reference reads JPEG folders only).
+
+    pix_fmt "nv12" (Y plane + interleaved UV), "i420" (= yuv420p: Y, U, V planes) or "rgb24"; frames are read through numpy.memmap and
+    uploaded once each; the network's input comes from ops.prepare_frame (`matrix`, `full_range`: the integer YUV -> RGB conversion of
+    include/floodseg_test.h).  len = frames // frame_delta; a file that is not a whole number of frames raises.  A raw file has no grid
+    folders: the grids are estimated (grids="estimate", flow/motion.py) unless no_warp; "files" raises.
+
+    For the YUV formats the block matcher gets the stream's Y plane AS IT IS (its one-channel route).  These grids DIFFER from grids
+    estimated on the RGB conversion of the same video: there the matcher reduces RGB to its own luma (77 R + 150 G + 29 B + 128) >> 8,
+    which is not the stream's Y (range, matrix and the clipping of the conversion all enter)."""
+
+    def __init__(self, path, height, width, pix_fmt, frame_delta=5, no_warp=False, size=None, grids="estimate", search=16, penalty=0,
+                 matrix="bt709", full_range=False, device="cuda"):
+        if pix_fmt not in RAW_PIX_FMTS:
+            raise ValueError(f"RawVideoWindows: pix_fmt must be one of {RAW_PIX_FMTS}, got {pix_fmt!r}")
+        if grids == "files":
+            raise ValueError('RawVideoWindows: a raw video file has no grids/ folders; use grids="estimate" (or no_warp=True)')
+        if matrix not in ("bt601", "bt709"):
+            raise ValueError(f'RawVideoWindows: matrix must be "bt601" or "bt709", got {matrix!r}')
+        if height < 1 or width < 1 or frame_delta < 1:
+            raise ValueError(f"RawVideoWindows: bad geometry {height} x {width}, frame_delta {frame_delta}")
+        self.estimator = _grid_source(grids, search, penalty)
+        if not no_warp:
+            from .motion import check_geometry
+
+            check_geometry(height, width)
+        self.path, self.video_id = path, path
+        self.height, self.width, self.pix_fmt = int(height), int(width), pix_fmt
+        self.matrix, self.full_range = matrix, bool(full_range)
+        self.frame_delta, self.no_warp, self.size, self.device = frame_delta, no_warp, size, device
+        self.frame_bytes = raw_frame_bytes(self.height, self.width, pix_fmt)
+        total = os.path.getsize(path)
+        if total == 0 or total % self.frame_bytes:
+            raise ValueError(f"RawVideoWindows: {path} holds {total} bytes, not a whole number of {self.height} x {self.width} {pix_fmt} "
+                             f"frames of {self.frame_bytes} bytes")
+        self.frames = total // self.frame_bytes
+        self.length = self.frames // frame_delta
+        self._file = np.memmap(path, dtype=np.uint8, mode="r", shape=(self.frames, self.frame_bytes))
+
+    def frame_path(self, f_id):
+        return f"{self.path}[{f_id}]"
+
+    def _complete(self, f_id):
+        return 0 <= f_id < self.frames
+
+    def _decode(self, f_id):
+        """Frame f_id's bytes on the device (one copy): uint8 [frame_bytes]."""
+        return torch.from_numpy(np.array(self._file[f_id])).to(self.device)
+
+    def planes(self, f_id):
+        """(frame, chroma) of frame f_id as ops.prepare_frame takes them: views of the one uploaded buffer."""
+        buf = self._decoded(f_id)
+        h, w = self.height, self.width
+        if self.pix_fmt == "rgb24":
+            return buf.view(h, w, 3), None
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        y = buf[:h * w].view(h, w)
+        if self.pix_fmt == "nv12":
+            return y, buf[h * w:].view(ch, cw, 2)
+        return y, (buf[h * w:h * w + ch * cw].view(ch, cw), buf[h * w + ch * cw:].view(ch, cw))
+
+    def raw_frame(self, f_id):
+        """What the grid estimator sees: the RGB frame [H,W,3], or the Y plane [H,W] of a YUV stream; None past either end."""
+        return self.planes(f_id)[0] if self._complete(f_id) else None
+
+    def _frame(self, f_id):
+        frame, chroma = self.planes(f_id)
+        return ops.prepare_frame(frame, self.size, MEAN, STD, fmt=self.pix_fmt, chroma=chroma, matrix=self.matrix, full_range=self.full_range)

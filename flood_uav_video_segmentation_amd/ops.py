@@ -417,6 +417,65 @@ def block_match(cur, ref, search=16, penalty=0, return_cost=False):
     return (mv, cost) if return_cost else mv
 
 
+# ------------------------------------------------------------------------------------------ frame ingest
+# base/foundation.py:27-31 (the value_scale = 255 statistics every transform chain of the reference normalises with)
+MEAN = [0.485 * 255, 0.456 * 255, 0.406 * 255]
+STD = [0.229 * 255, 0.224 * 255, 0.225 * 255]
+_FORMATS = {"rgb24": 0, "nv12": 1, "i420": 2}
+_MATRICES = {"bt601": 0, "bt709": 1}
+_norm_cache = {}  # (device, mean, std) -> device tensor [2,3]: one host-to-device copy per device and statistics, not one per frame
+
+
+def _norm_constants(dev, mean, std):
+    key = (dev, tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    t = _norm_cache.get(key)
+    if t is None:
+        if len(key[1]) != 3 or len(key[2]) != 3 or min(key[2]) <= 0:
+            raise RuntimeError(f"floodseg.prepare_frame: mean and std must be three values each, std positive, got {mean} and {std}")
+        t = _norm_cache[key] = torch.tensor([key[1], key[2]], dtype=torch.float32).to(dev)
+    return t
+
+
+def prepare_frame(frame, size=None, mean=MEAN, std=STD, fmt="rgb24", chroma=None, matrix="bt601", full_range=False, out=None):
+    """One decoded uint8 frame -> the network's input, float32 [1,3,h,w], in one launch (definition: include/floodseg_test.h,
+    frame_prepare): half-pixel bilinear resize to `size` (None = native), stored as the uint8 image cv2.resize would give (round half
+    to even, clamp), then (x - mean) / std -- transform_predict of the reference (flow/transform.py:26-106).
+    fmt "rgb24": frame = [H,W,3].  "nv12": frame = Y [H,W], chroma = the interleaved UV plane [ceil(H/2), ceil(W/2), 2].  "i420":
+    chroma = (U, V), [ceil(H/2), ceil(W/2)] each.  matrix "bt601" | "bt709" and full_range pick the integer YUV -> RGB conversion.
+    out: a caller-owned contiguous float32 [1,3,h,w] or [3,h,w] destination (one image of a batch tensor)."""
+    lib = _lib.load()
+    if fmt not in _FORMATS:
+        raise RuntimeError(f"floodseg.prepare_frame: fmt must be one of {sorted(_FORMATS)}, got {fmt!r}")
+    if matrix not in _MATRICES:
+        raise RuntimeError(f"floodseg.prepare_frame: matrix must be one of {sorted(_MATRICES)}, got {matrix!r}")
+    planes = [] if chroma is None else list(chroma) if isinstance(chroma, (tuple, list)) else [chroma]
+    dev = one_device(frame, out, *planes, what="floodseg.prepare_frame")
+    if frame.dtype != torch.uint8 or any(p.dtype != torch.uint8 for p in planes):
+        raise RuntimeError(f"floodseg.prepare_frame: frames must be uint8, got {[str(t.dtype) for t in [frame] + planes]}")
+    rgb = fmt == "rgb24"
+    if frame.dim() != (3 if rgb else 2) or (rgb and frame.shape[2] != 3) or frame.numel() == 0:
+        raise RuntimeError(f"floodseg.prepare_frame: a {fmt} frame must be {'[H,W,3]' if rgb else 'the Y plane [H,W]'}, got {tuple(frame.shape)}")
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    want = [] if rgb else [(ch, cw, 2)] if fmt == "nv12" else [(ch, cw), (ch, cw)]
+    if [tuple(p.shape) for p in planes] != want:
+        raise RuntimeError(f"floodseg.prepare_frame: a {H} x {W} {fmt} frame takes chroma {want if want else None}, got {[tuple(p.shape) for p in planes]}")
+    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if h < 1 or w < 1:
+        raise RuntimeError(f"floodseg.prepare_frame: size must be at least 1 x 1, got {h} x {w}")
+    with torch.cuda.device(dev):
+        frame = frame.contiguous()
+        planes = [p.contiguous() for p in planes]
+        if out is None:
+            out = torch.empty((1, 3, h, w), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) not in ((1, 3, h, w), (3, h, w)) or not out.is_contiguous():
+            raise RuntimeError(f"floodseg.prepare_frame: out must be contiguous float32 [1,3,{h},{w}] or [3,{h},{w}], got {out.dtype} {tuple(out.shape)}")
+        norm = _norm_constants(dev, mean, std)
+        check(lib.fs_frame_prepare(ptr(frame), ptr(planes[0]) if planes else None, ptr(planes[1]) if len(planes) > 1 else None, _FORMATS[fmt],
+                                   _MATRICES[matrix], int(bool(full_range)), H, W, ptr(norm[0]), ptr(norm[1]), ptr(out), h, w, stream_ptr()))
+    return out.view(1, 3, h, w)
+
+
 # ------------------------------------------------------------------------------------------ single-frame multi-scale test
 def ms_prepare(raw, new_hw, padded_hw, mean, std, flip=True):
     """One scale's network input from the raw 0-255 frame [3,H,W] (base/foundation.py:193-200, 267-273, 300-306): resized to

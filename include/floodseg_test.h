@@ -4,11 +4,12 @@
  * and token assembly, and the CNN heads' pyramid, classifier and concatenated-K shortcut kernels), for the parity tests
  * (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py, tests/test_gpu_head_ops.py) and the measurement tools (tools/).  The table
  * also carries EXTENSION OPS: product features that have no reference call site (block matching, flow/motion.py) and therefore no
- * place in the capped export list of floodseg.h; the Python package reaches them like any other function.
+ * place in the capped export list of floodseg.h; the Python package reaches them like any other function.  fs_test_api is frozen at
+ * block_match; later extension ops (frame ingest) are members of fs_ext_api, the table right behind it (end of this file).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
- * returns a table of function pointers.  The table is append-only; `size` is sizeof(fs_test_api) of the library that was built, so a
- * caller built against a longer table can tell which members exist.  Conventions (device pointers, fs_stream, return codes,
+ * returns a table of function pointers.  The table was append-only up to block_match and is frozen now; `size` is sizeof(fs_test_api)
+ * of the library that was built.  Conventions (device pointers, fs_stream, return codes,
  * fs_last_error) are those of floodseg.h.  No reference call site binds to anything in this file.
  */
 #ifndef FLOODSEG_TEST_H_
@@ -192,6 +193,43 @@ typedef struct fs_test_api {
     int (*block_match)(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int32_t* mv, int32_t* cost,
                        fs_stream stream);
 } fs_test_api;
+
+/* ---- The extension table.  fs_test_api above is FROZEN at block_match: its members, their order and its size never change again
+ * (callers and tests pin them).  Extension ops added since live in a second, append-only table that the library places directly behind
+ * it: fs_test_hooks() returns the address of fs_hook_tables.test, which is also the address of the fs_hook_tables object, so
+ *     const fs_hook_tables* t = (const fs_hook_tables*)fs_test_hooks();   t->ext.frame_prepare(...)
+ * A library built before this table existed returns a bare fs_test_api: a caller that may meet one checks t->ext.magic == FS_EXT_MAGIC
+ * (and ext.size for the members it needs) before it uses the table; the Python package and the library are built together. */
+#define FS_EXT_MAGIC 0x4653455854414231ull /* "FSEXTAB1" */
+
+typedef struct fs_ext_api {
+    uint64_t magic; /* FS_EXT_MAGIC */
+    size_t size;    /* sizeof(fs_ext_api) of the library that was built */
+
+    /* Frame ingest (csrc/ingest_ops.hip): one decoded uint8 device frame -> the network's input out = fp32 [3][h][w] (NCHW, one image; any
+     * 4-byte aligned address, e.g. one image of a [B][3][h][w] tensor), in one launch.  Per output pixel and channel c:
+     *   x = clamp(round_half_even(bilinear(rgb_c)), 0, 255);  out = (x - mean[c]) / std[c]   (fp32, true division)
+     * where bilinear is the half-pixel (align_corners = 0) resize of fs_resize_bilinear_nchw, operation for operation, on the uint8 taps
+     * as floats; when (h, w) == (H, W) the pixel is its own value (no rounding step is needed).  mean, std: 3 DEVICE floats each.
+     * format 0 = RGB24: frame = interleaved [H][W][3], u = v = NULL.
+     * format 1 = NV12: frame = Y [H][W], u = interleaved UV plane [ceil(H/2)][ceil(W/2)][2], v ignored.
+     * format 2 = I420: frame = Y [H][W], u, v = [ceil(H/2)][ceil(W/2)] each.
+     * Chroma is replicated: luma pixel (y, x) takes chroma sample (y >> 1, x >> 1); odd H and W are allowed.  YUV -> RGB is OUR DEFINITION,
+     * in int32 with an arithmetic shift, each result clipped to [0, 255]; d = U - 128, e = V - 128:
+     *   matrix 0 (BT.601), full_range 0: c = 298 (Y - 16); R = (c + 409 e + 128) >> 8; G = (c - 100 d - 208 e + 128) >> 8; B = (c + 516 d + 128) >> 8
+     *   matrix 0 (BT.601), full_range 1: c = 256 Y;        R = (c + 359 e + 128) >> 8; G = (c -  88 d - 183 e + 128) >> 8; B = (c + 454 d + 128) >> 8
+     *   matrix 1 (BT.709), full_range 0: c = 298 (Y - 16); R = (c + 459 e + 128) >> 8; G = (c -  55 d - 136 e + 128) >> 8; B = (c + 541 d + 128) >> 8
+     *   matrix 1 (BT.709), full_range 1: c = 256 Y;        R = (c + 403 e + 128) >> 8; G = (c -  48 d - 120 e + 128) >> 8; B = (c + 475 d + 128) >> 8
+     * H, W, h, w >= 1, H * W * 3 < 2^31 and h * w * 3 < 2^31; a null pointer (a chroma pointer the format needs included) and an unknown
+     * format, matrix or range are refused before a launch. */
+    int (*frame_prepare)(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
+                         const float* mean, const float* std, float* out, int h, int w, fs_stream stream);
+} fs_ext_api;
+
+typedef struct fs_hook_tables {
+    fs_test_api test;
+    fs_ext_api ext;
+} fs_hook_tables;
 
 const fs_test_api* fs_test_hooks(void);
 

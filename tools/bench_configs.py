@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -213,6 +213,73 @@ def main():
             four = 4 * pairs_ms[(search, "RGB")]
             rows.append((f"  four RGB pairs' grids at R={search}: {100 * four / (t_win * 1e3):.2f} % of the window, {four / (t_tail * 1e3):.2f} x its seg tail",
                          1e3 / four, four))
+    if want("ingest"):
+        # frame ingest (csrc/ingest_ops.hip, ops.prepare_frame): one decoded 1080 x 1920 uint8 frame -> the network's input, against the
+        # chain flow/dataset.py ran before the op existed (restated here as the A/B baseline), on the same frames, alternating, every
+        # loop >= 0.5 s.  Bytes per frame: what the op must read and write once.
+        import tempfile
+
+        import numpy as np
+        from flood_uav_video_segmentation_amd.flow.dataset import MEAN, STD, PredictWindows
+        gen = torch.Generator().manual_seed(1500)
+        rgb1080 = [torch.randint(0, 256, (1080, 1920, 3), generator=gen, dtype=torch.uint8).to(dev) for _ in range(2)]
+        rgb1072 = [f[:1072].contiguous() for f in rgb1080]
+        ys = [f[..., 1].contiguous() for f in rgb1080]
+        uvs = [f[::2, ::2, :2].contiguous() for f in rgb1080]
+        out = torch.empty((2, 3, 1072, 1920), dtype=torch.float32, device=dev)
+
+        def old_chain(img, size):  # PredictWindows._frame before ops.prepare_frame: six passes and two synchronous host-to-device copies
+            x = img.permute(2, 0, 1)[None].float()
+            if size is not None and tuple(x.shape[2:]) != tuple(size):
+                x = ops.resize_bilinear(x, size, align_corners=False).round_().clamp_(0, 255)
+            mean = torch.tensor(MEAN, device=img.device).view(1, 3, 1, 1)
+            std = torch.tensor(STD, device=img.device).view(1, 3, 1, 1)
+            return (x - mean) / std
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+        size = (1072, 1920)
+        cases = [("RGB24 1080 -> 1072 rows", lambda i: ops.prepare_frame(rgb1080[i % 2], size, out=out[i % 2]), lambda i: old_chain(rgb1080[i % 2], size), 1080 * 1920 * 3),
+                 ("RGB24 native 1072 rows", lambda i: ops.prepare_frame(rgb1072[i % 2], size, out=out[i % 2]), lambda i: old_chain(rgb1072[i % 2], size), 1072 * 1920 * 3),
+                 ("NV12 1080 -> 1072 rows", lambda i: ops.prepare_frame(ys[i % 2], size, fmt="nv12", chroma=uvs[i % 2], matrix="bt709", out=out[i % 2]), None,
+                  1080 * 1920 * 3 // 2)]
+        for name, new_fn, old_fn, read_bytes in cases:
+            assert old_fn is None or torch.equal(new_fn(0).view(1, 3, 1072, 1920), old_fn(0))
+            t_new = [timed(new_fn)]
+            t_old = [timed(old_fn)] if old_fn else []
+            t_new.append(timed(new_fn))      # alternating: new, old, new, old
+            if old_fn:
+                t_old.append(timed(old_fn))
+            tn = min(t_new)
+            moved = read_bytes + 3 * 1072 * 1920 * 4
+            rows.append((f"prepare_frame {name}: {moved / 1e6:.1f} MB, {moved / tn / 1e12:.2f} TB/s (host clock)", 1 / tn, tn * 1e3))
+            if old_fn:
+                to = min(t_old)
+                rows.append((f"  the torch chain it replaces (same frames, same call): {to / tn:.1f} x the time", 1 / to, to * 1e3))
+        # one PredictWindows item with grids="estimate" from a synthetic image folder, with and without the shared decode (HOST-bound:
+        # PIL decodes on the CPU; the figure shows decodes saved, not GPU time)
+        with tempfile.TemporaryDirectory() as root:
+            from PIL import Image
+            folder = os.path.join(root, "frames", "clip", "images")
+            os.makedirs(folder)
+            rng = np.random.RandomState(3)
+            base = (synth.make_clip(1, (1080 + 64, 1920 + 64), seed=1501)[0] * 50 + 120).clamp(0, 255).byte().permute(1, 2, 0).numpy()
+            for i in range(11):
+                Image.fromarray(np.ascontiguousarray(base[2 * i:2 * i + 1080, 3 * i:3 * i + 1920])).save(os.path.join(folder, f"{i}.jpg"), quality=90)
+            del rng
+
+            class TwiceDecoded(PredictWindows):  # the parent's behaviour: _frame and raw_frame each decode and upload
+                def _decoded(self, f_id):
+                    return self._decode(f_id)
+
+            for label, cls in (("shared decode", PredictWindows), ("every use decodes (parent)", TwiceDecoded)):
+                def item_step(i, cls=cls):
+                    ds = cls(root, "clip", frame_delta=5, size=size, grids="estimate")   # a fresh dataset: nothing cached across steps
+                    ds[i % 2]
+                    torch.cuda.current_stream().synchronize()
+                t = timeit(item_step, steps=6, warmup=2)
+                rows.append((f"PredictWindows item, grids=estimate, JPEG folder (host-bound), {label}", 1 / t, t * 1e3))
     del psp
     if want("cfg2"):
         dl3 = FlowDeepLabv3(HP(101)).eval()

@@ -6,6 +6,10 @@ frames in between and writes the colourised masks.
     python tools/predict_video.py --data-root dataset/flow --video-id florida-01 --frame-delta 5 \\
         --arch pspnet --layers 50 --ckpt logs/<run>/last.ckpt --out out/florida-01
 
+    python tools/predict_video.py --raw clip.nv12 --raw-size 1080 1920 --pix-fmt nv12 --matrix bt709 --arch pspnet --ckpt ... --out out/clip
+
+`--grids estimate` (with `--search`, `--penalty`) takes the grids from block matching of the decoded frames instead of the grids/
+folders; a raw video file (`--raw`, as `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24` writes it) always does.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -23,7 +27,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
@@ -45,9 +49,9 @@ def load_weights(net, args):
     net.load_state_dict(state)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--data-root", required=True)
+    ap.add_argument("--data-root", help="folder input: <data-root>/frames/<video-id>/...")
     ap.add_argument("--video-id", default="florida-01")                      # data.predict_v_id
     ap.add_argument("--frame-delta", type=int, default=5)                    # data.frame_delta
     ap.add_argument("--arch", choices=("pspnet", "deeplabv3"), default="pspnet")
@@ -64,9 +68,35 @@ def main():
     ap.add_argument("--out", help="directory for <frame>.png (model.save_images); omit to only time and score")
     ap.add_argument("--no-metrics", action="store_true")                     # model.compute_metrics False
     ap.add_argument("--no-keyframe-cache", action="store_true", help="segment both key frames of every window (reference behaviour)")
-    args = ap.parse_args()
+    ap.add_argument("--grids", choices=("files", "estimate"), help="grids/ and inv_grids/ folders (default for a frame folder), or block "
+                    "matching of the decoded frames (flow/motion.py; the only source for --raw)")
+    ap.add_argument("--search", type=int, default=16, help="--grids estimate: search range in pixels, 1..32")
+    ap.add_argument("--penalty", type=int, default=0, help="--grids estimate: cost per pixel of displacement, 0..255")
+    ap.add_argument("--raw", metavar="FILE", help="raw video input (ffmpeg -f rawvideo) instead of --data-root / --video-id")
+    ap.add_argument("--raw-size", type=int, nargs=2, metavar=("H", "W"), help="--raw: frame height and width")
+    ap.add_argument("--pix-fmt", choices=("nv12", "i420", "rgb24"), default="nv12", help="--raw: pixel format (i420 = ffmpeg's yuv420p)")
+    ap.add_argument("--matrix", choices=("bt601", "bt709"), default="bt709", help="--raw, YUV formats: conversion matrix")
+    ap.add_argument("--full-range", action="store_true", help="--raw, YUV formats: full-range (JPEG) levels instead of limited")
+    args = ap.parse_args(argv)
     if not args.synthetic_weights and not args.ckpt:
         ap.error("give --ckpt or --synthetic-weights")
+    if args.raw:
+        if args.data_root:
+            ap.error("--raw replaces --data-root / --video-id")
+        if not args.raw_size:
+            ap.error("--raw needs --raw-size H W")
+        if args.grids == "files":
+            ap.error("--raw has no grids/ folders: --grids estimate (the default there) or --no-warp")
+        args.grids = "estimate"
+    elif not args.data_root:
+        ap.error("give --data-root (a frame folder) or --raw (a raw video file)")
+    else:
+        args.grids = args.grids or "files"
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank, local_rank, world = shard.init()
     torch.cuda.set_device(local_rank)
@@ -80,7 +110,13 @@ def main():
     fm = FlowModel(net, feature_based=args.feature_based, no_warp=args.no_warp).eval()
     pred = FlowPredictor(fm, classes=args.classes, out_size=tuple(args.size), crop=None if args.no_cropping else tuple(args.crop),
                          compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache)
-    ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size))
+    if args.raw:
+        ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
+                             size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
+                             full_range=args.full_range)
+    else:
+        ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
+                            grids=args.grids, search=args.search, penalty=args.penalty)
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -121,7 +157,7 @@ def main():
     hist, frames, seconds = shard.reduce_run(hist.cpu() if world == 1 else hist, frames, seconds, "cpu" if world == 1 else torch.device("cuda", local_rank))
     if rank == 0:
         h = hist.double()
-        line = f"{frames} frames of {args.video_id} in {seconds:.2f} s = {frames / seconds:.1f} FPS on {world} GPU(s)"
+        line = f"{frames} frames of {args.raw or args.video_id} in {seconds:.2f} s = {frames / seconds:.1f} FPS on {world} GPU(s)"
         if not args.no_metrics and float(h[2].sum()) > 0:
             inter, union, target = h[0], h[1] + h[2] - h[0], h[2]
             line += (f"; temporal consistency mIoU {float((inter / (union + 1e-10)).mean()):.4f}"
