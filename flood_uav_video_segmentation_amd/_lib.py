@@ -135,6 +135,7 @@ _HOOKS = [
 # fs_test_api, in declaration order after `magic` and `size`; reached as load().fs_<name>(...) like the hooks above
 _EXT_HOOKS = [
     ("frame_prepare", c_int, [c_void, c_void, c_void] + [c_int] * 5 + [c_void, c_void, c_void, c_int, c_int, c_void]),
+    ("frame_compose", c_int, [c_void, c_int, c_int, c_void, c_int, c_void, c_void, c_void] + [c_int] * 5 + [c_void, c_void, c_void] + [c_int] * 3 + [c_void]),
 ]
 EXT_MAGIC = 0x4653455854414231  # FS_EXT_MAGIC
 

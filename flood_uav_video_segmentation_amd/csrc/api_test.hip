@@ -379,6 +379,30 @@ static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_
     if (reinterpret_cast<uintptr_t>(out) % 4 != 0) return fs::fail("fs_frame_prepare: out is not aligned to a float");
     return fs::launch_frame_prepare(frame, u, v, format, matrix, full_range, H, W, mean, std, out, h, w, S(stream));
 }
+static int fs_frame_compose(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u, const uint8_t* v,
+                            int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v, int out_format,
+                            int out_matrix, int out_full_range, fs_stream stream) {
+    if (!mask || !palette || !out) return fs::fail("fs_frame_compose: null pointer");
+    if (format < 0 || format > 2 || out_format < 0 || out_format > 2)
+        return fs::fail("fs_frame_compose: format must be 0 (RGB24), 1 (NV12) or 2 (I420), got %d in, %d out", format, out_format);
+    if ((matrix != 0 && matrix != 1) || (out_matrix != 0 && out_matrix != 1))
+        return fs::fail("fs_frame_compose: matrix must be 0 (BT.601) or 1 (BT.709), got %d in, %d out", matrix, out_matrix);
+    if ((full_range != 0 && full_range != 1) || (out_full_range != 0 && out_full_range != 1))
+        return fs::fail("fs_frame_compose: range must be 0 (limited) or 1 (full), got %d in, %d out", full_range, out_full_range);
+    if (K < 1 || K > 256) return fs::fail("fs_frame_compose: palette must hold 1..256 classes, got %d", K);
+    if (h < 1 || w < 1) return fs::fail("fs_frame_compose: empty frame (%d x %d)", h, w);
+    if ((int64_t)h * w * 3 >= ((int64_t)1 << 31)) return fs::fail("fs_frame_compose: output too large (%d x %d x 3 bytes pass 2^31)", h, w);
+    if (out_format != 0 && (!out_u || (out_format == 2 && !out_v))) return fs::fail("fs_frame_compose: null output chroma pointer for a YUV format");
+    if (!frame) {
+        if (H != 0 || W != 0 || u || v) return fs::fail("fs_frame_compose: background geometry or chroma (%d x %d) without a background frame", H, W);
+    } else {
+        if (H < 1 || W < 1) return fs::fail("fs_frame_compose: a background frame without its geometry (%d x %d)", H, W);
+        if ((int64_t)H * W * 3 >= ((int64_t)1 << 31)) return fs::fail("fs_frame_compose: background too large (%d x %d x 3 bytes pass 2^31)", H, W);
+        if (format != 0 && (!u || (format == 2 && !v))) return fs::fail("fs_frame_compose: null background chroma pointer for a YUV format");
+    }
+    return fs::launch_frame_compose(mask, h, w, palette, K, frame, u, v, format, matrix, full_range, H, W, out, out_u, out_v, out_format, out_matrix,
+                                    out_full_range, S(stream));
+}
 
 FS_API const fs_test_api* fs_test_hooks(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -426,6 +450,7 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         FS_EXT_MAGIC,
         sizeof(fs_ext_api),
         fs_frame_prepare,
+        fs_frame_compose,
     }};
     return &tables.test;
 }

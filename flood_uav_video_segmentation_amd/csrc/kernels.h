@@ -280,6 +280,13 @@ int launch_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int
 // floats each.  Arguments are validated by the caller (api_test.hip).
 int launch_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                          const float* mean, const float* std, float* out, int h, int w, hipStream_t s);
+// Frame egress (egress_ops.hip): mask uint8 [h][w] + palette uint8 [K][4] (R, G, B, A) (+ a decoded background frame, described as
+// launch_frame_prepare's input; frame == nullptr: none) -> one RGB24 / NV12 / I420 frame (out_format 0 / 1 / 2; out = the interleaved
+// frame or the Y plane, out_u = the UV plane or the U plane, out_v = the V plane); out_matrix / out_full_range pick the integer
+// RGB -> YUV conversion of include/floodseg_test.h.  Arguments are validated by the caller (api_test.hip).
+int launch_frame_compose(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u, const uint8_t* v,
+                         int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v, int out_format,
+                         int out_matrix, int out_full_range, hipStream_t s);
 // intersection / union / target histograms (util/util.py:52-63), int64[3][K] accumulated.
 int launch_iou_hist(const uint8_t* pred, const uint8_t* target, int64_t numel, int K, int ignore_index,
                     long long* hist3K, hipStream_t s);

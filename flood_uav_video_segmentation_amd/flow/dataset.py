@@ -117,6 +117,14 @@ class PredictWindows:
             return None
         return self._decoded(f_id)
 
+    def source(self, f_id):
+        """(frame, chroma, fmt, matrix, full_range) of decoded frame `f_id` as ops.prepare_frame and ops.compose_frame take a frame: the
+        very pixels the network's input was made from (an overlay's background); None when the image does not exist.  Goes through
+        the decode cache, so a key frame is still decoded and uploaded once.  With no_warp the frames BETWEEN the key frames are not
+        decoded by the prediction itself: an overlay decodes and uploads every one of them (frame_delta - 1 more per window)."""
+        frame = self.raw_frame(f_id)
+        return None if frame is None else (frame, None, "rgb24", "bt601", False)
+
     def _grid(self, g, name):
         """Grid `g` of grids/ (name "grids") or inv_grids/ as the float32 [1,67,120,2] device tensor of an item."""
         if self.estimator is None:
@@ -275,11 +283,7 @@ class EvalWindows(PredictWindows):
 RAW_PIX_FMTS = ("nv12", "i420", "rgb24")
 
 
-def raw_frame_bytes(height, width, pix_fmt):
-    """Bytes of one frame of a headerless raw video (ffmpeg -f rawvideo): chroma planes of the 4:2:0 formats round up."""
-    if pix_fmt == "rgb24":
-        return height * width * 3
-    return height * width + 2 * ((height + 1) // 2) * ((width + 1) // 2)
+raw_frame_bytes = ops.raw_frame_bytes  # bytes of one frame of a headerless raw video; chroma planes of the 4:2:0 formats round up
 
 
 class RawVideoWindows(PredictWindows):
@@ -335,15 +339,15 @@ class RawVideoWindows(PredictWindows):
 
     def planes(self, f_id):
         """(frame, chroma) of frame f_id as ops.prepare_frame takes them: views of the one uploaded buffer."""
-        buf = self._decoded(f_id)
-        h, w = self.height, self.width
-        if self.pix_fmt == "rgb24":
-            return buf.view(h, w, 3), None
-        ch, cw = (h + 1) // 2, (w + 1) // 2
-        y = buf[:h * w].view(h, w)
-        if self.pix_fmt == "nv12":
-            return y, buf[h * w:].view(ch, cw, 2)
-        return y, (buf[h * w:h * w + ch * cw].view(ch, cw), buf[h * w + ch * cw:].view(ch, cw))
+        return ops.frame_planes(self._decoded(f_id), self.height, self.width, self.pix_fmt)
+
+    def source(self, f_id):
+        """(frame, chroma, fmt, matrix, full_range) of frame f_id for ops.compose_frame's background (see PredictWindows.source: the
+        same cache, the same extra uploads under no_warp); None past either end of the file."""
+        if not self._complete(f_id):
+            return None
+        frame, chroma = self.planes(f_id)
+        return frame, chroma, self.pix_fmt, self.matrix, self.full_range
 
     def raw_frame(self, f_id):
         """What the grid estimator sees: the RGB frame [H,W,3], or the Y plane [H,W] of a YUV stream; None past either end."""
@@ -352,3 +356,124 @@ class RawVideoWindows(PredictWindows):
     def _frame(self, f_id):
         frame, chroma = self.planes(f_id)
         return ops.prepare_frame(frame, self.size, MEAN, STD, fmt=self.pix_fmt, chroma=chroma, matrix=self.matrix, full_range=self.full_range)
+
+
+class RawVideoWriter:
+    """Writes headerless raw video frames (what `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24 -s WxH` reads): the output side of
+    RawVideoWindows.  write(frame_id, buffer) takes one frame of raw_frame_bytes(height, width, pix_fmt) bytes -- a uint8 device
+    tensor (ops.compose_frame's `out` buffer) or a host numpy array / tensor.
+
+    A REGULAR FILE is written by position: frame i goes to byte i * frame_bytes (os.pwrite), in any order, and `frames` pre-sizes the
+    file.  The ranks of a torchrun launch can therefore write their disjoint window blocks into ONE file (give every rank the same
+    `frames`; the file is then not truncated on open, only sized).  Without `frames` the file is truncated on open: one writer.
+    A PIPE, a FIFO, any other file object, or "-" (standard output) takes frames strictly in order 0, 1, 2, ...; anything else raises,
+    and such a target is refused when world > 1.
+
+    Device frames go through two pinned host buffers, a non-blocking copy and an event each: write(i) enqueues frame i's copy, then
+    waits for frame i - 1's and hands it to the file, and returns while copy i is still in flight -- it overlaps the launches of frame
+    i + 1.  close() (or leaving the `with` block) drains both."""
+
+    def __init__(self, path_or_fileobj, height, width, pix_fmt, frames=None, world=1):
+        import stat
+        import sys
+
+        if pix_fmt not in RAW_PIX_FMTS:
+            raise ValueError(f"RawVideoWriter: pix_fmt must be one of {RAW_PIX_FMTS}, got {pix_fmt!r}")
+        if height < 1 or width < 1 or (frames is not None and frames < 0):
+            raise ValueError(f"RawVideoWriter: bad geometry {height} x {width}, frames {frames}")
+        self.height, self.width, self.pix_fmt = int(height), int(width), pix_fmt
+        self.frame_bytes = raw_frame_bytes(self.height, self.width, pix_fmt)
+        self._own_fd = self._fd = self._stream = None
+        self.frames = frames
+        self._next = 0         # sequential targets: the frame id due next
+        self._slots = None     # device frames: [pinned buffer, event, pending frame id or None] x 2
+        self._turn = 0
+        self.written = 0
+        if isinstance(path_or_fileobj, str) and path_or_fileobj == "-":
+            self._stream = sys.stdout.buffer
+        elif isinstance(path_or_fileobj, (str, os.PathLike)):
+            self._own_fd = os.open(path_or_fileobj, os.O_WRONLY | os.O_CREAT | (os.O_TRUNC if frames is None else 0), 0o644)
+            if stat.S_ISREG(os.fstat(self._own_fd).st_mode):
+                self._fd = self._own_fd
+            else:
+                self._stream = os.fdopen(self._own_fd, "wb", closefd=False)
+        else:
+            try:   # io.BytesIO has a fileno() that raises
+                fd = path_or_fileobj.fileno()
+                fd = fd if stat.S_ISREG(os.fstat(fd).st_mode) else None
+            except (AttributeError, OSError, ValueError):
+                fd = None
+            if fd is not None:
+                path_or_fileobj.flush()
+                self._fd = fd
+            else:
+                self._stream = path_or_fileobj
+        if self._stream is not None and world > 1:
+            self.close()
+            raise ValueError("RawVideoWriter: a pipe takes frames strictly in order and cannot be shared by the ranks of a multi-GPU run; "
+                             "write to a regular file (every rank the same `frames`)")
+        if self._fd is not None and frames is not None:
+            os.ftruncate(self._fd, frames * self.frame_bytes)
+
+    def _put(self, frame_id, data):
+        if self._fd is not None:
+            done = 0
+            while done < len(data):
+                done += os.pwrite(self._fd, data[done:], frame_id * self.frame_bytes + done)
+        else:
+            self._stream.write(data)
+        self.written += 1
+
+    def _drain(self, slot):
+        if slot[2] is not None:
+            slot[1].synchronize()
+            self._put(slot[2], memoryview(slot[0].numpy()))
+            slot[2] = None
+
+    def write(self, frame_id, frame):
+        frame_id = int(frame_id)
+        nbytes = frame.numel() * frame.element_size() if isinstance(frame, torch.Tensor) else np.asarray(frame).nbytes
+        dtype_ok = frame.dtype == torch.uint8 if isinstance(frame, torch.Tensor) else np.asarray(frame).dtype == np.uint8
+        if nbytes != self.frame_bytes or not dtype_ok:
+            raise ValueError(f"RawVideoWriter: a {self.height} x {self.width} {self.pix_fmt} frame is {self.frame_bytes} uint8 bytes, got {nbytes} "
+                             f"bytes of {frame.dtype}")
+        if frame_id < 0 or (self.frames is not None and frame_id >= self.frames):
+            raise ValueError(f"RawVideoWriter: frame id {frame_id} outside 0..{'' if self.frames is None else self.frames - 1}")
+        if self._stream is not None:
+            if frame_id != self._next:
+                raise ValueError(f"RawVideoWriter: a pipe takes frames strictly in order: frame {self._next} is due, got {frame_id}")
+            self._next += 1
+        if isinstance(frame, torch.Tensor) and frame.is_cuda:
+            if self._slots is None:
+                self._slots = [[torch.empty(self.frame_bytes, dtype=torch.uint8).pin_memory(), torch.cuda.Event(), None] for _ in range(2)]
+            slot, other = self._slots[self._turn], self._slots[self._turn ^ 1]
+            self._turn ^= 1
+            self._drain(slot)                                     # two writes ago: long finished
+            slot[0].copy_(frame.reshape(-1), non_blocking=True)
+            slot[1].record(torch.cuda.current_stream(frame.device))
+            slot[2] = frame_id
+            self._drain(other)                                    # the previous frame, while this one's copy is in flight
+            return
+        self.flush()                                              # keeps a sequential target in order
+        host = frame.contiguous().numpy() if isinstance(frame, torch.Tensor) else np.ascontiguousarray(frame)
+        self._put(frame_id, memoryview(host.reshape(-1)))
+
+    def flush(self):
+        """Wait for the device frames still in flight and hand them to the file, oldest first."""
+        if self._slots is not None:
+            self._drain(self._slots[self._turn])
+            self._drain(self._slots[self._turn ^ 1])
+        if self._stream is not None:
+            self._stream.flush()
+
+    def close(self):
+        self.flush()
+        if self._own_fd is not None:
+            os.close(self._own_fd)
+            self._own_fd = self._fd = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

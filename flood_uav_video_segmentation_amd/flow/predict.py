@@ -243,3 +243,39 @@ def colorize(masks_u8, palette=PALETTE):
         return out
     check(lib.fs_colorize(ptr(m), ptr(pal), pal.shape[0], ptr(out), m.numel(), stream_ptr()))
     return out
+
+
+def compose_window(masks_u8, item_or_sources=None, palette=PALETTE, alpha=None, out_fmt="nv12", out_matrix="bt709", out_full_range=False,
+                   dataset=None):
+    """The result video frames of one window, composed on the device (ops.compose_frame, one launch per frame): yields, for
+    masks_u8 [n,h,w], n flat uint8 buffers of ops.raw_frame_bytes(h, w, out_fmt) bytes each -- what RawVideoWriter.write takes, and
+    what ops.frame_planes splits into the planes ops.prepare_frame reads.
+    item_or_sources: None -- the class colours alone (the reference's video, flow/base.py:308-312); a sequence of n entries, or a
+    callable p -> entry, each a (frame, chroma, fmt, matrix, full_range) tuple as PredictWindows.source / RawVideoWindows.source
+    return it (None: no overlay for that frame) -- the colours blended over the footage; or a window item together with
+    `dataset=`, which stands for dataset.source(item["frame_id"] + p).  Sources are asked for one frame at a time, so the decoded
+    frames of a window need not be alive together.  palette / alpha: as ops.compose_frame ([K,3] + alpha, or [K,4])."""
+    if isinstance(item_or_sources, dict):
+        if dataset is None:
+            raise RuntimeError("floodseg.compose_window: a window item needs dataset= to find its decoded frames")
+        first = item_or_sources["frame_id"]
+        source = lambda p: dataset.source(first + p)  # noqa: E731
+    elif item_or_sources is None:
+        source = lambda p: None  # noqa: E731
+    elif callable(item_or_sources):
+        source = item_or_sources
+    else:
+        if len(item_or_sources) != masks_u8.shape[0]:
+            raise RuntimeError(f"floodseg.compose_window: {len(item_or_sources)} sources for {masks_u8.shape[0]} masks")
+        source = item_or_sources.__getitem__
+    if masks_u8.dim() != 3:
+        raise RuntimeError(f"floodseg.compose_window: masks must be [n,h,w], got {tuple(masks_u8.shape)}")
+    for p in range(masks_u8.shape[0]):
+        src = source(p)
+        out = torch.empty(ops.raw_frame_bytes(masks_u8.shape[1], masks_u8.shape[2], out_fmt), dtype=torch.uint8, device=masks_u8.device)
+        if src is None:
+            ops.compose_frame(masks_u8[p], palette, out_fmt=out_fmt, out_matrix=out_matrix, out_full_range=out_full_range, out=out)
+        else:
+            frame, chroma, fmt, matrix, full_range = src
+            ops.compose_frame(masks_u8[p], palette, frame, chroma, fmt, matrix, full_range, out_fmt, out_matrix, out_full_range, out=out, alpha=alpha)
+        yield out

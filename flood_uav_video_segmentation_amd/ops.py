@@ -476,6 +476,112 @@ def prepare_frame(frame, size=None, mean=MEAN, std=STD, fmt="rgb24", chroma=None
     return out.view(1, 3, h, w)
 
 
+# ------------------------------------------------------------------------------------------ frame egress
+_palette_cache = {}  # (device, palette bytes, K) -> device tensor [K,4]: one host-to-device copy per device and palette, not one per frame
+
+
+def raw_frame_bytes(height, width, pix_fmt):
+    """Bytes of one frame of a headerless raw video (ffmpeg -f rawvideo): chroma planes of the 4:2:0 formats round up."""
+    if pix_fmt == "rgb24":
+        return height * width * 3
+    return height * width + 2 * ((height + 1) // 2) * ((width + 1) // 2)
+
+
+def frame_planes(buf, height, width, pix_fmt):
+    """(frame, chroma) views of one raw frame's bytes `buf` (uint8 [raw_frame_bytes]) as prepare_frame takes and compose_frame returns
+    them: rgb24 -> ([H,W,3], None); nv12 -> (Y [H,W], UV [ceil(H/2),ceil(W/2),2]); i420 -> (Y, (U, V))."""
+    h, w = height, width
+    if pix_fmt == "rgb24":
+        return buf.view(h, w, 3), None
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    y = buf[:h * w].view(h, w)
+    if pix_fmt == "nv12":
+        return y, buf[h * w:].view(ch, cw, 2)
+    return y, (buf[h * w:h * w + ch * cw].view(ch, cw), buf[h * w + ch * cw:].view(ch, cw))
+
+
+def _palette_rgba(dev, palette, alpha, opaque_default):
+    """uint8 [K,4] (R, G, B, A) on `dev` from a [K,3] or [K,4] palette (numpy array, sequence or tensor), cached per device and contents."""
+    import numpy as np
+
+    pal = palette.detach().cpu().numpy() if isinstance(palette, torch.Tensor) else np.asarray(palette)
+    if pal.dtype != np.uint8 or pal.ndim != 2 or pal.shape[1] not in (3, 4) or not 1 <= pal.shape[0] <= 256:
+        raise RuntimeError(f"floodseg.compose_frame: palette must be uint8 [K,3] or [K,4] with 1 <= K <= 256, got {pal.dtype} {pal.shape}")
+    if pal.shape[1] == 4:
+        if alpha is not None:
+            raise RuntimeError("floodseg.compose_frame: alpha= goes with a [K,3] palette; a [K,4] palette carries its own opacities")
+    else:
+        if alpha is None and not opaque_default:
+            raise RuntimeError("floodseg.compose_frame: a [K,3] palette over a background needs alpha= (0..255)")
+        a = 255 if alpha is None else int(alpha)
+        if not 0 <= a <= 255:
+            raise RuntimeError(f"floodseg.compose_frame: alpha must be 0..255, got {alpha}")
+        pal = np.concatenate([pal, np.full((pal.shape[0], 1), a, dtype=np.uint8)], axis=1)
+    key = (dev, pal.tobytes(), pal.shape[0])
+    t = _palette_cache.get(key)
+    if t is None:
+        t = _palette_cache[key] = torch.from_numpy(np.ascontiguousarray(pal)).to(dev)
+    return t
+
+
+def compose_frame(mask, palette, background=None, chroma=None, fmt="rgb24", matrix="bt601", full_range=False, out_fmt="nv12", out_matrix=None,
+                  out_full_range=None, out=None, alpha=None):
+    """One uint8 mask [h,w] -> one result video frame in one launch (definition: include/floodseg_test.h, frame_compose): the class
+    colours of `palette`, optionally blended over the decoded frame the network saw, as RGB24, NV12 or I420 bytes for a video encoder.
+    palette: uint8 [K,3] or [K,4] (R, G, B, A), numpy or tensor, cached on the device by contents; a [K,3] palette takes `alpha`
+    (0..255) for every class, or is opaque when there is no background.  Mask values >= K are class 0 (colorize's rule).
+    background, chroma, fmt, matrix, full_range: one decoded frame exactly as prepare_frame takes it (any size: it is resized to
+    [h,w] as prepare_frame would, and blended o = (A * colour + (255 - A) * b + 127) // 255); None: the colours alone.
+    out_fmt "rgb24" | "nv12" | "i420"; out_matrix / out_full_range pick the integer RGB -> YUV conversion (default: the input's).
+    Returns rgb [h,w,3], or (y, chroma) in the shapes prepare_frame takes.  out: ONE caller-owned contiguous uint8 buffer of
+    raw_frame_bytes(h, w, out_fmt) bytes that the returned planes are views of (a slice at any byte offset is fine), so that one
+    device-to-host copy moves a frame."""
+    lib = _lib.load()
+    if fmt not in _FORMATS or out_fmt not in _FORMATS:
+        raise RuntimeError(f"floodseg.compose_frame: fmt and out_fmt must be one of {sorted(_FORMATS)}, got {fmt!r} and {out_fmt!r}")
+    out_matrix = matrix if out_matrix is None else out_matrix
+    out_full_range = full_range if out_full_range is None else out_full_range
+    if matrix not in _MATRICES or out_matrix not in _MATRICES:
+        raise RuntimeError(f"floodseg.compose_frame: matrix and out_matrix must be one of {sorted(_MATRICES)}, got {matrix!r} and {out_matrix!r}")
+    planes = [] if chroma is None else list(chroma) if isinstance(chroma, (tuple, list)) else [chroma]
+    dev = one_device(mask, background, out, *planes, what="floodseg.compose_frame")
+    if mask.dtype != torch.uint8 or mask.dim() != 2 or mask.numel() == 0:
+        raise RuntimeError(f"floodseg.compose_frame: mask must be a non-empty uint8 [h,w] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    h, w = int(mask.shape[0]), int(mask.shape[1])
+    H = W = 0
+    if background is None:
+        if planes:
+            raise RuntimeError("floodseg.compose_frame: chroma planes without a background frame")
+    else:
+        if background.dtype != torch.uint8 or any(p.dtype != torch.uint8 for p in planes):
+            raise RuntimeError(f"floodseg.compose_frame: frames must be uint8, got {[str(t.dtype) for t in [background] + planes]}")
+        rgb = fmt == "rgb24"
+        if background.dim() != (3 if rgb else 2) or (rgb and background.shape[2] != 3) or background.numel() == 0:
+            raise RuntimeError(f"floodseg.compose_frame: a {fmt} background must be {'[H,W,3]' if rgb else 'the Y plane [H,W]'}, got {tuple(background.shape)}")
+        H, W = int(background.shape[0]), int(background.shape[1])
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        want = [] if rgb else [(ch, cw, 2)] if fmt == "nv12" else [(ch, cw), (ch, cw)]
+        if [tuple(p.shape) for p in planes] != want:
+            raise RuntimeError(f"floodseg.compose_frame: a {H} x {W} {fmt} background takes chroma {want if want else None}, got {[tuple(p.shape) for p in planes]}")
+    nbytes = raw_frame_bytes(h, w, out_fmt)
+    with torch.cuda.device(dev):
+        pal = _palette_rgba(dev, palette, alpha, background is None)
+        mask = mask.contiguous()
+        planes = [p.contiguous() for p in planes]
+        background = background.contiguous() if background is not None else None
+        if out is None:
+            out = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != nbytes or not out.is_contiguous():
+            raise RuntimeError(f"floodseg.compose_frame: out must be a contiguous uint8 [{nbytes}] buffer (one {h} x {w} {out_fmt} frame), got {out.dtype} {tuple(out.shape)}")
+        frame, ochroma = frame_planes(out, h, w, out_fmt)
+        oplanes = [] if ochroma is None else list(ochroma) if isinstance(ochroma, tuple) else [ochroma]
+        check(lib.fs_frame_compose(ptr(mask), h, w, ptr(pal), pal.shape[0], ptr(background), ptr(planes[0]) if planes else None,
+                                   ptr(planes[1]) if len(planes) > 1 else None, _FORMATS[fmt], _MATRICES[matrix], int(bool(full_range)), H, W,
+                                   ptr(frame), ptr(oplanes[0]) if oplanes else None, ptr(oplanes[1]) if len(oplanes) > 1 else None,
+                                   _FORMATS[out_fmt], _MATRICES[out_matrix], int(bool(out_full_range)), stream_ptr()))
+    return frame if out_fmt == "rgb24" else (frame, ochroma)
+
+
 # ------------------------------------------------------------------------------------------ single-frame multi-scale test
 def ms_prepare(raw, new_hw, padded_hw, mean, std, flip=True):
     """One scale's network input from the raw 0-255 frame [3,H,W] (base/foundation.py:193-200, 267-273, 300-306): resized to

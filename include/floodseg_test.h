@@ -5,7 +5,7 @@
  * (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py, tests/test_gpu_head_ops.py) and the measurement tools (tools/).  The table
  * also carries EXTENSION OPS: product features that have no reference call site (block matching, flow/motion.py) and therefore no
  * place in the capped export list of floodseg.h; the Python package reaches them like any other function.  fs_test_api is frozen at
- * block_match; later extension ops (frame ingest) are members of fs_ext_api, the table right behind it (end of this file).
+ * block_match; later extension ops (frame ingest, frame egress) are members of fs_ext_api, the table right behind it (end of this file).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table was append-only up to block_match and is frozen now; `size` is sizeof(fs_test_api)
@@ -224,6 +224,32 @@ typedef struct fs_ext_api {
      * format, matrix or range are refused before a launch. */
     int (*frame_prepare)(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                          const float* mean, const float* std, float* out, int h, int w, fs_stream stream);
+
+    /* Frame egress (csrc/egress_ops.hip): one mask -> one result video frame, in one launch.  mask = uint8 [h][w]; palette = uint8 [K][4],
+     * (R, G, B, A) per class, 1 <= K <= 256.  Background (optional; frame = NULL, u = v = NULL, H = W = 0: none): one decoded uint8 frame
+     * H x W described exactly as frame_prepare's input (format, u, v, matrix, full_range).  Per output pixel:
+     *   c = mask < K ? mask : 0 (the rule of fs_colorize);  (R, G, B, A) = palette[c];
+     *   b = the uint8 image the network saw: the source pixel through frame_prepare's path, operation for operation, up to but not
+     *       including the normalisation (integer YUV -> RGB, half-pixel bilinear to h x w, round half to even, clamp to 0..255);
+     *   per channel, int32: o = (A * colour + (255 - A) * b + 127) / 255 (integer division); without a background o = colour whatever A.
+     * out_format 0 = RGB24: out = interleaved [h][w][3], out_u = out_v ignored.
+     * out_format 1 = NV12: out = Y [h][w], out_u = interleaved UV plane [ceil(h/2)][ceil(w/2)][2], out_v ignored.
+     * out_format 2 = I420: out = Y [h][w], out_u, out_v = [ceil(h/2)][ceil(w/2)] each.
+     * Y comes from each pixel's own o; a chroma sample from the per-channel mean of its 2 x 2 quad, (sum of four + 2) >> 2, rows and
+     * columns past the frame repeating the last one (odd h and w are allowed).  RGB -> YUV is OUR DEFINITION, in int32 with an arithmetic
+     * shift, each result clipped to [0, 255]; every chroma row sums to 0, so a grey pixel gives U = V = 128 exactly (which is why the
+     * BT.709 limited U row has -86 and not the nearest integer -87).  out_matrix / out_full_range need not equal the input's:
+     *   out_matrix 0 (BT.601), out_full_range 0: Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16; U = ((-38 R - 74 G + 112 B + 128) >> 8) + 128; V = ((112 R - 94 G - 18 B + 128) >> 8) + 128
+     *   out_matrix 0 (BT.601), out_full_range 1: Y = ((77 R + 150 G + 29 B + 128) >> 8) + 0; U = ((-43 R - 85 G + 128 B + 128) >> 8) + 128; V = ((128 R - 107 G - 21 B + 128) >> 8) + 128
+     *   out_matrix 1 (BT.709), out_full_range 0: Y = ((47 R + 157 G + 16 B + 128) >> 8) + 16; U = ((-26 R - 86 G + 112 B + 128) >> 8) + 128; V = ((112 R - 102 G - 10 B + 128) >> 8) + 128
+     *   out_matrix 1 (BT.709), out_full_range 1: Y = ((54 R + 183 G + 19 B + 128) >> 8) + 0; U = ((-29 R - 99 G + 128 B + 128) >> 8) + 128; V = ((128 R - 116 G - 12 B + 128) >> 8) + 128
+     * The output buffers are the caller's, at any byte address (8-byte aligned planes and w % 8 == 0 take the wide stores).  Refused
+     * before a launch: a null mask / palette / out, a null chroma pointer that a format needs (in or out), an unknown format, matrix or
+     * range (in or out; checked with or without a background), K outside 1..256, h or w < 1, h * w * 3 >= 2^31 or H * W * 3 >= 2^31,
+     * H / W / u / v given without a background frame, and a background frame with H or W < 1. */
+    int (*frame_compose)(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u, const uint8_t* v,
+                         int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v, int out_format,
+                         int out_matrix, int out_full_range, fs_stream stream);
 } fs_ext_api;
 
 typedef struct fs_hook_tables {

@@ -8,6 +8,12 @@ frames in between and writes the colourised masks.
 
     python tools/predict_video.py --raw clip.nv12 --raw-size 1080 1920 --pix-fmt nv12 --matrix bt709 --arch pspnet --ckpt ... --out out/clip
 
+    python tools/predict_video.py --raw clip.nv12 --raw-size 1080 1920 --arch pspnet --ckpt ... --raw-out result.nv12 --overlay 128
+
+`--raw-out FILE|-` writes the result VIDEO as raw frames (`--out-pix-fmt nv12|i420|rgb24`), composed on the device in one launch per
+frame (ops.compose_frame) and copied out through pinned buffers; the ffmpeg line that encodes it is printed on stderr.  `--overlay A`
+blends the class colours with opacity A (0..255) over the footage the network saw; omitted = opaque colours, the reference's video.
+Under torchrun every rank writes its own window block into the one file (not into a pipe).
 `--grids estimate` (with `--search`, `--penalty`) takes the grids from block matching of the decoded frames instead of the grids/
 folders; a raw video file (`--raw`, as `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24` writes it) always does.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
@@ -27,9 +33,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -77,7 +83,34 @@ def parse_args(argv=None):
     ap.add_argument("--pix-fmt", choices=("nv12", "i420", "rgb24"), default="nv12", help="--raw: pixel format (i420 = ffmpeg's yuv420p)")
     ap.add_argument("--matrix", choices=("bt601", "bt709"), default="bt709", help="--raw, YUV formats: conversion matrix")
     ap.add_argument("--full-range", action="store_true", help="--raw, YUV formats: full-range (JPEG) levels instead of limited")
+    ap.add_argument("--raw-out", metavar="FILE", help="write the result video as raw frames to FILE ('-' = standard output)")
+    ap.add_argument("--out-pix-fmt", choices=("nv12", "i420", "rgb24"), default="nv12", help="--raw-out: pixel format (i420 = ffmpeg's yuv420p)")
+    ap.add_argument("--overlay", type=int, metavar="A", help="--raw-out: blend the colours with opacity A (0..255) over the footage; "
+                    "omitted = opaque colours (the reference's video)")
+    ap.add_argument("--overlay-keep-class0", action="store_true", help="--overlay: class 0 gets opacity 0 (background stays plain footage)")
+    ap.add_argument("--out-matrix", choices=("bt601", "bt709"), help="--raw-out, YUV formats: conversion matrix (default: the input's for "
+                    "--raw, bt709 for a frame folder)")
+    ap.add_argument("--out-full-range", action="store_true", default=None, help="--raw-out, YUV formats: full-range levels (default: the "
+                    "input's for --raw, limited for a frame folder)")
     args = ap.parse_args(argv)
+    if not args.raw_out:
+        for given, name in ((args.overlay is not None, "--overlay"), (args.overlay_keep_class0, "--overlay-keep-class0"),
+                            (args.out_matrix is not None, "--out-matrix"), (args.out_full_range is not None, "--out-full-range"),
+                            (args.out_pix_fmt != "nv12", "--out-pix-fmt")):
+            if given:
+                ap.error(f"{name} needs --raw-out")
+    if args.overlay is not None and not 0 <= args.overlay <= 255:
+        ap.error("--overlay takes an opacity 0..255")
+    if args.overlay_keep_class0 and args.overlay is None:
+        ap.error("--overlay-keep-class0 needs --overlay")
+    if args.raw_out and args.out_pix_fmt == "rgb24" and (args.out_matrix is not None or args.out_full_range is not None):
+        ap.error("--out-matrix / --out-full-range apply to the YUV output formats")
+    if args.raw_out and args.raw and args.raw_out != "-" and os.path.abspath(args.raw_out) == os.path.abspath(args.raw):
+        ap.error("--raw-out would overwrite the --raw input")
+    if args.out_matrix is None:
+        args.out_matrix = args.matrix if args.raw else "bt709"
+    if args.out_full_range is None:
+        args.out_full_range = bool(args.full_range) if args.raw else False
     if not args.synthetic_weights and not args.ckpt:
         ap.error("give --ckpt or --synthetic-weights")
     if args.raw:
@@ -120,6 +153,21 @@ def main():
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
+    writer = None
+    if args.raw_out:
+        h, w = args.size
+        pal = np.asarray(palette, dtype=np.uint8)
+        if args.overlay is not None:   # per-class opacity: [K,4]
+            pal = np.concatenate([pal[:, :3], np.full((pal.shape[0], 1), args.overlay, dtype=np.uint8)], axis=1)
+            if args.overlay_keep_class0:
+                pal[0, 3] = 0
+        # every rank sizes the one file for all frames and writes its own window block into it
+        writer = RawVideoWriter(args.raw_out, h, w, args.out_pix_fmt, frames=None if args.raw_out == "-" else len(ds) * args.frame_delta,
+                                world=world)
+        if rank == 0:
+            ff = {"nv12": "nv12", "i420": "yuv420p", "rgb24": "rgb24"}[args.out_pix_fmt]
+            print(f"encode with: ffmpeg -f rawvideo -pix_fmt {ff} -s {w}x{h} -r 25 -i {args.raw_out} result.mp4"
+                  + ("" if args.out_pix_fmt == "rgb24" else f"   ({args.out_matrix}, {'full' if args.out_full_range else 'limited'} range)"), file=sys.stderr)
     shard.barrier()
 
     # windows are independent units given their two key frames: each rank takes a contiguous block (SURVEY 8e "frame-window
@@ -138,12 +186,19 @@ def main():
             first_mask = masks[0].clone()
         last_mask = masks[-1]
         frames += masks.shape[0]
+        if writer is not None:
+            frames_of = (lambda p: ds.source(item["frame_id"] + p)) if args.overlay is not None else None
+            for p, buf in enumerate(compose_window(masks, frames_of, pal, out_fmt=args.out_pix_fmt, out_matrix=args.out_matrix,
+                                                   out_full_range=args.out_full_range)):
+                writer.write(item["frame_id"] + p, buf)
         if args.out:
             from PIL import Image
 
             rgb = colorize(masks, palette).cpu().numpy()
             for p in range(rgb.shape[0]):
                 Image.fromarray(rgb[p]).save(os.path.join(args.out, f"{item['frame_id'] + p}.png"))
+    if writer is not None:
+        writer.close()   # the last two frames' copies and writes belong to the timed work
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0  # this rank's own work: the end-of-run exchange below waits for the slowest rank and is not part of it
     if world > 1 and not args.no_metrics:
@@ -162,7 +217,7 @@ def main():
             inter, union, target = h[0], h[1] + h[2] - h[0], h[2]
             line += (f"; temporal consistency mIoU {float((inter / (union + 1e-10)).mean()):.4f}"
                      f" mAcc {float((inter / (target + 1e-10)).mean()):.4f} acc {float(inter.sum() / (target.sum() + 1e-10)):.4f}")
-        print(line)
+        print(line, file=sys.stderr if args.raw_out == "-" else sys.stdout)   # standard output may be the video
     if world > 1:
         torch.distributed.destroy_process_group()
 
