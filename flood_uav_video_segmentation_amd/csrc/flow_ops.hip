@@ -9,12 +9,17 @@
 
 namespace fs {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 // The flat element index of these kernels is decomposed with divisions by run-time sizes: as a 64-bit value that is ~100 instructions
 // per division, several times the interpolation itself.  Every kernel is a template on the index type and runs on unsigned 32-bit
 // indices whenever the element count fits (always, for the frame sizes of this path); int64_t remains for anything larger.
+// FS_LAUNCH_INDEXED picks the instantiation: min(ceil(total / 256), cap) blocks of 256 threads.
+#define FS_LAUNCH_INDEXED(kernel_, total_, cap_, s_, ...)                                                                  \
+    do {                                                                                                                   \
+        const dim3 grid_((unsigned)std::min<int64_t>(cdiv64((total_), 256), (cap_)));                                      \
+        if ((total_) < ((int64_t)1 << 31)) hipLaunchKernelGGL((kernel_<unsigned>), grid_, dim3(256), 0, (s_), __VA_ARGS__); \
+        else hipLaunchKernelGGL((kernel_<int64_t>), grid_, dim3(256), 0, (s_), __VA_ARGS__);                               \
+    } while (0)
+
 // ------------------------------------------------------------------ grid_sample, NCHW
 template <typename I>
 __global__ __launch_bounds__(256) void grid_sample_nchw_kernel(const float* __restrict__ in, int B, int C, int Hi, int Wi,
@@ -26,14 +31,9 @@ __global__ __launch_bounds__(256) void grid_sample_nchw_kernel(const float* __re
         const I g = i - (I)b * Hg * Wg;
         const float gx = grid[i * 2 + 0], gy = grid[i * 2 + 1];
         const GsTaps t = gs_taps(gx, gy, Wi, Hi, ac);
-        const int x1 = t.x1ok ? t.x0 + 1 : t.x0, y1 = t.y1ok ? t.y0 + 1 : t.y0;
         for (int c = 0; c < C; ++c) {
             const float* pl = in + ((size_t)b * C + c) * Hi * Wi;
-            const float vnw = pl[(size_t)t.y0 * Wi + t.x0];
-            const float vne = t.x1ok ? pl[(size_t)t.y0 * Wi + x1] : 0.f;
-            const float vsw = t.y1ok ? pl[(size_t)y1 * Wi + t.x0] : 0.f;
-            const float vse = (t.x1ok && t.y1ok) ? pl[(size_t)y1 * Wi + x1] : 0.f;
-            out[((size_t)b * C + c) * Hg * Wg + g] = gs_combine(vnw, vne, vsw, vse, t);
+            out[((size_t)b * C + c) * Hg * Wg + g] = gs_sample(t, [&](int y, int x) { return pl[(size_t)y * Wi + x]; });
         }
     }
 }
@@ -41,31 +41,9 @@ __global__ __launch_bounds__(256) void grid_sample_nchw_kernel(const float* __re
 int launch_grid_sample_nchw(const float* in, int B, int C, int Hi, int Wi, const float* grid, int Hg, int Wg, float* out,
                             int align_corners, hipStream_t s) {
     const int64_t total = (int64_t)B * Hg * Wg;
-    if (total < ((int64_t)1 << 31)) hipLaunchKernelGGL((grid_sample_nchw_kernel<unsigned>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 8192)), dim3(256), 0, s, in,
-                       B, C, Hi, Wi, grid, Hg, Wg, out, align_corners);
-    else hipLaunchKernelGGL((grid_sample_nchw_kernel<int64_t>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 8192)), dim3(256), 0, s, in,
-                       B, C, Hi, Wi, grid, Hg, Wg, out, align_corners);
+    FS_LAUNCH_INDEXED(grid_sample_nchw_kernel, total, 8192, s, in, B, C, Hi, Wi, grid, Hg, Wg, out, align_corners);
     FS_HIP(hipGetLastError());
     return 0;
-}
-
-// The four taps of one grid_sample output for four channels of an NHWC map (`base` = the map + the channel offset).  All four loads are
-// issued unconditionally from clamped, always valid addresses and the out-of-image taps are zeroed afterwards: written as
-// `ok ? load : 0` the compiler has to branch around each load and waits for one before it issues the next (four serial round trips).
-__device__ __forceinline__ f32x4 gs_gather_nhwc(const float* __restrict__ base, int Wi, int ld, const GsTaps& t) {
-    const int x1 = t.x1ok ? t.x0 + 1 : t.x0, y1 = t.y1ok ? t.y0 + 1 : t.y0;
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 vnw = *reinterpret_cast<const f32x4*>(base + ((size_t)t.y0 * Wi + t.x0) * ld);
-    f32x4 vne = *reinterpret_cast<const f32x4*>(base + ((size_t)t.y0 * Wi + x1) * ld);
-    f32x4 vsw = *reinterpret_cast<const f32x4*>(base + ((size_t)y1 * Wi + t.x0) * ld);
-    f32x4 vse = *reinterpret_cast<const f32x4*>(base + ((size_t)y1 * Wi + x1) * ld);
-    vne = t.x1ok ? vne : z;
-    vsw = t.y1ok ? vsw : z;
-    vse = (t.x1ok && t.y1ok) ? vse : z;
-    f32x4 r;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) r[q] = gs_combine(vnw[q], vne[q], vsw[q], vse[q], t);
-    return r;
 }
 
 // ------------------------------------------------------------------ grid_sample, NHWC (C % 4 == 0)
@@ -91,10 +69,7 @@ int launch_grid_sample_nhwc(const float* in, int ld_in, int B, int C, int Hi, in
                             float* out, int ld_out, int align_corners, hipStream_t s) {
     FS_REQUIRE(C % 4 == 0 && ld_in % 4 == 0 && ld_out % 4 == 0, "grid_sample_nhwc: C/ld must be multiples of 4");
     const int64_t total = (int64_t)B * Hg * Wg * (C / 4);
-    if (total < ((int64_t)1 << 31)) hipLaunchKernelGGL((grid_sample_nhwc_kernel<unsigned>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 8192)), dim3(256), 0, s, in,
-                       ld_in, B, C / 4, Hi, Wi, grid, Hg, Wg, out, ld_out, align_corners);
-    else hipLaunchKernelGGL((grid_sample_nhwc_kernel<int64_t>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 8192)), dim3(256), 0, s, in,
-                       ld_in, B, C / 4, Hi, Wi, grid, Hg, Wg, out, ld_out, align_corners);
+    FS_LAUNCH_INDEXED(grid_sample_nhwc_kernel, total, 8192, s, in, ld_in, B, C / 4, Hi, Wi, grid, Hg, Wg, out, ld_out, align_corners);
     FS_HIP(hipGetLastError());
     return 0;
 }
@@ -110,20 +85,15 @@ __global__ __launch_bounds__(256) void resize_bilinear_nchw_kernel(const float* 
         const int oy = (int)((i / Wo) % Ho);
         const I pc = i / ((I)Wo * Ho);
         const LinCoord cy = lin_coord(oy, Hi, sy, ac), cx = lin_coord(ox, Wi, sx, ac);
-        const float* pl = in + (size_t)pc * Hi * Wi;
-        out[i] = bilerp(pl[cy.i0 * Wi + cx.i0], pl[cy.i0 * Wi + cx.i1], pl[cy.i1 * Wi + cx.i0], pl[cy.i1 * Wi + cx.i1], cy, cx);
+        out[i] = bilerp_at(in + (size_t)pc * Hi * Wi, Wi, cy, cx);
     }
 }
 
 int launch_resize_bilinear_nchw(const float* in, int BC, int Hi, int Wi, float* out, int Ho, int Wo, int align_corners,
                                 hipStream_t s) {
     const int64_t total = (int64_t)BC * Ho * Wo;
-    if (total < ((int64_t)1 << 31)) hipLaunchKernelGGL((resize_bilinear_nchw_kernel<unsigned>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 16384)), dim3(256), 0, s,
-                       in, BC, Hi, Wi, out, Ho, Wo, align_corners, resize_scale(Hi, Ho, align_corners),
-                       resize_scale(Wi, Wo, align_corners));
-    else hipLaunchKernelGGL((resize_bilinear_nchw_kernel<int64_t>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 16384)), dim3(256), 0, s,
-                       in, BC, Hi, Wi, out, Ho, Wo, align_corners, resize_scale(Hi, Ho, align_corners),
-                       resize_scale(Wi, Wo, align_corners));
+    FS_LAUNCH_INDEXED(resize_bilinear_nchw_kernel, total, 16384, s, in, BC, Hi, Wi, out, Ho, Wo, align_corners,
+                      resize_scale(Hi, Ho, align_corners), resize_scale(Wi, Wo, align_corners));
     FS_HIP(hipGetLastError());
     return 0;
 }
@@ -141,27 +111,16 @@ __global__ __launch_bounds__(256) void resize_bilinear_nhwc_kernel(const float* 
         const int b = (int)(m / ((I)Wo * Ho));
         const LinCoord cy = lin_coord(oy, Hi, sy, ac), cx = lin_coord(ox, Wi, sx, ac);
         const float* base = in + (size_t)b * Hi * Wi * ld_in + c4 * 4;
-        const f32x4 v00 = *reinterpret_cast<const f32x4*>(base + ((size_t)cy.i0 * Wi + cx.i0) * ld_in);
-        const f32x4 v01 = *reinterpret_cast<const f32x4*>(base + ((size_t)cy.i0 * Wi + cx.i1) * ld_in);
-        const f32x4 v10 = *reinterpret_cast<const f32x4*>(base + ((size_t)cy.i1 * Wi + cx.i0) * ld_in);
-        const f32x4 v11 = *reinterpret_cast<const f32x4*>(base + ((size_t)cy.i1 * Wi + cx.i1) * ld_in);
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = bilerp(v00[e], v01[e], v10[e], v11[e], cy, cx);
-        *reinterpret_cast<f32x4*>(out + (size_t)m * ld_out + c4 * 4) = r;
+        *reinterpret_cast<f32x4*>(out + (size_t)m * ld_out + c4 * 4) = bilerp4_nhwc(base, Wi, ld_in, cy, cx);
     }
 }
 
 int launch_resize_bilinear_nhwc(const float* in, int ld_in, int B, int C, int Hi, int Wi, float* out, int ld_out, int Ho, int Wo,
-                                int align_corners, hipStream_t s) {
+                                int align_corners, hipStream_t s, int max_blocks) {
     FS_REQUIRE(C % 4 == 0 && ld_in % 4 == 0 && ld_out % 4 == 0, "resize_nhwc: C/ld must be multiples of 4");
     const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
-    if (total < ((int64_t)1 << 31)) hipLaunchKernelGGL((resize_bilinear_nhwc_kernel<unsigned>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 16384)), dim3(256), 0, s,
-                       in, ld_in, B, C / 4, Hi, Wi, out, ld_out, Ho, Wo, align_corners, resize_scale(Hi, Ho, align_corners),
-                       resize_scale(Wi, Wo, align_corners));
-    else hipLaunchKernelGGL((resize_bilinear_nhwc_kernel<int64_t>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 16384)), dim3(256), 0, s,
-                       in, ld_in, B, C / 4, Hi, Wi, out, ld_out, Ho, Wo, align_corners, resize_scale(Hi, Ho, align_corners),
-                       resize_scale(Wi, Wo, align_corners));
+    FS_LAUNCH_INDEXED(resize_bilinear_nhwc_kernel, total, max_blocks, s, in, ld_in, B, C / 4, Hi, Wi, out, ld_out, Ho, Wo, align_corners,
+                      resize_scale(Hi, Ho, align_corners), resize_scale(Wi, Wo, align_corners));
     FS_HIP(hipGetLastError());
     return 0;
 }
@@ -213,53 +172,45 @@ int launch_blend(const float* a, float wa, const float* b, float wb, float* out,
 // ------------------------------------------------------------------ fused predict_segmentation tail
 // Virtual key-frame map: value of up_ac(lo)[k] at integer pixel (y, x) of the H x W frame.
 __device__ __forceinline__ float up_at(const float* __restrict__ pl, int h, int w, int y, int x, float sy, float sx) {
-    const LinCoord cy = lin_coord(y, h, sy, 1), cx = lin_coord(x, w, sx, 1);
-    return bilerp(pl[cy.i0 * w + cx.i0], pl[cy.i0 * w + cx.i1], pl[cy.i1 * w + cx.i0], pl[cy.i1 * w + cx.i1], cy, cx);
+    return bilerp_at(pl, w, lin_coord(y, h, sy, 1), lin_coord(x, w, sx, 1));
 }
 
-// One warp step for both directions (blockIdx.y = direction).  Step 0 samples the virtual
-// H x W map up_ac(lo) (flow/model.py:193 replaces o by its upsampled version before warping);
-// later steps sample the previous Hg x Wg result (the chain stays at grid resolution).
+// One warp step of one chain.  Step 0 (`first`) samples the virtual H x W map up_ac(lo) (flow/model.py:193 replaces o by its
+// upsampled version before warping); later steps sample the previous Hg x Wg result `src` (the chain stays at grid resolution).
+__device__ __forceinline__ void seg_warp_step(const float* lo, const float* src, const float* grid, float* dst, int K, int h, int w, int H,
+                                              int W, int Hg, int Wg, int first, float sy, float sx) {
+    const int G = Hg * Wg;
+    for (int g = blockIdx.x * 256 + threadIdx.x; g < G; g += gridDim.x * 256) {
+        const float gx = grid[g * 2 + 0], gy = grid[g * 2 + 1];
+        const int Hs = first ? H : Hg, Ws = first ? W : Wg;
+        const GsTaps t = gs_taps(gx, gy, Ws, Hs, 0);
+        for (int k = 0; k < K; ++k) {
+            float v;
+            if (first) {
+                const float* pl = lo + (size_t)k * h * w;
+                v = gs_sample(t, [&](int y, int x) { return up_at(pl, h, w, y, x, sy, sx); });
+            } else {
+                const float* pl = src + (size_t)k * G;
+                v = gs_sample(t, [&](int y, int x) { return pl[y * Ws + x]; });
+            }
+            dst[(size_t)k * G + g] = v;
+        }
+    }
+}
+
+// Both directions of one window (blockIdx.y = direction).
 __global__ __launch_bounds__(256) void seg_warp_step_kernel(const float* __restrict__ lo_prev, const float* __restrict__ lo_next,
                                                             const float* __restrict__ src_f, const float* __restrict__ src_b,
                                                             const float* __restrict__ grid_f, const float* __restrict__ grid_b,
                                                             float* __restrict__ dst_f, float* __restrict__ dst_b, int K, int h,
                                                             int w, int H, int W, int Hg, int Wg, int first, float sy, float sx) {
     const int dir = blockIdx.y;
-    const float* lo = dir ? lo_next : lo_prev;
-    const float* src = dir ? src_b : src_f;
-    const float* grid = dir ? grid_b : grid_f;
-    float* dst = dir ? dst_b : dst_f;
-    const int G = Hg * Wg;
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < G; g += gridDim.x * 256) {
-        const float gx = grid[g * 2 + 0], gy = grid[g * 2 + 1];
-        const int Hs = first ? H : Hg, Ws = first ? W : Wg;
-        const GsTaps t = gs_taps(gx, gy, Ws, Hs, 0);
-        const int x1 = t.x1ok ? t.x0 + 1 : t.x0, y1 = t.y1ok ? t.y0 + 1 : t.y0;
-        for (int k = 0; k < K; ++k) {
-            float vnw, vne, vsw, vse;
-            if (first) {
-                const float* pl = lo + (size_t)k * h * w;
-                vnw = up_at(pl, h, w, t.y0, t.x0, sy, sx);
-                vne = t.x1ok ? up_at(pl, h, w, t.y0, x1, sy, sx) : 0.f;
-                vsw = t.y1ok ? up_at(pl, h, w, y1, t.x0, sy, sx) : 0.f;
-                vse = (t.x1ok && t.y1ok) ? up_at(pl, h, w, y1, x1, sy, sx) : 0.f;
-            } else {
-                const float* pl = src + (size_t)k * G;
-                vnw = pl[t.y0 * Ws + t.x0];
-                vne = t.x1ok ? pl[t.y0 * Ws + x1] : 0.f;
-                vsw = t.y1ok ? pl[y1 * Ws + t.x0] : 0.f;
-                vse = (t.x1ok && t.y1ok) ? pl[y1 * Ws + x1] : 0.f;
-            }
-            dst[(size_t)k * G + g] = gs_combine(vnw, vne, vsw, vse, t);
-        }
-    }
+    seg_warp_step(dir ? lo_next : lo_prev, dir ? src_b : src_f, dir ? grid_b : grid_f, dir ? dst_b : dst_f, K, h, w, H, W, Hg, Wg, first, sy, sx);
 }
 
 // Fusion + upsample (+ argmax | + softmax accumulated into the sliding-crop canvas).  One thread per output pixel; KMAX
 // classes kept in registers.  Canvas mode (p.canvas != nullptr) is compute_predict_crop + the accumulation of compute_output
-// (flow/base.py:204-205, 226-234) without the [n,K,h,w] logits ever reaching HBM: softmax over K in fp32 exactly as
-// softmax_accumulate_kernel does it on materialised logits (max, exp(x - max), sum, divide), added to the float64 canvas at
+// (flow/base.py:204-205, 226-234) without the [n,K,h,w] logits ever reaching HBM: softmax over K in fp32 (softmax_k), added to the float64 canvas at
 // the crop's offset; successive crops are successive launches on one stream, so overlapping pixels never race.
 // WARP / CANVAS are compile-time: the headline route (linear interpolation, logits + masks) carries neither the warp path's eight
 // gathers per class and frame nor the softmax / float64 canvas code (one run-time kernel for all modes needed 167 registers: three
@@ -294,17 +245,7 @@ __global__ __launch_bounds__(256) void seg_fuse_kernel(SegTailParams p, float sy
                 p.out_mask[(size_t)f * HW + i] = (uint8_t)arg;
             }
             if (CANVAS) {
-                float mx = v[0];
-#pragma unroll
-                for (int k = 1; k < KMAX; ++k)
-                    if (k < K) mx = fmaxf(mx, v[k]);
-                float sum = 0.f;
-#pragma unroll
-                for (int k = 0; k < KMAX; ++k)
-                    if (k < K) sum += expf(v[k] - mx);
-#pragma unroll
-                for (int k = 0; k < KMAX; ++k)
-                    if (k < K) p.canvas[((size_t)f * K + k) * cHW + cpix] += (double)(expf(v[k] - mx) / sum);
+                softmax_k<KMAX>(v, K, [&](int k, float q) { p.canvas[((size_t)f * K + k) * cHW + cpix] += (double)q; });
                 if (f == 0) p.count[cpix] += 1.0;
             }
         };
@@ -315,12 +256,10 @@ __global__ __launch_bounds__(256) void seg_fuse_kernel(SegTailParams p, float sy
             for (int k = 0; k < KMAX; ++k) {
                 if (k < K) {
                     const float* pl = p.lo_prev + (size_t)k * p.h * p.w;
-                    a[k] = bilerp(pl[cy.i0 * p.w + cx.i0], pl[cy.i0 * p.w + cx.i1], pl[cy.i1 * p.w + cx.i0],
-                                  pl[cy.i1 * p.w + cx.i1], cy, cx);
+                    a[k] = bilerp_at(pl, p.w, cy, cx);
                     if (p.lo_next && !WARP) {
                         const float* pn = p.lo_next + (size_t)k * p.h * p.w;
-                        b[k] = bilerp(pn[cy.i0 * p.w + cx.i0], pn[cy.i0 * p.w + cx.i1], pn[cy.i1 * p.w + cx.i0],
-                                      pn[cy.i1 * p.w + cx.i1], cy, cx);
+                        b[k] = bilerp_at(pn, p.w, cy, cx);
                     }
                     v[k] = a[k];
                 }
@@ -348,10 +287,8 @@ __global__ __launch_bounds__(256) void seg_fuse_kernel(SegTailParams p, float sy
                         // scratch layout: [dir][step][K][Hg][Wg]; forward map f-1, backward map n-f-1
                         const float* pf = p.scratch + ((size_t)(f - 1) * K + k) * G;
                         const float* pb = p.scratch + ((size_t)(n - 1) * K + (size_t)(n - f - 1) * K + k) * G;
-                        va = bilerp(pf[gy_c.i0 * p.Wg + gx_c.i0], pf[gy_c.i0 * p.Wg + gx_c.i1], pf[gy_c.i1 * p.Wg + gx_c.i0],
-                                    pf[gy_c.i1 * p.Wg + gx_c.i1], gy_c, gx_c);
-                        vb = bilerp(pb[gy_c.i0 * p.Wg + gx_c.i0], pb[gy_c.i0 * p.Wg + gx_c.i1], pb[gy_c.i1 * p.Wg + gx_c.i0],
-                                    pb[gy_c.i1 * p.Wg + gx_c.i1], gy_c, gx_c);
+                        va = bilerp_at(pf, p.Wg, gy_c, gx_c);
+                        vb = bilerp_at(pb, p.Wg, gy_c, gx_c);
                     }
                     v[k] = __fadd_rn(__fmul_rn(wa, va), __fmul_rn(wb, vb));
                 }
@@ -466,13 +403,13 @@ __device__ __forceinline__ GsCell feat_cell(const FeatFuseArgs& a, int gy, int g
     const size_t m = (size_t)gy * a.W0 + gx;
     const float2 g = *reinterpret_cast<const float2*>(a.grid0 + m * 2);
     const GsTaps t = gs_taps(g.x, g.y, a.fw, a.fh, 1);
-    const int x1 = t.x1ok ? t.x0 + 1 : t.x0, y1 = t.y1ok ? t.y0 + 1 : t.y0;  // clamped: every address is valid, outside taps are zeroed
     const unsigned ld = (unsigned)a.C4 * 4u;
     GsCell c;
+    // t.x1 / t.y1 are clamped: every address is valid, outside taps are zeroed
     c.nw = (unsigned)(t.y0 * a.fw + t.x0) * ld;
-    c.ne = (unsigned)(t.y0 * a.fw + x1) * ld;
-    c.sw = (unsigned)(y1 * a.fw + t.x0) * ld;
-    c.se = (unsigned)(y1 * a.fw + x1) * ld;
+    c.ne = (unsigned)(t.y0 * a.fw + t.x1) * ld;
+    c.sw = (unsigned)(t.y1 * a.fw + t.x0) * ld;
+    c.se = (unsigned)(t.y1 * a.fw + t.x1) * ld;
     c.wnw = t.nw; c.wne = t.ne; c.wsw = t.sw; c.wse = t.se;
     c.x1ok = t.x1ok; c.y1ok = t.y1ok;
     c.all_in = t.x1ok && t.y1ok;
@@ -735,30 +672,7 @@ __global__ __launch_bounds__(256) void seg_warp_step_crops_kernel(const float* _
     const float* src = step ? base + (size_t)(step - 1) * map : nullptr;
     float* dst = base + (size_t)step * map;
     const float* grid = grids + ((size_t)c * 2 * (n - 1) + (size_t)dir * (n - 1) + step) * G * 2;
-    const int first = step == 0;
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < G; g += gridDim.x * 256) {
-        const float gx = grid[g * 2 + 0], gy = grid[g * 2 + 1];
-        const int Hs = first ? H : Hg, Ws = first ? W : Wg;
-        const GsTaps t = gs_taps(gx, gy, Ws, Hs, 0);
-        const int x1 = t.x1ok ? t.x0 + 1 : t.x0, y1 = t.y1ok ? t.y0 + 1 : t.y0;
-        for (int k = 0; k < K; ++k) {
-            float vnw, vne, vsw, vse;
-            if (first) {
-                const float* pl = lo + (size_t)k * h * w;
-                vnw = up_at(pl, h, w, t.y0, t.x0, sy, sx);
-                vne = t.x1ok ? up_at(pl, h, w, t.y0, x1, sy, sx) : 0.f;
-                vsw = t.y1ok ? up_at(pl, h, w, y1, t.x0, sy, sx) : 0.f;
-                vse = (t.x1ok && t.y1ok) ? up_at(pl, h, w, y1, x1, sy, sx) : 0.f;
-            } else {
-                const float* pl = src + (size_t)k * G;
-                vnw = pl[t.y0 * Ws + t.x0];
-                vne = t.x1ok ? pl[t.y0 * Ws + x1] : 0.f;
-                vsw = t.y1ok ? pl[y1 * Ws + t.x0] : 0.f;
-                vse = (t.x1ok && t.y1ok) ? pl[y1 * Ws + x1] : 0.f;
-            }
-            dst[(size_t)k * G + g] = gs_combine(vnw, vne, vsw, vse, t);
-        }
-    }
+    seg_warp_step(lo, src, grid, dst, K, h, w, H, W, Hg, Wg, step == 0, sy, sx);
 }
 
 template <int KMAX, int FN>
@@ -790,10 +704,10 @@ __global__ __launch_bounds__(256) void crops_fuse_kernel(CropsFuseParams p) {
                 for (int k = 0; k < KMAX; ++k) {
                     if (k < K) {
                         const float* pl = lp + (size_t)k * p.h * p.w;
-                        a[k] = bilerp(pl[cy.i0 * p.w + cx.i0], pl[cy.i0 * p.w + cx.i1], pl[cy.i1 * p.w + cx.i0], pl[cy.i1 * p.w + cx.i1], cy, cx);
+                        a[k] = bilerp_at(pl, p.w, cy, cx);
                         if (ln && p.no_warp) {
                             const float* pn = ln + (size_t)k * p.h * p.w;
-                            b[k] = bilerp(pn[cy.i0 * p.w + cx.i0], pn[cy.i0 * p.w + cx.i1], pn[cy.i1 * p.w + cx.i0], pn[cy.i1 * p.w + cx.i1], cy, cx);
+                            b[k] = bilerp_at(pn, p.w, cy, cx);
                         }
                     }
                 }
@@ -822,26 +736,14 @@ __global__ __launch_bounds__(256) void crops_fuse_kernel(CropsFuseParams p) {
                                 } else {
                                     const float* pf = sc + ((size_t)(f - 1) * K + k) * G;
                                     const float* pb = sc + ((size_t)(n - 1) * K + (size_t)(n - f - 1) * K + k) * G;
-                                    va = bilerp(pf[gy_c.i0 * p.Wg + gx_c.i0], pf[gy_c.i0 * p.Wg + gx_c.i1], pf[gy_c.i1 * p.Wg + gx_c.i0],
-                                                pf[gy_c.i1 * p.Wg + gx_c.i1], gy_c, gx_c);
-                                    vb = bilerp(pb[gy_c.i0 * p.Wg + gx_c.i0], pb[gy_c.i0 * p.Wg + gx_c.i1], pb[gy_c.i1 * p.Wg + gx_c.i0],
-                                                pb[gy_c.i1 * p.Wg + gx_c.i1], gy_c, gx_c);
+                                    va = bilerp_at(pf, p.Wg, gy_c, gx_c);
+                                    vb = bilerp_at(pb, p.Wg, gy_c, gx_c);
                                 }
                                 v[k] = __fadd_rn(__fmul_rn(wa, va), __fmul_rn(wb, vb));
                             }
                         }
                     }
-                    float mx = v[0];
-#pragma unroll
-                    for (int k = 1; k < KMAX; ++k)
-                        if (k < K) mx = fmaxf(mx, v[k]);
-                    float sum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < KMAX; ++k)
-                        if (k < K) sum += expf(v[k] - mx);
-#pragma unroll
-                    for (int k = 0; k < KMAX; ++k)
-                        if (k < K) acc[ff][k] += (double)(expf(v[k] - mx) / sum);
+                    softmax_k<KMAX>(v, K, [&](int k, float q) { acc[ff][k] += (double)q; });
                 }
             }
             const double count = (double)cnt;
@@ -931,9 +833,7 @@ __global__ __launch_bounds__(256) void resize_argmax_u8_kernel(const float* __re
         float best = -INFINITY;
         int arg = 0;
         for (int k = 0; k < K; ++k) {
-            const float* pl = in + ((size_t)b * K + k) * Hi * Wi;
-            const float v = bilerp(pl[(size_t)cy.i0 * Wi + cx.i0], pl[(size_t)cy.i0 * Wi + cx.i1], pl[(size_t)cy.i1 * Wi + cx.i0],
-                                   pl[(size_t)cy.i1 * Wi + cx.i1], cy, cx);
+            const float v = bilerp_at(in + ((size_t)b * K + k) * Hi * Wi, (size_t)Wi, cy, cx);  // 64-bit offsets: a plane may pass 2^31
             if (v > best) { best = v; arg = k; }
         }
         out[i] = (uint8_t)arg;
@@ -943,10 +843,7 @@ __global__ __launch_bounds__(256) void resize_argmax_u8_kernel(const float* __re
 int launch_resize_argmax_u8(const float* in, int B, int K, int Hi, int Wi, uint8_t* out, int Ho, int Wo, hipStream_t s) {
     FS_REQUIRE(K >= 1 && K <= 255, "resize_argmax_u8: K out of range");
     const int64_t total = (int64_t)B * Ho * Wo;
-    if (total < ((int64_t)1 << 31)) hipLaunchKernelGGL((resize_argmax_u8_kernel<unsigned>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 16384)), dim3(256), 0, s, in, B,
-                       K, Hi, Wi, out, Ho, Wo, resize_scale(Hi, Ho, 1), resize_scale(Wi, Wo, 1));
-    else hipLaunchKernelGGL((resize_argmax_u8_kernel<int64_t>), dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 16384)), dim3(256), 0, s, in, B,
-                       K, Hi, Wi, out, Ho, Wo, resize_scale(Hi, Ho, 1), resize_scale(Wi, Wo, 1));
+    FS_LAUNCH_INDEXED(resize_argmax_u8_kernel, total, 16384, s, in, B, K, Hi, Wi, out, Ho, Wo, resize_scale(Hi, Ho, 1), resize_scale(Wi, Wo, 1));
     FS_HIP(hipGetLastError());
     return 0;
 }
@@ -964,12 +861,10 @@ __global__ __launch_bounds__(256) void resize_crop_kernel(const float* __restric
         const int64_t b = i / HWo, px = i - b * HWo;
         const int oy = (int)(px / Wo), ox = (int)(px - (int64_t)oy * Wo);
         const LinCoord cy = lin_coord(oy, Hi, sy, ac), cx = lin_coord(ox, Wi, sx, ac);
-        const int o00 = cy.i0 * Wi + cx.i0, o01 = cy.i0 * Wi + cx.i1, o10 = cy.i1 * Wi + cx.i0, o11 = cy.i1 * Wi + cx.i1;
         float best = 0.f;
         int arg = 0;
         for (int k = 0; k < K; ++k) {
-            const float* pl = in + ((size_t)b * K + k) * Hi * Wi;
-            const float v = bilerp(pl[o00], pl[o01], pl[o10], pl[o11], cy, cx);
+            const float v = bilerp_at(in + ((size_t)b * K + k) * Hi * Wi, Wi, cy, cx);
             if (LOGITS) logits[((size_t)b * K + k) * HWo + px] = v;
             if (MASK && (k == 0 || v > best)) { best = v; arg = k; }
         }

@@ -163,7 +163,7 @@ int launch_resize_bilinear_nchw(const float* in, int BC, int Hi, int Wi, float* 
                                 int align_corners, hipStream_t s);
 // NHWC bilinear resize (feature maps).
 int launch_resize_bilinear_nhwc(const float* in, int ld_in, int B, int C, int Hi, int Wi, float* out, int ld_out,
-                                int Ho, int Wo, int align_corners, hipStream_t s);
+                                int Ho, int Wo, int align_corners, hipStream_t s, int max_blocks = 16384);
 // out = wa*a + wb*b  (b may be nullptr -> out = wa*a)
 int launch_blend(const float* a, float wa, const float* b, float wb, float* out, int64_t numel, hipStream_t s);
 

@@ -35,6 +35,16 @@ __device__ __forceinline__ HalfPix half_pix(int dst, int in_size, double scale) 
     return c;
 }
 
+// the same taps with fp32 weights, as bilerp takes them
+__device__ __forceinline__ LinCoord lin_from_half(const HalfPix& h) {
+    LinCoord c;
+    c.i0 = h.i0;
+    c.i1 = h.i1;
+    c.w1 = (float)h.w1;
+    c.w0 = __fadd_rn(1.f, -c.w1);
+    return c;
+}
+
 // ------------------------------------------------------------------ (a) frame preparation, one launch per scale
 // out[0] = the scaled (:200), mean-padded (:272-273), normalised (:300-306) frame [3][PH][PW]; out[1] (flip) = its horizontal
 // mirror.  A padding pixel holds `mean`, so its normalised value (mean - mean) / std is exactly 0.  Each thread owns one column
@@ -49,12 +59,7 @@ __global__ __launch_bounds__(256) void ms_prepare_kernel(const float* __restrict
     if (X >= PW) return;
     const int x = min(max(X - pad_left, 0), new_w - 1);
     const bool x_in = X >= pad_left && X < pad_left + new_w;
-    const HalfPix hx = half_pix(x, W, sx);
-    LinCoord cx;
-    cx.i0 = hx.i0;
-    cx.i1 = hx.i1;
-    cx.w1 = (float)hx.w1;
-    cx.w0 = __fadd_rn(1.f, -cx.w1);
+    const LinCoord cx = lin_from_half(half_pix(x, W, sx));
     const size_t plane_in = (size_t)H * W, plane_out = (size_t)PH * PW;
     const float mean[3] = {m0, m1, m2}, std[3] = {s0, s1, s2};
     for (int r = 0; r < MS_ROWS; ++r) {
@@ -62,17 +67,10 @@ __global__ __launch_bounds__(256) void ms_prepare_kernel(const float* __restrict
         if (Y >= PH) break;
         const int y = min(max(Y - pad_top, 0), new_h - 1);
         const bool inside = x_in && Y >= pad_top && Y < pad_top + new_h;
-        const HalfPix hy = half_pix(y, H, sy);
-        LinCoord cy;
-        cy.i0 = hy.i0;
-        cy.i1 = hy.i1;
-        cy.w1 = (float)hy.w1;
-        cy.w0 = __fadd_rn(1.f, -cy.w1);
-        const size_t r0 = (size_t)cy.i0 * W, r1 = (size_t)cy.i1 * W;
+        const LinCoord cy = lin_from_half(half_pix(y, H, sy));
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float* pl = raw + c * plane_in;
-            const float v = bilerp(pl[r0 + cx.i0], pl[r0 + cx.i1], pl[r1 + cx.i0], pl[r1 + cx.i1], cy, cx);
+            const float v = bilerp_at(raw + c * plane_in, (size_t)W, cy, cx);
             float o = __fdiv_rn(__fadd_rn(v, -mean[c]), std[c]);  // t.sub_(m).div_(s), :305-306
             if (!inside) o = 0.f;
             out[c * plane_out + (size_t)Y * PW + X] = o;
@@ -98,36 +96,19 @@ int launch_ms_prepare(const float* raw, int H, int W, int new_h, int new_w, int 
 // ------------------------------------------------------------------ (b) crop and flip fusion of one scale
 // Every pixel of the un-padded region of the scaled frame is written once from the crops that cover it, in the reference's crop
 // order (:281-291; the float64 sums depend on it).  Per covering crop: net_process' align_corners=True upsample (:322, the
-// operation order of crops_fuse_kernel / resize_bilinear_nchw) and fp32 softmax over K (:323, max, exp(x - max), sum, divide as
-// softmax_accumulate_kernel) of the crop's logits; with lo_flip the same for the flipped crop's logits at the mirrored column
+// operation order of crops_fuse_kernel / resize_bilinear_nchw: bilerp_at) and fp32 softmax over K (:323: softmax_k) of the crop's
+// logits; with lo_flip the same for the flipped crop's logits at the mirrored column
 // cw - 1 - x (output[1].flip(2)) and (a + b) / 2 in fp32 (:325).  Summed in float64 (:279, :291), divided by the float64 crop
 // count (:292); the padding is never computed (:293).  scaled: [new_h][new_w][K] float64, pixel-major, which is what (c) reads:
 // its four taps are four runs of K contiguous doubles.
 template <int KMAX>
 __device__ __forceinline__ void ms_crop_softmax(const float* __restrict__ lo, int K, int h, int w, const LinCoord& cy, const LinCoord& cx,
                                                 float (&p)[KMAX]) {
-    const int o00 = cy.i0 * w + cx.i0, o01 = cy.i0 * w + cx.i1, o10 = cy.i1 * w + cx.i0, o11 = cy.i1 * w + cx.i1;
     const int plane = h * w;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-            const float* pl = lo + (size_t)k * plane;
-            p[k] = bilerp(pl[o00], pl[o01], pl[o10], pl[o11], cy, cx);
-        }
-    float mx = p[0];
-#pragma unroll
-    for (int k = 1; k < KMAX; ++k)
-        if (k < K) mx = fmaxf(mx, p[k]);
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-            p[k] = expf(p[k] - mx);
-            sum += p[k];
-        }
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-        if (k < K) p[k] = p[k] / sum;
+        if (k < K) p[k] = bilerp_at(lo + (size_t)k * plane, w, cy, cx);
+    softmax_k<KMAX>(p, K, [&](int k, float q) { p[k] = q; });
 }
 
 template <int KMAX>

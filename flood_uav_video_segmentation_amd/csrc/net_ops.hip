@@ -7,8 +7,6 @@
 
 namespace fs {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // -------------------------------------------------------------------------------------------
 // Stem conv (Cin = 3) from NCHW, fused scale/shift + ReLU, NHWC out.
 // Block = 64 output pixels x 4 channel groups; filter bank lives in LDS ([tap*3+ci][Cout]).
@@ -590,37 +588,10 @@ int launch_rowdot_1x1(const float* in, int ld_in, const float* wgt, const float*
 // -------------------------------------------------------------------------------------------
 // Bilinear upsample of a tiny pooled map [B][hi*wi][C] into a channel slice of an NHWC buffer.
 // -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void upsample_into_kernel(const float* __restrict__ in, int hi, int wi, float* __restrict__ out,
-                                                            int ld_out, int B, int Ho, int Wo, int C4, int ac, float sy, float sx) {
-    const int64_t total = (int64_t)B * Ho * Wo * C4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c4 = (int)(i % C4);
-        const int64_t m = i / C4;
-        const int ox = (int)(m % Wo);
-        const int oy = (int)((m / Wo) % Ho);
-        const int b = (int)(m / ((int64_t)Wo * Ho));
-        const LinCoord cy = lin_coord(oy, hi, sy, ac), cx = lin_coord(ox, wi, sx, ac);
-        const float* base = in + (size_t)b * hi * wi * C4 * 4 + c4 * 4;
-        const f32x4 v00 = *reinterpret_cast<const f32x4*>(base + (size_t)(cy.i0 * wi + cx.i0) * C4 * 4);
-        const f32x4 v01 = *reinterpret_cast<const f32x4*>(base + (size_t)(cy.i0 * wi + cx.i1) * C4 * 4);
-        const f32x4 v10 = *reinterpret_cast<const f32x4*>(base + (size_t)(cy.i1 * wi + cx.i0) * C4 * 4);
-        const f32x4 v11 = *reinterpret_cast<const f32x4*>(base + (size_t)(cy.i1 * wi + cx.i1) * C4 * 4);
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = bilerp(v00[e], v01[e], v10[e], v11[e], cy, cx);
-        *reinterpret_cast<f32x4*>(out + (size_t)m * ld_out + c4 * 4) = r;
-    }
-}
-
 int launch_upsample_into(const float* in, int hi, int wi, float* out, int ld_out, int B, int Ho, int Wo, int C,
                          int align_corners, hipStream_t s) {
     FS_REQUIRE(C % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)out & 15) == 0, "upsample_into: C/ld_out must be multiples of 4");
-    const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
-    const int grid = (int)std::min<int64_t>(cdiv64(total, 256), 256 * 32);
-    hipLaunchKernelGGL(upsample_into_kernel, dim3(grid), dim3(256), 0, s, in, hi, wi, out, ld_out, B, Ho, Wo, C / 4,
-                       align_corners, resize_scale(hi, Ho, align_corners), resize_scale(wi, Wo, align_corners));
-    FS_HIP(hipGetLastError());
-    return 0;
+    return launch_resize_bilinear_nhwc(in, C, B, C, hi, wi, out, ld_out, Ho, Wo, align_corners, s, 256 * 32);  // the NHWC resize, dense input
 }
 
 // -------------------------------------------------------------------------------------------

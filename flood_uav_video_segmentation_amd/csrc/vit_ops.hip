@@ -8,7 +8,6 @@
 namespace fs {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------ patchify (zero padded right/bottom)
 __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ in, const float* __restrict__ in2, int B1,

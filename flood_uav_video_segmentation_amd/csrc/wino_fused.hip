@@ -25,8 +25,6 @@
 
 namespace fs {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // F(4,3) B^T d and A^T m on scalars, every multiply-add an explicit fma: all kernel forms then execute the same operations in the
 // same order whatever the optimiser would have contracted -- their results are bit-identical (tests/test_gpu_ops.py), which
 // lets the launcher pick the form by batch size without a frame's result depending on its batch.

@@ -56,7 +56,6 @@ int launch_winograd_filter(const float* w_oihw, float* U, int O, int I, int mt, 
 // VGPRs, and a 90x90x256 map is only 900 waves -- under one per SIMD, every load latency exposed: 15 us for 46 MB.  Split
 // this way the same map is 3600 waves of 8 loads each.)  The arithmetic (B^T d B, A^T m A; which products are formed and in
 // which order) is unchanged.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned wo_u32x4 __attribute__((ext_vector_type(4)));
 
 template <int MT>
