@@ -3,7 +3,7 @@
 //   SPLIT = false  v_mfma_f32_32x32x2_f32: exact f32 fmaf-chain numerics at 64 FLOP/clk/SIMD (157 TFLOP/s chip peak).
 //   SPLIT = true   (round 3, the networks' default) every fp32 operand as the exact sum of three bf16 terms, six of the nine cross
 //                  products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation: fp32 accuracy (the dropped terms are <= 2^-23 of a
-//                  product) at 2.67x the fp32 pipe's rate per clock.  See the comment at the split main loop, DESIGN.md 3.1b.
+//                  product) at 2.67x the fp32 pipe's rate per clock.  The arithmetic is defined in split.h.
 //
 // Mapping (one 256-thread workgroup = 4 waves, one per SIMD, 2x2 over the block tile):
 //   GEMM M = B*Ho*Wo output pixels (A rows, gathered NHWC pixels: 32 channels = one 128-B line)
@@ -14,7 +14,7 @@
 // MFMA operand trick: lane (i = l&31, h = l>>5) reads 4 consecutive k (one ds_read_b128) and
 // feeds element e to the e-th MFMA; A and B use the same k for the same (h, e), and the MFMA
 // sums over k, so any k permutation is legal.
-// D layout (32x32): col(n) = lane&31, row(m) = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+// D layout (32x32): col(n) = lane&31, row(m) = mfma32_row(reg, lane>>5) (split.h)
 //   -> each store instruction writes two 128-B channel runs: coalesced NHWC epilogue.
 // History (measured on MI355X, profiles/r01_conv_*.txt): the bring-up kernel staged tiles through VGPRs with two barriers
 // per chunk (120 TFLOP/s on the decoder conv); double-buffered LDS + register-pinned fragment prefetch alone: null;
@@ -32,10 +32,6 @@
 #include <cstdlib>
 
 namespace fs {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------
 // conv_igemm_dma_f32: the tiles go global -> LDS DIRECTLY
@@ -73,6 +69,24 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int conv_split_rows(int BN, int waves) { return (BN / 16 + waves - 1) / waves * waves * 16; }
 template <int BM, int BN, bool SPLIT, int WAVES = 4>
 constexpr int conv_tile_lds_floats() { return 2 * (BM * 32 + (SPLIT ? 3 * conv_split_rows(BN, WAVES) * 16 : BN * 32)); }
+
+// One unit of the split route's pixel split: level lvl of pair pr (split.h: split_round, then split_residue unless it is the pair's
+// last level).  raw = the step's fragment reads, rq = the pairs' residues, ah = the packed terms [row block][level][pair].  pin anchors
+// the unit where it is written (one per MFMA slot of the main loop): the optimiser would sink it to its use.
+template <int TM>
+__device__ __forceinline__ void split_unit(int lvl, int pr, const f32x4 (&raw)[TM][2], float (&rq)[4 * TM][2], u32x4 (&ah)[TM][3], bool pin) {
+    const int pi = pr / 4, pe = pr % 4;
+    float x0 = lvl == 0 ? raw[pi][pe >> 1][2 * (pe & 1)] : rq[pr][0];
+    float x1 = lvl == 0 ? raw[pi][pe >> 1][2 * (pe & 1) + 1] : rq[pr][1];
+    unsigned pk = split_round(x0, x1);
+    if (pin) asm volatile("" : "+v"(pk));
+    ah[pi][lvl][pe] = pk;
+    if (lvl < 2) {
+        split_residue(pk, x0, x1);
+        rq[pr][0] = x0;
+        rq[pr][1] = x1;
+    }
+}
 
 // One BM x BN output tile at (m0, n0): prologue, main loop, epilogue.  `lds` = conv_tile_lds_floats() floats, 1 KiB aligned; every
 // wave of the workgroup calls it with the same arguments.
@@ -274,12 +288,8 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
         FS_DMA_ADVANCE()
     }
     if constexpr (SPLIT) {
-        // Split operands: every fp32 value x is the exact sum h + m + l of three bf16 terms (h = bf16(x), m = bf16(x - h),
-        // l = bf16(x - h - m), round to nearest even; 3 x 8 significant bits with signed residues cover the 24 of fp32).  The filters
-        // arrive split (three planes); the pixels are split here, in registers, right after the fragment read.  Of the nine cross
-        // products the six of order <= 2^-16 go to the bf16 matrix pipe (v_mfma_f32_32x32x16_bf16: exact products, fp32 accumulate):
-        //   x * w = hh + (hm + mh) + (mm + hl + lh) + [ml + lm + ll <= 2^-23 |x w|, dropped: below the rounding of one fp32 add]
-        // A chunk of 32 k = two MFMA steps of 16 k; lane (i, hh) owns k = 16 s + 8 hh .. + 7 of row i in both operands.
+        // Split operands (split.h): the filters arrive split (three planes); the pixels are split here, in registers, right after the
+        // fragment read.  A chunk of 32 k = two MFMA steps of 16 k; lane (i, hh) owns k = 16 s + 8 hh .. + 7 of row i in both operands.
         bf16x8 A3[TM][3], B3[TN][3], A3n[TM][3], B3n[TN][3];
         f32x4 araw[TM][2];
         u32x4 ah[TM][3];
@@ -306,23 +316,13 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
         float rq[NP][2];
 #define FS_STEP3(A_, B_, RAW_, AN_)                                                                               \
     _Pragma("unroll") for (int k = 0; k < NS; ++k) {                                                              \
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};                                     \
         const int term = k / (TM * TN), i_ = (k % (TM * TN)) / TN, j_ = k % TN;                                   \
-        acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[i_][PA[term]], B_[j_][PB[term]], acc[i_][j_], 0, 0, 0); \
+        acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[i_][SPLIT_PA[term]], B_[j_][SPLIT_PB[term]], acc[i_][j_], 0, 0, 0); \
         _Pragma("unroll") for (int u = 0; u < NU; ++u) {                                                          \
-            const int lvl = u / NP, pr = u % NP, pi = pr / 4, pe = pr % 4;                                        \
+            const int lvl = u / NP, pr = u % NP;                                                                  \
             const int v_ = lvl < 2 ? u : NP + pr;  /* level unit (of the pair's level 1 for a final) */            \
             const int sl = S0 + (2 * NP <= NS - S0 ? v_ : v_ * (NS - S0) / (2 * NP));                             \
-            if ((lvl < 2 ? sl : (sl + 1 < NS ? sl + 1 : NS - 1)) != k) continue;                                  \
-            const float x0 = lvl == 0 ? RAW_[pi][pe >> 1][2 * (pe & 1)] : rq[pr][0];                              \
-            const float x1 = lvl == 0 ? RAW_[pi][pe >> 1][2 * (pe & 1) + 1] : rq[pr][1];                          \
-            unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x0, x1}, bf16x2));         \
-            asm volatile("" : "+v"(pk));  /* anchors the unit in THIS slot: the optimiser would sink it to its use */ \
-            ah[pi][lvl][pe] = pk;                                                                                 \
-            if (lvl < 2) {                                                                                        \
-                rq[pr][0] = x0 - __builtin_bit_cast(float, pk << 16);                                             \
-                rq[pr][1] = x1 - __builtin_bit_cast(float, pk & 0xffff0000u);                                     \
-            }                                                                                                     \
+            if ((lvl < 2 ? sl : (sl + 1 < NS ? sl + 1 : NS - 1)) == k) split_unit(lvl, pr, RAW_, rq, ah, true);   \
         }                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
     }                                                                                                             \
@@ -331,17 +331,7 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
         FS_READ3(0, 0, araw, B3)
         {   // prologue: split step 0's pixels (no MFMA to hide under yet)
 #pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                const int lvl = u / NP, pr = u % NP, pi = pr / 4, pe = pr % 4;
-                const float x0 = lvl == 0 ? araw[pi][pe >> 1][2 * (pe & 1)] : rq[pr][0];
-                const float x1 = lvl == 0 ? araw[pi][pe >> 1][2 * (pe & 1) + 1] : rq[pr][1];
-                const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x0, x1}, bf16x2));
-                ah[pi][lvl][pe] = pk;
-                if (lvl < 2) {
-                    rq[pr][0] = x0 - __builtin_bit_cast(float, pk << 16);
-                    rq[pr][1] = x1 - __builtin_bit_cast(float, pk & 0xffff0000u);
-                }
-            }
+            for (int u = 0; u < NU; ++u) split_unit(u / NP, u % NP, araw, rq, ah, false);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -514,22 +504,16 @@ namespace {
 // filter rows of the split bank are bf16: 16-B DMA pieces need a row stride that is a multiple of 8 elements
 bool ldw_ok(const ConvParams& p) { return (p.ld_wgt ? p.ld_wgt : p.KH * p.KW * p.Cin + (p.in2 ? p.Cin2 : 0)) % 8 == 0; }
 
-__global__ void split_bf16x3_kernel(const float* __restrict__ w, long long n, __bf16* __restrict__ planes) {
+__global__ void split_bf16x3_kernel(const float* __restrict__ w, long long n, unsigned short* __restrict__ planes) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float x = w[i];
-    const __bf16 h = (__bf16)x;
-    const float r = x - (float)h;
-    const __bf16 m = (__bf16)r;
-    planes[i] = h;
-    planes[n + i] = m;
-    planes[2 * n + i] = (__bf16)(r - (float)m);
+    split3(w[i], planes[i], planes[n + i], planes[2 * n + i]);
 }
 }  // namespace
 
 int launch_split_bf16x3(const float* w, long long n, void* planes, hipStream_t s) {
     FS_REQUIRE(w && planes && n > 0 && n % 8 == 0, "split_bf16x3: bad arguments (n=%lld)", n);
-    hipLaunchKernelGGL(split_bf16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, n, (__bf16*)planes);
+    hipLaunchKernelGGL(split_bf16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, n, (unsigned short*)planes);
     FS_HIP(hipGetLastError());
     return 0;
 }

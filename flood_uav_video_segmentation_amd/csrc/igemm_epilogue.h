@@ -1,10 +1,10 @@
 // Epilogue of the matrix-core GEMM kernel (conv_igemm.hip): y = act(acc * scale + shift (+ residual)) for the 32x32
-// accumulator blocks of v_mfma_f32_32x32x*: col(n) = lane & 31, row(m) = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
+// accumulator blocks of v_mfma_f32_32x32x*: col(n) = lane & 31, row(m) = mfma32_row(reg, lane >> 5) (split.h).
 #pragma once
 #include "kernels.h"
+#include "split.h"
 
 namespace fs {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // Epilogue of the DMA kernel: y = act(acc * scale + shift (+ residual)) stored through a buffer descriptor whose range
@@ -31,7 +31,7 @@ __device__ __forceinline__ void igemm_load_residual(float (&rv)[TM][TN][16], con
             const unsigned vr = n < p.Cout ? (unsigned)(m_base + i * 32) * row_r + (unsigned)n * 4u : SENT;
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                rv[i][j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, vr + (unsigned)((e & 3) + 8 * (e >> 2)) * row_r, 0, 0));
+                rv[i][j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, vr + (unsigned)mfma32_row(e, 0) * row_r, 0, 0));
         }
     }
 }
@@ -77,29 +77,16 @@ __device__ __forceinline__ void igemm_epilogue(const f32x16 (&acc)[TM][TN], cons
                 if (RES) v += rv[i][j][e];
                 if (ACT == 1) v = fmaxf(v, 0.f);
                 else if (ACT == 2) v = 0.5f * v * (1.f + gelu_erf(v * 0.70710678118654752f));  // nn.GELU (erf form)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rsrc, vo + (unsigned)((e & 3) + 8 * (e >> 2)) * row_o, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rsrc, vo + (unsigned)mfma32_row(e, 0) * row_o, 0, 0);
             }
         }
     }
 }
 
 // ---- the Segmenter's qkv Linear: K / V column tiles written as the attention's operand planes (ConvParams::kv_k)
-typedef unsigned ep_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 ep_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ep_f32x2 __attribute__((ext_vector_type(2)));
-
-// (x0, x1) -> the three bf16 terms of each (x = h + m + l exactly, round-to-nearest residues), packed {x0 term, x1 term}
-__device__ __forceinline__ void ep_split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = __builtin_bit_cast(unsigned, __builtin_convertvector((ep_f32x2){x0, x1}, ep_bf16x2));
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector((ep_f32x2){r0, r1}, ep_bf16x2));
-    const float q0 = r0 - __builtin_bit_cast(float, m << 16), q1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector((ep_f32x2){q0, q1}, ep_bf16x2));
-}
-
 // kind 1: K tile, kind 2: V tile.  m_base = first row of this lane's rows (block base + 4 * hh), n_rel = this lane's first column relative to
 // the start of K (resp. V) inside the qkv row.  Row r of the 32-row block is key kb + r of image p.kv_b; a lane holds rows
-// (e & 3) + 8 * (e >> 2) + 4 * hh of one column (channel d of one head) per 32-column block.
+// mfma32_row(e, hh) of one column (channel d of one head) per 32-column block.
 //   K  [bh][key][d]:   rows e, e + 1 are consecutive keys; lanes d, d + 1 exchange one of them (DPP), so every lane stores dwords (two
 //                      channels of one key) -- a store instruction covers four 64-B runs.
 //   V^T [bh][d][pos]:  inside 16 keys the position is (k & 3) + 4 (k >> 3) + 8 ((k >> 2) & 1): a lane's registers 8 g .. 8 g + 7 ARE
@@ -118,11 +105,11 @@ __device__ __forceinline__ void igemm_epilogue_kv(const f32x16 (&acc)[1][TN], co
         if (kind == 1) {
 #pragma unroll
             for (int ep = 0; ep < 8; ++ep) {
-                const int e0 = 2 * ep, key0 = m_base + (e0 & 3) + 8 * (e0 >> 2);
+                const int e0 = 2 * ep, key0 = m_base + mfma32_row(e0, 0);
                 const float v0 = key0 < N ? acc[0][j][e0] * sc[j] + sh[j] : 0.f;
                 const float v1 = key0 + 1 < N ? acc[0][j][e0 + 1] * sc[j] + sh[j] : 0.f;
                 unsigned H, Mm, L;
-                ep_split_pair(v0, v1, H, Mm, L);  // low halves: key0, high halves: key0 + 1, channel d
+                split_pair(v0, v1, H, Mm, L);  // low halves: key0, high halves: key0 + 1, channel d
                 // even lanes keep key0 and receive the neighbour's (channel d + 1); odd lanes keep key0 + 1 and receive channel d - 1's
                 const unsigned send_hm = odd ? ((H & 0xffffu) | (Mm << 16)) : ((H >> 16) | (Mm & 0xffff0000u));
                 const unsigned send_l = odd ? (L & 0xffffu) : (L >> 16);
@@ -141,14 +128,14 @@ __device__ __forceinline__ void igemm_epilogue_kv(const f32x16 (&acc)[1][TN], co
             const int kb = m_base - 4 * hh;  // first key of the 32-row block (a multiple of 32)
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-                ep_u32x4 H, Mm, L;
+                u32x4 H, Mm, L;
 #pragma unroll
                 for (int t2 = 0; t2 < 4; ++t2) {
-                    const int e0 = 8 * g + 2 * t2, key0 = m_base + (e0 & 3) + 8 * (e0 >> 2);
+                    const int e0 = 8 * g + 2 * t2, key0 = m_base + mfma32_row(e0, 0);
                     const float v0 = key0 < N ? acc[0][j][e0] * sc[j] + sh[j] : 0.f;
                     const float v1 = key0 + 1 < N ? acc[0][j][e0 + 1] * sc[j] + sh[j] : 0.f;
                     unsigned h, m, l;
-                    ep_split_pair(v0, v1, h, m, l);
+                    split_pair(v0, v1, h, m, l);
                     H[t2] = h; Mm[t2] = m; L[t2] = l;
                 }
                 const unsigned vo = (col_ok && kb < Npad) ? (unsigned)(((bh * 64 + d) * Npad + kb + 16 * g + 8 * hh) * 2) : SENT;
@@ -160,6 +147,5 @@ __device__ __forceinline__ void igemm_epilogue_kv(const f32x16 (&acc)[1][TN], co
     }
 }
 #endif
-
 
 }  // namespace fs

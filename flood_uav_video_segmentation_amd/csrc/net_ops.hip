@@ -2,6 +2,7 @@
 // weight packing and layout changes.  All NHWC unless the name says otherwise.
 #include "interp.h"
 #include "kernels.h"
+#include "split.h"
 
 #include <type_traits>
 
@@ -88,45 +89,79 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(StemParams p) {
 // The VALU version above spends 27 (147) x Cout fmas per pixel on ds_read-fed VALU: 47 us (139 us for the 7x7 stem) at
 // 713x713, B = 2, against an 11 us HBM write; this one needs 28 (148) MFMAs per 32 pixels.
 // -------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+// What the two matrix-core stem kernels share.  Frame geometry: row stride and plane size of the frame the taps are read from
+// (crop mode reads windows of a full frame: the frame's strides, zero padding at the CROP's border).
+struct StemFrame { int rowW; long long plane; };
+__device__ __forceinline__ StemFrame stem_frame(const StemParams& p) {
+    return {p.src.ncrops ? p.src.FW : p.W, p.src.ncrops ? (long long)p.src.FH * p.src.FW : (long long)p.H * p.W};
+}
+
+// tap table in LDS, k = (ky*KW + kx)*3 + ci: koff[k] = element offset of tap k from the patch origin, kyx[k] = ky << 16 | kx
+__device__ __forceinline__ void stem_tap_table(const StemParams& p, const StemFrame& f, int taps, int kpad, int* koff, int* kyx) {
+    for (int k = threadIdx.x; k < kpad; k += 256) {
+        const int kk = k < taps ? k : 0;
+        const int ci = kk % 3, kx = (kk / 3) % p.KW, ky = kk / (3 * p.KW);
+        koff[k] = (int)(ci * f.plane + (long long)ky * f.rowW + kx);
+        kyx[k] = k < taps ? (ky << 16 | kx) : (0x7fff << 16);  // padding taps: a row index no image has
+    }
+}
+
+// output pixel mm -> the input coordinates of its first tap and the address of that tap in its frame (plain batch or crop window)
+struct StemPixel { int iy0, ix0; const float* origin; };
+__device__ __forceinline__ StemPixel stem_pixel(const StemParams& p, const StemFrame& f, int mm) {
+    const int hw = p.Ho * p.Wo;
+    const int b = mm / hw, rem = mm - b * hw;
+    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
+    const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+    const float* inb;
+    if (p.src.ncrops) {
+        const int c = b < p.src.ncrops ? b : b - p.src.ncrops;
+        inb = (b < p.src.ncrops ? p.src.in : p.src.in2) + (size_t)p.src.cy[c] * f.rowW + p.src.cx[c];
+    } else {
+        inb = b < p.src.B1 ? p.src.in + (size_t)b * 3 * f.plane : p.src.in2 + (size_t)(b - p.src.B1) * 3 * f.plane;
+    }
+    return {iy0, ix0, inb + (long long)iy0 * f.rowW + ix0};  // may point before the frame: only dereferenced for in-range taps
+}
+
+// y = relu(acc * scale + shift) of one 32-pixel tile.  D layout: col n = lane & 31, row = mfma32_row(e, h): every store instruction
+// writes two 128-B channel runs.  Straight-line stores through a buffer descriptor whose range check is the row guard (rows >= M fall
+// outside: the launcher keeps M * ld_out * 4 < 2 GiB): written as `if (mr < M) store` every store sat in a basic block of its own
+// behind an s_waitcnt vmcnt(0), which also waits for the previous store (round 6).
+template <int NT>
+__device__ __forceinline__ void stem_store_tile(const f32x16 (&acc)[NT], const StemParams& p, __amdgpu_buffer_rsrc_t o_rsrc, int tile, int i, int h) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int n = j * 32 + i;
+        const float sc = p.scale[n], sh = p.shift[n];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int mr = tile * 32 + mfma32_row(e, h);
+            const float v = fmaxf(acc[j][e] * sc + sh, 0.f);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rsrc, (unsigned)(mr * p.ld_out + n) * 4u, 0, 0);
+        }
+    }
+}
 
 template <int NT /* 32-channel sub-tiles */>
 __global__ __launch_bounds__(256) void stem_conv_mfma_kernel(StemParams p, int ksteps) {
+#if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int taps = p.KH * p.KW * 3, kpad = 2 * ksteps;
     float* wl = smem;                                            // [kpad][Cout], rows >= taps are zero
-    int* koff = reinterpret_cast<int*>(smem + kpad * p.Cout);    // [kpad]: element offset of tap k from the patch origin
-    int* kyx = koff + kpad;                                      // [kpad]: ky << 16 | kx
-    const int rowW = p.src.ncrops ? p.src.FW : p.W;
-    const long long plane = p.src.ncrops ? (long long)p.src.FH * p.src.FW : (long long)p.H * p.W;
+    int* koff = reinterpret_cast<int*>(smem + kpad * p.Cout);    // [kpad]
+    int* kyx = koff + kpad;                                      // [kpad]
+    const StemFrame f = stem_frame(p);
     for (int i = threadIdx.x; i < kpad * p.Cout; i += 256) wl[i] = i < taps * p.Cout ? p.wgt[i] : 0.f;
-    for (int k = threadIdx.x; k < kpad; k += 256) {
-        const int kk = k < taps ? k : 0;  // k = (ky*KW + kx)*3 + ci
-        const int ci = kk % 3, kx = (kk / 3) % p.KW, ky = kk / (3 * p.KW);
-        koff[k] = (int)(ci * plane + (long long)ky * rowW + kx);
-        kyx[k] = k < taps ? (ky << 16 | kx) : (0x7fff << 16);  // padding taps: a row index no image has
-    }
+    stem_tap_table(p, f, taps, kpad, koff, kyx);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
-    const int M = p.B * p.Ho * p.Wo, hw = p.Ho * p.Wo;
-    // rows >= M fall outside the descriptor's range: the stores are dropped (launcher: M * ld_out * 4 < 2 GiB)
+    const int M = p.B * p.Ho * p.Wo;
     const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (unsigned)((long long)M * p.ld_out * 4), 0x00020000);
     const int tiles = (M + 31) / 32;
     for (int tile = blockIdx.x * 4 + wave; tile < tiles; tile += gridDim.x * 4) {
         const int m = tile * 32 + i;
         const bool mok = m < M;
-        const int mm = mok ? m : 0;
-        const int b = mm / hw, rem = mm - b * hw;
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-        const float* inb;
-        if (p.src.ncrops) {
-            const int c = b < p.src.ncrops ? b : b - p.src.ncrops;
-            inb = (b < p.src.ncrops ? p.src.in : p.src.in2) + (size_t)p.src.cy[c] * rowW + p.src.cx[c];
-        } else {
-            inb = b < p.src.B1 ? p.src.in + (size_t)b * 3 * plane : p.src.in2 + (size_t)(b - p.src.B1) * 3 * plane;
-        }
-        const float* origin = inb + (long long)iy0 * rowW + ix0;  // may point before the frame: only dereferenced for in-range taps
+        const StemPixel px = stem_pixel(p, f, mok ? m : 0);
         f32x16 acc[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j)
@@ -139,9 +174,9 @@ __global__ __launch_bounds__(256) void stem_conv_mfma_kernel(StemParams p, int k
             for (int u = 0; u < 8; ++u) {
                 const int k = 2 * (s0 + u) + h;
                 const int yx = kyx[k];
-                const int iy = iy0 + (yx >> 16), ix = ix0 + (yx & 0xffff);
+                const int iy = px.iy0 + (yx >> 16), ix = px.ix0 + (yx & 0xffff);
                 const bool ok = mok && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-                av[u] = ok ? origin[koff[k]] : 0.f;
+                av[u] = ok ? px.origin[koff[k]] : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -150,97 +185,51 @@ __global__ __launch_bounds__(256) void stem_conv_mfma_kernel(StemParams p, int k
                 for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], wl[k * p.Cout + j * 32 + i], acc[j], 0, 0, 0);
             }
         }
-        // D layout: col n = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * h: every store instruction writes two 128-B channel runs
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int n = j * 32 + i;
-            const float sc = p.scale[n], sh = p.shift[n];
-            // (straight-line stores through a buffer descriptor whose range check is the row guard: written as `if (mr < M) store` every
-            //  store sat in a basic block of its own behind an s_waitcnt vmcnt(0), which also waits for the previous store: round 6)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int mr = tile * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                const float v = fmaxf(acc[j][e] * sc + sh, 0.f);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rsrc, (unsigned)(mr * p.ld_out + n) * 4u, 0, 0);
-            }
-        }
+        stem_store_tile(acc, p, o_rsrc, tile, i, h);
     }
+#endif
 }
 
 // -------------------------------------------------------------------------------------------
-// (round 5) The same implicit GEMM on the bf16 matrix cores with SPLIT operands, the arithmetic of conv_igemm_dma_f32<SPLIT>: every
-// fp32 pixel and filter value as the exact sum of three bf16 terms, six of the nine cross products on v_mfma_f32_32x32x16_bf16 with
-// fp32 accumulation (the dropped ones are <= 2^-23 of a product).  Why here: five waves per SIMD shared the fp32 matrix pipe for
-// 32 x 64 cycles each and a wave lived 29.7 k cycles for its ONE tile (r04_experiments.txt section 4); the split form needs 12 x NT MFMAs
+// (round 5) The same implicit GEMM on the bf16 matrix cores with SPLIT operands, the arithmetic of conv_igemm_dma_f32<SPLIT> (split.h).
+// Why here: five waves per SIMD shared the fp32 matrix pipe for 32 x 64 cycles each and a wave lived 29.7 k cycles for its ONE tile (r04_experiments.txt section 4); the split form needs 12 x NT MFMAs
 // of 32 cycles per 16 taps instead of 8 x NT of 64 -- 2.7x less matrix time per tile -- and requests the NEXT step's taps before it
 // multiplies the current ones.  A lane (i = l & 31, h = l >> 5) owns taps 16 s + 8 h .. + 7 of pixel i in step s; the filter bank is
 // split once per workgroup into LDS as ready-made B fragments [plane][step][h][Cout][8 bf16].
 // -------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2s __attribute__((ext_vector_type(2)));
-typedef float f32x2s __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-typedef int i32x4s __attribute__((ext_vector_type(4)));
-
 template <int NT /* 32-channel sub-tiles */, int PF /* steps whose taps are in flight together */>
 __global__ __launch_bounds__(256) void stem_conv_split_kernel(StemParams p, int nsteps) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int taps = p.KH * p.KW * 3, kpad = 16 * nsteps;
-    u32x4s* wl = reinterpret_cast<u32x4s*>(smem);                              // [(pl * nsteps + s) * 2 + h][Cout] x 8 bf16
-    int* koff = reinterpret_cast<int*>(smem) + 3 * (kpad / 2) * p.Cout;        // [kpad]: element offset of tap k from the patch origin
-    int* kyx = koff + kpad;                                                    // [kpad]: ky << 16 | kx
-    const int rowW = p.src.ncrops ? p.src.FW : p.W;
-    const long long plane = p.src.ncrops ? (long long)p.src.FH * p.src.FW : (long long)p.H * p.W;
+    u32x4* wl = reinterpret_cast<u32x4*>(smem);                                // [(pl * nsteps + s) * 2 + h][Cout] x 8 bf16
+    int* koff = reinterpret_cast<int*>(smem) + 3 * (kpad / 2) * p.Cout;        // [kpad]
+    int* kyx = koff + kpad;                                                    // [kpad]
+    const StemFrame f = stem_frame(p);
+    const int rowW = f.rowW;
     for (int idx = threadIdx.x; idx < nsteps * 2 * p.Cout; idx += 256) {
         const int n = idx % p.Cout, sh_ = idx / p.Cout, hh = sh_ & 1, st = sh_ >> 1;
-        u32x4s q[3];
+        u32x4 q[3];
         float wv[8];  // all eight loads in flight at once, from clamped addresses; padding taps carry zero weights
 #pragma unroll
         for (int e = 0; e < 8; ++e) wv[e] = p.wgt[min(16 * st + 8 * hh + e, taps - 1) * p.Cout + n];
 #pragma unroll
         for (int e = 0; e < 8; ++e) wv[e] = 16 * st + 8 * hh + e < taps ? wv[e] : 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-            float w[2] = {wv[e], wv[e + 1]};
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2s){w[0], w[1]}, bf16x2s));
-                q[pl][e >> 1] = pk;
-                w[0] -= __builtin_bit_cast(float, pk << 16);
-                w[1] -= __builtin_bit_cast(float, pk & 0xffff0000u);
-            }
-        }
+        split8(wv, q);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) wl[((pl * nsteps + st) * 2 + hh) * p.Cout + n] = q[pl];
     }
-    for (int k = threadIdx.x; k < kpad; k += 256) {
-        const int kk = k < taps ? k : 0;  // k = (ky*KW + kx)*3 + ci
-        const int ci = kk % 3, kx = (kk / 3) % p.KW, ky = kk / (3 * p.KW);
-        koff[k] = (int)(ci * plane + (long long)ky * rowW + kx);
-        kyx[k] = k < taps ? (ky << 16 | kx) : (0x7fff << 16);  // padding taps: a row index no image has
-    }
+    stem_tap_table(p, f, taps, kpad, koff, kyx);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
-    const int M = p.B * p.Ho * p.Wo, hw = p.Ho * p.Wo;
-    // rows >= M fall outside the descriptor's range: the stores are dropped (launcher: M * ld_out * 4 < 2 GiB)
+    const int M = p.B * p.Ho * p.Wo;
     const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (unsigned)((long long)M * p.ld_out * 4), 0x00020000);
     const int tiles = (M + 31) / 32;
     for (int tile = blockIdx.x * 4 + wave; tile < tiles; tile += gridDim.x * 4) {
         const int m = tile * 32 + i;
-        const bool mok = m < M;
-        const int mm = mok ? m : 0;
-        const int b = mm / hw, rem = mm - b * hw;
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-        const float* inb;
-        if (p.src.ncrops) {
-            const int c = b < p.src.ncrops ? b : b - p.src.ncrops;
-            inb = (b < p.src.ncrops ? p.src.in : p.src.in2) + (size_t)p.src.cy[c] * rowW + p.src.cx[c];
-        } else {
-            inb = b < p.src.B1 ? p.src.in + (size_t)b * 3 * plane : p.src.in2 + (size_t)(b - p.src.B1) * 3 * plane;
-        }
-        const float* origin = inb + (long long)iy0 * rowW + ix0;  // may point before the frame: only dereferenced for in-range taps
+        const StemPixel px = stem_pixel(p, f, m < M ? m : 0);
+        const int iy0 = px.iy0, ix0 = px.ix0;
+        const float* origin = px.origin;
         f32x16 acc[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j)
@@ -255,9 +244,9 @@ __global__ __launch_bounds__(256) void stem_conv_split_kernel(StemParams p, int 
         // the compiler wraps the taps in an `if (mok)` region and waits for every load inside it.
         const int centre = p.pad * rowW + p.pad;
         auto gather = [&](int st, float (&av)[8]) -> unsigned {
-            const i32x4s* ko = reinterpret_cast<const i32x4s*>(koff + 16 * st + 8 * h);
-            const i32x4s* ky = reinterpret_cast<const i32x4s*>(kyx + 16 * st + 8 * h);
-            const i32x4s o4[2] = {ko[0], ko[1]}, y4[2] = {ky[0], ky[1]};
+            const i32x4* ko = reinterpret_cast<const i32x4*>(koff + 16 * st + 8 * h);
+            const i32x4* ky = reinterpret_cast<const i32x4*>(kyx + 16 * st + 8 * h);
+            const i32x4 o4[2] = {ko[0], ko[1]}, y4[2] = {ky[0], ky[1]};
             unsigned okbits = 0;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -278,43 +267,21 @@ __global__ __launch_bounds__(256) void stem_conv_split_kernel(StemParams p, int 
             for (int j = 0; j < PF; ++j) {
                 const int st = c0 + j;
                 if (st < nsteps) {  // uniform
-                    u32x4s a3[3];
+                    u32x4 a3[3];
+                    float x[8];
 #pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        float x0 = (okb[j] >> e) & 1 ? raw[j][e] : 0.f, x1 = (okb[j] >> (e + 1)) & 1 ? raw[j][e + 1] : 0.f;
-#pragma unroll
-                        for (int pl = 0; pl < 3; ++pl) {
-                            const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2s){x0, x1}, bf16x2s));
-                            a3[pl][e >> 1] = pk;
-                            x0 -= __builtin_bit_cast(float, pk << 16);
-                            x1 -= __builtin_bit_cast(float, pk & 0xffff0000u);
-                        }
-                    }
-                    // the six products of order <= 2^-16, smallest first: l h', h l', m m', m h', h m', h h'
-                    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+                    for (int e = 0; e < 8; ++e) x[e] = (okb[j] >> e) & 1 ? raw[j][e] : 0.f;
+                    split8(x, a3);
 #pragma unroll
                     for (int term = 0; term < 6; ++term)
 #pragma unroll
                         for (int jn = 0; jn < NT; ++jn)
-                            acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8s, a3[PA[term]]),
-                                                                              __builtin_bit_cast(bf16x8s, wl[((PB[term] * nsteps + st) * 2 + h) * p.Cout + jn * 32 + i]), acc[jn], 0, 0, 0);
+                            acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a3[SPLIT_PA[term]]),
+                                                                              __builtin_bit_cast(bf16x8, wl[((SPLIT_PB[term] * nsteps + st) * 2 + h) * p.Cout + jn * 32 + i]), acc[jn], 0, 0, 0);
                 }
             }
         }
-        // D layout: col n = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * h: every store instruction writes two 128-B channel runs
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int n = j * 32 + i;
-            const float sc = p.scale[n], sh = p.shift[n];
-            // (straight-line stores through a buffer descriptor whose range check is the row guard: written as `if (mr < M) store` every
-            //  store sat in a basic block of its own behind an s_waitcnt vmcnt(0), which also waits for the previous store: round 6)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int mr = tile * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                const float v = fmaxf(acc[j][e] * sc + sh, 0.f);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rsrc, (unsigned)(mr * p.ld_out + n) * 4u, 0, 0);
-            }
-        }
+        stem_store_tile(acc, p, o_rsrc, tile, i, h);
     }
 #endif
 }

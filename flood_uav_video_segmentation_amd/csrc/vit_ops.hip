@@ -2,12 +2,11 @@
 // patchify, token assembly, LayerNorm, fp32-MFMA attention, mask head.
 // Reference arithmetic: segm/model/vit.py:17-137, blocks.py:39-95, decoder.py:80-102, utils.py:65-76.
 #include "kernels.h"
+#include "split.h"
 
 #include <type_traits>
 
 namespace fs {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ------------------------------------------------------------------ patchify (zero padded right/bottom)
 __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ in, const float* __restrict__ in2, int B1,
@@ -204,9 +203,10 @@ int launch_layernorm(const float* in, const float* gamma, const float* beta, flo
 //                     O^T += V^T * P^T        B operand = the S^T accumulator registers as they stand   32 MFMAs
 // (the 32x32 accumulator has its column on the lane and rows (r&3)+8(r>>2)+4h in registers: fed back as
 //  the B operand, step r consumes key (r&3)+8(r>>2) from lane-half 0 and that key + 4 from lane-half 1,
-//  and the A operand reads V at exactly those two keys.)
+//  and the A operand reads V at exactly those two keys; the row formula is mfma32_row of split.h.)
 constexpr int ATT_DH = 64;
 constexpr int ATT_KT = 64;   // keys per tile of the key split (the unit nsplit divides)
+constexpr int ATT_ST = 32;   // keys per stage
 constexpr int ATT_NW = 4;    // waves per workgroup = 128 queries per staged K/V tile.  Measured on ViT-S/16 (N = 1937): 2 waves
                              // (64 queries, 4 workgroups/CU) 36 TFLOP/s -- the K/V staging per query doubles; 4 waves 52+
 
@@ -231,35 +231,70 @@ constexpr int ATT_NW = 4;    // waves per workgroup = 128 queries per staged K/V
 // __launch_bounds__(.., 3): three waves per SIMD (the register-staged kernel fitted 154 VGPRs instead of 210, no spills), so that
 // the three workgroups the key split aims at per CU are really co-resident: 96.8 -> 101.9 TFLOP/s on ViT-S/16
 // (profiles/r02_experiments.txt).
+// What the two attention kernels share.  AttWork: the query of this lane (q; qc = clamped to a row that exists), the workgroup's key
+// split and its share of the 64-key tiles as stages s0 .. s1 - 1 of 32 keys, and scale * log2(e): the softmax runs on v_exp_f32
+// (2^x, 1 ulp) directly -- exp(s - m) == 2^(s' - m') with s' = s * log2(e).
+struct AttWork { int split, q, qc, s0, s1; float scale2; };
+template <bool SPLIT>
+__device__ __forceinline__ AttWork att_work(int N, int nsplit, float scale, int wv, int l31) {
+    const int qtiles = SPLIT ? gridDim.x / nsplit : gridDim.x;
+    const int qt = SPLIT ? blockIdx.x % qtiles : blockIdx.x, split = SPLIT ? blockIdx.x / qtiles : 0;
+    const int q = qt * (32 * ATT_NW) + wv * 32 + l31;
+    const int ntiles_all = (N + ATT_KT - 1) / ATT_KT;
+    const int kt0 = SPLIT ? (ntiles_all * split) / nsplit : 0;
+    const int kt1 = SPLIT ? (ntiles_all * (split + 1)) / nsplit : ntiles_all;
+    return {split, q, min(q, N - 1), 2 * kt0, min(2 * kt1, (N + ATT_ST - 1) / ATT_ST), scale * 1.44269504088896340736f};
+}
+
+// SPLIT: the UNNORMALISED O^T of this split plus (running max, running sum) per query; otherwise the normalised rows of `out`.
+template <bool SPLIT>
+__device__ __forceinline__ void att_write(const f32x16 (&acc_o)[2], float m_run, float l_run, const AttWork& w, int b, int head, int heads, int N,
+                                          int nsplit, int hh, float* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml) {
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (w.q >= N) return;
+    const size_t row = ((size_t)(b * heads + head) * nsplit + w.split) * N + w.q;
+    float* op = SPLIT ? part_o + row * ATT_DH : out + ((size_t)b * N + w.q) * (heads * ATT_DH) + head * ATT_DH;
+    const float inv = SPLIT ? 1.f : 1.f / l_tot;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = SPLIT ? acc_o[i][4 * g + e] : acc_o[i][4 * g + e] * inv;
+            *reinterpret_cast<f32x4*>(op + i * 32 + 8 * g + 4 * hh) = v;
+        }
+    if (SPLIT && hh == 0) {
+        part_ml[2 * row] = m_run;
+        part_ml[2 * row + 1] = l_tot;
+    }
+}
+
 template <bool SPLIT>
 __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_dma_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                      float* __restrict__ part_o, float* __restrict__ part_ml, int N,
                                                                      int heads, float scale, int nsplit) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int ST = 32;  // keys per stage
+    constexpr int ST = ATT_ST;
     __shared__ __attribute__((aligned(1024))) float Ks[2][ST * ATT_DH];
     __shared__ __attribute__((aligned(1024))) float Vs[2][ST * ATT_DH];
     const int D = heads * ATT_DH, ld = 3 * D;
     const int b = blockIdx.z, head = blockIdx.y;
     const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
-    const int qtiles = SPLIT ? gridDim.x / nsplit : gridDim.x;
-    const int qt = SPLIT ? blockIdx.x % qtiles : blockIdx.x, split = SPLIT ? blockIdx.x / qtiles : 0;
-    const int q = qt * (32 * ATT_NW) + wv * 32 + l31;
-    const int qc = min(q, N - 1);
+    const AttWork w = att_work<SPLIT>(N, nsplit, scale, wv, l31);
+    const int s0 = w.s0, s1 = w.s1;
     const float* base = qkv + (size_t)b * N * ld + head * ATT_DH;
 
-    // this lane's query row, dims 32*hh .. 32*hh+31, pre-scaled by scale * log2(e): the softmax then runs on v_exp_f32
-    // (2^x, 1 ulp) directly -- exp(s - m) == 2^(s' - m') with s' = s * log2(e)
-    const float scale2 = scale * 1.44269504088896340736f;
+    // this lane's query row, dims 32*hh .. 32*hh+31, pre-scaled
     float qreg[32];
     {
-        const f32x4* qp = reinterpret_cast<const f32x4*>(base + (size_t)qc * ld + 32 * hh);
+        const f32x4* qp = reinterpret_cast<const f32x4*>(base + (size_t)w.qc * ld + 32 * hh);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const f32x4 v = qp[u];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) qreg[4 * u + e] = v[e] * scale2;
+            for (int e = 0; e < 4; ++e) qreg[4 * u + e] = v[e] * w.scale2;
         }
     }
     f32x16 acc_o[2];
@@ -268,12 +303,6 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_dma_kernel(const flo
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc_o[i][e] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
-
-    // this workgroup's keys: its share of the 64-key tiles, walked 32 keys at a time
-    const int ntiles_all = (N + ATT_KT - 1) / ATT_KT;
-    const int kt0 = SPLIT ? (ntiles_all * split) / nsplit : 0;
-    const int kt1 = SPLIT ? (ntiles_all * (split + 1)) / nsplit : ntiles_all;
-    const int s0 = 2 * kt0, s1 = min(2 * kt1, (N + ST - 1) / ST);
 
     // DMA pieces of this wave: rows 8 wv + 4 j + (lane >> 4), j = 0, 1; physical chunk lane & 15
     constexpr unsigned SENT = 0x80000000u;
@@ -345,47 +374,13 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_dma_kernel(const flo
             acc_o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, sT[r], acc_o[1], 0, 0, 0);
         }
     }
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (SPLIT) {
-        if (q < N) {
-            const size_t row = ((size_t)(b * heads + head) * nsplit + split) * N + q;
-            float* op = part_o + row * ATT_DH;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc_o[i][4 * g + e];
-                    *reinterpret_cast<f32x4*>(op + i * 32 + 8 * g + 4 * hh) = v;
-                }
-            if (hh == 0) {
-                part_ml[2 * row] = m_run;
-                part_ml[2 * row + 1] = l_tot;
-            }
-        }
-        return;
-    }
-    const float inv = 1.f / l_tot;
-    if (q < N) {
-        float* op = out + ((size_t)b * N + q) * D + head * ATT_DH;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc_o[i][4 * g + e] * inv;
-                *reinterpret_cast<f32x4*>(op + i * 32 + 8 * g + 4 * hh) = v;
-            }
-    }
+    att_write<SPLIT>(acc_o, m_run, l_run, w, b, head, heads, N, nsplit, hh, out, part_o, part_ml);
 #endif
 }
 
 // ------------------------------------------------------------------ attention on the bf16 matrix cores with SPLIT operands
-// (round 3, the default route; same idea as the split-operand conv kernel, conv_igemm.hip / DESIGN.md 3.1b): every fp32 value of
-// Q, K, V and of the probabilities P is the exact sum of three bf16 terms; the six cross products of order <= 2^-16 run on
-// v_mfma_f32_32x32x16_bf16 with fp32 accumulation, the three dropped ones are <= 2^-23 of a product.  Softmax stays in fp32.
+// (round 3, the default route; the arithmetic of the split-operand conv kernel: split.h): every fp32 value of Q, K, V
+// and of the probabilities P goes to v_mfma_f32_32x32x16_bf16 as its three bf16 terms.  Softmax stays in fp32.
 //   * a pre-pass (attention_split_kv_kernel) writes K as three planes [bh][key][64] and V TRANSPOSED as three planes
 //     [bh][64][key] (bf16; keys padded with zeros to a multiple of 32; inside every 16 keys the order is 0-3, 8-11, 4-7, 12-15,
 //     which is the order in which a lane of the S^T accumulator holds its eight keys of a 16-key step -- so P needs no shuffle);
@@ -394,19 +389,6 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_dma_kernel(const flo
 //     both fragment reads are one conflict-free ds_read_b128 per plane;
 //   * S^T = K Q^T: 4 steps of 16 d x 6 terms; O^T += V^T P^T: 2 d-blocks x 2 steps of 16 keys x 6 terms: 48 MFMAs of 32 cycles per
 //     32 keys instead of 64 of 64 cycles; Q is split once per workgroup, P once per stage (72 VALU instructions).
-typedef __bf16 abf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 abf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned au32x4 __attribute__((ext_vector_type(4)));
-typedef float af32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void att_split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = __builtin_bit_cast(unsigned, __builtin_convertvector((af32x2){x0, x1}, abf16x2));
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector((af32x2){r0, r1}, abf16x2));
-    const float q0 = r0 - __builtin_bit_cast(float, m << 16), q1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector((af32x2){q0, q1}, abf16x2));
-}
-
 // thread = (bh, key, 8 consecutive d); Kp / Vtp: [3][BH][Npad][64] and [3][BH][64][Npad] bf16
 __global__ __launch_bounds__(256) void attention_split_kv_kernel(const float* __restrict__ qkv, unsigned short* __restrict__ Kp,
                                                                  unsigned short* __restrict__ Vtp, int B, int N, int Npad, int heads) {
@@ -430,30 +412,17 @@ __global__ __launch_bounds__(256) void attention_split_kv_kernel(const float* __
 #pragma unroll
         for (int e = 0; e < 8; ++e) k[e] = v[e] = 0.f;
     }
-    au32x4 kh, km, kl;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        unsigned h, m, l;
-        att_split_pair(k[2 * e], k[2 * e + 1], h, m, l);
-        kh[e] = h; km[e] = m; kl[e] = l;
-    }
+    u32x4 kp[3];
+    split8(k, kp);
     const size_t ko = ((size_t)bh * Npad + key) * ATT_DH + 8 * dg;
-    *reinterpret_cast<au32x4*>(Kp + ko) = kh;
-    *reinterpret_cast<au32x4*>(Kp + plane + ko) = km;
-    *reinterpret_cast<au32x4*>(Kp + 2 * plane + ko) = kl;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(Kp + pl * plane + ko) = kp[pl];
     // V transposed; position of key k inside its group of 16: (k & 3) + 4 (k >> 3) + 8 ((k >> 2) & 1)
     const int kk = key & 15, pos = (key & ~15) + (kk & 3) + 4 * (kk >> 3) + 8 * ((kk >> 2) & 1);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float x = v[e];
-        const __bf16 hb = (__bf16)x;
-        const float r = x - (float)hb;
-        const __bf16 mb = (__bf16)r;
-        const __bf16 lb = (__bf16)(r - (float)mb);
         const size_t vo = ((size_t)bh * ATT_DH + 8 * dg + e) * Npad + pos;
-        Vtp[vo] = __builtin_bit_cast(unsigned short, hb);
-        Vtp[plane + vo] = __builtin_bit_cast(unsigned short, mb);
-        Vtp[2 * plane + vo] = __builtin_bit_cast(unsigned short, lb);
+        split3(v[e], Vtp[vo], Vtp[plane + vo], Vtp[2 * plane + vo]);
     }
 }
 
@@ -463,7 +432,7 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_bf16x3_kernel(const 
                                                                         float* __restrict__ part_o, float* __restrict__ part_ml, int N, int Npad,
                                                                         int heads, float scale, int nsplit, unsigned plane_bytes) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int ST = 32;     // keys per stage
+    constexpr int ST = ATT_ST;
     constexpr int PL = 1024;   // floats of LDS per plane and stage (4 KB: 32 keys x 128 B, or 64 d-rows x 64 B)
     __shared__ __attribute__((aligned(1024))) float Ks[2][3 * PL];
     __shared__ __attribute__((aligned(1024))) float Vs[2][3 * PL];
@@ -471,22 +440,14 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_bf16x3_kernel(const 
     const int b = blockIdx.z, head = blockIdx.y, bh = b * heads + head;
     const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
-    const int qtiles = SPLIT ? gridDim.x / nsplit : gridDim.x;
-    const int qt = SPLIT ? blockIdx.x % qtiles : blockIdx.x, split = SPLIT ? blockIdx.x / qtiles : 0;
-    const int q = qt * (32 * ATT_NW) + wv * 32 + l31;
-    const int qc = min(q, N - 1);
-    const float scale2 = scale * 1.44269504088896340736f;
+    const AttWork w = att_work<SPLIT>(N, nsplit, scale, wv, l31);  // the same queries and key ranges per split as attention_dma_kernel
+    const int s0 = w.s0, s1 = w.s1;
     f32x16 acc_o[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc_o[i][e] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
-
-    const int ntiles_all = (N + ATT_KT - 1) / ATT_KT;  // the same key ranges per split as attention_dma_kernel
-    const int kt0 = SPLIT ? (ntiles_all * split) / nsplit : 0;
-    const int kt1 = SPLIT ? (ntiles_all * (split + 1)) / nsplit : ntiles_all;
-    const int s0 = 2 * kt0, s1 = min(2 * kt1, (N + ST - 1) / ST);
 
     const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, 3u * plane_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Vtp, 0, 3u * plane_bytes, 0x00020000);
@@ -504,27 +465,23 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_bf16x3_kernel(const 
         }
     };
     const int kx = (l31 >> 1) & 7, vx = (l31 >> 2) & 3;
-    constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};  // (row-operand term, column-operand term): h l, l h, m m, h m, m h, h h
+    // the six products (split.h): the MFMA's first operand (K, V^T) takes term SPLIT_PB, its second (Q, P) term SPLIT_PA
 
     if (s0 < s1) issue(s0, 0);  // requested BEFORE this lane's query is fetched and split (round 5): the two latencies overlap
     // Q of this lane's query: d = 16 ks + 8 hh .. + 7 for the four steps, scaled, split once
-    abf16x8 Qp[4][3];
+    bf16x8 Qp[4][3];
     {
-        const float* qp = qkv + ((size_t)b * N + qc) * ld + head * ATT_DH + 8 * hh;
+        const float* qp = qkv + ((size_t)b * N + w.qc) * ld + head * ATT_DH + 8 * hh;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * ks), c = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 4);
-            au32x4 h, m, l;
-            const float x[8] = {a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]};
+            float x[8];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                unsigned hu, mu, lu;
-                att_split_pair(x[2 * e] * scale2, x[2 * e + 1] * scale2, hu, mu, lu);
-                h[e] = hu; m[e] = mu; l[e] = lu;
-            }
-            Qp[ks][0] = __builtin_bit_cast(abf16x8, h);
-            Qp[ks][1] = __builtin_bit_cast(abf16x8, m);
-            Qp[ks][2] = __builtin_bit_cast(abf16x8, l);
+            for (int e = 0; e < 4; ++e) { x[e] = a[e] * w.scale2; x[4 + e] = c[e] * w.scale2; }
+            u32x4 t[3];
+            split8(x, t);
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) Qp[ks][pl] = __builtin_bit_cast(bf16x8, t[pl]);
         }
     }
     for (int s = s0; s < s1; ++s) {
@@ -538,12 +495,12 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_bf16x3_kernel(const 
         for (int e = 0; e < 16; ++e) sT[e] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            abf16x8 kf[3];
+            bf16x8 kf[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                kf[pl] = __builtin_bit_cast(abf16x8, *reinterpret_cast<const au32x4*>(&Ks[buf][pl * PL + l31 * 32 + 4 * ((2 * ks + hh) ^ kx)]));
+                kf[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&Ks[buf][pl * PL + l31 * 32 + 4 * ((2 * ks + hh) ^ kx)]));
 #pragma unroll
-            for (int tm = 0; tm < 6; ++tm) sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[TA[tm]], Qp[ks][TB[tm]], sT, 0, 0, 0);
+            for (int tm = 0; tm < 6; ++tm) sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[SPLIT_PB[tm]], Qp[ks][SPLIT_PA[tm]], sT, 0, 0, 0);
         }
         if (key0 + 32 > N) {  // block-uniform: only the last stage has keys to mask
 #pragma unroll
@@ -573,59 +530,24 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_bf16x3_kernel(const 
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             // this lane's eight keys of the step are accumulator registers 8 ks .. 8 ks + 7 (keys 16 ks + 4 hh + 0-3 and + 8-11)
-            au32x4 ph, pm, pl3;
+            float x[8];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                unsigned hu, mu, lu;
-                att_split_pair(sT[8 * ks + 2 * e], sT[8 * ks + 2 * e + 1], hu, mu, lu);
-                ph[e] = hu; pm[e] = mu; pl3[e] = lu;
-            }
-            const abf16x8 pp[3] = {__builtin_bit_cast(abf16x8, ph), __builtin_bit_cast(abf16x8, pm), __builtin_bit_cast(abf16x8, pl3)};
+            for (int e = 0; e < 8; ++e) x[e] = sT[8 * ks + e];
+            u32x4 t[3];
+            split8(x, t);
+            const bf16x8 pp[3] = {__builtin_bit_cast(bf16x8, t[0]), __builtin_bit_cast(bf16x8, t[1]), __builtin_bit_cast(bf16x8, t[2])};
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                abf16x8 vf[3];
+                bf16x8 vf[3];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    vf[pl] = __builtin_bit_cast(abf16x8, *reinterpret_cast<const au32x4*>(&Vs[buf][pl * PL + (i * 32 + l31) * 16 + 4 * ((2 * ks + hh) ^ vx)]));
+                    vf[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&Vs[buf][pl * PL + (i * 32 + l31) * 16 + 4 * ((2 * ks + hh) ^ vx)]));
 #pragma unroll
-                for (int tm = 0; tm < 6; ++tm) acc_o[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[TA[tm]], pp[TB[tm]], acc_o[i], 0, 0, 0);
+                for (int tm = 0; tm < 6; ++tm) acc_o[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[SPLIT_PB[tm]], pp[SPLIT_PA[tm]], acc_o[i], 0, 0, 0);
             }
         }
     }
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (SPLIT) {
-        if (q < N) {
-            const size_t row = ((size_t)(b * heads + head) * nsplit + split) * N + q;
-            float* op = part_o + row * ATT_DH;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc_o[i][4 * g + e];
-                    *reinterpret_cast<f32x4*>(op + i * 32 + 8 * g + 4 * hh) = v;
-                }
-            if (hh == 0) {
-                part_ml[2 * row] = m_run;
-                part_ml[2 * row + 1] = l_tot;
-            }
-        }
-        return;
-    }
-    const float inv = 1.f / l_tot;
-    if (q < N) {
-        float* op = out + ((size_t)b * N + q) * D + head * ATT_DH;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc_o[i][4 * g + e] * inv;
-                *reinterpret_cast<f32x4*>(op + i * 32 + 8 * g + 4 * hh) = v;
-            }
-    }
+    att_write<SPLIT>(acc_o, m_run, l_run, w, b, head, heads, N, nsplit, hh, out, part_o, part_ml);
 #endif
 }
 
@@ -633,7 +555,6 @@ __global__ __launch_bounds__(64 * ATT_NW, 3) void attention_bf16x3_kernel(const 
 // NS > 0: the split count at compile time -- every (max, sum) pair and partial row is requested before the first is used (round 6: the maxima
 // were one pass of loads, the weighted sum a second one with each split's loads behind the previous split's arithmetic).  Same operations in
 // the same order as the generic form (NS == 0).
-typedef float f32x2c __attribute__((ext_vector_type(2)));
 template <int NS>
 __global__ __launch_bounds__(256) void attention_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                                 float* __restrict__ out, int B, int N, int heads, int nsplit) {
@@ -648,12 +569,12 @@ __global__ __launch_bounds__(256) void attention_combine_kernel(const float* __r
     float L = 0.f;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (NS > 0) {
-        f32x2c ml[NS > 0 ? NS : 1];
+        f32x2 ml[NS > 0 ? NS : 1];
         f32x4 v[NS > 0 ? NS : 1];
 #pragma unroll
         for (int sp = 0; sp < NS; ++sp) {
             const size_t row = ((size_t)bh * NS + sp) * N + q;
-            ml[sp] = *reinterpret_cast<const f32x2c*>(part_ml + 2 * row);
+            ml[sp] = *reinterpret_cast<const f32x2*>(part_ml + 2 * row);
             v[sp] = *reinterpret_cast<const f32x4*>(part_o + row * ATT_DH + c4 * 4);
         }
         float M = -INFINITY;

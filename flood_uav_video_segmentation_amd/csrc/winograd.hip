@@ -6,6 +6,7 @@
 // exactly 15 x 15 tiles of 6x6; its fp32 error is ~1.5x that of F(4,3) (measured 1.5e-5 vs 1.0e-5 relative on a
 // 512-channel conv; direct: 3e-7).  All kernels are HBM-bound elementwise-style passes over channel groups (NHWC).
 #include "kernels.h"
+#include "split.h"
 #include "winograd.h"
 
 namespace fs {
@@ -56,7 +57,6 @@ int launch_winograd_filter(const float* w_oihw, float* U, int O, int I, int mt, 
 // VGPRs, and a 90x90x256 map is only 900 waves -- under one per SIMD, every load latency exposed: 15 us for 46 MB.  Split
 // this way the same map is 3600 waves of 8 loads each.)  The arithmetic (B^T d B, A^T m A; which products are formed and in
 // which order) is unchanged.
-typedef unsigned wo_u32x4 __attribute__((ext_vector_type(4)));
 
 template <int MT>
 __global__ __launch_bounds__((MT + 2) * 32) void winograd_input_kernel(const float* __restrict__ in, int ld_in, float* __restrict__ V, int B, int H,
@@ -185,7 +185,7 @@ __global__ __launch_bounds__((MT + 2) * 32) void winograd_output_kernel(const fl
                 f32x4 v = y[c] * sc + sh;
                 if (relu) v = __builtin_elementwise_max(v, f32x4(0.f));
                 const unsigned vo = (oy < H && ox < W) ? rowoff + (unsigned)(ox * ld_out) * 4u : 0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wo_u32x4, v), o_rsrc, vo, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, vo, 0, 0);
             }
         }
         __syncthreads();

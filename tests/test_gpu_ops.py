@@ -161,6 +161,74 @@ def test_split_bf16x3_is_exact():
     assert lib.fs_split_bf16x3(ptr(wd), 12, ptr(planes), stream_ptr()) != 0  # n % 8 != 0 is refused
 
 
+def _bf16_rne(x):
+    """float32 array -> (bf16 bit patterns, the bf16 values as float32): round to nearest even on the uint32 pattern."""
+    import numpy as np
+
+    bits = x.view(np.uint32).astype(np.uint64)
+    hi = ((bits + 0x7FFF + ((bits >> 16) & 1)) >> 16).astype(np.uint32)
+    return hi.astype(np.uint16), (hi << 16).view(np.float32)
+
+
+def _split_planes_host(x):
+    """The three planes of csrc/split.h restated in numpy: round, subtract (exact in fp32), round, subtract, round."""
+    h, hf = _bf16_rne(x)
+    r = x - hf
+    m, mf = _bf16_rne(r)
+    l, _ = _bf16_rne(r - mf)
+    return h, m, l, r
+
+
+def _split_plane_inputs():
+    """+-0, subnormals, ties at the first and at the second level (to even both ways), every exponent that stays finite, and the
+    largest magnitudes the split takes (up to the last pattern that still rounds to the largest bf16, 3.3961e38 > 3.39e38)."""
+    import numpy as np
+
+    rng = np.random.default_rng(12)
+    special = np.array([0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x00000100, 0x00008000, 0x00018000, 0x007FFFFF, 0x807FFFFF,
+                        0x00800000, 0x3F800000, 0x3F808000, 0x3F818000, 0x3F804080, 0x3F8040C0, 0x3F80C040,
+                        0x7F7F0000, 0xFF7F0000, 0x7F7EFFFF, 0x7F7F7FFF, 0xFF7F7FFF], dtype=np.uint32)
+    big = np.array([3.39e38, -3.39e38, 3.38e38, -3.3895e38], dtype=np.float32).view(np.uint32)
+    # mantissa = a7 | b8 | c8: b8 c8 = 0x80 0x00 is a tie of the first rounding, a residue whose ninth bit is its last a tie of the second
+    a7 = np.array([0x00, 0x01, 0x2A, 0x7E, 0x7F], dtype=np.uint32)
+    b8 = np.arange(256, dtype=np.uint32)
+    c8 = np.array([0x00, 0x01, 0x20, 0x40, 0x60, 0x80, 0xC0, 0xFF], dtype=np.uint32)
+    ex = np.array([0, 1, 2, 17, 100, 126, 127, 128, 200, 253], dtype=np.uint32)  # 0: subnormals; 254 is left to `special` / `big`
+    grid = (ex[:, None, None, None] << 23) | (a7[None, :, None, None] << 16) | (b8[None, None, :, None] << 8) | c8[None, None, None, :]
+    grid = grid.reshape(-1)
+    grid = np.concatenate([grid, grid | np.uint32(0x80000000)])
+    rand = rng.integers(0, 0x7F7F0000, 1 << 15, dtype=np.uint32) | (rng.integers(0, 2, 1 << 15, dtype=np.uint32) << 31)
+    bits = np.concatenate([special, big, grid, rand])
+    bits = np.concatenate([bits, np.zeros(-len(bits) % 8, dtype=np.uint32)])
+    return bits.view(np.float32)
+
+
+def test_split_bf16x3_planes_bit_for_bit():
+    """fs_split_bf16x3 pins the PLANES, not only their sum: each of h, m, l is bit-equal to a host restatement of csrc/split.h
+    (numpy round-to-nearest-even on the uint32 pattern, three levels).  A changed rounding or residue step in the one definition
+    shows here even where h + m + l still adds up.  The generator is checked against itself first: it holds ties of both levels,
+    and its planes sum to x exactly wherever the split is exact (2^-110 <= |x|, and zero)."""
+    import numpy as np
+
+    x = _split_plane_inputs()
+    h, m, l, r = _split_planes_host(x)
+    xb, rb = x.view(np.uint32), r.view(np.uint32)
+    assert ((xb & 0xFFFF) == 0x8000).sum() >= 100 and (((rb & 0xFFFF) == 0x8000) & ((xb & 0xFFFF) != 0x8000)).sum() >= 100  # ties, levels 0 and 1
+    assert ((xb & 0x7F800000) == 0).sum() >= 1000 and np.abs(x).max() > 3.39e38 and np.isfinite(x).all()
+    f64 = lambda p: (p.astype(np.uint32) << 16).view(np.float32).astype(np.float64)  # noqa: E731
+    exact = (np.abs(x) >= 2.0 ** -110) | (x == 0)
+    assert np.array_equal((f64(h) + f64(m) + f64(l))[exact], x.astype(np.float64)[exact])
+    lib = _lib.load()
+    wd = torch.from_numpy(x.copy()).to(DEV)
+    planes = torch.empty(3 * wd.numel(), dtype=torch.bfloat16, device=DEV)
+    check(lib.fs_split_bf16x3(ptr(wd), wd.numel(), ptr(planes), stream_ptr()))
+    got = planes.view(torch.int16).cpu().numpy().view(np.uint16).reshape(3, -1)
+    for name, g, e in (("h", got[0], h), ("m", got[1], m), ("l", got[2], l)):
+        bad = np.nonzero(g != e)[0]
+        print(f"split plane {name}: {bad.size} of {e.size} differ")
+        assert bad.size == 0, (name, [(hex(int(xb[i])), hex(int(g[i])), hex(int(e[i]))) for i in bad[:8]])
+
+
 def test_conv_and_winograd_on_seeded_random_shapes():
     """30 seeded random geometries (batch, ragged H x W, channel counts that leave partial n-tiles, kernel 1 / 3, stride, dilation,
     residual, activation) through fs_conv2d_nhwc with the cost model's tile, and -- where eligible -- through the Winograd route,
