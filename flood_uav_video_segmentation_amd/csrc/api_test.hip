@@ -21,37 +21,14 @@ static int conv2d_entry(const float* in, int ld_in, const float* wgt_ohwi, const
                         int KW, int stride, int pad, int dil, int relu, int tile, fs_stream stream) {
     if (!in || (!wgt_ohwi && !wgt3) || !out || B < 1 || H < 1 || W < 1 || stride < 1 || dil < 1 || pad < 0)
         return fs::fail("fs_conv2d_nhwc: bad arguments");
-    fs::ConvParams p{};
-    p.in = in;
-    p.ld_in = ld_in;
-    p.wgt = wgt_ohwi;
-    p.wgt3 = wgt3;
-    p.plane_bytes = (unsigned)((size_t)Cout * KH * KW * Cin * 2);
-    p.scale = scale;
-    p.shift = shift;
-    p.res = res;
-    p.ld_res = ld_res;
-    p.out = out;
-    p.ld_out = ld_out;
-    p.B = B;
-    p.H = H;
-    p.W = W;
-    p.Cin = Cin;
-    p.Cout = Cout;
-    p.KH = KH;
-    p.KW = KW;
-    p.stride = stride;
-    p.pad = pad;
-    p.dil = dil;
-    p.relu = relu;
-    p.Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-    p.Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+    const int tid = tile & ~FS_CONV_CHUNK_MAJOR;
+    fs::ConvParams p = fs::conv2d_params(in, ld_in, wgt_ohwi, scale, shift, res, ld_res, out, ld_out, B, H, W, Cin, Cout, KH, KW, stride, pad, dil, relu,
+                                         (tile & FS_CONV_CHUNK_MAJOR) ? 1 : 0);
+    fs::attach_planes(p, wgt3, (size_t)Cout * KH * KW * Cin);
     if (p.Ho < 1 || p.Wo < 1) return fs::fail("fs_conv2d_nhwc: empty output");
     // tile = workgroup tile id 0..4 or 6 (6: split route only), optionally | FS_CONV_CHUNK_MAJOR; anything else is refused (no hidden experiment bits)
-    const int tid = tile & ~FS_CONV_CHUNK_MAJOR;
     if (tid < 0 || tid > 6 || tid == 5) return fs::fail("fs_conv2d_nhwc: tile must be 0..4 or 6, optionally | FS_CONV_CHUNK_MAJOR (got 0x%x)", tile);
-    p.korder = (tile & FS_CONV_CHUNK_MAJOR) ? 1 : 0;
-    return fs::launch_conv_igemm(p, S(stream), tile & ~FS_CONV_CHUNK_MAJOR);
+    return fs::launch_conv_igemm(p, S(stream), tid);
 }
 static int fs_conv2d_nhwc(const float* in, int ld_in, const float* wgt_ohwi, const float* scale, const float* shift,
                           const float* res, int ld_res, float* out, int ld_out, int B, int H, int W, int Cin, int Cout, int KH,
@@ -80,11 +57,11 @@ static int fs_attention(const float* qkv, float* out, int B, int N, int heads, f
     planes += (64 - ((uintptr_t)planes / 4) % 64) % 64;  // 256-B aligned
     return fs::launch_attention_split(qkv, out, B, N, heads, scale, scratch, planes, S(stream));
 }
+static size_t bank_floats(int mt, int Cin, int Cout) { return (size_t)(mt + 2) * (mt + 2) * Cout * Cin; }  // U [(mt+2)^2][Cout][Cin]
 static size_t fs_winograd_workspace_floats(int B, int H, int W, int Cin, int Cout, int dil, int tile_m) {
     if (B < 1 || H < 1 || W < 1 || dil < 1 || !(tile_m == 0 || tile_m == 3 || tile_m == 4 || tile_m == 6)) return 0;
-    const int mt = tile_m ? tile_m : fs::winograd_pick_m(B, H, W, dil);
-    const size_t G = (size_t)(mt + 2) * (mt + 2), T = (size_t)fs::winograd_tiles(B, H, W, dil, mt);
-    return G * T * ((size_t)Cin + (size_t)Cout) + G * (size_t)Cout * Cin;
+    const int mt = fs::wino_m(tile_m, H, W, dil);
+    return fs::wino_vm_floats(mt, (size_t)fs::winograd_tiles(B, H, W, dil, mt), Cin, Cout, 1) + bank_floats(mt, Cin, Cout);
 }
 static int fs_conv3x3_winograd_nhwc(const float* in, int ld_in, const float* wgt_oihw, const float* scale, const float* shift,
                                     float* out, int ld_out, int B, int H, int W, int Cin, int Cout, int dil, int relu, int tile_m,
@@ -92,34 +69,13 @@ static int fs_conv3x3_winograd_nhwc(const float* in, int ld_in, const float* wgt
     if (!in || !wgt_oihw || !out || !workspace || B < 1 || H < 1 || W < 1 || dil < 1 || Cin % 32 != 0 || Cout % 4 != 0 ||
         !(tile_m == 0 || tile_m == 3 || tile_m == 4 || tile_m == 6))
         return fs::fail("fs_conv3x3_winograd_nhwc: bad arguments (Cin %% 32, Cout %% 4, tile_m in {0, 3, 4, 6} required)");
-    const int mt = tile_m ? tile_m : fs::winograd_pick_m(B, H, W, dil);
-    const size_t G = (size_t)(mt + 2) * (mt + 2), T = (size_t)fs::winograd_tiles(B, H, W, dil, mt);
+    // workspace: the transformed bank U, then V and M back to back; fp32-MFMA GEMM (no planes)
+    const int mt = fs::wino_m(tile_m, H, W, dil);
     float* U = workspace;
-    float* V = U + G * (size_t)Cout * Cin;
-    float* Mb = V + G * T * Cin;
+    float* V = U + bank_floats(mt, Cin, Cout);
+    float* M = V + fs::wino_v_floats(mt, (size_t)fs::winograd_tiles(B, H, W, dil, mt), Cin, 1);
     if (int rc = fs::launch_winograd_filter(wgt_oihw, U, Cout, Cin, mt, S(stream))) return rc;
-    if (int rc = fs::launch_winograd_input(in, ld_in, V, B, H, W, Cin, dil, mt, S(stream))) return rc;
-    fs::ConvParams p{};
-    p.in = V;
-    p.ld_in = Cin;
-    p.wgt = U;
-    p.out = Mb;
-    p.ld_out = Cout;
-    p.B = 1;
-    p.H = (int)T;
-    p.W = 1;
-    p.Cin = Cin;
-    p.Ho = (int)T;
-    p.Wo = 1;
-    p.Cout = Cout;
-    p.KH = p.KW = 1;
-    p.stride = 1;
-    p.dil = 1;
-    p.groups = (int)G;
-    p.g_wgt = (long long)Cout * Cin;
-    fs::winograd_gemm_params(p, mt, (int)T, Cin, Cout);
-    if (int rc = fs::launch_conv_igemm(p, S(stream))) return rc;
-    return fs::launch_winograd_output(Mb, scale, shift, out, ld_out, B, H, W, Cout, relu, dil, mt, S(stream));
+    return fs::conv_winograd(nullptr, "", in, ld_in, U, nullptr, 0, V, M, scale, shift, out, ld_out, B, H, W, Cin, Cout, dil, relu, mt, S(stream));
 }
 static size_t fs_winograd_fused_workspace_floats(int Cin, int Cout) { return fs::wino_fused_bank_floats(Cin, Cout); }
 static int fs_conv3x3_winograd_fused_nhwc(const float* in, int ld_in, const float* wgt_oihw, const float* scale, const float* shift,
@@ -153,29 +109,12 @@ static int fs_stem_conv_nchw_split(const float* in_nchw, const float* wgt_hwio, 
 static int stem_entry(const float* in_nchw, const float* wgt_hwio, const float* scale, const float* shift, float* out_nhwc, int B, int H, int W, int Cout,
                       int KH, int KW, int stride, int pad, int split, fs_stream stream) {
     if (!in_nchw || !wgt_hwio || !scale || !shift || !out_nhwc || B < 1) return fs::fail("fs_stem_conv_nchw: bad arguments");
-    fs::StemParams p{};
-    p.src = fs::frames_plain(in_nchw, nullptr, B);
-    p.wgt = wgt_hwio;
-    p.scale = scale;
-    p.shift = shift;
-    p.out = out_nhwc;
-    p.ld_out = Cout;
-    p.B = B;
-    p.H = H;
-    p.W = W;
-    p.Ho = (H + 2 * pad - KH) / stride + 1;
-    p.Wo = (W + 2 * pad - KW) / stride + 1;
-    p.Cout = Cout;
-    p.KH = KH;
-    p.KW = KW;
-    p.stride = stride;
-    p.pad = pad;
-    p.split = split;
+    const fs::StemParams p = fs::stem_params(fs::frames_plain(in_nchw, nullptr, B), wgt_hwio, scale, shift, out_nhwc, B, H, W, Cout, KH, KW, stride, pad, split);
     return fs::launch_stem_conv(p, S(stream));
 }
 static int fs_maxpool3x3s2_nhwc(const float* in, float* out, int B, int H, int W, int C, fs_stream stream) {
     if (!in || !out || B < 1 || H < 1 || W < 1) return fs::fail("fs_maxpool3x3s2_nhwc: bad arguments");
-    return fs::launch_maxpool3x3s2(in, C, out, C, B, H, W, C, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1, S(stream));
+    return fs::launch_maxpool3x3s2(in, C, out, C, B, H, W, C, fs::conv_out_size(H, 3, 2, 1, 1), fs::conv_out_size(W, 3, 2, 1, 1), S(stream));
 }
 static int fs_adaptive_avgpool_nhwc(const float* in, int ld_in, float* out, int B, int H, int W, int C, int bin, fs_stream stream) {
     if (!in || !out || B < 1 || H < 1 || W < 1 || bin < 1) return fs::fail("fs_adaptive_avgpool_nhwc: bad arguments");
@@ -216,18 +155,15 @@ static int fs_linear(const float* in, const float* w, const void* w_planes, cons
         split = nsplit;
     }
     if (ln && !split) return fs::fail("fs_linear: the LayerNorm merge runs on split-K launches only");
-    const unsigned plane_bytes = (unsigned)((size_t)N * K * 2);
     if (split) {
         fs::ConvParams p = fs::linear_splitk_params(in, w, part, rows, K, N, split);
-        p.wgt3 = w_planes;
-        p.plane_bytes = plane_bytes;
+        fs::attach_planes(p, w_planes, (size_t)N * K);
         if (int rc = fs::launch_conv_igemm(p, S(stream))) return rc;
         if (ln) return fs::launch_splitk_combine_ln(part, split, bias, res, out, gamma, beta, ln_out, rows, N, S(stream));
         return fs::launch_splitk_combine(part, split, bias, res, out, rows, N, S(stream));
     }
     fs::ConvParams p = fs::linear_params(in, w, bias, res, out, rows, K, N, act, res != nullptr);
-    p.wgt3 = w_planes;
-    p.plane_bytes = plane_bytes;
+    fs::attach_planes(p, w_planes, (size_t)N * K);
     return fs::launch_conv_igemm(p, S(stream));
 }
 static size_t fs_qkv_attention_workspace_floats(int B, int tokens, int D) {
@@ -243,16 +179,13 @@ static int fs_qkv_attention(const float* in, const float* w, const void* w_plane
     const int heads = D / 64;
     float* planes = workspace;
     float* scratch = fs::attention_scratch_floats(B, tokens, heads) ? workspace + fs::attention_split_floats(B, tokens, heads) : nullptr;
-    const unsigned plane_bytes = (unsigned)((size_t)3 * D * D * 2);
     if (fused) {
         fs::ConvParams p = fs::linear_qkv_params(in, w, bias, qkv_out, B, tokens, D, planes);
-        p.wgt3 = w_planes;
-        p.plane_bytes = plane_bytes;
+        fs::attach_planes(p, w_planes, (size_t)3 * D * D);
         if (int rc = fs::launch_conv_igemm(p, S(stream), 6)) return rc;
     } else {
         fs::ConvParams p = fs::linear_params(in, w, bias, nullptr, qkv_out, B * tokens, D, 3 * D, 0, false);
-        p.wgt3 = w_planes;
-        p.plane_bytes = plane_bytes;
+        fs::attach_planes(p, w_planes, (size_t)3 * D * D);
         if (int rc = fs::launch_conv_igemm(p, S(stream))) return rc;
     }
     return fs::launch_attention_split(qkv_out, att_out, B, tokens, heads, 0.125f, scratch, planes, S(stream), fused != 0);
@@ -293,8 +226,7 @@ static int fs_dual_conv(const float* a, int ld_a, const float* b, int ld_b, cons
         return fs::fail("fs_dual_conv: bad arguments");
     if (tile < 0 || tile > 2) return fs::fail("fs_dual_conv: tile must be 0, 1 or 2 (got %d): the concatenated-K kernels have the two 128-row tiles", tile);
     fs::ConvParams p = fs::dual_conv_params(a, ld_a, b, ld_b, wgt, shift, out, ld_out, B, Ho, Wo, Cin, Cin2, H2, W2, stride2, Cout, relu);
-    p.wgt3 = wgt_planes;
-    p.plane_bytes = (unsigned)((size_t)Cout * ((size_t)Cin + Cin2) * 2);
+    fs::attach_planes(p, wgt_planes, (size_t)Cout * ((size_t)Cin + Cin2));
     return fs::launch_conv_igemm(p, S(stream), tile);
 }
 static int fs_pyramid_pool(const float* in, int ld_in, float* out, int B, int H, int W, int C, fs_stream stream) {
@@ -349,8 +281,7 @@ static int fs_ppm_head(const float* T, int ld, const float* reduced, int Cr, con
         if (bins[i] < 1 || bins[i] > 6) return fs::fail("fs_ppm_head: a level's slot holds 36 cells (bin %d)", bins[i]);
     float* zbuf = workspace;
     fs::ConvParams p = fs::ppm_z_params(reduced, zw, zbuf, B, Cr, 9 * C);
-    p.wgt3 = zw_planes;
-    p.plane_bytes = (unsigned)((size_t)4 * 9 * C * Cr * 2);
+    fs::attach_planes(p, zw_planes, (size_t)4 * 9 * C * Cr);
     if (int rc = fs::launch_conv_igemm(p, S(stream))) return rc;
     const float* Z[4];
     for (int i = 0; i < 4; ++i) Z[i] = zbuf + (size_t)i * p.g_out;

@@ -61,6 +61,30 @@ const char* conv_igemm_tile_name(const ConvParams& p, int tile = 0);
 // planes[t][i] (t = 0, 1, 2; bf16) = term t of w[i] as split.h defines it (split3); ConvParams::wgt3
 int launch_split_bf16x3(const float* w, long long n, void* planes, hipStream_t s);
 
+// Host-side builders: every ConvParams of the library comes from conv2d_params, directly or through gemm_params and the layer-level
+// builders on top of them (winograd_gemm_params below, conv_params / dual_conv_params / ppm_z_params / linear_*_params in net.h).
+// output size of a conv or pooling window along one axis (nn.Conv2d / nn.MaxPool2d, floor)
+static inline int conv_out_size(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1; }
+static inline ConvParams conv2d_params(const float* in, int ld_in, const float* wgt, const float* scale, const float* shift, const float* res, int ld_res,
+                                       float* out, int ld_out, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                                       int relu, int korder) {
+    ConvParams p{};
+    p.in = in; p.ld_in = ld_in; p.wgt = wgt; p.scale = scale; p.shift = shift; p.res = res; p.ld_res = ld_res; p.out = out; p.ld_out = ld_out;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+    p.Ho = conv_out_size(H, KH, stride, pad, dil);
+    p.Wo = conv_out_size(W, KW, stride, pad, dil);
+    p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil; p.relu = relu; p.korder = korder;
+    return p;
+}
+// out[rows][N] (ld_out) = in[rows][K] (ld_in) x w[N][K]^T: a 1x1 conv over a rows x 1 map; no scale / shift / residual / activation
+static inline ConvParams gemm_params(const float* in, int ld_in, const float* w, float* out, int ld_out, int rows, int K, int N) {
+    return conv2d_params(in, ld_in, w, nullptr, nullptr, nullptr, 0, out, ld_out, 1, rows, 1, K, N, 1, 1, 1, 0, 1, 0, 0);
+}
+// points a launch at the three bf16 planes of its filter bank of `elems` floats (the op-level hooks; the networks go through split_use)
+static inline void attach_planes(ConvParams& p, const void* planes, size_t elems) {
+    p.wgt3 = planes;
+    p.plane_bytes = (unsigned)(elems * 2);
+}
 
 // ---------------------------------------------------------------------------------
 // Stem convolution with Cin = 3 read straight from the caller's NCHW frame
@@ -95,6 +119,15 @@ struct StemParams {
     int split;  // != 0: the split-operand route (three bf16 terms per fp32 value, bf16 matrix cores, fp32 accumulation), round 5
 };
 int launch_stem_conv(const StemParams& p, hipStream_t s);
+static inline StemParams stem_params(const FrameSrc& src, const float* wgt, const float* scale, const float* shift, float* out, int B, int H, int W,
+                                     int Cout, int KH, int KW, int stride, int pad, int split) {
+    StemParams p{};
+    p.src = src; p.wgt = wgt; p.scale = scale; p.shift = shift; p.out = out; p.ld_out = Cout;
+    p.B = B; p.H = H; p.W = W; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.split = split;
+    p.Ho = conv_out_size(H, KH, stride, pad, 1);
+    p.Wo = conv_out_size(W, KW, stride, pad, 1);
+    return p;
+}
 
 // MaxPool2d(kernel 3, stride 2, padding 1) NHWC (model/resnet.py:117).
 int launch_maxpool3x3s2(const float* in, int ld_in, float* out, int ld_out, int B, int H, int W, int C,
@@ -346,13 +379,23 @@ int launch_winograd_output(const float* M /*[(m+2)^2][T][N]*/, const float* scal
 // element (position xi, tile t, channel c) of V (C = Cin) / M (C = Cout) lives at xi * s_pos + t * s_tile + c
 struct WinoLayout { bool tile_major; long long s_pos, s_tile; };
 WinoLayout winograd_layout(int mt, long long T, int C);
-// the grouped GEMM between the transforms: group g = position g, rows = tiles (fills the V / M addressing of a ConvParams)
-static inline void winograd_gemm_params(ConvParams& p, int mt, int T, int Cin, int Cout) {
+// the grouped GEMM between the transforms: group g = position g multiplies V's T tile rows with U + g * Cout * Cin into M; V / M are
+// tile-major when that fits a buffer descriptor (winograd.hip)
+static inline ConvParams winograd_gemm_params(const float* V, const float* U, float* M, int mt, int T, int Cin, int Cout) {
+    ConvParams p = gemm_params(V, Cin, U, M, Cout, T, Cin, Cout);
     const WinoLayout a = winograd_layout(mt, T, Cin), o = winograd_layout(mt, T, Cout);
     p.ld_in = (int)a.s_tile;
     p.g_in = a.s_pos;
     p.ld_out = (int)o.s_tile;
     p.g_out = o.s_pos;
+    p.groups = (mt + 2) * (mt + 2);
+    p.g_wgt = (long long)Cout * Cin;
+    return p;
+}
+// floats of V [(m+2)^2][T][Cin], rounded up to a multiple of `align`, and of V followed by M [(m+2)^2][T][Cout]
+static inline size_t wino_v_floats(int mt, size_t T, int Cin, size_t align) { return ((size_t)(mt + 2) * (mt + 2) * T * Cin + align - 1) / align * align; }
+static inline size_t wino_vm_floats(int mt, size_t T, int Cin, int Cout, size_t align) {
+    return wino_v_floats(mt, T, Cin, align) + (size_t)(mt + 2) * (mt + 2) * T * Cout;
 }
 static inline int winograd_tiles(int B, int H, int W, int dil, int mt) {
     return B * dil * dil * ((cdiv(H, dil) + mt - 1) / mt) * ((cdiv(W, dil) + mt - 1) / mt);
@@ -368,6 +411,8 @@ static inline int winograd_pick_m(int /*B*/, int H, int W, int dil) {
     const int m = winograd_gemm_rows(1, H, W, dil, 6) < winograd_gemm_rows(1, H, W, dil, 4) ? 6 : 4;
     return winograd_gemm_rows(1, H, W, dil, 3) < winograd_gemm_rows(1, H, W, dil, m) ? 3 : m;
 }
+// the tile size a conv runs with: a forced one (3, 4 or 6) or the map's own
+static inline int wino_m(int force, int H, int W, int dil) { return force ? force : winograd_pick_m(1, H, W, dil); }
 
 // ---------------------------------------------------------------------------------
 // Fused Winograd F(4x4,3x3) for 3x3 stride-1 pad-1 convs with few input channels (wino_fused.hip): input transform, the 36

@@ -44,7 +44,7 @@ struct ConvBN {
     int korder = 0;  // 1: filters packed chunk-major (3x3 convs)
     std::shared_ptr<WinoBank> wino;  // non-null: 3x3 stride-1 conv with pad == dil and Cin >= 256 (Winograd-eligible)
     float* wf = nullptr;  // non-null: packed F(4,3) bank [36][Cin/16][Cout][16] of the one-kernel Winograd (wino_fused.hip): 3x3 s1 p1, Cin <= 128
-    int out_size(int in) const { return (in + 2 * pad - dil * (KH - 1) - 1) / stride + 1; }
+    int out_size(int in) const { return conv_out_size(in, KH, stride, pad, dil); }
 };
 
 struct Bottleneck {
@@ -208,10 +208,20 @@ ConvParams ppm_z_params(const float* reduced, const float* zw, float* zbuf, int 
 // ([B][bin^2][C] each); one pass + ppm_pool_combine when H and W are multiples of 6 and the bins are 1, 2, 3, 6, four pooling launches
 // otherwise.  h: the handle whose profile the launches are recorded in, or nullptr.
 int pyramid_pool(fs_net* h, const float* feat, int ld_feat, float* pooled, int B, int H, int W, int C, const int bins[4], hipStream_t s);
+// A 3x3 stride-1 conv with pad == dil (+ scale / shift, ReLU) as Winograd F(mt x mt, 3x3): input transform of `in` into V -> the
+// (mt+2)^2 position GEMMs with the bank U [(mt+2)^2][Cout][Cin] into M -> output transform into `out` (run_conv, and the op-level hook).
+// U3 / plane_bytes: the bank's bf16 planes (ConvParams::wgt3) or nullptr / 0 = the fp32-MFMA kernel.  h: the handle whose profile the
+// three launches are recorded in as name.wino_in / .wino_gemm / .wino_out, or nullptr.
+int conv_winograd(fs_net* h, const std::string& name, const float* in, int ld_in, const float* U, const void* U3, unsigned plane_bytes, float* V,
+                  float* M, const float* scale, const float* shift, float* out, int ld_out, int B, int H, int W, int Cin, int Cout, int dil,
+                  int relu, int mt, hipStream_t s);
 int vit_reserve(fs_handle h, int B, int H, int W, hipStream_t s);
 int fetch(fs_net* h, const std::string& name, const RawTensor** out);
+// profile record around the launches between the two calls; no-ops unless h is a handle with profiling on
 int prof_begin(fs_net* h, const std::string& name, const char* kernel, double flops, double bytes, hipStream_t s);
 int prof_end(fs_net* h, hipStream_t s);
+// one implicit-GEMM launch with its profile record (kernel column = the tile the launch gets)
+int run_igemm(fs_net* h, const std::string& name, const ConvParams& p, double flops, double bytes, hipStream_t s, int tile = 0);
 int vit_finalize(fs_handle h, hipStream_t s);
 int vit_feature_shape(fs_handle h, int H, int W, int* C, int* fh, int* fw);
 int vit_encoder(fs_handle h, const FrameSrc& src, int B, int H, int W, float* out_tokens, hipStream_t s);

@@ -115,6 +115,13 @@ int wino_bank(fs_net* h, const ConvBN& c, int mt, hipStream_t s, const float** U
     return 0;
 }
 
+// the values of a loaded tensor, on the host
+int fetch_host(fs_net* h, const std::string& name, std::vector<float>& v) {
+    const RawTensor* t;
+    FS_TRY(fetch(h, name, &t));
+    return to_host(*t, v);
+}
+
 // conv weight + BatchNorm prefix (or bias name, or neither)
 int make_conv(fs_net* h, ConvBN& c, const std::string& wname, const std::string& bn, const std::string& bias, int stride,
               int pad, int dil, int relu, bool hwio, hipStream_t s) {
@@ -147,18 +154,14 @@ int make_conv(fs_net* h, ConvBN& c, const std::string& wname, const std::string&
         FS_TRY(launch_wino4_filter_packed(c.w, c.wf, c.Cout, c.Cin, s, 1));
     }
     if (!bn.empty()) {
-        const RawTensor *g, *b, *m, *v;
-        FS_TRY(fetch(h, bn + ".weight", &g));
-        FS_TRY(fetch(h, bn + ".bias", &b));
-        FS_TRY(fetch(h, bn + ".running_mean", &m));
-        FS_TRY(fetch(h, bn + ".running_var", &v));
-        FS_REQUIRE(g->numel() == c.Cout && b->numel() == c.Cout && m->numel() == c.Cout && v->numel() == c.Cout,
-                   "BatchNorm '%s' does not match %d output channels", bn.c_str(), c.Cout);
-        std::vector<float> hg, hb, hm, hv, sc((size_t)c.Cout), sh((size_t)c.Cout);
-        FS_TRY(to_host(*g, hg));
-        FS_TRY(to_host(*b, hb));
-        FS_TRY(to_host(*m, hm));
-        FS_TRY(to_host(*v, hv));
+        const size_t n = (size_t)c.Cout;
+        std::vector<float> hg, hb, hm, hv, sc(n), sh(n);
+        FS_TRY(fetch_host(h, bn + ".weight", hg));
+        FS_TRY(fetch_host(h, bn + ".bias", hb));
+        FS_TRY(fetch_host(h, bn + ".running_mean", hm));
+        FS_TRY(fetch_host(h, bn + ".running_var", hv));
+        FS_REQUIRE(hg.size() == n && hb.size() == n && hm.size() == n && hv.size() == n, "BatchNorm '%s' does not match %d output channels",
+                   bn.c_str(), c.Cout);
         for (int i = 0; i < c.Cout; ++i) {
             // ATen eval batch_norm: alpha = invstd * weight; beta = bias - mean * alpha  (eps = 1e-5)
             const float invstd = 1.0f / std::sqrt(hv[i] + 1e-5f);
@@ -182,7 +185,7 @@ int make_conv(fs_net* h, ConvBN& c, const std::string& wname, const std::string&
 }  // namespace
 
 int prof_begin(fs_net* h, const std::string& name, const char* kernel, double flops, double bytes, hipStream_t s) {
-    if (!h->profiling) return 0;
+    if (!h || !h->profiling) return 0;
     ProfRec r;
     r.name = name;
     r.kernel = kernel;
@@ -195,59 +198,51 @@ int prof_begin(fs_net* h, const std::string& name, const char* kernel, double fl
     return 0;
 }
 int prof_end(fs_net* h, hipStream_t s) {
-    if (!h->profiling) return 0;
+    if (!h || !h->profiling) return 0;
     FS_HIP(hipEventRecord(h->prof.back().e1, s));
     return 0;
 }
 
+int run_igemm(fs_net* h, const std::string& name, const ConvParams& p, double flops, double bytes, hipStream_t s, int tile) {
+    FS_TRY(prof_begin(h, name, conv_igemm_tile_name(p, tile), flops, bytes, s));
+    FS_TRY(launch_conv_igemm(p, s, tile));
+    return prof_end(h, s);
+}
+
+int conv_winograd(fs_net* h, const std::string& name, const float* in, int ld_in, const float* U, const void* U3, unsigned plane_bytes, float* V,
+                  float* M, const float* scale, const float* shift, float* out, int ld_out, int B, int H, int W, int Cin, int Cout, int dil,
+                  int relu, int mt, hipStream_t s) {
+    const int T = winograd_tiles(B, H, W, dil, mt);
+    ConvParams p = winograd_gemm_params(V, U, M, mt, T, Cin, Cout);
+    p.wgt3 = U3;
+    p.plane_bytes = plane_bytes;
+    const double G = p.groups, v_elems = G * T * Cin, m_elems = G * T * Cout, px = (double)B * H * W;
+    FS_TRY(prof_begin(h, name + ".wino_in", "winograd_input", 0, 4.0 * (px * Cin + v_elems), s));
+    FS_TRY(launch_winograd_input(in, ld_in, V, B, H, W, Cin, dil, mt, s));
+    FS_TRY(prof_end(h, s));
+    FS_TRY(run_igemm(h, name + ".wino_gemm", p, 2.0 * G * (double)T * Cin * Cout, 4.0 * (v_elems + G * Cout * Cin + m_elems), s));
+    FS_TRY(prof_begin(h, name + ".wino_out", "winograd_output", 0, 4.0 * (m_elems + px * Cout), s));
+    FS_TRY(launch_winograd_output(M, scale, shift, out, ld_out, B, H, W, Cout, relu, dil, mt, s));
+    return prof_end(h, s);
+}
+
 namespace {
 
-// Winograd workspace: V followed by M (fp32)
-size_t wino_v_floats(size_t G, size_t T, int Cin) { return (G * T * Cin + 7) / 8 * 8; }
-size_t wino_ws_floats(size_t G, size_t T, int Cin, int Cout) { return wino_v_floats(G, T, Cin) + G * T * Cout; }
-
-// 3x3 s1 p1 conv as Winograd F(4x4,3x3): input transform -> 36 grouped GEMMs -> output transform (+BN, ReLU)
+// 3x3 s1 conv with pad == dil on the three-launch Winograd route: the filter bank of the tile size this map takes (built on first
+// use), V followed by M (V rounded up to 8 floats) in the handle's Winograd workspace
 int run_conv_winograd(fs_net* h, const ConvBN& c, const float* in, int ld_in, int B, int H, int W, float* out, int ld_out,
                       hipStream_t s) {
-    const int mt = h->wino_force_m ? h->wino_force_m : winograd_pick_m(B, H, W, c.dil);
-    const int G = (mt + 2) * (mt + 2);
-    const int T = winograd_tiles(B, H, W, c.dil, mt);
+    const int mt = wino_m(h->wino_force_m, H, W, c.dil);
+    const size_t T = (size_t)winograd_tiles(B, H, W, c.dil, mt);
     const float* U = nullptr;
     FS_TRY(wino_bank(h, c, mt, s, &U));
-    const size_t v_elems = (size_t)G * T * c.Cin, m_elems = (size_t)G * T * c.Cout;
-    FS_TRY(ws_grow(h, &h->wino_ws, &h->wino_ws_elems, wino_ws_floats(G, T, c.Cin, c.Cout), false));
+    FS_TRY(ws_grow(h, &h->wino_ws, &h->wino_ws_elems, wino_vm_floats(mt, T, c.Cin, c.Cout, 8), false));
     float* V = h->wino_ws;
-    float* Mb = h->wino_ws + wino_v_floats(G, T, c.Cin);
-    ConvParams p{};
-    p.in = V;
-    p.ld_in = c.Cin;
-    p.wgt = U;
-    p.out = Mb;
-    p.ld_out = c.Cout;
-    p.B = 1;
-    p.H = T;
-    p.W = 1;
-    p.Cin = c.Cin;
-    p.Ho = T;
-    p.Wo = 1;
-    p.Cout = c.Cout;
-    p.KH = p.KW = 1;
-    p.stride = 1;
-    p.dil = 1;
-    p.groups = G;
-    p.g_wgt = (long long)c.Cout * c.Cin;
-    winograd_gemm_params(p, mt, T, c.Cin, c.Cout);  // V / M are tile-major when that fits a buffer descriptor (winograd.hip)
-    split_use(h, p);
-    const double flops = 2.0 * G * (double)T * c.Cin * c.Cout;
-    FS_TRY(prof_begin(h, c.name + ".wino_in", "winograd_input", 0, 4.0 * ((double)B * H * W * c.Cin + (double)v_elems), s));
-    FS_TRY(launch_winograd_input(in, ld_in, V, B, H, W, c.Cin, c.dil, mt, s));
-    FS_TRY(prof_end(h, s));
-    FS_TRY(prof_begin(h, c.name + ".wino_gemm", conv_igemm_tile_name(p), flops, 4.0 * ((double)v_elems + (double)G * c.Cout * c.Cin + (double)m_elems), s));
-    FS_TRY(launch_conv_igemm(p, s));
-    FS_TRY(prof_end(h, s));
-    FS_TRY(prof_begin(h, c.name + ".wino_out", "winograd_output", 0, 4.0 * ((double)m_elems + (double)B * H * W * c.Cout), s));
-    FS_TRY(launch_winograd_output(Mb, c.scale, c.shift, out, ld_out, B, H, W, c.Cout, c.relu, c.dil, mt, s));
-    return prof_end(h, s);
+    float* M = h->wino_ws + wino_v_floats(mt, T, c.Cin, 8);
+    ConvParams bank = winograd_gemm_params(V, U, M, mt, (int)T, c.Cin, c.Cout);  // the launch conv_winograd builds: looks U's planes up
+    split_use(h, bank);
+    return conv_winograd(h, c.name, in, ld_in, U, bank.wgt3, bank.plane_bytes, V, M, c.scale, c.shift, out, ld_out, B, H, W, c.Cin, c.Cout,
+                         c.dil, c.relu, mt, s);
 }
 
 // Winograd pays when its 36 GEMM rows per 4x4 tile undercut the 9 taps per pixel of the direct conv even after the
@@ -259,7 +254,7 @@ bool takes_winograd(const fs_net* h, const ConvBN& c, int B, int H, int W, bool 
     // 90 x 90 map (529 tiles per image: 134 workgroups for a key-frame pair, 8 stages each) the three-launch form is faster -- 34 vs 38 us
     // at B = 2, 26 vs 37 us at B = 1 (profiles/r05_experiments.txt section 10).  Decided on ONE image's geometry, never on the batch.
     if (c.Cin < 256 && c.wf && h->use_fused_winograd && (long)cdiv(H, 4) * cdiv(W, 4) >= 1500) return false;
-    const int mt = h->wino_force_m ? h->wino_force_m : winograd_pick_m(B, H, W, c.dil);
+    const int mt = wino_m(h->wino_force_m, H, W, c.dil);
     const double wino_rows = (double)(mt + 2) * (mt + 2) * winograd_tiles(B, H, W, c.dil, mt);
     const double direct_rows = 9.0 * (double)B * c.out_size(H) * c.out_size(W);
     // dilation <= 4 (the dilated ResNet stages, the heads): 0.8; the ASPP dilations leave the lattices of a 90x90 map
@@ -270,9 +265,8 @@ bool takes_winograd(const fs_net* h, const ConvBN& c, int B, int H, int W, bool 
 // fs_reserve: the Winograd workspace this conv needs at this geometry (0 = direct kernel), its filter bank built on `s`
 int reserve_conv(fs_net* h, const ConvBN& c, int B, int H, int W, hipStream_t s, size_t* need) {
     if (!takes_winograd(h, c, B, H, W, false)) return 0;
-    const int mt = h->wino_force_m ? h->wino_force_m : winograd_pick_m(B, H, W, c.dil);
-    const size_t G = (size_t)(mt + 2) * (mt + 2), T = (size_t)winograd_tiles(B, H, W, c.dil, mt);
-    *need = std::max(*need, wino_ws_floats(G, T, c.Cin, c.Cout));
+    const int mt = wino_m(h->wino_force_m, H, W, c.dil);
+    *need = std::max(*need, wino_vm_floats(mt, (size_t)winograd_tiles(B, H, W, c.dil, mt), c.Cin, c.Cout, 8));
     const float* U = nullptr;
     return wino_bank(h, c, mt, s, &U);
 }
@@ -290,30 +284,8 @@ bool takes_fused_winograd(const fs_net* h, const ConvBN& c, int B, int H, int W,
 // launch parameters of one conv + (BatchNorm | bias) + activation (+ residual) on the implicit-GEMM kernel
 ConvParams conv_params(const fs_net* h, const ConvBN& c, const float* in, int ld_in, int B, int H, int W, float* out, int ld_out, const float* res,
                        int ld_res) {
-    ConvParams p{};
-    p.in = in;
-    p.ld_in = ld_in;
-    p.wgt = c.w;
-    p.scale = c.scale;
-    p.shift = c.shift;
-    p.res = res;
-    p.ld_res = ld_res;
-    p.out = out;
-    p.ld_out = ld_out;
-    p.B = B;
-    p.H = H;
-    p.W = W;
-    p.Cin = c.Cin;
-    p.Ho = c.out_size(H);
-    p.Wo = c.out_size(W);
-    p.Cout = c.Cout;
-    p.KH = c.KH;
-    p.KW = c.KW;
-    p.stride = c.stride;
-    p.pad = c.pad;
-    p.dil = c.dil;
-    p.relu = c.relu;
-    p.korder = c.korder;
+    ConvParams p = conv2d_params(in, ld_in, c.w, c.scale, c.shift, res, ld_res, out, ld_out, B, H, W, c.Cin, c.Cout, c.KH, c.KW, c.stride, c.pad,
+                                 c.dil, c.relu, c.korder);
     p.res_touch = res != nullptr && h->res_touch;
     split_use(h, p);
     return p;
@@ -333,9 +305,7 @@ int run_conv(fs_net* h, const ConvBN& c, const float* in, int ld_in, int B, int 
     const double M = (double)B * p.Ho * p.Wo;
     const double flops = 2.0 * M * c.Cout * c.KH * c.KW * c.Cin;
     const double bytes = 4.0 * ((double)B * H * W * c.Cin + (double)c.Cout * c.KH * c.KW * c.Cin + M * c.Cout * (res ? 2 : 1));
-    FS_TRY(prof_begin(h, c.name, conv_igemm_tile_name(p), flops, bytes, s));
-    FS_TRY(launch_conv_igemm(p, s));
-    return prof_end(h, s);
+    return run_igemm(h, c.name, p, flops, bytes, s);
 }
 
 int ensure_workspace(fs_net* h, size_t buf_elems, size_t small_elems) {
@@ -359,10 +329,10 @@ Geometry geometry(const fs_net* h, int H, int W) {
     Geometry g;
     g.H1 = h->stem[0].out_size(H);
     g.W1 = h->stem[0].out_size(W);
-    g.H2 = (g.H1 + 2 - 3) / 2 + 1;
-    g.W2 = (g.W1 + 2 - 3) / 2 + 1;
-    g.H3 = (g.H2 + 2 - 3) / 2 + 1;
-    g.W3 = (g.W2 + 2 - 3) / 2 + 1;
+    g.H2 = conv_out_size(g.H1, 3, 2, 1, 1);  // MaxPool2d(3, stride 2, padding 1)
+    g.W2 = conv_out_size(g.W1, 3, 2, 1, 1);
+    g.H3 = conv_out_size(g.H2, 3, 2, 1, 1);  // conv2 of layer2.0: 3x3 stride 2 pad 1
+    g.W3 = conv_out_size(g.W2, 3, 2, 1, 1);
     return g;
 }
 
@@ -467,6 +437,33 @@ int net_load_weight(fs_handle h, const char* name, const float* data, const int6
     return 0;
 }
 
+namespace {
+// the last 1x1 conv of a head, [K][cls_cin][1][1] + bias, kept as loaded (the classifier kernels read [K][C])
+int load_classifier(fs_net* h, const std::string& prefix, int K) {
+    const RawTensor *w, *b;
+    FS_TRY(fetch(h, prefix + ".weight", &w));
+    FS_TRY(fetch(h, prefix + ".bias", &b));
+    FS_REQUIRE(w->shape.size() == 4 && w->shape[0] == K && w->shape[1] == h->cls_cin, "%s.weight has wrong shape", prefix.c_str());
+    FS_TRY(dev_alloc(h, &h->cls_w, (size_t)w->numel()));
+    FS_TRY(dev_alloc(h, &h->cls_b, (size_t)K));
+    FS_HIP(hipMemcpy(h->cls_w, w->d, (size_t)w->numel() * sizeof(float), hipMemcpyDeviceToDevice));
+    FS_HIP(hipMemcpy(h->cls_b, b->d, (size_t)K * sizeof(float), hipMemcpyDeviceToDevice));
+    return 0;
+}
+
+// end of finalize: the loaded tensors have all been packed into the handle's own banks
+int release_raw(fs_net* h) {
+    FS_HIP(hipDeviceSynchronize());
+    for (auto& kv : h->raw) {
+        (void)hipFree(kv.second.d);
+        kv.second.d = nullptr;
+    }
+    h->raw.clear();
+    h->finalized = true;
+    return 0;
+}
+}  // namespace
+
 int net_finalize(fs_handle h, hipStream_t s) {
     FS_REQUIRE(h, "fs_finalize: null handle");
     FS_REQUIRE(!h->finalized, "fs_finalize: already finalized");
@@ -474,14 +471,7 @@ int net_finalize(fs_handle h, hipStream_t s) {
     FS_HIP(hipStreamSynchronize(s));
     if (h->cfg.arch == FS_ARCH_SEGMENTER) {
         FS_TRY(vit_finalize(h, s));
-        FS_HIP(hipDeviceSynchronize());
-        for (auto& kv : h->raw) {
-            (void)hipFree(kv.second.d);
-            kv.second.d = nullptr;
-        }
-        h->raw.clear();
-        h->finalized = true;
-        return 0;
+        return release_raw(h);
     }
     const bool psp = h->cfg.arch == FS_ARCH_PSPNET;
     const std::string bb = psp ? "" : "backbone.";
@@ -581,14 +571,7 @@ int net_finalize(fs_handle h, hipStream_t s) {
             }
             FS_TRY(split_attach(h, zw, (size_t)4 * 9 * O * 512, s));
         }
-        const RawTensor *w, *b;
-        FS_TRY(fetch(h, "decoder.4.weight", &w));
-        FS_TRY(fetch(h, "decoder.4.bias", &b));
-        FS_REQUIRE(w->shape.size() == 4 && w->shape[0] == K && w->shape[1] == h->cls_cin, "decoder.4.weight has wrong shape");
-        FS_TRY(dev_alloc(h, &h->cls_w, (size_t)w->numel()));
-        FS_TRY(dev_alloc(h, &h->cls_b, (size_t)K));
-        FS_HIP(hipMemcpy(h->cls_w, w->d, (size_t)w->numel() * sizeof(float), hipMemcpyDeviceToDevice));
-        FS_HIP(hipMemcpy(h->cls_b, b->d, (size_t)K * sizeof(float), hipMemcpyDeviceToDevice));
+        FS_TRY(load_classifier(h, "decoder.4", K));
     } else {
         const int rates[4] = {0, 12, 24, 36};
         FS_TRY(make_conv(h, h->aspp[0], "classifier.0.convs.0.0.weight", "classifier.0.convs.0.1", "", 1, 0, 1, 1, false, s));
@@ -600,24 +583,10 @@ int net_finalize(fs_handle h, hipStream_t s) {
         FS_TRY(make_conv(h, h->project, "classifier.0.project.0.weight", "classifier.0.project.1", "", 1, 0, 1, 1, false, s));
         FS_TRY(make_conv(h, h->head_conv, "classifier.1.weight", "classifier.2", "", 1, 1, 1, 1, false, s));
         h->cls_cin = h->head_conv.Cout;
-        const RawTensor *w, *b;
-        FS_TRY(fetch(h, "classifier.4.weight", &w));
-        FS_TRY(fetch(h, "classifier.4.bias", &b));
-        FS_REQUIRE(w->shape.size() == 4 && w->shape[0] == K && w->shape[1] == h->cls_cin, "classifier.4.weight has wrong shape");
-        FS_TRY(dev_alloc(h, &h->cls_w, (size_t)w->numel()));
-        FS_TRY(dev_alloc(h, &h->cls_b, (size_t)K));
-        FS_HIP(hipMemcpy(h->cls_w, w->d, (size_t)w->numel() * sizeof(float), hipMemcpyDeviceToDevice));
-        FS_HIP(hipMemcpy(h->cls_b, b->d, (size_t)K * sizeof(float), hipMemcpyDeviceToDevice));
+        FS_TRY(load_classifier(h, "classifier.4", K));
     }
     FS_HIP(hipStreamSynchronize(s));
-    FS_HIP(hipDeviceSynchronize());
-    for (auto& kv : h->raw) {
-        (void)hipFree(kv.second.d);
-        kv.second.d = nullptr;
-    }
-    h->raw.clear();
-    h->finalized = true;
-    return 0;
+    return release_raw(h);
 }
 
 int net_feature_shape(fs_handle h, int H, int W, int* C, int* fh, int* fw) {
@@ -688,20 +657,14 @@ size_t net_reserved_bytes(fs_handle h) {
 // The builders of net.h: launch geometry shared with the op-level test hooks (api_test.hip)
 ConvParams dual_conv_params(const float* a, int ld_a, const float* b, int ld_b, const float* wgt, const float* shift, float* out, int ld_out, int B,
                             int Ho, int Wo, int Cin, int Cin2, int H2, int W2, int stride2, int Cout, int relu) {
-    ConvParams p{};
-    p.in = a; p.ld_in = ld_a; p.wgt = wgt; p.shift = shift; p.out = out; p.ld_out = ld_out;
-    p.B = B; p.H = Ho; p.W = Wo; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
-    p.KH = p.KW = 1; p.stride = 1; p.dil = 1; p.relu = relu;
+    ConvParams p = conv2d_params(a, ld_a, wgt, nullptr, shift, nullptr, 0, out, ld_out, B, Ho, Wo, Cin, Cout, 1, 1, 1, 0, 1, relu, 0);
     p.in2 = b; p.ld_in2 = ld_b; p.Cin2 = Cin2; p.stride2 = stride2; p.H2 = H2; p.W2 = W2;
     return p;
 }
 
 ConvParams ppm_z_params(const float* reduced, const float* zw, float* zbuf, int B, int Cr, int Cout9) {
     const int rows = B * 36;
-    ConvParams p{};
-    p.in = reduced; p.ld_in = Cr; p.wgt = zw; p.out = zbuf; p.ld_out = Cout9;
-    p.B = 1; p.H = rows; p.W = 1; p.Cin = Cr; p.Ho = rows; p.Wo = 1; p.Cout = Cout9;
-    p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
+    ConvParams p = gemm_params(reduced, Cr, zw, zbuf, Cout9, rows, Cr, Cout9);
     p.groups = 4;
     p.g_in = (long long)rows * Cr;
     p.g_wgt = (long long)Cout9 * Cr;
@@ -720,16 +683,16 @@ int pyramid_pool(fs_net* h, const float* feat, int ld_feat, float* pooled, int B
     }
     const double bytes = 4.0 * B * H * W * C;
     if (H % 6 == 0 && W % 6 == 0 && bins[0] == 1 && bins[1] == 2 && bins[2] == 3 && bins[3] == 6) {  // one pass over the map instead of four
-        if (h) FS_TRY(prof_begin(h, "ppm.pool6+combine", "adaptive_avgpool", 0, bytes, s));
+        FS_TRY(prof_begin(h, "ppm.pool6+combine", "adaptive_avgpool", 0, bytes, s));
         FS_TRY(launch_adaptive_avgpool(feat, ld_feat, pooled + pool_off[3], B, H, W, C, 6, s));
         FS_TRY(launch_ppm_pool_combine(pooled + pool_off[3], pooled + pool_off[0], pooled + pool_off[1], pooled + pool_off[2], B, C, s));
-        if (h) FS_TRY(prof_end(h, s));
+        FS_TRY(prof_end(h, s));
         return 0;
     }
     for (int i = 0; i < 4; ++i) {
-        if (h) FS_TRY(prof_begin(h, "ppm.pool" + std::to_string(bins[i]), "adaptive_avgpool", 0, bytes, s));
+        FS_TRY(prof_begin(h, "ppm.pool" + std::to_string(bins[i]), "adaptive_avgpool", 0, bytes, s));
         FS_TRY(launch_adaptive_avgpool(feat, ld_feat, pooled + pool_off[i], B, H, W, C, bins[i], s));
-        if (h) FS_TRY(prof_end(h, s));
+        FS_TRY(prof_end(h, s));
     }
     return 0;
 }
@@ -772,24 +735,7 @@ int encoder_core(fs_handle h, const FrameSrc& src, int B, int H, int W, float* o
     // ---- stem
     {
         const ConvBN& c = h->stem[0];
-        StemParams p{};
-        p.src = src;
-        p.wgt = c.w;
-        p.scale = c.scale;
-        p.shift = c.shift;
-        p.out = X;
-        p.ld_out = c.Cout;
-        p.B = B;
-        p.H = H;
-        p.W = W;
-        p.Ho = g.H1;
-        p.Wo = g.W1;
-        p.Cout = c.Cout;
-        p.KH = c.KH;
-        p.KW = c.KW;
-        p.stride = c.stride;
-        p.pad = c.pad;
-        p.split = h->use_split;
+        const StemParams p = stem_params(src, c.w, c.scale, c.shift, X, B, H, W, c.Cout, c.KH, c.KW, c.stride, c.pad, h->use_split);
         const double M = (double)B * g.H1 * g.W1;
         FS_TRY(prof_begin(h, c.name, h->use_split ? "stem_conv_split" : "stem_conv", 2.0 * M * c.Cout * c.KH * c.KW * 3, 4.0 * (B * 3.0 * H * W + M * c.Cout), s));
         FS_TRY(launch_stem_conv(p, s));
@@ -844,9 +790,7 @@ int encoder_core(fs_handle h, const FrameSrc& src, int B, int H, int W, float* o
             split_use(h, p);
             const double M = (double)B * oH * oW;
             const double fl = 2.0 * M * Cn * (p.Cin + p.Cin2), by = 4.0 * (M * p.Cin + (double)B * curH * curW * p.Cin2 + (double)Cn * (p.Cin + p.Cin2) + M * Cn);
-            FS_TRY(prof_begin(h, blk.c3ds.name, conv_igemm_tile_name(p), fl, by, s));
-            FS_TRY(launch_conv_igemm(p, s));
-            FS_TRY(prof_end(h, s));
+            FS_TRY(run_igemm(h, blk.c3ds.name, p, fl, by, s));
             if (!last) std::swap(X, F3);
         } else if (blk.has_ds) {
             FS_TRY(run_conv(h, blk.ds, X, C, B, curH, curW, F3, Cn, nullptr, 0, s));
@@ -944,10 +888,7 @@ int net_segment(fs_handle h, const FrameSrc& src, int B, int H, int W, float* ou
         const ConvBN& z = h->ppm_z[0];
         ConvParams p = ppm_z_params(reduced, z.w, zbuf, B, 512, z.Cout);
         split_use(h, p);
-        FS_TRY(prof_begin(h, "decoder.0.weight[:, ppm]", conv_igemm_tile_name(p), 2.0 * B * 50 * 512.0 * z.Cout,
-                          4.0 * (4.0 * z.Cout * 512 + B * 50.0 * (512 + z.Cout)), ps));
-        FS_TRY(launch_conv_igemm(p, ps));
-        FS_TRY(prof_end(h, ps));
+        FS_TRY(run_igemm(h, "decoder.0.weight[:, ppm]", p, 2.0 * B * 50 * 512.0 * z.Cout, 4.0 * (4.0 * z.Cout * 512 + B * 50.0 * (512 + z.Cout)), ps));
         for (int i = 0; i < 4; ++i) Z[i] = zbuf + (size_t)i * p.g_out;
     }
     ConvBN raw = h->cls_main;  // raw sums: BatchNorm + ReLU are applied after the pyramid term has been added

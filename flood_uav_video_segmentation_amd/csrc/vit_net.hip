@@ -27,37 +27,18 @@ int linear_splits(int K, int N, int rows_per_image, int act, bool split_route) {
 
 ConvParams linear_params(const float* in, const float* w, const float* bias, const float* res, float* out, int rows, int K, int N, int act,
                          bool res_touch) {
-    ConvParams p{};
-    p.in = in;
-    p.ld_in = K;
-    p.wgt = w;
-    p.scale = nullptr;
+    ConvParams p = gemm_params(in, K, w, out, N, rows, K, N);
     p.shift = bias;
     p.res = res;
     p.ld_res = N;
-    p.out = out;
-    p.ld_out = N;
-    p.B = 1;
-    p.H = rows;
-    p.W = 1;
-    p.Cin = K;
-    p.Ho = rows;
-    p.Wo = 1;
-    p.Cout = N;
-    p.KH = p.KW = 1;
-    p.stride = 1;
-    p.pad = 0;
-    p.dil = 1;
     p.relu = act;
     p.res_touch = res_touch;
     return p;
 }
 
 ConvParams linear_splitk_params(const float* in, const float* w, float* part, int rows, int K, int N, int split) {
-    ConvParams p{};
-    p.in = in; p.ld_in = K; p.wgt = w; p.ld_wgt = K; p.out = part; p.ld_out = N;
-    p.B = 1; p.H = rows; p.W = 1; p.Cin = K / split; p.Ho = rows; p.Wo = 1; p.Cout = N;
-    p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
+    ConvParams p = gemm_params(in, K, w, part, N, rows, K / split, N);
+    p.ld_wgt = K;
     p.groups = split;
     p.g_in = K / split;
     p.g_wgt = K / split;
@@ -68,10 +49,8 @@ ConvParams linear_splitk_params(const float* in, const float* w, float* part, in
 ConvParams linear_qkv_params(const float* in, const float* w, const float* bias, float* out, int B, int tokens, int D, float* planes) {
     const int heads = D / 64, Npad = (tokens + 31) / 32 * 32;
     const size_t plane_elems = (size_t)B * heads * Npad * 64;
-    ConvParams p{};
-    p.in = in; p.ld_in = D; p.wgt = w; p.shift = bias; p.out = out; p.ld_out = 3 * D;
-    p.B = 1; p.H = tokens; p.W = 1; p.Cin = D; p.Ho = tokens; p.Wo = 1; p.Cout = 3 * D;
-    p.KH = p.KW = 1; p.stride = 1; p.dil = 1;
+    ConvParams p = gemm_params(in, D, w, out, 3 * D, tokens, D, 3 * D);
+    p.shift = bias;
     p.groups = B;
     p.g_in = (long long)tokens * D;
     p.g_wgt = 0;
@@ -133,6 +112,7 @@ int run_linear(fs_net* h, const Linear& l, const float* in, int rows, float* out
         ConvParams p = linear_splitk_params(in, l.w, part, rows, l.in, l.out, split);
         split_use(h, p);
         const double flops = 2.0 * rows * (double)l.in * l.out;
+        // open-coded, not run_igemm: the profiled interval covers the GEMM and the merge pass behind it
         FS_TRY(prof_begin(h, l.name, conv_igemm_tile_name(p), flops, 4.0 * ((double)rows * (l.in + (split + 1.0) * l.out) + (double)l.in * l.out), s));
         FS_TRY(launch_conv_igemm(p, s));
         if (ln && ln_out && ln->D == l.out) {
@@ -145,10 +125,7 @@ int run_linear(fs_net* h, const Linear& l, const float* in, int rows, float* out
     }
     ConvParams p = linear_params(in, l.w, l.b, res, out, rows, l.in, l.out, act, res != nullptr && h->res_touch);
     split_use(h, p);
-    const double flops = 2.0 * rows * (double)l.in * l.out;
-    FS_TRY(prof_begin(h, l.name, conv_igemm_tile_name(p), flops, 4.0 * ((double)rows * (l.in + l.out) + (double)l.in * l.out), s));
-    FS_TRY(launch_conv_igemm(p, s));
-    return prof_end(h, s);
+    return run_igemm(h, l.name, p, 2.0 * rows * (double)l.in * l.out, 4.0 * ((double)rows * (l.in + l.out) + (double)l.in * l.out), s);
 }
 
 // qkv = in @ W^T + b for B images of `tokens` rows, grouped by image; the Q columns go to out[rows][3D] as fp32, the K and V columns to the
@@ -158,9 +135,7 @@ int run_linear_qkv(fs_net* h, const Linear& l, const float* in, int B, int token
     split_use(h, p);
     FS_REQUIRE(p.wgt3, "segmenter: the fused qkv epilogue needs the split filter bank");
     const double rows = (double)B * tokens;
-    FS_TRY(prof_begin(h, l.name, conv_igemm_tile_name(p, 6), 2.0 * rows * (double)l.in * l.out, 4.0 * (rows * (l.in + l.out) + (double)l.in * l.out), s));
-    FS_TRY(launch_conv_igemm(p, s, 6));
-    return prof_end(h, s);
+    return run_igemm(h, l.name, p, 2.0 * rows * (double)l.in * l.out, 4.0 * (rows * (l.in + l.out) + (double)l.in * l.out), s, 6);
 }
 
 int run_norm(fs_net* h, const LNorm& n, const float* in, float* out, int rows, int rows_per_batch, int drop_first, hipStream_t s) {
