@@ -139,6 +139,12 @@ _EXT_HOOKS = [
 ]
 EXT_MAGIC = 0x4653455854414231  # FS_EXT_MAGIC
 
+# members of fs_ext2_api, the third table (append-only, behind the two frozen ones), in declaration order after `magic` and `size`
+_EXT2_HOOKS = [
+    ("block_match_modes", c_int, [c_void, c_void] + [c_int] * 7 + [c_void, c_void, c_void, c_void, c_void]),
+]
+EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
@@ -152,6 +158,14 @@ class FsHookTables(ctypes.Structure):
     _fields_ = [("test", FsTestApi), ("ext", FsExtApi)]
 
 
+class FsExt2Api(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT2_HOOKS]
+
+
+class FsHookTables2(ctypes.Structure):
+    _fields_ = [("base", FsHookTables), ("ext2", FsExt2Api)]
+
+
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
     fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
@@ -160,8 +174,21 @@ class _Library:
         self._cdll = cdll
         self._hooks = None
         self._ext = None
+        self._ext2 = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT2_HOOKS):
+            if self._ext2 is None:
+                base = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables)).contents
+                if base.test.size != ctypes.sizeof(FsTestApi) or base.ext.magic != EXT_MAGIC or base.ext.size != ctypes.sizeof(FsExtApi):
+                    raise RuntimeError(f"floodseg: the library's first two hook tables are not the ones this binding knows ({name} is missing)")
+                ext2 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables2)).contents.ext2
+                if ext2.magic != EXT2_MAGIC or ext2.size < ctypes.sizeof(FsExt2Api):
+                    raise RuntimeError(f"floodseg: the library has no second extension table, or an older one than this binding ({name} is missing)")
+                self._ext2 = ext2
+            fn = getattr(self._ext2, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT_HOOKS):
             if self._ext is None:
                 tables = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables)).contents
@@ -219,6 +246,11 @@ def hook_names():
 def ext_hook_names():
     """Members of fs_ext_api after `magic` and `size`, in declaration order."""
     return [h[0] for h in _EXT_HOOKS]
+
+
+def ext2_hook_names():
+    """Members of fs_ext2_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT2_HOOKS]
 
 
 def check(rc):

@@ -287,15 +287,28 @@ static int fs_ppm_head(const float* T, int ld, const float* reduced, int Cr, con
     for (int i = 0; i < 4; ++i) Z[i] = zbuf + (size_t)i * p.g_out;
     return fs::launch_ppm_term_classify(T, ld, Z, bins, zbuf + (size_t)4 * p.g_out, scale, shift, B, H, W, C, relu, cls_w, cls_b, logits, K, S(stream));
 }
+// the argument refusals block_match and block_match_modes share, under the caller's name
+static int block_match_args(const char* what, const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty,
+                            const int32_t* mv) {
+    if (!cur || !ref || !mv) return fs::fail("%s: null pointer", what);
+    if (channels != 1 && channels != 3) return fs::fail("%s: channels must be 1 (luma) or 3 (RGB), got %d", what, channels);
+    if (H < 16 || W < 16) return fs::fail("%s: frame %d x %d is smaller than one 16 x 16 block", what, H, W);
+    if (search < 1 || search > 32) return fs::fail("%s: search range must be 1..32, got %d", what, search);
+    if (penalty < 0 || penalty > 255) return fs::fail("%s: penalty must be 0..255, got %d", what, penalty);
+    if ((int64_t)H * W * channels >= ((int64_t)1 << 31)) return fs::fail("%s: frame too large (%d x %d x %d bytes pass 2^31)", what, H, W, channels);
+    return 0;
+}
 static int fs_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int32_t* mv, int32_t* cost,
                           fs_stream stream) {
-    if (!cur || !ref || !mv) return fs::fail("fs_block_match: null pointer");
-    if (channels != 1 && channels != 3) return fs::fail("fs_block_match: channels must be 1 (luma) or 3 (RGB), got %d", channels);
-    if (H < 16 || W < 16) return fs::fail("fs_block_match: frame %d x %d is smaller than one 16 x 16 block", H, W);
-    if (search < 1 || search > 32) return fs::fail("fs_block_match: search range must be 1..32, got %d", search);
-    if (penalty < 0 || penalty > 255) return fs::fail("fs_block_match: penalty must be 0..255, got %d", penalty);
-    if ((int64_t)H * W * channels >= ((int64_t)1 << 31)) return fs::fail("fs_block_match: frame too large (%d x %d x %d bytes pass 2^31)", H, W, channels);
+    if (int rc = block_match_args("fs_block_match", cur, ref, H, W, channels, search, penalty, mv)) return rc;
     return fs::launch_block_match(cur, ref, H, W, channels, search, penalty, mv, cost, S(stream));
+}
+static int fs_block_match_modes(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int intra_bias,
+                                int cut_permille, int32_t* mv, int32_t* cost, int32_t* activity, int32_t* stats, fs_stream stream) {
+    if (int rc = block_match_args("fs_block_match_modes", cur, ref, H, W, channels, search, penalty, mv)) return rc;
+    if (intra_bias < 0 || intra_bias > 65535) return fs::fail("fs_block_match_modes: intra_bias must be 0..65535, got %d", intra_bias);
+    if (cut_permille < 0 || cut_permille > 1000) return fs::fail("fs_block_match_modes: cut_permille must be 0..1000, got %d", cut_permille);
+    return fs::launch_block_match_modes(cur, ref, H, W, channels, search, penalty, intra_bias, cut_permille, mv, cost, activity, stats, S(stream));
 }
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
@@ -383,5 +396,12 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_frame_prepare,
         fs_frame_compose,
     }};
-    return &tables.test;
+    // the two tables above are frozen in text and size; later extension ops live in a third, append-only table behind them.  `all`
+    // takes its first two tables from `tables` (one definition of the member lists), and &all.base.test is also &all.
+    static const fs_hook_tables2 all = {tables, {
+        FS_EXT2_MAGIC,
+        sizeof(fs_ext2_api),
+        fs_block_match_modes,
+    }};
+    return &all.base.test;
 }

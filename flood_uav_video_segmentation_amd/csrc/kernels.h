@@ -307,6 +307,11 @@ int launch_mv_to_grids(const int* mv, int n, int stride, int hb, int wb, int bs,
 // block raster order (the table launch_mv_to_grids takes), cost = int32 [H/16 * W/16] winning costs or nullptr (motion_ops.hip)
 int launch_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int R, int lambda, int* mv, int* cost,
                        hipStream_t s);
+// The same search with the inter / intra decision per block and the scene-cut decision per pair (include/floodseg_test.h,
+// block_match_modes): intra rows -- on a cut all rows -- are void rows (-1, 16, 16, -16, -16, -16, -16); activity = int32 [H/16 * W/16]
+// or nullptr, stats = int32 [4] {blocks, intra blocks, cut, 0} or nullptr, written by the call.  Two launches (search, finishing pass).
+int launch_block_match_modes(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int R, int lambda, int intra_bias, int cut_permille,
+                             int* mv, int* cost, int* activity, int* stats, hipStream_t s);
 // Frame ingest (ingest_ops.hip): one decoded uint8 frame -> normalised NCHW fp32 [3][h][w].  format 0: RGB24 [H][W][3] in `frame`;
 // 1: NV12, `frame` = Y [H][W], u = interleaved UV [ceil(H/2)][ceil(W/2)][2] (v unused); 2: I420, u and v = [ceil(H/2)][ceil(W/2)] each.
 // matrix 0 / 1 (BT.601 / BT.709) and full_range 0 / 1 pick the integer conversion of include/floodseg_test.h.  mean, std: 3 device

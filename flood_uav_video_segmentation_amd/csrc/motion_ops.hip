@@ -11,6 +11,10 @@
 // dwords, so lanes of neighbouring dy fall on different banks.  The winner is the minimum of a 64-bit key (cost, |dx| + |dy|, dy, dx)
 // over the lanes (__shfl_xor); waves do not share a block, so nothing crosses waves.
 // (v_mqsad_u32_u8 would give 32-bit sums, but it is the MASKED form: it leaves out the bytes where the current pixel is 0.)
+//
+// block_match_modes (the same search, MODES = true) also decides, per block, whether the winner explains the block at all (intra: its
+// SAD exceeds the block's own deviation from its mean) and, per frame pair, whether so many blocks are intra that the pair is a scene
+// cut; both are expressed as VOID ROWS, vectors that are not there, which mv_owner_kernel (flow_ops.hip) skips.
 #include "kernels.h"
 
 namespace fs {
@@ -51,10 +55,21 @@ __device__ inline uint32_t load_luma4(const uint8_t* __restrict__ f, int y, int 
 
 __device__ inline unsigned long long pack64(uint32_t lo, uint32_t hi) { return (unsigned long long)hi << 32 | lo; }
 
-template <bool RGB>
+// sum over the wave of a value every lane holds (the butterfly of the key minimum below); every lane gets the total
+__device__ inline uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// MODES adds the inter / intra decision of block_match_modes (include/floodseg_test.h): the block's activity from the 64 dwords of the
+// current block that the wave already staged, one dword per lane (v_sad_u8 against 0 for the sum, against the replicated mean for the
+// deviation, a wave sum each), and a void row in place of the winner's when sad > activity + intra_bias.  Without MODES none of that
+// exists and intra_bias / activity are unused: the <RGB, false> instantiations are block_match's kernel and nothing more.
+template <bool RGB, bool MODES>
 __global__ __launch_bounds__(256) void block_match_kernel(const uint8_t* __restrict__ cur, const uint8_t* __restrict__ ref, int H, int W, int R,
                                                           int lambda, int wb, int nwg_x, int whole_dwords, int* __restrict__ mv,
-                                                          int* __restrict__ cost) {
+                                                          int* __restrict__ cost, int intra_bias, int* __restrict__ activity) {
     __shared__ uint32_t s_ref[MAX_ROWS * MAX_PITCH4];
     __shared__ uint32_t s_cur[NB * MB * MB / 4];  // [block][row][4]
     const int by = blockIdx.x / nwg_x, bx0 = (blockIdx.x - by * nwg_x) * NB;
@@ -119,10 +134,42 @@ __global__ __launch_bounds__(256) void block_match_kernel(const uint8_t* __restr
         const int dst_x = bx * MB + MB / 2, dst_y = by * MB + MB / 2;
         const size_t blk = (size_t)by * wb + bx;
         // (source, w, h, src_x, src_y, dst_x, dst_y): one lane per field
-        const int v = lane == 0 ? -1 : lane < 3 ? MB : lane == 3 ? dst_x + dx : lane == 4 ? dst_y + dy : lane == 5 ? dst_x : dst_y;
+        int v = lane == 0 ? -1 : lane < 3 ? MB : lane == 3 ? dst_x + dx : lane == 4 ? dst_y + dy : lane == 5 ? dst_x : dst_y;
+        if (MODES) {
+            const uint32_t px = s_cur[b * (MB * MB / 4) + lane];  // four pixels of the block per lane
+            const uint32_t mean = (wave_sum(__builtin_amdgcn_sad_u8(px, 0u, 0u)) + 128u) >> 8;  // <= 255
+            const int act = (int)wave_sum(__builtin_amdgcn_sad_u8(px, mean * 0x01010101u, 0u));
+            const int sad = (int)(best >> 21) - lambda * (int)((best >> 14) & 127);
+            if (sad > act + intra_bias) v = lane == 0 ? -1 : lane < 3 ? MB : -MB;  // the void row: no vector was sent for this block
+            if (lane == 8 && activity) activity[blk] = act;
+        }
         if (lane < 7) mv[blk * 7 + lane] = v;
         if (lane == 7 && cost) cost[blk] = (int)(best >> 21);
     }
+}
+
+// The finishing pass of block_match_modes, ONE workgroup: the cut rule needs the pair's intra count before any row is final, so it runs
+// behind the search on the stream.  It counts the void rows the search wrote (src_x = -16 is no winner's: a candidate window lies
+// inside the frame, so a winner's src_x is >= 8) -- a sum of per-thread integer counts, no atomic and nothing to clear beforehand --
+// then, on a cut, makes every row void, and writes stats.  8040 rows at 1080p: 8 rows per thread.
+constexpr int FIN_THREADS = 1024;
+__global__ __launch_bounds__(FIN_THREADS) void block_match_finish_kernel(int* __restrict__ mv, int blocks, int cut_permille, int* __restrict__ stats) {
+    __shared__ int s_part[FIN_THREADS / 64];
+    int n = 0;
+    for (int i = threadIdx.x; i < blocks; i += FIN_THREADS) n += mv[(size_t)i * 7 + 3] == -MB;
+    n = (int)wave_sum((uint32_t)n);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    int intra = 0;
+#pragma unroll
+    for (int i = 0; i < FIN_THREADS / 64; ++i) intra += s_part[i];
+    const bool is_cut = (long long)intra * 1000 > (long long)cut_permille * blocks;
+    if (is_cut)
+        for (long long i = threadIdx.x; i < (long long)blocks * 7; i += FIN_THREADS) {
+            const int f = (int)(i % 7);
+            mv[i] = f == 0 ? -1 : f < 3 ? MB : -MB;
+        }
+    if (stats && threadIdx.x < 4) stats[threadIdx.x] = threadIdx.x == 0 ? blocks : threadIdx.x == 1 ? intra : threadIdx.x == 2 ? (int)is_cut : 0;
 }
 
 }  // namespace
@@ -132,10 +179,28 @@ int launch_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int
     const int whole = W % 4 == 0 && (reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(ref)) % 4 == 0;
     const dim3 grid((unsigned)(hb * nwg_x));
     if (channels == 3)
-        block_match_kernel<true><<<grid, 256, 0, s>>>(cur, ref, H, W, R, lambda, wb, nwg_x, whole, mv, cost);
+        block_match_kernel<true, false><<<grid, 256, 0, s>>>(cur, ref, H, W, R, lambda, wb, nwg_x, whole, mv, cost, 0, nullptr);
     else
-        block_match_kernel<false><<<grid, 256, 0, s>>>(cur, ref, H, W, R, lambda, wb, nwg_x, whole, mv, cost);
+        block_match_kernel<false, false><<<grid, 256, 0, s>>>(cur, ref, H, W, R, lambda, wb, nwg_x, whole, mv, cost, 0, nullptr);
     FS_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_block_match_modes(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int R, int lambda, int intra_bias, int cut_permille,
+                             int* mv, int* cost, int* activity, int* stats, hipStream_t s) {
+    const int hb = H / MB, wb = W / MB, nwg_x = cdiv(wb, NB);
+    const int whole = W % 4 == 0 && (reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(ref)) % 4 == 0;
+    const dim3 grid((unsigned)(hb * nwg_x));
+    if (channels == 3)
+        block_match_kernel<true, true><<<grid, 256, 0, s>>>(cur, ref, H, W, R, lambda, wb, nwg_x, whole, mv, cost, intra_bias, activity);
+    else
+        block_match_kernel<false, true><<<grid, 256, 0, s>>>(cur, ref, H, W, R, lambda, wb, nwg_x, whole, mv, cost, intra_bias, activity);
+    FS_HIP(hipGetLastError());
+    // cut_permille 1000 can never cut: without stats to fill there is nothing left to decide
+    if (cut_permille < 1000 || stats) {
+        block_match_finish_kernel<<<1, FIN_THREADS, 0, s>>>(mv, hb * wb, cut_permille, stats);
+        FS_HIP(hipGetLastError());
+    }
     return 0;
 }
 

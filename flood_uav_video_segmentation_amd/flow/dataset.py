@@ -23,26 +23,28 @@ MEAN = [0.485 * 255, 0.456 * 255, 0.406 * 255]
 STD = [0.229 * 255, 0.224 * 255, 0.225 * 255]
 
 
-def _grid_source(grids, search, penalty):
-    """grids="files": the grids/ and inv_grids/ folders (the reference's layout); "estimate": a flow.motion.GridEstimator."""
+def _grid_source(grids, search, penalty, intra_bias=None, scene_cut=None):
+    """grids="files": the grids/ and inv_grids/ folders (the reference's layout); "estimate": a flow.motion.GridEstimator
+    (intra_bias / scene_cut: its inter / intra and scene-cut decisions, both off when None)."""
     if grids == "files":
         return None
     if grids != "estimate":
         raise ValueError(f'grids must be "files" or "estimate", got {grids!r}')
     from .motion import GridEstimator
 
-    return GridEstimator(search, penalty)
+    return GridEstimator(search, penalty, intra_bias=intra_bias, scene_cut=scene_cut)
 
 
 class PredictWindows:
     """Window i of a video = key frames (i*delta, (i+1)*delta) + the delta-1 grids in between (flow/dataset.py:112-146).
 
-    grids="estimate" (extension): the grids come from block matching of the decoded frames (flow/motion.py, `search`, `penalty`)
-    instead of the grids/ and inv_grids/ folders -- the same grid ids, and a frame is complete when its image exists."""
+    grids="estimate" (extension): the grids come from block matching of the decoded frames (flow/motion.py, `search`, `penalty`,
+    `intra_bias`, `scene_cut`) instead of the grids/ and inv_grids/ folders -- the same grid ids, and a frame is complete when its
+    image exists."""
 
     def __init__(self, data_root, predict_v_id, frame_delta=5, no_warp=False, size=None, device="cuda", grids="files", search=16,
-                 penalty=0):
-        self.estimator = _grid_source(grids, search, penalty)
+                 penalty=0, intra_bias=None, scene_cut=None):
+        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
         self.data_root, self.video_id = data_root, predict_v_id
         self.frame_delta, self.no_warp = frame_delta, no_warp
         self.size = size  # (h, w) of transform_predict's Resize, None = native
@@ -196,10 +198,10 @@ class EvalWindows(PredictWindows):
     (batch_size_test = 1, flow/base.py:164)."""
 
     def __init__(self, data_root, data_list, split="test", frame_delta=5, no_warp=False, size=None, center_crop=None,
-                 classes_ignore=(), device="cuda", grids="files", search=16, penalty=0):
+                 classes_ignore=(), device="cuda", grids="files", search=16, penalty=0, intra_bias=None, scene_cut=None):
         if split not in ("val", "test"):
             raise ValueError("EvalWindows mirrors the val / test splits; use PredictWindows for predict")
-        self.estimator = _grid_source(grids, search, penalty)
+        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
         self.data_root, self.split = data_root, split
         self.frame_delta, self.no_warp = frame_delta, no_warp
         self.size, self.center_crop = size, center_crop      # Resize target (h, w); Crop('center') size of transform_val
@@ -300,7 +302,7 @@ class RawVideoWindows(PredictWindows):
     which is not the stream's Y (range, matrix and the clipping of the conversion all enter)."""
 
     def __init__(self, path, height, width, pix_fmt, frame_delta=5, no_warp=False, size=None, grids="estimate", search=16, penalty=0,
-                 matrix="bt709", full_range=False, device="cuda"):
+                 matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None):
         if pix_fmt not in RAW_PIX_FMTS:
             raise ValueError(f"RawVideoWindows: pix_fmt must be one of {RAW_PIX_FMTS}, got {pix_fmt!r}")
         if grids == "files":
@@ -309,7 +311,7 @@ class RawVideoWindows(PredictWindows):
             raise ValueError(f'RawVideoWindows: matrix must be "bt601" or "bt709", got {matrix!r}')
         if height < 1 or width < 1 or frame_delta < 1:
             raise ValueError(f"RawVideoWindows: bad geometry {height} x {width}, frame_delta {frame_delta}")
-        self.estimator = _grid_source(grids, search, penalty)
+        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
         if not no_warp:
             from .motion import check_geometry
 

@@ -6,7 +6,16 @@ encoder's vectors the reference reads with mvextractor (dataset/flow/extract_mot
 The table -> grid step is the code that serves mvextractor tables (flow/grids.py); only the table's origin differs.  An encoder
 chooses its vectors by rate-distortion, at sub-pel precision, and sends none for an I-frame; this is an integer full search
 on luma.  Grids estimated here are therefore not the grids mvextractor would give for the same video.
+
+A table row may be a VOID ROW, (-1, 16, 16, -16, -16, -16, -16): no vector for that block.  Its block indices floor-divide to -1, the
+grid producer skips it in both directions, and the block's cells keep the identity grid -- what the reference's script leaves for an
+intra macroblock and for a whole I-frame.  ops.block_match never writes one.  With intra_bias= and / or scene_cut= the table comes from
+ops.block_match_modes instead, which writes one for every block the matcher cannot explain (SAD of the winner > the block's deviation
+from its own mean + intra_bias) and, when more than the fraction scene_cut of the blocks are such, for every block: a scene cut
+degrades to "no motion".  Both are off by default; no default has been validated on real video (on flat, noisy water the winner's
+SAD is about 1.4 x the activity, so intra_bias = 0 marks such blocks).  A cut between two key frames still blends the two scenes.
 """
+import warnings
 from collections import OrderedDict
 
 import torch
@@ -28,13 +37,30 @@ def check_geometry(h, w):
                            f"(1072 x 1920 or 1080 x 1920 frames), got a {h} x {w} frame")
 
 
-def estimate_grids(cur, ref, search=16, penalty=0):
+def _warn_cut_without_bias(intra_bias, scene_cut):
+    """scene_cut counts INTRA blocks, and with intra_bias left None (= 65535) no block is ever intra: the cut rule can never fire."""
+    if scene_cut is not None and intra_bias is None:
+        warnings.warn("scene_cut without intra_bias never detects a cut: the cut rule counts intra blocks, and intra_bias=None marks none "
+                      "(give intra_bias as well, e.g. 0)", stacklevel=3)
+
+
+def estimate_grids(cur, ref, search=16, penalty=0, intra_bias=None, scene_cut=None, return_stats=False):
     """(grid, inv_grid) of frame `cur` against the past frame `ref`: float64 CUDA [67,120,2], normalised with the frame's own height
-    and width (extract_motion_vectors.py:94-98).  Enqueues only: nothing is read back to the host."""
+    and width (extract_motion_vectors.py:94-98).  Enqueues only: nothing is read back to the host.
+    intra_bias (0..65535) and / or scene_cut (fraction 0..1): the table comes from ops.block_match_modes (the one left None is off).
+    The cut rule counts intra blocks, so scene_cut needs intra_bias to have any effect: alone it never fires, and warns.
+    return_stats appends the call's device stats tensor int32 [4] (None when both are off): how GridEstimator gets at it."""
     check_geometry(int(cur.shape[0]), int(cur.shape[1]))
-    table = ops.block_match(cur, ref, search=search, penalty=penalty)
+    _warn_cut_without_bias(intra_bias, scene_cut)
+    stats = None
+    if intra_bias is None and scene_cut is None:
+        table = ops.block_match(cur, ref, search=search, penalty=penalty)
+    else:
+        table, stats = ops.block_match_modes(cur, ref, search=search, penalty=penalty, intra_bias=65535 if intra_bias is None else intra_bias,
+                                             scene_cut=scene_cut, return_stats=True)
     with torch.cuda.device(table.device):
-        return motion_vectors_to_grids(table, int(cur.shape[0]), int(cur.shape[1]), validate=False)
+        grids = motion_vectors_to_grids(table, int(cur.shape[0]), int(cur.shape[1]), validate=False)
+    return (*grids, stats) if return_stats else grids
 
 
 class GridEstimator:
@@ -45,18 +71,42 @@ class GridEstimator:
     default grid twice: an I-frame carries no vectors in the reference's pipeline either.  The last `cache` results and the last
     two decoded frames are kept (neighbouring windows ask for neighbouring frames)."""
 
-    def __init__(self, search=16, penalty=0, cache=64):
+    STATS_CHUNK = 256
+
+    def __init__(self, search=16, penalty=0, cache=64, intra_bias=None, scene_cut=None):
         if not 1 <= int(search) <= 32 or not 0 <= int(penalty) <= 255:
             raise ValueError(f"GridEstimator: search must be 1..32 and penalty 0..255, got {search}, {penalty}")
+        if intra_bias is not None and not 0 <= int(intra_bias) <= 65535:
+            raise ValueError(f"GridEstimator: intra_bias must be 0..65535 or None, got {intra_bias}")
+        if scene_cut is not None and not 0 <= float(scene_cut) <= 1:
+            raise ValueError(f"GridEstimator: scene_cut must be a fraction in [0, 1] or None, got {scene_cut}")
         self.search, self.penalty = int(search), int(penalty)
+        self.intra_bias = None if intra_bias is None else int(intra_bias)
+        self.scene_cut = None if scene_cut is None else float(scene_cut)
+        _warn_cut_without_bias(intra_bias, scene_cut)
         self._cache_size = int(cache)
         self._grids = OrderedDict()
         self._frames = OrderedDict()
+        self._stats = {}        # frame id -> one row of a chunk below
+        self._stat_chunks = []  # int32 [STATS_CHUNK, 4] device buffers: one allocation per STATS_CHUNK estimated pairs, not one per pair
 
     def reset(self):
-        """Forget every cached frame and grid (the caller moves to another video)."""
+        """Forget every cached frame, grid and stats tensor (the caller moves to another video)."""
         self._grids.clear()
         self._frames.clear()
+        self._stats.clear()
+        self._stat_chunks.clear()
+
+    def stats_for(self, frame_id):
+        """The device stats tensor int32 [4] = (blocks, intra blocks, cut, 0) of a pair this estimator has estimated with intra_bias /
+        scene_cut; None for a frame that took the default grid (no predecessor), that was not estimated, or with both decisions off.
+        Kept for every estimated frame until reset() -- 16 bytes each, rows of shared [256, 4] buffers, so a long video costs one 4 KB
+        allocation per 256 pairs -- unlike the grids, which the cache evicts.  Reading it back is the caller's choice, and cost."""
+        return self._stats.get(frame_id)
+
+    def estimated_stats(self):
+        """{frame_id: device stats tensor} of every pair estimated since the last reset()."""
+        return dict(self._stats)
 
     def _frame(self, frame_id, load_frame):
         if frame_id in self._frames:
@@ -81,7 +131,15 @@ class GridEstimator:
             default = torch.from_numpy(get_default_grid()).to(cur.device)
             out = (default, default.clone())
         else:
-            out = estimate_grids(cur, ref, self.search, self.penalty)
+            *out, stats = estimate_grids(cur, ref, self.search, self.penalty, self.intra_bias, self.scene_cut, return_stats=True)
+            out = tuple(out)
+            if stats is not None:
+                if frame_id not in self._stats:  # (a frame estimated again after its grids were evicted keeps its row)
+                    row = len(self._stats) % self.STATS_CHUNK
+                    if row == 0:
+                        self._stat_chunks.append(torch.empty((self.STATS_CHUNK, 4), dtype=torch.int32, device=stats.device))
+                    self._stats[frame_id] = self._stat_chunks[-1][row]
+                self._stats[frame_id].copy_(stats)  # 16 bytes device to device, enqueued like the rest
         self._grids[frame_id] = out
         while len(self._grids) > self._cache_size:
             self._grids.popitem(last=False)

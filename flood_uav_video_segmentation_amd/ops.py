@@ -400,7 +400,10 @@ def iou_hist(pred_u8, target_u8, classes, ignore_index=255, hist=None):
 def block_match(cur, ref, search=16, penalty=0, return_cost=False):
     """Full-search block matching of two uint8 frames [H,W] (luma) or [H,W,3] (RGB as decoded), `ref` the past frame: the motion-vector
     table int32 [H//16 * W//16, 7] that flow.grids.motion_vectors_to_grids takes (definition: include/floodseg_test.h, block_match).
-    return_cost: also the winning costs, int32 [H//16 * W//16]."""
+    return_cost: also the winning costs, int32 [H//16 * W//16].
+    Every row this op writes is a winner's.  A table may also hold VOID ROWS, (-1, 16, 16, -16, -16, -16, -16): "no vector for this
+    block", as an encoder sends none for an intra block.  The grid producer skips them, so their cells keep the identity grid;
+    block_match_modes below writes them."""
     lib = _lib.load()
     dev = one_device(cur, ref, what="floodseg.block_match")
     if cur.dtype != torch.uint8 or ref.dtype != torch.uint8:
@@ -415,6 +418,39 @@ def block_match(cur, ref, search=16, penalty=0, return_cost=False):
         cost = torch.empty((n,), dtype=torch.int32, device=dev) if return_cost else None
         check(lib.fs_block_match(ptr(cur), ptr(ref), h, w, 3 if cur.dim() == 3 else 1, int(search), int(penalty), ptr(mv), ptr(cost), stream_ptr()))
     return (mv, cost) if return_cost else mv
+
+
+VOID_ROW = (-1, 16, 16, -16, -16, -16, -16)  # a table row that carries no vector (include/floodseg_test.h, block_match_modes)
+
+
+def block_match_modes(cur, ref, search=16, penalty=0, intra_bias=65535, scene_cut=None, return_cost=False, return_activity=False,
+                      return_stats=False):
+    """block_match with two decisions made on the device (definition: include/floodseg_test.h, block_match_modes).  A block whose
+    winner explains it worse than its own mean does (SAD > activity + intra_bias, 0..65535) is INTRA and gets a void row; a pair with
+    more than the fraction `scene_cut` (0..1, mapped to per-mille with round(); None = never) of intra blocks is a CUT and gets void
+    rows only.  Returns the table, then, as asked for, cost int32 [n], activity int32 [n] and stats int32 [4] = (blocks, intra
+    blocks before the cut rule, cut, 0) -- device tensors all: nothing is read back."""
+    lib = _lib.load()
+    dev = one_device(cur, ref, what="floodseg.block_match_modes")
+    if cur.dtype != torch.uint8 or ref.dtype != torch.uint8:
+        raise RuntimeError(f"floodseg.block_match_modes: frames must be uint8, got {cur.dtype} and {ref.dtype}")
+    if cur.shape != ref.shape or cur.dim() not in (2, 3) or (cur.dim() == 3 and cur.shape[2] != 3):
+        raise RuntimeError(f"floodseg.block_match_modes: frames must be two [H,W] or [H,W,3] tensors of one size, got {tuple(cur.shape)} and {tuple(ref.shape)}")
+    if scene_cut is not None and not 0 <= float(scene_cut) <= 1:
+        raise RuntimeError(f"floodseg.block_match_modes: scene_cut must be a fraction in [0, 1] or None, got {scene_cut}")
+    permille = 1000 if scene_cut is None else int(round(float(scene_cut) * 1000))
+    h, w = int(cur.shape[0]), int(cur.shape[1])
+    with torch.cuda.device(dev):
+        cur, ref = cur.contiguous(), ref.contiguous()
+        n = (h // 16) * (w // 16)
+        mv = torch.empty((n, 7), dtype=torch.int32, device=dev)
+        cost = torch.empty((n,), dtype=torch.int32, device=dev) if return_cost else None
+        activity = torch.empty((n,), dtype=torch.int32, device=dev) if return_activity else None
+        stats = torch.empty((4,), dtype=torch.int32, device=dev) if return_stats else None
+        check(lib.fs_block_match_modes(ptr(cur), ptr(ref), h, w, 3 if cur.dim() == 3 else 1, int(search), int(penalty), int(intra_bias), permille,
+                                       ptr(mv), ptr(cost), ptr(activity), ptr(stats), stream_ptr()))
+    extra = [t for t in (cost, activity, stats) if t is not None]
+    return (mv, *extra) if extra else mv
 
 
 # ------------------------------------------------------------------------------------------ frame ingest

@@ -5,7 +5,8 @@
  * (tests/test_gpu_ops.py, tests/test_gpu_vit_ops.py, tests/test_gpu_head_ops.py) and the measurement tools (tools/).  The table
  * also carries EXTENSION OPS: product features that have no reference call site (block matching, flow/motion.py) and therefore no
  * place in the capped export list of floodseg.h; the Python package reaches them like any other function.  fs_test_api is frozen at
- * block_match; later extension ops (frame ingest, frame egress) are members of fs_ext_api, the table right behind it (end of this file).
+ * block_match; later extension ops (frame ingest, frame egress) are members of fs_ext_api, the table right behind it, and the ones
+ * after those (block_match_modes) of fs_ext2_api, the table behind both (end of this file).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table was append-only up to block_match and is frozen now; `size` is sizeof(fs_test_api)
@@ -188,7 +189,9 @@ typedef struct fs_test_api {
      * displacements |dx|, |dy| <= search (1..32) whose 16 x 16 window lies inside ref minimises, lexicographically,
      * (SAD + penalty (|dx| + |dy|), |dx| + |dy|, dy, dx), penalty 0..255.  mv = int32 [hb * wb][7], block raster order, rows
      * (-1, 16, 16, src_x, src_y, dst_x, dst_y) with dst = the block centre and src = dst + (dx, dy): the table fs_mv_to_grids takes.
-     * cost = int32 [hb * wb] winning costs, or NULL.  Integer arithmetic throughout: results are exact.  H, W >= 16 and
+     * cost = int32 [hb * wb] winning costs, or NULL.  Integer arithmetic throughout: results are exact.  This entry writes a winner's
+     * row for every block; a table may also hold VOID ROWS (-1, 16, 16, -16, -16, -16, -16), "no vector for this block", which
+     * fs_mv_to_grids skips: block_match_modes (fs_ext2_api, end of this file) writes them.  H, W >= 16 and
      * H * W * channels < 2^31; anything else is refused before a launch. */
     int (*block_match)(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int32_t* mv, int32_t* cost,
                        fs_stream stream);
@@ -256,6 +259,55 @@ typedef struct fs_hook_tables {
     fs_test_api test;
     fs_ext_api ext;
 } fs_hook_tables;
+
+/* ---- The second extension table.  fs_ext_api is pinned as well (frame_prepare, frame_compose, 32 bytes: tests/test_ingest_cpu.py,
+ * tests/test_egress_cpu.py), and so is the two-member fs_hook_tables.  Extension ops added since live in a THIRD table, append-only, that
+ * the library places directly behind the two frozen ones: the object fs_test_hooks() points into is an fs_hook_tables2, and its address
+ * is that of its fs_hook_tables and of its fs_test_api,
+ *     const fs_hook_tables2* t = (const fs_hook_tables2*)fs_test_hooks();   t->ext2.block_match_modes(...)
+ * A library built before this table existed returns an fs_hook_tables with nothing behind it: a caller that may meet one checks
+ * t->base.ext.magic first, then t->ext2.magic == FS_EXT2_MAGIC and ext2.size >= the end of the member it needs.  Only the POSITION of a
+ * member is fixed (block_match_modes is the first, at offset 16); the table grows at its end. */
+#define FS_EXT2_MAGIC 0x4653455854414232ull /* "FSEXTAB2" */
+
+typedef struct fs_ext2_api {
+    uint64_t magic; /* FS_EXT2_MAGIC */
+    size_t size;    /* sizeof(fs_ext2_api) of the library that was built */
+
+    /* Block matching with an inter / intra decision per block and a scene-cut decision per frame pair (csrc/motion_ops.hip).  An
+     * encoder sends no vector for an intra-coded macroblock and none at all for an I-frame, and the cells of such blocks keep the
+     * identity grid (dataset/flow/extract_motion_vectors.py:21-43); block_match emits a winner for every block, however bad.  This
+     * entry makes the two decisions on the device and expresses them as the reference's data does: as vectors that are not there.
+     * Integer arithmetic throughout: results are exact.
+     *
+     * cur, ref, H, W, channels, search, penalty, the luma, the 16 x 16 blocks of cur, the candidate window and the WINNER are
+     * block_match's, unchanged: the lexicographic minimum of (SAD + penalty (|dx| + |dy|), |dx| + |dy|, dy, dx).  Per block:
+     *   S        = the sum of the block's 256 luma values;  m = (S + 128) >> 8
+     *   activity = sum over the block of |Y - m|            (0..32640: the DC-intra cost)
+     *   sad      = winning cost - penalty (|dx| + |dy|)     (the winner's plain SAD, 0..65280)
+     *   intra    <=>  sad > activity + intra_bias           intra_bias 0..65535; from 65280 on no block is ever intra
+     * Per frame pair, with blocks = hb * wb and intra_blocks the number of intra blocks:
+     *   cut      <=>  intra_blocks * 1000 > cut_permille * blocks      cut_permille 0..1000; 1000 can never cut
+     * mv = int32 [hb * wb][7], block raster order, as block_match's.  The row of an inter block is block_match's row.  The row of an
+     * intra block -- on a cut, EVERY row -- is the VOID ROW (-1, 16, 16, -16, -16, -16, -16): its source and destination block indices
+     * floor-divide to -1, so fs_mv_to_grids skips it in both directions (the reference's two range checks) and the cells it would have
+     * owned keep the identity grid.  No compaction, no data-dependent sizes, no synchronisation.
+     * Side outputs, each optional (NULL skips it):
+     *   cost     = int32 [hb * wb] winning costs as block_match's, for intra blocks too;
+     *   activity = int32 [hb * wb];
+     *   stats    = int32 [4] = {blocks, intra_blocks (counted before the cut rule), cut as 0 | 1, 0}, written whole by every call (on the
+     *              stream; nothing accumulates), so a HIP-graph replay on new frames gives that replay's figures.
+     * The right intra_bias depends on the sensor's noise: on flat, noisy water sad is about 1.4 x activity, so bias 0 marks such
+     * blocks intra.  Refused before a launch: what block_match refuses (a null cur / ref / mv included), intra_bias outside 0..65535,
+     * cut_permille outside 0..1000. */
+    int (*block_match_modes)(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int intra_bias,
+                             int cut_permille, int32_t* mv, int32_t* cost, int32_t* activity, int32_t* stats, fs_stream stream);
+} fs_ext2_api;
+
+typedef struct fs_hook_tables2 {
+    fs_hook_tables base;
+    fs_ext2_api ext2;
+} fs_hook_tables2;
 
 const fs_test_api* fs_test_hooks(void);
 

@@ -200,9 +200,22 @@ def main():
             for name, (a, b) in (("luma", luma), ("RGB", rgb)):
                 t = timed(lambda i, a=a, b=b, search=search: ops.block_match(a, b, search=search))
                 rows.append((f"block_match 1080x1920 R={search:2d} {name} input (pairs/s)", 1 / t, t * 1e3))
+                # the same search with the intra / scene-cut decisions and the finishing pass, alternating with block_match on the same
+                # frames (three rounds each, the fastest of each side: the difference is a few microseconds)
+                alt = [(timed(lambda i, a=a, b=b, search=search: ops.block_match(a, b, search=search)),
+                        timed(lambda i, a=a, b=b, search=search: ops.block_match_modes(a, b, search=search, intra_bias=0, scene_cut=0.5,
+                                                                                       return_activity=True, return_stats=True)))
+                       for _ in range(3)]
+                t_old, t_new = min(x[0] for x in alt), min(x[1] for x in alt)
+                rows.append((f"  block_match_modes (bias 0, cut 0.5, activity + stats) R={search:2d} {name}: +{(t_new - t_old) * 1e6:.1f} us on "
+                             f"block_match's {t_old * 1e6:.1f} us beside it", 1 / t_new, t_new * 1e3))
                 t = timed(lambda i, a=a, b=b, search=search: motion.estimate_grids(a, b, search=search))
                 rows.append((f"  estimate_grids (matcher + grid producer) R={search:2d} {name}", 1 / t, t * 1e3))
                 pairs_ms[(search, name)] = t * 1e3
+        # the yardstick for "one short launch": block_match on a one-block frame (one workgroup, one candidate) through the same wrapper
+        tiny = [f[:16, :16].contiguous() for f in luma]
+        t = timed(lambda i: ops.block_match(tiny[0], tiny[1], search=1))
+        rows.append(("  near-empty launch beside them (block_match on a 16x16 frame, same wrapper)", 1 / t, t * 1e3))
         fm = FlowModel(psp, feature_based=False, no_warp=False).eval()
         t_win = timeit(window(fm, (wl, wr)), st)
         lows = psp.segment(keys[0:1], keys[1:2])

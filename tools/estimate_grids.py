@@ -9,6 +9,7 @@ and a frame whose predecessor is missing get the default grid.  Encoder vectors 
 sub-pel vectors, I-frames); the table -> grid step is the same code.
 
     python tools/estimate_grids.py dataset/flow florida-01 --search 16 --penalty 0
+    python tools/estimate_grids.py dataset/flow florida-01 --intra-bias 256 --scene-cut 0.5     (unexplained blocks and cuts: identity)
 """
 import argparse
 import os
@@ -26,6 +27,10 @@ def main(argv=None):
     ap.add_argument("video_id")
     ap.add_argument("--search", type=int, default=16)
     ap.add_argument("--penalty", type=int, default=0)
+    ap.add_argument("--intra-bias", type=int, metavar="N", help="0..65535: a block whose best match is worse than its own deviation from its "
+                    "mean + N gets no vector (its cells keep the identity grid); default: off.  The right N depends on the sensor's noise")
+    ap.add_argument("--scene-cut", type=float, metavar="F", help="0..1: a frame with more than this fraction of such blocks gets the default "
+                    "grid (a scene cut); default: off.  Counts the blocks --intra-bias marks: without --intra-bias it never fires")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
 
@@ -34,7 +39,7 @@ def main(argv=None):
     for name in ("grids", "inv_grids"):
         os.makedirs(os.path.join(folder, name), exist_ok=True)
     frames = PredictWindows(args.data_root, args.video_id, no_warp=True, device=args.device)  # paths + decoding only
-    estimator = GridEstimator(args.search, args.penalty)
+    estimator = GridEstimator(args.search, args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut)
     written = 0
     for i in ids:
         paths = [frames.grid_path(i, "grids"), frames.grid_path(i, "inv_grids")]

@@ -15,7 +15,9 @@ frame (ops.compose_frame) and copied out through pinned buffers; the ffmpeg line
 blends the class colours with opacity A (0..255) over the footage the network saw; omitted = opaque colours, the reference's video.
 Under torchrun every rank writes its own window block into the one file (not into a pipe).
 `--grids estimate` (with `--search`, `--penalty`) takes the grids from block matching of the decoded frames instead of the grids/
-folders; a raw video file (`--raw`, as `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24` writes it) always does.
+folders; a raw video file (`--raw`, as `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24` writes it) always does.  `--intra-bias N`
+and `--scene-cut F` (both off by default, no value validated on real video) leave blocks the matcher cannot explain, and whole frames
+across a scene cut, on the identity grid; the frames judged cuts and the mean intra share are printed after the run.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -78,6 +80,10 @@ def parse_args(argv=None):
                     "matching of the decoded frames (flow/motion.py; the only source for --raw)")
     ap.add_argument("--search", type=int, default=16, help="--grids estimate: search range in pixels, 1..32")
     ap.add_argument("--penalty", type=int, default=0, help="--grids estimate: cost per pixel of displacement, 0..255")
+    ap.add_argument("--intra-bias", type=int, metavar="N", help="--grids estimate: 0..65535; a block whose best match is worse than its own "
+                    "deviation from its mean + N gets no vector (identity grid cells).  Default: off; the right N depends on the sensor's noise")
+    ap.add_argument("--scene-cut", type=float, metavar="F", help="--grids estimate: 0..1; a frame with more than this fraction of such blocks "
+                    "gets the default grid (a scene cut).  Default: off.  Counts the blocks --intra-bias marks: without --intra-bias it never fires")
     ap.add_argument("--raw", metavar="FILE", help="raw video input (ffmpeg -f rawvideo) instead of --data-root / --video-id")
     ap.add_argument("--raw-size", type=int, nargs=2, metavar=("H", "W"), help="--raw: frame height and width")
     ap.add_argument("--pix-fmt", choices=("nv12", "i420", "rgb24"), default="nv12", help="--raw: pixel format (i420 = ffmpeg's yuv420p)")
@@ -146,10 +152,10 @@ def main():
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
-                             full_range=args.full_range)
+                             full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut)
     else:
         ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
-                            grids=args.grids, search=args.search, penalty=args.penalty)
+                            grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut)
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -218,6 +224,13 @@ def main():
             line += (f"; temporal consistency mIoU {float((inter / (union + 1e-10)).mean()):.4f}"
                      f" mAcc {float((inter / (target + 1e-10)).mean()):.4f} acc {float(inter.sum() / (target.sum() + 1e-10)):.4f}")
         print(line, file=sys.stderr if args.raw_out == "-" else sys.stdout)   # standard output may be the video
+    kept = ds.estimator.estimated_stats() if ds.estimator is not None else {}
+    if kept:  # --intra-bias / --scene-cut: the kept device stats are read back ONCE, here, after the timed run
+        ids = sorted(kept)
+        host = torch.stack([kept[i] for i in ids]).cpu().numpy()
+        cuts = [i for i, s in zip(ids, host) if s[2]]
+        print(f"rank {rank}: {len(ids)} frame pairs estimated, mean intra share {float((host[:, 1] / host[:, 0]).mean()):.4f}, "
+              f"scene cuts at frames {cuts if cuts else 'none'}", file=sys.stderr if args.raw_out == "-" else sys.stdout)
     if world > 1:
         torch.distributed.destroy_process_group()
 
