@@ -142,6 +142,11 @@ EXT_MAGIC = 0x4653455854414231  # FS_EXT_MAGIC
 # members of fs_ext2_api, the third table (append-only, behind the two frozen ones), in declaration order after `magic` and `size`
 _EXT2_HOOKS = [
     ("block_match_modes", c_int, [c_void, c_void] + [c_int] * 7 + [c_void, c_void, c_void, c_void, c_void]),
+    ("window_weights", c_int, [c_int, ctypes.POINTER(c_void), c_void, c_void, c_void]),
+    ("seg_tail_weighted", c_int, [c_void, c_void, ctypes.POINTER(c_void), ctypes.POINTER(c_void)] + [c_int] * 9 + [c_void] * 4 + [c_int] * 4
+     + [c_void, c_void, c_void]),
+    ("crops_fuse_weighted", c_int, [c_void, c_void, c_void, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)] + [c_int] * 9
+     + [c_void, c_void, c_int, c_int, c_void, c_void, c_void]),
 ]
 EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
 
@@ -183,9 +188,12 @@ class _Library:
                 if base.test.size != ctypes.sizeof(FsTestApi) or base.ext.magic != EXT_MAGIC or base.ext.size != ctypes.sizeof(FsExtApi):
                     raise RuntimeError(f"floodseg: the library's first two hook tables are not the ones this binding knows ({name} is missing)")
                 ext2 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables2)).contents.ext2
-                if ext2.magic != EXT2_MAGIC or ext2.size < ctypes.sizeof(FsExt2Api):
-                    raise RuntimeError(f"floodseg: the library has no second extension table, or an older one than this binding ({name} is missing)")
+                if ext2.magic != EXT2_MAGIC:
+                    raise RuntimeError(f"floodseg: the library has no second extension table ({name} is missing)")
                 self._ext2 = ext2
+            member = getattr(FsExt2Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
+            if self._ext2.size < member.offset + member.size:
+                raise RuntimeError(f"floodseg: the library's second extension table is older than this binding ({name} is missing)")
             fn = getattr(self._ext2, name[3:])
             setattr(self, name, fn)
             return fn

@@ -310,6 +310,64 @@ static int fs_block_match_modes(const uint8_t* cur, const uint8_t* ref, int H, i
     if (cut_permille < 0 || cut_permille > 1000) return fs::fail("fs_block_match_modes: cut_permille must be 0..1000, got %d", cut_permille);
     return fs::launch_block_match_modes(cur, ref, H, W, channels, search, penalty, intra_bias, cut_permille, mv, cost, activity, stats, S(stream));
 }
+static int fs_window_weights(int n, const int32_t* const* stats, float* weights, int32_t* source, fs_stream stream) {
+    if (n < 1 || n > fs::WINDOW_MAX_FRAMES) return fs::fail("fs_window_weights: n must be 1..%d, got %d", fs::WINDOW_MAX_FRAMES, n);
+    if (!weights || !source) return fs::fail("fs_window_weights: null output pointer");
+    return fs::launch_window_weights(stats, n, weights, source, S(stream));
+}
+// fs_seg_tail / fs_seg_tail_accumulate / fs_crops_fuse with per-frame blend weights: the same launch functions, one more pointer
+static int fs_seg_tail_weighted(const float* lo_prev, const float* lo_next, const float* const* grids_left, const float* const* grids_right, int K,
+                                int h, int w, int Hg, int Wg, int H, int W, int n, int no_warp, float* out_logits, uint8_t* out_mask, double* canvas,
+                                double* count, int cH, int cW, int y0, int x0, float* scratch, const float* weights, fs_stream stream) {
+    if (!lo_prev || h < 1 || w < 1 || H < 1 || W < 1) return fs::fail("fs_seg_tail_weighted: bad arguments");
+    if (canvas && (!count || cH < 1 || cW < 1)) return fs::fail("fs_seg_tail_weighted: a canvas without its count or size");
+    fs::SegTailParams p{};
+    p.lo_prev = lo_prev;
+    p.lo_next = lo_next;
+    p.grids_left = grids_left;
+    p.grids_right = grids_right;
+    p.K = K;
+    p.h = h;
+    p.w = w;
+    p.Hg = Hg;
+    p.Wg = Wg;
+    p.H = H;
+    p.W = W;
+    p.n = n;
+    p.no_warp = no_warp;
+    p.out_logits = out_logits;
+    p.out_mask = out_mask;
+    p.scratch = scratch;
+    p.canvas = canvas;
+    p.count = count;
+    p.cH = cH;
+    p.cW = cW;
+    p.y0 = y0;
+    p.x0 = x0;
+    p.weights = weights;
+    return fs::launch_seg_tail(p, S(stream));
+}
+static int fs_crops_fuse_weighted(const float* lo_prev, const float* lo_next, const float* crop_grids, int ncrops, const int* crop_y,
+                                  const int* crop_x, int K, int h, int w, int Hg, int Wg, int ch, int cw, int n, int no_warp, double* canvas,
+                                  uint8_t* mask, int H, int W, float* scratch, const float* weights, fs_stream stream) {
+    if (!lo_prev || !crop_y || !crop_x || ncrops < 1 || ncrops > 64 || h < 1 || w < 1 || ch < 1 || cw < 1 || H < 1 || W < 1 || H > 32767 || W > 32767)
+        return fs::fail("fs_crops_fuse_weighted: bad arguments (1..64 crops, frame at most 32767 px)");
+    fs::CropsFuseParams p{};
+    p.lo_prev = lo_prev;
+    p.lo_next = lo_next;
+    p.nc = ncrops;
+    for (int c = 0; c < ncrops; ++c) {
+        p.cy[c] = (short)crop_y[c];
+        p.cx[c] = (short)crop_x[c];
+    }
+    p.K = K; p.h = h; p.w = w; p.Hg = Hg; p.Wg = Wg; p.ch = ch; p.cw = cw; p.n = n; p.no_warp = no_warp;
+    p.canvas = canvas;
+    p.mask = mask;
+    p.H = H;
+    p.W = W;
+    p.weights = weights;
+    return fs::launch_crops_fuse(p, crop_grids, scratch, S(stream));
+}
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
     if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
@@ -402,6 +460,9 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         FS_EXT2_MAGIC,
         sizeof(fs_ext2_api),
         fs_block_match_modes,
+        fs_window_weights,
+        fs_seg_tail_weighted,
+        fs_crops_fuse_weighted,
     }};
     return &all.base.test;
 }

@@ -7,6 +7,8 @@
 #include "interp.h"
 #include "kernels.h"
 
+#include <type_traits>
+
 namespace fs {
 
 // The flat element index of these kernels is decomposed with divisions by run-time sizes: as a 64-bit value that is ~100 instructions
@@ -215,8 +217,16 @@ __global__ __launch_bounds__(256) void seg_warp_step_kernel(const float* __restr
 // WARP / CANVAS are compile-time: the headline route (linear interpolation, logits + masks) carries neither the warp path's eight
 // gathers per class and frame nor the softmax / float64 canvas code (one run-time kernel for all modes needed 167 registers: three
 // waves per SIMD for a pass that only waits for its stores).  Same operations in the same order in every instantiation.
-template <int KMAX, bool WARP, bool CANVAS>
-__global__ __launch_bounds__(256) void seg_fuse_kernel(SegTailParams p, float sy_lo, float sx_lo, float sy_g, float sx_g) {
+// DEVW: the two blend weights of frame f >= 1 are weights[2f], weights[2f+1] (device, launch_window_weights) instead of (n-f)/n, f/n,
+// and a zero weight HOLDS the frame: it is the other chain's value itself -- no 0 * x term, so neither the sign of a zero nor a
+// non-finite value of the unused chain reaches it, and that chain is not even read.  DEVW is compile-time and only the DEVW = true
+// instantiations take the struct that carries the pointer, so the DEVW = false ones stay the instruction streams (and the
+// kernel-argument segments) they were without it.
+template <int KMAX, bool WARP, bool CANVAS, bool DEVW>
+__global__ __launch_bounds__(256) void seg_fuse_kernel(std::conditional_t<DEVW, SegTailParams, SegFuseArgs> p, float sy_lo, float sx_lo,
+                                                       float sy_g, float sx_g) {
+    const float* weights = nullptr;
+    if constexpr (DEVW) weights = p.weights;
     const int64_t HW = (int64_t)p.H * p.W;
     const int K = p.K, n = p.n;
     const size_t cHW = (size_t)p.cH * p.cW;
@@ -274,8 +284,9 @@ __global__ __launch_bounds__(256) void seg_fuse_kernel(SegTailParams p, float sy
         }
         const int G = p.Hg * p.Wg;
         for (int f = 1; f < n; ++f) {
-            const float wa = (float)((double)(n - f) / (double)n);
-            const float wb = (float)((double)f / (double)n);
+            const float wa = DEVW ? weights[2 * f] : (float)((double)(n - f) / (double)n);
+            const float wb = DEVW ? weights[2 * f + 1] : (float)((double)f / (double)n);
+            const bool hold_a = DEVW && wb == 0.f, hold_b = DEVW && !hold_a && wa == 0.f;  // uniform: one key frame's chain alone
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) {
                 if (k < K) {
@@ -287,10 +298,10 @@ __global__ __launch_bounds__(256) void seg_fuse_kernel(SegTailParams p, float sy
                         // scratch layout: [dir][step][K][Hg][Wg]; forward map f-1, backward map n-f-1
                         const float* pf = p.scratch + ((size_t)(f - 1) * K + k) * G;
                         const float* pb = p.scratch + ((size_t)(n - 1) * K + (size_t)(n - f - 1) * K + k) * G;
-                        va = bilerp_at(pf, p.Wg, gy_c, gx_c);
-                        vb = bilerp_at(pb, p.Wg, gy_c, gx_c);
+                        if (!hold_b) va = bilerp_at(pf, p.Wg, gy_c, gx_c);
+                        if (!hold_a) vb = bilerp_at(pb, p.Wg, gy_c, gx_c);
                     }
-                    v[k] = __fadd_rn(__fmul_rn(wa, va), __fmul_rn(wb, vb));
+                    v[k] = hold_a ? va : hold_b ? vb : __fadd_rn(__fmul_rn(wa, va), __fmul_rn(wb, vb));
                 }
             }
             emit(f);
@@ -324,7 +335,12 @@ int launch_seg_tail(const SegTailParams& p, hipStream_t s) {
     }
     const dim3 grid((unsigned)cdiv(p.W, 256), (unsigned)std::min(p.H, 65535)), block(256);
     const bool canvas = p.canvas != nullptr;
-#define FS_SEG_FUSE(KM_, W_, C_) hipLaunchKernelGGL((seg_fuse_kernel<KM_, W_, C_>), grid, block, 0, s, p, sy_lo, sx_lo, sy_g, sx_g)
+    const SegFuseArgs& a = p;
+#define FS_SEG_FUSE(KM_, W_, C_)                                                                                                   \
+    do {                                                                                                                           \
+        if (p.weights) hipLaunchKernelGGL((seg_fuse_kernel<KM_, W_, C_, true>), grid, block, 0, s, p, sy_lo, sx_lo, sy_g, sx_g);    \
+        else hipLaunchKernelGGL((seg_fuse_kernel<KM_, W_, C_, false>), grid, block, 0, s, a, sy_lo, sx_lo, sy_g, sx_g);            \
+    } while (0)
     if (p.K <= 8) {
         if (warp) { if (canvas) FS_SEG_FUSE(8, true, true); else FS_SEG_FUSE(8, true, false); }
         else { if (canvas) FS_SEG_FUSE(8, false, true); else FS_SEG_FUSE(8, false, false); }
@@ -675,8 +691,11 @@ __global__ __launch_bounds__(256) void seg_warp_step_crops_kernel(const float* _
     seg_warp_step(lo, src, grid, dst, K, h, w, H, W, Hg, Wg, step == 0, sy, sx);
 }
 
-template <int KMAX, int FN>
-__global__ __launch_bounds__(256) void crops_fuse_kernel(CropsFuseParams p) {
+// DEVW: per-frame blend weights from p.weights, a zero weight holds the frame -- as in seg_fuse_kernel.
+template <int KMAX, int FN, bool DEVW>
+__global__ __launch_bounds__(256) void crops_fuse_kernel(std::conditional_t<DEVW, CropsFuseParams, CropsFuseArgs> p) {
+    const float* weights = nullptr;
+    if constexpr (DEVW) weights = p.weights;
     const int64_t HW = (int64_t)p.H * p.W;
     const int K = p.K, n = p.n, G = p.Hg * p.Wg;
     const size_t lo_stride = (size_t)K * p.h * p.w, map = (size_t)K * G;
@@ -721,8 +740,9 @@ __global__ __launch_bounds__(256) void crops_fuse_kernel(CropsFuseParams p) {
                     const int f = f0 + ff;
                     if (f >= n) break;
                     float v[KMAX];
-                    const float wa = (float)((double)(n - f) / (double)n);
-                    const float wb = (float)((double)f / (double)n);
+                    const float wa = DEVW ? weights[2 * f] : (float)((double)(n - f) / (double)n);
+                    const float wb = DEVW ? weights[2 * f + 1] : (float)((double)f / (double)n);
+                    const bool hold_a = DEVW && wb == 0.f, hold_b = DEVW && !hold_a && wa == 0.f;  // uniform; frame 0 reads neither
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) {
                         if (k < K) {
@@ -736,10 +756,10 @@ __global__ __launch_bounds__(256) void crops_fuse_kernel(CropsFuseParams p) {
                                 } else {
                                     const float* pf = sc + ((size_t)(f - 1) * K + k) * G;
                                     const float* pb = sc + ((size_t)(n - 1) * K + (size_t)(n - f - 1) * K + k) * G;
-                                    va = bilerp_at(pf, p.Wg, gy_c, gx_c);
-                                    vb = bilerp_at(pb, p.Wg, gy_c, gx_c);
+                                    if (!hold_b) va = bilerp_at(pf, p.Wg, gy_c, gx_c);
+                                    if (!hold_a) vb = bilerp_at(pb, p.Wg, gy_c, gx_c);
                                 }
-                                v[k] = __fadd_rn(__fmul_rn(wa, va), __fmul_rn(wb, vb));
+                                v[k] = hold_a ? va : hold_b ? vb : __fadd_rn(__fmul_rn(wa, va), __fmul_rn(wb, vb));
                             }
                         }
                     }
@@ -790,7 +810,9 @@ int launch_crops_fuse(CropsFuseParams p, const float* grids, float* scratch, hip
     } else {
         p.no_warp = 1;
     }
-    hipLaunchKernelGGL((crops_fuse_kernel<8, 5>), dim3((unsigned)cdiv(p.W, 256), (unsigned)std::min(p.H, 65535)), dim3(256), 0, s, p);
+    const dim3 fuse_grid((unsigned)cdiv(p.W, 256), (unsigned)std::min(p.H, 65535));
+    if (p.weights) hipLaunchKernelGGL((crops_fuse_kernel<8, 5, true>), fuse_grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((crops_fuse_kernel<8, 5, false>), fuse_grid, dim3(256), 0, s, static_cast<const CropsFuseArgs&>(p));
     FS_HIP(hipGetLastError());
     return 0;
 }

@@ -200,8 +200,9 @@ int launch_resize_bilinear_nhwc(const float* in, int ld_in, int B, int C, int Hi
 // out = wa*a + wb*b  (b may be nullptr -> out = wa*a)
 int launch_blend(const float* a, float wa, const float* b, float wb, float* out, int64_t numel, hipStream_t s);
 
-// Fused predict_segmentation tail.
-struct SegTailParams {
+// Fused predict_segmentation tail.  SegFuseArgs is what the unweighted fusion kernels take by value; SegTailParams adds what only the
+// weighted instantiations read, so the kernel-argument segment of the unweighted ones is the one they always had.
+struct SegFuseArgs {
     const float* lo_prev;   // [K, h, w]   decoder logits of the previous key frame
     const float* lo_next;   // [K, h, w]   or nullptr (single-frame)
     const float* const* grids_left;   // n-1 device pointers [Hg,Wg,2] (ignored when no_warp)
@@ -219,6 +220,9 @@ struct SegTailParams {
     double* count;          // float64 [cH, cW]
     int cH, cW, y0, x0;
 };
+struct SegTailParams : SegFuseArgs {
+    const float* weights;   // device [n][2] per-frame blend weights (launch_window_weights), or nullptr: (n-f)/n and f/n
+};
 int launch_seg_tail(const SegTailParams& p, hipStream_t s);
 
 // Fused predict_feature tail (flow/model.py:131-171): warp chains at grid resolution + every map of the decoder's batch in one launch.
@@ -235,7 +239,8 @@ struct FeatTailParams {
 int launch_feat_tail(const FeatTailParams& p, hipStream_t s);
 
 // Sliding crops in one pass (flow/base.py:182-209 after the network): every pixel of the full frame from the crops covering it.
-struct CropsFuseParams {
+// CropsFuseArgs / CropsFuseParams: split as SegFuseArgs / SegTailParams are.
+struct CropsFuseArgs {
     const float* lo_prev;   // [nc, K, h, w] per-crop decoder logits of the previous key frame
     const float* lo_next;   // the same for the next key frame, or nullptr (single frame)
     const float* scratch;   // warp mode: [nc][2][n-1][K][Hg][Wg] warped maps (filled by the launcher)
@@ -246,6 +251,9 @@ struct CropsFuseParams {
     uint8_t* mask;          // [n, H, W] its argmax or nullptr
     int H, W;
     float sy_lo, sx_lo, sy_g, sx_g;
+};
+struct CropsFuseParams : CropsFuseArgs {
+    const float* weights;   // device [n][2] per-frame blend weights (launch_window_weights), or nullptr: (n-f)/n and f/n
 };
 // grids: [nc][2(n-1)][Hg][Wg][2] (fs_crop_grids' output) in warp mode; scratch: nc * 2(n-1) * K * Hg * Wg floats
 int launch_crops_fuse(CropsFuseParams p, const float* grids, float* scratch, hipStream_t s);
@@ -312,6 +320,11 @@ int launch_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int
 // or nullptr, stats = int32 [4] {blocks, intra blocks, cut, 0} or nullptr, written by the call.  Two launches (search, finishing pass).
 int launch_block_match_modes(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int R, int lambda, int intra_bias, int cut_permille,
                              int* mv, int* cost, int* activity, int* stats, hipStream_t s);
+// Per-frame blend weights of one window from the cut flags of its n frame pairs (include/floodseg_test.h, window_weights):
+// stats[j-1] = the int32 [4] stats of pair (j-1 -> j) as launch_block_match_modes writes them (cut at index 2), or nullptr = no cut;
+// weights = float [n][2], source = int32 [n], written whole by ONE launch of one workgroup.  1 <= n <= WINDOW_MAX_FRAMES (caller).
+constexpr int WINDOW_MAX_FRAMES = 64;
+int launch_window_weights(const int* const* stats, int n, float* weights, int* source, hipStream_t s);
 // Frame ingest (ingest_ops.hip): one decoded uint8 frame -> normalised NCHW fp32 [3][h][w].  format 0: RGB24 [H][W][3] in `frame`;
 // 1: NV12, `frame` = Y [H][W], u = interleaved UV [ceil(H/2)][ceil(W/2)][2] (v unused); 2: I420, u and v = [ceil(H/2)][ceil(W/2)] each.
 // matrix 0 / 1 (BT.601 / BT.709) and full_range 0 / 1 pick the integer conversion of include/floodseg_test.h.  mean, std: 3 device

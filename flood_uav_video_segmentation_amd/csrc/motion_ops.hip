@@ -172,7 +172,45 @@ __global__ __launch_bounds__(FIN_THREADS) void block_match_finish_kernel(int* __
     if (stats && threadIdx.x < 4) stats[threadIdx.x] = threadIdx.x == 0 ? blocks : threadIdx.x == 1 ? intra : threadIdx.x == 2 ? (int)is_cut : 0;
 }
 
+// window_weights (include/floodseg_test.h): the per-frame blend weights of one window from the cut flags of its n frame pairs.  ONE
+// workgroup of one wave: lane j - 1 reads pair j's flag, the wave's ballot is the set of cut pairs, and lane f writes frame f's row --
+// both outputs whole, no atomic, nothing read on the host.  The no-cut row is the expression the fusion kernels evaluate themselves.
+struct WindowStats {
+    const int* pair[WINDOW_MAX_FRAMES];  // pair[j - 1]: the stats of (j-1 -> j), or nullptr
+};
+__global__ __launch_bounds__(64) void window_weights_kernel(WindowStats st, int n, float* __restrict__ weights, int* __restrict__ source) {
+    const int f = threadIdx.x;
+    const bool cut = f < n && st.pair[f] != nullptr && st.pair[f][2] != 0;  // lane f holds pair j = f + 1
+    const unsigned long long cuts = __ballot(cut);                          // bit j - 1 <=> pair j is a cut
+    if (f >= n) return;
+    float wa, wb;
+    int src;
+    if (cuts == 0) {
+        wa = (float)((double)(n - f) / (double)n);
+        wb = (float)((double)f / (double)n);
+        src = 0;
+    } else {
+        const int first = __ffsll((long long)cuts), last = 64 - __clzll((long long)cuts);  // smallest and largest cut pair j (1-based)
+        const bool prev = f < first || (f < last && 2 * f <= n);
+        wa = prev ? 1.f : 0.f;
+        wb = prev ? 0.f : 1.f;
+        src = f < first ? 1 : f >= last ? 2 : 3;
+    }
+    weights[2 * f] = wa;
+    weights[2 * f + 1] = wb;
+    source[f] = src;
+}
+
 }  // namespace
+
+int launch_window_weights(const int* const* stats, int n, float* weights, int* source, hipStream_t s) {
+    static_assert(WINDOW_MAX_FRAMES == 64, "window_weights_kernel keeps the cut pairs of a window in one 64-lane ballot");
+    WindowStats st{};
+    for (int j = 0; j < n; ++j) st.pair[j] = stats ? stats[j] : nullptr;
+    window_weights_kernel<<<1, 64, 0, s>>>(st, n, weights, source);
+    FS_HIP(hipGetLastError());
+    return 0;
+}
 
 int launch_block_match(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int R, int lambda, int* mv, int* cost, hipStream_t s) {
     const int hb = H / MB, wb = W / MB, nwg_x = cdiv(wb, NB);

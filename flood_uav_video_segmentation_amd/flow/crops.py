@@ -72,7 +72,7 @@ def _blank_canvas(n, classes, h, w, dev):
 
 
 def compute_output(flow_model, n, frame_prev, frame_next, mvs_left, mvs_right, crop_h, crop_w, classes, profiler=None,
-                   want_mask=False, function=None, key_cache=None, out_size=None, crop_batch=8, lows=None, want_canvas=True):
+                   want_mask=False, function=None, key_cache=None, out_size=None, crop_batch=8, lows=None, want_canvas=True, weights=None):
     """flow/base.py:182-209: returns the float64 [n,K,H,W] crop-averaged softmax (and, with want_mask, the uint8 argmax of its
     align_corners=True resize to `out_size` -- flow/base.py:275-276; out_size None = the frame size).
 
@@ -89,7 +89,11 @@ def compute_output(flow_model, n, frame_prev, frame_next, mvs_left, mvs_right, c
     With K <= 8 and at most 64 crops the whole post-network part is ONE pass over the frame (fs_crops_fuse): every canvas
     pixel is written once from the crops covering it, in crop order -- bit-identical to the per-crop accumulation, without its
     float64 read-modify-writes; want_canvas=False (predict_step only needs the masks) then skips the canvas altogether and
-    returns (None, mask)."""
+    returns (None, mask).
+    weights (extension): ops.window_weights' device [n,2] tensor for the tails of every crop (a zero weight holds one key frame's
+    chain); None = the reference's blend.  Not with a caller's `function`."""
+    if weights is not None and function is not None:
+        raise NotImplementedError("compute_output: per-frame blend weights cannot be passed through a caller's per-crop function")
     _, _, new_h, new_w = frame_prev.shape
     dev = frame_prev.device
     windows = crop_windows(new_h, new_w, crop_h, crop_w)
@@ -116,7 +120,7 @@ def compute_output(flow_model, n, frame_prev, frame_next, mvs_left, mvs_right, c
         if classes <= 8 and len(yx) <= 64:
             same = out_size is None or (int(out_size[0]), int(out_size[1])) == (new_h, new_w)
             canvas, mask = ops.crops_fuse(lo_prev, lo_next, grids, yx, (crop_h, crop_w), n, no_warp, (new_h, new_w),
-                                          want_canvas=want_canvas or (want_mask and not same), want_mask=want_mask and same)
+                                          want_canvas=want_canvas or (want_mask and not same), want_mask=want_mask and same, weights=weights)
             if want_mask and not same:
                 mask = ops.canvas_resize_argmax(canvas, out_size)
             return (canvas if want_canvas else None, mask) if want_mask else canvas
@@ -124,7 +128,8 @@ def compute_output(flow_model, n, frame_prev, frame_next, mvs_left, mvs_right, c
         for c, (y0, x0) in enumerate(yx):
             gl = [grids[c, j][None] for j in range(n - 1)] if grids is not None else mvs_left
             gr = [grids[c, n - 1 + j][None] for j in range(n - 1)] if grids is not None else mvs_right
-            ops.seg_tail_accumulate(lo_prev[c:c + 1], lo_next[c:c + 1], gl, gr, n, (crop_h, crop_w), no_warp, canvas, count, y0, x0)
+            ops.seg_tail_accumulate(lo_prev[c:c + 1], lo_next[c:c + 1], gl, gr, n, (crop_h, crop_w), no_warp, canvas, count, y0, x0,
+                                    weights=weights)
     else:
         lib = _lib.load()
         canvas, count = _blank_canvas(n, classes, new_h, new_w, dev)
@@ -133,7 +138,8 @@ def compute_output(flow_model, n, frame_prev, frame_next, mvs_left, mvs_right, c
             next_c = frame_next[:, :, s_h:e_h, s_w:e_w].contiguous()
             ml, mr = crop_motion_vector(mvs_left, mvs_right, new_h, new_w, e_h - s_h, e_w - s_w, s_h, s_w)
             if function is None:
-                logits = flow_model.predict(prev_c, next_c, ml, mr, n, profiler)["pred"]
+                extra = {} if weights is None else {"weights": weights}
+                logits = flow_model.predict(prev_c, next_c, ml, mr, n, profiler, **extra)["pred"]
             else:
                 logits = function(prev_c, next_c, ml, mr)
             if logits.shape[2] != crop_h or logits.shape[3] != crop_w:

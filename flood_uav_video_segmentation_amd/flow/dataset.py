@@ -35,15 +35,31 @@ def _grid_source(grids, search, penalty, intra_bias=None, scene_cut=None):
     return GridEstimator(search, penalty, intra_bias=intra_bias, scene_cut=scene_cut)
 
 
+def _check_hold_cuts(who, hold_cuts, grids, scene_cut):
+    """hold_cuts reacts to the cut flags the grid estimator's matcher writes: without them it could never do anything."""
+    if hold_cuts and (grids != "estimate" or scene_cut is None):
+        raise ValueError(f'{who}: hold_cuts needs the scene-cut decision of the estimated grids (grids="estimate" and scene_cut=)')
+    return bool(hold_cuts)
+
+
 class PredictWindows:
     """Window i of a video = key frames (i*delta, (i+1)*delta) + the delta-1 grids in between (flow/dataset.py:112-146).
 
     grids="estimate" (extension): the grids come from block matching of the decoded frames (flow/motion.py, `search`, `penalty`,
     `intra_bias`, `scene_cut`) instead of the grids/ and inv_grids/ folders -- the same grid ids, and a frame is complete when its
-    image exists."""
+    image exists.
+
+    hold_cuts=True (extension; needs grids="estimate" and scene_cut): an item also carries "weights" (float32 [frame_delta, 2]) and
+    "source" (int32 [frame_delta]), device tensors from ops.window_weights on the cut flags of the window's frame_delta frame pairs:
+    FlowPredictor hands the weights to the tails, which then hold one key frame across a cut instead of blending two scenes.  One
+    more search per window (the closing pair); with no_warp every pair is searched -- and every in-between frame decoded -- for its
+    flag alone."""
+
+    hold_cuts = False
 
     def __init__(self, data_root, predict_v_id, frame_delta=5, no_warp=False, size=None, device="cuda", grids="files", search=16,
-                 penalty=0, intra_bias=None, scene_cut=None):
+                 penalty=0, intra_bias=None, scene_cut=None, hold_cuts=False):
+        self.hold_cuts = _check_hold_cuts("PredictWindows", hold_cuts, grids, scene_cut)
         self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
         self.data_root, self.video_id = data_root, predict_v_id
         self.frame_delta, self.no_warp = frame_delta, no_warp
@@ -131,11 +147,20 @@ class PredictWindows:
         """Grid `g` of grids/ (name "grids") or inv_grids/ as the float32 [1,67,120,2] device tensor of an item."""
         if self.estimator is None:
             return load_grid(self.grid_path(g, name))[None].to(self.device)
+        pair = self._video_estimator().grids_for(g, self.raw_frame)
+        return pair[0 if name == "grids" else 1].float()[None]
+
+    def _video_estimator(self):
         if getattr(self, "_estimator_video", None) != self.video_id:  # EvalWindows walks several videos: frame ids are per video
             self.estimator.reset()
             self._estimator_video = self.video_id
-        pair = self.estimator.grids_for(g, self.raw_frame)
-        return pair[0 if name == "grids" else 1].float()[None]
+        return self.estimator
+
+    def _cut_weights(self, index):
+        """(weights, source) of window `index` from the cut flags of its frame pairs; asked for AFTER the item's grids, so that only
+        the closing pair (and, with no_warp, every pair) is still to be searched."""
+        stats = self._video_estimator().window_stats(index * self.frame_delta, self.frame_delta, self.raw_frame)
+        return ops.window_weights(stats, self.frame_delta)
 
     def _frame(self, f_id):
         """ToTensor, Resize (cv2.INTER_LINEAR on the uint8 image = half-pixel bilinear, stored back as uint8) and Normalize
@@ -158,6 +183,8 @@ class PredictWindows:
             fwd, inv = self.grid_ids(index)
             item["mvs_left"] = [self._grid(i, "grids") for i in fwd]
             item["mvs_right"] = [self._grid(i, "inv_grids") for i in inv]
+        if self.hold_cuts:
+            item["weights"], item["source"] = self._cut_weights(index)
         return item
 
 
@@ -295,14 +322,15 @@ class RawVideoWindows(PredictWindows):
     pix_fmt "nv12" (Y plane + interleaved UV), "i420" (= yuv420p: Y, U, V planes) or "rgb24"; frames are read through numpy.memmap and
     uploaded once each; the network's input comes from ops.prepare_frame (`matrix`, `full_range`: the integer YUV -> RGB conversion of
     include/floodseg_test.h).  len = frames // frame_delta; a file that is not a whole number of frames raises.  A raw file has no grid
-    folders: the grids are estimated (grids="estimate", flow/motion.py) unless no_warp; "files" raises.
+    folders: the grids are estimated (grids="estimate", flow/motion.py) unless no_warp; "files" raises.  hold_cuts: as PredictWindows'.
 
     For the YUV formats the block matcher gets the stream's Y plane AS IT IS (its one-channel route).  These grids DIFFER from grids
     estimated on the RGB conversion of the same video: there the matcher reduces RGB to its own luma (77 R + 150 G + 29 B + 128) >> 8,
     which is not the stream's Y (range, matrix and the clipping of the conversion all enter)."""
 
     def __init__(self, path, height, width, pix_fmt, frame_delta=5, no_warp=False, size=None, grids="estimate", search=16, penalty=0,
-                 matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None):
+                 matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None, hold_cuts=False):
+        self.hold_cuts = _check_hold_cuts("RawVideoWindows", hold_cuts, grids, scene_cut)
         if pix_fmt not in RAW_PIX_FMTS:
             raise ValueError(f"RawVideoWindows: pix_fmt must be one of {RAW_PIX_FMTS}, got {pix_fmt!r}")
         if grids == "files":

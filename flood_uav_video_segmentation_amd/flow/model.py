@@ -216,31 +216,38 @@ class FlowModel(nn.Module):
             return self.predict_feature(*args, **kwargs)
         return self.predict_segmentation(*args, **kwargs)
 
-    def predict_segmentation(self, frame_prev, frame_next, mvs_left, mvs_right, n, profiler=None, key_cache=None, with_mask=False):
+    def predict_segmentation(self, frame_prev, frame_next, mvs_left, mvs_right, n, profiler=None, key_cache=None, with_mask=False, weights=None):
         """Segment the key frames, propagate the LOGITS (reference :184-241).
         Returns {"pred": [n,K,h,w]} ([1,K,h,w] when frame_next is None).  key_cache: see KeyframeCache (extension).
         with_mask=True (extension): the fused tail also emits the per-frame argmax it has in registers anyway -- an extra
         "mask" entry, uint8 [n,h,w] = pred.max(1)[1] (flow/base.py:276) -- so that a caller who wants both does not re-read
-        the logits for it."""
+        the logits for it.
+        weights (extension): ops.window_weights' device [n,2] tensor -- the tail blends frame f with its row and holds one key
+        frame's chain where a weight is zero (a detected scene cut); None = the reference's (n-f)/n, f/n."""
         h, w = frame_prev.shape[2], frame_prev.shape[3]
         with _region(profiler, "predict_encoder"), _region(profiler, "predict_decoder"):
             lo_prev, lo_next = self._key_outputs(self._segment, self._tag("seg", h, w), frame_prev, frame_next, key_cache)
         with _region(profiler, "predict_warp"), _region(profiler, "predict_fusion"):
-            logits, mask = ops.seg_tail(lo_prev, lo_next, mvs_left, mvs_right, n, (h, w), self.no_warp, want_logits=True, want_mask=with_mask)
+            logits, mask = ops.seg_tail(lo_prev, lo_next, mvs_left, mvs_right, n, (h, w), self.no_warp, want_logits=True, want_mask=with_mask,
+                                        weights=weights)
         return {"pred": logits, "mask": mask} if with_mask else {"pred": logits}
 
-    def predict_masks(self, frame_prev, frame_next, mvs_left, mvs_right, n, profiler=None, key_cache=None):
-        """Same pipeline, but the fused tail emits the per-frame argmax directly: uint8 [n,h,w].
+    def predict_masks(self, frame_prev, frame_next, mvs_left, mvs_right, n, profiler=None, key_cache=None, weights=None):
+        """Same pipeline, but the fused tail emits the per-frame argmax directly: uint8 [n,h,w].  weights: as predict_segmentation's.
         (Extension for the native-resolution timed region of bench.py; not a reference method.)"""
         h, w = frame_prev.shape[2], frame_prev.shape[3]
         with _region(profiler, "predict_encoder"), _region(profiler, "predict_decoder"):
             lo_prev, lo_next = self._key_outputs(self._segment, self._tag("seg", h, w), frame_prev, frame_next, key_cache)
         with _region(profiler, "predict_fusion"):
-            _, mask = ops.seg_tail(lo_prev, lo_next, mvs_left, mvs_right, n, (h, w), self.no_warp, want_logits=False, want_mask=True)
+            _, mask = ops.seg_tail(lo_prev, lo_next, mvs_left, mvs_right, n, (h, w), self.no_warp, want_logits=False, want_mask=True,
+                                   weights=weights)
         return mask
 
-    def predict_feature(self, frame_prev, frame_next, mvs_left, mvs_right, n, profiler=None, key_cache=None, with_mask=False):
-        """Propagate encoder FEATURES, decode all n maps in one batch (reference :116-181).  with_mask: as in predict_segmentation."""
+    def predict_feature(self, frame_prev, frame_next, mvs_left, mvs_right, n, profiler=None, key_cache=None, with_mask=False, weights=None):
+        """Propagate encoder FEATURES, decode all n maps in one batch (reference :116-181).  with_mask: as in predict_segmentation.
+        weights: not supported -- the feature tail (fs_feat_tail) blends with (n-f)/n, f/n only; anything but None raises."""
+        if weights is not None:
+            raise NotImplementedError("FlowModel.predict_feature: per-frame blend weights (hold_cuts) exist for the segmentation tails only")
         h, w = frame_prev.shape[2], frame_prev.shape[3]
         with _region(profiler, "predict_encoder"):
             f, f_next = self._key_outputs(self._encode, self._tag("feat", h, w), frame_prev, frame_next, key_cache)

@@ -13,7 +13,12 @@ intra macroblock and for a whole I-frame.  ops.block_match never writes one.  Wi
 ops.block_match_modes instead, which writes one for every block the matcher cannot explain (SAD of the winner > the block's deviation
 from its own mean + intra_bias) and, when more than the fraction scene_cut of the blocks are such, for every block: a scene cut
 degrades to "no motion".  Both are off by default; no default has been validated on real video (on flat, noisy water the winner's
-SAD is about 1.4 x the activity, so intra_bias = 0 marks such blocks).  A cut between two key frames still blends the two scenes.
+SAD is about 1.4 x the activity, so intra_bias = 0 marks such blocks).
+
+What a cut does to the BLEND of the two key frames is the window datasets' hold_cuts= (flow/dataset.py): GridEstimator.window_stats
+hands the cut flags of a window's frame pairs -- the closing pair (last in-between frame -> next key frame) included, which feeds no
+grid and is searched for this alone -- to ops.window_weights, and the tails hold one key frame's chain on each side of the cut
+(include/floodseg_test.h, window_weights).  Without hold_cuts a cut between two key frames still blends the two scenes linearly.
 """
 import warnings
 from collections import OrderedDict
@@ -108,6 +113,33 @@ class GridEstimator:
         """{frame_id: device stats tensor} of every pair estimated since the last reset()."""
         return dict(self._stats)
 
+    def _keep_stats(self, frame_id, stats):
+        """Copy a call's stats into frame_id's row of the shared buffers (16 bytes device to device, enqueued like the rest)."""
+        if frame_id not in self._stats:  # (a frame estimated again after its grids were evicted keeps its row)
+            row = len(self._stats) % self.STATS_CHUNK
+            if row == 0:
+                self._stat_chunks.append(torch.empty((self.STATS_CHUNK, 4), dtype=torch.int32, device=stats.device))
+            self._stats[frame_id] = self._stat_chunks[-1][row]
+        self._stats[frame_id].copy_(stats)
+
+    def window_stats(self, first_id, n, load_frame):
+        """The n stats tensors (stats_for) of the pairs first_id+1 .. first_id+n of a window whose previous key frame is first_id, as
+        ops.window_weights takes them.  A pair that has not been estimated yet -- the closing pair (first_id+n-1 -> first_id+n) feeds no
+        grid of any window, and with no_warp no pair does -- gets the SEARCH alone here (no table -> grid step); a pair with a missing
+        frame yields None, "no cut".  All None with both decisions off."""
+        out = []
+        for j in range(first_id + 1, first_id + n + 1):
+            if j not in self._stats and (self.intra_bias is not None or self.scene_cut is not None):
+                ref = self._frame(j - 1, load_frame) if j > 0 else None
+                cur = self._frame(j, load_frame) if ref is not None else None
+                if cur is not None:
+                    _, stats = ops.block_match_modes(cur, ref, search=self.search, penalty=self.penalty,
+                                                     intra_bias=65535 if self.intra_bias is None else self.intra_bias,
+                                                     scene_cut=self.scene_cut, return_stats=True)
+                    self._keep_stats(j, stats)
+            out.append(self._stats.get(j))
+        return out
+
     def _frame(self, frame_id, load_frame):
         if frame_id in self._frames:
             return self._frames[frame_id]
@@ -134,12 +166,7 @@ class GridEstimator:
             *out, stats = estimate_grids(cur, ref, self.search, self.penalty, self.intra_bias, self.scene_cut, return_stats=True)
             out = tuple(out)
             if stats is not None:
-                if frame_id not in self._stats:  # (a frame estimated again after its grids were evicted keeps its row)
-                    row = len(self._stats) % self.STATS_CHUNK
-                    if row == 0:
-                        self._stat_chunks.append(torch.empty((self.STATS_CHUNK, 4), dtype=torch.int32, device=stats.device))
-                    self._stats[frame_id] = self._stat_chunks[-1][row]
-                self._stats[frame_id].copy_(stats)  # 16 bytes device to device, enqueued like the rest
+                self._keep_stats(frame_id, stats)
         self._grids[frame_id] = out
         while len(self._grids) > self._cache_size:
             self._grids.popitem(last=False)

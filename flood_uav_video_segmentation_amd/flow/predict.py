@@ -41,9 +41,12 @@ class FlowPredictor:
             self.key_cache.clear()
         self.last_output = None
 
-    def predict_window(self, frame_prev, frame_next, mvs_left, mvs_right, profiler=None, to_host=True, key_ids=None, key_cache=None):
+    def predict_window(self, frame_prev, frame_next, mvs_left, mvs_right, profiler=None, to_host=True, key_ids=None, key_cache=None,
+                       weights=None):
         """key_cache: a KeyframeCache to use for this call instead of the predictor's own (predict_clip's fallback passes a
-        cache that lives for the clip only)."""
+        cache that lives for the clip only).  weights: an item's "weights" (the window datasets' hold_cuts; ops.window_weights) for
+        the whole-frame and the sliding-crop tails alike, None = the reference's blend.  The key-frame cache is unaffected: the
+        network's outputs do not depend on them."""
         assert frame_prev.shape[0] == 1                      # flow/base.py:263
         assert len(mvs_left) == len(mvs_right)               # :264
         n = len(mvs_left) + 1                                # :266 -- the list length encodes n, also for no_warp dummies
@@ -51,6 +54,8 @@ class FlowPredictor:
         kc = cache.window(*key_ids) if (cache is not None and key_ids is not None) else None
         if self.crop is None:
             extra = {} if kc is None else {"key_cache": kc}
+            if weights is not None:
+                extra["weights"] = weights
             if self._native(frame_prev) and not getattr(self.model, "feature_based", True) and hasattr(self.model, "predict_masks"):
                 # out_size IS the frame size: the align_corners=True resize of :275 is the identity (source index = destination
                 # index, weight 0), so :275-276 is the argmax of the logits themselves -- which the fused tail emits without
@@ -62,7 +67,8 @@ class FlowPredictor:
         else:
             # :273 compute_output, then :275-276 (float64 resize + argmax) fused into the canvas's last pass
             _, masks = crops.compute_output(self.model, n, frame_prev, frame_next, mvs_left, mvs_right, self.crop[0], self.crop[1],
-                                            self.classes, profiler, want_mask=True, key_cache=kc, out_size=self.out_size, want_canvas=False)
+                                            self.classes, profiler, want_mask=True, key_cache=kc, out_size=self.out_size, want_canvas=False,
+                                            weights=weights)
         self._score(masks, n)
         return masks.cpu().numpy() if to_host else masks                # :277
 
@@ -124,15 +130,16 @@ class FlowPredictor:
             h, wd = w["frame_prev"].shape[2], w["frame_prev"].shape[3]
             if self.crop is None and self._native(w["frame_prev"]):
                 with _region(profiler, "predict_warp"), _region(profiler, "predict_fusion"):  # identity resize: see predict_window
-                    _, masks = ops.seg_tail(lo_prev, lo_next, w["mvs_left"], w["mvs_right"], n, (h, wd), fm.no_warp, want_logits=False, want_mask=True)
+                    _, masks = ops.seg_tail(lo_prev, lo_next, w["mvs_left"], w["mvs_right"], n, (h, wd), fm.no_warp, want_logits=False, want_mask=True,
+                                                weights=w.get("weights"))
             elif self.crop is None:
                 with _region(profiler, "predict_warp"), _region(profiler, "predict_fusion"):
-                    logits, _ = ops.seg_tail(lo_prev, lo_next, w["mvs_left"], w["mvs_right"], n, (h, wd), fm.no_warp, want_logits=True)
+                    logits, _ = ops.seg_tail(lo_prev, lo_next, w["mvs_left"], w["mvs_right"], n, (h, wd), fm.no_warp, want_logits=True, weights=w.get("weights"))
                 masks = ops.resize_argmax_u8(logits, self.out_size)
             else:
                 _, masks = crops.compute_output(fm, n, w["frame_prev"], w["frame_next"], w["mvs_left"], w["mvs_right"], self.crop[0],
                                                 self.crop[1], self.classes, profiler, want_mask=True, out_size=self.out_size,
-                                                lows=(lo_prev, lo_next), want_canvas=False)
+                                                lows=(lo_prev, lo_next), want_canvas=False, weights=w.get("weights"))
             self._score(masks, n)
             return masks.cpu().numpy() if to_host else masks
 
@@ -166,7 +173,7 @@ class FlowPredictor:
             store = {k: v for k, v in store.items() if k in live}  # only what a window still to come can need
             if plain is not None:
                 yield self.predict_window(plain["frame_prev"], plain["frame_next"], plain["mvs_left"], plain["mvs_right"], profiler, to_host,
-                                          plain.get("key_ids"), key_cache=local_cache)
+                                          plain.get("key_ids"), key_cache=local_cache, weights=plain.get("weights"))
             elif exhausted and not pending and not queue:
                 return
 

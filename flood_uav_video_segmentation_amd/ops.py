@@ -129,10 +129,52 @@ def _ptr_array(tensors):
     return arr
 
 
-def seg_tail(lo_prev, lo_next, grids_left, grids_right, n, out_hw, no_warp, want_logits=True, want_mask=False):
+def _window_weights_arg(weights, n, dev, what):
+    """The device [n,2] float32 blend weights of window_weights, checked; None stays None (the unweighted entry point)."""
+    if weights is None:
+        return None
+    if not weights.is_cuda or weights.device != dev:
+        raise RuntimeError(f"{what}: weights must live on the tensors' device ({dev})")
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (int(n), 2) or not weights.is_contiguous():
+        raise RuntimeError(f"{what}: weights must be a contiguous float32 [{int(n)}, 2] tensor, got {weights.dtype} {tuple(weights.shape)}")
+    return weights
+
+
+def window_weights(stats, n):
+    """Per-frame blend weights of one key-frame window from the cut flags of its n frame pairs (definition: include/floodseg_test.h,
+    window_weights).  stats: n entries, stats[j-1] = the int32 [4] stats tensor block_match_modes wrote for the pair (j-1 -> j), or
+    None (not estimated: no cut).  Returns (weights float32 [n,2], source int32 [n]: 0 blended, 1 held from the previous key frame,
+    2 held from the next one, 3 a scene neither key frame shows) -- device tensors from one launch; nothing is read back."""
+    lib = _lib.load()
+    n = int(n)
+    stats = list(stats)
+    if len(stats) != n:
+        raise RuntimeError(f"floodseg.window_weights: need one stats entry (or None) per frame pair, got {len(stats)} for n={n}")
+    if not 1 <= n <= 64:
+        raise RuntimeError(f"floodseg.window_weights: n must be 1..64, got {n}")
+    if any(t is not None for t in stats):
+        dev = one_device(*stats, what="floodseg.window_weights")
+    else:  # no pair was estimated: the linear weights, on the current device
+        dev = torch.device("cuda", torch.cuda.current_device())
+    for t in stats:
+        if t is not None and (t.dtype != torch.int32 or t.numel() < 4 or not t.is_contiguous()):
+            raise RuntimeError("floodseg.window_weights: a stats entry must be a contiguous int32 tensor of 4 values")
+    with torch.cuda.device(dev):
+        arr = (ctypes.c_void_p * n)()
+        for i, t in enumerate(stats):
+            arr[i] = None if t is None else t.data_ptr()
+        weights = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        source = torch.empty((n,), dtype=torch.int32, device=dev)
+        check(lib.fs_window_weights(n, arr, ptr(weights), ptr(source), stream_ptr()))
+    return weights, source
+
+
+def seg_tail(lo_prev, lo_next, grids_left, grids_right, n, out_hw, no_warp, want_logits=True, want_mask=False, weights=None):
     """Fused predict_segmentation tail (flow/model.py:184-241 after the two decoder calls).
 
     lo_prev/lo_next: [1,K,h,w] decoder logits; grids: lists of n-1 [1,Hg,Wg,2] tensors.
+    weights: None (frame f blends the two chains with (n-f)/n and f/n), or window_weights' device [n,2] tensor: frame f >= 1 blends
+    with its row, and a row with a zero HOLDS the frame -- it is the other chain's value, bit for bit.
     Returns (logits [n,K,H,W] or None, mask uint8 [n,H,W] or None).
     """
     lib = _lib.load()
@@ -162,8 +204,13 @@ def seg_tail(lo_prev, lo_next, grids_left, grids_right, n, out_hw, no_warp, want
                 gl = _ptr_array(keep[: n - 1])
                 gr = _ptr_array(keep[n - 1:])
                 scratch = torch.empty(2 * (n - 1) * k * hg * wg, dtype=torch.float32, device=dev)
-        check(lib.fs_seg_tail(ptr(lo_prev), ptr(lo_next), gl, gr, k, h, w, hg, wg, hh, ww, int(n), int(bool(no_warp)),
-                              ptr(logits), ptr(mask), ptr(scratch), stream_ptr()))
+        weights = _window_weights_arg(weights, n, dev, "floodseg.seg_tail")
+        if weights is None:
+            check(lib.fs_seg_tail(ptr(lo_prev), ptr(lo_next), gl, gr, k, h, w, hg, wg, hh, ww, int(n), int(bool(no_warp)),
+                                  ptr(logits), ptr(mask), ptr(scratch), stream_ptr()))
+        else:
+            check(lib.fs_seg_tail_weighted(ptr(lo_prev), ptr(lo_next), gl, gr, k, h, w, hg, wg, hh, ww, int(n), int(bool(no_warp)),
+                                           ptr(logits), ptr(mask), None, None, 0, 0, 0, 0, ptr(scratch), ptr(weights), stream_ptr()))
     return logits, mask
 
 
@@ -213,9 +260,9 @@ def feat_tail(f_prev, f_next, grids_left, grids_right, n, no_warp, default_grid=
     return stack
 
 
-def seg_tail_accumulate(lo_prev, lo_next, grids_left, grids_right, n, crop_hw, no_warp, canvas, count, y0, x0):
+def seg_tail_accumulate(lo_prev, lo_next, grids_left, grids_right, n, crop_hw, no_warp, canvas, count, y0, x0, weights=None):
     """The same tail feeding the sliding-crop canvas (flow/base.py:204-205, 226-234): softmax over K of every output frame
-    of this crop is ADDED to canvas [n,K,H,W] (float64) at (y0, x0), count[H,W] += 1 over the crop -- in place."""
+    of this crop is ADDED to canvas [n,K,H,W] (float64) at (y0, x0), count[H,W] += 1 over the crop -- in place.  weights: as seg_tail's."""
     lib = _lib.load()
     grids = [] if (lo_next is None or no_warp) else list(grids_left) + list(grids_right)
     dev = one_device(lo_prev, lo_next, canvas, count, *grids, what="floodseg.seg_tail_accumulate")
@@ -244,9 +291,15 @@ def seg_tail_accumulate(lo_prev, lo_next, grids_left, grids_right, n, crop_hw, n
                 gl = _ptr_array(keep[: n - 1])
                 gr = _ptr_array(keep[n - 1:])
                 scratch = torch.empty(2 * (n - 1) * k * hg * wg, dtype=torch.float32, device=dev)
-        check(lib.fs_seg_tail_accumulate(ptr(lo_prev), ptr(lo_next), gl, gr, k, h, w, hg, wg, int(crop_hw[0]), int(crop_hw[1]), int(n),
-                                         int(bool(no_warp)), ptr(canvas), ptr(count), canvas.shape[2], canvas.shape[3], int(y0), int(x0),
-                                         ptr(scratch), stream_ptr()))
+        weights = _window_weights_arg(weights, n, dev, "floodseg.seg_tail_accumulate")
+        if weights is None:
+            check(lib.fs_seg_tail_accumulate(ptr(lo_prev), ptr(lo_next), gl, gr, k, h, w, hg, wg, int(crop_hw[0]), int(crop_hw[1]), int(n),
+                                             int(bool(no_warp)), ptr(canvas), ptr(count), canvas.shape[2], canvas.shape[3], int(y0), int(x0),
+                                             ptr(scratch), stream_ptr()))
+        else:
+            check(lib.fs_seg_tail_weighted(ptr(lo_prev), ptr(lo_next), gl, gr, k, h, w, hg, wg, int(crop_hw[0]), int(crop_hw[1]), int(n),
+                                           int(bool(no_warp)), None, None, ptr(canvas), ptr(count), canvas.shape[2], canvas.shape[3], int(y0),
+                                           int(x0), ptr(scratch), ptr(weights), stream_ptr()))
 
 
 def crop_grids(grids, frame_hw, crop_yx, crop_hw):
@@ -270,10 +323,10 @@ def crop_grids(grids, frame_hw, crop_yx, crop_hw):
     return out
 
 
-def crops_fuse(lo_prev, lo_next, grids, crop_yx, crop_hw, n, no_warp, frame_hw, want_canvas=True, want_mask=False):
+def crops_fuse(lo_prev, lo_next, grids, crop_yx, crop_hw, n, no_warp, frame_hw, want_canvas=True, want_mask=False, weights=None):
     """compute_output after the network for ALL crops of a window in one pass (fs_crops_fuse): lo_prev / lo_next = per-crop
-    decoder logits [nc,K,h,w]; grids = crop_grids' output [nc, 2(n-1), fh, fw, 2] or None (no_warp).  Returns (float64 canvas
-    [n,K,H,W] already divided by the crop count, or None; uint8 argmax [n,H,W] or None) -- each pixel written once."""
+    decoder logits [nc,K,h,w]; grids = crop_grids' output [nc, 2(n-1), fh, fw, 2] or None (no_warp); weights: as seg_tail's.  Returns
+    (float64 canvas [n,K,H,W] already divided by the crop count, or None; uint8 argmax [n,H,W] or None) -- each pixel written once."""
     lib = _lib.load()
     dev = one_device(lo_prev, lo_next, grids, what="floodseg.crops_fuse")
     with torch.cuda.device(dev):
@@ -300,8 +353,14 @@ def crops_fuse(lo_prev, lo_next, grids, crop_yx, crop_hw, n, no_warp, frame_hw, 
         mask = torch.empty((frames, hh, ww), dtype=torch.uint8, device=dev) if want_mask else None
         ys = (ctypes.c_int * nc)(*[int(y) for y, _ in crop_yx])
         xs = (ctypes.c_int * nc)(*[int(x) for _, x in crop_yx])
-        check(lib.fs_crops_fuse(ptr(lo_prev), ptr(lo_next), ptr(grids) if warp else None, nc, ys, xs, k, h, w, hg, wg, int(crop_hw[0]),
-                                int(crop_hw[1]), int(n), int(not warp), ptr(canvas), ptr(mask), hh, ww, ptr(scratch), stream_ptr()))
+        weights = _window_weights_arg(weights, n, dev, "floodseg.crops_fuse")
+        if weights is None:
+            check(lib.fs_crops_fuse(ptr(lo_prev), ptr(lo_next), ptr(grids) if warp else None, nc, ys, xs, k, h, w, hg, wg, int(crop_hw[0]),
+                                    int(crop_hw[1]), int(n), int(not warp), ptr(canvas), ptr(mask), hh, ww, ptr(scratch), stream_ptr()))
+        else:
+            check(lib.fs_crops_fuse_weighted(ptr(lo_prev), ptr(lo_next), ptr(grids) if warp else None, nc, ys, xs, k, h, w, hg, wg,
+                                             int(crop_hw[0]), int(crop_hw[1]), int(n), int(not warp), ptr(canvas), ptr(mask), hh, ww,
+                                             ptr(scratch), ptr(weights), stream_ptr()))
     return canvas, mask
 
 

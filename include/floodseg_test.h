@@ -6,7 +6,8 @@
  * also carries EXTENSION OPS: product features that have no reference call site (block matching, flow/motion.py) and therefore no
  * place in the capped export list of floodseg.h; the Python package reaches them like any other function.  fs_test_api is frozen at
  * block_match; later extension ops (frame ingest, frame egress) are members of fs_ext_api, the table right behind it, and the ones
- * after those (block_match_modes) of fs_ext2_api, the table behind both (end of this file).
+ * after those (block_match_modes, window_weights, seg_tail_weighted, crops_fuse_weighted) of fs_ext2_api, the table behind both (end of
+ * this file).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table was append-only up to block_match and is frozen now; `size` is sizeof(fs_test_api)
@@ -302,6 +303,40 @@ typedef struct fs_ext2_api {
      * cut_permille outside 0..1000. */
     int (*block_match_modes)(const uint8_t* cur, const uint8_t* ref, int H, int W, int channels, int search, int penalty, int intra_bias,
                              int cut_permille, int32_t* mv, int32_t* cost, int32_t* activity, int32_t* stats, fs_stream stream);
+
+    /* Per-frame blend weights of one key-frame window from the cut flags of its frame pairs (csrc/motion_ops.hip): what lets the tails
+     * HOLD one key frame across a detected scene cut instead of blending two scenes.  OUR DEFINITION.  The window has frames 0..n:
+     * frame 0 is the previous key frame, frame n the next one (not emitted), 1 <= n <= 64.  stats = a HOST array of n DEVICE pointers,
+     * stats[j - 1] for the pair (j-1 -> j), j = 1..n, each an int32 [4] as block_match_modes writes it (cut at index 2); a NULL entry
+     * -- or stats == NULL -- means "not estimated: no cut".  Outputs, both on the device, written whole by one launch of one small
+     * workgroup (no atomics, nothing read on the host, so a HIP-graph replay on new stats gives that replay's weights):
+     *   weights = float [n][2] = (wa, wb) per emitted frame f = 0..n-1;  source = int32 [n].
+     * With first / last the smallest / largest j whose pair is a cut:
+     *   no cut:              wa = (float)((double)(n - f) / n), wb = (float)((double)f / n), source 0 (the linear blend, bit for bit
+     *                        the expression the tails evaluate without weights)
+     *   f < first:           (1, 0), source 1: held from the previous key frame
+     *   f >= last:           (0, 1), source 2: held from the next key frame
+     *   first <= f < last:   a scene neither key frame shows: (1, 0) if 2 f <= n, else (0, 1); source 3
+     * Frame 0 is (1, 0) in every case.  Refused before a launch: n < 1, n > 64, a null output. */
+    int (*window_weights)(int n, const int32_t* const* stats, float* weights, int32_t* source, fs_stream stream);
+
+    /* fs_seg_tail and fs_seg_tail_accumulate (floodseg.h) in one entry, with per-frame blend weights: every argument means what it
+     * means there (out_logits / out_mask: fs_seg_tail's outputs, each optional; canvas / count / cH / cW / y0 / x0: the sliding-crop
+     * canvas of fs_seg_tail_accumulate, canvas == NULL: none), through the same launch function.  weights = device float [n][2] as
+     * window_weights writes it, or NULL: the existing entries' result, bit for bit.  For frame f >= 1 with (wa, wb) = weights[f]:
+     *   wb == 0: v = va;   else wa == 0: v = vb;   else v = fadd_rn(fmul_rn(wa, va), fmul_rn(wb, vb))
+     * va / vb being the previous / next key frame's chain at that pixel (the warp chain, or the upsampled logits when no_warp).  A held
+     * frame is exactly one chain's value: no 0 * x term, so no sign of a zero and no non-finite value leaks from the unused chain.
+     * Frame 0 never reads its weights.  Warp chains, upsample, argmax, softmax and the float64 canvas are the unweighted tail's. */
+    int (*seg_tail_weighted)(const float* lo_prev, const float* lo_next, const float* const* grids_left, const float* const* grids_right, int K,
+                             int h, int w, int Hg, int Wg, int H, int W, int n, int no_warp, float* out_logits, uint8_t* out_mask, double* canvas,
+                             double* count, int cH, int cW, int y0, int x0, float* scratch, const float* weights, fs_stream stream);
+
+    /* fs_crops_fuse (floodseg.h) with the same per-frame weights: its arguments, then weights (device float [n][2], or NULL: the result
+     * of fs_crops_fuse).  Bit-identical to seg_tail_weighted in canvas mode per crop, in crop order, followed by fs_canvas_finish. */
+    int (*crops_fuse_weighted)(const float* lo_prev, const float* lo_next, const float* crop_grids, int ncrops, const int* crop_y,
+                               const int* crop_x, int K, int h, int w, int Hg, int Wg, int ch, int cw, int n, int no_warp, double* canvas,
+                               uint8_t* mask, int H, int W, float* scratch, const float* weights, fs_stream stream);
 } fs_ext2_api;
 
 typedef struct fs_hook_tables2 {

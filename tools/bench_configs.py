@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -293,6 +293,51 @@ def main():
                     torch.cuda.current_stream().synchronize()
                 t = timeit(item_step, steps=6, warmup=2)
                 rows.append((f"PredictWindows item, grids=estimate, JPEG folder (host-bound), {label}", 1 / t, t * 1e3))
+    if want("cuts"):
+        # holding one key frame across a scene cut (ops.window_weights, the weighted instantiations of the two fused tails): the weighted
+        # call against the unweighted one on the same held logits, alternating (three rounds each, the fastest of each side), every loop
+        # >= 0.5 s; weights of a window without a cut (the same blend) and of one cut in its middle (held frames read ONE chain).  Then
+        # what a window pays for its weights: one window_weights launch and the closing pair's search.
+        from flood_uav_video_segmentation_amd.flow.crops import crop_windows
+        gen = torch.Generator().manual_seed(1600)
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+
+        def flags(cuts):
+            return [torch.tensor([8040, 0, c, 0], dtype=torch.int32, device=dev) for c in cuts]
+        w_none, w_cut = ops.window_weights(flags([0] * N), N)[0], ops.window_weights(flags([0, 0, 1, 0, 0]), N)[0]
+
+        def ab(label, call):
+            alt = [(timed(lambda i: call(None)), timed(lambda i: call(w_none)), timed(lambda i: call(w_cut))) for _ in range(3)]
+            t_old, t_same, t_cut = (min(x[j] for x in alt) for j in range(3))
+            rows.append((f"{label}, unweighted", 1 / t_old, t_old * 1e3))
+            rows.append((f"  weights of a window without a cut: {(t_same / t_old - 1) * 100:+.2f} %", 1 / t_same, t_same * 1e3))
+            rows.append((f"  weights of a cut at pair 3 (two frames held from each side): {(t_cut / t_old - 1) * 100:+.2f} %", 1 / t_cut, t_cut * 1e3))
+        for (hh, ww), hg in (((713, 713), 44), ((1072, 1920), None)):
+            lo = torch.randn((2, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            gl, gr = (wl, wr) if hg else [[g.to(dev) for g in gs] for gs in synth.make_grids(N, 67, 120, seed=2001, frame=(hh, ww))]
+            for no_warp in (False, True):
+                ab(f"seg_tail {hh}x{ww} {'no_warp' if no_warp else 'warp'}, logits + masks",
+                   lambda w, lo=lo, gl=gl, gr=gr, no_warp=no_warp, hh=hh, ww=ww: ops.seg_tail(lo[0:1], lo[1:2], gl, gr, N, (hh, ww), no_warp, want_logits=True,
+                                                                                         want_mask=True, weights=w))
+        wins = crop_windows(1072, 1920, 713, 713)
+        yx = [(y, x) for (y, _, x, _) in wins]
+        lo_c = torch.randn((2, len(yx), 5, 90, 90), generator=gen).to(dev)
+        g1080 = [[g.to(dev) for g in gs] for gs in synth.make_grids(N, 67, 120, seed=2002, frame=(1072, 1920))]
+        cg = ops.crop_grids(g1080[0] + g1080[1], (1072, 1920), yx, (713, 713))
+        for no_warp in (False, True):
+            ab(f"crops_fuse 1072x1920, {len(yx)} crops of 713x713, {'no_warp' if no_warp else 'warp'}, masks only",
+               lambda w, no_warp=no_warp: ops.crops_fuse(lo_c[0], lo_c[1], None if no_warp else cg, yx, (713, 713), N, no_warp, (1072, 1920),
+                                                         want_canvas=False, want_mask=True, weights=w))
+        st5 = flags([0, 0, 1, 0, 0])
+        t = timed(lambda i: ops.window_weights(st5, N))
+        rows.append(("window_weights, n = 5 (one launch + two allocations, host clock)", 1 / t, t * 1e3))
+        rgb = [torch.randint(0, 256, (1080, 1920, 3), generator=gen, dtype=torch.uint8).to(dev) for _ in range(2)]
+        for search in (8, 16):
+            t = timed(lambda i, search=search: ops.block_match_modes(rgb[0], rgb[1], search=search, intra_bias=0, scene_cut=0.5, return_stats=True))
+            rows.append((f"the closing pair's search per window, 1080x1920 RGB R={search} (block_match_modes, stats only)", 1 / t, t * 1e3))
     del psp
     if want("cfg2"):
         dl3 = FlowDeepLabv3(HP(101)).eval()

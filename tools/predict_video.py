@@ -17,7 +17,10 @@ Under torchrun every rank writes its own window block into the one file (not int
 `--grids estimate` (with `--search`, `--penalty`) takes the grids from block matching of the decoded frames instead of the grids/
 folders; a raw video file (`--raw`, as `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24` writes it) always does.  `--intra-bias N`
 and `--scene-cut F` (both off by default, no value validated on real video) leave blocks the matcher cannot explain, and whole frames
-across a scene cut, on the identity grid; the frames judged cuts and the mean intra share are printed after the run.
+across a scene cut, on the identity grid; the frames judged cuts and the mean intra share are printed after the run.  `--hold-cuts`
+(needs `--scene-cut`; segmentation mode) also makes the blend react: in a window with a cut, a frame before the cut is the previous key
+frame's prediction alone and a frame after it the next key frame's, instead of a mix of two scenes; how many frames were blended and
+held is printed with the rest.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -84,6 +87,8 @@ def parse_args(argv=None):
                     "deviation from its mean + N gets no vector (identity grid cells).  Default: off; the right N depends on the sensor's noise")
     ap.add_argument("--scene-cut", type=float, metavar="F", help="--grids estimate: 0..1; a frame with more than this fraction of such blocks "
                     "gets the default grid (a scene cut).  Default: off.  Counts the blocks --intra-bias marks: without --intra-bias it never fires")
+    ap.add_argument("--hold-cuts", action="store_true", help="--scene-cut: across a detected cut hold one key frame's prediction on each side "
+                    "instead of blending the two scenes (one more block search per window)")
     ap.add_argument("--raw", metavar="FILE", help="raw video input (ffmpeg -f rawvideo) instead of --data-root / --video-id")
     ap.add_argument("--raw-size", type=int, nargs=2, metavar=("H", "W"), help="--raw: frame height and width")
     ap.add_argument("--pix-fmt", choices=("nv12", "i420", "rgb24"), default="nv12", help="--raw: pixel format (i420 = ffmpeg's yuv420p)")
@@ -117,6 +122,10 @@ def parse_args(argv=None):
         args.out_matrix = args.matrix if args.raw else "bt709"
     if args.out_full_range is None:
         args.out_full_range = bool(args.full_range) if args.raw else False
+    if args.hold_cuts and (args.scene_cut is None or args.grids == "files" or (not args.raw and args.grids is None)):
+        ap.error("--hold-cuts needs --scene-cut (and --grids estimate for a frame folder)")
+    if args.hold_cuts and args.feature_based:
+        ap.error("--hold-cuts exists for the segmentation tails only, not for --feature-based")
     if not args.synthetic_weights and not args.ckpt:
         ap.error("give --ckpt or --synthetic-weights")
     if args.raw:
@@ -152,10 +161,11 @@ def main():
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
-                             full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut)
+                             full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut, hold_cuts=args.hold_cuts)
     else:
         ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
-                            grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut)
+                            grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut,
+                            hold_cuts=args.hold_cuts)
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -182,12 +192,15 @@ def main():
     mine = shard.window_block(len(ds), rank, world)
     frames = 0
     first_mask = last_mask = None
+    sources = []  # --hold-cuts: every window's device `source` tensor, read back once after the timed run
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for w in mine:
         item = ds[w]
         masks = pred.predict_window(item["frame_prev"], item["frame_next"], item["mvs_left"], item["mvs_right"], to_host=False,
-                                    key_ids=item["key_ids"])
+                                    key_ids=item["key_ids"], weights=item.get("weights"))
+        if "source" in item:
+            sources.append(item["source"])
         if first_mask is None:
             first_mask = masks[0].clone()
         last_mask = masks[-1]
@@ -231,6 +244,10 @@ def main():
         cuts = [i for i, s in zip(ids, host) if s[2]]
         print(f"rank {rank}: {len(ids)} frame pairs estimated, mean intra share {float((host[:, 1] / host[:, 0]).mean()):.4f}, "
               f"scene cuts at frames {cuts if cuts else 'none'}", file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    if sources:
+        counts = torch.bincount(torch.cat(sources).cpu().long(), minlength=4).tolist()
+        print(f"rank {rank}: --hold-cuts: {counts[0]} frames blended, {counts[1]} held from the previous key frame, {counts[2]} from the next, "
+              f"{counts[3]} between two cuts", file=sys.stderr if args.raw_out == "-" else sys.stdout)
     if world > 1:
         torch.distributed.destroy_process_group()
 
