@@ -147,6 +147,8 @@ _EXT2_HOOKS = [
      + [c_void, c_void, c_void]),
     ("crops_fuse_weighted", c_int, [c_void, c_void, c_void, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)] + [c_int] * 9
      + [c_void, c_void, c_int, c_int, c_void, c_void, c_void]),
+    ("feat_tail_weighted", c_int, [c_void, c_void, c_int, c_int, c_int, ctypes.POINTER(c_void), ctypes.POINTER(c_void), c_int, c_int, c_void, c_int,
+                                   c_int, c_int, c_int, c_void, c_void, c_void, c_void]),
 ]
 EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
 

@@ -368,6 +368,31 @@ static int fs_crops_fuse_weighted(const float* lo_prev, const float* lo_next, co
     p.weights = weights;
     return fs::launch_crops_fuse(p, crop_grids, scratch, S(stream));
 }
+// fs_feat_tail with per-map blend weights: the same launch function, one more pointer
+static int fs_feat_tail_weighted(const float* f_prev, const float* f_next, int C, int fh, int fw, const float* const* grids_left,
+                                 const float* const* grids_right, int Hg, int Wg, const float* grid0, int H0, int W0, int n, int no_warp, float* stack,
+                                 float* scratch, const float* weights, fs_stream stream) {
+    if (!f_prev || !stack || C < 1 || fh < 1 || fw < 1) return fs::fail("fs_feat_tail_weighted: bad arguments");
+    fs::FeatTailParams p{};
+    p.f_prev = f_prev;
+    p.f_next = f_next;
+    p.grids_left = grids_left;
+    p.grids_right = grids_right;
+    p.grid0 = grid0;
+    p.C = C;
+    p.fh = fh;
+    p.fw = fw;
+    p.Hg = Hg;
+    p.Wg = Wg;
+    p.H0 = H0;
+    p.W0 = W0;
+    p.n = n;
+    p.no_warp = no_warp;
+    p.stack = stack;
+    p.scratch = scratch;
+    p.weights = weights;
+    return fs::launch_feat_tail(p, S(stream));
+}
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
     if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
@@ -463,6 +488,7 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_window_weights,
         fs_seg_tail_weighted,
         fs_crops_fuse_weighted,
+        fs_feat_tail_weighted,
     }};
     return &all.base.test;
 }

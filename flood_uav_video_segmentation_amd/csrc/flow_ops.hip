@@ -391,6 +391,11 @@ struct FeatFuseArgs {
     int same_g, same_0;    // the chain / identity maps already have the feature size: the reference skips the resize (:138, :158)
     float sy_g, sx_g, sy_0, sx_0;
 };
+// What only the weighted (DEVW) instantiations read, split off as SegTailParams is from SegFuseArgs: the unweighted kernels keep the
+// kernel-argument segment they had.
+struct FeatFuseWArgs : FeatFuseArgs {
+    const float* weights;  // device [n][2] per-map blend weights (launch_window_weights)
+};
 
 // Two launches write every map of the decoder's batch.  What bounds them is not HBM but the CUs' vector-memory path: with one float4 of
 // one pixel per thread a warped map costs 8 tap loads + 1 store per output (6 GB through the L1s for 0.66 GB written: 430-440 us
@@ -499,7 +504,13 @@ __global__ __launch_bounds__(256) void feat_fuse_key_kernel(FeatFuseArgs a, unsi
 
 // ---- maps 1..n-1: (map, row, run) per thread, S float4 lanes of the XCD's slab side by side.  Its own kernel: 6 waves per SIMD (the
 // key-map kernel holds 16 taps in registers), since what this loop waits for is the latency of its 4-load groups.
-__global__ __launch_bounds__(256, 6) void feat_fuse_warp_kernel(FeatFuseArgs a, int S, int nruns) {
+// DEVW: the two blend weights of map p are weights[2p], weights[2p+1] instead of (n-p)/n, p/n, and a zero weight HOLDS the map, as in
+// seg_fuse_kernel: it is the other chain's value itself (no 0 * x term) and the unused chain's two rows are not loaded -- half the tap
+// loads of a blended map.  Compile-time, and only the DEVW = true instantiation takes the struct with the pointer.
+template <bool DEVW>
+__global__ __launch_bounds__(256, 6) void feat_fuse_warp_kernel(std::conditional_t<DEVW, FeatFuseWArgs, FeatFuseArgs> a, int S, int nruns) {
+    const float* weights = nullptr;
+    if constexpr (DEVW) weights = a.weights;
     const int ld = a.C4 * 4;
     const size_t map = (size_t)a.fh * a.fw * ld;
     const unsigned bid = blockIdx.x;
@@ -512,8 +523,9 @@ __global__ __launch_bounds__(256, 6) void feat_fuse_warp_kernel(FeatFuseArgs a, 
     const int p = 1 + (int)(rowid / (unsigned)a.fh);
     const int oy = (int)(rowid - (unsigned)(p - 1) * (unsigned)a.fh);
     if (p >= a.n || c4 >= a.C4) return;
-    const float wa = (float)((double)(a.n - p) / (double)a.n);
-    const float wb = (float)((double)p / (double)a.n);
+    const float wa = DEVW ? weights[2 * p] : (float)((double)(a.n - p) / (double)a.n);
+    const float wb = DEVW ? weights[2 * p + 1] : (float)((double)p / (double)a.n);
+    const bool hold_a = DEVW && wb == 0.f, hold_b = DEVW && !hold_a && wa == 0.f;  // one key frame's chain alone
     const size_t cmap = (size_t)a.Hg * a.Wg * ld;
     const float* pf = a.chains + (size_t)(p - 1) * cmap + c4 * 4;                  // forward map p-1
     const float* pb = a.chains + (size_t)(a.n - 1 + a.n - p - 1) * cmap + c4 * 4;  // backward map n-p-1
@@ -521,11 +533,12 @@ __global__ __launch_bounds__(256, 6) void feat_fuse_warp_kernel(FeatFuseArgs a, 
     const int x0 = run * FEAT_RUN, x1 = min(a.fw, x0 + FEAT_RUN);
     if (a.same_g) {
         for (int ox = x0; ox < x1; ++ox) {
-            const f32x4 va = *reinterpret_cast<const f32x4*>(pf + ((size_t)oy * a.Wg + ox) * ld);
-            const f32x4 vb = *reinterpret_cast<const f32x4*>(pb + ((size_t)oy * a.Wg + ox) * ld);
+            f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = va;  // a held map leaves the unused one unread
+            if (!hold_b) va = *reinterpret_cast<const f32x4*>(pf + ((size_t)oy * a.Wg + ox) * ld);
+            if (!hold_a) vb = *reinterpret_cast<const f32x4*>(pb + ((size_t)oy * a.Wg + ox) * ld);
             f32x4 r;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) r[q] = __fadd_rn(__fmul_rn(wa, va[q]), __fmul_rn(wb, vb[q]));
+            for (int q = 0; q < 4; ++q) r[q] = hold_a ? va[q] : hold_b ? vb[q] : __fadd_rn(__fmul_rn(wa, va[q]), __fmul_rn(wb, vb[q]));
             *reinterpret_cast<f32x4*>(dst + (size_t)ox * ld) = r;
         }
         return;
@@ -546,10 +559,14 @@ __global__ __launch_bounds__(256, 6) void feat_fuse_warp_kernel(FeatFuseArgs a, 
 #define FS_FEAT_LOAD(S_, col_)                                        \
     do {                                                              \
         const size_t o_ = (size_t)(col_) * ld;                        \
-        S_##f0 = *reinterpret_cast<const f32x4*>(f0 + o_);            \
-        S_##f1 = *reinterpret_cast<const f32x4*>(f1 + o_);            \
-        S_##b0 = *reinterpret_cast<const f32x4*>(b0 + o_);            \
-        S_##b1 = *reinterpret_cast<const f32x4*>(b1 + o_);            \
+        if (!hold_b) {                                                \
+            S_##f0 = *reinterpret_cast<const f32x4*>(f0 + o_);        \
+            S_##f1 = *reinterpret_cast<const f32x4*>(f1 + o_);        \
+        }                                                             \
+        if (!hold_a) {                                                \
+            S_##b0 = *reinterpret_cast<const f32x4*>(b0 + o_);        \
+            S_##b1 = *reinterpret_cast<const f32x4*>(b1 + o_);        \
+        }                                                             \
     } while (0)
     const f32x2 wy0 = {cy.w0, cy.w0}, wy1 = {cy.w1, cy.w1}, wa2 = {wa, wa}, wb2 = {wb, wb};
     for (int ox = x0; ox < x1; ++ox) {
@@ -570,7 +587,7 @@ __global__ __launch_bounds__(256, 6) void feat_fuse_warp_kernel(FeatFuseArgs a, 
         const f32x2 tf = wxA * Af0.h_ + wxB * Bf0.h_, bf = wxA * Af1.h_ + wxB * Bf1.h_;       \
         const f32x2 tb = wxA * Ab0.h_ + wxB * Bb0.h_, bb = wxA * Ab1.h_ + wxB * Bb1.h_;       \
         const f32x2 va = wy0 * tf + wy1 * bf, vb = wy0 * tb + wy1 * bb;                       \
-        r.h_ = wa2 * va + wb2 * vb;                                                           \
+        r.h_ = hold_a ? va : hold_b ? vb : wa2 * va + wb2 * vb;                               \
     } while (0)
         FS_FEAT_HALF(lo);
         FS_FEAT_HALF(hi);
@@ -582,8 +599,15 @@ __global__ __launch_bounds__(256, 6) void feat_fuse_warp_kernel(FeatFuseArgs a, 
 
 // no_warp: every map is a blend of the two key-frame maps -- each float4 of f_prev / f_next is read ONCE and all n maps written from it
 // (a launch per map, or a map per blockIdx.y, re-reads 2 x 133 MB per map: 1.9 GB moved for 0.66 GB written).
+// DEVW: map p >= 1 blends with weights[2p], weights[2p+1], and a zero weight makes it the bits of x or of y (as in
+// feat_fuse_warp_kernel); map 0 never reads its weights.  The unweighted instantiation keeps its argument list (W is empty); the
+// weighted one takes the extended struct behind it and reads only `weights` of it.
+template <bool DEVW, typename... W>
 __global__ __launch_bounds__(256) void feat_fuse_nowarp_kernel(const float* __restrict__ f_prev, const float* __restrict__ f_next,
-                                                               float* __restrict__ stack, unsigned total4, int n, int nmaps) {
+                                                               float* __restrict__ stack, unsigned total4, int n, int nmaps, W... w) {
+    static_assert(sizeof...(W) == (DEVW ? 1 : 0), "the weighted instantiation takes one FeatFuseWArgs");
+    const float* weights = nullptr;
+    if constexpr (DEVW) weights = (w.weights, ...);
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= total4) return;
     const f32x4 x = reinterpret_cast<const f32x4*>(f_prev)[i];
@@ -594,10 +618,11 @@ __global__ __launch_bounds__(256) void feat_fuse_nowarp_kernel(const float* __re
     if (nmaps == 1) return;
     const f32x4 y = reinterpret_cast<const f32x4*>(f_next)[i];
     for (int p = 1; p < n; ++p) {
-        const float wa = (float)((double)(n - p) / (double)n);
-        const float wb = (float)((double)p / (double)n);
+        const float wa = DEVW ? weights[2 * p] : (float)((double)(n - p) / (double)n);
+        const float wb = DEVW ? weights[2 * p + 1] : (float)((double)p / (double)n);
+        const bool hold_a = DEVW && wb == 0.f, hold_b = DEVW && !hold_a && wa == 0.f;  // uniform
 #pragma unroll
-        for (int q = 0; q < 4; ++q) r[q] = __fadd_rn(__fmul_rn(wa, x[q]), __fmul_rn(wb, y[q]));
+        for (int q = 0; q < 4; ++q) r[q] = hold_a ? x[q] : hold_b ? y[q] : __fadd_rn(__fmul_rn(wa, x[q]), __fmul_rn(wb, y[q]));
         reinterpret_cast<f32x4*>(stack)[(size_t)p * total4 + i] = r;
     }
 }
@@ -611,6 +636,9 @@ int launch_feat_tail(const FeatTailParams& p, hipStream_t s) {
     FS_REQUIRE(total < ((int64_t)1 << 31), "feat_tail: feature map of at most 2^31 float4 elements");
     const bool warp = !p.no_warp;
     const int nmaps = p.f_next ? p.n : 1;
+    const float* weights = nmaps > 1 ? p.weights : nullptr;  // a single map reads no weights
+    // feat_cell keeps the key map's tap offsets as 32-bit element offsets into f_prev
+    FS_REQUIRE(!warp || (int64_t)p.fh * p.fw * p.C < ((int64_t)1 << 32), "feat_tail: warp mode takes feature maps of fewer than 2^32 elements");
     FeatFuseArgs a{};
     a.f_prev = p.f_prev;
     a.f_next = p.f_next;
@@ -632,6 +660,8 @@ int launch_feat_tail(const FeatTailParams& p, hipStream_t s) {
             FS_REQUIRE(p.scratch && p.grids_left && p.grids_right && p.Hg >= 1 && p.Wg >= 1, "feat_tail: warp mode needs grids and scratch");
             const int64_t gtotal = (int64_t)p.Hg * p.Wg * C4;
             FS_REQUIRE(gtotal < ((int64_t)1 << 31), "feat_tail: grid too large");
+            for (int j = 0; j < p.n - 1; ++j)
+                FS_REQUIRE(p.grids_left[j] && p.grids_right[j], "feat_tail: grid %d of a direction is a null pointer", j);
             const size_t cmap = (size_t)p.Hg * p.Wg * p.C;
             float* fwd = p.scratch;
             float* bwd = p.scratch + (size_t)(p.n - 1) * cmap;
@@ -650,9 +680,15 @@ int launch_feat_tail(const FeatTailParams& p, hipStream_t s) {
             a.sx_g = resize_scale(p.Wg, p.fw, 1);
         }
     }
+    FeatFuseWArgs aw{};
+    static_cast<FeatFuseArgs&>(aw) = a;
+    aw.weights = weights;
     if (!warp) {
-        hipLaunchKernelGGL(feat_fuse_nowarp_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, s, p.f_prev, p.f_next, p.stack, (unsigned)total, p.n,
-                           nmaps);
+        const dim3 grid((unsigned)cdiv64(total, 256));
+        if (weights)
+            hipLaunchKernelGGL((feat_fuse_nowarp_kernel<true, FeatFuseWArgs>), grid, dim3(256), 0, s, p.f_prev, p.f_next, p.stack, (unsigned)total, p.n, nmaps,
+                               aw);
+        else hipLaunchKernelGGL(feat_fuse_nowarp_kernel<false>, grid, dim3(256), 0, s, p.f_prev, p.f_next, p.stack, (unsigned)total, p.n, nmaps);
         FS_HIP(hipGetLastError());
         return 0;
     }
@@ -665,7 +701,10 @@ int launch_feat_tail(const FeatTailParams& p, hipStream_t s) {
     const int LP = cdiv(S, FEAT_KEY_CH);
     const unsigned blocks0 = 8u * (unsigned)cdiv64(npix * LP, 256);
     hipLaunchKernelGGL(feat_fuse_key_kernel, dim3(blocks0), dim3(256), 0, s, a, (unsigned)npix, S, LP);
-    if (blocks1) hipLaunchKernelGGL(feat_fuse_warp_kernel, dim3(blocks1), dim3(256), 0, s, a, S, nruns);
+    if (blocks1) {
+        if (weights) hipLaunchKernelGGL(feat_fuse_warp_kernel<true>, dim3(blocks1), dim3(256), 0, s, aw, S, nruns);
+        else hipLaunchKernelGGL(feat_fuse_warp_kernel<false>, dim3(blocks1), dim3(256), 0, s, a, S, nruns);
+    }
     FS_HIP(hipGetLastError());
     return 0;
 }

@@ -235,6 +235,8 @@ struct FeatTailParams {
     int C, fh, fw, Hg, Wg, H0, W0, n, no_warp;
     float* stack;           // NHWC [n | 1][fh][fw][C]: the decoder's batch
     float* scratch;         // >= 2*(n-1)*Hg*Wg*C floats when warping with two key frames
+    const float* weights;   // device [n][2] per-map blend weights (launch_window_weights), or nullptr: (n-p)/n and p/n; read only when
+                            // f_next is given and n > 1
 };
 int launch_feat_tail(const FeatTailParams& p, hipStream_t s);
 

@@ -245,9 +245,13 @@ class FlowModel(nn.Module):
 
     def predict_feature(self, frame_prev, frame_next, mvs_left, mvs_right, n, profiler=None, key_cache=None, with_mask=False, weights=None):
         """Propagate encoder FEATURES, decode all n maps in one batch (reference :116-181).  with_mask: as in predict_segmentation.
-        weights: not supported -- the feature tail (fs_feat_tail) blends with (n-f)/n, f/n only; anything but None raises."""
-        if weights is not None:
-            raise NotImplementedError("FlowModel.predict_feature: per-frame blend weights (hold_cuts) exist for the segmentation tails only")
+        weights (extension): as predict_segmentation's, served by the fused tail (fs_feat_tail_weighted): map p of the decoder's batch
+        blends the two feature chains with its row, and a row with a zero holds one key frame's chain.  The op-by-op route has no
+        weighted form: with fused_feature_tail = False, or a network that is not a HIP mirror (no `encode_frames`, whose NHWC fp32
+        features the fused tail takes), anything but None raises -- before the encoder runs."""
+        if weights is not None and not (self.fused_feature_tail and hasattr(self.model, "encode_frames")):
+            raise NotImplementedError("FlowModel.predict_feature: per-frame blend weights (hold_cuts) exist for the segmentation tails and "
+                                      "the fused feature tail only (fused_feature_tail = True and a HIP mirror that offers encode_frames)")
         h, w = frame_prev.shape[2], frame_prev.shape[3]
         with _region(profiler, "predict_encoder"):
             f, f_next = self._key_outputs(self._encode, self._tag("feat", h, w), frame_prev, frame_next, key_cache)
@@ -261,10 +265,14 @@ class FlowModel(nn.Module):
             if not self.no_warp and self.default_motion_vector.device != f.device:
                 self.default_motion_vector = self.default_motion_vector.to(device=f.device)
             with _region(profiler, "predict_warp"), _region(profiler, "predict_fusion"):
-                stack = ops.feat_tail(f, f_next, mvs_left, mvs_right, n, self.no_warp, None if self.no_warp else self.default_motion_vector)
+                stack = ops.feat_tail(f, f_next, mvs_left, mvs_right, n, self.no_warp, None if self.no_warp else self.default_motion_vector,
+                                      weights=weights)
             with _region(profiler, "predict_decoder"):
                 out, mask = self._decode_fit(stack, h, w, with_mask)
             return {"pred": out, "mask": mask} if with_mask else {"pred": out}
+        if weights is not None:  # a mirror whose features the fused tail cannot take: never blend where a hold was asked for
+            raise NotImplementedError("FlowModel.predict_feature: per-frame blend weights (hold_cuts) need the fused feature tail, which takes "
+                                      f"NHWC fp32 features of one frame with C % 4 == 0; the encoder gave {tuple(f.shape)} {f.dtype}")
         stack = (ops.empty_nhwc(nmaps, f.shape[1], f_h, f_w, f.device) if nhwc else
                  torch.empty((nmaps, f.shape[1], f_h, f_w), dtype=torch.float32, device=f.device))
         fwd, bwd = [], []

@@ -214,10 +214,12 @@ def seg_tail(lo_prev, lo_next, grids_left, grids_right, n, out_hw, no_warp, want
     return logits, mask
 
 
-def feat_tail(f_prev, f_next, grids_left, grids_right, n, no_warp, default_grid=None):
+def feat_tail(f_prev, f_next, grids_left, grids_right, n, no_warp, default_grid=None, weights=None):
     """Fused predict_feature tail (flow/model.py:131-171 between the encoder and the batched decoder call): f_prev / f_next
     [1,C,fh,fw] stored channels_last; grids: lists of n-1 [1,Hg,Wg,2]; default_grid [1,H0,W0,2] (warp mode).  Returns the decoder's
-    batch [n,C,fh,fw] ([1,C,fh,fw] when f_next is None), channels_last -- bit-identical to the op-by-op route."""
+    batch [n,C,fh,fw] ([1,C,fh,fw] when f_next is None), channels_last -- bit-identical to the op-by-op route.
+    weights: None (map p blends the two chains with (n-p)/n and p/n), or window_weights' device [n,2] tensor: map p >= 1 blends with
+    its row, and a row with a zero HOLDS the map -- it is the other key frame's chain, bit for bit, and the unused one is not read."""
     lib = _lib.load()
     warp = not no_warp
     grids = list(grids_left) + list(grids_right) if (warp and f_next is not None) else []
@@ -230,6 +232,7 @@ def feat_tail(f_prev, f_next, grids_left, grids_right, n, no_warp, default_grid=
         raise RuntimeError("floodseg.feat_tail: C must be a multiple of 4")
     if f_next is not None and f_next.shape != f_prev.shape:
         raise RuntimeError("floodseg.feat_tail: f_prev / f_next shapes differ")
+    weights = _window_weights_arg(weights, n, dev, "floodseg.feat_tail")
     with torch.cuda.device(dev):
         nmaps = n if f_next is not None else 1
         stack = empty_nhwc(nmaps, c, fh, fw, dev)
@@ -255,8 +258,12 @@ def feat_tail(f_prev, f_next, grids_left, grids_right, n, no_warp, default_grid=
                 gl = _ptr_array(keep[: n - 1])
                 gr = _ptr_array(keep[n - 1:])
                 scratch = torch.empty(2 * (n - 1) * hg * wg * c, dtype=torch.float32, device=dev)
-        check(lib.fs_feat_tail(ptr(f_prev), ptr(f_next), c, fh, fw, gl, gr, hg, wg, ptr(g0), h0, w0, int(n), int(bool(no_warp)), ptr(stack),
-                               ptr(scratch), stream_ptr()))
+        if weights is None:
+            check(lib.fs_feat_tail(ptr(f_prev), ptr(f_next), c, fh, fw, gl, gr, hg, wg, ptr(g0), h0, w0, int(n), int(bool(no_warp)), ptr(stack),
+                                   ptr(scratch), stream_ptr()))
+        else:
+            check(lib.fs_feat_tail_weighted(ptr(f_prev), ptr(f_next), c, fh, fw, gl, gr, hg, wg, ptr(g0), h0, w0, int(n), int(bool(no_warp)),
+                                            ptr(stack), ptr(scratch), ptr(weights), stream_ptr()))
     return stack
 
 

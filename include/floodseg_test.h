@@ -6,8 +6,8 @@
  * also carries EXTENSION OPS: product features that have no reference call site (block matching, flow/motion.py) and therefore no
  * place in the capped export list of floodseg.h; the Python package reaches them like any other function.  fs_test_api is frozen at
  * block_match; later extension ops (frame ingest, frame egress) are members of fs_ext_api, the table right behind it, and the ones
- * after those (block_match_modes, window_weights, seg_tail_weighted, crops_fuse_weighted) of fs_ext2_api, the table behind both (end of
- * this file).
+ * after those (block_match_modes, window_weights, seg_tail_weighted, crops_fuse_weighted, feat_tail_weighted) of fs_ext2_api, the table
+ * behind both (end of this file).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table was append-only up to block_match and is frozen now; `size` is sizeof(fs_test_api)
@@ -337,6 +337,21 @@ typedef struct fs_ext2_api {
     int (*crops_fuse_weighted)(const float* lo_prev, const float* lo_next, const float* crop_grids, int ncrops, const int* crop_y,
                                const int* crop_x, int K, int h, int w, int Hg, int Wg, int ch, int cw, int n, int no_warp, double* canvas,
                                uint8_t* mask, int H, int W, float* scratch, const float* weights, fs_stream stream);
+
+    /* fs_feat_tail (floodseg.h) with the same per-frame weights: its arguments, then weights (device float [n][2] as window_weights
+     * writes it, or NULL: the result of fs_feat_tail, bit for bit, through the same launch function).  For map p >= 1 of the decoder's
+     * batch with (wa, wb) = weights[2p], weights[2p+1]:
+     *   wb == 0: r = va;   else wa == 0: r = vb;   else r = fadd_rn(fmul_rn(wa, va), fmul_rn(wb, vb))
+     * va / vb being the previous / next key frame's value at that element: in warp mode the upsampled forward map p-1 / backward map
+     * n-p-1 of the warp chains (the map itself when the grid has the feature size), with no_warp f_prev / f_next.  A held map is exactly
+     * one chain's value: no 0 * x term, so neither the sign of a zero nor a NaN / Inf of the unused chain reaches it, and in warp mode
+     * the unused chain's rows are not read (half the tap loads of a blended map).  Map 0 never reads its weights (the key map through
+     * the default grid, or 1 * f_prev with no_warp); both warp chains are still computed; weights is ignored when f_next == NULL or
+     * n == 1.  Refused before a launch, here and by fs_feat_tail: a NULL entry among the n-1 grids of a direction (warp mode, two key
+     * frames), and fh * fw * C >= 2^32 in warp mode (the key map's tap offsets are 32-bit element offsets). */
+    int (*feat_tail_weighted)(const float* f_prev, const float* f_next, int C, int fh, int fw, const float* const* grids_left,
+                              const float* const* grids_right, int Hg, int Wg, const float* grid0, int H0, int W0, int n, int no_warp,
+                              float* stack, float* scratch, const float* weights, fs_stream stream);
 } fs_ext2_api;
 
 typedef struct fs_hook_tables2 {

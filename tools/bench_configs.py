@@ -294,7 +294,7 @@ def main():
                 t = timeit(item_step, steps=6, warmup=2)
                 rows.append((f"PredictWindows item, grids=estimate, JPEG folder (host-bound), {label}", 1 / t, t * 1e3))
     if want("cuts"):
-        # holding one key frame across a scene cut (ops.window_weights, the weighted instantiations of the two fused tails): the weighted
+        # holding one key frame across a scene cut (ops.window_weights, the weighted instantiations of the fused tails): the weighted
         # call against the unweighted one on the same held logits, alternating (three rounds each, the fastest of each side), every loop
         # >= 0.5 s; weights of a window without a cut (the same blend) and of one cut in its middle (held frames read ONE chain).  Then
         # what a window pays for its weights: one window_weights launch and the closing pair's search.
@@ -331,6 +331,15 @@ def main():
             ab(f"crops_fuse 1072x1920, {len(yx)} crops of 713x713, {'no_warp' if no_warp else 'warp'}, masks only",
                lambda w, no_warp=no_warp: ops.crops_fuse(lo_c[0], lo_c[1], None if no_warp else cg, yx, (713, 713), N, no_warp, (1072, 1920),
                                                          want_canvas=False, want_mask=True, weights=w))
+        # the feature tail (fs_feat_tail against feat_tail_weighted): PSPNet's maps at 713^2 and the Segmenter's token map, warp mode,
+        # 44 x 44 grids, the 67 x 120 default grid
+        from flood_uav_video_segmentation_amd.flow.model import get_default_grid
+        g0 = torch.from_numpy(get_default_grid()).float().unsqueeze(0).to(dev)
+        for label, C, fs in (("PSPNet", 4096, 90), ("Segmenter", 384, 45)):
+            ft = [(torch.randn((1, C, fs, fs), generator=gen) * 3).to(dev).contiguous(memory_format=torch.channels_last) for _ in range(2)]
+            ab(f"feat_tail {label} geometry (C {C}, {fs}x{fs} maps, 44x44 grids, n {N}), warp",
+               lambda w, ft=ft: ops.feat_tail(ft[0], ft[1], wl, wr, N, False, g0, weights=w))
+            del ft
         st5 = flags([0, 0, 1, 0, 0])
         t = timed(lambda i: ops.window_weights(st5, N))
         rows.append(("window_weights, n = 5 (one launch + two allocations, host clock)", 1 / t, t * 1e3))

@@ -18,9 +18,10 @@ Under torchrun every rank writes its own window block into the one file (not int
 folders; a raw video file (`--raw`, as `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24` writes it) always does.  `--intra-bias N`
 and `--scene-cut F` (both off by default, no value validated on real video) leave blocks the matcher cannot explain, and whole frames
 across a scene cut, on the identity grid; the frames judged cuts and the mean intra share are printed after the run.  `--hold-cuts`
-(needs `--scene-cut`; segmentation mode) also makes the blend react: in a window with a cut, a frame before the cut is the previous key
-frame's prediction alone and a frame after it the next key frame's, instead of a mix of two scenes; how many frames were blended and
-held is printed with the rest.
+(needs `--scene-cut`; segmentation mode and `--feature-based` alike) also makes the blend react: in a window with a cut, a frame before
+the cut is the previous key frame's prediction alone and a frame after it the next key frame's, instead of a mix of two scenes (in
+feature mode: the decoder sees one key frame's warped features, not a mixture); how many frames were blended and held is printed with
+the rest.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -88,7 +89,7 @@ def parse_args(argv=None):
     ap.add_argument("--scene-cut", type=float, metavar="F", help="--grids estimate: 0..1; a frame with more than this fraction of such blocks "
                     "gets the default grid (a scene cut).  Default: off.  Counts the blocks --intra-bias marks: without --intra-bias it never fires")
     ap.add_argument("--hold-cuts", action="store_true", help="--scene-cut: across a detected cut hold one key frame's prediction on each side "
-                    "instead of blending the two scenes (one more block search per window)")
+                    "instead of blending the two scenes, logits or (--feature-based) encoder features (one more block search per window)")
     ap.add_argument("--raw", metavar="FILE", help="raw video input (ffmpeg -f rawvideo) instead of --data-root / --video-id")
     ap.add_argument("--raw-size", type=int, nargs=2, metavar=("H", "W"), help="--raw: frame height and width")
     ap.add_argument("--pix-fmt", choices=("nv12", "i420", "rgb24"), default="nv12", help="--raw: pixel format (i420 = ffmpeg's yuv420p)")
@@ -124,8 +125,6 @@ def parse_args(argv=None):
         args.out_full_range = bool(args.full_range) if args.raw else False
     if args.hold_cuts and (args.scene_cut is None or args.grids == "files" or (not args.raw and args.grids is None)):
         ap.error("--hold-cuts needs --scene-cut (and --grids estimate for a frame folder)")
-    if args.hold_cuts and args.feature_based:
-        ap.error("--hold-cuts exists for the segmentation tails only, not for --feature-based")
     if not args.synthetic_weights and not args.ckpt:
         ap.error("give --ckpt or --synthetic-weights")
     if args.raw:
