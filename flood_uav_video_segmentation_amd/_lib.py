@@ -149,6 +149,9 @@ _EXT2_HOOKS = [
      + [c_void, c_void, c_int, c_int, c_void, c_void, c_void]),
     ("feat_tail_weighted", c_int, [c_void, c_void, c_int, c_int, c_int, ctypes.POINTER(c_void), ctypes.POINTER(c_void), c_int, c_int, c_void, c_int,
                                    c_int, c_int, c_int, c_void, c_void, c_void, c_void]),
+    ("mask_confidence", c_int, [c_void] + [c_int] * 4 + [c_void, c_void, c_int, c_int, c_void]),
+    ("canvas_confidence", c_int, [c_void] + [c_int] * 4 + [c_void, c_void, c_int, c_int, c_void]),
+    ("frame_report", c_int, [c_void, c_void] + [c_int] * 5 + [c_void, c_void]),
 ]
 EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
 

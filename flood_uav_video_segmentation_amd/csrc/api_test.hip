@@ -393,6 +393,16 @@ static int fs_feat_tail_weighted(const float* f_prev, const float* f_next, int C
     p.weights = weights;
     return fs::launch_feat_tail(p, S(stream));
 }
+// per-pixel confidence and the per-frame extent report (conf_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_mask_confidence(const float* logits, int n, int K, int h, int w, uint8_t* mask, uint8_t* confidence, int H, int W, fs_stream stream) {
+    return fs::launch_mask_confidence(logits, n, K, h, w, mask, confidence, H, W, S(stream));
+}
+static int fs_canvas_confidence(const double* canvas, int n, int K, int h, int w, uint8_t* mask, uint8_t* confidence, int H, int W, fs_stream stream) {
+    return fs::launch_canvas_confidence(canvas, n, K, h, w, mask, confidence, H, W, S(stream));
+}
+static int fs_frame_report(const uint8_t* mask, const uint8_t* confidence, int n, int H, int W, int K, int low, int64_t* report, fs_stream stream) {
+    return fs::launch_frame_report(mask, confidence, n, H, W, K, low, reinterpret_cast<long long*>(report), S(stream));
+}
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
     if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
@@ -489,6 +499,9 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_seg_tail_weighted,
         fs_crops_fuse_weighted,
         fs_feat_tail_weighted,
+        fs_mask_confidence,
+        fs_canvas_confidence,
+        fs_frame_report,
     }};
     return &all.base.test;
 }

@@ -343,6 +343,13 @@ int launch_frame_compose(const uint8_t* mask, int h, int w, const uint8_t* palet
 // intersection / union / target histograms (util/util.py:52-63), int64[3][K] accumulated.
 int launch_iou_hist(const uint8_t* pred, const uint8_t* target, int64_t numel, int K, int ignore_index,
                     long long* hist3K, hipStream_t s);
+// Per-pixel confidence and the per-frame extent report (conf_ops.hip; definitions: include/floodseg_test.h).  Each launcher refuses
+// null pointers, sizes < 1, K out of range (1..32 for logits, 1..255 otherwise) and planes of 2^31 elements before any launch.
+// mask / conf: uint8 [n][H][W] at any byte address.
+int launch_mask_confidence(const float* logits, int n, int K, int h, int w, uint8_t* mask, uint8_t* conf, int H, int W, hipStream_t s);
+int launch_canvas_confidence(const double* canvas, int n, int K, int Hi, int Wi, uint8_t* mask, uint8_t* conf, int Ho, int Wo, hipStream_t s);
+// out: int64 [n][K][3] = (pixels, sum of confidence codes, pixels with code < low), written whole; conf == nullptr: counts only
+int launch_frame_report(const uint8_t* mask, const uint8_t* conf, int n, int H, int W, int K, int low, long long* out, hipStream_t s);
 
 
 // ---------------------------------------------------------------------------------

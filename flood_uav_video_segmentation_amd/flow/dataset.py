@@ -310,6 +310,7 @@ class EvalWindows(PredictWindows):
 
 
 RAW_PIX_FMTS = ("nv12", "i420", "rgb24")
+RAW_OUT_PIX_FMTS = RAW_PIX_FMTS + ("gray",)  # the writer also takes one 8-bit plane per frame (ffmpeg -pix_fmt gray): confidence planes
 
 
 raw_frame_bytes = ops.raw_frame_bytes  # bytes of one frame of a headerless raw video; chroma planes of the 4:2:0 formats round up
@@ -389,8 +390,8 @@ class RawVideoWindows(PredictWindows):
 
 
 class RawVideoWriter:
-    """Writes headerless raw video frames (what `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24 -s WxH` reads): the output side of
-    RawVideoWindows.  write(frame_id, buffer) takes one frame of raw_frame_bytes(height, width, pix_fmt) bytes -- a uint8 device
+    """Writes headerless raw video frames (what `ffmpeg -f rawvideo -pix_fmt nv12|yuv420p|rgb24|gray -s WxH` reads): the output side of
+    RawVideoWindows ("gray": one 8-bit plane per frame, the confidence planes of FlowPredictor(confidence=True)).  write(frame_id, buffer) takes one frame of raw_frame_bytes(height, width, pix_fmt) bytes -- a uint8 device
     tensor (ops.compose_frame's `out` buffer) or a host numpy array / tensor.
 
     A REGULAR FILE is written by position: frame i goes to byte i * frame_bytes (os.pwrite), in any order, and `frames` pre-sizes the
@@ -407,8 +408,8 @@ class RawVideoWriter:
         import stat
         import sys
 
-        if pix_fmt not in RAW_PIX_FMTS:
-            raise ValueError(f"RawVideoWriter: pix_fmt must be one of {RAW_PIX_FMTS}, got {pix_fmt!r}")
+        if pix_fmt not in RAW_OUT_PIX_FMTS:
+            raise ValueError(f"RawVideoWriter: pix_fmt must be one of {RAW_OUT_PIX_FMTS}, got {pix_fmt!r}")
         if height < 1 or width < 1 or (frames is not None and frames < 0):
             raise ValueError(f"RawVideoWriter: bad geometry {height} x {width}, frames {frames}")
         self.height, self.width, self.pix_fmt = int(height), int(width), pix_fmt

@@ -4,6 +4,11 @@ FlowBaseModel.predict_step / on_predict_end (flow/base.py:236-343) without Light
     p = FlowPredictor(flow_model, classes=5, out_size=(1072, 1920), crop=None)
     masks = p.predict_window(frame_prev, frame_next, mvs_left, mvs_right)   # uint8 numpy [n, 1072, 1920]
     p.temporal_consistency()                                               # mIoU / mAcc / accuracy between consecutive frames
+
+Extension (no reference counterpart): FlowPredictor(..., confidence=True) also returns a uint8 confidence plane per mask and keeps a
+per-frame, per-class extent report on the device (ops.mask_confidence / canvas_confidence / frame_report):
+    masks, conf = p.predict_window(...)
+    p.extent_report()                                                      # int64 [frames, K, 3], read back once
 """
 import numpy as np
 import torch
@@ -18,10 +23,19 @@ PALETTE = np.array([[0, 0, 0], [30, 95, 170], [65, 117, 5], [212, 98, 1], [255, 
 class FlowPredictor:
     """cache_keyframes=True + `key_ids=(prev_frame_id, next_frame_id)` in predict_window: the network output of the previous
     window's `frame_next` is reused when it is this window's `frame_prev` (flow/dataset.py:112-114 builds consecutive windows
-    that way), so a video costs one new key-frame inference per window; masks are bit-identical to the uncached run."""
+    that way), so a video costs one new key-frame inference per window; masks are bit-identical to the uncached run.
+
+    confidence=True (extension): predict_window returns, and predict_clip yields, (masks, conf) -- conf uint8 [n,H,W], 255 x the
+    probability of the emitted class (the softmax of the frame's logits on the whole-frame route, the crop-averaged probability on
+    the sliding-crop route).  The masks are the confidence=False masks bit for bit; they come from the same launch as the confidence,
+    which needs the window's logits / canvas written out once (the masks-only tails skip that).  Every window's per-class report
+    (pixels, sum of confidence codes, pixels with confidence < low_confidence) goes into rows of chunked device buffers; nothing is
+    read back until extent_report()."""
+
+    REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
-                 cache_keyframes=False):
+                 cache_keyframes=False, confidence=False, low_confidence=128):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -33,13 +47,54 @@ class FlowPredictor:
         self.ignore_index = ignore_index
         self.last_output = None  # flow/base.py:247, :295
         self.hist = None         # int64[3,K]: intersection, |pred|, |target| accumulated over the run
+        if not 0 <= int(low_confidence) <= 255:
+            raise ValueError(f"FlowPredictor: low_confidence must be 0..255, got {low_confidence}")
+        self.confidence = bool(confidence)
+        self.low_confidence = int(low_confidence)
+        self._report_chunks = []  # int64 [REPORT_CHUNK, K, 3] device buffers, filled in frame order
+        self._report_frames = 0
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
-        its predecessor, flow/base.py:247,295 -- which must not be another video's last frame).  The histogram keeps running."""
+        its predecessor, flow/base.py:247,295 -- which must not be another video's last frame).  The histogram keeps running, and
+        so does the extent report (clear_report() drops it)."""
         if self.key_cache is not None:
             self.key_cache.clear()
         self.last_output = None
+
+    def clear_report(self):
+        """Forget the extent report of the frames predicted so far."""
+        self._report_chunks = []
+        self._report_frames = 0
+
+    def extent_report(self):
+        """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
+        the windows were predicted: per class the pixels, the sum of their confidence codes (mean confidence = sum / (255 pixels))
+        and the pixels with confidence < low_confidence.  ONE read-back, here."""
+        if not self._report_chunks:
+            return np.zeros((0, self.classes, 3), dtype=np.int64)
+        return torch.cat(self._report_chunks)[:self._report_frames].cpu().numpy()
+
+    def _keep_report(self, masks, conf):
+        """The window's report into the next rows of the chunked buffers (frame_report writes its rows whole; nothing is read)."""
+        done, n = 0, masks.shape[0]
+        while done < n:
+            row = self._report_frames % self.REPORT_CHUNK
+            if row == 0:
+                self._report_chunks.append(torch.zeros((self.REPORT_CHUNK, self.classes, 3), dtype=torch.int64, device=masks.device))
+            take = min(n - done, self.REPORT_CHUNK - row)
+            ops.frame_report(masks[done:done + take], conf[done:done + take], self.classes, self.low_confidence,
+                             out=self._report_chunks[-1][row:row + take])
+            done += take
+            self._report_frames += take
+
+    def _finish(self, masks, conf, n, to_host):
+        """Score, keep the report, and hand out what the caller asked for: masks, or (masks, conf) with confidence=True."""
+        self._score(masks, n)
+        if not self.confidence:
+            return masks.cpu().numpy() if to_host else masks            # :277
+        self._keep_report(masks, conf)
+        return (masks.cpu().numpy(), conf.cpu().numpy()) if to_host else (masks, conf)
 
     def predict_window(self, frame_prev, frame_next, mvs_left, mvs_right, profiler=None, to_host=True, key_ids=None, key_cache=None,
                        weights=None):
@@ -52,7 +107,19 @@ class FlowPredictor:
         n = len(mvs_left) + 1                                # :266 -- the list length encodes n, also for no_warp dummies
         cache = key_cache if key_cache is not None else self.key_cache
         kc = cache.window(*key_ids) if (cache is not None and key_ids is not None) else None
-        if self.crop is None:
+        conf = None
+        if self.confidence and self.crop is None:
+            extra = {} if kc is None else {"key_cache": kc}
+            if weights is not None:
+                extra["weights"] = weights
+            logits = self.model.predict(frame_prev, frame_next, mvs_left, mvs_right, n, profiler, **extra)["pred"]
+            masks, conf = ops.mask_confidence(logits, self.out_size)   # :275-276 and the winning class's softmax, one launch
+        elif self.confidence:
+            canvas = crops.compute_output(self.model, n, frame_prev, frame_next, mvs_left, mvs_right, self.crop[0], self.crop[1],
+                                          self.classes, profiler, want_mask=False, key_cache=kc, out_size=self.out_size, want_canvas=True,
+                                          weights=weights)
+            masks, conf = ops.canvas_confidence(canvas, self.out_size)
+        elif self.crop is None:
             extra = {} if kc is None else {"key_cache": kc}
             if weights is not None:
                 extra["weights"] = weights
@@ -69,8 +136,7 @@ class FlowPredictor:
             _, masks = crops.compute_output(self.model, n, frame_prev, frame_next, mvs_left, mvs_right, self.crop[0], self.crop[1],
                                             self.classes, profiler, want_mask=True, key_cache=kc, out_size=self.out_size, want_canvas=False,
                                             weights=weights)
-        self._score(masks, n)
-        return masks.cpu().numpy() if to_host else masks                # :277
+        return self._finish(masks, conf, n, to_host)
 
     def _native(self, frame):
         return self.out_size == (frame.shape[2], frame.shape[3])
@@ -128,7 +194,17 @@ class FlowPredictor:
             n = len(w["mvs_left"]) + 1
             lo_prev, lo_next = store[w["key_ids"][0]], store[w["key_ids"][1]]
             h, wd = w["frame_prev"].shape[2], w["frame_prev"].shape[3]
-            if self.crop is None and self._native(w["frame_prev"]):
+            conf = None
+            if self.confidence and self.crop is None:
+                with _region(profiler, "predict_warp"), _region(profiler, "predict_fusion"):
+                    logits, _ = ops.seg_tail(lo_prev, lo_next, w["mvs_left"], w["mvs_right"], n, (h, wd), fm.no_warp, want_logits=True, weights=w.get("weights"))
+                masks, conf = ops.mask_confidence(logits, self.out_size)
+            elif self.confidence:
+                canvas = crops.compute_output(fm, n, w["frame_prev"], w["frame_next"], w["mvs_left"], w["mvs_right"], self.crop[0],
+                                              self.crop[1], self.classes, profiler, want_mask=False, out_size=self.out_size,
+                                              lows=(lo_prev, lo_next), want_canvas=True, weights=w.get("weights"))
+                masks, conf = ops.canvas_confidence(canvas, self.out_size)
+            elif self.crop is None and self._native(w["frame_prev"]):
                 with _region(profiler, "predict_warp"), _region(profiler, "predict_fusion"):  # identity resize: see predict_window
                     _, masks = ops.seg_tail(lo_prev, lo_next, w["mvs_left"], w["mvs_right"], n, (h, wd), fm.no_warp, want_logits=False, want_mask=True,
                                                 weights=w.get("weights"))
@@ -140,8 +216,7 @@ class FlowPredictor:
                 _, masks = crops.compute_output(fm, n, w["frame_prev"], w["frame_next"], w["mvs_left"], w["mvs_right"], self.crop[0],
                                                 self.crop[1], self.classes, profiler, want_mask=True, out_size=self.out_size,
                                                 lows=(lo_prev, lo_next), want_canvas=False, weights=w.get("weights"))
-            self._score(masks, n)
-            return masks.cpu().numpy() if to_host else masks
+            return self._finish(masks, conf, n, to_host)
 
         while True:
             plain = None  # a window that cannot take the look-ahead route (no key_ids / feature mode / foreign network)
@@ -238,6 +313,27 @@ class FlowEvaluator:
         inter, union, target = h[0], h[1] + h[2] - h[0], h[2]
         iou_class, acc_class = inter / (union + 1e-10), inter / (target + 1e-10)
         return float(np.mean(iou_class)), float(np.mean(acc_class)), float(inter.sum() / (target.sum() + 1e-10)), iou_class, acc_class
+
+
+def write_extent_csv(path, frame_ids, report, frame_pixels, with_confidence=True):
+    """One CSV row per frame from an extent report int64 [frames, K, 3] (FlowPredictor.extent_report / ops.frame_report read back):
+    frame id, then per class k  area_k = pixels / frame_pixels,  conf_k = sum / (255 pixels)  (mean confidence, empty for a class
+    without pixels)  and  low_k = low-confidence pixels / pixels  (0 without pixels).  with_confidence=False: the areas only."""
+    report = np.asarray(report)
+    if report.ndim != 3 or report.shape[2] != 3 or len(frame_ids) != report.shape[0]:
+        raise ValueError(f"write_extent_csv: report must be [frames, K, 3] with one frame id per row, got {report.shape} and {len(frame_ids)} ids")
+    classes = report.shape[1]
+    cols = ["frame"] + [f"{name}_{k}" for k in range(classes) for name in (("area", "conf", "low") if with_confidence else ("area",))]
+    with open(path, "w", newline="") as f:
+        f.write(",".join(cols) + "\n")
+        for fid, rows in zip(frame_ids, report):
+            cells = [str(int(fid))]
+            for pixels, total, low in rows.tolist():
+                cells.append(f"{pixels / frame_pixels:.6f}")
+                if with_confidence:
+                    cells.append(f"{total / (255.0 * pixels):.6f}" if pixels else "")
+                    cells.append(f"{low / pixels:.6f}" if pixels else "0.000000")
+            f.write(",".join(cells) + "\n")
 
 
 def colorize(masks_u8, palette=PALETTE):

@@ -462,6 +462,78 @@ def iou_hist(pred_u8, target_u8, classes, ignore_index=255, hist=None):
     return hist
 
 
+# ------------------------------------------------------------------------------------------ confidence and the extent report
+def _confidence_out(n, size, h, w, dev):
+    hh, ww = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if hh < 1 or ww < 1:
+        raise RuntimeError(f"floodseg: size must be at least 1 x 1, got {hh} x {ww}")
+    return hh, ww, torch.empty((n, hh, ww), dtype=torch.uint8, device=dev), torch.empty((n, hh, ww), dtype=torch.uint8, device=dev)
+
+
+def mask_confidence(logits, size=None):
+    """fp32 logits [n,K,h,w] -> (mask, confidence), uint8 [n,H,W] each, in one launch (definition: include/floodseg_test.h,
+    mask_confidence): the argmax of the align_corners=True resize to `size` (None = the logits' size: the logits themselves) as
+    resize_argmax_u8 / argmax_u8 give it, and round(255 * softmax probability of that class).  K <= 32."""
+    lib = _lib.load()
+    dev = one_device(logits, what="floodseg.mask_confidence")
+    if logits.dtype != torch.float32 or logits.dim() != 4:
+        raise RuntimeError(f"floodseg.mask_confidence: logits must be float32 [n,K,h,w], got {logits.dtype} {tuple(logits.shape)}")
+    n, k, h, w = logits.shape
+    if not 1 <= k <= 32 or h < 1 or w < 1:
+        raise RuntimeError(f"floodseg.mask_confidence: 1..32 classes on a non-empty map, got {tuple(logits.shape)}")
+    with torch.cuda.device(dev):
+        hh, ww, mask, conf = _confidence_out(n, size, h, w, dev)
+        if n:
+            check(lib.fs_mask_confidence(ptr(logits.contiguous()), n, k, h, w, ptr(mask), ptr(conf), hh, ww, stream_ptr()))
+    return mask, conf
+
+
+def canvas_confidence(canvas, size=None):
+    """The float64 crop-averaged canvas [n,K,h,w] of crops_fuse(want_canvas=True) -> (mask, confidence), uint8 [n,H,W] each, in one
+    launch (definition: include/floodseg_test.h, canvas_confidence): canvas_resize_argmax's mask and round(255 * the winning mean
+    probability), the resize evaluated in float64."""
+    lib = _lib.load()
+    dev = one_device(canvas, what="floodseg.canvas_confidence")
+    if canvas.dtype != torch.float64 or canvas.dim() != 4:
+        raise RuntimeError(f"floodseg.canvas_confidence: canvas must be float64 [n,K,h,w], got {canvas.dtype} {tuple(canvas.shape)}")
+    n, k, h, w = canvas.shape
+    if not 1 <= k <= 255 or h < 1 or w < 1:
+        raise RuntimeError(f"floodseg.canvas_confidence: 1..255 classes on a non-empty map, got {tuple(canvas.shape)}")
+    with torch.cuda.device(dev):
+        hh, ww, mask, conf = _confidence_out(n, size, h, w, dev)
+        if n:
+            check(lib.fs_canvas_confidence(ptr(canvas.contiguous()), n, k, h, w, ptr(mask), ptr(conf), hh, ww, stream_ptr()))
+    return mask, conf
+
+
+def frame_report(mask, conf=None, classes=5, low=128, out=None):
+    """uint8 masks [n,H,W] (and their confidence planes) -> int64 [n,K,3]: per frame and class the pixels, the sum of their confidence
+    codes and the pixels with confidence < low (definition: include/floodseg_test.h, frame_report).  conf None: counts only.  Mask ids
+    >= classes are counted nowhere.  out: a caller-owned contiguous int64 [n,K,3] destination (rows of a larger buffer); it is
+    written whole, never accumulated into."""
+    lib = _lib.load()
+    dev = one_device(mask, conf, out, what="floodseg.frame_report")
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise RuntimeError(f"floodseg.frame_report: mask must be uint8 [n,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    if conf is not None and (conf.dtype != torch.uint8 or conf.shape != mask.shape):
+        raise RuntimeError(f"floodseg.frame_report: conf must be uint8 of the mask's shape {tuple(mask.shape)}, got {conf.dtype} {tuple(conf.shape)}")
+    k, low = int(classes), int(low)
+    if not 1 <= k <= 255 or not 0 <= low <= 255:
+        raise RuntimeError(f"floodseg.frame_report: classes must be 1..255 and low 0..255, got {classes} and {low}")
+    n, h, w = mask.shape
+    if h < 1 or w < 1:
+        raise RuntimeError(f"floodseg.frame_report: empty frames {tuple(mask.shape)}")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((n, k, 3), dtype=torch.int64, device=dev)
+        elif out.dtype != torch.int64 or tuple(out.shape) != (n, k, 3) or not out.is_contiguous():
+            raise RuntimeError(f"floodseg.frame_report: out must be a contiguous int64 [{n},{k},3] tensor, got {out.dtype} {tuple(out.shape)}")
+        if n:
+            check(lib.fs_frame_report(ptr(mask.contiguous()), ptr(conf.contiguous()) if conf is not None else None, n, h, w, k, low, ptr(out),
+                                      stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ block motion estimation
 def block_match(cur, ref, search=16, penalty=0, return_cost=False):
     """Full-search block matching of two uint8 frames [H,W] (luma) or [H,W,3] (RGB as decoded), `ref` the past frame: the motion-vector
@@ -586,15 +658,19 @@ def raw_frame_bytes(height, width, pix_fmt):
     """Bytes of one frame of a headerless raw video (ffmpeg -f rawvideo): chroma planes of the 4:2:0 formats round up."""
     if pix_fmt == "rgb24":
         return height * width * 3
+    if pix_fmt == "gray":  # one 8-bit plane (ffmpeg -pix_fmt gray): the confidence planes
+        return height * width
     return height * width + 2 * ((height + 1) // 2) * ((width + 1) // 2)
 
 
 def frame_planes(buf, height, width, pix_fmt):
     """(frame, chroma) views of one raw frame's bytes `buf` (uint8 [raw_frame_bytes]) as prepare_frame takes and compose_frame returns
-    them: rgb24 -> ([H,W,3], None); nv12 -> (Y [H,W], UV [ceil(H/2),ceil(W/2),2]); i420 -> (Y, (U, V))."""
+    them: rgb24 -> ([H,W,3], None); gray -> ([H,W], None); nv12 -> (Y [H,W], UV [ceil(H/2),ceil(W/2),2]); i420 -> (Y, (U, V))."""
     h, w = height, width
     if pix_fmt == "rgb24":
         return buf.view(h, w, 3), None
+    if pix_fmt == "gray":
+        return buf.view(h, w), None
     ch, cw = (h + 1) // 2, (w + 1) // 2
     y = buf[:h * w].view(h, w)
     if pix_fmt == "nv12":

@@ -6,8 +6,8 @@
  * also carries EXTENSION OPS: product features that have no reference call site (block matching, flow/motion.py) and therefore no
  * place in the capped export list of floodseg.h; the Python package reaches them like any other function.  fs_test_api is frozen at
  * block_match; later extension ops (frame ingest, frame egress) are members of fs_ext_api, the table right behind it, and the ones
- * after those (block_match_modes, window_weights, seg_tail_weighted, crops_fuse_weighted, feat_tail_weighted) of fs_ext2_api, the table
- * behind both (end of this file).
+ * after those (block_match_modes, window_weights, seg_tail_weighted, crops_fuse_weighted, feat_tail_weighted, mask_confidence,
+ * canvas_confidence, frame_report) of fs_ext2_api, the table behind both (end of this file).
  *
  * They are NOT part of the product's symbol surface (include/floodseg.h): the library exports ONE extra symbol, fs_test_hooks(), that
  * returns a table of function pointers.  The table was append-only up to block_match and is frozen now; `size` is sizeof(fs_test_api)
@@ -352,6 +352,39 @@ typedef struct fs_ext2_api {
     int (*feat_tail_weighted)(const float* f_prev, const float* f_next, int C, int fh, int fw, const float* const* grids_left,
                               const float* const* grids_right, int Hg, int Wg, const float* grid0, int H0, int W0, int n, int no_warp,
                               float* stack, float* scratch, const float* weights, fs_stream stream);
+
+    /* Per-pixel confidence from fp32 logits (csrc/conf_ops.hip).  OUR DEFINITION: the reference emits hard masks only.  logits =
+     * float [n][K][h][w] (NCHW, what the tails write as logits), 1 <= K <= 32; mask, confidence = uint8 [n][H][W], both written by one
+     * launch, at any byte address (dword stores when W % 4 == 0 and both are 4-byte aligned, byte stores otherwise).  Per output pixel:
+     *   v[k]  = the align_corners=True bilinear value fs_resize_argmax_u8 takes the argmax of (the same index, weight and
+     *           interpolation arithmetic in the same order); with (H, W) == (h, w) the logit itself, read directly
+     *   mask  = the first maximum of v: with a resize fs_resize_argmax_u8's rule (the first k whose v[k] exceeds -inf and that no later
+     *           k exceeds), at equal sizes fs_argmax_u8's (class 0 until a later value exceeds it).  The two differ on NaNs only.
+     *   p     = the fp32 softmax over the K values as the tails and fs_softmax_accumulate compute it: m = max v, e[k] = expf(v[k] - m),
+     *           s = e[0] + e[1] + ... in class order, p[k] = e[k] / s
+     *   c     = p[mask];   confidence = c == c ? min(255, max(0, round-half-even(255.f * c))) : 0     (product and rounding in fp32)
+     * So K == 1 gives 255, K equal logits give round(255 / K) with mask 0, and a NaN among a pixel's values gives 0.
+     * Refused before a launch: a null pointer, n, h, w, H or W < 1, n > 65535, K outside 1..32, h * w or H * W >= 2^31. */
+    int (*mask_confidence)(const float* logits, int n, int K, int h, int w, uint8_t* mask, uint8_t* confidence, int H, int W, fs_stream stream);
+
+    /* The same two planes from the float64 crop-averaged canvas [n][K][h][w] (mean class probabilities, already divided by the crop
+     * count: what fs_crops_fuse / fs_canvas_finish leave).  OUR DEFINITION.  1 <= K <= 255.  Per output pixel:
+     *   v[k]  = the float64 align_corners=True bilinear value fs_canvas_resize_argmax takes the argmax of (same arithmetic, at equal
+     *           sizes too: the canvas value itself for finite data; a NaN reaches the neighbours whose zero-weight taps read it)
+     *   mask  = fs_canvas_resize_argmax's: the first k whose v[k] exceeds -inf and that no later k exceeds (0 when there is none)
+     *   c     = v[mask];   confidence = c == c ? clamp(rint(255.0 * c), 0, 255) : 0                  (in double)
+     * Stores and refusals as mask_confidence's (K outside 1..255). */
+    int (*canvas_confidence)(const double* canvas, int n, int K, int h, int w, uint8_t* mask, uint8_t* confidence, int H, int W, fs_stream stream);
+
+    /* Per frame and class, the extent and how far it can be trusted (csrc/conf_ops.hip).  OUR DEFINITION.  mask, confidence = uint8
+     * [n][H][W]; 1 <= K <= 255; 0 <= low <= 255.  report = int64 [n][K][3]:
+     *   report[f][k] = (pixels of frame f with mask == k,  the sum of their confidence codes,  those of them with confidence < low)
+     * Mask ids >= K are counted nowhere: a frame's pixel counts then sum to less than H * W, which is how a caller sees them.
+     * confidence == NULL: the pixel counts only, the other two columns zero.  Every call writes the whole report (it is zeroed on the
+     * stream first), so the caller never clears it and a HIP-graph replay on new masks gives that replay's figures.  Integers
+     * throughout: exact, whatever the order.  Refused before a launch: a null mask or report, n, H or W < 1, n > 65535, K or low out of
+     * range, H * W >= 2^31 - 16384. */
+    int (*frame_report)(const uint8_t* mask, const uint8_t* confidence, int n, int H, int W, int K, int low, int64_t* report, fs_stream stream);
 } fs_ext2_api;
 
 typedef struct fs_hook_tables2 {

@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -293,6 +293,65 @@ def main():
                     torch.cuda.current_stream().synchronize()
                 t = timeit(item_step, steps=6, warmup=2)
                 rows.append((f"PredictWindows item, grids=estimate, JPEG folder (host-bound), {label}", 1 / t, t * 1e3))
+    if want("conf"):
+        # per-pixel confidence and the extent report (ops.mask_confidence / canvas_confidence / frame_report, csrc/conf_ops.hip): what the
+        # opt-in costs behind each tail, on the same held logits, alternating (three rounds each, the fastest of each side), every loop
+        # >= 0.5 s.  Whole frame: the masks-only tail against logits + mask_confidence + frame_report; sliding crops: crops_fuse
+        # masks-only against canvas + canvas_confidence + frame_report.  Then the three kernels alone with their achieved bytes / s.
+        from flood_uav_video_segmentation_amd.flow.crops import crop_windows
+        gen = torch.Generator().manual_seed(1700)
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+
+        def ab(label, old, new):
+            alt = [(timed(old), timed(new)) for _ in range(3)]
+            t_old, t_new = (min(x[j] for x in alt) for j in range(2))
+            rows.append((f"{label}, masks only", 1 / t_old, t_old * 1e3))
+            rows.append((f"  + confidence + report: {(t_new / t_old - 1) * 100:+.2f} % ({(t_new - t_old) * 1e3:+.3f} ms)", 1 / t_new, t_new * 1e3))
+
+        def alone(label, fn, nbytes):
+            t = min(timed(fn) for _ in range(3))
+            rows.append((f"  {label}: {nbytes / 1e6:.1f} MB, {nbytes / t / 1e12:.2f} TB/s", 1 / t, t * 1e3))
+
+        for (hh, ww), hg in (((713, 713), 44), ((1072, 1920), None)):
+            lo = torch.randn((2, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            gl, gr = (wl, wr) if hg else [[g.to(dev) for g in gs] for gs in synth.make_grids(N, 67, 120, seed=2001, frame=(hh, ww))]
+            report = torch.empty((N, 5, 3), dtype=torch.int64, device=dev)
+
+            def with_conf(i, lo=lo, gl=gl, gr=gr, no_warp=False, hh=hh, ww=ww, report=report):
+                logits, _ = ops.seg_tail(lo[0:1], lo[1:2], gl, gr, N, (hh, ww), no_warp, want_logits=True)
+                mask, conf = ops.mask_confidence(logits)
+                ops.frame_report(mask, conf, 5, 128, out=report)
+            for no_warp in (False, True):
+                ab(f"seg_tail {hh}x{ww} {'no_warp' if no_warp else 'warp'}",
+                   lambda i, lo=lo, gl=gl, gr=gr, no_warp=no_warp, hh=hh, ww=ww: ops.seg_tail(lo[0:1], lo[1:2], gl, gr, N, (hh, ww), no_warp, want_logits=False,
+                                                                                         want_mask=True),
+                   lambda i, f=with_conf, no_warp=no_warp: f(i, no_warp=no_warp))
+            logits = torch.randn((N, 5, hh, ww), generator=gen).to(dev) * 3
+            mask, conf = ops.mask_confidence(logits)
+            alone(f"mask_confidence {hh}x{ww} n {N} K 5", lambda i, x=logits: ops.mask_confidence(x), logits.numel() * 4 + 2 * mask.numel())
+            alone(f"frame_report {hh}x{ww} n {N} K 5", lambda i, m=mask, c=conf, r=report: ops.frame_report(m, c, 5, 128, out=r), 2 * mask.numel())
+            canvas = torch.softmax(logits.double(), 1)
+            alone(f"canvas_confidence {hh}x{ww} n {N} K 5", lambda i, x=canvas: ops.canvas_confidence(x), canvas.numel() * 8 + 2 * mask.numel())
+            del logits, canvas
+        wins = crop_windows(1072, 1920, 713, 713)
+        yx = [(y, x) for (y, _, x, _) in wins]
+        lo_c = torch.randn((2, len(yx), 5, 90, 90), generator=gen).to(dev)
+        g1080 = [[g.to(dev) for g in gs] for gs in synth.make_grids(N, 67, 120, seed=2002, frame=(1072, 1920))]
+        cg = ops.crop_grids(g1080[0] + g1080[1], (1072, 1920), yx, (713, 713))
+        report = torch.empty((N, 5, 3), dtype=torch.int64, device=dev)
+
+        def crops_conf(i, no_warp):
+            canvas, _ = ops.crops_fuse(lo_c[0], lo_c[1], None if no_warp else cg, yx, (713, 713), N, no_warp, (1072, 1920), want_canvas=True)
+            mask, conf = ops.canvas_confidence(canvas)
+            ops.frame_report(mask, conf, 5, 128, out=report)
+        for no_warp in (False, True):
+            ab(f"crops_fuse 1072x1920, {len(yx)} crops of 713x713, {'no_warp' if no_warp else 'warp'}",
+               lambda i, no_warp=no_warp: ops.crops_fuse(lo_c[0], lo_c[1], None if no_warp else cg, yx, (713, 713), N, no_warp, (1072, 1920),
+                                                         want_canvas=False, want_mask=True),
+               lambda i, no_warp=no_warp: crops_conf(i, no_warp))
     if want("cuts"):
         # holding one key frame across a scene cut (ops.window_weights, the weighted instantiations of the fused tails): the weighted
         # call against the unweighted one on the same held logits, alternating (three rounds each, the fastest of each side), every loop

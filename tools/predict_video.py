@@ -22,6 +22,11 @@ across a scene cut, on the identity grid; the frames judged cuts and the mean in
 the cut is the previous key frame's prediction alone and a frame after it the next key frame's, instead of a mix of two scenes (in
 feature mode: the decoder sees one key frame's warped features, not a mixture); how many frames were blended and held is printed with
 the rest.
+`--confidence` (an extension) also computes a per-pixel confidence, 255 x the probability of the emitted class, and a
+per-frame, per-class extent report on the device; the masks are unchanged.  `--report FILE.csv` writes, once at the end, one row per
+frame: the frame id and per class the area fraction, the mean confidence (sum / (255 pixels)) and the share of the class's pixels
+with confidence below `--low-confidence` (default 128); without `--confidence` the areas only.  `--conf-out FILE` (needs
+`--confidence`) writes the confidence planes as a headerless 8-bit grey raw video (`ffmpeg -f rawvideo -pix_fmt gray` reads it).
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -41,7 +46,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -104,7 +109,18 @@ def parse_args(argv=None):
                     "--raw, bt709 for a frame folder)")
     ap.add_argument("--out-full-range", action="store_true", default=None, help="--raw-out, YUV formats: full-range levels (default: the "
                     "input's for --raw, limited for a frame folder)")
+    ap.add_argument("--confidence", action="store_true", help="also compute a per-pixel confidence (255 x the probability of the emitted "
+                    "class) and a per-frame, per-class extent report on the device; the masks are unchanged")
+    ap.add_argument("--low-confidence", type=int, default=128, metavar="C", help="--confidence: a pixel with a confidence code below C "
+                    "(0..255) counts as low-confidence in the report")
+    ap.add_argument("--report", metavar="FILE.csv", help="write one row per frame: per class the area fraction and, with --confidence, the "
+                    "mean confidence and the low-confidence share (single GPU)")
+    ap.add_argument("--conf-out", metavar="FILE", help="--confidence: write the confidence planes as 8-bit grey raw video (-pix_fmt gray)")
     args = ap.parse_args(argv)
+    if args.conf_out and not args.confidence:
+        ap.error("--conf-out needs --confidence")
+    if not 0 <= args.low_confidence <= 255:
+        ap.error("--low-confidence takes a code 0..255")
     if not args.raw_out:
         for given, name in ((args.overlay is not None, "--overlay"), (args.overlay_keep_class0, "--overlay-keep-class0"),
                             (args.out_matrix is not None, "--out-matrix"), (args.out_full_range is not None, "--out-full-range"),
@@ -156,7 +172,10 @@ def main():
     load_weights(net, args)
     fm = FlowModel(net, feature_based=args.feature_based, no_warp=args.no_warp).eval()
     pred = FlowPredictor(fm, classes=args.classes, out_size=tuple(args.size), crop=None if args.no_cropping else tuple(args.crop),
-                         compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache)
+                         compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache, confidence=args.confidence,
+                         low_confidence=args.low_confidence)
+    if args.report and world > 1:
+        raise SystemExit("--report covers one process's frames: run it on a single GPU")
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
@@ -183,6 +202,9 @@ def main():
             ff = {"nv12": "nv12", "i420": "yuv420p", "rgb24": "rgb24"}[args.out_pix_fmt]
             print(f"encode with: ffmpeg -f rawvideo -pix_fmt {ff} -s {w}x{h} -r 25 -i {args.raw_out} result.mp4"
                   + ("" if args.out_pix_fmt == "rgb24" else f"   ({args.out_matrix}, {'full' if args.out_full_range else 'limited'} range)"), file=sys.stderr)
+    conf_writer = None
+    if args.conf_out:
+        conf_writer = RawVideoWriter(args.conf_out, args.size[0], args.size[1], "gray", frames=len(ds) * args.frame_delta, world=world)
     shard.barrier()
 
     # windows are independent units given their two key frames: each rank takes a contiguous block (SURVEY 8e "frame-window
@@ -192,12 +214,21 @@ def main():
     frames = 0
     first_mask = last_mask = None
     sources = []  # --hold-cuts: every window's device `source` tensor, read back once after the timed run
+    report_ids, areas = [], []  # --report: the frame ids, and without --confidence every window's device counts
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for w in mine:
         item = ds[w]
         masks = pred.predict_window(item["frame_prev"], item["frame_next"], item["mvs_left"], item["mvs_right"], to_host=False,
                                     key_ids=item["key_ids"], weights=item.get("weights"))
+        if args.confidence:
+            masks, conf = masks
+            if conf_writer is not None:
+                for p in range(conf.shape[0]):
+                    conf_writer.write(item["frame_id"] + p, conf[p].reshape(-1))
+        elif args.report:
+            areas.append(ops.frame_report(masks, None, args.classes))
+        report_ids.extend(item["frame_id"] + p for p in range(masks.shape[0]))
         if "source" in item:
             sources.append(item["source"])
         if first_mask is None:
@@ -217,6 +248,8 @@ def main():
                 Image.fromarray(rgb[p]).save(os.path.join(args.out, f"{item['frame_id'] + p}.png"))
     if writer is not None:
         writer.close()   # the last two frames' copies and writes belong to the timed work
+    if conf_writer is not None:
+        conf_writer.close()
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0  # this rank's own work: the end-of-run exchange below waits for the slowest rank and is not part of it
     if world > 1 and not args.no_metrics:
@@ -247,6 +280,9 @@ def main():
         counts = torch.bincount(torch.cat(sources).cpu().long(), minlength=4).tolist()
         print(f"rank {rank}: --hold-cuts: {counts[0]} frames blended, {counts[1]} held from the previous key frame, {counts[2]} from the next, "
               f"{counts[3]} between two cuts", file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    if args.report:  # the device report is read back ONCE, here, after the timed run
+        report = pred.extent_report() if args.confidence else (torch.cat(areas).cpu().numpy() if areas else np.zeros((0, args.classes, 3), np.int64))
+        write_extent_csv(args.report, report_ids, report, args.size[0] * args.size[1], with_confidence=args.confidence)
     if world > 1:
         torch.distributed.destroy_process_group()
 
