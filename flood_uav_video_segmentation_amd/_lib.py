@@ -152,6 +152,9 @@ _EXT2_HOOKS = [
     ("mask_confidence", c_int, [c_void] + [c_int] * 4 + [c_void, c_void, c_int, c_int, c_void]),
     ("canvas_confidence", c_int, [c_void] + [c_int] * 4 + [c_void, c_void, c_int, c_int, c_void]),
     ("frame_report", c_int, [c_void, c_void] + [c_int] * 5 + [c_void, c_void]),
+    ("mask_regions", c_int, [c_void] + [c_int] * 5 + [c_void, c_void]),
+    ("region_table", c_int, [c_void, c_void, c_void] + [c_int] * 6 + [c_void] * 5),
+    ("region_filter", c_int, [c_void, c_void, c_void] + [c_int] * 6 + [c_void, c_void, c_void]),
 ]
 EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
 

@@ -403,6 +403,19 @@ static int fs_canvas_confidence(const double* canvas, int n, int K, int h, int w
 static int fs_frame_report(const uint8_t* mask, const uint8_t* confidence, int n, int H, int W, int K, int low, int64_t* report, fs_stream stream) {
     return fs::launch_frame_report(mask, confidence, n, H, W, K, low, reinterpret_cast<long long*>(report), S(stream));
 }
+// connected regions of a mask (region_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_mask_regions(const uint8_t* mask, int n, int H, int W, int K, int connectivity, int32_t* labels, fs_stream stream) {
+    return fs::launch_mask_regions(mask, n, H, W, K, connectivity, labels, S(stream));
+}
+static int fs_region_table(const uint8_t* mask, const int32_t* labels, const uint8_t* confidence, int n, int H, int W, int K, int low, int max_regions,
+                           int64_t* table, int64_t* counts, int32_t* index, int32_t* workspace, fs_stream stream) {
+    return fs::launch_region_table(mask, labels, confidence, n, H, W, K, low, max_regions, reinterpret_cast<long long*>(table),
+                                   reinterpret_cast<long long*>(counts), index, workspace, S(stream));
+}
+static int fs_region_filter(const uint8_t* mask, const int32_t* index, const int64_t* table, int n, int H, int W, int K, int max_regions, int min_area,
+                            uint8_t* out, int32_t* votes, fs_stream stream) {
+    return fs::launch_region_filter(mask, index, reinterpret_cast<const long long*>(table), n, H, W, K, max_regions, min_area, out, votes, S(stream));
+}
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
     if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
@@ -502,6 +515,9 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_mask_confidence,
         fs_canvas_confidence,
         fs_frame_report,
+        fs_mask_regions,
+        fs_region_table,
+        fs_region_filter,
     }};
     return &all.base.test;
 }

@@ -351,6 +351,15 @@ int launch_canvas_confidence(const double* canvas, int n, int K, int Hi, int Wi,
 // out: int64 [n][K][3] = (pixels, sum of confidence codes, pixels with code < low), written whole; conf == nullptr: counts only
 int launch_frame_report(const uint8_t* mask, const uint8_t* conf, int n, int H, int W, int K, int low, long long* out, hipStream_t s);
 
+// Connected regions of a mask (region_ops.hip, region_uf.h; definitions: include/floodseg_test.h).  Each launcher refuses bad arguments
+// before it launches anything; workspaces are the caller's (sizes in the header), nothing is allocated or synchronised.
+int region_rank_chunks(int H, int W);  // ints of region_table's workspace per frame
+int launch_mask_regions(const uint8_t* mask, int n, int H, int W, int K, int connectivity, int* labels, hipStream_t s);
+int launch_region_table(const uint8_t* mask, const int* labels, const uint8_t* conf, int n, int H, int W, int K, int low, int max_regions,
+                        long long* table, long long* counts, int* index, int* workspace, hipStream_t s);
+int launch_region_filter(const uint8_t* mask, const int* index, const long long* table, int n, int H, int W, int K, int max_regions,
+                         int min_area, uint8_t* out, int* votes, hipStream_t s);
+
 
 // ---------------------------------------------------------------------------------
 // Segmenter / ViT pieces (segm/model/vit.py, blocks.py, decoder.py); token matrices are row-major

@@ -9,6 +9,9 @@ Extension (no reference counterpart): FlowPredictor(..., confidence=True) also r
 per-frame, per-class extent report on the device (ops.mask_confidence / canvas_confidence / frame_report):
     masks, conf = p.predict_window(...)
     p.extent_report()                                                      # int64 [frames, K, 3], read back once
+FlowPredictor(..., regions=True) keeps a per-frame table of the masks' connected regions on the device, and min_region_area=N emits
+masks without regions smaller than N pixels (ops.mask_regions / region_table / region_filter):
+    rows, totals = p.region_report()                                       # per frame int64 [regions, 10]; read back once
 """
 import numpy as np
 import torch
@@ -30,12 +33,26 @@ class FlowPredictor:
     the sliding-crop route).  The masks are the confidence=False masks bit for bit; they come from the same launch as the confidence,
     which needs the window's logits / canvas written out once (the masks-only tails skip that).  Every window's per-class report
     (pixels, sum of confidence codes, pixels with confidence < low_confidence) goes into rows of chunked device buffers; nothing is
-    read back until extent_report()."""
+    read back until extent_report().
+
+    regions=True (extension): every emitted mask is labelled (connectivity 4 or 8) and its region table -- per region class, area,
+    bounding box, coordinate sums, and with confidence=True the confidence sum and the low-confidence pixels -- goes into chunked
+    device buffers like the extent report: max_regions x 80 B per frame (1024 regions: 80 KiB a frame, 20 MiB per 256-frame chunk),
+    nothing read back until region_report().  A frame with more regions keeps its first max_regions (in raster order of their first
+    pixels) and reports the full count.  With min_region_area <= 1 the masks are the default masks bit for bit.
+    min_region_area=N > 1 (extension): regions smaller than N pixels are re-classed by the vote of their 4-neighbours (one pass; a
+    speckle nobody borders stays) before anything else sees the masks: what is returned, scored, reported and -- with regions=True,
+    after labelling the filtered masks again -- tabulated are the filtered masks.  The confidence plane stays as computed: a
+    re-classed pixel keeps the confidence of its old class.  The filter sees the first max_regions regions of a frame only (in
+    raster order of their first pixels): by the definition a region past the cap is neither a speckle nor a voter, so on a frame with
+    more regions than max_regions the lower part of the frame is left unfiltered.  The pass's region counts are kept on the device
+    (16 B per frame); despeckle_counts() reads them back so that a caller can see such frames and raise max_regions."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
-                 cache_keyframes=False, confidence=False, low_confidence=128):
+                 cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
+                 max_regions=1024):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -53,19 +70,35 @@ class FlowPredictor:
         self.low_confidence = int(low_confidence)
         self._report_chunks = []  # int64 [REPORT_CHUNK, K, 3] device buffers, filled in frame order
         self._report_frames = 0
+        if connectivity not in (4, 8):
+            raise ValueError(f"FlowPredictor: connectivity must be 4 or 8, got {connectivity}")
+        if not 1 <= int(max_regions) <= 65536:
+            raise ValueError(f"FlowPredictor: max_regions must be 1..65536, got {max_regions}")
+        if not 0 <= int(min_region_area) < 2 ** 31:
+            raise ValueError(f"FlowPredictor: min_region_area must be 0..2^31 - 1, got {min_region_area}")
+        self.regions = bool(regions)
+        self.min_region_area = int(min_region_area)
+        self.connectivity = int(connectivity)
+        self.max_regions = int(max_regions)
+        self._region_chunks = []  # (int64 [REPORT_CHUNK, max_regions, 10], int64 [REPORT_CHUNK, 2]) device buffers, in frame order
+        self._region_frames = 0
+        self._despeckle_counts = []  # min_region_area > 1: the filter pass's int64 [n, 2] counts, one device tensor per window
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
         its predecessor, flow/base.py:247,295 -- which must not be another video's last frame).  The histogram keeps running, and
-        so does the extent report (clear_report() drops it)."""
+        so do the extent report and the region report (clear_report() drops them)."""
         if self.key_cache is not None:
             self.key_cache.clear()
         self.last_output = None
 
     def clear_report(self):
-        """Forget the extent report of the frames predicted so far."""
+        """Forget the extent report and the region report of the frames predicted so far."""
         self._report_chunks = []
         self._report_frames = 0
+        self._region_chunks = []
+        self._region_frames = 0
+        self._despeckle_counts = []
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -88,9 +121,62 @@ class FlowPredictor:
             done += take
             self._report_frames += take
 
+    def region_report(self):
+        """regions=True: (rows, totals) for every frame predicted since the start (or clear_report()), in the order the windows were
+        predicted: rows[f] = int64 numpy [min(regions, max_regions), 10] (class, area, x0, y0, x1, y1, sum_x, sum_y, conf_sum,
+        low_pixels), totals = int64 numpy [frames], the frames' full region counts (totals[f] > max_regions: the table is cut).  The
+        read-back happens here and nowhere else, chunk by chunk into host arrays (no second copy of the report on the device)."""
+        if not self._region_chunks:
+            return [], np.zeros((0,), dtype=np.int64)
+        rows, totals, left = [], [], self._region_frames
+        for table, counts in self._region_chunks:
+            take = min(left, self.REPORT_CHUNK)
+            c, t = counts[:take].cpu().numpy(), table[:take].cpu().numpy()
+            rows.extend(t[f, :int(c[f, 1])] for f in range(take))
+            totals.append(c[:, 0])
+            left -= take
+        return rows, np.concatenate(totals)
+
+    def despeckle_counts(self):
+        """min_region_area > 1: int64 numpy [frames], the number of regions the filter pass found in each frame's unfiltered mask since
+        the start (or clear_report()).  A value above max_regions marks a frame of which only the first max_regions regions were
+        filtered.  One read-back, here."""
+        if not self._despeckle_counts:
+            return np.zeros((0,), dtype=np.int64)
+        return torch.cat(self._despeckle_counts)[:, 0].cpu().numpy()
+
+    def _despeckle(self, masks):
+        """The masks without regions below min_region_area: label, tabulate, filter (nothing is read back)."""
+        masks = masks.contiguous()
+        labels = ops.mask_regions(masks, self.classes, self.connectivity)
+        table, counts, index = ops.region_table(masks, labels, self.classes, None, self.low_confidence, self.max_regions)
+        self._despeckle_counts.append(counts)
+        return ops.region_filter(masks, index, table, self.classes, self.min_region_area)
+
+    def _keep_regions(self, masks, conf):
+        """The window's region tables into the next rows of the chunked buffers (region_table writes its rows whole; nothing is read)."""
+        masks = masks.contiguous()
+        labels = ops.mask_regions(masks, self.classes, self.connectivity)
+        done, n = 0, masks.shape[0]
+        while done < n:
+            row = self._region_frames % self.REPORT_CHUNK
+            if row == 0:
+                self._region_chunks.append((torch.zeros((self.REPORT_CHUNK, self.max_regions, 10), dtype=torch.int64, device=masks.device),
+                                            torch.zeros((self.REPORT_CHUNK, 2), dtype=torch.int64, device=masks.device)))
+            take = min(n - done, self.REPORT_CHUNK - row)
+            table, counts = self._region_chunks[-1]
+            ops.region_table(masks[done:done + take], labels[done:done + take], self.classes, None if conf is None else conf[done:done + take],
+                             self.low_confidence, self.max_regions, out=(table[row:row + take], counts[row:row + take]))
+            done += take
+            self._region_frames += take
+
     def _finish(self, masks, conf, n, to_host):
-        """Score, keep the report, and hand out what the caller asked for: masks, or (masks, conf) with confidence=True."""
+        """Despeckle, score, keep the reports, and hand out what the caller asked for: masks, or (masks, conf) with confidence=True."""
+        if self.min_region_area > 1:
+            masks = self._despeckle(masks)
         self._score(masks, n)
+        if self.regions:
+            self._keep_regions(masks, conf)
         if not self.confidence:
             return masks.cpu().numpy() if to_host else masks            # :277
         self._keep_report(masks, conf)
@@ -334,6 +420,22 @@ def write_extent_csv(path, frame_ids, report, frame_pixels, with_confidence=True
                     cells.append(f"{total / (255.0 * pixels):.6f}" if pixels else "")
                     cells.append(f"{low / pixels:.6f}" if pixels else "0.000000")
             f.write(",".join(cells) + "\n")
+
+
+def write_regions_csv(path, frame_ids, rows, with_confidence=True):
+    """One CSV row per frame and region from FlowPredictor.region_report()'s rows (per frame int64 [regions, 10]): frame id, the
+    region's number in the frame, class, area, the inclusive box x0, y0, x1, y1, the centroid cx = sum_x / area, cy = sum_y / area,
+    and with_confidence: conf = conf_sum / (255 area) (mean confidence) and low = low-confidence pixels / area."""
+    if len(frame_ids) != len(rows):
+        raise ValueError(f"write_regions_csv: one frame id per frame, got {len(frame_ids)} ids for {len(rows)} frames")
+    with open(path, "w") as fh:
+        fh.write("frame,region,class,area,x0,y0,x1,y1,cx,cy" + (",conf,low" if with_confidence else "") + "\n")
+        for fid, frame in zip(frame_ids, rows):
+            for r, (cls, area, x0, y0, x1, y1, sx, sy, cs, lo) in enumerate(np.asarray(frame).tolist()):
+                cells = [str(fid), str(r), str(cls), str(area), str(x0), str(y0), str(x1), str(y1), f"{sx / area:.3f}", f"{sy / area:.3f}"]
+                if with_confidence:
+                    cells += [f"{cs / (255.0 * area):.6f}", f"{lo / area:.6f}"]
+                fh.write(",".join(cells) + "\n")
 
 
 def colorize(masks_u8, palette=PALETTE):

@@ -534,6 +534,92 @@ def frame_report(mask, conf=None, classes=5, low=128, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ connected regions
+REGION_RANK_CHUNK = 1024  # pixels per int of region_table's workspace (include/floodseg_test.h)
+
+
+def _region_mask(mask, classes, what):
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise RuntimeError(f"floodseg.{what}: mask must be uint8 [n,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    n, h, w = mask.shape
+    if not 1 <= int(classes) <= 255 or h < 1 or w < 1 or h * w >= 2 ** 31 - 1:
+        raise RuntimeError(f"floodseg.{what}: 1..255 classes on non-empty frames below 2^31 - 1 pixels, got {classes} and {tuple(mask.shape)}")
+    return n, h, w, int(classes)
+
+
+def mask_regions(mask, classes, connectivity=8):
+    """uint8 masks [n,H,W] -> int32 labels [n,H,W] of their connected regions (definition: include/floodseg_test.h, mask_regions): a
+    region is a maximal connected set of pixels of one frame with the same id < classes, its label 1 + the raster index of its first
+    pixel; ids >= classes are background, label 0.  connectivity 4 or 8.  Three launches, no workspace, nothing read back."""
+    lib = _lib.load()
+    dev = one_device(mask, what="floodseg.mask_regions")
+    n, h, w, k = _region_mask(mask, classes, "mask_regions")
+    if connectivity not in (4, 8):
+        raise RuntimeError(f"floodseg.mask_regions: connectivity must be 4 or 8, got {connectivity}")
+    with torch.cuda.device(dev):
+        labels = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+        if n:
+            check(lib.fs_mask_regions(ptr(mask.contiguous()), n, h, w, k, int(connectivity), ptr(labels), stream_ptr()))
+    return labels
+
+
+def region_table(mask, labels, classes, conf=None, low=128, max_regions=1024, out=None):
+    """Masks and their labels (mask_regions) -> (table int64 [n,max_regions,10], counts int64 [n,2], index int32 [n,H,W]) (definition:
+    include/floodseg_test.h, region_table).  Table rows, in the order of the regions' first pixels: class, area, x0, y0, x1, y1
+    (inclusive), sum_x, sum_y, the sum of the confidence codes, the pixels with confidence < low (the last two 0 without conf).
+    counts = (regions, rows written); index = the row of each pixel's region, -1 for background and past max_regions.
+    out: caller-owned contiguous (table, counts) destinations (rows of larger buffers); they are written whole.  The workspace
+    (one int per 1024 pixels) is allocated here."""
+    lib = _lib.load()
+    dev = one_device(mask, labels, conf, *(out or ()), what="floodseg.region_table")
+    n, h, w, k = _region_mask(mask, classes, "region_table")
+    if labels.dtype != torch.int32 or labels.shape != mask.shape:
+        raise RuntimeError(f"floodseg.region_table: labels must be int32 of the mask's shape {tuple(mask.shape)}, got {labels.dtype} {tuple(labels.shape)}")
+    if conf is not None and (conf.dtype != torch.uint8 or conf.shape != mask.shape):
+        raise RuntimeError(f"floodseg.region_table: conf must be uint8 of the mask's shape {tuple(mask.shape)}, got {conf.dtype} {tuple(conf.shape)}")
+    low, cap = int(low), int(max_regions)
+    if not 0 <= low <= 255 or not 1 <= cap <= 65536:
+        raise RuntimeError(f"floodseg.region_table: low must be 0..255 and max_regions 1..65536, got {low} and {max_regions}")
+    with torch.cuda.device(dev):
+        if out is None:
+            table = torch.empty((n, cap, 10), dtype=torch.int64, device=dev)
+            counts = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        else:
+            table, counts = out
+            if (table.dtype != torch.int64 or tuple(table.shape) != (n, cap, 10) or not table.is_contiguous() or counts.dtype != torch.int64
+                    or tuple(counts.shape) != (n, 2) or not counts.is_contiguous()):
+                raise RuntimeError(f"floodseg.region_table: out must be contiguous int64 [{n},{cap},10] and [{n},2] tensors")
+        index = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+        if n:
+            work = torch.empty((n, -(-h * w // REGION_RANK_CHUNK)), dtype=torch.int32, device=dev)
+            check(lib.fs_region_table(ptr(mask.contiguous()), ptr(labels.contiguous()), ptr(conf.contiguous()) if conf is not None else None, n, h, w,
+                                      k, low, cap, ptr(table), ptr(counts), ptr(index), ptr(work), stream_ptr()))
+    return table, counts, index
+
+
+def region_filter(mask, index, table, classes, min_area):
+    """Despeckle (definition: include/floodseg_test.h, region_filter): every region of region_table's result with area < min_area takes
+    the class most of its pixels' 4-neighbours in large-enough regions have (lowest id on a tie; nobody to ask: it stays).  One pass
+    over the input mask; returns a new mask, equal to the input outside such regions and bit for bit for min_area <= 1.  The vote
+    workspace (int32 [n,max_regions,classes]) is allocated here."""
+    lib = _lib.load()
+    dev = one_device(mask, index, table, what="floodseg.region_filter")
+    n, h, w, k = _region_mask(mask, classes, "region_filter")
+    if index.dtype != torch.int32 or index.shape != mask.shape:
+        raise RuntimeError(f"floodseg.region_filter: index must be int32 of the mask's shape {tuple(mask.shape)}, got {index.dtype} {tuple(index.shape)}")
+    if table.dtype != torch.int64 or table.dim() != 3 or table.shape[0] != n or table.shape[2] != 10 or not 1 <= table.shape[1] <= 65536:
+        raise RuntimeError(f"floodseg.region_filter: table must be int64 [{n},max_regions,10], got {table.dtype} {tuple(table.shape)}")
+    if int(min_area) < 0 or int(min_area) >= 2 ** 31:
+        raise RuntimeError(f"floodseg.region_filter: min_area must be 0..2^31 - 1, got {min_area}")
+    with torch.cuda.device(dev):
+        out = torch.empty_like(mask, memory_format=torch.contiguous_format)
+        if n:
+            votes = torch.empty((n, table.shape[1], k), dtype=torch.int32, device=dev)
+            check(lib.fs_region_filter(ptr(mask.contiguous()), ptr(index.contiguous()), ptr(table.contiguous()), n, h, w, k, table.shape[1], int(min_area),
+                                       ptr(out), ptr(votes), stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ block motion estimation
 def block_match(cur, ref, search=16, penalty=0, return_cost=False):
     """Full-search block matching of two uint8 frames [H,W] (luma) or [H,W,3] (RGB as decoded), `ref` the past frame: the motion-vector

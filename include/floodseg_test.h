@@ -385,6 +385,53 @@ typedef struct fs_ext2_api {
      * throughout: exact, whatever the order.  Refused before a launch: a null mask or report, n, H or W < 1, n > 65535, K or low out of
      * range, H * W >= 2^31 - 16384. */
     int (*frame_report)(const uint8_t* mask, const uint8_t* confidence, int n, int H, int W, int K, int low, int64_t* report, fs_stream stream);
+
+    /* ---- Connected regions of a mask (csrc/region_ops.hip, csrc/region_uf.h).  OUR DEFINITION: the reference emits hard
+     * masks only.  Integers throughout; every result is a function of the inputs alone, whatever order threads arrive in.
+     *   mask         uint8 [n][H][W];  1 <= K <= 255;  connectivity 4 or 8.
+     *   background   a pixel with id >= K (what frame_report counts nowhere): no region, label 0, index -1, never changed, never votes.
+     *   region       a maximal set of pixels of ONE frame with the same id < K, connected under the connectivity (4: the edge
+     *                neighbours; 8: the corner neighbours as well).  Frames never connect.
+     *   anchor       the region's first pixel in raster order, (y_a, x_a).
+     *   label        1 + (y_a * W + x_a): canonical -- a function of the mask alone, whatever algorithm found the regions.
+     *
+     * mask_regions writes labels = int32 [n][H][W] (whole), in three launches on the stream: a union-find per 32 x 64 tile in LDS, a
+     * pass over the tile edges (find + atomic minimum on the plane itself; at 8 the diagonal pairs at tile corners too), and a pass
+     * that replaces every cell by its root's label.  parent <= own index always holds, so a find strictly descends and a failed
+     * union retries from a strictly smaller index: no loop waits for another thread, and nothing is iterated until stable.
+     * No workspace.  Refused before a launch: a null pointer, n, H or W < 1, n > 65535, K outside 1..255, connectivity not 4 or 8,
+     * H * W >= 2^31 - 1, ceil(H / 32) * ceil(W / 64) >= 2^24 (a frame of 2^24 tiles: thinner than a tile and over 2^29 pixels long). */
+    int (*mask_regions)(const uint8_t* mask, int n, int H, int W, int K, int connectivity, int32_t* labels, fs_stream stream);
+
+    /* The regions of each frame as a table, from the mask and mask_regions' labels (any plane of canonical labels of that mask).
+     *   table  = int64 [n][max_regions][10], rows in ascending anchor (= label) order:
+     *            (class, area, x0, y0, x1, y1, sum_x, sum_y, conf_sum, low_pixels) -- the bounding box inclusive; sum_x / sum_y the sums
+     *            of the pixels' coordinates (centroid = sum / area: the caller divides, the kernel does not); conf_sum the sum of the
+     *            region's confidence codes, low_pixels its pixels with confidence < low (0 <= low <= 255); both 0 when confidence ==
+     *            NULL.  confidence = uint8 [n][H][W] as mask_confidence writes it.
+     *   counts = int64 [n][2] = (regions in the frame, rows written = min(regions, max_regions)).
+     *   index  = int32 [n][H][W]: per pixel the row of its region; -1 for background and for regions beyond max_regions, which get no
+     *            row (the caller sees counts[f][0] > max_regions).
+     * Every call writes its three outputs whole: the table is zeroed on the stream first, so rows at and behind counts[f][1] are zero
+     * and a HIP-graph replay on new masks gives that replay's figures.  1 <= max_regions <= 65536.
+     * workspace = int32 [n][ceil(H * W / 1024)] (per-chunk anchor counts, scanned in place), the caller's; nothing is allocated and
+     * nothing is read on the host.  Refused before a launch: a null pointer (confidence may be NULL), what mask_regions refuses about
+     * n, H, W and K, low outside 0..255, max_regions outside 1..65536. */
+    int (*region_table)(const uint8_t* mask, const int32_t* labels, const uint8_t* confidence, int n, int H, int W, int K, int low, int max_regions,
+                        int64_t* table, int64_t* counts, int32_t* index, int32_t* workspace, fs_stream stream);
+
+    /* Despeckle: one pass of an area filter over region_table's result.  A SPECKLE is a region with a row and area < min_area.  Its
+     * replacement class is the class with the most VOTES, a vote being a pair (pixel p of the speckle, in-frame 4-neighbour q of p)
+     * where q's region has a row and area >= min_area; the vote goes to q's class.  Ties go to the lowest class id; with no vote the
+     * speckle stays as it is.  All votes read the INPUT mask: one pass, not iterated; out differs from mask on speckle pixels only.  (A
+     * 4-neighbour of the same class is in the same region under either connectivity, so a speckle never votes for itself; regions
+     * beyond max_regions are neither speckles nor voters.)  min_area <= 1 gives the input bit for bit.
+     * out = uint8 [n][H][W] at any byte address (dword stores when W % 4 == 0 and out is 4-byte aligned, byte stores otherwise), not
+     * the input plane.  votes = int32 [n][max_regions][K], the caller's workspace, zeroed on the stream by the call; afterwards a
+     * row's first cell holds its replacement class (-1: none).  Refused before a launch: a null pointer, what mask_regions refuses
+     * about n, H, W and K, max_regions outside 1..65536, min_area < 0. */
+    int (*region_filter)(const uint8_t* mask, const int32_t* index, const int64_t* table, int n, int H, int W, int K, int max_regions, int min_area,
+                         uint8_t* out, int32_t* votes, fs_stream stream);
 } fs_ext2_api;
 
 typedef struct fs_hook_tables2 {

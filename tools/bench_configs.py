@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -352,6 +352,57 @@ def main():
                lambda i, no_warp=no_warp: ops.crops_fuse(lo_c[0], lo_c[1], None if no_warp else cg, yx, (713, 713), N, no_warp, (1072, 1920),
                                                          want_canvas=False, want_mask=True),
                lambda i, no_warp=no_warp: crops_conf(i, no_warp))
+    if want("regions"):
+        # connected regions (ops.mask_regions / region_table / region_filter, csrc/region_ops.hip): each op alone at the two geometries
+        # on masks of a blob-like scene (the argmax of smooth random logits: a few large regions and many small ones) with the bytes
+        # each must move at least -- at the default cap of 1024 rows, which these scenes overflow (most regions get no row, no table
+        # atomics and no votes), and at a cap of 32768 that holds every region -- then what the opt-in adds to a window: the masks-only tail against the tail + label + table
+        # (regions=True) and against label + table + filter + label + table (min_region_area=9), alternating, every loop >= 0.5 s.
+        gen = torch.Generator().manual_seed(1800)
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+
+        def alone(label, fn, nbytes):
+            t = min(timed(fn) for _ in range(3))
+            rows.append((f"  {label}: {nbytes / 1e6:.1f} MB, {nbytes / t / 1e12:.3f} TB/s", 1 / t, t * 1e3))
+
+        def regions_of(mask, conf, cap=1024):
+            labels = ops.mask_regions(mask, 5, 8)
+            return ops.region_table(mask, labels, 5, conf, 128, cap)
+
+        def despeckled(mask, conf):
+            table, _, index = regions_of(mask, None)
+            out = ops.region_filter(mask, index, table, 5, 9)
+            return regions_of(out, conf)
+
+        for (hh, ww), hg in (((713, 713), 44), ((1072, 1920), None)):
+            low = torch.randn((N, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            mask, conf = ops.mask_confidence(low, (hh, ww))
+            px = mask.numel()
+            labels = ops.mask_regions(mask, 5, 8)
+            table, counts, index = ops.region_table(mask, labels, 5, conf, 128, 1024)
+            rows.append((f"regions {hh}x{ww} n {N} K 5: {counts[:, 0].tolist()} regions per frame", 0.0, 0.0))
+            alone(f"mask_regions {hh}x{ww} n {N} K 5 (8)", lambda i, m=mask: ops.mask_regions(m, 5, 8), px * (1 + 4 + 4 + 4))
+            for cap in (1024, 32768):
+                table, counts, index = ops.region_table(mask, labels, 5, conf, 128, cap)
+                alone(f"region_table {hh}x{ww} n {N} K 5 + conf, cap {cap}", lambda i, m=mask, l=labels, c=conf, cap=cap: ops.region_table(m, l, 5, c, 128, cap),
+                      px * (4 + 4 + 4 + 4 + 1 + 4) + N * cap * 80)
+                alone(f"region_filter {hh}x{ww} n {N} K 5 min 9, cap {cap}", lambda i, m=mask, x=index, t=table: ops.region_filter(m, x, t, 5, 9),
+                      px * (4 + 4 + 1 + 1) + N * cap * 5 * 4)
+            lo = torch.randn((2, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            gl, gr = (wl, wr) if hg else [[g.to(dev) for g in gs] for gs in synth.make_grids(N, 67, 120, seed=2001, frame=(hh, ww))]
+
+            def tail(i, lo=lo, gl=gl, gr=gr, hh=hh, ww=ww):
+                return ops.seg_tail(lo[0:1], lo[1:2], gl, gr, N, (hh, ww), False, want_logits=False, want_mask=True)[1]
+            alt = [(timed(tail), timed(lambda i: regions_of(tail(i), None)), timed(lambda i: despeckled(tail(i), None)),
+                    timed(lambda i: regions_of(tail(i), None, 32768))) for _ in range(3)]
+            t_old, t_reg, t_flt, t_big = (min(x[j] for x in alt) for j in range(4))
+            rows.append((f"seg_tail {hh}x{ww} warp, masks only", 1 / t_old, t_old * 1e3))
+            rows.append((f"  + regions: {(t_reg / t_old - 1) * 100:+.2f} % ({(t_reg - t_old) * 1e3:+.3f} ms)", 1 / t_reg, t_reg * 1e3))
+            rows.append((f"  + regions, max_regions 32768: {(t_big / t_old - 1) * 100:+.2f} % ({(t_big - t_old) * 1e3:+.3f} ms)", 1 / t_big, t_big * 1e3))
+            rows.append((f"  + min_region_area 9 + regions: {(t_flt / t_old - 1) * 100:+.2f} % ({(t_flt - t_old) * 1e3:+.3f} ms)", 1 / t_flt, t_flt * 1e3))
     if want("cuts"):
         # holding one key frame across a scene cut (ops.window_weights, the weighted instantiations of the fused tails): the weighted
         # call against the unweighted one on the same held logits, alternating (three rounds each, the fastest of each side), every loop

@@ -27,6 +27,13 @@ per-frame, per-class extent report on the device; the masks are unchanged.  `--r
 frame: the frame id and per class the area fraction, the mean confidence (sum / (255 pixels)) and the share of the class's pixels
 with confidence below `--low-confidence` (default 128); without `--confidence` the areas only.  `--conf-out FILE` (needs
 `--confidence`) writes the confidence planes as a headerless 8-bit grey raw video (`ffmpeg -f rawvideo -pix_fmt gray` reads it).
+
+`--regions FILE.csv` (an extension) labels the connected regions of every emitted mask on the device (`--connectivity` 4
+or 8, at most `--max-regions` rows per frame) and writes, once at the end, one row per frame and region: frame, class, area, bounding
+box, centroid and, with `--confidence`, the mean confidence and the low-confidence share.  A frame with more regions than
+`--max-regions` gets a warning and its first rows.  `--min-region N` removes regions smaller than N pixels from the emitted masks (each
+takes the class most of its 4-neighbours have); every output -- masks, overlays, reports, metrics -- then shows the filtered masks.
+The filter works on the first `--max-regions` regions of a frame (in raster order); a frame with more gets a warning after the run.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -46,7 +53,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv, write_regions_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -116,7 +123,16 @@ def parse_args(argv=None):
     ap.add_argument("--report", metavar="FILE.csv", help="write one row per frame: per class the area fraction and, with --confidence, the "
                     "mean confidence and the low-confidence share (single GPU)")
     ap.add_argument("--conf-out", metavar="FILE", help="--confidence: write the confidence planes as 8-bit grey raw video (-pix_fmt gray)")
+    ap.add_argument("--regions", metavar="FILE.csv", help="label the connected regions of every mask on the device and write one row per frame "
+                    "and region: class, area, box, centroid and, with --confidence, mean confidence and low-confidence share (single GPU)")
+    ap.add_argument("--min-region", type=int, default=0, metavar="N", help="remove regions smaller than N pixels from the emitted masks (each takes "
+                    "the class most of its 4-neighbours have); 0 or 1: off.  Only the first --max-regions regions of a frame are filtered: a "
+                    "frame with more gets a warning after the run")
+    ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8], help="--regions / --min-region: 4 = edge neighbours, 8 = corners too")
+    ap.add_argument("--max-regions", type=int, default=1024, metavar="N", help="--regions / --min-region: rows per frame (1..65536)")
     args = ap.parse_args(argv)
+    if args.min_region < 0 or not 1 <= args.max_regions <= 65536:
+        ap.error("--min-region takes N >= 0 and --max-regions 1..65536")
     if args.conf_out and not args.confidence:
         ap.error("--conf-out needs --confidence")
     if not 0 <= args.low_confidence <= 255:
@@ -173,9 +189,10 @@ def main():
     fm = FlowModel(net, feature_based=args.feature_based, no_warp=args.no_warp).eval()
     pred = FlowPredictor(fm, classes=args.classes, out_size=tuple(args.size), crop=None if args.no_cropping else tuple(args.crop),
                          compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache, confidence=args.confidence,
-                         low_confidence=args.low_confidence)
-    if args.report and world > 1:
-        raise SystemExit("--report covers one process's frames: run it on a single GPU")
+                         low_confidence=args.low_confidence, regions=bool(args.regions), min_region_area=args.min_region,
+                         connectivity=args.connectivity, max_regions=args.max_regions)
+    if (args.report or args.regions) and world > 1:
+        raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
@@ -214,7 +231,7 @@ def main():
     frames = 0
     first_mask = last_mask = None
     sources = []  # --hold-cuts: every window's device `source` tensor, read back once after the timed run
-    report_ids, areas = [], []  # --report: the frame ids, and without --confidence every window's device counts
+    report_ids, areas = [], []  # --report / --regions: the frame ids, and without --confidence every window's device counts
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for w in mine:
@@ -283,6 +300,18 @@ def main():
     if args.report:  # the device report is read back ONCE, here, after the timed run
         report = pred.extent_report() if args.confidence else (torch.cat(areas).cpu().numpy() if areas else np.zeros((0, args.classes, 3), np.int64))
         write_extent_csv(args.report, report_ids, report, args.size[0] * args.size[1], with_confidence=args.confidence)
+    if args.min_region > 1:  # the filter pass's counts, read back once after the timed run
+        for fid, total in zip(report_ids, pred.despeckle_counts().tolist()):
+            if total > args.max_regions:
+                print(f"warning: frame {fid} had {total} regions before --min-region, --max-regions {args.max_regions}: only the first "
+                      f"{args.max_regions} (in raster order) were filtered", file=sys.stderr)
+    if args.regions:  # likewise: one read-back after the timed run
+        region_rows, totals = pred.region_report()
+        write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence)
+        for fid, total in zip(report_ids, totals.tolist()):
+            if total > args.max_regions:
+                print(f"warning: frame {fid} has {total} regions, --max-regions {args.max_regions}: the first {args.max_regions} are listed",
+                      file=sys.stderr)
     if world > 1:
         torch.distributed.destroy_process_group()
 
