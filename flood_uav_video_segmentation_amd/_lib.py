@@ -155,6 +155,8 @@ _EXT2_HOOKS = [
     ("mask_regions", c_int, [c_void] + [c_int] * 5 + [c_void, c_void]),
     ("region_table", c_int, [c_void, c_void, c_void] + [c_int] * 6 + [c_void] * 5),
     ("region_filter", c_int, [c_void, c_void, c_void] + [c_int] * 6 + [c_void, c_void, c_void]),
+    ("region_links", c_int, [c_void] * 6 + [c_int] * 6 + [c_void] * 5),
+    ("region_tracks", c_int, [c_void] * 4 + [c_int] * 2 + [c_void] * 3),
 ]
 EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
 

@@ -416,6 +416,19 @@ static int fs_region_filter(const uint8_t* mask, const int32_t* index, const int
                             uint8_t* out, int32_t* votes, fs_stream stream) {
     return fs::launch_region_filter(mask, index, reinterpret_cast<const long long*>(table), n, H, W, K, max_regions, min_area, out, votes, S(stream));
 }
+// region identity across frames (track_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_region_links(const int32_t* index, const int64_t* table, const int64_t* counts, const int32_t* prev_index, const int64_t* prev_table,
+                           const int64_t* prev_counts, int n, int H, int W, int max_regions, int max_pairs, int min_overlap, int32_t* back, int32_t* fwd,
+                           int64_t* link_counts, void* workspace, fs_stream stream) {
+    return fs::launch_region_links(index, reinterpret_cast<const long long*>(table), reinterpret_cast<const long long*>(counts), prev_index,
+                                   reinterpret_cast<const long long*>(prev_table), reinterpret_cast<const long long*>(prev_counts), n, H, W, max_regions,
+                                   max_pairs, min_overlap, back, fwd, reinterpret_cast<long long*>(link_counts), workspace, S(stream));
+}
+static int fs_region_tracks(const int32_t* back, const int32_t* fwd, const int64_t* counts, const int64_t* prev_tracks, int n, int max_regions,
+                            int64_t* state, int64_t* tracks, fs_stream stream) {
+    return fs::launch_region_tracks(back, fwd, reinterpret_cast<const long long*>(counts), reinterpret_cast<const long long*>(prev_tracks), n, max_regions,
+                                    reinterpret_cast<long long*>(state), reinterpret_cast<long long*>(tracks), S(stream));
+}
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
     if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
@@ -518,6 +531,8 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_mask_regions,
         fs_region_table,
         fs_region_filter,
+        fs_region_links,
+        fs_region_tracks,
     }};
     return &all.base.test;
 }

@@ -12,6 +12,9 @@ per-frame, per-class extent report on the device (ops.mask_confidence / canvas_c
 FlowPredictor(..., regions=True) keeps a per-frame table of the masks' connected regions on the device, and min_region_area=N emits
 masks without regions smaller than N pixels (ops.mask_regions / region_table / region_filter):
     rows, totals = p.region_report()                                       # per frame int64 [regions, 10]; read back once
+FlowPredictor(..., regions=True, track=True) also links every frame's regions to those of the frame before it and gives each region a
+track id that lasts as long as the region does (ops.region_links / region_tracks):
+    tracks, overflowed = p.track_report()                                  # per frame int64 [regions, 4], parallel to rows
 """
 import numpy as np
 import torch
@@ -46,13 +49,23 @@ class FlowPredictor:
     re-classed pixel keeps the confidence of its old class.  The filter sees the first max_regions regions of a frame only (in
     raster order of their first pixels): by the definition a region past the cap is neither a speckle nor a voter, so on a frame with
     more regions than max_regions the lower part of the frame is left unfiltered.  The pass's region counts are kept on the device
-    (16 B per frame); despeckle_counts() reads them back so that a caller can see such frames and raise max_regions."""
+    (16 B per frame); despeckle_counts() reads them back so that a caller can see such frames and raise max_regions.
+
+    track=True (extension, needs regions=True): every tabulated frame is linked to the frame emitted before it -- the previous frame of
+    the window, or the last frame of the window before, whose index plane (a copy), table, counts and tracks row the predictor keeps
+    on the device -- by the pixel overlap of regions of one class, compared in place (no motion compensation), and every region gets
+    (track id, parent id, previous row, overlap): a region that is its best predecessor's best successor continues that track, every
+    other one is born with the next id and its best predecessor's track as parent.  A pair needs min_overlap pixels; max_pairs (a
+    power of two, default the next one >= 4 max_regions) is the size of the pair table -- a frame pair with more distinct overlapping
+    pairs gets no links (all its regions are born) and its flag in track_report().  max_regions x 32 B per frame in chunked device
+    buffers beside the region tables.  Ids count from 0 and never restart: reset() (a new video) drops the previous frame, so the next
+    frame's regions are all born, and keeps the next id; clear_report() drops the buffers and keeps both."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
-                 max_regions=1024):
+                 max_regions=1024, track=False, min_overlap=1, max_pairs=None):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -83,14 +96,28 @@ class FlowPredictor:
         self._region_chunks = []  # (int64 [REPORT_CHUNK, max_regions, 10], int64 [REPORT_CHUNK, 2]) device buffers, in frame order
         self._region_frames = 0
         self._despeckle_counts = []  # min_region_area > 1: the filter pass's int64 [n, 2] counts, one device tensor per window
+        if track and not regions:
+            raise ValueError("FlowPredictor: track=True needs regions=True (the tracks follow the region tables' rows)")
+        if int(min_overlap) < 1 or int(min_overlap) >= 2 ** 31:
+            raise ValueError(f"FlowPredictor: min_overlap must be 1..2^31 - 1, got {min_overlap}")
+        pairs = ops.default_max_pairs(self.max_regions) if max_pairs is None else int(max_pairs)
+        if not 16 <= pairs <= 2 ** 20 or pairs & (pairs - 1):
+            raise ValueError(f"FlowPredictor: max_pairs must be a power of two in 16..2^20, got {max_pairs}")
+        self.track = bool(track)
+        self.min_overlap = int(min_overlap)
+        self.max_pairs = pairs
+        self._track_chunks = []   # (int64 [REPORT_CHUNK, max_regions, 4], int64 [REPORT_CHUNK, 2] link counts), in step with _region_chunks
+        self._track_prev = None   # the last tabulated frame: (index [H,W], table [max_regions,10], counts [2], tracks [max_regions,4]), copies
+        self._track_state = None  # device int64 [2] = (next track id, 0)
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
         its predecessor, flow/base.py:247,295 -- which must not be another video's last frame).  The histogram keeps running, and
-        so do the extent report and the region report (clear_report() drops them)."""
+        so do the extent report, the region report and the track ids (clear_report() drops the reports)."""
         if self.key_cache is not None:
             self.key_cache.clear()
         self.last_output = None
+        self._track_prev = None  # the next frame's regions are all born; the next track id is kept
 
     def clear_report(self):
         """Forget the extent report and the region report of the frames predicted so far."""
@@ -99,6 +126,7 @@ class FlowPredictor:
         self._region_chunks = []
         self._region_frames = 0
         self._despeckle_counts = []
+        self._track_chunks = []  # the previous frame and the next track id stay
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -165,10 +193,44 @@ class FlowPredictor:
                                             torch.zeros((self.REPORT_CHUNK, 2), dtype=torch.int64, device=masks.device)))
             take = min(n - done, self.REPORT_CHUNK - row)
             table, counts = self._region_chunks[-1]
-            ops.region_table(masks[done:done + take], labels[done:done + take], self.classes, None if conf is None else conf[done:done + take],
-                             self.low_confidence, self.max_regions, out=(table[row:row + take], counts[row:row + take]))
+            got = ops.region_table(masks[done:done + take], labels[done:done + take], self.classes, None if conf is None else conf[done:done + take],
+                                   self.low_confidence, self.max_regions, out=(table[row:row + take], counts[row:row + take]))
+            if self.track:
+                self._keep_tracks(got[2], table[row:row + take], counts[row:row + take], row)
             done += take
             self._region_frames += take
+
+    def _keep_tracks(self, index, table, counts, row):
+        """Links and track ids of the piece region_table just wrote (rows row.. of the newest chunk), against the frame tabulated before
+        it; then that piece's last frame becomes the previous frame.  Nothing is read back."""
+        take, dev = index.shape[0], index.device
+        if row == 0:
+            self._track_chunks.append((torch.zeros((self.REPORT_CHUNK, self.max_regions, 4), dtype=torch.int64, device=dev),
+                                       torch.zeros((self.REPORT_CHUNK, 2), dtype=torch.int64, device=dev)))
+        if self._track_state is None:
+            self._track_state = torch.zeros(2, dtype=torch.int64, device=dev)
+        prev = self._track_prev
+        back, fwd, link_counts = ops.region_links(index, table, counts, None if prev is None else prev[:3], self.max_pairs, self.min_overlap)
+        tracks, flags = self._track_chunks[-1]
+        ops.region_tracks(back, fwd, counts, self._track_state, None if prev is None else prev[3], out=tracks[row:row + take])
+        flags[row:row + take].copy_(link_counts)
+        self._track_prev = (index[-1].clone(), table[-1].clone(), counts[-1].clone(), tracks[row + take - 1].clone())
+
+    def track_report(self):
+        """track=True: (tracks, overflowed) for every frame of region_report(), in its order: tracks[f] = int64 numpy [rows, 4] = (track
+        id, parent id, the row of the best predecessor in the frame before or -1, the overlap with it), row for row region_report()'s
+        rows[f]; overflowed = int64 numpy [frames], 1 where the frame's pair table overflowed (all its regions were born: raise
+        max_pairs).  The read-back happens here, chunk by chunk."""
+        if not self._track_chunks:
+            return [], np.zeros((0,), dtype=np.int64)
+        rows, flags, left = [], [], self._region_frames
+        for (tracks, link_counts), (_, counts) in zip(self._track_chunks, self._region_chunks):
+            take = min(left, self.REPORT_CHUNK)
+            c, t = counts[:take].cpu().numpy(), tracks[:take].cpu().numpy()
+            rows.extend(t[f, :int(c[f, 1])] for f in range(take))
+            flags.append(link_counts[:take, 1].cpu().numpy())
+            left -= take
+        return rows, np.concatenate(flags)
 
     def _finish(self, masks, conf, n, to_host):
         """Despeckle, score, keep the reports, and hand out what the caller asked for: masks, or (masks, conf) with confidence=True."""
@@ -422,20 +484,49 @@ def write_extent_csv(path, frame_ids, report, frame_pixels, with_confidence=True
             f.write(",".join(cells) + "\n")
 
 
-def write_regions_csv(path, frame_ids, rows, with_confidence=True):
+def write_regions_csv(path, frame_ids, rows, with_confidence=True, tracks=None):
     """One CSV row per frame and region from FlowPredictor.region_report()'s rows (per frame int64 [regions, 10]): frame id, the
     region's number in the frame, class, area, the inclusive box x0, y0, x1, y1, the centroid cx = sum_x / area, cy = sum_y / area,
-    and with_confidence: conf = conf_sum / (255 area) (mean confidence) and low = low-confidence pixels / area."""
+    and with_confidence: conf = conf_sum / (255 area) (mean confidence) and low = low-confidence pixels / area.  tracks =
+    FlowPredictor.track_report()'s rows (per frame int64 [regions, 4]): the columns track, parent (-1: none) and overlap (the pixels
+    shared with the best predecessor in the frame before) are appended; None: the file without them, byte for byte."""
     if len(frame_ids) != len(rows):
         raise ValueError(f"write_regions_csv: one frame id per frame, got {len(frame_ids)} ids for {len(rows)} frames")
+    if tracks is not None and (len(tracks) != len(rows) or any(len(t) != len(r) for t, r in zip(tracks, rows))):
+        raise ValueError("write_regions_csv: tracks must hold one row per region of every frame")
     with open(path, "w") as fh:
-        fh.write("frame,region,class,area,x0,y0,x1,y1,cx,cy" + (",conf,low" if with_confidence else "") + "\n")
-        for fid, frame in zip(frame_ids, rows):
+        fh.write("frame,region,class,area,x0,y0,x1,y1,cx,cy" + (",conf,low" if with_confidence else "") + (",track,parent,overlap" if tracks is not None else "")
+                 + "\n")
+        for f, (fid, frame) in enumerate(zip(frame_ids, rows)):
             for r, (cls, area, x0, y0, x1, y1, sx, sy, cs, lo) in enumerate(np.asarray(frame).tolist()):
                 cells = [str(fid), str(r), str(cls), str(area), str(x0), str(y0), str(x1), str(y1), f"{sx / area:.3f}", f"{sy / area:.3f}"]
                 if with_confidence:
                     cells += [f"{cs / (255.0 * area):.6f}", f"{lo / area:.6f}"]
+                if tracks is not None:
+                    tid, parent, _, overlap = np.asarray(tracks[f][r]).tolist()
+                    cells += [str(tid), str(parent), str(overlap)]
                 fh.write(",".join(cells) + "\n")
+
+
+def write_tracks_csv(path, frame_ids, rows, tracks):
+    """The growth summary: one CSV row per track, in id order, from region_report()'s rows and track_report()'s tracks: track id, class,
+    parent track (-1: none), the first and the last frame it was seen in, the number of frames, its area in the first and in the last of
+    them, its largest area and the (first) frame of that."""
+    if len(frame_ids) != len(rows) or len(tracks) != len(rows) or any(len(t) != len(r) for t, r in zip(tracks, rows)):
+        raise ValueError(f"write_tracks_csv: one frame id and one tracks row per region of every frame, got {len(frame_ids)} ids, {len(rows)} and "
+                         f"{len(tracks)} frames")
+    seen = {}  # id -> [class, parent, first frame, last frame, frames, first area, last area, max area, frame of the max]
+    for fid, frame, links in zip(frame_ids, rows, tracks):
+        for region, link in zip(np.asarray(frame).tolist(), np.asarray(links).tolist()):
+            tid, area = link[0], region[1]
+            t = seen.setdefault(tid, [region[0], link[1], fid, fid, 0, area, area, area, fid])
+            t[3], t[4], t[6] = fid, t[4] + 1, area
+            if area > t[7]:
+                t[7], t[8] = area, fid
+    with open(path, "w") as fh:
+        fh.write("track,class,parent,first_frame,last_frame,frames,first_area,last_area,max_area,max_frame\n")
+        for tid in sorted(seen):
+            fh.write(",".join(str(v) for v in [tid] + seen[tid]) + "\n")
 
 
 def colorize(masks_u8, palette=PALETTE):

@@ -620,6 +620,91 @@ def region_filter(mask, index, table, classes, min_area):
     return out
 
 
+# ------------------------------------------------------------------------------------------ region identity across frames
+def default_max_pairs(max_regions):
+    """The pair table of region_links by default: the next power of two >= 4 x max_regions (at least 16)."""
+    return max(16, 1 << (4 * int(max_regions) - 1).bit_length())
+
+
+def region_links_workspace_bytes(n, max_regions, max_pairs):
+    """FS_REGION_LINKS_WORKSPACE_BYTES of include/floodseg_test.h."""
+    return n * (12 * max_pairs + 16 * max_regions + 8)
+
+
+def _int64_2d(t, shape, name, what):
+    if t.dtype != torch.int64 or tuple(t.shape) != shape:
+        raise RuntimeError(f"floodseg.{what}: {name} must be int64 {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def region_links(index, table, counts, prev=None, max_pairs=None, min_overlap=1):
+    """region_table's (index int32 [n,H,W], table int64 [n,R,10], counts int64 [n,2]) of consecutive frames -> (back int32 [n,R,2],
+    fwd int32 [n,R,2], link_counts int64 [n,2]) (definition: include/floodseg_test.h, region_links): back[f][b] = (row, overlap) of the
+    row of frame f-1 that shares the most pixels with row b of frame f among the rows of b's class, fwd[f][a] the same for row a of frame
+    f-1 among the rows of frame f; (-1, 0) without a partner of at least min_overlap pixels.  prev = (index [H,W], table [R,10], counts
+    [2]) of the frame before frame 0, None: frame 0 has no links.  max_pairs: the slots of the pair table, a power of two in 16..2^20
+    (default: the next one >= 4 R); a frame pair with more distinct overlapping pairs has no links at all and link_counts[f] = (max_pairs,
+    1).  The workspace is allocated here."""
+    lib = _lib.load()
+    dev = one_device(index, table, counts, *(prev or ()), what="floodseg.region_links")
+    if index.dtype != torch.int32 or index.dim() != 3:
+        raise RuntimeError(f"floodseg.region_links: index must be int32 [n,H,W], got {index.dtype} {tuple(index.shape)}")
+    n, h, w = index.shape
+    if table.dtype != torch.int64 or table.dim() != 3 or table.shape[0] != n or table.shape[2] != 10 or not 1 <= table.shape[1] <= 65536:
+        raise RuntimeError(f"floodseg.region_links: table must be int64 [{n},max_regions,10], got {table.dtype} {tuple(table.shape)}")
+    cap = table.shape[1]
+    counts = _int64_2d(counts, (n, 2), "counts", "region_links")
+    if h < 1 or w < 1 or h * w >= 2 ** 31 - 1 or n > 65535:
+        raise RuntimeError(f"floodseg.region_links: at most 65535 non-empty frames below 2^31 - 1 pixels, got {tuple(index.shape)}")
+    pairs = default_max_pairs(cap) if max_pairs is None else int(max_pairs)
+    if not 16 <= pairs <= 2 ** 20 or pairs & (pairs - 1) or int(min_overlap) < 1 or int(min_overlap) >= 2 ** 31:
+        raise RuntimeError(f"floodseg.region_links: max_pairs must be a power of two in 16..2^20 and min_overlap >= 1, got {max_pairs} and {min_overlap}")
+    if prev is not None:
+        if len(prev) != 3 or prev[0].dtype != torch.int32 or tuple(prev[0].shape) != (h, w):
+            raise RuntimeError(f"floodseg.region_links: prev must be (index int32 [{h},{w}], table int64 [{cap},10], counts int64 [2])")
+        prev = (prev[0].contiguous(), _int64_2d(prev[1], (cap, 10), "prev table", "region_links"), _int64_2d(prev[2], (2,), "prev counts", "region_links"))
+    with torch.cuda.device(dev):
+        back = torch.empty((n, cap, 2), dtype=torch.int32, device=dev)
+        fwd = torch.empty((n, cap, 2), dtype=torch.int32, device=dev)
+        link_counts = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        if n:
+            work = torch.empty((region_links_workspace_bytes(n, cap, pairs) // 8,), dtype=torch.int64, device=dev)
+            p = prev or (None, None, None)
+            check(lib.fs_region_links(ptr(index.contiguous()), ptr(table.contiguous()), ptr(counts), ptr(p[0]), ptr(p[1]), ptr(p[2]), n, h, w, cap, pairs,
+                                      int(min_overlap), ptr(back), ptr(fwd), ptr(link_counts), ptr(work), stream_ptr()))
+    return back, fwd, link_counts
+
+
+def region_tracks(back, fwd, counts, state, prev_tracks=None, out=None):
+    """region_links' back / fwd and the frames' counts -> tracks int64 [n,R,4] = (track id, parent id, previous row, overlap with it)
+    (definition: include/floodseg_test.h, region_tracks): a region whose best predecessor's best successor it is continues that track;
+    every other region is born, with the next ids in row order and its best predecessor's track as parent (-1: none).  state = a
+    device int64 [2] = (next id, 0), read and updated in place.  prev_tracks = the int64 [R,4] tracks row of the frame before frame 0
+    (None: every region of frame 0 is born without a parent).  out: a caller-owned contiguous int64 [n,R,4] destination (rows of a larger
+    buffer); it is written whole."""
+    lib = _lib.load()
+    dev = one_device(back, fwd, counts, state, prev_tracks, out, what="floodseg.region_tracks")
+    if back.dtype != torch.int32 or back.dim() != 3 or back.shape[2] != 2 or not 1 <= back.shape[1] <= 65536 or back.shape[0] > 65535:
+        raise RuntimeError(f"floodseg.region_tracks: back must be int32 [n,max_regions,2], got {back.dtype} {tuple(back.shape)}")
+    n, cap = back.shape[0], back.shape[1]
+    if fwd.dtype != torch.int32 or fwd.shape != back.shape:
+        raise RuntimeError(f"floodseg.region_tracks: fwd must be int32 {list(back.shape)}, got {fwd.dtype} {tuple(fwd.shape)}")
+    counts = _int64_2d(counts, (n, 2), "counts", "region_tracks")
+    if state.dtype != torch.int64 or tuple(state.shape) != (2,) or not state.is_contiguous():
+        raise RuntimeError(f"floodseg.region_tracks: state must be a contiguous int64 [2] tensor, got {state.dtype} {tuple(state.shape)}")
+    if prev_tracks is not None:
+        prev_tracks = _int64_2d(prev_tracks, (cap, 4), "prev_tracks", "region_tracks")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((n, cap, 4), dtype=torch.int64, device=dev)
+        elif out.dtype != torch.int64 or tuple(out.shape) != (n, cap, 4) or not out.is_contiguous():
+            raise RuntimeError(f"floodseg.region_tracks: out must be a contiguous int64 [{n},{cap},4] tensor, got {out.dtype} {tuple(out.shape)}")
+        if n:
+            check(lib.fs_region_tracks(ptr(back.contiguous()), ptr(fwd.contiguous()), ptr(counts), ptr(prev_tracks), n, cap, ptr(state), ptr(out),
+                                       stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ block motion estimation
 def block_match(cur, ref, search=16, penalty=0, return_cost=False):
     """Full-search block matching of two uint8 frames [H,W] (luma) or [H,W,3] (RGB as decoded), `ref` the past frame: the motion-vector

@@ -432,6 +432,50 @@ typedef struct fs_ext2_api {
      * about n, H, W and K, max_regions outside 1..65536, min_area < 0. */
     int (*region_filter)(const uint8_t* mask, const int32_t* index, const int64_t* table, int n, int H, int W, int K, int max_regions, int min_area,
                          uint8_t* out, int32_t* votes, fs_stream stream);
+
+    /* ---- Region identity across frames (csrc/track_ops.hip, csrc/track_defs.h).  OUR DEFINITION.  Integers throughout;
+     * every result is a function of the inputs alone, whatever the hash function and whatever order threads arrive in.  R = max_regions.
+     * Two consecutive frames f-1 and f, both with region_table's index plane, table and counts at the same R:
+     *   overlap(a, b)  the number of pixels p with index[f-1][p] == a and index[f][p] == b, a a row of frame f-1 (0 <= a < its
+     *                  counts[1]) and b a row of frame f, BOTH ROWS OF THE SAME CLASS (table column 0).  Pixels are compared in place:
+     *                  no motion compensation.  Background and regions past the cap (index -1) take no part.
+     *   back[f][b]     (a, overlap(a, b)) for the row a with the largest overlap with b, the lowest a on a tie; (-1, 0) when that
+     *                  overlap is below min_overlap (>= 1).
+     *   fwd[f][a]      the same from the other side, indexed by the rows of frame f-1: (b, overlap(a, b)) for the row b of frame f with
+     *                  the largest overlap with a, the lowest b on a tie; (-1, 0) likewise.
+     *   pairs          the distinct (a, b) with overlap >= 1 are counted in a table of max_pairs slots, a power of two in 16 .. 2^20.
+     *                  A frame pair OVERFLOWS exactly when it has more than max_pairs such pairs (an insertion probes every slot
+     *                  before it gives up); then back[f] and fwd[f] are (-1, 0) throughout.
+     * region_links: index = int32 [n][H][W], table = int64 [n][R][10], counts = int64 [n][2].  Frame f >= 1 is linked to frame f-1 of
+     * the call, frame 0 to the frame prev_index [H][W] / prev_table [R][10] / prev_counts [2]; these three are all NULL when there is
+     * none, and frame 0 then gets (-1, 0) throughout and link_counts (0, 0).  Outputs, each written whole by every call (so a HIP-graph
+     * replay on new planes gives that replay's links):
+     *   back, fwd    = int32 [n][R][2]
+     *   link_counts  = int64 [n][2] = (pairs stored, overflow 0 | 1); an overflowing pair stores max_pairs.
+     * workspace = FS_REGION_LINKS_WORKSPACE_BYTES(n, R, max_pairs) bytes at an 8-byte aligned address, the caller's: per frame the
+     * keys (8 B x max_pairs), the packed best values (8 B x 2 R), two 32-bit figures and the pair counts (4 B x max_pairs).  It is
+     * cleared on the stream; nothing is allocated, synchronised or read on the host.
+     * Refused before a launch: a null pointer (prev_* may be NULL together), prev_* given in part, n, H or W < 1, n > 65535, R outside
+     * 1..65536, max_pairs not a power of two in 16 .. 2^20, min_overlap < 1, H * W >= 2^31 - 1, a workspace not aligned to 8 bytes. */
+#define FS_REGION_LINKS_WORKSPACE_BYTES(n, R, max_pairs) ((size_t)(n) * (12 * (size_t)(max_pairs) + 16 * (size_t)(R) + 8))
+    int (*region_links)(const int32_t* index, const int64_t* table, const int64_t* counts, const int32_t* prev_index, const int64_t* prev_table,
+                        const int64_t* prev_counts, int n, int H, int W, int max_regions, int max_pairs, int min_overlap, int32_t* back, int32_t* fwd,
+                        int64_t* link_counts, void* workspace, fs_stream stream);
+
+    /* Track ids from region_links' result.  Row b of frame f CONTINUES row a of frame f-1 exactly when back[f][b].row == a >= 0,
+     * fwd[f][a].row == b and a has a track; it then has a's track id and a's parent id.  Every other region with a row (b <
+     * counts[f][1]) is BORN: the born regions of a frame take the ids next_id, next_id + 1, ... in ascending row order, next_id
+     * advances by their number, and a born region's parent is the track id of back[f][b].row, -1 when it has none.  So a split leaves
+     * the larger piece on the old track and the others born with that parent; a merge continues the larger contributor and the other
+     * track ends, its fwd pointing into the merged region; no id occurs twice in a frame.
+     *   tracks = int64 [n][R][4] = (track id, parent id, previous row, overlap with it), the last two back[f][b] as given; rows at and
+     *            behind counts[f][1] are (-1, -1, -1, 0).  Written whole.
+     *   prev_tracks = int64 [R][4], the tracks row of the frame before frame 0, or NULL: every region of frame 0 is then born with
+     *            parent -1.   state = int64 [2] = (next id, 0) on the device, read and updated (ids count from 0 and never restart).
+     * Two launches: the rows without a region are filled in parallel, then one workgroup walks the frames in order.  Refused before a launch: a null pointer (prev_tracks may be NULL),
+     * n < 1, n > 65535, R outside 1..65536. */
+    int (*region_tracks)(const int32_t* back, const int32_t* fwd, const int64_t* counts, const int64_t* prev_tracks, int n, int max_regions,
+                         int64_t* state, int64_t* tracks, fs_stream stream);
 } fs_ext2_api;
 
 typedef struct fs_hook_tables2 {

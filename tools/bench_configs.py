@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions tracks cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | tracks | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -403,6 +403,69 @@ def main():
             rows.append((f"  + regions: {(t_reg / t_old - 1) * 100:+.2f} % ({(t_reg - t_old) * 1e3:+.3f} ms)", 1 / t_reg, t_reg * 1e3))
             rows.append((f"  + regions, max_regions 32768: {(t_big / t_old - 1) * 100:+.2f} % ({(t_big - t_old) * 1e3:+.3f} ms)", 1 / t_big, t_big * 1e3))
             rows.append((f"  + min_region_area 9 + regions: {(t_flt / t_old - 1) * 100:+.2f} % ({(t_flt - t_old) * 1e3:+.3f} ms)", 1 / t_flt, t_flt * 1e3))
+    if want("tracks"):
+        # region identity across frames (ops.region_links / region_tracks, csrc/track_ops.hip): each op alone per call of N frames at the two
+        # geometries on the closed-form lattice scene of the region tests (tests/regions_ref.py: disjoint 10 x 15 rectangles and one
+        # serpentine; 1981 regions a frame at 713 x 713, 5361 at 1072 x 1920) moving by 3 pixels per frame, frame 0 linked to a frame
+        # before it -- at a cap of 1024 rows (the scene overflows it: the lower part of the frame takes no part) and at 32768 -- with the
+        # bytes each must move at least; then what track=True adds to a window over regions=True alone (tail + label + table against tail +
+        # label + table + links + tracks + the copies of the last frame), alternating, every loop >= 0.5 s.
+        import numpy as np
+
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import regions_ref
+        gen = torch.Generator().manual_seed(1900)
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+
+        def alone(label, fn, nbytes):
+            t = min(timed(fn) for _ in range(3))
+            rows.append((f"  {label}: {nbytes / 1e6:.1f} MB, {nbytes / t / 1e12:.3f} TB/s", 1 / t, t * 1e3))
+
+        for (hh, ww), hg in (((713, 713), 44), ((1072, 1920), None)):
+            plane = regions_ref.lattice_scene(1, -(-hh // 16) * 16, -(-ww // 24) * 24)[0][0]
+            mask = torch.from_numpy(np.stack([np.roll(plane, 3 * f, 1)[:hh, :ww] for f in range(N + 1)])).to(dev)
+            labels = ops.mask_regions(mask, 4, 8)
+            px = N * hh * ww
+            for cap in (1024, 32768):
+                table, counts, index = ops.region_table(mask, labels, 4, None, 128, cap)
+                prev = (index[0].clone(), table[0].clone(), counts[0].clone())
+                index, table, counts = index[1:].contiguous(), table[1:].contiguous(), counts[1:].contiguous()
+                pairs = ops.default_max_pairs(cap)
+                state = torch.zeros(2, dtype=torch.int64, device=dev)
+                back, fwd, lc = ops.region_links(index, table, counts, prev)
+                seed = ops.region_tracks(back, fwd, counts, state)[0].clone()  # stands for the tracks row of the frame before
+                out = torch.empty((N, cap, 4), dtype=torch.int64, device=dev)
+                rows.append((f"tracks {hh}x{ww} n {N} cap {cap}: rows {counts[:, 1].tolist()}, pairs / overflow {lc.tolist()} of {pairs} slots", 0.0, 0.0))
+                alone(f"region_links {hh}x{ww} n {N} cap {cap}, max_pairs {pairs}", lambda i, x=index, t=table, c=counts, p=prev: ops.region_links(x, t, c, p),
+                      px * 8 + ops.region_links_workspace_bytes(N, cap, pairs) + N * cap * 16)
+                alone(f"region_tracks n {N} cap {cap}", lambda i, b=back, f=fwd, c=counts, s=state, p=seed, o=out: ops.region_tracks(b, f, c, s, p, out=o),
+                      N * cap * (16 + 32 + 32))
+            lo = torch.randn((2, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            gl, gr = (wl, wr) if hg else [[g.to(dev) for g in gs] for gs in synth.make_grids(N, 67, 120, seed=2001, frame=(hh, ww))]
+
+            def tail(i, lo=lo, gl=gl, gr=gr, hh=hh, ww=ww):
+                return ops.seg_tail(lo[0:1], lo[1:2], gl, gr, N, (hh, ww), False, want_logits=False, want_mask=True)[1]
+
+            def regions_of(m, cap):
+                return ops.region_table(m, ops.mask_regions(m, 5, 8), 5, None, 128, cap)
+
+            kept = {}
+
+            def tracked(m, cap):  # what FlowPredictor._keep_tracks does behind the table
+                table, counts, index = regions_of(m, cap)
+                prev, st = kept.get(cap), kept.setdefault(("state", cap), torch.zeros(2, dtype=torch.int64, device=dev))
+                back, fwd, _ = ops.region_links(index, table, counts, None if prev is None else prev[:3])
+                tracks = ops.region_tracks(back, fwd, counts, st, None if prev is None else prev[3])
+                kept[cap] = (index[-1].clone(), table[-1].clone(), counts[-1].clone(), tracks[-1].clone())
+
+            for cap in (1024, 32768):
+                alt = [(timed(lambda i: regions_of(tail(i), cap)), timed(lambda i: tracked(tail(i), cap))) for _ in range(3)]
+                t_reg, t_trk = (min(x[j] for x in alt) for j in range(2))
+                rows.append((f"seg_tail {hh}x{ww} warp + regions, max_regions {cap}", 1 / t_reg, t_reg * 1e3))
+                rows.append((f"  + track: {(t_trk / t_reg - 1) * 100:+.2f} % ({(t_trk - t_reg) * 1e3:+.3f} ms)", 1 / t_trk, t_trk * 1e3))
     if want("cuts"):
         # holding one key frame across a scene cut (ops.window_weights, the weighted instantiations of the fused tails): the weighted
         # call against the unweighted one on the same held logits, alternating (three rounds each, the fastest of each side), every loop

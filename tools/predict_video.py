@@ -34,6 +34,13 @@ box, centroid and, with `--confidence`, the mean confidence and the low-confiden
 `--max-regions` gets a warning and its first rows.  `--min-region N` removes regions smaller than N pixels from the emitted masks (each
 takes the class most of its 4-neighbours have); every output -- masks, overlays, reports, metrics -- then shows the filtered masks.
 The filter works on the first `--max-regions` regions of a frame (in raster order); a frame with more gets a warning after the run.
+`--tracks FILE.csv` (an extension; needs `--regions`) follows the regions from frame to frame on the device: a region that
+shares at least `--min-overlap` pixels with its best predecessor of the same class (compared in place), and is that one's best
+successor, keeps its track id; every other region starts a new track with its best predecessor's track as parent.  The regions CSV gets
+the columns track, parent and overlap, and FILE.csv one row per track: class, parent, first and last frame, frames seen, first / last /
+largest area and the frame of the largest -- the growth summary.  `--max-pairs` sizes the table of overlapping pairs of a frame pair (a
+power of two); a frame whose table overflowed gets a warning and all its regions start new tracks.  Single process only: ids are per
+predictor.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -53,7 +60,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv, write_regions_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv, write_regions_csv, write_tracks_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -130,7 +137,18 @@ def parse_args(argv=None):
                     "frame with more gets a warning after the run")
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8], help="--regions / --min-region: 4 = edge neighbours, 8 = corners too")
     ap.add_argument("--max-regions", type=int, default=1024, metavar="N", help="--regions / --min-region: rows per frame (1..65536)")
+    ap.add_argument("--tracks", metavar="FILE.csv", help="--regions: follow the regions from frame to frame on the device; the regions CSV gets "
+                    "the columns track, parent and overlap, and FILE.csv one row per track (class, parent, first / last frame, frames, first / "
+                    "last / largest area): the growth summary (single process)")
+    ap.add_argument("--min-overlap", type=int, default=1, metavar="N", help="--tracks: a region continues its predecessor only if they share at "
+                    "least N pixels")
+    ap.add_argument("--max-pairs", type=int, default=None, metavar="N", help="--tracks: slots of the table of overlapping region pairs of two "
+                    "consecutive frames, a power of two in 16..1048576 (default: the next one >= 4 x --max-regions)")
     args = ap.parse_args(argv)
+    if args.tracks and not args.regions:
+        ap.error("--tracks needs --regions")
+    if args.min_overlap < 1 or (args.max_pairs is not None and (not 16 <= args.max_pairs <= 2 ** 20 or args.max_pairs & (args.max_pairs - 1))):
+        ap.error("--min-overlap takes N >= 1 and --max-pairs a power of two in 16..1048576")
     if args.min_region < 0 or not 1 <= args.max_regions <= 65536:
         ap.error("--min-region takes N >= 0 and --max-regions 1..65536")
     if args.conf_out and not args.confidence:
@@ -187,10 +205,13 @@ def main():
     net = (FlowPSPNet if args.arch == "pspnet" else FlowDeepLabv3)(HP()).eval()
     load_weights(net, args)
     fm = FlowModel(net, feature_based=args.feature_based, no_warp=args.no_warp).eval()
+    if args.tracks and world > 1:
+        raise SystemExit("--tracks: track ids are per predictor and joining the ranks' blocks is out of scope: run it in a single process")
     pred = FlowPredictor(fm, classes=args.classes, out_size=tuple(args.size), crop=None if args.no_cropping else tuple(args.crop),
                          compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache, confidence=args.confidence,
                          low_confidence=args.low_confidence, regions=bool(args.regions), min_region_area=args.min_region,
-                         connectivity=args.connectivity, max_regions=args.max_regions)
+                         connectivity=args.connectivity, max_regions=args.max_regions, track=bool(args.tracks), min_overlap=args.min_overlap,
+                         max_pairs=args.max_pairs)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
@@ -307,7 +328,14 @@ def main():
                       f"{args.max_regions} (in raster order) were filtered", file=sys.stderr)
     if args.regions:  # likewise: one read-back after the timed run
         region_rows, totals = pred.region_report()
-        write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence)
+        track_rows, overflowed = pred.track_report() if args.tracks else (None, [])
+        write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence, tracks=track_rows)
+        if args.tracks:
+            write_tracks_csv(args.tracks, report_ids, region_rows, track_rows)
+            for fid, flag in zip(report_ids, overflowed.tolist()):
+                if flag:
+                    print(f"warning: frame {fid}: the pair table overflowed (--max-pairs {pred.max_pairs}): its regions all start new tracks",
+                          file=sys.stderr)
         for fid, total in zip(report_ids, totals.tolist()):
             if total > args.max_regions:
                 print(f"warning: frame {fid} has {total} regions, --max-regions {args.max_regions}: the first {args.max_regions} are listed",
