@@ -157,6 +157,7 @@ _EXT2_HOOKS = [
     ("region_filter", c_int, [c_void, c_void, c_void] + [c_int] * 6 + [c_void, c_void, c_void]),
     ("region_links", c_int, [c_void] * 6 + [c_int] * 6 + [c_void] * 5),
     ("region_tracks", c_int, [c_void] * 4 + [c_int] * 2 + [c_void] * 3),
+    ("region_links_mc", c_int, [c_void] * 8 + [c_int] * 8 + [c_void] * 5),
 ]
 EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
 

@@ -429,6 +429,15 @@ static int fs_region_tracks(const int32_t* back, const int32_t* fwd, const int64
     return fs::launch_region_tracks(back, fwd, reinterpret_cast<const long long*>(counts), reinterpret_cast<const long long*>(prev_tracks), n, max_regions,
                                     reinterpret_cast<long long*>(state), reinterpret_cast<long long*>(tracks), S(stream));
 }
+static int fs_region_links_mc(const int32_t* index, const int64_t* table, const int64_t* counts, const int32_t* prev_index, const int64_t* prev_table,
+                              const int64_t* prev_counts, const int32_t* mv, const int32_t* pair_stats, int n, int H, int W, int frame_h, int frame_w,
+                              int max_regions, int max_pairs, int min_overlap, int32_t* back, int32_t* fwd, int64_t* link_counts, void* workspace,
+                              fs_stream stream) {
+    return fs::launch_region_links_mc(index, reinterpret_cast<const long long*>(table), reinterpret_cast<const long long*>(counts), prev_index,
+                                      reinterpret_cast<const long long*>(prev_table), reinterpret_cast<const long long*>(prev_counts), mv, pair_stats, n, H, W,
+                                      frame_h, frame_w, max_regions, max_pairs, min_overlap, back, fwd, reinterpret_cast<long long*>(link_counts), workspace,
+                                      S(stream));
+}
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
     if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
@@ -533,6 +542,7 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_region_filter,
         fs_region_links,
         fs_region_tracks,
+        fs_region_links_mc,
     }};
     return &all.base.test;
 }

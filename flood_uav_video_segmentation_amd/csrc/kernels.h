@@ -360,11 +360,15 @@ int launch_region_table(const uint8_t* mask, const int* labels, const uint8_t* c
 int launch_region_filter(const uint8_t* mask, const int* index, const long long* table, int n, int H, int W, int K, int max_regions,
                          int min_area, uint8_t* out, int* votes, hipStream_t s);
 
-// Region identity across frames (track_ops.hip, track_defs.h; definitions: include/floodseg_test.h).  Both launchers refuse bad arguments
+// Region identity across frames (track_ops.hip, track_defs.h; definitions: include/floodseg_test.h).  The launchers refuse bad arguments
 // before they launch anything; the workspace is the caller's (FS_REGION_LINKS_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_links(const int* index, const long long* table, const long long* counts, const int* prev_index, const long long* prev_table,
                         const long long* prev_counts, int n, int H, int W, int max_regions, int max_pairs, int min_overlap, int* back, int* fwd,
                         long long* link_counts, void* workspace, hipStream_t s);
+// mv: int32 [n][(frame_h / 16) * (frame_w / 16)][7], pair_stats: int32 [n][4] or nullptr; workspace: FS_REGION_LINKS_MC_WORKSPACE_BYTES
+int launch_region_links_mc(const int* index, const long long* table, const long long* counts, const int* prev_index, const long long* prev_table,
+                           const long long* prev_counts, const int* mv, const int* pair_stats, int n, int H, int W, int frame_h, int frame_w,
+                           int max_regions, int max_pairs, int min_overlap, int* back, int* fwd, long long* link_counts, void* workspace, hipStream_t s);
 int launch_region_tracks(const int* back, const int* fwd, const long long* counts, const long long* prev_tracks, int n, int max_regions,
                          long long* state, long long* tracks, hipStream_t s);
 

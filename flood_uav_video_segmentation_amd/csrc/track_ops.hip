@@ -1,6 +1,7 @@
-// Region identity across frames (include/floodseg_test.h: region_links, region_tracks).  OUR DEFINITION -- the
-// reference emits hard masks only.  Opt-in passes behind region_table: nothing on the shipped routes calls them.
+// Region identity across frames (include/floodseg_test.h: region_links, region_links_mc, region_tracks).  OUR
+// DEFINITION -- the reference emits hard masks only.  Opt-in passes behind region_table: nothing on the shipped routes calls them.
 //   region_links    index planes + tables of consecutive frames -> per row its best-overlapping row of the other frame, both ways
+//   region_links_mc the same with the frame before gathered at every pixel's SOURCE under the block matcher's vectors
 //   region_tracks   the links -> a track id per region: continued from the frame before, or born
 // Integers throughout, and every result is a function of the inputs alone: the pair counts are integer sums, the best partner is an
 // integer maximum, and whether the pair table overflows depends on the number of distinct pairs only (track_defs.h, probe_slot).
@@ -42,17 +43,49 @@ __device__ __forceinline__ int rows_of(const long long* counts, int R) {  // row
     return (int)(c < 0 ? 0 : (c > R ? R : c));
 }
 
+// ------------------------------------------------------------------ pass 0 (region_links_mc): one packed shift per block
+// What the compensated overlap pass needs on top of the in-place one's arguments; empty for the in-place instantiation.
+template <bool MC>
+struct Motion {};
+template <>
+struct Motion<true> {
+    const unsigned* shifts;  // [n][hb * wb]: trk::mc_row_shift of every table row, behind the pair tables in the workspace
+    const int* pair_stats;   // [n][4], block_match_modes' stats, or nullptr
+    int FH, FW, hb, wb;      // the decoded frame and its blocks
+};
+
+// One table row per thread, grid = (blocks / 256, frames): 28 bytes in, 4 bytes out, so that the overlap pass reads one cache-resident
+// dword per pixel (the same one for 16 neighbours) and not a row.  A cut pair's flag word is set here, after the zeroing: the overlap
+// pass skips that pair and the unpack pass writes it like an overflowing one.
+__global__ __launch_bounds__(256) void track_shift_kernel(const int* __restrict__ mv, const int* __restrict__ pair_stats, const int* prev_index, int H, int W,
+                                                          int FH, int FW, int blocks, int R, unsigned max_pairs, unsigned long long* ws,
+                                                          unsigned* __restrict__ shifts) {
+    const int f = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    if (k < blocks) shifts[(size_t)f * blocks + k] = trk::mc_row_shift(mv + ((size_t)f * blocks + k) * trk::MC_VECTOR_INTS, H, W, FH, FW);
+    if (k == 0 && pair_stats && (f || prev_index)) {
+        const unsigned cut = trk::cut_flag(pair_stats + 4 * (size_t)f);
+        if (cut) pair_space(ws, f, R, max_pairs).flags[1] = cut;
+    }
+}
+
 // ------------------------------------------------------------------ pass 1: the overlap of every (a, b) pair
 // grid = (256-pixel row pieces, rows, frames), as region_accumulate_kernel: a wave is 64 consecutive pixels of one row.  Runs of equal
 // (a, b) inside the wave are found with a ballot, and the run's first lane inserts the pair and adds the run's length: one insertion
 // per run, not per pixel.  Frame 0 without a frame before it does nothing (the whole workgroup leaves before any cross-lane op).
+// MC: a is gathered at the pixel's source (track_defs.h: the block column is the thread's own, the block row the row's; the packed shift
+// of the block comes from pass 0), -1 where the source lies outside the mask; runs of equal (a, b) are runs whatever the sources.  A
+// cut pair does nothing.
+template <bool MC>
 __global__ __launch_bounds__(256) void track_overlap_kernel(const int* __restrict__ index, const long long* __restrict__ table,
                                                             const long long* __restrict__ counts, const int* __restrict__ prev_index,
                                                             const long long* __restrict__ prev_table, const long long* __restrict__ prev_counts,
-                                                            int H, int W, int R, unsigned max_pairs, unsigned long long* ws) {
+                                                            int H, int W, int R, unsigned max_pairs, unsigned long long* ws, Motion<MC> mo) {
     const int f = blockIdx.z;
     const size_t HW = (size_t)H * W;
     if (f == 0 && !prev_index) return;
+    if constexpr (MC) {
+        if (mo.pair_stats && trk::cut_flag(mo.pair_stats + 4 * (size_t)f)) return;
+    }
     const int* ia = f ? index + (size_t)(f - 1) * HW : prev_index;
     const long long* ta = f ? table + (size_t)(f - 1) * R * 10 : prev_table;
     const int rows_a = rows_of(f ? counts + 2 * (size_t)(f - 1) : prev_counts, R);
@@ -63,9 +96,24 @@ __global__ __launch_bounds__(256) void track_overlap_kernel(const int* __restric
     const int x = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
     const bool valid = x < W;
     const int xc = min(x, W - 1);
+    int bx = 0;
+    const unsigned* shifts = nullptr;
+    if constexpr (MC) {
+        bx = trk::mc_block(xc, W, mo.FW);
+        shifts = mo.shifts + (size_t)f * mo.hb * mo.wb;
+    }
     for (int y = blockIdx.y; y < H; y += gridDim.y) {
         const size_t i = (size_t)y * W + xc;
-        const int a = ia[i], b = ib[i];
+        int a;
+        if constexpr (MC) {
+            const int by = trk::mc_block(y, H, mo.FH);
+            const unsigned shift = by < mo.hb && bx < mo.wb ? shifts[(size_t)by * mo.wb + bx] : 0u;  // the remainder strip: no shift
+            int ys, xs;
+            a = trk::mc_source(y, xc, shift, H, W, &ys, &xs) ? ia[(size_t)ys * W + xs] : -1;
+        } else {
+            a = ia[i];
+        }
+        const int b = ib[i];
         const bool ok = valid && a >= 0 && a < rows_a && b >= 0 && b < rows_b;  // background and rows past the cap take no part
         const int ka = ok ? a : -1, kb = ok ? b : -1;
         const int pa = __shfl_up(ka, 1), pb = __shfl_up(kb, 1);
@@ -114,11 +162,12 @@ __global__ __launch_bounds__(256) void track_unpack_kernel(int R, unsigned max_p
                                                            int* __restrict__ fwd, long long* __restrict__ link_counts) {
     const int f = blockIdx.y;
     const PairSpace sp = pair_space(ws, f, R, max_pairs);
-    const bool overflow = sp.flags[1] != 0u;
+    const unsigned word = sp.flags[1];
+    const bool overflow = word != 0u;  // the pair table overflowed, or (region_links_mc) the pair is a cut: no links either way
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r == 0) {
         link_counts[2 * (size_t)f] = sp.flags[0];
-        link_counts[2 * (size_t)f + 1] = overflow ? 1 : 0;
+        link_counts[2 * (size_t)f + 1] = trk::link_flags(word);
     }
     if (r >= R) return;
     const size_t at = ((size_t)f * R + r) * 2;
@@ -205,29 +254,78 @@ int track_sizes(const char* what, int n, int max_regions) {
     return 0;
 }
 
+// what both link ops refuse, in region_links' order; `what` names the op in the message
+int links_checks(const char* what, const void* index, const void* table, const void* counts, const void* prev_index, const void* prev_table,
+                 const void* prev_counts, int n, int H, int W, int max_regions, int max_pairs, int min_overlap, const void* back, const void* fwd,
+                 const void* link_counts, const void* workspace) {
+    FS_REQUIRE(index && table && counts && back && fwd && link_counts && workspace, "%s: null pointer", what);
+    FS_REQUIRE(H >= 1 && W >= 1, "%s: sizes must be >= 1, got %dx%d", what, H, W);
+    if (int rc = track_sizes(what, n, max_regions)) return rc;
+    FS_REQUIRE((int64_t)H * W < ((int64_t)1 << 31) - 1, "%s: a frame of 2^31 - 1 pixels or more (%dx%d)", what, H, W);
+    FS_REQUIRE(max_pairs >= trk::MIN_PAIRS && max_pairs <= trk::MAX_PAIRS && (max_pairs & (max_pairs - 1)) == 0,
+               "%s: max_pairs=%d must be a power of two in %d..%d", what, max_pairs, trk::MIN_PAIRS, trk::MAX_PAIRS);
+    FS_REQUIRE(min_overlap >= 1, "%s: min_overlap=%d must be >= 1", what, min_overlap);
+    const int given = (prev_index != nullptr) + (prev_table != nullptr) + (prev_counts != nullptr);
+    FS_REQUIRE(given == 0 || given == 3, "%s: the previous frame is given in part (prev_index, prev_table and prev_counts go together)", what);
+    FS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "%s: the workspace is not aligned to 8 bytes", what);
+    return 0;
+}
+
+// the launches both link ops share: everything but the overlap pass (and region_links_mc's pass 0 in front of it)
+void launch_zero(unsigned long long* ws, int n, int max_regions, int max_pairs, hipStream_t s) {
+    const size_t words = (size_t)n * pair_words(max_regions, (unsigned)max_pairs);
+    hipLaunchKernelGGL(track_zero_kernel, dim3((unsigned)std::min<size_t>((words + 255) / 256, 1u << 20)), dim3(256), 0, s, ws, words);
+}
+void launch_best_unpack(const int* prev_index, int n, int max_regions, int max_pairs, int min_overlap, unsigned long long* ws, int* back, int* fwd,
+                        long long* link_counts, hipStream_t s) {
+    hipLaunchKernelGGL(track_best_kernel, dim3((unsigned)cdiv(max_pairs, 256), (unsigned)n), dim3(256), 0, s, prev_index, max_regions, (unsigned)max_pairs, ws);
+    hipLaunchKernelGGL(track_unpack_kernel, dim3((unsigned)cdiv(max_regions, 256), (unsigned)n), dim3(256), 0, s, max_regions, (unsigned)max_pairs,
+                       min_overlap, ws, back, fwd, link_counts);
+}
+
 }  // namespace
 
 int launch_region_links(const int* index, const long long* table, const long long* counts, const int* prev_index, const long long* prev_table,
                         const long long* prev_counts, int n, int H, int W, int max_regions, int max_pairs, int min_overlap, int* back, int* fwd,
                         long long* link_counts, void* workspace, hipStream_t s) {
-    FS_REQUIRE(index && table && counts && back && fwd && link_counts && workspace, "region_links: null pointer");
-    FS_REQUIRE(H >= 1 && W >= 1, "region_links: sizes must be >= 1, got %dx%d", H, W);
-    if (int rc = track_sizes("region_links", n, max_regions)) return rc;
-    FS_REQUIRE((int64_t)H * W < ((int64_t)1 << 31) - 1, "region_links: a frame of 2^31 - 1 pixels or more (%dx%d)", H, W);
-    FS_REQUIRE(max_pairs >= trk::MIN_PAIRS && max_pairs <= trk::MAX_PAIRS && (max_pairs & (max_pairs - 1)) == 0,
-               "region_links: max_pairs=%d must be a power of two in %d..%d", max_pairs, trk::MIN_PAIRS, trk::MAX_PAIRS);
-    FS_REQUIRE(min_overlap >= 1, "region_links: min_overlap=%d must be >= 1", min_overlap);
-    const int given = (prev_index != nullptr) + (prev_table != nullptr) + (prev_counts != nullptr);
-    FS_REQUIRE(given == 0 || given == 3, "region_links: the previous frame is given in part (prev_index, prev_table and prev_counts go together)");
-    FS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "region_links: the workspace is not aligned to 8 bytes");
+    if (int rc = links_checks("region_links", index, table, counts, prev_index, prev_table, prev_counts, n, H, W, max_regions, max_pairs, min_overlap, back,
+                              fwd, link_counts, workspace))
+        return rc;
     unsigned long long* ws = static_cast<unsigned long long*>(workspace);
-    const size_t words = (size_t)n * pair_words(max_regions, (unsigned)max_pairs);
-    hipLaunchKernelGGL(track_zero_kernel, dim3((unsigned)std::min<size_t>((words + 255) / 256, 1u << 20)), dim3(256), 0, s, ws, words);
-    hipLaunchKernelGGL(track_overlap_kernel, dim3((unsigned)cdiv(W, 256), (unsigned)std::min(H, 65535), (unsigned)n), dim3(256), 0, s, index, table, counts,
-                       prev_index, prev_table, prev_counts, H, W, max_regions, (unsigned)max_pairs, ws);
-    hipLaunchKernelGGL(track_best_kernel, dim3((unsigned)cdiv(max_pairs, 256), (unsigned)n), dim3(256), 0, s, prev_index, max_regions, (unsigned)max_pairs, ws);
-    hipLaunchKernelGGL(track_unpack_kernel, dim3((unsigned)cdiv(max_regions, 256), (unsigned)n), dim3(256), 0, s, max_regions, (unsigned)max_pairs,
-                       min_overlap, ws, back, fwd, link_counts);
+    launch_zero(ws, n, max_regions, max_pairs, s);
+    hipLaunchKernelGGL(track_overlap_kernel<false>, dim3((unsigned)cdiv(W, 256), (unsigned)std::min(H, 65535), (unsigned)n), dim3(256), 0, s, index, table,
+                       counts, prev_index, prev_table, prev_counts, H, W, max_regions, (unsigned)max_pairs, ws, Motion<false>{});
+    launch_best_unpack(prev_index, n, max_regions, max_pairs, min_overlap, ws, back, fwd, link_counts, s);
+    FS_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_region_links_mc(const int* index, const long long* table, const long long* counts, const int* prev_index, const long long* prev_table,
+                           const long long* prev_counts, const int* mv, const int* pair_stats, int n, int H, int W, int frame_h, int frame_w,
+                           int max_regions, int max_pairs, int min_overlap, int* back, int* fwd, long long* link_counts, void* workspace, hipStream_t s) {
+    if (int rc = links_checks("region_links_mc", index, table, counts, prev_index, prev_table, prev_counts, n, H, W, max_regions, max_pairs, min_overlap,
+                              back, fwd, link_counts, workspace))
+        return rc;
+    FS_REQUIRE(mv, "region_links_mc: null pointer (mv)");
+    FS_REQUIRE(frame_h >= trk::MC_BLOCK && frame_w >= trk::MC_BLOCK, "region_links_mc: the decoded frame must hold a block of %d, got frame %dx%d",
+               trk::MC_BLOCK, frame_h, frame_w);
+    FS_REQUIRE((int64_t)frame_h * frame_w < ((int64_t)1 << 31), "region_links_mc: a decoded frame of 2^31 pixels or more (%dx%d)", frame_h, frame_w);
+    // the packed shifts are 16-bit: |shift| <= 1024 * mask / frame + 1/2 must stay below 2^15 (track_defs.h)
+    FS_REQUIRE(H <= (int64_t)trk::MC_MAX_SCALE * frame_h && W <= (int64_t)trk::MC_MAX_SCALE * frame_w,
+               "region_links_mc: the mask (%dx%d) may be at most %d times the decoded frame (%dx%d) along an axis", H, W, trk::MC_MAX_SCALE, frame_h,
+               frame_w);
+    unsigned long long* ws = static_cast<unsigned long long*>(workspace);
+    Motion<true> mo;
+    mo.FH = frame_h, mo.FW = frame_w, mo.hb = frame_h / trk::MC_BLOCK, mo.wb = frame_w / trk::MC_BLOCK;
+    const int blocks = mo.hb * mo.wb;  // < 2^23
+    unsigned* shifts = reinterpret_cast<unsigned*>(ws + (size_t)n * pair_words(max_regions, (unsigned)max_pairs));
+    mo.shifts = shifts, mo.pair_stats = pair_stats;
+    launch_zero(ws, n, max_regions, max_pairs, s);
+    hipLaunchKernelGGL(track_shift_kernel, dim3((unsigned)cdiv(blocks, 256), (unsigned)n), dim3(256), 0, s, mv, pair_stats, prev_index, H, W, frame_h, frame_w,
+                       blocks, max_regions, (unsigned)max_pairs, ws, shifts);
+    hipLaunchKernelGGL(track_overlap_kernel<true>, dim3((unsigned)cdiv(W, 256), (unsigned)std::min(H, 65535), (unsigned)n), dim3(256), 0, s, index, table,
+                       counts, prev_index, prev_table, prev_counts, H, W, max_regions, (unsigned)max_pairs, ws, mo);
+    launch_best_unpack(prev_index, n, max_regions, max_pairs, min_overlap, ws, back, fwd, link_counts, s);
     FS_HIP(hipGetLastError());
     return 0;
 }

@@ -35,6 +35,13 @@ def _grid_source(grids, search, penalty, intra_bias=None, scene_cut=None):
     return GridEstimator(search, penalty, intra_bias=intra_bias, scene_cut=scene_cut)
 
 
+def _check_link_vectors(who, link_vectors, grids):
+    """link_vectors hands out the block matcher's tables: the grids/ folders hold grids, from which no vector can be recovered."""
+    if link_vectors and grids != "estimate":
+        raise ValueError(f'{who}: link_vectors needs the estimated grids\' motion-vector tables (grids="estimate"); the grids/ folders hold grids, not vectors')
+    return bool(link_vectors)
+
+
 def _check_hold_cuts(who, hold_cuts, grids, scene_cut):
     """hold_cuts reacts to the cut flags the grid estimator's matcher writes: without them it could never do anything."""
     if hold_cuts and (grids != "estimate" or scene_cut is None):
@@ -53,13 +60,21 @@ class PredictWindows:
     "source" (int32 [frame_delta]), device tensors from ops.window_weights on the cut flags of the window's frame_delta frame pairs:
     FlowPredictor hands the weights to the tails, which then hold one key frame across a cut instead of blending two scenes.  One
     more search per window (the closing pair); with no_warp every pair is searched -- and every in-between frame decoded -- for its
-    flag alone."""
+    flag alone.
+
+    link_vectors=True (extension; needs grids="estimate"): an item also carries "link_mvs" (int32 [frame_delta, blocks, 7]: per emitted
+    frame the matcher's table of that frame against the frame before it, all void for frame 0), "link_frame_size" (the decoded frame's
+    height and width) and, with intra_bias / scene_cut set, "link_stats" (int32 [frame_delta, 4], the same pairs' stats rows): what
+    FlowPredictor(compensate=True) links the regions with.  One more search per window (the pair that ends in the window's key frame),
+    unless hold_cuts has searched it; with no_warp every pair is searched for its vectors alone."""
 
     hold_cuts = False
+    link_vectors = False
 
     def __init__(self, data_root, predict_v_id, frame_delta=5, no_warp=False, size=None, device="cuda", grids="files", search=16,
-                 penalty=0, intra_bias=None, scene_cut=None, hold_cuts=False):
+                 penalty=0, intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False):
         self.hold_cuts = _check_hold_cuts("PredictWindows", hold_cuts, grids, scene_cut)
+        self.link_vectors = _check_link_vectors("PredictWindows", link_vectors, grids)
         self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
         self.data_root, self.video_id = data_root, predict_v_id
         self.frame_delta, self.no_warp = frame_delta, no_warp
@@ -185,7 +200,20 @@ class PredictWindows:
             item["mvs_right"] = [self._grid(i, "inv_grids") for i in inv]
         if self.hold_cuts:
             item["weights"], item["source"] = self._cut_weights(index)
+        if self.link_vectors:
+            self._link_keys(item, f_index)
         return item
+
+    def _link_keys(self, item, f_index):
+        """link_mvs, link_frame_size and link_stats of the window that emits frames f_index .. f_index + frame_delta - 1; asked for after
+        the item's grids (and weights), so that only the pairs nobody has searched yet are searched."""
+        est = self._video_estimator()
+        item["link_mvs"] = est.window_tables(f_index, self.frame_delta, self.raw_frame)
+        frame = self.raw_frame(f_index)
+        item["link_frame_size"] = (int(frame.shape[0]), int(frame.shape[1]))
+        stats = est.window_link_stats(f_index, self.frame_delta)
+        if stats is not None:
+            item["link_stats"] = stats
 
 
 def read_label_list(data_list, frame_delta):
@@ -323,15 +351,17 @@ class RawVideoWindows(PredictWindows):
     pix_fmt "nv12" (Y plane + interleaved UV), "i420" (= yuv420p: Y, U, V planes) or "rgb24"; frames are read through numpy.memmap and
     uploaded once each; the network's input comes from ops.prepare_frame (`matrix`, `full_range`: the integer YUV -> RGB conversion of
     include/floodseg_test.h).  len = frames // frame_delta; a file that is not a whole number of frames raises.  A raw file has no grid
-    folders: the grids are estimated (grids="estimate", flow/motion.py) unless no_warp; "files" raises.  hold_cuts: as PredictWindows'.
+    folders: the grids are estimated (grids="estimate", flow/motion.py) unless no_warp; "files" raises.  hold_cuts, link_vectors: as
+    PredictWindows'.
 
     For the YUV formats the block matcher gets the stream's Y plane AS IT IS (its one-channel route).  These grids DIFFER from grids
     estimated on the RGB conversion of the same video: there the matcher reduces RGB to its own luma (77 R + 150 G + 29 B + 128) >> 8,
     which is not the stream's Y (range, matrix and the clipping of the conversion all enter)."""
 
     def __init__(self, path, height, width, pix_fmt, frame_delta=5, no_warp=False, size=None, grids="estimate", search=16, penalty=0,
-                 matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None, hold_cuts=False):
+                 matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False):
         self.hold_cuts = _check_hold_cuts("RawVideoWindows", hold_cuts, grids, scene_cut)
+        self.link_vectors = bool(link_vectors)
         if pix_fmt not in RAW_PIX_FMTS:
             raise ValueError(f"RawVideoWindows: pix_fmt must be one of {RAW_PIX_FMTS}, got {pix_fmt!r}")
         if grids == "files":

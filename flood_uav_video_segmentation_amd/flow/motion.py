@@ -19,6 +19,11 @@ What a cut does to the BLEND of the two key frames is the window datasets' hold_
 hands the cut flags of a window's frame pairs -- the closing pair (last in-between frame -> next key frame) included, which feeds no
 grid and is searched for this alone -- to ops.window_weights, and the tails hold one key frame's chain on each side of the cut
 (include/floodseg_test.h, window_weights).  Without hold_cuts a cut between two key frames still blends the two scenes linearly.
+
+The TABLES themselves have a second consumer: the motion-compensated region links (ops.region_links with mv=) read the
+integer vectors, which the grids cannot replace -- a grid cell keeps only the source BLOCK of a vector, so any vector of -8..+7 pixels
+is the identity there.  GridEstimator.table_for / window_tables hand them out (the window datasets' link_vectors=True); the block
+search of a frame pair is shared with grids_for, whichever is asked first.
 """
 import warnings
 from collections import OrderedDict
@@ -49,6 +54,17 @@ def _warn_cut_without_bias(intra_bias, scene_cut):
                       "(give intra_bias as well, e.g. 0)", stacklevel=3)
 
 
+VOID_ROW = (-1, 16, 16, -16, -16, -16, -16)
+
+
+def _search(cur, ref, search, penalty, intra_bias, scene_cut):
+    """(table, stats) of the block search of `cur` against the past frame `ref`; stats None with both decisions off."""
+    if intra_bias is None and scene_cut is None:
+        return ops.block_match(cur, ref, search=search, penalty=penalty), None
+    return ops.block_match_modes(cur, ref, search=search, penalty=penalty, intra_bias=65535 if intra_bias is None else intra_bias,
+                                 scene_cut=scene_cut, return_stats=True)
+
+
 def estimate_grids(cur, ref, search=16, penalty=0, intra_bias=None, scene_cut=None, return_stats=False):
     """(grid, inv_grid) of frame `cur` against the past frame `ref`: float64 CUDA [67,120,2], normalised with the frame's own height
     and width (extract_motion_vectors.py:94-98).  Enqueues only: nothing is read back to the host.
@@ -57,12 +73,7 @@ def estimate_grids(cur, ref, search=16, penalty=0, intra_bias=None, scene_cut=No
     return_stats appends the call's device stats tensor int32 [4] (None when both are off): how GridEstimator gets at it."""
     check_geometry(int(cur.shape[0]), int(cur.shape[1]))
     _warn_cut_without_bias(intra_bias, scene_cut)
-    stats = None
-    if intra_bias is None and scene_cut is None:
-        table = ops.block_match(cur, ref, search=search, penalty=penalty)
-    else:
-        table, stats = ops.block_match_modes(cur, ref, search=search, penalty=penalty, intra_bias=65535 if intra_bias is None else intra_bias,
-                                             scene_cut=scene_cut, return_stats=True)
+    table, stats = _search(cur, ref, search, penalty, intra_bias, scene_cut)
     with torch.cuda.device(table.device):
         grids = motion_vectors_to_grids(table, int(cur.shape[0]), int(cur.shape[1]), validate=False)
     return (*grids, stats) if return_stats else grids
@@ -74,7 +85,11 @@ class GridEstimator:
     grids_for(frame_id, load_frame) -> (grid, inv_grid) float64 CUDA [67,120,2]; load_frame(i) returns the decoded uint8 frame
     [H,W,3] (or [H,W]) on the GPU, or None when frame i does not exist.  Frame 0, and a frame whose predecessor is missing, get the
     default grid twice: an I-frame carries no vectors in the reference's pipeline either.  The last `cache` results and the last
-    two decoded frames are kept (neighbouring windows ask for neighbouring frames)."""
+    two decoded frames are kept (neighbouring windows ask for neighbouring frames).
+
+    table_for(frame_id, load_frame) -> the int32 [blocks, 7] device table of frame_id against frame_id - 1 (an all-void table for frame
+    0 and for a frame whose predecessor is missing); window_tables stacks a window's.  Cached like the grids, and ONE block search per
+    frame pair serves both: grids_for takes the table table_for has searched, and the other way round."""
 
     STATS_CHUNK = 256
 
@@ -91,6 +106,7 @@ class GridEstimator:
         _warn_cut_without_bias(intra_bias, scene_cut)
         self._cache_size = int(cache)
         self._grids = OrderedDict()
+        self._tables = OrderedDict()  # frame id -> int32 [blocks, 7]: the searches, shared by grids_for and table_for
         self._frames = OrderedDict()
         self._stats = {}        # frame id -> one row of a chunk below
         self._stat_chunks = []  # int32 [STATS_CHUNK, 4] device buffers: one allocation per STATS_CHUNK estimated pairs, not one per pair
@@ -98,6 +114,7 @@ class GridEstimator:
     def reset(self):
         """Forget every cached frame, grid and stats tensor (the caller moves to another video)."""
         self._grids.clear()
+        self._tables.clear()
         self._frames.clear()
         self._stats.clear()
         self._stat_chunks.clear()
@@ -133,12 +150,54 @@ class GridEstimator:
                 ref = self._frame(j - 1, load_frame) if j > 0 else None
                 cur = self._frame(j, load_frame) if ref is not None else None
                 if cur is not None:
-                    _, stats = ops.block_match_modes(cur, ref, search=self.search, penalty=self.penalty,
-                                                     intra_bias=65535 if self.intra_bias is None else self.intra_bias,
-                                                     scene_cut=self.scene_cut, return_stats=True)
-                    self._keep_stats(j, stats)
+                    self._table(j, cur, ref)
             out.append(self._stats.get(j))
         return out
+
+    def _table(self, frame_id, cur, ref):
+        """The table of the pair (frame_id - 1, frame_id), searched once: kept among the last `cache` tables, its stats kept for good."""
+        if frame_id in self._tables:
+            self._tables.move_to_end(frame_id)
+            return self._tables[frame_id]
+        table, stats = _search(cur, ref, self.search, self.penalty, self.intra_bias, self.scene_cut)
+        if stats is not None:
+            self._keep_stats(frame_id, stats)
+        self._tables[frame_id] = table
+        while len(self._tables) > self._cache_size:
+            self._tables.popitem(last=False)
+        return table
+
+    def table_for(self, frame_id, load_frame):
+        """The int32 [blocks, 7] device table of frame_id against frame_id - 1, as ops.region_links takes it (mv=).  Frame 0, or a frame
+        whose predecessor is missing, gets an all-void table: no vectors, as for an I-frame."""
+        if frame_id in self._tables:
+            self._tables.move_to_end(frame_id)
+            return self._tables[frame_id]
+        cur = self._frame(frame_id, load_frame)
+        if cur is None:
+            raise FileNotFoundError(f"GridEstimator: frame {frame_id} does not exist")
+        ref = self._frame(frame_id - 1, load_frame) if frame_id > 0 else None
+        if ref is None:
+            blocks = (int(cur.shape[0]) // BLOCK) * (int(cur.shape[1]) // BLOCK)
+            return torch.tensor(VOID_ROW, dtype=torch.int32, device=cur.device).repeat(blocks, 1)
+        return self._table(frame_id, cur, ref)
+
+    def window_tables(self, first_id, n, load_frame):
+        """int32 [n, blocks, 7]: the tables of the pairs ending in frames first_id .. first_id + n - 1, the frames a window whose previous
+        key frame is first_id emits.  The first pair (the last frame of the window before -> this window's key frame) feeds no grid of
+        any window: one more search per window, unless window_stats (hold_cuts) has searched it as the window before's closing pair."""
+        return torch.stack([self.table_for(j, load_frame) for j in range(first_id, first_id + n)])
+
+    def window_link_stats(self, first_id, n):
+        """int32 [n, 4]: the stats rows of the same pairs (zeros for a pair without stats: no cut), after window_tables; None with both
+        decisions off."""
+        if self.intra_bias is None and self.scene_cut is None:
+            return None
+        rows = [self._stats.get(j) for j in range(first_id, first_id + n)]
+        some = next((r for r in rows if r is not None), None)
+        if some is None:
+            return None
+        return torch.stack([torch.zeros_like(some) if r is None else r for r in rows])
 
     def _frame(self, frame_id, load_frame):
         if frame_id in self._frames:
@@ -163,10 +222,10 @@ class GridEstimator:
             default = torch.from_numpy(get_default_grid()).to(cur.device)
             out = (default, default.clone())
         else:
-            *out, stats = estimate_grids(cur, ref, self.search, self.penalty, self.intra_bias, self.scene_cut, return_stats=True)
-            out = tuple(out)
-            if stats is not None:
-                self._keep_stats(frame_id, stats)
+            check_geometry(int(cur.shape[0]), int(cur.shape[1]))
+            table = self._table(frame_id, cur, ref)  # the search estimate_grids would make, shared with table_for
+            with torch.cuda.device(table.device):
+                out = tuple(motion_vectors_to_grids(table, int(cur.shape[0]), int(cur.shape[1]), validate=False))
         self._grids[frame_id] = out
         while len(self._grids) > self._cache_size:
             self._grids.popitem(last=False)

@@ -15,6 +15,9 @@ masks without regions smaller than N pixels (ops.mask_regions / region_table / r
 FlowPredictor(..., regions=True, track=True) also links every frame's regions to those of the frame before it and gives each region a
 track id that lasts as long as the region does (ops.region_links / region_tracks):
     tracks, overflowed = p.track_report()                                  # per frame int64 [regions, 4], parallel to rows
+FlowPredictor(..., regions=True, track=True, compensate=True) compares each frame with the frame before it READ AT THE SOURCE of every
+pixel under the block matcher's vectors, which the estimate-mode window datasets hand out with link_vectors=True (ops.region_links with
+mv=): a region that moves further than its own width per frame keeps its track.
 """
 import numpy as np
 import torch
@@ -59,13 +62,19 @@ class FlowPredictor:
     power of two, default the next one >= 4 max_regions) is the size of the pair table -- a frame pair with more distinct overlapping
     pairs gets no links (all its regions are born) and its flag in track_report().  max_regions x 32 B per frame in chunked device
     buffers beside the region tables.  Ids count from 0 and never restart: reset() (a new video) drops the previous frame, so the next
-    frame's regions are all born, and keeps the next id; clear_report() drops the buffers and keeps both."""
+    frame's regions are all born, and keeps the next id; clear_report() drops the buffers and keeps both.
+
+    compensate=True (extension, needs track=True): the links are motion-compensated -- every window must then come with link_mvs (int32
+    [n, blocks, 7]: per emitted frame the block matcher's table of that frame against the frame before it), link_frame_size (the decoded
+    frame's height and width) and optionally link_stats (int32 [n, 4], block_match_modes' stats rows: a pair flagged as a scene cut
+    gets no links and its flag in track_report(with_cuts=True)).  A window without link_mvs raises: there is no silent fall-back to the
+    in-place comparison.  The first frame after reset() has no frame before it, so its vectors are ignored."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
-                 max_regions=1024, track=False, min_overlap=1, max_pairs=None):
+                 max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -103,7 +112,10 @@ class FlowPredictor:
         pairs = ops.default_max_pairs(self.max_regions) if max_pairs is None else int(max_pairs)
         if not 16 <= pairs <= 2 ** 20 or pairs & (pairs - 1):
             raise ValueError(f"FlowPredictor: max_pairs must be a power of two in 16..2^20, got {max_pairs}")
+        if compensate and not track:
+            raise ValueError("FlowPredictor: compensate=True needs track=True (it changes how the tracks' links are counted)")
         self.track = bool(track)
+        self.compensate = bool(compensate)
         self.min_overlap = int(min_overlap)
         self.max_pairs = pairs
         self._track_chunks = []   # (int64 [REPORT_CHUNK, max_regions, 4], int64 [REPORT_CHUNK, 2] link counts), in step with _region_chunks
@@ -181,7 +193,19 @@ class FlowPredictor:
         self._despeckle_counts.append(counts)
         return ops.region_filter(masks, index, table, self.classes, self.min_region_area)
 
-    def _keep_regions(self, masks, conf):
+    def _link_inputs(self, n, link_mvs, link_frame_size, link_stats):
+        """compensate=True: the window's (mvs [n, blocks, 7], frame size, stats [n, 4] or None), checked; None otherwise."""
+        if not self.compensate:
+            return None
+        if link_mvs is None or link_frame_size is None:
+            raise ValueError("FlowPredictor: compensate=True needs link_mvs and link_frame_size with every window (an estimate-mode dataset with "
+                             "link_vectors=True provides them); the links are never compared in place instead")
+        if link_mvs.dim() != 3 or link_mvs.shape[0] != n or (link_stats is not None and tuple(link_stats.shape) != (n, 4)):
+            raise ValueError(f"FlowPredictor: link_mvs must be [n, blocks, 7] and link_stats [n, 4] for the window's n = {n} frames, got "
+                             f"{tuple(link_mvs.shape)} and {None if link_stats is None else tuple(link_stats.shape)}")
+        return link_mvs, (int(link_frame_size[0]), int(link_frame_size[1])), link_stats
+
+    def _keep_regions(self, masks, conf, link=None):
         """The window's region tables into the next rows of the chunked buffers (region_table writes its rows whole; nothing is read)."""
         masks = masks.contiguous()
         labels = ops.mask_regions(masks, self.classes, self.connectivity)
@@ -196,13 +220,15 @@ class FlowPredictor:
             got = ops.region_table(masks[done:done + take], labels[done:done + take], self.classes, None if conf is None else conf[done:done + take],
                                    self.low_confidence, self.max_regions, out=(table[row:row + take], counts[row:row + take]))
             if self.track:
-                self._keep_tracks(got[2], table[row:row + take], counts[row:row + take], row)
+                piece = None if link is None else (link[0][done:done + take], link[1], None if link[2] is None else link[2][done:done + take])
+                self._keep_tracks(got[2], table[row:row + take], counts[row:row + take], row, piece)
             done += take
             self._region_frames += take
 
-    def _keep_tracks(self, index, table, counts, row):
+    def _keep_tracks(self, index, table, counts, row, link=None):
         """Links and track ids of the piece region_table just wrote (rows row.. of the newest chunk), against the frame tabulated before
-        it; then that piece's last frame becomes the previous frame.  Nothing is read back."""
+        it; then that piece's last frame becomes the previous frame.  Nothing is read back.  link: the piece's (mvs, frame size, stats)
+        under compensate=True."""
         take, dev = index.shape[0], index.device
         if row == 0:
             self._track_chunks.append((torch.zeros((self.REPORT_CHUNK, self.max_regions, 4), dtype=torch.int64, device=dev),
@@ -210,19 +236,24 @@ class FlowPredictor:
         if self._track_state is None:
             self._track_state = torch.zeros(2, dtype=torch.int64, device=dev)
         prev = self._track_prev
-        back, fwd, link_counts = ops.region_links(index, table, counts, None if prev is None else prev[:3], self.max_pairs, self.min_overlap)
+        if link is None:
+            back, fwd, link_counts = ops.region_links(index, table, counts, None if prev is None else prev[:3], self.max_pairs, self.min_overlap)
+        else:
+            back, fwd, link_counts = ops.region_links(index, table, counts, None if prev is None else prev[:3], self.max_pairs, self.min_overlap,
+                                                      mv=link[0], frame_size=link[1], pair_stats=link[2])
         tracks, flags = self._track_chunks[-1]
         ops.region_tracks(back, fwd, counts, self._track_state, None if prev is None else prev[3], out=tracks[row:row + take])
         flags[row:row + take].copy_(link_counts)
         self._track_prev = (index[-1].clone(), table[-1].clone(), counts[-1].clone(), tracks[row + take - 1].clone())
 
-    def track_report(self):
+    def track_report(self, with_cuts=False):
         """track=True: (tracks, overflowed) for every frame of region_report(), in its order: tracks[f] = int64 numpy [rows, 4] = (track
         id, parent id, the row of the best predecessor in the frame before or -1, the overlap with it), row for row region_report()'s
         rows[f]; overflowed = int64 numpy [frames], 1 where the frame's pair table overflowed (all its regions were born: raise
-        max_pairs).  The read-back happens here, chunk by chunk."""
+        max_pairs).  with_cuts=True appends cuts = int64 numpy [frames], 1 where compensate=True found the pair flagged as a scene cut
+        (all its regions were born as well).  The read-back happens here, chunk by chunk."""
         if not self._track_chunks:
-            return [], np.zeros((0,), dtype=np.int64)
+            return ([], np.zeros((0,), dtype=np.int64)) + ((np.zeros((0,), dtype=np.int64),) if with_cuts else ())
         rows, flags, left = [], [], self._region_frames
         for (tracks, link_counts), (_, counts) in zip(self._track_chunks, self._region_chunks):
             take = min(left, self.REPORT_CHUNK)
@@ -230,29 +261,32 @@ class FlowPredictor:
             rows.extend(t[f, :int(c[f, 1])] for f in range(take))
             flags.append(link_counts[:take, 1].cpu().numpy())
             left -= take
-        return rows, np.concatenate(flags)
+        flags = np.concatenate(flags)                                        # the flag word: bit 0 overflow, bit 1 cut
+        return (rows, flags & 1, (flags >> 1) & 1) if with_cuts else (rows, flags & 1)
 
-    def _finish(self, masks, conf, n, to_host):
+    def _finish(self, masks, conf, n, to_host, link=None):
         """Despeckle, score, keep the reports, and hand out what the caller asked for: masks, or (masks, conf) with confidence=True."""
         if self.min_region_area > 1:
             masks = self._despeckle(masks)
         self._score(masks, n)
         if self.regions:
-            self._keep_regions(masks, conf)
+            self._keep_regions(masks, conf, link)
         if not self.confidence:
             return masks.cpu().numpy() if to_host else masks            # :277
         self._keep_report(masks, conf)
         return (masks.cpu().numpy(), conf.cpu().numpy()) if to_host else (masks, conf)
 
     def predict_window(self, frame_prev, frame_next, mvs_left, mvs_right, profiler=None, to_host=True, key_ids=None, key_cache=None,
-                       weights=None):
+                       weights=None, link_mvs=None, link_frame_size=None, link_stats=None):
         """key_cache: a KeyframeCache to use for this call instead of the predictor's own (predict_clip's fallback passes a
         cache that lives for the clip only).  weights: an item's "weights" (the window datasets' hold_cuts; ops.window_weights) for
         the whole-frame and the sliding-crop tails alike, None = the reference's blend.  The key-frame cache is unaffected: the
-        network's outputs do not depend on them."""
+        network's outputs do not depend on them.  link_mvs, link_frame_size, link_stats: an item's keys of those names (the estimate-mode
+        datasets' link_vectors=True), needed and used with compensate=True only."""
         assert frame_prev.shape[0] == 1                      # flow/base.py:263
         assert len(mvs_left) == len(mvs_right)               # :264
         n = len(mvs_left) + 1                                # :266 -- the list length encodes n, also for no_warp dummies
+        link = self._link_inputs(n, link_mvs, link_frame_size, link_stats)
         cache = key_cache if key_cache is not None else self.key_cache
         kc = cache.window(*key_ids) if (cache is not None and key_ids is not None) else None
         conf = None
@@ -284,7 +318,7 @@ class FlowPredictor:
             _, masks = crops.compute_output(self.model, n, frame_prev, frame_next, mvs_left, mvs_right, self.crop[0], self.crop[1],
                                             self.classes, profiler, want_mask=True, key_cache=kc, out_size=self.out_size, want_canvas=False,
                                             weights=weights)
-        return self._finish(masks, conf, n, to_host)
+        return self._finish(masks, conf, n, to_host, link)
 
     def _native(self, frame):
         return self.out_size == (frame.shape[2], frame.shape[3])
@@ -340,6 +374,7 @@ class FlowPredictor:
         def emit(w):
             assert w["frame_prev"].shape[0] == 1 and len(w["mvs_left"]) == len(w["mvs_right"])   # flow/base.py:263-264
             n = len(w["mvs_left"]) + 1
+            link = self._link_inputs(n, w.get("link_mvs"), w.get("link_frame_size"), w.get("link_stats"))
             lo_prev, lo_next = store[w["key_ids"][0]], store[w["key_ids"][1]]
             h, wd = w["frame_prev"].shape[2], w["frame_prev"].shape[3]
             conf = None
@@ -364,7 +399,7 @@ class FlowPredictor:
                 _, masks = crops.compute_output(fm, n, w["frame_prev"], w["frame_next"], w["mvs_left"], w["mvs_right"], self.crop[0],
                                                 self.crop[1], self.classes, profiler, want_mask=True, out_size=self.out_size,
                                                 lows=(lo_prev, lo_next), want_canvas=False, weights=w.get("weights"))
-            return self._finish(masks, conf, n, to_host)
+            return self._finish(masks, conf, n, to_host, link)
 
         while True:
             plain = None  # a window that cannot take the look-ahead route (no key_ids / feature mode / foreign network)
@@ -396,7 +431,8 @@ class FlowPredictor:
             store = {k: v for k, v in store.items() if k in live}  # only what a window still to come can need
             if plain is not None:
                 yield self.predict_window(plain["frame_prev"], plain["frame_next"], plain["mvs_left"], plain["mvs_right"], profiler, to_host,
-                                          plain.get("key_ids"), key_cache=local_cache, weights=plain.get("weights"))
+                                          plain.get("key_ids"), key_cache=local_cache, weights=plain.get("weights"), link_mvs=plain.get("link_mvs"),
+                                          link_frame_size=plain.get("link_frame_size"), link_stats=plain.get("link_stats"))
             elif exhausted and not pending and not queue:
                 return
 

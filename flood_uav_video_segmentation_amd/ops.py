@@ -631,22 +631,31 @@ def region_links_workspace_bytes(n, max_regions, max_pairs):
     return n * (12 * max_pairs + 16 * max_regions + 8)
 
 
+def region_links_mc_workspace_bytes(n, max_regions, max_pairs, hb, wb):
+    """FS_REGION_LINKS_MC_WORKSPACE_BYTES of include/floodseg_test.h: region_links' and one dword per block and frame behind it."""
+    return region_links_workspace_bytes(n, max_regions, max_pairs) + (n * hb * wb * 4 + 7) // 8 * 8
+
+
 def _int64_2d(t, shape, name, what):
     if t.dtype != torch.int64 or tuple(t.shape) != shape:
         raise RuntimeError(f"floodseg.{what}: {name} must be int64 {list(shape)}, got {t.dtype} {tuple(t.shape)}")
     return t.contiguous()
 
 
-def region_links(index, table, counts, prev=None, max_pairs=None, min_overlap=1):
+def region_links(index, table, counts, prev=None, max_pairs=None, min_overlap=1, mv=None, frame_size=None, pair_stats=None):
     """region_table's (index int32 [n,H,W], table int64 [n,R,10], counts int64 [n,2]) of consecutive frames -> (back int32 [n,R,2],
     fwd int32 [n,R,2], link_counts int64 [n,2]) (definition: include/floodseg_test.h, region_links): back[f][b] = (row, overlap) of the
     row of frame f-1 that shares the most pixels with row b of frame f among the rows of b's class, fwd[f][a] the same for row a of frame
     f-1 among the rows of frame f; (-1, 0) without a partner of at least min_overlap pixels.  prev = (index [H,W], table [R,10], counts
     [2]) of the frame before frame 0, None: frame 0 has no links.  max_pairs: the slots of the pair table, a power of two in 16..2^20
     (default: the next one >= 4 R); a frame pair with more distinct overlapping pairs has no links at all and link_counts[f] = (max_pairs,
-    1).  The workspace is allocated here."""
+    1).  The workspace is allocated here.
+    mv = int32 [n, (FH // 16) * (FW // 16), 7] with frame_size = (FH, FW): the MOTION-COMPENSATED links (definition: region_links_mc) --
+    mv[f] is block_match's / block_match_modes' table of frame f against frame f-1 on decoded frames of FH x FW pixels, and the frame
+    before is read at every pixel's source under its block's vector, scaled to the mask.  pair_stats = int32 [n, 4], block_match_modes'
+    stats rows (optional): a pair flagged as a cut gets no links and link_counts[f] = (0, 2).  With mv=None exactly the in-place call."""
     lib = _lib.load()
-    dev = one_device(index, table, counts, *(prev or ()), what="floodseg.region_links")
+    dev = one_device(index, table, counts, *(prev or ()), mv, pair_stats, what="floodseg.region_links")
     if index.dtype != torch.int32 or index.dim() != 3:
         raise RuntimeError(f"floodseg.region_links: index must be int32 [n,H,W], got {index.dtype} {tuple(index.shape)}")
     n, h, w = index.shape
@@ -663,13 +672,32 @@ def region_links(index, table, counts, prev=None, max_pairs=None, min_overlap=1)
         if len(prev) != 3 or prev[0].dtype != torch.int32 or tuple(prev[0].shape) != (h, w):
             raise RuntimeError(f"floodseg.region_links: prev must be (index int32 [{h},{w}], table int64 [{cap},10], counts int64 [2])")
         prev = (prev[0].contiguous(), _int64_2d(prev[1], (cap, 10), "prev table", "region_links"), _int64_2d(prev[2], (2,), "prev counts", "region_links"))
+    if mv is None:
+        if frame_size is not None or pair_stats is not None:
+            raise RuntimeError("floodseg.region_links: frame_size and pair_stats go with mv (the motion-compensated links)")
+    else:
+        if frame_size is None or len(frame_size) != 2 or min(int(v) for v in frame_size) < 16 or int(frame_size[0]) * int(frame_size[1]) >= 2 ** 31:
+            raise RuntimeError(f"floodseg.region_links: mv needs frame_size = (height, width) of the decoded frame, both >= 16, got {frame_size}")
+        fh, fw = int(frame_size[0]), int(frame_size[1])
+        hb, wb = fh // 16, fw // 16
+        if mv.dtype != torch.int32 or tuple(mv.shape) != (n, hb * wb, 7):
+            raise RuntimeError(f"floodseg.region_links: mv must be int32 [{n},{hb * wb},7] for a {fh} x {fw} frame, got {mv.dtype} {tuple(mv.shape)}")
+        if h > 31 * fh or w > 31 * fw:
+            raise RuntimeError(f"floodseg.region_links: the mask ({h} x {w}) may be at most 31 times the decoded frame ({fh} x {fw}) along an axis")
+        if pair_stats is not None and (pair_stats.dtype != torch.int32 or tuple(pair_stats.shape) != (n, 4)):
+            raise RuntimeError(f"floodseg.region_links: pair_stats must be int32 [{n},4], got {pair_stats.dtype} {tuple(pair_stats.shape)}")
     with torch.cuda.device(dev):
         back = torch.empty((n, cap, 2), dtype=torch.int32, device=dev)
         fwd = torch.empty((n, cap, 2), dtype=torch.int32, device=dev)
         link_counts = torch.empty((n, 2), dtype=torch.int64, device=dev)
-        if n:
+        p = prev or (None, None, None)
+        if n and mv is not None:
+            work = torch.empty((region_links_mc_workspace_bytes(n, cap, pairs, hb, wb) // 8,), dtype=torch.int64, device=dev)
+            check(lib.fs_region_links_mc(ptr(index.contiguous()), ptr(table.contiguous()), ptr(counts), ptr(p[0]), ptr(p[1]), ptr(p[2]), ptr(mv.contiguous()),
+                                         ptr(None if pair_stats is None else pair_stats.contiguous()), n, h, w, fh, fw, cap, pairs, int(min_overlap),
+                                         ptr(back), ptr(fwd), ptr(link_counts), ptr(work), stream_ptr()))
+        elif n:
             work = torch.empty((region_links_workspace_bytes(n, cap, pairs) // 8,), dtype=torch.int64, device=dev)
-            p = prev or (None, None, None)
             check(lib.fs_region_links(ptr(index.contiguous()), ptr(table.contiguous()), ptr(counts), ptr(p[0]), ptr(p[1]), ptr(p[2]), n, h, w, cap, pairs,
                                       int(min_overlap), ptr(back), ptr(fwd), ptr(link_counts), ptr(work), stream_ptr()))
     return back, fwd, link_counts

@@ -476,6 +476,47 @@ typedef struct fs_ext2_api {
      * n < 1, n > 65535, R outside 1..65536. */
     int (*region_tracks)(const int32_t* back, const int32_t* fwd, const int64_t* counts, const int64_t* prev_tracks, int n, int max_regions,
                          int64_t* state, int64_t* tracks, fs_stream stream);
+
+    /* region_links with MOTION COMPENSATION: the frame before is read at every pixel's SOURCE under the block matcher's vectors, so a
+     * region that moves further than its own width between two frames still overlaps itself.  Integers throughout; // is floor division.
+     * Inputs as region_links', and on top:
+     *   mv         = int32 [n][hb * wb][7], mv[f] the table of frame f against frame f-1 as block_match / block_match_modes write it,
+     *                measured on a decoded frame of frame_h x frame_w pixels (FH x FW below), hb = FH // 16, wb = FW // 16.  The mask
+     *                (H x W) and the decoded frame need not have the same size.  mv[0] is used only when prev_* is given.
+     *   pair_stats = int32 [n][4], rows as block_match_modes writes its stats, or NULL.
+     * For pixel (y, x) of frame f:
+     *   its centre in the frame   fy = ((2y + 1) FH) // (2H), fx = ((2x + 1) FW) // (2W)
+     *   its block                 by = fy // 16, bx = fx // 16; a pixel of the remainder strip (by >= hb or bx >= wb) has shift (0, 0)
+     *   its row                   r = mv[f][by * wb + bx]; a VOID row (r[5] < 0 or r[6] < 0; the matcher's void row is
+     *                             (-1, 16, 16, -16, -16, -16, -16)) has shift (0, 0); otherwise vx = r[3] - r[5], vy = r[4] - r[6]
+     *                             (source minus destination: where the block was in the frame before), and a row with |vx| or |vy| >
+     *                             1024 counts as void.  The differences are taken in 64 bits: ANY seven ints are a valid row.
+     *   its shift in mask pixels  sx = sign(vx) ((2 |vx| W + FW) // (2 FW)), sy = sign(vy) ((2 |vy| H + FH) // (2 FH)): nearest, ties
+     *                             away from zero
+     *   its source                (y + sy, x + sx); a pixel whose source lies outside the mask takes no part
+     *   overlap(a, b)  the number of pixels p of frame f with index[f][p] == b, a source s(p) inside the mask and index[f-1][s(p)] == a;
+     *                  both rows exist and are of the same class.  Several pixels may share a source, so the overlaps of a row a can add
+     *                  up to more than a's area; overlap(a, b) <= area(b) always holds.
+     * back, fwd, min_overlap, the pair table, its overflow rule, the tie rules and link_counts[f][0] are region_links', word for word.
+     * SCENE CUTS: where pair_stats is given and pair_stats[f][2] != 0 the pair gets no links at all -- back[f] and fwd[f] are (-1, 0)
+     * throughout and link_counts[f] = (0, 2): on a cut block_match_modes voids every row, and regions of two unrelated scenes would be
+     * compared in place.  Column 1 of link_counts is a flag word for this op: bit 0 overflow, bit 1 cut.  (Frame 0 without prev_* has no
+     * pair: (0, 0) as in region_links.)
+     * Consequences: with every row void, or every vector 0, all three outputs equal region_links' bit for bit; with H, W == FH, FW the
+     * shift is the vector itself; for n == 1 the outputs equal region_links on a previous index plane warped beforehand (a gathered at
+     * the source, -1 where the source is outside).
+     * workspace = FS_REGION_LINKS_MC_WORKSPACE_BYTES(n, R, max_pairs, hb, wb) bytes at an 8-byte aligned address: region_links' and, behind
+     * it, one packed dword per block and frame (sy << 16 | sx in 16-bit halves), written by a pass of its own so that the overlap pass
+     * reads one dword per pixel.  Five launches (zero, shifts, overlap, best, unpack); nothing is allocated, synchronised or read on the
+     * host; every output is written whole.
+     * Refused before a launch: everything region_links refuses; a null mv; frame_h or frame_w < 16; frame_h * frame_w >= 2^31; H > 31
+     * frame_h or W > 31 frame_w (a shift is at most 1024 * 31 + 1/2 mask pixels then and fits its 16 bits). */
+#define FS_REGION_LINKS_MC_WORKSPACE_BYTES(n, R, max_pairs, hb, wb) \
+    (FS_REGION_LINKS_WORKSPACE_BYTES(n, R, max_pairs) + (((size_t)(n) * (size_t)(hb) * (size_t)(wb) * 4 + 7) / 8) * 8)
+    int (*region_links_mc)(const int32_t* index, const int64_t* table, const int64_t* counts, const int32_t* prev_index, const int64_t* prev_table,
+                           const int64_t* prev_counts, const int32_t* mv, const int32_t* pair_stats, int n, int H, int W, int frame_h, int frame_w,
+                           int max_regions, int max_pairs, int min_overlap, int32_t* back, int32_t* fwd, int64_t* link_counts, void* workspace,
+                           fs_stream stream);
 } fs_ext2_api;
 
 typedef struct fs_hook_tables2 {

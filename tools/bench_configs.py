@@ -410,6 +410,10 @@ def main():
         # before it -- at a cap of 1024 rows (the scene overflows it: the lower part of the frame takes no part) and at 32768 -- with the
         # bytes each must move at least; then what track=True adds to a window over regions=True alone (tail + label + table against tail +
         # label + table + links + tracks + the copies of the last frame), alternating, every loop >= 0.5 s.
+        # The motion-compensated links (ops.region_links with mv=) run beside the in-place ones, the two alternating: the same scene with
+        # the uniform vector table of a 1080 x 1920 decoded frame that matches its 3 pixels per frame (-8 frame pixels at 713 wide, -3
+        # at 1920), so the compensated op finds every region where it was.  Its floor is the in-place one's plus the packed shifts.  Then
+        # what compensate=True adds to a window on top of track=True, and the one block search per window it costs the dataset.
         import numpy as np
 
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -429,6 +433,11 @@ def main():
             mask = torch.from_numpy(np.stack([np.roll(plane, 3 * f, 1)[:hh, :ww] for f in range(N + 1)])).to(dev)
             labels = ops.mask_regions(mask, 4, 8)
             px = N * hh * ww
+            fh, fw, hb, wb = 1080, 1920, 67, 120
+            vx = -((2 * 3 * fw + ww) // (2 * ww))                     # 3 mask pixels to the right per frame, in frame pixels, source minus destination
+            by, bx = np.mgrid[0:hb, 0:wb]
+            one = np.stack([np.full_like(bx, -1), np.full_like(bx, 16), np.full_like(bx, 16), bx * 16 + 8 + vx, by * 16 + 8, bx * 16 + 8, by * 16 + 8], -1)
+            mv = torch.from_numpy(np.stack([one.reshape(-1, 7)] * N).astype(np.int32)).to(dev)
             for cap in (1024, 32768):
                 table, counts, index = ops.region_table(mask, labels, 4, None, 128, cap)
                 prev = (index[0].clone(), table[0].clone(), counts[0].clone())
@@ -439,8 +448,16 @@ def main():
                 seed = ops.region_tracks(back, fwd, counts, state)[0].clone()  # stands for the tracks row of the frame before
                 out = torch.empty((N, cap, 4), dtype=torch.int64, device=dev)
                 rows.append((f"tracks {hh}x{ww} n {N} cap {cap}: rows {counts[:, 1].tolist()}, pairs / overflow {lc.tolist()} of {pairs} slots", 0.0, 0.0))
-                alone(f"region_links {hh}x{ww} n {N} cap {cap}, max_pairs {pairs}", lambda i, x=index, t=table, c=counts, p=prev: ops.region_links(x, t, c, p),
-                      px * 8 + ops.region_links_workspace_bytes(N, cap, pairs) + N * cap * 16)
+                in_place = lambda i, x=index, t=table, c=counts, p=prev: ops.region_links(x, t, c, p)  # noqa: E731
+                moved = lambda i, x=index, t=table, c=counts, p=prev: ops.region_links(x, t, c, p, mv=mv, frame_size=(fh, fw))  # noqa: E731
+                lc_mc = moved(0)[2]
+                alt = [(timed(in_place), timed(moved)) for _ in range(3)]
+                t_in, t_mc = (min(x[j] for x in alt) for j in range(2))
+                floor = px * 8 + ops.region_links_workspace_bytes(N, cap, pairs) + N * cap * 16
+                rows.append((f"  region_links {hh}x{ww} n {N} cap {cap}, max_pairs {pairs}: {floor / 1e6:.1f} MB, {floor / t_in / 1e12:.3f} TB/s", 1 / t_in, t_in * 1e3))
+                floor += N * hb * wb * (28 + 2 * 4)                   # the table rows read once, the packed shifts written and read
+                rows.append((f"  region_links compensated ({fh}x{fw} frame, vx {vx}), pairs / flags {lc_mc.tolist()}: {floor / 1e6:.1f} MB, "
+                             f"{floor / t_mc / 1e12:.3f} TB/s, {t_mc / t_in:.2f} x in place", 1 / t_mc, t_mc * 1e3))
                 alone(f"region_tracks n {N} cap {cap}", lambda i, b=back, f=fwd, c=counts, s=state, p=seed, o=out: ops.region_tracks(b, f, c, s, p, out=o),
                       N * cap * (16 + 32 + 32))
             lo = torch.randn((2, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
@@ -454,18 +471,26 @@ def main():
 
             kept = {}
 
-            def tracked(m, cap):  # what FlowPredictor._keep_tracks does behind the table
+            def tracked(m, cap, mv=None):  # what FlowPredictor._keep_tracks does behind the table
                 table, counts, index = regions_of(m, cap)
-                prev, st = kept.get(cap), kept.setdefault(("state", cap), torch.zeros(2, dtype=torch.int64, device=dev))
-                back, fwd, _ = ops.region_links(index, table, counts, None if prev is None else prev[:3])
+                key = (cap, mv is not None)
+                prev, st = kept.get(key), kept.setdefault(("state",) + key, torch.zeros(2, dtype=torch.int64, device=dev))
+                back, fwd, _ = ops.region_links(index, table, counts, None if prev is None else prev[:3], mv=mv, frame_size=None if mv is None else (fh, fw))
                 tracks = ops.region_tracks(back, fwd, counts, st, None if prev is None else prev[3])
-                kept[cap] = (index[-1].clone(), table[-1].clone(), counts[-1].clone(), tracks[-1].clone())
+                kept[key] = (index[-1].clone(), table[-1].clone(), counts[-1].clone(), tracks[-1].clone())
 
             for cap in (1024, 32768):
-                alt = [(timed(lambda i: regions_of(tail(i), cap)), timed(lambda i: tracked(tail(i), cap))) for _ in range(3)]
-                t_reg, t_trk = (min(x[j] for x in alt) for j in range(2))
+                alt = [(timed(lambda i: regions_of(tail(i), cap)), timed(lambda i: tracked(tail(i), cap)), timed(lambda i: tracked(tail(i), cap, mv)))
+                       for _ in range(3)]
+                t_reg, t_trk, t_cmp = (min(x[j] for x in alt) for j in range(3))
                 rows.append((f"seg_tail {hh}x{ww} warp + regions, max_regions {cap}", 1 / t_reg, t_reg * 1e3))
                 rows.append((f"  + track: {(t_trk / t_reg - 1) * 100:+.2f} % ({(t_trk - t_reg) * 1e3:+.3f} ms)", 1 / t_trk, t_trk * 1e3))
+                rows.append((f"  + track, compensate: {(t_cmp / t_reg - 1) * 100:+.2f} % ({(t_cmp - t_reg) * 1e3:+.3f} ms; {(t_cmp - t_trk) * 1e3:+.3f} ms over track)",
+                             1 / t_cmp, t_cmp * 1e3))
+        frames = torch.randint(0, 256, (2, 1080, 1920), generator=gen, dtype=torch.uint8).to(dev)
+        for search in (16, 32):  # link_vectors=True: one more search per window, the pair that ends in the window's key frame
+            t = min(timed(lambda i: ops.block_match(frames[1], frames[0], search=search)) for _ in range(3))
+            rows.append((f"block_match 1080x1920 luma, search {search}: the extra search per window of link_vectors=True", 1 / t, t * 1e3))
     if want("cuts"):
         # holding one key frame across a scene cut (ops.window_weights, the weighted instantiations of the fused tails): the weighted
         # call against the unweighted one on the same held logits, alternating (three rounds each, the fastest of each side), every loop

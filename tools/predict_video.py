@@ -39,7 +39,10 @@ shares at least `--min-overlap` pixels with its best predecessor of the same cla
 successor, keeps its track id; every other region starts a new track with its best predecessor's track as parent.  The regions CSV gets
 the columns track, parent and overlap, and FILE.csv one row per track: class, parent, first and last frame, frames seen, first / last /
 largest area and the frame of the largest -- the growth summary.  `--max-pairs` sizes the table of overlapping pairs of a frame pair (a
-power of two); a frame whose table overflowed gets a warning and all its regions start new tracks.  Single process only: ids are per
+power of two); a frame whose table overflowed gets a warning and all its regions start new tracks.  `--compensate` (needs `--tracks`
+and estimated grids: `--raw`, or `--grids estimate`) compares each frame with the frame before it read at the source of every pixel
+under the block matcher's vectors, so that a region which moves further than its own width per frame keeps its track; with
+`--scene-cut` the frames that follow a cut are listed and their regions all start new tracks.  Single process only: ids are per
 predictor.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
@@ -144,9 +147,15 @@ def parse_args(argv=None):
                     "least N pixels")
     ap.add_argument("--max-pairs", type=int, default=None, metavar="N", help="--tracks: slots of the table of overlapping region pairs of two "
                     "consecutive frames, a power of two in 16..1048576 (default: the next one >= 4 x --max-regions)")
+    ap.add_argument("--compensate", action="store_true", help="--tracks with estimated grids: compare each frame with the frame before it read at "
+                    "the source of every pixel under the block matcher's vectors, so that a small region that moves fast keeps its track")
     args = ap.parse_args(argv)
     if args.tracks and not args.regions:
         ap.error("--tracks needs --regions")
+    if args.compensate and not args.tracks:
+        ap.error("--compensate needs --tracks: it changes how the tracks' links are counted")
+    if args.compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
+        ap.error("--compensate needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
     if args.min_overlap < 1 or (args.max_pairs is not None and (not 16 <= args.max_pairs <= 2 ** 20 or args.max_pairs & (args.max_pairs - 1))):
         ap.error("--min-overlap takes N >= 1 and --max-pairs a power of two in 16..1048576")
     if args.min_region < 0 or not 1 <= args.max_regions <= 65536:
@@ -211,17 +220,18 @@ def main():
                          compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache, confidence=args.confidence,
                          low_confidence=args.low_confidence, regions=bool(args.regions), min_region_area=args.min_region,
                          connectivity=args.connectivity, max_regions=args.max_regions, track=bool(args.tracks), min_overlap=args.min_overlap,
-                         max_pairs=args.max_pairs)
+                         max_pairs=args.max_pairs, compensate=args.compensate)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
-                             full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut, hold_cuts=args.hold_cuts)
+                             full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut, hold_cuts=args.hold_cuts,
+                             link_vectors=args.compensate)
     else:
         ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
                             grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut,
-                            hold_cuts=args.hold_cuts)
+                            hold_cuts=args.hold_cuts, link_vectors=args.compensate)
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -258,7 +268,8 @@ def main():
     for w in mine:
         item = ds[w]
         masks = pred.predict_window(item["frame_prev"], item["frame_next"], item["mvs_left"], item["mvs_right"], to_host=False,
-                                    key_ids=item["key_ids"], weights=item.get("weights"))
+                                    key_ids=item["key_ids"], weights=item.get("weights"), link_mvs=item.get("link_mvs"),
+                                    link_frame_size=item.get("link_frame_size"), link_stats=item.get("link_stats"))
         if args.confidence:
             masks, conf = masks
             if conf_writer is not None:
@@ -328,7 +339,7 @@ def main():
                       f"{args.max_regions} (in raster order) were filtered", file=sys.stderr)
     if args.regions:  # likewise: one read-back after the timed run
         region_rows, totals = pred.region_report()
-        track_rows, overflowed = pred.track_report() if args.tracks else (None, [])
+        track_rows, overflowed, cut = pred.track_report(with_cuts=True) if args.tracks else (None, [], [])
         write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence, tracks=track_rows)
         if args.tracks:
             write_tracks_csv(args.tracks, report_ids, region_rows, track_rows)
@@ -336,6 +347,9 @@ def main():
                 if flag:
                     print(f"warning: frame {fid}: the pair table overflowed (--max-pairs {pred.max_pairs}): its regions all start new tracks",
                           file=sys.stderr)
+            cut_ids = [fid for fid, flag in zip(report_ids, cut.tolist()) if flag]
+            if cut_ids:
+                print(f"--compensate: frames {cut_ids} follow a scene cut: their regions all start new tracks", file=sys.stderr)
         for fid, total in zip(report_ids, totals.tolist()):
             if total > args.max_regions:
                 print(f"warning: frame {fid} has {total} regions, --max-regions {args.max_regions}: the first {args.max_regions} are listed",
