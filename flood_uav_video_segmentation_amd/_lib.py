@@ -161,6 +161,12 @@ _EXT2_HOOKS = [
 ]
 EXT2_MAGIC = 0x4653455854414232  # FS_EXT2_MAGIC
 
+# members of fs_ext3_api, the fourth table (append-only, behind the three frozen ones), in declaration order after `magic` and `size`
+_EXT3_HOOKS = [
+    ("region_outlines", c_int, [c_void] + [c_int] * 7 + [c_void] * 6),
+]
+EXT3_MAGIC = 0x4653455854414233  # FS_EXT3_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
@@ -182,6 +188,14 @@ class FsHookTables2(ctypes.Structure):
     _fields_ = [("base", FsHookTables), ("ext2", FsExt2Api)]
 
 
+class FsExt3Api(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT3_HOOKS]
+
+
+class FsHookTables3(ctypes.Structure):
+    _fields_ = [("base2", FsHookTables2), ("ext3", FsExt3Api)]
+
+
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
     fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
@@ -191,8 +205,25 @@ class _Library:
         self._hooks = None
         self._ext = None
         self._ext2 = None
+        self._ext3 = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT3_HOOKS):
+            if self._ext3 is None:
+                all2 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables2)).contents
+                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
+                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)):
+                    raise RuntimeError(f"floodseg: the library's first three hook tables are not the ones this binding knows ({name} is missing)")
+                ext3 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables3)).contents.ext3
+                if ext3.magic != EXT3_MAGIC:
+                    raise RuntimeError(f"floodseg: the library has no third extension table ({name} is missing)")
+                self._ext3 = ext3
+            member = getattr(FsExt3Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
+            if self._ext3.size < member.offset + member.size:
+                raise RuntimeError(f"floodseg: the library's third extension table is older than this binding ({name} is missing)")
+            fn = getattr(self._ext3, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT2_HOOKS):
             if self._ext2 is None:
                 base = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables)).contents
@@ -270,6 +301,11 @@ def ext_hook_names():
 def ext2_hook_names():
     """Members of fs_ext2_api after `magic` and `size`, in declaration order."""
     return [h[0] for h in _EXT2_HOOKS]
+
+
+def ext3_hook_names():
+    """Members of fs_ext3_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT3_HOOKS]
 
 
 def check(rc):

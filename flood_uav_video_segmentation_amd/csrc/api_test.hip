@@ -438,6 +438,12 @@ static int fs_region_links_mc(const int32_t* index, const int64_t* table, const 
                                       frame_h, frame_w, max_regions, max_pairs, min_overlap, back, fwd, reinterpret_cast<long long*>(link_counts), workspace,
                                       S(stream));
 }
+// region outlines (outline_ops.hip): the launcher validates, nothing is launched on a refusal
+static int fs_region_outlines(const int32_t* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,
+                              int64_t* contours, int32_t* vertices, int64_t* shape, int64_t* counts, void* workspace, fs_stream stream) {
+    return fs::launch_region_outlines(index, n, H, W, max_regions, connectivity, max_contours, max_vertices, reinterpret_cast<long long*>(contours),
+                                      vertices, reinterpret_cast<long long*>(shape), reinterpret_cast<long long*>(counts), workspace, S(stream));
+}
 static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int H, int W,
                             const float* mean, const float* std, float* out, int h, int w, fs_stream stream) {
     if (!frame || !mean || !std || !out) return fs::fail("fs_frame_prepare: null pointer");
@@ -544,5 +550,11 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         fs_region_tracks,
         fs_region_links_mc,
     }};
-    return &all.base.test;
+    // fs_ext2_api is frozen too (size and text); the fourth table lies behind it by the same pattern, and &all3.base2.base.test is &all3.
+    static const fs_hook_tables3 all3 = {all, {
+        FS_EXT3_MAGIC,
+        sizeof(fs_ext3_api),
+        fs_region_outlines,
+    }};
+    return &all3.base2.base.test;
 }

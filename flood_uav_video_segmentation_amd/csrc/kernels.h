@@ -372,6 +372,10 @@ int launch_region_links_mc(const int* index, const long long* table, const long 
 int launch_region_tracks(const int* back, const int* fwd, const long long* counts, const long long* prev_tracks, int n, int max_regions,
                          long long* state, long long* tracks, hipStream_t s);
 
+// Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
+// launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
+int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,
+                           long long* contours, int* vertices, long long* shape, long long* counts, void* workspace, hipStream_t s);
 
 // ---------------------------------------------------------------------------------
 // Segmenter / ViT pieces (segm/model/vit.py, blocks.py, decoder.py); token matrices are row-major

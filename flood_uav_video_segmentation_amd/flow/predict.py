@@ -18,6 +18,10 @@ track id that lasts as long as the region does (ops.region_links / region_tracks
 FlowPredictor(..., regions=True, track=True, compensate=True) compares each frame with the frame before it READ AT THE SOURCE of every
 pixel under the block matcher's vectors, which the estimate-mode window datasets hand out with link_vectors=True (ops.region_links with
 mv=): a region that moves further than its own width per frame keeps its track.
+FlowPredictor(..., regions=True, outlines=True) also outlines every region on the device -- ordered polygons on the pixel lattice, the
+outer contour and the holes, with the perimeter and the hole count per region (ops.region_outlines):
+    frames, flags = p.outline_report()                                     # per frame (contour rows, vertices, shape rows); read back once
+    write_outlines_geojson("o.geojson", ids, rows, (frames, flags))        # one Polygon feature per frame and region
 """
 import numpy as np
 import torch
@@ -68,13 +72,23 @@ class FlowPredictor:
     [n, blocks, 7]: per emitted frame the block matcher's table of that frame against the frame before it), link_frame_size (the decoded
     frame's height and width) and optionally link_stats (int32 [n, 4], block_match_modes' stats rows: a pair flagged as a scene cut
     gets no links and its flag in track_report(with_cuts=True)).  A window without link_mvs raises: there is no silent fall-back to the
-    in-place comparison.  The first frame after reset() has no frame before it, so its vectors are ignored."""
+    in-place comparison.  The first frame after reset() has no frame before it, so its vectors are ignored.
+
+    outlines=True (extension, needs regions=True): every tabulated frame's regions are outlined -- ordered polygons on the mask's pixel
+    lattice, an outer contour and the holes per region, plus per region its perimeter, contour and vertex counts (ops.region_outlines;
+    DESIGN §3.13) -- right behind the table of the (filtered) masks, into chunked device buffers beside the region tables; nothing is
+    read back until outline_report().  Device memory per frame: 8 max_vertices + 48 max_contours + 24 max_regions + 32 bytes (at the
+    defaults 472 KiB; a chunk holds as many frames as fit 64 MiB, 138 at the defaults), plus the op's workspace while a window is
+    outlined.  A frame with more than max_vertices vertices gets NO contours and flag bit 0, one with more than max_contours contours
+    keeps the first max_contours and flag bit 1; outline_report() hands the flags out.  The defaults (4096 contours, 32768 vertices) are
+    guesses for ragged 1080p water masks: no default has been validated on real video.  The masks are not touched."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
-                 max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False):
+                 max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False, outlines=False, max_contours=4096,
+                 max_vertices=32768):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -121,6 +135,17 @@ class FlowPredictor:
         self._track_chunks = []   # (int64 [REPORT_CHUNK, max_regions, 4], int64 [REPORT_CHUNK, 2] link counts), in step with _region_chunks
         self._track_prev = None   # the last tabulated frame: (index [H,W], table [max_regions,10], counts [2], tracks [max_regions,4]), copies
         self._track_state = None  # device int64 [2] = (next track id, 0)
+        if outlines and not regions:
+            raise ValueError("FlowPredictor: outlines=True needs regions=True (the outlines follow the region tables' index planes)")
+        if not 1 <= int(max_contours) <= 2 ** 20 or not 4 <= int(max_vertices) <= 2 ** 22:
+            raise ValueError(f"FlowPredictor: max_contours must be 1..2^20 and max_vertices 4..2^22, got {max_contours} and {max_vertices}")
+        self.outlines = bool(outlines)
+        self.max_contours = int(max_contours)
+        self.max_vertices = int(max_vertices)
+        per_frame = 8 * self.max_vertices + 48 * self.max_contours + 24 * self.max_regions + 32
+        self.outline_chunk = max(1, min(self.REPORT_CHUNK, ((64 << 20) - 1) // per_frame))  # frames per device buffer: below 64 MiB
+        self._outline_chunks = []  # (contours, vertices, shape, counts) device buffers of outline_chunk frames each, in frame order
+        self._outline_frames = 0
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
@@ -139,6 +164,8 @@ class FlowPredictor:
         self._region_frames = 0
         self._despeckle_counts = []
         self._track_chunks = []  # the previous frame and the next track id stay
+        self._outline_chunks = []
+        self._outline_frames = 0
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -219,11 +246,53 @@ class FlowPredictor:
             table, counts = self._region_chunks[-1]
             got = ops.region_table(masks[done:done + take], labels[done:done + take], self.classes, None if conf is None else conf[done:done + take],
                                    self.low_confidence, self.max_regions, out=(table[row:row + take], counts[row:row + take]))
+            if self.outlines:
+                self._keep_outlines(got[2])
             if self.track:
                 piece = None if link is None else (link[0][done:done + take], link[1], None if link[2] is None else link[2][done:done + take])
                 self._keep_tracks(got[2], table[row:row + take], counts[row:row + take], row, piece)
             done += take
             self._region_frames += take
+
+    def _keep_outlines(self, index):
+        """The outlines of the index planes region_table just wrote into the next rows of their own chunked buffers (region_outlines
+        writes its rows whole; nothing is read back)."""
+        done, n, dev = 0, index.shape[0], index.device
+        while done < n:
+            row = self._outline_frames % self.outline_chunk
+            if row == 0:
+                c = self.outline_chunk
+                self._outline_chunks.append((torch.zeros((c, self.max_contours, 6), dtype=torch.int64, device=dev),
+                                             torch.zeros((c, self.max_vertices, 2), dtype=torch.int32, device=dev),
+                                             torch.zeros((c, self.max_regions, 3), dtype=torch.int64, device=dev),
+                                             torch.zeros((c, 4), dtype=torch.int64, device=dev)))
+            take = min(n - done, self.outline_chunk - row)
+            ops.region_outlines(index[done:done + take], self.max_regions, self.connectivity, self.max_contours, self.max_vertices,
+                                out=tuple(b[row:row + take] for b in self._outline_chunks[-1]))
+            done += take
+            self._outline_frames += take
+
+    def outline_report(self):
+        """outlines=True: (frames, flags) for every frame of region_report(), in its order: frames[f] = (contours int64 numpy [rows, 6],
+        vertices int32 numpy [vertices, 2], shape int64 numpy [regions, 3]) -- the contour rows written (region row, first vertex
+        offset, vertex count, cracks, area2, anchor), all vertex lists back to back, and row for row region_report()'s rows[f] the
+        (perimeter, contours, vertices) of each region; flags = int64 numpy [frames], bit 0: more than max_vertices vertices (no
+        contours at all for that frame, shape's contours column -1), bit 1: more than max_contours contours (the first max_contours
+        are there).  The read-back happens here, chunk by chunk."""
+        if not self._outline_chunks:
+            return [], np.zeros((0,), dtype=np.int64)
+        regions = np.concatenate([counts[:, 1].cpu().numpy() for _, counts in self._region_chunks])
+        frames, flags, left = [], [], self._outline_frames
+        for contours, vertices, shape, counts in self._outline_chunks:
+            take = min(left, self.outline_chunk)
+            c = counts[:take].cpu().numpy()
+            rows, verts, shp = contours[:take].cpu().numpy(), vertices[:take].cpu().numpy(), shape[:take].cpu().numpy()
+            for f in range(take):
+                total = 0 if c[f, 3] & 1 else int(c[f, 2])
+                frames.append((rows[f, :int(c[f, 1])], verts[f, :total], shp[f, :int(regions[len(frames)])]))
+            flags.append(c[:, 3])
+            left -= take
+        return frames, np.concatenate(flags)
 
     def _keep_tracks(self, index, table, counts, row, link=None):
         """Links and track ids of the piece region_table just wrote (rows row.. of the newest chunk), against the frame tabulated before
@@ -520,19 +589,23 @@ def write_extent_csv(path, frame_ids, report, frame_pixels, with_confidence=True
             f.write(",".join(cells) + "\n")
 
 
-def write_regions_csv(path, frame_ids, rows, with_confidence=True, tracks=None):
+def write_regions_csv(path, frame_ids, rows, with_confidence=True, tracks=None, shapes=None):
     """One CSV row per frame and region from FlowPredictor.region_report()'s rows (per frame int64 [regions, 10]): frame id, the
     region's number in the frame, class, area, the inclusive box x0, y0, x1, y1, the centroid cx = sum_x / area, cy = sum_y / area,
     and with_confidence: conf = conf_sum / (255 area) (mean confidence) and low = low-confidence pixels / area.  tracks =
     FlowPredictor.track_report()'s rows (per frame int64 [regions, 4]): the columns track, parent (-1: none) and overlap (the pixels
-    shared with the best predecessor in the frame before) are appended; None: the file without them, byte for byte."""
+    shared with the best predecessor in the frame before) are appended; None: the file without them, byte for byte.  shapes = per
+    frame the int64 [regions, 3] shape rows of FlowPredictor.outline_report(): the columns perimeter and holes (contours - 1; -1 for a
+    frame whose outlines overflowed) are appended; None: the file without them, byte for byte."""
     if len(frame_ids) != len(rows):
         raise ValueError(f"write_regions_csv: one frame id per frame, got {len(frame_ids)} ids for {len(rows)} frames")
     if tracks is not None and (len(tracks) != len(rows) or any(len(t) != len(r) for t, r in zip(tracks, rows))):
         raise ValueError("write_regions_csv: tracks must hold one row per region of every frame")
+    if shapes is not None and (len(shapes) != len(rows) or any(len(t) != len(r) for t, r in zip(shapes, rows))):
+        raise ValueError("write_regions_csv: shapes must hold one row per region of every frame")
     with open(path, "w") as fh:
         fh.write("frame,region,class,area,x0,y0,x1,y1,cx,cy" + (",conf,low" if with_confidence else "") + (",track,parent,overlap" if tracks is not None else "")
-                 + "\n")
+                 + (",perimeter,holes" if shapes is not None else "") + "\n")
         for f, (fid, frame) in enumerate(zip(frame_ids, rows)):
             for r, (cls, area, x0, y0, x1, y1, sx, sy, cs, lo) in enumerate(np.asarray(frame).tolist()):
                 cells = [str(fid), str(r), str(cls), str(area), str(x0), str(y0), str(x1), str(y1), f"{sx / area:.3f}", f"{sy / area:.3f}"]
@@ -541,7 +614,56 @@ def write_regions_csv(path, frame_ids, rows, with_confidence=True, tracks=None):
                 if tracks is not None:
                     tid, parent, _, overlap = np.asarray(tracks[f][r]).tolist()
                     cells += [str(tid), str(parent), str(overlap)]
+                if shapes is not None:
+                    perimeter, contours, _ = np.asarray(shapes[f][r]).tolist()
+                    cells += [str(perimeter), str(contours - 1 if contours >= 0 else -1)]
                 fh.write(",".join(cells) + "\n")
+
+
+def write_outlines_geojson(path, frame_ids, rows, outlines, tracks=None):
+    """The regions' shapes as one GeoJSON FeatureCollection, one Feature per frame and region, from region_report()'s rows and
+    outlines = FlowPredictor.outline_report()'s (frames, flags).  The geometry is a Polygon whose rings are the region's outer contour
+    first, then its holes, each closed by repeating its first vertex; the coordinates are mask pixel lattice coordinates (x to the
+    right, y down; no georeferencing).  Properties: frame, region, class, area, perimeter, holes, and with tracks =
+    track_report()'s rows also track and parent.  A frame whose flag bit 0 is set (more vertices than max_vertices: it has no contours)
+    contributes no features and is named in the top-level list "overflowed_frames"; a frame with bit 1 (more contours than
+    max_contours) is named in "truncated_frames", and its regions come with the rings that have rows -- a region whose outer contour
+    has none is left out."""
+    import json
+
+    frames, flags = outlines
+    if len(frame_ids) != len(rows) or len(frames) != len(rows) or len(flags) != len(rows):
+        raise ValueError(f"write_outlines_geojson: one frame id and one outline per frame, got {len(frame_ids)} ids, {len(frames)} outlines "
+                         f"for {len(rows)} frames")
+    if tracks is not None and (len(tracks) != len(rows) or any(len(t) != len(r) for t, r in zip(tracks, rows))):
+        raise ValueError("write_outlines_geojson: tracks must hold one row per region of every frame")
+    features, overflowed, truncated = [], [], []
+    for f, (fid, table, (contours, vertices, shape)) in enumerate(zip(frame_ids, rows, frames)):
+        if int(flags[f]) & 1:
+            overflowed.append(fid)
+            continue
+        if int(flags[f]) & 2:
+            truncated.append(fid)
+        outer, holes = {}, {}
+        for region, first, count, _, area2, _ in np.asarray(contours).tolist():
+            ring = np.asarray(vertices[first:first + count]).tolist()
+            ring.append(ring[0])
+            if area2 > 0:
+                outer[region] = ring
+            else:
+                holes.setdefault(region, []).append(ring)
+        for r, row in enumerate(np.asarray(table).tolist()):
+            if r not in outer:
+                continue
+            perimeter, count, _ = np.asarray(shape[r]).tolist()
+            props = {"frame": fid, "region": r, "class": row[0], "area": row[1], "perimeter": perimeter, "holes": count - 1}
+            if tracks is not None:
+                props["track"], props["parent"] = np.asarray(tracks[f][r]).tolist()[:2]
+            features.append({"type": "Feature", "properties": props,
+                             "geometry": {"type": "Polygon", "coordinates": [outer[r]] + holes.get(r, [])}})
+    with open(path, "w") as fh:
+        json.dump({"type": "FeatureCollection", "overflowed_frames": overflowed, "truncated_frames": truncated, "features": features}, fh)
+        fh.write("\n")
 
 
 def write_tracks_csv(path, frame_ids, rows, tracks):

@@ -733,6 +733,48 @@ def region_tracks(back, fwd, counts, state, prev_tracks=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ region outlines
+def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
+    """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""
+    v = max_vertices
+    return n * 8 * (2 * v + 7 * ((v + 1) // 2) + ((h * w + 1023) // 1024 + 1) // 2 + (v + 1023) // 1024 + 2)
+
+
+def region_outlines(index, max_regions, connectivity=8, max_contours=4096, max_vertices=32768, out=None):
+    """region_table's index planes int32 [n,H,W] -> (contours int64 [n,max_contours,6], vertices int32 [n,max_vertices,2], shape int64
+    [n,max_regions,3], counts int64 [n,4]) (definition: include/floodseg_test.h, region_outlines): every region's outline as ordered
+    polygons on the pixel lattice.  A contours row is (region row, first vertex offset, vertex count, cracks, area2, anchor), in ascending
+    anchor order; area2 > 0 is a region's outer contour (clockwise on the screen), area2 < 0 a hole.  vertices holds all lists back to
+    back, not closed.  shape rows are (perimeter, contours, vertices) per region; counts rows (contours, rows written, vertices, flags):
+    bit 0 = more than max_vertices vertices (the frame gets no contours at all), bit 1 = more than max_contours contours.  connectivity
+    must be the one the labels were made with.  out: caller-owned contiguous destinations (rows of larger buffers) in the order of the
+    result; they are written whole.  The workspace (44 bytes per possible vertex and frame) is allocated here."""
+    lib = _lib.load()
+    dev = one_device(index, *(out or ()), what="floodseg.region_outlines")
+    if index.dtype != torch.int32 or index.dim() != 3:
+        raise RuntimeError(f"floodseg.region_outlines: index must be int32 [n,H,W], got {index.dtype} {tuple(index.shape)}")
+    n, h, w = index.shape
+    cap, mc, mv = int(max_regions), int(max_contours), int(max_vertices)
+    if h < 1 or w < 1 or h * w >= 2 ** 29 or n > 65535:
+        raise RuntimeError(f"floodseg.region_outlines: at most 65535 non-empty frames below 2^29 pixels, got {tuple(index.shape)}")
+    if connectivity not in (4, 8) or not 1 <= cap <= 65536 or not 1 <= mc <= 2 ** 20 or not 4 <= mv <= 2 ** 22:
+        raise RuntimeError("floodseg.region_outlines: connectivity 4 or 8, max_regions 1..65536, max_contours 1..2^20 and max_vertices 4..2^22, "
+                           f"got {connectivity}, {max_regions}, {max_contours} and {max_vertices}")
+    shapes = ((n, mc, 6), (n, mv, 2), (n, cap, 3), (n, 4))
+    dtypes = (torch.int64, torch.int32, torch.int64, torch.int64)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+        elif len(out) != 4 or any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, s, d in zip(out, shapes, dtypes)):
+            raise RuntimeError(f"floodseg.region_outlines: out must be contiguous int64 {list(shapes[0])}, int32 {list(shapes[1])}, int64 {list(shapes[2])} "
+                               f"and int64 {list(shapes[3])} tensors")
+        if n:
+            work = torch.empty((region_outlines_workspace_bytes(n, h, w, cap, mc, mv) // 8,), dtype=torch.int64, device=dev)
+            check(lib.fs_region_outlines(ptr(index.contiguous()), n, h, w, cap, int(connectivity), mc, mv, ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                         ptr(out[3]), ptr(work), stream_ptr()))
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------------------ block motion estimation
 def block_match(cur, ref, search=16, penalty=0, return_cost=False):
     """Full-search block matching of two uint8 frames [H,W] (luma) or [H,W,3] (RGB as decoded), `ref` the past frame: the motion-vector

@@ -524,6 +524,72 @@ typedef struct fs_hook_tables2 {
     fs_ext2_api ext2;
 } fs_hook_tables2;
 
+/* ---- The FOURTH table.  fs_ext2_api is frozen as well (14 members, 128 bytes; tests/test_tracks_mc_cpu.py), so ops added since live in
+ * a table of their own, append-only, that the library places directly behind fs_hook_tables2 by the same pattern: the object
+ * fs_test_hooks() points into is an fs_hook_tables3, and its address is that of its fs_hook_tables2,
+ *     const fs_hook_tables3* t = (const fs_hook_tables3*)fs_test_hooks();   t->ext3.region_outlines(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables2: a caller that may meet one checks
+ * t->base2.ext2.magic == FS_EXT2_MAGIC and ext2.size == sizeof(fs_ext2_api) first, then t->ext3.magic == FS_EXT3_MAGIC and ext3.size >=
+ * the end of the member it needs. */
+#define FS_EXT3_MAGIC 0x4653455854414233ull /* "FSEXTAB3" */
+
+typedef struct fs_ext3_api {
+    uint64_t magic; /* FS_EXT3_MAGIC */
+    size_t size;    /* sizeof(fs_ext3_api) of the library that was built */
+
+    /* ---- Region outlines (csrc/outline_ops.hip, csrc/outline_defs.h).  OUR DEFINITION.  Integers throughout; every result
+     * is a function of the inputs alone, whatever order threads arrive in.  R = max_regions.
+     * Inputs:
+     *   index         int32 [n][H][W] as region_table writes it: a pixel holds the row r of its region, 0 <= r < R, or -1 (background,
+     *                 regions past the cap).  Any value outside 0 .. R - 1 counts as -1.  Pixels with index -1 own no cracks.
+     *   connectivity  4 or 8, the one the labels were made with.
+     * CRACKS.  A lattice corner is (X, Y), 0 <= X <= W, 0 <= Y <= H.  A crack is a unit edge of a pixel p = (x, y) with index[p] = r >= 0
+     * whose 4-neighbour across that edge lies outside the frame or has an index different from r.  It is directed so that p is on its
+     * right, and has the slot id 4 * (y * W + x) + d:
+     *   d = 0  top     heading east    (x, y)         -> (x + 1, y)
+     *   d = 1  right   heading south   (x + 1, y)     -> (x + 1, y + 1)
+     *   d = 2  bottom  heading west    (x + 1, y + 1) -> (x, y + 1)
+     *   d = 3  left    heading north   (x, y + 1)     -> (x, y)
+     * so an outer boundary runs clockwise on the screen.
+     * SUCCESSOR.  The successor of a crack of r that ends at corner V is the crack of r that starts at V.  There are two such cracks only
+     * at a SADDLE, where r holds two diagonal pixels at V and neither of the other two: at connectivity 8 the successor is the left turn
+     * (onto the diagonal pixel), at 4 the right turn (the same pixel's next edge).  The successor is a permutation of the cracks; its
+     * cycles are the CONTOURS.
+     * VERTICES.  A run start is a crack whose predecessor has another direction; its vertex is its start corner.  A contour's ANCHOR is
+     * the smallest slot id among its run starts.  Its vertex list starts at the anchor's vertex, follows the successor order, holds one
+     * entry per run start and is not closed.  The contours of a frame are ordered by ascending anchor.  A region's outer contour has the
+     * anchor 4 * (label - 1): the top edge of its first pixel is a run start and the region's smallest slot.
+     * Outputs, each written whole by every call (so a HIP-graph replay on new planes gives that replay's figures):
+     *   contours = int64 [n][max_contours][6], rows in contour order, zero behind the last written row:
+     *              (region row, first vertex offset, vertex count, cracks = the contour's length, area2, anchor).
+     *              area2 = sum of x0 y1 - x1 y0 over the vertices as a closed polygon: positive for an outer contour, negative for a
+     *              hole.  Offsets are the exclusive prefix sums of the vertex counts over ALL contours of the frame, in contour order.
+     *   vertices = int32 [n][max_vertices][2] = (X, Y), the lists of all contours concatenated in contour order, those without a row
+     *              included; zero behind the total.
+     *   shape    = int64 [n][R][3] = per region row (perimeter = its cracks, contours, vertices); contours - 1 is its number of holes.
+     *              Rows without a region are zero.
+     *   counts   = int64 [n][4] = (contours, contour rows written, vertices, flags).
+     * OVERFLOW.  Flag bit 0: the frame has more than max_vertices vertices.  It gets nothing rather than an arbitrary part (the pair
+     * table's rule, region_links): contours and vertices are zero, counts = (0, 0, vertices, 1), and the contours column of shape is -1
+     * in every row that has a region (perimeter > 0); perimeter and vertices of shape are local sums and stay valid.  Flag bit 1: more
+     * than max_contours contours; the first max_contours get rows, and all vertex lists are still written.
+     * workspace = FS_REGION_OUTLINES_WORKSPACE_BYTES(n, H, W, R, max_contours, max_vertices) bytes at an 8-byte aligned address, the
+     * caller's: per frame 44 bytes per possible vertex, 4 per 1024 pixels, 8 per 1024 possible vertices and 16.  Nothing is allocated,
+     * synchronised or read on the host; the 11 + ceil(log2 max_vertices) launches capture into a HIP graph.
+     * Refused before a launch: a null pointer; n, H or W < 1; n > 65535; H * W >= 2^29 (slot ids are 32-bit); R outside 1..65536;
+     * connectivity other than 4 or 8; max_contours outside 1..2^20; max_vertices outside 4..2^22; a workspace not aligned to 8 bytes. */
+#define FS_REGION_OUTLINES_WORKSPACE_BYTES(n, H, W, R, max_contours, max_vertices)                                                     \
+    ((size_t)(n) * 8 * (2 * (size_t)(max_vertices) + 7 * (((size_t)(max_vertices) + 1) / 2) +                                        \
+                        (((size_t)(H) * (size_t)(W) + 1023) / 1024 + 1) / 2 + ((size_t)(max_vertices) + 1023) / 1024 + 2))
+    int (*region_outlines)(const int32_t* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,
+                           int64_t* contours, int32_t* vertices, int64_t* shape, int64_t* counts, void* workspace, fs_stream stream);
+} fs_ext3_api;
+
+typedef struct fs_hook_tables3 {
+    fs_hook_tables2 base2;
+    fs_ext3_api ext3;
+} fs_hook_tables3;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

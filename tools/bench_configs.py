@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions tracks cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions tracks outlines cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | tracks | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | tracks | outlines | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -403,6 +403,63 @@ def main():
             rows.append((f"  + regions: {(t_reg / t_old - 1) * 100:+.2f} % ({(t_reg - t_old) * 1e3:+.3f} ms)", 1 / t_reg, t_reg * 1e3))
             rows.append((f"  + regions, max_regions 32768: {(t_big / t_old - 1) * 100:+.2f} % ({(t_big - t_old) * 1e3:+.3f} ms)", 1 / t_big, t_big * 1e3))
             rows.append((f"  + min_region_area 9 + regions: {(t_flt / t_old - 1) * 100:+.2f} % ({(t_flt - t_old) * 1e3:+.3f} ms)", 1 / t_flt, t_flt * 1e3))
+    if want("outlines"):
+        # region outlines (ops.region_outlines, csrc/outline_ops.hip): the op alone per call of N frames, connectivity 8, at the two
+        # geometries, on the blob-like masks of the regions section (same seed, same draws: the argmax of smooth random logits) and on a
+        # second scene with a few large regions (logits 64 times coarser than the mask), with caps that hold every region, contour and
+        # vertex -- the totals are printed -- and with the bytes the passes must move at least: the index plane read by the marking and
+        # by the compaction pass (4 B a pixel each), per node 36 B a ranking round and 92 B for the other passes, and the outputs
+        # written once (zeroed).  Then what outlines=True adds to a window over regions=True alone (tail + label + table against tail +
+        # label + table + outlines), alternating, every loop >= 0.5 s: at the defaults (1024 rows, 4096 contours, 32768 vertices, which
+        # the blob scene overflows: the frame gets nothing) and at the caps that hold everything.
+        gen = torch.Generator().manual_seed(1800)
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+
+        def pow2(v):
+            return 1 << max(2, int(v - 1).bit_length())
+
+        for (hh, ww), hg in (((713, 713), 44), ((1072, 1920), None)):
+            low = torch.randn((N, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            lo = torch.randn((2, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            coarse = torch.randn((N, 5, (hh - 1) // 64 + 1, (ww - 1) // 64 + 1), generator=torch.Generator().manual_seed(1801)).to(dev)
+            gl, gr = (wl, wr) if hg else [[g.to(dev) for g in gs] for gs in synth.make_grids(N, 67, 120, seed=2001, frame=(hh, ww))]
+            fits = {}
+            for scene, logits in (("blobs", low), ("a few large regions", coarse)):
+                mask = ops.mask_confidence(logits, (hh, ww))[0]
+                cap = 32768
+                table, counts, index = ops.region_table(mask, ops.mask_regions(mask, 5, 8), 5, None, 128, cap)
+                probe = ops.region_outlines(index, cap, 8, 4, 4)[3]        # nothing fits: the counts carry the vertex totals
+                mv = pow2(int(probe[:, 2].max()))
+                mc = pow2(mv // 4)
+                got = ops.region_outlines(index, cap, 8, mc, mv)[3]
+                nodes, px = int(got[:, 2].sum()), mask.numel()
+                rounds = (mv - 1).bit_length()
+                floor = 8 * px + nodes * (36 * rounds + 92) + N * (48 * mc + 8 * mv + 24 * cap + 32)
+                rows.append((f"outlines {hh}x{ww} n {N} (8), {scene}: regions {counts[:, 0].tolist()} of {cap}, contours {got[:, 0].tolist()} of {mc}, "
+                             f"vertices {got[:, 2].tolist()} of {mv}, flags {got[:, 3].tolist()}", 0.0, 0.0))
+                t = min(timed(lambda i, x=index, mc=mc, mv=mv: ops.region_outlines(x, 32768, 8, mc, mv)) for _ in range(3))
+                rows.append((f"  region_outlines, {rounds} ranking rounds: floor {floor / 1e6:.1f} MB, {floor / t / 1e12:.3f} TB/s", 1 / t, t * 1e3))
+                fits[scene] = (mc, mv)
+
+            def tail(i, lo=lo, gl=gl, gr=gr, hh=hh, ww=ww):
+                return ops.seg_tail(lo[0:1], lo[1:2], gl, gr, N, (hh, ww), False, want_logits=False, want_mask=True)[1]
+
+            def regions_of(m, cap):
+                return ops.region_table(m, ops.mask_regions(m, 5, 8), 5, None, 128, cap)
+
+            def outlined(m, cap, mc, mv):
+                return ops.region_outlines(regions_of(m, cap)[2], cap, 8, mc, mv)
+
+            for cap, (mc, mv), note in ((1024, (4096, 32768), "the defaults"), (32768, fits["blobs"], "the blob scene's caps")):
+                note += f", flags {outlined(tail(0), cap, mc, mv)[3][:, 3].tolist()}"
+                alt = [(timed(lambda i: regions_of(tail(i), cap)), timed(lambda i: outlined(tail(i), cap, mc, mv))) for _ in range(3)]
+                t_reg, t_out = (min(x[j] for x in alt) for j in range(2))
+                rows.append((f"seg_tail {hh}x{ww} warp + regions, max_regions {cap}", 1 / t_reg, t_reg * 1e3))
+                rows.append((f"  + outlines, max_contours {mc}, max_vertices {mv} ({note}): {(t_out / t_reg - 1) * 100:+.2f} % ({(t_out - t_reg) * 1e3:+.3f} ms)",
+                             1 / t_out, t_out * 1e3))
     if want("tracks"):
         # region identity across frames (ops.region_links / region_tracks, csrc/track_ops.hip): each op alone per call of N frames at the two
         # geometries on the closed-form lattice scene of the region tests (tests/regions_ref.py: disjoint 10 x 15 rectangles and one

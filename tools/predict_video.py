@@ -44,6 +44,11 @@ and estimated grids: `--raw`, or `--grids estimate`) compares each frame with th
 under the block matcher's vectors, so that a region which moves further than its own width per frame keeps its track; with
 `--scene-cut` the frames that follow a cut are listed and their regions all start new tracks.  Single process only: ids are per
 predictor.
+`--outlines FILE.geojson` (an extension; needs `--regions`) outlines every region on the device and writes, once at the
+end, one GeoJSON Polygon feature per frame and region -- the outer contour first, then the holes, closed rings in mask pixel lattice
+coordinates -- with frame, region, class, area, perimeter and holes (and track, parent with `--tracks`); the regions CSV gets the columns
+perimeter and holes.  A frame with more than `--max-vertices` outline vertices gets no outlines at all, one with more than
+`--max-contours` contours keeps the first ones; both get a warning.  The defaults are guesses, not validated on real video.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -63,7 +68,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv, write_regions_csv, write_tracks_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -147,11 +152,21 @@ def parse_args(argv=None):
                     "least N pixels")
     ap.add_argument("--max-pairs", type=int, default=None, metavar="N", help="--tracks: slots of the table of overlapping region pairs of two "
                     "consecutive frames, a power of two in 16..1048576 (default: the next one >= 4 x --max-regions)")
+    ap.add_argument("--outlines", metavar="FILE.geojson", help="--regions: outline every region on the device and write one GeoJSON polygon "
+                    "(outer contour and holes, mask pixel coordinates) per frame and region; the regions CSV gets the columns perimeter and "
+                    "holes")
+    ap.add_argument("--max-contours", type=int, default=4096, metavar="N", help="--outlines: contour rows per frame (1..1048576)")
+    ap.add_argument("--max-vertices", type=int, default=32768, metavar="N", help="--outlines: polygon vertices per frame (4..4194304); a frame "
+                    "with more gets no outlines at all")
     ap.add_argument("--compensate", action="store_true", help="--tracks with estimated grids: compare each frame with the frame before it read at "
                     "the source of every pixel under the block matcher's vectors, so that a small region that moves fast keeps its track")
     args = ap.parse_args(argv)
     if args.tracks and not args.regions:
         ap.error("--tracks needs --regions")
+    if args.outlines and not args.regions:
+        ap.error("--outlines needs --regions")
+    if not 1 <= args.max_contours <= 2 ** 20 or not 4 <= args.max_vertices <= 2 ** 22:
+        ap.error("--max-contours takes 1..1048576 and --max-vertices 4..4194304")
     if args.compensate and not args.tracks:
         ap.error("--compensate needs --tracks: it changes how the tracks' links are counted")
     if args.compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
@@ -220,7 +235,8 @@ def main():
                          compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache, confidence=args.confidence,
                          low_confidence=args.low_confidence, regions=bool(args.regions), min_region_area=args.min_region,
                          connectivity=args.connectivity, max_regions=args.max_regions, track=bool(args.tracks), min_overlap=args.min_overlap,
-                         max_pairs=args.max_pairs, compensate=args.compensate)
+                         max_pairs=args.max_pairs, compensate=args.compensate, outlines=bool(args.outlines), max_contours=args.max_contours,
+                         max_vertices=args.max_vertices)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
@@ -340,7 +356,18 @@ def main():
     if args.regions:  # likewise: one read-back after the timed run
         region_rows, totals = pred.region_report()
         track_rows, overflowed, cut = pred.track_report(with_cuts=True) if args.tracks else (None, [], [])
-        write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence, tracks=track_rows)
+        outlines = pred.outline_report() if args.outlines else None
+        write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence, tracks=track_rows,
+                          shapes=[o[2] for o in outlines[0]] if outlines else None)
+        if outlines:
+            write_outlines_geojson(args.outlines, report_ids, region_rows, outlines, tracks=track_rows)
+            for fid, flag in zip(report_ids, outlines[1].tolist()):
+                if flag & 1:
+                    print(f"warning: frame {fid} has more than --max-vertices {args.max_vertices} outline vertices: it has no outlines",
+                          file=sys.stderr)
+                elif flag & 2:
+                    print(f"warning: frame {fid} has more than --max-contours {args.max_contours} contours: the first {args.max_contours} are "
+                          "written", file=sys.stderr)
         if args.tracks:
             write_tracks_csv(args.tracks, report_ids, region_rows, track_rows)
             for fid, flag in zip(report_ids, overflowed.tolist()):
