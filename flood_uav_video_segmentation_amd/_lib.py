@@ -167,6 +167,12 @@ _EXT3_HOOKS = [
 ]
 EXT3_MAGIC = 0x4653455854414233  # FS_EXT3_MAGIC
 
+# members of fs_ext4_api, the fifth table (append-only, behind the four frozen ones), in declaration order after `magic` and `size`
+_EXT4_HOOKS = [
+    ("outline_simplify", c_int, [c_void] * 3 + [c_int] * 5 + [c_void] * 5),
+]
+EXT4_MAGIC = 0x4653455854414234  # FS_EXT4_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
@@ -196,6 +202,14 @@ class FsHookTables3(ctypes.Structure):
     _fields_ = [("base2", FsHookTables2), ("ext3", FsExt3Api)]
 
 
+class FsExt4Api(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT4_HOOKS]
+
+
+class FsHookTables4(ctypes.Structure):
+    _fields_ = [("base3", FsHookTables3), ("ext4", FsExt4Api)]
+
+
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
     fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
@@ -206,8 +220,27 @@ class _Library:
         self._ext = None
         self._ext2 = None
         self._ext3 = None
+        self._ext4 = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT4_HOOKS):
+            if self._ext4 is None:
+                all3 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables3)).contents
+                all2 = all3.base2
+                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
+                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
+                        or all3.ext3.magic != EXT3_MAGIC or all3.ext3.size != ctypes.sizeof(FsExt3Api)):
+                    raise RuntimeError(f"floodseg: the library's first four hook tables are not the ones this binding knows ({name} is missing)")
+                ext4 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables4)).contents.ext4
+                if ext4.magic != EXT4_MAGIC:
+                    raise RuntimeError(f"floodseg: the library has no fourth extension table ({name} is missing)")
+                self._ext4 = ext4
+            member = getattr(FsExt4Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
+            if self._ext4.size < member.offset + member.size:
+                raise RuntimeError(f"floodseg: the library's fourth extension table is older than this binding ({name} is missing)")
+            fn = getattr(self._ext4, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT3_HOOKS):
             if self._ext3 is None:
                 all2 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables2)).contents
@@ -306,6 +339,11 @@ def ext2_hook_names():
 def ext3_hook_names():
     """Members of fs_ext3_api after `magic` and `size`, in declaration order."""
     return [h[0] for h in _EXT3_HOOKS]
+
+
+def ext4_hook_names():
+    """Members of fs_ext4_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT4_HOOKS]
 
 
 def check(rc):

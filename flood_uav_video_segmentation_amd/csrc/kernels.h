@@ -377,6 +377,11 @@ int launch_region_tracks(const int* back, const int* fwd, const long long* count
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,
                            long long* contours, int* vertices, long long* shape, long long* counts, void* workspace, hipStream_t s);
 
+// Outline simplification (simplify_ops.hip, simplify_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments
+// before it launches anything; the workspace is the caller's (FS_OUTLINE_SIMPLIFY_WORKSPACE_BYTES), nothing is allocated or synchronised.
+int launch_outline_simplify(const long long* contours, const int* vertices, const long long* counts, int n, int max_contours, int max_vertices, int tol_q,
+                            int max_rounds, long long* simple, int* simple_vertices, long long* simple_counts, void* workspace, hipStream_t s);
+
 // ---------------------------------------------------------------------------------
 // Segmenter / ViT pieces (segm/model/vit.py, blocks.py, decoder.py); token matrices are row-major
 // [rows][D] -- i.e. the same "NHWC with ld" layout, so every nn.Linear runs on conv_igemm_f32.

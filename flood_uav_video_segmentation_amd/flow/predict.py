@@ -22,6 +22,10 @@ FlowPredictor(..., regions=True, outlines=True) also outlines every region on th
 outer contour and the holes, with the perimeter and the hole count per region (ops.region_outlines):
     frames, flags = p.outline_report()                                     # per frame (contour rows, vertices, shape rows); read back once
     write_outlines_geojson("o.geojson", ids, rows, (frames, flags))        # one Polygon feature per frame and region
+FlowPredictor(..., regions=True, outlines=True, simplify=1.0) also simplifies every ring on the device to a tolerance in pixels
+(ops.outline_simplify):
+    simple, counts = p.simple_outline_report()                             # per frame (rows, kept vertices); counts [frames, 4]
+    write_outlines_geojson("o.geojson", ids, rows, (frames, flags), simplified=(simple, counts), tolerance=1.0)
 """
 import numpy as np
 import torch
@@ -81,14 +85,21 @@ class FlowPredictor:
     defaults 472 KiB; a chunk holds as many frames as fit 64 MiB, 138 at the defaults), plus the op's workspace while a window is
     outlined.  A frame with more than max_vertices vertices gets NO contours and flag bit 0, one with more than max_contours contours
     keeps the first max_contours and flag bit 1; outline_report() hands the flags out.  The defaults (4096 contours, 32768 vertices) are
-    guesses for ragged 1080p water masks: no default has been validated on real video.  The masks are not touched."""
+    guesses for ragged 1080p water masks: no default has been validated on real video.  The masks are not touched.
+
+    simplify=TOL (extension, needs outlines=True; None: off): every outlined frame's rings are simplified on the device right behind
+    the outlines -- Ramer-Douglas-Peucker per ring, every dropped vertex within TOL pixels of the kept segment that spans it
+    (ops.outline_simplify) -- into chunked device buffers of their own (32 max_contours + 8 max_vertices + 32 bytes per
+    frame); the outline buffers stay as they are, and nothing is read back until simple_outline_report().  simplify_rounds (1..256)
+    caps the rounds: a ring with segments still open after the last round keeps all their vertices and is flagged, and the report's
+    `rounds` column tells how many a frame needed.  The default of 32 is a guess for natural shorelines, NOT validated on real video."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
                  max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False, outlines=False, max_contours=4096,
-                 max_vertices=32768):
+                 max_vertices=32768, simplify=None, simplify_rounds=32):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -146,6 +157,18 @@ class FlowPredictor:
         self.outline_chunk = max(1, min(self.REPORT_CHUNK, ((64 << 20) - 1) // per_frame))  # frames per device buffer: below 64 MiB
         self._outline_chunks = []  # (contours, vertices, shape, counts) device buffers of outline_chunk frames each, in frame order
         self._outline_frames = 0
+        if simplify is not None and not outlines:
+            raise ValueError("FlowPredictor: simplify needs outlines=True (it simplifies the rings the outlines just wrote)")
+        if not 1 <= int(simplify_rounds) <= 256:
+            raise ValueError(f"FlowPredictor: simplify_rounds must be 1..256, got {simplify_rounds}")
+        if simplify is not None:
+            ops.simplify_tol_q(simplify)  # ValueError outside 0..256 pixels
+        self.simplify = None if simplify is None else float(simplify)
+        self.simplify_rounds = int(simplify_rounds)
+        per_frame = 8 * self.max_vertices + 32 * self.max_contours + 32
+        self.simple_chunk = max(1, min(self.REPORT_CHUNK, ((64 << 20) - 1) // per_frame))  # frames per device buffer: below 64 MiB
+        self._simple_chunks = []  # (simple, simple_vertices, simple_counts) device buffers of simple_chunk frames each, in frame order
+        self._simple_frames = 0
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
@@ -166,6 +189,8 @@ class FlowPredictor:
         self._track_chunks = []  # the previous frame and the next track id stay
         self._outline_chunks = []
         self._outline_frames = 0
+        self._simple_chunks = []
+        self._simple_frames = 0
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -267,10 +292,48 @@ class FlowPredictor:
                                              torch.zeros((c, self.max_regions, 3), dtype=torch.int64, device=dev),
                                              torch.zeros((c, 4), dtype=torch.int64, device=dev)))
             take = min(n - done, self.outline_chunk - row)
-            ops.region_outlines(index[done:done + take], self.max_regions, self.connectivity, self.max_contours, self.max_vertices,
-                                out=tuple(b[row:row + take] for b in self._outline_chunks[-1]))
+            piece = tuple(b[row:row + take] for b in self._outline_chunks[-1])
+            ops.region_outlines(index[done:done + take], self.max_regions, self.connectivity, self.max_contours, self.max_vertices, out=piece)
+            if self.simplify is not None:
+                self._keep_simple(piece[0], piece[1], piece[3])
             done += take
             self._outline_frames += take
+
+    def _keep_simple(self, contours, vertices, counts):
+        """The simplified rings of the outlines region_outlines just wrote into the next rows of their own chunked buffers
+        (outline_simplify writes its rows whole; nothing is read back)."""
+        done, n, dev = 0, contours.shape[0], contours.device
+        while done < n:
+            row = self._simple_frames % self.simple_chunk
+            if row == 0:
+                c = self.simple_chunk
+                self._simple_chunks.append((torch.zeros((c, self.max_contours, 4), dtype=torch.int64, device=dev),
+                                            torch.zeros((c, self.max_vertices, 2), dtype=torch.int32, device=dev),
+                                            torch.zeros((c, 4), dtype=torch.int64, device=dev)))
+            take = min(n - done, self.simple_chunk - row)
+            ops.outline_simplify(contours[done:done + take], vertices[done:done + take], counts[done:done + take], self.simplify, self.simplify_rounds,
+                                 out=tuple(b[row:row + take] for b in self._simple_chunks[-1]))
+            done += take
+            self._simple_frames += take
+
+    def simple_outline_report(self):
+        """simplify=TOL: (frames, counts) for every frame of outline_report(), in its order: frames[f] = (rows int64 numpy [rows, 4],
+        vertices int32 numpy [kept, 2]) -- row for row outline_report()'s contour rows (first offset, kept count, area2 of the kept
+        ring, flags: bit 0 unconverged) and the kept vertices back to back; counts = int64 numpy [frames, 4] = (rows, kept vertices,
+        rounds, flags), flags bit 0: some ring still had open segments after simplify_rounds rounds (all their vertices are kept: raise
+        simplify_rounds above the `rounds` column), bit 1: the frame's outlines had overflowed (nothing), bit 2: the outlines had more
+        contours than rows, bit 3: inconsistent rows (nothing).  The read-back happens here, chunk by chunk."""
+        if not self._simple_chunks:
+            return [], np.zeros((0, 4), dtype=np.int64)
+        frames, counts, left = [], [], self._simple_frames
+        for simple, vertices, cnt in self._simple_chunks:
+            take = min(left, self.simple_chunk)
+            c = cnt[:take].cpu().numpy()
+            rows, verts = simple[:take].cpu().numpy(), vertices[:take].cpu().numpy()
+            frames.extend((rows[f, :int(c[f, 0])], verts[f, :int(c[f, 1])]) for f in range(take))
+            counts.append(c)
+            left -= take
+        return frames, np.concatenate(counts)
 
     def outline_report(self):
         """outlines=True: (frames, flags) for every frame of region_report(), in its order: frames[f] = (contours int64 numpy [rows, 6],
@@ -620,7 +683,7 @@ def write_regions_csv(path, frame_ids, rows, with_confidence=True, tracks=None, 
                 fh.write(",".join(cells) + "\n")
 
 
-def write_outlines_geojson(path, frame_ids, rows, outlines, tracks=None):
+def write_outlines_geojson(path, frame_ids, rows, outlines, tracks=None, simplified=None, tolerance=None):
     """The regions' shapes as one GeoJSON FeatureCollection, one Feature per frame and region, from region_report()'s rows and
     outlines = FlowPredictor.outline_report()'s (frames, flags).  The geometry is a Polygon whose rings are the region's outer contour
     first, then its holes, each closed by repeating its first vertex; the coordinates are mask pixel lattice coordinates (x to the
@@ -628,7 +691,13 @@ def write_outlines_geojson(path, frame_ids, rows, outlines, tracks=None):
     track_report()'s rows also track and parent.  A frame whose flag bit 0 is set (more vertices than max_vertices: it has no contours)
     contributes no features and is named in the top-level list "overflowed_frames"; a frame with bit 1 (more contours than
     max_contours) is named in "truncated_frames", and its regions come with the rings that have rows -- a region whose outer contour
-    has none is left out."""
+    has none is left out.
+    simplified = FlowPredictor.simple_outline_report()'s (frames, counts), with tolerance = the tolerance in pixels they were made with:
+    the rings are the SIMPLIFIED ones (each ring on its own: neighbouring regions' rings may cross or leave slivers), every feature
+    gains the properties tolerance, vertices_full (the vertices its rings had before) and area2_simplified (twice the simplified
+    polygon's area, holes taken off; `area` stays the pixel count), and the frames in which some ring hit the round cap -- it kept all
+    vertices of the segments still open -- are named in the top-level list "unconverged_frames".  None: the file without any of it,
+    byte for byte."""
     import json
 
     frames, flags = outlines
@@ -637,16 +706,34 @@ def write_outlines_geojson(path, frame_ids, rows, outlines, tracks=None):
                          f"for {len(rows)} frames")
     if tracks is not None and (len(tracks) != len(rows) or any(len(t) != len(r) for t, r in zip(tracks, rows))):
         raise ValueError("write_outlines_geojson: tracks must hold one row per region of every frame")
-    features, overflowed, truncated = [], [], []
+    if simplified is not None:
+        if tolerance is None:
+            raise ValueError("write_outlines_geojson: simplified rings need the tolerance they were made with")
+        if len(simplified[0]) != len(rows) or len(simplified[1]) != len(rows):
+            raise ValueError(f"write_outlines_geojson: one simplified outline per frame, got {len(simplified[0])} for {len(rows)} frames")
+    features, overflowed, truncated, unconverged = [], [], [], []
     for f, (fid, table, (contours, vertices, shape)) in enumerate(zip(frame_ids, rows, frames)):
         if int(flags[f]) & 1:
             overflowed.append(fid)
             continue
         if int(flags[f]) & 2:
             truncated.append(fid)
-        outer, holes = {}, {}
-        for region, first, count, _, area2, _ in np.asarray(contours).tolist():
-            ring = np.asarray(vertices[first:first + count]).tolist()
+        outer, holes, full, simple_area2 = {}, {}, {}, {}
+        if simplified is not None:
+            simple_rows, simple_vertices = simplified[0][f]
+            if len(simple_rows) != len(contours) or int(simplified[1][f][3]) & 10:
+                raise ValueError(f"write_outlines_geojson: frame {fid} has {len(contours)} contour rows but {len(simple_rows)} simplified ones "
+                                 f"(flags {int(simplified[1][f][3])})")
+            if int(simplified[1][f][3]) & 1:
+                unconverged.append(fid)
+            simple_rows = np.asarray(simple_rows).tolist()
+        for k, (region, first, count, _, area2, _) in enumerate(np.asarray(contours).tolist()):
+            if simplified is None:
+                ring = np.asarray(vertices[first:first + count]).tolist()
+            else:
+                ring = np.asarray(simple_vertices[simple_rows[k][0]:simple_rows[k][0] + simple_rows[k][1]]).tolist()
+                full[region] = full.get(region, 0) + count
+                simple_area2[region] = simple_area2.get(region, 0) + simple_rows[k][2]
             ring.append(ring[0])
             if area2 > 0:
                 outer[region] = ring
@@ -659,10 +746,16 @@ def write_outlines_geojson(path, frame_ids, rows, outlines, tracks=None):
             props = {"frame": fid, "region": r, "class": row[0], "area": row[1], "perimeter": perimeter, "holes": count - 1}
             if tracks is not None:
                 props["track"], props["parent"] = np.asarray(tracks[f][r]).tolist()[:2]
+            if simplified is not None:
+                props["tolerance"], props["vertices_full"], props["area2_simplified"] = float(tolerance), full[r], simple_area2[r]
             features.append({"type": "Feature", "properties": props,
                              "geometry": {"type": "Polygon", "coordinates": [outer[r]] + holes.get(r, [])}})
     with open(path, "w") as fh:
-        json.dump({"type": "FeatureCollection", "overflowed_frames": overflowed, "truncated_frames": truncated, "features": features}, fh)
+        doc = {"type": "FeatureCollection", "overflowed_frames": overflowed, "truncated_frames": truncated}
+        if simplified is not None:
+            doc["unconverged_frames"] = unconverged
+        doc["features"] = features
+        json.dump(doc, fh)
         fh.write("\n")
 
 

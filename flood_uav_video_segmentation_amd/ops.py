@@ -775,6 +775,59 @@ def region_outlines(index, max_regions, connectivity=8, max_contours=4096, max_v
     return tuple(out)
 
 
+# ------------------------------------------------------------------------------------------ outline simplification
+def outline_simplify_workspace_bytes(n, max_contours, max_vertices):
+    """FS_OUTLINE_SIMPLIFY_WORKSPACE_BYTES of include/floodseg_test.h."""
+    return n * 8 * (6 * max_vertices + ((max_vertices + 1023) // 1024 + 1) // 2 + (max_contours + 1) // 2 + 262)
+
+
+def simplify_tol_q(tolerance):
+    """A tolerance in pixels -> tol_q = round(16 tolerance^2), the integer the op compares with (0..2^20, that is 0..256 px)."""
+    tol = float(tolerance)
+    if not 0.0 <= tol <= 256.0:                                # NaN fails both comparisons
+        raise ValueError(f"floodseg.outline_simplify: tolerance must be 0..256 pixels, got {tolerance}")
+    return int(round(16.0 * tol * tol))
+
+
+def outline_simplify(contours, vertices, counts, tolerance, max_rounds=32, out=None):
+    """region_outlines' (contours int64 [n,C,6], vertices int32 [n,V,2], counts int64 [n,4]) -> (simple int64 [n,C,4], simple_vertices
+    int32 [n,V,2], simple_counts int64 [n,4]) (definition: include/floodseg_test.h, outline_simplify): Ramer-Douglas-Peucker on every
+    contour ring, every dropped vertex within `tolerance` pixels of the kept segment that spans it (tol_q = round(16 tolerance^2)).  A
+    simple row is (first offset, kept count, area2 of the kept ring, flags: bit 0 unconverged), parallel to the contour rows;
+    simple_vertices holds the kept vertices back to back; simple_counts rows are (rows, kept vertices, rounds, flags): bit 0 = some
+    contour still had open segments after max_rounds rounds (their vertices are all kept), bit 1 = the frame's outlines had overflowed
+    (nothing), bit 2 = the outlines had more contours than rows, bit 3 = inconsistent rows (nothing).  rounds is the largest round that
+    split a segment: a frame flagged bit 0 needs a larger max_rounds (1..256; the default 32 is a guess for natural shorelines, not
+    validated on real video).  out: caller-owned contiguous destinations in the order of the result; they are written whole.  The
+    workspace (48 bytes per possible vertex and frame) is allocated here."""
+    tol_q = simplify_tol_q(tolerance)
+    if not 1 <= int(max_rounds) <= 256:
+        raise ValueError(f"floodseg.outline_simplify: max_rounds must be 1..256, got {max_rounds}")
+    lib = _lib.load()
+    dev = one_device(contours, vertices, counts, *(out or ()), what="floodseg.outline_simplify")
+    if (contours.dtype != torch.int64 or contours.dim() != 3 or contours.shape[2] != 6 or vertices.dtype != torch.int32 or vertices.dim() != 3
+            or vertices.shape[2] != 2 or counts.dtype != torch.int64 or tuple(counts.shape) != (contours.shape[0], 4)
+            or vertices.shape[0] != contours.shape[0]):
+        raise RuntimeError("floodseg.outline_simplify: contours must be int64 [n,C,6], vertices int32 [n,V,2] and counts int64 [n,4], got "
+                           f"{contours.dtype} {tuple(contours.shape)}, {vertices.dtype} {tuple(vertices.shape)} and {counts.dtype} {tuple(counts.shape)}")
+    n, mc, mv = contours.shape[0], contours.shape[1], vertices.shape[1]
+    if n > 65535 or not 1 <= mc <= 2 ** 20 or not 4 <= mv <= 2 ** 22:
+        raise RuntimeError(f"floodseg.outline_simplify: at most 65535 frames, 1..2^20 contour rows and 4..2^22 vertices, got {n}, {mc} and {mv}")
+    shapes = ((n, mc, 4), (n, mv, 2), (n, 4))
+    dtypes = (torch.int64, torch.int32, torch.int64)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+        elif len(out) != 3 or any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, s, d in zip(out, shapes, dtypes)):
+            raise RuntimeError(f"floodseg.outline_simplify: out must be contiguous int64 {list(shapes[0])}, int32 {list(shapes[1])} and int64 "
+                               f"{list(shapes[2])} tensors")
+        if n:
+            work = torch.empty((outline_simplify_workspace_bytes(n, mc, mv) // 8,), dtype=torch.int64, device=dev)
+            check(lib.fs_outline_simplify(ptr(contours.contiguous()), ptr(vertices.contiguous()), ptr(counts.contiguous()), n, mc, mv, tol_q,
+                                          int(max_rounds), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(work), stream_ptr()))
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------------------ block motion estimation
 def block_match(cur, ref, search=16, penalty=0, return_cost=False):
     """Full-search block matching of two uint8 frames [H,W] (luma) or [H,W,3] (RGB as decoded), `ref` the past frame: the motion-vector

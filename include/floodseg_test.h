@@ -590,6 +590,67 @@ typedef struct fs_hook_tables3 {
     fs_ext3_api ext3;
 } fs_hook_tables3;
 
+/* ---- The FIFTH table.  fs_ext3_api is frozen as well (1 member, 24 bytes; tests/test_outlines_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables3 by the same pattern:
+ *     const fs_hook_tables4* t = (const fs_hook_tables4*)fs_test_hooks();   t->ext4.outline_simplify(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables3: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext4.magic == FS_EXT4_MAGIC and ext4.size >= the end of the member it needs. */
+#define FS_EXT4_MAGIC 0x4653455854414234ull /* "FSEXTAB4" */
+
+typedef struct fs_ext4_api {
+    uint64_t magic; /* FS_EXT4_MAGIC */
+    size_t size;    /* sizeof(fs_ext4_api) of the library that was built */
+
+    /* ---- Outline simplification (csrc/simplify_ops.hip, csrc/simplify_defs.h).  OUR DEFINITION: Ramer-Douglas-Peucker
+     * on every contour ring of region_outlines, with a tolerance in pixels.  Integers throughout; every result is a function of the
+     * inputs alone, whatever order threads arrive in.  C = max_contours, V = max_vertices.
+     * Inputs: the outputs of region_outlines for n frames,
+     *   contours  int64 [n][C][6], of which the columns 1 (first vertex offset) and 2 (vertex count) are read,
+     *   vertices  int32 [n][V][2]; every coordinate is read clamped to 0..16384,
+     *   counts    int64 [n][4] = (contours, rows, vertices, flags): a frame's rows are the first counts[f][1], its total counts[f][2],
+     *   tol_q     = 16 * tolerance^2 in pixel^2 (0.5 px = 4, 1 px = 16, 2 px = 64), 0..2^20,
+     *   max_rounds  1..256.
+     * VALID FRAMES.  A frame is simplified only if its flag bit 0 is clear, 0 <= rows <= C, total <= V, every row has count >= 3, every
+     * row's offset is the exclusive prefix sum of the counts of the rows before it, and the counts sum to at most total -- what
+     * region_outlines guarantees.  Any other frame gets nothing and a flag, so no garbage plane steers a store outside the buffers.
+     * DISTANCE KEY.  For a segment a = v[l] -> b = v[r] and a vertex p: L = |b - a|^2, t = (b - a).(p - a);
+     *   L = 0: q = |p - a|^2;   t <= 0: q = |p - a|^2 L;   t >= L: q = |p - b|^2 L;   else q = cross(b - a, p - a)^2,
+     * so q / L is the squared distance from p to the SEGMENT, exactly (coordinates <= 2^14: q <= 2^58, 16 q <= 2^62).
+     * PER CONTOUR, vertices v[0..m-1], v[0] the anchor's vertex, index m = v[0] again.
+     *   Round 0: v[0] is kept; the whole ring (0, m) is one open segment with a = b = v[0], and it always splits at its vertex of
+     *     largest q -- the vertex farthest from v[0] -- smallest index on a tie.
+     *   Round k = 1..max_rounds: every open segment with interior vertices finds its interior vertex of largest q, smallest index on a
+     *     tie.  If the test passes the vertex is kept and the segment splits into two open segments examined in round k + 1; if not,
+     *     the segment is closed and its interior vertices are dropped.  The test is q > 0 in round 1, whatever the tolerance (a closed
+     *     lattice contour does not lie on one segment, so every ring keeps at least 3 vertices), and 16 q > tol_q L from round 2 on.
+     *   After the last round every segment still open keeps ALL its interior vertices and the contour is flagged unconverged: every
+     *     dropped vertex is within the tolerance of the kept segment that spans it, cap or no cap.
+     * Outputs, each written whole by every call:
+     *   simple          = int64 [n][C][4] = (first offset, kept count, area2 of the kept ring, flags) per row, parallel to the rows of
+     *                     contours; flag bit 0 = unconverged; rows behind the last are zero.
+     *   simple_vertices = int32 [n][V][2], the kept vertices in input order, rings back to back in row order (offsets are the
+     *                     exclusive prefix sums of the kept counts); zero behind the total.
+     *   simple_counts   = int64 [n][4] = (rows, kept vertices, rounds, flags); rounds = the largest round in which a segment of the
+     *                     frame split.  Flag bit 0: some contour is unconverged; bit 1: the input frame had overflowed its vertices
+     *                     (input flag bit 0) and gets nothing; bit 2: the input had more contours than rows (counts[f][0] >
+     *                     counts[f][1]), those without a row are not simplified; bit 3: the rows are inconsistent, the frame gets nothing.
+     * workspace = FS_OUTLINE_SIMPLIFY_WORKSPACE_BYTES(n, max_contours, max_vertices) bytes at an 8-byte aligned address, the caller's:
+     * per frame 48 bytes per possible vertex, 4 per possible contour, 4 per 1024 possible vertices and 2096.  Nothing is allocated,
+     * synchronised or read on the host; the 10 + 2 max_rounds launches capture into a HIP graph.
+     * Refused before a launch: a null pointer; n outside 1..65535; max_contours outside 1..2^20; max_vertices outside 4..2^22; tol_q
+     * outside 0..2^20; max_rounds outside 1..256; a workspace not aligned to 8 bytes. */
+#define FS_OUTLINE_SIMPLIFY_WORKSPACE_BYTES(n, max_contours, max_vertices)                                                             \
+    ((size_t)(n) * 8 * (6 * (size_t)(max_vertices) + (((size_t)(max_vertices) + 1023) / 1024 + 1) / 2 + ((size_t)(max_contours) + 1) / 2 + 262))
+    int (*outline_simplify)(const int64_t* contours, const int32_t* vertices, const int64_t* counts, int n, int max_contours, int max_vertices,
+                            int tol_q, int max_rounds, int64_t* simple, int32_t* simple_vertices, int64_t* simple_counts, void* workspace,
+                            fs_stream stream);
+} fs_ext4_api;
+
+typedef struct fs_hook_tables4 {
+    fs_hook_tables3 base3;
+    fs_ext4_api ext4;
+} fs_hook_tables4;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

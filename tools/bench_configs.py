@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions tracks outlines cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions tracks outlines simplify cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | tracks | outlines | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | tracks | outlines | simplify | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -460,6 +460,47 @@ def main():
                 rows.append((f"seg_tail {hh}x{ww} warp + regions, max_regions {cap}", 1 / t_reg, t_reg * 1e3))
                 rows.append((f"  + outlines, max_contours {mc}, max_vertices {mv} ({note}): {(t_out / t_reg - 1) * 100:+.2f} % ({(t_out - t_reg) * 1e3:+.3f} ms)",
                              1 / t_out, t_out * 1e3))
+    if want("simplify"):
+        # outline simplification (ops.outline_simplify, csrc/simplify_ops.hip): the four scenes of the outlines section (same seeds, same
+        # caps), outlined once; then per call of N frames the outlines alone and the simplification alone at 1 px and the default 32
+        # rounds, alternating, every loop >= 0.5 s, beside the bytes the simplification must move at least: the outputs written once
+        # (zeroed: 32 B a contour row, 8 B a vertex of the caps), per vertex 8 B read, 16 B of cell written and read per round it is
+        # open in (taken as the frame's `rounds`, an upper bound on no vertex), and 8 B per kept vertex.  Then the kept vertices and the
+        # rounds at 0.5, 1 and 2 px with 256 rounds allowed, which is what tells whether 32 are enough.
+        gen = torch.Generator().manual_seed(1800)
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+
+        def pow2(v):
+            return 1 << max(2, int(v - 1).bit_length())
+
+        for hh, ww in ((713, 713), (1072, 1920)):
+            low = torch.randn((N, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen).to(dev)
+            torch.randn((2, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=gen)     # the outlines section's second draw: keeps the scenes in step
+            coarse = torch.randn((N, 5, (hh - 1) // 64 + 1, (ww - 1) // 64 + 1), generator=torch.Generator().manual_seed(1801)).to(dev)
+            for scene, logits in (("blobs", low), ("a few large regions", coarse)):
+                mask = ops.mask_confidence(logits, (hh, ww))[0]
+                cap = 32768
+                index = ops.region_table(mask, ops.mask_regions(mask, 5, 8), 5, None, 128, cap)[2]
+                mv = pow2(int(ops.region_outlines(index, cap, 8, 4, 4)[3][:, 2].max()))
+                mc = pow2(mv // 4)
+                contours, vertices, _, counts = ops.region_outlines(index, cap, 8, mc, mv)
+                full = int(counts[:, 2].sum())
+                got = ops.outline_simplify(contours, vertices, counts, 1.0, 32)[2]
+                floor = N * (32 * mc + 8 * mv + 32) + full * (8 + 16 * int(got[:, 2].max())) + 8 * int(got[:, 1].sum())
+                alt = [(timed(lambda i: ops.region_outlines(index, cap, 8, mc, mv)), timed(lambda i: ops.outline_simplify(contours, vertices, counts, 1.0, 32)))
+                       for _ in range(3)]
+                t_out, t_smp = (min(x[j] for x in alt) for j in range(2))
+                rows.append((f"simplify {hh}x{ww} n {N} (8), {scene}: {full} vertices on {counts[:, 0].tolist()} contours, caps {mc} / {mv}", 0.0, 0.0))
+                rows.append(("  region_outlines alone", 1 / t_out, t_out * 1e3))
+                rows.append((f"  outline_simplify 1 px, 32 rounds ({10 + 2 * 32} launches): kept {got[:, 1].tolist()}, rounds {got[:, 2].tolist()}, flags "
+                             f"{got[:, 3].tolist()}; floor {floor / 1e6:.1f} MB, {floor / t_smp / 1e12:.3f} TB/s", 1 / t_smp, t_smp * 1e3))
+                for tol in (0.5, 1.0, 2.0):
+                    g = ops.outline_simplify(contours, vertices, counts, tol, 256)[2]
+                    rows.append((f"  {tol} px, 256 rounds allowed: kept {int(g[:, 1].sum())} of {full} ({g[:, 1].tolist()}), rounds {g[:, 2].tolist()}, flags "
+                                 f"{g[:, 3].tolist()}", 0.0, 0.0))
     if want("tracks"):
         # region identity across frames (ops.region_links / region_tracks, csrc/track_ops.hip): each op alone per call of N frames at the two
         # geometries on the closed-form lattice scene of the region tests (tests/regions_ref.py: disjoint 10 x 15 rectangles and one

@@ -49,6 +49,11 @@ end, one GeoJSON Polygon feature per frame and region -- the outer contour first
 coordinates -- with frame, region, class, area, perimeter and holes (and track, parent with `--tracks`); the regions CSV gets the columns
 perimeter and holes.  A frame with more than `--max-vertices` outline vertices gets no outlines at all, one with more than
 `--max-contours` contours keeps the first ones; both get a warning.  The defaults are guesses, not validated on real video.
+`--simplify PX` (an extension; needs `--outlines`) simplifies every ring on the device before it is written: every dropped
+vertex lies within PX pixels of the ring that is written, and every feature gains tolerance, vertices_full and area2_simplified.
+`--simplify-rounds N` (1..256, default 32) caps the rounds: a frame in which some ring still had open segments after N rounds gets a
+warning (those segments keep all their vertices), and the largest number of rounds a frame needed is printed at the end -- the figure
+to set N by.  The default is a guess for natural shorelines, not validated on real video.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -158,6 +163,10 @@ def parse_args(argv=None):
     ap.add_argument("--max-contours", type=int, default=4096, metavar="N", help="--outlines: contour rows per frame (1..1048576)")
     ap.add_argument("--max-vertices", type=int, default=32768, metavar="N", help="--outlines: polygon vertices per frame (4..4194304); a frame "
                     "with more gets no outlines at all")
+    ap.add_argument("--simplify", type=float, default=None, metavar="PX", help="--outlines: simplify every ring on the device (Douglas-Peucker), "
+                    "every dropped vertex within PX pixels (0..256) of the ring that is written")
+    ap.add_argument("--simplify-rounds", type=int, default=32, metavar="N", help="--simplify: the round cap (1..256); rings that need more keep "
+                    "all vertices of the segments still open and get a warning.  The default is a guess, not validated on real video")
     ap.add_argument("--compensate", action="store_true", help="--tracks with estimated grids: compare each frame with the frame before it read at "
                     "the source of every pixel under the block matcher's vectors, so that a small region that moves fast keeps its track")
     args = ap.parse_args(argv)
@@ -167,6 +176,12 @@ def parse_args(argv=None):
         ap.error("--outlines needs --regions")
     if not 1 <= args.max_contours <= 2 ** 20 or not 4 <= args.max_vertices <= 2 ** 22:
         ap.error("--max-contours takes 1..1048576 and --max-vertices 4..4194304")
+    if args.simplify is not None and not args.outlines:
+        ap.error("--simplify needs --outlines")
+    if args.simplify is not None and not 0.0 <= args.simplify <= 256.0:
+        ap.error("--simplify takes a tolerance of 0..256 pixels")
+    if not 1 <= args.simplify_rounds <= 256:
+        ap.error("--simplify-rounds takes 1..256")
     if args.compensate and not args.tracks:
         ap.error("--compensate needs --tracks: it changes how the tracks' links are counted")
     if args.compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
@@ -236,7 +251,7 @@ def main():
                          low_confidence=args.low_confidence, regions=bool(args.regions), min_region_area=args.min_region,
                          connectivity=args.connectivity, max_regions=args.max_regions, track=bool(args.tracks), min_overlap=args.min_overlap,
                          max_pairs=args.max_pairs, compensate=args.compensate, outlines=bool(args.outlines), max_contours=args.max_contours,
-                         max_vertices=args.max_vertices)
+                         max_vertices=args.max_vertices, simplify=args.simplify, simplify_rounds=args.simplify_rounds)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
@@ -360,7 +375,19 @@ def main():
         write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence, tracks=track_rows,
                           shapes=[o[2] for o in outlines[0]] if outlines else None)
         if outlines:
-            write_outlines_geojson(args.outlines, report_ids, region_rows, outlines, tracks=track_rows)
+            simple = pred.simple_outline_report() if args.simplify is not None else None
+            write_outlines_geojson(args.outlines, report_ids, region_rows, outlines, tracks=track_rows, simplified=simple, tolerance=args.simplify)
+            if simple:
+                for fid, (_, _, _, flag) in zip(report_ids, simple[1].tolist()):
+                    if flag & 1:
+                        print(f"warning: frame {fid} has rings that were still being split after --simplify-rounds {args.simplify_rounds}: their open "
+                              "segments keep all vertices", file=sys.stderr)
+                    if flag & ~1:
+                        print(f"warning: frame {fid} is not simplified in full (flags {flag}: 2 = its outlines overflowed, 4 = contours without a "
+                              "row, 8 = inconsistent rows)", file=sys.stderr)
+                kept, full = int(simple[1][:, 1].sum()), sum(len(o[1]) for o in outlines[0])
+                print(f"simplify {args.simplify} px: {kept} of {full} vertices written; the largest number of rounds a frame needed: "
+                      f"{int(simple[1][:, 2].max()) if len(simple[1]) else 0} (--simplify-rounds {args.simplify_rounds})", file=sys.stderr)
             for fid, flag in zip(report_ids, outlines[1].tolist()):
                 if flag & 1:
                     print(f"warning: frame {fid} has more than --max-vertices {args.max_vertices} outline vertices: it has no outlines",
