@@ -173,6 +173,13 @@ _EXT4_HOOKS = [
 ]
 EXT4_MAGIC = 0x4653455854414234  # FS_EXT4_MAGIC
 
+# members of fs_ext5_api, the sixth table (append-only, behind the five frozen ones), in declaration order after `magic` and `size`
+_EXT5_HOOKS = [
+    ("frame_compose_regions", c_int, [c_void, c_int, c_int, c_void, c_int, c_void, c_void, c_void] + [c_int] * 5 + [c_void, c_void, c_void] + [c_int] * 3
+     + [c_void] * 4 + [c_int, c_void, c_int, c_void, c_int, c_int, c_i64, ctypes.c_uint32, ctypes.c_uint32, c_void, c_void]),
+]
+EXT5_MAGIC = 0x4653455854414235  # FS_EXT5_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
@@ -210,6 +217,14 @@ class FsHookTables4(ctypes.Structure):
     _fields_ = [("base3", FsHookTables3), ("ext4", FsExt4Api)]
 
 
+class FsExt5Api(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT5_HOOKS]
+
+
+class FsHookTables5(ctypes.Structure):
+    _fields_ = [("base4", FsHookTables4), ("ext5", FsExt5Api)]
+
+
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
     fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
@@ -221,8 +236,28 @@ class _Library:
         self._ext2 = None
         self._ext3 = None
         self._ext4 = None
+        self._ext5 = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT5_HOOKS):
+            if self._ext5 is None:
+                all4 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables4)).contents
+                all2 = all4.base3.base2
+                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
+                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
+                        or all4.base3.ext3.magic != EXT3_MAGIC or all4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
+                        or all4.ext4.magic != EXT4_MAGIC or all4.ext4.size != ctypes.sizeof(FsExt4Api)):
+                    raise RuntimeError(f"floodseg: the library's first five hook tables are not the ones this binding knows ({name} is missing)")
+                ext5 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables5)).contents.ext5
+                if ext5.magic != EXT5_MAGIC:
+                    raise RuntimeError(f"floodseg: the library has no fifth extension table ({name} is missing)")
+                self._ext5 = ext5
+            member = getattr(FsExt5Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
+            if self._ext5.size < member.offset + member.size:
+                raise RuntimeError(f"floodseg: the library's fifth extension table is older than this binding ({name} is missing)")
+            fn = getattr(self._ext5, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT4_HOOKS):
             if self._ext4 is None:
                 all3 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables3)).contents
@@ -344,6 +379,11 @@ def ext3_hook_names():
 def ext4_hook_names():
     """Members of fs_ext4_api after `magic` and `size`, in declaration order."""
     return [h[0] for h in _EXT4_HOOKS]
+
+
+def ext5_hook_names():
+    """Members of fs_ext5_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT5_HOOKS]
 
 
 def check(rc):

@@ -464,32 +464,68 @@ static int fs_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_
     if (reinterpret_cast<uintptr_t>(out) % 4 != 0) return fs::fail("fs_frame_prepare: out is not aligned to a float");
     return fs::launch_frame_prepare(frame, u, v, format, matrix, full_range, H, W, mean, std, out, h, w, S(stream));
 }
+// the refusals frame_compose and frame_compose_regions share, under the caller's name
+static int frame_compose_args(const char* what, const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u,
+                              const uint8_t* v, int format, int matrix, int full_range, int H, int W, const uint8_t* out, const uint8_t* out_u,
+                              const uint8_t* out_v, int out_format, int out_matrix, int out_full_range) {
+    if (!mask || !palette || !out) return fs::fail("%s: null pointer", what);
+    if (format < 0 || format > 2 || out_format < 0 || out_format > 2)
+        return fs::fail("%s: format must be 0 (RGB24), 1 (NV12) or 2 (I420), got %d in, %d out", what, format, out_format);
+    if ((matrix != 0 && matrix != 1) || (out_matrix != 0 && out_matrix != 1))
+        return fs::fail("%s: matrix must be 0 (BT.601) or 1 (BT.709), got %d in, %d out", what, matrix, out_matrix);
+    if ((full_range != 0 && full_range != 1) || (out_full_range != 0 && out_full_range != 1))
+        return fs::fail("%s: range must be 0 (limited) or 1 (full), got %d in, %d out", what, full_range, out_full_range);
+    if (K < 1 || K > 256) return fs::fail("%s: palette must hold 1..256 classes, got %d", what, K);
+    if (h < 1 || w < 1) return fs::fail("%s: empty frame (%d x %d)", what, h, w);
+    if ((int64_t)h * w * 3 >= ((int64_t)1 << 31)) return fs::fail("%s: output too large (%d x %d x 3 bytes pass 2^31)", what, h, w);
+    if (out_format != 0 && (!out_u || (out_format == 2 && !out_v))) return fs::fail("%s: null output chroma pointer for a YUV format", what);
+    if (!frame) {
+        if (H != 0 || W != 0 || u || v) return fs::fail("%s: background geometry or chroma (%d x %d) without a background frame", what, H, W);
+    } else {
+        if (H < 1 || W < 1) return fs::fail("%s: a background frame without its geometry (%d x %d)", what, H, W);
+        if ((int64_t)H * W * 3 >= ((int64_t)1 << 31)) return fs::fail("%s: background too large (%d x %d x 3 bytes pass 2^31)", what, H, W);
+        if (format != 0 && (!u || (format == 2 && !v))) return fs::fail("%s: null background chroma pointer for a YUV format", what);
+    }
+    return 0;
+}
 static int fs_frame_compose(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u, const uint8_t* v,
                             int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v, int out_format,
                             int out_matrix, int out_full_range, fs_stream stream) {
-    if (!mask || !palette || !out) return fs::fail("fs_frame_compose: null pointer");
-    if (format < 0 || format > 2 || out_format < 0 || out_format > 2)
-        return fs::fail("fs_frame_compose: format must be 0 (RGB24), 1 (NV12) or 2 (I420), got %d in, %d out", format, out_format);
-    if ((matrix != 0 && matrix != 1) || (out_matrix != 0 && out_matrix != 1))
-        return fs::fail("fs_frame_compose: matrix must be 0 (BT.601) or 1 (BT.709), got %d in, %d out", matrix, out_matrix);
-    if ((full_range != 0 && full_range != 1) || (out_full_range != 0 && out_full_range != 1))
-        return fs::fail("fs_frame_compose: range must be 0 (limited) or 1 (full), got %d in, %d out", full_range, out_full_range);
-    if (K < 1 || K > 256) return fs::fail("fs_frame_compose: palette must hold 1..256 classes, got %d", K);
-    if (h < 1 || w < 1) return fs::fail("fs_frame_compose: empty frame (%d x %d)", h, w);
-    if ((int64_t)h * w * 3 >= ((int64_t)1 << 31)) return fs::fail("fs_frame_compose: output too large (%d x %d x 3 bytes pass 2^31)", h, w);
-    if (out_format != 0 && (!out_u || (out_format == 2 && !out_v))) return fs::fail("fs_frame_compose: null output chroma pointer for a YUV format");
-    if (!frame) {
-        if (H != 0 || W != 0 || u || v) return fs::fail("fs_frame_compose: background geometry or chroma (%d x %d) without a background frame", H, W);
-    } else {
-        if (H < 1 || W < 1) return fs::fail("fs_frame_compose: a background frame without its geometry (%d x %d)", H, W);
-        if ((int64_t)H * W * 3 >= ((int64_t)1 << 31)) return fs::fail("fs_frame_compose: background too large (%d x %d x 3 bytes pass 2^31)", H, W);
-        if (format != 0 && (!u || (format == 2 && !v))) return fs::fail("fs_frame_compose: null background chroma pointer for a YUV format");
-    }
+    if (int rc = frame_compose_args("fs_frame_compose", mask, h, w, palette, K, frame, u, v, format, matrix, full_range, H, W, out, out_u, out_v, out_format,
+                                    out_matrix, out_full_range))
+        return rc;
     return fs::launch_frame_compose(mask, h, w, palette, K, frame, u, v, format, matrix, full_range, H, W, out, out_u, out_v, out_format, out_matrix,
                                     out_full_range, S(stream));
 }
+// region overlay (overlay_ops.hip): frame_compose's refusals, then the layers'; nothing is launched on a refusal
+static int fs_frame_compose_regions(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u, const uint8_t* v,
+                                    int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v, int out_format,
+                                    int out_matrix, int out_full_range, const int32_t* index, const int64_t* table, const int64_t* counts,
+                                    const int64_t* tracks, int max_regions, const uint8_t* fill_palette, int fill_colours, const uint8_t* outline,
+                                    int outline_width, int label_scale, int64_t label_min_area, uint32_t halo_rgba, uint32_t ink_rgb, void* workspace,
+                                    fs_stream stream) {
+    const char* what = "fs_frame_compose_regions";
+    if (int rc = frame_compose_args(what, mask, h, w, palette, K, frame, u, v, format, matrix, full_range, H, W, out, out_u, out_v, out_format, out_matrix,
+                                    out_full_range))
+        return rc;
+    if (!index) return fs::fail("%s: null index plane", what);
+    if (max_regions < 1 || max_regions > 65536) return fs::fail("%s: max_regions must be 1..65536, got %d", what, max_regions);
+    if (fill_colours < 0 || fill_colours > 256) return fs::fail("%s: the fill palette must hold 0..256 colours, got %d", what, fill_colours);
+    if (outline_width < 0 || outline_width > 4) return fs::fail("%s: outline_width must be 0..4, got %d", what, outline_width);
+    if (label_scale < 0 || label_scale > 4) return fs::fail("%s: label_scale must be 0..4, got %d", what, label_scale);
+    if (label_min_area < 1) return fs::fail("%s: label_min_area must be at least 1, got %lld", what, (long long)label_min_area);
+    if (fill_colours > 0 && !fill_palette) return fs::fail("%s: %d fill colours without a fill palette", what, fill_colours);
+    if (label_scale > 0 && (!table || !counts)) return fs::fail("%s: labels need the region table and its counts", what);
+    if (label_scale > 0 && !workspace) return fs::fail("%s: labels need the marks workspace", what);
+    if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return fs::fail("%s: the workspace is not aligned to 4 bytes", what);
+    return fs::launch_frame_compose_regions(mask, h, w, palette, K, frame, u, v, format, matrix, full_range, H, W, out, out_u, out_v, out_format, out_matrix,
+                                            out_full_range, index, reinterpret_cast<const long long*>(table), reinterpret_cast<const long long*>(counts),
+                                            reinterpret_cast<const long long*>(tracks), max_regions, fill_palette, fill_colours, outline, outline_width,
+                                            label_scale, label_min_area, halo_rgba, ink_rgb, workspace, S(stream));
+}
 
-FS_API const fs_test_api* fs_test_hooks(void) {
+// the six tables as one object: each table is built from the one before it, so there is one definition of every member list
+static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
     static const fs_hook_tables tables = {{
         sizeof(fs_test_api),
@@ -569,5 +605,16 @@ FS_API const fs_test_api* fs_test_hooks(void) {
         sizeof(fs_ext4_api),
         fs_outline_simplify,
     }};
+    // fs_ext4_api is frozen too (one member, 24 bytes); the sixth table lies behind it by the same pattern, and &all5.base4 is &all5.
+    static const fs_hook_tables5 all5 = {all4, {
+        FS_EXT5_MAGIC,
+        sizeof(fs_ext5_api),
+        fs_frame_compose_regions,
+    }};
+    return all5;
+}
+
+FS_API const fs_test_api* fs_test_hooks(void) {
+    const fs_hook_tables4& all4 = hook_tables().base4;  // the first five tables of the object; its address is the whole object's
     return &all4.base3.base2.base.test;
 }

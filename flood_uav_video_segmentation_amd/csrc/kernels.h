@@ -340,6 +340,14 @@ int launch_frame_prepare(const uint8_t* frame, const uint8_t* u, const uint8_t* 
 int launch_frame_compose(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u, const uint8_t* v,
                          int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v, int out_format,
                          int out_matrix, int out_full_range, hipStream_t s);
+// Region overlay (overlay_ops.hip; include/floodseg_test.h, frame_compose_regions): launch_frame_compose's arguments and picture, plus
+// the fill-by-id, outline and id-label layers drawn from region_table's index plane / table / counts and region_tracks' rows.  workspace:
+// the marks plane, FS_FRAME_COMPOSE_REGIONS_WORKSPACE_BYTES(h, w) bytes (labels only).  Arguments are validated by the caller.
+int launch_frame_compose_regions(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u, const uint8_t* v,
+                                 int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v, int out_format,
+                                 int out_matrix, int out_full_range, const int32_t* index, const long long* table, const long long* counts,
+                                 const long long* tracks, int max_regions, const uint8_t* fill_palette, int P, const uint8_t* outline, int outline_width,
+                                 int label_scale, long long label_min_area, uint32_t halo_rgba, uint32_t ink_rgb, void* workspace, hipStream_t s);
 // intersection / union / target histograms (util/util.py:52-63), int64[3][K] accumulated.
 int launch_iou_hist(const uint8_t* pred, const uint8_t* target, int64_t numel, int K, int ignore_index,
                     long long* hist3K, hipStream_t s);

@@ -26,6 +26,9 @@ FlowPredictor(..., regions=True, outlines=True, simplify=1.0) also simplifies ev
 (ops.outline_simplify):
     simple, counts = p.simple_outline_report()                             # per frame (rows, kept vertices); counts [frames, 4]
     write_outlines_geojson("o.geojson", ids, rows, (frames, flags), simplified=(simple, counts), tolerance=1.0)
+FlowPredictor(..., regions=True, track=True, keep_window_regions=True) keeps the newest window's index planes, tables and tracks on the
+device so that the result video can show them (ops.compose_regions):
+    frames = compose_window(masks, item, palette, dataset=ds, regions=p.window_regions(), style={"outline": rgba, "label_scale": 2})
 """
 import numpy as np
 import torch
@@ -92,14 +95,19 @@ class FlowPredictor:
     (ops.outline_simplify) -- into chunked device buffers of their own (32 max_contours + 8 max_vertices + 32 bytes per
     frame); the outline buffers stay as they are, and nothing is read back until simple_outline_report().  simplify_rounds (1..256)
     caps the rounds: a ring with segments still open after the last round keeps all their vertices and is flagged, and the report's
-    `rounds` column tells how many a frame needed.  The default of 32 is a guess for natural shorelines, NOT validated on real video."""
+    `rounds` column tells how many a frame needed.  The default of 32 is a guess for natural shorelines, NOT validated on real video.
+
+    keep_window_regions=True (extension, needs regions=True): the index planes, table rows, counts and -- with track=True -- track rows of
+    the MOST RECENT window stay reachable on the device through window_regions(), one tuple per frame, for ops.compose_regions /
+    compose_window(regions=) to draw outlines, track colours and ids into the result video.  Views of the report
+    buffers and the window's index tensor: no copy, nothing read back, valid until the next window."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
                  max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False, outlines=False, max_contours=4096,
-                 max_vertices=32768, simplify=None, simplify_rounds=32):
+                 max_vertices=32768, simplify=None, simplify_rounds=32, keep_window_regions=False):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -169,6 +177,10 @@ class FlowPredictor:
         self.simple_chunk = max(1, min(self.REPORT_CHUNK, ((64 << 20) - 1) // per_frame))  # frames per device buffer: below 64 MiB
         self._simple_chunks = []  # (simple, simple_vertices, simple_counts) device buffers of simple_chunk frames each, in frame order
         self._simple_frames = 0
+        if keep_window_regions and not regions:
+            raise ValueError("FlowPredictor: keep_window_regions=True needs regions=True (it keeps the region tables' index planes and rows)")
+        self.keep_window_regions = bool(keep_window_regions)
+        self._window_regions = None  # the most recent window's pieces: [(index [take,H,W], table, counts, tracks or None)], device views
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
@@ -262,6 +274,7 @@ class FlowPredictor:
         masks = masks.contiguous()
         labels = ops.mask_regions(masks, self.classes, self.connectivity)
         done, n = 0, masks.shape[0]
+        kept = []
         while done < n:
             row = self._region_frames % self.REPORT_CHUNK
             if row == 0:
@@ -276,8 +289,24 @@ class FlowPredictor:
             if self.track:
                 piece = None if link is None else (link[0][done:done + take], link[1], None if link[2] is None else link[2][done:done + take])
                 self._keep_tracks(got[2], table[row:row + take], counts[row:row + take], row, piece)
+            if self.keep_window_regions:
+                kept.append((got[2], table[row:row + take], counts[row:row + take], self._track_chunks[-1][0][row:row + take] if self.track else None))
             done += take
             self._region_frames += take
+        if self.keep_window_regions:
+            self._window_regions = kept
+
+    def window_regions(self):
+        """keep_window_regions=True: the most recent window's regions as a list of n per-frame tuples (index int32 [H,W], table int64
+        [max_regions,10], counts int64 [2], tracks int64 [max_regions,4] or None without track=True) -- what ops.compose_regions and
+        compose_window(regions=) draw from.  Device tensors and views of the report buffers, nothing read back; valid until the next
+        window is predicted.  The index planes are those of the masks the window handed out (the filtered ones under min_region_area)."""
+        if not self.keep_window_regions:
+            raise RuntimeError("FlowPredictor.window_regions: the predictor was not made with keep_window_regions=True")
+        if self._window_regions is None:
+            raise RuntimeError("FlowPredictor.window_regions: no window has been predicted yet")
+        return [(index[f], table[f], counts[f], None if tracks is None else tracks[f])
+                for index, table, counts, tracks in self._window_regions for f in range(index.shape[0])]
 
     def _keep_outlines(self, index):
         """The outlines of the index planes region_table just wrote into the next rows of their own chunked buffers (region_outlines
@@ -792,8 +821,11 @@ def colorize(masks_u8, palette=PALETTE):
     return out
 
 
+REGION_STYLE_KEYS = ("fill_palette", "outline", "outline_width", "label_scale", "label_min_area", "halo", "ink")  # ops.compose_regions' drawing options
+
+
 def compose_window(masks_u8, item_or_sources=None, palette=PALETTE, alpha=None, out_fmt="nv12", out_matrix="bt709", out_full_range=False,
-                   dataset=None):
+                   dataset=None, regions=None, style=None):
     """The result video frames of one window, composed on the device (ops.compose_frame, one launch per frame): yields, for
     masks_u8 [n,h,w], n flat uint8 buffers of ops.raw_frame_bytes(h, w, out_fmt) bytes each -- what RawVideoWriter.write takes, and
     what ops.frame_planes splits into the planes ops.prepare_frame reads.
@@ -801,7 +833,19 @@ def compose_window(masks_u8, item_or_sources=None, palette=PALETTE, alpha=None, 
     callable p -> entry, each a (frame, chroma, fmt, matrix, full_range) tuple as PredictWindows.source / RawVideoWindows.source
     return it (None: no overlay for that frame) -- the colours blended over the footage; or a window item together with
     `dataset=`, which stands for dataset.source(item["frame_id"] + p).  Sources are asked for one frame at a time, so the decoded
-    frames of a window need not be alive together.  palette / alpha: as ops.compose_frame ([K,3] + alpha, or [K,4])."""
+    frames of a window need not be alive together.  palette / alpha: as ops.compose_frame ([K,3] + alpha, or [K,4]).
+    regions: FlowPredictor.window_regions()'s list, one (index, table, counts, tracks) entry per mask (None: that frame without
+    layers) -- the frames are then composed by ops.compose_regions with the drawing options of `style`, a dict with keys among
+    REGION_STYLE_KEYS (fill_palette, outline, outline_width, label_scale, label_min_area, halo, ink).  regions=None: ops.compose_frame."""
+    if style is not None and regions is None:
+        raise RuntimeError("floodseg.compose_window: style= goes with regions= (the layers are drawn from the regions)")
+    if regions is not None:
+        style = dict(style or {})
+        unknown = sorted(set(style) - set(REGION_STYLE_KEYS))
+        if unknown:
+            raise RuntimeError(f"floodseg.compose_window: unknown style keys {unknown}; the drawing options are {list(REGION_STYLE_KEYS)}")
+        if len(regions) != masks_u8.shape[0]:
+            raise RuntimeError(f"floodseg.compose_window: {len(regions)} region entries for {masks_u8.shape[0]} masks")
     if isinstance(item_or_sources, dict):
         if dataset is None:
             raise RuntimeError("floodseg.compose_window: a window item needs dataset= to find its decoded frames")
@@ -820,7 +864,17 @@ def compose_window(masks_u8, item_or_sources=None, palette=PALETTE, alpha=None, 
     for p in range(masks_u8.shape[0]):
         src = source(p)
         out = torch.empty(ops.raw_frame_bytes(masks_u8.shape[1], masks_u8.shape[2], out_fmt), dtype=torch.uint8, device=masks_u8.device)
-        if src is None:
+        if regions is not None and regions[p] is not None:
+            index, table, counts, tracks = regions[p]
+            if src is None:
+                ops.compose_regions(masks_u8[p], palette, index, table, counts, tracks, out_fmt=out_fmt, out_matrix=out_matrix,
+                                    out_full_range=out_full_range, out=out, **style)
+            else:
+                frame, chroma, fmt, matrix, full_range = src
+                ops.compose_regions(masks_u8[p], palette, index, table, counts, tracks, background=frame, chroma=chroma, fmt=fmt, matrix=matrix,
+                                    full_range=full_range, out_fmt=out_fmt, out_matrix=out_matrix, out_full_range=out_full_range, out=out, alpha=alpha,
+                                    **style)
+        elif src is None:
             ops.compose_frame(masks_u8[p], palette, out_fmt=out_fmt, out_matrix=out_matrix, out_full_range=out_full_range, out=out)
         else:
             frame, chroma, fmt, matrix, full_range = src

@@ -1054,6 +1054,129 @@ def compose_frame(mask, palette, background=None, chroma=None, fmt="rgb24", matr
     return frame if out_fmt == "rgb24" else (frame, ochroma)
 
 
+
+# ------------------------------------------------------------------------------------------ region overlay
+# A default fill palette for track ids: 16 hues spaced round the colour wheel, alternating two lightness levels so that neighbouring
+# entries differ in both.  The choice is a guess -- nobody has tested it on viewers or on colour-blind ones; pass fill_palette= for another.
+TRACK_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230),
+                 (210, 245, 60), (250, 190, 212), (0, 128, 128), (220, 190, 255), (170, 110, 40), (255, 250, 200), (128, 0, 0), (170, 255, 195))
+_plain_palette_cache = {}  # (device, bytes, rows, columns) -> device tensor: the fill and outline palettes, cached as the class palette is
+
+
+def compose_regions_workspace_bytes(h, w):
+    """Bytes of compose_regions' marks plane (FS_FRAME_COMPOSE_REGIONS_WORKSPACE_BYTES in include/floodseg_test.h): h * w rounded up to 4."""
+    return (int(h) * int(w) + 3) // 4 * 4
+
+
+def _plain_palette(dev, palette, columns, name, max_rows):
+    import numpy as np
+
+    pal = palette.detach().cpu().numpy() if isinstance(palette, torch.Tensor) else np.asarray(palette)
+    if pal.ndim == 2 and pal.dtype != np.uint8 and pal.size and pal.min() >= 0 and pal.max() <= 255 and np.issubdtype(pal.dtype, np.integer):
+        pal = pal.astype(np.uint8)  # a tuple of tuples, as TRACK_PALETTE
+    if pal.dtype != np.uint8 or pal.ndim != 2 or pal.shape[1] != columns or not 1 <= pal.shape[0] <= max_rows:
+        raise RuntimeError(f"floodseg.compose_regions: {name} must be uint8 [1..{max_rows},{columns}], got {pal.dtype} {pal.shape}")
+    key = (dev, pal.tobytes(), pal.shape[0], columns)
+    t = _plain_palette_cache.get(key)
+    if t is None:
+        t = _plain_palette_cache[key] = torch.from_numpy(np.ascontiguousarray(pal)).to(dev)
+    return t
+
+
+def _packed_colour(value, n, name):
+    v = tuple(int(c) for c in value)
+    if len(v) != n or any(not 0 <= c <= 255 for c in v):
+        raise RuntimeError(f"floodseg.compose_regions: {name} must be {n} values 0..255, got {value!r}")
+    return sum(c << (8 * i) for i, c in enumerate(v))
+
+
+def compose_regions(mask, palette, index, table=None, counts=None, tracks=None, fill_palette=None, outline=None, outline_width=1, label_scale=0,
+                    label_min_area=256, halo=(0, 0, 0, 160), ink=(255, 255, 255), background=None, chroma=None, fmt="rgb24", matrix="bt601",
+                    full_range=False, out_fmt="nv12", out_matrix=None, out_full_range=None, out=None, alpha=None):
+    """compose_frame's picture with the regions drawn into it (definition: include/floodseg_test.h, frame_compose_regions), on the device,
+    nothing read back.  mask, palette, background .. alpha, the returns and the out= contract are compose_frame's.
+    index int32 [h,w], table int64 [R,10], counts int64 [2]: one frame of region_table's result; tracks int64 [R,4]: that frame of
+    region_tracks' result, or None -- a region's id is then its row.
+    fill_palette uint8 [P,3] (e.g. TRACK_PALETTE), P <= 256: every region with an id >= 0 takes colour id % P, with its class's opacity.
+    outline uint8 [K,4] (R, G, B, A per class; A = 0: none for that class) with outline_width 0..4: a line that wide along the inside
+    of every region's boundary.  label_scale 1..4: the id (mod 10^7) in a 5 x 7 font of that scale, on a `halo` (R, G, B, A) backdrop
+    in `ink` (R, G, B), centred on the region's centroid and clamped to the frame, for regions of at least label_min_area pixels;
+    needs table and counts.  The marks workspace is allocated here.  With no layer on this is compose_frame, byte for byte."""
+    what = "floodseg.compose_regions"
+    lib = _lib.load()
+    if fmt not in _FORMATS or out_fmt not in _FORMATS:
+        raise RuntimeError(f"{what}: fmt and out_fmt must be one of {sorted(_FORMATS)}, got {fmt!r} and {out_fmt!r}")
+    out_matrix = matrix if out_matrix is None else out_matrix
+    out_full_range = full_range if out_full_range is None else out_full_range
+    if matrix not in _MATRICES or out_matrix not in _MATRICES:
+        raise RuntimeError(f"{what}: matrix and out_matrix must be one of {sorted(_MATRICES)}, got {matrix!r} and {out_matrix!r}")
+    planes = [] if chroma is None else list(chroma) if isinstance(chroma, (tuple, list)) else [chroma]
+    dev = one_device(mask, index, table, counts, tracks, background, out, *planes, what=what)
+    if mask.dtype != torch.uint8 or mask.dim() != 2 or mask.numel() == 0:
+        raise RuntimeError(f"{what}: mask must be a non-empty uint8 [h,w] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    h, w = int(mask.shape[0]), int(mask.shape[1])
+    if index.dtype != torch.int32 or tuple(index.shape) != (h, w):
+        raise RuntimeError(f"{what}: index must be int32 of the mask's shape {(h, w)}, got {index.dtype} {tuple(index.shape)}")
+    T, scale, min_area = int(outline_width), int(label_scale), int(label_min_area)
+    if not 0 <= T <= 4 or not 0 <= scale <= 4 or not 1 <= min_area < 2 ** 63:
+        raise RuntimeError(f"{what}: outline_width and label_scale must be 0..4 and label_min_area at least 1, got {outline_width}, {label_scale} and "
+                           f"{label_min_area}")
+    cap = None
+    for t, cols, name in ((table, 10, "table"), (tracks, 4, "tracks")):
+        if t is None:
+            continue
+        if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != cols or not 1 <= t.shape[0] <= 65536 or (cap is not None and t.shape[0] != cap):
+            raise RuntimeError(f"{what}: {name} must be int64 [max_regions,{cols}] with 1 <= max_regions <= 65536"
+                               f"{'' if cap is None else f' = {cap}'}, got {t.dtype} {tuple(t.shape)}")
+        cap = int(t.shape[0])
+    if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (2,)):
+        raise RuntimeError(f"{what}: counts must be int64 [2] (one frame of region_table's counts), got {counts.dtype} {tuple(counts.shape)}")
+    if scale and (table is None or counts is None):
+        raise RuntimeError(f"{what}: labels (label_scale={scale}) need table= and counts=")
+    if cap is None:
+        cap = 65536  # neither table nor tracks: every non-negative index below the largest cap is a row
+    halo_word, ink_word = _packed_colour(halo, 4, "halo"), _packed_colour(ink, 3, "ink")
+    H = W = 0
+    if background is None:
+        if planes:
+            raise RuntimeError(f"{what}: chroma planes without a background frame")
+    else:
+        if background.dtype != torch.uint8 or any(p.dtype != torch.uint8 for p in planes):
+            raise RuntimeError(f"{what}: frames must be uint8, got {[str(t.dtype) for t in [background] + planes]}")
+        rgb = fmt == "rgb24"
+        if background.dim() != (3 if rgb else 2) or (rgb and background.shape[2] != 3) or background.numel() == 0:
+            raise RuntimeError(f"{what}: a {fmt} background must be {'[H,W,3]' if rgb else 'the Y plane [H,W]'}, got {tuple(background.shape)}")
+        H, W = int(background.shape[0]), int(background.shape[1])
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        want = [] if rgb else [(ch, cw, 2)] if fmt == "nv12" else [(ch, cw), (ch, cw)]
+        if [tuple(p.shape) for p in planes] != want:
+            raise RuntimeError(f"{what}: a {H} x {W} {fmt} background takes chroma {want if want else None}, got {[tuple(p.shape) for p in planes]}")
+    nbytes = raw_frame_bytes(h, w, out_fmt)
+    with torch.cuda.device(dev):
+        pal = _palette_rgba(dev, palette, alpha, background is None)
+        fill = _plain_palette(dev, fill_palette, 3, "fill_palette", 256) if fill_palette is not None else None
+        line = _plain_palette(dev, outline, 4, "outline", 256) if outline is not None else None
+        if line is not None and line.shape[0] != pal.shape[0]:
+            raise RuntimeError(f"{what}: outline must have one (R, G, B, A) row per class of the palette ({pal.shape[0]}), got {tuple(line.shape)}")
+        mask = mask.contiguous()
+        planes = [p.contiguous() for p in planes]
+        background = background.contiguous() if background is not None else None
+        if out is None:
+            out = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != nbytes or not out.is_contiguous():
+            raise RuntimeError(f"{what}: out must be a contiguous uint8 [{nbytes}] buffer (one {h} x {w} {out_fmt} frame), got {out.dtype} {tuple(out.shape)}")
+        frame, ochroma = frame_planes(out, h, w, out_fmt)
+        oplanes = [] if ochroma is None else list(ochroma) if isinstance(ochroma, tuple) else [ochroma]
+        work = torch.empty((compose_regions_workspace_bytes(h, w),), dtype=torch.uint8, device=dev) if scale else None
+        check(lib.fs_frame_compose_regions(
+            ptr(mask), h, w, ptr(pal), pal.shape[0], ptr(background), ptr(planes[0]) if planes else None, ptr(planes[1]) if len(planes) > 1 else None,
+            _FORMATS[fmt], _MATRICES[matrix], int(bool(full_range)), H, W, ptr(frame), ptr(oplanes[0]) if oplanes else None,
+            ptr(oplanes[1]) if len(oplanes) > 1 else None, _FORMATS[out_fmt], _MATRICES[out_matrix], int(bool(out_full_range)),
+            ptr(index.contiguous()), ptr(table.contiguous()) if table is not None else None, ptr(counts.contiguous()) if counts is not None else None,
+            ptr(tracks.contiguous()) if tracks is not None else None, cap, ptr(fill), fill.shape[0] if fill is not None else 0, ptr(line), T, scale, min_area,
+            halo_word, ink_word, ptr(work), stream_ptr()))
+    return frame if out_fmt == "rgb24" else (frame, ochroma)
+
 # ------------------------------------------------------------------------------------------ single-frame multi-scale test
 def ms_prepare(raw, new_hw, padded_hw, mean, std, flip=True):
     """One scale's network input from the raw 0-255 frame [3,H,W] (base/foundation.py:193-200, 267-273, 300-306): resized to

@@ -651,6 +651,73 @@ typedef struct fs_hook_tables4 {
     fs_ext4_api ext4;
 } fs_hook_tables4;
 
+/* ---- The SIXTH table.  fs_ext4_api is frozen as well (1 member, 24 bytes; tests/test_simplify_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables4 by the same pattern:
+ *     const fs_hook_tables5* t = (const fs_hook_tables5*)fs_test_hooks();   t->ext5.frame_compose_regions(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables4: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext5.magic == FS_EXT5_MAGIC and ext5.size >= the end of the member it needs. */
+#define FS_EXT5_MAGIC 0x4653455854414235ull /* "FSEXTAB5" */
+
+typedef struct fs_ext5_api {
+    uint64_t magic; /* FS_EXT5_MAGIC */
+    size_t size;    /* sizeof(fs_ext5_api) of the library that was built */
+
+    /* ---- Region overlay of frame egress (csrc/overlay_ops.hip, csrc/overlay_defs.h).  OUR DEFINITION: the reference
+     * writes class colours only.  frame_compose's picture plus three optional layers drawn from region_table's index plane and
+     * region_tracks' rows: a fill colour per id, an outline inside every region, the id as a label.  Integers throughout; every output
+     * byte is a function of the inputs alone, whatever order threads arrive in.  R = max_regions; // is floor division.
+     * Inputs: frame_compose's (mask .. out_full_range), which keep their meaning, refusals included, and on top:
+     *   index          int32 [h][w] as region_table writes it; a value outside 0 .. R - 1 counts as -1.  1 <= R <= 65536.
+     *   table          int64 [R][10], counts int64 [2]: region_table's, read only for labels; both may be NULL when label_scale == 0.
+     *   tracks         int64 [R][4] as region_tracks writes one frame, or NULL.  The ID of row r is tracks[r][0], without tracks r itself.
+     *   fill_palette   uint8 [fill_colours][3], 0 <= fill_colours = P <= 256; not read (NULL) when P == 0.
+     *   outline        uint8 [K][4] = (R, G, B, A) per class, or NULL: no outline.
+     *   outline_width  T, 0..4.      label_scale  s, 0..4.      label_min_area >= 1.
+     *   halo_rgba, ink_rgb   packed R | G << 8 | B << 16 (| A << 24): the label's backdrop with its opacity, and the digits' colour.
+     * Per output pixel p, per channel in int32, in this order:
+     *   1. class colour   c = mask < K ? mask : 0;  (R, G, B, A) = palette[c];  r = the pixel's row, or -1.
+     *   2. fill by id     if P >= 1, r >= 0 and id(r) >= 0: (R, G, B) = fill_palette[id(r) % P]; A stays the class's.
+     *   3. base           o = frame_compose's: (A * colour + (255 - A) * b + 127) / 255 over the resized source b, or the colour alone.
+     *   4. outline        drawn when T >= 1, r >= 0, outline is given, OA = outline[c].A > 0, and some pixel q INSIDE THE FRAME with
+     *                     max(|qx - px|, |qy - py|) <= T has a row different from r:  o = (OA * outline[c] + (255 - OA) * o + 127) / 255.
+     *                     Pixels outside the frame are not neighbours (the frame edge draws no line); pixels of row -1 are never drawn
+     *                     but bound their neighbours.  The line is T pixels wide and lies inside the region.
+     *   5. label          where the marks plane has the ink bit o = ink; where it has the halo bit alone, with HA = the halo's A,
+     *                     o = (HA * halo + (255 - HA) * o + 127) / 255.
+     * Then RGB24, NV12 or I420 exactly as frame_compose does it: chroma from the (sum + 2) >> 2 mean of the FINAL o of each 2 x 2 quad,
+     * with the same edge rule.
+     * LABELS.  Row r is LIVE when r < min(counts[1], R).  A live row gets a label when s >= 1, id(r) >= 0, area = table[r][1] >=
+     * label_min_area, and the box fits: w >= tw + 2 s and h >= th + 2 s.  The text is the decimal digits of id mod 10^7, most significant
+     * first, no leading zeros, nd of them;  tw = (6 nd - 1) s, th = 7 s;  cx = sum_x // area, cy = sum_y // area (columns 6, 7);
+     *   x0 = min(max(cx - tw // 2, s), w - tw - s),  y0 = min(max(cy - th // 2, s), h - th - s);
+     *   halo rectangle [x0 - s, x0 + tw + s) x [y0 - s, y0 + th + s)  (at most 172 x 36 pixels, always inside the frame);
+     *   ink at (x, y) of the text box [x0, x0 + tw) x [y0, y0 + th):  u = (x - x0) // s, v = (y - y0) // s, digit k = u // 6, column
+     *   col = u % 6:  ink exactly when col < 5 and bit 4 - col of FONT[digit k][v] is set.  FONT, rows top to bottom, bit 4 leftmost:
+     *     0: 0E 11 13 15 19 11 0E    1: 04 0C 04 04 04 04 0E    2: 0E 11 01 02 04 08 1F    3: 1F 02 04 02 01 11 0E    4: 02 06 0A 12 1F 02 02
+     *     5: 1F 10 1E 01 01 11 0E    6: 06 08 10 1E 11 11 0E    7: 1F 01 02 04 08 08 08    8: 0E 11 11 0E 11 11 0E    9: 0E 11 11 0F 01 02 0C
+     * MARKS.  workspace = one uint8 per pixel, FS_FRAME_COMPOSE_REGIONS_WORKSPACE_BYTES(h, w) bytes at a 4-byte aligned address, the
+     * caller's; NULL is allowed when s == 0, and the plane is then neither zeroed nor read.  With s >= 1 the call zeroes it on the
+     * stream, then one workgroup per row ORs bit 0 (inside some label's halo rectangle) and bit 1 (ink of some label) into it with
+     * 32-bit integer atomics; overlapping labels OR together, so ink beats halo whatever the order of arrival.  Nothing is allocated,
+     * synchronised or read on the host: a HIP-graph replay on new planes gives that replay's picture.
+     * Consequences: with P == 0, T == 0 (or outline == NULL) and s == 0 the output is frame_compose's, byte for byte (the call is handed
+     * to frame_compose's kernel); with index all -1 and no live row likewise, whatever the options.
+     * Refused before a launch: everything frame_compose refuses; a null index; R, P, T, s or label_min_area out of range; fill colours
+     * without a fill palette; s >= 1 without table, counts or workspace; a workspace not aligned to 4 bytes. */
+#define FS_FRAME_COMPOSE_REGIONS_WORKSPACE_BYTES(h, w) ((((size_t)(h) * (size_t)(w) + 3) / 4) * 4)
+    int (*frame_compose_regions)(const uint8_t* mask, int h, int w, const uint8_t* palette, int K, const uint8_t* frame, const uint8_t* u,
+                                 const uint8_t* v, int format, int matrix, int full_range, int H, int W, uint8_t* out, uint8_t* out_u, uint8_t* out_v,
+                                 int out_format, int out_matrix, int out_full_range, const int32_t* index, const int64_t* table, const int64_t* counts,
+                                 const int64_t* tracks, int max_regions, const uint8_t* fill_palette, int fill_colours, const uint8_t* outline,
+                                 int outline_width, int label_scale, int64_t label_min_area, uint32_t halo_rgba, uint32_t ink_rgb, void* workspace,
+                                 fs_stream stream);
+} fs_ext5_api;
+
+typedef struct fs_hook_tables5 {
+    fs_hook_tables4 base4;
+    fs_ext5_api ext5;
+} fs_hook_tables5;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

@@ -3,7 +3,7 @@
 All fp32, synthetic weights/frames, inputs resident in HBM, uint8 masks copied to the host each step.
 
     python tools/bench_configs.py                 # all rows
-    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions tracks outlines simplify cfg2 cfg3 vitb) -- the command that
+    python tools/bench_configs.py --only cfg2     # one config (cfg0 cfg1 cfg4 feat motion ingest cuts conf regions tracks outlines simplify overlay cfg2 cfg3 vitb) -- the command that
                                                   # `rocprofv3 --kernel-trace --stats` wraps for profiles/r02_cfg*_kernel_stats.csv
 """
 import argparse
@@ -67,7 +67,7 @@ def _stream():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | tracks | outlines | simplify | cfg2 | cfg3 | vitb")
+    ap.add_argument("--only", default="", help="cfg0 | cfg1 | cfg4 | feat | crops | crops_cached | ms1 | ms6 | motion | ingest | cuts | conf | regions | tracks | outlines | simplify | overlay | cfg2 | cfg3 | vitb")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="hip_no_split_bf16 | hip_no_winograd | hip_winograd_tile=4 | ... (repeatable; model/hipnet.py::HIP_OPTIONS)")
     ap.add_argument("--lib", default=None, help="development A/B: load this build of the library instead of the in-tree one")
@@ -460,6 +460,71 @@ def main():
                 rows.append((f"seg_tail {hh}x{ww} warp + regions, max_regions {cap}", 1 / t_reg, t_reg * 1e3))
                 rows.append((f"  + outlines, max_contours {mc}, max_vertices {mv} ({note}): {(t_out / t_reg - 1) * 100:+.2f} % ({(t_out - t_reg) * 1e3:+.3f} ms)",
                              1 / t_out, t_out * 1e3))
+    if want("overlay"):
+        # region overlay (ops.compose_regions, csrc/overlay_ops.hip) against ops.compose_frame on the same mask, NV12 background (at the
+        # frame's size) and NV12 output, at the two geometries, on the blob-like masks of the regions section (the argmax of smooth random
+        # logits; at the default cap of 1024 rows, which holds the regions of the frame's top only, and at 32768, which holds all; ids = a
+        # permutation of the rows): outlines alone at T = 1 and T = 4, fill alone, all three layers.  Two
+        # figures per variant, alternating with compose_frame in one process, every loop >= 0.5 s, the fastest of three: the call as a
+        # caller makes it (host work included: these kernels take microseconds) and the device time per call, from a captured graph of 50
+        # calls replayed.  Beside each: the bytes the variant must move at least -- mask 1 B, index 4 B, background 1.5 B in, frame 1.5 B
+        # out per pixel, and with labels the marks plane zeroed and read (2 B) -- and that floor over the device time.
+        import numpy as np
+
+        from flood_uav_video_segmentation_amd.flow.predict import PALETTE
+
+        gen = torch.Generator().manual_seed(2100)
+
+        def timed(fn):
+            t = timeit(fn, steps=20, warmup=5)
+            return timeit(fn, steps=max(20, int(0.6 / t) + 1), warmup=0)
+
+        def graphed(fn, calls=50):
+            fn(0)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for i in range(calls):
+                    fn(i)
+            return (lambda i: g.replay()), calls
+
+        for (hh, ww), cap in (((713, 713), 1024), ((713, 713), 32768), ((1072, 1920), 1024), ((1072, 1920), 32768)):
+            low = torch.randn((1, 5, (hh - 1) // 8 + 1, (ww - 1) // 8 + 1), generator=torch.Generator().manual_seed(2100 + hh)).to(dev)
+            mask = ops.mask_confidence(low, (hh, ww))[0]
+            table, counts, index = ops.region_table(mask, ops.mask_regions(mask, 5, 8), 5, None, 128, cap)
+            tracks = torch.full((cap, 4), -1, dtype=torch.int64)
+            tracks[:, 0] = torch.randperm(cap, generator=gen)
+            tracks = tracks.to(dev)
+            y = torch.randint(0, 256, (hh, ww), generator=gen, dtype=torch.uint8).to(dev)
+            uv = torch.randint(0, 256, ((hh + 1) // 2, (ww + 1) // 2, 2), generator=gen, dtype=torch.uint8).to(dev)
+            pal = np.concatenate([np.asarray(PALETTE, np.uint8), np.full((5, 1), 128, np.uint8)], axis=1)
+            line = np.full((5, 4), 255, np.uint8)
+            fill = np.asarray(ops.TRACK_PALETTE, np.uint8)
+            out = torch.empty(ops.raw_frame_bytes(hh, ww, "nv12"), dtype=torch.uint8, device=dev)
+            m0, i0, t0, c0 = mask[0], index[0], table[0], counts[0]
+            px = hh * ww
+            base_floor = px * (1 + 1.5 + 1.5)
+
+            def plain(i):
+                ops.compose_frame(m0, pal, y, uv, "nv12", "bt709", False, "nv12", out=out)
+
+            variants = (("outline T 1", dict(outline=line, outline_width=1), 4), ("outline T 4", dict(outline=line, outline_width=4), 4),
+                        ("fill", dict(fill_palette=fill, outline_width=0), 4),
+                        ("outline T 2 + fill + ids x2", dict(outline=line, outline_width=2, fill_palette=fill, label_scale=2, label_min_area=256), 6))
+            rows.append((f"overlay {hh}x{ww}, NV12 in and out: regions {counts[0].tolist()} of {cap}", 0.0, 0.0))
+            gp, calls = graphed(plain)
+            for name, style, extra in variants:
+                def layered(i, style=style):
+                    ops.compose_regions(m0, pal, i0, t0, c0, tracks, background=y, chroma=uv, fmt="nv12", matrix="bt709", full_range=False,
+                                        out_fmt="nv12", out=out, **style)
+                gl, _ = graphed(layered)
+                alt = [(timed(plain), timed(layered), timed(gp) / calls, timed(gl) / calls) for _ in range(3)]
+                t_old, t_new, d_old, d_new = (min(x[j] for x in alt) for j in range(4))
+                floor = base_floor + extra * px
+                rows.append((f"  compose_frame, call {t_old * 1e6:.1f} us; device {d_old * 1e6:.2f} us, floor {base_floor / 1e6:.1f} MB, "
+                             f"{base_floor / d_old / 1e12:.2f} TB/s", 1 / d_old, d_old * 1e3))
+                rows.append((f"  compose_regions {name}, call {t_new * 1e6:.1f} us; device {d_new * 1e6:.2f} us ({d_new / d_old:.2f} x, floors "
+                             f"{floor / base_floor:.2f} x), floor {floor / 1e6:.1f} MB, {floor / d_new / 1e12:.2f} TB/s", 1 / d_new, d_new * 1e3))
     if want("simplify"):
         # outline simplification (ops.outline_simplify, csrc/simplify_ops.hip): the four scenes of the outlines section (same seeds, same
         # caps), outlined once; then per call of N frames the outlines alone and the simplification alone at 1 px and the default 32

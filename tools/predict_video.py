@@ -54,6 +54,13 @@ vertex lies within PX pixels of the ring that is written, and every feature gain
 `--simplify-rounds N` (1..256, default 32) caps the rounds: a frame in which some ring still had open segments after N rounds gets a
 warning (those segments keep all their vertices), and the largest number of rounds a frame needed is printed at the end -- the figure
 to set N by.  The default is a guess for natural shorelines, not validated on real video.
+`--draw-outlines [W]`, `--draw-tracks`, `--draw-ids [SCALE]` (an extension; all need `--raw-out` and `--regions`) draw the
+regions into the result video on the device (ops.compose_regions instead of ops.compose_frame): a white line W pixels wide (0..4,
+default 1) along the inside of every region's boundary (none for class 0 under `--overlay-keep-class0`); with `--tracks`, every region
+filled in a colour picked by its track id (ops.TRACK_PALETTE, with the class's opacity under `--overlay`) and / or labelled with its
+track id (mod 10^7) in a 5 x 7 font scaled by SCALE (1..4, default 2) at its centroid -- the number in the track column of the regions
+CSV and in the GeoJSON features.  `--label-min-area N` (default 256) leaves regions below N pixels without a label.  Colours, widths and
+the area bound are guesses, not validated on real video.  The PNG route (`--out`) is unchanged.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -169,7 +176,26 @@ def parse_args(argv=None):
                     "all vertices of the segments still open and get a warning.  The default is a guess, not validated on real video")
     ap.add_argument("--compensate", action="store_true", help="--tracks with estimated grids: compare each frame with the frame before it read at "
                     "the source of every pixel under the block matcher's vectors, so that a small region that moves fast keeps its track")
+    ap.add_argument("--draw-outlines", type=int, nargs="?", const=1, default=None, metavar="W", help="--raw-out with --regions: draw a white line W "
+                    "pixels wide (0..4, default 1) along the inside of every region's boundary")
+    ap.add_argument("--draw-tracks", action="store_true", help="--raw-out with --regions and --tracks: fill every region in a colour picked by its track id")
+    ap.add_argument("--draw-ids", type=int, nargs="?", const=2, default=None, metavar="SCALE", help="--raw-out with --regions and --tracks: print every "
+                    "region's track id at its centroid, in a 5 x 7 font scaled by SCALE (1..4, default 2)")
+    ap.add_argument("--label-min-area", type=int, default=None, metavar="N", help="--draw-ids: regions below N pixels get no label (default 256)")
     args = ap.parse_args(argv)
+    for given, name in ((args.draw_outlines is not None, "--draw-outlines"), (args.draw_tracks, "--draw-tracks"), (args.draw_ids is not None, "--draw-ids")):
+        if given and not (args.raw_out and args.regions):
+            ap.error(f"{name} needs --raw-out and --regions")
+        if given and name != "--draw-outlines" and not args.tracks:
+            ap.error(f"{name} needs --tracks")
+    if args.draw_outlines is not None and not 0 <= args.draw_outlines <= 4:
+        ap.error("--draw-outlines takes a width of 0..4 pixels")
+    if args.draw_ids is not None and not 1 <= args.draw_ids <= 4:
+        ap.error("--draw-ids takes a scale of 1..4")
+    if args.label_min_area is not None and args.draw_ids is None:
+        ap.error("--label-min-area needs --draw-ids")
+    if args.label_min_area is not None and args.label_min_area < 1:
+        ap.error("--label-min-area takes N >= 1")
     if args.tracks and not args.regions:
         ap.error("--tracks needs --regions")
     if args.outlines and not args.regions:
@@ -246,12 +272,13 @@ def main():
     fm = FlowModel(net, feature_based=args.feature_based, no_warp=args.no_warp).eval()
     if args.tracks and world > 1:
         raise SystemExit("--tracks: track ids are per predictor and joining the ranks' blocks is out of scope: run it in a single process")
+    draw = args.draw_outlines is not None or args.draw_tracks or args.draw_ids is not None
     pred = FlowPredictor(fm, classes=args.classes, out_size=tuple(args.size), crop=None if args.no_cropping else tuple(args.crop),
                          compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache, confidence=args.confidence,
                          low_confidence=args.low_confidence, regions=bool(args.regions), min_region_area=args.min_region,
                          connectivity=args.connectivity, max_regions=args.max_regions, track=bool(args.tracks), min_overlap=args.min_overlap,
                          max_pairs=args.max_pairs, compensate=args.compensate, outlines=bool(args.outlines), max_contours=args.max_contours,
-                         max_vertices=args.max_vertices, simplify=args.simplify, simplify_rounds=args.simplify_rounds)
+                         max_vertices=args.max_vertices, simplify=args.simplify, simplify_rounds=args.simplify_rounds, keep_window_regions=draw)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
@@ -281,6 +308,18 @@ def main():
             ff = {"nv12": "nv12", "i420": "yuv420p", "rgb24": "rgb24"}[args.out_pix_fmt]
             print(f"encode with: ffmpeg -f rawvideo -pix_fmt {ff} -s {w}x{h} -r 25 -i {args.raw_out} result.mp4"
                   + ("" if args.out_pix_fmt == "rgb24" else f"   ({args.out_matrix}, {'full' if args.out_full_range else 'limited'} range)"), file=sys.stderr)
+    style = None
+    if draw:  # the drawing options of ops.compose_regions
+        style = {"outline_width": 0}
+        if args.draw_outlines:
+            line = np.full((len(palette), 4), 255, dtype=np.uint8)   # white, opaque; a guess
+            if args.overlay_keep_class0:
+                line[0, 3] = 0
+            style.update(outline=line, outline_width=args.draw_outlines)
+        if args.draw_tracks:
+            style["fill_palette"] = np.asarray(ops.TRACK_PALETTE, dtype=np.uint8)
+        if args.draw_ids is not None:
+            style.update(label_scale=args.draw_ids, label_min_area=256 if args.label_min_area is None else args.label_min_area)
     conf_writer = None
     if args.conf_out:
         conf_writer = RawVideoWriter(args.conf_out, args.size[0], args.size[1], "gray", frames=len(ds) * args.frame_delta, world=world)
@@ -318,7 +357,8 @@ def main():
         if writer is not None:
             frames_of = (lambda p: ds.source(item["frame_id"] + p)) if args.overlay is not None else None
             for p, buf in enumerate(compose_window(masks, frames_of, pal, out_fmt=args.out_pix_fmt, out_matrix=args.out_matrix,
-                                                   out_full_range=args.out_full_range)):
+                                                   out_full_range=args.out_full_range, regions=pred.window_regions() if draw else None,
+                                                   style=style)):
                 writer.write(item["frame_id"] + p, buf)
         if args.out:
             from PIL import Image
