@@ -193,7 +193,7 @@ def seg_tail(lo_prev, lo_next, grids_left, grids_right, n, out_hw, no_warp, want
         keep = []
         if lo_next is not None:
             lo_next = _f32c(lo_next, "lo_next")
-            if not no_warp:
+            if not no_warp and n > 1:  # n == 1: no grids, every frame a key frame -- the one map of lo_prev (the frame loop is empty)
                 if len(grids_left) != n - 1 or len(grids_right) != n - 1:
                     raise RuntimeError("floodseg.seg_tail: need n-1 grids per direction")
                 keep = [_f32c(g, "grid") for g in grids]
@@ -287,7 +287,7 @@ def seg_tail_accumulate(lo_prev, lo_next, grids_left, grids_right, n, crop_hw, n
         keep = []
         if lo_next is not None:
             lo_next = _f32c(lo_next, "lo_next")
-            if not no_warp:
+            if not no_warp and n > 1:  # as seg_tail: a window of one frame has no grids
                 if len(grids_left) != n - 1 or len(grids_right) != n - 1:
                     raise RuntimeError("floodseg.seg_tail_accumulate: need n-1 grids per direction")
                 keep = [_f32c(g, "grid") for g in grids]

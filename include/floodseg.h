@@ -160,7 +160,9 @@ int fs_blend(const float* a, float wa, const float* b, float wb, float* out, int
 /* Fused tail of FlowModel.predict_segmentation (flow/model.py:184-241) from the two low-resolution
  * decoder outputs: upsample, (optional) warp chains at grid resolution, linear fusion, and optionally
  * the per-frame argmax.  grids_left/right: host arrays of n-1 device pointers [Hg,Wg,2] (ignored when
- * no_warp).  scratch: >= 2*(n-1)*K*Hg*Wg floats (warp mode).  lo_next may be NULL (single frame). */
+ * no_warp).  scratch: >= 2*(n-1)*K*Hg*Wg floats (warp mode).  lo_next may be NULL (single frame).
+ * Writes n frames ([n,K,H,W] logits, [n,H,W] masks), one when lo_next is NULL.  n == 1 with both key
+ * frames is a window of one frame: the one map of lo_prev, no grids, no scratch; lo_next does not enter it. */
 int fs_seg_tail(const float* lo_prev, const float* lo_next, const float* const* grids_left,
                 const float* const* grids_right, int K, int h, int w, int Hg, int Wg, int H, int W, int n, int no_warp,
                 float* out_logits, uint8_t* out_mask, float* scratch, fs_stream stream);
