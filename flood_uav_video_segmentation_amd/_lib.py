@@ -180,6 +180,12 @@ _EXT5_HOOKS = [
 ]
 EXT5_MAGIC = 0x4653455854414235  # FS_EXT5_MAGIC
 
+# members of fs_ext6_api, the seventh table (append-only, behind the six frozen ones), in declaration order after `magic` and `size`
+_EXT6_HOOKS = [
+    ("mask_stabilize", c_int, [c_void] * 4 + [c_int] * 9 + [c_void] * 5),
+]
+EXT6_MAGIC = 0x4653455854414236  # FS_EXT6_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
@@ -225,6 +231,14 @@ class FsHookTables5(ctypes.Structure):
     _fields_ = [("base4", FsHookTables4), ("ext5", FsExt5Api)]
 
 
+class FsExt6Api(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT6_HOOKS]
+
+
+class FsHookTables6(ctypes.Structure):
+    _fields_ = [("base5", FsHookTables5), ("ext6", FsExt6Api)]
+
+
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
     fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
@@ -237,8 +251,29 @@ class _Library:
         self._ext3 = None
         self._ext4 = None
         self._ext5 = None
+        self._ext6 = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT6_HOOKS):
+            if self._ext6 is None:
+                all5 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables5)).contents
+                all2 = all5.base4.base3.base2
+                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
+                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
+                        or all5.base4.base3.ext3.magic != EXT3_MAGIC or all5.base4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
+                        or all5.base4.ext4.magic != EXT4_MAGIC or all5.base4.ext4.size != ctypes.sizeof(FsExt4Api)
+                        or all5.ext5.magic != EXT5_MAGIC or all5.ext5.size != ctypes.sizeof(FsExt5Api)):
+                    raise RuntimeError(f"floodseg: the library's first six hook tables are not the ones this binding knows ({name} is missing)")
+                ext6 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables6)).contents.ext6
+                if ext6.magic != EXT6_MAGIC:
+                    raise RuntimeError(f"floodseg: the library has no sixth extension table ({name} is missing)")
+                self._ext6 = ext6
+            member = getattr(FsExt6Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
+            if self._ext6.size < member.offset + member.size:
+                raise RuntimeError(f"floodseg: the library's sixth extension table is older than this binding ({name} is missing)")
+            fn = getattr(self._ext6, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT5_HOOKS):
             if self._ext5 is None:
                 all4 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables4)).contents
@@ -384,6 +419,11 @@ def ext4_hook_names():
 def ext5_hook_names():
     """Members of fs_ext5_api after `magic` and `size`, in declaration order."""
     return [h[0] for h in _EXT5_HOOKS]
+
+
+def ext6_hook_names():
+    """Members of fs_ext6_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT6_HOOKS]
 
 
 def check(rc):

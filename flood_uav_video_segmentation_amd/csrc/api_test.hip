@@ -523,8 +523,16 @@ static int fs_frame_compose_regions(const uint8_t* mask, int h, int w, const uin
                                             reinterpret_cast<const long long*>(tracks), max_regions, fill_palette, fill_colours, outline, outline_width,
                                             label_scale, label_min_area, halo_rgba, ink_rgb, workspace, S(stream));
 }
+// temporal mask stabiliser (stabilize_ops.hip): the launcher validates, nothing is launched on a refusal
+static int fs_mask_stabilize(const uint8_t* mask, const uint8_t* confidence, const int32_t* mv, const int32_t* pair_stats, int n, int H, int W, int frame_h,
+                             int frame_w, int K, int persist, int trust, int has_state, uint32_t* state, uint8_t* out, int64_t* counts, void* workspace,
+                             fs_stream stream) {
+    return fs::launch_mask_stabilize(mask, confidence, mv, pair_stats, n, H, W, frame_h, frame_w, K, persist, trust, has_state, state, out,
+                                     reinterpret_cast<long long*>(counts), workspace, S(stream));
+}
 
-// the six tables as one object: each table is built from the one before it, so there is one definition of every member list
+// the seven tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
     static const fs_hook_tables tables = {{
@@ -611,7 +619,13 @@ static const fs_hook_tables5& hook_tables(void) {
         sizeof(fs_ext5_api),
         fs_frame_compose_regions,
     }};
-    return all5;
+    // fs_ext5_api is frozen too (one member, 24 bytes); the seventh table lies behind it by the same pattern, and &all6.base5 is &all6.
+    static const fs_hook_tables6 all6 = {all5, {
+        FS_EXT6_MAGIC,
+        sizeof(fs_ext6_api),
+        fs_mask_stabilize,
+    }};
+    return all6.base5;
 }
 
 FS_API const fs_test_api* fs_test_hooks(void) {

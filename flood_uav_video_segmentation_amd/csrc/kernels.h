@@ -380,6 +380,12 @@ int launch_region_links_mc(const int* index, const long long* table, const long 
 int launch_region_tracks(const int* back, const int* fwd, const long long* counts, const long long* prev_tracks, int n, int max_regions,
                          long long* state, long long* tracks, hipStream_t s);
 
+// Temporal mask stabiliser (stabilize_ops.hip, stabilize_defs.h; definition: include/floodseg_test.h, mask_stabilize).  The launcher
+// refuses bad arguments before it launches anything.  conf, mv, pair_stats and (without mv) workspace may be nullptr; has_state 0: the
+// state plane is written only.  workspace: FS_MASK_STABILIZE_WORKSPACE_BYTES with mv.
+int launch_mask_stabilize(const uint8_t* mask, const uint8_t* conf, const int* mv, const int* pair_stats, int n, int H, int W, int frame_h, int frame_w,
+                          int K, int persist, int trust, int has_state, uint32_t* state, uint8_t* out, long long* counts, void* workspace, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

@@ -29,6 +29,10 @@ FlowPredictor(..., regions=True, outlines=True, simplify=1.0) also simplifies ev
 FlowPredictor(..., regions=True, track=True, keep_window_regions=True) keeps the newest window's index planes, tables and tracks on the
 device so that the result video can show them (ops.compose_regions):
     frames = compose_window(masks, item, palette, dataset=ds, regions=p.window_regions(), style={"outline": rgba, "label_scale": 2})
+FlowPredictor(..., stabilize=3) debounces every pixel's class along the time axis before anything else sees the masks: a class is emitted
+once it has been observed 3 frames running (ops.mask_stabilize), optionally read along the block matcher's vectors
+(stabilize_compensate=True) and with confident observations taken at once (stabilize_trust=T with confidence=True):
+    p.stabilize_report()                                                   # int64 [frames, 4] = (held, switched, seeded, trusted)
 """
 import numpy as np
 import torch
@@ -100,14 +104,29 @@ class FlowPredictor:
     keep_window_regions=True (extension, needs regions=True): the index planes, table rows, counts and -- with track=True -- track rows of
     the MOST RECENT window stay reachable on the device through window_regions(), one tuple per frame, for ops.compose_regions /
     compose_window(regions=) to draw outlines, track colours and ids into the result video.  Views of the report
-    buffers and the window's index tensor: no copy, nothing read back, valid until the next window."""
+    buffers and the window's index tensor: no copy, nothing read back, valid until the next window.
+
+    stabilize=N (extension; None, 0 or 1: off, and the op is never called): every window's masks go through ops.mask_stabilize with
+    persist=N FIRST -- a pixel keeps its emitted class until another class has been observed N frames running, so a change that lasts is
+    emitted N - 1 frames late and a flicker shorter than N frames never shows -- and what is despeckled, scored (temporal_consistency()
+    included), tabulated, reported and returned are the stabilised masks.  The state plane (4 B per pixel) lives on the device across
+    windows: reset() drops it, so the next frame seeds; clear_report() keeps it and drops the counts.  The per-frame counts (held,
+    switched, seeded, trusted) go into chunked device buffers and are read back once by stabilize_report().  The confidence plane stays
+    as computed: a held pixel keeps the confidence of the class it was OBSERVED as (the despeckle's rule).  Mask ids >= classes pass
+    through.  stabilize_trust=T (0..256, needs confidence=True): an observation with confidence >= T is emitted at once.
+    stabilize_compensate=True: the state is read at every pixel's source under the block matcher's vectors -- every window must then
+    come with link_mvs and link_frame_size (and optionally link_stats: a frame flagged as a scene cut seeds), exactly what compensate=True
+    takes; a window without them raises, there is no silent in-place fall-back.  Without it a moving scene is compared in place, where
+    the filter lags behind the motion and can make the masks worse.  Under a sharded run every rank's block starts unseeded.  No default
+    here has been validated on real video."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
                  max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False, outlines=False, max_contours=4096,
-                 max_vertices=32768, simplify=None, simplify_rounds=32, keep_window_regions=False):
+                 max_vertices=32768, simplify=None, simplify_rounds=32, keep_window_regions=False, stabilize=None, stabilize_trust=None,
+                 stabilize_compensate=False):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -181,6 +200,21 @@ class FlowPredictor:
             raise ValueError("FlowPredictor: keep_window_regions=True needs regions=True (it keeps the region tables' index planes and rows)")
         self.keep_window_regions = bool(keep_window_regions)
         self._window_regions = None  # the most recent window's pieces: [(index [take,H,W], table, counts, tracks or None)], device views
+        persist = 0 if stabilize is None else int(stabilize)
+        if not 0 <= persist <= 255:
+            raise ValueError(f"FlowPredictor: stabilize must be 0..255 frames (None, 0 or 1: off), got {stabilize}")
+        if persist <= 1 and (stabilize_trust is not None or stabilize_compensate):
+            raise ValueError("FlowPredictor: stabilize_trust and stabilize_compensate need stabilize=N with N >= 2")
+        if stabilize_trust is not None and not self.confidence:
+            raise ValueError("FlowPredictor: stabilize_trust needs confidence=True (it compares the confidence plane with the threshold)")
+        if stabilize_trust is not None and not 0 <= int(stabilize_trust) <= 256:
+            raise ValueError(f"FlowPredictor: stabilize_trust must be 0..256, got {stabilize_trust}")
+        self.stabilize = persist if persist > 1 else 0
+        self.stabilize_trust = None if stabilize_trust is None else int(stabilize_trust)
+        self.stabilize_compensate = bool(stabilize_compensate)
+        self._stabilize_state = None   # the state plane int32 [H, W] on the device, carried from window to window
+        self._stabilize_chunks = []    # int64 [REPORT_CHUNK, 4] device buffers of the per-frame counts, in frame order
+        self._stabilize_frames = 0
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
@@ -190,6 +224,7 @@ class FlowPredictor:
             self.key_cache.clear()
         self.last_output = None
         self._track_prev = None  # the next frame's regions are all born; the next track id is kept
+        self._stabilize_state = None  # the next frame seeds
 
     def clear_report(self):
         """Forget the extent report and the region report of the frames predicted so far."""
@@ -203,6 +238,8 @@ class FlowPredictor:
         self._outline_frames = 0
         self._simple_chunks = []
         self._simple_frames = 0
+        self._stabilize_chunks = []  # the state plane stays
+        self._stabilize_frames = 0
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -257,10 +294,42 @@ class FlowPredictor:
         self._despeckle_counts.append(counts)
         return ops.region_filter(masks, index, table, self.classes, self.min_region_area)
 
+    def _stabilize(self, masks, conf, link):
+        """The window's masks through the debounce, the state plane carried on, the counts into the next rows of the chunked buffers
+        (nothing is read back)."""
+        kw = {} if not self.stabilize_compensate else dict(mv=link[0], frame_size=link[1], pair_stats=link[2])
+        out, self._stabilize_state, counts = ops.mask_stabilize(masks.contiguous(), self._stabilize_state, conf if self.stabilize_trust is not None else None,
+                                                                self.classes, self.stabilize, self.stabilize_trust, **kw)
+        done, n = 0, out.shape[0]
+        while done < n:
+            row = self._stabilize_frames % self.REPORT_CHUNK
+            if row == 0:
+                self._stabilize_chunks.append(torch.zeros((self.REPORT_CHUNK, 4), dtype=torch.int64, device=out.device))
+            take = min(n - done, self.REPORT_CHUNK - row)
+            self._stabilize_chunks[-1][row:row + take].copy_(counts[done:done + take])
+            done += take
+            self._stabilize_frames += take
+        return out
+
+    def stabilize_report(self):
+        """stabilize=N: int64 numpy [frames, 4] = (held, switched, seeded, trusted) pixels of every frame predicted since the start (or
+        clear_report()), in the order the windows were predicted.  ONE read-back, here."""
+        if not self._stabilize_chunks:
+            return np.zeros((0, 4), dtype=np.int64)
+        return torch.cat(self._stabilize_chunks)[:self._stabilize_frames].cpu().numpy()
+
+    def _track_link(self, link):
+        """What _link_inputs returned, for the tracks: theirs only under compensate=True (stabilize_compensate=True alone leaves them in place)."""
+        return link if self.compensate else None
+
     def _link_inputs(self, n, link_mvs, link_frame_size, link_stats):
-        """compensate=True: the window's (mvs [n, blocks, 7], frame size, stats [n, 4] or None), checked; None otherwise."""
-        if not self.compensate:
+        """compensate=True or stabilize_compensate=True: the window's (mvs [n, blocks, 7], frame size, stats [n, 4] or None), checked;
+        None otherwise."""
+        if not self.compensate and not self.stabilize_compensate:
             return None
+        if (link_mvs is None or link_frame_size is None) and not self.compensate:
+            raise ValueError("FlowPredictor: stabilize_compensate=True needs link_mvs and link_frame_size with every window (an estimate-mode dataset "
+                             "with link_vectors=True provides them); the state is never read in place instead")
         if link_mvs is None or link_frame_size is None:
             raise ValueError("FlowPredictor: compensate=True needs link_mvs and link_frame_size with every window (an estimate-mode dataset with "
                              "link_vectors=True provides them); the links are never compared in place instead")
@@ -426,12 +495,15 @@ class FlowPredictor:
         return (rows, flags & 1, (flags >> 1) & 1) if with_cuts else (rows, flags & 1)
 
     def _finish(self, masks, conf, n, to_host, link=None):
-        """Despeckle, score, keep the reports, and hand out what the caller asked for: masks, or (masks, conf) with confidence=True."""
+        """Stabilise, despeckle, score, keep the reports, and hand out what the caller asked for: masks, or (masks, conf) with
+        confidence=True."""
+        if self.stabilize:
+            masks = self._stabilize(masks, conf, link)
         if self.min_region_area > 1:
             masks = self._despeckle(masks)
         self._score(masks, n)
         if self.regions:
-            self._keep_regions(masks, conf, link)
+            self._keep_regions(masks, conf, self._track_link(link))
         if not self.confidence:
             return masks.cpu().numpy() if to_host else masks            # :277
         self._keep_report(masks, conf)

@@ -733,6 +733,74 @@ def region_tracks(back, fwd, counts, state, prev_tracks=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ temporal mask stabiliser
+def mask_stabilize_workspace_bytes(n, h, w, hb=0, wb=0):
+    """FS_MASK_STABILIZE_WORKSPACE_BYTES of include/floodseg_test.h: 0 in place (hb = wb = 0); with mv the second state plane (4 B per
+    pixel, rounded up to 16) and hb * wb + 1 dwords per frame."""
+    if hb * wb == 0:
+        return 0
+    return (h * w + 3) // 4 * 16 + (n * (hb * wb + 1) + 3) // 4 * 16
+
+
+def mask_stabilize(mask, state=None, conf=None, classes=5, persist=3, trust=None, mv=None, frame_size=None, pair_stats=None, out=None):
+    """Causal per-pixel class debounce along the time axis (definition: include/floodseg_test.h, mask_stabilize):
+    uint8 masks [n,H,W] -> (out uint8 [n,H,W], state uint32-as-int32 [H,W], counts int64 [n,4] = (held, switched, seeded, trusted)).
+    A pixel keeps its emitted class until another class has been observed `persist` frames running (persist=1: out == mask), or at
+    once where conf (uint8 [n,H,W]) >= trust (0..256; None: nothing is trusted outright).  Ids >= classes pass through and end the
+    pixel's history.  state: the int32 [H,W] plane an earlier call returned (the words: bit 31 valid, emitted | candidate << 8 | run <<
+    16), UPDATED IN PLACE and returned; None: frame 0 seeds and a new plane is returned.  One call over n frames equals any chain of calls.
+    mv = int32 [n, (FH // 16) * (FW // 16), 7] with frame_size = (FH, FW): the prior state is read at every pixel's SOURCE under the
+    block matcher's vectors (ops.region_links' rule), 0 where the source lies outside the mask.  pair_stats = int32 [n,4],
+    block_match_modes' stats rows: a frame flagged as a cut starts from no state, with or without mv.  out: a caller-owned contiguous
+    uint8 [n,H,W] destination.  The compensated workspace is allocated here; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.mask_stabilize"
+    dev = one_device(mask, state, conf, mv, pair_stats, out, what=what)
+    n, h, w, k = _region_mask(mask, classes, "mask_stabilize")
+    if conf is not None and (conf.dtype != torch.uint8 or conf.shape != mask.shape):
+        raise RuntimeError(f"{what}: conf must be uint8 of the mask's shape {tuple(mask.shape)}, got {conf.dtype} {tuple(conf.shape)}")
+    if not 1 <= int(persist) <= 255:
+        raise RuntimeError(f"{what}: persist must be 1..255, got {persist}")
+    if trust is not None and (conf is None or not 0 <= int(trust) <= 256):
+        raise RuntimeError(f"{what}: trust must be 0..256 and needs conf, got {trust} with conf {'given' if conf is not None else 'missing'}")
+    if state is not None and (state.dtype != torch.int32 or tuple(state.shape) != (h, w) or not state.is_contiguous() or state.data_ptr() % 16):
+        raise RuntimeError(f"{what}: state must be a contiguous 16-byte aligned int32 [{h},{w}] tensor (an earlier call's), got {state.dtype} {tuple(state.shape)}")
+    fh = fw = hb = wb = 0
+    if mv is None:
+        if frame_size is not None:
+            raise RuntimeError(f"{what}: frame_size goes with mv (the motion-compensated route)")
+    else:
+        if frame_size is None or len(frame_size) != 2 or min(int(v) for v in frame_size) < 16 or int(frame_size[0]) * int(frame_size[1]) >= 2 ** 31:
+            raise RuntimeError(f"{what}: mv needs frame_size = (height, width) of the decoded frame, both >= 16, got {frame_size}")
+        fh, fw = int(frame_size[0]), int(frame_size[1])
+        hb, wb = fh // 16, fw // 16
+        if mv.dtype != torch.int32 or tuple(mv.shape) != (n, hb * wb, 7):
+            raise RuntimeError(f"{what}: mv must be int32 [{n},{hb * wb},7] for a {fh} x {fw} frame, got {mv.dtype} {tuple(mv.shape)}")
+        if h > 31 * fh or w > 31 * fw or n > 65535:
+            raise RuntimeError(f"{what}: the mask ({h} x {w}) may be at most 31 times the decoded frame ({fh} x {fw}) along an axis, and n at most 65535")
+    if pair_stats is not None and (pair_stats.dtype != torch.int32 or tuple(pair_stats.shape) != (n, 4)):
+        raise RuntimeError(f"{what}: pair_stats must be int32 [{n},4], got {pair_stats.dtype} {tuple(pair_stats.shape)}")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or not out.is_contiguous():
+            raise RuntimeError(f"{what}: out must be a contiguous uint8 [{n},{h},{w}] tensor, got {out.dtype} {tuple(out.shape)}")
+        has_state = state is not None
+        if state is None:
+            state = torch.empty((h, w), dtype=torch.int32, device=dev)
+        counts = torch.empty((n, 4), dtype=torch.int64, device=dev)
+        if n:
+            work = None
+            if mv is not None:
+                work = torch.empty((mask_stabilize_workspace_bytes(n, h, w, hb, wb) // 16, 2), dtype=torch.int64, device=dev)
+            check(lib.fs_mask_stabilize(ptr(mask.contiguous()), ptr(None if conf is None else conf.contiguous()), ptr(None if mv is None else mv.contiguous()),
+                                        ptr(None if pair_stats is None else pair_stats.contiguous()), n, h, w, fh, fw, k, int(persist),
+                                        256 if trust is None else int(trust), int(has_state), ptr(state), ptr(out), ptr(counts), ptr(work), stream_ptr()))
+        elif not has_state:
+            state.zero_()
+    return out, state, counts
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

@@ -718,6 +718,78 @@ typedef struct fs_hook_tables5 {
     fs_ext5_api ext5;
 } fs_hook_tables5;
 
+/* ---- The SEVENTH table.  fs_ext5_api is frozen as well (1 member, 24 bytes; tests/test_overlay_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables5 by the same pattern:
+ *     const fs_hook_tables6* t = (const fs_hook_tables6*)fs_test_hooks();   t->ext6.mask_stabilize(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables5: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext6.magic == FS_EXT6_MAGIC and ext6.size >= the end of the member it needs. */
+#define FS_EXT6_MAGIC 0x4653455854414236ull /* "FSEXTAB6" */
+
+typedef struct fs_ext6_api {
+    uint64_t magic; /* FS_EXT6_MAGIC */
+    size_t size;    /* sizeof(fs_ext6_api) of the library that was built */
+
+    /* ---- Temporal mask stabiliser (csrc/stabilize_ops.hip, csrc/stabilize_defs.h).  OUR DEFINITION: the reference
+     * measures the flicker of its masks (the temporal-consistency mIoU) and has nothing that acts on it.  A causal, per-pixel class
+     * debounce along the time axis, optionally read along the block matcher's vectors.  Integers throughout; every result is a function
+     * of the inputs alone, whatever order threads arrive in.
+     * Inputs:
+     *   mask        uint8 [n][H][W], the observed classes o.
+     *   confidence  uint8 [n][H][W] as mask_confidence writes it, or NULL.
+     *   mv          int32 [n][hb * wb][7] with frame_h x frame_w = FH x FW, hb = FH // 16, wb = FW // 16: region_links_mc's tables, mv[f]
+     *               the table of frame f against frame f-1; or NULL: the in-place op (frame_h, frame_w are then not looked at).
+     *   pair_stats  int32 [n][4], rows as block_match_modes writes its stats, or NULL; it is honoured with and without mv.
+     *   K classes 1..255;  persist P 1..255;  trust T 0..256 (256, or no confidence plane: nothing is trusted outright).
+     *   state       uint32 [H][W], the caller's, kept across calls: read when has_state == 1, written by every call.
+     * STATE WORD of a pixel: bit 31 = valid, bits 0-7 = the emitted class e, bits 8-15 = the candidate class c, bits 16-23 = the run
+     * length r; the word 0 = no state.
+     * PRIOR WORD s of frame f and pixel p, with o = mask[f][p]:
+     *   0                                        if f == 0 and has_state == 0;
+     *   0 for every pixel of the frame           if pair_stats is given and pair_stats[f][2] != 0 (a scene cut);
+     *   with mv: the state after frame f-1 (the caller's for f == 0) at the SOURCE of p -- region_links_mc's rule, word for word: centre,
+     *            block, row, void rows, the 64-bit differences, the shift scaled to mask pixels, (y + sy, x + sx) -- and 0 when the
+     *            source lies outside the mask;
+     *   otherwise the state after frame f-1 at p.
+     * UPDATE, in this order:
+     *   1. o >= K:        out = o, new state 0, nothing counted (not a class: passed through, and the pixel's history ends).
+     *   2. s not valid:   e = c = o, r = 0, out = o.                                                      Counted as SEEDED.
+     *   3. o == e:        c = e, r = 0, out = e.
+     *   4. o != e:        if a confidence plane is given and confidence[f][p] >= T:
+     *                         e = c = o, r = 0, out = o.                                                  Counted as SWITCHED and as TRUSTED.
+     *                     else r' = (o == c) ? min(r + 1, 255) : 1, and c = o;
+     *                         if r' >= P:  e = o, r = 0, out = o.                                         Counted as SWITCHED.
+     *                         else         r = r', out = e.                                               Counted as HELD.
+     * Outputs, each written whole by every call (so a HIP-graph replay on new planes gives that replay's result):
+     *   out     uint8 [n][H][W];   state = the words after frame n-1;
+     *   counts  int64 [n][4] = (held, switched, seeded, trusted) per frame: order-independent integer sums.
+     * Consequences: P == 1 gives out == mask bit for bit, and so does T == 0 with a confidence plane; one call over n frames equals any
+     * split into chained calls (has_state = 1 from the second on, mv / pair_stats / confidence sliced alike); with every row void, or
+     * every vector 0, the compensated call equals the in-place one, all three outputs; a change that lasts is emitted P - 1 frames late.
+     * LAUNCHES.  Without mv one launch for the whole call (one per 2048 frames), behind a 32 n-byte clearing launch for the counts: a
+     * thread keeps the words of four consecutive pixels in registers through all n frames, so the state costs 8 bytes per pixel and
+     * CALL.  With mv one launch packs a shift dword per block and frame (with a no-prior flag per frame, and clears the counts), then
+     * one launch per frame gathers the prior words at their sources, ping-pong between the caller's plane and a second one in the
+     * workspace such that the last frame writes the caller's; for odd n with has_state the caller's plane is copied to the second one
+     * first (a frame must not gather from the plane it writes).  Events are summed per thread, wave and workgroup, then one 64-bit
+     * atomic per counter, frame and workgroup, on at most 2 workgroups of 1024 threads per compute unit.  Nothing is allocated,
+     * synchronised or read on the host.
+     * workspace = FS_MASK_STABILIZE_WORKSPACE_BYTES(n, H, W, hb, wb) bytes at a 16-byte aligned address with mv: the second plane (4 B per
+     * pixel, rounded up to 16) and hb * wb + 1 dwords per frame.  Without mv it is 0 bytes (pass hb = wb = 0) and NULL is allowed.
+     * Refused before a launch: a null mask, out, state or counts; n < 1; H or W < 1; H * W >= 2^31 - 1; K, P or T out of range; has_state
+     * other than 0 or 1; a state plane not aligned to 16 bytes, counts not aligned to 8; and with mv: a null workspace or one not aligned to
+     * 16 bytes; n > 65535; frame_h or frame_w < 16; frame_h * frame_w >= 2^31; H > 31 frame_h or W > 31 frame_w. */
+#define FS_MASK_STABILIZE_WORKSPACE_BYTES(n, H, W, hb, wb) \
+    (((size_t)(hb) * (size_t)(wb) != 0) * ((((size_t)(H) * (size_t)(W) + 3) / 4) * 16 + (((size_t)(n) * ((size_t)(hb) * (size_t)(wb) + 1) + 3) / 4) * 16))
+    int (*mask_stabilize)(const uint8_t* mask, const uint8_t* confidence, const int32_t* mv, const int32_t* pair_stats, int n, int H, int W, int frame_h,
+                          int frame_w, int K, int persist, int trust, int has_state, uint32_t* state, uint8_t* out, int64_t* counts, void* workspace,
+                          fs_stream stream);
+} fs_ext6_api;
+
+typedef struct fs_hook_tables6 {
+    fs_hook_tables5 base5;
+    fs_ext6_api ext6;
+} fs_hook_tables6;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

@@ -61,6 +61,15 @@ filled in a colour picked by its track id (ops.TRACK_PALETTE, with the class's o
 track id (mod 10^7) in a 5 x 7 font scaled by SCALE (1..4, default 2) at its centroid -- the number in the track column of the regions
 CSV and in the GeoJSON features.  `--label-min-area N` (default 256) leaves regions below N pixels without a label.  Colours, widths and
 the area bound are guesses, not validated on real video.  The PNG route (`--out`) is unchanged.
+`--stabilize N` (an extension; 2..255, 0 or 1: off) debounces every pixel's class along the time axis on the device before
+anything else sees the masks: a pixel keeps its emitted class until another class has been observed N frames running, so a change that
+lasts shows N - 1 frames late and a shorter flicker never does; every output -- masks, overlays, reports, regions, tracks, metrics --
+then shows the stabilised masks, and the totals of held, switched and seeded pixels are printed after the temporal-consistency line.
+`--stabilize-trust T` (0..256, needs `--confidence`) emits an observation whose confidence code is at least T at once.
+`--stabilize-compensate` (needs estimated grids: `--raw`, or `--grids estimate`) reads the state at the source of every pixel under the
+block matcher's vectors, and a frame that follows a `--scene-cut` starts afresh; without it a moving scene is compared in place, where
+the filter lags and can make the masks worse.  Under torchrun every rank's block of windows starts unseeded.  No default is validated
+on real video.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -176,6 +185,12 @@ def parse_args(argv=None):
                     "all vertices of the segments still open and get a warning.  The default is a guess, not validated on real video")
     ap.add_argument("--compensate", action="store_true", help="--tracks with estimated grids: compare each frame with the frame before it read at "
                     "the source of every pixel under the block matcher's vectors, so that a small region that moves fast keeps its track")
+    ap.add_argument("--stabilize", type=int, default=0, metavar="N", help="debounce every pixel's class along the time axis: a class is emitted once "
+                    "it has been observed N frames running (2..255; 0 or 1: off).  Not validated on real video")
+    ap.add_argument("--stabilize-trust", type=int, default=None, metavar="T", help="--stabilize with --confidence: an observation with a confidence "
+                    "code >= T (0..256) is emitted at once")
+    ap.add_argument("--stabilize-compensate", action="store_true", help="--stabilize with estimated grids: read the state at the source of every pixel "
+                    "under the block matcher's vectors")
     ap.add_argument("--draw-outlines", type=int, nargs="?", const=1, default=None, metavar="W", help="--raw-out with --regions: draw a white line W "
                     "pixels wide (0..4, default 1) along the inside of every region's boundary")
     ap.add_argument("--draw-tracks", action="store_true", help="--raw-out with --regions and --tracks: fill every region in a colour picked by its track id")
@@ -212,6 +227,15 @@ def parse_args(argv=None):
         ap.error("--compensate needs --tracks: it changes how the tracks' links are counted")
     if args.compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
         ap.error("--compensate needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
+    if not 0 <= args.stabilize <= 255:
+        ap.error("--stabilize takes N of 0..255 frames")
+    if (args.stabilize_trust is not None or args.stabilize_compensate) and args.stabilize <= 1:
+        ap.error("--stabilize-trust and --stabilize-compensate need --stabilize N with N >= 2")
+    if args.stabilize_trust is not None and (not args.confidence or not 0 <= args.stabilize_trust <= 256):
+        ap.error("--stabilize-trust takes a code 0..256 and needs --confidence")
+    if args.stabilize_compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
+        ap.error("--stabilize-compensate needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be "
+                 "recovered)")
     if args.min_overlap < 1 or (args.max_pairs is not None and (not 16 <= args.max_pairs <= 2 ** 20 or args.max_pairs & (args.max_pairs - 1))):
         ap.error("--min-overlap takes N >= 1 and --max-pairs a power of two in 16..1048576")
     if args.min_region < 0 or not 1 <= args.max_regions <= 65536:
@@ -278,18 +302,19 @@ def main():
                          low_confidence=args.low_confidence, regions=bool(args.regions), min_region_area=args.min_region,
                          connectivity=args.connectivity, max_regions=args.max_regions, track=bool(args.tracks), min_overlap=args.min_overlap,
                          max_pairs=args.max_pairs, compensate=args.compensate, outlines=bool(args.outlines), max_contours=args.max_contours,
-                         max_vertices=args.max_vertices, simplify=args.simplify, simplify_rounds=args.simplify_rounds, keep_window_regions=draw)
+                         max_vertices=args.max_vertices, simplify=args.simplify, simplify_rounds=args.simplify_rounds, keep_window_regions=draw,
+                         stabilize=args.stabilize, stabilize_trust=args.stabilize_trust, stabilize_compensate=args.stabilize_compensate)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
                              full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut, hold_cuts=args.hold_cuts,
-                             link_vectors=args.compensate)
+                             link_vectors=args.compensate or args.stabilize_compensate)
     else:
         ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
                             grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut,
-                            hold_cuts=args.hold_cuts, link_vectors=args.compensate)
+                            hold_cuts=args.hold_cuts, link_vectors=args.compensate or args.stabilize_compensate)
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -389,6 +414,10 @@ def main():
             line += (f"; temporal consistency mIoU {float((inter / (union + 1e-10)).mean()):.4f}"
                      f" mAcc {float((inter / (target + 1e-10)).mean()):.4f} acc {float(inter.sum() / (target.sum() + 1e-10)):.4f}")
         print(line, file=sys.stderr if args.raw_out == "-" else sys.stdout)   # standard output may be the video
+    if args.stabilize > 1:  # the device counts are read back ONCE, here, after the timed run
+        held, switched, seeded, trusted = pred.stabilize_report().sum(0).tolist()
+        print(f"rank {rank}: --stabilize {args.stabilize}: {held} pixels held, {switched} switched ({trusted} of them trusted), {seeded} seeded",
+              file=sys.stderr if args.raw_out == "-" else sys.stdout)
     kept = ds.estimator.estimated_stats() if ds.estimator is not None else {}
     if kept:  # --intra-bias / --scene-cut: the kept device stats are read back ONCE, here, after the timed run
         ids = sorted(kept)
