@@ -186,6 +186,13 @@ _EXT6_HOOKS = [
 ]
 EXT6_MAGIC = 0x4653455854414236  # FS_EXT6_MAGIC
 
+# members of fs_ext7_api, the eighth table (append-only, behind the seven frozen ones), in declaration order after `magic` and `size`
+_EXT7_HOOKS = [
+    ("mask_distance", c_int, [c_void] + [c_int] * 3 + [ctypes.c_uint32, c_int] + [c_void] * 4),
+    ("region_proximity", c_int, [c_void] * 5 + [c_int] * 5 + [ctypes.c_uint32, c_void, c_int] + [c_void] * 3),
+]
+EXT7_MAGIC = 0x4653455854414237  # FS_EXT7_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
@@ -239,6 +246,14 @@ class FsHookTables6(ctypes.Structure):
     _fields_ = [("base5", FsHookTables5), ("ext6", FsExt6Api)]
 
 
+class FsExt7Api(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT7_HOOKS]
+
+
+class FsHookTables7(ctypes.Structure):
+    _fields_ = [("base6", FsHookTables6), ("ext7", FsExt7Api)]
+
+
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
     fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
@@ -252,8 +267,31 @@ class _Library:
         self._ext4 = None
         self._ext5 = None
         self._ext6 = None
+        self._ext7 = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT7_HOOKS):
+            if self._ext7 is None:
+                all6 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables6)).contents
+                all5 = all6.base5
+                all2 = all5.base4.base3.base2
+                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
+                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
+                        or all5.base4.base3.ext3.magic != EXT3_MAGIC or all5.base4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
+                        or all5.base4.ext4.magic != EXT4_MAGIC or all5.base4.ext4.size != ctypes.sizeof(FsExt4Api)
+                        or all5.ext5.magic != EXT5_MAGIC or all5.ext5.size != ctypes.sizeof(FsExt5Api)
+                        or all6.ext6.magic != EXT6_MAGIC or all6.ext6.size != ctypes.sizeof(FsExt6Api)):
+                    raise RuntimeError(f"floodseg: the library's first seven hook tables are not the ones this binding knows ({name} is missing)")
+                ext7 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables7)).contents.ext7
+                if ext7.magic != EXT7_MAGIC:
+                    raise RuntimeError(f"floodseg: the library has no seventh extension table ({name} is missing)")
+                self._ext7 = ext7
+            member = getattr(FsExt7Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
+            if self._ext7.size < member.offset + member.size:
+                raise RuntimeError(f"floodseg: the library's seventh extension table is older than this binding ({name} is missing)")
+            fn = getattr(self._ext7, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT6_HOOKS):
             if self._ext6 is None:
                 all5 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables5)).contents
@@ -424,6 +462,11 @@ def ext5_hook_names():
 def ext6_hook_names():
     """Members of fs_ext6_api after `magic` and `size`, in declaration order."""
     return [h[0] for h in _EXT6_HOOKS]
+
+
+def ext7_hook_names():
+    """Members of fs_ext7_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT7_HOOKS]
 
 
 def check(rc):

@@ -531,7 +531,19 @@ static int fs_mask_stabilize(const uint8_t* mask, const uint8_t* confidence, con
                                      reinterpret_cast<long long*>(counts), workspace, S(stream));
 }
 
-// the seven tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// distance to a class (distance_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_mask_distance(const uint8_t* mask, int n, int H, int W, uint32_t source_set, int max_dist, uint32_t* d2, int32_t* nearest, void* workspace,
+                            fs_stream stream) {
+    return fs::launch_mask_distance(mask, n, H, W, source_set, max_dist, d2, nearest, workspace, S(stream));
+}
+static int fs_region_proximity(const uint8_t* mask, const uint32_t* d2, const int32_t* nearest, const int32_t* index, const int64_t* counts, int n, int H,
+                               int W, int K, int max_regions, uint32_t target_set, const int32_t* thresholds, int B, int64_t* exposure, int64_t* near,
+                               fs_stream stream) {
+    return fs::launch_region_proximity(mask, d2, nearest, index, reinterpret_cast<const long long*>(counts), n, H, W, K, max_regions, target_set, thresholds,
+                                       B, reinterpret_cast<long long*>(exposure), reinterpret_cast<long long*>(near), S(stream));
+}
+
+// the eight tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -625,7 +637,17 @@ static const fs_hook_tables5& hook_tables(void) {
         sizeof(fs_ext6_api),
         fs_mask_stabilize,
     }};
-    return all6.base5;
+    // fs_ext6_api is frozen too (one member, 24 bytes); the eighth table lies behind it by the same pattern, and &all7.base6 is &all7.
+    static const fs_hook_tables7 all7 = {all6, {
+        FS_EXT7_MAGIC,
+        sizeof(fs_ext7_api),
+        fs_mask_distance,
+        fs_region_proximity,
+    }};
+    {
+        const fs_hook_tables6& all6 = all7.base6;  // from here on the name means the head of the whole object, not the copy it was built from
+        return all6.base5;
+    }
 }
 
 FS_API const fs_test_api* fs_test_hooks(void) {

@@ -386,6 +386,15 @@ int launch_region_tracks(const int* back, const int* fwd, const long long* count
 int launch_mask_stabilize(const uint8_t* mask, const uint8_t* conf, const int* mv, const int* pair_stats, int n, int H, int W, int frame_h, int frame_w,
                           int K, int persist, int trust, int has_state, uint32_t* state, uint8_t* out, long long* counts, void* workspace, hipStream_t s);
 
+// Distance to a class (distance_ops.hip, distance_defs.h; definitions: include/floodseg_test.h, mask_distance and region_proximity).  The
+// launchers refuse bad arguments before they launch anything.  nearest may be nullptr in both; workspace: FS_MASK_DISTANCE_WORKSPACE_BYTES,
+// the caller's; thresholds: B ints in HOST memory.  Nothing is allocated or synchronised.
+int launch_mask_distance(const uint8_t* mask, int n, int H, int W, uint32_t source_set, int max_dist, uint32_t* d2, int32_t* nearest, void* workspace,
+                         hipStream_t s);
+int launch_region_proximity(const uint8_t* mask, const uint32_t* d2, const int32_t* nearest, const int32_t* index, const long long* counts, int n, int H,
+                            int W, int K, int max_regions, uint32_t target_set, const int32_t* thresholds, int B, long long* exposure, long long* near,
+                            hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

@@ -801,6 +801,107 @@ def mask_stabilize(mask, state=None, conf=None, classes=5, persist=3, trust=None
     return out, state, counts
 
 
+# ------------------------------------------------------------------------------------------ distance to a class
+DIST_NONE = 0xFFFFFFFF  # FS_DIST_NONE; the int32 tensors that carry d2 show it as -1
+
+
+def mask_distance_workspace_bytes(n, h, w):
+    """FS_MASK_DISTANCE_WORKSPACE_BYTES of include/floodseg_test.h: one dword per column and chunk of 64 rows, 2 bytes per pixel."""
+    return (n * ((h + 63) // 64) * w * 4 + n * h * w * 2 + 15) // 16 * 16
+
+
+def class_set(classes, name, what, allow_empty=False):
+    """An iterable of class ids 0..31 -> the uint32 with those bits set (source_set / target_set of the distance ops)."""
+    ids = [int(c) for c in classes]
+    if any(not 0 <= c <= 31 for c in ids) or (not ids and not allow_empty):
+        raise ValueError(f"{what}: {name} must be class ids 0..31{'' if allow_empty else ', at least one'}, got {list(classes)}")
+    bits = 0
+    for c in ids:
+        bits |= 1 << c
+    return bits
+
+
+def mask_distance(mask, sources, max_dist=0, want_nearest=True, out=None):
+    """The exact squared Euclidean distance of every pixel to the nearest pixel of the classes `sources` in its own frame (definition:
+    include/floodseg_test.h, mask_distance): uint8 masks [n,H,W] -> (d2, nearest).  d2: int32 [n,H,W] holding the uint32
+    values (0 on a source pixel; FS_DIST_NONE = 0xFFFFFFFF, read as -1, in a frame without a source and, with max_dist = R > 0, beyond
+    R pixels; every other value is the exact minimum).  nearest: int32 [n,H,W], the raster index y * W + x of the nearest source pixel,
+    the smallest index among several, -1 where d2 is FS_DIST_NONE; None with want_nearest=False.  sources: class ids 0..31.  Distances are
+    in mask pixels.  out: caller-owned contiguous (d2, nearest) destinations.  The workspace is allocated here; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.mask_distance"
+    dev = one_device(mask, *(out or ()), what=what)
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise ValueError(f"{what}: mask must be uint8 [n,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    n, h, w = mask.shape
+    if not 1 <= h <= 32768 or not 1 <= w <= 32768 or n > 65535:
+        raise ValueError(f"{what}: at most 65535 frames of 1..32768 pixels a side, got {tuple(mask.shape)}")
+    bits = class_set(sources, "sources", what)
+    if not 0 <= int(max_dist) <= 32767:
+        raise ValueError(f"{what}: max_dist must be 0..32767 pixels (0: unbounded), got {max_dist}")
+    with torch.cuda.device(dev):
+        if out is None:
+            d2 = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+            nearest = torch.empty((n, h, w), dtype=torch.int32, device=dev) if want_nearest else None
+        else:
+            d2, nearest = out
+            for t, name in ((d2, "d2"), (nearest, "nearest")):
+                if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n, h, w) or not t.is_contiguous()):
+                    raise ValueError(f"{what}: out's {name} must be a contiguous int32 [{n},{h},{w}] tensor, got {t.dtype} {tuple(t.shape)}")
+            if (nearest is not None) != bool(want_nearest):
+                raise ValueError(f"{what}: out = (d2, nearest) must hold a nearest plane exactly when want_nearest is set")
+        if n:
+            work = torch.empty((mask_distance_workspace_bytes(n, h, w) // 4,), dtype=torch.int32, device=dev)
+            check(lib.fs_mask_distance(ptr(mask.contiguous()), n, h, w, bits, int(max_dist), ptr(d2), ptr(nearest), ptr(work), stream_ptr()))
+    return d2, nearest
+
+
+def region_proximity(mask, d2, nearest, index, counts, classes, max_regions, targets, thresholds, out=None):
+    """mask_distance's field tabulated per class and per region (definition: include/floodseg_test.h, region_proximity):
+    -> (exposure int64 [n,classes,B], near int64 [n,max_regions,8]).  exposure[f][k][b] = the pixels of class k (k in targets, ids 0..31)
+    within thresholds[b] pixels of a source, cumulative in b.  near rows, one per row of region_table's table (index, counts):
+    (min_d2, at_x, at_y, src_x, src_y, src_row, near_pixels, 0) -- the region's smallest squared distance, the pixel that attains it
+    (lowest raster index), the source pixel nearest to it and that pixel's region row (-1: none; all three -1 with nearest=None), and
+    the region's pixels within thresholds[0]; a region out of reach of every source: (-1, -1, -1, -1, -1, -1, 0, 0).  thresholds: 1..8
+    strictly ascending ints 0..32767.  out: caller-owned contiguous (exposure, near) destinations; they are written whole."""
+    lib = _lib.load()
+    what = "floodseg.region_proximity"
+    dev = one_device(mask, d2, nearest, index, counts, *(out or ()), what=what)
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise ValueError(f"{what}: mask must be uint8 [n,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    n, h, w = mask.shape
+    if not 1 <= h <= 32768 or not 1 <= w <= 32768 or n > 65535:
+        raise ValueError(f"{what}: at most 65535 frames of 1..32768 pixels a side, got {tuple(mask.shape)}")
+    for t, name in ((d2, "d2"), (nearest, "nearest"), (index, "index")):
+        if (t is None and name != "nearest") or (t is not None and (t.dtype != torch.int32 or t.shape != mask.shape)):
+            raise ValueError(f"{what}: {name} must be int32 of the mask's shape {tuple(mask.shape)}, got "
+                             f"{None if t is None else (t.dtype, tuple(t.shape))}")
+    if counts.dtype != torch.int64 or tuple(counts.shape) != (n, 2):
+        raise ValueError(f"{what}: counts must be int64 [{n},2] (region_table's), got {counts.dtype} {tuple(counts.shape)}")
+    k, cap = int(classes), int(max_regions)
+    if not 1 <= k <= 255 or not 1 <= cap <= 65536:
+        raise ValueError(f"{what}: classes must be 1..255 and max_regions 1..65536, got {classes} and {max_regions}")
+    bits = class_set(targets, "targets", what, allow_empty=True)
+    thr = [int(t) for t in thresholds]
+    if not 1 <= len(thr) <= 8 or any(not 0 <= t <= 32767 for t in thr) or any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError(f"{what}: thresholds must be 1..8 strictly ascending distances of 0..32767 pixels, got {list(thresholds)}")
+    host = (ctypes.c_int32 * len(thr))(*thr)  # read by the library during the call
+    with torch.cuda.device(dev):
+        if out is None:
+            exposure = torch.empty((n, k, len(thr)), dtype=torch.int64, device=dev)
+            near = torch.empty((n, cap, 8), dtype=torch.int64, device=dev)
+        else:
+            exposure, near = out
+            if (exposure.dtype != torch.int64 or tuple(exposure.shape) != (n, k, len(thr)) or not exposure.is_contiguous() or near.dtype != torch.int64
+                    or tuple(near.shape) != (n, cap, 8) or not near.is_contiguous()):
+                raise ValueError(f"{what}: out must be contiguous int64 [{n},{k},{len(thr)}] and [{n},{cap},8] tensors")
+        if n:
+            check(lib.fs_region_proximity(ptr(mask.contiguous()), ptr(d2.contiguous()), ptr(None if nearest is None else nearest.contiguous()),
+                                          ptr(index.contiguous()), ptr(counts.contiguous()), n, h, w, k, cap, bits,
+                                          ctypes.cast(host, ctypes.c_void_p), len(thr), ptr(exposure), ptr(near), stream_ptr()))
+    return exposure, near
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

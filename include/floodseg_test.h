@@ -790,6 +790,85 @@ typedef struct fs_hook_tables6 {
     fs_ext6_api ext6;
 } fs_hook_tables6;
 
+/* ---- The EIGHTH table.  fs_ext6_api is frozen as well (1 member, 24 bytes; tests/test_stabilize_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables6 by the same pattern:
+ *     const fs_hook_tables7* t = (const fs_hook_tables7*)fs_test_hooks();   t->ext7.mask_distance(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables6: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext7.magic == FS_EXT7_MAGIC and ext7.size >= the end of the member it needs. */
+#define FS_EXT7_MAGIC 0x4653455854414237ull /* "FSEXTAB7" */
+#define FS_DIST_NONE 0xFFFFFFFFu            /* d2 of a pixel without a source in reach */
+
+typedef struct fs_ext7_api {
+    uint64_t magic; /* FS_EXT7_MAGIC */
+    size_t size;    /* sizeof(fs_ext7_api) of the library that was built */
+
+    /* ---- Exact distance to a class (csrc/distance_ops.hip, csrc/distance_defs.h).  OUR DEFINITION: the reference has
+     * nothing like it.  Integers throughout; every result is a function of the inputs alone, whatever order threads arrive in.
+     * Distances are in MASK PIXELS of a moving, un-georeferenced camera.
+     * Inputs:
+     *   mask        uint8 [n][H][W], at any byte address.
+     *   source_set  uint32, non-zero: bit k set = class k is a source.  Mask ids >= 32 are never sources.
+     *   max_dist    R, 0..32767; 0 = unbounded.
+     * A pixel q of frame f is a SOURCE PIXEL if mask[f][q] < 32 and bit mask[f][q] of source_set is set.
+     * Outputs, each written whole by every call (so a HIP-graph replay on new planes gives that replay's result):
+     *   d2       uint32 [n][H][W]: for pixel p of frame f the minimum of (p.y - q.y)^2 + (p.x - q.x)^2 over the source pixels q of frame f; 0
+     *            on a source pixel; FS_DIST_NONE where frame f has no source pixel, and with R > 0 also where that minimum exceeds R * R.  A
+     *            value that is not FS_DIST_NONE is always the exact minimum: R replaces values by FS_DIST_NONE, it never changes one.
+     *   nearest  int32 [n][H][W], or NULL: the raster index q.y * W + q.x of a source pixel that attains the minimum, among several the
+     *            smallest raster index; -1 wherever d2 is FS_DIST_NONE.
+     * Frames never see each other's sources.
+     * LAUNCHES.  The separable form, three launches.  (1) Per column and chunk of 64 rows one dword: the first and the last source row
+     * of the chunk.  (2) Per pixel the row of the nearest source pixel of its own COLUMN, the upper one on a tie (2 bytes, 0xFFFF: the
+     * column has none): the chunk's 64 mask bytes as one 64-bit word, the nearest rows outside the chunk from the dwords of (1), at most
+     * ceil(H / 64) - 1 of them.  (3) One workgroup per row stages the row's entries of (2) in LDS (2 W bytes, at most 64 KiB); a thread
+     * scans outwards from its own x, d = 0, 1, 2, ..., taking the minimum of (d * d + g * g, raster index) over the columns x - d and
+     * x + d, g the vertical distance to that column's entry, and stops at the first d with d * d > best (with nearest == NULL:
+     * d * d >= best), when d passes R, or at the row's ends: every candidate at offset d costs at least d * d.  A row without any entry
+     * means a frame without a source: nothing is scanned.  The scan is short where a source is near and O(W) per pixel for a frame with
+     * one source pixel and R = 0 (measured: profiles/r23_distance.txt).
+     * workspace = FS_MASK_DISTANCE_WORKSPACE_BYTES(n, H, W) bytes at a 4-byte aligned address, the caller's: the dwords of (1), then the
+     * entries of (2).  Nothing is allocated, synchronised or read on the host.
+     * Refused before a launch: a null mask, d2 or workspace; n < 1 or n > 65535; H or W < 1; H * W >= 2^31 - 1; H or W > 32768 (the bound
+     * keeps d2 < 2^31); source_set == 0; R outside 0..32767; d2, nearest or the workspace not aligned to 4 bytes. */
+#define FS_MASK_DISTANCE_WORKSPACE_BYTES(n, H, W) \
+    ((((size_t)(n) * (((size_t)(H) + 63) / 64) * (size_t)(W) * 4 + (size_t)(n) * (size_t)(H) * (size_t)(W) * 2) + 15) / 16 * 16)
+    int (*mask_distance)(const uint8_t* mask, int n, int H, int W, uint32_t source_set, int max_dist, uint32_t* d2, int32_t* nearest, void* workspace,
+                         fs_stream stream);
+
+    /* ---- The distance field tabulated per class and per region (csrc/distance_ops.hip).  OUR DEFINITION.
+     * Inputs:
+     *   mask        uint8 [n][H][W];   d2 uint32 [n][H][W] and nearest int32 [n][H][W] (or NULL) as mask_distance wrote them;
+     *   index       int32 [n][H][W] and counts int64 [n][2], region_table's;   K classes 1..255;   max_regions 1..65536;
+     *   target_set  uint32: bit k set = class k is tabulated in `exposure`;
+     *   thresholds  int32 [B] in HOST memory, 1 <= B <= 8, strictly ascending distances in pixels, each 0..32767 (read during the call).
+     * rows(f) = min(max(counts[f][1], 0), max_regions); a pixel p of frame f BELONGS to row r if index[f][p] == r and 0 <= r < rows(f).
+     * Outputs, each cleared on the stream and written whole by every call:
+     *   exposure  int64 [n][K][B]: exposure[f][k][b] = the number of pixels of frame f with mask == k and d2 <= thresholds[b]^2
+     *             (cumulative in b; FS_DIST_NONE is above every threshold); all zero for a class outside target_set and for k >= 32.
+     *   near      int64 [n][max_regions][8], row r of frame f = (min_d2, at_x, at_y, src_x, src_y, src_row, near_pixels, 0):
+     *             min_d2 the smallest d2 other than FS_DIST_NONE over the row's pixels, (at_x, at_y) the pixel that attains it, the
+     *             lowest raster index on a tie; (src_x, src_y) = nearest at that pixel, src_row = index at the source pixel, -1 if
+     *             that pixel belongs to no row; near_pixels = the row's pixels with d2 <= thresholds[0]^2.  A row none of whose pixels
+     *             has a d2 other than FS_DIST_NONE: (-1, -1, -1, -1, -1, -1, 0, 0).  nearest == NULL: src_x = src_y = src_row = -1.  Rows at
+     *             and behind rows(f) are zero.  Regions of every class get a row: a source region's own is min_d2 = 0 at its anchor.
+     * LAUNCHES.  Three: set up (the minimum's word starts at all ones, everything else at 0); one pass over the pixels (an LDS
+     * histogram [32][8] per workgroup, flushed cumulatively with one 64-bit atomic per non-zero cell; per row a 64-bit atomic minimum of
+     * d2 << 32 | raster index and an atomic sum, once per run of a row along the 1024 consecutive pixels a wave owns, and the minimum
+     * only where it would lower the word); finish (the word becomes the row).  Integer sums and minima: the order does not matter.  No
+     * workspace; nothing is allocated, synchronised or read on the host except `thresholds`.
+     * Refused before a launch: a null mask, d2, index, counts, thresholds, exposure or near; n < 1 or n > 65535; H or W < 1; H * W >= 2^31 -
+     * 1; H or W > 32768; K or max_regions out of range; B outside 1..8; a threshold outside 0..32767 or not above the one before it; d2,
+     * nearest or index not aligned to 4 bytes; counts, exposure or near not aligned to 8. */
+    int (*region_proximity)(const uint8_t* mask, const uint32_t* d2, const int32_t* nearest, const int32_t* index, const int64_t* counts, int n, int H,
+                            int W, int K, int max_regions, uint32_t target_set, const int32_t* thresholds, int B, int64_t* exposure, int64_t* near,
+                            fs_stream stream);
+} fs_ext7_api;
+
+typedef struct fs_hook_tables7 {
+    fs_hook_tables6 base6;
+    fs_ext7_api ext7;
+} fs_hook_tables7;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

@@ -70,6 +70,15 @@ then shows the stabilised masks, and the totals of held, switched and seeded pix
 block matcher's vectors, and a frame that follows a `--scene-cut` starts afresh; without it a moving scene is compared in place, where
 the filter lags and can make the masks worse.  Under torchrun every rank's block of windows starts unseeded.  No default is validated
 on real video.
+`--proximity PX [PX ...]` (an extension; needs `--regions`; 1..8 ascending distances in mask pixels) measures, on the device,
+the exact distance of every pixel to the nearest pixel of the classes `--proximity-sources` (default 1, water) and tabulates it: the
+regions CSV gains `dist` (the region's smallest distance, empty: none within reach), `near_px` (its pixels within the first PX) and
+`nearest_region` (and `nearest_track` with `--tracks`), the tracks CSV `first_dist`, `last_dist` and `min_dist`, and `--exposure FILE.csv`
+gets one row per frame: per class of `--proximity-targets` (default 3 4) the pixels within each PX.  `--proximity-max R` bounds the search
+to R >= the largest PX pixels (regions further away then have an empty `dist`); unbounded, the default, costs a scan of up to the
+frame's width per pixel where water is a single speck.  Distances
+are mask pixels of a moving, un-georeferenced camera -- no metres follow from them -- and the thresholds are guesses, not validated on
+real video.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -89,7 +98,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_extent_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_exposure_csv, write_extent_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -191,6 +200,16 @@ def parse_args(argv=None):
                     "code >= T (0..256) is emitted at once")
     ap.add_argument("--stabilize-compensate", action="store_true", help="--stabilize with estimated grids: read the state at the source of every pixel "
                     "under the block matcher's vectors")
+    ap.add_argument("--proximity", type=int, nargs="+", default=None, metavar="PX", help="--regions: measure every pixel's exact distance to the nearest "
+                    "source pixel on the device and tabulate it per region and class at these 1..8 ascending distances (mask pixels; guesses, not "
+                    "validated on real video)")
+    ap.add_argument("--proximity-sources", type=int, nargs="+", default=[1], metavar="CLASS", help="--proximity: the classes distances are measured to "
+                    "(default 1, water)")
+    ap.add_argument("--proximity-targets", type=int, nargs="+", default=[3, 4], metavar="CLASS", help="--proximity: the classes --exposure counts "
+                    "(default 3 4, buildings and streets)")
+    ap.add_argument("--proximity-max", type=int, default=None, metavar="R", help="--proximity: search no further than R pixels, R at least the largest "
+                    "PX (default: unbounded)")
+    ap.add_argument("--exposure", default=None, metavar="FILE.csv", help="--proximity: one row per frame, per target class the pixels within each PX")
     ap.add_argument("--draw-outlines", type=int, nargs="?", const=1, default=None, metavar="W", help="--raw-out with --regions: draw a white line W "
                     "pixels wide (0..4, default 1) along the inside of every region's boundary")
     ap.add_argument("--draw-tracks", action="store_true", help="--raw-out with --regions and --tracks: fill every region in a colour picked by its track id")
@@ -227,6 +246,15 @@ def parse_args(argv=None):
         ap.error("--compensate needs --tracks: it changes how the tracks' links are counted")
     if args.compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
         ap.error("--compensate needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
+    if args.proximity is not None and not args.regions:
+        ap.error("--proximity needs --regions: the distances are tabulated per region")
+    if args.proximity is None and (args.exposure or args.proximity_max is not None):
+        ap.error("--exposure and --proximity-max need --proximity PX [PX ...]")
+    if args.proximity is not None and (not 1 <= len(args.proximity) <= 8 or any(not 0 <= t <= 32767 for t in args.proximity)
+                                       or any(b <= a for a, b in zip(args.proximity, args.proximity[1:]))):
+        ap.error("--proximity takes 1..8 strictly ascending distances of 0..32767 pixels")
+    if args.proximity_max is not None and (not 0 <= args.proximity_max <= 32767 or 0 < args.proximity_max < args.proximity[-1]):
+        ap.error("--proximity-max takes R of 0..32767 pixels (0: unbounded), at least the largest PX")
     if not 0 <= args.stabilize <= 255:
         ap.error("--stabilize takes N of 0..255 frames")
     if (args.stabilize_trust is not None or args.stabilize_compensate) and args.stabilize <= 1:
@@ -303,7 +331,9 @@ def main():
                          connectivity=args.connectivity, max_regions=args.max_regions, track=bool(args.tracks), min_overlap=args.min_overlap,
                          max_pairs=args.max_pairs, compensate=args.compensate, outlines=bool(args.outlines), max_contours=args.max_contours,
                          max_vertices=args.max_vertices, simplify=args.simplify, simplify_rounds=args.simplify_rounds, keep_window_regions=draw,
-                         stabilize=args.stabilize, stabilize_trust=args.stabilize_trust, stabilize_compensate=args.stabilize_compensate)
+                         stabilize=args.stabilize, stabilize_trust=args.stabilize_trust, stabilize_compensate=args.stabilize_compensate,
+                         proximity=args.proximity, proximity_sources=args.proximity_sources, proximity_targets=args.proximity_targets,
+                         proximity_max=args.proximity_max)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
@@ -441,8 +471,11 @@ def main():
         region_rows, totals = pred.region_report()
         track_rows, overflowed, cut = pred.track_report(with_cuts=True) if args.tracks else (None, [], [])
         outlines = pred.outline_report() if args.outlines else None
+        exposure, near_rows = pred.proximity_report() if args.proximity else (None, None)
         write_regions_csv(args.regions, report_ids, region_rows, with_confidence=args.confidence, tracks=track_rows,
-                          shapes=[o[2] for o in outlines[0]] if outlines else None)
+                          shapes=[o[2] for o in outlines[0]] if outlines else None, proximity=near_rows)
+        if args.exposure:
+            write_exposure_csv(args.exposure, report_ids, exposure, args.proximity, args.size[0] * args.size[1])
         if outlines:
             simple = pred.simple_outline_report() if args.simplify is not None else None
             write_outlines_geojson(args.outlines, report_ids, region_rows, outlines, tracks=track_rows, simplified=simple, tolerance=args.simplify)
@@ -465,7 +498,7 @@ def main():
                     print(f"warning: frame {fid} has more than --max-contours {args.max_contours} contours: the first {args.max_contours} are "
                           "written", file=sys.stderr)
         if args.tracks:
-            write_tracks_csv(args.tracks, report_ids, region_rows, track_rows)
+            write_tracks_csv(args.tracks, report_ids, region_rows, track_rows, proximity=near_rows)
             for fid, flag in zip(report_ids, overflowed.tolist()):
                 if flag:
                     print(f"warning: frame {fid}: the pair table overflowed (--max-pairs {pred.max_pairs}): its regions all start new tracks",
