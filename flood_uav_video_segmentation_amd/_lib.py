@@ -193,6 +193,15 @@ _EXT7_HOOKS = [
 ]
 EXT7_MAGIC = 0x4653455854414237  # FS_EXT7_MAGIC
 
+# members of fs_ext8_api, the ninth table (append-only, behind the eight frozen ones), in declaration order after `magic` and `size`
+_EXT8_HOOKS = [
+    ("global_motion", c_int, [c_void] * 3 + [ctypes.c_uint32] + [c_int] * 6 + [ctypes.c_int64, c_int, c_void, c_void]),
+    ("pose_chain", c_int, [c_void] * 3 + [c_int] * 8 + [c_void]),
+    ("mosaic_accumulate", c_int, [c_void] * 2 + [c_int] * 8 + [c_void] * 2),
+    ("mosaic_resolve", c_int, [c_void] + [c_int] * 3 + [c_void] * 5),
+]
+EXT8_MAGIC = 0x4653455854414238  # FS_EXT8_MAGIC
+
 
 class FsTestApi(ctypes.Structure):
     _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
@@ -254,6 +263,14 @@ class FsHookTables7(ctypes.Structure):
     _fields_ = [("base6", FsHookTables6), ("ext7", FsExt7Api)]
 
 
+class FsExt8Api(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT8_HOOKS]
+
+
+class FsHookTables8(ctypes.Structure):
+    _fields_ = [("base7", FsHookTables7), ("ext8", FsExt8Api)]
+
+
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
     fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
@@ -268,8 +285,32 @@ class _Library:
         self._ext5 = None
         self._ext6 = None
         self._ext7 = None
+        self._ext8 = None
 
     def __getattr__(self, name):
+        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT8_HOOKS):
+            if self._ext8 is None:
+                all7 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables7)).contents
+                all5 = all7.base6.base5
+                all2 = all5.base4.base3.base2
+                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
+                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
+                        or all5.base4.base3.ext3.magic != EXT3_MAGIC or all5.base4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
+                        or all5.base4.ext4.magic != EXT4_MAGIC or all5.base4.ext4.size != ctypes.sizeof(FsExt4Api)
+                        or all5.ext5.magic != EXT5_MAGIC or all5.ext5.size != ctypes.sizeof(FsExt5Api)
+                        or all7.base6.ext6.magic != EXT6_MAGIC or all7.base6.ext6.size != ctypes.sizeof(FsExt6Api)
+                        or all7.ext7.magic != EXT7_MAGIC or all7.ext7.size != ctypes.sizeof(FsExt7Api)):
+                    raise RuntimeError(f"floodseg: the library's first eight hook tables are not the ones this binding knows ({name} is missing)")
+                ext8 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables8)).contents.ext8
+                if ext8.magic != EXT8_MAGIC:
+                    raise RuntimeError(f"floodseg: the library has no eighth extension table ({name} is missing)")
+                self._ext8 = ext8
+            member = getattr(FsExt8Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
+            if self._ext8.size < member.offset + member.size:
+                raise RuntimeError(f"floodseg: the library's eighth extension table is older than this binding ({name} is missing)")
+            fn = getattr(self._ext8, name[3:])
+            setattr(self, name, fn)
+            return fn
         if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT7_HOOKS):
             if self._ext7 is None:
                 all6 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables6)).contents
@@ -467,6 +508,11 @@ def ext6_hook_names():
 def ext7_hook_names():
     """Members of fs_ext7_api after `magic` and `size`, in declaration order."""
     return [h[0] for h in _EXT7_HOOKS]
+
+
+def ext8_hook_names():
+    """Members of fs_ext8_api after `magic` and `size`, in declaration order."""
+    return [h[0] for h in _EXT8_HOOKS]
 
 
 def check(rc):

@@ -543,7 +543,26 @@ static int fs_region_proximity(const uint8_t* mask, const uint32_t* d2, const in
                                        B, reinterpret_cast<long long*>(exposure), reinterpret_cast<long long*>(near), S(stream));
 }
 
-// the eight tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// the flood-extent mosaic (mosaic_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_global_motion(const int32_t* tables, const int32_t* pair_stats, const uint8_t* mask, uint32_t exclude_set, int n, int FH, int FW, int H, int W,
+                            int rounds, int64_t tol_q20, int min_inliers, int64_t* model, fs_stream stream) {
+    return fs::launch_global_motion(tables, pair_stats, mask, exclude_set, n, FH, FW, H, W, rounds, (long long)tol_q20, min_inliers,
+                                    reinterpret_cast<long long*>(model), S(stream));
+}
+static int fs_pose_chain(const int64_t* model, int64_t* state, int64_t* poses, int n, int H, int W, int CH, int CW, int ox, int oy, int max_bridge,
+                         fs_stream stream) {
+    return fs::launch_pose_chain(reinterpret_cast<const long long*>(model), reinterpret_cast<long long*>(state), reinterpret_cast<long long*>(poses), n, H, W,
+                                 CH, CW, ox, oy, max_bridge, S(stream));
+}
+static int fs_mosaic_accumulate(const uint8_t* mask, const int64_t* poses, int n, int H, int W, int K, int CH, int CW, int ox, int oy, uint16_t* votes,
+                                fs_stream stream) {
+    return fs::launch_mosaic_accumulate(mask, reinterpret_cast<const long long*>(poses), n, H, W, K, CH, CW, ox, oy, votes, S(stream));
+}
+static int fs_mosaic_resolve(const uint16_t* votes, int K, int CH, int CW, uint8_t* cls, uint8_t* conf, uint32_t* seen, int64_t* totals, fs_stream stream) {
+    return fs::launch_mosaic_resolve(votes, K, CH, CW, cls, conf, seen, reinterpret_cast<long long*>(totals), S(stream));
+}
+
+// the nine tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -644,8 +663,18 @@ static const fs_hook_tables5& hook_tables(void) {
         fs_mask_distance,
         fs_region_proximity,
     }};
+    // fs_ext7_api is frozen too (two members, 32 bytes; tests/test_distance_cpu.py); the ninth table lies behind it, and &all8.base7 is &all8.
+    static const fs_hook_tables8 all8 = {all7, {
+        FS_EXT8_MAGIC,
+        sizeof(fs_ext8_api),
+        fs_global_motion,
+        fs_pose_chain,
+        fs_mosaic_accumulate,
+        fs_mosaic_resolve,
+    }};
     {
-        const fs_hook_tables6& all6 = all7.base6;  // from here on the name means the head of the whole object, not the copy it was built from
+        const fs_hook_tables7& all7 = all8.base7;  // from here on both names mean the head of the whole object, not the copies it was built from
+        const fs_hook_tables6& all6 = all7.base6;
         return all6.base5;
     }
 }

@@ -395,6 +395,17 @@ int launch_region_proximity(const uint8_t* mask, const uint32_t* d2, const int32
                             int W, int K, int max_regions, uint32_t target_set, const int32_t* thresholds, int B, long long* exposure, long long* near,
                             hipStream_t s);
 
+// The flood-extent mosaic (mosaic_ops.hip, mosaic_defs.h; definitions: include/floodseg_test.h, global_motion, pose_chain,
+// mosaic_accumulate and mosaic_resolve).  The launchers refuse bad arguments before they launch anything.  pair_stats and mask may be
+// nullptr in launch_global_motion.  No workspace; nothing is allocated, synchronised or read on the host.
+int launch_global_motion(const int32_t* tables, const int32_t* pair_stats, const uint8_t* mask, uint32_t exclude_set, int n, int FH, int FW, int H, int W,
+                         int rounds, long long tol_q20, int min_inliers, long long* model, hipStream_t s);
+int launch_pose_chain(const long long* model, long long* state, long long* poses, int n, int H, int W, int CH, int CW, int ox, int oy, int max_bridge,
+                      hipStream_t s);
+int launch_mosaic_accumulate(const uint8_t* mask, const long long* poses, int n, int H, int W, int K, int CH, int CW, int ox, int oy, uint16_t* votes,
+                             hipStream_t s);
+int launch_mosaic_resolve(const uint16_t* votes, int K, int CH, int CW, uint8_t* cls, uint8_t* conf, uint32_t* seen, long long* totals, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

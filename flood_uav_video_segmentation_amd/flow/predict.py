@@ -38,6 +38,11 @@ water pixel of its frame, tabulated per class and per region (ops.mask_distance,
     exposure, near = p.proximity_report()                                  # [frames, K, B] pixels within each threshold; per frame [rows, 8]
     write_regions_csv("regions.csv", ids, rows, proximity=near)            # adds dist, near_px, nearest_region
     write_exposure_csv("exposure.csv", ids, exposure, (8, 16, 32), h * w)
+FlowPredictor(..., mosaic=(4096, 4096)) registers every frame's mask to the first frame through the camera's motion -- one robust affine
+per frame pair, fitted to the block matcher's vectors -- and accumulates the masks into one extent map in which each piece of ground is
+counted once (ops.global_motion, ops.pose_chain, ops.mosaic_accumulate, ops.mosaic_resolve):
+    cls, conf, seen, totals, poses = p.mosaic_report()                     # the mosaic mask, its confidence, votes, class areas, poses
+    write_mosaic_csv("mosaic.csv", ids, poses, totals)
 """
 import numpy as np
 import torch
@@ -136,7 +141,18 @@ class FlowPredictor:
     pixels from every source then reports min_d2 = -1, "not within R", and no scan is longer than R steps.  None or 0: unbounded, every
     region of a frame with a source gets its distance; a frame whose only source is a speck then costs a scan of up to the frame's
     width per pixel (measured at 7.4 ms for a 1072 x 1920 five-frame window against 0.18 ms on a flood scene and 0.45 ms at R = 32;
-    DESIGN §3.17).  The thresholds and the class choices are guesses, NOT validated on real video."""
+    DESIGN §3.17).  The thresholds and the class choices are guesses, NOT validated on real video.
+
+    mosaic=(CH, CW) (extension; None: off, and none of its ops is ever called; it does not need regions=True): the flood-extent mosaic
+    of DESIGN §3.18.  Every window must come with link_mvs and link_frame_size (and optionally link_stats), as for compensate=True.  The
+    masks handed out -- after the stabiliser and the despeckle -- vote, per frame, into a uint16 canvas [mosaic_classes, CH, CW] that
+    lives on the device with the pose chain's state; the first frame predicted is the anchor, placed with its top-left corner at
+    mosaic_origin = (oy, ox) (None: centred).  ops.global_motion fits each pair's model with mosaic_rounds, mosaic_tol and
+    mosaic_min_inliers, leaving out the blocks whose centre lies on a class of mosaic_exclude (default (1,), water: it moves on its
+    own); up to mosaic_bridge failed pairs running are bridged with the last good model, after which -- or at a scene cut -- the chain is
+    lost and the frames vote nowhere.  mosaic_report() resolves the canvas and reads back once; clear_report() drops canvas and state
+    (the next frame anchors a new mosaic), reset() keeps them.  All these defaults are guesses, NOT validated on real video; an affine
+    per pair is not a homography, the chain drifts over a long flight and nothing closes loops."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
 
@@ -144,7 +160,8 @@ class FlowPredictor:
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
                  max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False, outlines=False, max_contours=4096,
                  max_vertices=32768, simplify=None, simplify_rounds=32, keep_window_regions=False, stabilize=None, stabilize_trust=None,
-                 stabilize_compensate=False, proximity=None, proximity_sources=(1,), proximity_targets=(3, 4), proximity_max=None):
+                 stabilize_compensate=False, proximity=None, proximity_sources=(1,), proximity_targets=(3, 4), proximity_max=None, mosaic=None,
+                 mosaic_classes=None, mosaic_rounds=4, mosaic_tol=1.0, mosaic_min_inliers=12, mosaic_exclude=(1,), mosaic_bridge=2, mosaic_origin=None):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -252,6 +269,38 @@ class FlowPredictor:
         self.proximity_targets = tuple(int(c) for c in proximity_targets)
         self.proximity_max = int(proximity_max or 0) if self.proximity else 0
         self._proximity_chunks = []  # (int64 [REPORT_CHUNK, K, B] exposure, int64 [REPORT_CHUNK, max_regions, 8] near), in step with _region_chunks
+        self.mosaic = None
+        self.mosaic_classes = self.classes if mosaic_classes is None else int(mosaic_classes)
+        if mosaic is not None:
+            size = tuple(int(v) for v in mosaic)
+            if len(size) != 2 or any(not 1 <= v <= 16384 for v in size):
+                raise ValueError(f"FlowPredictor: mosaic must be the canvas size (CH, CW) with 1..16384 pixels a side, got {mosaic}")
+            if not 1 <= self.mosaic_classes <= 32:
+                raise ValueError(f"FlowPredictor: mosaic_classes must be 1..32, got {self.mosaic_classes}")
+            if not 0 <= int(mosaic_rounds) <= 8:
+                raise ValueError(f"FlowPredictor: mosaic_rounds must be 0..8, got {mosaic_rounds}")
+            if not 0 <= float(mosaic_tol) <= 64:
+                raise ValueError(f"FlowPredictor: mosaic_tol must be 0..64 frame pixels, got {mosaic_tol}")
+            if not 3 <= int(mosaic_min_inliers) <= 1 << 20:
+                raise ValueError(f"FlowPredictor: mosaic_min_inliers must be 3..2^20, got {mosaic_min_inliers}")
+            ops.class_set(mosaic_exclude, "mosaic_exclude", "FlowPredictor", allow_empty=True)
+            if not 0 <= int(mosaic_bridge) <= 64:
+                raise ValueError(f"FlowPredictor: mosaic_bridge must be 0..64 frame pairs, got {mosaic_bridge}")
+            if mosaic_origin is not None and (len(tuple(mosaic_origin)) != 2 or any(abs(int(v)) > 16384 for v in mosaic_origin)):
+                raise ValueError(f"FlowPredictor: mosaic_origin must be (oy, ox) within 16384 pixels of the canvas corner (None: the anchor frame is "
+                                 f"centred), got {mosaic_origin}")
+            self.mosaic = size
+        self.mosaic_rounds = int(mosaic_rounds)
+        self.mosaic_tol = float(mosaic_tol)
+        self.mosaic_min_inliers = int(mosaic_min_inliers)
+        self.mosaic_exclude = tuple(int(c) for c in mosaic_exclude)
+        self.mosaic_bridge = int(mosaic_bridge)
+        self.mosaic_origin = None if mosaic_origin is None else tuple(int(v) for v in mosaic_origin)
+        self._mosaic_votes = None   # uint16 [K, CH, CW] on the device, with the chain's state int64 [32] and the origin in use
+        self._mosaic_state = None
+        self._mosaic_at = None
+        self._mosaic_chunks = []    # int64 [REPORT_CHUNK, 16] device buffers of the per-frame pose rows, in frame order
+        self._mosaic_frames = 0
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
@@ -278,6 +327,9 @@ class FlowPredictor:
         self._stabilize_chunks = []  # the state plane stays
         self._stabilize_frames = 0
         self._proximity_chunks = []
+        self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
+        self._mosaic_chunks = []
+        self._mosaic_frames = 0
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -360,11 +412,54 @@ class FlowPredictor:
         """What _link_inputs returned, for the tracks: theirs only under compensate=True (stabilize_compensate=True alone leaves them in place)."""
         return link if self.compensate else None
 
+    def _keep_mosaic(self, masks, link):
+        """The window's masks into the vote canvas: one camera-motion model per frame pair from the window's tables, the pose chain carried
+        on in its device state, the gather, and the pose rows into the next rows of the chunked buffers (nothing is read back)."""
+        masks = masks.contiguous()
+        n, h, w = masks.shape
+        dev = masks.device
+        if self._mosaic_votes is None:
+            ch, cw = self.mosaic
+            self._mosaic_votes = torch.zeros((self.mosaic_classes, ch, cw), dtype=torch.int16, device=dev).view(torch.uint16)  # the same zero bits
+            self._mosaic_state = torch.zeros((32,), dtype=torch.int64, device=dev)
+            self._mosaic_at = self.mosaic_origin if self.mosaic_origin is not None else ((ch - h) // 2, (cw - w) // 2)
+        model = ops.global_motion(link[0], link[1], (h, w), self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks,
+                                  exclude=self.mosaic_exclude, pair_stats=link[2])
+        poses = ops.pose_chain(model, self._mosaic_state, (h, w), self.mosaic, self._mosaic_at, self.mosaic_bridge)
+        ops.mosaic_accumulate(masks, poses, self._mosaic_votes, self._mosaic_at)
+        done = 0
+        while done < n:
+            row = self._mosaic_frames % self.REPORT_CHUNK
+            if row == 0:
+                self._mosaic_chunks.append(torch.zeros((self.REPORT_CHUNK, 16), dtype=torch.int64, device=dev))
+            take = min(n - done, self.REPORT_CHUNK - row)
+            self._mosaic_chunks[-1][row:row + take].copy_(poses[done:done + take])
+            done += take
+            self._mosaic_frames += take
+
+    def mosaic_report(self):
+        """mosaic=(CH, CW): (cls, conf, seen, totals, poses) of the frames predicted since the start (or clear_report()): cls uint8 numpy
+        [CH, CW], the class most frames saw at each piece of ground (255: never seen); conf uint8, that class's share of the votes as a
+        code 0..255; seen int32, the number of votes; totals int64 [K, 2], per class the canvas pixels and the votes; poses int64
+        [frames, 16], per frame to_anchor (6) and from_anchor (6) in Q20, status (0 ok, 1 bridged, 2 lost), clipped, inliers, usable rows.
+        The resolve pass runs here, and so does the ONE read-back."""
+        k = self.mosaic_classes
+        if self._mosaic_votes is None:
+            ch, cw = self.mosaic or (0, 0)
+            return (np.full((ch, cw), 255, np.uint8), np.zeros((ch, cw), np.uint8), np.zeros((ch, cw), np.int32), np.zeros((k, 2), np.int64),
+                    np.zeros((0, 16), np.int64))
+        cls, conf, seen, totals = ops.mosaic_resolve(self._mosaic_votes)
+        poses = torch.cat(self._mosaic_chunks)[:self._mosaic_frames]
+        return cls.cpu().numpy(), conf.cpu().numpy(), seen.cpu().numpy(), totals.cpu().numpy(), poses.cpu().numpy()
+
     def _link_inputs(self, n, link_mvs, link_frame_size, link_stats):
         """compensate=True or stabilize_compensate=True: the window's (mvs [n, blocks, 7], frame size, stats [n, 4] or None), checked;
         None otherwise."""
-        if not self.compensate and not self.stabilize_compensate:
+        if not self.compensate and not self.stabilize_compensate and not self.mosaic:
             return None
+        if (link_mvs is None or link_frame_size is None) and not self.compensate and not self.stabilize_compensate:
+            raise ValueError("FlowPredictor: mosaic=(CH, CW) needs link_mvs and link_frame_size with every window (an estimate-mode dataset with "
+                             "link_vectors=True provides them); the camera's motion is never taken as zero instead")
         if (link_mvs is None or link_frame_size is None) and not self.compensate:
             raise ValueError("FlowPredictor: stabilize_compensate=True needs link_mvs and link_frame_size with every window (an estimate-mode dataset "
                              "with link_vectors=True provides them); the state is never read in place instead")
@@ -574,6 +669,8 @@ class FlowPredictor:
         self._score(masks, n)
         if self.regions:
             self._keep_regions(masks, conf, self._track_link(link))
+        if self.mosaic:
+            self._keep_mosaic(masks, link)
         if not self.confidence:
             return masks.cpu().numpy() if to_host else masks            # :277
         self._keep_report(masks, conf)
@@ -840,6 +937,31 @@ def write_exposure_csv(path, frame_ids, exposure, thresholds, frame_pixels):
             for pixels in rows.reshape(-1).tolist():
                 cells += [str(pixels), f"{pixels / frame_pixels:.6f}"]
             f.write(",".join(cells) + "\n")
+
+
+MOSAIC_STATUS = ("ok", "bridged", "lost")
+
+
+def write_mosaic_csv(path, frame_ids, poses, totals):
+    """FlowPredictor.mosaic_report()'s poses int64 [frames, 16] and totals int64 [K, 2] as one CSV of two tables.  First one row per
+    frame: frame id, status (ok, bridged, lost), clipped (1: a corner of the frame lies outside the canvas), inliers and usable rows of
+    the pair's fit, and the pose m00 .. m12 that takes a mask pixel of the frame to the anchor frame's pixels (empty for a lost frame).
+    Then, after an empty line, one row per class: the canvas pixels it won, their share of the seen pixels, and its votes.  Pixels are
+    mask pixels of the anchor frame, not metres."""
+    poses, totals = np.asarray(poses), np.asarray(totals)
+    if poses.ndim != 2 or poses.shape[1] != 16 or len(frame_ids) != poses.shape[0] or totals.ndim != 2 or totals.shape[1] != 2:
+        raise ValueError(f"write_mosaic_csv: poses must be [frames, 16] with one frame id per row and totals [K, 2], got {poses.shape}, {len(frame_ids)} "
+                         f"ids and {totals.shape}")
+    seen = int(totals[:, 0].sum())
+    with open(path, "w", newline="") as f:
+        f.write("frame,status,clipped,inliers,usable,m00,m01,m02,m10,m11,m12\n")
+        for fid, row in zip(frame_ids, poses.tolist()):
+            status = row[12] if 0 <= row[12] <= 2 else 2
+            pose = [f"{v / (1 << 20):.6f}" for v in row[:6]] if status != 2 else [""] * 6
+            f.write(",".join([str(int(fid)), MOSAIC_STATUS[status], str(row[13]), str(row[14]), str(row[15])] + pose) + "\n")
+        f.write("\nclass,pixels,share,votes\n")
+        for k, (pixels, votes) in enumerate(totals.tolist()):
+            f.write(f"{k},{pixels},{pixels / seen if seen else 0.0:.6f},{votes}\n")
 
 
 def _distance_cell(min_d2):

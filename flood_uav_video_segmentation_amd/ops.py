@@ -902,6 +902,137 @@ def region_proximity(mask, d2, nearest, index, counts, classes, max_regions, tar
     return exposure, near
 
 
+# ------------------------------------------------------------------------------------------ the flood-extent mosaic
+POSE_ONE = 1 << 20  # 1 << FS_POSE_FRAC: poses and pair models are Q20
+MOSAIC_MAX_SIDE = 16384
+
+
+def _mosaic_size(size, name, what, lo=1):
+    h, w = (int(v) for v in size)
+    if not lo <= h <= MOSAIC_MAX_SIDE or not lo <= w <= MOSAIC_MAX_SIDE:
+        raise ValueError(f"{what}: {name} must be (H, W) with {lo}..{MOSAIC_MAX_SIDE} pixels a side, got {tuple(size)}")
+    return h, w
+
+
+def _mosaic_origin(origin, what):
+    oy, ox = (int(v) for v in origin)
+    if abs(oy) > MOSAIC_MAX_SIDE or abs(ox) > MOSAIC_MAX_SIDE:
+        raise ValueError(f"{what}: origin must be (oy, ox) within {MOSAIC_MAX_SIDE} pixels of the canvas corner, got {tuple(origin)}")
+    return oy, ox
+
+
+def _mosaic_rows(t, name, what, n=None):
+    if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 16 or not 1 <= t.shape[0] <= 64 or (n is not None and t.shape[0] != n):
+        raise ValueError(f"{what}: {name} must be int64 [{'n' if n is None else n},16] with n in 1..64, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def global_motion(tables, frame_size, mask_size, rounds=4, tol=1.0, min_inliers=12, mask=None, exclude=(), pair_stats=None):
+    """One robust affine camera-motion model per frame pair from the block matcher's tables (definition: include/floodseg_test.h,
+    global_motion): int32 tables [n,blocks,7] of frames of frame_size = (FH, FW) -> model int64 [n,16] = the forward affine
+    (mask pixel of frame f -> mask pixel of frame f-1; six Q20 values), its inverse, status (0 ok, 1 cut, 2 too few, 3 degenerate or
+    implausible), usable rows, inliers, rounds completed.  mask_size = (H, W) of the masks the model is for.  rounds 0..8 least-squares
+    rounds from the vectors' mode (0: the mode translation); tol: the last round's inlier tolerance in frame pixels (0..64), doubled per
+    round before it; min_inliers 3..2^20.  mask uint8 [n,H,W] with exclude = class ids 0..31: rows whose block centre lies on an excluded
+    class do not count (water moves on its own).  pair_stats int32 [n,4]: a pair flagged as a cut is not fitted.  One launch; nothing is
+    read back."""
+    lib = _lib.load()
+    what = "floodseg.global_motion"
+    fh, fw = _mosaic_size(frame_size, "frame_size", what, 16)
+    h, w = _mosaic_size(mask_size, "mask_size", what)
+    if not 0 <= int(rounds) <= 8:
+        raise ValueError(f"{what}: rounds must be 0..8, got {rounds}")
+    if not 0 <= float(tol) <= 64:
+        raise ValueError(f"{what}: tol must be 0..64 frame pixels, got {tol}")
+    if not 3 <= int(min_inliers) <= 1 << 20:
+        raise ValueError(f"{what}: min_inliers must be 3..2^20, got {min_inliers}")
+    bits = class_set(exclude, "exclude", what, allow_empty=True)
+    blocks = (fh // 16) * (fw // 16)
+    if tables.dtype != torch.int32 or tables.dim() != 3 or not 1 <= tables.shape[0] <= 64 or tuple(tables.shape[1:]) != (blocks, 7):
+        raise ValueError(f"{what}: tables must be int32 [n,{blocks},7] with n in 1..64 for frames of {fh}x{fw}, got {tables.dtype} {tuple(tables.shape)}")
+    n = tables.shape[0]
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (n, h, w)):
+        raise ValueError(f"{what}: mask must be uint8 [{n},{h},{w}], got {mask.dtype} {tuple(mask.shape)}")
+    if pair_stats is not None and (pair_stats.dtype != torch.int32 or tuple(pair_stats.shape) != (n, 4)):
+        raise ValueError(f"{what}: pair_stats must be int32 [{n},4], got {pair_stats.dtype} {tuple(pair_stats.shape)}")
+    dev = one_device(tables, mask, pair_stats, what=what)
+    with torch.cuda.device(dev):
+        model = torch.empty((n, 16), dtype=torch.int64, device=dev)
+        check(lib.fs_global_motion(ptr(tables.contiguous()), ptr(None if pair_stats is None else pair_stats.contiguous()),
+                                   ptr(None if mask is None else mask.contiguous()), bits, n, fh, fw, h, w, int(rounds), int(round(float(tol) * POSE_ONE)),
+                                   int(min_inliers), ptr(model), stream_ptr()))
+    return model
+
+
+def pose_chain(model, state, mask_size, canvas_size, origin, max_bridge=2):
+    """global_motion's pair models composed into poses relative to the mosaic's anchor frame (definition: include/floodseg_test.h,
+    pose_chain): model int64 [n,16], state int64 [32] (all zero: fresh; UPDATED IN PLACE, carry it from window to window) -> poses int64
+    [n,16] = to_anchor (6), from_anchor (6), status (0 ok, 1 bridged, 2 lost), clipped, inliers, usable rows.  canvas_size = (CH, CW),
+    origin = (oy, ox), the canvas pixel of the anchor's top-left corner; max_bridge 0..64 failed pairs running are bridged with the last
+    good pair's model.  One launch of one wave; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.pose_chain"
+    h, w = _mosaic_size(mask_size, "mask_size", what)
+    ch, cw = _mosaic_size(canvas_size, "canvas_size", what)
+    oy, ox = _mosaic_origin(origin, what)
+    if not 0 <= int(max_bridge) <= 64:
+        raise ValueError(f"{what}: max_bridge must be 0..64, got {max_bridge}")
+    model = _mosaic_rows(model, "model", what)
+    if state.dtype != torch.int64 or tuple(state.shape) != (32,) or not state.is_contiguous():
+        raise ValueError(f"{what}: state must be a contiguous int64 [32] tensor, got {state.dtype} {tuple(state.shape)}")
+    dev = one_device(model, state, what=what)
+    with torch.cuda.device(dev):
+        poses = torch.empty((model.shape[0], 16), dtype=torch.int64, device=dev)
+        check(lib.fs_pose_chain(ptr(model), ptr(state), ptr(poses), model.shape[0], h, w, ch, cw, ox, oy, int(max_bridge), stream_ptr()))
+    return poses
+
+
+def _mosaic_votes(votes, what):
+    if votes.dtype != torch.uint16 or votes.dim() != 3 or not 1 <= votes.shape[0] <= 32 or not votes.is_contiguous():
+        raise ValueError(f"{what}: votes must be a contiguous uint16 [K,CH,CW] tensor with K in 1..32, got {votes.dtype} {tuple(votes.shape)}")
+    _mosaic_size(votes.shape[1:], "the canvas", what)
+    return votes
+
+
+def mosaic_accumulate(mask, poses, votes, origin):
+    """The masks of n frames gathered into the vote canvas (definition: include/floodseg_test.h, mosaic_accumulate): uint8 mask [n,H,W],
+    pose_chain's poses int64 [n,16], votes uint16 [K,CH,CW] UPDATED IN PLACE (and returned): every canvas pixel looks up, per frame that
+    is not lost, the frame pixel under its centre and gives that pixel's class one vote, saturating at 65535.  origin = (oy, ox).  One
+    launch that costs the frames' footprint, not the canvas; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.mosaic_accumulate"
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise ValueError(f"{what}: mask must be uint8 [n,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    n = mask.shape[0]
+    h, w = _mosaic_size(mask.shape[1:], "the mask", what)
+    poses = _mosaic_rows(poses, "poses", what, n)
+    votes = _mosaic_votes(votes, what)
+    oy, ox = _mosaic_origin(origin, what)
+    dev = one_device(mask, poses, votes, what=what)
+    with torch.cuda.device(dev):
+        check(lib.fs_mosaic_accumulate(ptr(mask.contiguous()), ptr(poses), n, h, w, votes.shape[0], votes.shape[1], votes.shape[2], ox, oy, ptr(votes),
+                                       stream_ptr()))
+    return votes
+
+
+def mosaic_resolve(votes):
+    """The vote canvas read out (definition: include/floodseg_test.h, mosaic_resolve): votes uint16 [K,CH,CW] -> (cls uint8 [CH,CW]: the
+    class with the most votes, the lowest id on a tie, 255 where unseen; conf uint8: the winner's share of the votes as a code 0..255;
+    seen int32 [CH,CW]: the votes; totals int64 [K,2]: per class the canvas pixels won and the votes received).  Nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.mosaic_resolve"
+    votes = _mosaic_votes(votes, what)
+    dev = one_device(votes, what=what)
+    k, ch, cw = votes.shape
+    with torch.cuda.device(dev):
+        cls = torch.empty((ch, cw), dtype=torch.uint8, device=dev)
+        conf = torch.empty((ch, cw), dtype=torch.uint8, device=dev)
+        seen = torch.empty((ch, cw), dtype=torch.int32, device=dev)
+        totals = torch.empty((k, 2), dtype=torch.int64, device=dev)
+        check(lib.fs_mosaic_resolve(ptr(votes), k, ch, cw, ptr(cls), ptr(conf), ptr(seen), ptr(totals), stream_ptr()))
+    return cls, conf, seen, totals
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

@@ -869,6 +869,113 @@ typedef struct fs_hook_tables7 {
     fs_ext7_api ext7;
 } fs_hook_tables7;
 
+/* ---- The NINTH table.  fs_ext7_api is frozen as well (2 members, 32 bytes; tests/test_distance_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables7 by the same pattern:
+ *     const fs_hook_tables8* t = (const fs_hook_tables8*)fs_test_hooks();   t->ext8.global_motion(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables7: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext8.magic == FS_EXT8_MAGIC and ext8.size >= the end of the member it needs. */
+#define FS_EXT8_MAGIC 0x4653455854414238ull /* "FSEXTAB8" */
+#define FS_POSE_FRAC 20                     /* poses and pair models are Q20: ONE = 1 << 20 */
+
+typedef struct fs_ext8_api {
+    uint64_t magic; /* FS_EXT8_MAGIC */
+    size_t size;    /* sizeof(fs_ext8_api) of the library that was built */
+
+    /* ---- THE FLOOD-EXTENT MOSAIC (csrc/mosaic_ops.hip, csrc/mosaic_defs.h).  OUR DEFINITION: the reference has nothing
+     * like it.  Four ops: a robust affine camera-motion fit per frame pair from the block matcher's table, a pose chain kept across
+     * windows, a per-class vote canvas that masks are gathered into, and a resolve pass.  Integers wherever possible; every result is a
+     * function of the inputs alone, whatever order threads arrive in.  Fixed point: ONE = 1 << FS_POSE_FRAC;
+     * rshr(v) = (v + (1 << 19)) >> 20 on int64 with an arithmetic shift.  An affine is six int64 (m00, m01, m02, m10, m11, m12) in Q20,
+     * x' = m00 x + m01 y + m02, acting on continuous pixel coordinates in which pixel i covers [i, i + 1).  The same rules as code:
+     * csrc/mosaic_defs.h (host and device) and tests/mosaic_ref.py (numpy).
+     *
+     * global_motion fits one model per frame pair.  Inputs:
+     *   tables      int32 [n][blocks][7], the matcher's rows (-1, 16, 16, src_x, src_y, dst_x, dst_y), blocks = (FH / 16) * (FW / 16);
+     *   pair_stats  int32 [n][4] or NULL: word 2 non-zero = the pair is a scene cut;
+     *   mask        uint8 [n][H][W] or NULL, with exclude_set (bit k set = class k is excluded; ids >= 32 never are);
+     *   rounds 0..8, tol_q20 0..64 ONE, min_inliers 3..2^20.
+     * A row is USABLE if src_x >= 0 (not void), its block centre lies in the frame (0 <= dst_x < FW, 0 <= dst_y < FH: the matcher writes no
+     * other), |dx|, |dy| <= 32 with dx = src_x - dst_x, dy = src_y - dst_y, and, with a mask, the class at
+     * mask[f][min(H - 1, dst_y H / FH)][min(W - 1, dst_x W / FW)] (floor divisions) is not excluded.  Block coordinates with hb = FH / 16,
+     * wb = FW / 16: p = 2 (dst_x >> 4) + 1 - wb, q = 2 (dst_y >> 4) + 1 - hb: units of 8 pixels about the centre of the block grid.
+     * The model is dx ~ a0 + a1 p + a2 q, dy ~ b0 + b1 p + b2 q, six Q20 int64.
+     * START: the 65 x 65 histogram of the usable (dy, dx); its mode is the largest count, then the smallest |dx| + |dy|, then the smallest
+     * dy, then the smallest dx (the matcher's own order); the start model is that translation with zero slopes.
+     * ROUNDS: in round r = 0 .. rounds - 1 the tolerance is T = min(tol_q20 << (rounds - 1 - r), 64 ONE); the inliers are the usable rows
+     * with |dx ONE - pred_x| <= T and |dy ONE - pred_y| <= T under the current model (integer comparisons); twelve int64 sums over them
+     * (N, Sp, Sq, Spp, Spq, Sqq, Sdx, Spdx, Sqdx, Sdy, Spdy, Sqdy); the next model is gm_solve's (mosaic_defs.h): the 3 x 3 normal equations
+     * by Cramer's rule in float64, the order of operations written out there, no fused multiply-add, each parameter rounded to Q20 to
+     * nearest, ties to even.  A round with N < min_inliers, or one whose determinant gm_solve computes as 0 or whose solution holds a
+     * parameter that is not a finite number below 2^20 pixels, stops the rounds: in round 0 the pair fails (too few / degenerate), later
+     * the model of the round before stands.  rounds = 0 is the mode translation.  A pair with fewer than min_inliers usable rows fails as
+     * too few whatever the rounds.
+     * CONVERSION (gm_finish): in frame pixels x_prev = x + a0 + a1 (x - 8 wb) / 8 + a2 (y - 8 hb) / 8 (y alike); scaled to mask pixels
+     * (m01 *= (W FH) / (FW H), m10 *= (H FW) / (FH W), m02 *= W / FW, m12 *= H / FH) in float64 and rounded once to Q20; the inverse affine
+     * in float64 from the QUANTISED forward model, rounded once.  A pair is implausible and fails as degenerate if any of |m00 - ONE|,
+     * |m11 - ONE|, |m01|, |m10| exceeds ONE / 4 (or a translation reaches 2^16 pixels, which keeps the chain's products in 63 bits).
+     * A pair whose pair_stats row has the cut flag set fails as a cut without being fitted.
+     * Output model int64 [n][16]: forward affine (6), inverse affine (6), status (0 ok, 1 cut, 2 too few, 3 degenerate or implausible),
+     * usable rows, inliers of the last completed round (the mode's count until a round completes), rounds completed.  On failure the
+     * twelve parameters are the identity.
+     * ONE launch: a workgroup of 1024 threads per pair; rows in a strided loop; the histogram in LDS (65 x 65 dwords, LDS atomics); the
+     * mode by a wave-then-workgroup maximum of a packed key; per round a classification and twelve sums reduced by shuffles, then across
+     * the waves in LDS; one thread solves and broadcasts through LDS.  No global atomics, no workspace, nothing between workgroups; the
+     * table is re-read (from L2) each round, 28 B x blocks.
+     * Refused before a launch: a null tables or model; n outside 1..64; FH or FW outside 16..16384; H or W outside 1..16384; rounds, tol_q20
+     * or min_inliers out of range; tables or pair_stats not aligned to 4 bytes, model not aligned to 8. */
+    int (*global_motion)(const int32_t* tables, const int32_t* pair_stats, const uint8_t* mask, uint32_t exclude_set, int n, int FH, int FW, int H, int W,
+                         int rounds, int64_t tol_q20, int min_inliers, int64_t* model, fs_stream stream);
+
+    /* ---- pose_chain composes the pair models into poses relative to the ANCHOR, the first frame of the mosaic.
+     * compose(A, B) = A o B: c00 = rshr(a00 b00 + a01 b10), c01 = rshr(a00 b01 + a01 b11), c02 = rshr(a00 b02 + a01 b12) + a02, row 1 alike:
+     * exact int64.  state int64 [32] on the device, read and written, lasts across calls; all zero = fresh.  It holds to_anchor (6),
+     * from_anchor (6), last_fwd (6), last_inv (6), a phase (0 fresh, 1 tracking, 2 lost), the frames seen, the frames lost, the length of
+     * the current bridge run, and four spare words.
+     * Frames are walked in order.  From a fresh state the first frame is the anchor: its pose is the identity, its own model row is
+     * ignored (its table relates it to a frame outside the mosaic), and the last good pair starts as the identity.  Otherwise a model
+     * with status 0 gives to_anchor = compose(to_anchor, fwd), from_anchor = compose(inv, from_anchor) and becomes the last good pair.  A
+     * model with status 2 or 3 (or any status that is none of 0..3, or a status-0 row whose entries exceed the pair bounds of
+     * mosaic_defs.h) is BRIDGED: the last good pair's model is used in its place, for at most max_bridge pairs running.  A cut, or a bridge
+     * run that is exhausted, makes the chain LOST; lost is sticky until the caller hands in a fresh state.  A frame whose composed
+     * |to_anchor translation| >= 2^14 ONE is lost as well (so is one whose linear entries reach 16 in either direction, or whose
+     * from_anchor translation reaches 2^20 ONE): these bounds keep every later product inside 63 bits; the derivation is in mosaic_defs.h.
+     * Output poses int64 [n][16]: to_anchor (6), from_anchor (6), status (0 ok, 1 bridged, 2 lost), clipped (1 if any of the frame's four
+     * corners (0, 0), (W, 0), (0, H), (W, H) under to_anchor plus the origin (ox, oy) falls outside [0, CW] x [0, CH]), inliers, usable rows
+     * (both copied from the model row; 0 for the anchor).  A lost frame's row holds identities, clipped 0.
+     * ONE launch of one wave; lane 0 walks the n <= 64 frames.
+     * Refused before a launch: a null pointer; n outside 1..64; H, W, CH or CW outside 1..16384; |ox| or |oy| > 16384; max_bridge outside
+     * 0..64; a pointer not aligned to 8 bytes. */
+    int (*pose_chain)(const int64_t* model, int64_t* state, int64_t* poses, int n, int H, int W, int CH, int CW, int ox, int oy, int max_bridge,
+                      fs_stream stream);
+
+    /* ---- mosaic_accumulate gathers n masks into the vote canvas.  votes uint16 [K][CH][CW], K <= 32, updated in place; (ox, oy) = the
+     * canvas pixel of the anchor frame's top-left corner.  For canvas pixel (X, Y) and each frame f that is not lost (status 0 or 1, and a
+     * from_anchor inside the pose bounds), in order: AX = (2 (X - ox) + 1) << 19, AY alike; sx = rshr(f00 AX + f01 AY) + f02, sy alike, with
+     * from_anchor; x = sx >> 20, y = sy >> 20 (floor); if 0 <= x < W, 0 <= y < H and k = mask[f][y][x] < K then
+     * votes[k][Y][X] = min(votes[k][Y][X] + 1, 65535).  A lost frame votes nowhere.  A gather with nearest sampling: every canvas pixel has
+     * one owner, so there are no atomics, no holes under zoom and no dependence on order.
+     * ONE launch: a workgroup per 64 x 16 canvas tile maps the tile's four corners through every live frame's from_anchor and drops the
+     * frames whose bounding box cannot touch the frame (one pixel of slack covers the rounding); a tile that no frame touches reads and
+     * writes nothing more, so a window costs its footprint, not the canvas.
+     * Refused before a launch: a null pointer; n outside 1..64; H, W, CH or CW outside 1..16384; K outside 1..32; |ox| or |oy| > 16384;
+     * poses not aligned to 8 bytes, votes not aligned to 2. */
+    int (*mosaic_accumulate)(const uint8_t* mask, const int64_t* poses, int n, int H, int W, int K, int CH, int CW, int ox, int oy, uint16_t* votes,
+                             fs_stream stream);
+
+    /* ---- mosaic_resolve reads the canvas.  Outputs, each written whole: cls uint8 [CH][CW] = the class with the most votes, the lowest id
+     * on a tie, 255 where there are none; conf uint8 = (255 max + total / 2) / total, 0 where unseen; seen uint32 = the total;
+     * totals int64 [K][2] = per class the canvas pixels won and the votes received.
+     * TWO launches: totals cleared; one pass, an LDS histogram per workgroup flushed with one 64-bit atomic per non-zero cell.
+     * Refused before a launch: a null pointer; K outside 1..32; CH or CW outside 1..16384; votes not aligned to 2 bytes, seen to 4,
+     * totals to 8. */
+    int (*mosaic_resolve)(const uint16_t* votes, int K, int CH, int CW, uint8_t* cls, uint8_t* conf, uint32_t* seen, int64_t* totals, fs_stream stream);
+} fs_ext8_api;
+
+typedef struct fs_hook_tables8 {
+    fs_hook_tables7 base7;
+    fs_ext8_api ext8;
+} fs_hook_tables8;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

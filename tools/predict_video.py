@@ -79,6 +79,16 @@ to R >= the largest PX pixels (regions further away then have an empty `dist`); 
 frame's width per pixel where water is a single speck.  Distances
 are mask pixels of a moving, un-georeferenced camera -- no metres follow from them -- and the thresholds are guesses, not validated on
 real video.
+`--mosaic FILE.png` (an extension; needs estimated grids: `--raw`, or `--grids estimate`; one process) registers every
+frame's mask to the first frame through the camera's motion -- one robust affine per frame pair, fitted on the device to the block
+matcher's vectors, without the blocks that lie on the classes of `--mosaic-exclude` (default 1, water) -- and accumulates the masks
+into one extent map of `--mosaic-size H W` pixels (default: twice the output size), in which each piece of ground is counted once.  The
+PNG shows, in the palette's colours, the class most frames saw at each pixel, black where no frame looked.  `--mosaic-rounds N` (0..8,
+default 4) and `--mosaic-tol PX` (default 1.0 frame pixels) steer the fit.  `--mosaic-report FILE.csv` lists per frame the pose, its
+status (ok, bridged, lost), whether the frame left the canvas, and the fit's inliers and usable blocks, then per class the canvas
+pixels and their share of the ground seen.  A scene cut ends the chain: the frames after it are reported as lost.  The defaults are
+guesses, not validated on real video; an affine per pair is not a homography, the chain drifts over a long flight and nothing closes
+loops; areas are pixels of the first frame, not metres.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -98,7 +108,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_exposure_csv, write_extent_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_exposure_csv, write_extent_csv, write_mosaic_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -210,6 +220,15 @@ def parse_args(argv=None):
     ap.add_argument("--proximity-max", type=int, default=None, metavar="R", help="--proximity: search no further than R pixels, R at least the largest "
                     "PX (default: unbounded)")
     ap.add_argument("--exposure", default=None, metavar="FILE.csv", help="--proximity: one row per frame, per target class the pixels within each PX")
+    ap.add_argument("--mosaic", default=None, metavar="FILE.png", help="register every frame's mask to the first frame through the camera's motion "
+                    "(estimated grids only) and write the accumulated extent map, each piece of ground counted once.  Not validated on real video")
+    ap.add_argument("--mosaic-size", type=int, nargs=2, default=None, metavar=("H", "W"), help="--mosaic: the canvas (default: twice --size)")
+    ap.add_argument("--mosaic-exclude", type=int, nargs="*", default=[1], metavar="K", help="--mosaic: blocks on these classes do not vote on the "
+                    "camera's motion (default 1, water)")
+    ap.add_argument("--mosaic-rounds", type=int, default=4, metavar="N", help="--mosaic: least-squares rounds of the motion fit (0..8; 0: the vectors' mode)")
+    ap.add_argument("--mosaic-tol", type=float, default=1.0, metavar="PX", help="--mosaic: inlier tolerance of the last round in frame pixels (0..64)")
+    ap.add_argument("--mosaic-report", default=None, metavar="FILE.csv", help="--mosaic: per frame the pose, status, clipped flag, inliers and usable "
+                    "blocks; per class the canvas pixels and their share of the ground seen")
     ap.add_argument("--draw-outlines", type=int, nargs="?", const=1, default=None, metavar="W", help="--raw-out with --regions: draw a white line W "
                     "pixels wide (0..4, default 1) along the inside of every region's boundary")
     ap.add_argument("--draw-tracks", action="store_true", help="--raw-out with --regions and --tracks: fill every region in a colour picked by its track id")
@@ -246,6 +265,16 @@ def parse_args(argv=None):
         ap.error("--compensate needs --tracks: it changes how the tracks' links are counted")
     if args.compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
         ap.error("--compensate needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
+    if not args.mosaic and (args.mosaic_size is not None or args.mosaic_report):
+        ap.error("--mosaic-size and --mosaic-report need --mosaic FILE.png")
+    if args.mosaic and (args.grids == "files" or (not args.raw and args.grids is None)):
+        ap.error("--mosaic needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
+    if args.mosaic and args.no_warp:
+        ap.error("--mosaic needs the block matcher's vectors: --no-warp estimates none")
+    if args.mosaic_size is not None and any(not 1 <= v <= 16384 for v in args.mosaic_size):
+        ap.error("--mosaic-size takes H W of 1..16384 pixels")
+    if not 0 <= args.mosaic_rounds <= 8 or not 0 <= args.mosaic_tol <= 64 or any(not 0 <= k <= 31 for k in args.mosaic_exclude):
+        ap.error("--mosaic-rounds takes 0..8, --mosaic-tol 0..64 pixels and --mosaic-exclude class ids 0..31")
     if args.proximity is not None and not args.regions:
         ap.error("--proximity needs --regions: the distances are tabulated per region")
     if args.proximity is None and (args.exposure or args.proximity_max is not None):
@@ -324,6 +353,9 @@ def main():
     fm = FlowModel(net, feature_based=args.feature_based, no_warp=args.no_warp).eval()
     if args.tracks and world > 1:
         raise SystemExit("--tracks: track ids are per predictor and joining the ranks' blocks is out of scope: run it in a single process")
+    if args.mosaic and world > 1:
+        raise SystemExit("--mosaic: every rank's pose chain would be its own and merging the ranks' mosaics is out of scope: run it in a single process")
+    mosaic_size = None if not args.mosaic else tuple(args.mosaic_size) if args.mosaic_size else (min(2 * args.size[0], 16384), min(2 * args.size[1], 16384))
     draw = args.draw_outlines is not None or args.draw_tracks or args.draw_ids is not None
     pred = FlowPredictor(fm, classes=args.classes, out_size=tuple(args.size), crop=None if args.no_cropping else tuple(args.crop),
                          compute_metrics=not args.no_metrics, cache_keyframes=not args.no_keyframe_cache, confidence=args.confidence,
@@ -333,18 +365,19 @@ def main():
                          max_vertices=args.max_vertices, simplify=args.simplify, simplify_rounds=args.simplify_rounds, keep_window_regions=draw,
                          stabilize=args.stabilize, stabilize_trust=args.stabilize_trust, stabilize_compensate=args.stabilize_compensate,
                          proximity=args.proximity, proximity_sources=args.proximity_sources, proximity_targets=args.proximity_targets,
-                         proximity_max=args.proximity_max)
+                         proximity_max=args.proximity_max, mosaic=mosaic_size, mosaic_classes=min(args.classes, 32), mosaic_rounds=args.mosaic_rounds,
+                         mosaic_tol=args.mosaic_tol, mosaic_exclude=args.mosaic_exclude)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
                              full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut, hold_cuts=args.hold_cuts,
-                             link_vectors=args.compensate or args.stabilize_compensate)
+                             link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic))
     else:
         ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
                             grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut,
-                            hold_cuts=args.hold_cuts, link_vectors=args.compensate or args.stabilize_compensate)
+                            hold_cuts=args.hold_cuts, link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic))
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -459,6 +492,20 @@ def main():
         counts = torch.bincount(torch.cat(sources).cpu().long(), minlength=4).tolist()
         print(f"rank {rank}: --hold-cuts: {counts[0]} frames blended, {counts[1]} held from the previous key frame, {counts[2]} from the next, "
               f"{counts[3]} between two cuts", file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    if args.mosaic:  # the canvas is resolved and read back ONCE, here, after the timed run
+        from PIL import Image
+
+        cls, _, seen, totals, poses = pred.mosaic_report()
+        rgb = colorize(torch.from_numpy(cls).cuda(), palette).cpu().numpy()
+        rgb[cls == 255] = 0  # no frame looked here
+        Image.fromarray(rgb).save(args.mosaic)
+        if args.mosaic_report:
+            write_mosaic_csv(args.mosaic_report, report_ids, poses, totals)
+        lost = int((poses[:, 12] == 2).sum())
+        print(f"--mosaic: {int((seen > 0).sum())} canvas pixels seen by {len(poses) - lost} frames"
+              + (f"; {lost} frames lost (a scene cut, or more failed fits running than are bridged)" if lost else "")
+              + (f"; {int(poses[:, 13].sum())} frames reach beyond the canvas (--mosaic-size)" if poses[:, 13].any() else ""),
+              file=sys.stderr if args.raw_out == "-" else sys.stdout)
     if args.report:  # the device report is read back ONCE, here, after the timed run
         report = pred.extent_report() if args.confidence else (torch.cat(areas).cpu().numpy() if areas else np.zeros((0, args.classes, 3), np.int64))
         write_extent_csv(args.report, report_ids, report, args.size[0] * args.size[1], with_confidence=args.confidence)
