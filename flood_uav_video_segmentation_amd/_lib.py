@@ -4,7 +4,9 @@ The product path has no CPU fallback: if the HIP library is missing or fails to 
 the ops raises.  torch is imported first on purpose -- torch ships its own libamdhip64 (same
 soname), and device pointers / streams are only interchangeable inside ONE HIP runtime instance.
 """
+import collections
 import ctypes
+import functools
 import os
 
 import torch  # noqa: F401  (must precede CDLL so both share torch's HIP runtime)
@@ -203,243 +205,94 @@ _EXT8_HOOKS = [
 EXT8_MAGIC = 0x4653455854414238  # FS_EXT8_MAGIC
 
 
-class FsTestApi(ctypes.Structure):
-    _fields_ = [("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _HOOKS]
+def _struct(name, *fields):
+    return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
 
 
-class FsExtApi(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT_HOOKS]
+def _members(hooks):
+    return [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in hooks]
 
 
-class FsHookTables(ctypes.Structure):
-    _fields_ = [("test", FsTestApi), ("ext", FsExtApi)]
+# the tables and the nested structs the library lays them out in (include/floodseg_test.h): every fs_hook_tablesN is the one before it
+# with one more table directly behind
+_EXT_HEAD = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)]
+FsTestApi = _struct("FsTestApi", ("size", ctypes.c_size_t), *_members(_HOOKS))
+FsExtApi = _struct("FsExtApi", *_EXT_HEAD, *_members(_EXT_HOOKS))
+FsHookTables = _struct("FsHookTables", ("test", FsTestApi), ("ext", FsExtApi))
+FsExt2Api = _struct("FsExt2Api", *_EXT_HEAD, *_members(_EXT2_HOOKS))
+FsHookTables2 = _struct("FsHookTables2", ("base", FsHookTables), ("ext2", FsExt2Api))
+FsExt3Api = _struct("FsExt3Api", *_EXT_HEAD, *_members(_EXT3_HOOKS))
+FsHookTables3 = _struct("FsHookTables3", ("base2", FsHookTables2), ("ext3", FsExt3Api))
+FsExt4Api = _struct("FsExt4Api", *_EXT_HEAD, *_members(_EXT4_HOOKS))
+FsHookTables4 = _struct("FsHookTables4", ("base3", FsHookTables3), ("ext4", FsExt4Api))
+FsExt5Api = _struct("FsExt5Api", *_EXT_HEAD, *_members(_EXT5_HOOKS))
+FsHookTables5 = _struct("FsHookTables5", ("base4", FsHookTables4), ("ext5", FsExt5Api))
+FsExt6Api = _struct("FsExt6Api", *_EXT_HEAD, *_members(_EXT6_HOOKS))
+FsHookTables6 = _struct("FsHookTables6", ("base5", FsHookTables5), ("ext6", FsExt6Api))
+FsExt7Api = _struct("FsExt7Api", *_EXT_HEAD, *_members(_EXT7_HOOKS))
+FsHookTables7 = _struct("FsHookTables7", ("base6", FsHookTables6), ("ext7", FsExt7Api))
+FsExt8Api = _struct("FsExt8Api", *_EXT_HEAD, *_members(_EXT8_HOOKS))
+FsHookTables8 = _struct("FsHookTables8", ("base7", FsHookTables7), ("ext8", FsExt8Api))
 
-
-class FsExt2Api(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT2_HOOKS]
-
-
-class FsHookTables2(ctypes.Structure):
-    _fields_ = [("base", FsHookTables), ("ext2", FsExt2Api)]
-
-
-class FsExt3Api(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT3_HOOKS]
-
-
-class FsHookTables3(ctypes.Structure):
-    _fields_ = [("base2", FsHookTables2), ("ext3", FsExt3Api)]
-
-
-class FsExt4Api(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT4_HOOKS]
-
-
-class FsHookTables4(ctypes.Structure):
-    _fields_ = [("base3", FsHookTables3), ("ext4", FsExt4Api)]
-
-
-class FsExt5Api(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT5_HOOKS]
-
-
-class FsHookTables5(ctypes.Structure):
-    _fields_ = [("base4", FsHookTables4), ("ext5", FsExt5Api)]
-
-
-class FsExt6Api(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT6_HOOKS]
-
-
-class FsHookTables6(ctypes.Structure):
-    _fields_ = [("base5", FsHookTables5), ("ext6", FsExt6Api)]
-
-
-class FsExt7Api(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT7_HOOKS]
-
-
-class FsHookTables7(ctypes.Structure):
-    _fields_ = [("base6", FsHookTables6), ("ext7", FsExt7Api)]
-
-
-class FsExt8Api(ctypes.Structure):
-    _fields_ = [("magic", ctypes.c_uint64), ("size", ctypes.c_size_t)] + [(name, ctypes.CFUNCTYPE(res, *args)) for name, res, args in _EXT8_HOOKS]
-
-
-class FsHookTables8(ctypes.Structure):
-    _fields_ = [("base7", FsHookTables7), ("ext8", FsExt8Api)]
+# One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
+# the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
+# ends with it, member: its name in there.
+# Adding a table: its _EXTn_HOOKS, EXTn_MAGIC, FsExtnApi and FsHookTablesn above, one row here, and extn_hook_names below.
+_Table = collections.namedtuple("_Table", "count nth hooks magic api outer member")
+_TABLES = [
+    _Table(None, None, _HOOKS, None, FsTestApi, FsHookTables, "test"),
+    _Table("one", "first", _EXT_HOOKS, "EXT_MAGIC", FsExtApi, FsHookTables, "ext"),
+    _Table("two", "second", _EXT2_HOOKS, "EXT2_MAGIC", FsExt2Api, FsHookTables2, "ext2"),
+    _Table("three", "third", _EXT3_HOOKS, "EXT3_MAGIC", FsExt3Api, FsHookTables3, "ext3"),
+    _Table("four", "fourth", _EXT4_HOOKS, "EXT4_MAGIC", FsExt4Api, FsHookTables4, "ext4"),
+    _Table("five", "fifth", _EXT5_HOOKS, "EXT5_MAGIC", FsExt5Api, FsHookTables5, "ext5"),
+    _Table("six", "sixth", _EXT6_HOOKS, "EXT6_MAGIC", FsExt6Api, FsHookTables6, "ext6"),
+    _Table("seven", "seventh", _EXT7_HOOKS, "EXT7_MAGIC", FsExt7Api, FsHookTables7, "ext7"),
+    _Table("eight", "eighth", _EXT8_HOOKS, "EXT8_MAGIC", FsExt8Api, FsHookTables8, "ext8"),
+]
+_TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
 
 class _Library:
     """The loaded library: exported functions as attributes (ctypes), and the op-level test hooks of fs_test_hooks() under the names
-    fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in the table)."""
+    fs_<member> (so `lib.fs_conv2d_nhwc(...)` works whether a symbol is exported or lives in a table)."""
 
     def __init__(self, cdll):
         self._cdll = cdll
-        self._hooks = None
-        self._ext = None
-        self._ext2 = None
-        self._ext3 = None
-        self._ext4 = None
-        self._ext5 = None
-        self._ext6 = None
-        self._ext7 = None
-        self._ext8 = None
+        self._tables = {}  # table number -> that table in the library, once its checks have passed
 
     def __getattr__(self, name):
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT8_HOOKS):
-            if self._ext8 is None:
-                all7 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables7)).contents
-                all5 = all7.base6.base5
-                all2 = all5.base4.base3.base2
-                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
-                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
-                        or all5.base4.base3.ext3.magic != EXT3_MAGIC or all5.base4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
-                        or all5.base4.ext4.magic != EXT4_MAGIC or all5.base4.ext4.size != ctypes.sizeof(FsExt4Api)
-                        or all5.ext5.magic != EXT5_MAGIC or all5.ext5.size != ctypes.sizeof(FsExt5Api)
-                        or all7.base6.ext6.magic != EXT6_MAGIC or all7.base6.ext6.size != ctypes.sizeof(FsExt6Api)
-                        or all7.ext7.magic != EXT7_MAGIC or all7.ext7.size != ctypes.sizeof(FsExt7Api)):
-                    raise RuntimeError(f"floodseg: the library's first eight hook tables are not the ones this binding knows ({name} is missing)")
-                ext8 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables8)).contents.ext8
-                if ext8.magic != EXT8_MAGIC:
-                    raise RuntimeError(f"floodseg: the library has no eighth extension table ({name} is missing)")
-                self._ext8 = ext8
-            member = getattr(FsExt8Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
-            if self._ext8.size < member.offset + member.size:
-                raise RuntimeError(f"floodseg: the library's eighth extension table is older than this binding ({name} is missing)")
-            fn = getattr(self._ext8, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT7_HOOKS):
-            if self._ext7 is None:
-                all6 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables6)).contents
-                all5 = all6.base5
-                all2 = all5.base4.base3.base2
-                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
-                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
-                        or all5.base4.base3.ext3.magic != EXT3_MAGIC or all5.base4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
-                        or all5.base4.ext4.magic != EXT4_MAGIC or all5.base4.ext4.size != ctypes.sizeof(FsExt4Api)
-                        or all5.ext5.magic != EXT5_MAGIC or all5.ext5.size != ctypes.sizeof(FsExt5Api)
-                        or all6.ext6.magic != EXT6_MAGIC or all6.ext6.size != ctypes.sizeof(FsExt6Api)):
-                    raise RuntimeError(f"floodseg: the library's first seven hook tables are not the ones this binding knows ({name} is missing)")
-                ext7 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables7)).contents.ext7
-                if ext7.magic != EXT7_MAGIC:
-                    raise RuntimeError(f"floodseg: the library has no seventh extension table ({name} is missing)")
-                self._ext7 = ext7
-            member = getattr(FsExt7Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
-            if self._ext7.size < member.offset + member.size:
-                raise RuntimeError(f"floodseg: the library's seventh extension table is older than this binding ({name} is missing)")
-            fn = getattr(self._ext7, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT6_HOOKS):
-            if self._ext6 is None:
-                all5 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables5)).contents
-                all2 = all5.base4.base3.base2
-                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
-                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
-                        or all5.base4.base3.ext3.magic != EXT3_MAGIC or all5.base4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
-                        or all5.base4.ext4.magic != EXT4_MAGIC or all5.base4.ext4.size != ctypes.sizeof(FsExt4Api)
-                        or all5.ext5.magic != EXT5_MAGIC or all5.ext5.size != ctypes.sizeof(FsExt5Api)):
-                    raise RuntimeError(f"floodseg: the library's first six hook tables are not the ones this binding knows ({name} is missing)")
-                ext6 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables6)).contents.ext6
-                if ext6.magic != EXT6_MAGIC:
-                    raise RuntimeError(f"floodseg: the library has no sixth extension table ({name} is missing)")
-                self._ext6 = ext6
-            member = getattr(FsExt6Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
-            if self._ext6.size < member.offset + member.size:
-                raise RuntimeError(f"floodseg: the library's sixth extension table is older than this binding ({name} is missing)")
-            fn = getattr(self._ext6, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT5_HOOKS):
-            if self._ext5 is None:
-                all4 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables4)).contents
-                all2 = all4.base3.base2
-                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
-                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
-                        or all4.base3.ext3.magic != EXT3_MAGIC or all4.base3.ext3.size != ctypes.sizeof(FsExt3Api)
-                        or all4.ext4.magic != EXT4_MAGIC or all4.ext4.size != ctypes.sizeof(FsExt4Api)):
-                    raise RuntimeError(f"floodseg: the library's first five hook tables are not the ones this binding knows ({name} is missing)")
-                ext5 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables5)).contents.ext5
-                if ext5.magic != EXT5_MAGIC:
-                    raise RuntimeError(f"floodseg: the library has no fifth extension table ({name} is missing)")
-                self._ext5 = ext5
-            member = getattr(FsExt5Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
-            if self._ext5.size < member.offset + member.size:
-                raise RuntimeError(f"floodseg: the library's fifth extension table is older than this binding ({name} is missing)")
-            fn = getattr(self._ext5, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT4_HOOKS):
-            if self._ext4 is None:
-                all3 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables3)).contents
-                all2 = all3.base2
-                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
-                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)
-                        or all3.ext3.magic != EXT3_MAGIC or all3.ext3.size != ctypes.sizeof(FsExt3Api)):
-                    raise RuntimeError(f"floodseg: the library's first four hook tables are not the ones this binding knows ({name} is missing)")
-                ext4 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables4)).contents.ext4
-                if ext4.magic != EXT4_MAGIC:
-                    raise RuntimeError(f"floodseg: the library has no fourth extension table ({name} is missing)")
-                self._ext4 = ext4
-            member = getattr(FsExt4Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
-            if self._ext4.size < member.offset + member.size:
-                raise RuntimeError(f"floodseg: the library's fourth extension table is older than this binding ({name} is missing)")
-            fn = getattr(self._ext4, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT3_HOOKS):
-            if self._ext3 is None:
-                all2 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables2)).contents
-                if (all2.base.test.size != ctypes.sizeof(FsTestApi) or all2.base.ext.magic != EXT_MAGIC or all2.base.ext.size != ctypes.sizeof(FsExtApi)
-                        or all2.ext2.magic != EXT2_MAGIC or all2.ext2.size != ctypes.sizeof(FsExt2Api)):
-                    raise RuntimeError(f"floodseg: the library's first three hook tables are not the ones this binding knows ({name} is missing)")
-                ext3 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables3)).contents.ext3
-                if ext3.magic != EXT3_MAGIC:
-                    raise RuntimeError(f"floodseg: the library has no third extension table ({name} is missing)")
-                self._ext3 = ext3
-            member = getattr(FsExt3Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
-            if self._ext3.size < member.offset + member.size:
-                raise RuntimeError(f"floodseg: the library's third extension table is older than this binding ({name} is missing)")
-            fn = getattr(self._ext3, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT2_HOOKS):
-            if self._ext2 is None:
-                base = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables)).contents
-                if base.test.size != ctypes.sizeof(FsTestApi) or base.ext.magic != EXT_MAGIC or base.ext.size != ctypes.sizeof(FsExtApi):
-                    raise RuntimeError(f"floodseg: the library's first two hook tables are not the ones this binding knows ({name} is missing)")
-                ext2 = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables2)).contents.ext2
-                if ext2.magic != EXT2_MAGIC:
-                    raise RuntimeError(f"floodseg: the library has no second extension table ({name} is missing)")
-                self._ext2 = ext2
-            member = getattr(FsExt2Api, name[3:])  # the table grows at its end: an older library holds the members up to its `size`
-            if self._ext2.size < member.offset + member.size:
-                raise RuntimeError(f"floodseg: the library's second extension table is older than this binding ({name} is missing)")
-            fn = getattr(self._ext2, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and any(name == "fs_" + h[0] for h in _EXT_HOOKS):
-            if self._ext is None:
-                tables = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsHookTables)).contents
-                if tables.test.size != ctypes.sizeof(FsTestApi) or tables.ext.magic != EXT_MAGIC or tables.ext.size < ctypes.sizeof(FsExtApi):
+        n = _TABLE_OF.get(name)
+        if n is None:
+            return getattr(self._cdll, name)  # an exported symbol, fs_test_hooks itself among them
+        want = _TABLES[n]
+        if n not in self._tables:
+            # Every table in front of table n must be the one this binding knows, to the byte, or table n is not where `outer` puts it; table
+            # n itself needs its magic and may be longer, since it grows at its end.  The two oldest tables accept any size from their own
+            # on and keep their own messages.
+            for t in _TABLES[:n + 1]:
+                table = getattr(ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(t.outer)).contents, t.member)
+                known = t.magic is None or table.magic == globals()[t.magic]
+                if t is not want:
+                    known = known and table.size == ctypes.sizeof(t.api)
+                elif n < 2:
+                    known = known and table.size >= ctypes.sizeof(t.api)
+                if known:
+                    continue
+                if n == 0:
+                    raise RuntimeError(f"floodseg: the library's test-hook table ({table.size} B) is older than this binding ({ctypes.sizeof(t.api)} B)")
+                if n == 1:
                     raise RuntimeError(f"floodseg: the library has no extension table, or an older one than this binding ({name} is missing)")
-                self._ext = tables.ext
-            fn = getattr(self._ext, name[3:])
-            setattr(self, name, fn)
-            return fn
-        if name.startswith("fs_") and name != "fs_test_hooks" and any(name == "fs_" + h[0] for h in _HOOKS):
-            if self._hooks is None:
-                table = ctypes.cast(self._cdll.fs_test_hooks(), ctypes.POINTER(FsTestApi)).contents
-                if table.size < ctypes.sizeof(FsTestApi):
-                    raise RuntimeError(f"floodseg: the library's test-hook table ({table.size} B) is older than this binding ({ctypes.sizeof(FsTestApi)} B)")
-                self._hooks = table
-            fn = getattr(self._hooks, name[3:])
-            setattr(self, name, fn)
-            return fn
-        return getattr(self._cdll, name)
+                if t is not want:
+                    raise RuntimeError(f"floodseg: the library's first {want.count} hook tables are not the ones this binding knows ({name} is missing)")
+                raise RuntimeError(f"floodseg: the library has no {want.nth} extension table ({name} is missing)")
+            self._tables[n] = table
+        member = getattr(want.api, name[3:])  # an older library holds the members up to its table's `size`
+        if n >= 2 and self._tables[n].size < member.offset + member.size:
+            raise RuntimeError(f"floodseg: the library's {want.nth} extension table is older than this binding ({name} is missing)")
+        fn = getattr(self._tables[n], name[3:])
+        setattr(self, name, fn)
+        return fn
 
 
 _lib = None
@@ -470,49 +323,13 @@ def exported_symbols():
     return sorted(_SIGNATURES)
 
 
-def hook_names():
-    """Members of fs_test_api after `size`, in declaration order."""
-    return [h[0] for h in _HOOKS]
+def _hook_names(n):
+    """Members of table n after `size` (an extension table: after `magic` and `size`), in declaration order."""
+    return [h[0] for h in _TABLES[n].hooks]
 
 
-def ext_hook_names():
-    """Members of fs_ext_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT_HOOKS]
-
-
-def ext2_hook_names():
-    """Members of fs_ext2_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT2_HOOKS]
-
-
-def ext3_hook_names():
-    """Members of fs_ext3_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT3_HOOKS]
-
-
-def ext4_hook_names():
-    """Members of fs_ext4_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT4_HOOKS]
-
-
-def ext5_hook_names():
-    """Members of fs_ext5_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT5_HOOKS]
-
-
-def ext6_hook_names():
-    """Members of fs_ext6_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT6_HOOKS]
-
-
-def ext7_hook_names():
-    """Members of fs_ext7_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT7_HOOKS]
-
-
-def ext8_hook_names():
-    """Members of fs_ext8_api after `magic` and `size`, in declaration order."""
-    return [h[0] for h in _EXT8_HOOKS]
+(hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
+ ext8_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

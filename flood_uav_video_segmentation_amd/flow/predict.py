@@ -54,6 +54,53 @@ from . import crops
 PALETTE = np.array([[0, 0, 0], [30, 95, 170], [65, 117, 5], [212, 98, 1], [255, 244, 116]], dtype=np.uint8)  # dataset/flow/list/colors.txt
 
 
+class FrameRows:
+    """One stage's per-frame device tables: parallel buffers, `spec` = one (shape of a frame's rows, dtype) each, allocated a chunk of
+    frames at a time -- one allocation per chunk, not one per window -- and filled in frame order; nothing is read back before a report
+    asks.  Every chunk is zero-filled: the reports trim a frame's rows by a counts column and hand out rows nobody wrote.  The chunk
+    size is an argument of every call, not kept here: the predictor's REPORT_CHUNK, outline_chunk and simple_chunk may be set at any
+    time before the first window, and without a reference back to the predictor the buffers are freed with it."""
+
+    def __init__(self, *spec):
+        self.spec = spec
+        self.clear()
+
+    def clear(self):
+        self.chunks = []  # one tuple of buffers [chunk, *shape] per chunk, in frame order
+        self.frames = 0   # frames written: the newest chunk is filled up to frames % chunk
+
+    def rows(self, row, take, chunk, device):
+        """Views of rows row .. row + take - 1 of the newest chunk, one per buffer; row == 0 starts a new chunk on `device`.  Called
+        directly by a table that keeps in step with another one's pieces(): that one counts the frames for both."""
+        if row == 0:
+            self.chunks.append(tuple(torch.zeros((chunk,) + tuple(shape), dtype=dtype, device=device) for shape, dtype in self.spec))
+        return tuple(b[row:row + take] for b in self.chunks[-1])
+
+    def pieces(self, n, chunk, device):
+        """The next n frames, cut at the chunk borders: yields (done, take, row, views) -- frames done .. done + take - 1 of the n go
+        into rows row .. of the newest chunk, which `views` are.  The frames count once the caller comes back for the next piece."""
+        done = 0
+        while done < n:
+            row = self.frames % chunk
+            take = min(n - done, chunk - row)
+            yield done, take, row, self.rows(row, take, chunk, device)
+            done += take
+            self.frames += take
+
+    def filled(self, chunk, *followers):
+        """Chunk by chunk (take, views of the rows written), for a report that reads back one chunk at a time; with followers -- tables
+        kept in step with this one through rows() -- the views of each of them after its own."""
+        left = self.frames
+        for i, buffers in enumerate(self.chunks):
+            take = min(left, chunk)
+            yield (take,) + tuple(tuple(b[:take] for b in t.chunks[i]) for t in (self,) + followers)
+            left -= take
+
+    def flat(self):
+        """The first buffer's rows written, as ONE device tensor (a copy), for a report that reads back once."""
+        return torch.cat([buffers[0] for buffers in self.chunks])[:self.frames]
+
+
 class FlowPredictor:
     """cache_keyframes=True + `key_ids=(prev_frame_id, next_frame_id)` in predict_window: the network output of the previous
     window's `frame_next` is reused when it is this window's `frame_prev` (flow/dataset.py:112-114 builds consecutive windows
@@ -64,7 +111,8 @@ class FlowPredictor:
     the sliding-crop route).  The masks are the confidence=False masks bit for bit; they come from the same launch as the confidence,
     which needs the window's logits / canvas written out once (the masks-only tails skip that).  Every window's per-class report
     (pixels, sum of confidence codes, pixels with confidence < low_confidence) goes into rows of chunked device buffers; nothing is
-    read back until extent_report().
+    read back until extent_report().  Every stage below keeps its per-frame rows the same way, in a FrameRows of its own (REPORT_CHUNK
+    frames a chunk; outline_chunk and simple_chunk for the two big ones), and clear_report() clears them all.
 
     regions=True (extension): every emitted mask is labelled (connectivity 4 or 8) and its region table -- per region class, area,
     bounding box, coordinate sums, and with confidence=True the confidence sum and the low-confidence pixels -- goes into chunked
@@ -177,8 +225,7 @@ class FlowPredictor:
             raise ValueError(f"FlowPredictor: low_confidence must be 0..255, got {low_confidence}")
         self.confidence = bool(confidence)
         self.low_confidence = int(low_confidence)
-        self._report_chunks = []  # int64 [REPORT_CHUNK, K, 3] device buffers, filled in frame order
-        self._report_frames = 0
+        self._extent = FrameRows(((classes, 3), torch.int64))  # the extent report's rows, REPORT_CHUNK frames a chunk
         if connectivity not in (4, 8):
             raise ValueError(f"FlowPredictor: connectivity must be 4 or 8, got {connectivity}")
         if not 1 <= int(max_regions) <= 65536:
@@ -189,8 +236,7 @@ class FlowPredictor:
         self.min_region_area = int(min_region_area)
         self.connectivity = int(connectivity)
         self.max_regions = int(max_regions)
-        self._region_chunks = []  # (int64 [REPORT_CHUNK, max_regions, 10], int64 [REPORT_CHUNK, 2]) device buffers, in frame order
-        self._region_frames = 0
+        self._regions = FrameRows(((self.max_regions, 10), torch.int64), ((2,), torch.int64))  # (table, counts), REPORT_CHUNK frames a chunk
         self._despeckle_counts = []  # min_region_area > 1: the filter pass's int64 [n, 2] counts, one device tensor per window
         if track and not regions:
             raise ValueError("FlowPredictor: track=True needs regions=True (the tracks follow the region tables' rows)")
@@ -205,7 +251,7 @@ class FlowPredictor:
         self.compensate = bool(compensate)
         self.min_overlap = int(min_overlap)
         self.max_pairs = pairs
-        self._track_chunks = []   # (int64 [REPORT_CHUNK, max_regions, 4], int64 [REPORT_CHUNK, 2] link counts), in step with _region_chunks
+        self._tracks = FrameRows(((self.max_regions, 4), torch.int64), ((2,), torch.int64))  # (tracks, link counts), in step with _regions
         self._track_prev = None   # the last tabulated frame: (index [H,W], table [max_regions,10], counts [2], tracks [max_regions,4]), copies
         self._track_state = None  # device int64 [2] = (next track id, 0)
         if outlines and not regions:
@@ -217,8 +263,8 @@ class FlowPredictor:
         self.max_vertices = int(max_vertices)
         per_frame = 8 * self.max_vertices + 48 * self.max_contours + 24 * self.max_regions + 32
         self.outline_chunk = max(1, min(self.REPORT_CHUNK, ((64 << 20) - 1) // per_frame))  # frames per device buffer: below 64 MiB
-        self._outline_chunks = []  # (contours, vertices, shape, counts) device buffers of outline_chunk frames each, in frame order
-        self._outline_frames = 0
+        self._outlines = FrameRows(((self.max_contours, 6), torch.int64), ((self.max_vertices, 2), torch.int32), ((self.max_regions, 3), torch.int64),
+                                   ((4,), torch.int64))  # (contours, vertices, shape, counts), outline_chunk frames a chunk
         if simplify is not None and not outlines:
             raise ValueError("FlowPredictor: simplify needs outlines=True (it simplifies the rings the outlines just wrote)")
         if not 1 <= int(simplify_rounds) <= 256:
@@ -229,8 +275,8 @@ class FlowPredictor:
         self.simplify_rounds = int(simplify_rounds)
         per_frame = 8 * self.max_vertices + 32 * self.max_contours + 32
         self.simple_chunk = max(1, min(self.REPORT_CHUNK, ((64 << 20) - 1) // per_frame))  # frames per device buffer: below 64 MiB
-        self._simple_chunks = []  # (simple, simple_vertices, simple_counts) device buffers of simple_chunk frames each, in frame order
-        self._simple_frames = 0
+        self._simple = FrameRows(((self.max_contours, 4), torch.int64), ((self.max_vertices, 2), torch.int32),
+                                 ((4,), torch.int64))  # (simple, simple_vertices, simple_counts), simple_chunk frames a chunk
         if keep_window_regions and not regions:
             raise ValueError("FlowPredictor: keep_window_regions=True needs regions=True (it keeps the region tables' index planes and rows)")
         self.keep_window_regions = bool(keep_window_regions)
@@ -248,8 +294,7 @@ class FlowPredictor:
         self.stabilize_trust = None if stabilize_trust is None else int(stabilize_trust)
         self.stabilize_compensate = bool(stabilize_compensate)
         self._stabilize_state = None   # the state plane int32 [H, W] on the device, carried from window to window
-        self._stabilize_chunks = []    # int64 [REPORT_CHUNK, 4] device buffers of the per-frame counts, in frame order
-        self._stabilize_frames = 0
+        self._stabilize_counts = FrameRows(((4,), torch.int64))  # the per-frame counts, REPORT_CHUNK frames a chunk
         self.proximity = None
         if proximity is not None:
             if not self.regions:
@@ -268,7 +313,7 @@ class FlowPredictor:
         self.proximity_sources = tuple(int(c) for c in proximity_sources)
         self.proximity_targets = tuple(int(c) for c in proximity_targets)
         self.proximity_max = int(proximity_max or 0) if self.proximity else 0
-        self._proximity_chunks = []  # (int64 [REPORT_CHUNK, K, B] exposure, int64 [REPORT_CHUNK, max_regions, 8] near), in step with _region_chunks
+        self._proximity = FrameRows(((classes, len(self.proximity or ())), torch.int64), ((self.max_regions, 8), torch.int64))  # (exposure, near), in step with _regions
         self.mosaic = None
         self.mosaic_classes = self.classes if mosaic_classes is None else int(mosaic_classes)
         if mosaic is not None:
@@ -299,8 +344,13 @@ class FlowPredictor:
         self._mosaic_votes = None   # uint16 [K, CH, CW] on the device, with the chain's state int64 [32] and the origin in use
         self._mosaic_state = None
         self._mosaic_at = None
-        self._mosaic_chunks = []    # int64 [REPORT_CHUNK, 16] device buffers of the per-frame pose rows, in frame order
-        self._mosaic_frames = 0
+        self._mosaic_poses = FrameRows(((16,), torch.int64))  # the per-frame pose rows, REPORT_CHUNK frames a chunk
+
+    # the chunk lists that tests count, under the names they had before the tables moved into FrameRows
+    _report_chunks = property(lambda self: self._extent.chunks)
+    _region_chunks = property(lambda self: self._regions.chunks)
+    _track_chunks = property(lambda self: self._tracks.chunks)
+    _proximity_chunks = property(lambda self: self._proximity.chunks)
 
     def reset(self):
         """Start a new video: forget the cached key frame and the last mask (the temporal-consistency metric pairs each frame with
@@ -314,58 +364,36 @@ class FlowPredictor:
 
     def clear_report(self):
         """Forget the extent report and the region report of the frames predicted so far."""
-        self._report_chunks = []
-        self._report_frames = 0
-        self._region_chunks = []
-        self._region_frames = 0
+        for table in (self._extent, self._regions, self._tracks, self._outlines, self._simple, self._stabilize_counts, self._proximity, self._mosaic_poses):
+            table.clear()  # the tracks' previous frame and next id stay, and so does the stabiliser's state plane
         self._despeckle_counts = []
-        self._track_chunks = []  # the previous frame and the next track id stay
-        self._outline_chunks = []
-        self._outline_frames = 0
-        self._simple_chunks = []
-        self._simple_frames = 0
-        self._stabilize_chunks = []  # the state plane stays
-        self._stabilize_frames = 0
-        self._proximity_chunks = []
         self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
-        self._mosaic_chunks = []
-        self._mosaic_frames = 0
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
         the windows were predicted: per class the pixels, the sum of their confidence codes (mean confidence = sum / (255 pixels))
         and the pixels with confidence < low_confidence.  ONE read-back, here."""
-        if not self._report_chunks:
+        if not self._extent.chunks:
             return np.zeros((0, self.classes, 3), dtype=np.int64)
-        return torch.cat(self._report_chunks)[:self._report_frames].cpu().numpy()
+        return self._extent.flat().cpu().numpy()
 
     def _keep_report(self, masks, conf):
         """The window's report into the next rows of the chunked buffers (frame_report writes its rows whole; nothing is read)."""
-        done, n = 0, masks.shape[0]
-        while done < n:
-            row = self._report_frames % self.REPORT_CHUNK
-            if row == 0:
-                self._report_chunks.append(torch.zeros((self.REPORT_CHUNK, self.classes, 3), dtype=torch.int64, device=masks.device))
-            take = min(n - done, self.REPORT_CHUNK - row)
-            ops.frame_report(masks[done:done + take], conf[done:done + take], self.classes, self.low_confidence,
-                             out=self._report_chunks[-1][row:row + take])
-            done += take
-            self._report_frames += take
+        for done, take, _, (rows,) in self._extent.pieces(masks.shape[0], self.REPORT_CHUNK, masks.device):
+            ops.frame_report(masks[done:done + take], conf[done:done + take], self.classes, self.low_confidence, out=rows)
 
     def region_report(self):
         """regions=True: (rows, totals) for every frame predicted since the start (or clear_report()), in the order the windows were
         predicted: rows[f] = int64 numpy [min(regions, max_regions), 10] (class, area, x0, y0, x1, y1, sum_x, sum_y, conf_sum,
         low_pixels), totals = int64 numpy [frames], the frames' full region counts (totals[f] > max_regions: the table is cut).  The
         read-back happens here and nowhere else, chunk by chunk into host arrays (no second copy of the report on the device)."""
-        if not self._region_chunks:
+        if not self._regions.chunks:
             return [], np.zeros((0,), dtype=np.int64)
-        rows, totals, left = [], [], self._region_frames
-        for table, counts in self._region_chunks:
-            take = min(left, self.REPORT_CHUNK)
-            c, t = counts[:take].cpu().numpy(), table[:take].cpu().numpy()
+        rows, totals = [], []
+        for take, (table, counts) in self._regions.filled(self.REPORT_CHUNK):
+            c, t = counts.cpu().numpy(), table.cpu().numpy()
             rows.extend(t[f, :int(c[f, 1])] for f in range(take))
             totals.append(c[:, 0])
-            left -= take
         return rows, np.concatenate(totals)
 
     def despeckle_counts(self):
@@ -390,23 +418,16 @@ class FlowPredictor:
         kw = {} if not self.stabilize_compensate else dict(mv=link[0], frame_size=link[1], pair_stats=link[2])
         out, self._stabilize_state, counts = ops.mask_stabilize(masks.contiguous(), self._stabilize_state, conf if self.stabilize_trust is not None else None,
                                                                 self.classes, self.stabilize, self.stabilize_trust, **kw)
-        done, n = 0, out.shape[0]
-        while done < n:
-            row = self._stabilize_frames % self.REPORT_CHUNK
-            if row == 0:
-                self._stabilize_chunks.append(torch.zeros((self.REPORT_CHUNK, 4), dtype=torch.int64, device=out.device))
-            take = min(n - done, self.REPORT_CHUNK - row)
-            self._stabilize_chunks[-1][row:row + take].copy_(counts[done:done + take])
-            done += take
-            self._stabilize_frames += take
+        for done, take, _, (rows,) in self._stabilize_counts.pieces(out.shape[0], self.REPORT_CHUNK, out.device):
+            rows.copy_(counts[done:done + take])
         return out
 
     def stabilize_report(self):
         """stabilize=N: int64 numpy [frames, 4] = (held, switched, seeded, trusted) pixels of every frame predicted since the start (or
         clear_report()), in the order the windows were predicted.  ONE read-back, here."""
-        if not self._stabilize_chunks:
+        if not self._stabilize_counts.chunks:
             return np.zeros((0, 4), dtype=np.int64)
-        return torch.cat(self._stabilize_chunks)[:self._stabilize_frames].cpu().numpy()
+        return self._stabilize_counts.flat().cpu().numpy()
 
     def _track_link(self, link):
         """What _link_inputs returned, for the tracks: theirs only under compensate=True (stabilize_compensate=True alone leaves them in place)."""
@@ -427,15 +448,8 @@ class FlowPredictor:
                                   exclude=self.mosaic_exclude, pair_stats=link[2])
         poses = ops.pose_chain(model, self._mosaic_state, (h, w), self.mosaic, self._mosaic_at, self.mosaic_bridge)
         ops.mosaic_accumulate(masks, poses, self._mosaic_votes, self._mosaic_at)
-        done = 0
-        while done < n:
-            row = self._mosaic_frames % self.REPORT_CHUNK
-            if row == 0:
-                self._mosaic_chunks.append(torch.zeros((self.REPORT_CHUNK, 16), dtype=torch.int64, device=dev))
-            take = min(n - done, self.REPORT_CHUNK - row)
-            self._mosaic_chunks[-1][row:row + take].copy_(poses[done:done + take])
-            done += take
-            self._mosaic_frames += take
+        for done, take, _, (rows,) in self._mosaic_poses.pieces(n, self.REPORT_CHUNK, dev):
+            rows.copy_(poses[done:done + take])
 
     def mosaic_report(self):
         """mosaic=(CH, CW): (cls, conf, seen, totals, poses) of the frames predicted since the start (or clear_report()): cls uint8 numpy
@@ -449,7 +463,7 @@ class FlowPredictor:
             return (np.full((ch, cw), 255, np.uint8), np.zeros((ch, cw), np.uint8), np.zeros((ch, cw), np.int32), np.zeros((k, 2), np.int64),
                     np.zeros((0, 16), np.int64))
         cls, conf, seen, totals = ops.mosaic_resolve(self._mosaic_votes)
-        poses = torch.cat(self._mosaic_chunks)[:self._mosaic_frames]
+        poses = self._mosaic_poses.flat()
         return cls.cpu().numpy(), conf.cpu().numpy(), seen.cpu().numpy(), totals.cpu().numpy(), poses.cpu().numpy()
 
     def _link_inputs(self, n, link_mvs, link_frame_size, link_stats):
@@ -475,42 +489,29 @@ class FlowPredictor:
         """The window's region tables into the next rows of the chunked buffers (region_table writes its rows whole; nothing is read)."""
         masks = masks.contiguous()
         labels = ops.mask_regions(masks, self.classes, self.connectivity)
-        done, n = 0, masks.shape[0]
         kept = []
-        while done < n:
-            row = self._region_frames % self.REPORT_CHUNK
-            if row == 0:
-                self._region_chunks.append((torch.zeros((self.REPORT_CHUNK, self.max_regions, 10), dtype=torch.int64, device=masks.device),
-                                            torch.zeros((self.REPORT_CHUNK, 2), dtype=torch.int64, device=masks.device)))
-            take = min(n - done, self.REPORT_CHUNK - row)
-            table, counts = self._region_chunks[-1]
-            got = ops.region_table(masks[done:done + take], labels[done:done + take], self.classes, None if conf is None else conf[done:done + take],
-                                   self.low_confidence, self.max_regions, out=(table[row:row + take], counts[row:row + take]))
+        for done, take, row, (table, counts) in self._regions.pieces(masks.shape[0], self.REPORT_CHUNK, masks.device):
+            _, _, index = ops.region_table(masks[done:done + take], labels[done:done + take], self.classes, None if conf is None else conf[done:done + take],
+                                           self.low_confidence, self.max_regions, out=(table, counts))
+            tracks = None
             if self.outlines:
-                self._keep_outlines(got[2])
+                self._keep_outlines(index)
             if self.track:
                 piece = None if link is None else (link[0][done:done + take], link[1], None if link[2] is None else link[2][done:done + take])
-                self._keep_tracks(got[2], table[row:row + take], counts[row:row + take], row, piece)
+                tracks = self._keep_tracks(index, table, counts, row, piece)
             if self.proximity:
-                self._keep_proximity(masks[done:done + take], got[2], counts[row:row + take], row)
+                self._keep_proximity(masks[done:done + take], index, counts, row)
             if self.keep_window_regions:
-                kept.append((got[2], table[row:row + take], counts[row:row + take], self._track_chunks[-1][0][row:row + take] if self.track else None))
-            done += take
-            self._region_frames += take
+                kept.append((index, table, counts, tracks))
         if self.keep_window_regions:
             self._window_regions = kept
 
     def _keep_proximity(self, masks, index, counts, row):
         """The distance field of the piece region_table just tabulated (rows row.. of the newest chunk) and its two tables into the same
         rows of their own chunked buffers (region_proximity writes its rows whole; nothing is read back)."""
-        take, dev = masks.shape[0], masks.device
-        if row == 0:
-            self._proximity_chunks.append((torch.zeros((self.REPORT_CHUNK, self.classes, len(self.proximity)), dtype=torch.int64, device=dev),
-                                           torch.zeros((self.REPORT_CHUNK, self.max_regions, 8), dtype=torch.int64, device=dev)))
+        rows = self._proximity.rows(row, masks.shape[0], self.REPORT_CHUNK, masks.device)
         d2, nearest = ops.mask_distance(masks, self.proximity_sources, self.proximity_max)
-        exposure, near = self._proximity_chunks[-1]
-        ops.region_proximity(masks, d2, nearest, index, counts, self.classes, self.max_regions, self.proximity_targets, self.proximity,
-                             out=(exposure[row:row + take], near[row:row + take]))
+        ops.region_proximity(masks, d2, nearest, index, counts, self.classes, self.max_regions, self.proximity_targets, self.proximity, out=rows)
 
     def proximity_report(self):
         """proximity=(PX, ...): (exposure, near) for every frame of region_report(), in its order: exposure = int64 numpy [frames, K, B], the
@@ -519,15 +520,13 @@ class FlowPredictor:
         region_report()'s rows[f]: the region's smallest squared distance to a source pixel (-1 in all six leading columns: the frame has
         no source pixel, or none within proximity_max), the pixel that attains it, the source pixel nearest to that one and its region's row (-1: none), and the region's
         pixels within the first threshold.  Distances are in mask pixels.  The read-back happens here, chunk by chunk."""
-        if not self._proximity_chunks:
+        if not self._proximity.chunks:
             return np.zeros((0, self.classes, len(self.proximity or ())), dtype=np.int64), []
-        exposures, rows, left = [], [], self._region_frames
-        for (exposure, near), (_, counts) in zip(self._proximity_chunks, self._region_chunks):
-            take = min(left, self.REPORT_CHUNK)
-            c, t = counts[:take].cpu().numpy(), near[:take].cpu().numpy()
+        exposures, rows = [], []
+        for take, (_, counts), (exposure, near) in self._regions.filled(self.REPORT_CHUNK, self._proximity):
+            c, t = counts.cpu().numpy(), near.cpu().numpy()
             rows.extend(t[f, :int(c[f, 1])] for f in range(take))
-            exposures.append(exposure[:take].cpu().numpy())
-            left -= take
+            exposures.append(exposure.cpu().numpy())
         return np.concatenate(exposures), rows
 
     def window_regions(self):
@@ -545,39 +544,17 @@ class FlowPredictor:
     def _keep_outlines(self, index):
         """The outlines of the index planes region_table just wrote into the next rows of their own chunked buffers (region_outlines
         writes its rows whole; nothing is read back)."""
-        done, n, dev = 0, index.shape[0], index.device
-        while done < n:
-            row = self._outline_frames % self.outline_chunk
-            if row == 0:
-                c = self.outline_chunk
-                self._outline_chunks.append((torch.zeros((c, self.max_contours, 6), dtype=torch.int64, device=dev),
-                                             torch.zeros((c, self.max_vertices, 2), dtype=torch.int32, device=dev),
-                                             torch.zeros((c, self.max_regions, 3), dtype=torch.int64, device=dev),
-                                             torch.zeros((c, 4), dtype=torch.int64, device=dev)))
-            take = min(n - done, self.outline_chunk - row)
-            piece = tuple(b[row:row + take] for b in self._outline_chunks[-1])
-            ops.region_outlines(index[done:done + take], self.max_regions, self.connectivity, self.max_contours, self.max_vertices, out=piece)
+        for done, take, _, rows in self._outlines.pieces(index.shape[0], self.outline_chunk, index.device):
+            ops.region_outlines(index[done:done + take], self.max_regions, self.connectivity, self.max_contours, self.max_vertices, out=rows)
             if self.simplify is not None:
-                self._keep_simple(piece[0], piece[1], piece[3])
-            done += take
-            self._outline_frames += take
+                self._keep_simple(rows[0], rows[1], rows[3])
 
     def _keep_simple(self, contours, vertices, counts):
         """The simplified rings of the outlines region_outlines just wrote into the next rows of their own chunked buffers
         (outline_simplify writes its rows whole; nothing is read back)."""
-        done, n, dev = 0, contours.shape[0], contours.device
-        while done < n:
-            row = self._simple_frames % self.simple_chunk
-            if row == 0:
-                c = self.simple_chunk
-                self._simple_chunks.append((torch.zeros((c, self.max_contours, 4), dtype=torch.int64, device=dev),
-                                            torch.zeros((c, self.max_vertices, 2), dtype=torch.int32, device=dev),
-                                            torch.zeros((c, 4), dtype=torch.int64, device=dev)))
-            take = min(n - done, self.simple_chunk - row)
+        for done, take, _, rows in self._simple.pieces(contours.shape[0], self.simple_chunk, contours.device):
             ops.outline_simplify(contours[done:done + take], vertices[done:done + take], counts[done:done + take], self.simplify, self.simplify_rounds,
-                                 out=tuple(b[row:row + take] for b in self._simple_chunks[-1]))
-            done += take
-            self._simple_frames += take
+                                 out=rows)
 
     def simple_outline_report(self):
         """simplify=TOL: (frames, counts) for every frame of outline_report(), in its order: frames[f] = (rows int64 numpy [rows, 4],
@@ -586,16 +563,14 @@ class FlowPredictor:
         rounds, flags), flags bit 0: some ring still had open segments after simplify_rounds rounds (all their vertices are kept: raise
         simplify_rounds above the `rounds` column), bit 1: the frame's outlines had overflowed (nothing), bit 2: the outlines had more
         contours than rows, bit 3: inconsistent rows (nothing).  The read-back happens here, chunk by chunk."""
-        if not self._simple_chunks:
+        if not self._simple.chunks:
             return [], np.zeros((0, 4), dtype=np.int64)
-        frames, counts, left = [], [], self._simple_frames
-        for simple, vertices, cnt in self._simple_chunks:
-            take = min(left, self.simple_chunk)
-            c = cnt[:take].cpu().numpy()
-            rows, verts = simple[:take].cpu().numpy(), vertices[:take].cpu().numpy()
+        frames, counts = [], []
+        for take, (simple, vertices, cnt) in self._simple.filled(self.simple_chunk):
+            c = cnt.cpu().numpy()
+            rows, verts = simple.cpu().numpy(), vertices.cpu().numpy()
             frames.extend((rows[f, :int(c[f, 0])], verts[f, :int(c[f, 1])]) for f in range(take))
             counts.append(c)
-            left -= take
         return frames, np.concatenate(counts)
 
     def outline_report(self):
@@ -605,41 +580,33 @@ class FlowPredictor:
         (perimeter, contours, vertices) of each region; flags = int64 numpy [frames], bit 0: more than max_vertices vertices (no
         contours at all for that frame, shape's contours column -1), bit 1: more than max_contours contours (the first max_contours
         are there).  The read-back happens here, chunk by chunk."""
-        if not self._outline_chunks:
+        if not self._outlines.chunks:
             return [], np.zeros((0,), dtype=np.int64)
-        regions = np.concatenate([counts[:, 1].cpu().numpy() for _, counts in self._region_chunks])
-        frames, flags, left = [], [], self._outline_frames
-        for contours, vertices, shape, counts in self._outline_chunks:
-            take = min(left, self.outline_chunk)
-            c = counts[:take].cpu().numpy()
-            rows, verts, shp = contours[:take].cpu().numpy(), vertices[:take].cpu().numpy(), shape[:take].cpu().numpy()
+        regions = np.concatenate([counts[:, 1].cpu().numpy() for _, counts in self._regions.chunks])
+        frames, flags = [], []
+        for take, (contours, vertices, shape, counts) in self._outlines.filled(self.outline_chunk):
+            c = counts.cpu().numpy()
+            rows, verts, shp = contours.cpu().numpy(), vertices.cpu().numpy(), shape.cpu().numpy()
             for f in range(take):
                 total = 0 if c[f, 3] & 1 else int(c[f, 2])
                 frames.append((rows[f, :int(c[f, 1])], verts[f, :total], shp[f, :int(regions[len(frames)])]))
             flags.append(c[:, 3])
-            left -= take
         return frames, np.concatenate(flags)
 
     def _keep_tracks(self, index, table, counts, row, link=None):
         """Links and track ids of the piece region_table just wrote (rows row.. of the newest chunk), against the frame tabulated before
         it; then that piece's last frame becomes the previous frame.  Nothing is read back.  link: the piece's (mvs, frame size, stats)
-        under compensate=True."""
-        take, dev = index.shape[0], index.device
-        if row == 0:
-            self._track_chunks.append((torch.zeros((self.REPORT_CHUNK, self.max_regions, 4), dtype=torch.int64, device=dev),
-                                       torch.zeros((self.REPORT_CHUNK, 2), dtype=torch.int64, device=dev)))
+        under compensate=True.  Returns the piece's track rows (views of the buffer)."""
+        tracks, flags = self._tracks.rows(row, index.shape[0], self.REPORT_CHUNK, index.device)
         if self._track_state is None:
-            self._track_state = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._track_state = torch.zeros(2, dtype=torch.int64, device=index.device)
         prev = self._track_prev
-        if link is None:
-            back, fwd, link_counts = ops.region_links(index, table, counts, None if prev is None else prev[:3], self.max_pairs, self.min_overlap)
-        else:
-            back, fwd, link_counts = ops.region_links(index, table, counts, None if prev is None else prev[:3], self.max_pairs, self.min_overlap,
-                                                      mv=link[0], frame_size=link[1], pair_stats=link[2])
-        tracks, flags = self._track_chunks[-1]
-        ops.region_tracks(back, fwd, counts, self._track_state, None if prev is None else prev[3], out=tracks[row:row + take])
-        flags[row:row + take].copy_(link_counts)
-        self._track_prev = (index[-1].clone(), table[-1].clone(), counts[-1].clone(), tracks[row + take - 1].clone())
+        kw = {} if link is None else dict(mv=link[0], frame_size=link[1], pair_stats=link[2])
+        back, fwd, link_counts = ops.region_links(index, table, counts, None if prev is None else prev[:3], self.max_pairs, self.min_overlap, **kw)
+        ops.region_tracks(back, fwd, counts, self._track_state, None if prev is None else prev[3], out=tracks)
+        flags.copy_(link_counts)
+        self._track_prev = (index[-1].clone(), table[-1].clone(), counts[-1].clone(), tracks[-1].clone())
+        return tracks
 
     def track_report(self, with_cuts=False):
         """track=True: (tracks, overflowed) for every frame of region_report(), in its order: tracks[f] = int64 numpy [rows, 4] = (track
@@ -647,15 +614,13 @@ class FlowPredictor:
         rows[f]; overflowed = int64 numpy [frames], 1 where the frame's pair table overflowed (all its regions were born: raise
         max_pairs).  with_cuts=True appends cuts = int64 numpy [frames], 1 where compensate=True found the pair flagged as a scene cut
         (all its regions were born as well).  The read-back happens here, chunk by chunk."""
-        if not self._track_chunks:
+        if not self._tracks.chunks:
             return ([], np.zeros((0,), dtype=np.int64)) + ((np.zeros((0,), dtype=np.int64),) if with_cuts else ())
-        rows, flags, left = [], [], self._region_frames
-        for (tracks, link_counts), (_, counts) in zip(self._track_chunks, self._region_chunks):
-            take = min(left, self.REPORT_CHUNK)
-            c, t = counts[:take].cpu().numpy(), tracks[:take].cpu().numpy()
+        rows, flags = [], []
+        for take, (_, counts), (tracks, link_counts) in self._regions.filled(self.REPORT_CHUNK, self._tracks):
+            c, t = counts.cpu().numpy(), tracks.cpu().numpy()
             rows.extend(t[f, :int(c[f, 1])] for f in range(take))
-            flags.append(link_counts[:take, 1].cpu().numpy())
-            left -= take
+            flags.append(link_counts[:, 1].cpu().numpy())
         flags = np.concatenate(flags)                                        # the flag word: bit 0 overflow, bit 1 cut
         return (rows, flags & 1, (flags >> 1) & 1) if with_cuts else (rows, flags & 1)
 
