@@ -204,6 +204,13 @@ _EXT8_HOOKS = [
 ]
 EXT8_MAGIC = 0x4653455854414238  # FS_EXT8_MAGIC
 
+# members of fs_ext9_api, the tenth table (append-only, behind the nine frozen ones), in declaration order after `magic` and `size`
+_EXT9_HOOKS = [
+    ("ortho_accumulate", c_int, [c_void] * 3 + [c_int] * 5 + [c_void, ctypes.c_uint32] + [c_int] * 7 + [c_void] * 3),
+    ("ortho_compose", c_int, [c_void] * 3 + [c_int, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, c_void, c_void]),
+]
+EXT9_MAGIC = 0x4653455854414239  # FS_EXT9_MAGIC
+
 
 def _struct(name, *fields):
     return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
@@ -233,6 +240,8 @@ FsExt7Api = _struct("FsExt7Api", *_EXT_HEAD, *_members(_EXT7_HOOKS))
 FsHookTables7 = _struct("FsHookTables7", ("base6", FsHookTables6), ("ext7", FsExt7Api))
 FsExt8Api = _struct("FsExt8Api", *_EXT_HEAD, *_members(_EXT8_HOOKS))
 FsHookTables8 = _struct("FsHookTables8", ("base7", FsHookTables7), ("ext8", FsExt8Api))
+FsExt9Api = _struct("FsExt9Api", *_EXT_HEAD, *_members(_EXT9_HOOKS))
+FsHookTables9 = _struct("FsHookTables9", ("base8", FsHookTables8), ("ext9", FsExt9Api))
 
 # One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
 # the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
@@ -249,6 +258,7 @@ _TABLES = [
     _Table("six", "sixth", _EXT6_HOOKS, "EXT6_MAGIC", FsExt6Api, FsHookTables6, "ext6"),
     _Table("seven", "seventh", _EXT7_HOOKS, "EXT7_MAGIC", FsExt7Api, FsHookTables7, "ext7"),
     _Table("eight", "eighth", _EXT8_HOOKS, "EXT8_MAGIC", FsExt8Api, FsHookTables8, "ext8"),
+    _Table("nine", "ninth", _EXT9_HOOKS, "EXT9_MAGIC", FsExt9Api, FsHookTables9, "ext9"),
 ]
 _TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
@@ -329,7 +339,7 @@ def _hook_names(n):
 
 
 (hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
- ext8_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
+ ext8_hook_names, ext9_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

@@ -562,7 +562,19 @@ static int fs_mosaic_resolve(const uint16_t* votes, int K, int CH, int CW, uint8
     return fs::launch_mosaic_resolve(votes, K, CH, CW, cls, conf, seen, reinterpret_cast<long long*>(totals), S(stream));
 }
 
-// the nine tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// the orthophoto under the mosaic (ortho_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_ortho_accumulate(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW,
+                               const int64_t* pose, uint32_t ordinal, int H, int W, int mode, int CH, int CW, int ox, int oy, uint64_t* rank, uint32_t* rgba,
+                               fs_stream stream) {
+    return fs::launch_ortho_accumulate(frame, u, v, format, matrix, full_range, FH, FW, reinterpret_cast<const long long*>(pose), ordinal, H, W, mode, CH, CW,
+                                       ox, oy, reinterpret_cast<unsigned long long*>(rank), rgba, S(stream));
+}
+static int fs_ortho_compose(const uint32_t* rgba, const uint8_t* cls, const uint8_t* palette, int K, uint32_t edge_set, uint32_t fill, int CH, int CW,
+                            uint8_t* out, fs_stream stream) {
+    return fs::launch_ortho_compose(rgba, cls, palette, K, edge_set, fill, CH, CW, out, S(stream));
+}
+
+// the ten tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -672,7 +684,15 @@ static const fs_hook_tables5& hook_tables(void) {
         fs_mosaic_accumulate,
         fs_mosaic_resolve,
     }};
+    // fs_ext8_api is frozen too (four members, 48 bytes; tests/test_mosaic_cpu.py); the tenth table lies behind it, and &all9.base8 is &all9.
+    static const fs_hook_tables9 all9 = {all8, {
+        FS_EXT9_MAGIC,
+        sizeof(fs_ext9_api),
+        fs_ortho_accumulate,
+        fs_ortho_compose,
+    }};
     {
+        const fs_hook_tables8& all8 = all9.base8;
         const fs_hook_tables7& all7 = all8.base7;  // from here on both names mean the head of the whole object, not the copies it was built from
         const fs_hook_tables6& all6 = all7.base6;
         return all6.base5;

@@ -128,4 +128,34 @@ __device__ __forceinline__ void resized4(const IngestSrc& s, int oy, int x0, int
         for (int c = 0; c < 3; ++c) v[i][c] = fminf(fmaxf(rintf(v[i][c]), 0.f), 255.f);  // .round_().clamp_(0, 255): the stored uint8 image
 }
 
+// The one-pixel form: pixel (oy, ox) of the same resized image (oy < h, ox < w), for a gather that wants single pixels at unrelated
+// places (ortho_ops.hip).  The same operations in the same order as resized4 on that column, so the two agree bit for bit; MODE as there.
+template <bool YUV, int MODE>
+__device__ __forceinline__ void resized1(const IngestSrc& s, int oy, int ox, float sy, float sx, float (&v)[3]) {
+    if (MODE == 2) {
+        // The rounding line below leaves a whole number in [0, 255] as it is, and MODE 2 still runs it: returning here lets the compiler
+        // pack a caller's clip(x >> 8) bytes straight from the integers with v_ashr_pk_u8_i32, and the dword a YUV caller then stored
+        // had bits of the shifted operand ORed into its third byte on gfx950 (tests/test_gpu_ortho.py, the identity-resize YUV cases).
+        fetch<YUV>(s, oy, ox, v);
+    } else if (MODE == 1) {
+        const LinCoord cy = lin_coord(oy, s.H, sy, 0);
+        float a[3], b[3];
+        fetch<YUV>(s, cy.i0, ox, a);
+        fetch<YUV>(s, cy.i1, ox, b);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = __fadd_rn(__fmul_rn(cy.w0, a[c]), __fmul_rn(cy.w1, b[c]));
+    } else {
+        const LinCoord cy = lin_coord(oy, s.H, sy, 0), cx = lin_coord(ox, s.W, sx, 0);
+        float t00[3], t01[3], t10[3], t11[3];
+        fetch<YUV>(s, cy.i0, cx.i0, t00);
+        fetch<YUV>(s, cy.i0, cx.i1, t01);
+        fetch<YUV>(s, cy.i1, cx.i0, t10);
+        fetch<YUV>(s, cy.i1, cx.i1, t11);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = bilerp(t00[c], t01[c], t10[c], t11[c], cy, cx);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = fminf(fmaxf(rintf(v[c]), 0.f), 255.f);
+}
+
 }  // namespace fs

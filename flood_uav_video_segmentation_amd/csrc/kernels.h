@@ -406,6 +406,15 @@ int launch_mosaic_accumulate(const uint8_t* mask, const long long* poses, int n,
                              hipStream_t s);
 int launch_mosaic_resolve(const uint16_t* votes, int K, int CH, int CW, uint8_t* cls, uint8_t* conf, uint32_t* seen, long long* totals, hipStream_t s);
 
+// The orthophoto under the mosaic (ortho_ops.hip, ortho_defs.h; definitions: include/floodseg_test.h, ortho_accumulate and
+// ortho_compose).  The launchers refuse bad arguments before they launch anything.  u and v as frame_prepare takes them; cls may be
+// nullptr in launch_ortho_compose (the plain orthophoto).  No workspace; nothing is allocated, synchronised or read on the host.
+int launch_ortho_accumulate(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW,
+                            const long long* pose, uint32_t ordinal, int H, int W, int mode, int CH, int CW, int ox, int oy, unsigned long long* rank,
+                            uint32_t* rgba, hipStream_t s);
+int launch_ortho_compose(const uint32_t* rgba, const uint8_t* cls, const uint8_t* palette, int K, uint32_t edge_set, uint32_t fill, int CH, int CW,
+                         uint8_t* out, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

@@ -42,6 +42,13 @@ def _check_link_vectors(who, link_vectors, grids):
     return bool(link_vectors)
 
 
+def _check_link_sources(who, link_sources, link_vectors):
+    """link_sources hands out the decoded frames of the very windows whose vectors link_vectors hands out: the one is of no use without the other."""
+    if link_sources and not link_vectors:
+        raise ValueError(f"{who}: link_sources=True needs link_vectors=True (the frames go with the poses fitted to those vectors), got link_vectors={link_vectors}")
+    return bool(link_sources)
+
+
 def _check_hold_cuts(who, hold_cuts, grids, scene_cut):
     """hold_cuts reacts to the cut flags the grid estimator's matcher writes: without them it could never do anything."""
     if hold_cuts and (grids != "estimate" or scene_cut is None):
@@ -66,15 +73,21 @@ class PredictWindows:
     frame the matcher's table of that frame against the frame before it, all void for frame 0), "link_frame_size" (the decoded frame's
     height and width) and, with intra_bias / scene_cut set, "link_stats" (int32 [frame_delta, 4], the same pairs' stats rows): what
     FlowPredictor(compensate=True) links the regions with.  One more search per window (the pair that ends in the window's key frame),
-    unless hold_cuts has searched it; with no_warp every pair is searched for its vectors alone."""
+    unless hold_cuts has searched it; with no_warp every pair is searched for its vectors alone.
+
+    link_sources=True (extension; needs link_vectors=True): an item also carries "link_sources", a list of source(frame_id + p) for the
+    window's frame_delta emitted frames (None where a frame does not exist): what FlowPredictor(ortho=...) samples the orthophoto from.
+    The frames go through the decode cache; with no_warp the in-between frames are decoded for this alone."""
 
     hold_cuts = False
     link_vectors = False
+    link_sources = False
 
     def __init__(self, data_root, predict_v_id, frame_delta=5, no_warp=False, size=None, device="cuda", grids="files", search=16,
-                 penalty=0, intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False):
+                 penalty=0, intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False, link_sources=False):
         self.hold_cuts = _check_hold_cuts("PredictWindows", hold_cuts, grids, scene_cut)
         self.link_vectors = _check_link_vectors("PredictWindows", link_vectors, grids)
+        self.link_sources = _check_link_sources("PredictWindows", link_sources, self.link_vectors)
         self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
         self.data_root, self.video_id = data_root, predict_v_id
         self.frame_delta, self.no_warp = frame_delta, no_warp
@@ -214,6 +227,8 @@ class PredictWindows:
         stats = est.window_link_stats(f_index, self.frame_delta)
         if stats is not None:
             item["link_stats"] = stats
+        if self.link_sources:
+            item["link_sources"] = [self.source(f_index + p) for p in range(self.frame_delta)]
 
 
 def read_label_list(data_list, frame_delta):
@@ -253,9 +268,12 @@ class EvalWindows(PredictWindows):
     (batch_size_test = 1, flow/base.py:164)."""
 
     def __init__(self, data_root, data_list, split="test", frame_delta=5, no_warp=False, size=None, center_crop=None,
-                 classes_ignore=(), device="cuda", grids="files", search=16, penalty=0, intra_bias=None, scene_cut=None):
+                 classes_ignore=(), device="cuda", grids="files", search=16, penalty=0, intra_bias=None, scene_cut=None, link_sources=False):
         if split not in ("val", "test"):
             raise ValueError("EvalWindows mirrors the val / test splits; use PredictWindows for predict")
+        if link_sources:  # taken so that the three datasets share a signature; an item here is one labelled frame and carries no link keys
+            raise ValueError(f"EvalWindows does not support link_sources (its items carry no link_mvs to go with the frames), got link_sources={link_sources}; "
+                             "use PredictWindows or RawVideoWindows with link_vectors=True")
         self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
         self.data_root, self.split = data_root, split
         self.frame_delta, self.no_warp = frame_delta, no_warp
@@ -359,9 +377,11 @@ class RawVideoWindows(PredictWindows):
     which is not the stream's Y (range, matrix and the clipping of the conversion all enter)."""
 
     def __init__(self, path, height, width, pix_fmt, frame_delta=5, no_warp=False, size=None, grids="estimate", search=16, penalty=0,
-                 matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False):
+                 matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False,
+                 link_sources=False):
         self.hold_cuts = _check_hold_cuts("RawVideoWindows", hold_cuts, grids, scene_cut)
         self.link_vectors = bool(link_vectors)
+        self.link_sources = _check_link_sources("RawVideoWindows", link_sources, self.link_vectors)
         if pix_fmt not in RAW_PIX_FMTS:
             raise ValueError(f"RawVideoWindows: pix_fmt must be one of {RAW_PIX_FMTS}, got {pix_fmt!r}")
         if grids == "files":

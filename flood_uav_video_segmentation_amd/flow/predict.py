@@ -51,7 +51,7 @@ from .. import _lib, ops
 from .._lib import check, ptr, stream_ptr
 from . import crops
 
-PALETTE = np.array([[0, 0, 0], [30, 95, 170], [65, 117, 5], [212, 98, 1], [255, 244, 116]], dtype=np.uint8)  # dataset/flow/list/colors.txt
+PALETTE = np.array(ops.FLOOD_PALETTE, dtype=np.uint8)  # dataset/flow/list/colors.txt (one table: ops.ortho_compose's default is the same object)
 
 
 class FrameRows:
@@ -200,16 +200,27 @@ class FlowPredictor:
     own); up to mosaic_bridge failed pairs running are bridged with the last good model, after which -- or at a scene cut -- the chain is
     lost and the frames vote nowhere.  mosaic_report() resolves the canvas and reads back once; clear_report() drops canvas and state
     (the next frame anchors a new mosaic), reset() keeps them.  All these defaults are guesses, NOT validated on real video; an affine
-    per pair is not a homography, the chain drifts over a long flight and nothing closes loops."""
+    per pair is not a homography, the chain drifts over a long flight and nothing closes loops.
+
+    ortho="centre" | "latest" (extension, needs mosaic=; None: off, and none of its ops is ever called): the orthophoto under that mosaic
+    (DESIGN §3.19).  Every window must then also come with link_sources (the datasets' link_sources=True): after the pose chain each
+    frame's pixels -- the uint8 image the network saw -- are gathered into a canvas of the mosaic's size by ops.ortho_accumulate with that
+    frame's pose row and its ordinal, the number of frames since the anchor; a None entry (a frame that does not exist) is skipped.
+    "centre": per canvas pixel the view in which the ground point is nearest the optical axis wins; "latest": the newest frame.
+    ortho_report() draws it, by default with the extent map over it, and reads back once; clear_report() drops the canvas and the
+    counter, reset() keeps them.  No feathering or exposure matching across seams, no lens model, the mask's resolution, and the chain's
+    drift shows as broken seams; NOT validated on real video."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
+    ORTHO_MAX_FRAMES = 1 << 31  # ordinals 0 .. 2^31 - 1: what ortho_report()'s int32 src can name
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
                  max_regions=1024, track=False, min_overlap=1, max_pairs=None, compensate=False, outlines=False, max_contours=4096,
                  max_vertices=32768, simplify=None, simplify_rounds=32, keep_window_regions=False, stabilize=None, stabilize_trust=None,
                  stabilize_compensate=False, proximity=None, proximity_sources=(1,), proximity_targets=(3, 4), proximity_max=None, mosaic=None,
-                 mosaic_classes=None, mosaic_rounds=4, mosaic_tol=1.0, mosaic_min_inliers=12, mosaic_exclude=(1,), mosaic_bridge=2, mosaic_origin=None):
+                 mosaic_classes=None, mosaic_rounds=4, mosaic_tol=1.0, mosaic_min_inliers=12, mosaic_exclude=(1,), mosaic_bridge=2, mosaic_origin=None,
+                 ortho=None):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -345,6 +356,13 @@ class FlowPredictor:
         self._mosaic_state = None
         self._mosaic_at = None
         self._mosaic_poses = FrameRows(((16,), torch.int64))  # the per-frame pose rows, REPORT_CHUNK frames a chunk
+        if ortho is not None and ortho not in ops.ORTHO_MODES:
+            raise ValueError(f"FlowPredictor: ortho must be None or one of {sorted(ops.ORTHO_MODES)}, got {ortho!r}")
+        if ortho is not None and self.mosaic is None:
+            raise ValueError(f"FlowPredictor: ortho={ortho!r} needs mosaic=(CH, CW): the orthophoto is gathered with the mosaic's poses, onto its canvas")
+        self.ortho = ortho
+        self._ortho_planes = None  # (rank, rgba) [CH, CW] on the device
+        self._ortho_frames = 0     # frames since the anchor: the next frame's ordinal
 
     # the chunk lists that tests count, under the names they had before the tables moved into FrameRows
     _report_chunks = property(lambda self: self._extent.chunks)
@@ -368,6 +386,7 @@ class FlowPredictor:
             table.clear()  # the tracks' previous frame and next id stay, and so does the stabiliser's state plane
         self._despeckle_counts = []
         self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
+        self._ortho_planes, self._ortho_frames = None, 0
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -433,9 +452,10 @@ class FlowPredictor:
         """What _link_inputs returned, for the tracks: theirs only under compensate=True (stabilize_compensate=True alone leaves them in place)."""
         return link if self.compensate else None
 
-    def _keep_mosaic(self, masks, link):
+    def _keep_mosaic(self, masks, link, sources=None):
         """The window's masks into the vote canvas: one camera-motion model per frame pair from the window's tables, the pose chain carried
-        on in its device state, the gather, and the pose rows into the next rows of the chunked buffers (nothing is read back)."""
+        on in its device state, the gather, and the pose rows into the next rows of the chunked buffers (nothing is read back).  ortho=:
+        then each frame's pixels into the orthophoto canvas, with that frame's pose row."""
         masks = masks.contiguous()
         n, h, w = masks.shape
         dev = masks.device
@@ -450,6 +470,32 @@ class FlowPredictor:
         ops.mosaic_accumulate(masks, poses, self._mosaic_votes, self._mosaic_at)
         for done, take, _, (rows,) in self._mosaic_poses.pieces(n, self.REPORT_CHUNK, dev):
             rows.copy_(poses[done:done + take])
+        if self.ortho:
+            if self._ortho_planes is None:
+                self._ortho_planes = ops.ortho_canvas(self.mosaic, dev)
+            for p in range(n):
+                if sources[p] is not None:
+                    ops.ortho_accumulate(sources[p], poses[p], self._ortho_frames + p, (h, w), *self._ortho_planes, self._mosaic_at, self.ortho)
+            self._ortho_frames += n
+
+    def ortho_report(self, palette=PALETTE, alpha=None, edge=(), fill=(0, 0, 0), overlay=True):
+        """ortho=: (image, src, covered) of the frames predicted since the start (or clear_report()): image uint8 numpy [CH, CW, 3], the
+        orthophoto -- with overlay=True the mosaic's classes blended over it (palette, alpha and edge as ops.ortho_compose takes them) --
+        showing `fill` where no frame has been; src int32 [CH, CW], the ordinal (frames since the anchor: the row of mosaic_report()'s
+        poses) of the frame each pixel came from, -1 where none; covered, the number of canvas pixels some frame won.  mosaic_resolve
+        (overlay=True) and ortho_compose run here, and so does the ONE read-back."""
+        if not self.ortho:
+            raise ValueError("FlowPredictor: ortho_report() needs ortho='centre' or 'latest'")
+        ch, cw = self.mosaic
+        if self._ortho_planes is None:
+            image = np.empty((ch, cw, 3), np.uint8)
+            image[:] = np.array(fill, np.uint8)
+            return image, np.full((ch, cw), -1, np.int32), 0
+        rank, rgba = self._ortho_planes
+        cls = ops.mosaic_resolve(self._mosaic_votes)[0] if overlay else None
+        image = ops.ortho_compose(rgba, cls, palette, alpha, fill, edge)
+        src = torch.where(rank == -1, rank, rank & 0xFFFFFFFF).to(torch.int32).cpu().numpy()
+        return image.cpu().numpy(), src, int((src >= 0).sum())
 
     def mosaic_report(self):
         """mosaic=(CH, CW): (cls, conf, seen, totals, poses) of the frames predicted since the start (or clear_report()): cls uint8 numpy
@@ -484,6 +530,19 @@ class FlowPredictor:
             raise ValueError(f"FlowPredictor: link_mvs must be [n, blocks, 7] and link_stats [n, 4] for the window's n = {n} frames, got "
                              f"{tuple(link_mvs.shape)} and {None if link_stats is None else tuple(link_stats.shape)}")
         return link_mvs, (int(link_frame_size[0]), int(link_frame_size[1])), link_stats
+
+    def _ortho_sources(self, n, link_sources):
+        """ortho=: the window's decoded frames, one (frame, chroma, fmt, matrix, full_range) or None per emitted frame, checked; None otherwise."""
+        if not self.ortho:
+            return None
+        if link_sources is None or len(link_sources) != n:
+            raise ValueError(f"FlowPredictor: ortho={self.ortho!r} needs link_sources with every window, one entry per frame of its n = {n} (an "
+                             f"estimate-mode dataset with link_sources=True provides them), got {None if link_sources is None else len(link_sources)}; "
+                             "the orthophoto is never left with a hole instead")
+        if self._ortho_frames + n > self.ORTHO_MAX_FRAMES:  # the op takes ordinals up to 2^32 - 2; ortho_report()'s src is int32 with -1 for "none"
+            raise ValueError(f"FlowPredictor: ortho= holds at most {self.ORTHO_MAX_FRAMES} frames per mosaic (ortho_report()'s src is int32), got "
+                             f"{self._ortho_frames} + {n}; clear_report() starts a new one")
+        return list(link_sources)
 
     def _keep_regions(self, masks, conf, link=None):
         """The window's region tables into the next rows of the chunked buffers (region_table writes its rows whole; nothing is read)."""
@@ -624,7 +683,7 @@ class FlowPredictor:
         flags = np.concatenate(flags)                                        # the flag word: bit 0 overflow, bit 1 cut
         return (rows, flags & 1, (flags >> 1) & 1) if with_cuts else (rows, flags & 1)
 
-    def _finish(self, masks, conf, n, to_host, link=None):
+    def _finish(self, masks, conf, n, to_host, link=None, sources=None):
         """Stabilise, despeckle, score, keep the reports, and hand out what the caller asked for: masks, or (masks, conf) with
         confidence=True."""
         if self.stabilize:
@@ -635,23 +694,25 @@ class FlowPredictor:
         if self.regions:
             self._keep_regions(masks, conf, self._track_link(link))
         if self.mosaic:
-            self._keep_mosaic(masks, link)
+            self._keep_mosaic(masks, link, sources)
         if not self.confidence:
             return masks.cpu().numpy() if to_host else masks            # :277
         self._keep_report(masks, conf)
         return (masks.cpu().numpy(), conf.cpu().numpy()) if to_host else (masks, conf)
 
     def predict_window(self, frame_prev, frame_next, mvs_left, mvs_right, profiler=None, to_host=True, key_ids=None, key_cache=None,
-                       weights=None, link_mvs=None, link_frame_size=None, link_stats=None):
+                       weights=None, link_mvs=None, link_frame_size=None, link_stats=None, link_sources=None):
         """key_cache: a KeyframeCache to use for this call instead of the predictor's own (predict_clip's fallback passes a
         cache that lives for the clip only).  weights: an item's "weights" (the window datasets' hold_cuts; ops.window_weights) for
         the whole-frame and the sliding-crop tails alike, None = the reference's blend.  The key-frame cache is unaffected: the
         network's outputs do not depend on them.  link_mvs, link_frame_size, link_stats: an item's keys of those names (the estimate-mode
-        datasets' link_vectors=True), needed and used with compensate=True only."""
+        datasets' link_vectors=True), needed and used with compensate=True only.  link_sources: an item's key of that name (the datasets'
+        link_sources=True), needed and used with ortho= only."""
         assert frame_prev.shape[0] == 1                      # flow/base.py:263
         assert len(mvs_left) == len(mvs_right)               # :264
         n = len(mvs_left) + 1                                # :266 -- the list length encodes n, also for no_warp dummies
         link = self._link_inputs(n, link_mvs, link_frame_size, link_stats)
+        sources = self._ortho_sources(n, link_sources)
         cache = key_cache if key_cache is not None else self.key_cache
         kc = cache.window(*key_ids) if (cache is not None and key_ids is not None) else None
         conf = None
@@ -683,7 +744,7 @@ class FlowPredictor:
             _, masks = crops.compute_output(self.model, n, frame_prev, frame_next, mvs_left, mvs_right, self.crop[0], self.crop[1],
                                             self.classes, profiler, want_mask=True, key_cache=kc, out_size=self.out_size, want_canvas=False,
                                             weights=weights)
-        return self._finish(masks, conf, n, to_host, link)
+        return self._finish(masks, conf, n, to_host, link, sources)
 
     def _native(self, frame):
         return self.out_size == (frame.shape[2], frame.shape[3])
@@ -740,6 +801,7 @@ class FlowPredictor:
             assert w["frame_prev"].shape[0] == 1 and len(w["mvs_left"]) == len(w["mvs_right"])   # flow/base.py:263-264
             n = len(w["mvs_left"]) + 1
             link = self._link_inputs(n, w.get("link_mvs"), w.get("link_frame_size"), w.get("link_stats"))
+            sources = self._ortho_sources(n, w.get("link_sources"))
             lo_prev, lo_next = store[w["key_ids"][0]], store[w["key_ids"][1]]
             h, wd = w["frame_prev"].shape[2], w["frame_prev"].shape[3]
             conf = None
@@ -764,7 +826,7 @@ class FlowPredictor:
                 _, masks = crops.compute_output(fm, n, w["frame_prev"], w["frame_next"], w["mvs_left"], w["mvs_right"], self.crop[0],
                                                 self.crop[1], self.classes, profiler, want_mask=True, out_size=self.out_size,
                                                 lows=(lo_prev, lo_next), want_canvas=False, weights=w.get("weights"))
-            return self._finish(masks, conf, n, to_host, link)
+            return self._finish(masks, conf, n, to_host, link, sources)
 
         while True:
             plain = None  # a window that cannot take the look-ahead route (no key_ids / feature mode / foreign network)
@@ -797,7 +859,8 @@ class FlowPredictor:
             if plain is not None:
                 yield self.predict_window(plain["frame_prev"], plain["frame_next"], plain["mvs_left"], plain["mvs_right"], profiler, to_host,
                                           plain.get("key_ids"), key_cache=local_cache, weights=plain.get("weights"), link_mvs=plain.get("link_mvs"),
-                                          link_frame_size=plain.get("link_frame_size"), link_stats=plain.get("link_stats"))
+                                          link_frame_size=plain.get("link_frame_size"), link_stats=plain.get("link_stats"),
+                                          link_sources=plain.get("link_sources"))
             elif exhausted and not pending and not queue:
                 return
 

@@ -1033,6 +1033,116 @@ def mosaic_resolve(votes):
     return cls, conf, seen, totals
 
 
+# ------------------------------------------------------------------------------------------ the orthophoto under the mosaic
+ORTHO_MODES = {"centre": 0, "latest": 1}
+FLOOD_PALETTE = ((0, 0, 0), (30, 95, 170), (65, 117, 5), (212, 98, 1), (255, 244, 116))  # dataset/flow/list/colors.txt; flow/predict.py's PALETTE is this table
+
+
+def ortho_canvas(size, device):
+    """A fresh orthophoto canvas of size = (CH, CW) on `device`: (rank int64 [CH,CW] holding the uint64 rank words, every bit set =
+    empty; rgba int32 [CH,CW], zero = unseen) for ops.ortho_accumulate."""
+    ch, cw = _mosaic_size(size, "size", "floodseg.ortho_canvas")
+    return torch.full((ch, cw), -1, dtype=torch.int64, device=device), torch.zeros((ch, cw), dtype=torch.int32, device=device)
+
+
+def _ortho_planes(rank, rgba, what):
+    if rgba.dtype != torch.int32 or rgba.dim() != 2 or not rgba.is_contiguous():
+        raise ValueError(f"{what}: rgba must be a contiguous int32 [CH,CW] tensor, got {rgba.dtype} {tuple(rgba.shape)}")
+    if rank is not None and (rank.dtype != torch.int64 or tuple(rank.shape) != tuple(rgba.shape) or not rank.is_contiguous()):
+        raise ValueError(f"{what}: rank must be a contiguous int64 {list(rgba.shape)} tensor like rgba, got {rank.dtype} {tuple(rank.shape)}")
+    return _mosaic_size(rgba.shape, "the canvas", what)
+
+
+def ortho_accumulate(source, pose, ordinal, mask_size, rank, rgba, origin, mode="centre"):
+    """One frame's pixels gathered into the orthophoto canvas (definition: include/floodseg_test.h, ortho_accumulate).
+    source = (frame, chroma, fmt, matrix, full_range) as the window datasets' source(f_id) returns it and prepare_frame takes it; the
+    image sampled is that frame through prepare_frame's resize to mask_size = (H, W), as stored uint8.  pose: ONE row of pose_chain's
+    output, int64 [16] on the device; ordinal: the frame's number since the anchor (0 .. 2^32 - 2).  rank, rgba: ortho_canvas's planes,
+    UPDATED IN PLACE (and returned): a canvas pixel takes the frame's pixel where the frame's rank is strictly smaller -- mode "centre":
+    the view in which the ground point is nearest the optical axis, ties to the earlier frame; "latest": the newest frame.  origin =
+    (oy, ox) as mosaic_accumulate's.  One launch that costs the frame's footprint; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.ortho_accumulate"
+    if not isinstance(source, (tuple, list)) or len(source) != 5:
+        raise ValueError(f"{what}: source must be the 5-tuple (frame, chroma, fmt, matrix, full_range), got a {type(source).__name__}"
+                         + (f" of {len(source)}" if isinstance(source, (tuple, list)) else ""))
+    frame, chroma, fmt, matrix, full_range = source
+    if fmt not in _FORMATS:
+        raise ValueError(f"{what}: fmt must be one of {sorted(_FORMATS)}, got {fmt!r}")
+    if matrix not in _MATRICES:
+        raise ValueError(f"{what}: matrix must be one of {sorted(_MATRICES)}, got {matrix!r}")
+    if mode not in ORTHO_MODES:
+        raise ValueError(f"{what}: mode must be one of {sorted(ORTHO_MODES)}, got {mode!r}")
+    if not 0 <= int(ordinal) < 0xFFFFFFFF:
+        raise ValueError(f"{what}: ordinal must be 0..{0xFFFFFFFF - 1}, got {ordinal}")
+    planes = [] if chroma is None else list(chroma) if isinstance(chroma, (tuple, list)) else [chroma]
+    if frame.dtype != torch.uint8 or any(p.dtype != torch.uint8 for p in planes):
+        raise ValueError(f"{what}: frames must be uint8, got {[str(t.dtype) for t in [frame] + planes]}")
+    rgb = fmt == "rgb24"
+    if frame.dim() != (3 if rgb else 2) or (rgb and frame.shape[2] != 3):
+        raise ValueError(f"{what}: a {fmt} frame must be {'[H,W,3]' if rgb else 'the Y plane [H,W]'}, got {tuple(frame.shape)}")
+    fh, fw = _mosaic_size(frame.shape[:2], "the frame", what)
+    want = [] if rgb else [((fh + 1) // 2, (fw + 1) // 2, 2)] if fmt == "nv12" else [((fh + 1) // 2, (fw + 1) // 2)] * 2
+    if [tuple(p.shape) for p in planes] != want:
+        raise ValueError(f"{what}: a {fh} x {fw} {fmt} frame takes chroma {want if want else None}, got {[tuple(p.shape) for p in planes]}")
+    h, w = _mosaic_size(mask_size, "mask_size", what)
+    if pose.dtype != torch.int64 or tuple(pose.shape) != (16,) or not pose.is_contiguous():
+        raise ValueError(f"{what}: pose must be one contiguous int64 [16] row of pose_chain's output, got {pose.dtype} {tuple(pose.shape)}")
+    ch, cw = _ortho_planes(rank, rgba, what)
+    oy, ox = _mosaic_origin(origin, what)
+    dev = one_device(frame, pose, rank, rgba, *planes, what=what)
+    with torch.cuda.device(dev):
+        planes = [p.contiguous() for p in planes]
+        check(lib.fs_ortho_accumulate(ptr(frame.contiguous()), ptr(planes[0]) if planes else None, ptr(planes[1]) if len(planes) > 1 else None, _FORMATS[fmt],
+                                      _MATRICES[matrix], int(bool(full_range)), fh, fw, ptr(pose), int(ordinal), h, w, ORTHO_MODES[mode], ch, cw, ox, oy,
+                                      ptr(rank), ptr(rgba), stream_ptr()))
+    return rank, rgba
+
+
+def ortho_compose(rgba, cls=None, palette=FLOOD_PALETTE, alpha=None, fill=(0, 0, 0), edge=()):
+    """The orthophoto canvas drawn, optionally with the extent map over it (definition: include/floodseg_test.h, ortho_compose): rgba
+    int32 [CH,CW] of ortho_accumulate, cls = mosaic_resolve's uint8 class plane or None (the plain orthophoto) -> uint8 [CH,CW,3].
+    Unseen ground shows fill = (r, g, b).  palette: uint8 [K,3] with alpha (0..255, default 96) or [K,4] as compose_frame takes it;
+    a class below K is blended over the imagery, 255 (never seen) and any id >= K leave it as it is.  edge: class ids (below min(K, 32))
+    that get a one-pixel opaque line along the inside of their boundary with other seen classes.  One launch; nothing is read back."""
+    import numpy as np
+
+    lib = _lib.load()
+    what = "floodseg.ortho_compose"
+    ch, cw = _ortho_planes(None, rgba, what)
+    if cls is not None and (cls.dtype != torch.uint8 or tuple(cls.shape) != (ch, cw)):
+        raise ValueError(f"{what}: cls must be uint8 [{ch},{cw}] like rgba, got {cls.dtype} {tuple(cls.shape)}")
+    fill = tuple(int(v) for v in fill)
+    if len(fill) != 3 or not all(0 <= v <= 255 for v in fill):
+        raise ValueError(f"{what}: fill must be (r, g, b) with 0..255 each, got {fill}")
+    if isinstance(palette, torch.Tensor):
+        pal = palette.detach().cpu().numpy()
+    else:
+        pal = np.asarray(palette) if hasattr(palette, "dtype") else np.asarray(palette, dtype=np.int64)
+        if not hasattr(palette, "dtype") and pal.size and 0 <= pal.min() and pal.max() <= 255:
+            pal = pal.astype(np.uint8)  # a plain sequence of 0..255 values
+    if pal.dtype != np.uint8 or pal.ndim != 2 or pal.shape[1] not in (3, 4) or not 1 <= pal.shape[0] <= 256:
+        raise ValueError(f"{what}: palette must be uint8 [K,3] or [K,4] with 1 <= K <= 256, got {pal.dtype} {pal.shape}")
+    if pal.shape[1] == 4 and alpha is not None:
+        raise ValueError(f"{what}: alpha={alpha} goes with a [K,3] palette; a [K,4] palette carries its own opacities")
+    if pal.shape[1] == 3:
+        alpha = 96 if alpha is None else int(alpha)
+        if not 0 <= alpha <= 255:
+            raise ValueError(f"{what}: alpha must be 0..255, got {alpha}")
+    k = pal.shape[0]
+    edge = tuple(int(c) for c in edge)
+    if any(not 0 <= c < min(k, 32) for c in edge):
+        raise ValueError(f"{what}: edge must hold class ids 0..{min(k, 32) - 1}, got {edge}")
+    bits = sum(1 << c for c in set(edge))
+    dev = one_device(rgba, cls, what=what)
+    with torch.cuda.device(dev):
+        pal = _palette_rgba(dev, pal, alpha if pal.shape[1] == 3 else None, False)
+        out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=dev)
+        check(lib.fs_ortho_compose(ptr(rgba), ptr(None if cls is None else cls.contiguous()), ptr(pal), k, bits, fill[0] | fill[1] << 8 | fill[2] << 16, ch, cw,
+                                   ptr(out), stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

@@ -976,6 +976,65 @@ typedef struct fs_hook_tables8 {
     fs_ext8_api ext8;
 } fs_hook_tables8;
 
+/* ---- The TENTH table.  fs_ext8_api is frozen as well (4 members, 48 bytes; tests/test_mosaic_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables8 by the same pattern:
+ *     const fs_hook_tables9* t = (const fs_hook_tables9*)fs_test_hooks();   t->ext9.ortho_accumulate(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables8: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext9.magic == FS_EXT9_MAGIC and ext9.size >= the end of the member it needs. */
+#define FS_EXT9_MAGIC 0x4653455854414239ull /* "FSEXTAB9" */
+#define FS_ORTHO_EMPTY 0xFFFFFFFFFFFFFFFFull /* a rank word no frame has won */
+
+typedef struct fs_ext9_api {
+    uint64_t magic; /* FS_EXT9_MAGIC */
+    size_t size;    /* sizeof(fs_ext9_api) of the library that was built */
+
+    /* ---- THE ORTHOPHOTO UNDER THE MOSAIC (csrc/ortho_ops.hip, csrc/ortho_defs.h).  OUR DEFINITION: the reference has
+     * nothing like it.  The gather that registers the frames' PIXELS the way mosaic_accumulate registers their classes, and a compose
+     * pass that lays the extent map over it.  The same rules as code: csrc/ortho_defs.h (host and device) and tests/ortho_ref.py (numpy).
+     *
+     * ortho_accumulate takes ONE frame per call.  Canvas state, both [CH][CW], updated in place: rank uint64 (FS_ORTHO_EMPTY = all ones:
+     * empty) and rgba uint32 (0: unseen).  The image sampled is I = the decoded frame (frame, u, v, format, matrix, full_range, FH, FW:
+     * exactly frame_prepare's arguments) through frame_prepare's own resize to the mask size H x W, as stored uint8: the image
+     * frame_compose draws under that frame's mask, bit for bit.  pose is ONE row of pose_chain's output, ordinal the frame's number since
+     * the anchor (the caller counts).  For canvas pixel (X, Y): if the pose is not lost and its from_anchor lies inside the pose bounds
+     * (pose_votes), (x, y) is the frame pixel mosaic_accumulate would take its vote from (anchor_coord, source_pixel with from_anchor; the
+     * origin (ox, oy) as there).  If 0 <= x < W and 0 <= y < H the frame's rank there is
+     *   mode 0 (centre):  key << 32 | ordinal with key = (2x + 1 - W)^2 + (2y + 1 - H)^2 < 2^29: the view in which the ground point is
+     *                     nearest the optical axis wins, ties go to the earlier frame (the orthomosaic seam rule);
+     *   mode 1 (latest):  (0xFFFFFFFF - ordinal) << 32 | ordinal: the newest frame wins.
+     * Only if that rank is STRICTLY smaller than the stored one are rank and rgba = R | G << 8 | B << 16 | 0xFF << 24 of I[y][x] stored.
+     * The result is therefore the minimum over the frames: it does not depend on the order of the calls or on how frames are split into
+     * windows; a repeated call changes nothing (safe under graph replay); every canvas pixel has one owner, so there are no atomics.
+     * ONE launch: a workgroup per 64 x 16 canvas tile; a tile whose four corners under from_anchor cannot touch the frame (touches, one
+     * pixel of slack) returns having read the pose row only, so a frame costs its footprint, not the canvas.  A thread reads its rank
+     * word; only a winner fetches the taps (four, two where only the rows are resampled, one at equal sizes; YUV -> RGB where needed).
+     * Refused before a launch: a null frame, pose, rank or rgba, or a null chroma pointer of a YUV format; format, matrix or range code
+     * out of range; FH, FW, H, W, CH or CW outside 1..16384; |ox| or |oy| > 16384; mode not 0 or 1; ordinal 0xFFFFFFFF; pose or rank not
+     * aligned to 8 bytes, rgba to 4. */
+    int (*ortho_accumulate)(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW,
+                            const int64_t* pose, uint32_t ordinal, int H, int W, int mode, int CH, int CW, int ox, int oy, uint64_t* rank, uint32_t* rgba,
+                            fs_stream stream);
+
+    /* ---- ortho_compose draws the canvas: out uint8 RGB24 [CH][CW][3], written whole.  under = the pixel's (R, G, B) where rgba >> 24 != 0,
+     * else fill (r | g << 8 | b << 16).  k = cls[Y][X] (mosaic_resolve's plane).  With cls NULL no class is drawn, whatever K is:
+     * out = under, the plain orthophoto (palette may then be NULL too).  Otherwise for k < K the output is (A_k colour_k + (255 - A_k) under + 127) / 255 per channel from palette uint8 [K][4] (R, G, B, A) -- frame_compose's
+     * blend -- and `under` otherwise: unlike frame_compose, ids >= K take no colour, because 255 means "never seen" here.  EDGE LINE: a
+     * pixel whose class k is in edge_set (bit k, k < min(K, 32)) and that has a 4-neighbour INSIDE the canvas whose class is neither k nor
+     * 255 takes colour_k opaque: a one-pixel line along the inside of that class's boundary.  Unseen ground makes no edge.
+     * ONE launch: 64 x 16 tiles, a thread per four pixels of a row; the palette in LDS; with an edge set the class tile and a one-pixel
+     * apron in LDS.  Four pixels leave as three dwords where CW % 4 == 0, rgba is aligned to 16 bytes and cls and out to 4; as bytes
+     * otherwise.
+     * Refused before a launch: a null rgba or out, or cls without a palette; CH or CW outside 1..16384; K outside 1..256; an edge_set bit at
+     * or above min(K, 32); fill >= 2^24; rgba not aligned to 4 bytes. */
+    int (*ortho_compose)(const uint32_t* rgba, const uint8_t* cls, const uint8_t* palette, int K, uint32_t edge_set, uint32_t fill, int CH, int CW,
+                         uint8_t* out, fs_stream stream);
+} fs_ext9_api;
+
+typedef struct fs_hook_tables9 {
+    fs_hook_tables8 base8;
+    fs_ext9_api ext9;
+} fs_hook_tables9;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

@@ -1,0 +1,266 @@
+"""The orthophoto under the flood-extent mosaic on the GPU (ops.ortho_accumulate, ops.ortho_compose) against the numpy
+restatement of the definition (tests/ortho_ref.py), bit for bit: every source format, colour matrix and range at a 2:1, an odd and an
+identity resize, on a canvas off the tile and the dword and on one that takes the wide stores; order and window independence; idempotence;
+compose with and without the extent map and its edge line; one HIP-graph capture; and FlowPredictor(ortho=...) over two windows.  That the
+cases cover a quarter of their canvas and that several frames win pixels is asserted from the REFERENCE (and, without a GPU, in
+tests/test_ortho_cpu.py)."""
+import functools
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import mosaic_ref as mref
+import ortho_ref as oref
+from flood_uav_video_segmentation_amd import ops
+from flood_uav_video_segmentation_amd.flow.dataset import RawVideoWindows
+from flood_uav_video_segmentation_amd.flow.model import FlowModel
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor
+from test_gpu_regions import DELTA, FH, FW, clip, network  # noqa: F401  (clip: the module's synthetic raw video)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PAL4 = np.array([[0, 0, 0, 0], [30, 95, 170, 96], [65, 117, 5, 255], [212, 98, 1, 1], [255, 244, 116, 128]], np.uint8)
+
+
+def dev(a):
+    return None if a is None else torch.from_numpy(np.array(a)).to(DEV)    # a copy: the shared inputs are read-only
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def dev_source(source):
+    frame, chroma, fmt, matrix, full_range = source
+    chroma = None if chroma is None else tuple(dev(c) for c in chroma) if isinstance(chroma, tuple) else dev(chroma)
+    return dev(frame), chroma, fmt, matrix, full_range
+
+
+@functools.lru_cache(maxsize=None)
+def sampled(frame_size, mask_size, fmt, matrix, full_range, seed):
+    """(the decoded frame as numpy, the uint8 image the reference samples), computed once per colour and size."""
+    source = oref.make_source(frame_size[0], frame_size[1], fmt, matrix, full_range, seed)
+    img = oref.image(source, mask_size)
+    img.setflags(write=False)
+    return source, img
+
+
+def planes_equal(rank, rgba, want):
+    return np.array_equal(host(rank).view(np.uint64), want[0]) and np.array_equal(host(rgba).view(np.uint32), want[1])
+
+
+# ------------------------------------------------------------------------------------------------ ortho_accumulate
+@pytest.mark.parametrize("canvas,mode", [((70, 150), "centre"), ((64, 128), "latest")])
+@pytest.mark.parametrize("fmt,matrix,full_range", oref.COLOURS)
+@pytest.mark.parametrize("frame_size,mask_size", oref.FRAME_SIZES)
+def test_accumulate_equals_the_definition(frame_size, mask_size, fmt, matrix, full_range, canvas, mode):
+    """Five frames -- identity, a translation off the canvas on two sides, a rotation with zoom, a lost row, an ok row out of pose_votes'
+    bounds -- one call each, compared after every call; the two rows that may not gather leave both planes untouched."""
+    origin, poses = oref.CANVASES[canvas], oref.case_poses(canvas)
+    want = oref.canvas(canvas)
+    rank, rgba = ops.ortho_canvas(canvas, DEV)
+    for f, pose in enumerate(poses):
+        source, img = sampled(frame_size, mask_size, fmt, matrix, full_range, 10 + f)
+        before = (want[0].copy(), want[1].copy())
+        oref.ortho_accumulate(img, pose, f, want[0], want[1], origin, mode)
+        ops.ortho_accumulate(dev_source(source), dev(pose), f, mask_size, rank, rgba, origin, mode)
+        assert planes_equal(rank, rgba, want), f
+        if f >= 3:
+            assert planes_equal(rank, rgba, before)                          # lost / out of bounds: nothing was written
+    src, covered = oref.winners(want[0])                                     # from the reference, not from the op
+    assert 4 * covered >= canvas[0] * canvas[1] and set(np.unique(src)) == {-1, 0, 1, 2}
+
+
+@pytest.mark.parametrize("canvas", list(oref.CANVASES))
+@pytest.mark.parametrize("mode", ["centre", "latest"])
+def test_the_result_depends_on_neither_order_nor_windows_and_a_repeat_changes_nothing(canvas, mode):
+    origin, poses, sizes = oref.CANVASES[canvas], oref.overlap_poses(), ((45, 70), (37, 53))
+    frames = [sampled(sizes[0], sizes[1], "nv12", "bt709", False, 30 + f) for f in range(3)]
+    want = oref.canvas(canvas)
+    for f in range(3):
+        oref.ortho_accumulate(frames[f][1], poses[f], f, want[0], want[1], origin, mode)
+    src, covered = oref.winners(want[0])
+    assert set(np.unique(src)) == {-1, 0, 1, 2} and 4 * covered >= canvas[0] * canvas[1]   # every frame wins some pixels: the order could matter
+    pose_rows = dev(poses)                                                   # rows of one [3, 16] tensor, as pose_chain hands them out
+
+    def gather(order, planes):
+        for f in order:
+            ops.ortho_accumulate(dev_source(frames[f][0]), pose_rows[f], f, sizes[1], *planes, origin, mode)
+        return planes
+
+    for order in ((0, 1, 2), (2, 1, 0), (1, 2, 0)):
+        assert planes_equal(*gather(order, ops.ortho_canvas(canvas, DEV)), want), order
+    planes = ops.ortho_canvas(canvas, DEV)                                   # two "windows": frames (2, 0), then (1,)
+    gather((2, 0), planes)
+    assert not planes_equal(*planes, want)
+    gather((1,), planes)
+    assert planes_equal(*planes, want)
+    gather((1, 0, 2, 2), planes)                                             # identical calls again: nothing changes
+    assert planes_equal(*planes, want)
+
+
+def test_nothing_is_stored_where_the_frame_does_not_reach_or_does_not_win():
+    """A 24 x 40 image at the origin of a 64 x 128 canvas touches the tiles of columns 0..63 and rows 0..31 (one pixel of slack): the other
+    tiles hold rank 0, which no frame can beat -- and which a kernel that stored without comparing would have replaced.  (That those tiles
+    are not even READ cannot be seen from the result: a read rank 0 loses just the same.)"""
+    source, img = sampled((48, 80), (24, 40), "i420", "bt601", True, 41)
+    rank = torch.zeros((64, 128), dtype=torch.int64, device=DEV)
+    rank[:32, :64] = -1
+    rgba = torch.full((64, 128), 0x12345678, dtype=torch.int32, device=DEV)
+    want = (host(rank).view(np.uint64).copy(), host(rgba).view(np.uint32).copy())
+    ident = mref.pose_rows([(mref.IDENTITY, mref.IDENTITY)])[0]
+    oref.ortho_accumulate(img, ident, 9, want[0], want[1], (0, 0))
+    ops.ortho_accumulate(dev_source(source), dev(ident), 9, (24, 40), rank, rgba, (0, 0))
+    assert planes_equal(rank, rgba, want) and (want[1][:24, :40] >> 24 == 255).all() and (want[1][24:, :] == 0x12345678).all()
+
+
+# ------------------------------------------------------------------------------------------------ ortho_compose
+@pytest.mark.parametrize("canvas", list(oref.CANVASES))
+@pytest.mark.parametrize("edge", [(), (1,), (1, 3)])
+def test_compose_equals_the_definition(canvas, edge):
+    """70 x 150: partial tiles and the byte route; 64 x 128: the three-dword stores.  The class plane holds 255 and an id >= K, and class
+    boundaries in row 0 and column 0."""
+    rgba, cls = oref.compose_planes(canvas)
+    fill = (9, 200, 77)
+    got = ops.ortho_compose(dev(rgba.view(np.int32)), dev(cls), PAL4, fill=fill, edge=edge)
+    want = oref.ortho_compose(rgba, cls, PAL4, fill, edge)
+    assert got.shape == canvas + (3,) and np.array_equal(host(got), want)
+    plain = oref.ortho_compose(rgba, None, None, fill)
+    assert np.array_equal(host(ops.ortho_compose(dev(rgba.view(np.int32)), None, PAL4, fill=fill)), plain)   # without the extent map
+    assert (want[(cls == 255) | (cls == 7)] == plain[(cls == 255) | (cls == 7)]).all() and (want != plain).any()
+    if edge:
+        assert not np.array_equal(want, oref.ortho_compose(rgba, cls, PAL4, fill, ())) and (want[0, :12] != oref.ortho_compose(rgba, cls, PAL4, fill, ())[0, :12]).any()
+    # a [K, 3] palette with one alpha is the [K, 4] palette that carries it
+    got3 = ops.ortho_compose(dev(rgba.view(np.int32)), dev(cls), PALETTE, alpha=77, fill=fill, edge=edge)
+    pal = np.concatenate([PALETTE, np.full((len(PALETTE), 1), 77, np.uint8)], 1)
+    assert np.array_equal(host(got3), oref.ortho_compose(rgba, cls, pal, fill, edge))
+
+
+@pytest.mark.parametrize("canvas", list(oref.CANVASES))
+def test_compose_with_a_256_entry_palette(canvas):
+    """K = 256 makes 255 an ordinary class: WITH a class plane a pixel of class 255 takes entry 255's colour, and WITHOUT one (the plain
+    orthophoto) no palette entry is looked up at all -- the kernel stages the palette only with a class plane.  Twice, around a launch that
+    leaves other bytes in shared memory, so a lookup of an unstaged entry could not pass by luck."""
+    rgba, cls = oref.compose_planes(canvas)
+    pal = np.random.RandomState(8).randint(1, 256, size=(256, 4)).astype(np.uint8)   # every entry opaque enough to show
+    d_rgba, fill = dev(rgba.view(np.int32)), (9, 200, 77)
+    plain = oref.ortho_compose(rgba, None, None, fill)
+    assert np.array_equal(host(ops.ortho_compose(d_rgba, None, pal, fill=fill)), plain)
+    got = ops.ortho_compose(d_rgba, dev(cls), pal, fill=fill, edge=(1, 3))
+    want = oref.ortho_compose(rgba, cls, pal, fill, (1, 3))
+    assert np.array_equal(host(got), want) and (want[cls == 255] != plain[cls == 255]).any()            # 255 < K: drawn
+    assert np.array_equal(host(ops.ortho_compose(d_rgba, None, pal, fill=fill)), plain)
+    assert np.array_equal(host(ops.ortho_compose(d_rgba, None, pal[:, :3], alpha=255, fill=fill)), plain)
+
+
+def test_compose_on_the_byte_route_of_a_misaligned_canvas():
+    """CW % 4 == 0 but the planes start off their alignment: slices of larger buffers, so the wide route is not taken."""
+    rgba, cls = oref.compose_planes((64, 128))
+    big_rgba = torch.zeros((64 * 128 + 8,), dtype=torch.int32, device=DEV)
+    big_cls = torch.zeros((64 * 128 + 8,), dtype=torch.uint8, device=DEV)
+    r, c = big_rgba[1:1 + 64 * 128].view(64, 128), big_cls[3:3 + 64 * 128].view(64, 128)
+    r.copy_(dev(rgba.view(np.int32)))
+    c.copy_(dev(cls))
+    assert np.array_equal(host(ops.ortho_compose(r, c, PAL4, fill=(1, 2, 3), edge=(1, 3))), oref.ortho_compose(rgba, cls, PAL4, (1, 2, 3), (1, 3)))
+
+
+# ------------------------------------------------------------------------------------------------ graph capture
+def test_accumulate_and_compose_in_a_captured_graph_replayed_twice():
+    canvas, origin = (70, 150), oref.CANVASES[(70, 150)]
+    source, img = sampled((45, 70), (37, 53), "nv12", "bt601", False, 50)
+    pose = oref.case_poses(canvas)[2]
+    want = oref.canvas(canvas)
+    oref.ortho_accumulate(img, pose, 4, want[0], want[1], origin)
+    cls = oref.compose_planes(canvas)[1]
+    want_image = oref.ortho_compose(want[1], cls, PAL4, (0, 0, 0), (1,))
+    src, d_pose, d_cls = dev_source(source), dev(pose), dev(cls)
+    rank, rgba = ops.ortho_canvas(canvas, DEV)
+    ops.ortho_accumulate(src, d_pose, 4, (37, 53), rank, rgba, origin)        # eager: the kernels are loaded and the palette is on the device
+    eager = ops.ortho_compose(rgba, d_cls, PAL4, edge=(1,))
+    assert planes_equal(rank, rgba, want) and np.array_equal(host(eager), want_image)
+    rank.fill_(-1)
+    rgba.zero_()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        ops.ortho_accumulate(src, d_pose, 4, (37, 53), rank, rgba, origin)
+        image = ops.ortho_compose(rgba, d_cls, PAL4, edge=(1,))
+    for _ in range(2):                                                       # the second replay finds the canvas as the first left it
+        graph.replay()
+        torch.cuda.synchronize()
+        assert planes_equal(rank, rgba, want) and np.array_equal(host(image), want_image)
+
+
+# ------------------------------------------------------------------------------------------------ FlowPredictor
+def test_predictor_keeps_the_orthophoto_and_changes_nothing_else(clip):  # noqa: F811
+    """Two windows of the synthetic network: the masks are bit-identical to ortho=None, ortho_report() is the reference applied to the
+    frames the dataset handed out and the poses the mosaic reports; clear_report() drops canvas and counter, reset() keeps them."""
+    size, canvas = (65, 65), (96, 120)
+    ds = RawVideoWindows(clip, FH, FW, "rgb24", size=size, frame_delta=DELTA, grids="estimate", search=8, link_vectors=True, link_sources=True)
+    items = [ds[0], ds[1]]
+    assert all(len(i["link_sources"]) == DELTA and i["link_sources"][0][2] == "rgb24" for i in items)
+    fm = FlowModel(network(), feature_based=False, no_warp=False).eval()
+    kw = dict(classes=5, out_size=size, crop=None, compute_metrics=True, cache_keyframes=False, mosaic=canvas, mosaic_min_inliers=6, mosaic_exclude=())
+
+    def run(pred, item, **more):
+        return pred.predict_window(item["frame_prev"], item["frame_next"], item["mvs_left"], item["mvs_right"], to_host=False, link_mvs=item["link_mvs"],
+                                   link_frame_size=item["link_frame_size"], link_stats=item.get("link_stats"), **more)
+
+    off = FlowPredictor(fm, **kw)
+    plain = np.concatenate([host(run(off, i)) for i in items])
+    on = FlowPredictor(fm, ortho="centre", **kw)
+    got = np.concatenate([host(run(on, i, link_sources=i["link_sources"])) for i in items])
+    assert np.array_equal(got, plain) and torch.equal(on.hist, off.hist)
+    for a, b in zip(on.mosaic_report(), off.mosaic_report()):
+        assert np.array_equal(a, b)                                          # the mosaic itself is what it was
+    cls, poses = on.mosaic_report()[0], on.mosaic_report()[4]
+    origin = ((96 - 65) // 2, (120 - 65) // 2)
+    want = oref.canvas(canvas)
+    frames = [s for i in items for s in i["link_sources"]]
+    for f, s in enumerate(frames):
+        oref.ortho_accumulate(oref.image((host(s[0]), None) + tuple(s[2:]), size), poses[f], f, want[0], want[1], origin, "centre")
+    want_src, want_covered = oref.winners(want[0])
+    assert want_covered >= 65 * 65 and len(set(np.unique(want_src)) - {-1}) >= 2                         # not vacuous
+    image, src, covered = on.ortho_report(edge=(1,))
+    pal = np.concatenate([PALETTE, np.full((5, 1), 96, np.uint8)], 1)
+    assert np.array_equal(src, want_src) and covered == want_covered
+    assert np.array_equal(image, oref.ortho_compose(want[1], cls, pal, (0, 0, 0), (1,)))
+    assert np.array_equal(on.ortho_report(overlay=False, fill=(5, 6, 7))[0], oref.ortho_compose(want[1], None, None, (5, 6, 7)))
+    on.reset()                                                                 # a new video: canvas and counter stay
+    assert on._ortho_planes is not None and on._ortho_frames == 2 * DELTA
+    on.clear_report()
+    assert on._ortho_planes is None and on._ortho_frames == 0 and on.ortho_report()[2] == 0
+    with pytest.raises(ValueError, match="needs link_sources with every window"):
+        run(on, items[0])
+    sources = list(items[1]["link_sources"])
+    sources[2] = None                                                          # a frame that does not exist is skipped; the ordinals go on
+    run(on, items[1], link_sources=sources)
+    src = on.ortho_report()[1]
+    assert on._ortho_frames == DELTA and 2 not in np.unique(src) and 0 in np.unique(src)
+
+
+def test_predict_video_writes_the_orthophoto(clip, tmp_path):  # noqa: F811
+    """The command-line tool is what this test is about: one child process, --mosaic with --ortho on the synthetic clip, the imagery
+    alone (--ortho-plain): the PNG has the canvas's size, is black exactly where no frame won, and the line printed counts those pixels."""
+    from PIL import Image                                                   # the tool's own dependency for --mosaic, --ortho and --out
+
+    png, ortho = str(tmp_path / "m.png"), str(tmp_path / "o.png")
+    cmd = [sys.executable, os.path.join(ROOT, "tools", "predict_video.py"), "--raw", clip, "--raw-size", str(FH), str(FW), "--pix-fmt", "rgb24", "--search", "8",
+           "--synthetic-weights", "--no-cropping", "--size", "65", "65", "--no-metrics", "--mosaic", png, "--mosaic-size", "96", "120", "--mosaic-exclude",
+           "--ortho", ortho, "--ortho-mode", "latest", "--ortho-plain"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    said = re.search(r"--ortho: (\d+) canvas pixels covered, taken from (\d+) frames \(latest view wins\)", r.stdout)
+    assert said, r.stdout[-2000:]
+    covered, frames = int(said.group(1)), int(said.group(2))
+    rgb = np.asarray(Image.open(ortho))
+    assert rgb.shape == (96, 120, 3) and 65 * 65 <= covered <= 96 * 120 and frames >= 1
+    assert int(rgb.any(-1).sum()) <= covered and covered - int(rgb.any(-1).sum()) <= covered // 50   # black inside the footprint: the clip's own black pixels
+    seen = int(re.search(r"--mosaic: (\d+) canvas pixels seen", r.stdout).group(1))
+    assert covered == seen                                                   # the same gather: a pixel some frame voted on is a pixel some frame won

@@ -1,0 +1,415 @@
+"""The orthophoto under the flood-extent mosaic, the parts that need no GPU: the definition in numpy (tests/ortho_ref.py) in its vectorised
+form against the literal loops; csrc/ortho_defs.h run on the CPU by a stand-alone sanitized host program; hand-computed canvases; the
+tenth hook table, the refusals, the argument checks of FlowPredictor, the datasets and the tool; that the GPU tests' cases are not
+vacuous; and the end-to-end property of the definition on a synthetic flight."""
+import ctypes
+import importlib.util
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import mosaic_ref as mref
+import motion_ref
+import ortho_ref as oref
+from flood_uav_video_segmentation_amd import _lib, ops
+from flood_uav_video_segmentation_amd.flow import dataset
+from flood_uav_video_segmentation_amd.flow.predict import FlowPredictor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["ortho_accumulate", "ortho_compose"]
+ONE = mref.ONE
+IDENT = mref.IDENTITY
+PALETTE = np.array([[0, 0, 0, 0], [30, 95, 170, 96], [65, 117, 5, 255], [212, 98, 1, 1], [255, 244, 116, 128]], np.uint8)
+
+
+def gathered(canvas, mask_size, mode, poses, accumulate=oref.ortho_accumulate, seed=3):
+    rng = np.random.RandomState(seed)
+    rank, rgba = oref.canvas(canvas)
+    for f, pose in enumerate(poses):
+        img = rng.randint(0, 256, size=mask_size + (3,)).astype(np.uint8)
+        accumulate(img, pose, f, rank, rgba, oref.CANVASES[canvas], mode)
+    return rank, rgba
+
+
+# ------------------------------------------------------------------------------------------------ the reference against itself
+@pytest.mark.parametrize("mode", ["centre", "latest"])
+def test_vectorised_accumulate_equals_the_loop(mode):
+    for canvas, mask_size, poses in (((70, 150), (24, 40), oref.case_poses((70, 150))), ((64, 128), (37, 53), oref.overlap_poses())):
+        a = gathered(canvas, mask_size, mode, poses)
+        b = gathered(canvas, mask_size, mode, poses, oref.ortho_accumulate_loop)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        src, covered = oref.winners(a[0])
+        assert covered > 0 and ((a[1] >> 24) == np.where(src >= 0, 255, 0)).all()
+
+
+@pytest.mark.parametrize("edge", [(), (1,), (1, 3)])
+def test_vectorised_compose_equals_the_loop(edge):
+    rgba, cls = oref.compose_planes((40, 70))
+    for kw in (dict(cls=cls, palette=PALETTE, fill=(9, 200, 77), edge=edge), dict(cls=None, palette=None, fill=(1, 2, 3), edge=())):
+        a, b = oref.ortho_compose(rgba, **kw), oref.ortho_compose_loop(rgba, **kw)
+        assert np.array_equal(a, b)
+    big = np.random.RandomState(8).randint(1, 256, size=(256, 4)).astype(np.uint8)   # K = 256: 255 is a class with a plane, nothing without one
+    for kw in (dict(cls=cls, palette=big, edge=edge), dict(cls=None, palette=big)):
+        assert np.array_equal(oref.ortho_compose(rgba, **kw), oref.ortho_compose_loop(rgba, **kw))
+    assert np.array_equal(oref.ortho_compose(rgba, None, big), oref.ortho_compose(rgba, None, None))
+    assert (oref.ortho_compose(rgba, cls, big)[cls == 255] != oref.ortho_compose(rgba, None, None)[cls == 255]).any()
+    plain = oref.ortho_compose(rgba, cls, PALETTE, (9, 200, 77), ())
+    lined = oref.ortho_compose(rgba, cls, PALETTE, (9, 200, 77), edge)
+    assert (not edge) == np.array_equal(plain, lined)                        # an edge set draws something
+    assert (plain[cls == 255] == oref.ortho_compose(rgba, None, None, (9, 200, 77))[cls == 255]).all()   # unseen and ids >= K: no colour
+    assert (plain[cls == 7] == oref.ortho_compose(rgba, None, None, (9, 200, 77))[cls == 7]).all() and (cls == 7).any()
+
+
+def test_the_gpu_cases_are_not_vacuous():
+    """What tests/test_gpu_ortho.py relies on, checked from the reference: every accumulate case covers a quarter of its canvas, the three
+    usable poses all win pixels, the lost and the out-of-bounds rows none; in the overlapping cases every frame wins some, in both modes."""
+    for canvas in oref.CANVASES:
+        for _, mask_size in oref.FRAME_SIZES:
+            for mode in ("centre", "latest"):
+                src, covered = oref.winners(gathered(canvas, mask_size, mode, oref.case_poses(canvas))[0])
+                assert 4 * covered >= canvas[0] * canvas[1], (canvas, mask_size, covered)
+                assert set(np.unique(src)) == {-1, 0, 1, 2}, (canvas, mask_size)
+        for mode in ("centre", "latest"):
+            src, covered = oref.winners(gathered(canvas, (37, 53), mode, oref.overlap_poses())[0])
+            assert set(np.unique(src)) == {-1, 0, 1, 2} and 4 * covered >= canvas[0] * canvas[1]
+    poses = oref.case_poses((70, 150))
+    assert [mref.pose_votes(p) for p in poses] == [True, True, True, False, False]
+
+
+# ------------------------------------------------------------------------------------------------ hand-computed canvases
+def test_canvases_by_hand():
+    img = np.random.RandomState(1).randint(0, 256, size=(6, 9, 3)).astype(np.uint8)
+    ident = mref.pose_rows([(IDENT, IDENT)])[0]
+    # an identity pose with an equal-size RGB frame reproduces the frame at the origin
+    rank, rgba = oref.ortho_accumulate(img, ident, 0, *oref.canvas((10, 14)), (2, 3))
+    want = np.zeros((10, 14), np.uint32)
+    want[2:8, 3:12] = img[..., 0].astype(np.uint32) | img[..., 1].astype(np.uint32) << 8 | img[..., 2].astype(np.uint32) << 16 | 0xFF000000
+    assert np.array_equal(rgba, want) and (rank[want == 0] == oref.EMPTY).all()
+    assert int(rank[2, 3]) == ((8 * 8 + 5 * 5) << 32) and int(rank[4, 7]) == ((0 + 1) << 32)    # (2x + 1 - 9)^2 + (2y + 1 - 6)^2, ordinal 0
+    assert np.array_equal(oref.ortho_compose(rgba, None, None, (7, 8, 9))[2:8, 3:12], img)
+    assert oref.ortho_compose(rgba, None, None, (7, 8, 9))[0, 0].tolist() == [7, 8, 9]
+    # two identical poses: centre keeps the earlier ordinal, latest the later -- whichever comes first
+    other = 255 - img
+    for mode, keeps in (("centre", 4), ("latest", 5)):
+        for order in ((4, 5), (5, 4)):
+            rank, rgba = oref.canvas((10, 14))
+            for ordinal in order:
+                oref.ortho_accumulate(img if ordinal == 4 else other, ident, ordinal, rank, rgba, (2, 3), mode)
+            src, covered = oref.winners(rank)
+            assert covered == 54 and (src[2:8, 3:12] == keeps).all() and (src[rank == oref.EMPTY] == -1).all()
+            assert np.array_equal(oref.ortho_compose(rgba)[2:8, 3:12], img if keeps == 4 else other)
+    # a second identical call changes nothing; a lost row writes nothing
+    again = oref.ortho_accumulate(other, ident, 5, rank.copy(), rgba.copy(), (2, 3), "latest")
+    assert np.array_equal(again[0], rank) and np.array_equal(again[1], rgba)
+    lost = mref.pose_rows([(IDENT, IDENT)], status=[2])[0]
+    fresh = oref.ortho_accumulate(img, lost, 0, *oref.canvas((10, 14)), (2, 3))
+    assert (fresh[0] == oref.EMPTY).all() and not fresh[1].any()
+    # the ranks: the key's bound and the latest mode's order
+    assert oref.centre_key(0, 0, 16384, 16384) == 2 * 16383 ** 2 < 1 << 29
+    assert oref.frame_rank("latest", 0, 0, 4, 4, 7) < oref.frame_rank("latest", 0, 0, 4, 4, 6) < oref.EMPTY
+    assert oref.frame_rank("latest", 0, 0, 4, 4, 0xFFFFFFFE) >> 32 == 1 and oref.frame_rank("centre", 1, 1, 4, 4, 0xFFFFFFFE) < oref.EMPTY
+    # compose by hand: one water pixel (class 1, alpha 96) between land, with and without its edge
+    rgba = np.full((1, 3), 0xFF000000 | 200 | 100 << 8 | 50 << 16, np.uint32)
+    cls = np.array([[2, 1, 255]], np.uint8)
+    pal = np.array([[0, 0, 0, 0], [30, 95, 170, 96], [65, 117, 5, 0]], np.uint8)
+    blend = [(96 * c + 159 * u + 127) // 255 for c, u in zip((30, 95, 170), (200, 100, 50))]
+    assert oref.ortho_compose(rgba, cls, pal).tolist() == [[[200, 100, 50], blend, [200, 100, 50]]]
+    assert oref.ortho_compose(rgba, cls, pal, edge=(1,)).tolist() == [[[200, 100, 50], [30, 95, 170], [200, 100, 50]]]
+    assert oref.ortho_compose(rgba, np.array([[255, 1, 255]], np.uint8), pal, edge=(1,)).tolist()[0][1] == blend   # unseen ground makes no edge
+
+
+# ------------------------------------------------------------------------------------------------ the header's functions on the CPU
+def host_commands():
+    """(commands, expected output lines) for tests/ortho_host_check.cpp, from the numpy reference and from arithmetic."""
+    rng = np.random.RandomState(23)
+    cmds, want = [], []
+
+    def add(cmd, out):
+        cmds.append(" ".join(str(int(v)) if not isinstance(v, str) else v for v in cmd))
+        want.append(" ".join(str(int(v)) for v in out))
+
+    for x, y, h, w in ((0, 0, 1, 1), (0, 0, 16384, 16384), (16383, 16383, 16384, 16384), (4, 2, 6, 9), (26, 18, 37, 53), (0, 36, 37, 53)):
+        add(["key", x, y, h, w], [oref.centre_key(x, y, h, w)])
+        for mode in ("centre", "latest"):
+            for ordinal in (0, 7, 0xFFFFFFFE):
+                r = oref.frame_rank(mode, x, y, h, w, ordinal)
+                add(["rank", oref.MODES[mode], x, y, h, w, ordinal], [r, ordinal])
+                assert r < oref.EMPTY
+    for a, b in ((0, 0), (0, 1), (1, 0), (oref.EMPTY - 1, oref.EMPTY), (oref.EMPTY, oref.EMPTY), (1 << 63, (1 << 63) - 1), ((1 << 63) - 1, 1 << 63)):
+        add(["replaces", a, b], [int(a < b)])
+    c, s = np.cos(np.radians(30)), np.sin(np.radians(30))
+    for back in (IDENT, mref.affine_pose(c, -s, s, c, 6, -2)[1], mref.affine_pose(0.5, 0, 0, 0.5, -100.25, 3)[1], mref.affine_pose(2, 0, 0, 2, 1, 1)[1]):
+        for X, Y, ox, oy in ((0, 0, 0, 0), (5, 7, 3, -2), (16383, 0, -16384, 16384), (40, 30, 20, 10)):
+            for mode in ("centre", "latest"):
+                ax, ay = (2 * (X - ox) + 1) << 19, (2 * (Y - oy) + 1) << 19
+                x, y = (mref.rshr(back[0] * ax + back[1] * ay) + back[2]) >> 20, (mref.rshr(back[3] * ax + back[4] * ay) + back[5]) >> 20
+                ok = 0 <= x < 53 and 0 <= y < 37
+                add(["cand"] + back + [X, Y, ox, oy, 37, 53, oref.MODES[mode], 11], [1, x, y, oref.frame_rank(mode, x, y, 37, 53, 11)] if ok else [0, 0, 0, 0])
+    for canvas, mask_size, poses in (((70, 150), (24, 40), oref.case_poses((70, 150))), ((64, 128), (37, 53), oref.overlap_poses()), ((33, 65), (32, 48), oref.overlap_poses()[::-1])):
+        for mode in ("centre", "latest"):
+            h, w = mask_size
+            index = np.arange(h * w, dtype=np.int64).reshape(h, w)         # the "image" holds each pixel's own index in its three bytes
+            img = np.stack([index & 255, (index >> 8) & 255, index >> 16], -1).astype(np.uint8)
+            oy, ox = oref.CANVASES.get(canvas, (4, 9))
+            rank, rgba = oref.canvas(canvas)
+            ordinals = [int(v) for v in rng.permutation(len(poses)) + 2]
+            for pose, ordinal in zip(poses, ordinals):
+                oref.ortho_accumulate(img, pose, ordinal, rank, rgba, (oy, ox), mode)
+            pixel = np.where(rank == np.uint64(oref.EMPTY), -1, (rgba & np.uint32(0xFFFFFF)).astype(np.int64))
+            cmd = ["gather", canvas[0], canvas[1], ox, oy, h, w, oref.MODES[mode], len(poses)]
+            for pose, ordinal in zip(poses, ordinals):
+                cmd += [int(v) for v in pose] + [ordinal]
+            add(cmd, [int(v) for v in rank.reshape(-1)] + [int(v) for v in pixel.reshape(-1)])
+    for r, g, b in ((0, 0, 0), (255, 255, 255), (1, 2, 3)):
+        add(["pack", r, g, b], [oref.pack_rgba((r, g, b))])
+    for rgba, fill in ((0, 0x102030), (0xFF010203, 0x102030), (0x00FFFFFF, 0x0000FF), (0x01000000, 0xFFFFFF)):
+        add(["under", rgba, fill], [(rgba if rgba >> 24 else fill) & 0xFFFFFF])
+    for k, kmax in ((0, 1), (4, 5), (5, 5), (255, 256), (255, 5), (7, 5)):
+        add(["takes", k, kmax], [int(k < kmax)])
+    for k, bits, near, out in ((1, 0b10, (1, 1, 1, 2), 1), (1, 0b10, (1, 1, 1, 1), 0), (1, 0b10, (255, 255, 1, 255), 0), (1, 0b100, (2, 2, 2, 2), 0),
+                               (3, 0b1010, (3, 0, 3, 3), 1), (31, 1 << 31, (31, 31, 30, 31), 1), (40, 0xFFFFFFFF, (1, 1, 1, 1), 0), (255, 0xFFFFFFFF, (1, 1, 1, 1), 0)):
+        add(["edge", k, bits] + list(near), [out])
+    return cmds, want
+
+
+def test_the_headers_rules_are_the_references_under_sanitizers(tmp_path):
+    """csrc/ortho_defs.h is plain __host__ __device__ C++: tests/ortho_host_check.cpp runs the keys, the ranks of both modes, the strict
+    update rule, the candidate of a canvas pixel, whole gathers tile by tile with the tile test, and compose's pixel rules as a
+    stand-alone program built with -fsanitize=address,undefined; every line it prints is the reference's."""
+    makefile = open(os.path.join(ROOT, "flood_uav_video_segmentation_amd", "csrc", "Makefile")).read()
+    hipcc = re.search(r"^HIPCC\s*\?=\s*(\S+)", makefile, flags=re.M).group(1)          # the compiler the project cannot be built without
+    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(hipcc)), "lib", "llvm", "bin", "clang++")
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++") or shutil.which("c++") or (os.path.exists(rocm_clang) and rocm_clang)
+    assert cxx, f"no host C++ compiler: none of $CXX, g++, clang++, c++ on PATH, and no {rocm_clang}"
+    exe, data = str(tmp_path / "ortho_host_check"), str(tmp_path / "commands.txt")
+    base = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I",
+            os.path.join(ROOT, "flood_uav_video_segmentation_amd", "csrc"), os.path.join(ROOT, "tests", "ortho_host_check.cpp"), "-o", exe]
+    for static in (["-static-libasan", "-static-libubsan"], ["-static-libsan"], []):   # the runtimes linked in where the compiler can
+        build = subprocess.run(base + static, capture_output=True, text=True)
+        if build.returncode == 0:
+            break
+    assert build.returncode == 0, build.stderr[-3000:]
+    cmds, want = host_commands()
+    with open(data, "w") as fh:
+        fh.write("\n".join(cmds) + "\n")
+    run = subprocess.run([exe, data], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, (run.stdout[-3000:], run.stderr[-3000:])
+    got = run.stdout.split("\n")[:-1]
+    assert len(got) == len(want) and len(want) > 100
+    for cmd, g, w in zip(cmds, got, want):
+        assert g == w, (cmd[:200], g[:200], w[:200])
+
+
+# ------------------------------------------------------------------------------------------------ library surface
+def test_the_tenth_table_in_header_initialiser_and_binding():
+    assert _lib.ext9_hook_names() == NEW
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "floodseg_test.h")).read(), flags=re.S)
+    body = text[text.index("typedef struct fs_ext9_api {"):text.index("} fs_ext9_api;")]
+    assert re.findall(r"\(\*([a-z0-9_]+)\)\s*\(", body) == NEW
+    assert re.findall(r"\b(uint64_t|size_t) ([a-z]+);", body) == [("uint64_t", "magic"), ("size_t", "size")]
+    assert text.index("} fs_hook_tables8;") < text.index("typedef struct fs_ext9_api {") < text.index("typedef struct fs_hook_tables9 {")
+    tables9 = text[text.index("typedef struct fs_hook_tables9 {"):text.index("} fs_hook_tables9;")]
+    assert re.findall(r"\b(fs_[a-z0-9_]+) ([a-z0-9]+);", tables9) == [("fs_hook_tables8", "base8"), ("fs_ext9_api", "ext9")]
+    assert int(re.search(r"#define FS_EXT9_MAGIC (0x[0-9a-f]+)ull", text).group(1), 16) == _lib.EXT9_MAGIC == int.from_bytes(b"FSEXTAB9", "big")
+    assert int(re.search(r"#define FS_ORTHO_EMPTY (0x[0-9A-F]+)ull", text).group(1), 16) == oref.EMPTY
+    src = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "flood_uav_video_segmentation_amd", "csrc", "api_test.hip")).read())   # code, not comments
+    init = src[src.index("static const fs_hook_tables9 all9 = {all8, {"):]
+    init = init[:init.index("}};")]
+    assert re.findall(r"^\s+(fs_[a-z0-9_]+),$", init, flags=re.M) == ["fs_" + name for name in NEW]
+    assert "FS_EXT9_MAGIC," in init and "sizeof(fs_ext9_api)," in init
+    assert re.search(r"const fs_hook_tables8& all8 = all9\.base8;\s+const fs_hook_tables7& all7 = all8\.base7;", src)
+    kernels = open(os.path.join(ROOT, "flood_uav_video_segmentation_amd", "csrc", "kernels.h")).read()
+    assert all("launch_" + name in kernels for name in NEW)
+    # the nine older tables and the export list are what they were
+    assert [len(names()) for names in (_lib.hook_names, _lib.ext_hook_names, _lib.ext2_hook_names, _lib.ext3_hook_names, _lib.ext4_hook_names, _lib.ext5_hook_names,
+                                       _lib.ext6_hook_names, _lib.ext7_hook_names, _lib.ext8_hook_names)] == [38, 2, 14, 1, 1, 1, 1, 2, 4]
+    assert [ctypes.sizeof(t) for t in (_lib.FsExtApi, _lib.FsExt2Api, _lib.FsExt3Api, _lib.FsExt4Api, _lib.FsExt5Api, _lib.FsExt6Api, _lib.FsExt7Api,
+                                       _lib.FsExt8Api)] == [32, 128, 24, 24, 24, 24, 32, 48]
+    assert _lib.ext8_hook_names() == ["global_motion", "pose_chain", "mosaic_accumulate", "mosaic_resolve"]
+    assert not any("fs_" + name in _lib.exported_symbols() for name in NEW) and len(_lib.exported_symbols()) == 40
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert sorted(re.findall(r" T (fs_[a-z0-9_]+)", out)) == _lib.exported_symbols()
+    public = open(os.path.join(ROOT, "include", "floodseg.h")).read()
+    assert not any(name in public for name in NEW)
+    lib = _lib.load()
+    assert lib.fs_version() == 600
+    assert _lib.FsHookTables9.ext9.offset == ctypes.sizeof(_lib.FsHookTables8)                           # directly behind, no padding
+    assert [getattr(_lib.FsExt9Api, name).offset for name in NEW] == [16, 24] and ctypes.sizeof(_lib.FsExt9Api) == 32
+    all9 = ctypes.cast(lib.fs_test_hooks(), ctypes.POINTER(_lib.FsHookTables9)).contents
+    assert all9.base8.ext8.magic == _lib.EXT8_MAGIC and all9.base8.ext8.size == 48
+    assert all9.base8.base7.ext7.magic == _lib.EXT7_MAGIC and all9.base8.base7.ext7.size == 32
+    assert all9.ext9.magic == _lib.EXT9_MAGIC and all9.ext9.size >= 32                                   # from below only: the table grows at its end
+    for name in NEW:
+        assert ctypes.cast(getattr(all9.ext9, name), ctypes.c_void_p).value == ctypes.cast(getattr(lib, "fs_" + name), ctypes.c_void_p).value
+        with pytest.raises(AttributeError):
+            getattr(ctypes.CDLL(_lib.LIB_PATH), "fs_" + name)                                            # a table member, not an exported symbol
+    assert ctypes.cast(all9.base8.ext8.mosaic_resolve, ctypes.c_void_p).value == ctypes.cast(lib.fs_mosaic_resolve, ctypes.c_void_p).value
+    # the rules' header reuses the mosaic's gather and leaves it alone
+    defs = open(os.path.join(ROOT, "flood_uav_video_segmentation_amd", "csrc", "ortho_defs.h")).read()
+    assert '#include "mosaic_defs.h"' in defs and all(f"mos::{fn}(" in defs for fn in ("source_pixel", "anchor_coord"))
+    kernel = open(os.path.join(ROOT, "flood_uav_video_segmentation_amd", "csrc", "ortho_ops.hip")).read()
+    assert "mos::pose_votes(" in kernel and "mos::touches(" in kernel and "atomic" not in kernel.split("namespace fs {")[1]
+    assert re.search(r"\$\(OBJDIR\)/ortho_ops\.o[^\n]*: CXXFLAGS \+= -ffp-contract=off", makefile_text()) and " ortho_ops.hip " in makefile_text()
+
+
+def makefile_text():
+    return open(os.path.join(ROOT, "flood_uav_video_segmentation_amd", "csrc", "Makefile")).read()
+
+
+def test_the_magic_is_checked_before_use(monkeypatch):
+    fresh = _lib._Library(ctypes.CDLL(_lib.LIB_PATH))
+    fresh._cdll.fs_test_hooks.restype = ctypes.c_void_p
+    monkeypatch.setattr(_lib, "EXT9_MAGIC", _lib.EXT9_MAGIC + 1)
+    with pytest.raises(RuntimeError, match="the library has no ninth extension table \\(fs_ortho_compose is missing\\)"):
+        fresh.fs_ortho_compose
+    assert fresh.fs_mosaic_resolve is not None                                # the tables in front of it stay usable
+    monkeypatch.undo()
+    monkeypatch.setattr(_lib, "EXT8_MAGIC", _lib.EXT8_MAGIC + 1)
+    with pytest.raises(RuntimeError, match="first nine hook tables are not the ones this binding knows \\(fs_ortho_accumulate is missing\\)"):
+        fresh.fs_ortho_accumulate
+    monkeypatch.undo()
+    assert all(getattr(fresh, "fs_" + name) is not None for name in NEW)
+
+
+def test_library_refuses_bad_arguments_before_a_launch():
+    """Dummy non-null pointers: every one of these must fail in argument validation (there is no GPU here to launch on)."""
+    lib = _lib.load()
+    assert len(oref.refusal_cases()) >= 30
+    for op, kw, word in oref.refusal_cases():
+        assert oref.call_op(lib, op, **kw) != 0, (op, kw)
+        msg = lib.fs_last_error()
+        assert msg.startswith(op.encode() + b":") and word in msg, (op, kw, msg)
+
+
+# ------------------------------------------------------------------------------------------------ Python argument checks
+def test_ops_refuse_with_the_offending_value():
+    frame, pose = torch.zeros((8, 12, 3), dtype=torch.uint8), torch.zeros((16,), dtype=torch.int64)
+    rank, rgba = torch.full((9, 9), -1, dtype=torch.int64), torch.zeros((9, 9), dtype=torch.int32)
+    y, uv = torch.zeros((8, 12), dtype=torch.uint8), torch.zeros((4, 6, 2), dtype=torch.uint8)
+    good = dict(source=(frame, None, "rgb24", "bt601", False), pose=pose, ordinal=0, mask_size=(8, 12), rank=rank, rgba=rgba, origin=(0, 0))
+    for kw, word in ((dict(mode="nearest"), "'nearest'"), (dict(ordinal=0xFFFFFFFF), "4294967295"), (dict(ordinal=-1), "-1"), (dict(mask_size=(0, 5)), "(0, 5)"),
+                     (dict(mask_size=(5, 16385)), "16385"), (dict(origin=(20000, 0)), "20000"), (dict(origin=(0, -16385)), "-16385"),
+                     (dict(pose=torch.zeros((2, 16), dtype=torch.int64)), "(2, 16)"), (dict(pose=pose.int()), "int32"), (dict(rank=rank.int()), "int32"),
+                     (dict(rank=rank[:5]), "(5, 9)"), (dict(rgba=rgba.long()), "int64"), (dict(source=(frame, None, "bgr24", "bt601", False)), "'bgr24'"),
+                     (dict(source=(frame, None, "rgb24", "bt2020", False)), "'bt2020'"), (dict(source=(frame.int(), None, "rgb24", "bt601", False)), "int32"),
+                     (dict(source=(y, None, "rgb24", "bt601", False)), "(8, 12)"), (dict(source=(y, None, "nv12", "bt601", False)), "(4, 6, 2)"),
+                     (dict(source=(y, uv[:3], "nv12", "bt601", False)), "(3, 6, 2)"), (dict(source=(frame, None, "rgb24")), "of 3")):
+        with pytest.raises(ValueError, match=re.escape(word)):
+            ops.ortho_accumulate(**{**good, **kw})
+    with pytest.raises(RuntimeError, match="floodseg.ortho_accumulate: tensors must live on the GPU"):
+        ops.ortho_accumulate(**good)
+    cls = torch.zeros((9, 9), dtype=torch.uint8)
+    for kw, word in ((dict(rgba=rgba.long()), "int64"), (dict(cls=cls[:4]), "(4, 9)"), (dict(cls=cls.int()), "int32"), (dict(fill=(0, 0, 256)), "256"),
+                     (dict(fill=(1, 2)), "(1, 2)"), (dict(palette=np.zeros((0, 3), np.uint8)), "(0, 3)"), (dict(palette=np.zeros((5, 3), np.int32)), "int32"),
+                     (dict(alpha=256), "256"), (dict(palette=PALETTE, alpha=9), "alpha=9"), (dict(edge=(5,)), "(5,)"), (dict(edge=(-1,)), "(-1,)"),
+                     (dict(palette=np.zeros((40, 3), np.uint8), edge=(32,)), "(32,)")):
+        with pytest.raises(ValueError, match=re.escape(word)):
+            ops.ortho_compose(**{**dict(rgba=rgba, cls=cls), **kw})
+    with pytest.raises(RuntimeError, match="floodseg.ortho_compose: tensors must live on the GPU"):
+        ops.ortho_compose(rgba, cls)
+    with pytest.raises(ValueError, match=re.escape("(0, 4)")):
+        ops.ortho_canvas((0, 4), "cpu")
+    rank, rgba = ops.ortho_canvas((3, 4), "cpu")
+    assert rank.dtype == torch.int64 and rgba.dtype == torch.int32 and (rank == -1).all() and not rgba.any() and rank.shape == rgba.shape == (3, 4)
+    assert rank.numpy().view(np.uint64)[0, 0] == oref.EMPTY
+
+
+def test_predictor_and_dataset_argument_checks(tmp_path):
+    ident = torch.nn.Identity()
+    p = FlowPredictor(ident)
+    assert p.ortho is None and p._ortho_planes is None and p._ortho_sources(3, None) is None     # off: no sources are asked for
+    with pytest.raises(ValueError, match="ortho_report\\(\\) needs ortho="):
+        p.ortho_report()
+    with pytest.raises(ValueError, match="ortho='centre' needs mosaic=\\(CH, CW\\)"):
+        FlowPredictor(ident, ortho="centre")
+    with pytest.raises(ValueError, match="'nearest'"):
+        FlowPredictor(ident, mosaic=(30, 40), ortho="nearest")
+    on = FlowPredictor(ident, mosaic=(30, 40), ortho="latest")
+    assert on.ortho == "latest" and on._ortho_frames == 0
+    image, src, covered = on.ortho_report(fill=(1, 2, 3))
+    assert image.shape == (30, 40, 3) and (image == np.array([1, 2, 3], np.uint8)).all() and (src == -1).all() and covered == 0
+    with pytest.raises(ValueError, match="needs link_sources with every window"):
+        on._ortho_sources(3, None)
+    with pytest.raises(ValueError, match="got 2"):
+        on._ortho_sources(3, [None, None])
+    assert on._ortho_sources(2, (None, None)) == [None, None]
+    on._ortho_frames = (1 << 31) - 2                                         # ordinals stay below 2^31: src is int32
+    assert on._ortho_sources(2, (None, None)) == [None, None]
+    with pytest.raises(ValueError, match=f"at most {1 << 31} frames per mosaic.*got {(1 << 31) - 2} \\+ 3"):
+        on._ortho_sources(3, (None, None, None))
+    on._ortho_planes, on._ortho_frames = ops.ortho_canvas((30, 40), "cpu"), 7
+    on.reset()
+    assert on._ortho_planes is not None and on._ortho_frames == 7            # a new video: the canvas and the counter stay
+    on.clear_report()
+    assert on._ortho_planes is None and on._ortho_frames == 0
+    # the datasets: link_sources needs link_vectors
+    raw = tmp_path / "v.rgb"
+    raw.write_bytes(bytes(32 * 48 * 3 * 4))
+    with pytest.raises(ValueError, match="link_sources=True needs link_vectors=True"):
+        dataset.RawVideoWindows(str(raw), 32, 48, "rgb24", frame_delta=2, device="cpu", link_sources=True)
+    kw = dict(frame_delta=2, device="cpu", no_warp=True, link_vectors=True)   # no_warp: the estimator's geometry check is not what is tested here
+    ds = dataset.RawVideoWindows(str(raw), 32, 48, "rgb24", link_sources=True, **kw)
+    assert ds.link_sources and not dataset.RawVideoWindows(str(raw), 32, 48, "rgb24", **kw).link_sources
+    assert [s[0].shape for s in (ds.source(0), ds.source(3))] == [(32, 48, 3)] * 2 and ds.source(4) is None   # what an item's list holds; None past the end
+    os.makedirs(tmp_path / "frames" / "v" / "images")
+    with pytest.raises(ValueError, match="PredictWindows: link_sources=True needs link_vectors=True"):
+        dataset.PredictWindows(str(tmp_path), "v", link_sources=True)
+    listing = tmp_path / "list.txt"
+    listing.write_text("")
+    with pytest.raises(ValueError, match="EvalWindows does not support link_sources"):
+        dataset.EvalWindows(str(tmp_path), str(listing), link_sources=True)
+    assert dataset.PredictWindows.link_sources is False
+
+
+def test_tool_refuses_an_orthophoto_without_a_mosaic(capsys):
+    spec = importlib.util.spec_from_file_location("predict_video_tool_ortho", os.path.join(ROOT, "tools", "predict_video.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    raw = ["--raw", "c.rgb", "--raw-size", "1072", "1920", "--synthetic-weights"]
+    a = tool.parse_args(raw + ["--mosaic", "m.png", "--ortho", "o.png"])
+    assert (a.ortho, a.ortho_mode, a.ortho_alpha, a.ortho_edge, a.ortho_plain) == ("o.png", "centre", 96, [], False)
+    assert tool.parse_args(raw + ["--mosaic", "m.png"]).ortho is None
+    a = tool.parse_args(raw + ["--mosaic", "m.png", "--ortho", "o.png", "--ortho-mode", "latest", "--ortho-alpha", "200", "--ortho-edge", "1", "3", "--ortho-plain"])
+    assert (a.ortho_mode, a.ortho_alpha, a.ortho_edge, a.ortho_plain) == ("latest", 200, [1, 3], True)
+    capsys.readouterr()
+    for bad, word in ((raw + ["--ortho", "o.png"], "need --mosaic"), (raw + ["--mosaic", "m.png", "--ortho-mode", "latest"], "need --ortho"),
+                      (raw + ["--mosaic", "m.png", "--ortho-plain"], "need --ortho"), (raw + ["--mosaic", "m.png", "--ortho", "o.png", "--ortho-alpha", "256"], "0..255"),
+                      (raw + ["--mosaic", "m.png", "--ortho", "o.png", "--ortho-edge", "5"], "0..4"),
+                      (raw + ["--no-warp", "--mosaic", "m.png", "--ortho", "o.png"], "--no-warp estimates none")):
+        with pytest.raises(SystemExit):
+            tool.parse_args(bad)
+        assert word in capsys.readouterr().err, bad
+
+
+# ------------------------------------------------------------------------------------------------ the definition end to end
+def test_a_synthetic_flight_gives_the_ground_image_at_every_covered_pixel():
+    """mosaic_ref.scene(): six 128 x 192 views cut from one 256 x 384 ground image at integer offsets, an equal-size mask, the tables from
+    the block matcher's reference, the poses from the mosaic's reference.  The orthophoto must equal the ground image at EVERY covered
+    canvas pixel, in both modes, and the covered pixels are exactly the mosaic's seen ones."""
+    frames, masks, offsets, labels = mref.scene()
+    tables = [motion_ref.block_match(frames[i], frames[max(i - 1, 0)], search=16)[0] for i in range(6)]
+    poses = mref.run_scene(tables, masks)[1]
+    world = np.random.RandomState(7).randint(0, 256, size=(256, 384)).astype(np.uint8)   # scene()'s texture
+    assert np.array_equal(world[60:188, 90:282], frames[0])
+    ground = np.stack([world, 255 - world, world // 2 + 17], -1)
+    (ch, cw), (oy, ox), (vh, vw) = mref.SCENE_CANVAS, mref.SCENE_ORIGIN, mref.SCENE_VIEW
+    y0, x0 = offsets[0][0] - oy, offsets[0][1] - ox                          # canvas pixel (Y, X) shows ground pixel (Y + y0, X + x0)
+    want_seen = mref.scene_expectation()[0]
+    for mode in ("centre", "latest"):
+        rank, rgba = oref.canvas((ch, cw))
+        for f, (y, x) in enumerate(offsets):
+            oref.ortho_accumulate(oref.image((ground[y:y + vh, x:x + vw], None, "rgb24", "bt601", False), (vh, vw)), poses[f], f, rank, rgba, (oy, ox), mode)
+        src, covered = oref.winners(rank)
+        assert covered == int((want_seen > 0).sum()) == 28434 and np.array_equal(src >= 0, want_seen > 0)
+        image = oref.ortho_compose(rgba, fill=(255, 0, 255))
+        assert np.array_equal(image[src >= 0], ground[y0:y0 + ch, x0:x0 + cw][src >= 0])                 # zero wrong pixels
+        assert (image[src < 0] == np.array([255, 0, 255], np.uint8)).all()
+        assert len(set(np.unique(src)) - {-1}) >= 3
+        if mode == "latest":                                                 # the newest view owns its whole footprint
+            top, left = oy + offsets[5][0] - offsets[0][0], ox + offsets[5][1] - offsets[0][1]
+            assert (src[top:top + vh, left:left + vw] == 5).all()

@@ -89,6 +89,12 @@ status (ok, bridged, lost), whether the frame left the canvas, and the fit's inl
 pixels and their share of the ground seen.  A scene cut ends the chain: the frames after it are reported as lost.  The defaults are
 guesses, not validated on real video; an affine per pair is not a homography, the chain drifts over a long flight and nothing closes
 loops; areas are pixels of the first frame, not metres.
+`--ortho FILE.png` (an extension; needs `--mosaic`, and so estimated grids and one process) gathers, with the same poses, the
+frames' pixels -- the image the network saw, at the mask's resolution -- into an orthophoto of the mosaic's size and writes it with the extent
+map blended over it at `--ortho-alpha A` (default 96 of 255); `--ortho-edge K [K ...]` draws a one-pixel line along the inside of those
+classes' boundaries, `--ortho-plain` leaves the extent map off.  `--ortho-mode centre` (default) gives each piece of ground to the view that
+saw it nearest its optical axis, `latest` to the newest view.  No feathering or exposure matching across seams and no lens model: the
+chain's drift shows as broken roads at the seams, which is what the picture is for.  Not validated on real video.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -227,6 +233,14 @@ def parse_args(argv=None):
                     "camera's motion (default 1, water)")
     ap.add_argument("--mosaic-rounds", type=int, default=4, metavar="N", help="--mosaic: least-squares rounds of the motion fit (0..8; 0: the vectors' mode)")
     ap.add_argument("--mosaic-tol", type=float, default=1.0, metavar="PX", help="--mosaic: inlier tolerance of the last round in frame pixels (0..64)")
+    ap.add_argument("--ortho", default=None, metavar="FILE.png", help="--mosaic: also gather the frames' pixels into an orthophoto of the mosaic's size and "
+                    "write it with the extent map drawn over it (DESIGN §3.19)")
+    ap.add_argument("--ortho-mode", choices=("centre", "latest"), default=None, help="--ortho: which view owns a piece of ground: the one that saw it nearest "
+                    "its optical axis (default), or the newest")
+    ap.add_argument("--ortho-alpha", type=int, default=None, metavar="A", help="--ortho: opacity of the class colours over the imagery (0..255, default 96)")
+    ap.add_argument("--ortho-edge", type=int, nargs="+", default=None, metavar="K", help="--ortho: classes that get a one-pixel opaque line along the inside "
+                    "of their boundary (default: none)")
+    ap.add_argument("--ortho-plain", action="store_true", help="--ortho: the imagery alone, without the extent map")
     ap.add_argument("--mosaic-report", default=None, metavar="FILE.csv", help="--mosaic: per frame the pose, status, clipped flag, inliers and usable "
                     "blocks; per class the canvas pixels and their share of the ground seen")
     ap.add_argument("--draw-outlines", type=int, nargs="?", const=1, default=None, metavar="W", help="--raw-out with --regions: draw a white line W "
@@ -273,6 +287,15 @@ def parse_args(argv=None):
         ap.error("--mosaic needs the block matcher's vectors: --no-warp estimates none")
     if args.mosaic_size is not None and any(not 1 <= v <= 16384 for v in args.mosaic_size):
         ap.error("--mosaic-size takes H W of 1..16384 pixels")
+    if not args.mosaic and (args.ortho or args.ortho_mode is not None or args.ortho_alpha is not None or args.ortho_edge is not None or args.ortho_plain):
+        ap.error("--ortho and its options need --mosaic FILE.png: the orthophoto is gathered with the mosaic's poses, onto its canvas")
+    if not args.ortho and (args.ortho_mode is not None or args.ortho_alpha is not None or args.ortho_edge is not None or args.ortho_plain):
+        ap.error("--ortho-mode, --ortho-alpha, --ortho-edge and --ortho-plain need --ortho FILE.png")
+    args.ortho_mode = args.ortho_mode or "centre"
+    args.ortho_alpha = 96 if args.ortho_alpha is None else args.ortho_alpha
+    args.ortho_edge = args.ortho_edge or []
+    if not 0 <= args.ortho_alpha <= 255 or any(not 0 <= k < min(args.classes, 32) for k in args.ortho_edge):
+        ap.error(f"--ortho-alpha takes 0..255 and --ortho-edge class ids 0..{min(args.classes, 32) - 1}")
     if not 0 <= args.mosaic_rounds <= 8 or not 0 <= args.mosaic_tol <= 64 or any(not 0 <= k <= 31 for k in args.mosaic_exclude):
         ap.error("--mosaic-rounds takes 0..8, --mosaic-tol 0..64 pixels and --mosaic-exclude class ids 0..31")
     if args.proximity is not None and not args.regions:
@@ -366,18 +389,19 @@ def main():
                          stabilize=args.stabilize, stabilize_trust=args.stabilize_trust, stabilize_compensate=args.stabilize_compensate,
                          proximity=args.proximity, proximity_sources=args.proximity_sources, proximity_targets=args.proximity_targets,
                          proximity_max=args.proximity_max, mosaic=mosaic_size, mosaic_classes=min(args.classes, 32), mosaic_rounds=args.mosaic_rounds,
-                         mosaic_tol=args.mosaic_tol, mosaic_exclude=args.mosaic_exclude)
+                         mosaic_tol=args.mosaic_tol, mosaic_exclude=args.mosaic_exclude, ortho=args.ortho_mode if args.ortho else None)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
                              full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut, hold_cuts=args.hold_cuts,
-                             link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic))
+                             link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic), link_sources=bool(args.ortho))
     else:
         ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
                             grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut,
-                            hold_cuts=args.hold_cuts, link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic))
+                            hold_cuts=args.hold_cuts, link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic),
+                            link_sources=bool(args.ortho))
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -427,7 +451,7 @@ def main():
         item = ds[w]
         masks = pred.predict_window(item["frame_prev"], item["frame_next"], item["mvs_left"], item["mvs_right"], to_host=False,
                                     key_ids=item["key_ids"], weights=item.get("weights"), link_mvs=item.get("link_mvs"),
-                                    link_frame_size=item.get("link_frame_size"), link_stats=item.get("link_stats"))
+                                    link_frame_size=item.get("link_frame_size"), link_stats=item.get("link_stats"), link_sources=item.get("link_sources"))
         if args.confidence:
             masks, conf = masks
             if conf_writer is not None:
@@ -505,6 +529,13 @@ def main():
         print(f"--mosaic: {int((seen > 0).sum())} canvas pixels seen by {len(poses) - lost} frames"
               + (f"; {lost} frames lost (a scene cut, or more failed fits running than are bridged)" if lost else "")
               + (f"; {int(poses[:, 13].sum())} frames reach beyond the canvas (--mosaic-size)" if poses[:, 13].any() else ""),
+              file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    if args.ortho:  # drawn and read back ONCE, here, after the timed run
+        from PIL import Image
+
+        image, src, covered = pred.ortho_report(palette=palette, alpha=args.ortho_alpha, edge=args.ortho_edge, overlay=not args.ortho_plain)
+        Image.fromarray(image).save(args.ortho)
+        print(f"--ortho: {covered} canvas pixels covered, taken from {len(set(np.unique(src).tolist()) - {-1})} frames ({args.ortho_mode} view wins)",
               file=sys.stderr if args.raw_out == "-" else sys.stdout)
     if args.report:  # the device report is read back ONCE, here, after the timed run
         report = pred.extent_report() if args.confidence else (torch.cat(areas).cpu().numpy() if areas else np.zeros((0, args.classes, 3), np.int64))
