@@ -211,6 +211,14 @@ _EXT9_HOOKS = [
 ]
 EXT9_MAGIC = 0x4653455854414239  # FS_EXT9_MAGIC
 
+# members of fs_ext10_api, the eleventh table (append-only, behind the ten frozen ones), in declaration order after `magic` and `size`
+_EXT10_HOOKS = [
+    ("map_view", c_int, [c_void] * 3 + [c_int] * 5 + [c_void, ctypes.c_uint32] + [c_int] * 6 + [c_void] * 2 + [c_int] + [c_void] * 4),
+    ("map_gate", c_int, [c_void, c_int, c_void, c_int, c_int, c_void]),
+    ("pose_correct", c_int, [c_void] * 3 + [c_int] * 6 + [c_void] * 2),
+]
+EXT10_MAGIC = 0x4653455854413130  # FS_EXT10_MAGIC
+
 
 def _struct(name, *fields):
     return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
@@ -242,6 +250,8 @@ FsExt8Api = _struct("FsExt8Api", *_EXT_HEAD, *_members(_EXT8_HOOKS))
 FsHookTables8 = _struct("FsHookTables8", ("base7", FsHookTables7), ("ext8", FsExt8Api))
 FsExt9Api = _struct("FsExt9Api", *_EXT_HEAD, *_members(_EXT9_HOOKS))
 FsHookTables9 = _struct("FsHookTables9", ("base8", FsHookTables8), ("ext9", FsExt9Api))
+FsExt10Api = _struct("FsExt10Api", *_EXT_HEAD, *_members(_EXT10_HOOKS))
+FsHookTables10 = _struct("FsHookTables10", ("base9", FsHookTables9), ("ext10", FsExt10Api))
 
 # One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
 # the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
@@ -259,6 +269,7 @@ _TABLES = [
     _Table("seven", "seventh", _EXT7_HOOKS, "EXT7_MAGIC", FsExt7Api, FsHookTables7, "ext7"),
     _Table("eight", "eighth", _EXT8_HOOKS, "EXT8_MAGIC", FsExt8Api, FsHookTables8, "ext8"),
     _Table("nine", "ninth", _EXT9_HOOKS, "EXT9_MAGIC", FsExt9Api, FsHookTables9, "ext9"),
+    _Table("ten", "tenth", _EXT10_HOOKS, "EXT10_MAGIC", FsExt10Api, FsHookTables10, "ext10"),
 ]
 _TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
@@ -339,7 +350,7 @@ def _hook_names(n):
 
 
 (hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
- ext8_hook_names, ext9_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
+ ext8_hook_names, ext9_hook_names, ext10_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

@@ -574,7 +574,22 @@ static int fs_ortho_compose(const uint32_t* rgba, const uint8_t* cls, const uint
     return fs::launch_ortho_compose(rgba, cls, palette, K, edge_set, fill, CH, CW, out, S(stream));
 }
 
-// the ten tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// frame-to-map registration (refine_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_map_view(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const int64_t* pose,
+                       uint32_t ordinal, int H, int W, int CH, int CW, int ox, int oy, const uint64_t* rank, const uint32_t* rgba, int min_age, uint8_t* cur,
+                       uint8_t* view, uint8_t* valid, fs_stream stream) {
+    return fs::launch_map_view(frame, u, v, format, matrix, full_range, FH, FW, reinterpret_cast<const long long*>(pose), ordinal, H, W, CH, CW, ox, oy,
+                               reinterpret_cast<const unsigned long long*>(rank), rgba, min_age, cur, view, valid, S(stream));
+}
+static int fs_map_gate(int32_t* table, int blocks, const uint8_t* valid, int H, int W, fs_stream stream) {
+    return fs::launch_map_gate(table, blocks, valid, H, W, S(stream));
+}
+static int fs_pose_correct(const int64_t* model, int64_t* state, int64_t* pose, int H, int W, int CH, int CW, int ox, int oy, int64_t* out, fs_stream stream) {
+    return fs::launch_pose_correct(reinterpret_cast<const long long*>(model), reinterpret_cast<long long*>(state), reinterpret_cast<long long*>(pose), H, W, CH,
+                                   CW, ox, oy, reinterpret_cast<long long*>(out), S(stream));
+}
+
+// the eleven tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -691,7 +706,16 @@ static const fs_hook_tables5& hook_tables(void) {
         fs_ortho_accumulate,
         fs_ortho_compose,
     }};
+    // fs_ext9_api is frozen too (two members, 32 bytes; tests/test_ortho_cpu.py); the eleventh table lies behind it, and &all10.base9 is &all10.
+    static const fs_hook_tables10 all10 = {all9, {
+        FS_EXT10_MAGIC,
+        sizeof(fs_ext10_api),
+        fs_map_view,
+        fs_map_gate,
+        fs_pose_correct,
+    }};
     {
+        const fs_hook_tables9& all9 = all10.base9;
         const fs_hook_tables8& all8 = all9.base8;
         const fs_hook_tables7& all7 = all8.base7;  // from here on both names mean the head of the whole object, not the copies it was built from
         const fs_hook_tables6& all6 = all7.base6;

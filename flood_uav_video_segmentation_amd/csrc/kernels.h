@@ -415,6 +415,15 @@ int launch_ortho_accumulate(const uint8_t* frame, const uint8_t* u, const uint8_
 int launch_ortho_compose(const uint32_t* rgba, const uint8_t* cls, const uint8_t* palette, int K, uint32_t edge_set, uint32_t fill, int CH, int CW,
                          uint8_t* out, hipStream_t s);
 
+// Frame-to-map registration (refine_ops.hip, refine_defs.h; definitions: include/floodseg_test.h, map_view, map_gate and pose_correct).
+// The launchers refuse bad arguments before they launch anything.  The frame arguments as launch_ortho_accumulate takes them; table is
+// the matcher's, `blocks` rows of seven ints, gated in place.  No workspace; nothing is allocated, synchronised or read on the host.
+int launch_map_view(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const long long* pose,
+                    uint32_t ordinal, int H, int W, int CH, int CW, int ox, int oy, const unsigned long long* rank, const uint32_t* rgba, int min_age,
+                    uint8_t* cur, uint8_t* view, uint8_t* valid, hipStream_t s);
+int launch_map_gate(int32_t* table, int blocks, const uint8_t* valid, int H, int W, hipStream_t s);
+int launch_pose_correct(const long long* model, long long* state, long long* pose, int H, int W, int CH, int CW, int ox, int oy, long long* out, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

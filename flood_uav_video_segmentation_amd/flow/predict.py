@@ -209,7 +209,18 @@ class FlowPredictor:
     "centre": per canvas pixel the view in which the ground point is nearest the optical axis wins; "latest": the newest frame.
     ortho_report() draws it, by default with the extent map over it, and reads back once; clear_report() drops the canvas and the
     counter, reset() keeps them.  No feathering or exposure matching across seams, no lens model, the mask's resolution, and the chain's
-    drift shows as broken seams; NOT validated on real video."""
+    drift shows as broken seams; NOT validated on real video.
+
+    mosaic_refine=True (extension, needs ortho=; False: off, none of its ops is ever called and _keep_mosaic's calls are what they were):
+    frame-to-map registration.  The window is then walked frame by frame: pose_chain with n = 1; for a frame whose ordinal
+    is a multiple of refine_every and whose source exists, ops.map_view draws the orthophoto canvas as the frame should see it under that
+    pose, ops.block_match_modes (refine_search 1..32, refine_penalty, refine_intra_bias) matches the frame against it, ops.map_gate voids
+    the rows that touch unmapped ground (or, with refine_min_age > 0, ground no frame at least that many ordinals older owns: loop
+    closure on a revisit only), ops.global_motion fits the residual motion with the mosaic's own settings and ops.pose_correct folds it
+    into the chain BEFORE the frame votes; then ops.ortho_accumulate with the corrected row, so a frame's view holds exactly the frames
+    before it.  refine_report() -> int64 [frames, 8]: status (0 corrected, 1 not attempted, 2 no fit, 3 out of the pose bounds, 4 the
+    chain is lost), usable rows, inliers, rounds, the fit's shift (x, y) in Q20, 0, 0.  Earlier frames are never re-posed, drift beyond
+    refine_search is not recovered, and all these defaults are guesses, NOT validated on real video."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
     ORTHO_MAX_FRAMES = 1 << 31  # ordinals 0 .. 2^31 - 1: what ortho_report()'s int32 src can name
@@ -220,7 +231,7 @@ class FlowPredictor:
                  max_vertices=32768, simplify=None, simplify_rounds=32, keep_window_regions=False, stabilize=None, stabilize_trust=None,
                  stabilize_compensate=False, proximity=None, proximity_sources=(1,), proximity_targets=(3, 4), proximity_max=None, mosaic=None,
                  mosaic_classes=None, mosaic_rounds=4, mosaic_tol=1.0, mosaic_min_inliers=12, mosaic_exclude=(1,), mosaic_bridge=2, mosaic_origin=None,
-                 ortho=None):
+                 ortho=None, mosaic_refine=False, refine_search=8, refine_penalty=0, refine_intra_bias=65535, refine_min_age=0, refine_every=1):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -363,6 +374,20 @@ class FlowPredictor:
         self.ortho = ortho
         self._ortho_planes = None  # (rank, rgba) [CH, CW] on the device
         self._ortho_frames = 0     # frames since the anchor: the next frame's ordinal
+        if mosaic_refine and not ortho:
+            raise ValueError("FlowPredictor: mosaic_refine=True needs ortho='centre' or 'latest': a frame is registered against the orthophoto canvas")
+        if not 1 <= int(refine_search) <= 32:
+            raise ValueError(f"FlowPredictor: refine_search must be 1..32 pixels, got {refine_search}")
+        if not 0 <= int(refine_penalty) <= 255 or not 0 <= int(refine_intra_bias) <= 65535:
+            raise ValueError(f"FlowPredictor: refine_penalty must be 0..255 and refine_intra_bias 0..65535, got {refine_penalty} and {refine_intra_bias}")
+        if not 0 <= int(refine_min_age) < 1 << 31:
+            raise ValueError(f"FlowPredictor: refine_min_age must be 0..2^31 - 1 frames, got {refine_min_age}")
+        if int(refine_every) < 1:
+            raise ValueError(f"FlowPredictor: refine_every must be at least 1, got {refine_every}")
+        self.mosaic_refine = bool(mosaic_refine)
+        self.refine_search, self.refine_penalty, self.refine_intra_bias = int(refine_search), int(refine_penalty), int(refine_intra_bias)
+        self.refine_min_age, self.refine_every = int(refine_min_age), int(refine_every)
+        self._refine_outs = FrameRows(((8,), torch.int64))  # pose_correct's out rows, kept in step with _mosaic_poses
 
     # the chunk lists that tests count, under the names they had before the tables moved into FrameRows
     _report_chunks = property(lambda self: self._extent.chunks)
@@ -382,7 +407,8 @@ class FlowPredictor:
 
     def clear_report(self):
         """Forget the extent report and the region report of the frames predicted so far."""
-        for table in (self._extent, self._regions, self._tracks, self._outlines, self._simple, self._stabilize_counts, self._proximity, self._mosaic_poses):
+        for table in (self._extent, self._regions, self._tracks, self._outlines, self._simple, self._stabilize_counts, self._proximity, self._mosaic_poses,
+                      self._refine_outs):
             table.clear()  # the tracks' previous frame and next id stay, and so does the stabiliser's state plane
         self._despeckle_counts = []
         self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
@@ -466,17 +492,62 @@ class FlowPredictor:
             self._mosaic_at = self.mosaic_origin if self.mosaic_origin is not None else ((ch - h) // 2, (cw - w) // 2)
         model = ops.global_motion(link[0], link[1], (h, w), self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks,
                                   exclude=self.mosaic_exclude, pair_stats=link[2])
-        poses = ops.pose_chain(model, self._mosaic_state, (h, w), self.mosaic, self._mosaic_at, self.mosaic_bridge)
+        if self.mosaic_refine:
+            poses, outs = self._refined_poses(masks, model, sources)
+        else:
+            poses = ops.pose_chain(model, self._mosaic_state, (h, w), self.mosaic, self._mosaic_at, self.mosaic_bridge)
         ops.mosaic_accumulate(masks, poses, self._mosaic_votes, self._mosaic_at)
-        for done, take, _, (rows,) in self._mosaic_poses.pieces(n, self.REPORT_CHUNK, dev):
+        for done, take, row, (rows,) in self._mosaic_poses.pieces(n, self.REPORT_CHUNK, dev):
             rows.copy_(poses[done:done + take])
-        if self.ortho:
+            if self.mosaic_refine:
+                self._refine_outs.rows(row, take, self.REPORT_CHUNK, dev)[0].copy_(outs[done:done + take])
+        if self.mosaic_refine:
+            self._refine_outs.frames = self._mosaic_poses.frames
+        elif self.ortho:
             if self._ortho_planes is None:
                 self._ortho_planes = ops.ortho_canvas(self.mosaic, dev)
             for p in range(n):
                 if sources[p] is not None:
                     ops.ortho_accumulate(sources[p], poses[p], self._ortho_frames + p, (h, w), *self._ortho_planes, self._mosaic_at, self.ortho)
             self._ortho_frames += n
+
+    def _refined_poses(self, masks, model, sources):
+        """mosaic_refine=True: the window walked frame by frame -> (poses [n, 16], pose_correct's out rows [n, 8]).  Every frame gets
+        pose_chain with n = 1; a frame whose turn it is and whose source exists is registered against the orthophoto canvas -- which at
+        that moment holds exactly the frames before it -- and its row corrected in place; then its pixels go into the canvas."""
+        n, h, w = masks.shape
+        dev, size, at = masks.device, (h, w), self._mosaic_at
+        if self._ortho_planes is None:
+            self._ortho_planes = ops.ortho_canvas(self.mosaic, dev)
+        rank, rgba = self._ortho_planes
+        poses = torch.empty((n, 16), dtype=torch.int64, device=dev)
+        outs = torch.zeros((n, 8), dtype=torch.int64, device=dev)
+        outs[:, 0] = 1  # not attempted
+        for p in range(n):
+            ordinal = self._ortho_frames + p
+            poses[p:p + 1] = ops.pose_chain(model[p:p + 1], self._mosaic_state, size, self.mosaic, at, self.mosaic_bridge)
+            if sources[p] is None:
+                continue
+            if ordinal % self.refine_every == 0:
+                cur, view, valid = ops.map_view(sources[p], poses[p], ordinal, size, rank, rgba, at, self.refine_min_age)
+                table, stats = ops.block_match_modes(cur, view, self.refine_search, self.refine_penalty, self.refine_intra_bias, return_stats=True)
+                ops.map_gate(table, valid)
+                fit = ops.global_motion(table[None], size, size, self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks[p:p + 1],
+                                        exclude=self.mosaic_exclude, pair_stats=stats[None])
+                outs[p] = ops.pose_correct(fit, self._mosaic_state, poses[p], size, self.mosaic, at)
+            ops.ortho_accumulate(sources[p], poses[p], ordinal, size, rank, rgba, at, self.ortho)
+        self._ortho_frames += n
+        return poses, outs
+
+    def refine_report(self):
+        """mosaic_refine=True: int64 numpy [frames, 8], pose_correct's out row of every frame predicted since the start (or
+        clear_report()), in the order of mosaic_report()'s poses: status (0 corrected, 1 not attempted, 2 no fit, 3 out of the pose
+        bounds, 4 the chain is lost), usable rows, inliers, rounds done, the fit's shift x and y in Q20, 0, 0.  The ONE read-back."""
+        if not self.mosaic_refine:
+            raise ValueError("FlowPredictor: refine_report() needs mosaic_refine=True")
+        if not self._refine_outs.chunks:
+            return np.zeros((0, 8), np.int64)
+        return self._refine_outs.flat().cpu().numpy()
 
     def ortho_report(self, palette=PALETTE, alpha=None, edge=(), fill=(0, 0, 0), overlay=True):
         """ortho=: (image, src, covered) of the frames predicted since the start (or clear_report()): image uint8 numpy [CH, CW, 3], the
@@ -970,23 +1041,33 @@ def write_exposure_csv(path, frame_ids, exposure, thresholds, frame_pixels):
 MOSAIC_STATUS = ("ok", "bridged", "lost")
 
 
-def write_mosaic_csv(path, frame_ids, poses, totals):
+REFINE_STATUS = ("corrected", "skipped", "no_fit", "out_of_bounds", "lost")
+
+
+def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):
     """FlowPredictor.mosaic_report()'s poses int64 [frames, 16] and totals int64 [K, 2] as one CSV of two tables.  First one row per
     frame: frame id, status (ok, bridged, lost), clipped (1: a corner of the frame lies outside the canvas), inliers and usable rows of
     the pair's fit, and the pose m00 .. m12 that takes a mask pixel of the frame to the anchor frame's pixels (empty for a lost frame).
     Then, after an empty line, one row per class: the canvas pixels it won, their share of the seen pixels, and its votes.  Pixels are
-    mask pixels of the anchor frame, not metres."""
+    mask pixels of the anchor frame, not metres.  refine: FlowPredictor.refine_report()'s int64 [frames, 8]; the frame rows then end with
+    refine (corrected, skipped, no_fit, out_of_bounds, lost), the usable rows and inliers of the fit against the map, and its shift in
+    mask pixels."""
     poses, totals = np.asarray(poses), np.asarray(totals)
+    if refine is not None and np.asarray(refine).shape != (poses.shape[0], 8):
+        raise ValueError(f"write_mosaic_csv: refine must be [frames, 8] with one row per pose row, got {np.asarray(refine).shape} for {poses.shape[0]} frames")
+    extra = [[]] * poses.shape[0] if refine is None else [
+        [REFINE_STATUS[r[0]] if 0 <= r[0] <= 4 else "lost", str(r[1]), str(r[2]), f"{r[4] / (1 << 20):.6f}", f"{r[5] / (1 << 20):.6f}"] for r in np.asarray(refine).tolist()]
     if poses.ndim != 2 or poses.shape[1] != 16 or len(frame_ids) != poses.shape[0] or totals.ndim != 2 or totals.shape[1] != 2:
         raise ValueError(f"write_mosaic_csv: poses must be [frames, 16] with one frame id per row and totals [K, 2], got {poses.shape}, {len(frame_ids)} "
                          f"ids and {totals.shape}")
     seen = int(totals[:, 0].sum())
     with open(path, "w", newline="") as f:
-        f.write("frame,status,clipped,inliers,usable,m00,m01,m02,m10,m11,m12\n")
-        for fid, row in zip(frame_ids, poses.tolist()):
+        f.write("frame,status,clipped,inliers,usable,m00,m01,m02,m10,m11,m12" + (",refine,refine_usable,refine_inliers,refine_dx,refine_dy" if refine is not None else "")
+                + "\n")
+        for fid, row, more in zip(frame_ids, poses.tolist(), extra):
             status = row[12] if 0 <= row[12] <= 2 else 2
             pose = [f"{v / (1 << 20):.6f}" for v in row[:6]] if status != 2 else [""] * 6
-            f.write(",".join([str(int(fid)), MOSAIC_STATUS[status], str(row[13]), str(row[14]), str(row[15])] + pose) + "\n")
+            f.write(",".join([str(int(fid)), MOSAIC_STATUS[status], str(row[13]), str(row[14]), str(row[15])] + pose + more) + "\n")
         f.write("\nclass,pixels,share,votes\n")
         for k, (pixels, votes) in enumerate(totals.tolist()):
             f.write(f"{k},{pixels},{pixels / seen if seen else 0.0:.6f},{votes}\n")

@@ -1053,16 +1053,8 @@ def _ortho_planes(rank, rgba, what):
     return _mosaic_size(rgba.shape, "the canvas", what)
 
 
-def ortho_accumulate(source, pose, ordinal, mask_size, rank, rgba, origin, mode="centre"):
-    """One frame's pixels gathered into the orthophoto canvas (definition: include/floodseg_test.h, ortho_accumulate; DESIGN §3.19).
-    source = (frame, chroma, fmt, matrix, full_range) as the window datasets' source(f_id) returns it and prepare_frame takes it; the
-    image sampled is that frame through prepare_frame's resize to mask_size = (H, W), as stored uint8.  pose: ONE row of pose_chain's
-    output, int64 [16] on the device; ordinal: the frame's number since the anchor (0 .. 2^32 - 2).  rank, rgba: ortho_canvas's planes,
-    UPDATED IN PLACE (and returned): a canvas pixel takes the frame's pixel where the frame's rank is strictly smaller -- mode "centre":
-    the view in which the ground point is nearest the optical axis, ties to the earlier frame; "latest": the newest frame.  origin =
-    (oy, ox) as mosaic_accumulate's.  One launch that costs the frame's footprint; nothing is read back."""
-    lib = _lib.load()
-    what = "floodseg.ortho_accumulate"
+def _ortho_source(source, what):
+    """The checks ortho_accumulate makes of its 5-tuple, for the ops that take the same one -> (frame, chroma planes, fmt, matrix, full_range, fh, fw)."""
     if not isinstance(source, (tuple, list)) or len(source) != 5:
         raise ValueError(f"{what}: source must be the 5-tuple (frame, chroma, fmt, matrix, full_range), got a {type(source).__name__}"
                          + (f" of {len(source)}" if isinstance(source, (tuple, list)) else ""))
@@ -1071,10 +1063,6 @@ def ortho_accumulate(source, pose, ordinal, mask_size, rank, rgba, origin, mode=
         raise ValueError(f"{what}: fmt must be one of {sorted(_FORMATS)}, got {fmt!r}")
     if matrix not in _MATRICES:
         raise ValueError(f"{what}: matrix must be one of {sorted(_MATRICES)}, got {matrix!r}")
-    if mode not in ORTHO_MODES:
-        raise ValueError(f"{what}: mode must be one of {sorted(ORTHO_MODES)}, got {mode!r}")
-    if not 0 <= int(ordinal) < 0xFFFFFFFF:
-        raise ValueError(f"{what}: ordinal must be 0..{0xFFFFFFFF - 1}, got {ordinal}")
     planes = [] if chroma is None else list(chroma) if isinstance(chroma, (tuple, list)) else [chroma]
     if frame.dtype != torch.uint8 or any(p.dtype != torch.uint8 for p in planes):
         raise ValueError(f"{what}: frames must be uint8, got {[str(t.dtype) for t in [frame] + planes]}")
@@ -1085,6 +1073,24 @@ def ortho_accumulate(source, pose, ordinal, mask_size, rank, rgba, origin, mode=
     want = [] if rgb else [((fh + 1) // 2, (fw + 1) // 2, 2)] if fmt == "nv12" else [((fh + 1) // 2, (fw + 1) // 2)] * 2
     if [tuple(p.shape) for p in planes] != want:
         raise ValueError(f"{what}: a {fh} x {fw} {fmt} frame takes chroma {want if want else None}, got {[tuple(p.shape) for p in planes]}")
+    return frame, planes, fmt, matrix, full_range, fh, fw
+
+
+def ortho_accumulate(source, pose, ordinal, mask_size, rank, rgba, origin, mode="centre"):
+    """One frame's pixels gathered into the orthophoto canvas (definition: include/floodseg_test.h, ortho_accumulate; DESIGN §3.19).
+    source = (frame, chroma, fmt, matrix, full_range) as the window datasets' source(f_id) returns it and prepare_frame takes it; the
+    image sampled is that frame through prepare_frame's resize to mask_size = (H, W), as stored uint8.  pose: ONE row of pose_chain's
+    output, int64 [16] on the device; ordinal: the frame's number since the anchor (0 .. 2^32 - 2).  rank, rgba: ortho_canvas's planes,
+    UPDATED IN PLACE (and returned): a canvas pixel takes the frame's pixel where the frame's rank is strictly smaller -- mode "centre":
+    the view in which the ground point is nearest the optical axis, ties to the earlier frame; "latest": the newest frame.  origin =
+    (oy, ox) as mosaic_accumulate's.  One launch that costs the frame's footprint; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.ortho_accumulate"
+    frame, planes, fmt, matrix, full_range, fh, fw = _ortho_source(source, what)
+    if mode not in ORTHO_MODES:
+        raise ValueError(f"{what}: mode must be one of {sorted(ORTHO_MODES)}, got {mode!r}")
+    if not 0 <= int(ordinal) < 0xFFFFFFFF:
+        raise ValueError(f"{what}: ordinal must be 0..{0xFFFFFFFF - 1}, got {ordinal}")
     h, w = _mosaic_size(mask_size, "mask_size", what)
     if pose.dtype != torch.int64 or tuple(pose.shape) != (16,) or not pose.is_contiguous():
         raise ValueError(f"{what}: pose must be one contiguous int64 [16] row of pose_chain's output, got {pose.dtype} {tuple(pose.shape)}")
@@ -1140,6 +1146,78 @@ def ortho_compose(rgba, cls=None, palette=FLOOD_PALETTE, alpha=None, fill=(0, 0,
         out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=dev)
         check(lib.fs_ortho_compose(ptr(rgba), ptr(None if cls is None else cls.contiguous()), ptr(pal), k, bits, fill[0] | fill[1] << 8 | fill[2] << 16, ch, cw,
                                    ptr(out), stream_ptr()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ frame-to-map registration
+def map_view(source, pose, ordinal, mask_size, rank, rgba, origin, min_age=0):
+    """The orthophoto canvas as this frame should see it under its predicted pose (definition: include/floodseg_test.h, map_view;
+    DESIGN §3.20).  source, pose (ONE row of pose_chain's output), ordinal, mask_size = (H, W), rank, rgba and origin = (oy, ox) as
+    ops.ortho_accumulate takes them; the canvas is only read.  -> (cur, view, valid), uint8 [H,W] each: the frame's own luma (of the
+    image ortho_accumulate samples), the luma of the canvas pixel under each frame pixel, and 1 where that canvas pixel exists, has been
+    seen and -- with min_age > 0 -- belongs to a frame at least min_age ordinals older (0 elsewhere, and everywhere for a lost pose).
+    block_match_modes(cur, view) then finds how far the frame lies from where the chain put it.  One launch; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.map_view"
+    frame, planes, fmt, matrix, full_range, fh, fw = _ortho_source(source, what)
+    if not 0 <= int(ordinal) < 0xFFFFFFFF:
+        raise ValueError(f"{what}: ordinal must be 0..{0xFFFFFFFF - 1}, got {ordinal}")
+    if not 0 <= int(min_age) < 1 << 31:
+        raise ValueError(f"{what}: min_age must be 0..2^31 - 1 frames, got {min_age}")
+    h, w = _mosaic_size(mask_size, "mask_size", what, 16)
+    if pose.dtype != torch.int64 or tuple(pose.shape) != (16,) or not pose.is_contiguous():
+        raise ValueError(f"{what}: pose must be one contiguous int64 [16] row of pose_chain's output, got {pose.dtype} {tuple(pose.shape)}")
+    ch, cw = _ortho_planes(rank, rgba, what)
+    oy, ox = _mosaic_origin(origin, what)
+    dev = one_device(frame, pose, rank, rgba, *planes, what=what)
+    with torch.cuda.device(dev):
+        planes = [p.contiguous() for p in planes]
+        cur, view, valid = (torch.empty((h, w), dtype=torch.uint8, device=dev) for _ in range(3))
+        check(lib.fs_map_view(ptr(frame.contiguous()), ptr(planes[0]) if planes else None, ptr(planes[1]) if len(planes) > 1 else None, _FORMATS[fmt],
+                              _MATRICES[matrix], int(bool(full_range)), fh, fw, ptr(pose), int(ordinal), h, w, ch, cw, ox, oy, ptr(rank), ptr(rgba),
+                              int(min_age), ptr(cur), ptr(view), ptr(valid), stream_ptr()))
+    return cur, view, valid
+
+
+def map_gate(table, valid):
+    """The matcher's table of (cur, view) gated IN PLACE (and returned) by map_view's valid plane (definition: include/floodseg_test.h,
+    map_gate): int32 table [(H//16) * (W//16), 7], uint8 valid [H,W].  A row stays iff its winner's 16 x 16 window lies wholly on valid
+    pixels; every other row becomes the void row.  One launch; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.map_gate"
+    if valid.dtype != torch.uint8 or valid.dim() != 2 or not valid.is_contiguous():
+        raise ValueError(f"{what}: valid must be a contiguous uint8 [H,W] tensor, got {valid.dtype} {tuple(valid.shape)}")
+    h, w = _mosaic_size(valid.shape, "valid", what, 16)
+    blocks = (h // 16) * (w // 16)
+    if table.dtype != torch.int32 or tuple(table.shape) != (blocks, 7) or not table.is_contiguous():
+        raise ValueError(f"{what}: table must be a contiguous int32 [{blocks},7] tensor for a {h} x {w} plane, got {table.dtype} {tuple(table.shape)}")
+    dev = one_device(table, valid, what=what)
+    with torch.cuda.device(dev):
+        check(lib.fs_map_gate(ptr(table), blocks, ptr(valid), h, w, stream_ptr()))
+    return table
+
+
+def pose_correct(model, state, pose, mask_size, canvas_size, origin):
+    """global_motion's fit of a frame against its map_view folded into the pose chain (definition: include/floodseg_test.h,
+    pose_correct): model int64 [16] or [1,16], state int64 [32] (pose_chain's) and pose int64 [16] (the frame's row) are UPDATED IN
+    PLACE where the fit is good -> out int64 [8] = (status, usable rows, inliers, rounds done, the fit's shift x and y in Q20, 0, 0);
+    status 0 corrected, 2 no fit, 3 the corrected pose would leave the pose bounds, 4 the chain is not tracking this row.  One launch
+    of one wave; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.pose_correct"
+    h, w = _mosaic_size(mask_size, "mask_size", what)
+    ch, cw = _mosaic_size(canvas_size, "canvas_size", what)
+    oy, ox = _mosaic_origin(origin, what)
+    if model.dtype != torch.int64 or tuple(model.shape) not in ((16,), (1, 16)) or not model.is_contiguous():
+        raise ValueError(f"{what}: model must be one contiguous int64 [16] row of global_motion's output, got {model.dtype} {tuple(model.shape)}")
+    if state.dtype != torch.int64 or tuple(state.shape) != (32,) or not state.is_contiguous():
+        raise ValueError(f"{what}: state must be a contiguous int64 [32] tensor, got {state.dtype} {tuple(state.shape)}")
+    if pose.dtype != torch.int64 or tuple(pose.shape) != (16,) or not pose.is_contiguous():
+        raise ValueError(f"{what}: pose must be one contiguous int64 [16] row of pose_chain's output, got {pose.dtype} {tuple(pose.shape)}")
+    dev = one_device(model, state, pose, what=what)
+    with torch.cuda.device(dev):
+        out = torch.empty((8,), dtype=torch.int64, device=dev)
+        check(lib.fs_pose_correct(ptr(model), ptr(state), ptr(pose), h, w, ch, cw, ox, oy, ptr(out), stream_ptr()))
     return out
 
 

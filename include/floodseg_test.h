@@ -1035,6 +1035,73 @@ typedef struct fs_hook_tables9 {
     fs_ext9_api ext9;
 } fs_hook_tables9;
 
+/* ---- The ELEVENTH table.  fs_ext9_api is frozen as well (2 members, 32 bytes; tests/test_ortho_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables9 by the same pattern:
+ *     const fs_hook_tables10* t = (const fs_hook_tables10*)fs_test_hooks();   t->ext10.map_view(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables9: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext10.magic == FS_EXT10_MAGIC and ext10.size >= the end of the member it needs. */
+#define FS_EXT10_MAGIC 0x4653455854413130ull /* "FSEXTA10" */
+
+typedef struct fs_ext10_api {
+    uint64_t magic; /* FS_EXT10_MAGIC */
+    size_t size;    /* sizeof(fs_ext10_api) of the library that was built */
+
+    /* ---- FRAME-TO-MAP REGISTRATION (csrc/refine_ops.hip, csrc/refine_defs.h).  OUR DEFINITION: the reference has nothing
+     * like it.  The pose chain is built from frame-to-frame fits alone and drifts; these three ops are the link between the orthophoto
+     * canvas, the block matcher and global_motion that lets a frame be registered against the ground mapped so far BEFORE it votes:
+     *   map_view -> block_match_modes(cur, view) -> map_gate -> global_motion (n = 1, frame_size = mask_size = (H, W)) -> pose_correct.
+     * The same rules as code: csrc/refine_defs.h (host and device) and tests/refine_ref.py (numpy).  All integer, bit for bit.
+     *
+     * map_view draws the map as this frame should see it under its predicted pose.  The frame arguments (frame, u, v, format, matrix,
+     * full_range, FH, FW), pose (ONE row of pose_chain's output), ordinal, H, W, CH, CW, ox, oy, rank and rgba are ortho_accumulate's;
+     * the canvas is only read.  Three uint8 planes [H][W], each written whole:
+     *   cur[y][x]   = luma(I[y][x]), I = ortho_accumulate's image (the frame through frame_prepare's resize to H x W, as stored uint8),
+     *                 luma = (77 R + 150 G + 29 B + 128) >> 8, the block matcher's;
+     *   valid[y][x] = 1 iff the pose is usable and the canvas pixel (X, Y) under the centre of frame pixel (x, y) lies in the canvas, has
+     *                 rgba >> 24 != 0 and, ONLY when min_age > 0, ordinal - (uint32_t)rank >= min_age taken in 64 bits (an owner with an
+     *                 ordinal above the frame's own is NOT valid); with min_age == 0 rank is not read.  0 otherwise;
+     *   view[y][x]  = luma of that canvas pixel's (R, G, B) where valid, 0 where not.
+     * The pose is usable when its status is 0 or 1 and to_anchor's linear entries are below 16 and its translation below 2^14 pixels in
+     * magnitude (pose_in_bounds' bounds for to_anchor), tested before any product.  Then, with t = to_anchor:
+     *   ax = (2x + 1) << 19, ay alike;  cx = ((t00 ax + t01 ay + 2^19) >> 20) + t02;  X = (cx >> 20) + ox;  Y alike.
+     * |t| < 2^24 and |ax| < 2^35: the two products stay below 2^60.
+     * ONE launch: a thread per four pixels of a row; dword stores where W % 4 == 0 and the three planes are aligned to 4 bytes, bytes
+     * otherwise.
+     * Refused before a launch: a null frame, pose, rank, rgba, cur, view or valid, or a null chroma pointer of a YUV format; format,
+     * matrix or range code out of range; FH, FW, CH or CW outside 1..16384; H or W outside 16..16384; |ox| or |oy| > 16384; ordinal
+     * 0xFFFFFFFF; min_age negative; pose or rank not aligned to 8 bytes, rgba to 4. */
+    int (*map_view)(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const int64_t* pose,
+                    uint32_t ordinal, int H, int W, int CH, int CW, int ox, int oy, const uint64_t* rank, const uint32_t* rgba, int min_age, uint8_t* cur,
+                    uint8_t* view, uint8_t* valid, fs_stream stream);
+
+    /* ---- map_gate: no vector from ground the map does not hold.  table is block_match_modes' for (cur, view), blocks = (H / 16) (W / 16)
+     * rows of 7 ints, gated IN PLACE: a row stays as it is iff the WINNER's window [src_x - 8, src_x + 8) x [src_y - 8, src_y + 8) lies
+     * inside the plane (tested in 64 bits before any read: a row is device memory and may hold anything) and all 256 bytes of `valid`
+     * under it are 1; every other row becomes the void row (-1, 16, 16, -16, -16, -16, -16).  A void row has no window inside any plane
+     * and stays void.  A candidate that lay over invalid pixels saw zeros there: if it won, its row is voided; if it lost, the winner
+     * beat it honestly.  ONE launch: a wave per row, four bytes a lane, one ballot.
+     * Refused before a launch: a null table or valid; H or W outside 16..16384; blocks != (H / 16) (W / 16); table not aligned to 4. */
+    int (*map_gate)(int32_t* table, int blocks, const uint8_t* valid, int H, int W, fs_stream stream);
+
+    /* ---- pose_correct folds global_motion's fit of (cur, view) into the chain.  model: ONE row of global_motion; state: pose_chain's 32
+     * words; pose: the frame's row, the one map_view drew with; out: 8 words = (status, usable rows, inliers, rounds done, fwd[2],
+     * fwd[5], 0, 0), the middle five copied from the model row.  The forward model maps a frame pixel to the view pixel that shows the
+     * same ground, and the view was drawn with to_anchor, so:
+     *   status 4: the pose row is lost, the state's phase is not TRACKING, or the state's to_anchor is not the row's.  Nothing changes.
+     *   status 2: model[12] != 0, or the model is outside pose_chain's pair bounds.  Nothing changes.
+     *   else to_next = compose(to_anchor, fwd), from_next = compose(inv, from_anchor) -- pose_chain's own two lines;
+     *   status 3: the state's poses or the new ones are outside pose_chain's pose bounds.  Nothing changes.
+     *   status 0: words 0..11 of the state and of the pose row become the new poses, pose[13] (clipped) is recomputed.
+     * last_fwd, last_inv, the phase, the counters and the bridge run of the state are never written.  ONE launch of one wave.
+     * Refused before a launch: a null pointer; H, W, CH or CW outside 1..16384; |ox| or |oy| > 16384; a pointer not aligned to 8 bytes. */
+    int (*pose_correct)(const int64_t* model, int64_t* state, int64_t* pose, int H, int W, int CH, int CW, int ox, int oy, int64_t* out, fs_stream stream);
+} fs_ext10_api;
+
+typedef struct fs_hook_tables10 {
+    fs_hook_tables9 base9;
+    fs_ext10_api ext10;
+} fs_hook_tables10;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

@@ -95,6 +95,13 @@ map blended over it at `--ortho-alpha A` (default 96 of 255); `--ortho-edge K [K
 classes' boundaries, `--ortho-plain` leaves the extent map off.  `--ortho-mode centre` (default) gives each piece of ground to the view that
 saw it nearest its optical axis, `latest` to the newest view.  No feathering or exposure matching across seams and no lens model: the
 chain's drift shows as broken roads at the seams, which is what the picture is for.  Not validated on real video.
+`--mosaic-refine` (an extension; needs `--ortho`) registers every frame against the orthophoto gathered so far before it
+votes: the map is drawn as the frame should see it under its predicted pose, the block matcher finds the residual shift within
+`--refine-search R` mask pixels (default 8), the camera-motion fit of `--mosaic` turns it into an affine, and the pose chain is corrected.
+`--refine-min-age N` matches only against ground owned by a frame at least N frames older (loop closure on a revisit only),
+`--refine-every N` registers every N-th frame, `--refine-intra-bias B` lets the matcher drop blocks the map does not explain.
+`--mosaic-report` then also lists the correction per frame.  Earlier frames are never re-posed and drift beyond the search radius is not
+recovered; the defaults are guesses, not validated on real video.
 Directory layout read (flow/dataset.py:222-240): <data-root>/frames/<video-id>/{images/<i>.jpg, grids/<i>.npy, inv_grids/<i>.npy}.
 Checkpoints are loaded with `torch.load(..., weights_only=True)` (a Lightning `state_dict` with the `model_G.model.` prefix, or
 a bare state_dict); `--synthetic-weights` uses the seeded random weights of the test-suite instead (no checkpoint ships with
@@ -241,6 +248,15 @@ def parse_args(argv=None):
     ap.add_argument("--ortho-edge", type=int, nargs="+", default=None, metavar="K", help="--ortho: classes that get a one-pixel opaque line along the inside "
                     "of their boundary (default: none)")
     ap.add_argument("--ortho-plain", action="store_true", help="--ortho: the imagery alone, without the extent map")
+    ap.add_argument("--mosaic-refine", action="store_true", help="--ortho: register every frame against the orthophoto so far and correct its pose before it "
+                    "votes (DESIGN 3.20; the defaults are guesses, not validated on real video)")
+    ap.add_argument("--refine-search", type=int, default=None, metavar="R", help="--mosaic-refine: the matcher's search radius against the map in mask pixels "
+                    "(1..32, default 8); drift beyond it is not recovered")
+    ap.add_argument("--refine-min-age", type=int, default=None, metavar="N", help="--mosaic-refine: match only against ground owned by a frame at least N "
+                    "frames older (default 0: any mapped ground; N > 0: loop closure on a revisit only)")
+    ap.add_argument("--refine-every", type=int, default=None, metavar="N", help="--mosaic-refine: register every N-th frame (default 1)")
+    ap.add_argument("--refine-intra-bias", type=int, default=None, metavar="B", help="--mosaic-refine: the matcher's intra bias against the map (0..65535, "
+                    "default 65535: no block is intra)")
     ap.add_argument("--mosaic-report", default=None, metavar="FILE.csv", help="--mosaic: per frame the pose, status, clipped flag, inliers and usable "
                     "blocks; per class the canvas pixels and their share of the ground seen")
     ap.add_argument("--draw-outlines", type=int, nargs="?", const=1, default=None, metavar="W", help="--raw-out with --regions: draw a white line W "
@@ -291,6 +307,17 @@ def parse_args(argv=None):
         ap.error("--ortho and its options need --mosaic FILE.png: the orthophoto is gathered with the mosaic's poses, onto its canvas")
     if not args.ortho and (args.ortho_mode is not None or args.ortho_alpha is not None or args.ortho_edge is not None or args.ortho_plain):
         ap.error("--ortho-mode, --ortho-alpha, --ortho-edge and --ortho-plain need --ortho FILE.png")
+    refine_options = (args.refine_search, args.refine_min_age, args.refine_every, args.refine_intra_bias)
+    if not args.ortho and (args.mosaic_refine or any(v is not None for v in refine_options)):
+        ap.error("--mosaic-refine and its options need --ortho FILE.png: a frame is registered against the orthophoto canvas")
+    if not args.mosaic_refine and any(v is not None for v in refine_options):
+        ap.error("--refine-search, --refine-min-age, --refine-every and --refine-intra-bias need --mosaic-refine")
+    args.refine_search = 8 if args.refine_search is None else args.refine_search
+    args.refine_min_age = 0 if args.refine_min_age is None else args.refine_min_age
+    args.refine_every = 1 if args.refine_every is None else args.refine_every
+    args.refine_intra_bias = 65535 if args.refine_intra_bias is None else args.refine_intra_bias
+    if not 1 <= args.refine_search <= 32 or args.refine_min_age < 0 or args.refine_every < 1 or not 0 <= args.refine_intra_bias <= 65535:
+        ap.error("--refine-search takes 1..32, --refine-min-age 0 or more, --refine-every 1 or more and --refine-intra-bias 0..65535")
     args.ortho_mode = args.ortho_mode or "centre"
     args.ortho_alpha = 96 if args.ortho_alpha is None else args.ortho_alpha
     args.ortho_edge = args.ortho_edge or []
@@ -389,7 +416,9 @@ def main():
                          stabilize=args.stabilize, stabilize_trust=args.stabilize_trust, stabilize_compensate=args.stabilize_compensate,
                          proximity=args.proximity, proximity_sources=args.proximity_sources, proximity_targets=args.proximity_targets,
                          proximity_max=args.proximity_max, mosaic=mosaic_size, mosaic_classes=min(args.classes, 32), mosaic_rounds=args.mosaic_rounds,
-                         mosaic_tol=args.mosaic_tol, mosaic_exclude=args.mosaic_exclude, ortho=args.ortho_mode if args.ortho else None)
+                         mosaic_tol=args.mosaic_tol, mosaic_exclude=args.mosaic_exclude, ortho=args.ortho_mode if args.ortho else None,
+                         mosaic_refine=args.mosaic_refine, refine_search=args.refine_search, refine_intra_bias=args.refine_intra_bias,
+                         refine_min_age=args.refine_min_age, refine_every=args.refine_every)
     if (args.report or args.regions) and world > 1:
         raise SystemExit("--report / --regions cover one process's frames: run them on a single GPU")
     if args.raw:
@@ -524,7 +553,7 @@ def main():
         rgb[cls == 255] = 0  # no frame looked here
         Image.fromarray(rgb).save(args.mosaic)
         if args.mosaic_report:
-            write_mosaic_csv(args.mosaic_report, report_ids, poses, totals)
+            write_mosaic_csv(args.mosaic_report, report_ids, poses, totals, pred.refine_report() if args.mosaic_refine else None)
         lost = int((poses[:, 12] == 2).sum())
         print(f"--mosaic: {int((seen > 0).sum())} canvas pixels seen by {len(poses) - lost} frames"
               + (f"; {lost} frames lost (a scene cut, or more failed fits running than are bridged)" if lost else "")
@@ -536,6 +565,10 @@ def main():
         image, src, covered = pred.ortho_report(palette=palette, alpha=args.ortho_alpha, edge=args.ortho_edge, overlay=not args.ortho_plain)
         Image.fromarray(image).save(args.ortho)
         print(f"--ortho: {covered} canvas pixels covered, taken from {len(set(np.unique(src).tolist()) - {-1})} frames ({args.ortho_mode} view wins)",
+              file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    if args.mosaic_refine:
+        status = pred.refine_report()[:, 0]
+        print(f"--mosaic-refine: {int((status == 0).sum())} of {len(status)} frames corrected against the map, {int((status == 2).sum())} without a fit",
               file=sys.stderr if args.raw_out == "-" else sys.stdout)
     if args.report:  # the device report is read back ONCE, here, after the timed run
         report = pred.extent_report() if args.confidence else (torch.cat(areas).cpu().numpy() if areas else np.zeros((0, args.classes, 3), np.int64))
