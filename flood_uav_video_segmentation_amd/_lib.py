@@ -219,6 +219,12 @@ _EXT10_HOOKS = [
 ]
 EXT10_MAGIC = 0x4653455854413130  # FS_EXT10_MAGIC
 
+# members of fs_ext11_api, the twelfth table (append-only, behind the eleven frozen ones), in declaration order after `magic` and `size`
+_EXT11_HOOKS = [
+    ("guide_vectors", c_int, [c_void] * 2 + [c_int] * 4 + [ctypes.c_int64] + [c_void] * 2 + [c_int, c_void, c_int, c_int] + [c_void] * 3),
+]
+EXT11_MAGIC = 0x4653455854413131  # FS_EXT11_MAGIC
+
 
 def _struct(name, *fields):
     return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
@@ -252,6 +258,8 @@ FsExt9Api = _struct("FsExt9Api", *_EXT_HEAD, *_members(_EXT9_HOOKS))
 FsHookTables9 = _struct("FsHookTables9", ("base8", FsHookTables8), ("ext9", FsExt9Api))
 FsExt10Api = _struct("FsExt10Api", *_EXT_HEAD, *_members(_EXT10_HOOKS))
 FsHookTables10 = _struct("FsHookTables10", ("base9", FsHookTables9), ("ext10", FsExt10Api))
+FsExt11Api = _struct("FsExt11Api", *_EXT_HEAD, *_members(_EXT11_HOOKS))
+FsHookTables11 = _struct("FsHookTables11", ("base10", FsHookTables10), ("ext11", FsExt11Api))
 
 # One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
 # the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
@@ -270,6 +278,7 @@ _TABLES = [
     _Table("eight", "eighth", _EXT8_HOOKS, "EXT8_MAGIC", FsExt8Api, FsHookTables8, "ext8"),
     _Table("nine", "ninth", _EXT9_HOOKS, "EXT9_MAGIC", FsExt9Api, FsHookTables9, "ext9"),
     _Table("ten", "tenth", _EXT10_HOOKS, "EXT10_MAGIC", FsExt10Api, FsHookTables10, "ext10"),
+    _Table("eleven", "eleventh", _EXT11_HOOKS, "EXT11_MAGIC", FsExt11Api, FsHookTables11, "ext11"),
 ]
 _TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
@@ -350,7 +359,7 @@ def _hook_names(n):
 
 
 (hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
- ext8_hook_names, ext9_hook_names, ext10_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
+ ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

@@ -589,7 +589,15 @@ static int fs_pose_correct(const int64_t* model, int64_t* state, int64_t* pose, 
                                    CW, ox, oy, reinterpret_cast<long long*>(out), S(stream));
 }
 
-// the eleven tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// the matcher's tables guided by the camera model (motion_ops.hip): the launcher validates, nothing is launched on a refusal
+static int fs_guide_vectors(const int32_t* mv, const int64_t* model, int n, int FH, int FW, int fill_void, int64_t outlier_q20, const uint8_t* cur,
+                            const uint8_t* ref, int channels, const int32_t* cost, int penalty, int guide_bias, int32_t* out, int64_t* counts,
+                            fs_stream stream) {
+    return fs::launch_guide_vectors(mv, reinterpret_cast<const long long*>(model), n, FH, FW, fill_void, (long long)outlier_q20, cur, ref, channels, cost,
+                                    penalty, guide_bias, out, reinterpret_cast<long long*>(counts), S(stream));
+}
+
+// the twelve tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -714,7 +722,14 @@ static const fs_hook_tables5& hook_tables(void) {
         fs_map_gate,
         fs_pose_correct,
     }};
+    // fs_ext10_api is frozen too (three members, 40 bytes; tests/test_guide_cpu.py); the twelfth table lies behind it, and &all11.base10 is &all11.
+    static const fs_hook_tables11 all11 = {all10, {
+        FS_EXT11_MAGIC,
+        sizeof(fs_ext11_api),
+        fs_guide_vectors,
+    }};
     {
+        const fs_hook_tables10& all10 = all11.base10;
         const fs_hook_tables9& all9 = all10.base9;
         const fs_hook_tables8& all8 = all9.base8;
         const fs_hook_tables7& all7 = all8.base7;  // from here on both names mean the head of the whole object, not the copies it was built from

@@ -327,6 +327,13 @@ int launch_block_match_modes(const uint8_t* cur, const uint8_t* ref, int H, int 
 // weights = float [n][2], source = int32 [n], written whole by ONE launch of one workgroup.  1 <= n <= WINDOW_MAX_FRAMES (caller).
 constexpr int WINDOW_MAX_FRAMES = 64;
 int launch_window_weights(const int* const* stats, int n, float* weights, int* source, hipStream_t s);
+// The matcher's tables guided by global_motion's camera model (motion_ops.hip, guide_defs.h; definition: include/floodseg_test.h,
+// guide_vectors): mv, out = int32 [n][FH/16 * FW/16][7] (out may be mv), model = int64 [n][16], counts = int64 [n][8]; cur, ref
+// (uint8 [n][FH][FW][channels]) and cost (int32 [n][blocks]) all given = evidence mode, all nullptr = table only.  The launcher refuses
+// bad arguments before it launches anything.  Two launches (counts cleared, the pass); nothing is allocated, synchronised or read on
+// the host.
+int launch_guide_vectors(const int32_t* mv, const long long* model, int n, int FH, int FW, int fill_void, long long outlier_q20, const uint8_t* cur,
+                         const uint8_t* ref, int channels, const int32_t* cost, int penalty, int guide_bias, int32_t* out, long long* counts, hipStream_t s);
 // Frame ingest (ingest_ops.hip): one decoded uint8 frame -> normalised NCHW fp32 [3][h][w].  format 0: RGB24 [H][W][3] in `frame`;
 // 1: NV12, `frame` = Y [H][W], u = interleaved UV [ceil(H/2)][ceil(W/2)][2] (v unused); 2: I420, u and v = [ceil(H/2)][ceil(W/2)] each.
 // matrix 0 / 1 (BT.601 / BT.709) and full_range 0 / 1 pick the integer conversion of include/floodseg_test.h.  mean, std: 3 device

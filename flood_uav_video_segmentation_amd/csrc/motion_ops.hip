@@ -15,7 +15,12 @@
 // block_match_modes (the same search, MODES = true) also decides, per block, whether the winner explains the block at all (intra: its
 // SAD exceeds the block's own deviation from its mean) and, per frame pair, whether so many blocks are intra that the pair is a scene
 // cut; both are expressed as VOID ROWS, vectors that are not there, which mv_owner_kernel (flow_ops.hip) skips.
+//
+// guide_vectors (further down; rules: guide_defs.h) passes over a finished table with global_motion's camera model: void rows take the
+// camera's vector, vectors that disagree with it are replaced -- in evidence mode only if the camera's window explains the block no
+// worse, measured with the luma and the wave sum of this file.
 #include "kernels.h"
+#include "guide_defs.h"
 
 namespace fs {
 namespace {
@@ -28,8 +33,10 @@ constexpr int MAX_ROWS = MB + 2 * MAX_R;
 
 __device__ inline uint32_t luma_u8(uint32_t r, uint32_t g, uint32_t b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
 
-// luma of pixels (y, x .. x + 3) as the four bytes of a dword, x a multiple of 4; pixels outside the frame give 0.
-// whole_dwords: W % 4 == 0 and a 4-byte aligned frame, so the four pixels are inside or outside together and start on a dword.
+// luma of pixels (y, x .. x + 3) as the four bytes of a dword; pixels outside the frame give 0.
+// whole_dwords: W % 4 == 0, a 4-byte aligned frame AND x a multiple of 4, so the four pixels are inside or outside together and start
+// on a dword (the search's staging; the guide kernel's cur block).  Without it x is ANY column and the pixels are read byte by byte:
+// guide_vectors_kernel reads the guide's window of ref that way, at x + pdx.
 template <bool RGB>
 __device__ inline uint32_t load_luma4(const uint8_t* __restrict__ f, int y, int x, int H, int W, bool whole_dwords) {
     if (y < 0 || y >= H || x + 3 < 0 || x >= W) return 0;
@@ -201,7 +208,113 @@ __global__ __launch_bounds__(64) void window_weights_kernel(WindowStats st, int 
     source[f] = src;
 }
 
+// guide_vectors (include/floodseg_test.h; the rules: guide_defs.h): the table of a frame pair guided by global_motion's camera model.
+// One wave per block, four blocks per workgroup; blockIdx.y is the pair.  Every lane computes the same prediction, class and decision
+// from the row (one word per lane, broadcast) and the pair's model row, so every branch is wave-uniform.  Only with EVIDENCE, and only
+// the wave whose row is an outlier with an available guide, touches the frames: four pixels of a block row per lane -- cur through
+// load_luma4's dword path where the frame allows, the guide's window of ref at whatever byte it starts on -- v_sad_u8 and one wave
+// sum.  The <*, false> instantiation holds no frame code.  out may be mv: a row is read and written by its own wave alone, read
+// first.  The counts go through an LDS tally per workgroup and leave with one 64-bit atomic per non-zero cell.
+template <bool RGB, bool EVIDENCE>
+__global__ __launch_bounds__(256) void guide_vectors_kernel(const int* mv, const long long* __restrict__ model, int blocks, int wb, int FH, int FW,
+                                                            int fill_void, long long outlier_q20, const uint8_t* __restrict__ cur,
+                                                            const uint8_t* __restrict__ ref, int whole_dwords, const int* __restrict__ cost, int penalty,
+                                                            int guide_bias, int* out, unsigned long long* __restrict__ counts) {
+    __shared__ uint32_t s_tally[guide::COUNT_WORDS];
+    if (threadIdx.x < guide::COUNT_WORDS) s_tally[threadIdx.x] = 0;
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int f = blockIdx.y, i = (int)blockIdx.x * 4 + wave;
+    if (i < blocks) {
+        const int by = i / wb, bx = i - by * wb;
+        const int cx = bx * MB + MB / 2, cy = by * MB + MB / 2;
+        const size_t blk = (size_t)f * blocks + i;
+        const int mine = lane < guide::ROW_WORDS ? mv[blk * guide::ROW_WORDS + lane] : 0;
+        int32_t r[guide::ROW_WORDS];
+#pragma unroll
+        for (int k = 0; k < guide::ROW_WORDS; ++k) r[k] = __shfl(mine, k, 64);
+        int64_t M[mos::MODEL_WORDS];
+#pragma unroll
+        for (int k = 0; k < mos::MODEL_WORDS; ++k) M[k] = model[(size_t)f * mos::MODEL_WORDS + k];
+        const bool guided = guide::pair_guides(M);  // status and bounds before any product
+        int64_t gx = 0, gy = 0, pdx = 0, pdy = 0;
+        bool avail = false;
+        if (guided) {
+            guide::predict(M, cx, cy, &gx, &gy, &pdx, &pdy);
+            avail = guide::available(pdx, pdy, cx, cy, FH, FW);
+        }
+        int dx, dy;
+        const int cls = guide::classify(r, cx, cy, &dx, &dy);
+        const bool outlier = guided && cls == guide::ROW_VECTOR && guide::is_outlier(dx, dy, gx, gy, outlier_q20);
+        bool ask;
+        int decision = guide::decide(cls, outlier, guided, avail, fill_void, &ask);
+        if (EVIDENCE && ask) {  // available: |pdx|, |pdy| <= 32 and the window lies inside the frame
+            const size_t frame = (size_t)f * FH * FW * (RGB ? 3 : 1);
+            const int y = cy - MB / 2 + (lane >> 2), x = cx - MB / 2 + 4 * (lane & 3);
+            const uint32_t a = load_luma4<RGB>(cur + frame, y, x, FH, FW, whole_dwords != 0);
+            const uint32_t b = load_luma4<RGB>(ref + frame, y + (int)pdy, x + (int)pdx, FH, FW, false);
+            const int64_t cost_g = guide::guide_cost((int64_t)wave_sum(__builtin_amdgcn_sad_u8(a, b, 0u)), penalty, pdx, pdy);
+            if (!guide::evidence_replaces(cost_g, cost[blk], guide_bias)) decision = guide::KEEP;
+        }
+        if (lane < guide::ROW_WORDS) out[blk * guide::ROW_WORDS + lane] = guide::out_word(decision, lane, mine, cx, cy, pdx, pdy);
+        if (lane == 0) {
+            atomicAdd(&s_tally[guide::C_BLOCKS], 1u);
+            if (cls == guide::ROW_VOID) atomicAdd(&s_tally[guide::C_VOID], 1u);
+            if (cls == guide::ROW_FOREIGN) atomicAdd(&s_tally[guide::C_FOREIGN], 1u);
+            if (outlier) atomicAdd(&s_tally[guide::C_OUTLIERS], 1u);
+            if (decision == guide::FILL) atomicAdd(&s_tally[guide::C_FILLED], 1u);
+            if (decision == guide::REPLACE) atomicAdd(&s_tally[guide::C_REPLACED], 1u);
+            if (decision == guide::DROP) atomicAdd(&s_tally[guide::C_DROPPED], 1u);
+            if (decision == guide::KEEP) atomicAdd(&s_tally[guide::C_KEPT], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < guide::COUNT_WORDS && s_tally[threadIdx.x] != 0u)
+        atomicAdd(counts + (size_t)f * guide::COUNT_WORDS + threadIdx.x, (unsigned long long)s_tally[threadIdx.x]);
+}
+
+// counts is cleared by a kernel, not a memset node: n * 8 <= 512 words, one thread each
+__global__ __launch_bounds__(512) void guide_clear_kernel(unsigned long long* __restrict__ counts, int words) {
+    if ((int)threadIdx.x < words) counts[threadIdx.x] = 0ull;
+}
+
+bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
 }  // namespace
+
+int launch_guide_vectors(const int32_t* mv, const long long* model, int n, int FH, int FW, int fill_void, long long outlier_q20, const uint8_t* cur,
+                         const uint8_t* ref, int channels, const int32_t* cost, int penalty, int guide_bias, int32_t* out, long long* counts, hipStream_t s) {
+    static_assert(mos::MAX_FRAMES * guide::COUNT_WORDS <= 512, "guide_clear_kernel clears counts with one workgroup of 512");
+    FS_REQUIRE(mv && model && out && counts, "guide_vectors: null pointer (mv %p, model %p, out %p, counts %p)", (const void*)mv, (const void*)model,
+               (void*)out, (void*)counts);
+    FS_REQUIRE(n >= 1 && n <= mos::MAX_FRAMES, "guide_vectors: n must be 1..%d, got %d", mos::MAX_FRAMES, n);
+    FS_REQUIRE(FH >= guide::MIN_SIDE && FH <= mos::MAX_SIDE && FW >= guide::MIN_SIDE && FW <= mos::MAX_SIDE,
+               "guide_vectors: the frame must be %d..%d pixels a side, got %dx%d", guide::MIN_SIDE, mos::MAX_SIDE, FH, FW);
+    FS_REQUIRE(outlier_q20 >= -1 && outlier_q20 <= guide::MAX_OUTLIER_Q20, "guide_vectors: outlier_q20 must be -1 (off) or 0..%lld, got %lld",
+               (long long)guide::MAX_OUTLIER_Q20, outlier_q20);
+    FS_REQUIRE(penalty >= 0 && penalty <= guide::MAX_PENALTY, "guide_vectors: penalty must be 0..%d, got %d", guide::MAX_PENALTY, penalty);
+    FS_REQUIRE(guide_bias >= 0 && guide_bias <= guide::MAX_BIAS, "guide_vectors: guide_bias must be 0..%d, got %d", guide::MAX_BIAS, guide_bias);
+    const bool evidence = cur && ref && cost;
+    FS_REQUIRE(evidence || (!cur && !ref && !cost), "guide_vectors: cur, ref and cost come together or not at all (cur %p, ref %p, cost %p)",
+               (const void*)cur, (const void*)ref, (const void*)cost);
+    FS_REQUIRE(channels == 1 || channels == 3, "guide_vectors: channels must be 1 (luma) or 3 (RGB), got %d", channels);
+    FS_REQUIRE(aligned_to(mv, 4) && aligned_to(out, 4) && aligned_to(cost, 4), "guide_vectors: mv, out or cost is not aligned to 4 bytes");
+    FS_REQUIRE(aligned_to(model, 8) && aligned_to(counts, 8), "guide_vectors: model or counts is not aligned to 8 bytes");
+    const int wb = FW / MB, blocks = (FH / MB) * wb;
+    guide_clear_kernel<<<1, 512, 0, s>>>(reinterpret_cast<unsigned long long*>(counts), n * guide::COUNT_WORDS);
+    FS_HIP(hipGetLastError());
+    const dim3 grid((unsigned)cdiv(blocks, 4), (unsigned)n);
+    const int whole = FW % 4 == 0 && aligned_to(cur, 4);
+    unsigned long long* tally = reinterpret_cast<unsigned long long*>(counts);
+    if (!evidence)
+        guide_vectors_kernel<false, false><<<grid, 256, 0, s>>>(mv, model, blocks, wb, FH, FW, fill_void, outlier_q20, nullptr, nullptr, 0, nullptr, 0, 0, out, tally);
+    else if (channels == 3)
+        guide_vectors_kernel<true, true><<<grid, 256, 0, s>>>(mv, model, blocks, wb, FH, FW, fill_void, outlier_q20, cur, ref, whole, cost, penalty, guide_bias, out, tally);
+    else
+        guide_vectors_kernel<false, true><<<grid, 256, 0, s>>>(mv, model, blocks, wb, FH, FW, fill_void, outlier_q20, cur, ref, whole, cost, penalty, guide_bias, out, tally);
+    FS_HIP(hipGetLastError());
+    return 0;
+}
 
 int launch_window_weights(const int* const* stats, int n, float* weights, int* source, hipStream_t s) {
     static_assert(WINDOW_MAX_FRAMES == 64, "window_weights_kernel keeps the cut pairs of a window in one 64-lane ballot");

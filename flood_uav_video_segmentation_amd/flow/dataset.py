@@ -23,16 +23,19 @@ MEAN = [0.485 * 255, 0.456 * 255, 0.406 * 255]
 STD = [0.229 * 255, 0.224 * 255, 0.225 * 255]
 
 
-def _grid_source(grids, search, penalty, intra_bias=None, scene_cut=None):
+def _grid_source(grids, search, penalty, intra_bias=None, scene_cut=None, **guide):
     """grids="files": the grids/ and inv_grids/ folders (the reference's layout); "estimate": a flow.motion.GridEstimator
-    (intra_bias / scene_cut: its inter / intra and scene-cut decisions, both off when None)."""
+    (intra_bias / scene_cut: its inter / intra and scene-cut decisions, both off when None; guide, guide_outlier, guide_bias,
+    guide_rounds, guide_tol, guide_min_inliers: its tables guided by the fitted camera motion, off by default)."""
     if grids == "files":
+        if guide.get("guide") or guide.get("guide_outlier") is not None or guide.get("guide_bias") is not None:
+            raise ValueError('guide needs the estimated grids\' motion-vector tables (grids="estimate"); the grids/ folders hold grids, not vectors')
         return None
     if grids != "estimate":
         raise ValueError(f'grids must be "files" or "estimate", got {grids!r}')
     from .motion import GridEstimator
 
-    return GridEstimator(search, penalty, intra_bias=intra_bias, scene_cut=scene_cut)
+    return GridEstimator(search, penalty, intra_bias=intra_bias, scene_cut=scene_cut, **guide)
 
 
 def _check_link_vectors(who, link_vectors, grids):
@@ -75,6 +78,11 @@ class PredictWindows:
     FlowPredictor(compensate=True) links the regions with.  One more search per window (the pair that ends in the window's key frame),
     unless hold_cuts has searched it; with no_warp every pair is searched for its vectors alone.
 
+    guide=True (extension; needs grids="estimate"; guide_outlier, guide_bias, guide_rounds, guide_tol, guide_min_inliers as
+    flow.motion.GridEstimator takes them): the grids and link_mvs come from the tables guided by the fitted camera motion
+    (ops.guide_vectors), and with link_vectors an item also carries "link_raw_mvs", the tables as searched, and
+    "link_guide_counts" (int64 [frame_delta, 8], the same pairs' rows of ops.guide_vectors' counts): what FlowPredictor.guide_report() keeps.
+
     link_sources=True (extension; needs link_vectors=True): an item also carries "link_sources", a list of source(frame_id + p) for the
     window's frame_delta emitted frames (None where a frame does not exist): what FlowPredictor(ortho=...) samples the orthophoto from.
     The frames go through the decode cache; with no_warp the in-between frames are decoded for this alone."""
@@ -84,11 +92,13 @@ class PredictWindows:
     link_sources = False
 
     def __init__(self, data_root, predict_v_id, frame_delta=5, no_warp=False, size=None, device="cuda", grids="files", search=16,
-                 penalty=0, intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False, link_sources=False):
+                 penalty=0, intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False, link_sources=False, guide=False, guide_outlier=None,
+                 guide_bias=None, guide_rounds=4, guide_tol=1.0, guide_min_inliers=12):
         self.hold_cuts = _check_hold_cuts("PredictWindows", hold_cuts, grids, scene_cut)
         self.link_vectors = _check_link_vectors("PredictWindows", link_vectors, grids)
         self.link_sources = _check_link_sources("PredictWindows", link_sources, self.link_vectors)
-        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
+        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut, guide=guide, guide_outlier=guide_outlier, guide_bias=guide_bias,
+                                      guide_rounds=guide_rounds, guide_tol=guide_tol, guide_min_inliers=guide_min_inliers)
         self.data_root, self.video_id = data_root, predict_v_id
         self.frame_delta, self.no_warp = frame_delta, no_warp
         self.size = size  # (h, w) of transform_predict's Resize, None = native
@@ -222,6 +232,11 @@ class PredictWindows:
         the item's grids (and weights), so that only the pairs nobody has searched yet are searched."""
         est = self._video_estimator()
         item["link_mvs"] = est.window_tables(f_index, self.frame_delta, self.raw_frame)
+        if est.guide:  # link_mvs are the GUIDED tables; the tables as searched go with them, for consumers that fit the camera themselves
+            item["link_raw_mvs"] = est.window_raw_tables(f_index, self.frame_delta, self.raw_frame)
+            counts = est.window_guide_counts(f_index, self.frame_delta)
+            if counts is not None:
+                item["link_guide_counts"] = counts
         frame = self.raw_frame(f_index)
         item["link_frame_size"] = (int(frame.shape[0]), int(frame.shape[1]))
         stats = est.window_link_stats(f_index, self.frame_delta)
@@ -268,13 +283,15 @@ class EvalWindows(PredictWindows):
     (batch_size_test = 1, flow/base.py:164)."""
 
     def __init__(self, data_root, data_list, split="test", frame_delta=5, no_warp=False, size=None, center_crop=None,
-                 classes_ignore=(), device="cuda", grids="files", search=16, penalty=0, intra_bias=None, scene_cut=None, link_sources=False):
+                 classes_ignore=(), device="cuda", grids="files", search=16, penalty=0, intra_bias=None, scene_cut=None, link_sources=False, guide=False, guide_outlier=None,
+                 guide_bias=None, guide_rounds=4, guide_tol=1.0, guide_min_inliers=12):
         if split not in ("val", "test"):
             raise ValueError("EvalWindows mirrors the val / test splits; use PredictWindows for predict")
         if link_sources:  # taken so that the three datasets share a signature; an item here is one labelled frame and carries no link keys
             raise ValueError(f"EvalWindows does not support link_sources (its items carry no link_mvs to go with the frames), got link_sources={link_sources}; "
                              "use PredictWindows or RawVideoWindows with link_vectors=True")
-        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
+        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut, guide=guide, guide_outlier=guide_outlier, guide_bias=guide_bias,
+                                      guide_rounds=guide_rounds, guide_tol=guide_tol, guide_min_inliers=guide_min_inliers)
         self.data_root, self.split = data_root, split
         self.frame_delta, self.no_warp = frame_delta, no_warp
         self.size, self.center_crop = size, center_crop      # Resize target (h, w); Crop('center') size of transform_val
@@ -378,7 +395,8 @@ class RawVideoWindows(PredictWindows):
 
     def __init__(self, path, height, width, pix_fmt, frame_delta=5, no_warp=False, size=None, grids="estimate", search=16, penalty=0,
                  matrix="bt709", full_range=False, device="cuda", intra_bias=None, scene_cut=None, hold_cuts=False, link_vectors=False,
-                 link_sources=False):
+                 link_sources=False, guide=False, guide_outlier=None,
+                 guide_bias=None, guide_rounds=4, guide_tol=1.0, guide_min_inliers=12):
         self.hold_cuts = _check_hold_cuts("RawVideoWindows", hold_cuts, grids, scene_cut)
         self.link_vectors = bool(link_vectors)
         self.link_sources = _check_link_sources("RawVideoWindows", link_sources, self.link_vectors)
@@ -390,7 +408,8 @@ class RawVideoWindows(PredictWindows):
             raise ValueError(f'RawVideoWindows: matrix must be "bt601" or "bt709", got {matrix!r}')
         if height < 1 or width < 1 or frame_delta < 1:
             raise ValueError(f"RawVideoWindows: bad geometry {height} x {width}, frame_delta {frame_delta}")
-        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut)
+        self.estimator = _grid_source(grids, search, penalty, intra_bias, scene_cut, guide=guide, guide_outlier=guide_outlier, guide_bias=guide_bias,
+                                      guide_rounds=guide_rounds, guide_tol=guide_tol, guide_min_inliers=guide_min_inliers)
         if not no_warp:
             from .motion import check_geometry
 

@@ -24,6 +24,15 @@ The TABLES themselves have a second consumer: the motion-compensated region link
 integer vectors, which the grids cannot replace -- a grid cell keeps only the source BLOCK of a vector, so any vector of -8..+7 pixels
 is the identity there.  GridEstimator.table_for / window_tables hand them out (the window datasets' link_vectors=True); the block
 search of a frame pair is shared with grids_for, whichever is asked first.
+
+GUIDED TABLES (guide=True).  The tables are weakest on flat, noisy water: with intra_bias = 0 such blocks are void rows
+that keep the identity grid while the ground around them moves with the camera, and without it they carry the least bad of 1089 wrong
+vectors.  After the pair's single search ops.global_motion fits the camera model to the table (in frame pixels) and ops.guide_vectors
+fills the void rows with the camera's vector and, with guide_outlier=, replaces vectors that disagree with it -- with guide_bias=
+only where the camera's window explains the block no worse than the winner did, up to that bias.  The GUIDED table takes the table's
+place everywhere (the cache, grids_for, table_for, window_tables); the RAW one is kept beside it (raw_table_for, window_raw_tables) for
+consumers that fit the camera themselves and must not feed on rows the fit produced.  A cut pair and a failed fit pass through
+untouched.  Off by default; the defaults are guesses, not validated on real video.
 """
 import warnings
 from collections import OrderedDict
@@ -57,23 +66,67 @@ def _warn_cut_without_bias(intra_bias, scene_cut):
 VOID_ROW = (-1, 16, 16, -16, -16, -16, -16)
 
 
-def _search(cur, ref, search, penalty, intra_bias, scene_cut):
-    """(table, stats) of the block search of `cur` against the past frame `ref`; stats None with both decisions off."""
+def _search(cur, ref, search, penalty, intra_bias, scene_cut, return_cost=False):
+    """(table, stats) of the block search of `cur` against the past frame `ref`; stats None with both decisions off.  return_cost:
+    (table, stats, cost), cost the winning costs int32 [blocks]."""
     if intra_bias is None and scene_cut is None:
+        if return_cost:
+            table, cost = ops.block_match(cur, ref, search=search, penalty=penalty, return_cost=True)
+            return table, None, cost
         return ops.block_match(cur, ref, search=search, penalty=penalty), None
+    if return_cost:
+        table, cost, stats = ops.block_match_modes(cur, ref, search=search, penalty=penalty, intra_bias=65535 if intra_bias is None else intra_bias,
+                                                   scene_cut=scene_cut, return_cost=True, return_stats=True)
+        return table, stats, cost
     return ops.block_match_modes(cur, ref, search=search, penalty=penalty, intra_bias=65535 if intra_bias is None else intra_bias,
                                  scene_cut=scene_cut, return_stats=True)
 
 
-def estimate_grids(cur, ref, search=16, penalty=0, intra_bias=None, scene_cut=None, return_stats=False):
+def _check_guide(what, guide, guide_outlier, guide_bias, guide_rounds, guide_tol, guide_min_inliers):
+    """The guide arguments GridEstimator and estimate_grids share -> them, normalised."""
+    if guide_outlier is not None and not 0 <= float(guide_outlier) <= 64:
+        raise ValueError(f"{what}: guide_outlier must be 0..64 frame pixels or None, got {guide_outlier}")
+    if guide_bias is not None and not 0 <= int(guide_bias) <= 65535:
+        raise ValueError(f"{what}: guide_bias must be 0..65535 or None, got {guide_bias}")
+    if not 0 <= int(guide_rounds) <= 8 or not 0 <= float(guide_tol) <= 64 or not 3 <= int(guide_min_inliers) <= 1 << 20:
+        raise ValueError(f"{what}: guide_rounds must be 0..8, guide_tol 0..64 and guide_min_inliers 3..2^20, got {guide_rounds}, {guide_tol}, "
+                         f"{guide_min_inliers}")
+    if not guide and (guide_outlier is not None or guide_bias is not None):
+        raise ValueError(f"{what}: guide_outlier / guide_bias need guide=True, got guide={guide!r}")
+    return (bool(guide), None if guide_outlier is None else float(guide_outlier), None if guide_bias is None else int(guide_bias), int(guide_rounds),
+            float(guide_tol), int(guide_min_inliers))
+
+
+def _guided_search(cur, ref, search, penalty, intra_bias, scene_cut, guide_outlier, guide_bias, guide_rounds, guide_tol, guide_min_inliers):
+    """(guided table, stats, raw table, counts int64 [8]) of one pair: the search, the camera fit in frame pixels, the guided table."""
+    size = (int(cur.shape[0]), int(cur.shape[1]))
+    if guide_bias is None:
+        (raw, stats), cost = _search(cur, ref, search, penalty, intra_bias, scene_cut), None
+    else:
+        raw, stats, cost = _search(cur, ref, search, penalty, intra_bias, scene_cut, return_cost=True)
+    model = ops.global_motion(raw[None], size, size, rounds=guide_rounds, tol=guide_tol, min_inliers=guide_min_inliers,
+                              pair_stats=None if stats is None else stats[None])
+    evidence = {} if cost is None else dict(cur=cur[None], ref=ref[None], cost=cost[None], penalty=penalty, guide_bias=guide_bias)
+    table, counts = ops.guide_vectors(raw[None], model, size, fill_void=True, outlier=guide_outlier, **evidence)
+    return table[0], stats, raw, counts[0]
+
+
+def estimate_grids(cur, ref, search=16, penalty=0, intra_bias=None, scene_cut=None, return_stats=False, guide=False, guide_outlier=None,
+                   guide_bias=None, guide_rounds=4, guide_tol=1.0, guide_min_inliers=12):
     """(grid, inv_grid) of frame `cur` against the past frame `ref`: float64 CUDA [67,120,2], normalised with the frame's own height
     and width (extract_motion_vectors.py:94-98).  Enqueues only: nothing is read back to the host.
     intra_bias (0..65535) and / or scene_cut (fraction 0..1): the table comes from ops.block_match_modes (the one left None is off).
     The cut rule counts intra blocks, so scene_cut needs intra_bias to have any effect: alone it never fires, and warns.
-    return_stats appends the call's device stats tensor int32 [4] (None when both are off): how GridEstimator gets at it."""
+    return_stats appends the call's device stats tensor int32 [4] (None when both are off): how GridEstimator gets at it.
+    guide=True (with guide_outlier, guide_bias, guide_rounds, guide_tol, guide_min_inliers as GridEstimator takes them): the grids come
+    from the table guided by the fitted camera motion (ops.guide_vectors)."""
     check_geometry(int(cur.shape[0]), int(cur.shape[1]))
     _warn_cut_without_bias(intra_bias, scene_cut)
-    table, stats = _search(cur, ref, search, penalty, intra_bias, scene_cut)
+    guide = _check_guide("estimate_grids", guide, guide_outlier, guide_bias, guide_rounds, guide_tol, guide_min_inliers)
+    if guide[0]:
+        table, stats = _guided_search(cur, ref, search, penalty, intra_bias, scene_cut, *guide[1:])[:2]
+    else:
+        table, stats = _search(cur, ref, search, penalty, intra_bias, scene_cut)
     with torch.cuda.device(table.device):
         grids = motion_vectors_to_grids(table, int(cur.shape[0]), int(cur.shape[1]), validate=False)
     return (*grids, stats) if return_stats else grids
@@ -89,11 +142,17 @@ class GridEstimator:
 
     table_for(frame_id, load_frame) -> the int32 [blocks, 7] device table of frame_id against frame_id - 1 (an all-void table for frame
     0 and for a frame whose predecessor is missing); window_tables stacks a window's.  Cached like the grids, and ONE block search per
-    frame pair serves both: grids_for takes the table table_for has searched, and the other way round."""
+    frame pair serves both: grids_for takes the table table_for has searched, and the other way round.
+
+    guide=True: every table is the search's table guided by the camera model fitted to it (module docstring); guide_outlier (frame
+    pixels, None = fill void rows only), guide_bias (0..65535: ask the frames, None = replace outliers as they stand), guide_rounds /
+    guide_tol / guide_min_inliers = ops.global_motion's rounds / tol / min_inliers.  raw_table_for / window_raw_tables hand out the
+    tables as searched, guide_counts_for the pair's row of ops.guide_vectors' counts, guide_report all of them in one read-back."""
 
     STATS_CHUNK = 256
 
-    def __init__(self, search=16, penalty=0, cache=64, intra_bias=None, scene_cut=None):
+    def __init__(self, search=16, penalty=0, cache=64, intra_bias=None, scene_cut=None, guide=False, guide_outlier=None, guide_bias=None,
+                 guide_rounds=4, guide_tol=1.0, guide_min_inliers=12):
         if not 1 <= int(search) <= 32 or not 0 <= int(penalty) <= 255:
             raise ValueError(f"GridEstimator: search must be 1..32 and penalty 0..255, got {search}, {penalty}")
         if intra_bias is not None and not 0 <= int(intra_bias) <= 65535:
@@ -104,12 +163,17 @@ class GridEstimator:
         self.intra_bias = None if intra_bias is None else int(intra_bias)
         self.scene_cut = None if scene_cut is None else float(scene_cut)
         _warn_cut_without_bias(intra_bias, scene_cut)
+        (self.guide, self.guide_outlier, self.guide_bias, self.guide_rounds, self.guide_tol,
+         self.guide_min_inliers) = _check_guide("GridEstimator", guide, guide_outlier, guide_bias, guide_rounds, guide_tol, guide_min_inliers)
         self._cache_size = int(cache)
         self._grids = OrderedDict()
         self._tables = OrderedDict()  # frame id -> int32 [blocks, 7]: the searches, shared by grids_for and table_for
         self._frames = OrderedDict()
         self._stats = {}        # frame id -> one row of a chunk below
         self._stat_chunks = []  # int32 [STATS_CHUNK, 4] device buffers: one allocation per STATS_CHUNK estimated pairs, not one per pair
+        self._raw = OrderedDict()  # guide=True: frame id -> the table as searched, cached beside the guided one in _tables
+        self._guide_counts = {}    # frame id -> one row of a chunk below
+        self._guide_chunks = []    # int64 [STATS_CHUNK, 8] device buffers, as the stats'
 
     def reset(self):
         """Forget every cached frame, grid and stats tensor (the caller moves to another video)."""
@@ -118,6 +182,9 @@ class GridEstimator:
         self._frames.clear()
         self._stats.clear()
         self._stat_chunks.clear()
+        self._raw.clear()
+        self._guide_counts.clear()
+        self._guide_chunks.clear()
 
     def stats_for(self, frame_id):
         """The device stats tensor int32 [4] = (blocks, intra blocks, cut, 0) of a pair this estimator has estimated with intra_bias /
@@ -139,6 +206,27 @@ class GridEstimator:
             self._stats[frame_id] = self._stat_chunks[-1][row]
         self._stats[frame_id].copy_(stats)
 
+    def guide_counts_for(self, frame_id):
+        """The device row int64 [8] = ops.GUIDE_COUNTS of a pair this estimator has guided; None for a frame that was not estimated, that
+        took the void table, or with guide=False.  Kept until reset() in shared [256, 8] buffers, like the stats."""
+        return self._guide_counts.get(frame_id)
+
+    def guide_report(self):
+        """(frame ids, int64 [m, 8] host array) of every pair guided since the last reset(), in frame order: ops.GUIDE_COUNTS per pair, read
+        back ONCE here (one stack, one copy)."""
+        ids = sorted(self._guide_counts)
+        if not ids:
+            return [], torch.zeros((0, 8), dtype=torch.int64).numpy()
+        return ids, torch.stack([self._guide_counts[j] for j in ids]).cpu().numpy()
+
+    def _keep_guide_counts(self, frame_id, counts):
+        if frame_id not in self._guide_counts:
+            row = len(self._guide_counts) % self.STATS_CHUNK
+            if row == 0:
+                self._guide_chunks.append(torch.empty((self.STATS_CHUNK, 8), dtype=torch.int64, device=counts.device))
+            self._guide_counts[frame_id] = self._guide_chunks[-1][row]
+        self._guide_counts[frame_id].copy_(counts)
+
     def window_stats(self, first_id, n, load_frame):
         """The n stats tensors (stats_for) of the pairs first_id+1 .. first_id+n of a window whose previous key frame is first_id, as
         ops.window_weights takes them.  A pair that has not been estimated yet -- the closing pair (first_id+n-1 -> first_id+n) feeds no
@@ -159,12 +247,18 @@ class GridEstimator:
         if frame_id in self._tables:
             self._tables.move_to_end(frame_id)
             return self._tables[frame_id]
-        table, stats = _search(cur, ref, self.search, self.penalty, self.intra_bias, self.scene_cut)
+        if self.guide:
+            table, stats, raw, counts = _guided_search(cur, ref, self.search, self.penalty, self.intra_bias, self.scene_cut, self.guide_outlier,
+                                                       self.guide_bias, self.guide_rounds, self.guide_tol, self.guide_min_inliers)
+            self._keep_guide_counts(frame_id, counts)
+            self._raw[frame_id] = raw  # evicted with its guided table below: the two caches hold the same frames
+        else:
+            table, stats = _search(cur, ref, self.search, self.penalty, self.intra_bias, self.scene_cut)
         if stats is not None:
             self._keep_stats(frame_id, stats)
         self._tables[frame_id] = table
         while len(self._tables) > self._cache_size:
-            self._tables.popitem(last=False)
+            self._raw.pop(self._tables.popitem(last=False)[0], None)
         return table
 
     def table_for(self, frame_id, load_frame):
@@ -187,6 +281,27 @@ class GridEstimator:
         key frame is first_id emits.  The first pair (the last frame of the window before -> this window's key frame) feeds no grid of
         any window: one more search per window, unless window_stats (hold_cuts) has searched it as the window before's closing pair."""
         return torch.stack([self.table_for(j, load_frame) for j in range(first_id, first_id + n)])
+
+    def raw_table_for(self, frame_id, load_frame):
+        """table_for's table as the search wrote it, before guidance (the same tensor as table_for's with guide=False).  The pair is
+        searched once, whichever of the two is asked first."""
+        table = self.table_for(frame_id, load_frame)
+        return self._raw.get(frame_id, table) if self.guide else table
+
+    def window_raw_tables(self, first_id, n, load_frame):
+        """window_tables of the raw tables: int32 [n, blocks, 7]."""
+        return torch.stack([self.raw_table_for(j, load_frame) for j in range(first_id, first_id + n)])
+
+    def window_guide_counts(self, first_id, n):
+        """int64 [n, 8]: the counts rows of the same pairs (zeros for a pair that was not guided: frame 0, a missing predecessor), after
+        window_tables; None with guide=False."""
+        if not self.guide:
+            return None
+        rows = [self._guide_counts.get(j) for j in range(first_id, first_id + n)]
+        some = next((r for r in rows if r is not None), None)
+        if some is None:
+            return None
+        return torch.stack([torch.zeros_like(some) if r is None else r for r in rows])
 
     def window_link_stats(self, first_id, n):
         """int32 [n, 4]: the stats rows of the same pairs (zeros for a pair without stats: no cut), after window_tables; None with both

@@ -367,6 +367,7 @@ class FlowPredictor:
         self._mosaic_state = None
         self._mosaic_at = None
         self._mosaic_poses = FrameRows(((16,), torch.int64))  # the per-frame pose rows, REPORT_CHUNK frames a chunk
+        self._guide_counts = FrameRows(((8,), torch.int64))   # the windows' link_guide_counts rows (the datasets' guide=True), as they come
         if ortho is not None and ortho not in ops.ORTHO_MODES:
             raise ValueError(f"FlowPredictor: ortho must be None or one of {sorted(ops.ORTHO_MODES)}, got {ortho!r}")
         if ortho is not None and self.mosaic is None:
@@ -408,7 +409,7 @@ class FlowPredictor:
     def clear_report(self):
         """Forget the extent report and the region report of the frames predicted so far."""
         for table in (self._extent, self._regions, self._tracks, self._outlines, self._simple, self._stabilize_counts, self._proximity, self._mosaic_poses,
-                      self._refine_outs):
+                      self._refine_outs, self._guide_counts):
             table.clear()  # the tracks' previous frame and next id stay, and so does the stabiliser's state plane
         self._despeckle_counts = []
         self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
@@ -474,6 +475,25 @@ class FlowPredictor:
             return np.zeros((0, 4), dtype=np.int64)
         return self._stabilize_counts.flat().cpu().numpy()
 
+    def _keep_guide_counts(self, n, link_guide_counts):
+        """A window's link_guide_counts (int64 [n, 8], ops.guide_vectors' counts of its n frame pairs; None: the window was not guided)
+        into the next rows of the chunked buffers, device to device; nothing is read back."""
+        if link_guide_counts is None:
+            return
+        if link_guide_counts.dtype != torch.int64 or tuple(link_guide_counts.shape) != (n, 8):
+            raise ValueError(f"FlowPredictor: link_guide_counts must be int64 [{n}, 8] for the window's n = {n} frames, got {link_guide_counts.dtype} "
+                             f"{tuple(link_guide_counts.shape)}")
+        for done, take, _, (rows,) in self._guide_counts.pieces(n, self.REPORT_CHUNK, link_guide_counts.device):
+            rows.copy_(link_guide_counts[done:done + take])
+
+    def guide_report(self):
+        """int64 numpy [frames, 8] = ops.GUIDE_COUNTS (blocks, void rows in, filled, outliers, replaced, dropped, kept by evidence, foreign)
+        of the frame pair that ends in every frame predicted since the start (or clear_report()) whose window came with
+        link_guide_counts, in the order the windows were predicted; a frame without a guided pair has a row of zeros.  ONE read-back, here."""
+        if not self._guide_counts.chunks:
+            return np.zeros((0, 8), dtype=np.int64)
+        return self._guide_counts.flat().cpu().numpy()
+
     def _track_link(self, link):
         """What _link_inputs returned, for the tracks: theirs only under compensate=True (stabilize_compensate=True alone leaves them in place)."""
         return link if self.compensate else None
@@ -490,7 +510,7 @@ class FlowPredictor:
             self._mosaic_votes = torch.zeros((self.mosaic_classes, ch, cw), dtype=torch.int16, device=dev).view(torch.uint16)  # the same zero bits
             self._mosaic_state = torch.zeros((32,), dtype=torch.int64, device=dev)
             self._mosaic_at = self.mosaic_origin if self.mosaic_origin is not None else ((ch - h) // 2, (cw - w) // 2)
-        model = ops.global_motion(link[0], link[1], (h, w), self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks,
+        model = ops.global_motion(link[0] if link[3] is None else link[3], link[1], (h, w), self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks,
                                   exclude=self.mosaic_exclude, pair_stats=link[2])
         if self.mosaic_refine:
             poses, outs = self._refined_poses(masks, model, sources)
@@ -583,9 +603,10 @@ class FlowPredictor:
         poses = self._mosaic_poses.flat()
         return cls.cpu().numpy(), conf.cpu().numpy(), seen.cpu().numpy(), totals.cpu().numpy(), poses.cpu().numpy()
 
-    def _link_inputs(self, n, link_mvs, link_frame_size, link_stats):
-        """compensate=True or stabilize_compensate=True: the window's (mvs [n, blocks, 7], frame size, stats [n, 4] or None), checked;
-        None otherwise."""
+    def _link_inputs(self, n, link_mvs, link_frame_size, link_stats, link_raw_mvs=None):
+        """compensate=True, stabilize_compensate=True or mosaic=: the window's (mvs [n, blocks, 7], frame size, stats [n, 4] or None, raw
+        mvs or None), checked; None otherwise.  The raw mvs are the tables as searched, which a dataset with guide=True hands out beside
+        the guided link_mvs: the mosaic's camera fit takes them, so that it never feeds on rows a camera fit produced."""
         if not self.compensate and not self.stabilize_compensate and not self.mosaic:
             return None
         if (link_mvs is None or link_frame_size is None) and not self.compensate and not self.stabilize_compensate:
@@ -600,7 +621,10 @@ class FlowPredictor:
         if link_mvs.dim() != 3 or link_mvs.shape[0] != n or (link_stats is not None and tuple(link_stats.shape) != (n, 4)):
             raise ValueError(f"FlowPredictor: link_mvs must be [n, blocks, 7] and link_stats [n, 4] for the window's n = {n} frames, got "
                              f"{tuple(link_mvs.shape)} and {None if link_stats is None else tuple(link_stats.shape)}")
-        return link_mvs, (int(link_frame_size[0]), int(link_frame_size[1])), link_stats
+        if link_raw_mvs is not None and (link_raw_mvs.shape != link_mvs.shape or link_raw_mvs.dtype != link_mvs.dtype):
+            raise ValueError(f"FlowPredictor: link_raw_mvs must have link_mvs' shape and dtype, got {link_raw_mvs.dtype} {tuple(link_raw_mvs.shape)} and "
+                             f"{link_mvs.dtype} {tuple(link_mvs.shape)}")
+        return link_mvs, (int(link_frame_size[0]), int(link_frame_size[1])), link_stats, link_raw_mvs
 
     def _ortho_sources(self, n, link_sources):
         """ortho=: the window's decoded frames, one (frame, chroma, fmt, matrix, full_range) or None per emitted frame, checked; None otherwise."""
@@ -772,17 +796,21 @@ class FlowPredictor:
         return (masks.cpu().numpy(), conf.cpu().numpy()) if to_host else (masks, conf)
 
     def predict_window(self, frame_prev, frame_next, mvs_left, mvs_right, profiler=None, to_host=True, key_ids=None, key_cache=None,
-                       weights=None, link_mvs=None, link_frame_size=None, link_stats=None, link_sources=None):
+                       weights=None, link_mvs=None, link_frame_size=None, link_stats=None, link_sources=None, link_raw_mvs=None,
+                       link_guide_counts=None):
         """key_cache: a KeyframeCache to use for this call instead of the predictor's own (predict_clip's fallback passes a
         cache that lives for the clip only).  weights: an item's "weights" (the window datasets' hold_cuts; ops.window_weights) for
         the whole-frame and the sliding-crop tails alike, None = the reference's blend.  The key-frame cache is unaffected: the
         network's outputs do not depend on them.  link_mvs, link_frame_size, link_stats: an item's keys of those names (the estimate-mode
         datasets' link_vectors=True), needed and used with compensate=True only.  link_sources: an item's key of that name (the datasets'
-        link_sources=True), needed and used with ortho= only."""
+        link_sources=True), needed and used with ortho= only.  link_raw_mvs: an item's key of that name (the datasets' guide=True): the
+        tables as searched, which the mosaic's camera fit takes in place of the guided link_mvs; tracks and stabiliser take link_mvs.
+        link_guide_counts: an item's key of that name, kept for guide_report()."""
         assert frame_prev.shape[0] == 1                      # flow/base.py:263
         assert len(mvs_left) == len(mvs_right)               # :264
         n = len(mvs_left) + 1                                # :266 -- the list length encodes n, also for no_warp dummies
-        link = self._link_inputs(n, link_mvs, link_frame_size, link_stats)
+        link = self._link_inputs(n, link_mvs, link_frame_size, link_stats, link_raw_mvs)
+        self._keep_guide_counts(n, link_guide_counts)
         sources = self._ortho_sources(n, link_sources)
         cache = key_cache if key_cache is not None else self.key_cache
         kc = cache.window(*key_ids) if (cache is not None and key_ids is not None) else None
@@ -871,7 +899,8 @@ class FlowPredictor:
         def emit(w):
             assert w["frame_prev"].shape[0] == 1 and len(w["mvs_left"]) == len(w["mvs_right"])   # flow/base.py:263-264
             n = len(w["mvs_left"]) + 1
-            link = self._link_inputs(n, w.get("link_mvs"), w.get("link_frame_size"), w.get("link_stats"))
+            link = self._link_inputs(n, w.get("link_mvs"), w.get("link_frame_size"), w.get("link_stats"), w.get("link_raw_mvs"))
+            self._keep_guide_counts(n, w.get("link_guide_counts"))
             sources = self._ortho_sources(n, w.get("link_sources"))
             lo_prev, lo_next = store[w["key_ids"][0]], store[w["key_ids"][1]]
             h, wd = w["frame_prev"].shape[2], w["frame_prev"].shape[3]
@@ -931,7 +960,8 @@ class FlowPredictor:
                 yield self.predict_window(plain["frame_prev"], plain["frame_next"], plain["mvs_left"], plain["mvs_right"], profiler, to_host,
                                           plain.get("key_ids"), key_cache=local_cache, weights=plain.get("weights"), link_mvs=plain.get("link_mvs"),
                                           link_frame_size=plain.get("link_frame_size"), link_stats=plain.get("link_stats"),
-                                          link_sources=plain.get("link_sources"))
+                                          link_sources=plain.get("link_sources"), link_raw_mvs=plain.get("link_raw_mvs"),
+                                          link_guide_counts=plain.get("link_guide_counts"))
             elif exhausted and not pending and not queue:
                 return
 
@@ -1042,6 +1072,17 @@ MOSAIC_STATUS = ("ok", "bridged", "lost")
 
 
 REFINE_STATUS = ("corrected", "skipped", "no_fit", "out_of_bounds", "lost")
+
+
+def write_guide_csv(path, frame_ids, counts):
+    """FlowPredictor.guide_report()'s (or GridEstimator.guide_report()'s) int64 [m, 8] counts with their frame ids as a CSV, one row per
+    frame (the pair that ends in that frame): frame, then ops.GUIDE_COUNTS (blocks, void rows in, filled, outliers, replaced, dropped, kept by evidence, foreign)."""
+    from ..ops import GUIDE_COUNTS
+
+    with open(path, "w") as fh:
+        fh.write("frame," + ",".join(GUIDE_COUNTS) + "\n")
+        for frame, row in zip(frame_ids, counts):
+            fh.write(f"{int(frame)}," + ",".join(str(int(v)) for v in row) + "\n")
 
 
 def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):

@@ -1373,6 +1373,61 @@ def block_match_modes(cur, ref, search=16, penalty=0, intra_bias=65535, scene_cu
     return (mv, *extra) if extra else mv
 
 
+GUIDE_COUNTS = ("blocks", "void_in", "filled", "outliers", "replaced", "dropped", "kept", "foreign")  # the columns of guide_vectors' counts
+
+
+def guide_vectors(tables, model, frame_size, fill_void=True, outlier=None, cur=None, ref=None, cost=None, penalty=0, guide_bias=None, out=None):
+    """The matcher's tables guided by the fitted camera motion (definition: include/floodseg_test.h, guide_vectors): int32
+    tables [n,blocks,7] of frames of frame_size = (FH, FW) and model int64 [n,16], global_motion's rows fitted with mask_size ==
+    frame_size -> (tables, counts).  fill_void: a void row whose block the camera's vector can serve takes that vector.  outlier (frame
+    pixels, 0..64, None = off; converted to Q20 as global_motion converts tol): a vector further from the camera's than that in x or y is
+    replaced by the camera's, or dropped (made void) where the camera's window leaves the frame.  With cur, ref (uint8 [n,FH,FW] or
+    [n,FH,FW,3]) and cost (int32 [n,blocks], the matcher's winning costs; penalty = the matcher's) an outlier is replaced only if the
+    camera's window explains the block no worse than the winner did, up to guide_bias (0..65535, None = 0): SAD_g + penalty (|dx| + |dy|)
+    <= cost + guide_bias; without them it is replaced as it stands.  A pair whose model has status != 0 is copied.  out: an int32
+    tensor of tables' shape, which may be tables itself.  counts int64 [n,8] = GUIDE_COUNTS per pair.  Two launches; nothing is read
+    back."""
+    lib = _lib.load()
+    what = "floodseg.guide_vectors"
+    fh, fw = _mosaic_size(frame_size, "frame_size", what, 16)
+    blocks = (fh // 16) * (fw // 16)
+    if tables.dtype != torch.int32 or tables.dim() != 3 or not 1 <= tables.shape[0] <= 64 or tuple(tables.shape[1:]) != (blocks, 7) or not tables.is_contiguous():
+        raise ValueError(f"{what}: tables must be contiguous int32 [n,{blocks},7] with n in 1..64 for frames of {fh}x{fw}, got {tables.dtype} {tuple(tables.shape)}")
+    n = tables.shape[0]
+    model = _mosaic_rows(model, "model", what, n)
+    if outlier is not None and not 0 <= float(outlier) <= 64:
+        raise ValueError(f"{what}: outlier must be 0..64 frame pixels or None, got {outlier}")
+    if not 0 <= int(penalty) <= 255:
+        raise ValueError(f"{what}: penalty must be 0..255, got {penalty}")
+    if guide_bias is not None and not 0 <= int(guide_bias) <= 65535:
+        raise ValueError(f"{what}: guide_bias must be 0..65535 or None, got {guide_bias}")
+    given = [name for name, t in (("cur", cur), ("ref", ref), ("cost", cost)) if t is not None]
+    if given and len(given) != 3:
+        raise ValueError(f"{what}: cur, ref and cost come together or not at all, got only {given}")
+    channels = 1
+    if given:
+        if cur.dtype != torch.uint8 or ref.dtype != torch.uint8 or cur.shape != ref.shape or tuple(cur.shape[:3]) != (n, fh, fw) \
+                or cur.dim() not in (3, 4) or (cur.dim() == 4 and cur.shape[3] not in (1, 3)):
+            raise ValueError(f"{what}: cur and ref must be uint8 [{n},{fh},{fw}] or [{n},{fh},{fw},3], got {cur.dtype} {tuple(cur.shape)} and "
+                             f"{ref.dtype} {tuple(ref.shape)} (channels must be 1 or 3)")
+        channels = int(cur.shape[3]) if cur.dim() == 4 else 1
+        if cost.dtype != torch.int32 or tuple(cost.shape) != (n, blocks):
+            raise ValueError(f"{what}: cost must be int32 [{n},{blocks}], got {cost.dtype} {tuple(cost.shape)}")
+    if out is not None and (out.dtype != torch.int32 or out.shape != tables.shape or not out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous int32 {list(tables.shape)} tensor, got {out.dtype} {tuple(out.shape)}")
+    dev = one_device(tables, model, cur, ref, cost, out, what=what)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty_like(tables)
+        counts = torch.empty((n, 8), dtype=torch.int64, device=dev)
+        if given:
+            cur, ref, cost = cur.contiguous(), ref.contiguous(), cost.contiguous()
+        check(lib.fs_guide_vectors(ptr(tables), ptr(model), n, fh, fw, int(bool(fill_void)), -1 if outlier is None else int(round(float(outlier) * POSE_ONE)),
+                                   ptr(cur), ptr(ref), channels, ptr(cost), int(penalty), 0 if guide_bias is None else int(guide_bias), ptr(out),
+                                   ptr(counts), stream_ptr()))
+    return out, counts
+
+
 # ------------------------------------------------------------------------------------------ frame ingest
 # base/foundation.py:27-31 (the value_scale = 255 statistics every transform chain of the reference normalises with)
 MEAN = [0.485 * 255, 0.456 * 255, 0.406 * 255]

@@ -1102,6 +1102,70 @@ typedef struct fs_hook_tables10 {
     fs_ext10_api ext10;
 } fs_hook_tables10;
 
+/* ---- The TWELFTH table.  fs_ext10_api is frozen as well (3 members, 40 bytes; tests/test_guide_cpu.py), so ops added since live in a
+ * table of their own, append-only, that the library places directly behind fs_hook_tables10 by the same pattern:
+ *     const fs_hook_tables11* t = (const fs_hook_tables11*)fs_test_hooks();   t->ext11.guide_vectors(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables10: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext11.magic == FS_EXT11_MAGIC and ext11.size >= the end of the member it needs. */
+#define FS_EXT11_MAGIC 0x4653455854413131ull /* "FSEXTA11" */
+
+typedef struct fs_ext11_api {
+    uint64_t magic; /* FS_EXT11_MAGIC */
+    size_t size;    /* sizeof(fs_ext11_api) of the library that was built */
+
+    /* ---- THE MATCHER'S VECTORS GUIDED BY THE CAMERA MODEL (csrc/motion_ops.hip, csrc/guide_defs.h).  OUR DEFINITION: the
+     * global-motion predictor candidate of an encoder, applied to the finished table.  Integers throughout, bit for bit; the same rules
+     * as code: csrc/guide_defs.h (host and device) and tests/guide_ref.py (numpy).  ONE, rshr and pair_in_bounds are global_motion's
+     * (fs_ext8_api above, csrc/mosaic_defs.h).
+     * Inputs:
+     *   mv           int32 [n][hb * wb][7], hb = FH / 16, wb = FW / 16: the tables of n frame pairs as block_match / block_match_modes write them;
+     *   model        int64 [n][16]: global_motion's rows, fitted with mask_size == frame_size so that the forward affine is in frame pixels;
+     *   fill_void    0 | 1;   outlier_q20  -1 = off, else 0 .. 64 ONE;
+     *   evidence, all three or none: cur, ref uint8 [n][FH][FW][channels] (channels 1 = luma, 3 = RGB reduced with block_match's luma),
+     *   cost int32 [n][hb * wb] (the matcher's winning costs); penalty 0..255 (the matcher's); guide_bias 0..65535.
+     * Outputs: out int32 of mv's shape (it may BE mv); counts int64 [n][8], written whole by every call.
+     * Per pair f and block i = by wb + bx, with the centre taken from the INDEX, (cx, cy) = (16 bx + 8, 16 by + 8) (a void row has lost
+     * its dst), M = model[f], CX = cx ONE, CY = cy ONE:
+     *   PREDICTION   gx = rshr(M0 CX + M1 CY) + M2 - CX, gy = rshr(M3 CX + M4 CY) + M5 - CY (Q20); pdx = rshr(gx), pdy = rshr(gy).
+     *                The pair has NO GUIDE if M[12] != 0 or the row fails pair_in_bounds(M, M + 6); both are tested before any product
+     *                (a row may hold anything).  Inside the bounds |M0|, |M1| <= 2^21 and CX < 2^34: a product is below 2^55, the sum of
+     *                two below 2^56, |gx| < 2^38.
+     *   AVAILABLE    the block's guide is available iff |pdx|, |pdy| <= 32 and the 16 x 16 window at (cx - 8 + pdx, cy - 8 + pdy) lies
+     *                inside the frame: the matcher's own candidate rule.
+     *   CLASS        VOID: r[3] < 0 or r[5] < 0 or r[6] < 0.  FOREIGN: not void, and (r[5], r[6]) != (cx, cy) or |r[3] - r[5]| > 32 or
+     *                |r[4] - r[6]| > 32 (differences in 64 bits).  VECTOR (dx, dy) = (r[3] - r[5], r[4] - r[6]): otherwise.
+     *   OUTLIER      a VECTOR row of a pair with a guide, outlier_q20 >= 0 and |dx ONE - gx| > outlier_q20 or |dy ONE - gy| > outlier_q20
+     *                (integer comparisons; equality is not an outlier).
+     *   DECISION     a pair without a guide: every row copied.  FOREIGN: copied.  VOID with fill_void and an available guide: FILLED,
+     *                (-1, 16, 16, cx + pdx, cy + pdy, cx, cy); otherwise as it was.  OUTLIER without an available guide: DROPPED, the void
+     *                row (-1, 16, 16, -16, -16, -16, -16) -- the camera says its source lay outside the previous frame, so whatever it
+     *                matched is something else.  OUTLIER with an available guide: without evidence REPLACED by the guide row; with
+     *                evidence cost_g = SAD of the block of cur[f] at (cx - 8, cy - 8) against the window of ref[f] at
+     *                (cx - 8 + pdx, cy - 8 + pdy), in the matcher's luma, + penalty (|pdx| + |pdy|), REPLACED iff
+     *                cost_g <= cost[f][i] + guide_bias (in 64 bits), else KEPT BY EVIDENCE (copied).  Every other VECTOR row: copied.
+     *   counts[f]    (blocks, void rows in, filled, outliers, replaced, dropped, kept by evidence, foreign); void and foreign rows are
+     *                counted whether or not the pair has a guide, the other five are 0 without one.
+     * So fill_void = 0 with outlier_q20 = -1 is a copy, and so is a model with status != 0; without evidence a second pass over the
+     * result with the same model changes no row and fills nothing; a table of the rounded model vectors has no outlier at
+     * outlier_q20 >= ONE / 2.
+     * TWO launches: counts cleared by a kernel (not a memset node: DESIGN §3.16); then one wave per block, four blocks per workgroup of
+     * 256, blockIdx.y the pair.  Every lane computes the same prediction, class and decision: the branches are wave-uniform.  Only a wave
+     * whose row is an outlier with an available guide, in evidence mode, reads the frames: 4 pixels a lane, v_sad_u8, one wave sum.
+     * Lanes 0..6 write the row.  counts: an LDS tally per workgroup, one 64-bit atomic per non-zero cell (integer sums: any order gives
+     * the same result).  No thread waits for another workgroup; nothing is allocated, synchronised or read on the host.
+     * Refused before a launch, the offending value named: a null mv, model, out or counts; n outside 1..64; FH or FW outside 16..16384;
+     * outlier_q20 outside -1 .. 64 ONE; penalty outside 0..255; guide_bias outside 0..65535; some but not all of cur, ref, cost;
+     * channels other than 1 or 3; mv, out or cost not aligned to 4 bytes, model or counts not aligned to 8. */
+    int (*guide_vectors)(const int32_t* mv, const int64_t* model, int n, int FH, int FW, int fill_void, int64_t outlier_q20, const uint8_t* cur,
+                         const uint8_t* ref, int channels, const int32_t* cost, int penalty, int guide_bias, int32_t* out, int64_t* counts,
+                         fs_stream stream);
+} fs_ext11_api;
+
+typedef struct fs_hook_tables11 {
+    fs_hook_tables10 base10;
+    fs_ext11_api ext11;
+} fs_hook_tables11;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

@@ -121,7 +121,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_exposure_csv, write_extent_csv, write_mosaic_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_exposure_csv, write_extent_csv, write_guide_csv, write_mosaic_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -168,6 +168,12 @@ def parse_args(argv=None):
                     "deviation from its mean + N gets no vector (identity grid cells).  Default: off; the right N depends on the sensor's noise")
     ap.add_argument("--scene-cut", type=float, metavar="F", help="--grids estimate: 0..1; a frame with more than this fraction of such blocks "
                     "gets the default grid (a scene cut).  Default: off.  Counts the blocks --intra-bias marks: without --intra-bias it never fires")
+    ap.add_argument("--guide", action="store_true", help="--grids estimate: guide the matcher's tables with the camera motion fitted to them "
+                    "(ops.guide_vectors; DESIGN 3.21): blocks without a vector take the camera's.  Default: off")
+    ap.add_argument("--guide-outlier", type=float, metavar="PX", help="--guide: also replace vectors further than PX pixels (0..64) from the camera's")
+    ap.add_argument("--guide-bias", type=int, metavar="N", help="--guide-outlier: replace only where the camera's window explains the block no worse "
+                    "than the winner did, up to N (0..65535); default: replace as it stands")
+    ap.add_argument("--guide-report", metavar="FILE.csv", help="--guide: per frame pair the counts of void, filled, outlier, replaced, dropped and kept rows")
     ap.add_argument("--hold-cuts", action="store_true", help="--scene-cut: across a detected cut hold one key frame's prediction on each side "
                     "instead of blending the two scenes, logits or (--feature-based) encoder features (one more block search per window)")
     ap.add_argument("--raw", metavar="FILE", help="raw video input (ffmpeg -f rawvideo) instead of --data-root / --video-id")
@@ -295,6 +301,14 @@ def parse_args(argv=None):
         ap.error("--compensate needs --tracks: it changes how the tracks' links are counted")
     if args.compensate and (args.grids == "files" or (not args.raw and args.grids is None)):
         ap.error("--compensate needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
+    if not args.guide and (args.guide_outlier is not None or args.guide_bias is not None or args.guide_report):
+        ap.error("--guide-outlier, --guide-bias and --guide-report need --guide")
+    if args.guide and (args.grids == "files" or (not args.raw and args.grids is None)):
+        ap.error("--guide needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
+    if (args.guide_outlier is not None and not 0 <= args.guide_outlier <= 64) or (args.guide_bias is not None and not 0 <= args.guide_bias <= 65535):
+        ap.error("--guide-outlier takes 0..64 pixels and --guide-bias 0..65535")
+    if args.guide_bias is not None and args.guide_outlier is None:
+        ap.error("--guide-bias needs --guide-outlier: only a vector that disagrees with the camera's is put to the frames")
     if not args.mosaic and (args.mosaic_size is not None or args.mosaic_report):
         ap.error("--mosaic-size and --mosaic-report need --mosaic FILE.png")
     if args.mosaic and (args.grids == "files" or (not args.raw and args.grids is None)):
@@ -425,12 +439,13 @@ def main():
         ds = RawVideoWindows(args.raw, args.raw_size[0], args.raw_size[1], args.pix_fmt, frame_delta=args.frame_delta, no_warp=args.no_warp,
                              size=tuple(args.size), grids=args.grids, search=args.search, penalty=args.penalty, matrix=args.matrix,
                              full_range=args.full_range, intra_bias=args.intra_bias, scene_cut=args.scene_cut, hold_cuts=args.hold_cuts,
-                             link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic), link_sources=bool(args.ortho))
+                             link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic), link_sources=bool(args.ortho),
+                             guide=args.guide, guide_outlier=args.guide_outlier, guide_bias=args.guide_bias)
     else:
         ds = PredictWindows(args.data_root, args.video_id, frame_delta=args.frame_delta, no_warp=args.no_warp, size=tuple(args.size),
                             grids=args.grids, search=args.search, penalty=args.penalty, intra_bias=args.intra_bias, scene_cut=args.scene_cut,
                             hold_cuts=args.hold_cuts, link_vectors=args.compensate or args.stabilize_compensate or bool(args.mosaic),
-                            link_sources=bool(args.ortho))
+                            link_sources=bool(args.ortho), guide=args.guide, guide_outlier=args.guide_outlier, guide_bias=args.guide_bias)
     palette = np.loadtxt(args.palette).astype("uint8") if args.palette else PALETTE
     if args.out and rank == 0:
         os.makedirs(args.out, exist_ok=True)
@@ -480,7 +495,8 @@ def main():
         item = ds[w]
         masks = pred.predict_window(item["frame_prev"], item["frame_next"], item["mvs_left"], item["mvs_right"], to_host=False,
                                     key_ids=item["key_ids"], weights=item.get("weights"), link_mvs=item.get("link_mvs"),
-                                    link_frame_size=item.get("link_frame_size"), link_stats=item.get("link_stats"), link_sources=item.get("link_sources"))
+                                    link_frame_size=item.get("link_frame_size"), link_stats=item.get("link_stats"), link_sources=item.get("link_sources"),
+                                    link_raw_mvs=item.get("link_raw_mvs"), link_guide_counts=item.get("link_guide_counts"))
         if args.confidence:
             masks, conf = masks
             if conf_writer is not None:
@@ -541,6 +557,12 @@ def main():
         cuts = [i for i, s in zip(ids, host) if s[2]]
         print(f"rank {rank}: {len(ids)} frame pairs estimated, mean intra share {float((host[:, 1] / host[:, 0]).mean()):.4f}, "
               f"scene cuts at frames {cuts if cuts else 'none'}", file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    if args.guide and ds.estimator is not None:  # the kept device counts are read back ONCE, here, after the timed run
+        guided_ids, guided = ds.estimator.guide_report()
+        if args.guide_report:
+            write_guide_csv(args.guide_report, guided_ids, guided)
+        print(f"rank {rank}: --guide: {len(guided_ids)} frame pairs, {int(guided[:, 2].sum())} rows filled, {int(guided[:, 4].sum())} replaced, "
+              f"{int(guided[:, 5].sum())} dropped, {int(guided[:, 6].sum())} kept by evidence", file=sys.stderr if args.raw_out == "-" else sys.stdout)
     if sources:
         counts = torch.bincount(torch.cat(sources).cpu().long(), minlength=4).tolist()
         print(f"rank {rank}: --hold-cuts: {counts[0]} frames blended, {counts[1]} held from the previous key frame, {counts[2]} from the next, "
