@@ -225,6 +225,16 @@ _EXT11_HOOKS = [
 ]
 EXT11_MAGIC = 0x4653455854413131  # FS_EXT11_MAGIC
 
+# members of fs_ext12_api, the thirteenth table (append-only, behind the twelve frozen ones), in declaration order after `magic` and `size`
+_EXT12_HOOKS = [
+    ("map_coarse", c_int, [c_void] + [c_int] * 3 + [c_void] * 3),
+    ("map_patch", c_int, [c_void] * 3 + [c_int] * 5 + [c_void] + [c_int] * 7 + [c_void] * 4),
+    ("map_locate", c_int, [c_void] * 2 + [c_int] * 2 + [c_void] * 3 + [c_int] * 2 + [c_void] * 3),
+    ("pose_relocate", c_int, [c_void] * 4 + [c_int] * 9 + [c_void]),
+    ("relocate_commit", c_int, [c_void] * 6 + [c_int] + [c_void] * 2),
+]
+EXT12_MAGIC = 0x4653455854413132  # FS_EXT12_MAGIC
+
 
 def _struct(name, *fields):
     return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
@@ -260,6 +270,8 @@ FsExt10Api = _struct("FsExt10Api", *_EXT_HEAD, *_members(_EXT10_HOOKS))
 FsHookTables10 = _struct("FsHookTables10", ("base9", FsHookTables9), ("ext10", FsExt10Api))
 FsExt11Api = _struct("FsExt11Api", *_EXT_HEAD, *_members(_EXT11_HOOKS))
 FsHookTables11 = _struct("FsHookTables11", ("base10", FsHookTables10), ("ext11", FsExt11Api))
+FsExt12Api = _struct("FsExt12Api", *_EXT_HEAD, *_members(_EXT12_HOOKS))
+FsHookTables12 = _struct("FsHookTables12", ("base11", FsHookTables11), ("ext12", FsExt12Api))
 
 # One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
 # the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
@@ -279,6 +291,7 @@ _TABLES = [
     _Table("nine", "ninth", _EXT9_HOOKS, "EXT9_MAGIC", FsExt9Api, FsHookTables9, "ext9"),
     _Table("ten", "tenth", _EXT10_HOOKS, "EXT10_MAGIC", FsExt10Api, FsHookTables10, "ext10"),
     _Table("eleven", "eleventh", _EXT11_HOOKS, "EXT11_MAGIC", FsExt11Api, FsHookTables11, "ext11"),
+    _Table("twelve", "twelfth", _EXT12_HOOKS, "EXT12_MAGIC", FsExt12Api, FsHookTables12, "ext12"),
 ]
 _TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
@@ -359,7 +372,7 @@ def _hook_names(n):
 
 
 (hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
- ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
+ ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names, ext12_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

@@ -597,7 +597,33 @@ static int fs_guide_vectors(const int32_t* mv, const int64_t* model, int n, int 
                                     penalty, guide_bias, out, reinterpret_cast<long long*>(counts), S(stream));
 }
 
-// the twelve tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// relocalisation against the orthophoto (relocate_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_map_coarse(const uint32_t* rgba, int CH, int CW, int scale, uint8_t* cl, uint8_t* cv, fs_stream stream) {
+    return fs::launch_map_coarse(rgba, CH, CW, scale, cl, cv, S(stream));
+}
+static int fs_map_patch(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const int64_t* state, int H,
+                        int W, int CH, int CW, int ox, int oy, int scale, uint8_t* tl, uint8_t* tv, int64_t* geom, fs_stream stream) {
+    return fs::launch_map_patch(frame, u, v, format, matrix, full_range, FH, FW, reinterpret_cast<const long long*>(state), H, W, CH, CW, ox, oy, scale, tl, tv,
+                                reinterpret_cast<long long*>(geom), S(stream));
+}
+static int fs_map_locate(const uint8_t* cl, const uint8_t* cv, int ch, int cw, const uint8_t* tl, const uint8_t* tv, const int64_t* geom, int min_overlap_permille,
+                         int exclude, uint32_t* scores, int64_t* found, fs_stream stream) {
+    return fs::launch_map_locate(cl, cv, ch, cw, tl, tv, reinterpret_cast<const long long*>(geom), min_overlap_permille, exclude, scores,
+                                 reinterpret_cast<long long*>(found), S(stream));
+}
+static int fs_pose_relocate(const int64_t* found, const int64_t* state, int64_t* cand_state, int64_t* cand_pose, int max_mean, int ratio_permille, int H, int W,
+                            int CH, int CW, int ox, int oy, int scale, fs_stream stream) {
+    return fs::launch_pose_relocate(reinterpret_cast<const long long*>(found), reinterpret_cast<const long long*>(state), reinterpret_cast<long long*>(cand_state),
+                                    reinterpret_cast<long long*>(cand_pose), max_mean, ratio_permille, H, W, CH, CW, ox, oy, scale, S(stream));
+}
+static int fs_relocate_commit(const int64_t* cand_state, const int64_t* cand_pose, const int64_t* correct_out, int64_t* state, int64_t* pose, const int64_t* found,
+                              int scale, int64_t* out, fs_stream stream) {
+    return fs::launch_relocate_commit(reinterpret_cast<const long long*>(cand_state), reinterpret_cast<const long long*>(cand_pose),
+                                      reinterpret_cast<const long long*>(correct_out), reinterpret_cast<long long*>(state), reinterpret_cast<long long*>(pose),
+                                      reinterpret_cast<const long long*>(found), scale, reinterpret_cast<long long*>(out), S(stream));
+}
+
+// the thirteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -728,7 +754,18 @@ static const fs_hook_tables5& hook_tables(void) {
         sizeof(fs_ext11_api),
         fs_guide_vectors,
     }};
+    // fs_ext11_api is frozen too (one member, 24 bytes; tests/test_relocate_cpu.py); the thirteenth table lies behind it, and &all12.base11 is &all12.
+    static const fs_hook_tables12 all12 = {all11, {
+        FS_EXT12_MAGIC,
+        sizeof(fs_ext12_api),
+        fs_map_coarse,
+        fs_map_patch,
+        fs_map_locate,
+        fs_pose_relocate,
+        fs_relocate_commit,
+    }};
     {
+        const fs_hook_tables11& all11 = all12.base11;
         const fs_hook_tables10& all10 = all11.base10;
         const fs_hook_tables9& all9 = all10.base9;
         const fs_hook_tables8& all8 = all9.base8;

@@ -431,6 +431,21 @@ int launch_map_view(const uint8_t* frame, const uint8_t* u, const uint8_t* v, in
 int launch_map_gate(int32_t* table, int blocks, const uint8_t* valid, int H, int W, hipStream_t s);
 int launch_pose_correct(const long long* model, long long* state, long long* pose, int H, int W, int CH, int CW, int ox, int oy, long long* out, hipStream_t s);
 
+// Relocalisation of a lost pose chain against the orthophoto (relocate_ops.hip, relocate_defs.h; definitions: include/floodseg_test.h,
+// map_coarse, map_patch, map_locate, pose_relocate and relocate_commit).  The launchers refuse bad arguments before they launch
+// anything.  cl, cv = uint8 [CH / S][CW / S]; tl, tv = uint8 [65536], the first tw th bytes written as [th][tw]; geom = int64 [8];
+// scores = uint32 [ch][cw][2], the caller's workspace; found = int64 [16]; the frame arguments as launch_map_view takes them.  Nothing is
+// allocated, synchronised or read on the host.
+int launch_map_coarse(const uint32_t* rgba, int CH, int CW, int S, uint8_t* cl, uint8_t* cv, hipStream_t s);
+int launch_map_patch(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const long long* state, int H,
+                     int W, int CH, int CW, int ox, int oy, int S, uint8_t* tl, uint8_t* tv, long long* geom, hipStream_t s);
+int launch_map_locate(const uint8_t* cl, const uint8_t* cv, int ch, int cw, const uint8_t* tl, const uint8_t* tv, const long long* geom, int min_overlap_permille,
+                      int exclude, uint32_t* scores, long long* found, hipStream_t s);
+int launch_pose_relocate(const long long* found, const long long* state, long long* cand_state, long long* cand_pose, int max_mean, int ratio_permille, int H, int W,
+                         int CH, int CW, int ox, int oy, int S, hipStream_t s);
+int launch_relocate_commit(const long long* cand_state, const long long* cand_pose, const long long* correct_out, long long* state, long long* pose,
+                           const long long* found, int S, long long* out, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

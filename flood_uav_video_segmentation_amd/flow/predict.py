@@ -220,7 +220,20 @@ class FlowPredictor:
     into the chain BEFORE the frame votes; then ops.ortho_accumulate with the corrected row, so a frame's view holds exactly the frames
     before it.  refine_report() -> int64 [frames, 8]: status (0 corrected, 1 not attempted, 2 no fit, 3 out of the pose bounds, 4 the
     chain is lost), usable rows, inliers, rounds, the fit's shift (x, y) in Q20, 0, 0.  Earlier frames are never re-posed, drift beyond
-    refine_search is not recovered, and all these defaults are guesses, NOT validated on real video."""
+    refine_search is not recovered, and all these defaults are guesses, NOT validated on real video.
+
+    mosaic_relocate=True (extension, needs mosaic_refine=True; False: off, none of its ops is ever called): a lost chain is relocalised
+    against the orthophoto.  Behind its own registration, every frame whose source exists and whose ordinal is a multiple
+    of relocate_every gets ops.map_coarse (relocate_scale 4, 8 or 16), ops.map_patch with the last pose the chain's state holds,
+    ops.map_locate (relocate_min_overlap 0..1 of the patch's cells on mapped ground, relocate_exclude cells around the best placement
+    that the runner-up must keep away from), ops.pose_relocate (relocate_max_mean, relocate_ratio), the fine registration above on the
+    CANDIDATE pose, and ops.relocate_commit, which replaces the chain's state and the frame's row on the device only if the candidate
+    passed all of it.  Nothing is read back, so the host does not know whether the chain is lost: the sequence runs for every such frame
+    and its kernels return at once for a chain that is tracking (status 1).  A relocated frame votes and enters the orthophoto like a
+    tracked one.  relocate_report() -> int64 [frames, 8]: status (0 relocated, 1 not attempted, 2 no placement, 3 rejected by the mean,
+    4 rejected by uniqueness, 5 the fine registration failed, 6 the patch was refused, 7 out of the pose bounds), the shift in canvas
+    pixels (x, y), sad*, n*, sad2, n2, eligible placements.  Translation only; flat water and repetitive ground are rejected, not placed;
+    ground voted before the break is never re-posed; all these defaults are guesses, NOT validated on real video."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
     ORTHO_MAX_FRAMES = 1 << 31  # ordinals 0 .. 2^31 - 1: what ortho_report()'s int32 src can name
@@ -231,7 +244,8 @@ class FlowPredictor:
                  max_vertices=32768, simplify=None, simplify_rounds=32, keep_window_regions=False, stabilize=None, stabilize_trust=None,
                  stabilize_compensate=False, proximity=None, proximity_sources=(1,), proximity_targets=(3, 4), proximity_max=None, mosaic=None,
                  mosaic_classes=None, mosaic_rounds=4, mosaic_tol=1.0, mosaic_min_inliers=12, mosaic_exclude=(1,), mosaic_bridge=2, mosaic_origin=None,
-                 ortho=None, mosaic_refine=False, refine_search=8, refine_penalty=0, refine_intra_bias=65535, refine_min_age=0, refine_every=1):
+                 ortho=None, mosaic_refine=False, refine_search=8, refine_penalty=0, refine_intra_bias=65535, refine_min_age=0, refine_every=1,
+                 mosaic_relocate=False, relocate_scale=8, relocate_every=1, relocate_min_overlap=0.5, relocate_exclude=2, relocate_max_mean=16, relocate_ratio=0.8):
         from .model import KeyframeCache
 
         self.model = flow_model
@@ -389,6 +403,23 @@ class FlowPredictor:
         self.refine_search, self.refine_penalty, self.refine_intra_bias = int(refine_search), int(refine_penalty), int(refine_intra_bias)
         self.refine_min_age, self.refine_every = int(refine_min_age), int(refine_every)
         self._refine_outs = FrameRows(((8,), torch.int64))  # pose_correct's out rows, kept in step with _mosaic_poses
+        if mosaic_relocate and not mosaic_refine:
+            raise ValueError("FlowPredictor: mosaic_relocate=True needs mosaic_refine=True: a coarse placement is committed only through the fine registration")
+        if relocate_scale not in ops.RELOCATE_SCALES:
+            raise ValueError(f"FlowPredictor: relocate_scale must be one of {list(ops.RELOCATE_SCALES)}, got {relocate_scale!r}")
+        if int(relocate_every) < 1:
+            raise ValueError(f"FlowPredictor: relocate_every must be at least 1, got {relocate_every}")
+        if not 0.001 <= float(relocate_min_overlap) <= 1.0 or not 0.001 <= float(relocate_ratio) <= 1.0:
+            raise ValueError(f"FlowPredictor: relocate_min_overlap and relocate_ratio must be 0.001..1, got {relocate_min_overlap} and {relocate_ratio}")
+        if not 0 <= int(relocate_exclude) <= 64:
+            raise ValueError(f"FlowPredictor: relocate_exclude must be 0..64 cells, got {relocate_exclude}")
+        if not 0 <= int(relocate_max_mean) <= 255:
+            raise ValueError(f"FlowPredictor: relocate_max_mean must be 0..255, got {relocate_max_mean}")
+        self.mosaic_relocate = bool(mosaic_relocate)
+        self.relocate_scale, self.relocate_every, self.relocate_exclude = int(relocate_scale), int(relocate_every), int(relocate_exclude)
+        self.relocate_min_overlap, self.relocate_ratio = int(round(1000 * float(relocate_min_overlap))), int(round(1000 * float(relocate_ratio)))  # permille
+        self.relocate_max_mean = int(relocate_max_mean)
+        self._relocate_outs = FrameRows(((8,), torch.int64))  # relocate_commit's out rows, kept in step with _mosaic_poses
 
     # the chunk lists that tests count, under the names they had before the tables moved into FrameRows
     _report_chunks = property(lambda self: self._extent.chunks)
@@ -409,7 +440,7 @@ class FlowPredictor:
     def clear_report(self):
         """Forget the extent report and the region report of the frames predicted so far."""
         for table in (self._extent, self._regions, self._tracks, self._outlines, self._simple, self._stabilize_counts, self._proximity, self._mosaic_poses,
-                      self._refine_outs, self._guide_counts):
+                      self._refine_outs, self._relocate_outs, self._guide_counts):
             table.clear()  # the tracks' previous frame and next id stay, and so does the stabiliser's state plane
         self._despeckle_counts = []
         self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
@@ -513,7 +544,7 @@ class FlowPredictor:
         model = ops.global_motion(link[0] if link[3] is None else link[3], link[1], (h, w), self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks,
                                   exclude=self.mosaic_exclude, pair_stats=link[2])
         if self.mosaic_refine:
-            poses, outs = self._refined_poses(masks, model, sources)
+            poses, outs, relocs = self._refined_poses(masks, model, sources)
         else:
             poses = ops.pose_chain(model, self._mosaic_state, (h, w), self.mosaic, self._mosaic_at, self.mosaic_bridge)
         ops.mosaic_accumulate(masks, poses, self._mosaic_votes, self._mosaic_at)
@@ -521,6 +552,10 @@ class FlowPredictor:
             rows.copy_(poses[done:done + take])
             if self.mosaic_refine:
                 self._refine_outs.rows(row, take, self.REPORT_CHUNK, dev)[0].copy_(outs[done:done + take])
+            if self.mosaic_relocate:
+                self._relocate_outs.rows(row, take, self.REPORT_CHUNK, dev)[0].copy_(relocs[done:done + take])
+        if self.mosaic_relocate:
+            self._relocate_outs.frames = self._mosaic_poses.frames
         if self.mosaic_refine:
             self._refine_outs.frames = self._mosaic_poses.frames
         elif self.ortho:
@@ -532,9 +567,10 @@ class FlowPredictor:
             self._ortho_frames += n
 
     def _refined_poses(self, masks, model, sources):
-        """mosaic_refine=True: the window walked frame by frame -> (poses [n, 16], pose_correct's out rows [n, 8]).  Every frame gets
-        pose_chain with n = 1; a frame whose turn it is and whose source exists is registered against the orthophoto canvas -- which at
-        that moment holds exactly the frames before it -- and its row corrected in place; then its pixels go into the canvas."""
+        """mosaic_refine=True: the window walked frame by frame -> (poses [n, 16], pose_correct's out rows [n, 8], relocate_commit's out
+        rows [n, 8] or None).  Every frame gets pose_chain with n = 1; a frame whose turn it is and whose source exists is registered
+        against the orthophoto canvas -- which at that moment holds exactly the frames before it -- and its row corrected in place; with
+        mosaic_relocate=True the relocation sequence follows; then its pixels go into the canvas."""
         n, h, w = masks.shape
         dev, size, at = masks.device, (h, w), self._mosaic_at
         if self._ortho_planes is None:
@@ -543,6 +579,7 @@ class FlowPredictor:
         poses = torch.empty((n, 16), dtype=torch.int64, device=dev)
         outs = torch.zeros((n, 8), dtype=torch.int64, device=dev)
         outs[:, 0] = 1  # not attempted
+        relocs = outs.clone() if self.mosaic_relocate else None
         for p in range(n):
             ordinal = self._ortho_frames + p
             poses[p:p + 1] = ops.pose_chain(model[p:p + 1], self._mosaic_state, size, self.mosaic, at, self.mosaic_bridge)
@@ -555,9 +592,39 @@ class FlowPredictor:
                 fit = ops.global_motion(table[None], size, size, self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks[p:p + 1],
                                         exclude=self.mosaic_exclude, pair_stats=stats[None])
                 outs[p] = ops.pose_correct(fit, self._mosaic_state, poses[p], size, self.mosaic, at)
+            if self.mosaic_relocate and ordinal % self.relocate_every == 0:
+                relocs[p] = self._relocate(sources[p], masks[p:p + 1], poses[p], ordinal)
             ops.ortho_accumulate(sources[p], poses[p], ordinal, size, rank, rgba, at, self.ortho)
         self._ortho_frames += n
-        return poses, outs
+        return poses, outs, relocs
+
+    def _relocate(self, source, mask, pose, ordinal):
+        """One frame's relocation sequence -> relocate_commit's out row.  The chain's state and `pose` change only in
+        relocate_commit's kernel, and only for a lost chain whose candidate passed the fine registration."""
+        size, at, s = tuple(mask.shape[1:]), self._mosaic_at, self.relocate_scale
+        rank, rgba = self._ortho_planes
+        cl, cv = ops.map_coarse(rgba, s)
+        tl, tv, geom = ops.map_patch(source, self._mosaic_state, size, self.mosaic, at, s)
+        found = ops.map_locate(cl, cv, tl, tv, geom, self.relocate_min_overlap, self.relocate_exclude)
+        cand_state, cand_pose = ops.pose_relocate(found, self._mosaic_state, size, self.mosaic, at, s, self.relocate_max_mean, self.relocate_ratio)
+        cur, view, valid = ops.map_view(source, cand_pose, ordinal, size, rank, rgba, at, self.refine_min_age)
+        table, stats = ops.block_match_modes(cur, view, self.refine_search, self.refine_penalty, self.refine_intra_bias, return_stats=True)
+        ops.map_gate(table, valid)
+        fit = ops.global_motion(table[None], size, size, self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=mask, exclude=self.mosaic_exclude,
+                                pair_stats=stats[None])
+        correct_out = ops.pose_correct(fit, cand_state, cand_pose, size, self.mosaic, at)
+        return ops.relocate_commit(cand_state, cand_pose, correct_out, self._mosaic_state, pose, found, s)
+
+    def relocate_report(self):
+        """mosaic_relocate=True: int64 numpy [frames, 8], relocate_commit's out row of every frame predicted since the start (or
+        clear_report()), in the order of mosaic_report()'s poses: status (0 relocated, 1 not attempted, 2 no placement, 3 rejected by the
+        mean, 4 rejected by uniqueness, 5 the fine registration failed, 6 the patch was refused, 7 out of the pose bounds), the shift in
+        canvas pixels x and y, sad*, n*, sad2, n2, eligible placements.  The ONE read-back."""
+        if not self.mosaic_relocate:
+            raise ValueError("FlowPredictor: relocate_report() needs mosaic_relocate=True")
+        if not self._relocate_outs.chunks:
+            return np.zeros((0, 8), np.int64)
+        return self._relocate_outs.flat().cpu().numpy()
 
     def refine_report(self):
         """mosaic_refine=True: int64 numpy [frames, 8], pose_correct's out row of every frame predicted since the start (or
@@ -1083,6 +1150,21 @@ def write_guide_csv(path, frame_ids, counts):
         fh.write("frame," + ",".join(GUIDE_COUNTS) + "\n")
         for frame, row in zip(frame_ids, counts):
             fh.write(f"{int(frame)}," + ",".join(str(int(v)) for v in row) + "\n")
+
+
+RELOCATE_STATUS = ("relocated", "not_attempted", "no_placement", "rejected_mean", "rejected_uniqueness", "fine_failed", "patch_refused", "out_of_bounds")
+
+
+def write_relocate_csv(path, frame_ids, report):
+    """FlowPredictor.relocate_report()'s int64 [frames, 8] as a CSV, one row per frame: frame id, status, the shift in canvas pixels, the
+    best placement's summed absolute difference and cells, the runner-up's, and the eligible placements."""
+    report = np.asarray(report)
+    if report.ndim != 2 or report.shape[1] != 8 or len(frame_ids) != report.shape[0]:
+        raise ValueError(f"write_relocate_csv: report must be [frames, 8] with one frame id per row, got {report.shape} and {len(frame_ids)} ids")
+    with open(path, "w", newline="") as f:
+        f.write("frame,status,shift_x,shift_y,sad,cells,sad2,cells2,eligible\n")
+        for fid, row in zip(frame_ids, report.tolist()):
+            f.write(",".join([str(int(fid)), RELOCATE_STATUS[row[0]] if 0 <= row[0] < len(RELOCATE_STATUS) else "patch_refused"] + [str(v) for v in row[1:]]) + "\n")
 
 
 def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):

@@ -1221,6 +1221,141 @@ def pose_correct(model, state, pose, mask_size, canvas_size, origin):
     return out
 
 
+# ------------------------------------------------------------------------------------------ relocalisation against the orthophoto
+RELOCATE_SCALES = (4, 8, 16)
+RELOCATE_PATCH_BYTES = 65536  # FS map_patch: tl and tv, of which the first tw * th bytes are written
+
+
+def _relocate_scale(scale, what):
+    if scale not in RELOCATE_SCALES:
+        raise ValueError(f"{what}: scale must be one of {list(RELOCATE_SCALES)}, got {scale!r}")
+    return int(scale)
+
+
+def _relocate_row(t, words, name, what):
+    if t.dtype != torch.int64 or tuple(t.shape) != (words,) or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous int64 [{words}] tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def map_coarse(rgba, scale):
+    """The orthophoto canvas reduced to scale x scale cells (definition: include/floodseg_test.h, map_coarse): rgba uint32
+    (held as int32) [CH,CW] -> (cl, cv) uint8 [CH // scale, CW // scale]: a cell is valid (cv 1) iff every one of its pixels has been
+    seen, and cl is then the rounded mean of their lumas; 0, 0 otherwise.  One launch; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.map_coarse"
+    if rgba.dtype != torch.int32 or rgba.dim() != 2 or not rgba.is_contiguous():
+        raise ValueError(f"{what}: rgba must be a contiguous int32 [CH,CW] tensor (ortho_canvas's), got {rgba.dtype} {tuple(rgba.shape)}")
+    ch, cw = _mosaic_size(rgba.shape, "the canvas", what)
+    s = _relocate_scale(scale, what)
+    if ch // s < 1 or cw // s < 1:
+        raise ValueError(f"{what}: a {ch} x {cw} canvas has no cell of scale {s}")
+    dev = one_device(rgba, what=what)
+    with torch.cuda.device(dev):
+        cl, cv = (torch.empty((ch // s, cw // s), dtype=torch.uint8, device=dev) for _ in range(2))
+        check(lib.fs_map_coarse(ptr(rgba), ch, cw, s, ptr(cl), ptr(cv), stream_ptr()))
+    return cl, cv
+
+
+def map_patch(source, state, mask_size, canvas_size, origin, scale):
+    """A lost frame drawn into canvas cells with the last pose the chain's state holds (definition: include/floodseg_test.h, map_patch).
+    source, mask_size = (H, W), origin = (oy, ox) as ops.map_view takes them; state: pose_chain's int64 [32], only read.  -> (tl, tv,
+    geom): uint8 [65536] each, of which the first tw * th bytes are the patch's lumas and validity as [th, tw], and int64 [8] =
+    (status, pu0, pv0, tw, th, valid cells, 0, 0); status 0 drawn, 1 the chain is not lost, 2 its poses are out of bounds, 3 / 4 the
+    patch has no or too many cells / more cells than the coarse canvas.  Two launches; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.map_patch"
+    frame, planes, fmt, matrix, full_range, fh, fw = _ortho_source(source, what)
+    h, w = _mosaic_size(mask_size, "mask_size", what)
+    ch, cw = _mosaic_size(canvas_size, "canvas_size", what)
+    oy, ox = _mosaic_origin(origin, what)
+    s = _relocate_scale(scale, what)
+    if ch // s < 1 or cw // s < 1:
+        raise ValueError(f"{what}: a {ch} x {cw} canvas has no cell of scale {s}")
+    _relocate_row(state, 32, "state", what)
+    dev = one_device(frame, state, *planes, what=what)
+    with torch.cuda.device(dev):
+        planes = [p.contiguous() for p in planes]
+        tl, tv = (torch.empty((RELOCATE_PATCH_BYTES,), dtype=torch.uint8, device=dev) for _ in range(2))
+        geom = torch.empty((8,), dtype=torch.int64, device=dev)
+        check(lib.fs_map_patch(ptr(frame.contiguous()), ptr(planes[0]) if planes else None, ptr(planes[1]) if len(planes) > 1 else None, _FORMATS[fmt],
+                               _MATRICES[matrix], int(bool(full_range)), fh, fw, ptr(state), h, w, ch, cw, ox, oy, s, ptr(tl), ptr(tv), ptr(geom), stream_ptr()))
+    return tl, tv, geom
+
+
+def map_locate(cl, cv, tl, tv, geom, min_overlap_permille=500, exclude=2):
+    """The patch slid over the whole coarse canvas in whole cells (definition: include/floodseg_test.h, map_locate): cl, cv map_coarse's,
+    tl, tv, geom map_patch's -> found int64 [16] = (status, u*, v*, sad*, n*, runner-up exists, u2, v2, sad2, n2, placements, eligible
+    placements, valid patch cells, 0, 0, 0); status 0 found, 1 no eligible placement, 2 bad geom.  A placement is eligible with at
+    least min_overlap_permille / 1000 of the patch's valid cells on valid canvas cells; the best has the smallest mean absolute
+    difference; the runner-up is the best more than `exclude` cells from it.  Two launches; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.map_locate"
+    if cl.dtype != torch.uint8 or cl.dim() != 2 or not cl.is_contiguous() or cv.dtype != torch.uint8 or tuple(cv.shape) != tuple(cl.shape) or not cv.is_contiguous():
+        raise ValueError(f"{what}: cl and cv must be contiguous uint8 planes of one shape, got {cl.dtype} {tuple(cl.shape)} and {cv.dtype} {tuple(cv.shape)}")
+    ch, cw = (int(v) for v in cl.shape)
+    if not (1 <= ch <= 4096 and 1 <= cw <= 4096):
+        raise ValueError(f"{what}: the coarse canvas must be 1..4096 cells a side, got {(ch, cw)}")
+    for name, t in (("tl", tl), ("tv", tv)):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (RELOCATE_PATCH_BYTES,) or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be map_patch's contiguous uint8 [{RELOCATE_PATCH_BYTES}] tensor, got {t.dtype} {tuple(t.shape)}")
+    _relocate_row(geom, 8, "geom", what)
+    if not 1 <= int(min_overlap_permille) <= 1000:
+        raise ValueError(f"{what}: min_overlap_permille must be 1..1000, got {min_overlap_permille}")
+    if not 0 <= int(exclude) <= 64:
+        raise ValueError(f"{what}: exclude must be 0..64 cells, got {exclude}")
+    dev = one_device(cl, cv, tl, tv, geom, what=what)
+    with torch.cuda.device(dev):
+        scores = torch.empty((ch, cw, 2), dtype=torch.int32, device=dev)
+        found = torch.empty((16,), dtype=torch.int64, device=dev)
+        check(lib.fs_map_locate(ptr(cl), ptr(cv), ch, cw, ptr(tl), ptr(tv), ptr(geom), int(min_overlap_permille), int(exclude), ptr(scores), ptr(found), stream_ptr()))
+    return found
+
+
+def pose_relocate(found, state, mask_size, canvas_size, origin, scale, max_mean=16, ratio_permille=800):
+    """map_locate's placement as a CANDIDATE state and pose row (definition: include/floodseg_test.h, pose_relocate); `state` is only
+    read.  -> (cand_state int64 [32], cand_pose int64 [16]).  Accepted iff found, sad* <= max_mean n*, and no runner-up or
+    1000 sad* n2 <= ratio_permille sad2 n*: the candidate is then the state with both poses translated by (scale u*, scale v*) canvas
+    pixels, tracking, its last pair motion the identity; otherwise the state and a lost row.  cand_state[28] holds the decision
+    (relocate_commit's status codes).  One launch; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.pose_relocate"
+    h, w = _mosaic_size(mask_size, "mask_size", what)
+    ch, cw = _mosaic_size(canvas_size, "canvas_size", what)
+    oy, ox = _mosaic_origin(origin, what)
+    s = _relocate_scale(scale, what)
+    if not 0 <= int(max_mean) <= 255:
+        raise ValueError(f"{what}: max_mean must be 0..255, got {max_mean}")
+    if not 1 <= int(ratio_permille) <= 1000:
+        raise ValueError(f"{what}: ratio_permille must be 1..1000, got {ratio_permille}")
+    _relocate_row(found, 16, "found", what)
+    _relocate_row(state, 32, "state", what)
+    dev = one_device(found, state, what=what)
+    with torch.cuda.device(dev):
+        cand_state = torch.empty((32,), dtype=torch.int64, device=dev)
+        cand_pose = torch.empty((16,), dtype=torch.int64, device=dev)
+        check(lib.fs_pose_relocate(ptr(found), ptr(state), ptr(cand_state), ptr(cand_pose), int(max_mean), int(ratio_permille), h, w, ch, cw, ox, oy, s, stream_ptr()))
+    return cand_state, cand_pose
+
+
+def relocate_commit(cand_state, cand_pose, correct_out, state, pose, found, scale):
+    """The candidate replaces the chain's state and the frame's pose row, IN PLACE, iff pose_relocate accepted the placement and
+    pose_correct then reported 0 on the candidate (definition: include/floodseg_test.h, relocate_commit); otherwise nothing changes.
+    -> out int64 [8] = (status, scale u*, scale v*, sad*, n*, sad2, n2, eligible placements); status 0 relocated, 1 not attempted (the
+    chain is not lost), 2 no placement, 3 rejected by the mean, 4 rejected by uniqueness, 5 the fine registration failed, 6 the patch
+    was refused, 7 out of the pose bounds.  One launch; the decision is taken on the device, nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.relocate_commit"
+    s = _relocate_scale(scale, what)
+    for name, t, words in (("cand_state", cand_state, 32), ("cand_pose", cand_pose, 16), ("correct_out", correct_out, 8), ("state", state, 32), ("pose", pose, 16),
+                           ("found", found, 16)):
+        _relocate_row(t, words, name, what)
+    dev = one_device(cand_state, cand_pose, correct_out, state, pose, found, what=what)
+    with torch.cuda.device(dev):
+        out = torch.empty((8,), dtype=torch.int64, device=dev)
+        check(lib.fs_relocate_commit(ptr(cand_state), ptr(cand_pose), ptr(correct_out), ptr(state), ptr(pose), ptr(found), s, ptr(out), stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

@@ -1166,6 +1166,108 @@ typedef struct fs_hook_tables11 {
     fs_ext11_api ext11;
 } fs_hook_tables11;
 
+/* ---- The THIRTEENTH table.  fs_ext11_api is frozen as well (1 member, 24 bytes; tests/test_relocate_cpu.py), so ops added since live in
+ * a table of their own, append-only, that the library places directly behind fs_hook_tables11 by the same pattern:
+ *     const fs_hook_tables12* t = (const fs_hook_tables12*)fs_test_hooks();   t->ext12.map_locate(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables11: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext12.magic == FS_EXT12_MAGIC and ext12.size >= the end of the member it needs. */
+#define FS_EXT12_MAGIC 0x4653455854413132ull /* "FSEXTA12" */
+
+typedef struct fs_ext12_api {
+    uint64_t magic; /* FS_EXT12_MAGIC */
+    size_t size;    /* sizeof(fs_ext12_api) of the library that was built */
+
+    /* ---- RELOCALISATION AGAINST THE ORTHOPHOTO (csrc/relocate_ops.hip, csrc/relocate_defs.h).  OUR DEFINITION: the
+     * reference has nothing like it.  pose_chain makes a lost chain stay lost; these five ops find where on the map a lost frame lies
+     * by an exhaustive coarse search and let the chain resume ON THE SAME MOSAIC.  For one lost frame (pose_chain has just written a
+     * lost row and the state's phase is 2; words 0..11 of the state still hold the last pose):
+     *   map_coarse -> map_patch -> map_locate -> pose_relocate -> [map_view -> block_match_modes -> map_gate -> global_motion ->
+     *   pose_correct, all on the CANDIDATE state and row] -> relocate_commit.
+     * The same rules as code: csrc/relocate_defs.h (host and device) and tests/relocate_ref.py (numpy).  All integer, bit for bit.
+     * S is the coarse cell edge, 4, 8 or 16; ch = CH / S, cw = CW / S (floor: a remainder strip owns no cell); luma_of is map_view's.
+     *
+     * map_coarse: cl, cv uint8 [ch][cw].  cv = 1 iff all S^2 words of the cell have rgba >> 24 != 0; then cl = (sum of luma_of + S^2 / 2)
+     * / S^2 (the sum is at most 255 * 256); otherwise cl = cv = 0.  ONE launch, a thread per cell.
+     * Refused before a launch: a null pointer; CH or CW outside 1..16384; S not 4, 8 or 16; ch or cw == 0; rgba not aligned to 4. */
+    int (*map_coarse)(const uint32_t* rgba, int CH, int CW, int S, uint8_t* cl, uint8_t* cv, fs_stream stream);
+
+    /* ---- map_patch draws the lost frame into canvas cells with the last pose the state holds.  The frame arguments, H, W, CH, CW, ox, oy
+     * as map_view's; state: pose_chain's 32 words, only read.  tl, tv: 65536 bytes each, of which the first tw th are written, as
+     * [th][tw]; geom int64 [8] = (status, pu0, pv0, tw, th, nt, 0, 0), written by EVERY call (a failing one: the status, then zeros).
+     * In this order, everything read from the state tested before any product:
+     *   status 1: state[24] != 2 (the chain is not lost).        status 2: the state's poses fail pose_chain's pose bounds.
+     *   The four corners (x, y) in {0, W} x {0, H} under t = to_anchor, frame_clipped's rule: cx = t00 x + t01 y + t02 + ox ONE (|t| <
+     *   2^24, x <= 2^14: below 2^40), cy alike.  The patch covers canvas pixels [min cx >> 20, (max cx + ONE - 1) >> 20), widened
+     *   outwards to whole cells: pu0 = that lower pixel >> log2 S (arithmetic), pu1 = (the upper + S - 1) >> log2 S, tw = pu1 - pu0 (0 for a range without a pixel); v alike.
+     *   status 3: tw < 1, th < 1 or tw th > 65536.               status 4: tw > cw or th > ch.
+     *   status 0: patch cell (i, j) is canvas cell (pu0 + i, pv0 + j) -- it may lie outside the canvas.  It is valid (tv = 1) iff every
+     *   one of its S^2 canvas pixels (X, Y) has source_pixel(from_anchor, anchor_coord(X, ox), anchor_coord(Y, oy)) inside [0, W) x
+     *   [0, H); tl is then the rounded mean, as map_coarse's, of luma(I[y][x]), I and luma as map_view's cur; otherwise tl = tv = 0.
+     *   Once tw S <= CW <= 2^14, |X - ox| < 2^15 + 32, so source_pixel's products stay below 2^61.  nt = the number of valid cells.
+     * TWO launches: a wave per cell (the grid covers min(65536, ch cw) cells; a wave past tw th returns), then one workgroup that
+     * counts nt and writes geom.
+     * Refused before a launch: a null frame, state, tl, tv or geom, or a null chroma pointer of a YUV format; format, matrix or range
+     * code out of range; FH, FW, H, W, CH or CW outside 1..16384; |ox| or |oy| > 16384; S not 4, 8 or 16; ch or cw == 0; state or geom
+     * not aligned to 8 bytes. */
+    int (*map_patch)(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const int64_t* state, int H,
+                     int W, int CH, int CW, int ox, int oy, int S, uint8_t* tl, uint8_t* tv, int64_t* geom, fs_stream stream);
+
+    /* ---- map_locate slides the patch over the whole coarse canvas.  cl, cv: map_coarse's, ch x cw CELLS; tl, tv, geom: map_patch's;
+     * scores: the caller's workspace, uint32 [ch][cw][2]; found int64 [16] = (status, u*, v*, sad*, n*, runner-up exists, u2, v2, sad2,
+     * n2, placements, eligible placements, nt, 0, 0, 0), written by every call.
+     *   status 2 (bad geom, everything else 0): geom[0] != 0, tw or th outside 1..cw / 1..ch, tw th > 65536, nt outside 0..tw th, or
+     *   |pu0| or |pv0| >= 2^20 -- tested before any product or index.
+     *   Placements: every shift (u, v) in cells with 0 <= pu0 + u <= cw - tw and 0 <= pv0 + v <= ch - th.  Over the cells where
+     *   cv[pv0 + v + j][pu0 + u + i] == 1 and tv[j][i] == 1: n = their number, sad = the sum of |cl - tl|.
+     *   Eligible: n >= 1 and 1000 n >= min_overlap_permille nt.
+     *   Order: the smaller mean, compared as sad_a n_b < sad_b n_a in 64 bits (sad < 2^24, n <= 2^16: below 2^40); then the larger n,
+     *   the smaller v, the smaller u.  Best: the first eligible placement in that order; status 1 (no eligible placement) if none.
+     *   Runner-up: the first eligible placement with max(|u - u*|, |v - v*|) > exclude.
+     * A shift by (u, v) cells is the state's pose translated by (S u, S v) canvas pixels.
+     * TWO launches: the score plane (a workgroup per 64 x 4 placements; patch and canvas strip through LDS as bytes, four cells per
+     * v_sad_u8 on dwords ANDed with the joint validity, n from the same mask; no atomics), then one workgroup that folds the plane.
+     * Refused before a launch: a null pointer; ch or cw outside 1..4096; min_overlap_permille outside 1..1000; exclude outside 0..64;
+     * geom, found or scores not aligned to 8 bytes. */
+    int (*map_locate)(const uint8_t* cl, const uint8_t* cv, int ch, int cw, const uint8_t* tl, const uint8_t* tv, const int64_t* geom, int min_overlap_permille,
+                      int exclude, uint32_t* scores, int64_t* found, fs_stream stream);
+
+    /* ---- pose_relocate turns the placement into a CANDIDATE state (32 words) and pose row (16 words); `state` is only read.  The
+     * decision, in this order, lands in cand_state[28] (a spare word of the candidate only):
+     *   1 state[24] != 2: the chain is not lost, there is nothing to do (a caller need not know beforehand whether it is);
+     *   2 found[0] == 1 (no eligible placement);
+     *   6 found[0] != 0, the state's poses out of the pose bounds, n* outside 1..65536, sad* outside 0..255 n*, |u*| or
+     *     |v*| > 16384, or a flagged runner-up with such counts -- all tested before any product;
+     *   3 sad* > max_mean n*;
+     *   4 a runner-up exists and 1000 sad* n2 > ratio_permille sad2 n* (below 2^50);
+     *   7 the translated poses fail the pose bounds;      0 accepted.
+     * The translation by (dx, dy) = (S u*, S v*) whole canvas pixels is exact: to[2] += dx ONE, to[5] += dy ONE, from[2] -= from[0] dx +
+     * from[1] dy, from[5] -= from[3] dx + from[4] dy (2^24 x 2^18 = 2^42).
+     * Accepted: the candidate state is the state with both poses translated, last_fwd = last_inv = identity (a bridge after relocation
+     * never replays the motion from before the break), phase 1, bridge run 0; the row is (to, from, 0, frame_clipped, 0, 0).
+     * Otherwise: the candidate state is the state, the row (identity, identity, 2, 0, 0, 0) -- map_view then sees nothing and
+     * pose_correct reports 4.  ONE launch of one wave.
+     * Refused before a launch: a null pointer; max_mean outside 0..255; ratio_permille outside 1..1000; H, W, CH or CW outside
+     * 1..16384; |ox| or |oy| > 16384; S not 4, 8 or 16; a pointer not aligned to 8 bytes; cand_state == state. */
+    int (*pose_relocate)(const int64_t* found, const int64_t* state, int64_t* cand_state, int64_t* cand_pose, int max_mean, int ratio_permille, int H, int W,
+                         int CH, int CW, int ox, int oy, int S, fs_stream stream);
+
+    /* ---- relocate_commit.  correct_out: pose_correct's row for the candidate.  out int64 [8] = (status, S u*, S v*, sad*, n*, sad2, n2,
+     * eligible placements); the numbers are found's (0 where found has none).  status: cand_state[28] if it is 1, 2, 3, 4, 6 or 7 (any
+     * other value but 0: 6); else 5 (fine registration failed) unless correct_out[0] == 0, the candidate's phase is 1, its row's status
+     * 0 and its poses inside the pose bounds; else 0: words 0..27 of the candidate state replace the state's and words 0..13 of the
+     * candidate row the row's (the state's spare words and the row's pair counts stay).  With any other status NOTHING is written but
+     * out: the chain stays lost exactly as it was, and a coarse-only pose never votes.  1 (not attempted) is also the caller's row for a
+     * frame it did not try.  ONE launch of one wave; the decision is taken on the device.
+     * Refused before a launch: a null pointer; S not 4, 8 or 16; a pointer not aligned to 8 bytes. */
+    int (*relocate_commit)(const int64_t* cand_state, const int64_t* cand_pose, const int64_t* correct_out, int64_t* state, int64_t* pose, const int64_t* found,
+                           int S, int64_t* out, fs_stream stream);
+} fs_ext12_api;
+
+typedef struct fs_hook_tables12 {
+    fs_hook_tables11 base11;
+    fs_ext12_api ext12;
+} fs_hook_tables12;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus
