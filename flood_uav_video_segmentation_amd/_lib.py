@@ -235,6 +235,17 @@ _EXT12_HOOKS = [
 ]
 EXT12_MAGIC = 0x4653455854413132  # FS_EXT12_MAGIC
 
+# members of fs_ext13_api, the fourteenth table (append-only, behind the thirteen frozen ones), in declaration order after `magic` and `size`
+_EXT13_HOOKS = [
+    ("merge_view", c_int, [c_void] + [c_int] * 4 + [c_void] + [c_int] * 4 + [c_void] + [c_int] * 4 + [c_void] * 5),
+    ("merge_gate", c_int, [c_void] + [c_int] + [c_void] * 2 + [c_int] * 2 + [c_void]),
+    ("link_correct", c_int, [c_void] * 2 + [c_int] * 6 + [c_void] * 2),
+    ("mosaic_merge", c_int, [c_void] + [c_int] * 4 + [c_void] + [c_int] * 5 + [c_void] * 5 + [ctypes.c_uint32] + [c_int] + [c_void] * 2),
+    ("merge_patch", c_int, [c_void] + [c_int] * 4 + [c_void] + [c_int] * 9 + [c_void] * 4),
+    ("link_place", c_int, [c_void] * 2 + [c_int] * 3 + [c_void] * 3),
+]
+EXT13_MAGIC = 0x4653455854413133  # FS_EXT13_MAGIC
+
 
 def _struct(name, *fields):
     return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
@@ -272,6 +283,8 @@ FsExt11Api = _struct("FsExt11Api", *_EXT_HEAD, *_members(_EXT11_HOOKS))
 FsHookTables11 = _struct("FsHookTables11", ("base10", FsHookTables10), ("ext11", FsExt11Api))
 FsExt12Api = _struct("FsExt12Api", *_EXT_HEAD, *_members(_EXT12_HOOKS))
 FsHookTables12 = _struct("FsHookTables12", ("base11", FsHookTables11), ("ext12", FsExt12Api))
+FsExt13Api = _struct("FsExt13Api", *_EXT_HEAD, *_members(_EXT13_HOOKS))
+FsHookTables13 = _struct("FsHookTables13", ("base12", FsHookTables12), ("ext13", FsExt13Api))
 
 # One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
 # the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
@@ -292,6 +305,7 @@ _TABLES = [
     _Table("ten", "tenth", _EXT10_HOOKS, "EXT10_MAGIC", FsExt10Api, FsHookTables10, "ext10"),
     _Table("eleven", "eleventh", _EXT11_HOOKS, "EXT11_MAGIC", FsExt11Api, FsHookTables11, "ext11"),
     _Table("twelve", "twelfth", _EXT12_HOOKS, "EXT12_MAGIC", FsExt12Api, FsHookTables12, "ext12"),
+    _Table("thirteen", "thirteenth", _EXT13_HOOKS, "EXT13_MAGIC", FsExt13Api, FsHookTables13, "ext13"),
 ]
 _TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
@@ -372,7 +386,7 @@ def _hook_names(n):
 
 
 (hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
- ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names, ext12_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
+ ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names, ext12_hook_names, ext13_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

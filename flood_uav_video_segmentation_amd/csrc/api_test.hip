@@ -623,7 +623,37 @@ static int fs_relocate_commit(const int64_t* cand_state, const int64_t* cand_pos
                                       reinterpret_cast<const long long*>(found), scale, reinterpret_cast<long long*>(out), S(stream));
 }
 
-// the thirteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// map-to-map registration and the merge of two mosaics (merge_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_merge_view(const uint32_t* rgba_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b,
+                         const int64_t* link, int Y0, int X0, int WH, int WW, uint8_t* cur, uint8_t* view, uint8_t* valid_a, uint8_t* valid_b, fs_stream stream) {
+    return fs::launch_merge_view(rgba_a, CH_a, CW_a, ox_a, oy_a, rgba_b, CH_b, CW_b, ox_b, oy_b, reinterpret_cast<const long long*>(link), Y0, X0, WH, WW, cur, view,
+                                 valid_a, valid_b, S(stream));
+}
+static int fs_merge_gate(int32_t* table, int blocks, const uint8_t* valid_a, const uint8_t* valid_b, int H, int W, fs_stream stream) {
+    return fs::launch_merge_gate(table, blocks, valid_a, valid_b, H, W, S(stream));
+}
+static int fs_link_correct(const int64_t* model, int64_t* link, int Y0, int X0, int WH, int WW, int ox_a, int oy_a, int64_t* out, fs_stream stream) {
+    return fs::launch_link_correct(reinterpret_cast<const long long*>(model), reinterpret_cast<long long*>(link), Y0, X0, WH, WW, ox_a, oy_a,
+                                   reinterpret_cast<long long*>(out), S(stream));
+}
+static int fs_mosaic_merge(uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint16_t* votes_b, int CH_b, int CW_b, int ox_b, int oy_b, int K,
+                           const int64_t* link, uint64_t* rank_a, uint32_t* rgba_a, const uint64_t* rank_b, const uint32_t* rgba_b, uint32_t ordinal_offset, int mode,
+                           int64_t* counts, fs_stream stream) {
+    return fs::launch_mosaic_merge(votes_a, CH_a, CW_a, ox_a, oy_a, votes_b, CH_b, CW_b, ox_b, oy_b, K, reinterpret_cast<const long long*>(link),
+                                   reinterpret_cast<unsigned long long*>(rank_a), rgba_a, reinterpret_cast<const unsigned long long*>(rank_b), rgba_b,
+                                   ordinal_offset, mode, reinterpret_cast<long long*>(counts), S(stream));
+}
+static int fs_merge_patch(const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b, const int64_t* link, int CH_a, int CW_a, int ox_a, int oy_a, int scale,
+                          int y0, int x0, int y1, int x1, uint8_t* tl, uint8_t* tv, int64_t* geom, fs_stream stream) {
+    return fs::launch_merge_patch(rgba_b, CH_b, CW_b, ox_b, oy_b, reinterpret_cast<const long long*>(link), CH_a, CW_a, ox_a, oy_a, scale, y0, x0, y1, x1, tl, tv,
+                                  reinterpret_cast<long long*>(geom), S(stream));
+}
+static int fs_link_place(const int64_t* found, const int64_t* link, int scale, int max_mean, int ratio_permille, int64_t* cand, int64_t* out, fs_stream stream) {
+    return fs::launch_link_place(reinterpret_cast<const long long*>(found), reinterpret_cast<const long long*>(link), scale, max_mean, ratio_permille,
+                                 reinterpret_cast<long long*>(cand), reinterpret_cast<long long*>(out), S(stream));
+}
+
+// the fourteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -764,7 +794,19 @@ static const fs_hook_tables5& hook_tables(void) {
         fs_pose_relocate,
         fs_relocate_commit,
     }};
+    // fs_ext12_api is frozen too (five members, 56 bytes; tests/test_merge_cpu.py); the fourteenth table lies behind it, and &all13.base12 is &all13.
+    static const fs_hook_tables13 all13 = {all12, {
+        FS_EXT13_MAGIC,
+        sizeof(fs_ext13_api),
+        fs_merge_view,
+        fs_merge_gate,
+        fs_link_correct,
+        fs_mosaic_merge,
+        fs_merge_patch,
+        fs_link_place,
+    }};
     {
+        const fs_hook_tables12& all12 = all13.base12;
         const fs_hook_tables11& all11 = all12.base11;
         const fs_hook_tables10& all10 = all11.base10;
         const fs_hook_tables9& all9 = all10.base9;

@@ -446,6 +446,22 @@ int launch_pose_relocate(const long long* found, const long long* state, long lo
 int launch_relocate_commit(const long long* cand_state, const long long* cand_pose, const long long* correct_out, long long* state, long long* pose,
                            const long long* found, int S, long long* out, hipStream_t s);
 
+// Map-to-map registration and the merge of two mosaics (merge_ops.hip, merge_defs.h; definitions: include/floodseg_test.h, merge_view,
+// merge_gate, link_correct, mosaic_merge, merge_patch and link_place).  The launchers refuse bad arguments before they launch anything.  link = int64 [16];
+// cur, view, valid_a, valid_b = uint8 [WH][WW]; out, counts = int64 [8]; rank and rgba of mosaic_merge all four or all null.  Nothing is
+// allocated, synchronised or read on the host.
+int launch_merge_view(const uint32_t* rgba_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b,
+                      const long long* link, int Y0, int X0, int WH, int WW, uint8_t* cur, uint8_t* view, uint8_t* valid_a, uint8_t* valid_b, hipStream_t s);
+int launch_merge_gate(int32_t* table, int blocks, const uint8_t* valid_a, const uint8_t* valid_b, int H, int W, hipStream_t s);
+int launch_link_correct(const long long* model, long long* link, int Y0, int X0, int WH, int WW, int ox_a, int oy_a, long long* out, hipStream_t s);
+int launch_mosaic_merge(uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint16_t* votes_b, int CH_b, int CW_b, int ox_b, int oy_b, int K,
+                        const long long* link, unsigned long long* rank_a, uint32_t* rgba_a, const unsigned long long* rank_b, const uint32_t* rgba_b,
+                        uint32_t ordinal_offset, int mode, long long* counts, hipStream_t s);
+// tl, tv, geom as launch_map_patch writes them and launch_map_locate reads them; found = map_locate's; cand = int64 [16]
+int launch_merge_patch(const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b, const long long* link, int CH_a, int CW_a, int ox_a, int oy_a, int S, int y0,
+                       int x0, int y1, int x1, uint8_t* tl, uint8_t* tv, long long* geom, hipStream_t s);
+int launch_link_place(const long long* found, const long long* link, int S, int max_mean, int ratio_permille, long long* cand, long long* out, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

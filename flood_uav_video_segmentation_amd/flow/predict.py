@@ -420,6 +420,9 @@ class FlowPredictor:
         self.relocate_min_overlap, self.relocate_ratio = int(round(1000 * float(relocate_min_overlap))), int(round(1000 * float(relocate_ratio)))  # permille
         self.relocate_max_mean = int(relocate_max_mean)
         self._relocate_outs = FrameRows(((8,), torch.int64))  # relocate_commit's out rows, kept in step with _mosaic_poses
+        self._mosaic_mask = None   # (H, W) of the masks the mosaic was anchored with
+        self._mosaic_tail = None   # int64 [12] on the device once a part has been merged: the last merged frame's two poses
+        self._merges = []          # per merged part (link, register_mosaics' out rows, mosaic_merge's counts), on the device
 
     # the chunk lists that tests count, under the names they had before the tables moved into FrameRows
     _report_chunks = property(lambda self: self._extent.chunks)
@@ -445,6 +448,8 @@ class FlowPredictor:
         self._despeckle_counts = []
         self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
         self._ortho_planes, self._ortho_frames = None, 0
+        self._mosaic_mask = self._mosaic_tail = None
+        self._merges = []
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -541,6 +546,7 @@ class FlowPredictor:
             self._mosaic_votes = torch.zeros((self.mosaic_classes, ch, cw), dtype=torch.int16, device=dev).view(torch.uint16)  # the same zero bits
             self._mosaic_state = torch.zeros((32,), dtype=torch.int64, device=dev)
             self._mosaic_at = self.mosaic_origin if self.mosaic_origin is not None else ((ch - h) // 2, (cw - w) // 2)
+            self._mosaic_mask = (h, w)
         model = ops.global_motion(link[0] if link[3] is None else link[3], link[1], (h, w), self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks,
                                   exclude=self.mosaic_exclude, pair_stats=link[2])
         if self.mosaic_refine:
@@ -614,6 +620,50 @@ class FlowPredictor:
                                 pair_stats=stats[None])
         correct_out = ops.pose_correct(fit, cand_state, cand_pose, size, self.mosaic, at)
         return ops.relocate_commit(cand_state, cand_pose, correct_out, self._mosaic_state, pose, found, s)
+
+    # ---- merging another predictor's mosaic into this one
+    def mosaic_part(self):
+        """mosaic=: this predictor's mosaic as a dict of DEVICE tensors and plain numbers, nothing read back: votes uint16 [K, CH, CW]; rank,
+        rgba (ortho=; None without); state int64 [32]; poses int64 [frames, 16]; tail int64 [12], the two poses (to_anchor, from_anchor)
+        after the last frame -- or after the last merged part's; origin (oy, ox); mask_size (H, W); frames, the next ordinal; mode.  The
+        tensors are the predictor's own, not copies.  write_mosaic_part() saves it, another predictor's merge_mosaic() takes it."""
+        if self._mosaic_votes is None:
+            raise ValueError("FlowPredictor: mosaic_part() needs mosaic=(CH, CW) and at least one predicted window")
+        rank, rgba = self._ortho_planes if self._ortho_planes is not None else (None, None)
+        tail = self._mosaic_tail if self._mosaic_tail is not None else self._mosaic_state[:12].clone()
+        return dict(votes=self._mosaic_votes, rank=rank, rgba=rgba, state=self._mosaic_state, poses=self._mosaic_poses.flat(), tail=tail,
+                    origin=tuple(self._mosaic_at), mask_size=tuple(self._mosaic_mask), frames=max(self._ortho_frames, self._mosaic_poses.frames), mode=self.ortho)
+
+    def merge_mosaic(self, part, link=None, **register):
+        """Register another mosaic (mosaic_part()'s dict, or read_mosaic_part()'s) against this predictor's and fold it in: ops.register_mosaics
+        on the two orthophotos (so both need ortho=), then ops.mosaic_merge with this predictor's frame count as the ordinal offset.
+        link: int64 [16] on the device; default: this mosaic's tail with status 1 -- the multi-rank case, in which the part's anchor
+        frame is the frame after this one's last.  **register goes to ops.register_mosaics; a place= without b_box takes the part's
+        seen box where it has one.  Afterwards the ordinal counter has grown by the part's frames and, if the link was registered
+        (decided on the device), the tail is compose(b_to_a, the part's tail).  Nothing is read back; merge_report() does that.
+        Votes are not idempotent: merging the same part twice counts its frames twice."""
+        if self._mosaic_votes is None or self._ortho_planes is None or part.get("rgba") is None:
+            raise ValueError("FlowPredictor: merge_mosaic() needs mosaic= and ortho= on both sides and at least one predicted window: the registration reads both orthophotos")
+        mine = self.mosaic_part()
+        if mine["frames"] + int(part["frames"]) > self.ORTHO_MAX_FRAMES:  # before anything is enqueued: a refused merge changes nothing
+            raise ValueError(f"FlowPredictor: an orthophoto takes at most {self.ORTHO_MAX_FRAMES} frames, got {mine['frames']} + {int(part['frames'])} with the part")
+        link, outs, counts = merge_part(mine, part, link, **register)
+        self._ortho_frames, self._mosaic_tail = mine["frames"], mine["tail"]
+        self._merges.append((link, outs, counts))
+        return link
+
+    def merge_report(self):
+        """(links int64 numpy [parts, 16], outs: per part int64 [rows, 8] -- link_place's row first where a placement ran, then one
+        link_correct row per round --, counts int64 [parts, 8]) of the parts merged since the start (or clear_report()).  The ONE read-back."""
+        if not self._merges:
+            return np.zeros((0, 16), np.int64), [], np.zeros((0, 8), np.int64)
+        flat = torch.cat([t.reshape(-1) for m in self._merges for t in m]).cpu().numpy()
+        links, outs, counts, at = [], [], [], 0
+        for _, o, _ in self._merges:
+            rows = int(o.shape[0])
+            links.append(flat[at:at + 16]), outs.append(flat[at + 16:at + 16 + 8 * rows].reshape(rows, 8)), counts.append(flat[at + 16 + 8 * rows:at + 24 + 8 * rows])
+            at += 24 + 8 * rows
+        return np.stack(links), outs, np.stack(counts)
 
     def relocate_report(self):
         """mosaic_relocate=True: int64 numpy [frames, 8], relocate_commit's out row of every frame predicted since the start (or
@@ -1165,6 +1215,103 @@ def write_relocate_csv(path, frame_ids, report):
         f.write("frame,status,shift_x,shift_y,sad,cells,sad2,cells2,eligible\n")
         for fid, row in zip(frame_ids, report.tolist()):
             f.write(",".join([str(int(fid)), RELOCATE_STATUS[row[0]] if 0 <= row[0] < len(RELOCATE_STATUS) else "patch_refused"] + [str(v) for v in row[1:]]) + "\n")
+
+
+def _compose_q20(a, b):
+    """mosaic_defs.h's compose (b first) on int64 device tensors [6]: the merged tail, without a read-back."""
+    half = 1 << 19
+    lin = [((a[3 * r] * b[c] + a[3 * r + 1] * b[3 + c] + half) >> 20) + (a[3 * r + 2] if c == 2 else 0) for r in range(2) for c in range(3)]
+    return torch.stack(lin)
+
+
+def merge_part(mine, part, link=None, **register):
+    """Register the mosaic `part` against the mosaic `mine` (mosaic_part()'s or read_mosaic_part()'s dicts, both with an orthophoto, on
+    one device) and fold it in: ops.register_mosaics, then ops.mosaic_merge with mine's frame count as the ordinal offset.  mine's votes,
+    rank and rgba are updated in place, mine["frames"] grows by the part's and mine["tail"] becomes compose(b_to_a, part's tail) where
+    the link registered (decided on the device).  link: default mine's tail with status 1.  -> (link, outs, counts), device tensors."""
+    dev = mine["votes"].device
+    if (mine.get("mode") or None) != (part.get("mode") or None) or mine.get("mode") not in ops.ORTHO_MODES:
+        raise ValueError(f"merge_part: both mosaics need an orthophoto of ONE mode (a rank word's key means the distance from the optical axis in 'centre' "
+                         f"and the ordinal in 'latest'), got {mine.get('mode')!r} and {part.get('mode')!r}")
+    if tuple(int(v) for v in mine["mask_size"]) != tuple(int(v) for v in part["mask_size"]):
+        raise ValueError(f"merge_part: both mosaics must be of masks of one size (a canvas pixel is a mask pixel of the anchor frame), got "
+                         f"{tuple(mine['mask_size'])} and {tuple(part['mask_size'])}")
+    if link is None:
+        link = torch.cat([mine["tail"], torch.tensor([ops.LINK_INITIAL, 0, 0, 0], dtype=torch.int64, device=dev)])
+    if register.get("place") is not None and "b_box" not in register["place"] and part.get("box") is not None:
+        register["place"] = dict(register["place"], b_box=tuple(int(v) for v in part["box"]))
+    at, other = tuple(int(v) for v in mine["origin"]), tuple(int(v) for v in part["origin"])
+    link, outs = ops.register_mosaics((mine["rgba"], at), (part["rgba"], other), link, **register)
+    counts = ops.mosaic_merge(mine["votes"], at, part["votes"], other, link, (mine["rank"], mine["rgba"]), (part["rank"], part["rgba"]), int(mine["frames"]),
+                              mine["mode"])
+    moved = torch.cat([_compose_q20(link[0:6], part["tail"][0:6]), _compose_q20(part["tail"][6:12], link[6:12])])
+    mine["tail"] = torch.where(link[12] == ops.LINK_REGISTERED, moved, mine["tail"])
+    mine["frames"] = int(mine["frames"]) + int(part["frames"])
+    return link, outs, counts
+
+
+PART_ARRAYS = ("votes", "rank", "rgba", "state", "poses", "tail")
+LINK_STATUS = ("registered", "initial", "no_fit", "out_of_bounds")
+
+
+def part_seen_box(poses, mask_size, canvas_size, origin):
+    """(y0, x0, y1, x1): the canvas box that holds every frame that voted, from the pose rows on the host (frame_clipped's corners, clipped
+    to the canvas); the whole canvas if none did."""
+    (h, w), (ch, cw), (oy, ox) = mask_size, canvas_size, origin
+    xs, ys = [], []
+    for row in np.asarray(poses).tolist():
+        if row[12] not in (0, 1):
+            continue
+        for x, y in ((0, 0), (w, 0), (0, h), (w, h)):
+            xs.append(row[0] * x + row[1] * y + row[2] + ox * (1 << 20)), ys.append(row[3] * x + row[4] * y + row[5] + oy * (1 << 20))
+    if not xs:
+        return 0, 0, ch, cw
+    y0, x0 = max(0, min(ys) >> 20), max(0, min(xs) >> 20)
+    y1, x1 = min(ch, (max(ys) + (1 << 20) - 1) >> 20), min(cw, (max(xs) + (1 << 20) - 1) >> 20)
+    return (y0, x0, y1, x1) if y0 < y1 and x0 < x1 else (0, 0, ch, cw)
+
+
+def mosaic_part_arrays(part):
+    """FlowPredictor.mosaic_part()'s dict as the numpy arrays of a part file (the read-back of a part happens here), with the seen box."""
+    arrays = {k: part[k].cpu().numpy() if torch.is_tensor(part[k]) else np.asarray(part[k]) for k in PART_ARRAYS if part.get(k) is not None}
+    if arrays["votes"].dtype != np.uint16 or arrays["votes"].ndim != 3:
+        raise ValueError(f"write_mosaic_part: votes must be uint16 [K, CH, CW], got {arrays['votes'].dtype} {arrays['votes'].shape}")
+    arrays["origin"], arrays["mask_size"] = np.array(part["origin"], np.int64), np.array(part["mask_size"], np.int64)
+    arrays["frames"], arrays["mode"] = np.array(int(part["frames"]), np.int64), np.array(part.get("mode") or "")
+    arrays["box"] = np.array(part_seen_box(arrays["poses"], part["mask_size"], arrays["votes"].shape[1:], part["origin"]), np.int64)
+    return arrays
+
+
+def write_mosaic_part(path, part):
+    """A mosaic as ONE .npz: mosaic_part()'s arrays, the pose rows, and the seen bounding box taken from the pose rows here on the host."""
+    with open(path, "wb") as f:   # a file object: numpy then appends no suffix of its own
+        np.savez_compressed(f, **mosaic_part_arrays(part))
+
+
+def read_mosaic_part(path, device):
+    """write_mosaic_part()'s file as the dict FlowPredictor.merge_mosaic() takes, its arrays on `device`."""
+    with np.load(path) as z:
+        missing = [k for k in ("votes", "state", "poses", "tail", "origin", "mask_size", "frames", "mode", "box") if k not in z.files]
+        if missing:
+            raise ValueError(f"read_mosaic_part: {path} is no mosaic part: it lacks {missing}")
+        part = {k: torch.from_numpy(z[k]).to(device) for k in PART_ARRAYS if k in z.files}
+        part.update(rank=part.get("rank"), rgba=part.get("rgba"), origin=tuple(int(v) for v in z["origin"]), mask_size=tuple(int(v) for v in z["mask_size"]),
+                    frames=int(z["frames"]), mode=str(z["mode"]) or None, box=tuple(int(v) for v in z["box"]))
+    return part
+
+
+def write_merge_csv(path, names, report):
+    """FlowPredictor.merge_report() as a CSV, one row per merged part: its name, the link's status, b_to_a m00 .. m12, the inliers and
+    usable rows of the fit that registered it, the status of every register row, and mosaic_merge's counts."""
+    links, outs, counts = report
+    if len(names) != len(links) or len(outs) != len(links) or len(counts) != len(links):
+        raise ValueError(f"write_merge_csv: one name per merged part, got {len(names)} names for {len(links)} links, {len(outs)} out tables and {len(counts)} count rows")
+    with open(path, "w", newline="") as f:
+        f.write("part,link,m00,m01,m02,m10,m11,m12,inliers,usable,register,reached,voted,votes,taken\n")
+        for name, link, out, count in zip(names, np.asarray(links).tolist(), outs, np.asarray(counts).tolist()):
+            status = LINK_STATUS[link[12]] if 0 <= link[12] < len(LINK_STATUS) else "out_of_bounds"
+            f.write(",".join([str(name), status] + [f"{v / (1 << 20):.6f}" for v in link[:6]] + [str(link[13]), str(link[14]), "/".join(str(int(r[0])) for r in out)]
+                             + [str(v) for v in count[1:5]]) + "\n")
 
 
 def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):

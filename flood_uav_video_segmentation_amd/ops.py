@@ -1356,6 +1356,239 @@ def relocate_commit(cand_state, cand_pose, correct_out, state, pose, found, scal
     return out
 
 
+# ------------------------------------------------------------------------------------------ map-to-map registration, the merge of two mosaics
+LINK_REGISTERED, LINK_INITIAL, LINK_NO_FIT, LINK_OUT_OF_BOUNDS = 0, 1, 2, 3  # word 12 of a link
+
+
+def mosaic_link(b_to_a=None, a_to_b=None, status=LINK_INITIAL, device=None):
+    """A link row, int64 [16], on `device`: b_to_a and a_to_b as six Q20 integers each (default: the identity), the status (default 1:
+    a guess that ops.register_mosaics has yet to confirm), zeros."""
+    ident = [POSE_ONE, 0, 0, 0, POSE_ONE, 0]
+    fwd, back = (ident if m is None else [int(v) for v in m] for m in (b_to_a, a_to_b))
+    if len(fwd) != 6 or len(back) != 6:
+        raise ValueError(f"floodseg.mosaic_link: b_to_a and a_to_b must hold six Q20 integers each, got {len(fwd)} and {len(back)}")
+    if int(status) not in (LINK_REGISTERED, LINK_INITIAL, LINK_NO_FIT, LINK_OUT_OF_BOUNDS):
+        raise ValueError(f"floodseg.mosaic_link: status must be 0..3, got {status!r}")
+    return torch.tensor(fwd + back + [int(status), 0, 0, 0], dtype=torch.int64, device=device)
+
+
+def _merge_window(window, canvas, what):
+    ch, cw = canvas
+    if window is None:
+        window = (0, 0, ch // 16 * 16, cw // 16 * 16)
+    if len(window) != 4:
+        raise ValueError(f"{what}: window must be (Y0, X0, WH, WW), got {tuple(window)}")
+    y0, x0, wh, ww = (int(v) for v in window)
+    if wh < 16 or ww < 16 or wh % 16 or ww % 16 or y0 < 0 or x0 < 0 or y0 + wh > ch or x0 + ww > cw:
+        raise ValueError(f"{what}: window must be (Y0, X0, WH, WW) of whole blocks of 16 (at least one) inside the {ch} x {cw} canvas, got {(y0, x0, wh, ww)}")
+    return y0, x0, wh, ww
+
+
+def _same_memory(a, b):
+    return a.data_ptr() == b.data_ptr()
+
+
+def merge_view(rgba_a, origin_a, rgba_b, origin_b, link, window=None):
+    """Two orthophoto canvases as the block matcher should see them (definition: include/floodseg_test.h, merge_view).
+    rgba_a, rgba_b: int32 [CH,CW] of ortho_canvas, only read; origin_* = (oy, ox); link int64 [16] (ops.mosaic_link); window = (Y0, X0,
+    WH, WW) of A's canvas in whole blocks of 16, default the whole canvas cut down to multiples of 16.  -> (cur, view, valid_a, valid_b)
+    uint8 [WH,WW]: A's luma and where A has been seen; the luma of the B pixel under each A pixel and 1 where that pixel exists and
+    has been seen (0 elsewhere, and everywhere for a link that is neither registered nor initial or is out of bounds).  One launch;
+    nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.merge_view"
+    ch_a, cw_a = _ortho_planes(None, rgba_a, what)
+    ch_b, cw_b = _ortho_planes(None, rgba_b, what)
+    oy_a, ox_a = _mosaic_origin(origin_a, what)
+    oy_b, ox_b = _mosaic_origin(origin_b, what)
+    _relocate_row(link, 16, "link", what)
+    y0, x0, wh, ww = _merge_window(window, (ch_a, cw_a), what)
+    if _same_memory(rgba_a, rgba_b):
+        raise ValueError(f"{what}: A and B are the same memory (rgba at {rgba_a.data_ptr():#x})")
+    dev = one_device(rgba_a, rgba_b, link, what=what)
+    with torch.cuda.device(dev):
+        cur, view, valid_a, valid_b = (torch.empty((wh, ww), dtype=torch.uint8, device=dev) for _ in range(4))
+        check(lib.fs_merge_view(ptr(rgba_a), ch_a, cw_a, ox_a, oy_a, ptr(rgba_b), ch_b, cw_b, ox_b, oy_b, ptr(link), y0, x0, wh, ww, ptr(cur), ptr(view),
+                                ptr(valid_a), ptr(valid_b), stream_ptr()))
+    return cur, view, valid_a, valid_b
+
+
+def merge_gate(table, valid_a, valid_b):
+    """The matcher's table of merge_view's (cur, view) gated IN PLACE (and returned) (definition: include/floodseg_test.h, merge_gate):
+    int32 table [(H//16) * (W//16), 7], uint8 valid_a, valid_b [H,W].  A row stays iff the block's own 16 x 16 window lies wholly on
+    valid_a and its winner's window wholly on valid_b; every other row becomes the void row.  One launch; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.merge_gate"
+    if valid_a.dtype != torch.uint8 or valid_a.dim() != 2 or not valid_a.is_contiguous():
+        raise ValueError(f"{what}: valid_a must be a contiguous uint8 [H,W] tensor, got {valid_a.dtype} {tuple(valid_a.shape)}")
+    if valid_b.dtype != torch.uint8 or tuple(valid_b.shape) != tuple(valid_a.shape) or not valid_b.is_contiguous():
+        raise ValueError(f"{what}: valid_b must be a contiguous uint8 {list(valid_a.shape)} tensor like valid_a, got {valid_b.dtype} {tuple(valid_b.shape)}")
+    h, w = _mosaic_size(valid_a.shape, "valid_a", what, 16)
+    blocks = (h // 16) * (w // 16)
+    if table.dtype != torch.int32 or tuple(table.shape) != (blocks, 7) or not table.is_contiguous():
+        raise ValueError(f"{what}: table must be a contiguous int32 [{blocks},7] tensor for a {h} x {w} plane, got {table.dtype} {tuple(table.shape)}")
+    dev = one_device(table, valid_a, valid_b, what=what)
+    with torch.cuda.device(dev):
+        check(lib.fs_merge_gate(ptr(table), blocks, ptr(valid_a), ptr(valid_b), h, w, stream_ptr()))
+    return table
+
+
+def link_correct(model, link, window, origin_a):
+    """global_motion's fit of merge_view's (cur, view), with frame_size = mask_size = the window, folded into the link IN PLACE
+    (definition: include/floodseg_test.h, link_correct): model int64 [16] or [1,16]; window = (Y0, X0, WH, WW) the view was drawn for;
+    origin_a = (oy, ox) of A.  -> out int64 [8] = (status, usable rows, inliers, rounds done, the fit's shift x and y in Q20, 0, 0);
+    status 0 corrected (the link's status becomes 0), 2 no fit, 3 out of the pose bounds, 4 the link was neither registered nor
+    initial; on 2, 3 and 4 the link is unchanged.  One launch of one wave; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.link_correct"
+    if model.dtype != torch.int64 or tuple(model.shape) not in ((16,), (1, 16)) or not model.is_contiguous():
+        raise ValueError(f"{what}: model must be one contiguous int64 [16] row of global_motion's output, got {model.dtype} {tuple(model.shape)}")
+    _relocate_row(link, 16, "link", what)
+    y0, x0, wh, ww = _merge_window(window, (MOSAIC_MAX_SIDE, MOSAIC_MAX_SIDE), what)
+    oy, ox = _mosaic_origin(origin_a, what)
+    dev = one_device(model, link, what=what)
+    with torch.cuda.device(dev):
+        out = torch.empty((8,), dtype=torch.int64, device=dev)
+        check(lib.fs_link_correct(ptr(model), ptr(link), y0, x0, wh, ww, ox, oy, ptr(out), stream_ptr()))
+    return out
+
+
+def mosaic_merge(votes_a, origin_a, votes_b, origin_b, link, ortho_a=None, ortho_b=None, ordinal_offset=0, mode="centre"):
+    """Mosaic B folded into mosaic A, IN PLACE, under a registered link (definition: include/floodseg_test.h, mosaic_merge).  votes_a,
+    votes_b: uint16 [K,CH,CW] with one K; origin_* = (oy, ox); ortho_a, ortho_b: (rank, rgba) of ortho_canvas, both or neither.  Every A
+    canvas pixel adds the votes of the B pixel under it (saturating at 65535) and takes B's orthophoto pixel where B's rank, with
+    ordinal_offset added to its ordinal (mode "latest": and its key rebuilt from it), is strictly smaller than A's.  A link whose
+    status is not 0 changes nothing; that is decided on the device.  -> counts int64 [8] = (link status, A pixels B reached, pixels
+    that received a vote, votes added before saturation, orthophoto pixels taken, 0, 0, 0).  VOTES ARE NOT IDEMPOTENT: a second call
+    adds B's votes again (the orthophoto is unchanged by it).  Two launches; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.mosaic_merge"
+    votes_a, votes_b = _mosaic_votes(votes_a, what), _mosaic_votes(votes_b, what)
+    if votes_a.shape[0] != votes_b.shape[0]:
+        raise ValueError(f"{what}: both vote canvases must have one K, got {votes_a.shape[0]} and {votes_b.shape[0]}")
+    oy_a, ox_a = _mosaic_origin(origin_a, what)
+    oy_b, ox_b = _mosaic_origin(origin_b, what)
+    _relocate_row(link, 16, "link", what)
+    if mode not in ORTHO_MODES:
+        raise ValueError(f"{what}: mode must be one of {sorted(ORTHO_MODES)}, got {mode!r}")
+    if not 0 <= int(ordinal_offset) < 0xFFFFFFFF:
+        raise ValueError(f"{what}: ordinal_offset must be 0..{0xFFFFFFFF - 1}, got {ordinal_offset}")
+    if (ortho_a is None) != (ortho_b is None):
+        raise ValueError(f"{what}: ortho_a and ortho_b go together, got {'None' if ortho_a is None else 'planes'} and {'None' if ortho_b is None else 'planes'}")
+    planes = []
+    for name, ortho, votes in (("ortho_a", ortho_a, votes_a), ("ortho_b", ortho_b, votes_b)):
+        if ortho is None:
+            continue
+        if not isinstance(ortho, (tuple, list)) or len(ortho) != 2:
+            raise ValueError(f"{what}: {name} must be (rank, rgba), got a {type(ortho).__name__}")
+        if _ortho_planes(ortho[0], ortho[1], what) != tuple(votes.shape[1:]):
+            raise ValueError(f"{what}: {name} must be as large as its vote canvas {tuple(votes.shape[1:])}, got {tuple(ortho[1].shape)}")
+        planes += list(ortho)
+    pairs = [(votes_a, votes_b)] + ([(planes[0], planes[2]), (planes[1], planes[3])] if planes else [])
+    if any(_same_memory(x, y) for x, y in pairs):
+        raise ValueError(f"{what}: A and B are the same memory (votes at {votes_a.data_ptr():#x} and {votes_b.data_ptr():#x})")
+    dev = one_device(votes_a, votes_b, link, *planes, what=what)
+    with torch.cuda.device(dev):
+        counts = torch.empty((8,), dtype=torch.int64, device=dev)
+        rank_a, rgba_a, rank_b, rgba_b = (ptr(p) for p in planes) if planes else (None,) * 4
+        check(lib.fs_mosaic_merge(ptr(votes_a), votes_a.shape[1], votes_a.shape[2], ox_a, oy_a, ptr(votes_b), votes_b.shape[1], votes_b.shape[2], ox_b, oy_b,
+                                  votes_a.shape[0], ptr(link), rank_a, rgba_a, rank_b, rgba_b, int(ordinal_offset), ORTHO_MODES[mode], ptr(counts), stream_ptr()))
+    return counts
+
+
+def merge_patch(rgba_b, origin_b, link, canvas_a, origin_a, scale, b_box=None):
+    """Mosaic B's orthophoto drawn into A's canvas cells under the link, for ops.map_locate against ops.map_coarse(rgba_a) (definition:
+    include/floodseg_test.h, merge_patch).  canvas_a = (CH, CW) of A; b_box = (y0, x0, y1, x1) in B canvas pixels, the part of B that is
+    drawn (default the whole canvas; FlowPredictor's parts pass the bounding box of what their frames saw).  -> (tl, tv, geom) exactly
+    as ops.map_patch returns them; geom[0]: 0 drawn, 1 the link is neither registered nor initial, 2 the link is out of bounds or the
+    box lands too far from A's anchor, 3 / 4 the patch has no or too many cells / more cells than A's coarse canvas.  Two launches;
+    nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.merge_patch"
+    ch_b, cw_b = _ortho_planes(None, rgba_b, what)
+    ch_a, cw_a = _mosaic_size(canvas_a, "canvas_a", what)
+    oy_a, ox_a = _mosaic_origin(origin_a, what)
+    oy_b, ox_b = _mosaic_origin(origin_b, what)
+    s = _relocate_scale(scale, what)
+    if ch_a // s < 1 or cw_a // s < 1:
+        raise ValueError(f"{what}: a {ch_a} x {cw_a} canvas has no cell of scale {s}")
+    _relocate_row(link, 16, "link", what)
+    box = (0, 0, ch_b, cw_b) if b_box is None else tuple(int(v) for v in b_box)
+    if len(box) != 4 or not (0 <= box[0] < box[2] <= ch_b and 0 <= box[1] < box[3] <= cw_b):
+        raise ValueError(f"{what}: b_box must be a non-empty (y0, x0, y1, x1) inside the {ch_b} x {cw_b} canvas B, got {box}")
+    dev = one_device(rgba_b, link, what=what)
+    with torch.cuda.device(dev):
+        tl, tv = (torch.empty((RELOCATE_PATCH_BYTES,), dtype=torch.uint8, device=dev) for _ in range(2))
+        geom = torch.empty((8,), dtype=torch.int64, device=dev)
+        check(lib.fs_merge_patch(ptr(rgba_b), ch_b, cw_b, ox_b, oy_b, ptr(link), ch_a, cw_a, ox_a, oy_a, s, *box, ptr(tl), ptr(tv), ptr(geom), stream_ptr()))
+    return tl, tv, geom
+
+
+def link_place(found, link, scale, max_mean=16, ratio_permille=800):
+    """map_locate's placement of merge_patch's patch as a CANDIDATE link (definition: include/floodseg_test.h, link_place); `link` is only
+    read.  -> (cand int64 [16], out int64 [8]).  Accepted as ops.pose_relocate accepts (the mean, the uniqueness, the bounds): the
+    candidate is then the link with both affines moved by (scale u*, scale v*) A canvas pixels and status 1; otherwise the link as
+    it was.  out = (code, scale u*, scale v*, sad*, n*, sad2, n2, eligible placements); code 0 placed, 1 the link is neither registered
+    nor initial, 2 no placement, 3 / 4 rejected by the mean / by uniqueness, 6 an unusable row, 7 out of the pose bounds.  One launch
+    of one wave; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.link_place"
+    s = _relocate_scale(scale, what)
+    if not 0 <= int(max_mean) <= 255:
+        raise ValueError(f"{what}: max_mean must be 0..255, got {max_mean}")
+    if not 1 <= int(ratio_permille) <= 1000:
+        raise ValueError(f"{what}: ratio_permille must be 1..1000, got {ratio_permille}")
+    _relocate_row(found, 16, "found", what)
+    _relocate_row(link, 16, "link", what)
+    dev = one_device(found, link, what=what)
+    with torch.cuda.device(dev):
+        cand = torch.empty((16,), dtype=torch.int64, device=dev)
+        out = torch.empty((8,), dtype=torch.int64, device=dev)
+        check(lib.fs_link_place(ptr(found), ptr(link), s, int(max_mean), int(ratio_permille), ptr(cand), ptr(out), stream_ptr()))
+    return cand, out
+
+
+_PLACE_KEYS = {"scale", "min_overlap_permille", "exclude", "max_mean", "ratio_permille", "b_box"}
+
+
+def register_mosaics(a, b, link, rounds=2, search=16, intra_bias=0, fit_rounds=4, tol=1.0, min_inliers=12, window=None, place=None):
+    """Mosaic B registered against mosaic A: a = (rgba_a, origin_a), b = (rgba_b, origin_b), link int64 [16] with status 0
+    or 1, UPDATED IN PLACE.  With place = dict(scale=4 | 8 | 16[, min_overlap_permille, exclude, max_mean, ratio_permille, b_box]) the
+    coarse placement runs first: merge_patch, map_coarse(rgba_a), map_locate, link_place, and the candidate replaces the link (a device
+    copy).  Then `rounds` times: merge_view, block_match_modes(cur, view, search, 0, intra_bias), merge_gate, global_motion(fit_rounds,
+    tol, min_inliers) on the window, link_correct.  Without place the residual between the link and the truth must lie within `search`
+    pixels; a link that no round confirms keeps its status 1, and ops.mosaic_merge then changes nothing.  Enqueues only (6 launches a
+    round, 7 and a copy for the placement, one stream, nothing read back): capturable as one linear graph.  -> (link, outs int64
+    [rounds (+ 1: link_place's row first), 8]).  The defaults are guesses, not validated on real video."""
+    what = "floodseg.register_mosaics"
+    if place is not None and (not isinstance(place, dict) or "scale" not in place or set(place) - _PLACE_KEYS):
+        raise ValueError(f"{what}: place must be a dict with scale and at most {sorted(_PLACE_KEYS)}, got {place!r}")
+    if not 1 <= int(rounds) <= 8:
+        raise ValueError(f"{what}: rounds must be 1..8, got {rounds}")
+    if not 1 <= int(search) <= 32:
+        raise ValueError(f"{what}: search must be 1..32 pixels, got {search}")
+    for name, m in (("a", a), ("b", b)):
+        if not isinstance(m, (tuple, list)) or len(m) != 2:
+            raise ValueError(f"{what}: {name} must be (rgba, origin), got a {type(m).__name__}")
+    (rgba_a, origin_a), (rgba_b, origin_b) = a, b
+    win = _merge_window(window, _ortho_planes(None, rgba_a, what), what)
+    outs = []
+    if place is not None:
+        tl, tv, geom = merge_patch(rgba_b, origin_b, link, rgba_a.shape, origin_a, place["scale"], place.get("b_box"))
+        cl, cv = map_coarse(rgba_a, place["scale"])
+        found = map_locate(cl, cv, tl, tv, geom, place.get("min_overlap_permille", 500), place.get("exclude", 2))
+        cand, out = link_place(found, link, place["scale"], place.get("max_mean", 16), place.get("ratio_permille", 800))
+        link.copy_(cand)
+        outs.append(out)
+    for _ in range(int(rounds)):
+        cur, view, valid_a, valid_b = merge_view(rgba_a, origin_a, rgba_b, origin_b, link, win)
+        table, stats = block_match_modes(cur, view, search, 0, intra_bias, return_stats=True)
+        merge_gate(table, valid_a, valid_b)
+        fit = global_motion(table[None], win[2:], win[2:], fit_rounds, tol, min_inliers, pair_stats=stats[None])
+        outs.append(link_correct(fit, link, win, origin_a))
+    return link, torch.stack(outs)
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

@@ -1268,6 +1268,120 @@ typedef struct fs_hook_tables12 {
     fs_ext12_api ext12;
 } fs_hook_tables12;
 
+/* ---- The FOURTEENTH table.  fs_ext12_api is frozen as well (5 members, 56 bytes; tests/test_merge_cpu.py), so ops added since live in
+ * a table of their own, append-only, that the library places directly behind fs_hook_tables12 by the same pattern:
+ *     const fs_hook_tables13* t = (const fs_hook_tables13*)fs_test_hooks();   t->ext13.mosaic_merge(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables12: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext13.magic == FS_EXT13_MAGIC and ext13.size >= the end of the member it needs. */
+#define FS_EXT13_MAGIC 0x4653455854413133ull /* "FSEXTA13" */
+
+typedef struct fs_ext13_api {
+    uint64_t magic; /* FS_EXT13_MAGIC */
+    size_t size;    /* sizeof(fs_ext13_api) of the library that was built */
+
+    /* ---- MAP-TO-MAP REGISTRATION AND THE MERGE OF TWO MOSAICS (csrc/merge_ops.hip, csrc/merge_defs.h).  OUR DEFINITION:
+     * the reference has nothing like it.  Two mosaics A and B (vote canvas, orthophoto, origin each) of overlapping ground, each with a
+     * pose chain and an anchor frame of its own, are registered against each other and B is folded into A:
+     *   [merge_view -> block_match_modes(cur, view) -> merge_gate -> global_motion (frame_size = mask_size = the window) -> link_correct]
+     *   a few times, then mosaic_merge.
+     * The same rules as code: csrc/merge_defs.h (host and device) and tests/merge_ref.py (numpy).  All integer, bit for bit.
+     *
+     * A LINK is int64 [16], shaped like a pose row: words 0..5 b_to_a (B's anchor coordinates -> A's, Q20; to_anchor's place), 6..11
+     * a_to_b (from_anchor's place), 12 the status (0 registered, 1 initial: a caller's guess not yet confirmed, 2 no fit, 3 out of the
+     * pose bounds), 13..15 inliers, usable rows, rounds done of the fit that registered it.  It is IN BOUNDS under pose_chain's pose
+     * bounds (|linear| < 16 ONE both ways, |b_to_a translation| < 2^14 ONE, |a_to_b translation| < 2^20 ONE), tested before any product.
+     *
+     * THE GATHER all ops share: a canvas is addressed as in mosaic_accumulate (pixel (X, Y) of a canvas with origin (ox, oy) has the
+     * anchor coordinate ((2 (X - ox) + 1) << 19, (2 (Y - oy) + 1) << 19)).  The B canvas pixel under A canvas pixel (X, Y) is
+     *   (bx, by) = source_pixel(a_to_b, anchor_coord(X, ox_a), anchor_coord(Y, oy_a)) + (ox_b, oy_b)
+     * with mosaic_accumulate's source_pixel (it yields pixel indices of B's anchor frame already); it EXISTS iff 0 <= bx < CW_b and
+     * 0 <= by < CH_b.  |X - ox_a| <= 2^15, so the products stay below 2^61 as in mosaic_accumulate.
+     *
+     * merge_view draws, for the window [Y0, Y0 + WH) x [X0, X0 + WW) of A's canvas, four uint8 planes [WH][WW]: cur = luma_of(A's
+     * word) (map_view's luma_of; whatever the word holds), valid_a = 1 iff that word's alpha byte is not 0; view = luma_of(B's word
+     * under it) and valid_b = 1 where that pixel exists and ITS alpha byte is not 0, both 0 elsewhere -- and everywhere for a link whose
+     * status is neither 0 nor 1 or that is out of bounds.  ONE launch, a thread per four pixels of a row, a dword per plane.
+     * Refused before a launch: a null pointer; CH or CW of A or B outside 1..16384; |ox| or |oy| of A or B > 16384; a window that is
+     * not whole blocks of 16 (WH, WW >= 16, multiples of 16) inside A's canvas; rgba_a == rgba_b; rgba not aligned to 4, link not
+     * aligned to 8, a plane not aligned to 4 bytes. */
+    int (*merge_view)(const uint32_t* rgba_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b,
+                      const int64_t* link, int Y0, int X0, int WH, int WW, uint8_t* cur, uint8_t* view, uint8_t* valid_a, uint8_t* valid_b, fs_stream stream);
+
+    /* ---- merge_gate gates the matcher's table of (cur, view), H x W = the window, IN PLACE.  Row i belongs to the block at
+     * (16 (i % (W / 16)), 16 (i / (W / 16))) -- taken from the row's INDEX, not from its words.  The row stays iff that block's own
+     * 16 x 16 window lies wholly on valid_a == 1 AND map_gate's rule holds on valid_b: the winner's window [src_x - 8, src_x + 8) x
+     * [src_y - 8, src_y + 8) lies inside the plane (tested in 64 bits before a byte is read) and wholly on valid_b == 1.  Every other
+     * row becomes the void row (-1, 16, 16, -16, -16, -16, -16); a void row has no window in any plane and stays void.  ONE launch, a
+     * wave per row.
+     * Refused before a launch: a null pointer; H or W outside 16..16384; blocks != (H / 16) (W / 16); table not aligned to 4. */
+    int (*merge_gate)(int32_t* table, int blocks, const uint8_t* valid_a, const uint8_t* valid_b, int H, int W, fs_stream stream);
+
+    /* ---- link_correct folds global_motion's row for (cur, view) into the link, IN PLACE.  The fit's forward model F takes a window
+     * pixel to its place in view; with s = (X0 - ox_a, Y0 - oy_a) the correction in A's anchor coordinates is C(P) = F(P - s) + s:
+     * F's linear part and the translation F.t + s ONE - F.lin s (whole pixels: exact); the inverse model is conjugated the same way.
+     * out int64 [8] = (status, usable, inliers, rounds done, F.t x, F.t y, 0, 0), pose_correct's layout.  In this order:
+     *   4  the link's status is neither 0 nor 1;
+     *   2  model[12] != 0, or the model or the CONJUGATED pair is out of global_motion's pair bounds (|linear| <= 2 ONE, |t| < 2^16 ONE);
+     *   3  the link is out of the pose bounds, or the result would be;
+     *   0  a_to_b <- compose(a_to_b, C), b_to_a <- compose(C^-1, b_to_a), the link's status becomes 0 and its words 13..15 the fit's
+     *      inliers, usable rows and rounds.
+     * On 2, 3 and 4 the link is unchanged.  ONE launch of one wave.
+     * Refused before a launch: a null pointer; a window that is not whole blocks of 16 with 0 <= Y0, X0 and Y0 + WH, X0 + WW <= 16384;
+     * |ox_a| or |oy_a| > 16384; a pointer not aligned to 8 bytes; model == link. */
+    int (*link_correct)(const int64_t* model, int64_t* link, int Y0, int X0, int WH, int WW, int ox_a, int oy_a, int64_t* out, fs_stream stream);
+
+    /* ---- mosaic_merge folds B into A, IN PLACE, under a link whose status is 0 and that is in bounds; under any other link NOTHING of A
+     * changes (decided on the device) and counts = (the link's status, 0, ...).  votes uint16 [K][CH][CW] on both sides, the same K; rank
+     * and rgba: ortho_accumulate's planes of A and B, all four or all null (votes only).  For every A canvas pixel whose B pixel exists:
+     *   votes: for every k < K, votes_a[k] = min(65535, votes_a[k] + votes_b[k][that pixel]) -- nearest neighbour, one owner per A pixel;
+     *   orthophoto: where B's rank word is not all ones, ord' = its low word + ordinal_offset; ord' > 0xFFFFFFFE takes nothing; the new
+     *   word is (high << 32) | ord' with high = B's high word (mode 0, centre) or 0xFFFFFFFF - ord' (mode 1, latest); A's pixel takes
+     *   the word and B's rgba iff the new word is strictly smaller than A's: ties stay with A, and a second identical call changes
+     *   nothing in the orthophoto.  VOTES ARE NOT IDEMPOTENT: a second call adds them again.
+     * counts int64 [8] = (link status, A pixels whose B pixel exists, of those the pixels where B had a vote, the votes added before
+     * saturation, orthophoto pixels taken, 0, 0, 0).
+     * TWO launches: a kernel that clears counts, then one workgroup of 256 per 64 x 16 tile of A; a tile B's canvas rectangle cannot
+     * reach (mosaic_accumulate's touches with B's origin folded into the translation) returns before touching a canvas.  No canvas
+     * takes an atomic; counts go through an LDS tally and one 64-bit atomic per workgroup and non-zero cell.
+     * Refused before a launch: a null votes, link or counts pointer, or some but not all of the four orthophoto pointers; CH or CW of
+     * A or B outside 1..16384; |ox| or |oy| > 16384; K outside 1..32; mode not 0 or 1; ordinal_offset == 0xFFFFFFFF; A and B the same
+     * memory (votes, rank or rgba); votes not aligned to 2, rgba to 4, rank, link or counts to 8 bytes. */
+    int (*mosaic_merge)(uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint16_t* votes_b, int CH_b, int CW_b, int ox_b, int oy_b, int K,
+                        const int64_t* link, uint64_t* rank_a, uint32_t* rgba_a, const uint64_t* rank_b, const uint32_t* rgba_b, uint32_t ordinal_offset, int mode,
+                        int64_t* counts, fs_stream stream);
+
+    /* ---- merge_patch and link_place: the COARSE PLACEMENT for two mosaics whose link is not known to within the matcher's search, through
+     * §3.22's map_coarse(rgba_a) and map_locate, which run unchanged:
+     *   merge_patch -> map_coarse -> map_locate -> link_place -> [the fine rounds above on the candidate].
+     * merge_patch draws B into A's canvas cells under the link; tl, tv, geom exactly as map_patch writes them.  The geometry is
+     * map_patch's box rule on the corners of b_box = [x0, x1) x [y0, y1) (B canvas pixels) under t = b_to_a: a corner (x, y) lies at
+     * cx = t00 (x - ox_b) + t01 (y - oy_b) + t02 + ox_a ONE (below 2^41), cy alike; canvas pixels [min cx >> 20, (max cx + ONE - 1) >> 20),
+     * widened outwards to whole cells.  status 1: the link's status is neither 0 nor 1.  status 2: the link is out of the pose bounds,
+     * or the box's pixels lie more than 2^15 from A's anchor (the gather's products then stay below 2^62).  status 3, 4: map_patch's.
+     * status 0: patch cell (i, j) is A's canvas cell (pu0 + i, pv0 + j); it is valid iff the B pixel under every one of its S^2 canvas
+     * pixels exists (THE GATHER above) and has been seen; tl is then the rounded mean of their luma_of, as map_coarse's.
+     * TWO launches, as map_patch's.
+     * Refused before a launch: a null pointer; CH or CW of A or B outside 1..16384; |ox| or |oy| > 16384; S not 4, 8 or 16; A's canvas
+     * without a cell; a b_box that is empty or not inside B's canvas; rgba_b not aligned to 4, link or geom to 8 bytes. */
+    int (*merge_patch)(const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b, const int64_t* link, int CH_a, int CW_a, int ox_a, int oy_a, int S, int y0,
+                       int x0, int y1, int x1, uint8_t* tl, uint8_t* tv, int64_t* geom, fs_stream stream);
+
+    /* ---- link_place turns map_locate's placement into a CANDIDATE link (16 words); `link` is only read.  pose_relocate's acceptance and
+     * codes, in this order: 1 the link's status is neither 0 nor 1; 2 found[0] == 1; 6 found[0] != 0, the link out of the pose bounds,
+     * or counts that pose_relocate refuses; 3 sad* > max_mean n*; 4 a runner-up with 1000 sad* n2 > ratio_permille sad2 n*; 7 the moved
+     * link fails the pose bounds; 0 placed: both affines moved by (S u*, S v*) A canvas pixels with pose_relocate's exact translation,
+     * status 1, words 13..15 zero.  With any other code the candidate is the link as it was.  out int64 [8] = relocate_commit's row
+     * (code, S u*, S v*, sad*, n*, sad2, n2, eligible placements).  ONE launch of one wave.
+     * Refused before a launch: a null pointer; S not 4, 8 or 16; max_mean outside 0..255; ratio_permille outside 1..1000; a pointer not
+     * aligned to 8 bytes; cand == link. */
+    int (*link_place)(const int64_t* found, const int64_t* link, int S, int max_mean, int ratio_permille, int64_t* cand, int64_t* out, fs_stream stream);
+} fs_ext13_api;
+
+typedef struct fs_hook_tables13 {
+    fs_hook_tables12 base12;
+    fs_ext13_api ext13;
+} fs_hook_tables13;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

@@ -3,7 +3,8 @@ costs -- and ops.mosaic_resolve, the report's, on one 1072 x 1920 five-frame win
 (the frames' footprint is a fifth of the canvas) and a pose set that covers the whole canvas (every frame magnified four times).
 Device events, medians of 20 groups of 5 back-to-back calls, eagerly through the Python wrappers and as a captured graph replayed; the
 clock read before and after.  Next to mosaic_accumulate its byte floor: the mask bytes read plus 2 B read and 2 B written per touched
-vote, at 8 TB/s.  Prints to stdout."""
+vote, at 8 TB/s.  Then the four per-merge calls of DESIGN §3.23 (ops.merge_view, ops.merge_gate, ops.link_correct, ops.mosaic_merge) on
+two such canvases, B over a quarter of A and over all of it, each next to the bytes it must move.  Prints to stdout."""
 import os
 import statistics
 import subprocess
@@ -141,4 +142,35 @@ for name, poses in (("slow pan (3, 2) px a frame", pose_rows(1.0, [(3 * f, 2 * f
     row("mosaic_resolve after it", lambda: ops.mosaic_resolve(votes), pixels * (2 * K + 1 + 1 + 4))
 say("(mosaic_resolve: per canvas pixel 2 B of votes per class read, cls, conf and seen written.  eager: through the Python wrapper, its output")
 say(" allocations and the enqueue included; graph: GROUP such calls captured and replayed, per call.)")
+
+# ---- the four calls a merge costs: A and B cut from one random texture, so the fit is a real one (the identity)
+say()
+say(f"merging two {CANVAS[0]} x {CANVAS[1]}-class mosaics, K = {K}: the link is registered and exact; origins (0, 0)")
+say(f"{'call':<58}{'eager us':>10}{'min':>9}{'max':>9}{'graph us':>10}{'MB moved':>10}{'floor us':>10}{'floor/graph':>12}")
+ground = torch.from_numpy(rng.randint(0, 1 << 24, size=CANVAS).astype(np.int32)).cuda() | (0xFF << 24) - (1 << 32)   # alpha 255: seen everywhere
+votes_a = torch.from_numpy(rng.randint(0, 40, size=(K,) + CANVAS).astype(np.int16)).cuda().view(torch.uint16)
+rank_a = torch.from_numpy(rng.randint(0, 1 << 40, size=CANVAS)).cuda()
+for name, (bh, bw), (ty, tx) in (("B over a quarter of A", (CANVAS[0] // 2, CANVAS[1] // 2), (CANVAS[0] // 4, CANVAS[1] // 4)), ("B over all of A", CANVAS, (0, 0))):
+    rgba_b = ground[ty:ty + bh, tx:tx + bw].clone()   # a copy: the whole-canvas crop would be A's own memory, which the ops refuse
+    votes_b = torch.from_numpy(rng.randint(0, 40, size=(K, bh, bw)).astype(np.int16)).cuda().view(torch.uint16)
+    rank_b = torch.from_numpy(rng.randint(0, 1 << 40, size=(bh, bw))).cuda()
+    link = ops.mosaic_link([ONE, 0, tx * ONE, 0, ONE, ty * ONE], [ONE, 0, -tx * ONE, 0, ONE, -ty * ONE], ops.LINK_REGISTERED, "cuda")
+    window, reached, pixels = (0, 0) + CANVAS, bh * bw, CANVAS[0] * CANVAS[1]
+    row(f"merge_view, {name}", lambda: ops.merge_view(ground, (0, 0), rgba_b, (0, 0), link, window), 4 * pixels + 4 * reached + 4 * pixels)
+    cur, view, valid_a, valid_b = ops.merge_view(ground, (0, 0), rgba_b, (0, 0), link, window)
+    table, stats = ops.block_match_modes(cur, view, 16, 0, 0, return_stats=True)
+    blocks = table.shape[0]
+    row(f"merge_gate, {blocks} rows", lambda: ops.merge_gate(table, valid_a, valid_b), blocks * (28 + 512))
+    fit = ops.global_motion(table[None], CANVAS, CANVAS, 4, 1.0, 12, pair_stats=stats[None])
+    scratch = link.clone()
+    row("link_correct (with a 128-byte copy of the link in front)", lambda: ops.link_correct(fit, scratch.copy_(link), window, (0, 0)))
+    host_fit, kept = fit.cpu().numpy()[0], int((table[:, 3] >= 0).sum())
+    say(f"  (the fit: status {host_fit[12]}, usable {host_fit[13]}, inliers {host_fit[14]}, shift {host_fit[2] / ONE:.3f}, {host_fit[5] / ONE:.3f} px; {kept} rows survive the gate)")
+    va, ra, ca = votes_a.clone(), rank_a.clone(), ground.clone()
+    row(f"mosaic_merge, votes only, {name}", lambda: ops.mosaic_merge(va, (0, 0), votes_b, (0, 0), link), reached * 2 * K * 3)
+    row(f"mosaic_merge with the orthophoto, {name}", lambda: ops.mosaic_merge(va, (0, 0), votes_b, (0, 0), link, (ra, ca), (rank_b, rgba_b), 7, "centre"),
+        reached * (2 * K * 3 + 16))
+    counts = ops.mosaic_merge(va, (0, 0), votes_b, (0, 0), link, (ra, ca), (rank_b, rgba_b), 7, "centre").cpu().numpy()
+    say(f"  (counts {counts[:5].tolist()}; MB moved: 2 B of B and 2 + 2 B of A per class and reached pixel, + the two rank words; repeated calls saturate")
+    say("   the votes but read and write the same cells; the orthophoto takes its pixels in the FIRST call only: the 12 B written per pixel won are not in these times)")
 say(f"clock after: {clocks()}")

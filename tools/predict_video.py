@@ -79,7 +79,10 @@ to R >= the largest PX pixels (regions further away then have an empty `dist`); 
 frame's width per pixel where water is a single speck.  Distances
 are mask pixels of a moving, un-georeferenced camera -- no metres follow from them -- and the thresholds are guesses, not validated on
 real video.
-`--mosaic FILE.png` (an extension; needs estimated grids: `--raw`, or `--grids estimate`; one process) registers every
+`--mosaic FILE.png` (an extension; needs estimated grids: `--raw`, or `--grids estimate`.  Under torchrun, with `--ortho`,
+every rank mosaics its own block of windows and writes `FILE.partNNN.npz`; rank 0 then registers the parts against each other in rank
+order, merges them and writes the outputs, DESIGN §3.23 -- `--mosaic-report` lists rank 0's frames and `FILE.merge.csv` beside it one row
+per merged part.  `--mosaic-part FILE.npz`, with `--ortho`, saves the (merged) mosaic for `tools/merge_mosaics.py`) registers every
 frame's mask to the first frame through the camera's motion -- one robust affine per frame pair, fitted on the device to the block
 matcher's vectors, without the blocks that lie on the classes of `--mosaic-exclude` (default 1, water) -- and accumulates the masks
 into one extent map of `--mosaic-size H W` pixels (default: twice the output size), in which each piece of ground is counted once.  The
@@ -89,7 +92,7 @@ status (ok, bridged, lost), whether the frame left the canvas, and the fit's inl
 pixels and their share of the ground seen.  A scene cut ends the chain: the frames after it are reported as lost.  The defaults are
 guesses, not validated on real video; an affine per pair is not a homography, the chain drifts over a long flight and nothing closes
 loops; areas are pixels of the first frame, not metres.
-`--ortho FILE.png` (an extension; needs `--mosaic`, and so estimated grids and one process) gathers, with the same poses, the
+`--ortho FILE.png` (an extension; needs `--mosaic`, and so estimated grids) gathers, with the same poses, the
 frames' pixels -- the image the network saw, at the mask's resolution -- into an orthophoto of the mosaic's size and writes it with the extent
 map blended over it at `--ortho-alpha A` (default 96 of 255); `--ortho-edge K [K ...]` draws a one-pixel line along the inside of those
 classes' boundaries, `--ortho-plain` leaves the extent map off.  `--ortho-mode centre` (default) gives each piece of ground to the view that
@@ -128,7 +131,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flood_uav_video_segmentation_amd import ops, shard, synth  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.dataset import PredictWindows, RawVideoWindows, RawVideoWriter  # noqa: E402
 from flood_uav_video_segmentation_amd.flow.model import FlowModel  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_exposure_csv, write_extent_csv, write_guide_csv, write_mosaic_csv, write_relocate_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, FlowPredictor, colorize, compose_window, write_exposure_csv, write_extent_csv, write_guide_csv, read_mosaic_part, write_merge_csv, write_mosaic_csv, write_mosaic_part, write_relocate_csv, write_outlines_geojson, write_regions_csv, write_tracks_csv  # noqa: E402
 from flood_uav_video_segmentation_amd.model.deeplabv3 import FlowDeepLabv3  # noqa: E402
 from flood_uav_video_segmentation_amd.model.pspnet import FlowPSPNet  # noqa: E402
 
@@ -281,6 +284,8 @@ def parse_args(argv=None):
     ap.add_argument("--relocate-ratio", type=float, default=None, metavar="F", help="--mosaic-relocate: the best placement's mean must be at most F times the "
                     "runner-up's, 0.001..1 (default 0.8)")
     ap.add_argument("--relocate-report", default=None, metavar="FILE.csv", help="--mosaic-relocate: the outcome of the relocation per frame as CSV")
+    ap.add_argument("--mosaic-part", default=None, metavar="FILE.npz", help="--mosaic --ortho: also save the mosaic (votes, orthophoto, pose rows, seen box) as one "
+                    "file that tools/merge_mosaics.py merges with other runs' (DESIGN 3.23)")
     ap.add_argument("--mosaic-report", default=None, metavar="FILE.csv", help="--mosaic: per frame the pose, status, clipped flag, inliers and usable "
                     "blocks; per class the canvas pixels and their share of the ground seen")
     ap.add_argument("--draw-outlines", type=int, nargs="?", const=1, default=None, metavar="W", help="--raw-out with --regions: draw a white line W "
@@ -329,6 +334,8 @@ def parse_args(argv=None):
         ap.error("--guide-bias needs --guide-outlier: only a vector that disagrees with the camera's is put to the frames")
     if not args.mosaic and (args.mosaic_size is not None or args.mosaic_report):
         ap.error("--mosaic-size and --mosaic-report need --mosaic FILE.png")
+    if args.mosaic_part and not (args.mosaic and args.ortho):
+        ap.error("--mosaic-part needs --mosaic FILE.png and --ortho FILE.png: mosaics are registered against each other on their orthophotos")
     if args.mosaic and (args.grids == "files" or (not args.raw and args.grids is None)):
         ap.error("--mosaic needs the block matcher's vectors: --grids estimate (the grids/ folders hold grids, from which no vector can be recovered)")
     if args.mosaic and args.no_warp:
@@ -435,6 +442,37 @@ def parse_args(argv=None):
     return args
 
 
+def mosaic_part_path(mosaic, rank):
+    """The part file rank `rank` of a multi-rank launch writes beside --mosaic FILE.png: FILE.partNNN.npz."""
+    return f"{os.path.splitext(mosaic)[0]}.part{int(rank):03d}.npz"
+
+
+def merge_command(args, paths):
+    """The tools/merge_mosaics.py command line that merges `paths` into what --mosaic, --ortho and --mosaic-report name."""
+    merged = os.path.splitext(args.mosaic_report)[0] + ".merge.csv" if args.mosaic_report else None
+    return " ".join(["python", "tools/merge_mosaics.py"] + list(paths) + ["--out", args.mosaic] + (["--ortho", args.ortho] if args.ortho else [])
+                    + (["--report", merged] if merged else []))
+
+
+def check_multi_rank_mosaic(args, world):
+    """--mosaic under a multi-rank launch: every rank's pose chain is its own, and the ranks' mosaics are registered against each other on
+    their orthophotos, so the launch needs --ortho."""
+    if args.mosaic and world > 1 and not args.ortho:
+        raise SystemExit("--mosaic under a multi-rank launch needs --ortho FILE.png: every rank's pose chain is its own, and the ranks' mosaics are "
+                         "registered against each other on their orthophotos before they are merged")
+
+
+def merge_rank_parts(pred, args, blocks):
+    """Rank 0 of a multi-rank launch, after every rank has written its part: fold the parts of the ranks behind it, in rank order, into
+    its own predictor's mosaic (FlowPredictor.merge_mosaic with the default link: a rank's anchor frame is the frame after the last one
+    of the rank before it).  blocks[r]: the number of windows rank r had; a rank without windows wrote no part.  -> the merged parts'
+    paths.  Enqueues only; pred.merge_report() reads back."""
+    paths = [mosaic_part_path(args.mosaic, r) for r in range(1, len(blocks)) if blocks[r] > 0]
+    for path in paths:
+        pred.merge_mosaic(read_mosaic_part(path, "cuda"))
+    return paths
+
+
 def main():
     args = parse_args()
 
@@ -450,8 +488,7 @@ def main():
     fm = FlowModel(net, feature_based=args.feature_based, no_warp=args.no_warp).eval()
     if args.tracks and world > 1:
         raise SystemExit("--tracks: track ids are per predictor and joining the ranks' blocks is out of scope: run it in a single process")
-    if args.mosaic and world > 1:
-        raise SystemExit("--mosaic: every rank's pose chain would be its own and merging the ranks' mosaics is out of scope: run it in a single process")
+    check_multi_rank_mosaic(args, world)
     mosaic_size = None if not args.mosaic else tuple(args.mosaic_size) if args.mosaic_size else (min(2 * args.size[0], 16384), min(2 * args.size[1], 16384))
     draw = args.draw_outlines is not None or args.draw_tracks or args.draw_ids is not None
     pred = FlowPredictor(fm, classes=args.classes, out_size=tuple(args.size), crop=None if args.no_cropping else tuple(args.crop),
@@ -602,7 +639,25 @@ def main():
         counts = torch.bincount(torch.cat(sources).cpu().long(), minlength=4).tolist()
         print(f"rank {rank}: --hold-cuts: {counts[0]} frames blended, {counts[1]} held from the previous key frame, {counts[2]} from the next, "
               f"{counts[3]} between two cuts", file=sys.stderr if args.raw_out == "-" else sys.stdout)
-    if args.mosaic:  # the canvas is resolved and read back ONCE, here, after the timed run
+    if args.mosaic and world > 1:  # every rank's mosaic is its own: each writes FILE.partNNN.npz, rank 0 merges them behind the wait below
+        blocks = [len(shard.window_block(len(ds), r, world)) for r in range(world)]
+        if blocks[rank] > 0:
+            write_mosaic_part(mosaic_part_path(args.mosaic, rank), pred.mosaic_part())
+        shard.barrier(torch.device("cuda", local_rank))
+        if rank == 0 and blocks[0] > 0:
+            paths = merge_rank_parts(pred, args, blocks)
+            links, outs, counts = pred.merge_report()
+            if args.mosaic_report:
+                write_merge_csv(os.path.splitext(args.mosaic_report)[0] + ".merge.csv", [os.path.basename(p) for p in paths], (links, outs, counts))
+            for path, link, count in zip(paths, links.tolist(), counts.tolist()):
+                print(f"--mosaic: {os.path.basename(path)} " + (f"merged: {count[2]} pixels received {count[3]} votes, {count[4]} orthophoto pixels taken"
+                                                               if link[12] == 0 else "could NOT be registered against the ranks before it and is left out"),
+                      file=sys.stderr if args.raw_out == "-" else sys.stdout)
+        elif rank == 0:  # fewer windows than ranks: rank 0 has no mosaic to merge into
+            print("--mosaic: rank 0 had no window; merge the parts by hand: "
+                  + merge_command(args, [mosaic_part_path(args.mosaic, r) for r in range(world) if blocks[r] > 0]), file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    mosaic_out = bool(args.mosaic) and (world == 1 or (rank == 0 and len(mine) > 0))  # under a multi-rank launch rank 0 writes the merged outputs
+    if mosaic_out:  # the canvas is resolved and read back ONCE, here, after the timed run
         from PIL import Image
 
         cls, _, seen, totals, poses = pred.mosaic_report()
@@ -616,7 +671,10 @@ def main():
               + (f"; {lost} frames lost (a scene cut, or more failed fits running than are bridged)" if lost else "")
               + (f"; {int(poses[:, 13].sum())} frames reach beyond the canvas (--mosaic-size)" if poses[:, 13].any() else ""),
               file=sys.stderr if args.raw_out == "-" else sys.stdout)
-    if args.ortho:  # drawn and read back ONCE, here, after the timed run
+    if args.mosaic_part and mosaic_out:  # the part's read-back, after the timed run (a multi-rank launch: the merged mosaic)
+        write_mosaic_part(args.mosaic_part, pred.mosaic_part())
+        print(f"--mosaic-part: {args.mosaic_part} (merge parts with tools/merge_mosaics.py)", file=sys.stderr if args.raw_out == "-" else sys.stdout)
+    if args.ortho and mosaic_out:  # drawn and read back ONCE, here, after the timed run
         from PIL import Image
 
         image, src, covered = pred.ortho_report(palette=palette, alpha=args.ortho_alpha, edge=args.ortho_edge, overlay=not args.ortho_plain)
@@ -629,7 +687,7 @@ def main():
               file=sys.stderr if args.raw_out == "-" else sys.stdout)
     if args.mosaic_relocate:
         relocated = pred.relocate_report()
-        if args.relocate_report:
+        if args.relocate_report and rank == 0:
             write_relocate_csv(args.relocate_report, report_ids, relocated)
         print(f"--mosaic-relocate: the chain was relocalised {int((relocated[:, 0] == 0).sum())} times; {int((relocated[:, 0] > 1).sum())} attempts on a lost chain failed",
               file=sys.stderr if args.raw_out == "-" else sys.stdout)
