@@ -429,6 +429,8 @@ int launch_map_view(const uint8_t* frame, const uint8_t* u, const uint8_t* v, in
                     uint32_t ordinal, int H, int W, int CH, int CW, int ox, int oy, const unsigned long long* rank, const uint32_t* rgba, int min_age,
                     uint8_t* cur, uint8_t* view, uint8_t* valid, hipStream_t s);
 int launch_map_gate(int32_t* table, int blocks, const uint8_t* valid, int H, int W, hipStream_t s);
+// the one gate launch, UNCHECKED: behind launch_map_gate (own == nullptr) and launch_merge_gate (own = valid_a), which check the arguments
+int launch_gate_rows(int32_t* table, int blocks, const uint8_t* own, const uint8_t* valid, int H, int W, hipStream_t s);
 int launch_pose_correct(const long long* model, long long* state, long long* pose, int H, int W, int CH, int CW, int ox, int oy, long long* out, hipStream_t s);
 
 // Relocalisation of a lost pose chain against the orthophoto (relocate_ops.hip, relocate_defs.h; definitions: include/floodseg_test.h,

@@ -1,8 +1,9 @@
 // The rules of map-to-map registration and of folding one mosaic into another (merge_ops.hip; definitions: include/floodseg_test.h,
 // merge_view, merge_gate, link_correct and mosaic_merge).  Plain __host__ __device__ C++ with nothing of HIP in it, on top
-// of mosaic_defs.h, ortho_defs.h and refine_defs.h (and, for the coarse placement, relocate_defs.h's cells, order and translation),
-// which it leaves alone: the kernels call these functions, and a host program (tests/test_merge_cpu.py builds
-// tests/merge_host_check.cpp) runs them on the CPU.  Everything here is integer arithmetic.
+// of mosaic_defs.h, ortho_defs.h, refine_defs.h and relocate_defs.h.  A rule that two ops of the family share is written once, in the
+// oldest header that needs it (the corners' box; the fit's report row; the cells of a box, the placement gate and its report row), and
+// called from here.  The kernels call these functions, and a host program (tests/test_merge_cpu.py builds tests/merge_host_check.cpp)
+// runs them on the CPU.  Everything here is integer arithmetic.
 #ifndef FS_MERGE_DEFS_H_
 #define FS_MERGE_DEFS_H_
 
@@ -38,7 +39,7 @@ FS_MOS_HD bool link_merges(const int64_t* link) { return link[12] == LINK_REGIST
 // THE BOUNDS, beside mosaic_defs.h's: |g translation| < 2^40 + 2^14 ONE (|ox_b| <= 2^14) < 2^41.
 //   an A canvas pixel:  |X - ox_a| <= 2^15, |anchor_coord| < 2^36;  2^24 x 2^36 = 2^60, two of them 2^61, + 2^19 under the shift;
 //                       the shifted sum below 2^42, + 2^41 < 2^43
-//   a tile corner:      2^24 x 2^15 whole pixels = 2^39, two 2^40, + 2^41 < 2^42
+//   a tile corner:      corner_box's widest caller: its bounds are written for this translation
 FS_MOS_HD void gather_affine(const int64_t* link, int ox_b, int oy_b, int64_t* g) {
     for (int i = 0; i < 6; ++i) g[i] = link[6 + i];
     g[2] += (int64_t)ox_b * mos::ONE, g[5] += (int64_t)oy_b * mos::ONE;
@@ -117,7 +118,7 @@ FS_MOS_HD int correct_step(const int64_t* model, int64_t* link, int X0, int Y0, 
             }
         }
     }
-    out[0] = status, out[1] = model[13], out[2] = model[14], out[3] = model[15], out[4] = model[2], out[5] = model[5], out[6] = 0, out[7] = 0;
+    refn::fit_report(status, model, out);
     return status;
 }
 
@@ -133,34 +134,24 @@ FS_MOS_HD bool shifted_rank(uint64_t rank_b, uint32_t ordinal_offset, int mode, 
     return true;
 }
 
-// ---- merge_patch: B drawn into A's canvas cells under the link, for map_locate.  The geometry is patch_geometry's box rule applied to
-// the corners of b_box = [x0, x1) x [y0, y1) (B canvas pixels; whole pixels, so the corners are exact in Q20) under b_to_a.  Status:
-// map_patch's codes -- 1: the link is neither registered nor initial (nothing to place); 2: the link is out of the pose bounds, or the
-// box lands more than 2^15 pixels from A's anchor; 3: no cell or more than 65536; 4: more cells than A's coarse canvas.
-// THE BOUNDS: a corner: |x - ox_b| <= 2^15; 2^24 x 2^15 = 2^39, two of them 2^40, + 2^34 + |ox_a| ONE (2^34) < 2^41: a canvas pixel below
-// 2^21 in magnitude.  Status 2's second test then holds every pixel of the patch within 2^15 + 16 of A's anchor (the widening to whole
-// cells adds at most S - 1 <= 15), so |anchor_coord| < 2^36 + 2^25 and b_pixel's products stay below 2^24 x 2^37 = 2^61, two of them 2^62.
+// ---- merge_patch: B drawn into A's canvas cells under the link, for map_locate.  The geometry is map_patch's -- guard, box, reach test,
+// cells -- on the corners of b_box = [x0, x1) x [y0, y1) (B canvas pixels) under b_to_a.  Status: map_patch's codes -- 1: the link is
+// neither registered nor initial (nothing to place); 2: the link is out of the pose bounds, or the box lands more than 2^15 pixels from
+// A's anchor; 3 and 4: relo::box_cells'.  A corner is |x - ox_b| <= 2^15 and b_to_a's translation below 2^34: inside corner_box's bounds.
+// Status 2's second test then holds every pixel of the patch within 2^15 + 16 of A's anchor (the widening to whole cells adds at most
+// S - 1 <= 15), so |anchor_coord| < 2^36 + 2^25 and b_pixel's products stay below 2^24 x 2^37 = 2^61, two of them 2^62.
 constexpr int64_t PATCH_REACH = (int64_t)1 << 15;
 FS_MOS_HD bool box_ok(int y0, int x0, int y1, int x1, int CH_b, int CW_b) { return y0 >= 0 && x0 >= 0 && y0 < y1 && x0 < x1 && y1 <= CH_b && x1 <= CW_b; }
 FS_MOS_HD int box_geometry(const int64_t* link, int y0, int x0, int y1, int x1, int ox_b, int oy_b, int CH_a, int CW_a, int ox_a, int oy_a, int S, int64_t* geom) {
     for (int i = 0; i < relo::GEOM_WORDS; ++i) geom[i] = 0;
     if (link[12] != LINK_REGISTERED && link[12] != LINK_INITIAL) return (int)(geom[0] = relo::PATCH_NOT_LOST);
     if (!link_in_bounds(link)) return (int)(geom[0] = relo::PATCH_OUT_OF_BOUNDS);
-    int64_t lo_x = INT64_MAX, hi_x = INT64_MIN, lo_y = INT64_MAX, hi_y = INT64_MIN;
-    for (int c = 0; c < 4; ++c) {
-        const int64_t x = (int64_t)((c & 1) ? x1 : x0) - ox_b, y = (int64_t)((c & 2) ? y1 : y0) - oy_b;
-        const int64_t cx = link[0] * x + link[1] * y + link[2] + (int64_t)ox_a * mos::ONE;  // below 2^41, see above
-        const int64_t cy = link[3] * x + link[4] * y + link[5] + (int64_t)oy_a * mos::ONE;
-        lo_x = cx < lo_x ? cx : lo_x, hi_x = cx > hi_x ? cx : hi_x, lo_y = cy < lo_y ? cy : lo_y, hi_y = cy > hi_y ? cy : hi_y;
-    }
-    const int64_t X0 = lo_x >> mos::FRAC, X1 = (hi_x + mos::ONE - 1) >> mos::FRAC, Y0 = lo_y >> mos::FRAC, Y1 = (hi_y + mos::ONE - 1) >> mos::FRAC;
+    int64_t lo_x, hi_x, lo_y, hi_y;
+    mos::corner_box(link, (int64_t)x0 - ox_b, (int64_t)y0 - oy_b, (int64_t)x1 - ox_b, (int64_t)y1 - oy_b, &lo_x, &hi_x, &lo_y, &hi_y);
+    const int64_t sx = (int64_t)ox_a * mos::ONE, sy = (int64_t)oy_a * mos::ONE;
+    const int64_t X0 = relo::floor_pixel(lo_x + sx), Y0 = relo::floor_pixel(lo_y + sy), X1 = relo::ceil_pixel(hi_x + sx), Y1 = relo::ceil_pixel(hi_y + sy);
     if (X0 - ox_a < -PATCH_REACH || X1 - ox_a > PATCH_REACH || Y0 - oy_a < -PATCH_REACH || Y1 - oy_a > PATCH_REACH) return (int)(geom[0] = relo::PATCH_OUT_OF_BOUNDS);
-    const int64_t pu0 = relo::floor_cell(X0, S), pu1 = relo::floor_cell(X1 + S - 1, S), pv0 = relo::floor_cell(Y0, S), pv1 = relo::floor_cell(Y1 + S - 1, S);
-    const int64_t tw = X1 > X0 ? pu1 - pu0 : 0, th = Y1 > Y0 ? pv1 - pv0 : 0;
-    if (tw < 1 || th < 1 || tw * th > relo::MAX_PATCH_CELLS) return (int)(geom[0] = relo::PATCH_CELLS);
-    if (tw > CW_a / S || th > CH_a / S) return (int)(geom[0] = relo::PATCH_WIDER_THAN_MAP);
-    geom[1] = pu0, geom[2] = pv0, geom[3] = tw, geom[4] = th;
-    return relo::PATCH_OK;
+    return relo::box_cells(X0, Y0, X1, Y1, CH_a, CW_a, S, geom);
 }
 // one pixel of a cell: the luma of the seen B pixel under A canvas pixel (X, Y) -- which may lie outside A's canvas --, or false
 FS_MOS_HD bool patch_pixel(const int64_t* g, int64_t X, int64_t Y, int ox_a, int oy_a, const uint32_t* rgba_b, int CH_b, int CW_b, uint32_t* luma) {
@@ -172,41 +163,21 @@ FS_MOS_HD bool patch_pixel(const int64_t* g, int64_t X, int64_t Y, int ox_a, int
     return true;
 }
 
-// ---- link_place: map_locate's placement as a CANDIDATE link.  relocate_step's acceptance and codes: 1 the link is neither registered nor
-// initial; 2 no eligible placement; 6 an unusable found row or a link out of bounds (tested before any product); 3 the mean; 4 the
-// uniqueness; 7 the moved link leaves the pose bounds; 0 placed: both affines moved by (S u*, S v*) A canvas pixels with translate's
-// exact rule (2^24 x 2^18 = 2^42), status 1 (initial: the fine rounds have yet to confirm it), words 13..15 zero.  With any other code
-// the candidate is the link as it was.  out = relocate_commit's row: (code, S u*, S v*, sad*, n*, sad2, n2, eligible placements).
+// ---- link_place: map_locate's placement as a CANDIDATE link.  relo::placement_gate with the link as the holder, so relocate_step's
+// acceptance and codes: 1 the link is neither registered nor initial; 2 no eligible placement; 6 an unusable found row or a link out of
+// bounds; 3 the mean; 4 the uniqueness; 7 the moved link leaves the pose bounds; 0 placed: both affines moved by (S u*, S v*) A canvas
+// pixels, status 1 (initial: the fine rounds have yet to confirm it), words 13..15 zero.  With any other code the candidate is the link
+// as it was.  out = relocate_commit's row: the code, then relo::placement_report's words.
 FS_MOS_HD int place_step(const int64_t* found, const int64_t* link, int max_mean, int ratio_permille, int S, int64_t* cand, int64_t* out) {
-    int decision = relo::RELOCATED;
-    int64_t to[6] = {0, 0, 0, 0, 0, 0}, from[6] = {0, 0, 0, 0, 0, 0};
-    if (link[12] != LINK_REGISTERED && link[12] != LINK_INITIAL) {
-        decision = relo::NOT_ATTEMPTED;
-    } else if (found[0] == relo::FOUND_NONE) {
-        decision = relo::NO_PLACEMENT;
-    } else if (found[0] != relo::FOUND || !link_in_bounds(link) || !relo::pair_ok(found[3], found[4]) || mos::iabs64(found[1]) > mos::MAX_SIDE ||
-               mos::iabs64(found[2]) > mos::MAX_SIDE || (found[5] != 0 && !relo::pair_ok(found[8], found[9]))) {
-        decision = relo::PATCH_REFUSED;
-    } else if (found[3] > (int64_t)max_mean * found[4]) {
-        decision = relo::REJECTED_MEAN;
-    } else if (found[5] != 0 && 1000 * found[3] * found[9] > (int64_t)ratio_permille * found[8] * found[4]) {
-        decision = relo::REJECTED_UNIQUENESS;
-    } else {
-        relo::translate(link, link + 6, (int64_t)S * found[1], (int64_t)S * found[2], to, from);
-        if (!mos::pose_in_bounds(to, from)) decision = relo::OUT_OF_BOUNDS;
-    }
+    int64_t to[6], from[6];
+    const int decision = relo::placement_gate(found, link[12] == LINK_REGISTERED || link[12] == LINK_INITIAL, link, max_mean, ratio_permille, S, to, from);
     for (int i = 0; i < LINK_WORDS; ++i) cand[i] = link[i];
     if (decision == relo::RELOCATED) {
         for (int i = 0; i < 6; ++i) cand[i] = to[i], cand[6 + i] = from[i];
         cand[12] = LINK_INITIAL, cand[13] = 0, cand[14] = 0, cand[15] = 0;
     }
-    for (int i = 0; i < OUT_WORDS; ++i) out[i] = 0;
     out[0] = decision;
-    if (found[0] == relo::FOUND && mos::iabs64(found[1]) <= mos::MAX_SIDE && mos::iabs64(found[2]) <= mos::MAX_SIDE) {  // S u: below 2^18
-        out[1] = (int64_t)S * found[1], out[2] = (int64_t)S * found[2], out[3] = found[3], out[4] = found[4];
-        if (found[5] != 0) out[5] = found[8], out[6] = found[9];
-    }
-    if (found[0] == relo::FOUND || found[0] == relo::FOUND_NONE) out[7] = found[11];
+    relo::placement_report(found, S, out);
     return decision;
 }
 

@@ -6,8 +6,8 @@
 //   merge_view    one launch; a thread per four pixels of a window row.  The link is read at a uniform address (scalar registers).  Per
 //                 pixel one word of A, and one word of B where the gather lands inside B's canvas.  Four uint8 planes, a dword per
 //                 thread and plane (the window is whole blocks of 16, the planes are aligned to 4).
-//   merge_gate    one wave per table row; the 256 valid_a bytes under the block's own window and the 256 valid_b bytes under the
-//                 winner's, four of each per lane, one ballot; a row that does not survive is overwritten with the void row.
+//   merge_gate    the checks, then refine_ops.hip's gate launch (launch_gate_rows) with valid_a for the block's own window: one wave per
+//                 table row, the 256 valid_a bytes under the block's own window and the 256 valid_b bytes under the winner's.
 //   link_correct  one wave; the rows go through LDS together, lane 0 runs correct_step.
 //   mosaic_merge  a clearing kernel for `counts` (a kernel, not a memset node: DESIGN §3.16), then one workgroup of 256 per 64 x 16 tile
 //                 of A as in mosaic_accumulate.  A tile that B's canvas rectangle cannot reach, and every tile under a link that is not
@@ -15,13 +15,15 @@
 //                 read and a write of A only where B has votes, and with the orthophoto a rank word of B and of A and, where B wins,
 //                 12 bytes written.  Every A pixel has one owner: no canvas takes an atomic.  The counts go through an LDS tally and
 //                 one 64-bit atomic per workgroup and non-zero cell.
-//   merge_patch   map_patch's two launches with B's canvas in the frame's place: a wave per cell of the patch (a lane per pixel of the cell, one
-//                 word of B each, a ballot and a wave sum), then one workgroup that counts the valid cells and writes geom.
+//   merge_patch   patch_kernels.h's two launches (cells, finish), which map_patch shares, on CanvasPatch below: the geometry is
+//                 box_geometry's on the link row, a pixel is one word of B under the one gather.
 //   link_place    one wave; lane 0 runs place_step.
 // Every loop bound follows from the arguments; nothing is allocated, synchronised or read back on the host.
 #include "egress_px.h"
 #include "kernels.h"
+#include "map_checks.h"
 #include "merge_defs.h"
+#include "patch_kernels.h"
 
 namespace fs {
 
@@ -31,17 +33,6 @@ constexpr int GROUP = 4;                  // merge_view: a thread owns four pixe
 constexpr int VIEW_TX = 64, VIEW_TY = 4;  // 256 threads: 256 pixels of a row by 4 rows
 constexpr int TILE_W = 64, TILE_H = 16, THREADS = 256;
 constexpr int TALLY = 4;                  // reached, voted, votes, taken
-constexpr int WAVE = 64;
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
-
-struct PatchArgs {  // merge_patch's geometry arguments, as box_geometry takes them
-    int y0, x0, y1, x1, ox_b, oy_b, CH_a, CW_a, ox_a, oy_a, S;
-};
 
 // ------------------------------------------------------------------ merge_view
 __global__ __launch_bounds__(VIEW_TX* VIEW_TY) void merge_view_kernel(const uint32_t* __restrict__ rgba_a, int CW_a, int ox_a, int oy_a,
@@ -71,27 +62,6 @@ __global__ __launch_bounds__(VIEW_TX* VIEW_TY) void merge_view_kernel(const uint
     *reinterpret_cast<uint32_t*>(view + at) = pack4(m[0], m[1], m[2], m[3]);
     *reinterpret_cast<uint32_t*>(valid_a + at) = pack4(va[0], va[1], va[2], va[3]);
     *reinterpret_cast<uint32_t*>(valid_b + at) = pack4(vb[0], vb[1], vb[2], vb[3]);
-}
-
-// ------------------------------------------------------------------ merge_gate: one wave per row
-__global__ __launch_bounds__(64) void merge_gate_kernel(int32_t* __restrict__ table, const uint8_t* __restrict__ valid_a, const uint8_t* __restrict__ valid_b, int H,
-                                                        int W) {
-    const int index = blockIdx.x, lane = threadIdx.x;
-    int32_t* row = table + (size_t)index * refn::ROW_WORDS;
-    int32_t r[refn::ROW_WORDS];  // a uniform address: every lane holds the row before any lane writes it
-#pragma unroll
-    for (int i = 0; i < refn::ROW_WORDS; ++i) r[i] = row[i];
-    int64_t x0, y0;
-    bool ok = refn::window_in_plane(r, H, W, &x0, &y0);  // uniform: in 64 bits, before any byte of valid_b is read
-    if (ok) {
-        const uint8_t* p = valid_b + (size_t)(y0 + (lane >> 2)) * W + (size_t)(x0 + (lane & 3) * 4);  // lane: row lane / 4, four bytes at column (lane % 4) * 4
-        ok = p[0] == 1 && p[1] == 1 && p[2] == 1 && p[3] == 1;
-        const int wb = W / mrg::BLOCK, ax = (index % wb) * mrg::BLOCK, ay = (index / wb) * mrg::BLOCK;  // the block's own window: inside the plane
-        const uint8_t* q = valid_a + (size_t)(ay + (lane >> 2)) * W + (size_t)(ax + (lane & 3) * 4);
-        ok = ok && q[0] == 1 && q[1] == 1 && q[2] == 1 && q[3] == 1;
-    }
-    const bool keep = __ballot(ok) == ~0ull;
-    if (!keep && lane < refn::ROW_WORDS) row[lane] = refn::void_word(lane);
 }
 
 // ------------------------------------------------------------------ link_correct: lane 0 runs correct_step
@@ -174,53 +144,24 @@ __global__ __launch_bounds__(THREADS) void mosaic_merge_kernel(uint16_t* __restr
     if (tid < TALLY && tally[tid]) atomicAdd(counts + 1 + tid, tally[tid]);
 }
 
-// ------------------------------------------------------------------ merge_patch
-__global__ __launch_bounds__(THREADS) void merge_patch_cells_kernel(const uint32_t* __restrict__ rgba_b, int CH_b, int CW_b, const long long* __restrict__ link_row,
-                                                                    PatchArgs a, uint8_t* __restrict__ tl, uint8_t* __restrict__ tv) {
-    int64_t link[mrg::LINK_WORDS], geom[relo::GEOM_WORDS];  // the same address in every thread: scalar loads
-#pragma unroll
-    for (int i = 0; i < mrg::LINK_WORDS; ++i) link[i] = link_row[i];
-    if (mrg::box_geometry(link, a.y0, a.x0, a.y1, a.x1, a.ox_b, a.oy_b, a.CH_a, a.CW_a, a.ox_a, a.oy_a, a.S, geom) != relo::PATCH_OK) return;  // uniform
-    const int tw = (int)geom[3], th = (int)geom[4], lane = threadIdx.x & (WAVE - 1);
-    const int cell = blockIdx.x * (THREADS / WAVE) + threadIdx.x / WAVE;  // wave-uniform
-    if (cell >= tw * th) return;
-    int64_t g[6];
-    mrg::gather_affine(link, a.ox_b, a.oy_b, g);
-    const int j = cell / tw, i = cell - j * tw;
-    const int64_t X0 = (geom[1] + i) * a.S, Y0 = (geom[2] + j) * a.S;
-    uint32_t sum = 0;
-    bool ok = true;
-    for (int p = lane; p < a.S * a.S; p += WAVE) {
-        uint32_t luma;
-        if (!mrg::patch_pixel(g, X0 + p % a.S, Y0 + p / a.S, a.ox_a, a.oy_a, rgba_b, CH_b, CW_b, &luma)) {
-            ok = false;
-            continue;
-        }
-        sum += luma;
+// ------------------------------------------------------------------ merge_patch: patch_kernels.h's two launches on canvas B
+struct LinkBox {  // the patch of b_box under the link: the link row and box_geometry's arguments
+    static constexpr int ROW_WORDS = mrg::LINK_WORDS;
+    const long long* row;
+    int y0, x0, y1, x1, ox_b, oy_b, CH_a, CW_a, ox_a, oy_a, S;
+    __device__ int geometry(const int64_t* link, int64_t* geom) const {
+        return mrg::box_geometry(link, y0, x0, y1, x1, ox_b, oy_b, CH_a, CW_a, ox_a, oy_a, S, geom);
     }
-    const bool all = __ballot(!ok) == 0ull;
-    sum = wave_sum(sum);
-    if (lane == 0) tl[cell] = all ? (uint8_t)relo::cell_mean(sum, a.S) : (uint8_t)0, tv[cell] = all ? 1 : 0;
-}
-
-__global__ __launch_bounds__(THREADS) void merge_patch_finish_kernel(const long long* __restrict__ link_row, PatchArgs a, const uint8_t* __restrict__ tv,
-                                                                     long long* __restrict__ geom_out) {
-    __shared__ uint32_t part[THREADS / WAVE];
-    int64_t link[mrg::LINK_WORDS], geom[relo::GEOM_WORDS];
-#pragma unroll
-    for (int i = 0; i < mrg::LINK_WORDS; ++i) link[i] = link_row[i];
-    const bool ok = mrg::box_geometry(link, a.y0, a.x0, a.y1, a.x1, a.ox_b, a.oy_b, a.CH_a, a.CW_a, a.ox_a, a.oy_a, a.S, geom) == relo::PATCH_OK;  // uniform
-    uint32_t count = 0;
-    if (ok)
-        for (int c = threadIdx.x; c < (int)(geom[3] * geom[4]); c += THREADS) count += tv[c] == 1 ? 1u : 0u;
-    count = wave_sum(count);
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        geom[5] = ok ? (int64_t)(part[0] + part[1] + part[2] + part[3]) : 0;
-        for (int i = 0; i < relo::GEOM_WORDS; ++i) geom_out[i] = geom[i];
+};
+struct CanvasPatch : LinkBox {  // its pixels: the seen words of B's canvas under the one gather
+    const uint32_t* rgba_b;
+    int CH_b, CW_b;
+    __device__ bool luma(const int64_t* link, int64_t X, int64_t Y, uint32_t* l) const {
+        int64_t g[6];  // uniform, and the same for every pixel of the cell
+        mrg::gather_affine(link, ox_b, oy_b, g);
+        return mrg::patch_pixel(g, X, Y, ox_a, oy_a, rgba_b, CH_b, CW_b, l);
     }
-}
+};
 
 // ------------------------------------------------------------------ link_place: lane 0 runs place_step
 __global__ __launch_bounds__(64) void link_place_kernel(const long long* __restrict__ found_row, const long long* __restrict__ link_row, int max_mean,
@@ -234,19 +175,12 @@ __global__ __launch_bounds__(64) void link_place_kernel(const long long* __restr
     for (int i = 0; i < mrg::OUT_WORDS; ++i) out_row[i] = out[i];
 }
 
-bool side_ok(int v, int lo) { return v >= lo && v <= mos::MAX_SIDE; }
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-bool origin_ok(int ox, int oy) { return ox >= -mos::MAX_SIDE && ox <= mos::MAX_SIDE && oy >= -mos::MAX_SIDE && oy <= mos::MAX_SIDE; }
-
 }  // namespace
 
 int launch_merge_view(const uint32_t* rgba_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b,
                       const long long* link, int Y0, int X0, int WH, int WW, uint8_t* cur, uint8_t* view, uint8_t* valid_a, uint8_t* valid_b, hipStream_t s) {
     FS_REQUIRE(rgba_a && rgba_b && link && cur && view && valid_a && valid_b, "merge_view: null pointer");
-    FS_REQUIRE(side_ok(CH_a, 1) && side_ok(CW_a, 1), "merge_view: canvas A must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH_a, CW_a);
-    FS_REQUIRE(side_ok(CH_b, 1) && side_ok(CW_b, 1), "merge_view: canvas B must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH_b, CW_b);
-    FS_REQUIRE(origin_ok(ox_a, oy_a), "merge_view: origin A must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox_a, oy_a);
-    FS_REQUIRE(origin_ok(ox_b, oy_b), "merge_view: origin B must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox_b, oy_b);
+    FS_TRY(check_canvases("merge_view", CH_a, CW_a, ox_a, oy_a, CH_b, CW_b, ox_b, oy_b));
     FS_REQUIRE(mrg::window_ok(Y0, X0, WH, WW, CH_a, CW_a),
                "merge_view: the window must be whole blocks of 16 (at least one) inside canvas A, got (Y0, X0, WH, WW) = (%d, %d, %d, %d) on %dx%d", Y0, X0, WH, WW,
                CH_a, CW_a);
@@ -263,13 +197,10 @@ int launch_merge_view(const uint32_t* rgba_a, int CH_a, int CW_a, int ox_a, int 
 
 int launch_merge_gate(int32_t* table, int blocks, const uint8_t* valid_a, const uint8_t* valid_b, int H, int W, hipStream_t s) {
     FS_REQUIRE(table && valid_a && valid_b, "merge_gate: null pointer");
-    FS_REQUIRE(side_ok(H, mrg::MIN_SIDE) && side_ok(W, mrg::MIN_SIDE), "merge_gate: the planes must be %d..%d pixels a side, got %dx%d", mrg::MIN_SIDE,
-               mos::MAX_SIDE, H, W);
+    FS_TRY(check_sides("merge_gate", "the planes", mrg::MIN_SIDE, H, W));
     FS_REQUIRE(blocks == (H / 16) * (W / 16), "merge_gate: blocks=%d is not the %d rows of a %dx%d plane's table", blocks, (H / 16) * (W / 16), H, W);
     FS_REQUIRE(aligned(table, 4), "merge_gate: table is not aligned to 4 bytes");
-    merge_gate_kernel<<<dim3((unsigned)blocks), dim3(64), 0, s>>>(table, valid_a, valid_b, H, W);
-    FS_HIP(hipGetLastError());
-    return 0;
+    return launch_gate_rows(table, blocks, valid_a, valid_b, H, W, s);  // refine_ops.hip's gate, with the block's own window in valid_a
 }
 
 int launch_link_correct(const long long* model, long long* link, int Y0, int X0, int WH, int WW, int ox_a, int oy_a, long long* out, hipStream_t s) {
@@ -277,7 +208,7 @@ int launch_link_correct(const long long* model, long long* link, int Y0, int X0,
     FS_REQUIRE(mrg::window_ok(Y0, X0, WH, WW, mos::MAX_SIDE, mos::MAX_SIDE),
                "link_correct: the window must be whole blocks of 16 (at least one) inside a canvas of at most %d pixels a side, got (Y0, X0, WH, WW) = (%d, %d, %d, %d)",
                mos::MAX_SIDE, Y0, X0, WH, WW);
-    FS_REQUIRE(origin_ok(ox_a, oy_a), "link_correct: origin A must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox_a, oy_a);
+    FS_TRY(check_origin("link_correct", "origin A", ox_a, oy_a));
     FS_REQUIRE(aligned(model, 8) && aligned(link, 8) && aligned(out, 8), "link_correct: model, link or out is not aligned to 8 bytes");
     FS_REQUIRE(model != link, "link_correct: model and link are the same memory");
     link_correct_kernel<<<dim3(1), dim3(64), 0, s>>>(model, link, X0, Y0, ox_a, oy_a, out);
@@ -291,10 +222,7 @@ int launch_mosaic_merge(uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_
     FS_REQUIRE(votes_a && votes_b && link && counts, "mosaic_merge: null pointer");
     const bool ortho = rank_a || rgba_a || rank_b || rgba_b;
     FS_REQUIRE(!ortho || (rank_a && rgba_a && rank_b && rgba_b), "mosaic_merge: null pointer (an orthophoto takes rank and rgba of both A and B)");
-    FS_REQUIRE(side_ok(CH_a, 1) && side_ok(CW_a, 1), "mosaic_merge: canvas A must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH_a, CW_a);
-    FS_REQUIRE(side_ok(CH_b, 1) && side_ok(CW_b, 1), "mosaic_merge: canvas B must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH_b, CW_b);
-    FS_REQUIRE(origin_ok(ox_a, oy_a), "mosaic_merge: origin A must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox_a, oy_a);
-    FS_REQUIRE(origin_ok(ox_b, oy_b), "mosaic_merge: origin B must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox_b, oy_b);
+    FS_TRY(check_canvases("mosaic_merge", CH_a, CW_a, ox_a, oy_a, CH_b, CW_b, ox_b, oy_b));
     FS_REQUIRE(K >= 1 && K <= mos::MAX_CLASSES, "mosaic_merge: classes=%d out of range (1..%d)", K, mos::MAX_CLASSES);
     FS_REQUIRE(mode == orth::MODE_CENTRE || mode == orth::MODE_LATEST, "mosaic_merge: mode must be 0 (centre) or 1 (latest), got mode=%d", mode);
     FS_REQUIRE(ordinal_offset != orth::ORDINAL_NONE, "mosaic_merge: ordinal_offset=%u is reserved", ordinal_offset);
@@ -319,29 +247,24 @@ int launch_mosaic_merge(uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_
 int launch_merge_patch(const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int oy_b, const long long* link, int CH_a, int CW_a, int ox_a, int oy_a, int S, int y0,
                        int x0, int y1, int x1, uint8_t* tl, uint8_t* tv, long long* geom, hipStream_t s) {
     FS_REQUIRE(rgba_b && link && tl && tv && geom, "merge_patch: null pointer");
-    FS_REQUIRE(side_ok(CH_a, 1) && side_ok(CW_a, 1), "merge_patch: canvas A must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH_a, CW_a);
-    FS_REQUIRE(side_ok(CH_b, 1) && side_ok(CW_b, 1), "merge_patch: canvas B must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH_b, CW_b);
-    FS_REQUIRE(origin_ok(ox_a, oy_a), "merge_patch: origin A must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox_a, oy_a);
-    FS_REQUIRE(origin_ok(ox_b, oy_b), "merge_patch: origin B must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox_b, oy_b);
-    FS_REQUIRE(relo::scale_ok(S), "merge_patch: the cell edge must be 4, 8 or 16, got S=%d", S);
-    FS_REQUIRE(CH_a / S >= 1 && CW_a / S >= 1, "merge_patch: a %dx%d canvas A has no cell of S=%d", CH_a, CW_a, S);
+    FS_TRY(check_canvases("merge_patch", CH_a, CW_a, ox_a, oy_a, CH_b, CW_b, ox_b, oy_b));
+    FS_TRY(check_cell_edge("merge_patch", S));
+    FS_TRY(check_has_cell("merge_patch", "canvas A", CH_a, CW_a, S));
     FS_REQUIRE(mrg::box_ok(y0, x0, y1, x1, CH_b, CW_b), "merge_patch: b_box must be a non-empty (y0, x0, y1, x1) inside canvas B, got (%d, %d, %d, %d) on %dx%d", y0,
                x0, y1, x1, CH_b, CW_b);
     FS_REQUIRE(aligned(rgba_b, 4), "merge_patch: rgba_b is not aligned to 4 bytes");
     FS_REQUIRE(aligned(link, 8) && aligned(geom, 8), "merge_patch: link or geom is not aligned to 8 bytes");
-    const PatchArgs a = {y0, x0, y1, x1, ox_b, oy_b, CH_a, CW_a, ox_a, oy_a, S};
-    const int64_t cells = (int64_t)(CH_a / S) * (CW_a / S);  // a patch that passes has no more cells than A's coarse canvas, and at most 65536
-    const dim3 grid((unsigned)cdiv64(cells < relo::MAX_PATCH_CELLS ? cells : relo::MAX_PATCH_CELLS, THREADS / WAVE));
-    merge_patch_cells_kernel<<<grid, THREADS, 0, s>>>(rgba_b, CH_b, CW_b, link, a, tl, tv);
+    const LinkBox box = {link, y0, x0, y1, x1, ox_b, oy_b, CH_a, CW_a, ox_a, oy_a, S};
+    launch_patch_cells(CanvasPatch{box, rgba_b, CH_b, CW_b}, CH_a, CW_a, tl, tv, s);
     FS_HIP(hipGetLastError());
-    merge_patch_finish_kernel<<<1, THREADS, 0, s>>>(link, a, tv, geom);
+    patch_finish_kernel<<<1, PATCH_THREADS, 0, s>>>(box, tv, geom);
     FS_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_link_place(const long long* found, const long long* link, int S, int max_mean, int ratio_permille, long long* cand, long long* out, hipStream_t s) {
     FS_REQUIRE(found && link && cand && out, "link_place: null pointer");
-    FS_REQUIRE(relo::scale_ok(S), "link_place: the cell edge must be 4, 8 or 16, got S=%d", S);
+    FS_TRY(check_cell_edge("link_place", S));
     FS_REQUIRE(max_mean >= 0 && max_mean <= 255, "link_place: max_mean must be 0..255, got %d", max_mean);
     FS_REQUIRE(ratio_permille >= 1 && ratio_permille <= 1000, "link_place: ratio_permille must be 1..1000, got %d", ratio_permille);
     FS_REQUIRE(aligned(found, 8) && aligned(link, 8) && aligned(cand, 8) && aligned(out, 8), "link_place: found, link, cand or out is not aligned to 8 bytes");

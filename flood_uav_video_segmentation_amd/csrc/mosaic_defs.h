@@ -47,8 +47,8 @@ enum Phase { PHASE_FRESH = 0, PHASE_TRACKING = 1, PHASE_LOST = 2 };
 //   compose(inv, from_anchor):  linear 2^21 x 2^24 = 2^45, two 2^46;          translation 2^21 x 2^40 = 2^61, two 2^62, + 2^36 < 2^63
 //   a canvas pixel:             |X - ox| <= 2^15 (X < 2^14, |ox| <= 2^14), so |AX| = |(2 (X - ox) + 1) << 19| < 2^36;
 //                               2^24 x 2^36 = 2^60, two 2^61, + 2^19 and the translation 2^40 < 2^62
-//   a frame corner:             to_anchor's linear entry x (W <= 2^14 whole pixels) = 2^38, two 2^39, + 2^34 and ox ONE < 2^40
-//   a tile corner (touches):    from_anchor's linear entry x (2^15 whole pixels) = 2^39, two 2^40, + 2^40 < 2^42
+//   a rectangle's corner (corner_box, the widest caller): linear entry < 2^24 x (|corner| <= 2^15 whole pixels) = 2^39, two 2^40,
+//                               + a translation below 2^41 < 2^42; a caller's origin (|ox| ONE <= 2^34) on top stays below 2^43
 // The rounding sums of gm_solve: |p|, |q| < 2^10 and at most 2^20 rows, so every sum is below 2^40 and exact in float64.
 constexpr int64_t PAIR_LINEAR_MAX = 2 * ONE;
 constexpr int64_t PAIR_SHIFT_LIMIT = ((int64_t)1 << 16) * ONE;
@@ -83,6 +83,17 @@ FS_MOS_HD bool pair_in_bounds(const int64_t* fwd, const int64_t* inv) {
 FS_MOS_HD bool pose_in_bounds(const int64_t* to_anchor, const int64_t* from_anchor) {
     return linear_within(to_anchor, POSE_LINEAR_LIMIT - 1) && linear_within(from_anchor, POSE_LINEAR_LIMIT - 1) && shift_below(to_anchor, POSE_SHIFT_LIMIT) &&
            shift_below(from_anchor, POSE_BACK_SHIFT_LIMIT);
+}
+
+// ---- THE BOX RULE: the bounding box, in Q20, of the four corners of the whole-pixel rectangle [x0, x1] x [y0, y1] under affine m.  A
+// whole pixel times a Q20 entry needs no rounding, so the box is exact; the affine image of the rectangle lies inside it.  Adding a whole
+// origin (ox ONE) to a minimum or a maximum is exact too, so origins stay with the callers.  Products: see THE BOUNDS above; every caller
+// says in one line why its operands are inside them.  A corner's coordinate m0 x + m1 y + m2 is a term in x plus a term in y, so its
+// extremes over the four corners are the sums of the terms' extremes: the corners' own eight products, and no corner is enumerated.
+FS_MOS_HD void corner_box(const int64_t* m, int64_t x0, int64_t y0, int64_t x1, int64_t y1, int64_t* lo_x, int64_t* hi_x, int64_t* lo_y, int64_t* hi_y) {
+    const int64_t ax0 = m[0] * x0, ax1 = m[0] * x1, ay0 = m[1] * y0, ay1 = m[1] * y1, bx0 = m[3] * x0, bx1 = m[3] * x1, by0 = m[4] * y0, by1 = m[4] * y1;
+    *lo_x = (ax0 < ax1 ? ax0 : ax1) + (ay0 < ay1 ? ay0 : ay1) + m[2], *hi_x = (ax0 < ax1 ? ax1 : ax0) + (ay0 < ay1 ? ay1 : ay0) + m[2];
+    *lo_y = (bx0 < bx1 ? bx0 : bx1) + (by0 < by1 ? by0 : by1) + m[5], *hi_y = (bx0 < bx1 ? bx1 : bx0) + (by0 < by1 ? by1 : by0) + m[5];
 }
 
 // ---- a table row.  Usable: not void, the block centre inside the frame (the matcher writes no other), |dx|, |dy| <= 32; the mask test is
@@ -251,15 +262,11 @@ FS_MOS_HD void write_model(int64_t* row, const int64_t* fwd, const int64_t* inv,
 // ---- the pose chain: one frame.  state: to_anchor (6), from_anchor (6), last_fwd (6), last_inv (6), phase, frames seen, frames lost, the
 // current bridge run, 4 spare words (zero).  Everything read from `model` and `state` is tested before use: a status that is none of
 // 0..3 counts as 3, an ok model out of the pair bounds counts as 3, a phase that is none of 0..2 counts as lost.
+// frame_clipped: a corner outside the canvas [0, CW] x [0, CH] is an edge of the corners' box outside it; pose_in_bounds held to_anchor.
 FS_MOS_HD bool frame_clipped(const int64_t* to_anchor, int H, int W, int CH, int CW, int ox, int oy) {
-    bool out = false;
-    for (int c = 0; c < 4; ++c) {
-        const int64_t x = (c & 1) ? W : 0, y = (c & 2) ? H : 0;  // the frame's corners in continuous pixel coordinates
-        const int64_t cx = to_anchor[0] * x + to_anchor[1] * y + to_anchor[2] + (int64_t)ox * ONE;  // exact: x ONE needs no rounding
-        const int64_t cy = to_anchor[3] * x + to_anchor[4] * y + to_anchor[5] + (int64_t)oy * ONE;
-        out = out || cx < 0 || cy < 0 || cx > (int64_t)CW * ONE || cy > (int64_t)CH * ONE;
-    }
-    return out;
+    int64_t lo_x, hi_x, lo_y, hi_y;
+    corner_box(to_anchor, 0, 0, W, H, &lo_x, &hi_x, &lo_y, &hi_y);
+    return lo_x + (int64_t)ox * ONE < 0 || lo_y + (int64_t)oy * ONE < 0 || hi_x + (int64_t)ox * ONE > (int64_t)CW * ONE || hi_y + (int64_t)oy * ONE > (int64_t)CH * ONE;
 }
 FS_MOS_HD void pose_step(const int64_t* model, int64_t* state, int64_t* pose, int H, int W, int CH, int CW, int ox, int oy, int max_bridge) {
     int64_t* to_anchor = state;
@@ -324,15 +331,11 @@ FS_MOS_HD void source_pixel(const int64_t* from_anchor, int64_t AX, int64_t AY, 
     *x = (rshr(from_anchor[0] * AX + from_anchor[1] * AY) + from_anchor[2]) >> FRAC;
     *y = (rshr(from_anchor[3] * AX + from_anchor[4] * AY) + from_anchor[5]) >> FRAC;
 }
-// can frame `from_anchor` touch the canvas rectangle [X0, X1) x [Y0, Y1)?  The affine image of a rectangle lies inside the bounding box of
-// its corners; a pixel's rounded source lies within one Q20 unit of the exact image of its centre, and one whole pixel is allowed for.
+// can frame `from_anchor` touch the canvas rectangle [X0, X1) x [Y0, Y1)?  Its image lies inside corner_box's box (|X - ox| <= 2^15, a
+// translation below 2^41); a pixel's rounded source lies within one Q20 unit of its centre's exact image: one whole pixel is allowed for.
 FS_MOS_HD bool touches(const int64_t* from_anchor, int X0, int Y0, int X1, int Y1, int ox, int oy, int H, int W) {
-    int64_t lo_x = INT64_MAX, hi_x = INT64_MIN, lo_y = INT64_MAX, hi_y = INT64_MIN;
-    for (int c = 0; c < 4; ++c) {
-        const int64_t ax = (int64_t)((c & 1) ? X1 : X0) - ox, ay = (int64_t)((c & 2) ? Y1 : Y0) - oy;  // whole pixels: exact in Q20
-        const int64_t x = from_anchor[0] * ax + from_anchor[1] * ay + from_anchor[2], y = from_anchor[3] * ax + from_anchor[4] * ay + from_anchor[5];
-        lo_x = x < lo_x ? x : lo_x, hi_x = x > hi_x ? x : hi_x, lo_y = y < lo_y ? y : lo_y, hi_y = y > hi_y ? y : hi_y;
-    }
+    int64_t lo_x, hi_x, lo_y, hi_y;
+    corner_box(from_anchor, (int64_t)X0 - ox, (int64_t)Y0 - oy, (int64_t)X1 - ox, (int64_t)Y1 - oy, &lo_x, &hi_x, &lo_y, &hi_y);
     return hi_x >= -ONE && lo_x <= (int64_t)(W + 1) * ONE && hi_y >= -ONE && lo_y <= (int64_t)(H + 1) * ONE;
 }
 FS_MOS_HD uint16_t vote_add(uint16_t v, uint32_t more) {  // `more` single votes, each saturating at 65535

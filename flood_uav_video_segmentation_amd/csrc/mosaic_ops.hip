@@ -17,6 +17,7 @@
 // an index or an operand of a product is tested first (mask ids, a row's block centre and vector, a model's and a pose's status and
 // magnitudes, the state's phase).
 #include "kernels.h"
+#include "map_checks.h"
 #include "mosaic_defs.h"
 
 namespace fs {
@@ -295,17 +296,14 @@ __global__ __launch_bounds__(RES_THREADS) void mosaic_resolve_kernel(const uint1
     if (tid < 2 * K && hist[tid >> 1][tid & 1]) atomicAdd(totals + tid, (unsigned long long)hist[tid >> 1][tid & 1]);
 }
 
-bool side_ok(int v, int lo) { return v >= lo && v <= mos::MAX_SIDE; }
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
 }  // namespace
 
 int launch_global_motion(const int32_t* tables, const int32_t* pair_stats, const uint8_t* mask, uint32_t exclude_set, int n, int FH, int FW, int H, int W,
                          int rounds, long long tol_q20, int min_inliers, long long* model, hipStream_t s) {
     FS_REQUIRE(tables && model, "global_motion: null pointer");
     FS_REQUIRE(n >= 1 && n <= mos::MAX_FRAMES, "global_motion: n must be 1..%d frame pairs, got n=%d", mos::MAX_FRAMES, n);
-    FS_REQUIRE(side_ok(FH, 16) && side_ok(FW, 16), "global_motion: the frame must be 16..%d pixels a side, got %dx%d", mos::MAX_SIDE, FH, FW);
-    FS_REQUIRE(side_ok(H, 1) && side_ok(W, 1), "global_motion: the mask must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, H, W);
+    FS_TRY(check_sides("global_motion", "the frame", 16, FH, FW));
+    FS_TRY(check_sides("global_motion", "the mask", 1, H, W));
     FS_REQUIRE(rounds >= 0 && rounds <= mos::MAX_ROUNDS, "global_motion: rounds=%d out of range (0..%d)", rounds, mos::MAX_ROUNDS);
     FS_REQUIRE(tol_q20 >= 0 && tol_q20 <= mos::MAX_TOL_Q20, "global_motion: tol_q20=%lld out of range (0..%lld: 64 pixels)", tol_q20, (long long)mos::MAX_TOL_Q20);
     FS_REQUIRE(min_inliers >= 3 && min_inliers <= (1 << 20), "global_motion: min_inliers=%d out of range (3..%d)", min_inliers, 1 << 20);
@@ -322,10 +320,7 @@ int launch_pose_chain(const long long* model, long long* state, long long* poses
                       hipStream_t s) {
     FS_REQUIRE(model && state && poses, "pose_chain: null pointer");
     FS_REQUIRE(n >= 1 && n <= mos::MAX_FRAMES, "pose_chain: n must be 1..%d frames, got n=%d", mos::MAX_FRAMES, n);
-    FS_REQUIRE(side_ok(H, 1) && side_ok(W, 1), "pose_chain: the mask must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, H, W);
-    FS_REQUIRE(side_ok(CH, 1) && side_ok(CW, 1), "pose_chain: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(ox >= -mos::MAX_SIDE && ox <= mos::MAX_SIDE && oy >= -mos::MAX_SIDE && oy <= mos::MAX_SIDE,
-               "pose_chain: the origin must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox, oy);
+    FS_TRY(check_mask_on_canvas("pose_chain", 1, H, W, CH, CW, ox, oy));
     FS_REQUIRE(max_bridge >= 0 && max_bridge <= mos::MAX_FRAMES, "pose_chain: max_bridge=%d out of range (0..%d)", max_bridge, mos::MAX_FRAMES);
     FS_REQUIRE(aligned(model, 8) && aligned(state, 8) && aligned(poses, 8), "pose_chain: model, state or poses is not aligned to 8 bytes");
     hipLaunchKernelGGL(pose_chain_kernel, dim3(1), dim3(64), 0, s, model, state, poses, n, H, W, CH, CW, ox, oy, max_bridge);
@@ -337,11 +332,10 @@ int launch_mosaic_accumulate(const uint8_t* mask, const long long* poses, int n,
                              hipStream_t s) {
     FS_REQUIRE(mask && poses && votes, "mosaic_accumulate: null pointer");
     FS_REQUIRE(n >= 1 && n <= mos::MAX_FRAMES, "mosaic_accumulate: n must be 1..%d frames, got n=%d", mos::MAX_FRAMES, n);
-    FS_REQUIRE(side_ok(H, 1) && side_ok(W, 1), "mosaic_accumulate: the mask must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, H, W);
+    FS_TRY(check_sides("mosaic_accumulate", "the mask", 1, H, W));
     FS_REQUIRE(K >= 1 && K <= mos::MAX_CLASSES, "mosaic_accumulate: classes=%d out of range (1..%d)", K, mos::MAX_CLASSES);
-    FS_REQUIRE(side_ok(CH, 1) && side_ok(CW, 1), "mosaic_accumulate: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(ox >= -mos::MAX_SIDE && ox <= mos::MAX_SIDE && oy >= -mos::MAX_SIDE && oy <= mos::MAX_SIDE,
-               "mosaic_accumulate: the origin must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox, oy);
+    FS_TRY(check_sides("mosaic_accumulate", "the canvas", 1, CH, CW));
+    FS_TRY(check_origin("mosaic_accumulate", "the origin", ox, oy));
     FS_REQUIRE(aligned(poses, 8), "mosaic_accumulate: poses is not aligned to 8 bytes");
     FS_REQUIRE(aligned(votes, 2), "mosaic_accumulate: votes is not aligned to 2 bytes");
     hipLaunchKernelGGL(mosaic_accumulate_kernel, dim3((unsigned)cdiv(CW, TILE_W), (unsigned)cdiv(CH, TILE_H)), dim3(ACC_THREADS), 0, s, mask, poses, n, H, W,
@@ -353,7 +347,7 @@ int launch_mosaic_accumulate(const uint8_t* mask, const long long* poses, int n,
 int launch_mosaic_resolve(const uint16_t* votes, int K, int CH, int CW, uint8_t* cls, uint8_t* conf, uint32_t* seen, long long* totals, hipStream_t s) {
     FS_REQUIRE(votes && cls && conf && seen && totals, "mosaic_resolve: null pointer");
     FS_REQUIRE(K >= 1 && K <= mos::MAX_CLASSES, "mosaic_resolve: classes=%d out of range (1..%d)", K, mos::MAX_CLASSES);
-    FS_REQUIRE(side_ok(CH, 1) && side_ok(CW, 1), "mosaic_resolve: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
+    FS_TRY(check_sides("mosaic_resolve", "the canvas", 1, CH, CW));
     FS_REQUIRE(aligned(votes, 2), "mosaic_resolve: votes is not aligned to 2 bytes");
     FS_REQUIRE(aligned(seen, 4), "mosaic_resolve: seen is not aligned to 4 bytes");
     FS_REQUIRE(aligned(totals, 8), "mosaic_resolve: totals is not aligned to 8 bytes");

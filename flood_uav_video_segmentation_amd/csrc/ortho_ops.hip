@@ -16,6 +16,7 @@
 #include "egress_px.h"
 #include "ingest_src.h"
 #include "kernels.h"
+#include "map_checks.h"
 #include "ortho_defs.h"
 
 namespace fs {
@@ -132,24 +133,14 @@ __global__ __launch_bounds__(THREADS) void ortho_compose_kernel(const uint32_t* 
     }
 }
 
-bool side_ok(int v) { return v >= 1 && v <= mos::MAX_SIDE; }
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
 }  // namespace
 
 int launch_ortho_accumulate(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW,
                             const long long* pose, uint32_t ordinal, int H, int W, int mode, int CH, int CW, int ox, int oy, unsigned long long* rank,
                             uint32_t* rgba, hipStream_t s) {
     FS_REQUIRE(frame && pose && rank && rgba, "ortho_accumulate: null pointer");
-    FS_REQUIRE(format >= 0 && format <= 2, "ortho_accumulate: format must be 0 (RGB24), 1 (NV12) or 2 (I420), got %d", format);
-    FS_REQUIRE(matrix == 0 || matrix == 1, "ortho_accumulate: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    FS_REQUIRE(full_range == 0 || full_range == 1, "ortho_accumulate: range must be 0 (limited) or 1 (full), got %d", full_range);
-    FS_REQUIRE(format == 0 || (u && (format != 2 || v)), "ortho_accumulate: null chroma pointer for a YUV format");
-    FS_REQUIRE(side_ok(FH) && side_ok(FW), "ortho_accumulate: the frame must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, FH, FW);
-    FS_REQUIRE(side_ok(H) && side_ok(W), "ortho_accumulate: the mask must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, H, W);
-    FS_REQUIRE(side_ok(CH) && side_ok(CW), "ortho_accumulate: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(ox >= -mos::MAX_SIDE && ox <= mos::MAX_SIDE && oy >= -mos::MAX_SIDE && oy <= mos::MAX_SIDE,
-               "ortho_accumulate: the origin must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox, oy);
+    FS_TRY(check_frame_source("ortho_accumulate", u, v, format, matrix, full_range, FH, FW));
+    FS_TRY(check_mask_on_canvas("ortho_accumulate", 1, H, W, CH, CW, ox, oy));
     FS_REQUIRE(mode == orth::MODE_CENTRE || mode == orth::MODE_LATEST, "ortho_accumulate: mode must be 0 (centre) or 1 (latest), got mode=%d", mode);
     FS_REQUIRE(ordinal != orth::ORDINAL_NONE, "ortho_accumulate: ordinal=%u is reserved", ordinal);
     FS_REQUIRE(aligned(pose, 8), "ortho_accumulate: pose is not aligned to 8 bytes");
@@ -168,7 +159,7 @@ int launch_ortho_compose(const uint32_t* rgba, const uint8_t* cls, const uint8_t
                          uint8_t* out, hipStream_t s) {
     FS_REQUIRE(rgba && out, "ortho_compose: null pointer");
     FS_REQUIRE(!cls || palette, "ortho_compose: null pointer (a class plane without a palette)");
-    FS_REQUIRE(side_ok(CH) && side_ok(CW), "ortho_compose: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
+    FS_TRY(check_sides("ortho_compose", "the canvas", 1, CH, CW));
     FS_REQUIRE(K >= 1 && K <= 256, "ortho_compose: palette must hold 1..256 classes, got %d", K);
     const int edge_bits = K < 32 ? K : 32;
     FS_REQUIRE(edge_bits == 32 || (edge_set >> edge_bits) == 0u, "ortho_compose: edge_set=0x%x names a class at or above %d", edge_set, edge_bits);

@@ -68,6 +68,10 @@ FS_MOS_HD bool gate_keeps(const int32_t* row, const uint8_t* valid, int H, int W
 // to_anchor o fwd).  Only words 0..11 of the state (the two poses) and words 0..11 and 13 of the pose row are ever written, and only
 // with status 0.  Everything read is device memory and is tested before use; the products of compose are inside mosaic_defs.h's
 // bounds because pose_in_bounds and pair_in_bounds are tested first, exactly as pose_step does.
+// the report row of pose_correct and merge_defs.h's link_correct: status, then the fit's usable rows, inliers, rounds and translation
+FS_MOS_HD void fit_report(int status, const int64_t* model, int64_t* out) {
+    out[0] = status, out[1] = model[13], out[2] = model[14], out[3] = model[15], out[4] = model[2], out[5] = model[5], out[6] = 0, out[7] = 0;
+}
 FS_MOS_HD int refine_step(const int64_t* model, int64_t* state, int64_t* pose, int64_t* out, int H, int W, int CH, int CW, int ox, int oy) {
     int status = REFINE_OK;
     bool same = true;
@@ -89,7 +93,7 @@ FS_MOS_HD int refine_step(const int64_t* model, int64_t* state, int64_t* pose, i
             pose[13] = mos::frame_clipped(to_next, H, W, CH, CW, ox, oy) ? 1 : 0;
         }
     }
-    out[0] = status, out[1] = model[13], out[2] = model[14], out[3] = model[15], out[4] = model[2], out[5] = model[5], out[6] = 0, out[7] = 0;
+    fit_report(status, model, out);
     return status;
 }
 

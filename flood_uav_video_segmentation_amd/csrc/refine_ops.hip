@@ -8,13 +8,15 @@
 //                 where that pixel is inside the canvas.  Three uint8 planes, written whole: dwords where W % 4 == 0 and the planes are
 //                 aligned, bytes otherwise.
 //   map_gate      one wave per table row; the 256 valid bytes under the winner's window, four per lane, one ballot; a row that does not
-//                 survive is overwritten with the void row by lanes 0..6.
+//                 survive is overwritten with the void row by lanes 0..6.  The same kernel with OWN set is merge_ops.hip's merge_gate.
+// The argument checks that the map family shares are map_checks.h's.
 //   pose_correct  one wave; the rows go through LDS together, lane 0 runs refine_step.
 // Every loop bound follows from the arguments; nothing is allocated, synchronised or read back on the host; no atomics.  Compile with
 // -ffp-contract=off (csrc/Makefile): the resize must round as ingest's, egress's and ortho's do.
 #include "egress_px.h"
 #include "ingest_src.h"
 #include "kernels.h"
+#include "map_checks.h"
 #include "refine_defs.h"
 
 namespace fs {
@@ -91,18 +93,25 @@ void view_mode(const IngestSrc& s, const long long* pose, uint32_t ordinal, int 
         view_width<YUV, 0>(wide, grid, st, s, pose, ordinal, H, W, CH, CW, ox, oy, sy, sx, rank, rgba, min_age, cur, view, valid);
 }
 
-// ------------------------------------------------------------------ map_gate: one wave per row
-__global__ __launch_bounds__(64) void map_gate_kernel(int32_t* __restrict__ table, const uint8_t* __restrict__ valid, int H, int W) {
-    int32_t* row = table + (size_t)blockIdx.x * refn::ROW_WORDS;
-    const int lane = threadIdx.x;
+// ------------------------------------------------------------------ map_gate and merge_gate: one wave per row.  OWN (merge_gate): the
+// block's own 16 x 16 window, at (16 (index % wb), 16 (index / wb)) and so inside the plane, must be valid in `own` as well.
+__device__ __forceinline__ bool window_valid(const uint8_t* plane, int64_t x0, int64_t y0, int W, int lane) {
+    const uint8_t* p = plane + (size_t)(y0 + (lane >> 2)) * W + (size_t)(x0 + (lane & 3) * 4);  // lane: row lane / 4, four bytes at column (lane % 4) * 4
+    return p[0] == 1 && p[1] == 1 && p[2] == 1 && p[3] == 1;
+}
+template <bool OWN>
+__global__ __launch_bounds__(64) void gate_kernel(int32_t* __restrict__ table, const uint8_t* __restrict__ own, const uint8_t* __restrict__ valid, int H, int W) {
+    const int index = blockIdx.x, lane = threadIdx.x;
+    int32_t* row = table + (size_t)index * refn::ROW_WORDS;
     int32_t r[refn::ROW_WORDS];  // a uniform address: every lane holds the row before any lane writes it
 #pragma unroll
     for (int i = 0; i < refn::ROW_WORDS; ++i) r[i] = row[i];
     int64_t x0, y0;
-    bool ok = refn::window_in_plane(r, H, W, &x0, &y0);  // uniform: in 64 bits, before any byte of the plane is read
+    bool ok = refn::window_in_plane(r, H, W, &x0, &y0);  // uniform: in 64 bits, before any byte of a plane is read
     if (ok) {
-        const uint8_t* p = valid + (size_t)(y0 + (lane >> 2)) * W + (size_t)(x0 + (lane & 3) * 4);  // lane: row lane / 4, four bytes at column (lane % 4) * 4
-        ok = p[0] == 1 && p[1] == 1 && p[2] == 1 && p[3] == 1;
+        ok = window_valid(valid, x0, y0, W, lane);
+        constexpr int BLOCK = 2 * refn::HALF_BLOCK;
+        if (OWN) ok = ok && window_valid(own, (index % (W / BLOCK)) * BLOCK, (index / (W / BLOCK)) * BLOCK, W, lane);
     }
     const bool keep = __ballot(ok) == ~0ull;
     if (!keep && lane < refn::ROW_WORDS) row[lane] = refn::void_word(lane);
@@ -131,25 +140,14 @@ __global__ __launch_bounds__(64) void pose_correct_kernel(const long long* __res
     if (lane < refn::OUT_WORDS) out[lane] = so[lane];
 }
 
-bool side_ok(int v, int lo) { return v >= lo && v <= mos::MAX_SIDE; }
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-bool origin_ok(int ox, int oy) { return ox >= -mos::MAX_SIDE && ox <= mos::MAX_SIDE && oy >= -mos::MAX_SIDE && oy <= mos::MAX_SIDE; }
-
 }  // namespace
 
 int launch_map_view(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const long long* pose,
                     uint32_t ordinal, int H, int W, int CH, int CW, int ox, int oy, const unsigned long long* rank, const uint32_t* rgba, int min_age,
                     uint8_t* cur, uint8_t* view, uint8_t* valid, hipStream_t s) {
     FS_REQUIRE(frame && pose && rank && rgba && cur && view && valid, "map_view: null pointer");
-    FS_REQUIRE(format >= 0 && format <= 2, "map_view: format must be 0 (RGB24), 1 (NV12) or 2 (I420), got %d", format);
-    FS_REQUIRE(matrix == 0 || matrix == 1, "map_view: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    FS_REQUIRE(full_range == 0 || full_range == 1, "map_view: range must be 0 (limited) or 1 (full), got %d", full_range);
-    FS_REQUIRE(format == 0 || (u && (format != 2 || v)), "map_view: null chroma pointer for a YUV format");
-    FS_REQUIRE(side_ok(FH, 1) && side_ok(FW, 1), "map_view: the frame must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, FH, FW);
-    FS_REQUIRE(side_ok(H, refn::MIN_SIDE) && side_ok(W, refn::MIN_SIDE), "map_view: the mask must be %d..%d pixels a side, got %dx%d", refn::MIN_SIDE,
-               mos::MAX_SIDE, H, W);
-    FS_REQUIRE(side_ok(CH, 1) && side_ok(CW, 1), "map_view: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(origin_ok(ox, oy), "map_view: the origin must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox, oy);
+    FS_TRY(check_frame_source("map_view", u, v, format, matrix, full_range, FH, FW));
+    FS_TRY(check_mask_on_canvas("map_view", refn::MIN_SIDE, H, W, CH, CW, ox, oy));
     FS_REQUIRE(ordinal != orth::ORDINAL_NONE, "map_view: ordinal=%u is reserved", ordinal);
     FS_REQUIRE(min_age >= 0, "map_view: min_age=%d is negative", min_age);
     FS_REQUIRE(aligned(pose, 8), "map_view: pose is not aligned to 8 bytes");
@@ -165,22 +163,27 @@ int launch_map_view(const uint8_t* frame, const uint8_t* u, const uint8_t* v, in
     return 0;
 }
 
-int launch_map_gate(int32_t* table, int blocks, const uint8_t* valid, int H, int W, hipStream_t s) {
-    FS_REQUIRE(table && valid, "map_gate: null pointer");
-    FS_REQUIRE(side_ok(H, refn::MIN_SIDE) && side_ok(W, refn::MIN_SIDE), "map_gate: the plane must be %d..%d pixels a side, got %dx%d", refn::MIN_SIDE,
-               mos::MAX_SIDE, H, W);
-    FS_REQUIRE(blocks == (H / 16) * (W / 16), "map_gate: blocks=%d is not the %d rows of a %dx%d plane's table", blocks, (H / 16) * (W / 16), H, W);
-    FS_REQUIRE(aligned(table, 4), "map_gate: table is not aligned to 4 bytes");
-    map_gate_kernel<<<dim3((unsigned)blocks), dim3(64), 0, s>>>(table, valid, H, W);
+// the launch behind map_gate (own == nullptr) and merge_ops.hip's merge_gate; the arguments are the caller's to check
+int launch_gate_rows(int32_t* table, int blocks, const uint8_t* own, const uint8_t* valid, int H, int W, hipStream_t s) {
+    if (own)
+        gate_kernel<true><<<dim3((unsigned)blocks), dim3(64), 0, s>>>(table, own, valid, H, W);
+    else
+        gate_kernel<false><<<dim3((unsigned)blocks), dim3(64), 0, s>>>(table, own, valid, H, W);
     FS_HIP(hipGetLastError());
     return 0;
 }
 
+int launch_map_gate(int32_t* table, int blocks, const uint8_t* valid, int H, int W, hipStream_t s) {
+    FS_REQUIRE(table && valid, "map_gate: null pointer");
+    FS_TRY(check_sides("map_gate", "the plane", refn::MIN_SIDE, H, W));
+    FS_REQUIRE(blocks == (H / 16) * (W / 16), "map_gate: blocks=%d is not the %d rows of a %dx%d plane's table", blocks, (H / 16) * (W / 16), H, W);
+    FS_REQUIRE(aligned(table, 4), "map_gate: table is not aligned to 4 bytes");
+    return launch_gate_rows(table, blocks, nullptr, valid, H, W, s);
+}
+
 int launch_pose_correct(const long long* model, long long* state, long long* pose, int H, int W, int CH, int CW, int ox, int oy, long long* out, hipStream_t s) {
     FS_REQUIRE(model && state && pose && out, "pose_correct: null pointer");
-    FS_REQUIRE(side_ok(H, 1) && side_ok(W, 1), "pose_correct: the mask must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, H, W);
-    FS_REQUIRE(side_ok(CH, 1) && side_ok(CW, 1), "pose_correct: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(origin_ok(ox, oy), "pose_correct: the origin must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox, oy);
+    FS_TRY(check_mask_on_canvas("pose_correct", 1, H, W, CH, CW, ox, oy));
     FS_REQUIRE(aligned(model, 8) && aligned(state, 8) && aligned(pose, 8) && aligned(out, 8), "pose_correct: model, state, pose or out is not aligned to 8 bytes");
     pose_correct_kernel<<<dim3(1), dim3(64), 0, s>>>(model, state, pose, H, W, CH, CW, ox, oy, out);
     FS_HIP(hipGetLastError());

@@ -40,34 +40,38 @@ FS_MOS_HD void coarse_cell(const uint32_t* rgba, int CW, int cx, int cy, int S, 
     *luma = all ? (uint8_t)cell_mean(sum, S) : (uint8_t)0, *valid = all ? 1 : 0;
 }
 
-// ---- map_patch: the geometry of the patch from the LOST state's poses.  Everything read from the state is tested before any product:
-//   the phase is PHASE_LOST; pose_in_bounds: |linear entry| < 2^24, |to_anchor translation| < 2^34, |from_anchor translation| < 2^40.
-//   a frame corner (frame_clipped's rule): 2^24 x (W <= 2^14) = 2^38, two of them 2^39, + 2^34 + |ox| ONE (2^34) < 2^40; as a canvas
-//   pixel below 2^20 in magnitude, as a cell below 2^18: tw, th < 2^19, tw th < 2^38 in 64 bits.
-//   AFTER the patch is known to be no wider than the coarse canvas (tw S <= CW <= 2^14): corner (0, 0) lies at to_anchor's translation,
-//   below 2^14 pixels from the anchor, and every pixel of the patch within 2^14 + 2 S of it, so |X - ox| < 2^15 + 32 and
-//   |anchor_coord| < 2^36 + 2^25: source_pixel's products stay below 2^24 x 2^37 = 2^61, two of them 2^62, inside 63 bits, and the
-//   rounded sum below 2^42, + 2^40.
-FS_MOS_HD int64_t floor_cell(int64_t px, int S) { return px >> scale_shift(S); }  // arithmetic shift: floor for negative pixels too
-FS_MOS_HD int patch_geometry(const int64_t* state, int H, int W, int CH, int CW, int ox, int oy, int S, int64_t* geom) {
-    for (int i = 0; i < GEOM_WORDS; ++i) geom[i] = 0;
-    if (state[24] != mos::PHASE_LOST) return (int)(geom[0] = PATCH_NOT_LOST);
-    if (!mos::pose_in_bounds(state, state + 6)) return (int)(geom[0] = PATCH_OUT_OF_BOUNDS);
-    int64_t lo_x = INT64_MAX, hi_x = INT64_MIN, lo_y = INT64_MAX, hi_y = INT64_MIN;
-    for (int c = 0; c < 4; ++c) {
-        const int64_t x = (c & 1) ? W : 0, y = (c & 2) ? H : 0;
-        const int64_t cx = state[0] * x + state[1] * y + state[2] + (int64_t)ox * mos::ONE;  // below 2^40, see above
-        const int64_t cy = state[3] * x + state[4] * y + state[5] + (int64_t)oy * mos::ONE;
-        lo_x = cx < lo_x ? cx : lo_x, hi_x = cx > hi_x ? cx : hi_x, lo_y = cy < lo_y ? cy : lo_y, hi_y = cy > hi_y ? cy : hi_y;
-    }
-    // canvas pixels [floor(lo), ceil(hi)), widened outwards to whole cells of the canvas's own grid
-    const int64_t X0 = lo_x >> mos::FRAC, X1 = (hi_x + mos::ONE - 1) >> mos::FRAC, Y0 = lo_y >> mos::FRAC, Y1 = (hi_y + mos::ONE - 1) >> mos::FRAC;
+// ---- THE CELLS OF A BOX, for map_patch and merge_defs.h's merge_patch alike.  A box of canvas coordinates in Q20 (mos::corner_box's,
+// the origin added) covers the canvas pixels [floor(lo), ceil(hi)); box_cells widens them outwards to whole cells of the canvas's own
+// grid and writes geom[1..4] = (pu0, pv0, tw, th), or refuses: 3 no cell (a box without a pixel has none) or more than 65536, 4 more
+// cells than the coarse canvas.  A box edge is below 2^43 (mosaic_defs.h), so a canvas pixel is below 2^23 in magnitude and a cell below
+// 2^21: tw th < 2^44 in 64 bits.
+FS_MOS_HD int64_t floor_pixel(int64_t q20) { return q20 >> mos::FRAC; }  // arithmetic shifts: floor and ceiling for negative values too
+FS_MOS_HD int64_t ceil_pixel(int64_t q20) { return (q20 + mos::ONE - 1) >> mos::FRAC; }
+FS_MOS_HD int64_t floor_cell(int64_t px, int S) { return px >> scale_shift(S); }
+FS_MOS_HD int box_cells(int64_t X0, int64_t Y0, int64_t X1, int64_t Y1, int CH, int CW, int S, int64_t* geom) {
     const int64_t pu0 = floor_cell(X0, S), pu1 = floor_cell(X1 + S - 1, S), pv0 = floor_cell(Y0, S), pv1 = floor_cell(Y1 + S - 1, S);
-    const int64_t tw = X1 > X0 ? pu1 - pu0 : 0, th = Y1 > Y0 ? pv1 - pv0 : 0;  // a box without a pixel has no cell
+    const int64_t tw = X1 > X0 ? pu1 - pu0 : 0, th = Y1 > Y0 ? pv1 - pv0 : 0;
     if (tw < 1 || th < 1 || tw * th > MAX_PATCH_CELLS) return (int)(geom[0] = PATCH_CELLS);
     if (tw > CW / S || th > CH / S) return (int)(geom[0] = PATCH_WIDER_THAN_MAP);
     geom[1] = pu0, geom[2] = pv0, geom[3] = tw, geom[4] = th;
     return PATCH_OK;
+}
+
+// ---- map_patch: the geometry of the patch from the LOST state's poses: guard, box, cells.  Everything read from the state is tested
+// before any product: the phase is PHASE_LOST; pose_in_bounds holds to_anchor's translation below 2^34, and the corners are 0..W <= 2^14:
+// inside corner_box's bounds.
+//   AFTER the patch is known to be no wider than the coarse canvas (tw S <= CW <= 2^14): corner (0, 0) lies at to_anchor's translation,
+//   below 2^14 pixels from the anchor, and every pixel of the patch within 2^14 + 2 S of it, so |X - ox| < 2^15 + 32 and
+//   |anchor_coord| < 2^36 + 2^25: source_pixel's products stay below 2^24 x 2^37 = 2^61, two of them 2^62, inside 63 bits, and the
+//   rounded sum below 2^42, + 2^40.
+FS_MOS_HD int patch_geometry(const int64_t* state, int H, int W, int CH, int CW, int ox, int oy, int S, int64_t* geom) {
+    for (int i = 0; i < GEOM_WORDS; ++i) geom[i] = 0;
+    if (state[24] != mos::PHASE_LOST) return (int)(geom[0] = PATCH_NOT_LOST);
+    if (!mos::pose_in_bounds(state, state + 6)) return (int)(geom[0] = PATCH_OUT_OF_BOUNDS);
+    int64_t lo_x, hi_x, lo_y, hi_y;
+    mos::corner_box(state, 0, 0, W, H, &lo_x, &hi_x, &lo_y, &hi_y);
+    const int64_t sx = (int64_t)ox * mos::ONE, sy = (int64_t)oy * mos::ONE;
+    return box_cells(floor_pixel(lo_x + sx), floor_pixel(lo_y + sy), ceil_pixel(hi_x + sx), ceil_pixel(hi_y + sy), CH, CW, S, geom);
 }
 // the frame pixel under canvas pixel (X, Y) of the patch, or false; the caller holds a PATCH_OK geometry of this state
 FS_MOS_HD bool patch_source(const int64_t* state, int64_t X, int64_t Y, int ox, int oy, int H, int W, int* x, int* y) {
@@ -125,36 +129,48 @@ FS_MOS_HD void write_found(int64_t* found, int status, const Score& best, const 
     found[5] = 1, found[6] = second.u, found[7] = second.v, found[8] = second.sad, found[9] = second.n;
 }
 
-// ---- pose_relocate.  found and state are device memory: a count outside 1..2^16, a sum outside 0..255 n, or a shift beyond 2^14 cells
-// makes the row unusable (PATCH_REFUSED), tested before any product.  Then
+// ---- THE PLACEMENT GATE of pose_relocate and merge_defs.h's link_place.  holder: the twelve words (to, from) that the placement would
+// move -- the state's two poses, or a link; attempted: the holder's own guard (a lost chain; a registered or initial link).  found and
+// the holder are device memory: a holder out of pose_in_bounds, a count outside 1..2^16, a sum outside 0..255 n, or a shift beyond
+// 2^14 cells makes the row unusable (PATCH_REFUSED).  Each test comes before the products it protects:
 //   the mean test      sad* <= max_mean n*:                          255 x 2^16 < 2^24
 //   the uniqueness     1000 sad* n2 <= ratio_permille sad2 n*:       1000 x 2^24 x 2^16 < 2^50
 //   the translation    S u ONE: 16 x 2^14 x 2^20 = 2^38;  from[0] S u: 2^24 x 2^18 = 2^42, two of them 2^43, + 2^40
+// Returns the decision; with RELOCATED (to, from) is the holder moved by (S u*, S v*) canvas pixels, and is for no use otherwise.
 FS_MOS_HD bool pair_ok(int64_t sad, int64_t n) { return n >= 1 && n <= MAX_PATCH_CELLS && sad >= 0 && sad <= 255 * n; }
 FS_MOS_HD void translate(const int64_t* to, const int64_t* from, int64_t dx, int64_t dy, int64_t* to_out, int64_t* from_out) {  // by whole canvas pixels: exact
     for (int i = 0; i < 6; ++i) to_out[i] = to[i], from_out[i] = from[i];
     to_out[2] += dx * mos::ONE, to_out[5] += dy * mos::ONE;
     from_out[2] -= from[0] * dx + from[1] * dy, from_out[5] -= from[3] * dx + from[4] * dy;
 }
+FS_MOS_HD int placement_gate(const int64_t* found, bool attempted, const int64_t* holder, int max_mean, int ratio_permille, int S, int64_t* to, int64_t* from) {
+    for (int i = 0; i < 6; ++i) to[i] = 0, from[i] = 0;
+    if (!attempted) return NOT_ATTEMPTED;
+    if (found[0] == FOUND_NONE) return NO_PLACEMENT;
+    if (found[0] != FOUND || !mos::pose_in_bounds(holder, holder + 6) || !pair_ok(found[3], found[4]) || mos::iabs64(found[1]) > mos::MAX_SIDE ||
+        mos::iabs64(found[2]) > mos::MAX_SIDE || (found[5] != 0 && !pair_ok(found[8], found[9])))
+        return PATCH_REFUSED;
+    if (found[3] > (int64_t)max_mean * found[4]) return REJECTED_MEAN;
+    if (found[5] != 0 && 1000 * found[3] * found[9] > (int64_t)ratio_permille * found[8] * found[4]) return REJECTED_UNIQUENESS;
+    translate(holder, holder + 6, (int64_t)S * found[1], (int64_t)S * found[2], to, from);
+    return mos::pose_in_bounds(to, from) ? RELOCATED : OUT_OF_BOUNDS;
+}
+// the report row of relocate_commit and link_place, words 1..7: (S u*, S v*, sad*, n*, sad2, n2, eligible placements), zero where found
+// does not hold them.  S u: below 2^18.
+FS_MOS_HD void placement_report(const int64_t* found, int S, int64_t* out) {
+    for (int i = 1; i < OUT_WORDS; ++i) out[i] = 0;
+    if (found[0] == FOUND && mos::iabs64(found[1]) <= mos::MAX_SIDE && mos::iabs64(found[2]) <= mos::MAX_SIDE) {
+        out[1] = (int64_t)S * found[1], out[2] = (int64_t)S * found[2], out[3] = found[3], out[4] = found[4];
+        if (found[5] != 0) out[5] = found[8], out[6] = found[9];
+    }
+    if (found[0] == FOUND || found[0] == FOUND_NONE) out[7] = found[11];
+}
+
+// ---- pose_relocate: the gate on a lost chain -- a chain that is not lost has nothing to do, and no caller needs to know that beforehand.
 FS_MOS_HD int relocate_step(const int64_t* found, const int64_t* state, int64_t* cand_state, int64_t* cand_pose, int max_mean, int ratio_permille, int H, int W,
                             int CH, int CW, int ox, int oy, int S) {
-    int decision = RELOCATED;
-    int64_t to[6] = {0, 0, 0, 0, 0, 0}, from[6] = {0, 0, 0, 0, 0, 0};
-    if (state[24] != mos::PHASE_LOST) {
-        decision = NOT_ATTEMPTED;  // a chain that is not lost: nothing to do, and no caller needs to know that beforehand
-    } else if (found[0] == FOUND_NONE) {
-        decision = NO_PLACEMENT;
-    } else if (found[0] != FOUND || !mos::pose_in_bounds(state, state + 6) || !pair_ok(found[3], found[4]) ||
-               mos::iabs64(found[1]) > mos::MAX_SIDE || mos::iabs64(found[2]) > mos::MAX_SIDE || (found[5] != 0 && !pair_ok(found[8], found[9]))) {
-        decision = PATCH_REFUSED;
-    } else if (found[3] > (int64_t)max_mean * found[4]) {
-        decision = REJECTED_MEAN;
-    } else if (found[5] != 0 && 1000 * found[3] * found[9] > (int64_t)ratio_permille * found[8] * found[4]) {
-        decision = REJECTED_UNIQUENESS;
-    } else {
-        translate(state, state + 6, (int64_t)S * found[1], (int64_t)S * found[2], to, from);
-        if (!mos::pose_in_bounds(to, from)) decision = OUT_OF_BOUNDS;
-    }
+    int64_t to[6], from[6];
+    const int decision = placement_gate(found, state[24] == mos::PHASE_LOST, state, max_mean, ratio_permille, S, to, from);
     for (int i = 0; i < mos::STATE_WORDS; ++i) cand_state[i] = state[i];
     if (decision == RELOCATED) {
         for (int i = 0; i < 6; ++i) cand_state[i] = cand_pose[i] = to[i], cand_state[6 + i] = cand_pose[6 + i] = from[i];
@@ -184,13 +200,8 @@ FS_MOS_HD int commit_step(const int64_t* cand_state, const int64_t* cand_pose, c
         for (int i = 0; i < COMMIT_STATE_WORDS; ++i) state[i] = cand_state[i];
         for (int i = 0; i < COMMIT_POSE_WORDS; ++i) pose[i] = cand_pose[i];
     }
-    for (int i = 0; i < OUT_WORDS; ++i) out[i] = 0;
     out[0] = status;
-    if (found[0] == FOUND && mos::iabs64(found[1]) <= mos::MAX_SIDE && mos::iabs64(found[2]) <= mos::MAX_SIDE) {  // S u: below 2^18
-        out[1] = (int64_t)S * found[1], out[2] = (int64_t)S * found[2], out[3] = found[3], out[4] = found[4];
-        if (found[5] != 0) out[5] = found[8], out[6] = found[9];
-    }
-    if (found[0] == FOUND || found[0] == FOUND_NONE) out[7] = found[11];
+    placement_report(found, S, out);
     return status;
 }
 

@@ -4,9 +4,8 @@
 // relocate_defs.h's on top of refine_defs.h (__host__ __device__, also run on the CPU by the tests); the image is ingest_src.h's
 // resized1, the one map_view calls cur.  This file is the launches:
 //   map_coarse       a thread per cell: S rows of S canvas words; adjacent lanes read adjacent 4 S bytes of a canvas row.
-//   map_patch        two launches.  Cells: a wave per patch cell, four cells a workgroup; every wave derives the geometry from the state
-//                    (a uniform address: scalar loads), gathers its S^2 pixels through source_pixel as ortho_accumulate does, and
-//                    reduces sum and validity with shuffles.  Finish: one workgroup counts the valid cells and writes geom.
+//   map_patch        patch_kernels.h's two launches (cells, finish), which merge_patch shares, on FramePatch below: the geometry is
+//                    patch_geometry's on the state row, a pixel is gathered through source_pixel as ortho_accumulate does.
 //   map_locate       two launches.  SCORES (the hot one): a workgroup owns 64 x 4 placements, a wave one row of 64 shifts.  The patch goes
 //                    through LDS in chunks of 64 x 8 cells, the coarse canvas under the tile as a strip of 128 x 11 cells, both as bytes
 //                    with the validity widened to 0x00 / 0xFF.  A lane's window is unaligned by its shift: it reads the aligned dwords
@@ -23,22 +22,17 @@
 #include "egress_px.h"
 #include "ingest_src.h"
 #include "kernels.h"
-#include "relocate_defs.h"
+#include "map_checks.h"
+#include "patch_kernels.h"
 
 namespace fs {
 
 namespace {
 
-constexpr int THREADS = 256, WAVE = 64;
+constexpr int THREADS = 256;
 constexpr int PU = 64, PV = 4;               // scores: the placements of a workgroup
 constexpr int TC = 64, TR = 8;               // scores: a chunk of the patch
 constexpr int SW = TC + PU, SR = TR + PV - 1;  // scores: the strip of the coarse canvas under a chunk for every placement of the tile
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
 
 // ------------------------------------------------------------------ map_coarse
 __global__ __launch_bounds__(THREADS) void map_coarse_kernel(const uint32_t* __restrict__ rgba, int CW, int ch, int cw, int S, uint8_t* __restrict__ cl,
@@ -50,65 +44,36 @@ __global__ __launch_bounds__(THREADS) void map_coarse_kernel(const uint32_t* __r
     cl[(size_t)cy * cw + cx] = l, cv[(size_t)cy * cw + cx] = v;
 }
 
-// ------------------------------------------------------------------ map_patch
+// ------------------------------------------------------------------ map_patch: patch_kernels.h's two launches on the frame
+struct FrameBox {  // the patch of a lost chain's frame: the state row and patch_geometry's arguments
+    static constexpr int ROW_WORDS = mos::STATE_WORDS;
+    const long long* row;
+    int H, W, CH, CW, ox, oy, S;
+    __device__ int geometry(const int64_t* state, int64_t* geom) const { return relo::patch_geometry(state, H, W, CH, CW, ox, oy, S, geom); }
+};
 template <bool YUV, int MODE>
-__global__ __launch_bounds__(THREADS) void patch_cells_kernel(IngestSrc s, const long long* __restrict__ state_row, int H, int W, int CH, int CW, int ox, int oy,
-                                                              int S, float sy, float sx, uint8_t* __restrict__ tl, uint8_t* __restrict__ tv) {
-    int64_t state[mos::STATE_WORDS], geom[relo::GEOM_WORDS];  // the same address in every thread: scalar loads
-#pragma unroll
-    for (int i = 0; i < mos::STATE_WORDS; ++i) state[i] = state_row[i];
-    if (relo::patch_geometry(state, H, W, CH, CW, ox, oy, S, geom) != relo::PATCH_OK) return;  // uniform
-    const int tw = (int)geom[3], th = (int)geom[4], lane = threadIdx.x & (WAVE - 1);
-    const int cell = blockIdx.x * (THREADS / WAVE) + threadIdx.x / WAVE;  // wave-uniform
-    if (cell >= tw * th) return;
-    const int j = cell / tw, i = cell - j * tw;
-    const int64_t X0 = (geom[1] + i) * S, Y0 = (geom[2] + j) * S;
-    uint32_t sum = 0;
-    bool ok = true;
-    for (int p = lane; p < S * S; p += WAVE) {
+struct FramePatch : FrameBox {  // its pixels: the frame resized to the mask's size, as ortho_accumulate gathers it
+    IngestSrc s;
+    float sy, sx;
+    __device__ bool luma(const int64_t* state, int64_t X, int64_t Y, uint32_t* l) const {
         int x, y;
-        if (!relo::patch_source(state, X0 + p % S, Y0 + p / S, ox, oy, H, W, &x, &y)) {
-            ok = false;
-            continue;
-        }
+        if (!relo::patch_source(state, X, Y, ox, oy, H, W, &x, &y)) return false;
         float v[3];
         resized1<YUV, MODE>(s, y, x, sy, sx, v);
-        sum += refn::luma((uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]);
+        *l = refn::luma((uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]);
+        return true;
     }
-    const bool all = __ballot(!ok) == 0ull;
-    sum = wave_sum(sum);
-    if (lane == 0) tl[cell] = all ? (uint8_t)relo::cell_mean(sum, S) : (uint8_t)0, tv[cell] = all ? 1 : 0;
-}
-
-__global__ __launch_bounds__(THREADS) void patch_finish_kernel(const long long* __restrict__ state_row, int H, int W, int CH, int CW, int ox, int oy, int S,
-                                                               const uint8_t* __restrict__ tv, long long* __restrict__ geom_out) {
-    __shared__ uint32_t part[THREADS / WAVE];
-    int64_t state[mos::STATE_WORDS], geom[relo::GEOM_WORDS];
-#pragma unroll
-    for (int i = 0; i < mos::STATE_WORDS; ++i) state[i] = state_row[i];
-    const bool ok = relo::patch_geometry(state, H, W, CH, CW, ox, oy, S, geom) == relo::PATCH_OK;  // uniform
-    uint32_t count = 0;
-    if (ok)
-        for (int c = threadIdx.x; c < (int)(geom[3] * geom[4]); c += THREADS) count += tv[c] == 1 ? 1u : 0u;
-    count = wave_sum(count);
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) geom[5] = ok ? (int64_t)(part[0] + part[1] + part[2] + part[3]) : 0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < relo::GEOM_WORDS; ++i) geom_out[i] = geom[i];
-}
+};
 
 template <bool YUV>
-void patch_mode(const IngestSrc& s, const long long* state, int H, int W, int CH, int CW, int ox, int oy, int S, uint8_t* tl, uint8_t* tv, hipStream_t st) {
-    const int64_t cells = (int64_t)(CH / S) * (CW / S);  // a patch that passes has no more cells than the coarse canvas, and at most 65536
-    const dim3 grid((unsigned)cdiv64(cells < relo::MAX_PATCH_CELLS ? cells : relo::MAX_PATCH_CELLS, THREADS / WAVE));
-    const float sy = resize_scale(s.H, H, 0), sx = resize_scale(s.W, W, 0);  // as refine_ops.hip and ortho_ops.hip take them
-    if (s.H == H && s.W == W)
-        patch_cells_kernel<YUV, 2><<<grid, THREADS, 0, st>>>(s, state, H, W, CH, CW, ox, oy, S, sy, sx, tl, tv);
-    else if (s.W == W)
-        patch_cells_kernel<YUV, 1><<<grid, THREADS, 0, st>>>(s, state, H, W, CH, CW, ox, oy, S, sy, sx, tl, tv);
+void patch_mode(const IngestSrc& s, const FrameBox& box, uint8_t* tl, uint8_t* tv, hipStream_t st) {
+    const float sy = resize_scale(s.H, box.H, 0), sx = resize_scale(s.W, box.W, 0);  // as refine_ops.hip and ortho_ops.hip take them
+    if (s.H == box.H && s.W == box.W)
+        launch_patch_cells(FramePatch<YUV, 2>{box, s, sy, sx}, box.CH, box.CW, tl, tv, st);
+    else if (s.W == box.W)
+        launch_patch_cells(FramePatch<YUV, 1>{box, s, sy, sx}, box.CH, box.CW, tl, tv, st);
     else
-        patch_cells_kernel<YUV, 0><<<grid, THREADS, 0, st>>>(s, state, H, W, CH, CW, ox, oy, S, sy, sx, tl, tv);
+        launch_patch_cells(FramePatch<YUV, 0>{box, s, sy, sx}, box.CH, box.CW, tl, tv, st);
 }
 
 // ------------------------------------------------------------------ map_locate: the score plane
@@ -262,17 +227,13 @@ __global__ __launch_bounds__(WAVE) void relocate_commit_kernel(const long long* 
     for (int i = 0; i < relo::OUT_WORDS; ++i) out_row[i] = out[i];
 }
 
-bool side_ok(int v) { return v >= 1 && v <= mos::MAX_SIDE; }
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-bool origin_ok(int ox, int oy) { return ox >= -mos::MAX_SIDE && ox <= mos::MAX_SIDE && oy >= -mos::MAX_SIDE && oy <= mos::MAX_SIDE; }
-
 }  // namespace
 
 int launch_map_coarse(const uint32_t* rgba, int CH, int CW, int S, uint8_t* cl, uint8_t* cv, hipStream_t s) {
     FS_REQUIRE(rgba && cl && cv, "map_coarse: null pointer");
-    FS_REQUIRE(side_ok(CH) && side_ok(CW), "map_coarse: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(relo::scale_ok(S), "map_coarse: the cell edge must be 4, 8 or 16, got S=%d", S);
-    FS_REQUIRE(CH / S >= 1 && CW / S >= 1, "map_coarse: a %dx%d canvas has no cell of S=%d", CH, CW, S);
+    FS_TRY(check_sides("map_coarse", "the canvas", 1, CH, CW));
+    FS_TRY(check_cell_edge("map_coarse", S));
+    FS_TRY(check_has_cell("map_coarse", "canvas", CH, CW, S));
     FS_REQUIRE(aligned(rgba, 4), "map_coarse: rgba is not aligned to 4 bytes");
     const int ch = CH / S, cw = CW / S;
     map_coarse_kernel<<<dim3((unsigned)cdiv(cw, WAVE), (unsigned)cdiv(ch, THREADS / WAVE)), THREADS, 0, s>>>(rgba, CW, ch, cw, S, cl, cv);
@@ -283,24 +244,19 @@ int launch_map_coarse(const uint32_t* rgba, int CH, int CW, int S, uint8_t* cl, 
 int launch_map_patch(const uint8_t* frame, const uint8_t* u, const uint8_t* v, int format, int matrix, int full_range, int FH, int FW, const long long* state, int H,
                      int W, int CH, int CW, int ox, int oy, int S, uint8_t* tl, uint8_t* tv, long long* geom, hipStream_t s) {
     FS_REQUIRE(frame && state && tl && tv && geom, "map_patch: null pointer");
-    FS_REQUIRE(format >= 0 && format <= 2, "map_patch: format must be 0 (RGB24), 1 (NV12) or 2 (I420), got %d", format);
-    FS_REQUIRE(matrix == 0 || matrix == 1, "map_patch: matrix must be 0 (BT.601) or 1 (BT.709), got %d", matrix);
-    FS_REQUIRE(full_range == 0 || full_range == 1, "map_patch: range must be 0 (limited) or 1 (full), got %d", full_range);
-    FS_REQUIRE(format == 0 || (u && (format != 2 || v)), "map_patch: null chroma pointer for a YUV format");
-    FS_REQUIRE(side_ok(FH) && side_ok(FW), "map_patch: the frame must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, FH, FW);
-    FS_REQUIRE(side_ok(H) && side_ok(W), "map_patch: the mask must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, H, W);
-    FS_REQUIRE(side_ok(CH) && side_ok(CW), "map_patch: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(origin_ok(ox, oy), "map_patch: the origin must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox, oy);
-    FS_REQUIRE(relo::scale_ok(S), "map_patch: the cell edge must be 4, 8 or 16, got S=%d", S);
-    FS_REQUIRE(CH / S >= 1 && CW / S >= 1, "map_patch: a %dx%d canvas has no cell of S=%d", CH, CW, S);
+    FS_TRY(check_frame_source("map_patch", u, v, format, matrix, full_range, FH, FW));
+    FS_TRY(check_mask_on_canvas("map_patch", 1, H, W, CH, CW, ox, oy));
+    FS_TRY(check_cell_edge("map_patch", S));
+    FS_TRY(check_has_cell("map_patch", "canvas", CH, CW, S));
     FS_REQUIRE(aligned(state, 8) && aligned(geom, 8), "map_patch: state or geom is not aligned to 8 bytes");
     const IngestSrc src = make_ingest_src(frame, u, v, format, matrix, full_range, FH, FW);
+    const FrameBox box = {state, H, W, CH, CW, ox, oy, S};
     if (format == 0)
-        patch_mode<false>(src, state, H, W, CH, CW, ox, oy, S, tl, tv, s);
+        patch_mode<false>(src, box, tl, tv, s);
     else
-        patch_mode<true>(src, state, H, W, CH, CW, ox, oy, S, tl, tv, s);
+        patch_mode<true>(src, box, tl, tv, s);
     FS_HIP(hipGetLastError());
-    patch_finish_kernel<<<1, THREADS, 0, s>>>(state, H, W, CH, CW, ox, oy, S, tv, geom);
+    patch_finish_kernel<<<1, PATCH_THREADS, 0, s>>>(box, tv, geom);
     FS_HIP(hipGetLastError());
     return 0;
 }
@@ -325,10 +281,8 @@ int launch_pose_relocate(const long long* found, const long long* state, long lo
     FS_REQUIRE(found && state && cand_state && cand_pose, "pose_relocate: null pointer");
     FS_REQUIRE(max_mean >= 0 && max_mean <= 255, "pose_relocate: max_mean must be 0..255, got %d", max_mean);
     FS_REQUIRE(ratio_permille >= 1 && ratio_permille <= 1000, "pose_relocate: ratio_permille must be 1..1000, got %d", ratio_permille);
-    FS_REQUIRE(side_ok(H) && side_ok(W), "pose_relocate: the mask must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, H, W);
-    FS_REQUIRE(side_ok(CH) && side_ok(CW), "pose_relocate: the canvas must be 1..%d pixels a side, got %dx%d", mos::MAX_SIDE, CH, CW);
-    FS_REQUIRE(origin_ok(ox, oy), "pose_relocate: the origin must lie within %d pixels of the canvas corner, got (%d, %d)", mos::MAX_SIDE, ox, oy);
-    FS_REQUIRE(relo::scale_ok(S), "pose_relocate: the cell edge must be 4, 8 or 16, got S=%d", S);
+    FS_TRY(check_mask_on_canvas("pose_relocate", 1, H, W, CH, CW, ox, oy));
+    FS_TRY(check_cell_edge("pose_relocate", S));
     FS_REQUIRE(aligned(found, 8) && aligned(state, 8) && aligned(cand_state, 8) && aligned(cand_pose, 8),
                "pose_relocate: found, state, cand_state or cand_pose is not aligned to 8 bytes");
     FS_REQUIRE(state != cand_state, "pose_relocate: cand_state is the state itself");
@@ -340,7 +294,7 @@ int launch_pose_relocate(const long long* found, const long long* state, long lo
 int launch_relocate_commit(const long long* cand_state, const long long* cand_pose, const long long* correct_out, long long* state, long long* pose,
                            const long long* found, int S, long long* out, hipStream_t s) {
     FS_REQUIRE(cand_state && cand_pose && correct_out && state && pose && found && out, "relocate_commit: null pointer");
-    FS_REQUIRE(relo::scale_ok(S), "relocate_commit: the cell edge must be 4, 8 or 16, got S=%d", S);
+    FS_TRY(check_cell_edge("relocate_commit", S));
     FS_REQUIRE(aligned(cand_state, 8) && aligned(cand_pose, 8) && aligned(correct_out, 8) && aligned(state, 8) && aligned(pose, 8) && aligned(found, 8) &&
                    aligned(out, 8),
                "relocate_commit: a row is not aligned to 8 bytes");

@@ -126,6 +126,25 @@ def test_patch_equals_the_reference_in_every_status(s):
     assert seen == {0, 1, 2, 3, 4}
 
 
+def test_the_patch_kernel_on_canvas_b_in_every_shape():
+    """The cells kernel that map_patch shares, with canvas B as its source, at S = 4 (16 of a wave's 64 lanes hold a pixel) and S = 16
+    (four pixels a lane): a b_box that lands on exactly one cell of A, and one on 3 x 2 cells -- no multiple of the four a workgroup
+    takes -- of which one holds B's only unseen pixel."""
+    rng = np.random.RandomState(12)
+    link = gref.link_row(*mref.affine_pose(1, 0, 0, 1, 32 - 8 + OB[1] - OA[1], 32 - 4 + OB[0] - OA[0]), status=gref.REGISTERED)   # B's (8, 4) on A's (32, 32)
+    for s in (4, 16):
+        b = rng.randint(0, 1 << 24, size=(64, 96)).astype(np.uint32) | np.uint32(0xFF000000)
+        b[4 + s + 1, 8 + 1] = 0                                               # in the second row of cells, first column
+        for box, cells, valid in (((4, 8, 4 + s, 8 + s), (1, 1), 1), ((4, 8, 4 + 2 * s, 8 + 3 * s), (3, 2), 5)):
+            want = gref.merge_patch(b, OB, link, (96, 160), OA, s, box)
+            assert want[2].tolist() == [0, 32 // s, 32 // s, cells[0], cells[1], valid, 0, 0], (s, box, want[2])            # the reference first
+            tl, tv, geom = ops.merge_patch(rgba32(b), OB, dev(link), (96, 160), OA, s, box)
+            assert np.array_equal(host(geom), want[2]), (s, box, host(geom).tolist())
+            assert np.array_equal(host(tl)[:want[0].size], want[0].reshape(-1)) and np.array_equal(host(tv)[:want[1].size], want[1].reshape(-1)), (s, box)
+            if valid == 5:
+                assert want[1].tolist() == [[1, 1, 1], [0, 1, 1]]
+
+
 def test_place_equals_the_reference_in_every_code():
     for name, found, link, max_mean, ratio, code in gref.place_cases():
         for s in (4, 8):

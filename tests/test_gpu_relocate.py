@@ -113,6 +113,37 @@ def test_patch_equals_the_definition(name):
     assert rotated[1][0, 0] == 0 and rotated[1][-1, -1] == 0 and 0 < rotated[2][5] < rotated[1].size
 
 
+def shape_states(s):
+    """(label, state, cells, valid cells) for a 32 x 48 frame on a canvas with its anchor at (30, 20): the frame shrunk onto exactly one
+    cell; the frame on whole cells at canvas (32, 32) under a from_anchor sheared by 1/62, so that of all its pixels only the source of
+    the bottom left one falls outside the frame (x = 0.5 - 31.5 / 62 < 0) and one cell is invalid; and the frame one pixel off the cell
+    grid, its rim of cells invalid.  3 x 2 = 6 cells at S = 16 and 13 x 9 = 117 at S = 4: no multiple of the four a workgroup takes."""
+    k = 16913                                                                 # ONE / 62 in Q20
+    sheared = [ONE, -k, -2 * ONE + 12 * k, 0, ONE, -12 * ONE]                 # the inverse of the shift by (2, 12), and - y / 62 in x
+    return [("one cell", lref.lost_state(*mref.affine_pose(s / 48, 0, 0, s / 32, 2, 12)), 1, 1),
+            ("one pixel outside", lref.lost_state(mref.affine_pose(1, 0, 0, 1, 2, 12)[0], sheared), (48 // s) * (32 // s), (48 // s) * (32 // s) - 1),
+            ("off the grid", lref.lost_state(*mref.affine_pose(1, 0, 0, 1, 3, 13)), (48 // s + 1) * (32 // s + 1), (48 // s - 1) * (32 // s - 1))]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("fmt", ["rgb24", "nv12"])
+def test_the_patch_kernel_in_every_shape_and_source(fmt, mode):
+    """The one cells kernel behind map_patch on every frame source it is instantiated for -- RGB24 and NV12, each resized in both
+    directions (0), in height only (1) and not at all (2) -- at S = 4 (16 of a wave's 64 lanes hold a pixel) and S = 16 (four pixels a
+    lane), on shape_states' patches."""
+    mask, canvas, origin = (32, 48), (96, 160), (20, 30)
+    source = oref.make_source(*{0: (64, 96), 1: (64, 48), 2: (32, 48)}[mode], fmt, "bt709", False, seed=90 + mode)
+    img, d_source = oref.image(source, mask), dev_source(source)
+    for s in (4, 16):
+        for label, state, cells, valid in shape_states(s):
+            want = lref.map_patch(img, state, canvas, origin, s)
+            assert want[2][0] == 0 and want[2][3] * want[2][4] == cells and want[2][5] == valid, (s, label, want[2])      # the reference first
+            check_patch(ops.map_patch(d_source, dev(state), mask, canvas, origin, s), want)
+    X, Y = np.meshgrid(np.arange(32, 80), np.arange(32, 64))                   # "one pixel outside" means one
+    x, y = lref._source(shape_states(4)[1][1][6:12].tolist(), X, Y, origin[1], origin[0])
+    assert ((x < 0) | (x >= 48) | (y < 0) | (y >= 32)).sum() == 1 and x[31, 0] == -1
+
+
 # ------------------------------------------------------------------------------------------------ map_locate
 @pytest.mark.parametrize("name", list(SCENES))
 def test_locate_equals_the_definition(name):

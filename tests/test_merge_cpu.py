@@ -17,6 +17,7 @@ import torch
 
 import merge_ref as gref
 import mosaic_ref as mref
+import placement_rows
 from flood_uav_video_segmentation_amd import _lib, ops
 from flood_uav_video_segmentation_amd.flow.predict import (FlowPredictor, merge_part, mosaic_part_arrays, part_seen_box, read_mosaic_part, write_merge_csv,
                                                            write_mosaic_part)
@@ -194,7 +195,45 @@ def host_commands():
         for s in (4, 16):
             cand, out = gref.place_step(found, link, s, max_mean, ratio)
             add(["place", s, max_mean, ratio] + flat(found) + flat(link), flat(cand) + flat(out))
+    for name, link, box, size_a, s, status, cells in box_cases():
+        geom = gref.box_geometry(link, box, OB, size_a, OA, s)
+        assert geom[0] == status and (cells is None or tuple(geom[1:5]) == cells), (name, geom)          # the reference first: the case is what it says
+        add(["geometry"] + list(box) + [OB[1], OB[0], size_a[0], size_a[1], OA[1], OA[0], s] + flat(link), geom)
+    for name, found, (to, back), code in placement_rows.gate_rows():
+        link, state = gref.link_row(to, back, status=gref.REGISTERED, tail=(7, 8, 9)), gref.lref.lost_state(to, back)
+        for s in (4, 16):
+            cand, out = gref.place_step(found, link, s, placement_rows.MAX_MEAN, placement_rows.RATIO)
+            step = gref.lref.relocate_step(found, state, s=s, max_mean=placement_rows.MAX_MEAN, ratio=placement_rows.RATIO, **gref.lref.STEP_GEOMETRY)
+            assert out[0] == code == step[0][28], name                                                    # one gate: pose_relocate draws the same code
+            add(["place", s, placement_rows.MAX_MEAN, placement_rows.RATIO] + flat(found) + flat(link), flat(cand) + flat(out))
     return cmds, want
+
+
+def box_cases():
+    """(name, link, b_box, canvas A, S, status, (pu0, pv0, tw, th) or None) for merge_patch's geometry where a rule on the corners' box and
+    a rule corner by corner could part.  Origins OA and OB; a b_box of 32 x 48 pixels of B turned by 30 degrees, so that each extremum
+    comes from another corner, with the link's translation chosen in Q20 so that the box starts exactly on a pixel's edge of A, or a unit
+    off it; a box exactly as wide as A's coarse canvas and one cell wider; and a link that flattens the box to no pixel."""
+    (oya, oxa), (oyb, oxb), cases = OA, OB, []
+    y0, x0, y1, x1 = box = (4, 8, 36, 56)
+    shift = lambda tx, ty: gref.link_row([ONE, 0, tx * ONE, 0, ONE, ty * ONE], [ONE, 0, -tx * ONE, 0, ONE, -ty * ONE], status=gref.REGISTERED)  # noqa: E731
+    # upright: B pixel x lands on A pixel x - oxb + tx + oxa; tx puts x0 on A's pixel 0
+    tx, ty = oxb - oxa - x0, oyb - oya - y0 + 8
+    cases.append(("as wide as the coarse canvas", shift(tx, ty), box, (64, 48), 4, 0, (0, 2, 12, 8)))    # x 0..48: cells 0..11 of 12
+    cases.append(("one cell wider", shift(tx + 1, ty), box, (64, 48), 4, 4, None))                       # x 1..49: cells 0..12
+    cases.append(("a box of no width", gref.link_row([0, 0, 5 * ONE, 0, ONE, 0], status=gref.REGISTERED), box, (64, 48), 4, 3, None))
+    c, s = np.cos(np.radians(30)), np.sin(np.radians(30))
+    lin = [int(round(v * ONE)) for v in (c, -s, s, c)]
+    corners = [(x - oxb, y - oyb) for x, y in ((x0, y0), (x1, y0), (x0, y1), (x1, y1))]
+    xs, ys = [lin[0] * x + lin[1] * y for x, y in corners], [lin[2] * x + lin[3] * y for x, y in corners]
+    assert len({xs.index(min(xs)), xs.index(max(xs)), ys.index(min(ys)), ys.index(max(ys))}) == 4
+    wide, high = -(-(max(xs) - min(xs)) // ONE), -(-(max(ys) - min(ys)) // ONE)
+    for d in (0, -1):                                                                                    # the box starts at A's pixel (40, 24), or a unit before it
+        link = gref.link_row([lin[0], lin[1], 40 * ONE - min(xs) - oxa * ONE + d, lin[2], lin[3], 24 * ONE - min(ys) - oya * ONE + d], status=gref.REGISTERED)
+        X0, Y0 = 40 + d, 24 + d
+        cases.append((f"rotated, {d} units off the pixel's edge", link, box, (128, 192), 4, 0,
+                      (X0 // 4, Y0 // 4, (40 + wide + 3) // 4 - X0 // 4, (24 + high + 3) // 4 - Y0 // 4)))
+    return cases
 
 
 def test_the_headers_rules_are_the_references_under_sanitizers(tmp_path):
@@ -271,10 +310,11 @@ def test_the_fourteenth_table_and_the_freeze_of_the_thirteenth():
         with pytest.raises(AttributeError):
             getattr(ctypes.CDLL(_lib.LIB_PATH), "fs_" + name)                                            # a table member, not an exported symbol
     assert ctypes.cast(all13.base12.ext12.map_locate, ctypes.c_void_p).value == ctypes.cast(lib.fs_map_locate, ctypes.c_void_p).value
-    # the rules' header builds on the older ones and leaves them alone; the kernels take their rules from it; no canvas takes an atomic
+    # the rules' header builds on the older ones: a rule two ops share is theirs, called from here; the kernels take their rules from it; no canvas takes an atomic
     defs = open(os.path.join(CSRC, "merge_defs.h")).read()
-    assert '#include "relocate_defs.h"' in defs and all(f"mos::{fn}(" in defs for fn in ("source_pixel", "anchor_coord", "pose_in_bounds", "touches", "compose"))
-    assert all(f"refn::{fn}(" in defs for fn in ("luma_of", "seen", "gate_keeps")) and "orth::rank_ordinal(" in defs and "relo::translate(" in defs
+    assert '#include "relocate_defs.h"' in defs and all(f"mos::{fn}(" in defs for fn in ("source_pixel", "anchor_coord", "pose_in_bounds", "touches", "compose", "corner_box"))
+    assert all(f"refn::{fn}(" in defs for fn in ("luma_of", "seen", "gate_keeps", "fit_report")) and "orth::rank_ordinal(" in defs
+    assert all(f"relo::{fn}(" in defs for fn in ("box_cells", "placement_gate", "placement_report")) and "translate(" not in defs   # the move is the gate's
     assert defs.count("mos::source_pixel(") == 1                                                         # the one gather the ops share
     kernel = open(os.path.join(CSRC, "merge_ops.hip")).read()
     assert all(f"mrg::{fn}(" in kernel for fn in ("link_views", "link_merges", "gather_affine", "b_pixel", "b_reaches", "view_pixel", "correct_step", "shifted_rank",
@@ -283,11 +323,12 @@ def test_the_fourteenth_table_and_the_freeze_of_the_thirteenth():
     assert "asm" not in code and "hipMemset" not in code
     atomics = re.findall(r"atomic\w*\(([^,]+),", code)
     assert atomics and all(a.strip().startswith(("&tally[", "counts +")) for a in atomics)                # the tally and counts only
-    # the four headers it builds on are byte for byte what they were before this table existed (no git needed: a checkout may have none)
-    for older, digest in (("mosaic_defs.h", "0e030073aa985364cd83e1b034172bdfac33e8aa3afb0a3f5aa6062e2ea38bd7"),
+    # the four headers it builds on are byte for byte what they became when the family's shared rules (the corners' box, the cells of a box,
+    # the placement gate, the two report rows) were written once, in them (no git needed: a checkout may have none)
+    for older, digest in (("mosaic_defs.h", "e691732e4314af07baa789dc7c3fb306ab002605536cd97ff10e48957de23d2c"),
                           ("ortho_defs.h", "7406b782e77f4778c32786c9a5363a3ff6adad4831944c0925d5b174de12a347"),
-                          ("refine_defs.h", "18dbb7b97e42aec9f7f45a1e5febe53bdfe411387fcd953d11670c5a94aece02"),
-                          ("relocate_defs.h", "fcfc20224e6450ea9c1f8166f3e14d2f27ad75ce80f85a22806778f575229a43")):
+                          ("refine_defs.h", "d6167c7b09f800b4e9a07b3843c8992abd8300df18a2c1cbb0868d0d10829d45"),
+                          ("relocate_defs.h", "a36b5c734d196339835b549aa37b4885f18e4bbe450006f56d677ee9eca984d8")):
         assert hashlib.sha256(open(os.path.join(CSRC, older), "rb").read().replace(b"\r\n", b"\n")).hexdigest() == digest, older   # whatever line endings a checkout made
     assert " merge_ops.hip " in open(os.path.join(CSRC, "Makefile")).read()
 

@@ -188,6 +188,27 @@ def test_pose_chain_by_hand():
 
 
 # ------------------------------------------------------------------------------------------------ the header's functions on the CPU
+def clip_cases():
+    """(to_anchor, clipped) for a 40 x 60 frame on a 100 x 100 canvas with its anchor at (20, 10): the header tests the corners' bounding
+    box, the reference corner by corner.  Each edge of the canvas in turn: the extreme corner exactly ON it (inside), and one Q20 unit
+    beyond it (clipped); upright, and turned by 30 degrees, where each of the four extrema comes from another corner."""
+    (h, w), (ch, cw), (oy, ox) = (40, 60), (100, 100), (10, 20)
+    c, s = np.cos(np.radians(30)), np.sin(np.radians(30))
+    cases = []
+    for lin in ([ONE, 0, 0, ONE], [int(round(v * ONE)) for v in (c, -s, s, c)]):
+        corners = ((0, 0), (w, 0), (0, h), (w, h))
+        xs, ys = [lin[0] * x + lin[1] * y for x, y in corners], [lin[2] * x + lin[3] * y for x, y in corners]
+        if lin[1]:
+            assert len({xs.index(min(xs)), xs.index(max(xs)), ys.index(min(ys)), ys.index(max(ys))}) == 4
+        left, right = -min(xs) - ox * ONE, cw * ONE - max(xs) - ox * ONE      # the translations that put the box's edge on the canvas's
+        top, bottom = -min(ys) - oy * ONE, ch * ONE - max(ys) - oy * ONE
+        assert left < right and top < bottom                                  # the box fits: between the two the frame is inside
+        for tx, ty, clipped in ((left, top, 0), (right, bottom, 0), (left - 1, top + ONE, 1), (right + 1, top + ONE, 1), (left + ONE, top - 1, 1),
+                                (left + ONE, bottom + 1, 1), (left + ONE, top + ONE, 0)):
+            cases.append(([lin[0], lin[1], tx, lin[2], lin[3], ty], clipped))
+    return cases
+
+
 def host_commands():
     """(commands, expected output lines) for tests/mosaic_host_check.cpp, from the numpy reference and from arithmetic."""
     rng = np.random.RandomState(17)
@@ -244,6 +265,13 @@ def host_commands():
         state = after
         if after[24] == 2:
             state = np.zeros(32, np.int64)                                   # lost is sticky: go on from a fresh state
+    for to, clipped in clip_cases():                                         # a tracking chain that stands at `to`, and a pair that moves nothing
+        state = np.zeros(32, np.int64)
+        state[0:6], state[6:12], state[12:18], state[18:24], state[24] = to, IDENT, IDENT, IDENT, 1
+        row = IDENT + IDENT + [0, 20, 18, 4]
+        poses, after = mref.pose_chain(np.array([row], np.int64), state, (40, 60), (100, 100), (10, 20), max_bridge=2)
+        assert poses[0, :6].tolist() == to and poses[0, 12] == 0 and poses[0, 13] == int(clipped), (to, poses[0])   # the reference first
+        add(["pose"] + state.tolist() + row + [40, 60, 100, 100, 20, 10, 2], poses[0].tolist() + after.tolist())
     c, s = np.cos(np.radians(30)), np.sin(np.radians(30))
     for back in (IDENT, mref.affine_pose(c, -s, s, c, 6, -2)[1], mref.affine_pose(0.5, 0, 0, 0.5, -100.25, 3)[1], mref.affine_pose(2, 0, 0, 2, 1, 1)[1]):
         for X, Y, ox, oy in ((0, 0, 0, 0), (5, 7, 3, -2), (16383, 0, -16384, 16384), (0, 16383, 16384, -16384)):

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import mosaic_ref as mref
+import placement_rows
 import refine_ref as rref
 import relocate_ref as lref
 from flood_uav_video_segmentation_amd import _lib, ops
@@ -202,7 +203,50 @@ def host_commands():
     for name, cs, cp, co, state, pose, found, status in lref.commit_cases():
         st, p, out = lref.commit_step(cs, cp, co, state, pose, found, 4)
         add(["commit", 4] + flat(cs) + flat(cp) + flat(co) + flat(state) + flat(pose) + flat(found), flat(out) + flat(st) + flat(p))
+    for name, state, size, s, status, cells in box_cases():
+        geom = lref.patch_geometry(state, size, CANVAS, ORIGIN, s)
+        assert geom[0] == status and (cells is None or tuple(geom[1:5]) == cells), (name, geom)          # the reference first: the case is what it says
+        add(["geometry", size[0], size[1], CANVAS[0], CANVAS[1], ORIGIN[1], ORIGIN[0], s] + flat(state), geom)
+    for name, found, (to, back), code in placement_rows.gate_rows():
+        for s in (4, 16):
+            cs, cp = lref.relocate_step(found, lref.lost_state(to, back), s=s, max_mean=placement_rows.MAX_MEAN, ratio=placement_rows.RATIO, **g)
+            assert cs[28] == code, name
+            add(["step", *g["mask_size"], *g["canvas_size"], g["origin"][1], g["origin"][0], s, placement_rows.MAX_MEAN, placement_rows.RATIO] + flat(found)
+                + flat(lref.lost_state(to, back)), flat(cs) + flat(cp))
     return cmds, want
+
+
+def box_cases():
+    """(name, state, mask size, S, status, (pu0, pv0, tw, th) or None) where a rule on the corners' box and a rule corner by corner could part:
+    on CANVAS = 100 x 150 with its anchor at (30, 20), so 37 x 25 cells of 4.  The extrema of the rotated frame come from four different
+    corners; its translation is then chosen in Q20 so that an edge of the box lies exactly on a pixel's edge, and one unit beyond it."""
+    (oy, ox), cases = ORIGIN, []
+    flat_to = lambda tx, ty: lref.lost_state([ONE, 0, tx * ONE, 0, ONE, ty * ONE], [ONE, 0, -tx * ONE, 0, ONE, -ty * ONE])  # noqa: E731
+    cases.append(("as wide as the coarse canvas", flat_to(-ox, 0), (36, 148), 4, 0, (0, 5, 37, 9)))       # x 0..148: cells 0..36
+    cases.append(("one cell wider", flat_to(1 - ox, 0), (36, 148), 4, 4, None))                           # x 1..149: cells 0..37
+    cases.append(("one cell higher", flat_to(0, 1 - oy), (100, 44), 4, 4, None))                          # y 1..101: cells 0..25 of 25
+    cases.append(("a box of no width", lref.lost_state([0, 0, 5 * ONE, 0, ONE, 0], mref.IDENTITY), (36, 44), 4, 3, None))   # hi == lo on a pixel's edge
+    cases.append(("a box of no height", lref.lost_state([ONE, 0, 0, 0, 0, -3 * ONE], mref.IDENTITY), (36, 44), 8, 3, None))
+    c, s = np.cos(np.radians(30)), np.sin(np.radians(30))
+    lin = [int(round(v * ONE)) for v in (c, -s, s, c)]
+    h, w = 36, 44
+    corners = ((0, 0), (w, 0), (0, h), (w, h))
+    xs, ys = [lin[0] * x + lin[1] * y for x, y in corners], [lin[2] * x + lin[3] * y for x, y in corners]
+    assert len({xs.index(min(xs)), xs.index(max(xs)), ys.index(min(ys)), ys.index(max(ys))}) == 4
+    wide, high = -(-(max(xs) - min(xs)) // ONE), -(-(max(ys) - min(ys)) // ONE)                            # whole pixels the box spans when it starts on an edge
+    for d in (0, -1, 1):                                                                                  # the box starts at canvas pixel (40, 24) exactly, or a unit off
+        to = [lin[0], lin[1], 40 * ONE - min(xs) - ox * ONE + d, lin[2], lin[3], 24 * ONE - min(ys) - oy * ONE + d]
+        X0, X1, Y0, Y1 = 40 - (d < 0), 40 + wide + (d > 0 and (max(xs) - min(xs)) % ONE == 0), 24 - (d < 0), 24 + high + (d > 0 and (max(ys) - min(ys)) % ONE == 0)
+        cells = (X0 // 4, Y0 // 4, (X1 + 3) // 4 - X0 // 4, (Y1 + 3) // 4 - Y0 // 4)
+        cases.append((f"rotated, {d} units off the pixel's edge", lref.lost_state(to, mref.IDENTITY), (h, w), 4, 0, cells))
+    # ... and its far edge exactly on a pixel's edge: one unit more takes another pixel, and with it another cell
+    to = [lin[0], lin[1], 96 * ONE - max(xs) - ox * ONE, lin[2], lin[3], 64 * ONE - max(ys) - oy * ONE]
+    for d, more in ((0, 0), (1, 1)):
+        moved = to[:2] + [to[2] + d] + to[3:5] + [to[5] + d]
+        X0, Y0 = (96 * ONE - (max(xs) - min(xs)) + d) // ONE, (64 * ONE - (max(ys) - min(ys)) + d) // ONE
+        cells = (X0 // 4, Y0 // 4, 24 + more - X0 // 4, 16 + more - Y0 // 4)
+        cases.append((f"rotated, the far edge {d} units past a cell's edge", lref.lost_state(moved, mref.IDENTITY), (h, w), 4, 0, cells))
+    return cases
 
 
 def test_the_headers_rules_are_the_references_under_sanitizers(tmp_path):
