@@ -246,6 +246,12 @@ _EXT13_HOOKS = [
 ]
 EXT13_MAGIC = 0x4653455854413133  # FS_EXT13_MAGIC
 
+# members of fs_ext14_api, the fifteenth table (append-only, behind the fourteen frozen ones), in declaration order after `magic` and `size`
+_EXT14_HOOKS = [
+    ("mosaic_change", c_int, [c_void] + [c_int] * 4 + [c_void] + [c_int] * 5 + [c_void] + [c_int] * 3 + [ctypes.c_uint32] + [c_void] * 6),
+]
+EXT14_MAGIC = 0x4653455854413134  # FS_EXT14_MAGIC
+
 
 def _struct(name, *fields):
     return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
@@ -285,6 +291,8 @@ FsExt12Api = _struct("FsExt12Api", *_EXT_HEAD, *_members(_EXT12_HOOKS))
 FsHookTables12 = _struct("FsHookTables12", ("base11", FsHookTables11), ("ext12", FsExt12Api))
 FsExt13Api = _struct("FsExt13Api", *_EXT_HEAD, *_members(_EXT13_HOOKS))
 FsHookTables13 = _struct("FsHookTables13", ("base12", FsHookTables12), ("ext13", FsExt13Api))
+FsExt14Api = _struct("FsExt14Api", *_EXT_HEAD, *_members(_EXT14_HOOKS))
+FsHookTables14 = _struct("FsHookTables14", ("base13", FsHookTables13), ("ext14", FsExt14Api))
 
 # One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
 # the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
@@ -306,6 +314,7 @@ _TABLES = [
     _Table("eleven", "eleventh", _EXT11_HOOKS, "EXT11_MAGIC", FsExt11Api, FsHookTables11, "ext11"),
     _Table("twelve", "twelfth", _EXT12_HOOKS, "EXT12_MAGIC", FsExt12Api, FsHookTables12, "ext12"),
     _Table("thirteen", "thirteenth", _EXT13_HOOKS, "EXT13_MAGIC", FsExt13Api, FsHookTables13, "ext13"),
+    _Table("fourteen", "fourteenth", _EXT14_HOOKS, "EXT14_MAGIC", FsExt14Api, FsHookTables14, "ext14"),
 ]
 _TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
@@ -386,7 +395,8 @@ def _hook_names(n):
 
 
 (hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
- ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names, ext12_hook_names, ext13_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
+ ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names, ext12_hook_names, ext13_hook_names,
+ ext14_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

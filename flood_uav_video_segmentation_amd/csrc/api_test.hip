@@ -653,7 +653,15 @@ static int fs_link_place(const int64_t* found, const int64_t* link, int scale, i
                                  reinterpret_cast<long long*>(cand), reinterpret_cast<long long*>(out), S(stream));
 }
 
-// the fourteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// the flood-extent change between two registered mosaics (change_ops.hip): the launcher validates, nothing is launched on a refusal
+static int fs_mosaic_change(const uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint16_t* votes_b, int CH_b, int CW_b, int ox_b, int oy_b, int K,
+                            const int64_t* link, int min_votes, int min_conf, int tolerance, uint32_t watch_set, uint8_t* change, uint8_t* cls_a, uint8_t* cls_b,
+                            int64_t* transitions, int64_t* counts, fs_stream stream) {
+    return fs::launch_mosaic_change(votes_a, CH_a, CW_a, ox_a, oy_a, votes_b, CH_b, CW_b, ox_b, oy_b, K, reinterpret_cast<const long long*>(link), min_votes, min_conf,
+                                    tolerance, watch_set, change, cls_a, cls_b, reinterpret_cast<long long*>(transitions), reinterpret_cast<long long*>(counts), S(stream));
+}
+
+// the fifteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -805,7 +813,14 @@ static const fs_hook_tables5& hook_tables(void) {
         fs_merge_patch,
         fs_link_place,
     }};
+    // fs_ext13_api is frozen too (six members, 64 bytes; tests/test_change_cpu.py); the fifteenth table lies behind it, and &all14.base13 is &all14.
+    static const fs_hook_tables14 all14 = {all13, {
+        FS_EXT14_MAGIC,
+        sizeof(fs_ext14_api),
+        fs_mosaic_change,
+    }};
     {
+        const fs_hook_tables13& all13 = all14.base13;
         const fs_hook_tables12& all12 = all13.base12;
         const fs_hook_tables11& all11 = all12.base11;
         const fs_hook_tables10& all10 = all11.base10;

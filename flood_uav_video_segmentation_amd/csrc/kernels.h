@@ -464,6 +464,14 @@ int launch_merge_patch(const uint32_t* rgba_b, int CH_b, int CW_b, int ox_b, int
                        int x0, int y1, int x1, uint8_t* tl, uint8_t* tv, long long* geom, hipStream_t s);
 int launch_link_place(const long long* found, const long long* link, int S, int max_mean, int ratio_permille, long long* cand, long long* out, hipStream_t s);
 
+// The flood-extent change between two registered mosaics (change_ops.hip, change_defs.h; definition: include/floodseg_test.h,
+// mosaic_change).  The launcher refuses bad arguments before it launches anything.  votes as launch_mosaic_merge takes
+// them, both only read; change, cls_a, cls_b = uint8 [CH_a][CW_a]; transitions = int64 [2][K][K]; counts = int64 [8].  No workspace;
+// nothing is allocated, synchronised or read on the host.
+int launch_mosaic_change(const uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint16_t* votes_b, int CH_b, int CW_b, int ox_b, int oy_b, int K,
+                         const long long* link, int min_votes, int min_conf, int tolerance, uint32_t watch_set, uint8_t* change, uint8_t* cls_a, uint8_t* cls_b,
+                         long long* transitions, long long* counts, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

@@ -652,6 +652,11 @@ class FlowPredictor:
         self._merges.append((link, outs, counts))
         return link
 
+    def change_against(self, part, **kw):
+        """Where another mosaic of the same ground (mosaic_part()'s dict, or read_mosaic_part()'s) differs from this predictor's, in this
+        one's canvas: mosaic_change(self.mosaic_part(), part, **kw).  Neither mosaic is changed; nothing is read back."""
+        return mosaic_change(self.mosaic_part(), part, **kw)
+
     def merge_report(self):
         """(links int64 numpy [parts, 16], outs: per part int64 [rows, 8] -- link_place's row first where a placement ran, then one
         link_correct row per round --, counts int64 [parts, 8]) of the parts merged since the start (or clear_report()).  The ONE read-back."""
@@ -1312,6 +1317,132 @@ def write_merge_csv(path, names, report):
             status = LINK_STATUS[link[12]] if 0 <= link[12] < len(LINK_STATUS) else "out_of_bounds"
             f.write(",".join([str(name), status] + [f"{v / (1 << 20):.6f}" for v in link[:6]] + [str(link[13]), str(link[14]), "/".join(str(int(r[0])) for r in out)]
                              + [str(v) for v in count[1:5]]) + "\n")
+
+
+# ---- the change between two mosaics of the same ground
+# ops.mosaic_change's six codes as ops.ortho_compose draws them (R, G, B, A): "not comparable" and "same" leave the imagery as it is
+CHANGE_PALETTE = np.array([[0, 0, 0, 0], [0, 0, 0, 0], [255, 255, 0, 96], [255, 0, 255, 176], [0, 64, 255, 208], [255, 128, 0, 208]], dtype=np.uint8)
+_CHANGE_KEYS = {"min_votes", "min_conf", "tolerance", "watch"}
+_CHANGE_REGISTER_KEYS = {"rounds", "search", "intra_bias", "fit_rounds", "tol", "min_inliers", "window", "place"}
+_CHANGE_REGION_KEYS = {"max_regions", "connectivity", "max_contours", "max_vertices", "simplify_rounds"}
+
+
+def mosaic_change(part_a, part_b, link=None, register=True, regions=False, min_region_area=0, outlines=False, simplify=None, **options):
+    """Where mosaic B differs from mosaic A, in A's canvas (mosaic_part()'s or read_mosaic_part()'s dicts on one device; B is usually the
+    later flight).  The two are NOT merged and neither is changed.  register=True: both need an orthophoto, and ops.register_mosaics
+    runs on their rgba planes from `link` (default: the identity with status 1; rounds, search, intra_bias, fit_rounds, tol, min_inliers,
+    window and place go to it, a place= without b_box taking B's seen box).  register=False: the link is used as given, and only a link
+    with status 0 compares anything.  Then ops.mosaic_change with min_votes, min_conf, tolerance and watch.  regions=True: the change
+    plane, a mask with the ids 0..5, goes through ops.mask_regions and ops.region_table with classes=6 (min_region_area > 1: and
+    ops.region_filter first; outlines=True: ops.region_outlines; simplify=TOL: ops.outline_simplify; max_regions, connectivity,
+    max_contours, max_vertices and simplify_rounds as FlowPredictor takes them), so every gained or lost area is a region with area,
+    box, centroid and polygon.  -> a dict of device tensors: change, cls_a, cls_b, transitions, counts (ops.mosaic_change's), link, outs
+    (register_mosaics' rows, None without), regions = (table, counts, index) or None, outlines and simplified = the ops' tuples or
+    None, tolerance = simplify.  Enqueues only; change_report() reads back.  The defaults are guesses, not validated on real video."""
+    unknown = set(options) - _CHANGE_KEYS - _CHANGE_REGISTER_KEYS - _CHANGE_REGION_KEYS
+    if unknown:
+        raise ValueError(f"mosaic_change: unknown options {sorted(unknown)}")
+    if tuple(int(v) for v in part_a["mask_size"]) != tuple(int(v) for v in part_b["mask_size"]):
+        raise ValueError(f"mosaic_change: both mosaics must be of masks of one size (a canvas pixel is a mask pixel of the anchor frame), got "
+                         f"{tuple(part_a['mask_size'])} and {tuple(part_b['mask_size'])}")
+    if part_a["votes"].shape[0] != part_b["votes"].shape[0]:
+        raise ValueError(f"mosaic_change: both mosaics must count the same classes, got {part_a['votes'].shape[0]} and {part_b['votes'].shape[0]}")
+    if register and (part_a.get("rgba") is None or part_b.get("rgba") is None):
+        raise ValueError("mosaic_change: register=True reads both orthophotos (mosaic parts made with ortho=); pass register=False with a registered link otherwise")
+    if not register and link is None:
+        raise ValueError("mosaic_change: register=False needs the link")
+    if (outlines or simplify is not None or min_region_area > 1) and not regions:
+        raise ValueError("mosaic_change: min_region_area, outlines and simplify go with regions=True")
+    if simplify is not None and not outlines:
+        raise ValueError("mosaic_change: simplify= goes with outlines=True")
+    dev = part_a["votes"].device
+    at, other = tuple(int(v) for v in part_a["origin"]), tuple(int(v) for v in part_b["origin"])
+    outs = None
+    if register:
+        kw = {k: v for k, v in options.items() if k in _CHANGE_REGISTER_KEYS}
+        if kw.get("place") is not None and "b_box" not in kw["place"] and part_b.get("box") is not None:
+            kw["place"] = dict(kw["place"], b_box=tuple(int(v) for v in part_b["box"]))
+        link = ops.mosaic_link(device=dev) if link is None else link.clone()
+        link, outs = ops.register_mosaics((part_a["rgba"], at), (part_b["rgba"], other), link, **kw)
+    elif set(options) & _CHANGE_REGISTER_KEYS:
+        raise ValueError(f"mosaic_change: {sorted(set(options) & _CHANGE_REGISTER_KEYS)} go with register=True")
+    change, cls_a, cls_b, transitions, counts = ops.mosaic_change(part_a["votes"], at, part_b["votes"], other, link,
+                                                                  **{k: v for k, v in options.items() if k in _CHANGE_KEYS})
+    result = dict(change=change, cls_a=cls_a, cls_b=cls_b, transitions=transitions, counts=counts, link=link, outs=outs, regions=None, outlines=None,
+                  simplified=None, tolerance=simplify)
+    if regions:
+        cap, conn = int(options.get("max_regions", 1024)), int(options.get("connectivity", 8))
+        mask = change[None]
+        labels = ops.mask_regions(mask, ops.CHANGE_CLASSES, conn)
+        table, region_counts, index = ops.region_table(mask, labels, ops.CHANGE_CLASSES, None, 128, cap)
+        if min_region_area > 1:
+            mask = ops.region_filter(mask, index, table, ops.CHANGE_CLASSES, min_region_area)
+            labels = ops.mask_regions(mask, ops.CHANGE_CLASSES, conn)
+            table, region_counts, index = ops.region_table(mask, labels, ops.CHANGE_CLASSES, None, 128, cap)
+            result["change"] = mask[0]
+        result["regions"] = (table, region_counts, index)
+        if outlines:
+            result["outlines"] = ops.region_outlines(index, cap, conn, int(options.get("max_contours", 4096)), int(options.get("max_vertices", 32768)))
+            if simplify is not None:
+                contours, vertices, _, outline_counts = result["outlines"]
+                result["simplified"] = ops.outline_simplify(contours, vertices, outline_counts, simplify, int(options.get("simplify_rounds", 32)))
+    return result
+
+
+def change_report(result):
+    """mosaic_change()'s result on the host -- the ONE place that reads back: counts int64 numpy [8], transitions [2, K, K], link [16], outs
+    [rows, 8] or None; with regions: rows = [int64 [regions, 10]] as FlowPredictor.region_report() hands a frame's (what
+    write_regions_csv and write_outlines_geojson take, with frame_ids = [0]); outlines and simplified as outline_report() and
+    simple_outline_report() hand them, for that one frame; shapes = [the regions' (perimeter, contours, vertices)]."""
+    host = lambda t: t.cpu().numpy()  # noqa: E731
+    report = dict(counts=host(result["counts"]), transitions=host(result["transitions"]), link=host(result["link"]),
+                  outs=None if result["outs"] is None else host(result["outs"]), rows=None, outlines=None, simplified=None, shapes=None, tolerance=result["tolerance"])
+    if result["regions"] is not None:
+        table, counts, _ = result["regions"]
+        written = int(host(counts)[0, 1])
+        report["rows"] = [host(table)[0, :written]]
+        if result["outlines"] is not None:
+            contours, vertices, shape, c = (host(t) for t in result["outlines"])
+            total = 0 if c[0, 3] & 1 else int(c[0, 2])
+            report["outlines"] = ([(contours[0, :int(c[0, 1])], vertices[0, :total], shape[0, :written])], c[:, 3])
+            report["shapes"] = [shape[0, :written]]
+            if result["simplified"] is not None:
+                simple, kept, sc = (host(t) for t in result["simplified"])
+                report["simplified"] = ([(simple[0, :int(sc[0, 0])], kept[0, :int(sc[0, 1])])], sc)
+    return report
+
+
+def write_change_csv(path, report, class_names=None):
+    """change_report()'s counts and transitions as one CSV of two tables.  First one row per class pair that has a comparable pixel: the
+    class in A (`from`), the class in B (`to`), the comparable pixels and of those the changed ones (code >= 3: not the same and not
+    explained by the tolerance).  Then, after an empty line, the eight counts by name."""
+    counts, pairs = np.asarray(report["counts"]).tolist(), np.asarray(report["transitions"])
+    k = pairs.shape[1]
+    name = (lambda c: str(c)) if class_names is None else (lambda c: str(class_names[c]))
+    with open(path, "w", newline="") as f:
+        f.write("from,to,comparable,changed\n")
+        for ca in range(k):
+            for cb in range(k):
+                if pairs[0, ca, cb]:
+                    f.write(f"{name(ca)},{name(cb)},{int(pairs[0, ca, cb])},{int(pairs[1, ca, cb])}\n")
+        f.write("\nlink,reached,comparable," + ",".join(ops.CHANGE_CODES[1:]) + "\n")
+        f.write(",".join([LINK_STATUS[counts[0]] if 0 <= counts[0] < len(LINK_STATUS) else "out_of_bounds"] + [str(v) for v in counts[1:]]) + "\n")
+
+
+def change_image(result, rgba=None, palette=CHANGE_PALETTE, fill=(0, 0, 0)):
+    """The change plane drawn over mosaic A's orthophoto (rgba = part_a["rgba"]) through ops.ortho_compose, or over a plain fill without
+    one -> uint8 [CH, CW, 3] on the device.  Codes 0 and 1 of CHANGE_PALETTE have alpha 0: only what differs is drawn."""
+    change = result["change"]
+    if rgba is None:
+        rgba = torch.zeros(tuple(change.shape), dtype=torch.int32, device=change.device)  # never seen: the fill shows everywhere
+    return ops.ortho_compose(rgba, change, palette, fill=fill)
+
+
+def write_change_png(path, result, rgba=None, palette=CHANGE_PALETTE, fill=(0, 0, 0)):
+    """change_image() as a PNG (the read-back of the picture happens here)."""
+    from PIL import Image
+
+    Image.fromarray(change_image(result, rgba, palette, fill).cpu().numpy()).save(path)
 
 
 def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):

@@ -1589,6 +1589,55 @@ def register_mosaics(a, b, link, rounds=2, search=16, intra_bias=0, fit_rounds=4
     return link, torch.stack(outs)
 
 
+# ------------------------------------------------------------------------------------------ the change between two registered mosaics
+CHANGE_CODES = ("not_comparable", "same", "explained", "changed", "gained", "lost")  # the values of mosaic_change's change plane
+CHANGE_CLASSES = len(CHANGE_CODES)  # the change plane as a mask for ops.mask_regions and ops.region_table
+CHANGE_MAX_TOLERANCE = 8
+
+
+def mosaic_change(votes_a, origin_a, votes_b, origin_b, link, min_votes=1, min_conf=0, tolerance=1, watch=(1,)):
+    """Where two mosaics of the same ground differ, in A's canvas, under a registered link (definition: include/floodseg_test.h,
+    mosaic_change).  votes_a, votes_b: uint16 [K,CH,CW] with one K, only read; origin_* = (oy, ox); link int64 [16] of
+    ops.register_mosaics.  A pixel's class is mosaic_resolve's winner where its votes reach min_votes (1..65535) and the winner's share
+    min_conf (0..255), else 255; B's pixel under each A pixel comes through mosaic_merge's gather.  tolerance = r (0..8 pixels): a pixel
+    whose two classes differ is "explained" where B holds A's class and A holds B's class within r pixels.  watch: the class ids that
+    count as water.  -> (change, cls_a, cls_b, transitions, counts): change uint8 [CH_a,CW_a] with 0 not comparable, 1 same, 2
+    explained, 3 changed between two watched or two other classes, 4 gained (A not watched, B watched), 5 lost; cls_a, cls_b uint8
+    [CH_a,CW_a]; transitions int64 [2,K,K], [0][ca][cb] the comparable pixels and [1][ca][cb] those with code >= 3; counts int64 [8] =
+    (link status, A pixels whose B pixel exists, comparable, same, explained, changed, gained, lost).  A link whose status is not 0
+    compares nothing (all 0); that is decided on the device.  Three launches; nothing is read back.
+    The defaults are guesses, not validated on real video."""
+    lib = _lib.load()
+    what = "floodseg.mosaic_change"
+    votes_a, votes_b = _mosaic_votes(votes_a, what), _mosaic_votes(votes_b, what)
+    if votes_a.shape[0] != votes_b.shape[0]:
+        raise ValueError(f"{what}: both vote canvases must have one K, got {votes_a.shape[0]} and {votes_b.shape[0]}")
+    oy_a, ox_a = _mosaic_origin(origin_a, what)
+    oy_b, ox_b = _mosaic_origin(origin_b, what)
+    _relocate_row(link, 16, "link", what)
+    if not 1 <= int(min_votes) <= 65535:
+        raise ValueError(f"{what}: min_votes must be 1..65535, got {min_votes}")
+    if not 0 <= int(min_conf) <= 255:
+        raise ValueError(f"{what}: min_conf must be 0..255, got {min_conf}")
+    if not 0 <= int(tolerance) <= CHANGE_MAX_TOLERANCE:
+        raise ValueError(f"{what}: tolerance must be 0..{CHANGE_MAX_TOLERANCE} pixels, got {tolerance}")
+    k = votes_a.shape[0]
+    watch_set = class_set(watch, "watch", what, allow_empty=True)
+    if watch_set >> k:
+        raise ValueError(f"{what}: watch must be class ids below K = {k}, got {list(watch)}")
+    if _same_memory(votes_a, votes_b):
+        raise ValueError(f"{what}: A and B are the same memory (votes at {votes_a.data_ptr():#x})")
+    dev = one_device(votes_a, votes_b, link, what=what)
+    with torch.cuda.device(dev):
+        change, cls_a, cls_b = (torch.empty(tuple(votes_a.shape[1:]), dtype=torch.uint8, device=dev) for _ in range(3))
+        transitions = torch.empty((2, k, k), dtype=torch.int64, device=dev)
+        counts = torch.empty((8,), dtype=torch.int64, device=dev)
+        check(lib.fs_mosaic_change(ptr(votes_a), votes_a.shape[1], votes_a.shape[2], ox_a, oy_a, ptr(votes_b), votes_b.shape[1], votes_b.shape[2], ox_b, oy_b, k,
+                                   ptr(link), int(min_votes), int(min_conf), int(tolerance), watch_set, ptr(change), ptr(cls_a), ptr(cls_b), ptr(transitions),
+                                   ptr(counts), stream_ptr()))
+    return change, cls_a, cls_b, transitions, counts
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

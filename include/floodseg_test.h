@@ -1382,6 +1382,70 @@ typedef struct fs_hook_tables13 {
     fs_ext13_api ext13;
 } fs_hook_tables13;
 
+/* ---- The FIFTEENTH table.  fs_ext13_api is frozen as well (6 members, 64 bytes; tests/test_change_cpu.py), so ops added since live in
+ * a table of their own, append-only, that the library places directly behind fs_hook_tables13 by the same pattern:
+ *     const fs_hook_tables14* t = (const fs_hook_tables14*)fs_test_hooks();   t->ext14.mosaic_change(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables13: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext14.magic == FS_EXT14_MAGIC and ext14.size >= the end of the member it needs. */
+#define FS_EXT14_MAGIC 0x4653455854413134ull /* "FSEXTA14" */
+
+typedef struct fs_ext14_api {
+    uint64_t magic; /* FS_EXT14_MAGIC */
+    size_t size;    /* sizeof(fs_ext14_api) of the library that was built */
+
+    /* ---- THE FLOOD-EXTENT CHANGE BETWEEN TWO REGISTERED MOSAICS (csrc/change_ops.hip, csrc/change_defs.h).  OUR DEFINITION:
+     * the reference has nothing like it.  Two vote canvases of the same ground, A and B, under a link that ops of the fourteenth table
+     * registered, are compared class by class IN A'S CANVAS; neither canvas is changed.  The same rules as code: csrc/change_defs.h (host
+     * and device) and tests/change_ref.py (numpy).  All integer, bit for bit.
+     *
+     * votes_a uint16 [K][CH_a][CW_a] with origin (ox_a, oy_a), votes_b uint16 [K][CH_b][CW_b] with origin (ox_b, oy_b), the same K in
+     * 1..32; link int64 [16] as the fourteenth table defines it; min_votes 1..65535, min_conf 0..255, tolerance r 0..8 pixels;
+     * watch_set: bit k for k < K.
+     *
+     * THE DECIDED CLASS of a canvas pixel: with total = the sum of its K counts and most = the largest, taken by the first class that
+     * has it (mosaic_resolve's winner: strictly more votes, so the lowest id on a tie), it is that class iff total >= min_votes and
+     * vote_confidence(most, total) = (255 most + total / 2) / total >= min_conf; 255 otherwise.
+     *
+     * THE CLASS PLANES, uint8 [CH_a][CW_a], always written whole: cls_a[Y][X] is the decided class of A's pixel; cls_b[Y][X] the
+     * decided class of the B pixel under it through THE GATHER of the fourteenth table, 255 where that pixel does not exist, and 255
+     * everywhere unless the link's status is 0 and it is in bounds (decided on the device, as in mosaic_merge).
+     *
+     * THE WINDOW SETS: win_a(X, Y) is the OR of 1u << cls_a over the pixels of [X - r, X + r] x [Y - r, Y + r] that lie inside A's
+     * canvas and whose cls_a is not 255; win_b(X, Y) the same over cls_b.
+     *
+     * THE CHANGE CODE, change uint8 [CH_a][CW_a], with ca = cls_a and cb = cls_b at the pixel, the first that applies:
+     *   0  not comparable: ca or cb is 255;
+     *   1  same: ca == cb;
+     *   2  differs, but explained by a shift of at most r pixels: bit ca is in win_b AND bit cb is in win_a (never with r = 0);
+     *   3  changed, ca and cb both in watch_set or both outside it;
+     *   4  gained: ca not in watch_set, cb in it ("flooded" when B is the later flight and watch_set is water);
+     *   5  lost: ca in watch_set, cb not.
+     * Both tests of code 2 are needed: a misregistration of at most r pixels passes both, and a class B brings that A holds nowhere
+     * within r keeps every one of its pixels.
+     *
+     * transitions int64 [2][K][K]: [0][ca][cb] counts the comparable pixels (code >= 1), [1][ca][cb] those with code >= 3.
+     * counts int64 [8] = (the link's status, A pixels whose B pixel exists, comparable, same, explained, changed-other, gained, lost).
+     * Under a link that does not merge counts = (status, 0, ...), transitions and change are all 0.
+     *
+     * THREE launches on one stream: a kernel that clears counts and transitions; change_classes, one workgroup of 256 per 64 x 16 tile
+     * of A, a thread owning a column of four rows and looping over K (a tile that B's canvas rectangle cannot reach resolves A and
+     * writes 255 to cls_b without touching B); change_codes on the same tiles, 1u << cls of both planes staged in LDS for the tile plus
+     * an apron of r pixels clipped at the canvas edge, the window OR done separably (rows, then columns), r = 0 an instantiation of its
+     * own that stages nothing.  Every plane pixel has one owner; counts and transitions go through an LDS tally of 8 + 2 K^2 dwords
+     * and one 64-bit atomic per workgroup and non-zero cell.  Nothing else takes an atomic.
+     * Refused before a launch: a null pointer; K outside 1..32; CH or CW of A or B outside 1..16384; |ox| or |oy| > 16384; min_votes
+     * outside 1..65535, min_conf outside 0..255, tolerance outside 0..8; a watch_set bit at or above K; votes_a == votes_b; an output
+     * that overlaps an input; votes not aligned to 2, link, counts or transitions not aligned to 8 bytes. */
+    int (*mosaic_change)(const uint16_t* votes_a, int CH_a, int CW_a, int ox_a, int oy_a, const uint16_t* votes_b, int CH_b, int CW_b, int ox_b, int oy_b, int K,
+                         const int64_t* link, int min_votes, int min_conf, int tolerance, uint32_t watch_set, uint8_t* change, uint8_t* cls_a, uint8_t* cls_b,
+                         int64_t* transitions, int64_t* counts, fs_stream stream);
+} fs_ext14_api;
+
+typedef struct fs_hook_tables14 {
+    fs_hook_tables13 base13;
+    fs_ext14_api ext14;
+} fs_hook_tables14;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus

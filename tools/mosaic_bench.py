@@ -4,7 +4,8 @@ costs -- and ops.mosaic_resolve, the report's, on one 1072 x 1920 five-frame win
 Device events, medians of 20 groups of 5 back-to-back calls, eagerly through the Python wrappers and as a captured graph replayed; the
 clock read before and after.  Next to mosaic_accumulate its byte floor: the mask bytes read plus 2 B read and 2 B written per touched
 vote, at 8 TB/s.  Then the four per-merge calls of DESIGN §3.23 (ops.merge_view, ops.merge_gate, ops.link_correct, ops.mosaic_merge) on
-two such canvases, B over a quarter of A and over all of it, each next to the bytes it must move.  Prints to stdout."""
+two such canvases, B over a quarter of A and over all of it, each next to the bytes it must move.  Last ops.mosaic_change (DESIGN §3.24,
+profiles/r31_change.txt) on the same two pairs at tolerance 0, 1, 3 and 8; `--change-only` runs that part alone.  Prints to stdout."""
 import os
 import statistics
 import subprocess
@@ -91,7 +92,41 @@ def pose_rows(scale, shifts):
     return torch.tensor(rows, dtype=torch.int64, device="cuda")
 
 
+def change_section():
+    """ops.mosaic_change: the three launches of one call, B over a quarter of A and over all of it.  Votes of a blocky class
+    map with 5 % noise on both sides, so that almost every pixel of a tile lands in one (ca, cb) cell, as on a real map.  MB moved:
+    change_classes reads 2K B of A a pixel and 2K B of B a reached pixel and writes 2 B; change_codes reads 2 B and writes 1 B a pixel
+    (the aprons are not counted)."""
+    say()
+    say(f"the change between two {CANVAS[0]} x {CANVAS[1]} mosaics, K = {K}: the link is registered and exact; origins (0, 0); min_votes 1, min_conf 0, watch (1,)")
+    say(f"{'call':<58}{'eager us':>10}{'min':>9}{'max':>9}{'graph us':>10}{'MB moved':>10}{'floor us':>10}{'floor/graph':>12}")
+
+    def votes_of(size, seed):
+        r = np.random.RandomState(seed)
+        cls = np.kron(r.randint(0, K, (size[0] // 32 + 1, size[1] // 32 + 1)), np.ones((32, 32), np.int64))[:size[0], :size[1]]
+        cls = np.where(r.rand(*size) < 0.05, r.randint(0, K, size), cls)
+        v = r.randint(0, 3, size=(K,) + tuple(size)).astype(np.int16)
+        v[cls, np.arange(size[0])[:, None], np.arange(size[1])[None, :]] += 20
+        return torch.from_numpy(v).cuda().view(torch.uint16)
+
+    votes_a = votes_of(CANVAS, 2)
+    pixels = CANVAS[0] * CANVAS[1]
+    for name, (bh, bw), (ty, tx) in (("B over a quarter of A", (CANVAS[0] // 2, CANVAS[1] // 2), (CANVAS[0] // 4, CANVAS[1] // 4)), ("B over all of A", CANVAS, (0, 0))):
+        votes_b = votes_of((bh, bw), 3)
+        link = ops.mosaic_link([ONE, 0, tx * ONE, 0, ONE, ty * ONE], [ONE, 0, -tx * ONE, 0, ONE, -ty * ONE], ops.LINK_REGISTERED, "cuda")
+        moved = 2 * K * pixels + 2 * K * bh * bw + 2 * pixels + 3 * pixels
+        for r in (0, 1, 3, 8):
+            row(f"mosaic_change, tolerance {r}, {name}", lambda: ops.mosaic_change(votes_a, (0, 0), votes_b, (0, 0), link, 1, 0, r, (1,)), moved)
+        counts = ops.mosaic_change(votes_a, (0, 0), votes_b, (0, 0), link, 1, 0, 1, (1,))[4].cpu().numpy()
+        say(f"  (counts at tolerance 1: {counts.tolist()}; eager includes the wrapper's five output allocations)")
+
+
 torch.set_grad_enabled(False)
+if "--change-only" in sys.argv[1:]:
+    say(f"clock before: {clocks()}")
+    change_section()
+    say(f"clock after: {clocks()}")
+    sys.exit(0)
 rng = np.random.RandomState(0)
 base = np.kron(rng.randint(0, 5, (H // 16 + 2, W // 16 + 2)), np.ones((16, 16), np.int64))
 frames = np.stack([base[f:f + H, 2 * f:2 * f + W] for f in range(N)])
@@ -173,4 +208,5 @@ for name, (bh, bw), (ty, tx) in (("B over a quarter of A", (CANVAS[0] // 2, CANV
     counts = ops.mosaic_merge(va, (0, 0), votes_b, (0, 0), link, (ra, ca), (rank_b, rgba_b), 7, "centre").cpu().numpy()
     say(f"  (counts {counts[:5].tolist()}; MB moved: 2 B of B and 2 + 2 B of A per class and reached pixel, + the two rank words; repeated calls saturate")
     say("   the votes but read and write the same cells; the orthophoto takes its pixels in the FIRST call only: the 12 B written per pixel won are not in these times)")
+change_section()
 say(f"clock after: {clocks()}")
