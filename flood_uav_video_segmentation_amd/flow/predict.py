@@ -50,55 +50,12 @@ import torch
 from .. import _lib, ops
 from .._lib import check, ptr, stream_ptr
 from . import crops
+from .frame_rows import FrameRows
+from .mosaic import (CHANGE_PALETTE, LINK_STATUS, MOSAIC_STATUS, PART_ARRAYS, REFINE_STATUS, RELOCATE_STATUS, _CHANGE_KEYS, _CHANGE_REGION_KEYS,  # noqa: F401
+                     _CHANGE_REGISTER_KEYS, MosaicBuilder, _compose_q20, change_image, change_report, merge_part, mosaic_change, mosaic_part_arrays, part_seen_box,
+                     read_mosaic_part, write_change_csv, write_change_png, write_merge_csv, write_mosaic_csv, write_mosaic_part, write_relocate_csv)
 
 PALETTE = np.array(ops.FLOOD_PALETTE, dtype=np.uint8)  # dataset/flow/list/colors.txt (one table: ops.ortho_compose's default is the same object)
-
-
-class FrameRows:
-    """One stage's per-frame device tables: parallel buffers, `spec` = one (shape of a frame's rows, dtype) each, allocated a chunk of
-    frames at a time -- one allocation per chunk, not one per window -- and filled in frame order; nothing is read back before a report
-    asks.  Every chunk is zero-filled: the reports trim a frame's rows by a counts column and hand out rows nobody wrote.  The chunk
-    size is an argument of every call, not kept here: the predictor's REPORT_CHUNK, outline_chunk and simple_chunk may be set at any
-    time before the first window, and without a reference back to the predictor the buffers are freed with it."""
-
-    def __init__(self, *spec):
-        self.spec = spec
-        self.clear()
-
-    def clear(self):
-        self.chunks = []  # one tuple of buffers [chunk, *shape] per chunk, in frame order
-        self.frames = 0   # frames written: the newest chunk is filled up to frames % chunk
-
-    def rows(self, row, take, chunk, device):
-        """Views of rows row .. row + take - 1 of the newest chunk, one per buffer; row == 0 starts a new chunk on `device`.  Called
-        directly by a table that keeps in step with another one's pieces(): that one counts the frames for both."""
-        if row == 0:
-            self.chunks.append(tuple(torch.zeros((chunk,) + tuple(shape), dtype=dtype, device=device) for shape, dtype in self.spec))
-        return tuple(b[row:row + take] for b in self.chunks[-1])
-
-    def pieces(self, n, chunk, device):
-        """The next n frames, cut at the chunk borders: yields (done, take, row, views) -- frames done .. done + take - 1 of the n go
-        into rows row .. of the newest chunk, which `views` are.  The frames count once the caller comes back for the next piece."""
-        done = 0
-        while done < n:
-            row = self.frames % chunk
-            take = min(n - done, chunk - row)
-            yield done, take, row, self.rows(row, take, chunk, device)
-            done += take
-            self.frames += take
-
-    def filled(self, chunk, *followers):
-        """Chunk by chunk (take, views of the rows written), for a report that reads back one chunk at a time; with followers -- tables
-        kept in step with this one through rows() -- the views of each of them after its own."""
-        left = self.frames
-        for i, buffers in enumerate(self.chunks):
-            take = min(left, chunk)
-            yield (take,) + tuple(tuple(b[:take] for b in t.chunks[i]) for t in (self,) + followers)
-            left -= take
-
-    def flat(self):
-        """The first buffer's rows written, as ONE device tensor (a copy), for a report that reads back once."""
-        return torch.cat([buffers[0] for buffers in self.chunks])[:self.frames]
 
 
 class FlowPredictor:
@@ -200,7 +157,9 @@ class FlowPredictor:
     own); up to mosaic_bridge failed pairs running are bridged with the last good model, after which -- or at a scene cut -- the chain is
     lost and the frames vote nowhere.  mosaic_report() resolves the canvas and reads back once; clear_report() drops canvas and state
     (the next frame anchors a new mosaic), reset() keeps them.  All these defaults are guesses, NOT validated on real video; an affine
-    per pair is not a homography, the chain drifts over a long flight and nothing closes loops.
+    per pair is not a homography, the chain drifts over a long flight and nothing closes loops.  This and the stages below are
+    flow/mosaic.py's: the predictor always makes ONE MosaicBuilder of its arguments (mosaic_builder; mosaic=None: one that is off) and hands it
+    every window's masks; but for the switches mosaic, ortho, mosaic_refine and mosaic_relocate, settings and state are the builder's alone.
 
     ortho="centre" | "latest" (extension, needs mosaic=; None: off, and none of its ops is ever called): the orthophoto under that mosaic
     (DESIGN §3.19).  Every window must then also come with link_sources (the datasets' link_sources=True): after the pose chain each
@@ -211,7 +170,7 @@ class FlowPredictor:
     counter, reset() keeps them.  No feathering or exposure matching across seams, no lens model, the mask's resolution, and the chain's
     drift shows as broken seams; NOT validated on real video.
 
-    mosaic_refine=True (extension, needs ortho=; False: off, none of its ops is ever called and _keep_mosaic's calls are what they were):
+    mosaic_refine=True (extension, needs ortho=; False: off, none of its ops is ever called and MosaicBuilder.add's calls are what they were):
     frame-to-map registration.  The window is then walked frame by frame: pose_chain with n = 1; for a frame whose ordinal
     is a multiple of refine_every and whose source exists, ops.map_view draws the orthophoto canvas as the frame should see it under that
     pose, ops.block_match_modes (refine_search 1..32, refine_penalty, refine_intra_bias) matches the frame against it, ops.map_gate voids
@@ -236,7 +195,6 @@ class FlowPredictor:
     ground voted before the break is never re-posed; all these defaults are guesses, NOT validated on real video."""
 
     REPORT_CHUNK = 256  # frames per device buffer of the report: one allocation per 256 frames, not one per window
-    ORTHO_MAX_FRAMES = 1 << 31  # ordinals 0 .. 2^31 - 1: what ortho_report()'s int32 src can name
 
     def __init__(self, flow_model, classes=5, out_size=(1072, 1920), crop=None, compute_metrics=True, ignore_index=255,
                  cache_keyframes=False, confidence=False, low_confidence=128, regions=False, min_region_area=0, connectivity=8,
@@ -350,79 +308,14 @@ class FlowPredictor:
         self.proximity_targets = tuple(int(c) for c in proximity_targets)
         self.proximity_max = int(proximity_max or 0) if self.proximity else 0
         self._proximity = FrameRows(((classes, len(self.proximity or ())), torch.int64), ((self.max_regions, 8), torch.int64))  # (exposure, near), in step with _regions
-        self.mosaic = None
-        self.mosaic_classes = self.classes if mosaic_classes is None else int(mosaic_classes)
-        if mosaic is not None:
-            size = tuple(int(v) for v in mosaic)
-            if len(size) != 2 or any(not 1 <= v <= 16384 for v in size):
-                raise ValueError(f"FlowPredictor: mosaic must be the canvas size (CH, CW) with 1..16384 pixels a side, got {mosaic}")
-            if not 1 <= self.mosaic_classes <= 32:
-                raise ValueError(f"FlowPredictor: mosaic_classes must be 1..32, got {self.mosaic_classes}")
-            if not 0 <= int(mosaic_rounds) <= 8:
-                raise ValueError(f"FlowPredictor: mosaic_rounds must be 0..8, got {mosaic_rounds}")
-            if not 0 <= float(mosaic_tol) <= 64:
-                raise ValueError(f"FlowPredictor: mosaic_tol must be 0..64 frame pixels, got {mosaic_tol}")
-            if not 3 <= int(mosaic_min_inliers) <= 1 << 20:
-                raise ValueError(f"FlowPredictor: mosaic_min_inliers must be 3..2^20, got {mosaic_min_inliers}")
-            ops.class_set(mosaic_exclude, "mosaic_exclude", "FlowPredictor", allow_empty=True)
-            if not 0 <= int(mosaic_bridge) <= 64:
-                raise ValueError(f"FlowPredictor: mosaic_bridge must be 0..64 frame pairs, got {mosaic_bridge}")
-            if mosaic_origin is not None and (len(tuple(mosaic_origin)) != 2 or any(abs(int(v)) > 16384 for v in mosaic_origin)):
-                raise ValueError(f"FlowPredictor: mosaic_origin must be (oy, ox) within 16384 pixels of the canvas corner (None: the anchor frame is "
-                                 f"centred), got {mosaic_origin}")
-            self.mosaic = size
-        self.mosaic_rounds = int(mosaic_rounds)
-        self.mosaic_tol = float(mosaic_tol)
-        self.mosaic_min_inliers = int(mosaic_min_inliers)
-        self.mosaic_exclude = tuple(int(c) for c in mosaic_exclude)
-        self.mosaic_bridge = int(mosaic_bridge)
-        self.mosaic_origin = None if mosaic_origin is None else tuple(int(v) for v in mosaic_origin)
-        self._mosaic_votes = None   # uint16 [K, CH, CW] on the device, with the chain's state int64 [32] and the origin in use
-        self._mosaic_state = None
-        self._mosaic_at = None
-        self._mosaic_poses = FrameRows(((16,), torch.int64))  # the per-frame pose rows, REPORT_CHUNK frames a chunk
+        # the mosaic family's settings and state (flow/mosaic.py): checked and kept there, also when mosaic is None
+        self.mosaic_builder = MosaicBuilder(mosaic, self.classes if mosaic_classes is None else mosaic_classes, mosaic_rounds, mosaic_tol, mosaic_min_inliers,
+                                            mosaic_exclude, mosaic_bridge, mosaic_origin, ortho, mosaic_refine, refine_search, refine_penalty, refine_intra_bias,
+                                            refine_min_age, refine_every, mosaic_relocate, relocate_scale, relocate_every, relocate_min_overlap, relocate_exclude,
+                                            relocate_max_mean, relocate_ratio, chunk=self.REPORT_CHUNK)
+        self.mosaic, self.ortho = self.mosaic_builder.size, ortho  # the switches this class's own control flow reads
+        self.mosaic_refine, self.mosaic_relocate = bool(mosaic_refine), bool(mosaic_relocate)
         self._guide_counts = FrameRows(((8,), torch.int64))   # the windows' link_guide_counts rows (the datasets' guide=True), as they come
-        if ortho is not None and ortho not in ops.ORTHO_MODES:
-            raise ValueError(f"FlowPredictor: ortho must be None or one of {sorted(ops.ORTHO_MODES)}, got {ortho!r}")
-        if ortho is not None and self.mosaic is None:
-            raise ValueError(f"FlowPredictor: ortho={ortho!r} needs mosaic=(CH, CW): the orthophoto is gathered with the mosaic's poses, onto its canvas")
-        self.ortho = ortho
-        self._ortho_planes = None  # (rank, rgba) [CH, CW] on the device
-        self._ortho_frames = 0     # frames since the anchor: the next frame's ordinal
-        if mosaic_refine and not ortho:
-            raise ValueError("FlowPredictor: mosaic_refine=True needs ortho='centre' or 'latest': a frame is registered against the orthophoto canvas")
-        if not 1 <= int(refine_search) <= 32:
-            raise ValueError(f"FlowPredictor: refine_search must be 1..32 pixels, got {refine_search}")
-        if not 0 <= int(refine_penalty) <= 255 or not 0 <= int(refine_intra_bias) <= 65535:
-            raise ValueError(f"FlowPredictor: refine_penalty must be 0..255 and refine_intra_bias 0..65535, got {refine_penalty} and {refine_intra_bias}")
-        if not 0 <= int(refine_min_age) < 1 << 31:
-            raise ValueError(f"FlowPredictor: refine_min_age must be 0..2^31 - 1 frames, got {refine_min_age}")
-        if int(refine_every) < 1:
-            raise ValueError(f"FlowPredictor: refine_every must be at least 1, got {refine_every}")
-        self.mosaic_refine = bool(mosaic_refine)
-        self.refine_search, self.refine_penalty, self.refine_intra_bias = int(refine_search), int(refine_penalty), int(refine_intra_bias)
-        self.refine_min_age, self.refine_every = int(refine_min_age), int(refine_every)
-        self._refine_outs = FrameRows(((8,), torch.int64))  # pose_correct's out rows, kept in step with _mosaic_poses
-        if mosaic_relocate and not mosaic_refine:
-            raise ValueError("FlowPredictor: mosaic_relocate=True needs mosaic_refine=True: a coarse placement is committed only through the fine registration")
-        if relocate_scale not in ops.RELOCATE_SCALES:
-            raise ValueError(f"FlowPredictor: relocate_scale must be one of {list(ops.RELOCATE_SCALES)}, got {relocate_scale!r}")
-        if int(relocate_every) < 1:
-            raise ValueError(f"FlowPredictor: relocate_every must be at least 1, got {relocate_every}")
-        if not 0.001 <= float(relocate_min_overlap) <= 1.0 or not 0.001 <= float(relocate_ratio) <= 1.0:
-            raise ValueError(f"FlowPredictor: relocate_min_overlap and relocate_ratio must be 0.001..1, got {relocate_min_overlap} and {relocate_ratio}")
-        if not 0 <= int(relocate_exclude) <= 64:
-            raise ValueError(f"FlowPredictor: relocate_exclude must be 0..64 cells, got {relocate_exclude}")
-        if not 0 <= int(relocate_max_mean) <= 255:
-            raise ValueError(f"FlowPredictor: relocate_max_mean must be 0..255, got {relocate_max_mean}")
-        self.mosaic_relocate = bool(mosaic_relocate)
-        self.relocate_scale, self.relocate_every, self.relocate_exclude = int(relocate_scale), int(relocate_every), int(relocate_exclude)
-        self.relocate_min_overlap, self.relocate_ratio = int(round(1000 * float(relocate_min_overlap))), int(round(1000 * float(relocate_ratio)))  # permille
-        self.relocate_max_mean = int(relocate_max_mean)
-        self._relocate_outs = FrameRows(((8,), torch.int64))  # relocate_commit's out rows, kept in step with _mosaic_poses
-        self._mosaic_mask = None   # (H, W) of the masks the mosaic was anchored with
-        self._mosaic_tail = None   # int64 [12] on the device once a part has been merged: the last merged frame's two poses
-        self._merges = []          # per merged part (link, register_mosaics' out rows, mosaic_merge's counts), on the device
 
     # the chunk lists that tests count, under the names they had before the tables moved into FrameRows
     _report_chunks = property(lambda self: self._extent.chunks)
@@ -442,14 +335,10 @@ class FlowPredictor:
 
     def clear_report(self):
         """Forget the extent report and the region report of the frames predicted so far."""
-        for table in (self._extent, self._regions, self._tracks, self._outlines, self._simple, self._stabilize_counts, self._proximity, self._mosaic_poses,
-                      self._refine_outs, self._relocate_outs, self._guide_counts):
+        for table in (self._extent, self._regions, self._tracks, self._outlines, self._simple, self._stabilize_counts, self._proximity, self._guide_counts):
             table.clear()  # the tracks' previous frame and next id stay, and so does the stabiliser's state plane
         self._despeckle_counts = []
-        self._mosaic_votes = self._mosaic_state = self._mosaic_at = None  # the next frame anchors a new mosaic
-        self._ortho_planes, self._ortho_frames = None, 0
-        self._mosaic_mask = self._mosaic_tail = None
-        self._merges = []
+        self.mosaic_builder.clear()  # the next frame anchors a new mosaic
 
     def extent_report(self):
         """confidence=True: int64 numpy [frames, K, 3] for every frame predicted since the start (or clear_report()), in the order
@@ -534,105 +423,13 @@ class FlowPredictor:
         """What _link_inputs returned, for the tracks: theirs only under compensate=True (stabilize_compensate=True alone leaves them in place)."""
         return link if self.compensate else None
 
-    def _keep_mosaic(self, masks, link, sources=None):
-        """The window's masks into the vote canvas: one camera-motion model per frame pair from the window's tables, the pose chain carried
-        on in its device state, the gather, and the pose rows into the next rows of the chunked buffers (nothing is read back).  ortho=:
-        then each frame's pixels into the orthophoto canvas, with that frame's pose row."""
-        masks = masks.contiguous()
-        n, h, w = masks.shape
-        dev = masks.device
-        if self._mosaic_votes is None:
-            ch, cw = self.mosaic
-            self._mosaic_votes = torch.zeros((self.mosaic_classes, ch, cw), dtype=torch.int16, device=dev).view(torch.uint16)  # the same zero bits
-            self._mosaic_state = torch.zeros((32,), dtype=torch.int64, device=dev)
-            self._mosaic_at = self.mosaic_origin if self.mosaic_origin is not None else ((ch - h) // 2, (cw - w) // 2)
-            self._mosaic_mask = (h, w)
-        model = ops.global_motion(link[0] if link[3] is None else link[3], link[1], (h, w), self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks,
-                                  exclude=self.mosaic_exclude, pair_stats=link[2])
-        if self.mosaic_refine:
-            poses, outs, relocs = self._refined_poses(masks, model, sources)
-        else:
-            poses = ops.pose_chain(model, self._mosaic_state, (h, w), self.mosaic, self._mosaic_at, self.mosaic_bridge)
-        ops.mosaic_accumulate(masks, poses, self._mosaic_votes, self._mosaic_at)
-        for done, take, row, (rows,) in self._mosaic_poses.pieces(n, self.REPORT_CHUNK, dev):
-            rows.copy_(poses[done:done + take])
-            if self.mosaic_refine:
-                self._refine_outs.rows(row, take, self.REPORT_CHUNK, dev)[0].copy_(outs[done:done + take])
-            if self.mosaic_relocate:
-                self._relocate_outs.rows(row, take, self.REPORT_CHUNK, dev)[0].copy_(relocs[done:done + take])
-        if self.mosaic_relocate:
-            self._relocate_outs.frames = self._mosaic_poses.frames
-        if self.mosaic_refine:
-            self._refine_outs.frames = self._mosaic_poses.frames
-        elif self.ortho:
-            if self._ortho_planes is None:
-                self._ortho_planes = ops.ortho_canvas(self.mosaic, dev)
-            for p in range(n):
-                if sources[p] is not None:
-                    ops.ortho_accumulate(sources[p], poses[p], self._ortho_frames + p, (h, w), *self._ortho_planes, self._mosaic_at, self.ortho)
-            self._ortho_frames += n
-
-    def _refined_poses(self, masks, model, sources):
-        """mosaic_refine=True: the window walked frame by frame -> (poses [n, 16], pose_correct's out rows [n, 8], relocate_commit's out
-        rows [n, 8] or None).  Every frame gets pose_chain with n = 1; a frame whose turn it is and whose source exists is registered
-        against the orthophoto canvas -- which at that moment holds exactly the frames before it -- and its row corrected in place; with
-        mosaic_relocate=True the relocation sequence follows; then its pixels go into the canvas."""
-        n, h, w = masks.shape
-        dev, size, at = masks.device, (h, w), self._mosaic_at
-        if self._ortho_planes is None:
-            self._ortho_planes = ops.ortho_canvas(self.mosaic, dev)
-        rank, rgba = self._ortho_planes
-        poses = torch.empty((n, 16), dtype=torch.int64, device=dev)
-        outs = torch.zeros((n, 8), dtype=torch.int64, device=dev)
-        outs[:, 0] = 1  # not attempted
-        relocs = outs.clone() if self.mosaic_relocate else None
-        for p in range(n):
-            ordinal = self._ortho_frames + p
-            poses[p:p + 1] = ops.pose_chain(model[p:p + 1], self._mosaic_state, size, self.mosaic, at, self.mosaic_bridge)
-            if sources[p] is None:
-                continue
-            if ordinal % self.refine_every == 0:
-                cur, view, valid = ops.map_view(sources[p], poses[p], ordinal, size, rank, rgba, at, self.refine_min_age)
-                table, stats = ops.block_match_modes(cur, view, self.refine_search, self.refine_penalty, self.refine_intra_bias, return_stats=True)
-                ops.map_gate(table, valid)
-                fit = ops.global_motion(table[None], size, size, self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=masks[p:p + 1],
-                                        exclude=self.mosaic_exclude, pair_stats=stats[None])
-                outs[p] = ops.pose_correct(fit, self._mosaic_state, poses[p], size, self.mosaic, at)
-            if self.mosaic_relocate and ordinal % self.relocate_every == 0:
-                relocs[p] = self._relocate(sources[p], masks[p:p + 1], poses[p], ordinal)
-            ops.ortho_accumulate(sources[p], poses[p], ordinal, size, rank, rgba, at, self.ortho)
-        self._ortho_frames += n
-        return poses, outs, relocs
-
-    def _relocate(self, source, mask, pose, ordinal):
-        """One frame's relocation sequence -> relocate_commit's out row.  The chain's state and `pose` change only in
-        relocate_commit's kernel, and only for a lost chain whose candidate passed the fine registration."""
-        size, at, s = tuple(mask.shape[1:]), self._mosaic_at, self.relocate_scale
-        rank, rgba = self._ortho_planes
-        cl, cv = ops.map_coarse(rgba, s)
-        tl, tv, geom = ops.map_patch(source, self._mosaic_state, size, self.mosaic, at, s)
-        found = ops.map_locate(cl, cv, tl, tv, geom, self.relocate_min_overlap, self.relocate_exclude)
-        cand_state, cand_pose = ops.pose_relocate(found, self._mosaic_state, size, self.mosaic, at, s, self.relocate_max_mean, self.relocate_ratio)
-        cur, view, valid = ops.map_view(source, cand_pose, ordinal, size, rank, rgba, at, self.refine_min_age)
-        table, stats = ops.block_match_modes(cur, view, self.refine_search, self.refine_penalty, self.refine_intra_bias, return_stats=True)
-        ops.map_gate(table, valid)
-        fit = ops.global_motion(table[None], size, size, self.mosaic_rounds, self.mosaic_tol, self.mosaic_min_inliers, mask=mask, exclude=self.mosaic_exclude,
-                                pair_stats=stats[None])
-        correct_out = ops.pose_correct(fit, cand_state, cand_pose, size, self.mosaic, at)
-        return ops.relocate_commit(cand_state, cand_pose, correct_out, self._mosaic_state, pose, found, s)
-
-    # ---- merging another predictor's mosaic into this one (DESIGN §3.23)
+    # ---- the mosaic family (DESIGN §3.18-3.24): what mosaic_builder hands out, under the names and with the contracts it has here
     def mosaic_part(self):
         """mosaic=: this predictor's mosaic as a dict of DEVICE tensors and plain numbers, nothing read back: votes uint16 [K, CH, CW]; rank,
         rgba (ortho=; None without); state int64 [32]; poses int64 [frames, 16]; tail int64 [12], the two poses (to_anchor, from_anchor)
         after the last frame -- or after the last merged part's; origin (oy, ox); mask_size (H, W); frames, the next ordinal; mode.  The
         tensors are the predictor's own, not copies.  write_mosaic_part() saves it, another predictor's merge_mosaic() takes it."""
-        if self._mosaic_votes is None:
-            raise ValueError("FlowPredictor: mosaic_part() needs mosaic=(CH, CW) and at least one predicted window")
-        rank, rgba = self._ortho_planes if self._ortho_planes is not None else (None, None)
-        tail = self._mosaic_tail if self._mosaic_tail is not None else self._mosaic_state[:12].clone()
-        return dict(votes=self._mosaic_votes, rank=rank, rgba=rgba, state=self._mosaic_state, poses=self._mosaic_poses.flat(), tail=tail,
-                    origin=tuple(self._mosaic_at), mask_size=tuple(self._mosaic_mask), frames=max(self._ortho_frames, self._mosaic_poses.frames), mode=self.ortho)
+        return self.mosaic_builder.part()
 
     def merge_mosaic(self, part, link=None, **register):
         """Register another mosaic (mosaic_part()'s dict, or read_mosaic_part()'s) against this predictor's and fold it in: ops.register_mosaics
@@ -642,54 +439,30 @@ class FlowPredictor:
         seen box where it has one.  Afterwards the ordinal counter has grown by the part's frames and, if the link was registered
         (decided on the device), the tail is compose(b_to_a, the part's tail).  Nothing is read back; merge_report() does that.
         Votes are not idempotent: merging the same part twice counts its frames twice."""
-        if self._mosaic_votes is None or self._ortho_planes is None or part.get("rgba") is None:
-            raise ValueError("FlowPredictor: merge_mosaic() needs mosaic= and ortho= on both sides and at least one predicted window: the registration reads both orthophotos")
-        mine = self.mosaic_part()
-        if mine["frames"] + int(part["frames"]) > self.ORTHO_MAX_FRAMES:  # before anything is enqueued: a refused merge changes nothing
-            raise ValueError(f"FlowPredictor: an orthophoto takes at most {self.ORTHO_MAX_FRAMES} frames, got {mine['frames']} + {int(part['frames'])} with the part")
-        link, outs, counts = merge_part(mine, part, link, **register)
-        self._ortho_frames, self._mosaic_tail = mine["frames"], mine["tail"]
-        self._merges.append((link, outs, counts))
-        return link
+        return self.mosaic_builder.merge(part, link, **register)
 
     def change_against(self, part, **kw):
         """Where another mosaic of the same ground (mosaic_part()'s dict, or read_mosaic_part()'s) differs from this predictor's, in this
         one's canvas: mosaic_change(self.mosaic_part(), part, **kw).  Neither mosaic is changed; nothing is read back."""
-        return mosaic_change(self.mosaic_part(), part, **kw)
+        return self.mosaic_builder.change_against(part, **kw)
 
     def merge_report(self):
         """(links int64 numpy [parts, 16], outs: per part int64 [rows, 8] -- link_place's row first where a placement ran, then one
         link_correct row per round --, counts int64 [parts, 8]) of the parts merged since the start (or clear_report()).  The ONE read-back."""
-        if not self._merges:
-            return np.zeros((0, 16), np.int64), [], np.zeros((0, 8), np.int64)
-        flat = torch.cat([t.reshape(-1) for m in self._merges for t in m]).cpu().numpy()
-        links, outs, counts, at = [], [], [], 0
-        for _, o, _ in self._merges:
-            rows = int(o.shape[0])
-            links.append(flat[at:at + 16]), outs.append(flat[at + 16:at + 16 + 8 * rows].reshape(rows, 8)), counts.append(flat[at + 16 + 8 * rows:at + 24 + 8 * rows])
-            at += 24 + 8 * rows
-        return np.stack(links), outs, np.stack(counts)
+        return self.mosaic_builder.merge_report()
 
     def relocate_report(self):
         """mosaic_relocate=True: int64 numpy [frames, 8], relocate_commit's out row of every frame predicted since the start (or
         clear_report()), in the order of mosaic_report()'s poses: status (0 relocated, 1 not attempted, 2 no placement, 3 rejected by the
         mean, 4 rejected by uniqueness, 5 the fine registration failed, 6 the patch was refused, 7 out of the pose bounds), the shift in
         canvas pixels x and y, sad*, n*, sad2, n2, eligible placements.  The ONE read-back."""
-        if not self.mosaic_relocate:
-            raise ValueError("FlowPredictor: relocate_report() needs mosaic_relocate=True")
-        if not self._relocate_outs.chunks:
-            return np.zeros((0, 8), np.int64)
-        return self._relocate_outs.flat().cpu().numpy()
+        return self.mosaic_builder.relocate_report()
 
     def refine_report(self):
         """mosaic_refine=True: int64 numpy [frames, 8], pose_correct's out row of every frame predicted since the start (or
         clear_report()), in the order of mosaic_report()'s poses: status (0 corrected, 1 not attempted, 2 no fit, 3 out of the pose
         bounds, 4 the chain is lost), usable rows, inliers, rounds done, the fit's shift x and y in Q20, 0, 0.  The ONE read-back."""
-        if not self.mosaic_refine:
-            raise ValueError("FlowPredictor: refine_report() needs mosaic_refine=True")
-        if not self._refine_outs.chunks:
-            return np.zeros((0, 8), np.int64)
-        return self._refine_outs.flat().cpu().numpy()
+        return self.mosaic_builder.refine_report()
 
     def ortho_report(self, palette=PALETTE, alpha=None, edge=(), fill=(0, 0, 0), overlay=True):
         """ortho=: (image, src, covered) of the frames predicted since the start (or clear_report()): image uint8 numpy [CH, CW, 3], the
@@ -697,18 +470,7 @@ class FlowPredictor:
         showing `fill` where no frame has been; src int32 [CH, CW], the ordinal (frames since the anchor: the row of mosaic_report()'s
         poses) of the frame each pixel came from, -1 where none; covered, the number of canvas pixels some frame won.  mosaic_resolve
         (overlay=True) and ortho_compose run here, and so does the ONE read-back."""
-        if not self.ortho:
-            raise ValueError("FlowPredictor: ortho_report() needs ortho='centre' or 'latest'")
-        ch, cw = self.mosaic
-        if self._ortho_planes is None:
-            image = np.empty((ch, cw, 3), np.uint8)
-            image[:] = np.array(fill, np.uint8)
-            return image, np.full((ch, cw), -1, np.int32), 0
-        rank, rgba = self._ortho_planes
-        cls = ops.mosaic_resolve(self._mosaic_votes)[0] if overlay else None
-        image = ops.ortho_compose(rgba, cls, palette, alpha, fill, edge)
-        src = torch.where(rank == -1, rank, rank & 0xFFFFFFFF).to(torch.int32).cpu().numpy()
-        return image.cpu().numpy(), src, int((src >= 0).sum())
+        return self.mosaic_builder.ortho_report(palette, alpha, edge, fill, overlay)
 
     def mosaic_report(self):
         """mosaic=(CH, CW): (cls, conf, seen, totals, poses) of the frames predicted since the start (or clear_report()): cls uint8 numpy
@@ -716,14 +478,7 @@ class FlowPredictor:
         code 0..255; seen int32, the number of votes; totals int64 [K, 2], per class the canvas pixels and the votes; poses int64
         [frames, 16], per frame to_anchor (6) and from_anchor (6) in Q20, status (0 ok, 1 bridged, 2 lost), clipped, inliers, usable rows.
         The resolve pass runs here, and so does the ONE read-back."""
-        k = self.mosaic_classes
-        if self._mosaic_votes is None:
-            ch, cw = self.mosaic or (0, 0)
-            return (np.full((ch, cw), 255, np.uint8), np.zeros((ch, cw), np.uint8), np.zeros((ch, cw), np.int32), np.zeros((k, 2), np.int64),
-                    np.zeros((0, 16), np.int64))
-        cls, conf, seen, totals = ops.mosaic_resolve(self._mosaic_votes)
-        poses = self._mosaic_poses.flat()
-        return cls.cpu().numpy(), conf.cpu().numpy(), seen.cpu().numpy(), totals.cpu().numpy(), poses.cpu().numpy()
+        return self.mosaic_builder.report()
 
     def _link_inputs(self, n, link_mvs, link_frame_size, link_stats, link_raw_mvs=None):
         """compensate=True, stabilize_compensate=True or mosaic=: the window's (mvs [n, blocks, 7], frame size, stats [n, 4] or None, raw
@@ -747,19 +502,6 @@ class FlowPredictor:
             raise ValueError(f"FlowPredictor: link_raw_mvs must have link_mvs' shape and dtype, got {link_raw_mvs.dtype} {tuple(link_raw_mvs.shape)} and "
                              f"{link_mvs.dtype} {tuple(link_mvs.shape)}")
         return link_mvs, (int(link_frame_size[0]), int(link_frame_size[1])), link_stats, link_raw_mvs
-
-    def _ortho_sources(self, n, link_sources):
-        """ortho=: the window's decoded frames, one (frame, chroma, fmt, matrix, full_range) or None per emitted frame, checked; None otherwise."""
-        if not self.ortho:
-            return None
-        if link_sources is None or len(link_sources) != n:
-            raise ValueError(f"FlowPredictor: ortho={self.ortho!r} needs link_sources with every window, one entry per frame of its n = {n} (an "
-                             f"estimate-mode dataset with link_sources=True provides them), got {None if link_sources is None else len(link_sources)}; "
-                             "the orthophoto is never left with a hole instead")
-        if self._ortho_frames + n > self.ORTHO_MAX_FRAMES:  # the op takes ordinals up to 2^32 - 2; ortho_report()'s src is int32 with -1 for "none"
-            raise ValueError(f"FlowPredictor: ortho= holds at most {self.ORTHO_MAX_FRAMES} frames per mosaic (ortho_report()'s src is int32), got "
-                             f"{self._ortho_frames} + {n}; clear_report() starts a new one")
-        return list(link_sources)
 
     def _keep_regions(self, masks, conf, link=None):
         """The window's region tables into the next rows of the chunked buffers (region_table writes its rows whole; nothing is read)."""
@@ -911,7 +653,7 @@ class FlowPredictor:
         if self.regions:
             self._keep_regions(masks, conf, self._track_link(link))
         if self.mosaic:
-            self._keep_mosaic(masks, link, sources)
+            self.mosaic_builder.add(masks, link, sources, self.REPORT_CHUNK)
         if not self.confidence:
             return masks.cpu().numpy() if to_host else masks            # :277
         self._keep_report(masks, conf)
@@ -933,7 +675,7 @@ class FlowPredictor:
         n = len(mvs_left) + 1                                # :266 -- the list length encodes n, also for no_warp dummies
         link = self._link_inputs(n, link_mvs, link_frame_size, link_stats, link_raw_mvs)
         self._keep_guide_counts(n, link_guide_counts)
-        sources = self._ortho_sources(n, link_sources)
+        sources = self.mosaic_builder.check_sources(n, link_sources)
         cache = key_cache if key_cache is not None else self.key_cache
         kc = cache.window(*key_ids) if (cache is not None and key_ids is not None) else None
         conf = None
@@ -1023,7 +765,7 @@ class FlowPredictor:
             n = len(w["mvs_left"]) + 1
             link = self._link_inputs(n, w.get("link_mvs"), w.get("link_frame_size"), w.get("link_stats"), w.get("link_raw_mvs"))
             self._keep_guide_counts(n, w.get("link_guide_counts"))
-            sources = self._ortho_sources(n, w.get("link_sources"))
+            sources = self.mosaic_builder.check_sources(n, w.get("link_sources"))
             lo_prev, lo_next = store[w["key_ids"][0]], store[w["key_ids"][1]]
             h, wd = w["frame_prev"].shape[2], w["frame_prev"].shape[3]
             conf = None
@@ -1190,12 +932,6 @@ def write_exposure_csv(path, frame_ids, exposure, thresholds, frame_pixels):
             f.write(",".join(cells) + "\n")
 
 
-MOSAIC_STATUS = ("ok", "bridged", "lost")
-
-
-REFINE_STATUS = ("corrected", "skipped", "no_fit", "out_of_bounds", "lost")
-
-
 def write_guide_csv(path, frame_ids, counts):
     """FlowPredictor.guide_report()'s (or GridEstimator.guide_report()'s) int64 [m, 8] counts with their frame ids as a CSV, one row per
     frame (the pair that ends in that frame): frame, then ops.GUIDE_COUNTS (blocks, void rows in, filled, outliers, replaced, dropped, kept by evidence, foreign)."""
@@ -1205,273 +941,6 @@ def write_guide_csv(path, frame_ids, counts):
         fh.write("frame," + ",".join(GUIDE_COUNTS) + "\n")
         for frame, row in zip(frame_ids, counts):
             fh.write(f"{int(frame)}," + ",".join(str(int(v)) for v in row) + "\n")
-
-
-RELOCATE_STATUS = ("relocated", "not_attempted", "no_placement", "rejected_mean", "rejected_uniqueness", "fine_failed", "patch_refused", "out_of_bounds")
-
-
-def write_relocate_csv(path, frame_ids, report):
-    """FlowPredictor.relocate_report()'s int64 [frames, 8] as a CSV, one row per frame: frame id, status, the shift in canvas pixels, the
-    best placement's summed absolute difference and cells, the runner-up's, and the eligible placements."""
-    report = np.asarray(report)
-    if report.ndim != 2 or report.shape[1] != 8 or len(frame_ids) != report.shape[0]:
-        raise ValueError(f"write_relocate_csv: report must be [frames, 8] with one frame id per row, got {report.shape} and {len(frame_ids)} ids")
-    with open(path, "w", newline="") as f:
-        f.write("frame,status,shift_x,shift_y,sad,cells,sad2,cells2,eligible\n")
-        for fid, row in zip(frame_ids, report.tolist()):
-            f.write(",".join([str(int(fid)), RELOCATE_STATUS[row[0]] if 0 <= row[0] < len(RELOCATE_STATUS) else "patch_refused"] + [str(v) for v in row[1:]]) + "\n")
-
-
-def _compose_q20(a, b):
-    """mosaic_defs.h's compose (b first) on int64 device tensors [6]: the merged tail, without a read-back."""
-    half = 1 << 19
-    lin = [((a[3 * r] * b[c] + a[3 * r + 1] * b[3 + c] + half) >> 20) + (a[3 * r + 2] if c == 2 else 0) for r in range(2) for c in range(3)]
-    return torch.stack(lin)
-
-
-def merge_part(mine, part, link=None, **register):
-    """Register the mosaic `part` against the mosaic `mine` (mosaic_part()'s or read_mosaic_part()'s dicts, both with an orthophoto, on
-    one device) and fold it in: ops.register_mosaics, then ops.mosaic_merge with mine's frame count as the ordinal offset.  mine's votes,
-    rank and rgba are updated in place, mine["frames"] grows by the part's and mine["tail"] becomes compose(b_to_a, part's tail) where
-    the link registered (decided on the device).  link: default mine's tail with status 1.  -> (link, outs, counts), device tensors."""
-    dev = mine["votes"].device
-    if (mine.get("mode") or None) != (part.get("mode") or None) or mine.get("mode") not in ops.ORTHO_MODES:
-        raise ValueError(f"merge_part: both mosaics need an orthophoto of ONE mode (a rank word's key means the distance from the optical axis in 'centre' "
-                         f"and the ordinal in 'latest'), got {mine.get('mode')!r} and {part.get('mode')!r}")
-    if tuple(int(v) for v in mine["mask_size"]) != tuple(int(v) for v in part["mask_size"]):
-        raise ValueError(f"merge_part: both mosaics must be of masks of one size (a canvas pixel is a mask pixel of the anchor frame), got "
-                         f"{tuple(mine['mask_size'])} and {tuple(part['mask_size'])}")
-    if link is None:
-        link = torch.cat([mine["tail"], torch.tensor([ops.LINK_INITIAL, 0, 0, 0], dtype=torch.int64, device=dev)])
-    if register.get("place") is not None and "b_box" not in register["place"] and part.get("box") is not None:
-        register["place"] = dict(register["place"], b_box=tuple(int(v) for v in part["box"]))
-    at, other = tuple(int(v) for v in mine["origin"]), tuple(int(v) for v in part["origin"])
-    link, outs = ops.register_mosaics((mine["rgba"], at), (part["rgba"], other), link, **register)
-    counts = ops.mosaic_merge(mine["votes"], at, part["votes"], other, link, (mine["rank"], mine["rgba"]), (part["rank"], part["rgba"]), int(mine["frames"]),
-                              mine["mode"])
-    moved = torch.cat([_compose_q20(link[0:6], part["tail"][0:6]), _compose_q20(part["tail"][6:12], link[6:12])])
-    mine["tail"] = torch.where(link[12] == ops.LINK_REGISTERED, moved, mine["tail"])
-    mine["frames"] = int(mine["frames"]) + int(part["frames"])
-    return link, outs, counts
-
-
-PART_ARRAYS = ("votes", "rank", "rgba", "state", "poses", "tail")
-LINK_STATUS = ("registered", "initial", "no_fit", "out_of_bounds")
-
-
-def part_seen_box(poses, mask_size, canvas_size, origin):
-    """(y0, x0, y1, x1): the canvas box that holds every frame that voted, from the pose rows on the host (frame_clipped's corners, clipped
-    to the canvas); the whole canvas if none did."""
-    (h, w), (ch, cw), (oy, ox) = mask_size, canvas_size, origin
-    xs, ys = [], []
-    for row in np.asarray(poses).tolist():
-        if row[12] not in (0, 1):
-            continue
-        for x, y in ((0, 0), (w, 0), (0, h), (w, h)):
-            xs.append(row[0] * x + row[1] * y + row[2] + ox * (1 << 20)), ys.append(row[3] * x + row[4] * y + row[5] + oy * (1 << 20))
-    if not xs:
-        return 0, 0, ch, cw
-    y0, x0 = max(0, min(ys) >> 20), max(0, min(xs) >> 20)
-    y1, x1 = min(ch, (max(ys) + (1 << 20) - 1) >> 20), min(cw, (max(xs) + (1 << 20) - 1) >> 20)
-    return (y0, x0, y1, x1) if y0 < y1 and x0 < x1 else (0, 0, ch, cw)
-
-
-def mosaic_part_arrays(part):
-    """FlowPredictor.mosaic_part()'s dict as the numpy arrays of a part file (the read-back of a part happens here), with the seen box."""
-    arrays = {k: part[k].cpu().numpy() if torch.is_tensor(part[k]) else np.asarray(part[k]) for k in PART_ARRAYS if part.get(k) is not None}
-    if arrays["votes"].dtype != np.uint16 or arrays["votes"].ndim != 3:
-        raise ValueError(f"write_mosaic_part: votes must be uint16 [K, CH, CW], got {arrays['votes'].dtype} {arrays['votes'].shape}")
-    arrays["origin"], arrays["mask_size"] = np.array(part["origin"], np.int64), np.array(part["mask_size"], np.int64)
-    arrays["frames"], arrays["mode"] = np.array(int(part["frames"]), np.int64), np.array(part.get("mode") or "")
-    arrays["box"] = np.array(part_seen_box(arrays["poses"], part["mask_size"], arrays["votes"].shape[1:], part["origin"]), np.int64)
-    return arrays
-
-
-def write_mosaic_part(path, part):
-    """A mosaic as ONE .npz: mosaic_part()'s arrays, the pose rows, and the seen bounding box taken from the pose rows here on the host."""
-    with open(path, "wb") as f:   # a file object: numpy then appends no suffix of its own
-        np.savez_compressed(f, **mosaic_part_arrays(part))
-
-
-def read_mosaic_part(path, device):
-    """write_mosaic_part()'s file as the dict FlowPredictor.merge_mosaic() takes, its arrays on `device`."""
-    with np.load(path) as z:
-        missing = [k for k in ("votes", "state", "poses", "tail", "origin", "mask_size", "frames", "mode", "box") if k not in z.files]
-        if missing:
-            raise ValueError(f"read_mosaic_part: {path} is no mosaic part: it lacks {missing}")
-        part = {k: torch.from_numpy(z[k]).to(device) for k in PART_ARRAYS if k in z.files}
-        part.update(rank=part.get("rank"), rgba=part.get("rgba"), origin=tuple(int(v) for v in z["origin"]), mask_size=tuple(int(v) for v in z["mask_size"]),
-                    frames=int(z["frames"]), mode=str(z["mode"]) or None, box=tuple(int(v) for v in z["box"]))
-    return part
-
-
-def write_merge_csv(path, names, report):
-    """FlowPredictor.merge_report() as a CSV, one row per merged part: its name, the link's status, b_to_a m00 .. m12, the inliers and
-    usable rows of the fit that registered it, the status of every register row, and mosaic_merge's counts."""
-    links, outs, counts = report
-    if len(names) != len(links) or len(outs) != len(links) or len(counts) != len(links):
-        raise ValueError(f"write_merge_csv: one name per merged part, got {len(names)} names for {len(links)} links, {len(outs)} out tables and {len(counts)} count rows")
-    with open(path, "w", newline="") as f:
-        f.write("part,link,m00,m01,m02,m10,m11,m12,inliers,usable,register,reached,voted,votes,taken\n")
-        for name, link, out, count in zip(names, np.asarray(links).tolist(), outs, np.asarray(counts).tolist()):
-            status = LINK_STATUS[link[12]] if 0 <= link[12] < len(LINK_STATUS) else "out_of_bounds"
-            f.write(",".join([str(name), status] + [f"{v / (1 << 20):.6f}" for v in link[:6]] + [str(link[13]), str(link[14]), "/".join(str(int(r[0])) for r in out)]
-                             + [str(v) for v in count[1:5]]) + "\n")
-
-
-# ---- the change between two mosaics of the same ground (DESIGN §3.24)
-# ops.mosaic_change's six codes as ops.ortho_compose draws them (R, G, B, A): "not comparable" and "same" leave the imagery as it is
-CHANGE_PALETTE = np.array([[0, 0, 0, 0], [0, 0, 0, 0], [255, 255, 0, 96], [255, 0, 255, 176], [0, 64, 255, 208], [255, 128, 0, 208]], dtype=np.uint8)
-_CHANGE_KEYS = {"min_votes", "min_conf", "tolerance", "watch"}
-_CHANGE_REGISTER_KEYS = {"rounds", "search", "intra_bias", "fit_rounds", "tol", "min_inliers", "window", "place"}
-_CHANGE_REGION_KEYS = {"max_regions", "connectivity", "max_contours", "max_vertices", "simplify_rounds"}
-
-
-def mosaic_change(part_a, part_b, link=None, register=True, regions=False, min_region_area=0, outlines=False, simplify=None, **options):
-    """Where mosaic B differs from mosaic A, in A's canvas (mosaic_part()'s or read_mosaic_part()'s dicts on one device; B is usually the
-    later flight).  The two are NOT merged and neither is changed.  register=True: both need an orthophoto, and ops.register_mosaics
-    runs on their rgba planes from `link` (default: the identity with status 1; rounds, search, intra_bias, fit_rounds, tol, min_inliers,
-    window and place go to it, a place= without b_box taking B's seen box).  register=False: the link is used as given, and only a link
-    with status 0 compares anything.  Then ops.mosaic_change with min_votes, min_conf, tolerance and watch.  regions=True: the change
-    plane, a mask with the ids 0..5, goes through ops.mask_regions and ops.region_table with classes=6 (min_region_area > 1: and
-    ops.region_filter first; outlines=True: ops.region_outlines; simplify=TOL: ops.outline_simplify; max_regions, connectivity,
-    max_contours, max_vertices and simplify_rounds as FlowPredictor takes them), so every gained or lost area is a region with area,
-    box, centroid and polygon.  -> a dict of device tensors: change, cls_a, cls_b, transitions, counts (ops.mosaic_change's), link, outs
-    (register_mosaics' rows, None without), regions = (table, counts, index) or None, outlines and simplified = the ops' tuples or
-    None, tolerance = simplify.  Enqueues only; change_report() reads back.  The defaults are guesses, not validated on real video."""
-    unknown = set(options) - _CHANGE_KEYS - _CHANGE_REGISTER_KEYS - _CHANGE_REGION_KEYS
-    if unknown:
-        raise ValueError(f"mosaic_change: unknown options {sorted(unknown)}")
-    if tuple(int(v) for v in part_a["mask_size"]) != tuple(int(v) for v in part_b["mask_size"]):
-        raise ValueError(f"mosaic_change: both mosaics must be of masks of one size (a canvas pixel is a mask pixel of the anchor frame), got "
-                         f"{tuple(part_a['mask_size'])} and {tuple(part_b['mask_size'])}")
-    if part_a["votes"].shape[0] != part_b["votes"].shape[0]:
-        raise ValueError(f"mosaic_change: both mosaics must count the same classes, got {part_a['votes'].shape[0]} and {part_b['votes'].shape[0]}")
-    if register and (part_a.get("rgba") is None or part_b.get("rgba") is None):
-        raise ValueError("mosaic_change: register=True reads both orthophotos (mosaic parts made with ortho=); pass register=False with a registered link otherwise")
-    if not register and link is None:
-        raise ValueError("mosaic_change: register=False needs the link")
-    if (outlines or simplify is not None or min_region_area > 1) and not regions:
-        raise ValueError("mosaic_change: min_region_area, outlines and simplify go with regions=True")
-    if simplify is not None and not outlines:
-        raise ValueError("mosaic_change: simplify= goes with outlines=True")
-    dev = part_a["votes"].device
-    at, other = tuple(int(v) for v in part_a["origin"]), tuple(int(v) for v in part_b["origin"])
-    outs = None
-    if register:
-        kw = {k: v for k, v in options.items() if k in _CHANGE_REGISTER_KEYS}
-        if kw.get("place") is not None and "b_box" not in kw["place"] and part_b.get("box") is not None:
-            kw["place"] = dict(kw["place"], b_box=tuple(int(v) for v in part_b["box"]))
-        link = ops.mosaic_link(device=dev) if link is None else link.clone()
-        link, outs = ops.register_mosaics((part_a["rgba"], at), (part_b["rgba"], other), link, **kw)
-    elif set(options) & _CHANGE_REGISTER_KEYS:
-        raise ValueError(f"mosaic_change: {sorted(set(options) & _CHANGE_REGISTER_KEYS)} go with register=True")
-    change, cls_a, cls_b, transitions, counts = ops.mosaic_change(part_a["votes"], at, part_b["votes"], other, link,
-                                                                  **{k: v for k, v in options.items() if k in _CHANGE_KEYS})
-    result = dict(change=change, cls_a=cls_a, cls_b=cls_b, transitions=transitions, counts=counts, link=link, outs=outs, regions=None, outlines=None,
-                  simplified=None, tolerance=simplify)
-    if regions:
-        cap, conn = int(options.get("max_regions", 1024)), int(options.get("connectivity", 8))
-        mask = change[None]
-        labels = ops.mask_regions(mask, ops.CHANGE_CLASSES, conn)
-        table, region_counts, index = ops.region_table(mask, labels, ops.CHANGE_CLASSES, None, 128, cap)
-        if min_region_area > 1:
-            mask = ops.region_filter(mask, index, table, ops.CHANGE_CLASSES, min_region_area)
-            labels = ops.mask_regions(mask, ops.CHANGE_CLASSES, conn)
-            table, region_counts, index = ops.region_table(mask, labels, ops.CHANGE_CLASSES, None, 128, cap)
-            result["change"] = mask[0]
-        result["regions"] = (table, region_counts, index)
-        if outlines:
-            result["outlines"] = ops.region_outlines(index, cap, conn, int(options.get("max_contours", 4096)), int(options.get("max_vertices", 32768)))
-            if simplify is not None:
-                contours, vertices, _, outline_counts = result["outlines"]
-                result["simplified"] = ops.outline_simplify(contours, vertices, outline_counts, simplify, int(options.get("simplify_rounds", 32)))
-    return result
-
-
-def change_report(result):
-    """mosaic_change()'s result on the host -- the ONE place that reads back: counts int64 numpy [8], transitions [2, K, K], link [16], outs
-    [rows, 8] or None; with regions: rows = [int64 [regions, 10]] as FlowPredictor.region_report() hands a frame's (what
-    write_regions_csv and write_outlines_geojson take, with frame_ids = [0]); outlines and simplified as outline_report() and
-    simple_outline_report() hand them, for that one frame; shapes = [the regions' (perimeter, contours, vertices)]."""
-    host = lambda t: t.cpu().numpy()  # noqa: E731
-    report = dict(counts=host(result["counts"]), transitions=host(result["transitions"]), link=host(result["link"]),
-                  outs=None if result["outs"] is None else host(result["outs"]), rows=None, outlines=None, simplified=None, shapes=None, tolerance=result["tolerance"])
-    if result["regions"] is not None:
-        table, counts, _ = result["regions"]
-        written = int(host(counts)[0, 1])
-        report["rows"] = [host(table)[0, :written]]
-        if result["outlines"] is not None:
-            contours, vertices, shape, c = (host(t) for t in result["outlines"])
-            total = 0 if c[0, 3] & 1 else int(c[0, 2])
-            report["outlines"] = ([(contours[0, :int(c[0, 1])], vertices[0, :total], shape[0, :written])], c[:, 3])
-            report["shapes"] = [shape[0, :written]]
-            if result["simplified"] is not None:
-                simple, kept, sc = (host(t) for t in result["simplified"])
-                report["simplified"] = ([(simple[0, :int(sc[0, 0])], kept[0, :int(sc[0, 1])])], sc)
-    return report
-
-
-def write_change_csv(path, report, class_names=None):
-    """change_report()'s counts and transitions as one CSV of two tables.  First one row per class pair that has a comparable pixel: the
-    class in A (`from`), the class in B (`to`), the comparable pixels and of those the changed ones (code >= 3: not the same and not
-    explained by the tolerance).  Then, after an empty line, the eight counts by name."""
-    counts, pairs = np.asarray(report["counts"]).tolist(), np.asarray(report["transitions"])
-    k = pairs.shape[1]
-    name = (lambda c: str(c)) if class_names is None else (lambda c: str(class_names[c]))
-    with open(path, "w", newline="") as f:
-        f.write("from,to,comparable,changed\n")
-        for ca in range(k):
-            for cb in range(k):
-                if pairs[0, ca, cb]:
-                    f.write(f"{name(ca)},{name(cb)},{int(pairs[0, ca, cb])},{int(pairs[1, ca, cb])}\n")
-        f.write("\nlink,reached,comparable," + ",".join(ops.CHANGE_CODES[1:]) + "\n")
-        f.write(",".join([LINK_STATUS[counts[0]] if 0 <= counts[0] < len(LINK_STATUS) else "out_of_bounds"] + [str(v) for v in counts[1:]]) + "\n")
-
-
-def change_image(result, rgba=None, palette=CHANGE_PALETTE, fill=(0, 0, 0)):
-    """The change plane drawn over mosaic A's orthophoto (rgba = part_a["rgba"]) through ops.ortho_compose, or over a plain fill without
-    one -> uint8 [CH, CW, 3] on the device.  Codes 0 and 1 of CHANGE_PALETTE have alpha 0: only what differs is drawn."""
-    change = result["change"]
-    if rgba is None:
-        rgba = torch.zeros(tuple(change.shape), dtype=torch.int32, device=change.device)  # never seen: the fill shows everywhere
-    return ops.ortho_compose(rgba, change, palette, fill=fill)
-
-
-def write_change_png(path, result, rgba=None, palette=CHANGE_PALETTE, fill=(0, 0, 0)):
-    """change_image() as a PNG (the read-back of the picture happens here)."""
-    from PIL import Image
-
-    Image.fromarray(change_image(result, rgba, palette, fill).cpu().numpy()).save(path)
-
-
-def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):
-    """FlowPredictor.mosaic_report()'s poses int64 [frames, 16] and totals int64 [K, 2] as one CSV of two tables.  First one row per
-    frame: frame id, status (ok, bridged, lost), clipped (1: a corner of the frame lies outside the canvas), inliers and usable rows of
-    the pair's fit, and the pose m00 .. m12 that takes a mask pixel of the frame to the anchor frame's pixels (empty for a lost frame).
-    Then, after an empty line, one row per class: the canvas pixels it won, their share of the seen pixels, and its votes.  Pixels are
-    mask pixels of the anchor frame, not metres.  refine: FlowPredictor.refine_report()'s int64 [frames, 8]; the frame rows then end with
-    refine (corrected, skipped, no_fit, out_of_bounds, lost), the usable rows and inliers of the fit against the map, and its shift in
-    mask pixels."""
-    poses, totals = np.asarray(poses), np.asarray(totals)
-    if refine is not None and np.asarray(refine).shape != (poses.shape[0], 8):
-        raise ValueError(f"write_mosaic_csv: refine must be [frames, 8] with one row per pose row, got {np.asarray(refine).shape} for {poses.shape[0]} frames")
-    extra = [[]] * poses.shape[0] if refine is None else [
-        [REFINE_STATUS[r[0]] if 0 <= r[0] <= 4 else "lost", str(r[1]), str(r[2]), f"{r[4] / (1 << 20):.6f}", f"{r[5] / (1 << 20):.6f}"] for r in np.asarray(refine).tolist()]
-    if poses.ndim != 2 or poses.shape[1] != 16 or len(frame_ids) != poses.shape[0] or totals.ndim != 2 or totals.shape[1] != 2:
-        raise ValueError(f"write_mosaic_csv: poses must be [frames, 16] with one frame id per row and totals [K, 2], got {poses.shape}, {len(frame_ids)} "
-                         f"ids and {totals.shape}")
-    seen = int(totals[:, 0].sum())
-    with open(path, "w", newline="") as f:
-        f.write("frame,status,clipped,inliers,usable,m00,m01,m02,m10,m11,m12" + (",refine,refine_usable,refine_inliers,refine_dx,refine_dy" if refine is not None else "")
-                + "\n")
-        for fid, row, more in zip(frame_ids, poses.tolist(), extra):
-            status = row[12] if 0 <= row[12] <= 2 else 2
-            pose = [f"{v / (1 << 20):.6f}" for v in row[:6]] if status != 2 else [""] * 6
-            f.write(",".join([str(int(fid)), MOSAIC_STATUS[status], str(row[13]), str(row[14]), str(row[15])] + pose + more) + "\n")
-        f.write("\nclass,pixels,share,votes\n")
-        for k, (pixels, votes) in enumerate(totals.tolist()):
-            f.write(f"{k},{pixels},{pixels / seen if seen else 0.0:.6f},{votes}\n")
 
 
 def _distance_cell(min_d2):

@@ -229,7 +229,7 @@ def test_predictor_merges_the_split_flight_directly_and_through_a_part_file(mode
     def run(lo, hi):
         pred = FlowPredictor(torch.nn.Identity(), **kw)
         sources = [(dev(images[f]), None, "rgb24", "bt601", False) for f in range(lo, hi)]
-        pred._keep_mosaic(dev(np.stack(masks[lo:hi])), (dev(np.stack(tables[lo:hi])), size, None, None), sources)
+        pred.mosaic_builder.add(dev(np.stack(masks[lo:hi])), (dev(np.stack(tables[lo:hi])), size, None, None), sources)
         return pred
 
     single, second = run(0, 6), run(3, 6)
@@ -244,7 +244,7 @@ def test_predictor_merges_the_split_flight_directly_and_through_a_part_file(mode
         links, outs, counts = first.merge_report()
         want, w_link, w_outs, w_counts = gref.merge_parts(a, b, link, mode)
         assert np.array_equal(links[0], w_link) and np.array_equal(outs[0], w_outs) and np.array_equal(counts[0], w_counts) and links[0][:6].tolist() == true
-        assert first._ortho_frames == 6 and first.mosaic_part()["frames"] == 6
+        assert first.mosaic_builder.frames == 6 and first.mosaic_part()["frames"] == 6
         assert host(first.mosaic_part()["tail"]).tolist() == whole["tail"].tolist() == host(single.mosaic_part()["tail"]).tolist()
         first.clear_report()
         assert first.merge_report()[0].shape == (0, 16)
@@ -261,10 +261,10 @@ def test_predictor_merges_the_split_flight_directly_and_through_a_part_file(mode
         assert np.array_equal(x, y)
     # a merge that would pass the orthophoto's frame limit is refused before anything is enqueued: nothing of the predictor changes
     first = run(0, 3)
-    first.ORTHO_MAX_FRAMES = 5
+    first.mosaic_builder.MAX_FRAMES = 5
     with pytest.raises(ValueError, match="got 3 \\+ 3 with the part"):
         first.merge_mosaic(second.mosaic_part())
-    assert np.array_equal(host(first.mosaic_part()["votes"]), a["votes"]) and first._ortho_frames == 3 and first.merge_report()[0].shape == (0, 16)
+    assert np.array_equal(host(first.mosaic_part()["votes"]), a["votes"]) and first.mosaic_builder.frames == 3 and first.merge_report()[0].shape == (0, 16)
     assert np.array_equal(host(first.mosaic_part()["rank"]).view(np.uint64), a["rank"])
 
 

@@ -265,13 +265,13 @@ def test_predictor_keeps_the_mosaic_and_changes_nothing_else(clip):  # noqa: F81
     votes = mref.mosaic_accumulate(plain, poses, np.zeros((5, 96, 120), np.uint16), origin)
     want = mref.mosaic_resolve(votes)
     cls, conf, seen, totals, rows = on.mosaic_report()
-    assert np.array_equal(rows, poses) and np.array_equal(host(on._mosaic_state), state)
+    assert np.array_equal(rows, poses) and np.array_equal(host(on.mosaic_builder.state), state)
     assert np.array_equal(cls, want[0]) and np.array_equal(conf, want[1]) and np.array_equal(seen, want[2].astype(np.int32)) and np.array_equal(totals, want[3])
     assert (poses[:, 12] == 0).sum() >= 2 and seen.max() >= 2 and totals[:, 1].sum() > 0     # not vacuous: frames were registered and voted
     on.reset()                                                                 # a new video: canvas and state stay
-    assert on.mosaic_report()[4].shape == (2 * DELTA, 16) and on._mosaic_votes is not None
+    assert on.mosaic_report()[4].shape == (2 * DELTA, 16) and on.mosaic_builder.votes is not None
     on.clear_report()
-    assert on._mosaic_votes is None and on._mosaic_state is None and on.mosaic_report()[4].shape == (0, 16)
+    assert on.mosaic_builder.votes is None and on.mosaic_builder.state is None and on.mosaic_report()[4].shape == (0, 16)
     run(on, items[1])                                                          # the next frame anchors a new mosaic
     rows = on.mosaic_report()[4]
     assert rows.shape == (DELTA, 16) and rows[0].tolist() == IDENT + IDENT + [0, 0, 0, 0]

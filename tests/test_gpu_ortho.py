@@ -233,16 +233,16 @@ def test_predictor_keeps_the_orthophoto_and_changes_nothing_else(clip):  # noqa:
     assert np.array_equal(image, oref.ortho_compose(want[1], cls, pal, (0, 0, 0), (1,)))
     assert np.array_equal(on.ortho_report(overlay=False, fill=(5, 6, 7))[0], oref.ortho_compose(want[1], None, None, (5, 6, 7)))
     on.reset()                                                                 # a new video: canvas and counter stay
-    assert on._ortho_planes is not None and on._ortho_frames == 2 * DELTA
+    assert on.mosaic_builder.planes is not None and on.mosaic_builder.frames == 2 * DELTA
     on.clear_report()
-    assert on._ortho_planes is None and on._ortho_frames == 0 and on.ortho_report()[2] == 0
+    assert on.mosaic_builder.planes is None and on.mosaic_builder.frames == 0 and on.ortho_report()[2] == 0
     with pytest.raises(ValueError, match="needs link_sources with every window"):
         run(on, items[0])
     sources = list(items[1]["link_sources"])
     sources[2] = None                                                          # a frame that does not exist is skipped; the ordinals go on
     run(on, items[1], link_sources=sources)
     src = on.ortho_report()[1]
-    assert on._ortho_frames == DELTA and 2 not in np.unique(src) and 0 in np.unique(src)
+    assert on.mosaic_builder.frames == DELTA and 2 not in np.unique(src) and 0 in np.unique(src)
 
 
 def test_predict_video_writes_the_orthophoto(clip, tmp_path):  # noqa: F811

@@ -214,7 +214,7 @@ def test_predictor_registers_every_frame_and_is_todays_without_it(clip):  # noqa
     votes = mref.mosaic_accumulate(masks, poses, np.zeros((5, 96, 120), np.uint16), origin)
     assert np.array_equal(on.mosaic_report()[0], mref.mosaic_resolve(votes)[0])               # the frames vote with the corrected rows
     on.clear_report()
-    assert on.refine_report().shape == (0, 8) and on._ortho_frames == 0
+    assert on.refine_report().shape == (0, 8) and on.mosaic_builder.frames == 0
     # every second frame, and a frame without a source: those rows say "not attempted"
     sources = list(items[0]["link_sources"])
     sources[2] = None

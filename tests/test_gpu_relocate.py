@@ -16,7 +16,7 @@ import ortho_ref as oref
 import refine_ref as rref
 import relocate_ref as lref
 from flood_uav_video_segmentation_amd import ops
-from flood_uav_video_segmentation_amd.flow.predict import FlowPredictor
+from flood_uav_video_segmentation_amd.flow.mosaic import MosaicBuilder
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -297,8 +297,8 @@ def test_the_sequence_recovers_the_cut_flight_eagerly_and_from_one_graph():
 
 # ------------------------------------------------------------------------------------------------ FlowPredictor
 def test_predictor_relocalises_the_cut_flight_and_is_todays_without_it():
-    """The flight handed to FlowPredictor's mosaic step in two windows of seven frames (synthesised tables and a stats row that flags the
-    cut, as an estimate-mode dataset hands them out; the masks are all one class, which votes).  mosaic_relocate=True: mosaic_report()'s
+    """The flight handed to FlowPredictor's mosaic step, a MosaicBuilder without a predictor, in two windows of seven frames (synthesised
+    tables and a stats row that flags the cut, as an estimate-mode dataset hands them out; the masks are all one class, which votes).  mosaic_relocate=True: mosaic_report()'s
     poses and relocate_report() are the reference's, the orthophoto the one those rows gather.  False: every report equals a predictor's
     built without the argument, and every frame after the cut is lost."""
     (a, _), wants = flights()
@@ -309,29 +309,29 @@ def test_predictor_relocalises_the_cut_flight_and_is_todays_without_it():
     stats[lref.CUT_AT, 2] = 1
     frames = dev(np.stack(images))
     masks = torch.zeros((len(images),) + SIZE, dtype=torch.uint8, device=DEV)
-    kw = dict(classes=5, out_size=SIZE, mosaic=CANVAS, mosaic_min_inliers=6, mosaic_exclude=(), mosaic_origin=ORIGIN, ortho="centre", mosaic_refine=True, refine_search=8)
+    kw = dict(classes=5, min_inliers=6, exclude=(), origin=ORIGIN, ortho="centre", refine=True, refine_search=8)
 
     def run(pred):
         for lo in (0, 7):
             sources = [(frames[f], None, "rgb24", "bt601", False) for f in range(lo, lo + 7)]
-            pred._keep_mosaic(masks[lo:lo + 7], (tables[lo:lo + 7], SIZE, stats[lo:lo + 7], None), sources)
+            pred.add(masks[lo:lo + 7], (tables[lo:lo + 7], SIZE, stats[lo:lo + 7], None), sources)
         return pred
 
-    plain, off = run(FlowPredictor(torch.nn.Identity(), **kw)), run(FlowPredictor(torch.nn.Identity(), mosaic_relocate=False, **kw))
-    on = run(FlowPredictor(torch.nn.Identity(), mosaic_relocate=True, relocate_scale=4, **kw))
-    for x, y in zip(off.mosaic_report() + off.ortho_report() + (off.refine_report(),), plain.mosaic_report() + plain.ortho_report() + (plain.refine_report(),)):
+    plain, off = run(MosaicBuilder(CANVAS, **kw)), run(MosaicBuilder(CANVAS, relocate=False, **kw))
+    on = run(MosaicBuilder(CANVAS, relocate=True, relocate_scale=4, **kw))
+    for x, y in zip(off.report() + off.ortho_report() + (off.refine_report(),), plain.report() + plain.ortho_report() + (plain.refine_report(),)):
         assert np.array_equal(x, y)
-    assert off.mosaic_report()[4][:, 12].tolist() == [0] * lref.CUT_AT + [2] * 4
+    assert off.report()[4][:, 12].tolist() == [0] * lref.CUT_AT + [2] * 4
     with pytest.raises(ValueError, match="relocate_report\\(\\) needs mosaic_relocate=True"):
         off.relocate_report()
     poses, outs, relocs, _, planes = wants[0]
-    assert np.array_equal(on.mosaic_report()[4], poses) and np.array_equal(on.relocate_report(), relocs) and np.array_equal(on.refine_report(), outs)
+    assert np.array_equal(on.report()[4], poses) and np.array_equal(on.relocate_report(), relocs) and np.array_equal(on.refine_report(), outs)
     want_src, want_covered = oref.winners(planes[0])
     image, src, covered = on.ortho_report(overlay=False)
     assert np.array_equal(src, want_src) and covered == want_covered and np.array_equal(image, oref.ortho_compose(planes[1]))
     votes = mref.mosaic_accumulate(host(masks), poses, np.zeros((5,) + CANVAS, np.uint16), ORIGIN)
-    assert np.array_equal(on.mosaic_report()[0], mref.mosaic_resolve(votes)[0])
-    on.clear_report()
+    assert np.array_equal(on.report()[0], mref.mosaic_resolve(votes)[0])
+    on.clear()
     assert on.relocate_report().shape == (0, 8)
 
 

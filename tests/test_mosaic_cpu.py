@@ -442,13 +442,13 @@ def test_ops_refuse_with_the_offending_value():
 def test_predictor_argument_checks():
     ident = torch.nn.Identity()
     p = FlowPredictor(ident)
-    assert p.mosaic is None and p._mosaic_votes is None
+    assert p.mosaic is None and p.mosaic_builder.votes is None
     cls, conf, seen, totals, poses = p.mosaic_report()
     assert cls.shape == (0, 0) and totals.shape == (5, 2) and poses.shape == (0, 16)
     assert p._link_inputs(3, None, None, None) is None                       # off: no vectors are asked for
     on = FlowPredictor(ident, mosaic=(300, 400))                                # it does not need regions=True
-    assert on.mosaic == (300, 400) and on.mosaic_classes == 5 and on.mosaic_exclude == (1,) and on.mosaic_bridge == 2 and on.mosaic_origin is None
-    assert (on.mosaic_rounds, on.mosaic_tol, on.mosaic_min_inliers) == (4, 1.0, 12)
+    assert on.mosaic == (300, 400) and on.mosaic_builder.classes == 5 and on.mosaic_builder.exclude == (1,) and on.mosaic_builder.bridge == 2 and on.mosaic_builder.origin is None
+    assert (on.mosaic_builder.rounds, on.mosaic_builder.tol, on.mosaic_builder.min_inliers) == (4, 1.0, 12)
     cls, conf, seen, totals, poses = on.mosaic_report()
     assert cls.shape == (300, 400) and (cls == 255).all() and not conf.any() and not seen.any() and poses.shape == (0, 16)
     with pytest.raises(ValueError, match="mosaic=\\(CH, CW\\) needs link_mvs and link_frame_size"):
@@ -458,7 +458,7 @@ def test_predictor_argument_checks():
                      (dict(mosaic_bridge=-1), "-1"), (dict(mosaic_origin=(1, 2, 3)), "(1, 2, 3)"), (dict(mosaic_origin=(0, 20000)), "20000")):
         with pytest.raises(ValueError, match=re.escape(word)):
             FlowPredictor(ident, **{**dict(mosaic=(300, 400)), **kw})
-    assert FlowPredictor(ident, mosaic=(9, 9), mosaic_classes=32, mosaic_exclude=(), mosaic_origin=(-3, 4)).mosaic_origin == (-3, 4)
+    assert FlowPredictor(ident, mosaic=(9, 9), mosaic_classes=32, mosaic_exclude=(), mosaic_origin=(-3, 4)).mosaic_builder.origin == (-3, 4)
 
 
 def test_the_mosaic_csv(tmp_path):

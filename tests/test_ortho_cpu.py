@@ -322,7 +322,7 @@ def test_ops_refuse_with_the_offending_value():
 def test_predictor_and_dataset_argument_checks(tmp_path):
     ident = torch.nn.Identity()
     p = FlowPredictor(ident)
-    assert p.ortho is None and p._ortho_planes is None and p._ortho_sources(3, None) is None     # off: no sources are asked for
+    assert p.ortho is None and p.mosaic_builder.planes is None and p.mosaic_builder.check_sources(3, None) is None     # off: no sources are asked for
     with pytest.raises(ValueError, match="ortho_report\\(\\) needs ortho="):
         p.ortho_report()
     with pytest.raises(ValueError, match="ortho='centre' needs mosaic=\\(CH, CW\\)"):
@@ -330,23 +330,23 @@ def test_predictor_and_dataset_argument_checks(tmp_path):
     with pytest.raises(ValueError, match="'nearest'"):
         FlowPredictor(ident, mosaic=(30, 40), ortho="nearest")
     on = FlowPredictor(ident, mosaic=(30, 40), ortho="latest")
-    assert on.ortho == "latest" and on._ortho_frames == 0
+    assert on.ortho == "latest" and on.mosaic_builder.frames == 0
     image, src, covered = on.ortho_report(fill=(1, 2, 3))
     assert image.shape == (30, 40, 3) and (image == np.array([1, 2, 3], np.uint8)).all() and (src == -1).all() and covered == 0
     with pytest.raises(ValueError, match="needs link_sources with every window"):
-        on._ortho_sources(3, None)
+        on.mosaic_builder.check_sources(3, None)
     with pytest.raises(ValueError, match="got 2"):
-        on._ortho_sources(3, [None, None])
-    assert on._ortho_sources(2, (None, None)) == [None, None]
-    on._ortho_frames = (1 << 31) - 2                                         # ordinals stay below 2^31: src is int32
-    assert on._ortho_sources(2, (None, None)) == [None, None]
+        on.mosaic_builder.check_sources(3, [None, None])
+    assert on.mosaic_builder.check_sources(2, (None, None)) == [None, None]
+    on.mosaic_builder.frames = (1 << 31) - 2                                         # ordinals stay below 2^31: src is int32
+    assert on.mosaic_builder.check_sources(2, (None, None)) == [None, None]
     with pytest.raises(ValueError, match=f"at most {1 << 31} frames per mosaic.*got {(1 << 31) - 2} \\+ 3"):
-        on._ortho_sources(3, (None, None, None))
-    on._ortho_planes, on._ortho_frames = ops.ortho_canvas((30, 40), "cpu"), 7
+        on.mosaic_builder.check_sources(3, (None, None, None))
+    on.mosaic_builder.planes, on.mosaic_builder.frames = ops.ortho_canvas((30, 40), "cpu"), 7
     on.reset()
-    assert on._ortho_planes is not None and on._ortho_frames == 7            # a new video: the canvas and the counter stay
+    assert on.mosaic_builder.planes is not None and on.mosaic_builder.frames == 7            # a new video: the canvas and the counter stay
     on.clear_report()
-    assert on._ortho_planes is None and on._ortho_frames == 0
+    assert on.mosaic_builder.planes is None and on.mosaic_builder.frames == 0
     # the datasets: link_sources needs link_vectors
     raw = tmp_path / "v.rgb"
     raw.write_bytes(bytes(32 * 48 * 3 * 4))

@@ -251,7 +251,7 @@ def test_ops_refuse_with_the_offending_value():
 def test_predictor_tool_and_csv_argument_checks(tmp_path, capsys):
     ident = torch.nn.Identity()
     off = FlowPredictor(ident, mosaic=(30, 40), ortho="centre")
-    assert off.mosaic_refine is False and (off.refine_search, off.refine_penalty, off.refine_intra_bias, off.refine_min_age, off.refine_every) == (8, 0, 65535, 0, 1)
+    assert off.mosaic_refine is False and (off.mosaic_builder.refine_search, off.mosaic_builder.refine_penalty, off.mosaic_builder.refine_intra_bias, off.mosaic_builder.refine_min_age, off.mosaic_builder.refine_every) == (8, 0, 65535, 0, 1)
     with pytest.raises(ValueError, match="refine_report\\(\\) needs mosaic_refine=True"):
         off.refine_report()
     with pytest.raises(ValueError, match="mosaic_refine=True needs ortho="):
@@ -262,8 +262,8 @@ def test_predictor_tool_and_csv_argument_checks(tmp_path, capsys):
             FlowPredictor(ident, mosaic=(30, 40), ortho="centre", mosaic_refine=True, **kw)
     on = FlowPredictor(ident, mosaic=(30, 40), ortho="latest", mosaic_refine=True, refine_search=16, refine_min_age=8, refine_every=2)
     assert on.mosaic_refine and on.refine_report().shape == (0, 8)
-    on._refine_outs.rows(0, 2, on.REPORT_CHUNK, "cpu")[0].copy_(torch.tensor([rref.SKIPPED_ROW, (2, 5, 0, 0, 0, 0, 0, 0)]))
-    on._refine_outs.frames = 2
+    on.mosaic_builder.refine_outs.rows(0, 2, on.REPORT_CHUNK, "cpu")[0].copy_(torch.tensor([rref.SKIPPED_ROW, (2, 5, 0, 0, 0, 0, 0, 0)]))
+    on.mosaic_builder.refine_outs.frames = 2
     assert on.refine_report().tolist() == [list(rref.SKIPPED_ROW), [2, 5, 0, 0, 0, 0, 0, 0]]
     on.clear_report()
     assert on.refine_report().shape == (0, 8)

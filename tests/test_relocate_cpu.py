@@ -409,8 +409,8 @@ def test_ops_refuse_with_the_offending_value():
 def test_predictor_tool_and_csv_argument_checks(tmp_path, capsys):
     ident = torch.nn.Identity()
     off = FlowPredictor(ident, mosaic=(30, 40), ortho="centre", mosaic_refine=True)
-    assert off.mosaic_relocate is False and (off.relocate_scale, off.relocate_every, off.relocate_min_overlap, off.relocate_exclude, off.relocate_max_mean,
-                                             off.relocate_ratio) == (8, 1, 500, 2, 16, 800)
+    assert off.mosaic_relocate is False and (off.mosaic_builder.relocate_scale, off.mosaic_builder.relocate_every, off.mosaic_builder.relocate_min_overlap, off.mosaic_builder.relocate_exclude, off.mosaic_builder.relocate_max_mean,
+                                             off.mosaic_builder.relocate_ratio) == (8, 1, 500, 2, 16, 800)
     with pytest.raises(ValueError, match="relocate_report\\(\\) needs mosaic_relocate=True"):
         off.relocate_report()
     with pytest.raises(ValueError, match="mosaic_relocate=True needs mosaic_refine=True"):
@@ -420,10 +420,10 @@ def test_predictor_tool_and_csv_argument_checks(tmp_path, capsys):
         with pytest.raises(ValueError, match=word):
             FlowPredictor(ident, mosaic=(30, 40), ortho="centre", mosaic_refine=True, mosaic_relocate=True, **kw)
     on = FlowPredictor(ident, mosaic=(30, 40), ortho="latest", mosaic_refine=True, mosaic_relocate=True, relocate_scale=4, relocate_every=3, relocate_ratio=0.5)
-    assert on.mosaic_relocate and (on.relocate_scale, on.relocate_every, on.relocate_ratio) == (4, 3, 500) and on.relocate_report().shape == (0, 8)
+    assert on.mosaic_relocate and (on.mosaic_builder.relocate_scale, on.mosaic_builder.relocate_every, on.mosaic_builder.relocate_ratio) == (4, 3, 500) and on.relocate_report().shape == (0, 8)
     rows = [list(lref.NOT_ATTEMPTED_ROW), [0, -36, 0, 0, 384, 2312, 195, 325], [4, 8, 4, 10, 5, 11, 5, 7]]
-    on._relocate_outs.rows(0, 3, on.REPORT_CHUNK, "cpu")[0].copy_(torch.tensor(rows))
-    on._relocate_outs.frames = 3
+    on.mosaic_builder.relocate_outs.rows(0, 3, on.REPORT_CHUNK, "cpu")[0].copy_(torch.tensor(rows))
+    on.mosaic_builder.relocate_outs.frames = 3
     assert on.relocate_report().tolist() == rows
     path = str(tmp_path / "r.csv")
     write_relocate_csv(path, [7, 8, 9], on.relocate_report())

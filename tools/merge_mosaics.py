@@ -3,7 +3,7 @@
     python tools/merge_mosaics.py FLIGHT.part000.npz FLIGHT.part001.npz ... --out MOSAIC.png [--ortho ORTHO.png] [--report MERGE.csv]
                                   [--search-scale S]
 
-The parts are what `tools/predict_video.py --mosaic-part FILE.npz` (or flow.predict.write_mosaic_part) wrote, each with an orthophoto.  They
+The parts are what `tools/predict_video.py --mosaic-part FILE.npz` (or flow.mosaic.write_mosaic_part) wrote, each with an orthophoto.  They
 are merged IN ORDER into the first: part k is registered against the mosaic so far, starting from the link "its anchor frame is the frame
 after the last one merged" (the case of consecutive blocks of one video), and its votes and orthophoto are folded in on the GPU.
 `--search-scale S` (4, 8 or 16) first slides the part's seen box over the whole map in S x S cells, for parts that do not follow on from
@@ -20,7 +20,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from flood_uav_video_segmentation_amd import ops  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import LINK_STATUS, PALETTE, colorize, merge_part, read_mosaic_part, write_merge_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.mosaic import LINK_STATUS, merge_part, read_mosaic_part, write_merge_csv  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import PALETTE, colorize  # noqa: E402
 
 
 def parse_args(argv=None):

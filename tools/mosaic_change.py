@@ -4,7 +4,7 @@
                                   [--outlines OUTLINES.geojson] [--min-region N] [--tolerance R] [--min-votes N] [--min-conf C]
                                   [--watch K ...] [--search-scale S] [--no-register]
 
-BEFORE and AFTER are mosaic parts, what `tools/predict_video.py --mosaic-part FILE.npz` (or flow.predict.write_mosaic_part) wrote.  AFTER
+BEFORE and AFTER are mosaic parts, what `tools/predict_video.py --mosaic-part FILE.npz` (or flow.mosaic.write_mosaic_part) wrote.  AFTER
 is registered against BEFORE on their orthophotos, starting from "both have the same anchor" (`--search-scale S`, 4, 8 or 16, first
 slides AFTER's seen box over the whole map in S x S cells, as merge_mosaics.py does), and compared class by class in BEFORE's canvas;
 nothing is merged.  --out is BEFORE's orthophoto with the pixels that differ drawn over it: explained by the tolerance, changed between
@@ -21,8 +21,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from flood_uav_video_segmentation_amd import ops  # noqa: E402
-from flood_uav_video_segmentation_amd.flow.predict import (LINK_STATUS, change_report, mosaic_change, read_mosaic_part, write_change_csv, write_change_png,  # noqa: E402
-                                                           write_outlines_geojson, write_regions_csv)
+from flood_uav_video_segmentation_amd.flow.mosaic import LINK_STATUS, change_report, mosaic_change, read_mosaic_part, write_change_csv, write_change_png  # noqa: E402
+from flood_uav_video_segmentation_amd.flow.predict import write_outlines_geojson, write_regions_csv  # noqa: E402
 
 
 def parse_args(argv=None):
