@@ -661,7 +661,18 @@ static int fs_mosaic_change(const uint16_t* votes_a, int CH_a, int CW_a, int ox_
                                     tolerance, watch_set, change, cls_a, cls_b, reinterpret_cast<long long*>(transitions), reinterpret_cast<long long*>(counts), S(stream));
 }
 
-// the fifteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// dry-route reachability (access_ops.hip): the launchers validate, nothing is launched on a refusal
+static int fs_mask_access(const uint8_t* mask, const uint8_t* seeds, int n, int H, int W, const uint8_t* cost, uint32_t terminal_set, int connectivity,
+                          uint32_t max_cost, int rounds, int resume, uint32_t* d, int32_t* origin, int32_t* status, void* workspace, fs_stream stream) {
+    return fs::launch_mask_access(mask, seeds, n, H, W, cost, terminal_set, connectivity, max_cost, rounds, resume, d, origin, status, workspace, S(stream));
+}
+static int fs_region_access(const uint8_t* mask, const uint32_t* d, const int32_t* origin, const int32_t* index, const int64_t* counts, int n, int H, int W,
+                            int K, int max_regions, int64_t* reach, int64_t* rows, fs_stream stream) {
+    return fs::launch_region_access(mask, d, origin, index, reinterpret_cast<const long long*>(counts), n, H, W, K, max_regions,
+                                    reinterpret_cast<long long*>(reach), reinterpret_cast<long long*>(rows), S(stream));
+}
+
+// the sixteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -819,7 +830,15 @@ static const fs_hook_tables5& hook_tables(void) {
         sizeof(fs_ext14_api),
         fs_mosaic_change,
     }};
+    // fs_ext14_api is frozen too (one member, 24 bytes; tests/test_access_cpu.py); the sixteenth table lies behind it, and &all15.base14 is &all15.
+    static const fs_hook_tables15 all15 = {all14, {
+        FS_EXT15_MAGIC,
+        sizeof(fs_ext15_api),
+        fs_mask_access,
+        fs_region_access,
+    }};
     {
+        const fs_hook_tables14& all14 = all15.base14;
         const fs_hook_tables13& all13 = all14.base13;
         const fs_hook_tables12& all12 = all13.base12;
         const fs_hook_tables11& all11 = all12.base11;

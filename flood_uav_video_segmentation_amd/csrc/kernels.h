@@ -472,6 +472,16 @@ int launch_mosaic_change(const uint16_t* votes_a, int CH_a, int CW_a, int ox_a, 
                          const long long* link, int min_votes, int min_conf, int tolerance, uint32_t watch_set, uint8_t* change, uint8_t* cls_a, uint8_t* cls_b,
                          long long* transitions, long long* counts, hipStream_t s);
 
+// Dry-route reachability (access_ops.hip, access_defs.h; definitions: include/floodseg_test.h, mask_access and region_access; DESIGN
+// §3.25).  The launchers refuse bad arguments before they launch anything.  mask, seeds = uint8 [n][H][W]; cost = uint8 [32] in HOST
+// memory, read during the call; d = uint32 and origin = int32 (or null) [n][H][W]; status = int32 [n][4]; the workspace is the caller's
+// (FS_MASK_ACCESS_WORKSPACE_BYTES, 8-byte aligned).  2 + rounds launches; nothing is allocated, synchronised or read back on the host.
+int launch_mask_access(const uint8_t* mask, const uint8_t* seeds, int n, int H, int W, const uint8_t* cost, uint32_t terminal_set, int connectivity,
+                       uint32_t max_cost, int rounds, int resume, uint32_t* d, int32_t* origin, int32_t* status, void* workspace, hipStream_t s);
+// index, counts = region_table's; reach = int64 [n][K][4]; rows = int64 [n][max_regions][8].  Three launches, no workspace.
+int launch_region_access(const uint8_t* mask, const uint32_t* d, const int32_t* origin, const int32_t* index, const long long* counts, int n, int H, int W,
+                         int K, int max_regions, long long* reach, long long* rows, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

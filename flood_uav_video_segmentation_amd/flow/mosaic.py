@@ -1,7 +1,7 @@
-"""The flood-extent mosaic and everything built on it (DESIGN §3.18-3.24): the vote canvas and its pose chain, the orthophoto under it,
-frame-to-map registration, relocalisation, the merge of two mosaics and the change between them.  MosaicBuilder owns all of it -- the
-settings, the canvases and the chain's state on the device, the per-frame report rows -- and needs no network: only masks and the block
-matcher's tables.  A mosaic with its orthophoto, every frame registered against the map before it votes:
+"""The flood-extent mosaic and everything built on it (DESIGN §3.18-3.25): the vote canvas and its pose chain, the orthophoto under it,
+frame-to-map registration, relocalisation, the merge of two mosaics, the change between them and dry-route reachability on one.
+MosaicBuilder owns all of it -- the settings, the canvases and the chain's state on the device, the per-frame report rows -- and needs
+no network: only masks and the block matcher's tables.  A mosaic with its orthophoto, every frame registered against the map before it votes:
 
     b = MosaicBuilder((4096, 4096), ortho="centre", refine=True)
     for masks, tables, stats, frames in windows:         # device tensors: uint8 [n, H, W]; ops.block_match_modes' int32 [n, blocks, 7] and
@@ -235,6 +235,10 @@ class MosaicBuilder:
     def change_against(self, part, **kw):
         """mosaic_change(self.part(), part, **kw): neither mosaic is changed; nothing is read back."""
         return mosaic_change(self.part(), part, **kw)
+
+    def access(self, **kw):
+        """mosaic_access(self, **kw): dry-route reachability on this mosaic; the mosaic is not changed."""
+        return mosaic_access(self, **kw)
 
     def merge_report(self):
         """(links int64 numpy [parts, 16], per part the out rows [rows, 8], counts [parts, 8]) of the parts merged.  The ONE read-back."""
@@ -523,6 +527,198 @@ def write_change_png(path, result, rgba=None, palette=CHANGE_PALETTE, fill=(0, 0
     from PIL import Image
 
     Image.fromarray(change_image(result, rgba, palette, fill).cpu().numpy()).save(path)
+
+
+# ---- dry-route reachability on the mosaic
+ACCESS_COST = {4: 1, 0: 2, 2: 6, 3: 2}   # Street 1, Background 2, Tree 6, Building 2 (the step onto its wall); Water and unseen ground 0: barriers.  A guess
+ACCESS_TERMINAL = (3,)            # Building: arrived at, never crossed
+ACCESS_MAX_ROUNDS = 4096          # the round limit of mosaic_access by default.  A guess: a route that crosses more tiles than this stays unconverged
+ACCESS_MOVES = ((-1, 0, 5), (1, 0, 5), (0, -1, 5), (0, 1, 5), (-1, -1, 7), (1, -1, 7), (-1, 1, 7), (1, 1, 7))   # csrc/access_defs.h's move table: (dx, dy, step)
+ACCESS_CUT_OFF = (255, 0, 255)    # write_access_png: a terminal region that no route reaches
+_ACCESS_KEYS = {"connectivity", "max_cost", "max_regions", "chunk", "max_rounds", "want_origin"}
+
+
+def access_seeds(cls, seeds):
+    """The seed plane of mosaic_access, uint8 like cls [CH, CW], on cls' device.  seeds: "border" (the seen pixels with an unseen or no
+    4-neighbour: where ground the flight never saw begins), or a dict with any of points = [(x, y), ...] canvas pixels, classes = class
+    ids, border = True."""
+    spec = dict(border=True) if isinstance(seeds, str) and seeds == "border" else seeds
+    if not isinstance(spec, dict) or not spec or set(spec) - {"points", "classes", "border"}:
+        raise ValueError(f"mosaic_access: seeds must be \"border\" or a dict with points, classes and/or border, got {seeds!r}")
+    ch, cw = cls.shape
+    plane = torch.zeros((ch, cw), dtype=torch.uint8, device=cls.device)
+    points = [tuple(int(v) for v in p) for p in spec.get("points", ())]
+    if any(len(p) != 2 or not (0 <= p[0] < cw and 0 <= p[1] < ch) for p in points):
+        raise ValueError(f"mosaic_access: seed points must be (x, y) inside the {ch} x {cw} canvas, got {list(spec['points'])}")
+    if points:
+        at = torch.tensor(points, dtype=torch.int64, device=cls.device)
+        plane[at[:, 1], at[:, 0]] = 1
+    ids = [int(c) for c in spec.get("classes", ())]
+    if any(not 0 <= c <= 31 for c in ids):
+        raise ValueError(f"mosaic_access: seed classes must be class ids 0..31, got {ids}")
+    for c in ids:
+        plane |= (cls == c).to(torch.uint8)
+    if spec.get("border"):
+        seen = torch.nn.functional.pad(cls != 255, (1, 1, 1, 1), value=False)
+        inner = seen[1:-1, 2:] & seen[1:-1, :-2] & seen[2:, 1:-1] & seen[:-2, 1:-1]
+        plane |= (seen[1:-1, 1:-1] & ~inner).to(torch.uint8)
+    return plane
+
+
+def mosaic_access(part_or_builder, seeds="border", cost=None, terminal=ACCESS_TERMINAL, min_votes=1, regions=True, **options):
+    """Which ground of a mosaic can be reached over ground that is not under water, and at what cost.  part_or_builder: a
+    MosaicBuilder or a part (part()'s or read_mosaic_part()'s dict).  The class plane is ops.mosaic_resolve's winner where the pixel has
+    min_votes votes, 255 otherwise: unseen ground is a barrier.  seeds: see access_seeds.  cost: {class id: 0..255}, by default Street 1,
+    Background 2, Tree 6, Building 2, Water 0 = barrier; terminal: classes that are arrived at but never crossed, by default Building.
+    ops.mask_access then runs in chunks of `chunk` rounds (default ops.ACCESS_ROUNDS), the 16 bytes of its status read back after each,
+    until it says converged or max_rounds (default 4096) rounds are enqueued; connectivity, max_cost and want_origin go to it.
+    regions=True: the class plane goes through ops.mask_regions and ops.region_table (max_regions, default 1024) and ops.region_access
+    tabulates the field per region.  -> a dict: cls, seeds, d, origin, status (device tensors), converged (bool: False means every
+    value is only an upper bound), rounds (enqueued), regions = (table, counts, index) or None, reach and rows (ops.region_access') or
+    None, cost (the 32 costs), terminal, connectivity, classes.
+    Costs are mask pixels of the anchor frame in tenths on the 5-7 chamfer metric, not metres.  The default costs and the round limit are
+    guesses, not validated on real video."""
+    unknown = set(options) - _ACCESS_KEYS
+    if unknown:
+        raise ValueError(f"mosaic_access: unknown options {sorted(unknown)}")
+    part = part_or_builder.part() if hasattr(part_or_builder, "part") else part_or_builder
+    votes = part["votes"]
+    if not 1 <= int(min_votes) <= 65535:
+        raise ValueError(f"mosaic_access: min_votes must be 1..65535, got {min_votes}")
+    table = ops.access_cost_table(ACCESS_COST if cost is None else cost, "mosaic_access")
+    terminal = tuple(int(c) for c in terminal)
+    ops.class_set(terminal, "terminal", "mosaic_access", allow_empty=True)
+    conn, chunk, limit = int(options.get("connectivity", 8)), int(options.get("chunk", ops.ACCESS_ROUNDS)), int(options.get("max_rounds", ACCESS_MAX_ROUNDS))
+    if conn not in (4, 8):
+        raise ValueError(f"mosaic_access: connectivity must be 4 or 8, got {conn}")
+    if not 1 <= chunk <= 65535 or limit < 1:
+        raise ValueError(f"mosaic_access: chunk must be 1..65535 rounds and max_rounds at least 1, got {chunk} and {limit}")
+    cls, _, seen, _ = ops.mosaic_resolve(votes)
+    if int(min_votes) > 1:
+        cls = torch.where(seen >= int(min_votes), cls, torch.full_like(cls, 255))
+    plane = access_seeds(cls, seeds)
+    kw = dict(terminal=terminal, connectivity=conn, max_cost=int(options.get("max_cost", 0)), want_origin=bool(options.get("want_origin", True)))
+    mask, planes, rounds, converged = cls[None], None, 0, False
+    while not converged and rounds < limit:
+        step = min(chunk, limit - rounds)
+        d, origin, status = ops.mask_access(mask, plane[None], table, rounds=step, resume=planes, **kw)
+        planes, rounds = (d, origin), rounds + step
+        converged = bool(status[0, 0].item())  # the read-back of 16 bytes per chunk: only here, at report time
+    result = dict(cls=cls, seeds=plane, d=d[0], origin=None if origin is None else origin[0], status=status[0], converged=converged, rounds=rounds, regions=None,
+                  reach=None, rows=None, cost=table, terminal=terminal, connectivity=conn, classes=int(votes.shape[0]))
+    if regions:
+        k, cap = int(votes.shape[0]), int(options.get("max_regions", 1024))
+        labels = ops.mask_regions(mask, k, conn)
+        region_table, region_counts, index = ops.region_table(mask, labels, k, None, 128, cap)
+        result["regions"] = (region_table, region_counts, index)
+        result["reach"], result["rows"] = ops.region_access(mask, d, origin, index, region_counts, k, cap)
+    return result
+
+
+def access_report(result):
+    """mosaic_access()'s result on the host: cls uint8 [CH, CW], d uint32 (ops.ACCESS_NONE: no value), origin int32 or None, status [4],
+    converged, rounds, table = region_table's rows [regions, 10], rows = region_access' [regions, 8], reach [K, 4], index int32 [CH, CW] = the
+    row of every pixel's region (all None without regions),
+    and cost, terminal, connectivity, classes as mosaic_access holds them."""
+    host = lambda t: t.cpu().numpy()  # noqa: E731
+    report = {k: result[k] for k in ("converged", "rounds", "cost", "terminal", "connectivity", "classes")}
+    report.update(cls=host(result["cls"]), d=host(result["d"]).view(np.uint32), origin=None if result["origin"] is None else host(result["origin"]),
+                  status=host(result["status"]), table=None, rows=None, reach=None, index=None)
+    if result["regions"] is not None:
+        table, counts, index = result["regions"]
+        written = int(host(counts)[0, 1])
+        report.update(table=host(table)[0, :written], rows=host(result["rows"])[0, :written], reach=host(result["reach"])[0], index=host(index)[0])
+    return report
+
+
+def write_access_csv(path, report, class_names=None):
+    """access_report()'s regions as a CSV, one row per region: its row number, class, area and centroid (region_table's), its state --
+    reached or cut_off; from a field that did not converge reached_bound (the cost is an upper bound) or not_reached_yet -- and for a
+    reached one the cost of the cheapest route to it, the pixel of the region that route arrives at, the seed it starts from and that
+    seed's region row (empty: none).  Costs are tenths of a mask pixel of the anchor frame on the 5-7 chamfer metric, times the classes'
+    costs: not metres."""
+    if report["table"] is None:
+        raise ValueError("write_access_csv: the result has no regions (mosaic_access(regions=True))")
+    name = (lambda c: str(c)) if class_names is None else (lambda c: str(class_names[c]))
+    done = bool(report["converged"])
+    with open(path, "w", newline="") as f:
+        f.write("region,class,area,centroid_x,centroid_y,state,cost,at_x,at_y,origin_x,origin_y,origin_region\n")
+        for r, (t, a) in enumerate(zip(np.asarray(report["table"]).tolist(), np.asarray(report["rows"]).tolist())):
+            reached = a[0] >= 0
+            state = ("reached" if done else "reached_bound") if reached else ("cut_off" if done else "not_reached_yet")
+            route = [str(v) if reached else "" for v in a[:5]] + [str(a[5]) if reached and a[5] >= 0 else ""]
+            f.write(",".join([str(r), name(t[0]), str(t[1]), f"{t[6] / t[1]:.2f}", f"{t[7] / t[1]:.2f}", state] + route) + "\n")
+
+
+def access_image(report, palette=ops.FLOOD_PALETTE, fill=(0, 0, 0), cut_off=ACCESS_CUT_OFF):
+    """The cost field as a ramp over the class colours, drawn on the host -> uint8 numpy [CH, CW, 3].  A pixel with a value keeps between
+    all (cost 0) and a third (the largest cost) of its class colour's brightness; a pixel without one is drawn at a sixth of it; unseen
+    ground is `fill`; the regions of the terminal classes that no route reaches (with regions=True) are `cut_off`."""
+    cls, d = report["cls"], report["d"]
+    colours = np.array([fill] * 256, np.float64)
+    colours[:len(palette)] = np.array(palette, np.float64)
+    base = colours[cls]
+    has = d != ops.ACCESS_NONE
+    top = max(int(d[has].max()) if has.any() else 0, 1)
+    t = np.where(has, d.astype(np.float64) / top, 0.0)[..., None]
+    img = np.where(has[..., None], base * (1.0 - t * 2 / 3), base / 6.0)
+    img[cls == 255] = fill
+    if report["table"] is not None:
+        lost = [r for r, (t, a) in enumerate(zip(report["table"].tolist(), report["rows"].tolist())) if t[0] in report["terminal"] and a[0] < 0]
+        img[np.isin(report["index"], lost)] = cut_off
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def write_access_png(path, report, **kw):
+    """access_image() as a PNG."""
+    from PIL import Image
+
+    Image.fromarray(access_image(report, **kw)).save(path)
+
+
+def access_route(report, x, y):
+    """The route from a seed to canvas pixel (x, y), read backwards off the field on the host: from (x, y), at every pixel p the first
+    neighbour q, in the move table's order, with an allowed move q -> p and d[q] + move == d[p], until a pixel with d = 0.  O(route
+    length).  -> [(x, y), ..., (seed_x, seed_y)].  Needs a converged field; a pixel without a value has no route."""
+    cls, d, cost, conn = report["cls"], report["d"], report["cost"], report["connectivity"]
+    if not report["converged"]:
+        raise ValueError("access_route: the field has not converged: its values are upper bounds, not route costs")
+    ch, cw = cls.shape
+    x, y = int(x), int(y)
+    if not (0 <= x < cw and 0 <= y < ch) or d[y, x] == ops.ACCESS_NONE:
+        raise ValueError(f"access_route: ({x}, {y}) has no value")
+    terminal = set(int(k) for k in report["terminal"])
+    walk = lambda px, py: 0 <= px < cw and 0 <= py < ch and cls[py, px] < 32 and cost[cls[py, px]] > 0 and int(cls[py, px]) not in terminal  # noqa: E731
+    chain = [(x, y)]
+    while d[y, x] != 0:
+        for dx, dy, step in ACCESS_MOVES[:8 if conn == 8 else 4]:
+            qx, qy = x + dx, y + dy
+            if not walk(qx, qy) or d[qy, qx] == ops.ACCESS_NONE or (dx and dy and not (walk(qx, y) and walk(x, qy))):
+                continue
+            if int(d[qy, qx]) + step * (cost[cls[qy, qx]] + cost[cls[y, x]]) == int(d[y, x]):
+                x, y = qx, qy
+                break
+        else:
+            raise ValueError(f"access_route: no neighbour of ({x}, {y}) explains its value")
+        chain.append((x, y))
+    return chain
+
+
+def write_access_geojson(path, report):
+    """One LineString per reached region of a terminal class: access_route() from the region's cheapest pixel to its seed, in canvas
+    pixel centres (x + 0.5, y + 0.5), with the region's row, class and cost as properties."""
+    import json
+
+    if report["table"] is None:
+        raise ValueError("write_access_geojson: the result has no regions (mosaic_access(regions=True))")
+    features = []
+    for r, (t, a) in enumerate(zip(np.asarray(report["table"]).tolist(), np.asarray(report["rows"]).tolist())):
+        if t[0] in report["terminal"] and a[0] >= 0:
+            chain = access_route(report, a[1], a[2])
+            features.append(dict(type="Feature", properties=dict(region=r, cls=t[0], cost=a[0]),
+                                 geometry=dict(type="LineString", coordinates=[[px + 0.5, py + 0.5] for px, py in chain])))
+    with open(path, "w") as f:
+        json.dump(dict(type="FeatureCollection", features=features), f)
 
 
 def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):

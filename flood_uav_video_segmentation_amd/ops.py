@@ -902,6 +902,123 @@ def region_proximity(mask, d2, nearest, index, counts, classes, max_regions, tar
     return exposure, near
 
 
+# ------------------------------------------------------------------------------------------ dry-route reachability
+ACCESS_NONE = 0xFFFFFFFF  # FS_ACCESS_NONE; the int32 tensors that carry d show it as -1
+ACCESS_TILE = 32  # FS_ACCESS_TILE
+ACCESS_MAX_COST = 2 ** 31 - 4096  # FS_ACCESS_MAX_COST
+ACCESS_ROUNDS = 64  # rounds per call by default: a guess (an open field needs about one per tile the route crosses)
+
+
+def mask_access_workspace_bytes(n, h, w):
+    """FS_MASK_ACCESS_WORKSPACE_BYTES of include/floodseg_test.h: one 64-bit key per pixel, two dwords per tile, four per frame."""
+    return n * h * w * 8 + n * (-(-h // ACCESS_TILE)) * (-(-w // ACCESS_TILE)) * 8 + n * 16
+
+
+def access_cost_table(cost, what="floodseg.mask_access"):
+    """A cost argument -> the 32 bytes the library reads: a mapping {class id: cost} or a sequence of up to 32 costs, each 0..255."""
+    items = list(cost.items()) if hasattr(cost, "items") else list(enumerate(cost))
+    table = [0] * 32
+    for k, c in items:
+        if not 0 <= int(k) <= 31 or not 0 <= int(c) <= 255:
+            raise ValueError(f"{what}: cost must map class ids 0..31 to 0..255, got {cost}")
+        table[int(k)] = int(c)
+    if not any(table):
+        raise ValueError(f"{what}: the cost table is all zero (cost[k] > 0: class k can be walked on)")
+    return table
+
+
+def mask_access(mask, seeds, cost, terminal=(), connectivity=8, max_cost=0, rounds=ACCESS_ROUNDS, resume=None, want_origin=True, out=None):
+    """The cheapest route from any seed pixel to every pixel of its frame over ground that can be walked on (definition:
+    include/floodseg_test.h, mask_access): uint8 masks and seed planes [n,H,W] -> (d, origin, status).  cost: {class id:
+    0..255} or a sequence, 0 = barrier (ids >= 32 always are); terminal: classes that can be arrived at but not crossed.  A move
+    costs 5 (orthogonal) or 7 (diagonal, connectivity 8, no corner cutting) times the sum of the two pixels' costs.  d: int32 [n,H,W]
+    holding the uint32 values (0 on a seed that counts; FS_ACCESS_NONE, read as -1, where no route exists or it costs more than
+    max_cost).  origin: int32 [n,H,W], the raster index of the seed the route starts from, the smallest among several, -1 where d is
+    FS_ACCESS_NONE; None with want_origin=False.  status: int32 [n,4] = (converged, rounds that lowered a value, pixels with a value,
+    0), on the device.  The call enqueues `rounds` rounds and reads nothing back: where status says 0 the values are upper bounds --
+    costs of real routes -- and resume=(d, origin) of that call continues in place towards the same result.  out: caller-owned contiguous
+    (d, origin) destinations.  The workspace is allocated here.  The default of `rounds` is a guess."""
+    lib = _lib.load()
+    what = "floodseg.mask_access"
+    if resume is not None and out is not None:
+        raise ValueError(f"{what}: give resume or out, not both (a resumed call writes the planes it resumes from)")
+    planes = resume if resume is not None else out
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise ValueError(f"{what}: mask must be uint8 [n,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    if seeds.dtype != torch.uint8 or seeds.shape != mask.shape:
+        raise ValueError(f"{what}: seeds must be uint8 of the mask's shape {tuple(mask.shape)}, got {seeds.dtype} {tuple(seeds.shape)}")
+    n, h, w = mask.shape
+    if not 1 <= h <= 32768 or not 1 <= w <= 32768 or n > 65535 or h * w >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: at most 65535 frames of 1..32768 pixels a side, got {tuple(mask.shape)}")
+    table = access_cost_table(cost, what)
+    bits = class_set(terminal, "terminal", what, allow_empty=True)
+    if connectivity not in (4, 8):
+        raise ValueError(f"{what}: connectivity must be 4 or 8, got {connectivity}")
+    if not 0 <= int(max_cost) <= ACCESS_MAX_COST:
+        raise ValueError(f"{what}: max_cost must be 0..{ACCESS_MAX_COST} (0: the largest), got {max_cost}")
+    if not 1 <= int(rounds) <= 65535:
+        raise ValueError(f"{what}: rounds must be 1..65535, got {rounds}")
+    host = (ctypes.c_uint8 * 32)(*table)  # read by the library during the call
+    if planes is not None:
+        for t, name in zip(planes, ("d", "origin")):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n, h, w) or not t.is_contiguous()):
+                raise ValueError(f"{what}: the {name} plane must be a contiguous int32 [{n},{h},{w}] tensor, got {t.dtype} {tuple(t.shape)}")
+        if planes[0] is None or (planes[1] is not None) != bool(want_origin):
+            raise ValueError(f"{what}: (d, origin) must hold d, and an origin plane exactly when want_origin is set")
+    dev = one_device(mask, seeds, *(planes or ()), what=what)
+    with torch.cuda.device(dev):
+        if planes is None:
+            d = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+            origin = torch.empty((n, h, w), dtype=torch.int32, device=dev) if want_origin else None
+        else:
+            d, origin = planes
+        status = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        if n:
+            work = torch.empty((mask_access_workspace_bytes(n, h, w) // 8,), dtype=torch.int64, device=dev)
+            check(lib.fs_mask_access(ptr(mask.contiguous()), ptr(seeds.contiguous()), n, h, w, ctypes.cast(host, ctypes.c_void_p), bits, int(connectivity),
+                                     int(max_cost), int(rounds), int(resume is not None), ptr(d), ptr(origin), ptr(status), ptr(work), stream_ptr()))
+    return d, origin, status
+
+
+def region_access(mask, d, origin, index, counts, classes, max_regions, out=None):
+    """mask_access' field tabulated per class and per region (definition: include/floodseg_test.h, region_access):
+    -> (reach int64 [n,classes,4], rows int64 [n,max_regions,8]).  reach[f][k] = (pixels of class k, those with a value, the sum of
+    their values, the largest).  rows, one per row of region_table's table (index, counts): (min_d, at_x, at_y, origin_x, origin_y,
+    origin_row, valued pixels, max_d) -- the region's cheapest pixel (lowest raster index), the seed its route starts from and that
+    seed's region row (-1: none; all three -1 with origin=None); a region no pixel of which has a value: (-1, -1, -1, -1, -1, -1, 0, -1).
+    out: caller-owned contiguous (reach, rows) destinations; they are written whole."""
+    lib = _lib.load()
+    what = "floodseg.region_access"
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise ValueError(f"{what}: mask must be uint8 [n,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    n, h, w = mask.shape
+    if not 1 <= h <= 32768 or not 1 <= w <= 32768 or n > 65535 or h * w >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: at most 65535 frames of 1..32768 pixels a side, got {tuple(mask.shape)}")
+    for t, name in ((d, "d"), (origin, "origin"), (index, "index")):
+        if (t is None and name != "origin") or (t is not None and (t.dtype != torch.int32 or t.shape != mask.shape)):
+            raise ValueError(f"{what}: {name} must be int32 of the mask's shape {tuple(mask.shape)}, got "
+                             f"{None if t is None else (t.dtype, tuple(t.shape))}")
+    if counts.dtype != torch.int64 or tuple(counts.shape) != (n, 2):
+        raise ValueError(f"{what}: counts must be int64 [{n},2] (region_table's), got {counts.dtype} {tuple(counts.shape)}")
+    k, cap = int(classes), int(max_regions)
+    if not 1 <= k <= 255 or not 1 <= cap <= 65536:
+        raise ValueError(f"{what}: classes must be 1..255 and max_regions 1..65536, got {classes} and {max_regions}")
+    if out is not None and (out[0].dtype != torch.int64 or tuple(out[0].shape) != (n, k, 4) or not out[0].is_contiguous() or out[1].dtype != torch.int64
+                            or tuple(out[1].shape) != (n, cap, 8) or not out[1].is_contiguous()):
+        raise ValueError(f"{what}: out must be contiguous int64 [{n},{k},4] and [{n},{cap},8] tensors")
+    dev = one_device(mask, d, origin, index, counts, *(out or ()), what=what)
+    with torch.cuda.device(dev):
+        if out is None:
+            reach = torch.empty((n, k, 4), dtype=torch.int64, device=dev)
+            rows = torch.empty((n, cap, 8), dtype=torch.int64, device=dev)
+        else:
+            reach, rows = out
+        if n:
+            check(lib.fs_region_access(ptr(mask.contiguous()), ptr(d.contiguous()), ptr(None if origin is None else origin.contiguous()),
+                                       ptr(index.contiguous()), ptr(counts.contiguous()), n, h, w, k, cap, ptr(reach), ptr(rows), stream_ptr()))
+    return reach, rows
+
+
 # ------------------------------------------------------------------------------------------ the flood-extent mosaic
 POSE_ONE = 1 << 20  # 1 << FS_POSE_FRAC: poses and pair models are Q20
 MOSAIC_MAX_SIDE = 16384

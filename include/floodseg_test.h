@@ -1446,6 +1446,99 @@ typedef struct fs_hook_tables14 {
     fs_ext14_api ext14;
 } fs_hook_tables14;
 
+/* ---- The SIXTEENTH table.  fs_ext14_api is frozen as well (1 member, 24 bytes; tests/test_access_cpu.py), so ops added since live in
+ * a table of their own, append-only, that the library places directly behind fs_hook_tables14 by the same pattern:
+ *     const fs_hook_tables15* t = (const fs_hook_tables15*)fs_test_hooks();   t->ext15.mask_access(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables14: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext15.magic == FS_EXT15_MAGIC and ext15.size >= the end of the member it needs. */
+#define FS_EXT15_MAGIC 0x4653455854413135ull /* "FSEXTA15" */
+#define FS_ACCESS_NONE 0xFFFFFFFFu           /* mask_access' d where no route exists or the cheapest one costs more than R */
+#define FS_ACCESS_TILE 32                    /* the edge of the tile one workgroup of mask_access relaxes */
+#define FS_ACCESS_MAX_COST 0x7FFFF000u       /* the largest R: 2^31 - 4096 */
+
+typedef struct fs_ext15_api {
+    uint64_t magic; /* FS_EXT15_MAGIC */
+    size_t size;    /* sizeof(fs_ext15_api) of the library that was built */
+
+    /* ---- DRY-ROUTE REACHABILITY: THE COST FIELD (csrc/access_ops.hip, csrc/access_defs.h).  OUR DEFINITION: the reference
+     * has nothing like it.  The cheapest route from any seed pixel to every pixel over ground that can be walked on, around barriers.
+     * The same rules as code: csrc/access_defs.h (host and device) and tests/access_ref.py (a heap Dijkstra and a literal relaxation).
+     * Integers throughout.  Costs are in MASK PIXELS of whatever produced the mask, tenths of a pixel on the 5-7 chamfer metric.
+     * Inputs, per frame:
+     *   mask          uint8 [n][H][W], at any byte address.  Ids >= 32 (the mosaic's 255 = never seen among them) are always barriers.
+     *   seeds         uint8 [n][H][W], at any byte address; non-zero marks a seed.
+     *   cost          uint8 [32] in HOST memory (read during the call): the walking cost of class k; 0 = barrier.  Not all zero.
+     *   terminal_set  uint32: a class in it with cost > 0 is TERMINAL: it can be arrived at, never left or crossed.
+     *   connectivity  4 or 8.      max_cost  R: 0 = the largest allowed, FS_ACCESS_MAX_COST; else 1 <= R <= FS_ACCESS_MAX_COST.
+     * A pixel is PASSABLE if its class has cost > 0 and is not terminal.  A seed pixel counts only if it is passable.
+     * A MOVE goes from a pixel p to a neighbour q of the same frame and costs step * (cost[mask[p]] + cost[mask[q]]), step = 5 for an
+     * orthogonal move and 7 for a diagonal one (connectivity 8 only).  It is allowed iff p is passable, q is passable or terminal, and,
+     * for a diagonal move, both pixels orthogonally between p and q are passable (no corner cutting: a diagonal line of barrier pixels
+     * one pixel wide is a wall).  The largest move costs 7 * 510 = 3570, so no sum below passes 2^31.
+     * Outputs:
+     *   d       uint32 [n][H][W]: the minimum total cost of a sequence of allowed moves from any seed pixel of the same frame that counts;
+     *           0 on such a seed; FS_ACCESS_NONE where no sequence exists or the minimum exceeds R.  A value that is not FS_ACCESS_NONE is
+     *           the exact minimum: R only removes values.
+     *   origin  int32 [n][H][W], or NULL: the raster index y * W + x of a seed pixel that attains d, the smallest index among several (the
+     *           minimum of the 64-bit key d << 32 | origin over all routes); -1 where d is FS_ACCESS_NONE.
+     *   status  int32 [n][4], written on the device: (converged 0/1, the rounds of this call in which a value was lowered, the pixels
+     *           with a value, 0).
+     * THE CONTRACT.  The op enqueues `rounds` (1..65535) rounds whatever happens in them.  The fixed point is unique, so once status
+     * says converged the planes are a function of the inputs alone.  Where it does not, every value that is not FS_ACCESS_NONE is still
+     * the cost of a real route: an upper bound, never too small, and origin is the seed of such a route.  resume = 1: the op starts from
+     * the d (and origin) planes as an earlier call with the same other arguments left them, instead of from the seeds, and goes on
+     * towards the same fixed point; a converged frame stays exactly as it is.  The second status word depends on how the tiles cut the
+     * frame and on which of two neighbouring tiles of a round wrote first; the planes and the other words do not once converged.
+     * LAUNCHES.  2 + rounds.  (1) Every pixel's key d << 32 | origin as one 64-bit word of the workspace (from the seeds, or from the
+     * planes); every tile dirty.  (2) One round: one workgroup of 256 per FS_ACCESS_TILE x FS_ACCESS_TILE tile; a tile that is not dirty
+     * returns at once; a dirty one stages its keys and a ring of one pixel in LDS (34 x 34 x 10 bytes), turns the classes into the eight
+     * move costs of each of its four pixels per thread, and sweeps in gather form -- all read, a barrier, the owners write, a barrier --
+     * until a sweep lowers nothing, at most 128 times (then it marks itself dirty); lowered keys go back as aligned 64-bit words; the
+     * tile marks dirty every neighbour tile whose ring holds a pixel it lowered.  Nothing waits on another workgroup: a tile that reads a
+     * neighbour's key while that neighbour lowers it sees the old or the new word and is marked by that neighbour either way.  (3) The
+     * keys become the planes; status.  The two sets of dirty flags alternate by the round's parity.
+     * workspace = FS_MASK_ACCESS_WORKSPACE_BYTES(n, H, W) bytes at an 8-byte aligned address, the caller's: the keys, two dwords per
+     * tile, four per frame.  Its contents need not survive between calls.  Nothing is allocated, synchronised or read back on the host;
+     * `cost` is read during the call.
+     * Refused before a launch: a null mask, seeds, cost, d, status or workspace; n < 1 or n > 65535; H or W < 1; H * W >= 2^31 - 1; H or
+     * W > 32768; connectivity not 4 or 8; R above FS_ACCESS_MAX_COST; rounds outside 1..65535; resume not 0 or 1; d, origin or status not
+     * aligned to 4 bytes, the workspace not to 8; a cost table that is all zero. */
+#define FS_MASK_ACCESS_WORKSPACE_BYTES(n, H, W)                                                                                                      \
+    ((size_t)(n) * (size_t)(H) * (size_t)(W) * 8 +                                                                                                   \
+     (size_t)(n) * (((size_t)(H) + FS_ACCESS_TILE - 1) / FS_ACCESS_TILE) * (((size_t)(W) + FS_ACCESS_TILE - 1) / FS_ACCESS_TILE) * 8 + (size_t)(n) * 16)
+    int (*mask_access)(const uint8_t* mask, const uint8_t* seeds, int n, int H, int W, const uint8_t* cost, uint32_t terminal_set, int connectivity,
+                       uint32_t max_cost, int rounds, int resume, uint32_t* d, int32_t* origin, int32_t* status, void* workspace, fs_stream stream);
+
+    /* ---- The cost field tabulated per class and per region (csrc/access_ops.hip).  OUR DEFINITION; the sibling of
+     * region_proximity.
+     * Inputs:
+     *   mask    uint8 [n][H][W];   d uint32 [n][H][W] and origin int32 [n][H][W] (or NULL) as mask_access wrote them;
+     *   index   int32 [n][H][W] and counts int64 [n][2], region_table's;   K classes 1..255;   max_regions 1..65536.
+     * rows(f) = min(max(counts[f][1], 0), max_regions); a pixel p of frame f BELONGS to row r if index[f][p] == r and 0 <= r < rows(f).
+     * Outputs, each cleared on the stream and written whole by every call:
+     *   reach  int64 [n][K][4]: per class k (the pixels with mask == k, those of them with a value, the sum of their values, the
+     *          largest value; the last two 0 without one).
+     *   rows   int64 [n][max_regions][8], row r of frame f = (min_d, at_x, at_y, origin_x, origin_y, origin_row, valued, max_d): min_d
+     *          the smallest d other than FS_ACCESS_NONE over the row's pixels, (at_x, at_y) the pixel that attains it, the lowest raster
+     *          index on a tie; (origin_x, origin_y) = origin at that pixel, origin_row = index at the origin pixel, -1 if that pixel
+     *          belongs to no row; valued = the row's pixels with a value, max_d the largest of them.  A row none of whose pixels has a
+     *          value: (-1, -1, -1, -1, -1, -1, 0, -1).  origin == NULL: origin_x = origin_y = origin_row = -1.  Rows at and behind
+     *          rows(f) are zero.
+     * LAUNCHES.  Three: set up; one pass over the pixels (an LDS table [K][4] per workgroup, a wave whose 64 pixels are of one class
+     * adding to it once, flushed with one 64-bit atomic per non-zero cell; per row a 64-bit atomic minimum of d << 32 | raster index, an atomic sum and an atomic maximum, once per run of a
+     * row along the 1024 consecutive pixels a wave owns); finish.  Integer sums, minima and maxima: the order does not matter.  No
+     * workspace; nothing is allocated, synchronised or read on the host.
+     * Refused before a launch: a null mask, d, index, counts, reach or rows; n, H, W as mask_access; K or max_regions out of range; d,
+     * origin or index not aligned to 4 bytes; counts, reach or rows not aligned to 8. */
+    int (*region_access)(const uint8_t* mask, const uint32_t* d, const int32_t* origin, const int32_t* index, const int64_t* counts, int n, int H, int W,
+                         int K, int max_regions, int64_t* reach, int64_t* rows, fs_stream stream);
+} fs_ext15_api;
+
+typedef struct fs_hook_tables15 {
+    fs_hook_tables14 base14;
+    fs_ext15_api ext15;
+} fs_hook_tables15;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus
