@@ -2,8 +2,11 @@
 //
 //   SPLIT = false  v_mfma_f32_32x32x2_f32: exact f32 fmaf-chain numerics at 64 FLOP/clk/SIMD (157 TFLOP/s chip peak).
 //   SPLIT = true   (round 3, the networks' default) every fp32 operand as the exact sum of three bf16 terms, six of the nine cross
-//                  products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation: fp32 accuracy (the dropped terms are <= 2^-23 of a
+//                  products on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: fp32 accuracy (the dropped terms are <= 2^-23 of a
 //                  product) at 2.67x the fp32 pipe's rate per clock.  The arithmetic is defined in split.h.
+//                  The 16x16x32 shape (since profiles/r33_mfma_shape.txt) costs the same matrix-pipe cycles per FLOP as 32x32x16 and
+//                  more issue slots, but fewer joules: under these launches the card sits at its power cap, so it holds ~2.05 GHz
+//                  instead of ~1.85 and a launch ends 3-6 % sooner.  Every split tile runs the same loop: all tiles give the same bits.
 //
 // Mapping (one 256-thread workgroup = 4 waves, one per SIMD, 2x2 over the block tile):
 //   GEMM M = B*Ho*Wo output pixels (A rows, gathered NHWC pixels: 32 channels = one 128-B line)
@@ -16,6 +19,8 @@
 // sums over k, so any k permutation is legal.
 // D layout (32x32): col(n) = lane&31, row(m) = mfma32_row(reg, lane>>5) (split.h)
 //   -> each store instruction writes two 128-B channel runs: coalesced NHWC epilogue.
+// (The four lines above describe the fp32 route.  The split route's LDS keys, lane maps and 16x16 accumulators are described at its
+//  loop below and in split.h; after the loop its accumulators are regrouped into this 32x32 layout, so the epilogues are shared.)
 // History (measured on MI355X, profiles/r01_conv_*.txt): the bring-up kernel staged tiles through VGPRs with two barriers
 // per chunk (120 TFLOP/s on the decoder conv); double-buffered LDS + register-pinned fragment prefetch alone: null;
 // global_load_lds with a zero page: 128; buffer_load...lds with range-check padding: 138.  Tried and measured null,
@@ -116,7 +121,8 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
     const int nchunks = nchunks1 + (DUAL ? p.Cin2 >> 5 : 0);
 
     const int sc = t & 7, r0 = t >> 3;
-    const int swz = sc ^ ((r0 >> 1) & 7);  // logical chunk this lane fetches into LDS slot sc (same key for rows r0+32j)
+    // logical chunk this lane fetches into LDS slot sc (same key for rows r0+32j; SPLIT: the key of the 16-row x 4-k-block reads, split.h)
+    const int swz = sc ^ (SPLIT ? split_row_key(r0) : ((r0 >> 1) & 7));
     constexpr unsigned SENT = 0x80000000u;  // >= num_records of both descriptors (tensors < 2 GiB, checked by the launcher)
     // A descriptor starts `pad` rows and `pad` pixels BEFORE the tensor so that every tap offset (soffset) is >= 0;
     // lanes that are valid by the tap mask always land inside the tensor.
@@ -176,13 +182,13 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
     }
     unsigned b_voff[RB1];
     if (SPLIT) {
-        // lane -> (row, 16-B slot) of a 16-row x 64-B group; the slot holds piece slot ^ ((row >> 2) & 3) of the row's 32 bf16, which
-        // makes the fragment reads (16 consecutive rows, one piece) hit 16 different 16-B columns of the 256-B bank row
+        // lane -> (row, 16-B slot) of a 16-row x 64-B group; the slot holds piece slot ^ split_plane_key(row) of the row's 32 bf16, which
+        // keeps the fragment reads (16 consecutive rows x the four pieces) off each other's banks
 #pragma unroll
         for (int j = 0; j < RB1; ++j) {
             const int row = 16 * (wv + (NT / 64) * j) + (lane >> 2);
             const int n = n0 + row;
-            b_voff[j] = (n < p.Cout && row < BN) ? (unsigned)(n * ldw * 2 + (((lane & 3) ^ ((row >> 2) & 3)) * 16)) : SENT;
+            b_voff[j] = (n < p.Cout && row < BN) ? (unsigned)(n * ldw * 2 + (((lane & 3) ^ split_plane_key(row)) * 16)) : SENT;
         }
     } else {
 #pragma unroll
@@ -289,62 +295,85 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
     }
     if constexpr (SPLIT) {
         // Split operands (split.h): the filters arrive split (three planes); the pixels are split here, in registers, right after the
-        // fragment read.  A chunk of 32 k = two MFMA steps of 16 k; lane (i, hh) owns k = 16 s + 8 hh .. + 7 of row i in both operands.
-        bf16x8 A3[TM][3], B3[TN][3], A3n[TM][3], B3n[TN][3];
+        // fragment read.  The MFMA is v_mfma_f32_16x16x32_bf16: a chunk of 32 k = two ROW HALVES u = 0, 1 of 16 rows x 32 k.  Lane
+        // (r = l & 15, kb = l >> 4) owns k = 8 kb .. 8 kb + 7 of tile row 16 u + mfma16_row(r) (pixels) and of column 16 j + r (filters).
+        // A filter fragment covers the chunk's whole k and serves both halves: WN / 16 x 3 fragments, read once per chunk.
+        static_assert(TM == 1, "split tiles: one 32-row block per wave");
+        constexpr int NB = WN / 16;  // 16-column accumulator blocks per half (even)
+        const int r16 = lane & 15, kb = lane >> 4;
+        const int prow = mfma16_row(r16);
+        // floats from the stage's start: the lane's first 16-B piece of its pixel row (the second is at ^ 4), of its filter row
+        const int a_off = (wm * WM + prow) * BK + 4 * ((2 * kb) ^ split_row_key(prow));
+        const int b_off = BM * BK + (wn * WN + r16) * 16 + 4 * (kb ^ split_plane_key(r16));
+        bf16x8 A3[TM][3], A3n[TM][3], Bf[NB][3];
+        f32x4 acc16[2][NB];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc16[u][j][e] = 0.f;
         f32x4 araw[TM][2];
         u32x4 ah[TM][3];
-#define FS_READ3(STG, S_, RAW_, B_)                                                                               \
+#define FS_READ_A(STG, U_)                                                                                        \
     {                                                                                                             \
-        const float* a_src = lds + (STG) * STAGE;                                                                 \
-        const float* b_src = a_src + BM * BK;                                                                     \
-        const int c0 = (4 * (S_) + 2 * hh) ^ sw;                                                                  \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                          \
-            RAW_[i][0] = *reinterpret_cast<const f32x4*>(&a_src[(wm * WM + i * 32 + l31) * BK + 4 * c0]);         \
-            RAW_[i][1] = *reinterpret_cast<const f32x4*>(&a_src[(wm * WM + i * 32 + l31) * BK + 4 * (c0 ^ 1)]);   \
-        }                                                                                                         \
-        const int bslot = (2 * (S_) + hh) ^ ((l31 >> 2) & 3);                                                     \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                            \
-            _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                                      \
-                B_[j][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&b_src[pl * BPL + (wn * WN + j * 32 + l31) * 16 + 4 * bslot])); \
+        const float* a_src = lds + (STG) * STAGE + (U_) * 16 * BK;                                                \
+        araw[0][0] = *reinterpret_cast<const f32x4*>(&a_src[a_off]);                                              \
+        araw[0][1] = *reinterpret_cast<const f32x4*>(&a_src[a_off ^ 4]);                                          \
     }
-        // One MFMA step: 6 TM TN MFMAs (32 cycles each on the SIMD's matrix pipe, 8 of them holding the issue port) with the split
-        // of the NEXT step's pixels threaded through them in program order -- every slot is fenced (sched_barrier), because the
-        // compiler otherwise issues the MFMAs back to back and the ~36 TM VALU instructions of the split after them.  Units of the
-        // split: level 0 of every pair (cvt_pk, two unpacks, subtract), then level 1 of every pair, one unit per slot from slot S0 on
-        // (the fragment reads land under the first slots); a pair's final cvt_pk rides in the slot after its level 1.
-        constexpr int NS = 6 * TM * TN, NP = 4 * TM, NU = 3 * NP, S0 = NS >= 24 ? 4 : NS / 6;
+#define FS_READ_B(STG, J_)                                                                                        \
+    {                                                                                                             \
+        const float* b_src = lds + (STG) * STAGE + (J_) * 256;                                                    \
+        _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                                          \
+            Bf[J_][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&b_src[pl * BPL + b_off]));   \
+    }
+        // One row half: 6 NB MFMAs (16 cycles each on the SIMD's matrix pipe) with the split of the NEXT half's pixels threaded through
+        // them in program order -- every slot is fenced (sched_barrier), because the compiler otherwise issues the MFMAs back to back
+        // and the ~36 VALU instructions of the split after them.  Units of the split: level 0 of every pair (cvt_pk, two unpacks,
+        // subtract), then level 1 of every pair, one unit every SD slots from slot S0 on (the fragment reads land under the first
+        // slots); a pair's final cvt_pk rides in the slot after its level 1.
+        // Half 0 runs term-outer (as the 32x32x16 loop did); half 1 runs column-block-pair-outer with the six terms inner, two blocks
+        // alternating, so that a pair's six filter fragments are dead after its 12 MFMAs: the next chunk's are requested into the same
+        // registers right there (ROLL_ = that chunk's stage) and roll over about one half ahead of their first use.  Every output
+        // element sees the six terms in SPLIT_PA / SPLIT_PB order in either half and in every tile.
+        constexpr int NS = 6 * NB, NP = 4, NU = 3 * NP, S0 = NS >= 24 ? 4 : NS / 6;
+        constexpr int SD = 4 * NP <= NS - S0 ? 2 : 1;
         float rq[NP][2];
-#define FS_STEP3(A_, B_, RAW_, AN_)                                                                               \
+#define FS_HALF(U_, PAIRS_, ROLL_, A_, AN_)                                                                       \
     _Pragma("unroll") for (int k = 0; k < NS; ++k) {                                                              \
-        const int term = k / (TM * TN), i_ = (k % (TM * TN)) / TN, j_ = k % TN;                                   \
-        acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[i_][SPLIT_PA[term]], B_[j_][SPLIT_PB[term]], acc[i_][j_], 0, 0, 0); \
+        const int term = (PAIRS_) ? (k % 12) / 2 : k / NB, j_ = (PAIRS_) ? 2 * (k / 12) + (k & 1) : k % NB;       \
+        acc16[U_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_[0][SPLIT_PA[term]], Bf[j_][SPLIT_PB[term]], acc16[U_][j_], 0, 0, 0); \
+        if ((PAIRS_) && k % 12 == 11) {                                                                           \
+            FS_READ_B(ROLL_, j_ - 1)                                                                              \
+            FS_READ_B(ROLL_, j_)                                                                                  \
+        }                                                                                                         \
         _Pragma("unroll") for (int u = 0; u < NU; ++u) {                                                          \
             const int lvl = u / NP, pr = u % NP;                                                                  \
             const int v_ = lvl < 2 ? u : NP + pr;  /* level unit (of the pair's level 1 for a final) */            \
-            const int sl = S0 + (2 * NP <= NS - S0 ? v_ : v_ * (NS - S0) / (2 * NP));                             \
-            if ((lvl < 2 ? sl : (sl + 1 < NS ? sl + 1 : NS - 1)) == k) split_unit(lvl, pr, RAW_, rq, ah, true);   \
+            const int sl = S0 + (2 * NP <= NS - S0 ? SD * v_ : v_ * (NS - S0) / (2 * NP));                        \
+            if ((lvl < 2 ? sl : (sl + 1 < NS ? sl + 1 : NS - 1)) == k) split_unit(lvl, pr, araw, rq, ah, true);   \
         }                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
     }                                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                                \
-        _Pragma("unroll") for (int pl = 0; pl < 3; ++pl) AN_[i][pl] = __builtin_bit_cast(bf16x8, ah[i][pl]);
-        FS_READ3(0, 0, araw, B3)
-        {   // prologue: split step 0's pixels (no MFMA to hide under yet)
+    _Pragma("unroll") for (int pl = 0; pl < 3; ++pl) AN_[0][pl] = __builtin_bit_cast(bf16x8, ah[0][pl]);
+        FS_READ_A(0, 0)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) FS_READ_B(0, j)
+        {   // prologue: split half 0's pixels (no MFMA to hide under yet)
 #pragma unroll
             for (int u = 0; u < NU; ++u) split_unit(u / NP, u % NP, araw, rq, ah, false);
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) A3[i][pl] = __builtin_bit_cast(bf16x8, ah[i][pl]);
+            for (int pl = 0; pl < 3; ++pl) A3[0][pl] = __builtin_bit_cast(bf16x8, ah[0][pl]);
         }
         unsigned touch0 = 0, touch1 = 0;
         int touch_kc = (!DUAL && p.res && p.res_touch) ? max(nchunks - 2, 0) : -1;  // the chunk after whose barrier the residual lines are touched
         asm volatile("" : "+s"(touch_kc));  // opaque: the loop is not to be versioned on it
         for (int kc = 0; kc < nchunks; ++kc) {
-            FS_READ3(cur, 1, araw, B3n)
+            FS_READ_A(cur, 1)
             __builtin_amdgcn_sched_barrier(0);
-            FS_STEP3(A3, B3, araw, A3n)
+            FS_HALF(0, false, 0, A3, A3n)
             __builtin_amdgcn_sched_barrier(0);
+            // every read of stage `cur` has been issued: the pixels of half 1 above, the filter fragments during the previous half 1
             FS_DMA_PUBLISH()  // every wave's reads of stage `cur` are done, chunk kc + 1 has landed
             if (kc + 2 < nchunks) {
                 FS_DMA_ALL(cur)
@@ -362,16 +391,32 @@ __device__ __forceinline__ void conv_tile(ConvParams p, const int m0, const int 
                 touch1 = __builtin_amdgcn_raw_buffer_load_b32(t_rsrc, ok1 ? (unsigned)((m0 + r1t) * p.ld_res + n0 + c1t * 32) * 4u : 0x80000000u, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            FS_READ3(cur ^ 1, 0, araw, B3)  // (after the last chunk: a stale stage, read and never used)
+            FS_READ_A(cur ^ 1, 0)  // (after the last chunk: a stale stage, read and never used -- as are the fragments half 1 rolls in)
             __builtin_amdgcn_sched_barrier(0);
-            FS_STEP3(A3n, B3n, araw, A3)
+            FS_HALF(1, true, cur ^ 1, A3n, A3)
             __builtin_amdgcn_sched_barrier(0);
             cur ^= 1;
         }
         asm volatile("" ::"v"(touch0), "v"(touch1));  // keeps the two dead loads (and their registers) alive to here
+        // Back to the 32x32 layout of the epilogues: with the rows of a half in mfma16_row order, one v_permlane16_swap per register
+        // pair turns column blocks 2 J and 2 J + 1 of half u into registers 8 u .. 8 u + 7 of 32-column block J.
+#pragma unroll
+        for (int J = 0; J < TN; ++J)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    // (scalars first: __builtin_bit_cast applied to a vector ELEMENT reads element 0 with this compiler)
+                    const float x = acc16[u][2 * J][e], y = acc16[u][2 * J + 1][e];
+                    const auto sw2 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, y), false, false);
+                    const unsigned lo = sw2[0], hi = sw2[1];
+                    acc[0][J][8 * u + e] = __builtin_bit_cast(float, lo);
+                    acc[0][J][8 * u + 4 + e] = __builtin_bit_cast(float, hi);
+                }
         if (!DUAL && p.res) igemm_load_residual(rv, p, M, em_base, en_base);
-#undef FS_READ3
-#undef FS_STEP3
+#undef FS_READ_A
+#undef FS_READ_B
+#undef FS_HALF
     } else {
     if (!DUAL && p.res && nchunks <= 2) igemm_load_residual(rv, p, M, em_base, en_base);
     FS_FRAGS(0, 0, a0, b0)

@@ -1,5 +1,6 @@
 // Epilogue of the matrix-core GEMM kernel (conv_igemm.hip): y = act(acc * scale + shift (+ residual)) for the 32x32
-// accumulator blocks of v_mfma_f32_32x32x*: col(n) = lane & 31, row(m) = mfma32_row(reg, lane >> 5) (split.h).
+// accumulator blocks of v_mfma_f32_32x32x*: col(n) = lane & 31, row(m) = mfma32_row(reg, lane >> 5) (split.h).  The split route
+// accumulates in 16x16 blocks and regroups them into this layout behind its loop (conv_igemm.hip), so nothing here knows about them.
 #pragma once
 #include "kernels.h"
 #include "split.h"
