@@ -259,6 +259,14 @@ _EXT15_HOOKS = [
 ]
 EXT15_MAGIC = 0x4653455854413135  # FS_EXT15_MAGIC
 
+# members of fs_ext16_api, the seventeenth table (append-only, behind the sixteen frozen ones), in declaration order after `magic` and `size`
+_EXT16_HOOKS = [
+    ("ground_area", c_int, [c_void] + [c_int] * 4 + [c_void] + [c_int] + [c_void] + [c_int] + [c_void] * 4),
+    ("ground_rectify", c_int, [c_void] + [c_int] * 7 + [ctypes.c_int64] * 2 + [c_int] + [c_void] * 4 + [c_int] + [ctypes.c_uint32] + [c_void]),
+    ("ground_points", c_int, [c_void] + [c_int] + [c_void] + [c_int] * 2 + [c_void] * 2),
+]
+EXT16_MAGIC = 0x4653455854413136  # FS_EXT16_MAGIC
+
 
 def _struct(name, *fields):
     return type(name, (ctypes.Structure,), {"_fields_": list(fields)})
@@ -302,6 +310,8 @@ FsExt14Api = _struct("FsExt14Api", *_EXT_HEAD, *_members(_EXT14_HOOKS))
 FsHookTables14 = _struct("FsHookTables14", ("base13", FsHookTables13), ("ext14", FsExt14Api))
 FsExt15Api = _struct("FsExt15Api", *_EXT_HEAD, *_members(_EXT15_HOOKS))
 FsHookTables15 = _struct("FsHookTables15", ("base14", FsHookTables14), ("ext15", FsExt15Api))
+FsExt16Api = _struct("FsExt16Api", *_EXT_HEAD, *_members(_EXT16_HOOKS))
+FsHookTables16 = _struct("FsHookTables16", ("base15", FsHookTables15), ("ext16", FsExt16Api))
 
 # One row per hook table, in the library's order.  count / nth: the words the error messages use for the tables in front of it and for
 # the table itself; magic: the NAME of its module global, read when a lookup happens; api: the table's struct; outer: the struct that
@@ -325,6 +335,7 @@ _TABLES = [
     _Table("thirteen", "thirteenth", _EXT13_HOOKS, "EXT13_MAGIC", FsExt13Api, FsHookTables13, "ext13"),
     _Table("fourteen", "fourteenth", _EXT14_HOOKS, "EXT14_MAGIC", FsExt14Api, FsHookTables14, "ext14"),
     _Table("fifteen", "fifteenth", _EXT15_HOOKS, "EXT15_MAGIC", FsExt15Api, FsHookTables15, "ext15"),
+    _Table("sixteen", "sixteenth", _EXT16_HOOKS, "EXT16_MAGIC", FsExt16Api, FsHookTables16, "ext16"),
 ]
 _TABLE_OF = {"fs_" + h[0]: n for n, t in enumerate(_TABLES) for h in t.hooks}
 
@@ -406,7 +417,7 @@ def _hook_names(n):
 
 (hook_names, ext_hook_names, ext2_hook_names, ext3_hook_names, ext4_hook_names, ext5_hook_names, ext6_hook_names, ext7_hook_names,
  ext8_hook_names, ext9_hook_names, ext10_hook_names, ext11_hook_names, ext12_hook_names, ext13_hook_names,
- ext14_hook_names, ext15_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
+ ext14_hook_names, ext15_hook_names, ext16_hook_names) = (functools.partial(_hook_names, n) for n in range(len(_TABLES)))
 
 
 def check(rc):

@@ -672,7 +672,23 @@ static int fs_region_access(const uint8_t* mask, const uint32_t* d, const int32_
                                     reinterpret_cast<long long*>(reach), reinterpret_cast<long long*>(rows), S(stream));
 }
 
-// the sixteen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
+// georeferencing (ground_ops.hip): the launchers validate, nothing is launched on a refusal; the models are host arrays of nine doubles
+static int fs_ground_area(const uint8_t* cls, int CH, int CW, int ox, int oy, const double* forward, int K, const int32_t* index, int max_regions,
+                          int64_t* class_area2, int64_t* region_area2, int64_t* counts, fs_stream stream) {
+    return fs::launch_ground_area(cls, CH, CW, ox, oy, forward, K, index, max_regions, reinterpret_cast<long long*>(class_area2),
+                                  reinterpret_cast<long long*>(region_area2), reinterpret_cast<long long*>(counts), S(stream));
+}
+static int fs_ground_rectify(const double* inverse, int CH, int CW, int ox, int oy, int GH, int GW, int gsd_mm, int64_t e0_mm, int64_t ntop_mm, int nplanes,
+                             const uint8_t* const* planes, uint8_t* const* outs, const uint32_t* rgba, uint8_t* rgb_out, int fill, uint32_t rgb_fill,
+                             fs_stream stream) {
+    return fs::launch_ground_rectify(inverse, CH, CW, ox, oy, GH, GW, gsd_mm, (long long)e0_mm, (long long)ntop_mm, nplanes, planes, outs, rgba, rgb_out, fill,
+                                     rgb_fill, S(stream));
+}
+static int fs_ground_points(const int32_t* points, int n, const double* forward, int ox, int oy, int64_t* out, fs_stream stream) {
+    return fs::launch_ground_points(points, n, forward, ox, oy, reinterpret_cast<long long*>(out), S(stream));
+}
+
+// the seventeen tables as one object: each table is built from the one before it, so there is one definition of every member list.  The
 // first six are handed out as the fs_hook_tables5 at the head of that object.
 static const fs_hook_tables5& hook_tables(void) {
     // fs_test_api (frozen) with the extension table right behind it: one object, so &tables.test is also &tables
@@ -837,7 +853,16 @@ static const fs_hook_tables5& hook_tables(void) {
         fs_mask_access,
         fs_region_access,
     }};
+    // fs_ext15_api is frozen too (two members, 32 bytes; tests/test_ground_cpu.py); the seventeenth table lies behind it, and &all16.base15 is &all16.
+    static const fs_hook_tables16 all16 = {all15, {
+        FS_EXT16_MAGIC,
+        sizeof(fs_ext16_api),
+        fs_ground_area,
+        fs_ground_rectify,
+        fs_ground_points,
+    }};
     {
+        const fs_hook_tables15& all15 = all16.base15;
         const fs_hook_tables14& all14 = all15.base14;
         const fs_hook_tables13& all13 = all14.base13;
         const fs_hook_tables12& all12 = all13.base12;

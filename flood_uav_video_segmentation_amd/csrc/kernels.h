@@ -482,6 +482,16 @@ int launch_mask_access(const uint8_t* mask, const uint8_t* seeds, int n, int H, 
 int launch_region_access(const uint8_t* mask, const uint32_t* d, const int32_t* origin, const int32_t* index, const long long* counts, int n, int H, int W,
                          int K, int max_regions, long long* reach, long long* rows, hipStream_t s);
 
+// Georeferencing the mosaic (ground_ops.hip, ground_defs.h; definitions: include/floodseg_test.h, ground_area, ground_rectify and
+// ground_points).  The launchers refuse bad arguments, the models' bounds among them, before they launch anything.  forward,
+// inverse = nine doubles in HOST memory, read during the call; planes, outs = HOST arrays of device pointers.  Nothing is allocated,
+// synchronised or read back on the host.  ground_area: two launches; the other two: one.
+int launch_ground_area(const uint8_t* cls, int CH, int CW, int ox, int oy, const double* forward, int K, const int32_t* index, int max_regions,
+                       long long* class_area2, long long* region_area2, long long* counts, hipStream_t s);
+int launch_ground_rectify(const double* inverse, int CH, int CW, int ox, int oy, int GH, int GW, int gsd_mm, long long e0_mm, long long ntop_mm, int nplanes,
+                          const uint8_t* const* planes, uint8_t* const* outs, const uint32_t* rgba, uint8_t* rgb_out, int fill, uint32_t rgb_fill, hipStream_t s);
+int launch_ground_points(const int32_t* points, int n, const double* forward, int ox, int oy, long long* out, hipStream_t s);
+
 // Region outlines (outline_ops.hip, outline_defs.h; definitions: include/floodseg_test.h).  The launcher refuses bad arguments before it
 // launches anything; the workspace is the caller's (FS_REGION_OUTLINES_WORKSPACE_BYTES), nothing is allocated or synchronised.
 int launch_region_outlines(const int* index, int n, int H, int W, int max_regions, int connectivity, int max_contours, int max_vertices,

@@ -1,5 +1,6 @@
-"""The flood-extent mosaic and everything built on it (DESIGN §3.18-3.25): the vote canvas and its pose chain, the orthophoto under it,
-frame-to-map registration, relocalisation, the merge of two mosaics, the change between them and dry-route reachability on one.
+"""The flood-extent mosaic and everything built on it (DESIGN §3.18-3.26): the vote canvas and its pose chain, the orthophoto under it,
+frame-to-map registration, relocalisation, the merge of two mosaics, the change between them, dry-route reachability on one, and one in
+metres: ground areas, map polygons and north-up rasters through a flow.georef.GroundModel.
 MosaicBuilder owns all of it -- the settings, the canvases and the chain's state on the device, the per-frame report rows -- and needs
 no network: only masks and the block matcher's tables.  A mosaic with its orthophoto, every frame registered against the map before it votes:
 
@@ -239,6 +240,10 @@ class MosaicBuilder:
     def access(self, **kw):
         """mosaic_access(self, **kw): dry-route reachability on this mosaic; the mosaic is not changed."""
         return mosaic_access(self, **kw)
+
+    def ground(self, model, **kw):
+        """mosaic_ground(self, model, **kw): this mosaic in metres and as north-up rasters; the mosaic is not changed."""
+        return mosaic_ground(self, model, **kw)
 
     def merge_report(self):
         """(links int64 numpy [parts, 16], per part the out rows [rows, 8], counts [parts, 8]) of the parts merged.  The ONE read-back."""
@@ -719,6 +724,195 @@ def write_access_geojson(path, report):
                                  geometry=dict(type="LineString", coordinates=[[px + 0.5, py + 0.5] for px, py in chain])))
     with open(path, "w") as f:
         json.dump(dict(type="FeatureCollection", features=features), f)
+
+
+# ---- the mosaic in metres
+_GROUND_KEYS = {"max_regions", "connectivity", "max_contours", "max_vertices", "simplify_rounds", "fill", "rgb_fill", "raster"}
+
+
+def mosaic_ground(part_or_builder, model, gsd=None, regions=False, outlines=False, simplify=None, min_votes=1, change=None, **options):
+    """The mosaic in map coordinates (DESIGN §3.26).  part_or_builder: a MosaicBuilder or a part (part()'s or read_mosaic_part()'s dict);
+    model: a flow.georef.GroundModel fitted in THIS canvas (GroundModel.fit(..., origin=part["origin"])).  The id plane is
+    ops.mosaic_resolve's class plane (255 where a pixel has fewer than min_votes votes), or, with change = mosaic_change()'s result in this
+    part's canvas, its change plane with the six ids of ops.CHANGE_CODES: gained and lost water in m^2.  Then ops.ground_area; with
+    regions=True ops.mask_regions and ops.region_table on the plane (max_regions, connectivity) and the areas per region; with
+    outlines=True ops.region_outlines (max_contours, max_vertices), simplify=TOL ops.outline_simplify (simplify_rounds), and
+    ops.ground_points on the vertices; and ops.ground_rectify of the plane, the confidence plane and, where the part has one, the
+    orthophoto, onto the north-up raster model.raster() gives for gsd metres (default: the model's mean pixel size, rounded to
+    millimetres; raster=False: no raster).  fill and rgb_fill go to ops.ground_rectify.  -> a dict of device tensors and plain numbers;
+    enqueues only, ground_report() reads back.  A planar model over an affine pose chain: the chain's drift and parallax are in the
+    result; no DEM, no lens model; not validated on real video or against surveyed points."""
+    unknown = set(options) - _GROUND_KEYS
+    if unknown:
+        raise ValueError(f"mosaic_ground: unknown options {sorted(unknown)}")
+    if not (hasattr(model, "forward") and hasattr(model, "inverse") and hasattr(model, "raster")):
+        raise ValueError(f"mosaic_ground: model must be a flow.georef.GroundModel, got {model!r}")
+    part = part_or_builder.part() if hasattr(part_or_builder, "part") else part_or_builder
+    if not 1 <= int(min_votes) <= 65535:
+        raise ValueError(f"mosaic_ground: min_votes must be 1..65535, got {min_votes}")
+    if (outlines or simplify is not None) and not regions:
+        raise ValueError("mosaic_ground: outlines and simplify go with regions=True")
+    if simplify is not None and not outlines:
+        raise ValueError("mosaic_ground: simplify= goes with outlines=True")
+    if gsd is not None and not (float(gsd) * 1000.0 >= 1.0 and round(float(gsd) * 1000.0) <= ops.GROUND_MAX_GSD_MM):
+        raise ValueError(f"mosaic_ground: gsd must be 0.001 .. {ops.GROUND_MAX_GSD_MM / 1000.0} metres, got {gsd}")
+    votes, origin = part["votes"], tuple(int(v) for v in part["origin"])
+    size = tuple(int(v) for v in votes.shape[1:])
+    cls, conf, seen, _ = ops.mosaic_resolve(votes)
+    if int(min_votes) > 1:
+        cls = torch.where(seen >= int(min_votes), cls, torch.full_like(cls, 255))
+    plane, k = cls, int(votes.shape[0])
+    if change is not None:
+        plane, k = change["change"], ops.CHANGE_CLASSES
+        if tuple(plane.shape) != size:
+            raise ValueError(f"mosaic_ground: the change plane {tuple(plane.shape)} is not of this mosaic's canvas {size} (mosaic A's is the one it is made in)")
+    result = dict(model=model, origin=origin, size=size, classes=k, plane=plane, conf=conf, changed=change is not None, regions=None, outlines=None,
+                  simplified=None, tolerance=simplify, points=None, simple_points=None, raster=None)
+    index, cap = None, 0
+    if regions:
+        cap, conn = int(options.get("max_regions", 1024)), int(options.get("connectivity", 8))
+        labels = ops.mask_regions(plane[None], k, conn)
+        table, region_counts, index = ops.region_table(plane[None], labels, k, None, 128, cap)
+        result["regions"] = (table, region_counts, index)
+        if outlines:
+            result["outlines"] = ops.region_outlines(index, cap, conn, int(options.get("max_contours", 4096)), int(options.get("max_vertices", 32768)))
+            contours, vertices, _, outline_counts = result["outlines"]
+            result["points"] = ops.ground_points(vertices[0], model, origin)
+            if simplify is not None:
+                result["simplified"] = ops.outline_simplify(contours, vertices, outline_counts, simplify, int(options.get("simplify_rounds", 32)))
+                result["simple_points"] = ops.ground_points(result["simplified"][1][0], model, origin)
+    result["class_area2"], result["region_area2"], result["counts"] = ops.ground_area(plane, model, origin, k, None if index is None else index[0], cap)
+    if options.get("raster", True):
+        raster_size, gsd_mm, top_left = model.raster(size, origin, None if gsd is None else int(round(float(gsd) * 1000.0)))
+        planes, rgb = ops.ground_rectify(model, origin, raster_size, gsd_mm, top_left, (plane, conf), part.get("rgba"), int(options.get("fill", 255)),
+                                         tuple(options.get("rgb_fill", (0, 0, 0))))
+        result["raster"] = dict(size=raster_size, gsd_mm=gsd_mm, top_left_mm=top_left, plane=planes[0], conf=planes[1], rgb=rgb)
+    return result
+
+
+def ground_report(result):
+    """mosaic_ground()'s result on the host -- the ONE place that reads back.  -> a dict: classes = one row per id (id, pixels' area in
+    m^2, share of the summed area); summed_m2; counts = ops.ground_area's (pixels summed, folded, ids beyond the classes, 0); regions =
+    one row per region (row, id, pixels, m^2, centroid E, centroid N) or None -- the centroid is region_table's pixel centroid taken
+    through the model; rings = {region row: [ring, ...]} of (E, N) metres, the outer ring first, each closed, simplified ones where
+    simplify was given (None without outlines; `flags` = region_outlines' for the frame); raster = dict(plane, conf, rgb (numpy),
+    gsd_mm, top_left_mm, world = the world file's six numbers) or None; model, rms, residuals (the fit's, metres), crs."""
+    host = lambda t: t.cpu().numpy()  # noqa: E731
+    model = result["model"]
+    class_area2, counts = host(result["class_area2"]), host(result["counts"])
+    total = int(class_area2.sum())
+    report = dict(model=model, rms=model.rms, residuals=model.residuals, crs=model.crs, counts=counts, changed=result["changed"],
+                  classes=[(k, a / 2e6, (a / total if total else 0.0)) for k, a in enumerate(class_area2.tolist())], summed_m2=total / 2e6, regions=None,
+                  rings=None, flags=0, tolerance=result["tolerance"], raster=None)
+    if result["regions"] is not None:
+        table, region_counts, _ = result["regions"]
+        written = int(host(region_counts)[0, 1])
+        rows, area2 = host(table)[0, :written], host(result["region_area2"])[:written]
+        centre = np.array([[t[6] / t[1] + 0.5, t[7] / t[1] + 0.5] for t in rows.tolist()], np.float64).reshape(-1, 2)   # continuous canvas coordinates
+        en =model.to_ground(centre, result["origin"])
+        report["regions"] = [(r, int(t[0]), int(t[1]), int(a) / 2e6, float(c[0]), float(c[1])) for r, (t, a, c) in enumerate(zip(rows.tolist(), area2.tolist(), en))]
+        if result["outlines"] is not None:
+            contours, _, _, c = (host(t) for t in result["outlines"])
+            report["flags"] = int(c[0, 3])
+            rings = {}
+            if not int(c[0, 3]) & 1:
+                rows6 = contours[0, :int(c[0, 1])].tolist()
+                if result["simplified"] is not None:
+                    simple, _, sc = (host(t) for t in result["simplified"])
+                    spans = [(s[0], s[1]) for s in simple[0, :int(sc[0, 0])].tolist()]
+                    mm = host(result["simple_points"])
+                else:
+                    spans = [(row[1], row[2]) for row in rows6]
+                    mm = host(result["points"])
+                for row, (first, count) in zip(rows6, spans):
+                    ring = model.mm_to_en(mm[first:first + count]).tolist()
+                    if not ring:
+                        continue
+                    ring.append(ring[0])
+                    if row[4] > 0:
+                        rings.setdefault(row[0], []).insert(0, ring)
+                    else:
+                        rings.setdefault(row[0], []).append(ring)
+            report["rings"] = rings
+    if result["raster"] is not None:
+        r = result["raster"]
+        report["raster"] = dict(plane=host(r["plane"]), conf=host(r["conf"]), rgb=None if r["rgb"] is None else host(r["rgb"]), gsd_mm=r["gsd_mm"],
+                                top_left_mm=r["top_left_mm"], world=model.world_file(r["gsd_mm"], r["top_left_mm"]))
+    return report
+
+
+def write_ground_csv(path, report, class_names=None):
+    """ground_report() as one CSV of up to three tables: one row per id (its name, m^2, hectares, share of the summed area); after an
+    empty line the fit (kind, control points, RMS and largest residual in metres, CRS, folded pixels); and, with regions, one row per
+    region (row, id, pixels, m^2, centroid easting and northing in metres)."""
+    codes = ops.CHANGE_CODES if report["changed"] else class_names
+    name = (lambda c: str(c)) if codes is None else (lambda c: str(codes[c]) if c < len(codes) else str(c))
+    model = report["model"]
+    worst = float(np.sqrt((model.residuals ** 2).sum(axis=1)).max()) if len(model.residuals) else 0.0
+    with open(path, "w", newline="") as f:
+        f.write("class,area_m2,hectares,share\n")
+        for k, m2, share in report["classes"]:
+            f.write(f"{name(k)},{m2:.6f},{m2 / 1e4:.6f},{share:.6f}\n")
+        f.write("\nkind,points,rms_m,max_residual_m,crs,folded_pixels\n")
+        f.write(f"{model.kind},{len(model.residuals)},{model.rms:.6f},{worst:.6f},{model.crs or ''},{int(report['counts'][1])}\n")
+        if report["regions"] is not None:
+            f.write("\nregion,class,pixels,area_m2,centroid_e,centroid_n\n")
+            for r, k, pixels, m2, e, n in report["regions"]:
+                f.write(f"{r},{name(k)},{pixels},{m2:.6f},{e:.3f},{n:.3f}\n")
+
+
+def ground_image(report, what="class", palette=ops.FLOOD_PALETTE, fill=(0, 0, 0)):
+    """The rectified raster as a picture, uint8 numpy [GH, GW, 3]: what = "class" (the id plane through the palette; CHANGE_PALETTE's
+    colours for a change plane), "ortho" (the rectified orthophoto) or "conf" (the confidence plane as grey)."""
+    r = report["raster"]
+    if r is None:
+        raise ValueError("ground_image: the result has no raster (mosaic_ground(raster=True))")
+    if what == "ortho":
+        if r["rgb"] is None:
+            raise ValueError("ground_image: the mosaic has no orthophoto (a builder made with ortho=)")
+        return r["rgb"]
+    if what == "conf":
+        return np.repeat(r["conf"][..., None], 3, axis=2)
+    if what != "class":
+        raise ValueError(f"ground_image: what must be class, ortho or conf, got {what!r}")
+    colours = np.array([fill] * 256, np.uint8)
+    table = CHANGE_PALETTE[:, :3] if report["changed"] else np.array(palette, np.uint8)
+    colours[:len(table)] = table
+    return colours[r["plane"]]
+
+
+def write_ground_png(path, report, what="class", **kw):
+    """ground_image() as a PNG with its world file beside it (the PNG's name with the extension .pgw): six lines -- gsd, 0, 0, -gsd, and
+    the easting and northing of the top-left pixel's CENTRE -- in metres."""
+    from PIL import Image
+
+    Image.fromarray(ground_image(report, what, **kw)).save(path)
+    stem = path[:-4] if path.lower().endswith(".png") else path
+    with open(stem + ".pgw", "w") as f:
+        f.write("".join(f"{v!r}\n" for v in report["raster"]["world"]))
+
+
+def write_ground_geojson(path, report, class_names=None):
+    """The regions as one GeoJSON FeatureCollection in map coordinates: one Polygon per region with an outer ring, the outer ring first,
+    then its holes, in eastings and northings (metres); properties region, class, pixels, area_m2; the model's CRS name in a `crs`
+    member (the pre-2016 GeoJSON form, which GIS software still reads), left out without a name."""
+    import json
+
+    if report["rings"] is None:
+        raise ValueError("write_ground_geojson: the result has no outlines (mosaic_ground(regions=True, outlines=True))")
+    codes = ops.CHANGE_CODES if report["changed"] else class_names
+    features = []
+    for r, k, pixels, m2, e, n in report["regions"]:
+        if r in report["rings"]:
+            props = {"region": r, "class": k if codes is None or k >= len(codes) else str(codes[k]), "pixels": pixels, "area_m2": m2, "centroid": [e, n]}
+            features.append(dict(type="Feature", properties=props, geometry=dict(type="Polygon", coordinates=report["rings"][r])))
+    doc = dict(type="FeatureCollection", features=features)
+    if report["crs"]:
+        doc["crs"] = dict(type="name", properties=dict(name=report["crs"]))
+    if report["tolerance"] is not None:
+        doc["tolerance"] = report["tolerance"]
+    with open(path, "w") as f:
+        json.dump(doc, f)
 
 
 def write_mosaic_csv(path, frame_ids, poses, totals, refine=None):

@@ -1755,6 +1755,138 @@ def mosaic_change(votes_a, origin_a, votes_b, origin_b, link, min_votes=1, min_c
     return change, cls_a, cls_b, transitions, counts
 
 
+# ------------------------------------------------------------------------------------------ georeferencing the mosaic
+GROUND_MAX_PLANES = 8  # FS_GROUND_MAX_PLANES
+GROUND_NO_POINT = -2 ** 63  # FS_GROUND_NO_POINT
+GROUND_MAX_GSD_MM = 1 << 20
+
+
+def ground_model_rows(model, what="floodseg.ground_area"):
+    """A ground model -> (forward, inverse), two lists of nine finite floats: an object with .forward and .inverse (flow.georef.GroundModel)
+    or a pair of sequences.  forward: anchor pixel coordinates to millimetres about the model's ground origin; inverse: back."""
+    pair = (model.forward, model.inverse) if hasattr(model, "forward") and hasattr(model, "inverse") else model
+    try:
+        rows = [[float(v) for v in (m.reshape(-1).tolist() if hasattr(m, "reshape") else list(m))] for m in pair]
+    except (TypeError, ValueError):
+        rows = None
+    if rows is None or len(rows) != 2 or any(len(r) != 9 for r in rows):
+        raise ValueError(f"{what}: model must hold a forward and an inverse model of nine float64 each, got {model!r}")
+    for name, r in zip(("forward", "inverse"), rows):
+        if any(v != v or v in (float("inf"), float("-inf")) for v in r):
+            raise ValueError(f"{what}: the {name} model holds a value that is not finite: {r}")
+    return rows
+
+
+def _ground_plane(t, name, what, shape=None):
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{what}: {name} must be a uint8 [CH,CW] tensor{'' if shape is None else ' of the canvas ' + str(list(shape))}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    _mosaic_size(t.shape, name, what)
+    return t.contiguous()
+
+
+def ground_area(cls, model, origin, classes, index=None, max_regions=0):
+    """Hectares instead of pixels (definition: include/floodseg_test.h, ground_area): cls uint8 [CH,CW] (mosaic_resolve's
+    class plane, or mosaic_change's change plane with classes=6; 255 = unseen) -> (class_area2 int64 [classes], region_area2 int64
+    [max_regions], counts int64 [4]).  Every canvas pixel's four lattice corners go through the model's corner rule to int64 millimetres
+    and the pixel's area2 is their shoelace sum, twice its area in mm^2, oriented positive; adjacent pixels share corners, so the sums
+    are exact.  index: region_table's int32 index plane of this canvas ([CH,CW] or [1,CH,CW]) with max_regions >= 1.  counts = (pixels
+    summed, folded pixels, pixels with classes <= id < 255, 0).  origin = (oy, ox).  The model's bounds are the library's to refuse
+    (RuntimeError naming the model).  Two launches; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.ground_area"
+    cls = _ground_plane(cls, "cls", what)
+    ch, cw = cls.shape
+    forward, _ = ground_model_rows(model, what)
+    oy, ox = _mosaic_origin(origin, what)
+    k, cap = int(classes), int(max_regions)
+    if not 1 <= k <= 255:
+        raise ValueError(f"{what}: classes must be 1..255, got {classes}")
+    if not 0 <= cap <= 65536:
+        raise ValueError(f"{what}: max_regions must be 0..65536, got {max_regions}")
+    if (index is None) != (cap == 0):
+        raise ValueError(f"{what}: index goes with max_regions >= 1 and only with it, got max_regions={max_regions} and index "
+                         f"{'None' if index is None else 'given'}")
+    if index is not None:
+        if index.dtype != torch.int32 or index.numel() != ch * cw or tuple(index.shape[-2:]) != (ch, cw):
+            raise ValueError(f"{what}: index must be int32 [{ch},{cw}] (region_table's of this canvas), got {index.dtype} {tuple(index.shape)}")
+        index = index.contiguous()
+    dev = one_device(cls, index, what=what)
+    host = (ctypes.c_double * 9)(*forward)  # read by the library during the call
+    with torch.cuda.device(dev):
+        class_area2 = torch.empty((k,), dtype=torch.int64, device=dev)
+        region_area2 = torch.empty((cap,), dtype=torch.int64, device=dev)
+        counts = torch.empty((4,), dtype=torch.int64, device=dev)
+        check(lib.fs_ground_area(ptr(cls), ch, cw, ox, oy, ctypes.cast(host, ctypes.c_void_p), k, ptr(index), cap, ptr(class_area2),
+                                 ptr(region_area2 if cap else None), ptr(counts), stream_ptr()))
+    return class_area2, region_area2, counts
+
+
+def ground_rectify(model, origin, raster_size, gsd_mm, top_left_mm, planes=(), rgba=None, fill=255, rgb_fill=(0, 0, 0)):
+    """North-up rasters of canvas planes (definition: include/floodseg_test.h, ground_rectify) -> (rasters, rgb): a list of
+    uint8 [GH,GW] tensors, one per uint8 [CH,CW] plane of `planes` (class, confidence, change, any id plane; nearest sampling, `fill`
+    outside the canvas), and uint8 [GH,GW,3] from the orthophoto's int32 rgba plane (Q8 bilinear over seen taps, the nearest tap beside
+    unseen ground, rgb_fill where that is unseen too), None without rgba.  raster_size = (GH, GW); gsd_mm: the raster pixel's side in whole
+    millimetres, 1..2^20; top_left_mm = (E, N) of the raster's top-left CORNER in whole millimetres about the model's ground origin.
+    Raster pixel (u, v) samples the ground point (E + (u + 0.5) gsd, N - (v + 0.5) gsd) through the model's inverse.  origin = (oy, ox).
+    One launch for all planes; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.ground_rectify"
+    _, inverse = ground_model_rows(model, what)
+    oy, ox = _mosaic_origin(origin, what)
+    gh, gw = _mosaic_size(raster_size, "raster_size", what)
+    if int(gsd_mm) != gsd_mm or not 1 <= int(gsd_mm) <= GROUND_MAX_GSD_MM:
+        raise ValueError(f"{what}: gsd_mm must be a whole number 1..{GROUND_MAX_GSD_MM}, got {gsd_mm}")
+    e0, ntop = top_left_mm
+    if int(e0) != e0 or int(ntop) != ntop or abs(int(e0)) >= 2 ** 40 or abs(int(ntop)) >= 2 ** 40:
+        raise ValueError(f"{what}: top_left_mm must be (E, N) in whole millimetres within 2^40 of the ground origin, got {tuple(top_left_mm)}")
+    planes = list(planes)
+    if len(planes) > GROUND_MAX_PLANES or (not planes and rgba is None):
+        raise ValueError(f"{what}: 0..{GROUND_MAX_PLANES} planes and at least one plane or rgba, got {len(planes)} planes and rgba "
+                         f"{'None' if rgba is None else 'given'}")
+    shape = tuple(rgba.shape) if rgba is not None else tuple(planes[0].shape) if torch.is_tensor(planes[0]) else None
+    if rgba is not None:
+        _ortho_planes(None, rgba, what)
+    planes = [_ground_plane(p, f"plane {i}", what, shape) for i, p in enumerate(planes)]
+    ch, cw = shape
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"{what}: fill must be 0..255, got {fill}")
+    if len(tuple(rgb_fill)) != 3 or any(not 0 <= int(c) <= 255 for c in rgb_fill):
+        raise ValueError(f"{what}: rgb_fill must be (r, g, b) with 0..255 each, got {tuple(rgb_fill)}")
+    word = int(rgb_fill[0]) | int(rgb_fill[1]) << 8 | int(rgb_fill[2]) << 16
+    dev = one_device(*planes, rgba, what=what)
+    host = (ctypes.c_double * 9)(*inverse)  # read by the library during the call, as the two pointer arrays
+    with torch.cuda.device(dev):
+        outs = [torch.empty((gh, gw), dtype=torch.uint8, device=dev) for _ in planes]
+        rgb = torch.empty((gh, gw, 3), dtype=torch.uint8, device=dev) if rgba is not None else None
+        ins = (ctypes.c_void_p * max(len(planes), 1))(*[p.data_ptr() for p in planes])
+        dst = (ctypes.c_void_p * max(len(planes), 1))(*[o.data_ptr() for o in outs])
+        check(lib.fs_ground_rectify(ctypes.cast(host, ctypes.c_void_p), ch, cw, ox, oy, gh, gw, int(gsd_mm), int(e0), int(ntop), len(planes),
+                                    ctypes.cast(ins, ctypes.c_void_p), ctypes.cast(dst, ctypes.c_void_p), ptr(rgba), ptr(rgb), int(fill), word, stream_ptr()))
+    return outs, rgb
+
+
+def ground_points(points, model, origin):
+    """Canvas lattice points in map coordinates (definition: include/floodseg_test.h, ground_points): points int32 [n,2] =
+    (x, y), pixel corners as region_outlines and outline_simplify write their vertices -> int64 [n,2] = (E, N) millimetres about the
+    model's ground origin, by ground_area's corner rule: a polygon's shoelace over them equals ground_area's sum over its pixels.  A
+    point the model cannot place gets GROUND_NO_POINT twice.  origin = (oy, ox).  One launch; nothing is read back."""
+    lib = _lib.load()
+    what = "floodseg.ground_points"
+    if not torch.is_tensor(points) or points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 2 or points.shape[0] > 2 ** 28:
+        raise ValueError(f"{what}: points must be int32 [n,2] with n <= 2^28, got {getattr(points, 'dtype', type(points))} {tuple(getattr(points, 'shape', ()))}")
+    forward, _ = ground_model_rows(model, what)
+    oy, ox = _mosaic_origin(origin, what)
+    dev = one_device(points, what=what)
+    n = int(points.shape[0])
+    host = (ctypes.c_double * 9)(*forward)  # read by the library during the call
+    with torch.cuda.device(dev):
+        out = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        if n:
+            check(lib.fs_ground_points(ptr(points.contiguous()), n, ctypes.cast(host, ctypes.c_void_p), ox, oy, ptr(out), stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ region outlines
 def region_outlines_workspace_bytes(n, h, w, max_regions, max_contours, max_vertices):
     """FS_REGION_OUTLINES_WORKSPACE_BYTES of include/floodseg_test.h."""

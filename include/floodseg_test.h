@@ -1539,6 +1539,82 @@ typedef struct fs_hook_tables15 {
     fs_ext15_api ext15;
 } fs_hook_tables15;
 
+/* ---- The SEVENTEENTH table.  fs_ext15_api is frozen as well (2 members, 32 bytes; tests/test_ground_cpu.py), so ops added since live in
+ * a table of their own, append-only, that the library places directly behind fs_hook_tables15 by the same pattern:
+ *     const fs_hook_tables16* t = (const fs_hook_tables16*)fs_test_hooks();   t->ext16.ground_area(...)
+ * A library built before this table existed has nothing behind its fs_hook_tables15: a caller that may meet one checks the older
+ * tables' magics and sizes first, then t->ext16.magic == FS_EXT16_MAGIC and ext16.size >= the end of the member it needs. */
+#define FS_EXT16_MAGIC 0x4653455854413136ull /* "FSEXTA16" */
+#define FS_GROUND_MAX_PLANES 8               /* uint8 planes of one ground_rectify call */
+#define FS_GROUND_NO_POINT INT64_MIN         /* ground_points: both words of a point the model cannot place */
+
+typedef struct fs_ext16_api {
+    uint64_t magic; /* FS_EXT16_MAGIC */
+    size_t size;    /* sizeof(fs_ext16_api) of the library that was built */
+
+    /* ---- GEOREFERENCING: GROUND AREAS (csrc/ground_ops.hip, csrc/ground_defs.h).  OUR DEFINITION: the reference has nothing
+     * like it.  The same rules as code: csrc/ground_defs.h (host and device) and tests/ground_ref.py (vectorised numpy and literal loops).
+     * A MODEL is nine float64 (a0 a1 a2 b0 b1 b2 c0 c1 c2) in HOST memory, read during the call.  The FORWARD model takes anchor pixel
+     * coordinates (i, j) -- canvas lattice point (X, Y) is i = X - ox, j = Y - oy; canvas pixel (X, Y) covers [X, X+1) x [Y, Y+1) -- to
+     * millimetres east and north of a ground origin that only the host knows.
+     * THE CORNER of lattice point (i, j), all in float64, one operation per statement, no contraction:
+     *     ne = (a0*i + a1*j) + a2;  nn = (b0*i + b1*j) + b2;  d = (c0*i + c1*j) + c2;  E = (int64) floor(ne / d + 0.5), N likewise.
+     * THE AREA of canvas pixel (X, Y): area2 = the shoelace sum of its corners (X,Y), (X+1,Y), (X+1,Y+1), (X,Y+1) about the first, in
+     * int64: twice the signed area in mm^2; times the model's ORIENTATION, the sign of det(model) (-1 with north up), it is positive;
+     * a pixel whose oriented area2 is <= 0 is FOLDED: counted, not summed.  Adjacent pixels share corners, so the areas of any set of
+     * pixels sum exactly to the shoelace of the set's boundary.
+     * Inputs:  cls uint8 [CH][CW] (mosaic_resolve's class plane, mosaic_change's change plane, any id plane; 255 = unseen: skipped);
+     *          K classes 1..255;  index int32 [CH][CW] (region_table's, of one frame) with max_regions 1..65536, or NULL with 0.
+     * Outputs, cleared on the stream by a kernel and written whole by every call:
+     *   class_area2   int64 [K]: the sum of the oriented area2 over the pixels of class k that are not folded;
+     *   region_area2  int64 [max_regions] (NULL with max_regions 0): the same over the summed pixels whose index is r;
+     *   counts        int64 [4] = (pixels summed, folded pixels of an id < K, pixels with K <= id < 255, 0).
+     * LAUNCHES.  Two: clear; one workgroup of 256 per 64 x 16 canvas tile.  It reads its bytes and returns if all are 255; otherwise it
+     * projects its 65 x 17 corners once into LDS, sums classes through an int64 LDS histogram flushed with one 64-bit atomic per
+     * non-zero cell, and merges the region sums per run of equal rows in the wave.  Integer sums: the order does not matter.
+     * THE BOUNDS (ground_defs.h derives why no product and no sum leaves 63 bits).  Refused before a launch, naming the model: a value
+     * that is not finite; det(model) = 0; the denominator not positive at each of the four canvas corners; the largest corner
+     * denominator more than 4 times the smallest; |E| or |N| >= 2^31 - 1 mm at a canvas corner; one pixel's corner differences that may
+     * reach 2^30 (bounded through (|a| + the largest corner |E| times |c|) / the smallest denominator); a corner quadrilateral of 2^61 mm^2 or more.  Also refused:
+     * a null cls, forward, class_area2 or counts; CH or CW outside 1..16384; |ox| or |oy| > 16384; K or max_regions out of range; index
+     * or region_area2 without max_regions >= 1 or the reverse; index not aligned to 4 bytes, an output not to 8. */
+    int (*ground_area)(const uint8_t* cls, int CH, int CW, int ox, int oy, const double* forward, int K, const int32_t* index, int max_regions,
+                       int64_t* class_area2, int64_t* region_area2, int64_t* counts, fs_stream stream);
+
+    /* ---- GEOREFERENCING: NORTH-UP RASTERS (csrc/ground_ops.hip).  OUR DEFINITION.  Raster pixel (u, v) of a GH x GW raster
+     * with integer gsd_mm whose top-left ground CORNER is (e0_mm, ntop_mm), through the INVERSE model (millimetres to anchor coordinates):
+     *     Eg = e0 + (u + 0.5) * gsd;  Ng = ntop - (v + 0.5) * gsd;  x, y = the three sums and two divisions of the corner rule.
+     * A pixel with |x| or |y| >= 2^20 (or not a number) takes the fills.  uint8 planes, NEAREST: canvas X = floor(x) + ox, Y = floor(y) + oy;
+     * outside the canvas: `fill`.  COLOUR from the orthophoto's rgba plane (r | g << 8 | b << 16 | a << 24, a = 0: unseen): taps at
+     * floor(x - 0.5), floor(y - 0.5) and one further; Q8 weights w = floor(frac * 256); per channel (sum of w * c + 32768) >> 16; a tap
+     * that is unseen or off the canvas makes the pixel take the nearest tap (floor(x), floor(y)); an unseen nearest tap gives rgb_fill.
+     * Inputs:  nplanes 0..FS_GROUND_MAX_PLANES; planes, outs = HOST arrays of nplanes device pointers, uint8 [CH][CW] and [GH][GW];
+     *          rgba uint32 [CH][CW] with rgb_out uint8 [GH][GW][3], or both NULL; fill 0..255; rgb_fill = r | g << 8 | b << 16.
+     * LAUNCHES.  One: a workgroup of 256 per 64 x 16 raster tile, one owner per raster pixel, no atomics, all planes at once.  A tile whose
+     * four lattice corners map beyond the SAME side of the canvas box grown by one pixel writes the fills and returns: with a positive
+     * denominator the tile lies in the hull of those four points.
+     * Refused before a launch, naming the value: an inverse value that is not finite; the denominator not positive at the four raster
+     * corners, or their ratio above 4; CH, CW, GH or GW outside 1..16384; |ox| or |oy| > 16384; gsd_mm outside 1..2^20; e0_mm or ntop_mm
+     * 2^40 or more from the origin; nplanes out of range; a null plane; rgba without rgb_out or the reverse; neither a plane nor rgba;
+     * fill or rgb_fill out of range; rgba not aligned to 4 bytes. */
+    int (*ground_rectify)(const double* inverse, int CH, int CW, int ox, int oy, int GH, int GW, int gsd_mm, int64_t e0_mm, int64_t ntop_mm, int nplanes,
+                          const uint8_t* const* planes, uint8_t* const* outs, const uint32_t* rgba, uint8_t* rgb_out, int fill, uint32_t rgb_fill,
+                          fs_stream stream);
+
+    /* ---- GEOREFERENCING: POINTS (csrc/ground_ops.hip).  points int32 [n][2] = (x, y) canvas lattice points (the vertices of
+     * region_outlines and outline_simplify, pixel corners) -> out int64 [n][2] = (E, N) millimetres: THE CORNER of ground_area, the same
+     * function, so a polygon's shoelace over these points equals ground_area's sum of its pixels.  A point with |x| or |y| > 2^20, a
+     * denominator that is not positive there or a result of 2^53 or more gets FS_GROUND_NO_POINT in both words.  One launch.
+     * Refused: a null pointer; n outside 1..2^28; |ox| or |oy| > 16384; a model value that is not finite or det = 0; points not aligned
+     * to 4 bytes, out not to 8. */
+    int (*ground_points)(const int32_t* points, int n, const double* forward, int ox, int oy, int64_t* out, fs_stream stream);
+} fs_ext16_api;
+
+typedef struct fs_hook_tables16 {
+    fs_hook_tables15 base15;
+    fs_ext16_api ext16;
+} fs_hook_tables16;
+
 const fs_test_api* fs_test_hooks(void);
 
 #ifdef __cplusplus
